@@ -3,6 +3,16 @@
 bench.py — reads classified/sec on the Deepbinner classify hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {1,2,3}] [--steps-per-launch S]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (with `roofline`, whose launch
+times are taken inside the timed region).  `--full` adds what takes runs of its own (N = 1): the
+kernel's phase probe (one more launch), the side rates of --config 1, `cpu_baseline` and
+`other_configs`.  `--dump-outputs DIR` writes what the timed path computed in its last step:
+DIR/calls.npy (the gathered per-read calls) and DIR/probs_<model>.npy (the probabilities of the
+reads on this process's devices), float32; above 64 MB in all, the same seeded sample of reads of
+every array, and DIR/read_index.npy (float64) says which.  The inputs are seeded: the same
+arguments give the same inputs.
 
 --config 1 (default; the configuration the metric is quoted on): BASELINE.json configs[1],
     EXP-NBD103_read_starts, 10,000 synthetic 1024-sample int16 signals per GPU, batch 256.
@@ -25,9 +35,9 @@ to its 256 workgroups off a counter; 10,000 windows are 39.06 rounds, so a launc
 configs[1] step ends with 2.3 % of the GPU idle - a boundary effect of the launch, not of the
 kernel (configs[2] / [3], whose steps are 100,000 / 1,000,000 windows, do not see it).  Default:
 10 for --config 1 (cut down to a divisor of --steps), 1 otherwise; `--steps-per-launch 1` is the
-one-launch-per-step form of rounds 1-4 (`value_one_launch_per_step` in the line is its rate).  With
-N > 1 the same switch separates what a straggling rank costs from what the collective costs: the
-exchange is paid once per S steps.
+one-launch-per-step form of rounds 1-4 (`value_one_launch_per_step` in the --full line is its
+rate).  With N > 1 the same switch separates what a straggling rank costs from what the collective
+costs: the exchange is paid once per S steps.
 
 N > 1 runs either way, with no torch anywhere:
   * `python bench.py --gpus N`: ONE process drives the N devices (a thread per device,
@@ -45,8 +55,8 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 than the direct convolutions) = how busy the matrix pipe is, <= 1;
                 `frac_algorithmic_equivalent` counts the direct convolutions' FLOP instead;
   cpu_baseline  the oracle's C restatement (oracle/dbref.c, OpenMP) on a bounded sample of the same
-                reads on this box's host cores (N = 1 only): best of 3 with one thread per usable
-                CPU (cgroup quota), and with the reference's default of 12 threads.
+                reads on this box's host cores (--full, N = 1 only): best of 3 with one thread per
+                usable CPU (cgroup quota), and with the reference's default of 12 threads.
 """
 
 import argparse
@@ -258,6 +268,13 @@ class ShardJob:
         done = [a.elapsed_ms(b) for a, b in (self.timed or [])]
         return sum(done) / len(done) if done else None
 
+    def last_step_probs(self):
+        """Every model's probabilities of this device's reads in the last step queued (the last
+        of a launch's `steps_per_launch` copies)."""
+        return [buf.download((self.n, m.n_classes), np.float32,
+                             self.shard.stream.ptr)[self.n - self.n_step:]
+                for m, buf in zip(self.models, self.probs)]
+
     def _classify(self, final):
         s, cfg = self.shard, self.cfg
         if not self.side_calls:
@@ -297,6 +314,28 @@ class PinnedCalls:
     def array(self):
         return np.ctypeslib.as_array(ctypes.cast(self.ptr, ctypes.POINTER(ctypes.c_int32)),
                                      shape=(self.count,)).copy()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261016
+
+
+def dump_outputs(directory, arrays):
+    """arrays: {name: per-read array (first axis = reads, all starting at read 0)} ->
+    DIR/<name>.npy in float32; above DUMP_LIMIT_BYTES a fixed seeded sample of the reads, the same
+    for every array (an array of fewer reads keeps the sampled reads it has), whose indices go to
+    DIR/read_index.npy."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    rows = max(len(v) for v in arrays.values())
+    per_row = sum(v[:1].nbytes for v in arrays.values())
+    if rows * per_row > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (per_row + 8)
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, keep, replace=False))
+        arrays = {k: v[index[index < len(v)]] for k, v in arrays.items()}
+        arrays['read_index'] = index.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, value in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), value)
 
 
 def cpu_baseline(cfg, weights, reads, gpu_calls, gpu_probs):
@@ -454,8 +493,8 @@ def side_rates(weights, reads):
 
 
 def other_configs():
-    """The other BASELINE.json configurations on this one GPU, inside the default run's budget, so that
-    every configuration has a figure the driver observed (N = 1, --config 1 only):
+    """The other BASELINE.json configurations on this one GPU, so that every configuration has a
+    figure the driver observed (--full, N = 1, --config 1 only):
       "2", "3": this script again as a child (`--config K --steps 3 --warmup 1`, no CPU leg): reads/s and
                 roofline.frac of its line;
       "4":     the realtime stream over multi-read containers written on the spot by this package's
@@ -608,7 +647,15 @@ def main():
                     help='skip the short runs of configs[2], [3] and [4] beside --config 1 (other_configs)')
     ap.add_argument('--no-kernel-timing', action='store_true',
                     help='experiment: skip the per-launch HIP events (roofline object omitted)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own (N = 1): the phase probe, the '
+                         'side rates, cpu_baseline and other_configs (the --no-* switches above '
+                         'leave parts out)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s calls and probabilities to DIR/*.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     cfg = CONFIGS[args.config]
 
     rank, local_rank, env_size = sharding.env_world()
@@ -761,6 +808,18 @@ def main():
     barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if args.dump_outputs and is_lead:
+        # the last timed step, before anything else runs: its gathered calls (every device's
+        # block holds steps_per_launch passes; the last pass is the last step) and the
+        # probabilities of this process's devices, model by model
+        snapshot = pinned.array()
+        outputs = {'calls': np.concatenate(
+            [snapshot[r * launch_block + (spl - 1) * shard_sizes[r]:
+                      r * launch_block + spl * shard_sizes[r]] for r in range(world)])}
+        device_probs = run_all(lambda j: j.last_step_probs())
+        for k, name in enumerate(cfg['models']):
+            outputs['probs_' + name] = np.concatenate([d[k] for d in device_probs])
     kernel_ms = launches = windows = 0
     shader_ghz = None
     phase_cycles, phase_groups = None, 0
@@ -774,6 +833,7 @@ def main():
         run_all(lambda j: j.models[0].timing_enable(False))
         if not args.no_kernel_timing:
             shader_ghz = lead.timing_model.clock_read()      # of the timed region's last launch
+        if not args.no_kernel_timing and args.full:
             try:
                 # the phases of a group of four windows (dbh_forward_phases_read): ONE more launch, behind
                 # the timed region - the stamps cost about 1 % of the kernel's time
@@ -784,7 +844,7 @@ def main():
             except Exception:                                   # noqa: BLE001
                 phase_cycles, phase_groups = None, 0
             lead.timing_model.phases_enable(False)
-            lead.timing_model.clock_enable(False)
+        lead.timing_model.clock_enable(False)
     if rdzv is not None:
         elapsed = rdzv.max_float(elapsed)
 
@@ -917,7 +977,7 @@ def main():
             'algorithmic_hbm_bytes_per_window': bytes_per_window,
             'hbm_frac_at_algorithmic_bytes': rate * bytes_per_window / PEAK_HBM_BYTES_PER_S,
         }
-    if is_lead and world == 1:
+    if is_lead and world == 1 and args.full:
         if args.config == 1 and not args.no_side_rates:
             result.update(side_rates(weights[0], all_reads0))
         if args.config == 1 and not args.no_other_configs and not args.no_side_rates:
@@ -937,6 +997,8 @@ def main():
     if pending:
         # (behind everything of this configuration's own: its models and buffers are released)
         result.update(other_configs())
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     if is_lead:
         print(json.dumps(result))
         sys.stdout.flush()

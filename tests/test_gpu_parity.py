@@ -780,7 +780,7 @@ def test_bench_rccl_path_single_rank(hip):
     """The RCCL code path of bench.py (rendezvous, ncclGetUniqueId / ncclCommInitRank through the
     C ABI, ncclAllGather of the calls on the launch stream, MAX-over-ranks) forced on with ONE rank
     under the driver's launcher - what the N = 2/4/8 runs execute, minus the peers."""
-    result = _run_bench(['--gpus', '1', '--steps', '3', '--warmup', '1'],
+    result = _run_bench(['--gpus', '1', '--steps', '3', '--warmup', '1', '--full'],
                         {'DEEPBINNER_BENCH_FORCE_RANKS': '1', 'DEEPBINNER_COMM_FORCE': '1'},
                         launcher=1)
     assert result['n_gpus'] == 1 and result['value'] > 0 and 'roofline' in result
@@ -814,13 +814,36 @@ def test_bench_gather_on_the_side_stream_gives_the_same_calls(hip):
     """The side-stream form of the exchange forced for RCCL (one rank) over five steps - both
     sets of call arrays, each reused behind its release event: the calls that reach the host are
     the CPU port's, and the line says where the exchange was queued and how long it took."""
-    result = _run_bench(['--gpus', '1', '--steps', '5', '--warmup', '2', '--no-side-rates'],
+    result = _run_bench(['--gpus', '1', '--steps', '5', '--warmup', '2', '--no-side-rates',
+                         '--full'],
                         {'DEEPBINNER_COMM_FORCE': '1', 'DEEPBINNER_BENCH_GATHER': 'side'})
     assert result['gather']['transport'] == 'rccl'
     assert result['gather']['queued_on'].startswith('side stream')
     assert result['gather']['ms_per_step'] > 0
     assert result['calls_not_none_rank0'] > 0
     assert result['cpu_baseline']['calls_match_gpu'] is True
+
+
+def test_bench_dump_outputs_are_the_last_steps_results(hip, hip_models, tmp_path):
+    """`bench.py --dump-outputs DIR` (a plain run, ten steps per launch cut down to three): the
+    last step's calls and probabilities, float32, are what the model gives for the same seeded
+    reads through the host entry point."""
+    from bench import config_reads
+    result = _run_bench(['--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)], {})
+    assert 'cpu_baseline' not in result and 'other_configs' not in result
+    assert result['steps'] == 3 and result['config']['steps_per_launch'] == 3
+    assert sorted(p.name for p in tmp_path.iterdir()) == ['calls.npy',
+                                                          'probs_EXP-NBD103_read_starts.npy']
+    calls = np.load(str(tmp_path / 'calls.npy'))
+    probs = np.load(str(tmp_path / 'probs_EXP-NBD103_read_starts.npy'))
+    assert calls.dtype == probs.dtype == np.float32
+    assert calls.shape == (10000,) and probs.shape == (10000, 13)
+    assert int((calls != 0).sum()) == result['calls_not_none_rank0'] > 0
+    reads = config_reads(10000, 20260927)
+    want_probs, want_calls = hip_models['EXP-NBD103_read_starts'].classify_packed(
+        reads.reshape(-1), np.arange(10001, dtype=np.int64) * 1024, 'start', 512, 0.5)
+    assert np.array_equal(calls, want_calls.astype(np.float32))
+    assert float(np.abs(probs - want_probs).max()) < 1e-6
 
 
 @pytest.mark.parametrize('config', [2, 3])

@@ -388,11 +388,14 @@ def test_shipped_weights_are_what_h5py_reads_from_the_reference_models():
         assert weights.flat().size == want['n_parameters'] == 107197
 
 
-def test_keras_model_file_import():
-    """The reference's own model files load through hdf5_lite (only where they are mounted)."""
-    ref = '/root/reference/models/EXP-NBD103_read_starts'
-    if not os.path.isfile(ref):
-        pytest.skip('reference checkout not present')
+def test_keras_model_file_import(tmp_path):
+    """The reference's own Keras model file loads through hdf5_lite (tests/golden/keras/: the
+    file with its optimizer state zeroed, gzipped - oracle/make_keras_golden.py)."""
+    import gzip
+    ref = str(tmp_path / 'EXP-NBD103_read_starts')
+    with gzip.open(os.path.join(GOLD, 'keras', 'EXP-NBD103_read_starts.gz'), 'rb') as f:
+        with open(ref, 'wb') as out:
+            out.write(f.read())
     from deepbinner_amd.model_format import ModelWeights
     w, shape = ModelWeights.load(ref)
     assert shape == [None, 1024, 1] and w.n_classes == 13
@@ -468,6 +471,32 @@ def test_bench_workload_string_names_the_configuration():
         'BASELINE.json configs[1]: EXP-NBD103_read_starts model, 10000 synthetic')
     assert bench.PUBLISHED_CPU == {'value': 15, 'unit': 'reads/s', 'threads': 12,
                                    'source': 'README.md:213'}
+
+
+def test_bench_dump_outputs_float32_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """`--dump-outputs`: every array as float32 .npy; above the size limit the same seeded sample
+    of reads for every array (a shorter array keeps the sampled reads it has), its indices in
+    read_index.npy, the whole within the limit."""
+    import bench
+    rng = np.random.default_rng(3)
+    calls = rng.integers(0, 13, 1000).astype(np.int32)
+    probs = rng.random((1000, 13)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / 'all'), {'calls': calls, 'probs_m': probs})
+    got = {n: np.load(str(tmp_path / 'all' / (n + '.npy'))) for n in ('calls', 'probs_m')}
+    assert sorted(p.name for p in (tmp_path / 'all').iterdir()) == ['calls.npy', 'probs_m.npy']
+    assert got['calls'].dtype == np.float32 and np.array_equal(got['calls'], calls)
+    assert np.array_equal(got['probs_m'], probs)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 20000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), {'calls': calls, 'probs_m': probs[:600]})
+    a, b = [{p.stem: np.load(str(p)) for p in (tmp_path / run).iterdir()} for run in 'ab']
+    assert sorted(a) == ['calls', 'probs_m', 'read_index']
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    index = a['read_index'].astype(np.int64)
+    assert a['read_index'].dtype == np.float64 and np.all(np.diff(index) > 0)
+    assert np.array_equal(a['calls'], calls[index].astype(np.float32))
+    assert np.array_equal(a['probs_m'], probs[index[index < 600]])
+    assert sum(v.nbytes for v in a.values()) <= 20000
 
 
 def test_devices_flag_under_a_per_gpu_launcher_is_refused(monkeypatch):

@@ -14,9 +14,9 @@ cd $R
 python -m pytest tests -m gpu -q > $E/pytest_gpu.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $E/smoke.log 2>&1
 for c in 1 2 3; do
-  python bench.py --config $c 2>/dev/null | grep '^{' > $E/bench_config$c.json
+  python bench.py --full --config $c 2>/dev/null | grep '^{' > $E/bench_config$c.json
 done
-python bench.py --steps-per-launch 1 2>/dev/null | grep '^{' > $E/bench_config1_one_launch_per_step.json
+python bench.py --full --steps-per-launch 1 2>/dev/null | grep '^{' > $E/bench_config1_one_launch_per_step.json
 DEEPBINNER_SOAK=1 python -m pytest tests/test_gpu_parity.py -m gpu -q -s -k soak 2>&1 | grep -E "soak:|passed|failed" > $E/soak.log
 bash tools/profile_gpu.sh > $E/profile_gpu.log 2>&1
 cp $R/gpurun_out/prof_stats_bench.log $E/bench_under_rocprofv3.log
