@@ -38,6 +38,9 @@
 //      could be overtaken by a write that wraps around the ring goes in token order instead:
 //      dbh_inflate_core.h, ring_hazard): 3.04 ms.
 //      The ring is written out in coalesced 256-byte pieces, with the Adler-32 sums on the way.
+// Streams of mode DBH_INFLATE_VBZ (ONT's VBZ filter, zstd stage undone by the loader) are no
+// kernel's here: both kernels pass them by, and dbh_vbz.hip's kernel, launched behind them by
+// dbh_inflate_dev, decodes them.
 // What dbh_inflate_dev launches is both of them AT ONCE, a pair of waves per stream
 // (inflate_pair_kernel: wave 0 is kernel 1, wave 1 is kernel 2 resolving the tokens as they come;
 // described in front of it) - a stream then lasts as long as the slower of its halves, not their
@@ -613,6 +616,7 @@ __global__ __launch_bounds__(64 * kWaves2) void inflate_resolve_kernel(
         const dbh_inflate_stream s = streams[i];
         uint8_t* dst = out + s.out_offset;
         const int64_t cap = s.out_bytes;
+        if (s.mode == DBH_INFLATE_VBZ) continue;     // (dbh_vbz.hip's kernel decodes it)
         if (s.mode != DBH_INFLATE_ZLIB) {
             // stored as it is (an unfiltered chunk, a contiguous dataset, or bytes the host has
             // inflated itself): copy, zero-extend
@@ -886,6 +890,7 @@ __device__ __forceinline__ void resolve_pre_stream(
     {
         uint8_t* dst = out + s.out_offset;
         const int64_t cap = s.out_bytes;
+        if (s.mode == DBH_INFLATE_VBZ) return;       // (dbh_vbz.hip's kernel decodes it)
         if (s.mode != DBH_INFLATE_ZLIB) {
             const int64_t have = s.comp_bytes < cap ? s.comp_bytes : cap;
             const uint8_t* src = comp + s.comp_offset;
@@ -1177,6 +1182,12 @@ int hip_failed(hipError_t e, const char* what) {
 
 using namespace dbh_inflate_detail;
 
+// dbh_vbz.hip: the streams of mode DBH_INFLATE_VBZ (the kernels above leave them alone)
+hipError_t dbh_vbz_launch(const uint8_t* comp_dev, int64_t comp_bytes,
+                          const dbh_inflate_stream* streams_dev, int n_streams,
+                          int64_t total_out_bytes, uint8_t* out_dev, int32_t* status_dev,
+                          hipStream_t stream);
+
 extern "C" {
 
 const char* dbh_inflate_last_error(void) { return g_error; }
@@ -1214,6 +1225,8 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
         hipLaunchKernelGGL(inflate_pair_kernel, dim3((unsigned)n), dim3(128), 0, (hipStream_t)stream,
                            comp_dev, comp_bytes, streams_dev, n, tokens, info, out_dev, status_dev);
         DBI_HIP(hipGetLastError());
+        DBI_HIP(dbh_vbz_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev,
+                               status_dev, (hipStream_t)stream));
         return DBH_OK;
     }
     if (wave_per_stream()) {
@@ -1238,6 +1251,8 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
                            (hipStream_t)stream, comp_dev, streams_dev, n, (const uint32_t*)tokens,
                            info, out_dev, status_dev);
     DBI_HIP(hipGetLastError());
+    DBI_HIP(dbh_vbz_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev,
+                           status_dev, (hipStream_t)stream));
     return DBH_OK;
 }
 

@@ -5,7 +5,7 @@
 // exactly as deepbinner_amd/hdf5_lite.py restates it in Python (that module stays the readable
 // description and the parity reference for this one: tests/test_fast5_native.py).
 // Host-only: g++ -O2 -shared -fPIC fast5_reader.cpp -lz -ldl -pthread (libdeflate, if the system has
-// it, is looked up at run time).
+// it, and libzstd, for VBZ, are looked up at run time).
 #include "../../include/deepbinner_fast5.h"
 
 #include <dlfcn.h>
@@ -169,6 +169,113 @@ const LibDeflate& libdeflate() {
     return lib;
 }
 
+// libzstd, for ONT's VBZ filter (HDF5 filter 32020): looked up at run time like libdeflate - no
+// header, no build dependency.  DEEPBINNER_ZSTD_LIB names another library (tests point it at
+// nothing to see VBZ refused).  Where it cannot be loaded, a VBZ Signal with a zstd stage is
+// refused (F5_ERR_FILTER), as it was before this reader knew VBZ.
+struct LibZstd {
+    using Decompress = size_t (*)(void*, size_t, const void*, size_t);
+    using ContentSize = unsigned long long (*)(const void*, size_t);
+    using IsError = unsigned (*)(size_t);
+    Decompress decompress = nullptr;
+    ContentSize content_size = nullptr;
+    IsError is_error = nullptr;
+    LibZstd() {
+        const char* name = std::getenv("DEEPBINNER_ZSTD_LIB");
+        void* lib = dlopen(name && name[0] ? name : "libzstd.so.1", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) return;
+        decompress = reinterpret_cast<Decompress>(dlsym(lib, "ZSTD_decompress"));
+        content_size = reinterpret_cast<ContentSize>(dlsym(lib, "ZSTD_getFrameContentSize"));
+        is_error = reinterpret_cast<IsError>(dlsym(lib, "ZSTD_isError"));
+        if (!decompress || !content_size || !is_error) decompress = nullptr;
+    }
+    bool usable() const { return decompress != nullptr; }
+};
+const LibZstd& libzstd() {
+    static const LibZstd lib;
+    return lib;
+}
+
+// ---- VBZ (filter 32020), version 0: the layout DESIGN.md section "VBZ" pins -------------------
+//   u32 LE original_size | payload (a zstd frame if cd[3] != 0, else the streamvbyte bytes)
+//   streamvbyte: ceil(n/4) control bytes (2 bits per value, low bits first), then the values in
+//   code + 1 little-endian bytes each; value u -> zigzag -> delta, restarting at every chunk.
+// Every self-check failure is a refused read (UnsupportedFilter -> F5_ERR_FILTER), never samples.
+constexpr int kVbzFilter = 32020;
+
+// cd[0] version 0, cd[1] 2-byte integers, cd[2] delta + zigzag on; cd[3] (absent = 0) zstd level
+bool vbz_accepted(const std::vector<uint32_t>& cd) {
+    return cd.size() >= 3 && cd[0] == 0 && cd[1] == 2 && cd[2] == 1;
+}
+bool vbz_zstd(const std::vector<uint32_t>& cd) { return cd.size() >= 4 && cd[3] != 0; }
+
+// streamvbyte bytes -> n int16 samples; false if the data the control bytes call for do not end
+// exactly at the end of the bytes
+bool vbz_unpack(const uint8_t* p, size_t bytes, int64_t n, int16_t* out) {
+    const size_t ctrl = (size_t)((n + 3) / 4);
+    if (ctrl > bytes) return false;
+    const uint8_t* d = p + ctrl;
+    const uint8_t* const end = p + bytes;
+    uint32_t prev = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int len = ((p[i >> 2] >> ((i & 3) * 2)) & 3) + 1;
+        if (end - d < len) return false;
+        uint32_t u = 0;
+        for (int k = 0; k < len; ++k) u |= (uint32_t)d[k] << (8 * k);
+        d += len;
+        prev += (u >> 1) ^ (0u - (u & 1u));
+        out[i] = (int16_t)(uint16_t)prev;
+    }
+    return d == end;
+}
+
+// The chunk's original_size after the self-checks (even, at most `cap` bytes)
+uint32_t vbz_original_size(const uint8_t* src, size_t n, size_t cap) {
+    if (n < 4) throw UnsupportedFilter("VBZ chunk shorter than its header");
+    const uint32_t size = (uint32_t)src[0] | (uint32_t)src[1] << 8 | (uint32_t)src[2] << 16 |
+                          (uint32_t)src[3] << 24;
+    if ((size & 1) || size > cap) throw UnsupportedFilter("VBZ chunk of an impossible size");
+    return size;
+}
+
+// The streamvbyte bytes a zstd-compressed VBZ chunk holds (its frame's content size), checked
+// against what n values can occupy (n/4 control bytes + 1..4 bytes each)
+uint64_t vbz_frame_size(const uint8_t* src, size_t n, uint32_t original_size) {
+    const LibZstd& z = libzstd();
+    if (!z.usable()) throw UnsupportedFilter("VBZ needs libzstd");
+    const unsigned long long size = z.content_size(src + 4, n - 4);
+    const uint64_t values = original_size / 2, ctrl = (values + 3) / 4;
+    if (size >= (unsigned long long)-2 || size < ctrl + values || size > ctrl + 4 * values)
+        throw UnsupportedFilter("VBZ chunk with a bad zstd frame");
+    return (uint64_t)size;
+}
+
+// zstd stage undone: `dst` (frame_size bytes) <- the chunk's streamvbyte bytes
+void vbz_unzstd(const uint8_t* src, size_t n, uint8_t* dst, uint64_t frame_size) {
+    const LibZstd& z = libzstd();
+    if (!z.usable()) throw UnsupportedFilter("VBZ needs libzstd");
+    const size_t got = z.decompress(dst, (size_t)frame_size, src + 4, n - 4);
+    if (z.is_error(got) || got != frame_size) throw UnsupportedFilter("VBZ chunk: zstd failed");
+}
+
+// one VBZ chunk as stored -> its int16 bytes (original_size of them; the caller zero-extends)
+void vbz_decode(const uint8_t* src, size_t n, const std::vector<uint32_t>& cd, size_t cap,
+                std::vector<uint8_t>* out, std::vector<uint8_t>* tmp) {
+    const uint32_t size = vbz_original_size(src, n, cap);
+    const uint8_t* packed = src + 4;
+    size_t packed_bytes = n - 4;
+    if (vbz_zstd(cd)) {
+        const uint64_t frame = vbz_frame_size(src, n, size);
+        tmp->resize((size_t)frame);
+        vbz_unzstd(src, n, tmp->data(), frame);
+        packed = tmp->data();
+        packed_bytes = (size_t)frame;
+    }
+    out->resize(size);
+    if (!vbz_unpack(packed, packed_bytes, size / 2, reinterpret_cast<int16_t*>(out->data())))
+        throw UnsupportedFilter("VBZ chunk: data bytes do not match the control bytes");
+}
+
 // The chunk inflated last.  A read stored as ONE chunk (common) is asked for twice, once per end,
 // and deflate cannot be entered in the middle.  One per thread: a Fast5 whose reads are resolved
 // is read-only otherwise, so several threads can decode different reads of it at once.
@@ -178,6 +285,7 @@ const LibDeflate& libdeflate() {
 // serialises the threads on the address-space lock).
 struct ChunkCache {
     std::vector<uint8_t> data, scratch;
+    std::vector<uint8_t> vbz;           // a VBZ chunk's streamvbyte bytes (zstd stage undone)
     uint64_t addr = ~0ull, bytes = 0;
     const void* owner = nullptr;        // the file the cached chunk came from (addresses repeat
                                         // from file to file: a thread may serve several)
@@ -316,15 +424,19 @@ class Fast5 {
     // What a read's Signal consists of on disk, piece by piece, in sample order.  A piece covers
     // samples [first, first + count) of the read.
     struct RawPiece {
-        int kind = 0;              // kZlib / kStored / kHostDecode / kZeros
-        uint64_t file_off = 0;     // where its bytes lie in the file (kZlib, kStored)
+        int kind = 0;              // kZlib / kStored / kHostDecode / kZeros / kVbz
+        uint64_t file_off = 0;     // where its bytes lie in the file (kZlib, kStored, kVbz)
         uint64_t nbytes = 0;       // how many
         int64_t first = 0, count = 0;
         uint64_t chunk_addr = 0, chunk_bytes = 0;      // kHostDecode: the chunk, for decode_chunk
         uint32_t mask = 0;
         int64_t comp_offset = 0, comp_bytes = 0;       // its place in a batch's byte buffer
+        // kVbz: what the GPU is handed - the chunk with its zstd stage undone (u32 original_size,
+        // streamvbyte bytes): vbz_bytes of them; vbz_zstd: the chunk has a zstd stage to undo
+        uint64_t vbz_bytes = 0;
+        bool vbz_zstd = false;
     };
-    enum { kZlib = 0, kStored = 1, kHostDecode = 2, kZeros = 3 };
+    enum { kZlib = 0, kStored = 1, kHostDecode = 2, kZeros = 3, kVbz = 4 };
 
     // zlib_above: deflate streams longer than this many bytes are left to the host (a lane of the
     // GPU decoder walks ONE stream: a stream ten times the usual length holds its wave ten times
@@ -398,6 +510,17 @@ class Fast5 {
             } else if (n_applied == 1 && applied[0] == 3 && nbytes >= 4) {
                 q.kind = kStored;
                 q.nbytes = nbytes - 4;
+            } else if (n_applied == 1 && applied[0] == kVbzFilter) {
+                // VBZ alone: the size of what the GPU gets needs the chunk's header (and the zstd
+                // frame's); the self-checks on sizes run here, a failure refuses the read
+                q.kind = kVbz;
+                for (const Filter& f : s.filters)
+                    if (f.id == kVbzFilter) q.vbz_zstd = vbz_zstd(f.cd);
+                uint8_t head[32];
+                const uint64_t h = std::min<uint64_t>(nbytes, sizeof(head));
+                read_bytes(start, h, head);
+                const uint32_t size = vbz_original_size(head, (size_t)h, (size_t)s.chunk_elems * 2);
+                q.vbz_bytes = q.vbz_zstd ? 4 + vbz_frame_size(head, (size_t)h, size) : nbytes;
             } else {
                 q.kind = kHostDecode;              // shuffle, or an order not seen in the field
             }
@@ -1205,8 +1328,11 @@ class Fast5 {
                 for (uint64_t k = 0; k < ncd; ++k) f.cd.push_back((uint32_t)u(p + 4 * k, 4));
                 p += 4 * ncd;
                 if (fversion == 1 && (ncd % 2) == 1) p += 4;
-                if (f.id != 1 && f.id != 2 && f.id != 3 && s.layout == 2)
-                    throw UnsupportedFilter("Signal uses a filter other than deflate/shuffle/fletcher32");
+                if (f.id == kVbzFilter && s.layout == 2 &&
+                    (!vbz_accepted(f.cd) || (vbz_zstd(f.cd) && !libzstd().usable())))
+                    throw UnsupportedFilter("Signal uses a VBZ variant this reader does not decode");
+                if (f.id != 1 && f.id != 2 && f.id != 3 && f.id != kVbzFilter && s.layout == 2)
+                    throw UnsupportedFilter("Signal uses a filter other than deflate/shuffle/fletcher32/vbz");
                 s.filters.push_back(f);
             }
         }
@@ -1303,6 +1429,10 @@ class Fast5 {
             } else if (f.id == 3) {
                 if (raw->size() < 4) throw FormatError("chunk shorter than its checksum");
                 raw->resize(raw->size() - 4);
+            } else if (f.id == kVbzFilter) {
+                vbz_decode(raw->data(), raw->size(), f.cd, (size_t)s.chunk_elems * 2, &tmp,
+                           &cache->vbz);
+                raw->swap(tmp);
             } else {
                 throw FormatError("unsupported filter");
             }
@@ -2125,6 +2255,24 @@ extern "C" {
 
 const char* f5_version(void) { return "deepbinner_fast5 0.1"; }
 
+int f5_vbz_decode(const uint8_t* chunk, int64_t chunk_bytes, const uint32_t* cd, int n_cd,
+                  int64_t max_samples, int16_t* out, int64_t* n_samples) {
+    if ((!chunk && chunk_bytes) || chunk_bytes < 0 || (!cd && n_cd) || n_cd < 0 || max_samples < 0 ||
+        (!out && max_samples) || !n_samples)
+        return F5_ERR_ARGUMENT;
+    *n_samples = 0;
+    const std::vector<uint32_t> values(cd, cd + n_cd);
+    if (!vbz_accepted(values) || (vbz_zstd(values) && !libzstd().usable())) return F5_ERR_FILTER;
+    std::vector<uint8_t> samples, tmp;
+    const int rc = guarded([&] {
+        vbz_decode(chunk, (size_t)chunk_bytes, values, (size_t)max_samples * 2, &samples, &tmp);
+    });
+    if (rc != F5_OK) return rc;
+    if (!samples.empty()) std::memcpy(out, samples.data(), samples.size());
+    *n_samples = (int64_t)samples.size() / 2;
+    return F5_OK;
+}
+
 int f5_usable_cpus(void) { return usable_cpus(); }
 
 const char* f5_status_string(int status) {
@@ -2305,9 +2453,9 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
                 for (Fast5::RawPiece& p : st.pieces) {
                     const uint64_t wanted = (uint64_t)p.count * 2;
                     const size_t at = st.bytes.size();
-                    if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored) {
-                        const uint64_t take = p.kind == Fast5::kZlib ? p.nbytes
-                                                                     : std::min(p.nbytes, wanted);
+                    if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored || p.kind == Fast5::kVbz) {
+                        const uint64_t take = p.kind != Fast5::kStored ? p.nbytes
+                                                                       : std::min(p.nbytes, wanted);
                         st.bytes.resize(at + (size_t)take);
                         file.read_bytes(p.file_off, take, reinterpret_cast<uint8_t*>(&st.bytes[at]));
                         p.nbytes = take;
@@ -2368,14 +2516,18 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
         for (int64_t i = 0; i < n_files; ++i)
             for (Fast5::RawPiece& p : staged[(size_t)i].pieces) {
                 p.comp_offset = at;
-                p.comp_bytes = p.kind == Fast5::kHostDecode ? p.count * 2 : (int64_t)p.nbytes;
+                p.comp_bytes = p.kind == Fast5::kHostDecode ? p.count * 2
+                               : p.kind == Fast5::kVbz      ? (int64_t)p.vbz_bytes
+                                                            : (int64_t)p.nbytes;
                 at += p.comp_bytes;
                 f5_raw_stream rec;
                 rec.comp_offset = p.comp_offset;
                 rec.comp_bytes = p.comp_bytes;
                 rec.out_offset = (batch->offsets[(size_t)i] + p.first) * 2;
                 rec.out_bytes = p.count * 2;
-                rec.mode = p.kind == Fast5::kZlib ? F5_RAW_ZLIB : F5_RAW_STORED;
+                rec.mode = p.kind == Fast5::kZlib  ? F5_RAW_ZLIB
+                           : p.kind == Fast5::kVbz ? F5_RAW_VBZ
+                                                   : F5_RAW_STORED;
                 rec.reserved = (int32_t)i;
                 batch->streams.push_back(rec);
             }
@@ -2391,6 +2543,18 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
             for (const Fast5::RawPiece& p : st.pieces) {
                 const uint8_t* src = reinterpret_cast<const uint8_t*>(st.bytes.data()) + p.file_off;
                 uint8_t* dst = comp + p.comp_offset;
+                if (p.kind == Fast5::kVbz && p.vbz_zstd) {
+                    // zstd on the host, the streamvbyte stage on the GPU
+                    const int rc = guarded([&] {
+                        std::memcpy(dst, src, 4);
+                        vbz_unzstd(src, (size_t)p.nbytes, dst + 4, p.vbz_bytes - 4);
+                    });
+                    if (rc != F5_OK) {
+                        std::memset(dst, 0, (size_t)p.comp_bytes);   // (the GPU refuses it too)
+                        inflate_failed[(size_t)i] = rc;
+                    }
+                    continue;
+                }
                 if (p.kind != Fast5::kHostDecode) {
                     std::memcpy(dst, src, (size_t)p.comp_bytes);
                     continue;
@@ -2887,6 +3051,7 @@ struct f5_stream {
                     p.comp_bytes = p.kind == Fast5::kZlib     ? (int64_t)p.nbytes
                                    : p.kind == Fast5::kStored ? std::min<int64_t>((int64_t)p.nbytes, wanted)
                                    : p.kind == Fast5::kZeros  ? 0
+                                   : p.kind == Fast5::kVbz    ? (int64_t)p.vbz_bytes
                                                               : wanted;
                     at += p.comp_bytes;
                     f5_raw_stream rec;
@@ -2894,7 +3059,9 @@ struct f5_stream {
                     rec.comp_bytes = p.comp_bytes;
                     rec.out_offset = (c->batch->offsets[(size_t)i] + p.first) * 2;
                     rec.out_bytes = wanted;
-                    rec.mode = p.kind == Fast5::kZlib ? F5_RAW_ZLIB : F5_RAW_STORED;
+                    rec.mode = p.kind == Fast5::kZlib  ? F5_RAW_ZLIB
+                               : p.kind == Fast5::kVbz ? F5_RAW_VBZ
+                                                       : F5_RAW_STORED;
                     rec.reserved = (int32_t)i;         // which read of the batch it belongs to
                     c->batch->streams.push_back(rec);
                 }
@@ -2916,7 +3083,8 @@ struct f5_stream {
                 for (int64_t i = 0; i < c->count; ++i)
                     if (c->batch->status[(size_t)i] == F5_OK)
                         for (const Fast5::RawPiece& p : c->pieces[(size_t)i])
-                            if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored) {
+                            if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored ||
+                                p.kind == Fast5::kVbz) {
                                 where[(size_t)i] = p.file_off;
                                 break;
                             }
@@ -2937,6 +3105,7 @@ struct f5_stream {
         thread_local ChunkCache cache;
         thread_local std::vector<Fast5::IoItem> items;
         thread_local std::vector<char> failed;
+        thread_local std::vector<uint8_t> vbz_chunk;
         uint8_t* comp = reinterpret_cast<uint8_t*>(c->batch->comp.data());
         auto fail = [&](int64_t i, int rc) {
             // what could not be fetched or decoded reads as nothing: a stored stream of no
@@ -2954,7 +3123,8 @@ struct f5_stream {
             const int64_t i = c->fetch_order[(size_t)k];
             if (c->batch->status[(size_t)i] != F5_OK) continue;
             for (const Fast5::RawPiece& p : c->pieces[(size_t)i])
-                if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored)
+                if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored ||
+                    (p.kind == Fast5::kVbz && !p.vbz_zstd))
                     items.push_back({p.file_off, (uint64_t)p.comp_bytes, comp + p.comp_offset, i});
         }
         const int rc_all = guarded([&] { c->file->read_many(items, &failed); });
@@ -2967,8 +3137,16 @@ struct f5_stream {
             const int rc = guarded([&] {
                 const ReadEntry& r = c->file->read(i);
                 for (const Fast5::RawPiece& p : c->pieces[(size_t)i])
-                    if (p.kind == Fast5::kHostDecode)
+                    if (p.kind == Fast5::kHostDecode) {
                         c->file->decode_piece(r.signal, p, comp + p.comp_offset, &cache);
+                    } else if (p.kind == Fast5::kVbz && p.vbz_zstd) {
+                        // zstd on the host, the streamvbyte stage on the GPU
+                        vbz_chunk.resize((size_t)p.nbytes);
+                        c->file->read_bytes(p.file_off, p.nbytes, vbz_chunk.data());
+                        uint8_t* dst = comp + p.comp_offset;
+                        std::memcpy(dst, vbz_chunk.data(), 4);
+                        vbz_unzstd(vbz_chunk.data(), vbz_chunk.size(), dst + 4, p.vbz_bytes - 4);
+                    }
             });
             if (rc != F5_OK) fail(i, rc);
         }

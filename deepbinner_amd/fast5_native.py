@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     'f5_batch_read_ids', 'f5_batch_free', 'f5_stream_open', 'f5_stream_next', 'f5_stream_close',
     'f5_set_sample_allocator', 'f5_release_idle_buffers', 'f5_stream_open_raw', 'f5_batch_comp',
     'f5_batch_comp_bytes', 'f5_batch_streams', 'f5_batch_n_streams', 'f5_write_single_reads',
-    'f5_single_read_image', 'f5_load_batch_raw',
+    'f5_single_read_image', 'f5_load_batch_raw', 'f5_vbz_decode',
 ]
 
 
@@ -89,6 +89,8 @@ def load_library():
         'f5_batch_n_streams': (c_i64, [c_void_p]),
         'f5_set_sample_allocator': (c_int, [c_void_p, c_void_p, c_void_p]),
         'f5_release_idle_buffers': (None, []),
+        'f5_vbz_decode': (c_int, [c_void_p, c_i64, P(ctypes.c_uint32), c_int, c_i64, c_void_p,
+                                  P(c_i64)]),
     }
     for name, (restype, argtypes) in sigs.items():
         fn = getattr(lib, name)
@@ -328,10 +330,28 @@ def stream_reads(fast5_files, keep=None, threads=0, depth=0):
         lib.f5_stream_close(stream)
 
 
-RAW_ZLIB, RAW_STORED = 0, 1
+RAW_ZLIB, RAW_STORED, RAW_VBZ = 0, 1, 2
 # f5_raw_stream (include/deepbinner_fast5.h) = dbh_inflate_stream (include/deepbinner_hip.h)
 RAW_STREAM = np.dtype([('comp_offset', '<i8'), ('comp_bytes', '<i8'), ('out_offset', '<i8'),
                        ('out_bytes', '<i8'), ('mode', '<i4'), ('read', '<i4')])
+
+
+def vbz_decode(chunk, cd, max_samples):
+    """One VBZ chunk as stored (filter 32020, client values ``cd``) -> its int16 samples, through
+    the native loader's decoder and self-checks (``f5_vbz_decode``); None where it refuses the
+    chunk (F5_ERR_FILTER).  ``max_samples``: the chunk's size in samples."""
+    lib = load_library()
+    chunk = np.frombuffer(bytes(chunk), dtype=np.uint8)
+    values = (ctypes.c_uint32 * max(len(cd), 1))(*[int(v) for v in cd])
+    out = np.zeros(max(int(max_samples), 1), dtype=np.int16)
+    n = ctypes.c_int64(0)
+    status = lib.f5_vbz_decode(chunk.ctypes.data if chunk.size else None, int(chunk.size), values,
+                               len(cd), int(max_samples), out.ctypes.data, ctypes.byref(n))
+    if status == F5_ERR_FILTER:
+        return None
+    if status != F5_OK:
+        raise Fast5NativeError(status_string(status))
+    return out[:n.value].copy()
 
 
 def stream_raw(fast5_files, threads=0, depth=0, host_inflate_above=0):

@@ -12,7 +12,8 @@ just the slice of the HDF5 file format those files use:
 * old-style groups (symbol-table message -> v1 B-tree -> SNOD nodes + local heap);
 * new-style groups: compact (link messages in the header) and dense (fractal heap indexed by a
   version-2 B-tree on link names);
-* datasets: compact / contiguous / chunked with deflate, shuffle and fletcher32 filters; the chunk
+* datasets: compact / contiguous / chunked with deflate, shuffle, fletcher32 and ONT's VBZ
+  (filter 32020, version 0, zstd through the system's libzstd: ``vbz_decode``) filters; the chunk
   index is a v1 B-tree (layout message v1-v3) or, in files written with ``libver='latest'`` by
   HDF5 >= 1.10 (layout message v4), the single chunk itself, an implicit run, a fixed array or an
   extensible array (with their paged and super-block forms);
@@ -27,17 +28,106 @@ Anything outside that slice raises ``OSError`` — the same exception class h5py
 unreadable file, which ``load_fast5s.get_read_id_and_signal`` turns into ``(None, None)``.
 """
 
+import ctypes
 import mmap
+import os
 import zlib
 
 import numpy as np
 
 _SIGNATURE = b'\x89HDF\r\n\x1a\n'
 _UNDEF = 0xFFFFFFFFFFFFFFFF
+VBZ_FILTER = 32020
 
 
 class Hdf5FormatError(OSError):
     pass
+
+
+# ---- VBZ (ONT's HDF5 filter 32020), version 0 - the layout and self-checks of DESIGN.md, "VBZ",
+# the same accept / reject decisions as the native loader's (fast5_reader.cpp, vbz_decode) ------
+_ZSTD = []
+
+
+def _zstd():
+    """libzstd through ctypes (DEEPBINNER_ZSTD_LIB names another one), or None."""
+    if not _ZSTD:
+        lib = None
+        try:
+            lib = ctypes.CDLL(os.environ.get('DEEPBINNER_ZSTD_LIB') or 'libzstd.so.1')
+            lib.ZSTD_getFrameContentSize.restype = ctypes.c_ulonglong
+            lib.ZSTD_getFrameContentSize.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+            lib.ZSTD_decompress.restype = ctypes.c_size_t
+            lib.ZSTD_decompress.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_size_t]
+            lib.ZSTD_isError.restype = ctypes.c_uint
+            lib.ZSTD_isError.argtypes = [ctypes.c_size_t]
+        except (OSError, AttributeError):
+            lib = None
+        _ZSTD.append(lib)
+    return _ZSTD[0]
+
+
+def vbz_accepted(cd):
+    """cd[0] version 0, cd[1] 2-byte integers, cd[2] delta + zigzag on; cd[3] (absent = 0): zstd
+    level, and a zstd stage needs libzstd."""
+    cd = list(cd)
+    if len(cd) < 3 or cd[0] != 0 or cd[1] != 2 or cd[2] != 1:
+        return False
+    return not (len(cd) >= 4 and cd[3] != 0) or _zstd() is not None
+
+
+def vbz_unpack(packed, n):
+    """streamvbyte bytes -> n int16 samples (zigzag, delta from 0), vectorised; None if the data
+    the control bytes call for do not end exactly at the end of ``packed``."""
+    arr = np.frombuffer(packed, dtype=np.uint8)
+    n_ctrl = (n + 3) // 4
+    if n_ctrl > len(arr):
+        return None
+    ctrl = arr[:n_ctrl]
+    lengths = (((ctrl[:, None] >> np.array([0, 2, 4, 6], dtype=np.uint8)) & 3).reshape(-1)[:n]
+               .astype(np.int64) + 1)
+    data = arr[n_ctrl:]
+    if int(lengths.sum()) != len(data):
+        return None
+    starts = np.cumsum(lengths) - lengths
+    padded = np.concatenate([data, np.zeros(3, dtype=np.uint8)]).astype(np.uint32)
+    u = (padded[starts] | padded[starts + 1] << 8 | padded[starts + 2] << 16 |
+         padded[starts + 3] << 24)
+    u &= ((np.uint64(1) << (8 * lengths).astype(np.uint64)) - np.uint64(1)).astype(np.uint32)
+    delta = (u >> np.uint32(1)) ^ (np.uint32(0) - (u & np.uint32(1)))
+    return np.cumsum(delta, dtype=np.uint32).astype(np.uint16).view(np.int16)
+
+
+def vbz_decode(chunk, cd, cap):
+    """One VBZ chunk as stored -> the bytes of its int16 samples (original_size of them; at most
+    ``cap``).  Raises Hdf5FormatError for a variant not decoded here and for every self-check that
+    fails: a refused read, never wrong samples."""
+    if not vbz_accepted(cd):
+        raise Hdf5FormatError('unsupported filter id %d (VBZ variant %s)' % (VBZ_FILTER, list(cd)))
+    chunk = bytes(chunk)
+    if len(chunk) < 4:
+        raise Hdf5FormatError('VBZ chunk shorter than its header')
+    size = int.from_bytes(chunk[:4], 'little')
+    if size & 1 or size > cap:
+        raise Hdf5FormatError('VBZ chunk of an impossible size')
+    n = size // 2
+    packed = chunk[4:]
+    if len(cd) >= 4 and cd[3] != 0:
+        lib = _zstd()
+        frame = lib.ZSTD_getFrameContentSize(packed, len(packed))
+        n_ctrl = (n + 3) // 4
+        if frame >= (1 << 64) - 2 or frame < n_ctrl + n or frame > n_ctrl + 4 * n:
+            raise Hdf5FormatError('VBZ chunk with a bad zstd frame')
+        out = ctypes.create_string_buffer(max(int(frame), 1))
+        got = lib.ZSTD_decompress(out, int(frame), packed, len(packed))
+        if lib.ZSTD_isError(got) or got != frame:
+            raise Hdf5FormatError('VBZ chunk: zstd failed')
+        packed = out.raw[:int(frame)]
+    samples = vbz_unpack(packed, n)
+    if samples is None:
+        raise Hdf5FormatError('VBZ chunk: data bytes do not match the control bytes')
+    return samples.tobytes()
 
 
 def _u(buf, off, size):
@@ -444,6 +534,8 @@ class Dataset(_Object):
                     raw = arr[:n * esize].reshape(esize, n).T.tobytes() + arr[n * esize:].tobytes()
                 elif fid == 3:  # fletcher32: strip the trailing checksum
                     raw = raw[:-4]
+                elif fid == VBZ_FILTER and dt.itemsize == 2:
+                    raw = vbz_decode(raw, cd, chunk_elems * dt.itemsize)
                 else:
                     raise Hdf5FormatError('unsupported filter id %d' % fid)
             need = chunk_elems * dt.itemsize

@@ -195,7 +195,7 @@ def _attribute_group(image, attributes):
     return header, btree, heap
 
 
-def _dataset_int16(image, samples, compress, packed=None):
+def _dataset_int16(image, samples, compress, packed=None, signal_filter=None):
     samples = np.ascontiguousarray(samples, dtype='<i2')
     n = len(samples)
     messages = [_message(0x0001, _simple_dataspace(n)),
@@ -203,7 +203,23 @@ def _dataset_int16(image, samples, compress, packed=None):
                 # fill value, version 2: allocate late / write never / undefined
                 _message(0x0005, struct.pack('<BBBB', 2, 2, 0, 0))]
     raw = samples.tobytes()
-    if compress and n > 0:
+    if signal_filter is not None and n > 0:
+        # a pipeline of the caller's: its message body, the chunk size in samples and the chunks
+        # as stored with their filter masks (tests: VBZ copies of fast5 files)
+        chunk_elems = int(signal_filter['chunk'])
+        chunks = list(signal_filter['chunks'])
+        assert 0 < len(chunks) <= 2 * CHUNK_K and len(chunks) == -(-n // chunk_elems)
+        addrs = [image.add(data) for data, _ in chunks]
+        key_size = 8 + 8 * 2
+        node = b'TREE' + struct.pack('<BBHQQ', 1, 0, len(chunks), UNDEF, UNDEF)
+        for k, ((data, mask), addr) in enumerate(zip(chunks, addrs)):
+            node += struct.pack('<IIQQ', len(data), mask, k * chunk_elems, 0) + struct.pack('<Q', addr)
+        node += struct.pack('<IIQQ', 0, 0, n, 0)
+        btree = image.add(node + b'\0' * (24 + 2 * CHUNK_K * 8 + (2 * CHUNK_K + 1) * key_size -
+                                          len(node)))
+        messages.append(_message(0x000B, signal_filter['pipeline']))
+        messages.append(_message(0x0008, struct.pack('<BBBQII', 3, 2, 2, btree, chunk_elems, 2)))
+    elif compress and n > 0:
         if packed is None:
             packed = zlib.compress(raw, 1)
         chunk = image.add(packed)
@@ -225,10 +241,11 @@ def _dataset_int16(image, samples, compress, packed=None):
     return image.add(_object_header(messages))
 
 
-def _read_group(image, read_id, signal, compress, read_number, metadata, packed_signal=None):
+def _read_group(image, read_id, signal, compress, read_number, metadata, packed_signal=None,
+                signal_filter=None):
     """/read_<read_id> with Raw/Signal and whatever ``metadata`` holds -> (header, btree, heap)."""
     signal = np.asarray(signal)
-    dataset = _dataset_int16(image, signal, compress, packed_signal)
+    dataset = _dataset_int16(image, signal, compress, packed_signal, signal_filter)
     metadata = metadata or {}
     attrs = [string_attribute('read_id', read_id)]
     raw_values = dict(metadata.get('Raw') or {})
@@ -257,17 +274,21 @@ def _finish(image, superblock, root):
 
 
 def single_read_fast5_bytes(read_id, signal, compress=True, read_number=None, metadata=None,
-                            packed_signal=None):
+                            packed_signal=None, signal_filter=None):
     """The bytes of a one-read fast5 file holding ``signal`` (int16) as read ``read_id``.
     ``metadata``: what else the read's group of a multi-read container held, copied as
     ont_fast5_api's multi_to_single_fast5 does (the tool the reference runs, realtime.py:183-190):
     ``{'read': {attribute: value}, 'Raw': {...}, 'channel_id': {...}, 'tracking_id': {...},
     'context_tags': {...}}`` ('read': the read group's own attributes, e.g. run_id) - basecallers
     need ``channel_id`` (digitisation, offset, range, sampling_rate).  ``packed_signal``: the
-    zlib stream of the signal's bytes where the caller has it already (a chunk as stored)."""
+    zlib stream of the signal's bytes where the caller has it already (a chunk as stored).
+    ``signal_filter`` (None: the deflated chunk above): another filter pipeline for the Signal -
+    ``{'pipeline': <body of the filter pipeline message>, 'chunk': <samples per chunk>, 'chunks':
+    [(<chunk as stored>, <filter mask>), ...]}`` (at most 64 chunks; tests write VBZ files so)."""
     image = _Image()
     superblock = image.reserve(96)
-    read = _read_group(image, read_id, signal, compress, read_number, metadata, packed_signal)
+    read = _read_group(image, read_id, signal, compress, read_number, metadata, packed_signal,
+                       signal_filter)
     root = _group(image, {'read_' + read_id: read}, [string_attribute('file_version', '2.0')])
     return _finish(image, superblock, root)
 
@@ -277,7 +298,8 @@ def multi_read_fast5_bytes(reads, compress=True):
     one ``/read_<id>`` group per read under the root).  ``reads``: (read_id, signal) or (read_id,
     signal, metadata) or (read_id, signal, metadata, deflated) tuples - ``deflated`` being
     ``zlib.compress(signal.tobytes(), 1)`` done beforehand (on other threads, or once for many
-    reads that share a signal).  The root group's links share one symbol-table node; the file
+    reads that share a signal) or, as a fifth item, a ``signal_filter`` as in
+    ``single_read_fast5_bytes``.  The root group's links share one symbol-table node; the file
     records the node size that takes (group leaf node K) in its superblock, as libhdf5 does for
     H5Pset_sym_k.  Used to build the containers of the streaming tests and tools."""
     reads = list(reads)
@@ -289,9 +311,11 @@ def multi_read_fast5_bytes(reads, compress=True):
         read_id, signal = read[0], read[1]
         metadata = read[2] if len(read) > 2 else None
         packed = read[3] if len(read) > 3 else None
+        signal_filter = read[4] if len(read) > 4 else None
         name = 'read_' + read_id
         assert name not in groups, 'duplicate read id ' + read_id
-        groups[name] = _read_group(image, read_id, signal, compress, None, metadata, packed)
+        groups[name] = _read_group(image, read_id, signal, compress, None, metadata, packed,
+                                   signal_filter)
     image.leaf_k = max(GROUP_LEAF_K, (len(groups) + 1) // 2)
     if groups:
         root = _group(image, groups, [string_attribute('file_version', '2.0')])

@@ -283,7 +283,7 @@ def classify_pair(start_model, end_model, samples, offsets, scan_size, score_dif
     return calls
 
 
-INFLATE_ZLIB, INFLATE_STORED = 0, 1
+INFLATE_ZLIB, INFLATE_STORED, INFLATE_VBZ = 0, 1, 2
 # dbh_inflate_stream (include/deepbinner_hip.h)
 INFLATE_STREAM = np.dtype([('comp_offset', '<i8'), ('comp_bytes', '<i8'), ('out_offset', '<i8'),
                            ('out_bytes', '<i8'), ('mode', '<i4'), ('reserved', '<i4')])

@@ -36,7 +36,9 @@ extern "C" {
 #define F5_ERR_MULTI 4     /* several reads where the caller asked for a one-read file */
 #define F5_ERR_ARGUMENT 5
 #define F5_ERR_FILTER 6    /* Signal compressed with a filter other than deflate / shuffle /
-                              fletcher32 (e.g. ONT's VBZ, HDF5 filter 32020) */
+                              fletcher32 / VBZ version 0 (HDF5 filter 32020, with libzstd.so.1 at
+                              hand where it has a zstd stage), or a VBZ chunk that fails its
+                              self-checks ("VBZ") */
 #define F5_ERR_EXISTS 7    /* f5_write_single_reads: a file of that name is there already - left
                               as it is (the reference never moves a file over another one,
                               realtime.py:111-144: such a clash is counted and skipped) */
@@ -107,7 +109,9 @@ void f5_stream_close(f5_stream* stream);
  *   - one f5_raw_stream per piece of stored Signal (a chunk, or a whole unchunked dataset), longest
  *     deflate stream first: where its bytes lie in the byte buffer, where its output goes in the
  *     sample buffer (byte offsets) and how many bytes of it are wanted, and whether it is a zlib
- *     stream (F5_RAW_ZLIB) or the bytes themselves (F5_RAW_STORED: unfiltered data, chunks with
+ *     stream (F5_RAW_ZLIB), a VBZ chunk with its zstd stage undone by the loader's threads
+ *     (F5_RAW_VBZ: u32 original_size, then the streamvbyte bytes - sized from the zstd frame's
+ *     content size), or the bytes themselves (F5_RAW_STORED: unfiltered data, chunks with
  *     filters beyond deflate / fletcher32 - inflated and unshuffled by the host after all - and
  *     the deflate streams the host is to keep: those longer than host_inflate_above bytes, or,
  *     with host_inflate_above = -p (1..100), the longest ones of each container holding p per
@@ -118,6 +122,7 @@ void f5_stream_close(f5_stream* stream);
  * 5-6 ms of parsing: three in flight starve sixteen threads). */
 #define F5_RAW_ZLIB 0
 #define F5_RAW_STORED 1
+#define F5_RAW_VBZ 2
 typedef struct f5_raw_stream {
     int64_t comp_offset, comp_bytes;
     int64_t out_offset, out_bytes;
@@ -141,7 +146,8 @@ int64_t f5_batch_n_streams(const f5_batch* batch);
  * (scalar strings, integers, floats; what a basecaller needs), in the layout of
  * deepbinner_amd/hdf5_write.py (superblock 0, symbol-table groups, one deflated chunk), byte for
  * byte.  A Signal stored as ONE deflate-compressed chunk - what MinKNOW and ont_fast5_api write -
- * is carried over as stored: nothing is inflated, nothing deflated again.  A file is written
+ * is carried over as stored: nothing is inflated, nothing deflated again; any other Signal - a VBZ
+ * one among them - is decoded and written as one deflated chunk, readable without a plugin.  A file is written
  * under a temporary name beside its own and linked into place: an existing file is never
  * overwritten (status F5_ERR_EXISTS), no symlink followed, no partial file left under the final
  * name.  status[i] = F5_OK or why read i could not be written; n_threads as everywhere.  *bytes_written (may be NULL): total
@@ -152,6 +158,14 @@ int f5_write_single_reads(const char* container, int64_t n, const int64_t* read_
 /* the bytes such a file would hold (tests); *size is set even if capacity is too small */
 int f5_single_read_image(const char* container, int64_t read_index, uint8_t* out, int64_t capacity,
                          int64_t* size);
+
+/* One VBZ chunk as stored (filter 32020; cd / n_cd: the filter's client values) -> its samples,
+ * through the loader's own decoder and self-checks: F5_OK and *n_samples = original_size / 2
+ * (refused above max_samples), or F5_ERR_FILTER for a variant this reader does not decode or a
+ * chunk that fails a check.  out holds max_samples int16.  (Tests: the host side of the GPU's
+ * decoder.) */
+int f5_vbz_decode(const uint8_t* chunk, int64_t chunk_bytes, const uint32_t* cd, int n_cd,
+                  int64_t max_samples, int16_t* out, int64_t* n_samples);
 
 /* Where the packed samples of a batch live.  Freed batches leave their sample buffer in a pool
  * (bounded by DEEPBINNER_FAST5_POOL_MB, default 2048) for the next batch that fits, so that a

@@ -199,13 +199,19 @@ int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_cal
  * stream that holds more is cut there (a partial last chunk), one that ends earlier is
  * zero-extended (MinKNOW's short final chunk, as libhdf5 does it).  DBH_INFLATE_STORED: the
  * bytes are the data itself (an unfiltered chunk, or what the host inflated for the filters the
- * GPU does not do) - copied, zero-extended.
+ * GPU does not do) - copied, zero-extended.  DBH_INFLATE_VBZ: a chunk of ONT's VBZ filter (HDF5
+ * filter 32020, version 0) with its zstd stage undone - u32 LE original_size, then the
+ * streamvbyte bytes ("VBZ") - unpacked, un-zigzagged and summed into int16 samples by a
+ * kernel of its own (dbh_vbz.hip, one wave per stream) in the same call; cut / zero-extended to
+ * out_bytes like the others; a stream whose data do not end exactly where it does, or whose
+ * original_size is odd, is refused (status != 0, output zeros).
  * status per stream: 0 = ok; anything else = damaged or beyond this decoder (its output is then
  * all zeros): the caller decodes that stream on the host if it wants the verdict of zlib itself.
  * The compressed buffer must be readable for 64 bytes beyond its end (the decoder fetches ahead).
  * Output regions must not overlap; out_offset must be even (samples are int16). */
 #define DBH_INFLATE_ZLIB 0
 #define DBH_INFLATE_STORED 1
+#define DBH_INFLATE_VBZ 2
 typedef struct dbh_inflate_stream {
     int64_t comp_offset, comp_bytes;       /* the stream inside the compressed buffer           */
     int64_t out_offset, out_bytes;         /* its output inside the output buffer (bytes)       */
