@@ -169,6 +169,7 @@ def load_trained_model(model_file, out_dest=None):
         weights, _ = ModelWeights.load(str(model_file))
     except Exception:       # whatever a damaged or foreign file trips inside the readers
         sys.exit(invalid)
+    check_model_geometry(weights.input_size, weights.n_classes)
     model = build_model(weights)
     print('done', file=out_dest)
     # the shape contract of seam b1: one input (None, L, 1) with L > 10, one output (None, C)
@@ -178,10 +179,6 @@ def load_trained_model(model_file, out_dest=None):
     out_shape = tuple(model.outputs[0].shape)
     if len(out_shape) < 2:
         sys.exit(invalid)
-    if hasattr(model, 'classify_packed') and int(shapes[0][1]) != MODEL_INPUT_SIZE:
-        # the loaders keep scanned_end_samples() of each read end, sized for this input length
-        sys.exit('Error: model input size {} is not supported (the loaders and the device library '
-                 'are built for {})'.format(int(shapes[0][1]), MODEL_INPUT_SIZE))
     return model, int(shapes[0][1]), int(out_shape[1])
 
 
@@ -228,7 +225,8 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
     replicas = device_replicas(start_model, end_model)
     host_share = raw_inflate_share(start_model, end_model, args, len(fast5_files), replicas)
     if host_share is None:
-        batches = load_in_batches(fast5_files, args)
+        batches = load_in_batches(fast5_files, args,
+                                  scanned_end_samples(args.scan_size, start_input_size, end_input_size))
     else:
         # Signals as stored, inflated on the GPU beside the classification of the batch before:
         # several batches in flight per GPU, each on a replica of the models
@@ -251,15 +249,42 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
     return classifications, read_id_to_fast5_file
 
 
-MODEL_INPUT_SIZE = 1024        # every shipped model; dbh_model_create refuses anything else
+MODEL_INPUT_SIZE = 1024        # every shipped model (and the persistent forward kernel's size)
+# the geometry the device library takes (dbh_model_create_ex): other sizes and class counts than
+# the shipped models' run on its general forward path
+MIN_INPUT_SIZE, MAX_INPUT_SIZE = 96, 16384
+MIN_CLASSES, MAX_CLASSES = 2, 256
 
 
-def scanned_end_samples(scan_size, input_size=MODEL_INPUT_SIZE):
+def check_model_geometry(input_size, n_classes):
+    """Refuse, before anything is built on a device, a model the device library cannot run: an
+    odd input size (the reference's own message, classify.py:396-407), one below 96 samples (the
+    network's global average would have no position left) or above 16,384, or a class count
+    outside 2 .. 256."""
+    if input_size % 2:
+        sys.exit('Error: the model input size must be even (currently {})'.format(input_size))
+    if not MIN_INPUT_SIZE <= input_size <= MAX_INPUT_SIZE:
+        sys.exit('Error: model input size {} is not supported (input sizes from {} to {} samples '
+                 'are)'.format(input_size, MIN_INPUT_SIZE, MAX_INPUT_SIZE))
+    if not MIN_CLASSES <= n_classes <= MAX_CLASSES:
+        sys.exit('Error: a model with {} classes is not supported (from {} to {} classes '
+                 'are)'.format(n_classes, MIN_CLASSES, MAX_CLASSES))
+
+
+def scanned_end_samples(scan_size, input_size=MODEL_INPUT_SIZE, end_input_size=None):
     """Samples at either end of a read that some window can touch: the loaders may drop the
     middle of longer reads.  Windows start every input_size // 2 samples up to scan_size and are
-    input_size long (reference classify.py:330-349).  The loaders run before any model object is
-    in reach, hence the constant - which is also what the device library insists on."""
-    return int(scan_size) + input_size // 2
+    input_size long (reference classify.py:330-349).  With two models (start and end) of
+    different input sizes, the larger one decides; None stands for a side without a model."""
+    sizes = [s for s in (input_size, end_input_size) if s is not None]
+    return int(scan_size) + max(sizes or [MODEL_INPUT_SIZE]) // 2
+
+
+def models_input_size(start_model, end_model):
+    """The larger input size of the (one or two) loaded models, for scanned_end_samples."""
+    sizes = [int(getattr(m, 'input_size', MODEL_INPUT_SIZE))
+             for m in (start_model, end_model) if m is not None]
+    return max(sizes or [MODEL_INPUT_SIZE])
 
 
 RAW_CLASSIFY_MIN_FILES = 8192       # below that the CPU loader is done before a pipeline fills
@@ -341,7 +366,8 @@ def _classify_raw_batch(batch, start_replica, end_replica, args):
     redone = {}           # read index -> its verbose row, for reads the host had to decode
     for i in sorted(set(batch.records['read'][stream_status != 0].tolist())):
         ids, samples, offsets, status = fast5_native.load_batch(
-            [batch.files[i]], scanned_end_samples(args.scan_size), 1)
+            [batch.files[i]], scanned_end_samples(args.scan_size,
+                                                  models_input_size(start_replica, end_replica)), 1)
         if status[0] != 0:
             read_ids[i] = None
             continue
@@ -380,13 +406,17 @@ def _classify_raw_batch(batch, start_replica, end_replica, args):
     return files, calls, lines
 
 
-def load_in_batches(fast5_files, args):
+def load_in_batches(fast5_files, args, keep=None):
     """The reference's ``for fast5_batch in chunker(...)`` + per-file load (classify.py:141-150):
     yields, per batch of ``args.batch_size`` files, the list of (fast5_file, read_id, signal).
     With more than one loader process (``--loader_procs``, or automatically for big jobs) the
-    files of later batches are loaded while the caller classifies the current one."""
+    files of later batches are loaded while the caller classifies the current one.  ``keep``:
+    samples per read end the loaders keep (scanned_end_samples of the models; None = what
+    1024-sample models need)."""
+    if keep is None:
+        keep = scanned_end_samples(args.scan_size)
     if reader_kind() == 'native':
-        yield from _native_batches(fast5_files, args)
+        yield from _native_batches(fast5_files, args, keep)
         return
     procs = choose_loader_procs(getattr(args, 'loader_procs', None), len(fast5_files))
     if procs <= 1:
@@ -394,7 +424,6 @@ def load_in_batches(fast5_files, args):
             yield [(f,) + tuple(get_read_id_and_signal(f)) for f in fast5_batch]
         return
     # only the scanned ends of a read matter to call_batch: spare the result pipe the middle
-    keep = scanned_end_samples(args.scan_size)
     with LoaderPool(procs) as pool:
         batch = []
         for item in pool.load(list(fast5_files), keep):
@@ -406,14 +435,13 @@ def load_in_batches(fast5_files, args):
             yield batch
 
 
-def _native_batches(fast5_files, args):
+def _native_batches(fast5_files, args, keep):
     """load_in_batches on the native loader (libdeepbinner_fast5.so): every batch is parsed and
     inflated by the library's own worker threads (``--loader_procs`` of them; 0 = one per hardware
     thread this process may keep busy - misc.usable_cpus - at most 32), and the next batch is loaded on a background thread - the
     call releases the GIL - while the caller classifies the current one."""
     from concurrent.futures import ThreadPoolExecutor
     from . import fast5_native
-    keep = scanned_end_samples(args.scan_size)
     threads = int(getattr(args, 'loader_procs', 0) or 0) or max(1, min(32, usable_cpus()))
     batches = list(chunker(fast5_files, args.batch_size))
 

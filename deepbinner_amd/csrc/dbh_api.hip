@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_general.h"
 #define DBH_FORWARD_NS dbh
 #define DBH_TIMELINE 0
 #include "dbh_forward.hip"
@@ -173,6 +174,9 @@ void pack_weights(const float* w, int n_classes, std::vector<float>& packed) {
 
 struct dbh_model {
     int n_classes = 0;
+    int input_size = dbh::kWindow;
+    int kind = DBH_MODEL_KIND_PERSISTENT;   // DBH_MODEL_KIND_GENERAL: dbh_general.hip runs it
+    dbh_gen::Net gen;                       // ... with these weights
     int device = 0;
     int cus = 256;               // workgroups of a persistent forward launch (one per CU)
     int cus_total = 256;         // ... before dbh_model_reserve_cus took some away
@@ -242,6 +246,8 @@ struct dbh_model {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
     int64_t timed_windows = 0;
+    // activations of the general path's dbh_predict_dev / dbh_predict, per stream (like `tails`)
+    std::vector<Tail> gen_scratch;
 };
 
 namespace {
@@ -288,6 +294,7 @@ int ensure_host(void** ptr, size_t* have, size_t need) {
 int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev,
                    int debug_stage, float* debug_dev, hipStream_t stream,
                    const FusedInput& in = FusedInput()) {
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;   // (introspection)
     if (n == 0) return DBH_OK;
     // grid.x limit is 2^31-1 blocks; chunk anyway to keep launches bounded
     const int64_t kChunk = (int64_t)(1 << 20) * in.steps;   // whole reads per launch
@@ -389,6 +396,38 @@ int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev
 }
 
 inline int steps_for(int scan_size) { return scan_size / (dbh::kWindow / 2); }
+
+// scan steps of a model (classify.py:330-331: windows every input_size / 2 samples), 0 when
+// scan_size is not a positive multiple of that (check_input_size, classify.py:396-407)
+inline int model_steps(const dbh_model* m, int scan_size) {
+    const int half = m->input_size / 2;
+    const int steps = scan_size / half;
+    return (steps > 0 && steps * half == scan_size) ? steps : 0;
+}
+
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// the general path's share of dbh_classify_workspace_bytes: per-window probabilities, then the
+// activations of one chunk
+size_t general_workspace(const dbh_model* m, int64_t n_reads, int steps) {
+    const int64_t windows = n_reads * steps;
+    return align256((size_t)windows * m->n_classes * sizeof(float)) +
+           dbh_gen::activation_bytes(m->gen, windows);
+}
+
+// dbh_predict(_dev) on a general model: activations in a per-stream buffer of the model
+int general_predict(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev,
+                    hipStream_t stream) {
+    if (n == 0) return DBH_OK;
+    size_t k = 0;
+    while (k < m->gen_scratch.size() && m->gen_scratch[k].stream != stream) ++k;
+    if (k == m->gen_scratch.size()) m->gen_scratch.push_back(dbh_model::Tail{stream, nullptr, 0});
+    dbh_model::Tail& sc = m->gen_scratch[k];
+    const int st = ensure(&sc.ptr, &sc.bytes, dbh_gen::activation_bytes(m->gen, n));
+    if (st != DBH_OK) return st;
+    DBH_HIP(dbh_gen::forward(m->gen, x_dev, nullptr, nullptr, 1, 0, n, probs_dev, sc.ptr, stream));
+    return DBH_OK;
+}
 
 }  // namespace
 
@@ -598,8 +637,43 @@ int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int 
     return DBH_OK;
 }
 
+int dbh_model_create_ex(const float* weights, int64_t n_floats, int n_classes, int input_size,
+                        unsigned flags, dbh_model** model) {
+    if (!weights || !model || flags > DBH_MODEL_GENERAL) return DBH_ERR_INVALID_ARGUMENT;
+    *model = nullptr;
+    if (!dbh_gen::geometry_ok(input_size, n_classes)) return DBH_ERR_UNSUPPORTED;
+    if (n_floats != canon_param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
+    if (flags == DBH_MODEL_AUTO && input_size == dbh::kWindow && n_classes <= dbh::kMaxClasses)
+        return dbh_model_create(weights, n_floats, n_classes, input_size, model);
+    int count = 0;
+    int st = dbh_device_count(&count);
+    if (st != DBH_OK) return st;
+    dbh_model* m = new (std::nothrow) dbh_model();
+    if (!m) return DBH_ERR_OUT_OF_MEMORY;
+    m->n_classes = n_classes;
+    m->input_size = input_size;
+    m->kind = DBH_MODEL_KIND_GENERAL;
+    hipError_t e = hipGetDevice(&m->device);
+    if (e == hipSuccess) e = dbh_gen::create(weights, n_classes, input_size, &m->gen);
+    if (e != hipSuccess) {
+        delete m;
+        return hip_fail(e, "dbh_model_create_ex");
+    }
+    *model = m;
+    return DBH_OK;
+}
+
+int dbh_model_kind(const dbh_model* m, int* kind) {
+    if (!m || !kind) return DBH_ERR_INVALID_ARGUMENT;
+    *kind = m->kind;
+    return DBH_OK;
+}
+
 int dbh_model_destroy(dbh_model* m) {
     if (!m) return DBH_OK;
+    dbh_gen::destroy(&m->gen);
+    for (auto& t : m->gen_scratch)
+        if (t.ptr) (void)hipFree(t.ptr);
     if (m->d_packed) (void)hipFree(m->d_packed);
     if (m->d_in) (void)hipFree(m->d_in);
     if (m->d_work) (void)hipFree(m->d_work);
@@ -637,7 +711,7 @@ int dbh_model_destroy(dbh_model* m) {
 
 int dbh_model_input_size(const dbh_model* m, int* input_size) {
     if (!m || !input_size) return DBH_ERR_INVALID_ARGUMENT;
-    *input_size = dbh::kWindow;
+    *input_size = m->input_size;
     return DBH_OK;
 }
 int dbh_model_output_size(const dbh_model* m, int* n_classes) {
@@ -649,6 +723,8 @@ int dbh_model_output_size(const dbh_model* m, int* n_classes) {
 int dbh_predict_dev(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev,
                     dbh_stream stream) {
     if (!m || n < 0 || (n > 0 && (!x_dev || !probs_dev))) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind == DBH_MODEL_KIND_GENERAL)
+        return general_predict(m, x_dev, n, probs_dev, (hipStream_t)stream);
     return launch_forward(m, x_dev, n, probs_dev, -1, nullptr, (hipStream_t)stream);
 }
 
@@ -656,18 +732,21 @@ int dbh_predict(dbh_model* m, const float* x_host, int64_t n, float* probs_host)
     if (!m || n < 0 || (n > 0 && (!x_host || !probs_host))) return DBH_ERR_INVALID_ARGUMENT;
     if (n == 0) return DBH_OK;
     DBH_HIP(hipSetDevice(m->device));      // (see dbh_classify_i16)
-    // bounded staging: 65,536 windows (256 MiB of fp32 input) per round trip
-    const int64_t kChunk = 65536;
+    // bounded staging: 65,536 windows of 1,024 samples (256 MiB of fp32 input) per round trip
+    const int64_t L = m->input_size;
+    const int64_t kChunk = 65536 * dbh::kWindow / L;
     const int64_t cap = n < kChunk ? n : kChunk;
-    int st = ensure(&m->d_in, &m->in_bytes, (size_t)cap * dbh::kWindow * sizeof(float));
+    int st = ensure(&m->d_in, &m->in_bytes, (size_t)(cap * L) * sizeof(float));
     if (st != DBH_OK) return st;
     st = ensure(&m->d_out, &m->out_bytes, (size_t)cap * m->n_classes * sizeof(float));
     if (st != DBH_OK) return st;
     for (int64_t off = 0; off < n; off += kChunk) {
         const int64_t cnt = (n - off < kChunk) ? (n - off) : kChunk;
-        DBH_HIP(hipMemcpyAsync(m->d_in, x_host + off * dbh::kWindow,
-                               (size_t)cnt * dbh::kWindow * sizeof(float), hipMemcpyHostToDevice, 0));
-        st = launch_forward(m, (const float*)m->d_in, cnt, (float*)m->d_out, -1, nullptr, 0);
+        DBH_HIP(hipMemcpyAsync(m->d_in, x_host + off * L, (size_t)(cnt * L) * sizeof(float),
+                               hipMemcpyHostToDevice, 0));
+        st = m->kind == DBH_MODEL_KIND_GENERAL
+                 ? general_predict(m, (const float*)m->d_in, cnt, (float*)m->d_out, 0)
+                 : launch_forward(m, (const float*)m->d_in, cnt, (float*)m->d_out, -1, nullptr, 0);
         if (st != DBH_OK) return st;
         DBH_HIP(hipMemcpyAsync(probs_host + off * m->n_classes, m->d_out,
                                (size_t)cnt * m->n_classes * sizeof(float), hipMemcpyDeviceToHost, 0));
@@ -746,8 +825,12 @@ int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_cal
 int dbh_classify_workspace_bytes(const dbh_model* m, int64_t n_reads, int scan_size,
                                  size_t* bytes) {
     if (!m || !bytes || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
-    const int steps = steps_for(scan_size);
-    if (steps <= 0 || steps * (dbh::kWindow / 2) != scan_size) return DBH_ERR_INVALID_ARGUMENT;
+    const int steps = model_steps(m, scan_size);
+    if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind == DBH_MODEL_KIND_GENERAL) {
+        *bytes = general_workspace(m, n_reads, steps);
+        return DBH_OK;
+    }
     // the per-window probabilities the merge kernel reads; one scan step needs nothing (the
     // forward kernel finishes the read itself), and the windows themselves never leave LDS
     const size_t windows = (size_t)n_reads * steps;
@@ -765,11 +848,21 @@ int classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* of
                      size_t* tail_bytes = nullptr) {
     if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
-    const int steps = steps_for(scan_size);
-    if (steps <= 0 || steps * (dbh::kWindow / 2) != scan_size ||
-        (side != DBH_SIDE_START && side != DBH_SIDE_END) || !samples_dev || !offsets_dev ||
-        !probs_dev || !calls_dev)
+    const int steps = model_steps(m, scan_size);
+    if (steps <= 0 || (side != DBH_SIDE_START && side != DBH_SIDE_END) || !samples_dev ||
+        !offsets_dev || !probs_dev || !calls_dev)
         return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind == DBH_MODEL_KIND_GENERAL) {
+        // every window's probabilities to the workspace, then the merge (any steps, C <= 256)
+        if (!workspace_dev) return DBH_ERR_INVALID_ARGUMENT;
+        float* wprobs = (float*)workspace_dev;
+        void* act = (char*)workspace_dev + align256((size_t)(n_reads * steps) * m->n_classes * sizeof(float));
+        DBH_HIP(dbh_gen::forward(m->gen, nullptr, samples_dev, offsets_dev, steps, side,
+                                 n_reads * steps, wprobs, act, (hipStream_t)stream));
+        DBH_HIP(dbh_gen::merge(wprobs, n_reads, steps, m->n_classes, score_diff, probs_dev,
+                               calls_dev, (hipStream_t)stream));
+        return DBH_OK;
+    }
     FusedInput in;
     in.samples = samples_dev;
     in.offsets = offsets_dev;
@@ -802,6 +895,7 @@ extern "C" {
 
 int dbh_model_set_read_length_hint(dbh_model* m, int64_t read_length, int64_t capacity_samples) {
     if (!m || read_length < 0 || capacity_samples < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_OK;       // (nothing to tune)
     m->hint_len = read_length;
     m->hint_cap = read_length > 0 ? capacity_samples : 0;
     return DBH_OK;
@@ -829,10 +923,13 @@ int dbh_classify_i16_batched_dev(dbh_model* m, const int16_t* samples_dev,
     // through ONE launch without a boundary between them (DEEPBINNER_LAUNCH_PER_BATCH=1 brings
     // the launch per batch back, for comparison).  Reads with several scan steps go in chunks
     // whose per-window probabilities fit a bounded workspace, one merge launch per chunk.
-    const int steps = steps_for(scan_size);
+    const int steps = model_steps(m, scan_size);
     if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
-    const int64_t chunk = m->launch_per_batch ? (int64_t)batch_size
-                                              : (steps == 1 ? n_reads : ((int64_t)1 << 20) / steps);
+    // (a general model goes 65,536 windows at a time: its workspace holds them all, C up to 256)
+    const int64_t chunk = m->kind == DBH_MODEL_KIND_GENERAL
+                              ? std::max<int64_t>(1, 65536 / steps)
+                              : m->launch_per_batch ? (int64_t)batch_size
+                                                    : (steps == 1 ? n_reads : ((int64_t)1 << 20) / steps);
     size_t work = 0;
     int st = dbh_classify_workspace_bytes(m, chunk < n_reads ? chunk : n_reads, scan_size, &work);
     if (st != DBH_OK) return st;
@@ -909,8 +1006,13 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
     if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
     if (!offsets_host) return DBH_ERR_INVALID_ARGUMENT;
-    const int steps = steps_for(scan_size);
-    if (steps <= 0 || steps * (dbh::kWindow / 2) != scan_size) return DBH_ERR_INVALID_ARGUMENT;
+    int steps = 0;          // the larger of the models' (they may differ in input size)
+    for (dbh_model* mj : job.model) {
+        if (!mj) continue;
+        const int s = model_steps(mj, scan_size);
+        if (s <= 0) return DBH_ERR_INVALID_ARGUMENT;
+        steps = std::max(steps, s);
+    }
     const bool both = job.model[0] && job.model[1];
     if (both && (job.model[0]->device != job.model[1]->device ||
                  job.model[0]->n_classes != job.model[1]->n_classes))
@@ -924,7 +1026,8 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
     if (total_samples < 0 || (total_samples > 0 && !samples_host)) return DBH_ERR_INVALID_ARGUMENT;
     const bool pinned = total_samples > 0 &&
                         is_pinned(samples_host + offsets_host[0], (size_t)total_samples * 2);
-    const int64_t group = std::max<int64_t>(1, m->host_group_windows / steps);
+    const int64_t group = std::max<int64_t>(
+        1, (m->kind == DBH_MODEL_KIND_GENERAL ? dbh_model::kDefaultGroup : m->host_group_windows) / steps);
     constexpr int kSlots = dbh_model::kSlots;
     struct Pending { int64_t r0 = 0, cnt = 0; bool live = false; } pending[kSlots];
     // what comes back per read of a group, in this order
@@ -988,7 +1091,11 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
         size_t out_off[5];
         const size_t out_bytes = out_layout(cnt, out_off);
         size_t work = 0;
-        st = dbh_classify_workspace_bytes(m, cnt, scan_size, &work);
+        for (dbh_model* mj : job.model) {
+            size_t wj = 0;
+            if (mj && st == DBH_OK) st = dbh_classify_workspace_bytes(mj, cnt, scan_size, &wj);
+            work = std::max(work, wj);
+        }
         // host side: the relative offsets always, the samples only when they have to be staged
         if (st == DBH_OK)
             st = ensure_host(&sl.h_in, &sl.h_in_bytes, off_bytes + (pinned ? 0 : sample_bytes));
@@ -1166,8 +1273,8 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
     if (both && (start_model->device != end_model->device ||
                  start_model->n_classes != end_model->n_classes))
         return DBH_ERR_INVALID_ARGUMENT;
-    const int steps = steps_for(scan_size);
-    if (steps <= 0 || steps * (dbh::kWindow / 2) != scan_size) return DBH_ERR_INVALID_ARGUMENT;
+    for (dbh_model* mj : {start_model, end_model})
+        if (mj && model_steps(mj, scan_size) <= 0) return DBH_ERR_INVALID_ARGUMENT;
     const int64_t total_samples = offsets_host[n_reads] - offsets_host[0];
     if (offsets_host[0] != 0 || total_samples < 0) return DBH_ERR_INVALID_ARGUMENT;
     const int64_t out_bytes = total_samples * 2;
@@ -1192,7 +1299,11 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
     const size_t probs_bytes = (size_t)n_reads * C * sizeof(float);
     size_t token_bytes = 0, work = 0;
     int st = dbh_inflate_workspace_bytes(out_bytes, n_streams, &token_bytes);
-    if (st == DBH_OK) st = dbh_classify_workspace_bytes(m, n_reads, scan_size, &work);
+    for (dbh_model* mj : {start_model, end_model}) {
+        size_t wj = 0;
+        if (mj && st == DBH_OK) st = dbh_classify_workspace_bytes(mj, n_reads, scan_size, &wj);
+        work = std::max(work, wj);
+    }
     if (st == DBH_OK) st = ensure_host(&d.h_small, &d.h_small_bytes, in_small + out_small);
     if (st == DBH_OK) st = ensure(&d.d_small, &d.d_small_bytes, in_small + out_small);
     if (st == DBH_OK) st = ensure(&d.d_comp, &d.d_comp_bytes, (size_t)comp_bytes + 64);
@@ -1409,12 +1520,14 @@ int dbh_host_is_pinned(const void* ptr, size_t bytes, int* pinned) {
 
 int dbh_model_set_host_group(dbh_model* m, int64_t windows_per_group) {
     if (!m || windows_per_group < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_OK;       // (nothing to tune)
     m->host_group_windows = windows_per_group > 0 ? windows_per_group : dbh_model::kDefaultGroup;
     return DBH_OK;
 }
 
 int dbh_model_reserve_cus(dbh_model* m, int n_cus) {
     if (!m || n_cus < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_OK;       // (nothing to tune)
     m->cus = m->cus_total - n_cus > 1 ? m->cus_total - n_cus : 1;
     return DBH_OK;
 }
@@ -1428,6 +1541,7 @@ int dbh_stage_floats(int stage, int64_t* floats_per_window) {
 int dbh_debug_forward(dbh_model* m, const float* x_host, int64_t n, int stage, float* out_host) {
     if (!m || n <= 0 || !x_host || !out_host || stage < 0 || stage > 7)
         return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     const size_t per = (size_t)dbh::kStageFloats[stage];
     int st = ensure(&m->d_in, &m->in_bytes, (size_t)n * dbh::kWindow * sizeof(float));
     if (st != DBH_OK) return st;
@@ -1465,11 +1579,13 @@ int dbh_forward_executed_mfmas(int n_classes, int64_t* mfmas_per_window,
 int dbh_forward_truncated_dev(dbh_model* m, const float* x_dev, int64_t n, int last_stage,
                               dbh_stream stream) {
     if (!m || n <= 0 || !x_dev || last_stage < 0 || last_stage > 6) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     return launch_forward(m, x_dev, n, nullptr, 100 + last_stage, nullptr, (hipStream_t)stream);
 }
 
 int dbh_forward_timeline(dbh_model* m, const float* x_host, int64_t n, int64_t* stamps_host) {
     if (!m || n <= 0 || !x_host || !stamps_host) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     const size_t stamp_bytes = (size_t)n * dbh::kWaves * 64 * sizeof(int64_t);
     int st = ensure(&m->d_in, &m->in_bytes, (size_t)n * dbh::kWindow * sizeof(float));
     if (st != DBH_OK) return st;
@@ -1506,6 +1622,7 @@ int dbh_forward_timeline(dbh_model* m, const float* x_host, int64_t n, int64_t* 
 int dbh_forward_timeline_i16(dbh_model* m, const int16_t* samples_host, int64_t n,
                              int64_t* stamps_host) {
     if (!m || n <= 0 || !samples_host || !stamps_host) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     const size_t stamp_bytes = (size_t)n * dbh::kWaves * 64 * sizeof(int64_t);
     const size_t sample_bytes = (size_t)n * dbh::kWindow * sizeof(int16_t);
     const size_t offset_bytes = (size_t)(n + 1) * sizeof(int64_t);
@@ -1554,6 +1671,7 @@ int dbh_forward_timeline_i16(dbh_model* m, const int16_t* samples_host, int64_t 
 
 int dbh_forward_timing_enable_span(dbh_model* m, int every_nth, int span) {
     if (!m || span < 1 || (every_nth > 0 && span > every_nth)) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     m->timing = every_nth > 0 ? every_nth : 0;
     m->timing_span = span;
     m->open_stop = nullptr;
@@ -1566,11 +1684,14 @@ int dbh_forward_timing_enable_span(dbh_model* m, int every_nth, int span) {
 }
 
 int dbh_forward_timing_enable(dbh_model* m, int enable) {
+    if (!m) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     return dbh_forward_timing_enable_span(m, enable, 1);
 }
 
 int dbh_forward_timing_read(dbh_model* m, double* total_ms, int64_t* launches, int64_t* windows) {
     if (!m || !total_ms || !launches || !windows) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     double sum = 0.0;
     for (size_t i = 0; i < m->events_used; ++i) {
         DBH_HIP(hipEventSynchronize(m->events[i].second));
@@ -1590,6 +1711,7 @@ int dbh_forward_timing_read(dbh_model* m, double* total_ms, int64_t* launches, i
 
 int dbh_forward_clock_enable(dbh_model* m, int enable) {
     if (!m) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     m->clock_probe = enable != 0;
     if (!enable) m->clock_grid = 0;
     return DBH_OK;
@@ -1597,6 +1719,7 @@ int dbh_forward_clock_enable(dbh_model* m, int enable) {
 
 int dbh_forward_clock_read(dbh_model* m, double* shader_ghz) {
     if (!m || !shader_ghz) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     *shader_ghz = 0.0;
     if (!m->clock_probe || m->clock_grid == 0 || !m->d_clock) return DBH_ERR_INVALID_ARGUMENT;
     DBH_HIP(hipSetDevice(m->device));
@@ -1621,12 +1744,14 @@ int dbh_forward_clock_read(dbh_model* m, double* shader_ghz) {
 
 int dbh_forward_phases_enable(dbh_model* m, int enable) {
     if (!m) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     m->phase_probe = enable != 0;
     return DBH_OK;
 }
 
 int dbh_forward_phases_read(dbh_model* m, double* mean_cycles, int64_t* groups) {
     if (!m || !mean_cycles || !groups) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     if (!m->clock_probe || !m->phase_probe || m->clock_grid == 0 || !m->d_clock) return DBH_ERR_INVALID_ARGUMENT;
     DBH_HIP(hipSetDevice(m->device));
     DBH_HIP(hipDeviceSynchronize());

@@ -96,6 +96,8 @@ def load_library():
         'dbh_stream_wait_event': (c_int, [c_void_p, c_void_p]),
         'dbh_event_elapsed_ms': (c_int, [c_void_p, c_void_p, P(ctypes.c_float)]),
         'dbh_model_create': (c_int, [_f32(), c_i64, c_int, c_int, P(c_void_p)]),
+        'dbh_model_create_ex': (c_int, [_f32(), c_i64, c_int, c_int, ctypes.c_uint, P(c_void_p)]),
+        'dbh_model_kind': (c_int, [c_void_p, P(c_int)]),
         'dbh_model_destroy': (c_int, [c_void_p]),
         'dbh_model_input_size': (c_int, [c_void_p, P(c_int)]),
         'dbh_model_output_size': (c_int, [c_void_p, P(c_int)]),
@@ -180,7 +182,7 @@ EXPORTED_SYMBOLS = [
     'dbh_stream_create', 'dbh_stream_destroy', 'dbh_stream_synchronize', 'dbh_event_create',
     'dbh_event_destroy', 'dbh_event_record', 'dbh_event_synchronize', 'dbh_stream_wait_event',
     'dbh_event_elapsed_ms',
-    'dbh_model_create', 'dbh_model_destroy', 'dbh_model_set_read_length_hint', 'dbh_model_input_size', 'dbh_model_output_size',
+    'dbh_model_create', 'dbh_model_create_ex', 'dbh_model_kind', 'dbh_model_destroy', 'dbh_model_set_read_length_hint', 'dbh_model_input_size', 'dbh_model_output_size',
     'dbh_predict', 'dbh_predict_dev', 'dbh_classify_i16', 'dbh_classify_pair_i16',
     'dbh_model_set_host_group', 'dbh_model_reserve_cus', 'dbh_host_device_pointer',
     'dbh_host_alloc', 'dbh_host_release',
@@ -488,10 +490,18 @@ class _TensorSpec:
         self.shape = tuple(shape)
 
 
-class HipModel:
-    """A trained Deepbinner model resident on one MI355X."""
+MODEL_AUTO, MODEL_GENERAL = 0, 1                 # dbh_model_create_ex flags
+KIND_PERSISTENT, KIND_GENERAL = 0, 1             # dbh_model_kind
+MIN_INPUT_SIZE, MAX_INPUT_SIZE = 96, 16384       # the geometry dbh_model_create_ex takes
+MIN_CLASSES, MAX_CLASSES = 2, 256
 
-    def __init__(self, weights, device=None):
+
+class HipModel:
+    """A trained Deepbinner model resident on one MI355X.  Models of the shipped geometry (input
+    size 1024, at most 32 classes) run on the persistent forward kernel; any other supported
+    geometry - or ``general=True`` - on the general path (``kind``: KIND_PERSISTENT / KIND_GENERAL)."""
+
+    def __init__(self, weights, device=None, general=False):
         if not isinstance(weights, ModelWeights):
             raise TypeError('weights must be a ModelWeights')
         self._lib = load_library()
@@ -504,9 +514,14 @@ class HipModel:
         self.weights = weights
         flat = weights.flat()
         handle = ctypes.c_void_p()
-        check(self._lib.dbh_model_create(flat, flat.size, weights.n_classes, weights.input_size,
-                                         ctypes.byref(handle)), 'dbh_model_create')
+        check(self._lib.dbh_model_create_ex(flat, flat.size, weights.n_classes, weights.input_size,
+                                            MODEL_GENERAL if general else MODEL_AUTO,
+                                            ctypes.byref(handle)), 'dbh_model_create_ex')
         self._handle = handle
+        self.general = bool(general)
+        kind = ctypes.c_int(0)
+        check(self._lib.dbh_model_kind(handle, ctypes.byref(kind)), 'dbh_model_kind')
+        self.kind = kind.value
         self.n_classes = weights.n_classes
         self.input_size = weights.input_size
         self.inputs = [_TensorSpec((None, self.input_size, 1))]
@@ -535,7 +550,7 @@ class HipModel:
 
     # -- seam b1 ------------------------------------------------------------------------------
     def predict(self, x, batch_size=None, verbose=0):
-        """x: [N, 1024, 1] (or [N, 1024]) float -> float32 [N, n_classes], a fresh writable array.
+        """x: [N, L, 1] (or [N, L]) float -> float32 [N, n_classes], a fresh writable array.
         ``batch_size`` is accepted for signature compatibility; results do not depend on it."""
         x = np.asarray(x)
         if x.ndim == 3:
@@ -654,7 +669,7 @@ class HipModel:
     def clone(self):
         """The same weights as another model on the same GPU: its own streams and buffers - one
         more queue."""
-        return HipModel(self.weights, device=self.device)
+        return HipModel(self.weights, device=self.device, general=self.general)
 
     def set_read_length_hint(self, read_length, capacity_samples=0):
         """Tell the ``*_dev`` entry points that every read is ``read_length`` samples long (0

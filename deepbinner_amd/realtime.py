@@ -336,7 +336,8 @@ class Session:
     def _keep(self):
         """Samples per read end the loaders keep: only the scanned ends (all that call_batch
         looks at) unless the whole signals are needed."""
-        return None if self._signals_wanted() else classify.scanned_end_samples(self.args.scan_size)
+        return None if self._signals_wanted() else classify.scanned_end_samples(
+            self.args.scan_size, self.start_size, self.end_size)
 
     def _packed_containers(self, fast5s):
         """(container number, path, read ids, samples, offsets) per readable container, in order;

@@ -687,7 +687,11 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
     classifications, id_to_file, lines = {}, {}, []
 
     def classify_shard():
-        for loaded in c.load_in_batches(mine, args):
+        keep = c.scanned_end_samples(args.scan_size, start_input_size, end_input_size)
+        # (the loaders' default keep is that of 1024-sample models)
+        batches = (c.load_in_batches(mine, args) if keep == c.scanned_end_samples(args.scan_size)
+                   else c.load_in_batches(mine, args, keep))
+        for loaded in batches:
             read_ids, signals = [], []
             for fast5_file, read_id, signal in loaded:
                 if signal is None:

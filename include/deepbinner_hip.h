@@ -34,7 +34,8 @@ typedef enum {
     DBH_ERR_NO_DEVICE = 2,        /* no gfx950-capable HIP device visible */
     DBH_ERR_HIP = 3,              /* a HIP runtime call failed; see dbh_last_error() */
     DBH_ERR_BAD_WEIGHTS = 4,      /* blob size does not match the Deepbinner architecture */
-    DBH_ERR_UNSUPPORTED = 5,      /* e.g. input_size != 1024 or n_classes > 32 */
+    DBH_ERR_UNSUPPORTED = 5,      /* geometry outside the limits (dbh_model_create_ex), or a
+                                     persistent-kernel call on a general model */
     DBH_ERR_OUT_OF_MEMORY = 6,
     DBH_ERR_COMM = 7              /* RCCL missing or a collective failed; see dbh_comm_last_error() */
 } dbh_status;
@@ -90,6 +91,27 @@ int dbh_event_elapsed_ms(dbh_event start, dbh_event stop, float* ms);
  * n_floats must equal the architecture's parameter count for n_classes (107,197 for 13). */
 int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int input_size,
                      dbh_model** model);
+/* Any Deepbinner geometry the reference's own `train` writes: input_size L even, 96 <= L <= 16,384
+ * (classify.py:396-407 wants it even; the global average needs one position, so L >= 95), and
+ * 2 <= n_classes <= 256 (a 96-barcode kit gives 97).  flags: DBH_MODEL_AUTO runs the persistent
+ * forward kernel when L = 1024 and n_classes <= 32 (what dbh_model_create takes) and the GENERAL
+ * path otherwise - a layer-by-layer MFMA implicit GEMM over chunks of windows ("General
+ * models"); DBH_MODEL_GENERAL forces the general path (A/B runs, tests).  Same blob and n_floats
+ * check as dbh_model_create (DBH_ERR_BAD_WEIGHTS); a geometry outside the limits is
+ * DBH_ERR_UNSUPPORTED, both before any device work.
+ * A general model takes every network entry point (dbh_predict*, dbh_classify_*, the pair calls;
+ * scan_size must be a multiple of L/2 and gives scan_size / (L/2) steps); the two models of a pair
+ * call may differ in L and kind but not in n_classes.  The tuning calls (set_host_group,
+ * reserve_cus, set_read_length_hint) accept it and do nothing; the introspection calls of the
+ * persistent kernel (dbh_debug_forward, dbh_forward_truncated_dev, dbh_forward_timeline*,
+ * dbh_forward_timing_*, dbh_forward_clock_*, dbh_forward_phases_*) return DBH_ERR_UNSUPPORTED. */
+#define DBH_MODEL_AUTO 0
+#define DBH_MODEL_GENERAL 1
+#define DBH_MODEL_KIND_PERSISTENT 0
+#define DBH_MODEL_KIND_GENERAL 1
+int dbh_model_create_ex(const float* weights, int64_t n_floats, int n_classes, int input_size,
+                        unsigned flags, dbh_model** model);
+int dbh_model_kind(const dbh_model* model, int* kind);              /* DBH_MODEL_KIND_*             */
 int dbh_model_destroy(dbh_model* model);
 int dbh_model_input_size(const dbh_model* model, int* input_size);   /* model.inputs[0].shape[1], classify.py:93-96  */
 int dbh_model_output_size(const dbh_model* model, int* n_classes);   /* model.outputs[0].shape[1], classify.py:94-97 */
@@ -102,14 +124,14 @@ int dbh_model_output_size(const dbh_model* model, int* n_classes);   /* model.ou
  * on the device (the per-launch scratch is kept per stream), the host-side calls themselves must
  * still not overlap. */
 /* ---- seam b1: model.predict (classify.py:361) ------------------------------------------ */
-/* x: n_windows x 1024 fp32 (already normalised);  probs: n_windows x n_classes fp32 softmax. */
+/* x: n_windows x input_size fp32 (already normalised);  probs: n_windows x n_classes fp32 softmax. */
 int dbh_predict(dbh_model* model, const float* x_host, int64_t n_windows, float* probs_host);
 int dbh_predict_dev(dbh_model* model, const float* x_dev, int64_t n_windows, float* probs_dev,
                     dbh_stream stream);
 
 /* ---- seam b2: call_batch (classify.py:325-384) ------------------------------------------ */
 /* samples: concatenated int16 raw signals; offsets[n_reads+1] delimit each read (any length
- * >= 0).  For each read: scan_size/512 windows (classify.py:330-349), normalise
+ * >= 0).  For each read: scan_size/(input_size/2) windows (classify.py:330-349), normalise
  * (trim_signal.py:61-69, fp64), zero-pad (classify.py:352-357), forward pass, min/max merge
  * (classify.py:368-374), make_sum_to_one (classify.py:387-393) and the top-2 threshold call
  * (classify.py:285-295).  probs: n_reads x n_classes fp32; calls: n_reads int32, 0 = 'none'. */
@@ -161,7 +183,9 @@ int dbh_host_is_pinned(const void* ptr, size_t bytes, int* pinned);
 int dbh_model_set_read_length_hint(dbh_model* model, int64_t read_length,
                                    int64_t capacity_samples);
 /* device-resident variant; workspace_dev must hold dbh_classify_workspace_bytes() bytes (unused,
- * and may be NULL, when scan_size is 512: the whole read then finishes inside one launch). */
+ * and may be NULL, when scan_size is 512 on a persistent model: the whole read then finishes
+ * inside one launch; a general model always needs it - per-window probabilities and the
+ * activations of one chunk of windows). */
 int dbh_classify_workspace_bytes(const dbh_model* model, int64_t n_reads, int scan_size,
                                  size_t* bytes);
 int dbh_classify_i16_dev(dbh_model* model, const int16_t* samples_dev, const int64_t* offsets_dev,
