@@ -7,7 +7,7 @@ import zlib
 import numpy as np
 import pytest
 
-from general_fixtures import ENDS, STARTS, geometry, save
+from general_fixtures import ENDS, STARTS, geometry, golden_signals, save, synthetic_reads
 
 pytestmark = pytest.mark.gpu
 
@@ -28,21 +28,6 @@ def models(hip):
     yield get
     for m in out.values():
         m.close()
-
-
-def golden_signals():
-    from conftest import GOLD
-    reads = np.load(os.path.join(GOLD, 'reads.npz'))
-    offsets = reads['offsets']
-    return [reads['samples'][offsets[i]:offsets[i + 1]] for i in range(len(offsets) - 1)]
-
-
-def synthetic_reads(input_size, scan_size, seed):
-    """Lengths 0, below one window, about one window, and longer than twice the scan."""
-    rng = np.random.default_rng(seed)
-    lengths = [0, 1, input_size // 3, input_size - 1, input_size, input_size + 17,
-               scan_size + input_size // 2, 2 * scan_size + input_size + 5]
-    return [np.clip(rng.normal(500, 80, n), -32768, 32767).astype(np.int16) for n in lengths]
 
 
 def oracle_probs(weights, windows):
