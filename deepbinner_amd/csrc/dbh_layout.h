@@ -93,10 +93,13 @@ constexpr int conv_weight_floats(int i) {
 // kActScale = 2^-60: the input is scaled on the way in, biases and BN shifts are packed scaled,
 // the logits are scaled back before the softmax.  A power of two commutes with every fp32
 // rounding (nothing here comes near the subnormal range or overflow), so all values are exactly
-// 2^-60 times what they would be - and ReLU becomes the `clamp` output modifier ([0, 1]: no
-// activation of this network comes near 2^60 - the largest, before BN2, are ~1e8) of whatever instruction produces the value: the
-// output transforms of the Winograd layers end in a packed add or fma, and there is no packed
-// fp32 max in the ISA, so this takes a third of their epilogues' vector instructions away.
+// 2^-60 times what they would be - and ReLU becomes the `clamp` output modifier ([0, 1]) of
+// whatever instruction produces the value.  THE LIMIT this puts on a model: every activation must
+// stay below 2^60 (a larger one is cut to 2^60 without an error).  The shipped models' largest,
+// before BN2, are ~1e8 = 2^27 on real reads; tests/test_gpu_weight_families.py runs a model
+// whose activations reach 2^54.  The general path (dbh_general.hip) has no such limit.
+// Why: the output transforms of the Winograd layers end in a packed add or fma, and there is no
+// packed fp32 max in the ISA, so this takes a third of their epilogues' vector instructions away.
 // ---------------------------------------------------------------------------------------------
 constexpr float kActScale = 1.f / 1152921504606846976.f;       // 2^-60
 constexpr float kActUnscale = 1152921504606846976.f;

@@ -88,7 +88,14 @@ int dbh_event_elapsed_ms(dbh_event start, dbh_event stop, float* ms);
 /* ---- model (replaces keras.models.load_model, classify.py:90) -------------------------- */
 /* weights: the canonical flat fp32 blob (deepbinner_amd/model_format.py): for conv 1..20
  * kernel[k][C_in][C_out] then bias[C_out]; for batch-norm 1..7 gamma, beta, mean, variance.
- * n_floats must equal the architecture's parameter count for n_classes (107,197 for 13). */
+ * n_floats must equal the architecture's parameter count for n_classes (107,197 for 13).
+ * RANGE: the persistent forward kernel this call uses holds activations times 2^-60 and takes its
+ * ReLU from a [0, 1] clamp, so every activation of the model (the output of every convolution and
+ * batch normalisation, on the windows it will see) must stay below 2^60 = 1.15e18; a larger one
+ * is cut to 2^60 without an error.  The shipped models reach 2^27 on real reads.  A model that
+ * may exceed the limit goes through dbh_model_create_ex with DBH_MODEL_GENERAL: the general path
+ * works in plain fp32 and has fp32's own range.  Batch-norm gammas of either sign and of zero are
+ * supported by both. */
 int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int input_size,
                      dbh_model** model);
 /* Any Deepbinner geometry the reference's own `train` writes: input_size L even, 96 <= L <= 16,384
