@@ -368,6 +368,7 @@ def _classify_raw_batch(batch, start_replica, end_replica, args):
         ids, samples, offsets, status = fast5_native.load_batch(
             [batch.files[i]], scanned_end_samples(args.scan_size,
                                                   models_input_size(start_replica, end_replica)), 1)
+        warn_about_filters(status)       # (damage only the GPU's VBZ self-checks could see)
         if status[0] != 0:
             read_ids[i] = None
             continue

@@ -416,6 +416,7 @@ class Session:
                                                                           threads=1)
             except OSError:
                 one_status = [1]
+            classify.warn_about_filters(np.asarray(one_status))
             if one_status[0] != 0:
                 ids[i] = None
                 continue

@@ -1,6 +1,8 @@
 """VBZ on the GPU: streams of mode DBH_INFLATE_VBZ through dbh_inflate beside zlib and stored
 streams, and VBZ raw batches through dbh_classify_pair_deflated(_verbose) and the raw stream of
-a 4,000-read container ("VBZ")."""
+a 4,000-read container ("VBZ"); and, end to end, reads whose damage or unusual encoding
+sits inside an intact zstd frame, with the GPU decoding and with the host decoding.  The decoder
+itself against its reference: tests/test_gpu_vbz_codes.py."""
 
 import os
 import struct
@@ -153,5 +155,161 @@ def test_a_vbz_container_streams_to_the_calls_of_its_deflate_twin(hip, tmp_path)
                        for i in range(0, 4000, 97))
             calls.append(got)
     assert np.array_equal(calls[0], calls[1])
+    start.close()
+    end.close()
+
+
+# ---- end to end: damage and unusual encodings INSIDE an intact zstd frame -----------------------
+def unusual_reads():
+    """[(read id, signal, encode or None)]: ordinary VBZ reads and, between them, 'damaged' (its
+    streamvbyte bytes a refused mutant of unchanged length - one control code changed - compressed
+    again, so that the zstd frame is intact and of a plausible size: only the streamvbyte
+    self-check can tell), 'forced' (every value on a 3- or 4-byte code) and 'unwrapped' (a
+    full-range signal, its deltas taken in 32 bits) -> (reads, {kind: read id})"""
+    import vbz_reference as ref
+    rng = np.random.default_rng(13)
+
+    def squiggle(n):
+        levels = np.repeat(rng.normal(450, 80, n // 8 + 1), 8)[:n]
+        return np.clip(np.rint(levels + rng.normal(0, 8, n)), 0, 2047).astype(np.int16)
+
+    def damaged(s):
+        good = struct.pack('<I', 2 * len(s)) + vf.streamvbyte(s)
+        mutant = bytearray(good)
+        i = len(s) // 3
+        ref.set_code(mutant, i, int(ref.code_lengths(good)[i]) % 4)      # (one byte longer, or 4 -> 1)
+        assert len(mutant) == len(good) and ref.decode(good) is not None
+        assert ref.decode(bytes(mutant)) is None
+        return bytes(mutant[:4]) + vf.zstd_compress(bytes(mutant[4:]))
+
+    def forced(s):
+        d = np.diff(np.concatenate([[0], s.astype(np.int64)]))
+        u = ((d << 1) ^ (d >> 63)).astype(np.uint32)
+        payload = struct.pack('<I', 2 * len(s)) + vf.pack_values(u, rng.integers(3, 5, len(s)))
+        assert set(ref.code_lengths(payload).tolist()) == {3, 4}
+        assert np.array_equal(ref.decode(payload), s)
+        return payload[:4] + vf.zstd_compress(payload[4:])
+
+    def unwrapped(s):
+        chunk = vf.vbz_chunk(s, 1, wrap=False)
+        assert (ref.code_lengths(struct.pack('<I', 2 * len(s)) + vf.streamvbyte(s, wrap=False)) == 3).any()
+        return chunk
+
+    kinds = [None, None, damaged, None, forced, None, unwrapped, None]
+    reads, special = [], {}
+    for encode in kinds:
+        n = int(rng.integers(3000, 9000))
+        signal = rng.integers(-32768, 32768, n).astype(np.int16) if encode is unwrapped else squiggle(n)
+        rid = str(uuid.UUID(bytes=rng.bytes(16), version=4))
+        reads.append((rid, signal, encode))
+        if encode is not None:
+            special[encode.__name__] = rid
+    return reads, special
+
+
+def write_unusual(tmp_path, reads):
+    """the reads as a VBZ container, as a directory of one-read VBZ files, and the deflate twins
+    of both -> {'multi': dir, 'multi_twin': dir, 'single': dir, 'single_twin': dir}"""
+    from deepbinner_amd import hdf5_write
+    dirs = {}
+    for name in ('multi', 'multi_twin', 'single', 'single_twin'):
+        dirs[name] = tmp_path / name
+        dirs[name].mkdir()
+    filters = [vf.signal_filter(s, encode=encode) for _, s, encode in reads]
+    (dirs['multi'] / 'reads.fast5').write_bytes(hdf5_write.multi_read_fast5_bytes(
+        [(rid, s, None, None, sf) for (rid, s, _), sf in zip(reads, filters)]))
+    (dirs['multi_twin'] / 'reads.fast5').write_bytes(hdf5_write.multi_read_fast5_bytes(
+        [(rid, s) for rid, s, _ in reads]))
+    for (rid, s, _), sf in zip(reads, filters):
+        (dirs['single'] / (rid + '.fast5')).write_bytes(
+            hdf5_write.single_read_fast5_bytes(rid, s, signal_filter=sf))
+        (dirs['single_twin'] / (rid + '.fast5')).write_bytes(hdf5_write.single_read_fast5_bytes(rid, s))
+    return {k: str(v) for k, v in dirs.items()}
+
+
+FILTER_WARNING = 'Warning: skipping reads whose signal is compressed with a filter'
+
+
+def test_damage_inside_an_intact_zstd_frame_end_to_end(hip, tmp_path, monkeypatch, capsys):
+    """`classify --native` over one-read files and `realtime` over a container, with the GPU
+    decoding the streams and with the host decoding them: the same table; the damaged read skipped
+    with the filter warning either way; the reads with forced long codes and with unwrapped deltas
+    called as their deflate twins are."""
+    import contextlib
+    import io
+    from deepbinner_amd import classify, deepbinner as cli
+    from test_gpu_streaming import run_realtime
+    reads, special = unusual_reads()
+    assert set(special) == {'damaged', 'forced', 'unwrapped'}
+    dirs = write_unusual(tmp_path, reads)
+    monkeypatch.setenv('DEEPBINNER_RAW_CLASSIFY_MIN_FILES', '1')
+    monkeypatch.delenv('DEEPBINNER_HOST_INFLATE_SHARE', raising=False)
+
+    def classify_table(directory, gpu_inflate):
+        monkeypatch.setenv('DEEPBINNER_GPU_INFLATE', gpu_inflate)
+        monkeypatch.setattr(classify, '_FILTER_WARNING_GIVEN', False)
+        capsys.readouterr()
+        cli.main(['classify', '--native', directory])
+        done = capsys.readouterr()
+        rows = done.out.splitlines()
+        return rows[0], sorted(r.split('\t') for r in rows[1:]), done.err
+
+    def realtime_table(directory, out, gpu_inflate):
+        monkeypatch.setenv('DEEPBINNER_GPU_INFLATE', gpu_inflate)
+        monkeypatch.setattr(classify, '_FILTER_WARNING_GIVEN', False)
+        err = io.StringIO()
+        with contextlib.redirect_stderr(err):
+            table, _ = run_realtime(directory, str(tmp_path / out), 1, monkeypatch, capsys)
+        return sorted(r[:2] for r in table), err.getvalue()
+
+    kept = sorted(rid for rid, _, _ in reads if rid != special['damaged'])
+    header, want, err = classify_table(dirs['single_twin'], '0')
+    assert [r[0] for r in want] == sorted(rid for rid, _, _ in reads) and FILTER_WARNING not in err
+    want = [r for r in want if r[0] != special['damaged']]
+    for flag in ('1', '0'):
+        got_header, got, err = classify_table(dirs['single'], flag)
+        assert got_header == header and [r[0] for r in got] == kept, flag
+        assert got == want, flag
+        assert err.count(FILTER_WARNING) == 1, (flag, err)
+    twin, err = realtime_table(dirs['multi_twin'], 'out_twin', '1')
+    assert FILTER_WARNING not in err and len(twin) == len(reads)
+    assert [r for r in twin if r[0] != special['damaged']] == want
+    for flag in ('1', '0'):
+        got, err = realtime_table(dirs['multi'], 'out_' + flag, flag)
+        assert got == want, flag
+        assert err.count(FILTER_WARNING) == 1, (flag, err)
+
+
+def test_unusual_vbz_batches_through_classify_pair_deflated(hip, tmp_path):
+    """the raw batches of the same files and container: the original samples for the reads with
+    forced long codes and with unwrapped deltas, a non-zero stream status for the damaged read
+    alone, and the calls the host-decoded samples give"""
+    from deepbinner_amd import fast5_native
+    from deepbinner_amd.model_format import ModelWeights
+    reads, special = unusual_reads()
+    dirs = write_unusual(tmp_path, reads)
+    by_id = {rid: s for rid, s, _ in reads}
+    start = hip.HipModel(ModelWeights.load(os.path.join(MODEL_DIR, 'EXP-NBD103_read_starts.dbw'))[0])
+    end = hip.HipModel(ModelWeights.load(os.path.join(MODEL_DIR, 'EXP-NBD103_read_ends.dbw'))[0])
+    paths = sorted(os.path.join(dirs['single'], n) for n in os.listdir(dirs['single']))
+    batches = [fast5_native.load_batch_raw(paths, 4)]
+    batches += [b[1:] for b in fast5_native.stream_raw([os.path.join(dirs['multi'], 'reads.fast5')],
+                                                       threads=2)]
+    assert len(batches) == 2
+    for ids, offsets, status, comp, records in batches:
+        assert list(status) == [0] * len(reads) and (records['mode'] == 2).all()
+        calls, stream_status, samples = hip.classify_pair_deflated(
+            start, end, comp, records, offsets, 6144, 0.5, want_samples=True)
+        refused = {ids[int(r)] for r in records['read'][stream_status != 0]}
+        assert refused == {special['damaged']}
+        clean = np.zeros(len(samples), dtype=np.int16)
+        for i, rid in enumerate(ids):
+            got = samples[offsets[i]:offsets[i + 1]]
+            if rid == special['damaged']:
+                assert not got.any()
+            else:
+                assert np.array_equal(got, by_id[rid]), rid
+                clean[offsets[i]:offsets[i + 1]] = by_id[rid]
+        assert np.array_equal(calls, hip.classify_pair(start, end, clean, offsets, 6144, 0.5))
     start.close()
     end.close()

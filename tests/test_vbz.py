@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import vbz_fixtures as vf
+import vbz_reference
 from deepbinner_amd import fast5_native, hdf5_lite, load_fast5s
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,6 +29,9 @@ def both_decoders(chunk, cd, max_samples):
     return native, python
 
 
+UNWRAPPED = ('codes',)
+
+
 def codec_cases():
     rng = np.random.default_rng(32020)
     cases = {'n%d' % n: rng.integers(-32768, 32768, n).astype(np.int16)
@@ -35,8 +39,9 @@ def codec_cases():
     cases['jumps'] = np.array([-32768, 32767] * 50 + [0, -32768, 32767, -1], dtype=np.int16)
     squiggle = np.cumsum(rng.integers(-40, 41, 10 ** 6)) + 500
     cases['n1e6'] = squiggle.astype(np.int16)
-    # deltas that need 1, 2 and 3 bytes, in every position of a control byte
-    cases['codes'] = np.cumsum(np.array([1, 200, -300, 40000 % 65536 - 32768] * 64)).astype(np.int16)
+    # deltas that need 1, 2 and 3 bytes, in every position of a control byte (five deltas that
+    # sum to zero, over and over; encoded with the deltas taken in 32 bits: UNWRAPPED below)
+    cases['codes'] = (np.cumsum(np.array([1, 200, -300, 40000, -39901] * 64)) - 20000).astype(np.int16)
     return cases
 
 
@@ -44,7 +49,12 @@ def codec_cases():
 @pytest.mark.parametrize('level', [1, 0])
 def test_codec_round_trip_through_both_decoders(name, level):
     samples = codec_cases()[name]
-    chunk = vf.vbz_chunk(samples, level)
+    chunk = vf.vbz_chunk(samples, level, wrap=name not in UNWRAPPED)
+    if name == 'codes':
+        lengths = vbz_reference.code_lengths(struct.pack('<I', 2 * len(samples)) +
+                                             vf.streamvbyte(samples, wrap=False))
+        assert {(int(n), k % 4) for k, n in enumerate(lengths)} >= {
+            (n, at) for n in (1, 2, 3) for at in range(4)}
     native, python = both_decoders(chunk, CD[:3] + (level,), len(samples))
     assert native is not None and python is not None
     assert np.array_equal(native, samples) and np.array_equal(python, samples)

@@ -39,12 +39,16 @@ def zstd_compress(data, level=1):
     return out.raw[:k]
 
 
-def streamvbyte(samples):
-    """int16 samples -> streamvbyte bytes of their zigzagged deltas (delta from 0)."""
+def streamvbyte(samples, wrap=True):
+    """int16 samples -> streamvbyte bytes of their zigzagged deltas (delta from 0).  ``wrap``: the
+    delta of two samples wrapped to int16 (codes of 1 and 2 bytes only); False: taken in 32 bits
+    as it is, so that a jump beyond +-32,767 takes a 3-byte code.  Both decode to the same samples
+    (the decoder sums modulo 2^32 and truncates)."""
     x = np.asarray(samples, dtype=np.int16).astype(np.int64)
     delta = np.diff(np.concatenate([[0], x]))
-    delta = ((delta + 32768) % 65536) - 32768             # the int16 delta, wrapped
-    u = ((delta << 1) ^ (delta >> 63)).astype(np.uint32)
+    if wrap:
+        delta = ((delta + 32768) % 65536) - 32768         # the int16 delta, wrapped
+    u = (((delta << 1) ^ (delta >> 63)) & 0xFFFFFFFF).astype(np.uint32)
     return pack_values(u)
 
 
@@ -62,11 +66,11 @@ def pack_values(u, lengths=None):
     return ctrl.astype(np.uint8).tobytes() + data.tobytes()
 
 
-def vbz_chunk(samples, level=1, original_size=None):
+def vbz_chunk(samples, level=1, original_size=None, wrap=True):
     """One chunk as the VBZ filter stores it: u32 original_size, then the zstd frame of the
     streamvbyte bytes (level 0: the streamvbyte bytes themselves)."""
     samples = np.asarray(samples, dtype=np.int16)
-    packed = streamvbyte(samples)
+    packed = streamvbyte(samples, wrap)
     size = len(samples) * 2 if original_size is None else original_size
     return struct.pack('<I', size) + (zstd_compress(packed, level) if level else packed)
 
