@@ -1,6 +1,7 @@
 // dbh_api.hip — host side of libdeepbinner_hip.so: the C ABI declared in
 // include/deepbinner_hip.h.  Packs the canonical weight blob into the kernel's fragment order,
-// owns the device buffers, launches the kernels of dbh_forward.hip.
+// owns the device buffers, launches the kernels of dbh_forward.hip and holds the small seam kernels
+// (stand-alone normalise, merge, combine_calls).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,93 @@
 #include "dbh_forward.hip"
 #undef DBH_FORWARD_NS
 #undef DBH_TIMELINE
+
+// =============================================================================================
+// Seam b2 as kernels of their own (the forward kernel does both itself when it is handed samples):
+// on the arithmetic of dbh_seam.h, like it.
+// =============================================================================================
+namespace dbh {
+
+// One block per (read, step): slice the window (classify.py:337-349), z-normalise it in fp64
+// (trim_signal.py:61-69; the sums are exact integers), zero-pad right ('start') or left ('end')
+// (classify.py:352-357) and emit fp32, which is what Keras casts the float64 input to.
+__global__ __launch_bounds__(256) void dbh_normalise_kernel(
+    const int16_t* __restrict__ samples, const long long* __restrict__ offsets, int steps,
+    int side, float* __restrict__ windows) {
+    __shared__ long long red[2][4];
+    const long long read = blockIdx.x / steps;
+    const int step = blockIdx.x - (int)(read * steps);
+    const long long base = offsets[read];
+    const long long len = offsets[read + 1] - base;
+    long long a, b;
+    window_bounds(len, step, side, kWindow, &a, &b);
+    const int cnt = (int)(b - a);
+    const int tid = threadIdx.x;
+    const int16_t* src = samples + base + a;
+
+    int v[4];
+    long long s1 = 0, s2 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = tid + i * 256;
+        v[i] = (k < cnt) ? (int)src[k] : 0;
+        s1 += v[i];
+        s2 += (long long)v[i] * v[i];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        s1 += __shfl_xor(s1, off);
+        s2 += __shfl_xor(s2, off);
+    }
+    if ((tid & 63) == 0) {
+        red[0][tid >> 6] = s1;
+        red[1][tid >> 6] = s2;
+    }
+    __syncthreads();
+    s1 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    s2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+
+    float* out = windows + (long long)blockIdx.x * kWindow;
+    double mean, inv;
+    mean_std(s1, s2, cnt, &mean, &inv);
+    const int pad_left = (side == 0) ? 0 : kWindow - cnt;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int k = tid + i * 256;          // position in the source slice
+        if (k < cnt) out[pad_left + k] = (float)(((double)v[i] - mean) * inv);
+    }
+    // zero padding: [cnt, 1024) for 'start', [0, 1024-cnt) for 'end'
+    const int pad_begin = (side == 0) ? cnt : 0;
+    const int pad_count = kWindow - cnt;
+    for (int k = tid; k < pad_count; k += 256) out[pad_begin + k] = 0.f;
+}
+
+// 32 lanes per read: merge the per-step softmax vectors (classify.py:368-374: min for class 0,
+// max for the barcodes), rescale the barcodes so the vector sums to one (classify.py:387-393,
+// in fp64 like NumPy-1.x scalar promotion did) and make the call (classify.py:285-295).
+__global__ __launch_bounds__(256) void dbh_merge_kernel(const float* __restrict__ wprobs,
+                                                        long long n_reads, int steps,
+                                                        int n_classes, double score_diff,
+                                                        float* __restrict__ probs,
+                                                        int* __restrict__ calls) {
+    const long long read = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int c = threadIdx.x & 31;
+    if (read >= n_reads) return;   // whole 32-lane groups exit together
+    const bool valid = c < n_classes;
+    float merged = 0.f;
+    if (valid) {
+        const float* src = wprobs + read * steps * n_classes + c;
+        merged = src[0];
+        for (int s = 1; s < steps; ++s) {
+            const float v = src[(long long)s * n_classes];
+            merged = (c == 0) ? fminf(merged, v) : fmaxf(merged, v);
+        }
+    }
+    renormalise_and_call(merged, c, n_classes, score_diff, probs + read * n_classes,
+                         calls + read);
+}
+
+}  // namespace dbh
 
 namespace {
 
@@ -143,13 +231,13 @@ void pack_weights(const float* w, int n_classes, std::vector<float>& packed) {
                                 const int ci = frag_cin(i, sp, lane >> 4, e);
                                 const int co = 16 * t + (lane & 15);
                                 float v = co < cout ? kernel[((size_t)tap * cin + ci) * cout + co] : 0.f;
-                                if (i == 4 && DBH_FOLD_BN2) v = (float)((double)v * fold_scale[ci]);   // BN2's scale
+                                if (i == 4) v = (float)((double)v * fold_scale[ci]);   // BN2's scale
                                 dst[((((size_t)tap * sp_n + sp) * nt + t) * 64 + lane) * 2 + e] = v;
                             }
         }
         float* bdst = packed.data() + bias_offset(i);
         for (int c = 0; c < cout; ++c) bdst[c] = bias[c] * kActScale;      // (exact: a power of two)
-        if (i == 4 && DBH_FOLD_BN2)       // ... and BN2's shift, through conv1d_5's weights, in its bias
+        if (i == 4)       // ... and BN2's shift, through conv1d_5's weights, in its bias
             for (int c = 0; c < cout; ++c) {
                 double extra = 0.0;
                 for (int ci = 0; ci < cin; ++ci) extra += (double)kernel[(size_t)ci * cout + c] * fold_shift[ci];

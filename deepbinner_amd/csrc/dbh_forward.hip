@@ -1,73 +1,69 @@
 // dbh_forward.hip — the Deepbinner forward pass as ONE persistent gfx950 kernel: at most one
-// 512-thread workgroup (8 wave64s, 2 per SIMD) per CU; workgroup b starts with window b and takes
-// every further window off a counter in global memory, carrying each 1024-sample window through
-// all 20 convolutions with the activations resident in registers (conv1 .. conv6) or in LDS the
-// whole way.  Per
-// window HBM gives 2 KiB of int16 and takes n_classes floats + a call; the weights stream from L2
-// by LDS-DMA; the one round trip through global memory is conv17's 16 x 48 output, parked in a
-// per-workgroup slot until the batched tail runs (3 KB per window, written and read back by the
-// same CU - dirty in L2, so part of it does reach HBM: ~1.2 KB per window of write traffic
-// against 56 B of results, profiles/r04_v1).
+// 512-thread workgroup (8 wave64s, 2 per SIMD) per CU, which takes the launch's 1024-sample windows
+// in GROUPS OF FOUR (the first group by its block index, every further one off a counter in global
+// memory) and carries them through all 20 convolutions with the activations in registers or in
+// LDS.  Per window HBM gives 2 KiB of int16 and takes n_classes floats + a call; the weights stream
+// from L2 by LDS-DMA.  Two things are parked in the workgroup's scratch in global memory (120 KB,
+// dbh_layout.h: kWgScratchFloats): conv7's 128 x 48 output of a group's earlier windows until the
+// group's stage D, and conv17's 16 x 48 output until the batched tail.
 //
 // What it computes: reference deepbinner/network_architecture.py:18-95 as evaluated by
 // model.predict (deepbinner/classify.py:361) — see oracle/network_ref.py for the operator
 // semantics (TensorFlow SAME padding, valid-count average pooling, BN after ReLU/pool) — and, in
 // seam-b2 mode, the slicing and z-normalisation in front of it (classify.py:337-357,
-// trim_signal.py:61-69) and the renormalise + call behind it (classify.py:285-295, 387-393).
+// trim_signal.py:61-69) and the renormalise + call behind it (classify.py:285-295, 387-393); the
+// arithmetic of both seams is dbh_seam.h's, shared with the stand-alone kernels and the general path.
 //
-// How (DESIGN.md section 4 has the full account and the measurements behind each choice):
-//   - every convolution is a sum of [positions x C_in] . [C_in x C_out] products on the fp32
-//     matrix pipe (v_mfma_f32_16x16x4_f32: M = 16 positions, N = 16 output channels, K = 4 input
-//     channels).  The pipe is shared with the vector ALU: every other vector instruction costs
-//     matrix time, so the code counts them;
-//   - stage B (conv1 .. conv4, 84 % of the work) and conv5, conv6 behind it are ONE CHAIN IN
-//     REGISTERS (stage_b_chain): every layer runs TRANSPOSED (M = output channels = the weights as
-//     the A operand, N = the wave's 16 quads), so that an MFMA leaves each lane with the output
-//     channels of its own quad that the next layer's k-steps want from it; output transform, bias,
-//     ReLU, the next input transform are in-lane but for one halo position each side (a DPP row
-//     shift; at a wave's two ends 2 x 48 floats through LDS and a counter word the neighbours
-//     poll).  No activation image and no workgroup barrier from the top of a window to conv6's
-//     last store; conv1 (one input channel) is computed inside conv2's first tile the same way;
-//   - the k = 3 layers with enough positions run as Winograd: F(4,3) for conv2,3,4 (L = 512, one
-//     tile of 16 quads per wave, N tile by N tile with the transformed inputs in registers) and
-//     conv7 (L = 256, a tile per wave PAIR, split by output channels), F(2,3) for conv6, conv8,
-//     conv9, conv13, conv15 - 9,588 MFMAs per window instead of the direct form's 16,452;
-//   - from conv7 on: A fragments (activations): ds_read_b64 from the [position][channel] LDS image
-//     (row pitch 50 floats), B fragments (weights): ds_read_b128 / b64 from fragment-ordered copies
-//     that LDS-DMA brought in a phase ahead; both issued from inline asm one step ahead with
-//     hand-counted waits.  conv17's weights, used once per window, go to registers by buffer loads;
-//   - there, outputs are stored in place once every wave has read its inputs (one barrier
-//     mid-layer), the epilogue of an N tile inside the MFMA steps of the next one;
-//   - activations are held times 2^-60 so that ReLU is the clamp modifier of the instruction that
-//     produces a value (dbh_layout.h: kActScale);
-//   - the average pooling in front of conv10 is applied to conv10's OUTPUT (a 1x1 convolution
-//     commutes with it), in registers;
-//   - the last three layers run for eight windows at a time, one wave per window (batched tail);
-//   - the next window's samples, statistics and first weights are fetched under the current one's
-//     last stages; memory requests are ordered for the wait counts hipcc derives (it does not see
-//     the inline-asm LDS-DMA requests, and merges control flow pessimistically).
+// Every convolution is a sum of products on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32), which is
+// shared with the vector ALU: every other vector instruction costs matrix time, so the code counts
+// them.  The k = 3 layers with enough positions run as Winograd - F(4,3): conv2, 3, 4, 7, 8, 9;
+// F(2,3): conv6, 13, 15, 16 - 9,156 MFMAs executed per window (DESIGN.md sections 3 and 4 have the
+// layouts, the full account and the measurements behind each choice).  Activations are held times
+// 2^-60 so that ReLU is the clamp modifier of the instruction that produces a value (dbh_layout.h:
+// kActScale).  Memory requests are ordered for the wait counts hipcc derives: it does not see the
+// inline-asm LDS-DMA requests and LDS reads, whose waits are counted by hand.
+//
+// The file, in its order:
+//   - small tools: cycle stamps (timeline build), DPP row reductions, priority by progress, the
+//     barriers, LDS reads from inline asm;
+//   - conv_tiles / epilogue: the direct form out of an LDS image, A fragments by ds_read_b64 from
+//     the [position][channel] image, B fragments from fragment-ordered weights, one step ahead -
+//     what the batched tail (conv18, conv19) runs on; the epilogue also finishes conv17;
+//   - LDS-DMA of weights (dma_piece, dma_weights, dma_weights_one), packed-fp32 helpers;
+//   - the F(4,3) pieces: input transform, B fragments, output transform, w43t_mfmas - the
+//     TRANSPOSED tile step (M = output channels = the weights as the A operand, N = the wave's 16
+//     quads), which leaves each lane with the output channels of its own quad that the next
+//     layer's k-steps want from it;
+//   - stage A inside conv2's first tile (w43a_*: conv1, one input channel, on the same registers);
+//   - stage_b_chain: conv2 -> conv3 -> conv4 (L = 512, 84 % of the work) -> conv5 -> conv6 as ONE
+//     CHAIN IN REGISTERS per window - halo positions by DPP row shift and, at a wave's two ends,
+//     2 x 48 floats of LDS that the neighbours poll a counter word for; weight thirds through a ring
+//     of slots; no activation image and no workgroup barrier down to conv6's last store;
+//   - stage_d_chain: conv8 -> conv9 and the inception block conv10 .. conv16 on the same registers,
+//     the group's four windows together (a wave = half a window); the average pooling in front of
+//     conv10 is applied to conv10's OUTPUT (a 1x1 convolution commutes with it);
+//   - conv7 (w43ns_step, w43_nsplit_half: L = 256, a tile per wave PAIR, split by output
+//     channels), between the two chains;
+//   - the kernel's arguments, the window statistics and sample fetch of seam b2;
+//   - dbh_forward_kernel: the persistent loop - stages A-C window by window, stages D-E for the
+//     group, stage F (conv17: every wave an EIGHTH of the contraction for all four windows, weights
+//     from L2 straight to registers; the next group's samples and statistics underneath), and for
+//     up to eight windows at a time the batched tail (conv18 .. conv20, softmax, call), one wave
+//     per window.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
 #include "dbh_layout.h"
-
-// (A/B switches of tools/ab_variants.sh; the defaults are what ships)
-#ifndef DBH_EXP_A_DMA_UNDER_MFMA
-#define DBH_EXP_A_DMA_UNDER_MFMA 1
-#endif
-// timing-only ablations of stage_b_chain (results wrong on purpose; tools/ab_variants.sh):
-// 1 = no polls, 2 = no edge rows / posts, 4 = no LDS-DMA requests, 8 = no output / input
-// transforms of conv2 -> conv3 -> conv4, 16 = no epilogue of conv4, 32 = no arrivals, 64 = no halo polls, 256 = no DPP row shifts (adds instead),
-// 128 = no tile-word polls
-#ifndef DBH_ABL
-#define DBH_ABL 0
-#endif
+#include "dbh_seam.h"
 
 // This file is compiled twice by dbh_api.hip: as namespace dbh with DBH_TIMELINE 0 (the product)
 // and as namespace dbh_timeline with DBH_TIMELINE 1 (cycle stamps for tools/timeline.py).  The
 // stamps are global stores, and on gfx9 a store shares the vmcnt counter with the loads: one
 // conditional store anywhere makes hipcc wait for vmcnt(0) at every later use of a prefetched
 // register, so they must not even be compiled into the production kernel.
+// These two are the file's only build-time variants: what an experiment decided is plain code here
+// (HISTORY.md lists the switches that were retired), and a new one is a patched copy built beside
+// the product (the Makefile's EXTRA, tools/ab_variants.sh).
 #ifndef DBH_FORWARD_NS
 #define DBH_FORWARD_NS dbh
 #endif
@@ -75,22 +71,6 @@
 #define DBH_TIMELINE 0
 #endif
 
-// where stage F's requests are made inside the chain: 0 = in front of conv1d_16's MFMAs, 1 = in
-// front of conv1d_15 (an experiment)
-// the next group's FIRST window staged and its statistics made under stage F like the other three
-// (1: +0.4 %), or carried in registers to that group's stage A (0: every wave summing and dividing
-// behind that stage's first barrier)
-#ifndef DBH_STATS0_IN_F
-#define DBH_STATS0_IN_F 1
-#endif
-// stage D's operands of the earlier windows asked for behind conv7's mid-layer barrier (1: +0.13 %,
-// the group's last conv7 12.9 k -> 12.0 k cycles) or behind its last MFMAs (0)
-#ifndef DBH_Y_EARLY
-#define DBH_Y_EARLY 1
-#endif
-#ifndef DBH_F_AHEAD_EARLY
-#define DBH_F_AHEAD_EARLY 0
-#endif
 namespace DBH_FORWARD_NS {
 using namespace dbh;
 
@@ -100,20 +80,29 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int kWaves = 8;
 constexpr int kThreads = kWaves * 64;
 
+// Tuning values, each the winner of an A/B on the device (HISTORY.md has the other values' cost).
+// How many of the eight waves issue stage B's LDS-DMA requests (the low ones: they run ahead of
+// their partners on the same SIMDs anyway, and a request is ~100 cycles of issue during which the
+// partner has the matrix pipe to itself); stage D's and conv7's request schedules deal to as many.
+constexpr int kDmaWaves = 4;
+// How many waves share a block copy (dma_weights).
+constexpr int kDmaAllWaves = 4;
+// Where in a layer's 18 steps the priority schedule of stage B starts over (the step whose
+// priority is 3 again).  At that wrap the wave in front has priority 3 against the 0 of the one
+// behind and pulls away, so it must not lie at the layer's first steps, where the halo rows of the
+// neighbours are needed: there the schedule should take a normal step DOWN, which lets whoever is
+// behind catch up.
+// (0 / 3 / 5 / 9 / 12: 45.65 / 45.76 / 45.66 / 45.70 / 45.58 us per 256 windows, profiles/r05_ablation.txt)
+constexpr int kPrioPhase = 12;
+// How the six channel groups of conv7's shared N tile are split between the two waves of a SIMD:
+// the older one (w < 4) takes the first kConv7Low, the younger one the rest.  (3 / 3 until
+// round 5; the older wave wins every tie for the matrix pipe and reached the exchange first.)
+constexpr int kConv7Low = 3;
+
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// ---------------------------------------------------------------------------------------------
-// acc[m][t] += sum over (tap, sp, e) of A-tile(m) x B-tile(t).
-//   a_lane: this lane's A address for tile 0, tap 0, sp 0:
-//           region + (first_row + (lane&15)*row_step) * S + 2*(lane>>4)
-//   b_lane: this lane's B address for tap 0, sp 0, tile 0:  weights + t0*128 + lane*2
-//   MROWS : physical rows between consecutive M tiles (16 * conv stride)
-//   SPTOT : C_in/8 of the whole layer (stride of the tap index in the weight image);
-//           SP <= SPTOT is how many channel-pairs groups this call walks (split-K).
-// All offsets are compile-time so every access is base + immediate.
-// ---------------------------------------------------------------------------------------------
 // Cycle stamps for the timeline mode (debug_stage 300): ts is non-null in timeline launches and
 // points at ONE register of the wave whose lane `id` takes stamp `id` (v_writelane: no memory
 // traffic - a global store per stamp made every vmcnt(0) of the kernel, the arrivals of stage B
@@ -193,30 +182,6 @@ struct NoSide {
     template <int I>
     __device__ __forceinline__ void operator()(IntC<I>) const {}
 };
-// begin(): a layer's one-off requests (LDS-DMA for a later layer), issued behind the first step's
-// fragment reads
-struct NoBegin {
-    __device__ __forceinline__ void operator()() const {}
-};
-struct NoHook {
-    __device__ __forceinline__ void operator()() const {}
-};
-// Marks side work made of plain global loads to registers: a Winograd step issues those BETWEEN
-// its MFMAs, one after every second MFMA, because a bunch of vector-memory instructions holds
-// the wave (and its in-order MFMAs) ~35 cycles each, a lone one ~9 (tools/microbench/
-// mfma_issue.hip).  LDS-DMA requests do not gain from this (M0 set-up) and stay up front.
-template <class F>
-struct Interleaved {
-    F f;
-    template <int I>
-    __device__ __forceinline__ void operator()(IntC<I> t) const { f(t); }
-};
-template <class F>
-__device__ __forceinline__ Interleaved<F> interleaved(F f) { return Interleaved<F>{f}; }
-template <class T>
-struct is_interleaved : std::false_type {};
-template <class F>
-struct is_interleaved<Interleaved<F>> : std::true_type {};
 
 // Wave-wide sum of a non-negative 32-bit integer per lane (result < 2^31) with DPP row
 // reductions + three readlanes instead of six rounds of ds_bpermute.
@@ -239,26 +204,10 @@ __device__ __forceinline__ void progress_priority() {
     __builtin_amdgcn_s_setprio(3 - (4 * STEP) / STEPS);
 }
 
-// how many of the eight waves issue stage B's LDS-DMA requests (the low ones: they run ahead of
-// their partners on the same SIMDs anyway, and a request is ~100 cycles of issue during which the
-// partner has the matrix pipe to itself)
-#ifndef DBH_DMA_WAVES
-#define DBH_DMA_WAVES 4
-#endif
-// where in a layer's 18 steps the priority schedule of stage B starts over (the step whose
-// priority is 3 again).  At that wrap the wave in front has priority 3 against the 0 of the one
-// behind and pulls away, so it must not lie at the layer's first steps, where the halo rows of the
-// neighbours are needed: there the schedule should take a normal step DOWN, which lets whoever is
-// behind catch up.
-#ifndef DBH_CATCHUP
-#define DBH_CATCHUP 0
-#endif
-#ifndef DBH_PRIO_PHASE
-#define DBH_PRIO_PHASE 12
-#endif
+// stage B's form: the same schedule, started over at step kPrioPhase of the layer's STEPS
 template <int STEP, int STEPS>
 __device__ __forceinline__ void progress_priority_pair(bool) {
-    __builtin_amdgcn_s_setprio(3 - (4 * ((STEP + DBH_PRIO_PHASE) % STEPS)) / STEPS);
+    __builtin_amdgcn_s_setprio(3 - (4 * ((STEP + kPrioPhase) % STEPS)) / STEPS);
 }
 
 template <int MT, int NT>
@@ -386,9 +335,18 @@ __device__ __forceinline__ void conv_step(unsigned a_addr, unsigned b_addr, Frag
         conv_step<TAPS, SP, SPTOT, MT, NT, NTTOT, S, MROWS, IT + 1>(a_addr, b_addr, buf, acc, side);
 }
 
+// ---------------------------------------------------------------------------------------------
 // acc[m][t] += sum over (tap, sp, e) of A-tile(m) x B-tile(t), software-pipelined: the fragments
 // of step it+1 are requested before the MFMAs of step it are issued.  a_lane / b_lane must
 // point into LDS.
+//   a_lane: this lane's A address for tile 0, tap 0, sp 0:
+//           region + (first_row + (lane&15)*row_step) * S + 2*(lane>>4)
+//   b_lane: this lane's B address for tap 0, sp 0, tile 0:  weights + t0*128 + lane*2
+//   MROWS : physical rows between consecutive M tiles (16 * conv stride)
+//   SPTOT : C_in/8 of the whole layer (stride of the tap index in the weight image);
+//           SP <= SPTOT is how many channel-pairs groups this call walks (split-K).
+// All offsets are compile-time so every access is base + immediate.
+// ---------------------------------------------------------------------------------------------
 template <int TAPS, int SP, int SPTOT, int MT, int NT, int NTTOT, int S, int MROWS,
           class Side = NoSide>
 __device__ __forceinline__ void conv_tiles(const float* a_lane, const float* b_lane,
@@ -397,14 +355,6 @@ __device__ __forceinline__ void conv_tiles(const float* a_lane, const float* b_l
     Frags<MT, NT> buf[2];
     load_frags<TAPS, SP, SPTOT, MT, NT, NTTOT, S, MROWS, 0>(buf[0], a_addr, b_addr);
     conv_step<TAPS, SP, SPTOT, MT, NT, NTTOT, S, MROWS, 0>(a_addr, b_addr, buf, acc, side);
-}
-
-template <int MT, int NT>
-__device__ __forceinline__ void zero_acc(f4 (&acc)[MT][NT]) {
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[m][t] = f4{0.f, 0.f, 0.f, 0.f};
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -512,13 +462,6 @@ __device__ __forceinline__ void epilogue(const f4 (&acc)[MT][NT], float* out_lan
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_view(const float* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
 }
-__device__ __forceinline__ f2 buffer_load_f2(__amdgpu_buffer_rsrc_t view, unsigned lane_bytes,
-                                             unsigned uniform_bytes) {
-    // (two dword loads: this hipcc lowers the b64 / b128 forms of the builtin to ONE dword, splat)
-    const unsigned lo = __builtin_amdgcn_raw_buffer_load_b32(view, (int)lane_bytes, (int)uniform_bytes, 0);
-    const unsigned hi = __builtin_amdgcn_raw_buffer_load_b32(view, (int)lane_bytes + 4, (int)uniform_bytes, 0);
-    return f2{__builtin_bit_cast(float, lo), __builtin_bit_cast(float, hi)};
-}
 
 // One 1 KiB piece: 64 lanes x 16 B from the wave-uniform global address `g_piece` (in scalar
 // registers: the instruction's SADDR form, the lane's 16 lane bytes as its 32-bit offset - no
@@ -527,7 +470,6 @@ __device__ __forceinline__ f2 buffer_load_f2(__amdgpu_buffer_rsrc_t view, unsign
 // nothing else in this kernel uses M0.
 __device__ __forceinline__ void dma_piece(const float* g_piece, const float* lds_piece,
                                           unsigned lane_bytes) {
-    if (DBH_ABL & 4) return;
     const unsigned m0v = lds_addr(lds_piece);
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                  :
@@ -535,15 +477,8 @@ __device__ __forceinline__ void dma_piece(const float* g_piece, const float* lds
                  : "memory");
 }
 
-// (DBH_DMA_ALL_WAVES: how many waves share a block copy - A/B knob; stage B's own requests have
-// theirs, DBH_DMA_WAVES)
-#ifndef DBH_DMA_ALL_WAVES
-#define DBH_DMA_ALL_WAVES 4
-#endif
-#ifndef DBH_CONV8_DMA
-#define DBH_CONV8_DMA 1
-#endif
-template <int NFLOATS, int NW = DBH_DMA_ALL_WAVES>
+// A block copy, its pieces dealt to the first NW waves.
+template <int NFLOATS, int NW = kDmaAllWaves>
 __device__ __forceinline__ void dma_weights(const float* __restrict__ g, float* lds_dst, int lane,
                                             int wave) {
     static_assert(NFLOATS % 256 == 0, "weight blocks are whole 1 KiB pieces");
@@ -568,21 +503,6 @@ __device__ __forceinline__ void dma_weights_one(const float* __restrict__ g, flo
         dma_piece(g + piece * 256, lds_dst + piece * 256, (unsigned)lane * 16u);
 }
 
-// The same copy, spread over the NIT steps of the running layer (step IT issues its share).
-template <int NFLOATS, int IT, int NIT, int NW = DBH_DMA_ALL_WAVES>
-__device__ __forceinline__ void dma_weights_slice(const float* __restrict__ g, float* lds_dst,
-                                                  int lane, int wave) {
-    constexpr int kPieces = NFLOATS / 256;
-    constexpr int kPerWave = (kPieces + NW - 1) / NW;
-    const unsigned lane_bytes = (unsigned)lane * 16u;
-    if (wave >= NW) return;
-#pragma unroll
-    for (int i = IT * kPerWave / NIT; i < (IT + 1) * kPerWave / NIT; ++i) {
-        const int piece = wave + NW * i;
-        if (piece < kPieces) dma_piece(g + piece * 256, lds_dst + piece * 256, lane_bytes);
-    }
-}
-
 __device__ __forceinline__ void zero_row(float* region, int row, int stride, int channels,
                                          int tid) {
     if (tid < channels) region[row * stride + tid] = 0.f;
@@ -596,18 +516,6 @@ __device__ __forceinline__ void dump_stage(const float* region, int stride, int 
     }
 }
 
-// a + b / a - b on both halves of a register pair.  (Written as asm because hipcc splits a plain
-// f2 add into two scalar ones whenever it likes the register allocation better.)
-__device__ __forceinline__ f2 pk_add(f2 a, f2 b) {
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f2 pk_sub(f2 a, f2 b) {
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 // ReLU for free: the `clamp` output modifier ([0, 1]) on the instruction that produces the value -
 // activations are held times 2^-60 (dbh_layout.h: kActScale), so 1.0 is out of their reach.
 __device__ __forceinline__ f2 pk_add_relu(f2 a, f2 b) {
@@ -639,95 +547,6 @@ __device__ __forceinline__ f2 max_raw2(f2 a, f2 b) { return f2{max_raw(a.x, b.x)
 // distance between an MFMA and the first VALU instruction that reads its result with s_nop, but
 // it does not look into inline asm: an accumulator read HERE straight after the MFMA chain (the
 // exposed epilogue of a layer's last tile) arrives stale.
-
-// ---------------------------------------------------------------------------------------------
-// F(2,3) with 16 input channels out of an LDS image (conv13, conv15 of the inception block; conv6,
-// 16 -> 48 at L = 256, ran this way until round 5 and is now part of stage_b_chain): 2/3 of the
-// direct form's MFMAs.  One tile of 16 pairs per wave as in conv7, but with two channel groups a
-// tile is only two steps of eight MFMAs, so the three N tiles run as ONE six-step pipeline: steps
-// 0-1 build U (eight register pairs) and multiply for tile 0, steps 2-3 tile 1 with tile 0's
-// outputs stored inside them, steps 4-5 tile 2 with tile 1's.  Input and output live in different
-// buffers (IN_OFF at pitch kS16, OUT_OFF at pitch kS48): no barrier before the stores.
-// Weights by N tile: [t][sp][matrix pair][lane][matrix of the pair][e].
-// ---------------------------------------------------------------------------------------------
-struct W23U16 {
-    f2 u[4][2];      // [xi][sp]
-};
-struct W23Pipe16 {
-    f2 rows[2][4];   // [step parity][input row]
-    f4 b[2][2];      // [step parity][matrix pair]
-};
-
-// NSTEPS: two per N tile the wave works on (b_addr = the first of them).
-template <int G, int NSTEPS, class Side>
-__device__ __forceinline__ void w23c16_step(W23U16& U, unsigned a_addr, unsigned b_addr,
-                                            W23Pipe16& pipe, f4 (&acc)[3][4], const float (&bias)[3],
-                                            const Side& side) {
-    constexpr int T = G / 2, SP = G % 2;
-    auto loads = [&](auto step_tag) {
-        constexpr int N = decltype(step_tag)::value;
-        if constexpr (N < 2) {
-            pipe.rows[N & 1][0] = ds_read_f2<(0 * kS16 + N * 8) * 4>(a_addr);
-            pipe.rows[N & 1][1] = ds_read_f2<(1 * kS16 + N * 8) * 4>(a_addr);
-            pipe.rows[N & 1][2] = ds_read_f2<(2 * kS16 + N * 8) * 4>(a_addr);
-            pipe.rows[N & 1][3] = ds_read_f2<(3 * kS16 + N * 8) * 4>(a_addr);
-        }
-        pipe.b[N & 1][0] = ds_read_f4<((N * 2 + 0) * 256) * 4>(b_addr);
-        pipe.b[N & 1][1] = ds_read_f4<((N * 2 + 1) * 256) * 4>(b_addr);
-    };
-    if constexpr (G == 0) loads(IntC<0>{});
-    if constexpr (G + 1 < NSTEPS) {
-        loads(IntC<G + 1>{});
-        if constexpr (G + 1 < 2) asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    f4(&b)[2] = pipe.b[G & 1];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) asm volatile("" : "+v"(b[p]));
-    progress_priority<G, NSTEPS>();
-    if constexpr (T == 0) {
-        f2(&d)[4] = pipe.rows[G & 1];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(d[k]));
-        __builtin_amdgcn_sched_barrier(0);
-        U.u[0][SP] = pk_sub(d[0], d[2]);
-        U.u[1][SP] = pk_add(d[1], d[2]);
-        U.u[2][SP] = pk_sub(d[2], d[1]);
-        U.u[3][SP] = pk_sub(d[1], d[3]);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) asm volatile("" : "+v"(U.u[x][SP]));
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (SP == 0) {
-        // M0 starts at +bias, M3 at -bias (even = M0+M1+M2, odd = M1-M2-M3 both get the bias)
-        const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
-        const float bv = bias[T];
-        acc[T][0] = mfma4(U.u[0][SP].x, b[0][0], f4{bv, bv, bv, bv});
-        acc[T][1] = mfma4(U.u[1][SP].x, b[0][2], zero);
-        acc[T][2] = mfma4(U.u[2][SP].x, b[1][0], zero);
-        acc[T][3] = mfma4(U.u[3][SP].x, b[1][2], f4{-bv, -bv, -bv, -bv});
-    } else {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            acc[T][2 * p] = mfma4(U.u[2 * p][SP].x, b[p][0], acc[T][2 * p]);
-            acc[T][2 * p + 1] = mfma4(U.u[2 * p + 1][SP].x, b[p][2], acc[T][2 * p + 1]);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        acc[T][2 * p] = mfma4(U.u[2 * p][SP].y, b[p][1], acc[T][2 * p]);
-        acc[T][2 * p + 1] = mfma4(U.u[2 * p + 1][SP].y, b[p][3], acc[T][2 * p + 1]);
-    }
-#pragma unroll
-    for (int x = 0; x < 4; ++x) asm volatile("" : "+v"(acc[T][x]));
-    __builtin_amdgcn_sched_barrier(0);
-    side(IntC<G>{});
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (G + 1 < NSTEPS)
-        w23c16_step<G + 1, NSTEPS>(U, a_addr, b_addr, pipe, acc, bias, side);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Winograd F(4,3) convolution (48 -> 48 channels, k = 3, 'same', stride 1) at L = 512, in place.
@@ -778,26 +597,9 @@ __device__ __forceinline__ void w43_load_rows(f2 (&d)[6], unsigned a_addr) {
 //   a = d4-4d2, b = d3-4d1: U1 = a+b, U2 = a-b;   c = d4-d2, g = d3-d1: U3 = c+2g, U4 = c-2g
 template <int SP>
 __device__ __forceinline__ void w43_transform(W43U& U, const f2 (&d)[6]) {
-#ifdef DBH_EXP_SCALAR_TRANSFORM
-    // A/B knob (tools/ab_variants.sh): the same arithmetic one component at a time - twice the
-    // instructions, none of them packed (MI355X_MICROARCH.md lists packed fp32 VALU beside MFMAs
-    // as an anti-lever; measured in THIS kernel: see DESIGN.md section 4)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const float d0 = d[0][e], d1 = d[1][e], d2 = d[2][e], d3 = d[3][e], d4 = d[4][e], d5 = d[5][e];
-        const float a = fmaf(-4.f, d2, d4), b = fmaf(-4.f, d1, d3);
-        const float c = d4 - d2, g = d3 - d1;
-        U.u[0][SP][e] = fmaf(4.f, d0, fmaf(-5.f, d2, d4));
-        U.u[1][SP][e] = a + b;
-        U.u[2][SP][e] = a - b;
-        U.u[3][SP][e] = fmaf(2.f, g, c);
-        U.u[4][SP][e] = fmaf(-2.f, g, c);
-        U.u[5][SP][e] = fmaf(4.f, d1, fmaf(-5.f, d3, d5));
-    }
-#pragma unroll
-    for (int x = 0; x < 6; ++x) asm volatile("" : "+v"(U.u[x][SP]));
-    return;
-#endif
+    // (The same arithmetic one component at a time - twice the instructions, none of them packed;
+    // MI355X_MICROARCH.md lists packed fp32 VALU beside MFMAs as an anti-lever - was measured in
+    // THIS kernel and lost: DESIGN.md section 4.)
     const f2 m4 = f2{-4.f, -4.f}, p2 = f2{2.f, 2.f}, m2 = f2{-2.f, -2.f};
     const f2 p4 = f2{4.f, 4.f}, m5 = f2{-5.f, -5.f};
     const f2 a = __builtin_elementwise_fma(m4, d[2], d[4]), b = __builtin_elementwise_fma(m4, d[1], d[3]);
@@ -821,53 +623,9 @@ __device__ __forceinline__ void w43_load_b(f4 (&b)[3], unsigned b_addr) {
 }
 
 // Half (h = rows 2h, 2h+1 of every accumulator = quads 2q + 8h, 2q + 1 + 8h of the wave's tile)
-// of the epilogue of N tile T: output transform, ReLU (+ MaxPool2 + BatchNorm), stores in place.
-// MFMA row m = 4q'+r' of the wave's tile works on quad pm(m) = 2q' + (r'&1) + 8(r'>>1), so that the
-// four lane groups of one store write quads 2 apart = 16-bank-aligned quarters of the LDS banks.
-template <int T, bool POOL, bool BN>
-__device__ __forceinline__ void w43_epilogue_half(const f4 (&acc)[6], int h, float sc, float sh,
-                                                  lds_float* out_q) {
-    constexpr int NV = POOL ? 2 : 4;
-    const f2 k2 = f2{2.f, 2.f}, k4 = f2{4.f, 4.f}, k8 = f2{8.f, 8.f};
-    const f2 a0 = f2{acc[0][2 * h], acc[0][2 * h + 1]};
-    const f2 a1 = f2{acc[1][2 * h], acc[1][2 * h + 1]};
-    const f2 a2 = f2{acc[2][2 * h], acc[2][2 * h + 1]};
-    const f2 a3 = f2{acc[3][2 * h], acc[3][2 * h + 1]};
-    const f2 a4 = f2{acc[4][2 * h], acc[4][2 * h + 1]};
-    const f2 a5 = f2{acc[5][2 * h], acc[5][2 * h + 1]};
-    const f2 s12 = a1 + a2, d12 = a1 - a2, s34 = a3 + a4, d34 = a3 - a4;
-    // (ReLU = the clamp modifier of each output's last instruction)
-    const f2 y0 = pk_add_relu(a0 + s12, s34);
-    const f2 y1 = pk_fma_relu(k2, d34, d12);
-    const f2 y2 = pk_fma_relu(k4, s34, s12);
-    const f2 y3 = pk_fma_relu(k8, d34, d12 + a5);      // (a5 through a visible add: see pk_fma_relu)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        float v0 = y0[e], v1 = y1[e], v2 = y2[e], v3 = y3[e];
-        // quad j = wave*16 + 2q + e + 8h = pm(4q + 2h + e); out_q = this lane's place in quad
-        // wave*16 + 2q (one address per layer; the rest are immediate offsets of the stores)
-        lds_float* dst = out_q + NV * (e + 8 * h) * kS48 + T * 16;
-        if constexpr (POOL) {
-            f2 p = f2{fmaxf(v0, v1), fmaxf(v2, v3)};
-            if (BN) p = __builtin_elementwise_fma(p, f2{sc, sc}, f2{sh, sh});
-            dst[0] = p.x;
-            dst[kS48] = p.y;
-        } else {
-            if (BN) {
-                v0 = fmaf(v0, sc, sh);
-                v1 = fmaf(v1, sc, sh);
-                v2 = fmaf(v2, sc, sh);
-                v3 = fmaf(v3, sc, sh);
-            }
-            dst[0] = v0;
-            dst[kS48] = v1;
-            dst[2 * kS48] = v2;
-            dst[3 * kS48] = v3;
-        }
-    }
-}
-
-// The same epilogue (MaxPool2 + BatchNorm) into conv1d_7's PARK in global memory (round 6): the
+// of the epilogue of N tile T of conv1d_7: output transform, ReLU, MaxPool2, BatchNorm.  MFMA row
+// m = 4q'+r' of the wave's tile works on quad pm(m) = 2q' + (r'&1) + 8(r'>>1).  The outputs go to
+// conv1d_7's PARK (global memory, or LDS for a group's last window) in the
 // layout stage D's chain loads its operands from - [half of the window][row i of the quad][channel
 // group g][lane (q, n) of the reading wave][r], channels 16g + 4q + r of position 4 (16 half + n) + i
 // (dbh_layout.h: kPark7Floats).  park_lane: this lane's place for pooled row 0 of quad 2q of its
@@ -1145,7 +903,6 @@ static_assert(kThirdPieces == 3, "");
 // have nothing to say with an address of their own in a 1 KB scratch, kChainDummy)
 // arrive_addr: lane 0 -> word 0 of kSyncTiles, the others -> scratch (chain_addresses)
 __device__ __forceinline__ void chain_arrive(unsigned arrive_addr, int t) {
-    if (DBH_ABL & 32) return;
     // release: this wave's LDS reads are done and its LDS-DMA pieces have landed
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\tds_add_u32 %0, %1 offset:%2" ::"v"(arrive_addr), "v"(1u),
                  "n"(t * 4)
@@ -1153,7 +910,6 @@ __device__ __forceinline__ void chain_arrive(unsigned arrive_addr, int t) {
 }
 template <int BASE = kSyncTiles>
 __device__ __forceinline__ void chain_wait(float* lds, int t, unsigned target) {
-    if (DBH_ABL & (1 | 32 | 128)) return;
     const unsigned addr = lds_addr(lds + BASE + t);
     for (;;) {
         unsigned seen;
@@ -1173,7 +929,6 @@ __device__ __forceinline__ unsigned chain_peek(float* lds, int t) {
 }
 template <int BASE = kSyncTiles>
 __device__ __forceinline__ void chain_check(float* lds, int t, unsigned peeked, unsigned target) {
-    if (DBH_ABL & (1 | 32 | 128)) return;
     asm volatile("" : "+v"(peeked));     // (the use stays behind the wait that retired the read)
     if ((int)(__builtin_amdgcn_readfirstlane(peeked) - target) >= 0) return;
     chain_wait<BASE>(lds, t, target);
@@ -1201,7 +956,6 @@ __device__ __forceinline__ bool halo_ready(u2 seen, unsigned target) {
 }
 template <int BASE = kSyncHalo>
 __device__ __forceinline__ void halo_wait(float* lds, int wave, unsigned target) {
-    if (DBH_ABL & (1 | 2 | 8 | 64)) return;
     const unsigned addr = lds_addr(lds + BASE + 2 * wave);
     for (;;) {
         u2 seen;
@@ -1218,7 +972,6 @@ __device__ __forceinline__ u2 halo_peek(float* lds, int wave) {
 }
 template <int BASE = kSyncHalo>
 __device__ __forceinline__ void halo_check(float* lds, int wave, u2 peeked, unsigned target) {
-    if (DBH_ABL & (1 | 2 | 8 | 64)) return;
     asm volatile("" : "+v"(peeked));
     if (halo_ready(peeked, target)) return;
     halo_wait<BASE>(lds, wave, target);
@@ -1272,12 +1025,12 @@ __device__ __forceinline__ void w43t_load_halo(f2 (&hb)[2], unsigned h_addr) {
 // One step of a chained tile.  HOFF >= 0: tile 0 of conv3 / conv4 - the step first turns
 // Y[g][h] (g = SP >> 1, h = SP & 1) and its two halo positions into U[.][SP].  pre(SP) runs in
 // front of the step's LDS requests (polls), side(SP) behind its MFMAs.
-template <int HOFF, int STEP0, int STEPS, int SP, int CATCH, int HLAY, class Pre, class Side>
+template <int HOFF, int STEP0, int STEPS, int SP, int HLAY, class Pre, class Side>
 __device__ __forceinline__ void w43t_step(W43U& U, f2 (&Y)[3][2][4], unsigned h_addr,
                                           unsigned b_addr, f2 (&hbuf)[2][2], f4 (&buf)[2][3],
                                           f4 (&acc)[6], f4 bias4, bool wave_hi, const Pre& pre,
                                           const Side& side) {
-    constexpr bool BUILD = HOFF >= 0 && !(DBH_ABL & 8);
+    constexpr bool BUILD = HOFF >= 0;
     pre(IntC<SP>{});
     if constexpr (SP + 1 < 6) {
         if constexpr (BUILD) w43t_load_halo<SP + 1, (BUILD ? HOFF : 0), HLAY>(hbuf[(SP + 1) & 1], h_addr);
@@ -1290,25 +1043,18 @@ __device__ __forceinline__ void w43t_step(W43U& U, f2 (&Y)[3][2][4], unsigned h_
     f4(&b)[3] = buf[SP & 1];
 #pragma unroll
     for (int p = 0; p < 3; ++p) asm volatile("" : "+v"(b[p]));
-    if constexpr (SP < CATCH) {
-        // the last tile before a workgroup barrier: the younger wave of the SIMD, which runs ~1k
-        // cycles behind its partner through all of stage B (the older one wins every tie), gets
-        // the pipe first for a few steps, so that the two reach the barrier together instead of
-        // the older one waiting there while the younger one finishes alone
-        if (wave_hi) __builtin_amdgcn_s_setprio(3);
-        else __builtin_amdgcn_s_setprio(0);
-    } else {
-        progress_priority_pair<STEP0 + SP, STEPS>(wave_hi);
-    }
+    // (In the last tile before a workgroup barrier the younger wave of the SIMD, which runs ~1k
+    // cycles behind its partner through all of stage B, was given the pipe first for 2, 4 or 6 steps
+    // so that the two would reach the barrier together: 44.78 - 44.85 us per 256 windows against
+    // 44.67, profiles/r05_ablation.txt.)
+    progress_priority_pair<STEP0 + SP, STEPS>(wave_hi);
     if constexpr (BUILD) {
         f2(&hb)[2] = hbuf[SP & 1];
         asm volatile("" : "+v"(hb[0]), "+v"(hb[1]));
         __builtin_amdgcn_sched_barrier(0);
         const f2(&yy)[4] = Y[SP >> 1][SP & 1];
-        const f2 d0 = (DBH_ABL & 256) ? hb[0] + yy[3]
-                                      : f2{row_from_left(hb[0].x, yy[3].x), row_from_left(hb[0].y, yy[3].y)};
-        const f2 d5 = (DBH_ABL & 256) ? hb[1] + yy[0]
-                                      : f2{row_from_right(hb[1].x, yy[0].x), row_from_right(hb[1].y, yy[0].y)};
+        const f2 d0 = f2{row_from_left(hb[0].x, yy[3].x), row_from_left(hb[0].y, yy[3].y)};
+        const f2 d5 = f2{row_from_right(hb[1].x, yy[0].x), row_from_right(hb[1].y, yy[0].y)};
         const f2 m4 = f2{-4.f, -4.f}, p2 = f2{2.f, 2.f}, m2 = f2{-2.f, -2.f};
         const f2 p4 = f2{4.f, 4.f}, m5 = f2{-5.f, -5.f};
         const f2 a = __builtin_elementwise_fma(m4, yy[1], yy[3]), b2 = __builtin_elementwise_fma(m4, yy[0], yy[2]);
@@ -1328,14 +1074,14 @@ __device__ __forceinline__ void w43t_step(W43U& U, f2 (&Y)[3][2][4], unsigned h_
     side(IntC<SP>{});
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (SP + 1 < 6)
-        w43t_step<HOFF, STEP0, STEPS, SP + 1, CATCH, HLAY>(U, Y, h_addr, b_addr, hbuf, buf, acc, bias4, wave_hi,
-                                                           pre, side);
+        w43t_step<HOFF, STEP0, STEPS, SP + 1, HLAY>(U, Y, h_addr, b_addr, hbuf, buf, acc, bias4, wave_hi, pre,
+                                                    side);
 }
 
 // bias_addr: this lane's place in the LDS parameter table (kParams + 4q); BIAS_OFF: floats from
 // there to the tile's four biases - requested first, so that step 0's hand-counted wait retires it
 // (a load the compiler sees would be waited for with lgkmcnt(0), fragment requests and all)
-template <int HOFF, int STEP0, int STEPS, int BIAS_OFF, int CATCH = 0, int HLAY = 0, class Pre, class Side>
+template <int HOFF, int STEP0, int STEPS, int BIAS_OFF, int HLAY = 0, class Pre, class Side>
 __device__ __forceinline__ void w43t_tile(W43U& U, f2 (&Y)[3][2][4], unsigned h_addr,
                                           unsigned bias_addr, const float* slot_lane,
                                           f4 (&acc)[6], bool wave_hi, const Pre& pre,
@@ -1344,9 +1090,9 @@ __device__ __forceinline__ void w43t_tile(W43U& U, f2 (&Y)[3][2][4], unsigned h_
     f2 hbuf[2][2];
     f4 buf[2][3];
     const f4 bias4 = ds_read_f4<BIAS_OFF * 4>(bias_addr);
-    if constexpr (HOFF >= 0 && !(DBH_ABL & 8)) w43t_load_halo<0, (HOFF >= 0 ? HOFF : 0), HLAY>(hbuf[0], h_addr);
+    if constexpr (HOFF >= 0) w43t_load_halo<0, (HOFF >= 0 ? HOFF : 0), HLAY>(hbuf[0], h_addr);
     w43_load_b<0>(buf[0], b_addr);
-    w43t_step<HOFF, STEP0, STEPS, 0, CATCH, HLAY>(U, Y, h_addr, b_addr, hbuf, buf, acc, bias4, wave_hi, pre, side);
+    w43t_step<HOFF, STEP0, STEPS, 0, HLAY>(U, Y, h_addr, b_addr, hbuf, buf, acc, bias4, wave_hi, pre, side);
 }
 
 struct NoPre {
@@ -1400,9 +1146,7 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
     // two edge rows to the halo arrays, and the post that announces a finished tile
     auto finish = [&](auto L_tag, auto g_tag, auto h_tag, const f4(&a)[6]) {
         constexpr int L = decltype(L_tag)::value, g = decltype(g_tag)::value, h = decltype(h_tag)::value;
-        if (DBH_ABL & 8) return;
         w43t_outputs<h>(a, Y[g][h]);
-        if (DBH_ABL & 2) return;
         asm volatile("ds_write_b64 %0, %2 offset:%4\n\tds_write_b64 %1, %3 offset:%4"
                      :
                      : "v"(a0_addr[L]), "v"(a3_addr[L]), "v"(Y[g][h][0]), "v"(Y[g][h][3]),
@@ -1415,20 +1159,12 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
     f2 X[3][2][2];
     auto store = [&](auto g_tag, auto h_tag, const f4(&a)[6]) {
         constexpr int g = decltype(g_tag)::value, h = decltype(h_tag)::value;
-        if (DBH_ABL & 16) return;
         f2 y[4];
         w43t_outputs<h>(a, y);
         // (BN2 is folded into conv5's weights and bias by the packer - dbh_api.hip: pack_weights -
         // so the pooled values go to conv5 as they are; only the debug dump applies it)
         X[g][h][0] = max_raw2(y[0], y[1]);
         X[g][h][1] = max_raw2(y[2], y[3]);
-        if (!DBH_FOLD_BN2) {
-            const f4 sc4 = tab4[((kTabBias1 - kTabBias0) + (bn_scale_offset(1) - kTabBn0)) / 4 + 4 * g];
-            const f4 sh4 = tab4[((kTabBias1 - kTabBias0) + (bn_shift_offset(1) - kTabBn0)) / 4 + 4 * g];
-            const f2 sc = h ? f2{sc4.z, sc4.w} : f2{sc4.x, sc4.y}, sh = h ? f2{sh4.z, sh4.w} : f2{sh4.x, sh4.y};
-            X[g][h][0] = __builtin_elementwise_fma(X[g][h][0], sc, sh);
-            X[g][h][1] = __builtin_elementwise_fma(X[g][h][1], sc, sh);
-        }
         if (in_a.dump_b) {          // debug_stage 1 (wave-uniform)
             const f4 sc4 = tab4[((kTabBias1 - kTabBias0) + (bn_scale_offset(1) - kTabBn0)) / 4 + 4 * g];
             const f4 sh4 = tab4[((kTabBias1 - kTabBias0) + (bn_shift_offset(1) - kTabBn0)) / 4 + 4 * g];
@@ -1436,7 +1172,7 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
             float* dst = dump_b_base() + 2 * (wave * 16 + n) * 48 + 4 * q;
 #pragma unroll
             for (int pp = 0; pp < 2; ++pp) {
-                const f2 v = DBH_FOLD_BN2 ? __builtin_elementwise_fma(X[g][h][pp], sc, sh) : X[g][h][pp];
+                const f2 v = __builtin_elementwise_fma(X[g][h][pp], sc, sh);
                 dst[pp * 48 + 16 * g + 2 * h] = v.x * kActUnscale;
                 dst[pp * 48 + 16 * g + 2 * h + 1] = v.y * kActUnscale;
             }
@@ -1466,24 +1202,18 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
     const IntC<0> c0;
     const IntC<1> c1;
     const IntC<2> c2;
-    constexpr int NW = DBH_DMA_WAVES;
-    constexpr int kThirdSteps = (kWinoHalf / 256 + NW - 1) / NW;       // 3 (5 with four waves)
-#ifndef DBH_THIRD_PACK
-#define DBH_THIRD_PACK 1
-#endif
-    // request(s) of step `step` of a third: with four requesting waves a wave has five pieces; one
-    // per step would put the last behind step 4, a step in front of the arrival that waits for it
-    // to land - two per step are through by step 2
+    constexpr int NW = kDmaWaves;
+    static_assert(NW == 4, "the request schedules below deal pieces to four waves");
+    constexpr int kThirdSteps = (kWinoHalf / 256 + NW - 1) / NW;       // a wave's pieces of a third: 5
+    // request(s) of step `step` of a third: a wave has five pieces; one per step put the last
+    // behind step 4, a step in front of the arrival that waits for it to land - two per step are
+    // through by step 2
     auto third = [&](int conv, int t, float* dst, int step) {
         const float* src = packed + weight_offset(conv) + t * kWinoHalf;
-        if (DBH_THIRD_PACK && NW < 8) {
-            if (2 * step < kThirdSteps) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step);
-            if (2 * step + 1 < kThirdSteps) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step + 1);
-        } else {
-            dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, step);
-        }
+        if (2 * step < kThirdSteps) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step);
+        if (2 * step + 1 < kThirdSteps) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step + 1);
     };
-    // conv3's 54 pieces: request i of this wave (7 per wave with eight requesters, 14 with four)
+    // conv3's 54 pieces: request i of this wave's 14
     auto conv3_piece = [&](int i) {
         dma_weights_one<3 * kWinoHalf, NW>(packed + weight_offset(2), lds + kChainW3, lane, wave, i);
     };
@@ -1492,20 +1222,16 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
     u2 pk_h = u2{0u, 0u};
 
     // ---- conv2 (its tile 0 computes conv1d_1 itself).  conv3's 54 pieces go to the idle
-    // activation buffer one behind each of the first seven steps.
+    // activation buffer two or one behind each of the first ten steps.
     {
         const f4 bias2 = tab4[B2 / 4];
         w43a_tile0(U, in_a, lds, third0, lane, acc[0], bias2, between_a, [&](auto tag) {
             constexpr int SP = decltype(tag)::value;
-            if constexpr (NW == 8) {
-                conv3_piece(SP);
-            } else {          // 2, 2, 2, 1, 1, 1
-                if constexpr (SP < 3) {
-                    conv3_piece(2 * SP);
-                    conv3_piece(2 * SP + 1);
-                } else {
-                    conv3_piece(SP + 3);
-                }
+            if constexpr (SP < 3) {          // 2, 2, 2, 1, 1, 1
+                conv3_piece(2 * SP);
+                conv3_piece(2 * SP + 1);
+            } else {
+                conv3_piece(SP + 3);
             }
         });
     }
@@ -1518,12 +1244,8 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
     w43t_tile<-1, 6, 18, B2 + 16>(U, Y, h_addr, bias_addr, lds + kSlot1 + lane * 4, acc[1], wave_hi, NoPre(),
                                   [&](auto tag) {
                                       constexpr int SP = decltype(tag)::value;
-                                      if constexpr (NW == 8) {
-                                          if constexpr (SP == 0) conv3_piece(6);
-                                      } else {          // 2, 1, 1, 1
-                                          if constexpr (SP == 0) conv3_piece(9);
-                                          if constexpr (SP < 4) conv3_piece(10 + SP);
-                                      }
+                                      if constexpr (SP == 0) conv3_piece(9);          // 2, 1, 1, 1
+                                      if constexpr (SP < 4) conv3_piece(10 + SP);
                                       if constexpr (SP == 1) finish(c0, c0, c0, acc[0]);
                                       if constexpr (SP == 3) finish(c0, c0, c1, acc[0]);
                                   });
@@ -1638,16 +1360,16 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
             // conv6's weights (9 pieces), to the upper buffer
             if constexpr (SP == 0)
                 dma_weights_one<conv_weight_floats(5), NW>(packed + weight_offset(5), lds + kW6, lane, wave, 0);
-            if constexpr (SP == (DBH_THIRD_PACK ? 1 : 2))
+            if constexpr (SP == 1)
                 dma_weights_one<conv_weight_floats(5), NW>(packed + weight_offset(5), lds + kW6, lane, wave, 1);
-            if constexpr (SP == (DBH_THIRD_PACK ? 2 : 4) && NW < 8)
+            if constexpr (SP == 2)
                 dma_weights_one<conv_weight_floats(5), NW>(packed + weight_offset(5), lds + kW6, lane, wave, 2);
             if constexpr (SP == 1) store(c0, c0, acc[0]);
             if constexpr (SP == 3) store(c0, c1, acc[0]);
         });
     chain_arrive(arrive_addr, 1);
     mark(ts, 12);
-    w43t_tile<-1, 12, 18, B4 + 32, DBH_CATCHUP>(
+    w43t_tile<-1, 12, 18, B4 + 32>(
         U, Y, h_addr, bias_addr, lds + kSlot2 + lane * 4, acc[0], wave_hi,
         [&](auto tag) {
             constexpr int SP = decltype(tag)::value;
@@ -1760,7 +1482,7 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
     mark(ts, 15);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     asm volatile("" : "+v"(hl), "+v"(hr), "+v"(pk_h));
-    if (!(DBH_ABL & (1 | 2 | 8 | 64)) && !halo_ready(pk_h, halos0 + 7)) {
+    if (!halo_ready(pk_h, halos0 + 7)) {
         halo_wait(lds, wave, halos0 + 7);
         hl = ds_read_f4<(kHaloRows + 48) * 4>(h_addr);
         hr = ds_read_f4<96 * 4>(h_addr);
@@ -1860,7 +1582,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
     const int k = wave >> 1, hf = wave & 1;
     const unsigned tiles0 = d_groups * 8u, halos0 = d_groups * 7u;
     d_groups += 1;
-    constexpr int NW = DBH_DMA_WAVES;
+    constexpr int NW = kDmaWaves;
     static_assert(NW == 4, "the request schedule below deals pieces to four waves");
     // request(s) of step `step` of a copy of NFLOATS: two per step
     auto copy_step = [&](auto nfloats_tag, const float* src, float* dst, int step) {
@@ -1964,7 +1686,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
 
     // ---- conv8.  Tile 0 builds U from Y and the partner's edge rows.
     halo_wait<kSyncDHalo>(lds, wave, halos0 + 1);
-    w43t_tile<0, 0, 18, B8, 0, 1>(
+    w43t_tile<0, 0, 18, B8, 1>(
         U, Y, h_addr, bias_addr, lds + kDS0 + lane * 4, acc[1], wave_hi, NoPre(), [&](auto tag) {
             constexpr int SP = decltype(tag)::value;
             // conv8's third 2 -> slot 2, conv9's third 0 -> slot 3 (conv1d_7's N tiles 1 and 2 lay there)
@@ -1973,7 +1695,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
         });
     chain_arrive(arrive_addr, 0);
     mark(ts, 27);
-    w43t_tile<-1, 6, 18, B8 + 16, 0, 1>(
+    w43t_tile<-1, 6, 18, B8 + 16, 1>(
         U, Y, h_addr, bias_addr, lds + kDS1 + lane * 4, acc[0], wave_hi,
         [&](auto tag) {
             if constexpr (decltype(tag)::value == 5) pk_a = chain_peek<kSyncDTiles>(lds, 0);
@@ -1987,7 +1709,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
     mark(ts, 28);
     // slots 2 and 3 have landed (requested in tile 0), and every wave has left slot 0
     chain_check<kSyncDTiles>(lds, 0, pk_a, tiles0 + 8);
-    w43t_tile<-1, 12, 18, B8 + 32, 0, 1>(
+    w43t_tile<-1, 12, 18, B8 + 32, 1>(
         U, Y, h_addr, bias_addr, lds + kDS2 + lane * 4, acc[1], wave_hi,
         [&](auto tag) {
             if constexpr (decltype(tag)::value == 5) {
@@ -2011,7 +1733,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
 
     // ---- conv9 + MaxPool + BN4.  Tile 2 of conv8 is finished inside the first two steps.
     halo_check<kSyncDHalo>(lds, wave, pk_h, halos0 + 3);
-    w43t_tile<kDHaloLayer, 0, 18, B9, 0, 1>(
+    w43t_tile<kDHaloLayer, 0, 18, B9, 1>(
         U, Y, h_addr, bias_addr, lds + kDS3 + lane * 4, acc[0], wave_hi,
         [&](auto tag) {
             constexpr int SP = decltype(tag)::value;
@@ -2032,7 +1754,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
     chain_arrive(arrive_addr, 3);
     mark(ts, 30);
     chain_check<kSyncDTiles>(lds, 2, pk_a, tiles0 + 8);      // conv9's third 1 has landed in slot 0
-    w43t_tile<-1, 6, 18, B9 + 16, 0, 1>(
+    w43t_tile<-1, 6, 18, B9 + 16, 1>(
         U, Y, h_addr, bias_addr, lds + kDS0 + lane * 4, acc[1], wave_hi,
         [&](auto tag) {
             if constexpr (decltype(tag)::value == 5) pk_a = chain_peek<kSyncDTiles>(lds, 3);
@@ -2050,7 +1772,7 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
     chain_arrive(arrive_addr, 4);
     mark(ts, 31);
     chain_check<kSyncDTiles>(lds, 3, pk_a, tiles0 + 8);      // conv9's third 2 has landed in slot 1
-    w43t_tile<-1, 12, 18, B9 + 32, 0, 1>(
+    w43t_tile<-1, 12, 18, B9 + 32, 1>(
         U, Y, h_addr, bias_addr, lds + kDS1 + lane * 4, acc[0], wave_hi,
         [&](auto tag) {
             if constexpr (decltype(tag)::value == 5) pk_a = chain_peek<kSyncDTiles>(lds, 4);
@@ -2254,10 +1976,6 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
     }
     __builtin_amdgcn_sched_barrier(0);
     mark(ts, 36);
-#if DBH_F_AHEAD_EARLY
-    ahead();
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     // ---- conv15 -> the pair of conv16's input positions (48 channels: Y16[t][p] = channels 16t + 4q + r)
     f4 Y16[3][2];
     {
@@ -2322,9 +2040,8 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
         // barrier, which retires them
 #pragma unroll
         for (int t = 0; t < 3; ++t) asm volatile("" : "+v"(U0[t]), "+v"(U1[t]), "+v"(U2[t]), "+v"(U3[t]));
-#if !DBH_F_AHEAD_EARLY
+        // (made a layer earlier, in front of conv1d_15, they gained nothing: HISTORY.md, row h3)
         ahead();
-#endif
         // The fragments of a third of the contraction at a time (four 16-byte reads: twelve
         // registers' worth less to hold beside this lane's 48 outputs), asked for ONE THIRD AHEAD
         // from inline asm and waited for by count: as plain loads hipcc put each read and an
@@ -2402,10 +2119,6 @@ __device__ __forceinline__ void stage_d_chain(float* lds, const float* __restric
     mark(ts, 33);
 }
 
-struct NoBetween {
-    __device__ __forceinline__ void operator()(int) const {}
-};
-
 // ---------------------------------------------------------------------------------------------
 // F(4,3) at L = 256 (conv7 + MaxPool + BN): 64 quads = four tiles of 16 for eight waves, 864 MFMAs
 // instead of F(2,3)'s 1,152.  The two waves of a SIMD, w and w + 4, share tile w & 3 and split its
@@ -2440,12 +2153,6 @@ struct W43nsPipe {
     f4 b[2][3];      // [step parity][matrix pair]
 };
 
-// How the six channel groups of conv7's shared N tile are split between the two waves of a SIMD:
-// the older one (w < 4) takes the first DBH_CONV7_LOW, the younger one the rest.  (3 / 3 until
-// round 5; the older wave wins every tie for the matrix pipe and reached the exchange first.)
-#ifndef DBH_CONV7_LOW
-#define DBH_CONV7_LOW 3
-#endif
 // Step G of a wave's 6 + n: G < 6 = channel group G of its own N tile (TOWN) and of U; G >= 6 =
 // channel group SP0 + G - 6 of the shared N tile 1.  One software pipeline.
 template <int TOWN, int SP0, bool WITH_BIAS, int G, class Side>
@@ -2460,7 +2167,7 @@ __device__ __forceinline__ void w43ns_step(W43U& U, unsigned a_addr, unsigned b_
         pipe.b[N & 1][1] = ds_read_f4<(T * kWinoHalf + (SP * 3 + 1) * 256) * 4>(b_addr);
         pipe.b[N & 1][2] = ds_read_f4<(T * kWinoHalf + (SP * 3 + 2) * 256) * 4>(b_addr);
     };
-    constexpr int GEND = 6 + (SP0 == 0 ? DBH_CONV7_LOW : 6 - DBH_CONV7_LOW);
+    constexpr int GEND = 6 + (SP0 == 0 ? kConv7Low : 6 - kConv7Low);
     if constexpr (G == 0) loads(IntC<0>{});
     if constexpr (G + 1 < GEND) {
         loads(IntC<G + 1>{});
@@ -2539,17 +2246,14 @@ __device__ __forceinline__ void w43_partial_outputs(const f4 (&acc)[6], int h, f
 // (a full barrier) before anything reads what they bring.
 //   LAST = true (the group's last window, which stage D follows at once): the output goes to the
 // same layout in LDS (kPark7Lds: rows of the input image every wave has read by the mid-layer
-// barrier) and the layer ends with a full barrier, which then has nothing slow to wait for.
-//   after(): the caller's requests behind the layer's last MFMAs (U and the pipeline are dead: ~120
-// free registers); returns how many of them - the wave's newest - may still be in flight behind
-// the LAST form's closing barrier.
-template <int CONV, int BNI, bool HIGH, bool LAST, class Side, class After>
+// barrier); what side(0..5) asked for was retired by the mid-layer barrier, what side(6) asks for
+// (loads to registers) is waited for where it is used.
+template <int CONV, int BNI, bool HIGH, bool LAST, class Side>
 __device__ __forceinline__ void w43_nsplit_half(float* lds, const float* __restrict__ packed,
                                                 float* __restrict__ park, int tid, int lane,
                                                 int wave, unsigned* ts, int ts_base,
-                                                unsigned& pair_rounds, const Side& side,
-                                                const After& after) {
-    constexpr int TOWN = HIGH ? 2 : 0, SP0 = HIGH ? DBH_CONV7_LOW : 0;
+                                                unsigned& pair_rounds, const Side& side) {
+    constexpr int TOWN = HIGH ? 2 : 0, SP0 = HIGH ? kConv7Low : 0;
     const int n = lane & 15, q = lane >> 4;
     const int m = wave & 3;
     EpiParams<3, true> ep;
@@ -2587,7 +2291,6 @@ __device__ __forceinline__ void w43_nsplit_half(float* lds, const float* __restr
             if constexpr (G == 6) w43_epilogue_half_park<TOWN, ParkPtr>(own, 0, ep.sc[TOWN], ep.sh[TOWN], park_lane);
             if constexpr (G == 7) w43_epilogue_half_park<TOWN, ParkPtr>(own, 1, ep.sc[TOWN], ep.sh[TOWN], park_lane);
         });
-    const bool in_flight = after();
     // the shared N tile: the partial outputs of this wave's three channel groups
     f2 y[2][4];
     w43_partial_outputs(shared, 0, y[0]);
@@ -2615,477 +2318,20 @@ __device__ __forceinline__ void w43_nsplit_half(float* lds, const float* __restr
             // quad offset e + 8h from the lane's first (pm(4q + 2h + e)); pooled row 2e + (HIGH ? 1 : 0)
             park_lane[(2 * e + (HIGH ? 1 : 0)) * 768 + 256 + h * 16] = p;
         }
-    if constexpr (LAST) {
-        // (the weights stage D's first tiles read have landed: requested before after()'s twelve
-        // loads, and loads return in order; this form has no stores in flight)
-        (void)in_flight;       // (what was asked for before the mid-layer barrier was retired there)
-        lds_barrier();
-    } else {
-        lds_barrier();
-    }
+    lds_barrier();
     mark(ts, LAST ? ts_base + 2 : ts_base + 3);      // (the LAST form is stamped 59, 60, 61)
 }
 
-struct NoAfter {
-    __device__ __forceinline__ bool operator()() const { return false; }
-};
-template <int CONV, int BNI, bool LAST, class Side, class After = NoAfter>
+template <int CONV, int BNI, bool LAST, class Side>
 __device__ __forceinline__ void w43_nsplit_pooled_layer(float* lds, const float* __restrict__ packed,
                                                         float* __restrict__ park, int tid, int lane,
                                                         int wave, unsigned* ts, int ts_base,
-                                                        unsigned& pair_rounds, const Side& side,
-                                                        const After& after = After()) {
+                                                        unsigned& pair_rounds, const Side& side) {
     static_assert(kConv[CONV].wino == 4 && kConv[CONV].cin == 48 && kConv[CONV].cout_pad == 48, "");
     if (wave < 4)
-        w43_nsplit_half<CONV, BNI, false, LAST>(lds, packed, park, tid, lane, wave, ts, ts_base, pair_rounds, side, after);
+        w43_nsplit_half<CONV, BNI, false, LAST>(lds, packed, park, tid, lane, wave, ts, ts_base, pair_rounds, side);
     else
-        w43_nsplit_half<CONV, BNI, true, LAST>(lds, packed, park, tid, lane, wave, ts, ts_base, pair_rounds, side, after);
-}
-
-// ---------------------------------------------------------------------------------------------
-// A small-M layer (one 16-position tile: conv17/18/19).  Each weight is used once per window,
-// so B fragments skip LDS: every wave fetches its share from L2 into registers well AHEAD of
-// use (SmallMRegs::prefetch).  A wave owns NTW of the 3 N tiles and 1/KS of the contraction:
-//   conv17 (K = 576): KS = 8, NTW = 3 -> all 8 waves, 54 MFMAs each, partial tiles summed via LDS;
-//   conv18/19 (K = 144): KS = 1, NTW = 1 -> 3 waves, 36 MFMAs each, no reduction phase at all.
-// ---------------------------------------------------------------------------------------------
-template <int CONV, int KS, int NTW, bool BN>
-struct SmallMRegs {
-    static constexpr int TAPS = kConv[CONV].taps;
-    static constexpr int SPTOT = kConv[CONV].cin / 8;
-    static constexpr int SP = SPTOT / KS;
-    static constexpr int NGROUPS = 3 / NTW;             // wave groups along N
-    static constexpr int ACTIVE = KS * NGROUPS;
-    static_assert(SP * KS == SPTOT && NGROUPS * NTW == 3 && ACTIVE <= kWaves, "bad split");
-    f2 b[TAPS * SP * NTW];
-    EpiParams<1, BN> ep;
-    __device__ __forceinline__ void prefetch(const float* __restrict__ packed, int bn_index,
-                                             int lane, int wave) {
-        if (ACTIVE == kWaves || wave < ACTIVE) {
-            const int t0 = (wave % NGROUPS) * NTW, ks = wave / NGROUPS;
-            const float* b_lane = packed + weight_offset(CONV) + (ks * SP * 3 + t0) * 128 + lane * 2;
-#pragma unroll
-            for (int tap = 0; tap < TAPS; ++tap)
-#pragma unroll
-                for (int sp = 0; sp < SP; ++sp)
-#pragma unroll
-                    for (int t = 0; t < NTW; ++t)
-                        b[(tap * SP + sp) * NTW + t] = *reinterpret_cast<const f2*>(
-                            b_lane + ((tap * SPTOT + sp) * 3 + t) * 128);
-        }
-        prefetch_epilogue(packed, bn_index, lane, wave);
-    }
-    __device__ __forceinline__ void prefetch_epilogue(const float* __restrict__ packed,
-                                                      int bn_index, int lane, int wave) {
-        if (wave < 3) {     // the waves that run the epilogue (one N tile each)
-            const int ch = wave * 16 + (lane & 15);
-            ep.load(packed + bias_offset(CONV) + ch,
-                    packed + (BN ? bn_scale_offset(bn_index) : 0) + ch,
-                    packed + (BN ? bn_shift_offset(bn_index) : 0) + ch);
-        }
-    }
-    // fragments [K0, K1) only - for trickling the fetch across the steps of an earlier layer
-    template <int K0, int K1>
-    __device__ __forceinline__ void prefetch_slice(const float* __restrict__ packed, int lane,
-                                                   int wave) {
-        if (ACTIVE == kWaves || wave < ACTIVE) {
-            const int t0 = (wave % NGROUPS) * NTW, ks = wave / NGROUPS;
-            // buffer loads: the wave's part of the address is scalar, the lane's one shift
-            const __amdgpu_buffer_rsrc_t view = buffer_view(packed + weight_offset(CONV));
-            const unsigned wave_bytes = (unsigned)((ks * SP * 3 + t0) * 128) * 4u;
-            const unsigned lane_bytes = (unsigned)lane * 8u;
-#pragma unroll
-            for (int k = K0; k < K1; ++k) {
-                const int t = k % NTW, sp = (k / NTW) % SP, tap = k / (NTW * SP);
-                b[k] = buffer_load_f2(view, lane_bytes,
-                                      wave_bytes + (unsigned)(((tap * SPTOT + sp) * 3 + t) * 128) * 4u);
-            }
-        }
-    }
-};
-
-// TO_GLOBAL: out_region is a dense [16][48] block in global memory (row 0 = position 0) instead
-// of an LDS activation buffer, and the layer ends without a barrier of its own.
-// pre_barrier / post_barrier: work of the caller's that rides on the layer's one barrier (every
-// wave calls pre_barrier before it, post_barrier after it).
-// between(tap): a request of the caller's behind the MFMAs of tap `tap` (LDS-DMA pieces: one at a
-// time between MFMAs instead of a bunch in front of them).
-// all_waves (TO_GLOBAL only): the partial tiles are summed by ALL eight waves, 24 of the 192 output
-// quadruples each (ep_all: bias / BN of this lane's quadruple: small_m_all_params), instead of by
-// waves 0-2 while the others wait for them at the next barrier.
-template <int CONV, int S_IN, int STRIDE, int KS, int NTW, bool POOL, bool BN, bool TO_GLOBAL = false,
-          class PreBarrier = NoHook, class PostBarrier = NoHook, class Between = NoBetween>
-__device__ __forceinline__ void small_m_layer(float* lds, const float* in_region, float* out_region,
-                                              float* red, const SmallMRegs<CONV, KS, NTW, BN>& regs, int lane,
-                                              int wave, unsigned* ts, int ts_base,
-                                              const PreBarrier& pre_barrier = PreBarrier(),
-                                              const PostBarrier& post_barrier = PostBarrier(),
-                                              const Between& between = Between(),
-                                              const EpiParams<1, BN>* ep_all = nullptr) {
-    using R = SmallMRegs<CONV, KS, NTW, BN>;
-    constexpr int TAPS = R::TAPS, SP = R::SP;
-    const int n = lane & 15, q = lane >> 4;
-    f4 acc[1][NTW];
-    zero_acc(acc);
-    if (wave < R::ACTIVE) {
-        const int ks = wave / R::NGROUPS;
-        // stride-2 'same' pads on the right only: logical row 2p+tap = physical row 2p+tap+1;
-        // stride-1 'same' k=3: physical row p+tap.
-        const int first = (STRIDE == 2) ? 1 : 0;
-        const float* a_lane = in_region + (first + n * STRIDE) * S_IN + 2 * q + ks * SP * 8;
-        // even/odd k-steps accumulate separately so consecutive MFMAs never wait on each other
-        f4 odd[NTW];
-#pragma unroll
-        for (int t = 0; t < NTW; ++t) odd[t] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int tap = 0; tap < TAPS; ++tap) {
-            f2 a[SP];
-#pragma unroll
-            for (int sp = 0; sp < SP; ++sp)
-                a[sp] = *reinterpret_cast<const f2*>(a_lane + tap * S_IN + sp * 8);
-#pragma unroll
-            for (int sp = 0; sp < SP; ++sp)
-#pragma unroll
-                for (int t = 0; t < NTW; ++t) {
-                    const f2 bw = regs.b[(tap * SP + sp) * NTW + t];
-                    acc[0][t] = mfma4(a[sp].x, bw.x, acc[0][t]);
-                    odd[t] = mfma4(a[sp].y, bw.y, odd[t]);
-                }
-            between(tap);
-        }
-#pragma unroll
-        for (int t = 0; t < NTW; ++t) acc[0][t] += odd[t];
-    }
-    if constexpr (KS > 1) {
-        static_assert(NTW == 3, "split-K path assumes every wave holds all three N tiles");
-        if (wave < R::ACTIVE) {
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-                *reinterpret_cast<f4*>(red + (wave * 3 + t) * 256 + lane * 4) = acc[0][t];
-        }
-        pre_barrier();
-        mark(ts, ts_base);
-        lds_barrier();
-        mark(ts, ts_base + 1);
-        post_barrier();
-        if (ep_all != nullptr) {
-            if constexpr (TO_GLOBAL) {
-                if (lane < 24) {
-                    const int e = wave * 24 + lane, t = e >> 6, l2 = e & 63;
-                    f4 sum[1][1];
-                    sum[0][0] = *reinterpret_cast<const f4*>(red + t * 256 + l2 * 4);
-#pragma unroll
-                    for (int ks = 1; ks < KS; ++ks)
-                        sum[0][0] += *reinterpret_cast<const f4*>(red + (ks * 3 + t) * 256 + l2 * 4);
-                    epilogue<1, 1, 48, false, BN>(sum, out_region + 4 * (l2 >> 4) * 48 + t * 16 + (l2 & 15), *ep_all);
-                }
-            }
-        } else if (wave < 3) {
-            const int t = wave;
-            f4 sum[1][1];
-            sum[0][0] = *reinterpret_cast<const f4*>(red + t * 256 + lane * 4);
-#pragma unroll
-            for (int ks = 1; ks < KS; ++ks)
-                sum[0][0] +=
-                    *reinterpret_cast<const f4*>(red + (ks * 3 + t) * 256 + lane * 4);
-            if constexpr (TO_GLOBAL) {
-                static_assert(!POOL, "");
-                epilogue<1, 1, 48, false, BN>(sum, out_region + 4 * q * 48 + t * 16 + n, regs.ep);
-            } else {
-                float* out_lane = out_region + (1 + (POOL ? 2 * q : 4 * q)) * kS48 + t * 16 + n;
-                epilogue<1, 1, kS48, POOL, BN>(sum, out_lane, regs.ep);
-            }
-        }
-    } else {
-        static_assert(NTW == 1, "direct path: one N tile per wave");
-        mark(ts, ts_base);
-        mark(ts, ts_base + 1);
-        if (wave < 3) {
-            float* out_lane = out_region + (1 + (POOL ? 2 * q : 4 * q)) * kS48 + wave * 16 + n;
-            epilogue<1, 1, kS48, POOL, BN>(acc, out_lane, regs.ep);
-        }
-    }
-    mark(ts, ts_base + 2);
-    if constexpr (!TO_GLOBAL) full_barrier();  
-    mark(ts, ts_base + 3);
-}
-
-// One wave's share of the 1x1 convolutions of the inception block (4 position tiles x 1 N tile).
-// ep: bias (and BN5 scale / shift) of this lane's channel, loaded by the caller ahead of the call
-template <int NTTOT, int S_OUT, bool POOLBN>
-__device__ __forceinline__ void inception_1x1(const float* in_region, const float* w_lds,
-                                              float* out_region, int out_ch,
-                                              const EpiParams<1, POOLBN>& ep, int t, int lane) {
-    const int n = lane & 15, q = lane >> 4;
-    f4 acc[4][1];
-    bias_acc(acc, ep);
-    conv_tiles<1, 6, 6, 4, 1, NTTOT, kS48, 16>(in_region + (n + 1) * kS48 + 2 * q,
-                                               w_lds + t * 128 + lane * 2, acc);
-    float* out_lane = out_region + (1 + (POOLBN ? 2 * q : 4 * q)) * S_OUT + out_ch + n;
-    epilogue<4, 1, S_OUT, POOLBN, POOLBN, false>(acc, out_lane, ep);
-}
-
-// conv10 reads AveragePooling1D(3, stride 1, 'same') of X.  A 1x1 convolution commutes with a
-// pooling along the positions: W . (x[p-1] + x[p] + x[p+1]) / c[p] = (z[p-1] + z[p] + z[p+1]) / c[p]
-// with z = W . x (no bias, z = 0 outside the window; c[p] = the number of taps inside it:
-// TensorFlow's valid-count divisor, oracle/network_ref.py).  So the convolution runs on X itself
-// and the pooling on its OUTPUT, in registers: the wave holds all 64 positions of its 16 channels
-// (lane (n, q), tile m, register r <-> position 16 m + 4 q + r), the neighbours across the lane
-// groups come by ds_bpermute.  No average-pooled copy of X in LDS, no phase of its own (it cost
-// ~1.7k cycles per window with its barrier: profiles/r03_v1/timeline_5120_fused.txt, "E0").
-// Then bias, ReLU, MaxPool2, BN5 as everywhere.
-template <int NTTOT, int S_OUT>
-__device__ __forceinline__ void inception_1x1_of_avgpool(const float* in_region, const float* w_lds,
-                                                         float* out_region, int out_ch,
-                                                         const EpiParams<1, true>& ep, int t,
-                                                         int lane) {
-    const int n = lane & 15, q = lane >> 4;
-    f4 z[4][1];
-    zero_acc(z);
-    conv_tiles<1, 6, 6, 4, 1, NTTOT, kS48, 16>(in_region + (n + 1) * kS48 + 2 * q,
-                                               w_lds + t * 128 + lane * 2, z);
-    // position 4q - 1 lives in register 3 of the lane group before (the tile before, for q = 0),
-    // position 4q + 4 in register 0 of the lane group behind
-    const int from_before = ((lane + 48) & 63) * 4, from_behind = ((lane + 16) & 63) * 4;
-    float before[4], behind[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        // (pinned copies: handed z[m][0].w directly, this hipcc sends register x both times)
-        float last = z[m][0].w, first = z[m][0].x;
-        asm volatile("" : "+v"(last), "+v"(first));
-        before[m] = __builtin_bit_cast(
-            float, __builtin_amdgcn_ds_bpermute(from_before, __builtin_bit_cast(int, last)));
-        behind[m] = __builtin_bit_cast(
-            float, __builtin_amdgcn_ds_bpermute(from_behind, __builtin_bit_cast(int, first)));
-    }
-    const float third = 1.f / 3.f, b = ep.b[0], sc = ep.sc[0], sh = ep.sh[0];
-    float* out_lane = out_region + (1 + 2 * q) * S_OUT + out_ch + n;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const float prev = q > 0 ? before[m] : (m > 0 ? before[m > 0 ? m - 1 : 0] : 0.f);
-        const float next = q < 3 ? behind[m] : (m < 3 ? behind[m < 3 ? m + 1 : 3] : 0.f);
-        const f4 v = z[m][0];
-        const float t1 = v.x + v.y, t2 = v.z + v.w;
-        // x (1 / count), not / count: one ulp of the quotient is far inside the tolerance
-        const float inv0 = (m == 0 && q == 0) ? 0.5f : third;
-        const float inv3 = (m == 3 && q == 3) ? 0.5f : third;
-        const float y0 = fmaxf(fmaf(prev + t1, inv0, b), 0.f);
-        const float y1 = fmaxf(fmaf(t1 + v.z, third, b), 0.f);
-        const float y2 = fmaxf(fmaf(v.y + t2, third, b), 0.f);
-        const float y3 = fmaxf(fmaf(t2 + next, inv3, b), 0.f);
-        out_lane[(m * 8 + 0) * S_OUT] = fmaf(fmaxf(y0, y1), sc, sh);
-        out_lane[(m * 8 + 1) * S_OUT] = fmaf(fmaxf(y2, y3), sc, sh);
-    }
-}
-
-// The 16 -> 48, k = 3 convolutions of the inception block (conv13, conv15; L = 64) as Winograd
-// F(2,3): pair tile m (16 pairs = 32 positions) x NT channel tiles from tile T0, 16 MFMAs per
-// (pair tile, channel tile) instead of the direct form's 24.  POOLBN: the pair's two outputs are
-// max-pooled (that IS MaxPool2) and batch-normalised into the concat buffer; otherwise both are
-// stored, ReLU'd.  Pointers are for channel tile T0.
-template <int NT, int S_OUT, bool POOLBN>
-__device__ __forceinline__ void inception_k3_wino(const float* in_region, const float* w_tile0,
-                                                  float* out_region, int out_ch,
-                                                  const float* __restrict__ bias_lane,
-                                                  const float* __restrict__ scale_lane,
-                                                  const float* __restrict__ shift_lane, int m,
-                                                  int lane) {
-    const int n = lane & 15, q = lane >> 4;
-    EpiParams<NT, POOLBN> ep;
-    ep.load(bias_lane, scale_lane, shift_lane);
-    float bias[3] = {ep.b[0], NT > 1 ? ep.b[NT > 1 ? 1 : 0] : 0.f, NT > 2 ? ep.b[NT > 2 ? 2 : 0] : 0.f};
-    // pair j = m*16 + n needs logical rows 2j-1 .. 2j+2 = physical rows 2j .. 2j+3
-    const unsigned a_addr = lds_addr(in_region + (m * 32 + 2 * n) * kS16 + 2 * q);
-    const unsigned b_addr = lds_addr(w_tile0 + lane * 4);
-    W23U16 U;
-    W23Pipe16 pipe;
-    f4 acc[3][4];
-    w23c16_step<0, 2 * NT>(U, a_addr, b_addr, pipe, acc, bias, NoSide());
-    // pair m*16 + 4q + r of the window -> pooled position (same number) or positions 2j, 2j + 1
-    float* out_lane = out_region + (1 + (POOLBN ? 1 : 2) * (m * 16 + 4 * q)) * S_OUT + out_ch + n;
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float even = acc[t][0][r] + acc[t][1][r] + acc[t][2][r];
-            const float odd = acc[t][1][r] - acc[t][2][r] - acc[t][3][r];
-            if constexpr (POOLBN) {
-                const float o = fmaxf(fmaxf(even, odd), 0.f);
-                out_lane[r * S_OUT + t * 16] = fmaf(o, ep.sc[t], ep.sh[t]);
-            } else {
-                out_lane[(2 * r) * S_OUT + t * 16] = fmaxf(even, 0.f);
-                out_lane[(2 * r + 1) * S_OUT + t * 16] = fmaxf(odd, 0.f);
-            }
-        }
-}
-
-// k=3 convolution of the inception block: MT position tiles from tile m0 x NT channel tiles
-// from tile t (pointers are for channel tile t; NT > 1 walks on in steps of 16 channels).
-template <int SP, int MT, int NT, int S_IN, int S_OUT, bool POOLBN>
-__device__ __forceinline__ void inception_k3(const float* in_region, const float* w_lds,
-                                             float* out_region, int out_ch,
-                                             const float* __restrict__ bias_lane,
-                                             const float* __restrict__ scale_lane,
-                                             const float* __restrict__ shift_lane, int t, int m0,
-                                             int lane) {
-    const int n = lane & 15, q = lane >> 4;
-    EpiParams<NT, POOLBN> ep;
-    ep.load(bias_lane, scale_lane, shift_lane);
-    f4 acc[MT][NT];
-    bias_acc(acc, ep);
-    conv_tiles<3, SP, SP, MT, NT, 3, S_IN, 16>(in_region + (m0 * 16 + n) * S_IN + 2 * q,
-                                               w_lds + t * 128 + lane * 2, acc);
-    float* out_lane = out_region +
-                      (1 + (POOLBN ? m0 * 8 + 2 * q : m0 * 16 + 4 * q)) * S_OUT + out_ch + n;
-    epilogue<MT, NT, S_OUT, POOLBN, POOLBN, false>(acc, out_lane, ep);
-}
-
-// ---------------------------------------------------------------------------------------------
-// make_sum_to_one + barcode call for one read held by a 32-lane group (lane c = class c):
-// classify.py:387-393 in fp64 (what NumPy-1.x scalar promotion gave the reference) and
-// classify.py:285-295 (ties to the lower class index: Python's stable sort with reverse=True).
-// Shared by the stand-alone merge kernel and the forward kernel's fused single-step finish.
-// ---------------------------------------------------------------------------------------------
-// 64-bit / index moves inside a 16-lane row (DPP, no LDS round trip) for the reductions below.
-template <int CTRL>
-__device__ __forceinline__ int dpp_move_i32(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp_move_f64(double v) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const unsigned lo = (unsigned)dpp_move_i32<CTRL>((int)b);
-    const unsigned hi = (unsigned)dpp_move_i32<CTRL>((int)(b >> 32));
-    return __builtin_bit_cast(double, (long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// The 32 lanes c = 0..31 of one read (two 16-lane rows) finish it: make_sum_to_one in fp64
-// (classify.py:387-393), then the top-two call rule (classify.py:285-295; ties to the lower
-// index).  Each all-reduce is four DPP steps inside the rows plus one v_permlane16_swap across
-// them - five ds_bpermute rounds of 64-bit values apiece made this the slowest 3k cycles of a
-// window.
-template <class T, class Combine>
-__device__ __forceinline__ T reduce32(T v, const Combine& combine) {
-    v = combine(v, T::template moved<0xB1>(v));     // quad_perm [1,0,3,2]
-    v = combine(v, T::template moved<0x4E>(v));     // quad_perm [2,3,0,1]
-    v = combine(v, T::template moved<0x141>(v));    // row_half_mirror
-    v = combine(v, T::template moved<0x140>(v));    // row_mirror
-    T row0, row1;                                   // both rows' results, seen from both rows
-    T::rows(v, &row0, &row1);
-    return combine(row0, row1);
-}
-// v_permlane16_swap_b32 (gfx950): (x, x) -> {the even row's x in both rows of a pair, the odd
-// row's x in both rows} - the cross-row step of a 32-lane reduction without an LDS round trip.
-__device__ __forceinline__ void rows_i32(int x, int* even, int* odd) {
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
-    *even = (int)r[0];
-    *odd = (int)r[1];
-}
-__device__ __forceinline__ void rows_f64(double x, double* even, double* odd) {
-    const long long b = __builtin_bit_cast(long long, x);
-    int lo0, lo1, hi0, hi1;
-    rows_i32((int)b, &lo0, &lo1);
-    rows_i32((int)(b >> 32), &hi0, &hi1);
-    *even = __builtin_bit_cast(double, (long long)(((unsigned long long)(unsigned)hi0 << 32) | (unsigned)lo0));
-    *odd = __builtin_bit_cast(double, (long long)(((unsigned long long)(unsigned)hi1 << 32) | (unsigned)lo1));
-}
-struct RedF64 {
-    double v;
-    template <int CTRL>
-    static __device__ __forceinline__ RedF64 moved(const RedF64& a) {
-        return RedF64{dpp_move_f64<CTRL>(a.v)};
-    }
-    static __device__ __forceinline__ void rows(const RedF64& a, RedF64* even, RedF64* odd) {
-        rows_f64(a.v, &even->v, &odd->v);
-    }
-};
-struct RedBest {
-    double v;
-    int i;
-    template <int CTRL>
-    static __device__ __forceinline__ RedBest moved(const RedBest& a) {
-        return RedBest{dpp_move_f64<CTRL>(a.v), dpp_move_i32<CTRL>(a.i)};
-    }
-    static __device__ __forceinline__ void rows(const RedBest& a, RedBest* even, RedBest* odd) {
-        rows_f64(a.v, &even->v, &odd->v);
-        rows_i32(a.i, &even->i, &odd->i);
-    }
-};
-
-__device__ __forceinline__ void renormalise_and_call(float merged, int c, int n_classes,
-                                                     double score_diff, float* probs_row,
-                                                     int* call_out) {
-    const bool valid = c < n_classes;
-    double p = (double)merged;
-    const double rest =
-        reduce32(RedF64{(valid && c > 0) ? p : 0.0},
-                 [](const RedF64& a, const RedF64& b) { return RedF64{a.v + b.v}; }).v;
-    // (class 0 of this lane's half; the source lane made here: as a loop invariant its byte address
-    // was kept in a register around the whole persistent loop - and spilled)
-    int half_first;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(half_first));
-    half_first = (half_first & 32) << 2;
-    const long long p_bits = __builtin_bit_cast(long long, p);
-    const unsigned p0_lo = (unsigned)__builtin_amdgcn_ds_bpermute(half_first, (int)(unsigned)p_bits);
-    const unsigned p0_hi = (unsigned)__builtin_amdgcn_ds_bpermute(half_first, (int)(p_bits >> 32));
-    const double p0 = __builtin_bit_cast(double, ((long long)p0_hi << 32) | (long long)p0_lo);
-    const double factor = (1.0 - p0) / rest;
-    if (c > 0) p = p * factor;
-    if (valid) probs_row[c] = (float)p;
-
-    const RedBest best = reduce32(RedBest{valid ? p : -1.0, c}, [](const RedBest& a, const RedBest& b) {
-        return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-    });
-    const double second =
-        reduce32(RedF64{(valid && c != best.i) ? p : -1.0},
-                 [](const RedF64& a, const RedF64& b) { return RedF64{fmax(a.v, b.v)}; }).v;
-    if (c == 0) *call_out = (best.i != 0 && (best.v - second) >= score_diff) ? best.i : 0;
-}
-
-// Window w of a launch = (read w / steps, scan step w % steps).  Window indices fit 32 bits
-// (n_windows is an int) and steps == 1 - whole reads, the classify path - needs no division at
-// all; a 64-bit division is ~150 scalar instructions that every wave would run per window.
-__device__ __forceinline__ void split_window(unsigned win, int steps, unsigned* read, int* step) {
-    if (steps == 1) {
-        *read = win;
-        *step = 0;
-    } else {
-        *read = win / (unsigned)steps;
-        *step = (int)(win - *read * (unsigned)steps);
-    }
-}
-
-// Window bounds of scan step `step` inside a read of `len` samples (classify.py:337-349).
-__device__ __forceinline__ void window_bounds(long long len, int step, int side, long long* a,
-                                              long long* b) {
-    const long long sig_start = (long long)step * (kWindow / 2);
-    const long long sig_end = sig_start + kWindow;
-    if (side == 0) {
-        *a = sig_start < len ? sig_start : len;
-        *b = sig_end < len ? sig_end : len;
-    } else {
-        *a = len - sig_end > 0 ? len - sig_end : 0;
-        *b = len - sig_start > 0 ? len - sig_start : 0;
-    }
-}
-
-// z-normalisation constants from exact integer sums (trim_signal.py:61-69): x -> (x - mean) * inv
-// with mean = sum(x)/n and inv = 1/std = n / sqrt(n*sum(x^2) - sum(x)^2), the radicand exact in
-// int64; inv = 1 when std is 0 (the reference then only subtracts the mean).  Two fp64 divisions
-// and one square root per window instead of a division per sample: fp64 division is ~20
-// instructions at half rate, and stage A has nothing to hide them behind.  The product differs
-// from the reference's quotient by at most one fp64 ulp before the cast to fp32 (the parity
-// tests allow one fp32 ulp; both normalising kernels share this function, so they agree to the
-// bit with each other).
-__device__ __forceinline__ void mean_std(long long s1, long long s2, int cnt, double* mean,
-                                         double* inv) {
-    *mean = 0.0;
-    *inv = 1.0;
-    if (cnt > 0) {
-        *mean = (double)s1 / (double)cnt;
-        const long long num = (long long)cnt * s2 - s1 * s1;
-        if (num > 0) *inv = (double)cnt / sqrt((double)num);
-    }
+        w43_nsplit_half<CONV, BNI, true, LAST>(lds, packed, park, tid, lane, wave, ts, ts_base, pair_rounds, side);
 }
 
 // A pointer read from the kernel-argument segment is a generic ("flat") pointer to the compiler,
@@ -3177,7 +2423,7 @@ __device__ __forceinline__ void fetch_window(const int16_t* __restrict__ samples
                                              long long len, int step, int side, int tid, int j,
                                              int q, int& cnt, int& v0, int& v1, int (&raw)[6]) {
     long long wa, wb;
-    window_bounds(len, step, side, &wa, &wb);
+    window_bounds(len, step, side, kWindow, &wa, &wb);
     cnt = (int)(wb - wa);
     fetch_window_at(samples + base + wa, cnt, (side == 0) ? 0 : kWindow - cnt, tid, j, q, v0, v1,
                     raw);
@@ -3293,19 +2539,7 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
     // debug_stage >= 0 (tests, timeline): the batched tail runs behind every group
     const bool tail_every_group = debug_stage >= 0;
 
-    // the first window of the next group, fetched under the group's last stage F: count, left padding
-    // and this lane's two samples
-    int carry_cnt = 0, carry_pad = 0, carry_v0 = 0, carry_v1 = 0;
-
     while (group_n > 0) {
-    // (taken over and cleared at once: defined on every path round the loop, the four do not count as
-    // live across stage B)
-    const int first_cnt = carry_cnt, first_pad = carry_pad;
-    int first_v0 = carry_v0, first_v1 = carry_v1;
-    carry_cnt = 0;
-    carry_pad = 0;
-    carry_v0 = 0;
-    carry_v1 = 0;
     // how many windows the NEXT group asks for: by what was left when this one was handed out
     const int left_now = n_windows - (group_start + group_n);
     const int chunk_next = win_counter_entry == nullptr             ? kGroup
@@ -3446,11 +2680,12 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
                 window_mean_inv(lds, in_cnt, &mean, &inv);
             } else {
                 int cnt, pad;
-                if (k == 0 && DBH_STATS0_IN_F) {
+                if (k == 0) {
                     // the group's first window was staged like the others (its statistics by wave 4
                     // under the group before's stage F); the barrier publishes slot 0's weights
                     // (asked for in that stage F) and keeps this group off the LDS that group's last
-                    // reads still use
+                    // reads still use.  (At first this window came in registers and every wave
+                    // summed and divided behind this barrier: 0.4 % slower.)
                     full_barrier();
                     mark(ts, 51);
                     thirds_mode = thirds_ahead ? 0 : 2;
@@ -3459,21 +2694,6 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
                     inv = reinterpret_cast<const double*>(st)[1];
                     cnt = reinterpret_cast<const int*>(st)[4];
                     pad = reinterpret_cast<const int*>(st)[5];
-                } else if (k == 0) {
-                    // the group's first window came in registers (fetched under the last stage F of
-                    // the group before): its samples go to the staging and its exact sums ride on
-                    // the barrier that also publishes slot 0's weights (asked for in that stage F)
-                    // and keeps this group off the LDS that group's last reads still use
-                    short* put = reinterpret_cast<short*>(lds + kStage);
-                    put[tid] = (short)first_v0;
-                    put[tid + 512] = (short)first_v1;
-                    window_partial_sums(lds, first_cnt, first_v0, first_v1, tid, lane, wave);
-                    full_barrier();
-                    mark(ts, 51);
-                    window_mean_inv(lds, first_cnt, &mean, &inv);
-                    cnt = first_cnt;
-                    pad = first_pad;
-                    thirds_mode = thirds_ahead ? 0 : 2;
                 } else {
                     thirds_mode = 1;
                     const float* st = lds + kStageStats + k * 8;
@@ -3571,7 +2791,7 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
     }
     {
         auto third_step = [&](const float* src, float* dst, int step) {
-            constexpr int NW = DBH_DMA_WAVES;
+            constexpr int NW = kDmaWaves;
             constexpr int per_wave = (kWinoHalf / 256 + NW - 1) / NW;
             if (2 * step < per_wave) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step);
             if (2 * step + 1 < per_wave) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step + 1);
@@ -3627,9 +2847,10 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
 
     // ---------------- stage C of the group's LAST window, with stage D's first requests ---------
     // Stage D's operands of the group's EARLIER windows start their trip from the parks behind this
-    // layer's last MFMAs (waves 2k, 2k + 1 own window k there; twelve 16-byte loads per lane into
-    // registers conv7 has finished with; in front of the layer's exchange, last epilogue and
-    // closing barrier, which does not wait for them) - the parks are MALL / HBM resident (120 KB per
+    // layer's mid-layer barrier (waves 2k, 2k + 1 own window k there; twelve 16-byte loads per lane;
+    // the layer's closing barrier does not wait for them.  Asked for behind the layer's last MFMAs,
+    // as at first, the kernel was 0.13 % slower and the group's last conv7 took 12.9 k cycles
+    // against 12.0 k) - the parks are MALL / HBM resident (120 KB per
     // workgroup: more than the L2 holds), a round trip of thousands of cycles.  The last window's own output goes to
     // LDS (w43_nsplit_half<LAST>) and is read back behind the layer's closing barrier.  conv8's
     // thirds 0 and 1 -> stage D's slots 0 and 1 (the idle part of the activation buffer) in the
@@ -3643,7 +2864,7 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
     unsigned c7_since = phases_on ? (unsigned)__builtin_readcyclecounter() : 0u;
     {
         auto third_step = [&](const float* src, float* dst, int step) {
-            constexpr int NW = DBH_DMA_WAVES;
+            constexpr int NW = kDmaWaves;
             constexpr int per_wave = (kWinoHalf / 256 + NW - 1) / NW;
             if (2 * step < per_wave) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step);
             if (2 * step + 1 < per_wave) dma_weights_one<kWinoHalf, NW>(src, dst, lane, wave, 2 * step + 1);
@@ -3653,23 +2874,13 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
                 constexpr int G = decltype(tag)::value;
                 if constexpr (G < 3) third_step(packed + weight_offset(7), lds + kDS0, G);
                 else if constexpr (G < 6) third_step(packed + weight_offset(7) + kWinoHalf, lds + kDS1, G - 3);
-#if DBH_Y_EARLY
-                if constexpr (G == 6)
-                    d_load_y(Y, (const float*)(wg_scratch + kWgPark7Off + (wave >> 1) * kPark7Floats +
-                                               (wave & 1) * 3072 + lane * 4));
-#endif
-            },
-            [&]() -> bool {
-#if DBH_Y_EARLY
-                return true;
-#endif
                 // (every wave: the two that own the last window load what their park holds - stale -
                 // and overwrite it below.  Loaded under a condition the registers would count as
                 // live around the whole persistent loop - on the path that takes neither branch -
                 // and be spilled in stage B.)
-                d_load_y(Y, (const float*)(wg_scratch + kWgPark7Off + (wave >> 1) * kPark7Floats +
-                                           (wave & 1) * 3072 + lane * 4));
-                return true;
+                if constexpr (G == 6)
+                    d_load_y(Y, (const float*)(wg_scratch + kWgPark7Off + (wave >> 1) * kPark7Floats +
+                                               (wave & 1) * 3072 + lane * 4));
             });
     }
     phase_add(12, c7_since);
@@ -3773,9 +2984,8 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
     // workgroup's slots in global memory for the batched tail below.
     //   The NEXT group's samples (seam b2) are fetched meanwhile: the places of its windows in the
     // sample buffer (offsets) came with the fragments; the samples themselves are asked for in front
-    // of the MFMAs; their exact sums ride on the last barrier, and waves 5-7 turn those of windows
-    // 1-3 into mean and 1/std while the samples go to the LDS staging; window 0 stays in registers
-    // for that group's stage A (whose first barrier carries its sums).
+    // of the MFMAs; their exact sums ride on the last barrier, and waves 4-7 turn them into mean
+    // and 1/std (one window each) while the samples go to the LDS staging.
     phase_stamp(2);
     const bool batch_ends = tail_every_group || tail_slot + group_n + next_n > kTailBatch || next_n == 0;
     const bool slot0_next = seam_b2 && next_n > 0;       // the next group's first window: conv2's weights
@@ -3809,7 +3019,7 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
             const long long next_end =
                 ((long long)__builtin_amdgcn_readfirstlane((int)(noff1[w] >> 32)) << 32) |
                 (unsigned)__builtin_amdgcn_readfirstlane((int)noff1[w]);
-            window_bounds(next_end - next_base, nstep[w], side_arg, &wa, &wb);
+            window_bounds(next_end - next_base, nstep[w], side_arg, kWindow, &wa, &wb);
             ncnt[w] = (int)(wb - wa);
             npad[w] = (side_arg == 0) ? 0 : kWindow - ncnt[w];
             const int16_t* src = (const int16_t*)samples_entry + next_base + wa;
@@ -3910,9 +3120,9 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
     }
     phase_add(7, f_since);
     mark(ts, 43);
-    // the next group's windows 1 .. 3: samples to the staging, exact sums for the barrier below
+    // the next group's windows: samples to the staging, exact sums for the barrier below
 #pragma unroll
-    for (int w = DBH_STATS0_IN_F ? 0 : 1; w < kGroup; ++w) {
+    for (int w = 0; w < kGroup; ++w) {
         asm volatile("" : "+v"(nv0[w]), "+v"(nv1[w]));
         if (seam_b2 && w < next_n) {
             window_partial_sums(lds, ncnt[w], nv0[w], nv1[w], tid, lane, wave, w);
@@ -3933,18 +3143,12 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
         dma_weights<conv_weight_floats(18)>(packed + weight_offset(18), lds + kTW19, lane, wave);
         dma_weights<conv_weight_floats(19)>(packed + weight_offset(19), lds + kTW20, lane, wave);
     }
-    if (wave >= (DBH_STATS0_IN_F ? 4 : 5)) {
+    if (wave >= 4) {
         const int w = wave - 4;
         if (seam_b2 && w < next_n) {
             double mean, inv;
-            if (DBH_STATS0_IN_F) {
-                const int c = w == 0 ? ncnt[0] : w == 1 ? ncnt[1] : w == 2 ? ncnt[2] : ncnt[3];
-                window_mean_inv(lds, c, &mean, &inv, w);
-            } else {
-                window_mean_inv(lds, ncnt[1], &mean, &inv, 1);
-                if (w == 2) window_mean_inv(lds, ncnt[2], &mean, &inv, 2);
-                if (w == 3) window_mean_inv(lds, ncnt[3], &mean, &inv, 3);
-            }
+            const int c = w == 0 ? ncnt[0] : w == 1 ? ncnt[1] : w == 2 ? ncnt[2] : ncnt[3];
+            window_mean_inv(lds, c, &mean, &inv, w);
             float* st = lds + kStageStats + w * 8;
             if (lane == 0) {
                 reinterpret_cast<double*>(st)[0] = mean;
@@ -3957,12 +3161,6 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
     phase_add(8, f_since);
     mark_realtime(ts, 63);
     phase_stamp(3);
-    if (!DBH_STATS0_IN_F) {
-        carry_cnt = ncnt[0];
-        carry_pad = npad[0];
-        carry_v0 = nv0[0];
-        carry_v1 = nv1[0];
-    }
 
     // ---------------- stages G + H for the batch: conv18, conv19 (+ MaxPool + BN7), conv20 (1x1 ->
     // classes) + ReLU + GlobalAveragePool + Softmax (+ renormalise + call), one wave per window ---
@@ -4139,89 +3337,6 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
         for (int i = threadIdx.x; i < kPhaseMarks * kPhaseGroups; i += kThreads)
             c[4 + i] = i < phase_group * kPhaseMarks ? (long long)reinterpret_cast<const unsigned*>(lds + kPhase)[i] : -1;
     }
-}
-
-// =============================================================================================
-// Seam b2 helpers.
-// =============================================================================================
-
-// One block per (read, step): slice the window (classify.py:337-349), z-normalise it in fp64
-// (trim_signal.py:61-69; the sums are exact integers), zero-pad right ('start') or left ('end')
-// (classify.py:352-357) and emit fp32, which is what Keras casts the float64 input to.
-__global__ __launch_bounds__(256) void dbh_normalise_kernel(
-    const int16_t* __restrict__ samples, const long long* __restrict__ offsets, int steps,
-    int side, float* __restrict__ windows) {
-    __shared__ long long red[2][4];
-    const long long read = blockIdx.x / steps;
-    const int step = blockIdx.x - (int)(read * steps);
-    const long long base = offsets[read];
-    const long long len = offsets[read + 1] - base;
-    long long a, b;
-    window_bounds(len, step, side, &a, &b);
-    const int cnt = (int)(b - a);
-    const int tid = threadIdx.x;
-    const int16_t* src = samples + base + a;
-
-    int v[4];
-    long long s1 = 0, s2 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = tid + i * 256;
-        v[i] = (k < cnt) ? (int)src[k] : 0;
-        s1 += v[i];
-        s2 += (long long)v[i] * v[i];
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        s1 += __shfl_xor(s1, off);
-        s2 += __shfl_xor(s2, off);
-    }
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = s1;
-        red[1][tid >> 6] = s2;
-    }
-    __syncthreads();
-    s1 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    s2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-
-    float* out = windows + (long long)blockIdx.x * kWindow;
-    double mean, inv;
-    mean_std(s1, s2, cnt, &mean, &inv);
-    const int pad_left = (side == 0) ? 0 : kWindow - cnt;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = tid + i * 256;          // position in the source slice
-        if (k < cnt) out[pad_left + k] = (float)(((double)v[i] - mean) * inv);
-    }
-    // zero padding: [cnt, 1024) for 'start', [0, 1024-cnt) for 'end'
-    const int pad_begin = (side == 0) ? cnt : 0;
-    const int pad_count = kWindow - cnt;
-    for (int k = tid; k < pad_count; k += 256) out[pad_begin + k] = 0.f;
-}
-
-// 32 lanes per read: merge the per-step softmax vectors (classify.py:368-374: min for class 0,
-// max for the barcodes), rescale the barcodes so the vector sums to one (classify.py:387-393,
-// in fp64 like NumPy-1.x scalar promotion did) and make the call (classify.py:285-295).
-__global__ __launch_bounds__(256) void dbh_merge_kernel(const float* __restrict__ wprobs,
-                                                        long long n_reads, int steps,
-                                                        int n_classes, double score_diff,
-                                                        float* __restrict__ probs,
-                                                        int* __restrict__ calls) {
-    const long long read = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
-    const int c = threadIdx.x & 31;
-    if (read >= n_reads) return;   // whole 32-lane groups exit together
-    const bool valid = c < n_classes;
-    float merged = 0.f;
-    if (valid) {
-        const float* src = wprobs + read * steps * n_classes + c;
-        merged = src[0];
-        for (int s = 1; s < steps; ++s) {
-            const float v = src[(long long)s * n_classes];
-            merged = (c == 0) ? fminf(merged, v) : fmaxf(merged, v);
-        }
-    }
-    renormalise_and_call(merged, c, n_classes, score_diff, probs + read * n_classes,
-                         calls + read);
 }
 
 }  // namespace DBH_FORWARD_NS

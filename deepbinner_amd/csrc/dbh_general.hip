@@ -14,6 +14,7 @@
 // No atomics and no cross-window arithmetic: a window's result does not depend on the chunk,
 // the batch or the stream it travels in.
 #include "dbh_general.h"
+#include "dbh_seam.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,8 +35,8 @@ constexpr int kMaxL7 = kMaxInput / 128;            // positions reaching the hea
 enum { kInPlain = 0, kInBn = 1, kInAvgBn = 2 };
 
 // ---- front: slice + normalise (+ given fp32 windows) and conv1d_1 (k 3, stride 2, 1 -> 48) ---
-// Same arithmetic as dbh_forward.hip's normalise (exact integer sums, fp64 constants), so that the
-// windows agree with classify.py:330-357.
+// The persistent path's arithmetic (dbh_seam.h: window bounds, exact integer sums, fp64 constants), so
+// that the windows agree with it and with classify.py:330-357.
 __global__ __launch_bounds__(kThreads) void front_kernel(
     const float* __restrict__ x, const int16_t* __restrict__ samples,
     const long long* __restrict__ offsets, int steps, int side, long long w0, int L, int L1,
@@ -55,15 +56,8 @@ __global__ __launch_bounds__(kThreads) void front_kernel(
         const int step = (int)(win - read * steps);
         const long long base = offsets[read];
         const long long len = offsets[read + 1] - base;
-        const long long sig_start = (long long)step * (L / 2), sig_end = sig_start + L;
         long long a, b;
-        if (side == 0) {
-            a = sig_start < len ? sig_start : len;
-            b = sig_end < len ? sig_end : len;
-        } else {
-            a = len - sig_end > 0 ? len - sig_end : 0;
-            b = len - sig_start > 0 ? len - sig_start : 0;
-        }
+        dbh::window_bounds(len, step, side, L, &a, &b);
         cnt = (int)(b - a);
         pad_left = side == 0 ? 0 : L - cnt;
         src = samples + base + a;
@@ -84,11 +78,7 @@ __global__ __launch_bounds__(kThreads) void front_kernel(
         __syncthreads();
         s1 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
         s2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        if (cnt > 0) {
-            mean = (double)s1 / (double)cnt;
-            const long long num = (long long)cnt * s2 - s1 * s1;
-            if (num > 0) inv = (double)cnt / sqrt((double)num);
-        }
+        dbh::mean_std(s1, s2, cnt, &mean, &inv);
     } else {
         __syncthreads();
     }

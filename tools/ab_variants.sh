@@ -1,6 +1,7 @@
 #!/bin/bash
 # A/B of kernel variants on the SAME GPU box (boxes differ by ~1 %).  The variants are built HERE
-# (build container) first:   tools/ab_variants.sh build NAME "-DDBH_EXP_X=1" ...
+# (build container) first:   tools/ab_variants.sh build NAME "EXTRA FLAGS" ...   (the Makefile's EXTRA:
+# whatever the experiment's patch of the sources reads, e.g. a -D of its own; the product has none)
 # and compared on the box:   tools/ab_variants.sh run [rounds] NAME...     ("base" = the product)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 V=$R/deepbinner_amd/csrc/_variants

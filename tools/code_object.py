@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """The gfx950 code object inside libdeepbinner_hip.so: kernel metadata (registers, spills, scratch,
 LDS) and a census of the forward kernel's instruction stream.  Used by tests/test_code_object.py
-(the CPU-box guard on what ships) and by hand:  python tools/code_object.py [lib.so]"""
+(the CPU-box guard on what ships) and by hand:  python tools/code_object.py [lib.so]
+                                                python tools/code_object.py --same OLD.so NEW.so"""
 import collections
+import hashlib
 import json
 import os
 import re
@@ -167,6 +169,10 @@ def lgkm_wait_histogram(insts):
     return {str(k): h[k] for k in sorted(h)}
 
 
+META = ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count',
+        'private_segment_fixed_size', 'group_segment_fixed_size')
+
+
 def summary(lib):
     """everything tests/test_code_object.py looks at, as one dict"""
     with tempfile.TemporaryDirectory() as d:
@@ -176,16 +182,53 @@ def summary(lib):
         insts = disassemble(co, fwd)
         c = census(insts)
         return {
-            'metadata': {k: md[fwd].get(k) for k in ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count',
-                                                     'sgpr_spill_count', 'private_segment_fixed_size',
-                                                     'group_segment_fixed_size')},
+            'metadata': {k: md[fwd].get(k) for k in META},
             'census': c,
             'lgkm_waits': lgkm_wait_histogram(insts),
             'mfma_read_hazards': [list(b) for b in mfma_read_hazards(insts)][:20],
         }
 
 
+def kernels(lib):
+    """-> {kernel symbol: (instruction count, hash of the instruction stream, metadata fields)}"""
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        co = extract(lib, d)
+        for name, m in kernel_metadata(co).items():
+            insts = disassemble(co, name)
+            digest = hashlib.sha256('\n'.join(insts).encode()).hexdigest()[:16]
+            out[name] = (len(insts), digest, {k: m.get(k) for k in META + ('kernarg_segment_size',)})
+    return out
+
+
+def same(old_lib, new_lib):
+    """the kernels of two builds side by side, for a change that must not alter the compiled code:
+    -> (report lines, number of kernels present on both sides that differ)"""
+    old, new = kernels(old_lib), kernels(new_lib)
+    lines, differ = [], 0
+    for name in sorted(set(old) & set(new)):
+        (n0, h0, m0), (n1, h1, m1) = old[name], new[name]
+        ok = (n0, h0, m0) == (n1, h1, m1)
+        differ += not ok
+        meta = ' '.join(f'{k}={m0[k]}' if m0[k] == m1[k] else f'{k}={m0[k]}->{m1[k]}' for k in m0)
+        lines.append(f"{'same' if ok else 'DIFFERS'} {name}\n     instructions {n0 if n0 == n1 else f'{n0}->{n1}'}"
+                     f" stream {h0 if h0 == h1 else f'{h0}->{h1}'}\n     {meta}")
+    for side, only in (('old', set(old) - set(new)), ('new', set(new) - set(old))):
+        for name in sorted(only):
+            n, h, _ = (old if side == 'old' else new)[name]
+            lines.append(f'only in {side}: {name}\n     instructions {n} stream {h}')
+    return lines, differ
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == '--same':
+        # python tools/code_object.py --same OLD.so NEW.so: exit status 1 if a kernel of both differs
+        # (only the first translation unit's code object is looked at: build another file of the
+        # library alone, with the Makefile's flags, to compare its kernels)
+        lines, differ = same(sys.argv[2], sys.argv[3])
+        print('\n'.join(lines))
+        print(f'{differ} kernel(s) differ')
+        sys.exit(1 if differ else 0)
     if len(sys.argv) > 1 and sys.argv[1] == '--bless':
         # record what the built library carries (tests/golden/code_object.json): run after every
         # deliberate change of the forward kernel, and read the diff
