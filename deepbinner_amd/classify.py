@@ -329,8 +329,10 @@ def _raw_batches(fast5_files, args, host_share, n_queues):
     chunks = list(chunker(fast5_files, size))
 
     def load(chunk):
+        # DEEPBINNER_VBZ_ZSTD=gpu: VBZ chunks keep their zstd stage for the GPU (default: host)
         return RawBatch(chunk, fast5_native.load_batch_raw(chunk, max(1, threads // 2),
-                                                            -host_share))
+                                                            -host_share,
+                                                            vbz_zstd=fast5_native.vbz_zstd_route()))
 
     with ThreadPoolExecutor(max_workers=2, thread_name_prefix='deepbinner-raw-loader') as pool:
         waiting = collections.deque()

@@ -38,9 +38,9 @@
 //      could be overtaken by a write that wraps around the ring goes in token order instead:
 //      dbh_inflate_core.h, ring_hazard): 3.04 ms.
 //      The ring is written out in coalesced 256-byte pieces, with the Adler-32 sums on the way.
-// Streams of mode DBH_INFLATE_VBZ (ONT's VBZ filter, zstd stage undone by the loader) are no
-// kernel's here: both kernels pass them by, and dbh_vbz.hip's kernel, launched behind them by
-// dbh_inflate_dev, decodes them.
+// Streams of mode DBH_INFLATE_VBZ (ONT's VBZ filter, zstd stage undone by the loader) and
+// DBH_INFLATE_VBZ_ZSTD (the chunk as stored) are no kernel's here: both kernels pass them by, and
+// dbh_zstd.hip's and dbh_vbz.hip's kernels, launched behind them by dbh_inflate_dev, decode them.
 // What dbh_inflate_dev launches is both of them AT ONCE, a pair of waves per stream
 // (inflate_pair_kernel: wave 0 is kernel 1, wave 1 is kernel 2 resolving the tokens as they come;
 // described in front of it) - a stream then lasts as long as the slower of its halves, not their
@@ -616,7 +616,7 @@ __global__ __launch_bounds__(64 * kWaves2) void inflate_resolve_kernel(
         const dbh_inflate_stream s = streams[i];
         uint8_t* dst = out + s.out_offset;
         const int64_t cap = s.out_bytes;
-        if (s.mode == DBH_INFLATE_VBZ) continue;     // (dbh_vbz.hip's kernel decodes it)
+        if (s.mode == DBH_INFLATE_VBZ || s.mode == DBH_INFLATE_VBZ_ZSTD) continue;     // (dbh_vbz.hip, dbh_zstd.hip)
         if (s.mode != DBH_INFLATE_ZLIB) {
             // stored as it is (an unfiltered chunk, a contiguous dataset, or bytes the host has
             // inflated itself): copy, zero-extend
@@ -890,7 +890,7 @@ __device__ __forceinline__ void resolve_pre_stream(
     {
         uint8_t* dst = out + s.out_offset;
         const int64_t cap = s.out_bytes;
-        if (s.mode == DBH_INFLATE_VBZ) return;       // (dbh_vbz.hip's kernel decodes it)
+        if (s.mode == DBH_INFLATE_VBZ || s.mode == DBH_INFLATE_VBZ_ZSTD) return;       // (dbh_vbz.hip, dbh_zstd.hip)
         if (s.mode != DBH_INFLATE_ZLIB) {
             const int64_t have = s.comp_bytes < cap ? s.comp_bytes : cap;
             const uint8_t* src = comp + s.comp_offset;
@@ -1186,7 +1186,28 @@ using namespace dbh_inflate_detail;
 hipError_t dbh_vbz_launch(const uint8_t* comp_dev, int64_t comp_bytes,
                           const dbh_inflate_stream* streams_dev, int n_streams,
                           int64_t total_out_bytes, uint8_t* out_dev, int32_t* status_dev,
+                          const uint8_t* work_dev, const char* produced0, int64_t produced_stride,
                           hipStream_t stream);
+// dbh_zstd.hip: the zstd stage of the streams of mode DBH_INFLATE_VBZ_ZSTD, into their workspace
+// slots; the content size of each into the `produced` word of its record
+hipError_t dbh_zstd_launch(const uint8_t* comp_dev, int64_t comp_bytes,
+                           const dbh_inflate_stream* streams_dev, int n_streams,
+                           int64_t total_out_bytes, uint8_t* work_dev, int32_t* status_dev,
+                           char* produced0, int64_t produced_stride, hipStream_t stream);
+
+namespace dbh_inflate_detail {
+// the two VBZ stages behind the inflate kernels, on the same queue
+int vbz_stages(const uint8_t* comp_dev, int64_t comp_bytes, const dbh_inflate_stream* streams_dev, int n,
+               int64_t total_out_bytes, uint8_t* out_dev, void* workspace_dev, StreamInfo* info,
+               int32_t* status_dev, hipStream_t stream) {
+    char* produced0 = reinterpret_cast<char*>(&info[0].produced);
+    DBI_HIP(dbh_zstd_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes,
+                            (uint8_t*)workspace_dev, status_dev, produced0, (int64_t)sizeof(StreamInfo), stream));
+    DBI_HIP(dbh_vbz_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, status_dev,
+                           (const uint8_t*)workspace_dev, produced0, (int64_t)sizeof(StreamInfo), stream));
+    return DBH_OK;
+}
+}  // namespace dbh_inflate_detail
 
 extern "C" {
 
@@ -1225,9 +1246,8 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
         hipLaunchKernelGGL(inflate_pair_kernel, dim3((unsigned)n), dim3(128), 0, (hipStream_t)stream,
                            comp_dev, comp_bytes, streams_dev, n, tokens, info, out_dev, status_dev);
         DBI_HIP(hipGetLastError());
-        DBI_HIP(dbh_vbz_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev,
-                               status_dev, (hipStream_t)stream));
-        return DBH_OK;
+        return vbz_stages(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, workspace_dev,
+                          info, status_dev, (hipStream_t)stream);
     }
     if (wave_per_stream()) {
         hipLaunchKernelGGL(inflate_tokens_wave_kernel, dim3((unsigned)n), dim3(dbi::kWaveLanes), 0,
@@ -1251,9 +1271,8 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
                            (hipStream_t)stream, comp_dev, streams_dev, n, (const uint32_t*)tokens,
                            info, out_dev, status_dev);
     DBI_HIP(hipGetLastError());
-    DBI_HIP(dbh_vbz_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev,
-                           status_dev, (hipStream_t)stream));
-    return DBH_OK;
+    return vbz_stages(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, workspace_dev, info,
+                      status_dev, (hipStream_t)stream);
 }
 
 int dbh_inflate(const uint8_t* comp_host, size_t comp_bytes, const dbh_inflate_stream* streams_host,

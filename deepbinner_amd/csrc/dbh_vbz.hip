@@ -50,10 +50,14 @@ __device__ __forceinline__ uint32_t load_u32(const uint8_t* p) {
     return v;
 }
 
+// `unpacked` (mode DBH_INFLATE_VBZ_ZSTD): the streamvbyte bytes lie there, unpacked_bytes of them,
+// put there by dbh_zstd.hip's kernel, whose verdict is in *status_slot; the stream's bytes in comp
+// then hold the original_size alone.  Null: they follow the original_size in comp.
 __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int64_t comp_total,
                                            const dbh_inflate_stream& s, int64_t total_out,
                                            uint8_t* __restrict__ out, int32_t* status_slot,
-                                           int lane) {
+                                           int lane, const uint8_t* unpacked = nullptr,
+                                           int64_t unpacked_bytes = 0) {
     // an output region outside the buffer is not written at all
     if (s.out_offset < 0 || s.out_bytes < 0 || (s.out_offset & 1) ||
         s.out_offset > total_out - s.out_bytes) {
@@ -64,15 +68,24 @@ __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int
     const int64_t out_n = s.out_bytes / 2;
     bool bad = s.comp_offset < 0 || s.comp_bytes < 4 || s.comp_offset > comp_total - s.comp_bytes;
     int64_t n = 0, written = 0;
+    int refused = kRefused;
+    if (unpacked && !bad) {
+        const int before = *status_slot;                   // (every lane reads it before lane 0 writes)
+        if (before != 0) {
+            bad = true;
+            refused = before;
+        }
+    }
+    const int64_t payload = unpacked ? unpacked_bytes : s.comp_bytes - 4;
     if (!bad) {
         const uint8_t* const src = comp + s.comp_offset;
         const uint32_t size = load_u32(src);
         n = size / 2;
         const int64_t ctrl = (n + 3) / 4;
-        bad = (size & 1) || ctrl > s.comp_bytes - 4;
-        const uint8_t* const cbase = src + 4;
+        bad = (size & 1) || ctrl > payload;
+        const uint8_t* const cbase = unpacked ? unpacked : src + 4;
         const uint8_t* const dbase = cbase + ctrl;
-        const int64_t data_len = s.comp_bytes - 4 - ctrl;
+        const int64_t data_len = payload - ctrl;
         const int64_t keep = n < out_n ? n : out_n;
         const bool aligned16 = (s.out_offset & 15) == 0;
         int64_t doff = 0;                          // data bytes of the steps before (uniform)
@@ -144,17 +157,26 @@ __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int
     }
     // zero-extension (a chunk shorter than asked for), or all of it for a refused stream
     for (int64_t k = written + lane; k < out_n; k += 64) dst[k] = 0;
-    if (lane == 0) *status_slot = bad ? kRefused : 0;
+    if (lane == 0) *status_slot = bad ? refused : 0;
 }
 
 __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
     const uint8_t* __restrict__ comp, int64_t comp_total,
     const dbh_inflate_stream* __restrict__ streams, int n_streams, int64_t total_out,
-    uint8_t* __restrict__ out, int32_t* __restrict__ status_out) {
+    uint8_t* __restrict__ out, int32_t* status_out, const uint8_t* work, const char* produced0,
+    int64_t produced_stride) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int i = blockIdx.x * kWaves + wave; i < n_streams; i += gridDim.x * kWaves) {
         const dbh_inflate_stream s = streams[i];
+        if (s.mode == DBH_INFLATE_VBZ_ZSTD) {
+            // (a stream with no room in the workspace was refused by the zstd kernel: nothing is read)
+            const int64_t have = *reinterpret_cast<const int64_t*>(produced0 + (int64_t)i * produced_stride);
+            const bool placed = s.out_offset >= 0 && s.out_bytes >= 0 && s.out_offset <= total_out - s.out_bytes;
+            vbz_stream(comp, comp_total, s, total_out, out, status_out + i, lane,
+                       work + (placed ? 4 * s.out_offset : 0), placed ? have : 0);
+            continue;
+        }
         if (s.mode != DBH_INFLATE_VBZ) continue;
         vbz_stream(comp, comp_total, s, total_out, out, status_out + i, lane);
     }
@@ -166,11 +188,11 @@ __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
 __attribute__((visibility("hidden"))) hipError_t dbh_vbz_launch(
     const uint8_t* comp_dev, int64_t comp_bytes, const dbh_inflate_stream* streams_dev,
     int n_streams, int64_t total_out_bytes, uint8_t* out_dev, int32_t* status_dev,
-    hipStream_t stream) {
+    const uint8_t* work_dev, const char* produced0, int64_t produced_stride, hipStream_t stream) {
     using namespace dbh_vbz_detail;
     const int blocks = (n_streams + kWaves - 1) / kWaves;
     hipLaunchKernelGGL(vbz_decode_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)),
                        dim3(64 * kWaves), 0, stream, comp_dev, comp_bytes, streams_dev, n_streams,
-                       total_out_bytes, out_dev, status_dev);
+                       total_out_bytes, out_dev, status_dev, work_dev, produced0, produced_stride);
     return hipGetLastError();
 }

@@ -39,6 +39,8 @@
 #include <thread>
 #include <vector>
 
+#include "dbh_zstd_core.h"
+
 namespace {
 
 constexpr uint64_t kUndef = ~0ull;
@@ -250,6 +252,19 @@ uint64_t vbz_frame_size(const uint8_t* src, size_t n, uint32_t original_size) {
     return (uint64_t)size;
 }
 
+// The same size from the frame's header alone (dbh_zstd_core.h, the GPU decoder's own parser):
+// the route on which the GPU undoes the zstd stage and libzstd is not called.  A frame that
+// decoder refuses by its header (no content size, a dictionary id, a checksum) refuses the read.
+uint64_t vbz_frame_size_header(const uint8_t* src, size_t n, uint32_t original_size) {
+    dbz::Frame fr;
+    if (n < 4 || dbz::frame_header(src + 4, n - 4, &fr) != dbz::kOk)
+        throw UnsupportedFilter("VBZ chunk with a bad zstd frame");
+    const uint64_t values = original_size / 2, ctrl = (values + 3) / 4;
+    if (fr.content < ctrl + values || fr.content > ctrl + 4 * values)
+        throw UnsupportedFilter("VBZ chunk with a bad zstd frame");
+    return fr.content;
+}
+
 // zstd stage undone: `dst` (frame_size bytes) <- the chunk's streamvbyte bytes
 void vbz_unzstd(const uint8_t* src, size_t n, uint8_t* dst, uint64_t frame_size) {
     const LibZstd& z = libzstd();
@@ -435,13 +450,17 @@ class Fast5 {
         // streamvbyte bytes): vbz_bytes of them; vbz_zstd: the chunk has a zstd stage to undo
         uint64_t vbz_bytes = 0;
         bool vbz_zstd = false;
+        // the chunk goes out as stored, zstd frame and all (F5_RAW_VBZ_ZSTD): the GPU undoes it
+        bool vbz_gpu = false;
     };
     enum { kZlib = 0, kStored = 1, kHostDecode = 2, kZeros = 3, kVbz = 4 };
 
     // zlib_above: deflate streams longer than this many bytes are left to the host (a lane of the
     // GPU decoder walks ONE stream: a stream ten times the usual length holds its wave ten times
     // as long, while a CPU core inflates it in a millisecond); <= 0: no limit.
-    void signal_pieces(const SignalInfo& s, int64_t zlib_above, std::vector<RawPiece>* out) const {
+    // vbz_zstd_gpu (F5_RAW_FLAG_VBZ_ZSTD_GPU): VBZ chunks with a zstd stage are handed on as stored.
+    void signal_pieces(const SignalInfo& s, int64_t zlib_above, std::vector<RawPiece>* out,
+                       bool vbz_zstd_gpu = false) const {
         out->clear();
         if (s.n <= 0) return;
         RawPiece p;
@@ -520,7 +539,14 @@ class Fast5 {
                 const uint64_t h = std::min<uint64_t>(nbytes, sizeof(head));
                 read_bytes(start, h, head);
                 const uint32_t size = vbz_original_size(head, (size_t)h, (size_t)s.chunk_elems * 2);
-                q.vbz_bytes = q.vbz_zstd ? 4 + vbz_frame_size(head, (size_t)h, size) : nbytes;
+                if (q.vbz_zstd && vbz_zstd_gpu) {
+                    (void)vbz_frame_size_header(head, (size_t)h, size);     // (sized and checked)
+                    q.vbz_zstd = false;                // nothing for the host to undo
+                    q.vbz_gpu = true;
+                    q.vbz_bytes = nbytes;
+                } else {
+                    q.vbz_bytes = q.vbz_zstd ? 4 + vbz_frame_size(head, (size_t)h, size) : nbytes;
+                }
             } else {
                 q.kind = kHostDecode;              // shuffle, or an order not seen in the field
             }
@@ -2417,7 +2443,13 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
 // buffer.
 int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
                       int64_t host_inflate_above, f5_batch** out) {
-    if (!paths || !out || n_files < 0) return F5_ERR_ARGUMENT;
+    return f5_load_batch_raw_ex(paths, n_files, n_threads, host_inflate_above, 0u, out);
+}
+
+int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_threads,
+                         int64_t host_inflate_above, unsigned flags, f5_batch** out) {
+    if (!paths || !out || n_files < 0 || (flags & ~(unsigned)F5_RAW_FLAG_VBZ_ZSTD_GPU)) return F5_ERR_ARGUMENT;
+    const bool vbz_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
     *out = nullptr;
     f5_batch* batch = nullptr;
     try {
@@ -2449,7 +2481,7 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
                 }
                 const ReadEntry& r = file.read(0);
                 st.samples = r.signal.n;
-                file.signal_pieces(r.signal, zlib_above, &st.pieces);
+                file.signal_pieces(r.signal, zlib_above, &st.pieces, vbz_gpu);
                 for (Fast5::RawPiece& p : st.pieces) {
                     const uint64_t wanted = (uint64_t)p.count * 2;
                     const size_t at = st.bytes.size();
@@ -2526,7 +2558,7 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
                 rec.out_offset = (batch->offsets[(size_t)i] + p.first) * 2;
                 rec.out_bytes = p.count * 2;
                 rec.mode = p.kind == Fast5::kZlib  ? F5_RAW_ZLIB
-                           : p.kind == Fast5::kVbz ? F5_RAW_VBZ
+                           : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
                                                    : F5_RAW_STORED;
                 rec.reserved = (int32_t)i;
                 batch->streams.push_back(rec);
@@ -2877,6 +2909,7 @@ struct f5_stream {
     int depth = 3;
     bool raw = false;                // hand out the Signal pieces as stored (f5_stream_open_raw)
     int64_t zlib_above = 0;          // ... except deflate streams longer than this: host-inflated
+    bool vbz_zstd_gpu = false;       // F5_RAW_FLAG_VBZ_ZSTD_GPU: VBZ chunks go out as stored
     int host_share = 0;              // ... and the longest ones holding this share (%) of the bytes
     static constexpr int64_t kLongStreamBytes = 64 * 1024;
     std::mutex m;
@@ -2978,7 +3011,7 @@ struct f5_stream {
                 const ReadEntry& r = c->file->read(i);
                 const int64_t n = r.signal.n;
                 c->lengths[(size_t)i] = (!raw && keep > 0 && n > 2 * keep) ? 2 * keep : n;
-                if (raw) c->file->signal_pieces(r.signal, zlib_above, &c->pieces[(size_t)i]);
+                if (raw) c->file->signal_pieces(r.signal, zlib_above, &c->pieces[(size_t)i], vbz_zstd_gpu);
                 copy_read_id(r.read_id, &c->batch->read_ids[(size_t)i * F5_READ_ID_MAX]);
             });
     }
@@ -3060,7 +3093,7 @@ struct f5_stream {
                     rec.out_offset = (c->batch->offsets[(size_t)i] + p.first) * 2;
                     rec.out_bytes = wanted;
                     rec.mode = p.kind == Fast5::kZlib  ? F5_RAW_ZLIB
-                               : p.kind == Fast5::kVbz ? F5_RAW_VBZ
+                               : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
                                                        : F5_RAW_STORED;
                     rec.reserved = (int32_t)i;         // which read of the batch it belongs to
                     c->batch->streams.push_back(rec);
@@ -3280,6 +3313,12 @@ int f5_stream_open(const char* const* paths, int64_t n_paths, int64_t keep, int 
 
 int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads, int depth,
                        int64_t host_inflate_above, f5_stream** out) {
+    return f5_stream_open_raw_ex(paths, n_paths, n_threads, depth, host_inflate_above, 0u, out);
+}
+
+int f5_stream_open_raw_ex(const char* const* paths, int64_t n_paths, int n_threads, int depth,
+                          int64_t host_inflate_above, unsigned flags, f5_stream** out) {
+    if (flags & ~(unsigned)F5_RAW_FLAG_VBZ_ZSTD_GPU) return F5_ERR_ARGUMENT;
     f5_stream* s = nullptr;
     // A raw container is little work per read (no inflating) behind a serial start (one thread
     // opens and parses it: 5-6 ms of the ~30 ms of CPU a container of 4,000 reads costs): a window
@@ -3304,6 +3343,7 @@ int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads,
         {
             std::lock_guard<std::mutex> g(s->m);
             s->raw = true;
+            s->vbz_zstd_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
             // (>= 0: a length in bytes; < 0: minus the host's share of the bytes in per cent)
             s->zlib_above = host_inflate_above > 0 ? host_inflate_above : 0;
             s->host_share = host_inflate_above < 0

@@ -28,7 +28,8 @@ EXPORTED_SYMBOLS = [
     'f5_batch_read_ids', 'f5_batch_free', 'f5_stream_open', 'f5_stream_next', 'f5_stream_close',
     'f5_set_sample_allocator', 'f5_release_idle_buffers', 'f5_stream_open_raw', 'f5_batch_comp',
     'f5_batch_comp_bytes', 'f5_batch_streams', 'f5_batch_n_streams', 'f5_write_single_reads',
-    'f5_single_read_image', 'f5_load_batch_raw', 'f5_vbz_decode',
+    'f5_single_read_image', 'f5_load_batch_raw', 'f5_vbz_decode', 'f5_stream_open_raw_ex',
+    'f5_load_batch_raw_ex',
 ]
 
 
@@ -80,6 +81,9 @@ def load_library():
         'f5_stream_close': (None, [c_void_p]),
         'f5_stream_open_raw': (c_int, [P(c_char_p), c_i64, c_int, c_int, c_i64, P(c_void_p)]),
         'f5_load_batch_raw': (c_int, [P(c_char_p), c_i64, c_int, c_i64, P(c_void_p)]),
+        'f5_stream_open_raw_ex': (c_int, [P(c_char_p), c_i64, c_int, c_int, c_i64, ctypes.c_uint,
+                                          P(c_void_p)]),
+        'f5_load_batch_raw_ex': (c_int, [P(c_char_p), c_i64, c_int, c_i64, ctypes.c_uint, P(c_void_p)]),
         'f5_write_single_reads': (c_int, [c_char_p, c_i64, P(c_i64), P(c_char_p), c_int,
                                           P(ctypes.c_int32), P(c_i64)]),
         'f5_single_read_image': (c_int, [c_char_p, c_i64, c_void_p, c_i64, P(c_i64)]),
@@ -255,18 +259,36 @@ def _unpack_raw_batch(lib, batch):
     return ids, offsets, st, comp, records
 
 
-def load_batch_raw(fast5_files, threads=0, host_inflate_above=0):
+RAW_FLAG_VBZ_ZSTD_GPU = 1
+
+
+def _raw_flags(vbz_zstd):
+    if vbz_zstd not in ('host', 'gpu'):
+        raise ValueError("vbz_zstd must be 'host' or 'gpu', not {!r}".format(vbz_zstd))
+    return RAW_FLAG_VBZ_ZSTD_GPU if vbz_zstd == 'gpu' else 0
+
+
+def vbz_zstd_route():
+    """DEEPBINNER_VBZ_ZSTD: 'gpu' hands VBZ chunks to the GPU with their zstd stage (RAW_VBZ_ZSTD);
+    unset or 'host': the loader's threads undo it (RAW_VBZ)."""
+    route = os.environ.get('DEEPBINNER_VBZ_ZSTD') or 'host'
+    _raw_flags(route)
+    return route
+
+
+def load_batch_raw(fast5_files, threads=0, host_inflate_above=0, vbz_zstd='host'):
     """One-read files with their Signals AS STORED -> (read_ids, offsets, status, comp, records),
     laid out like a batch of ``stream_raw`` (read i = file i), for
     ``hip_backend.classify_pair_deflated``.  ``host_inflate_above`` as there: > 0 bytes, or minus
     the per cent of the batch's compressed bytes (its longest streams) the host's threads inflate
-    themselves."""
+    themselves.  ``vbz_zstd``: 'host' - the loader's threads undo the zstd stage of VBZ chunks
+    (RAW_VBZ) - or 'gpu' - they go out as stored (RAW_VBZ_ZSTD) and libzstd is not called."""
     lib = load_library()
     n = len(fast5_files)
     paths = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in fast5_files])
     handle = ctypes.c_void_p()
-    status = lib.f5_load_batch_raw(paths, n, int(threads), int(host_inflate_above),
-                                   ctypes.byref(handle))
+    status = lib.f5_load_batch_raw_ex(paths, n, int(threads), int(host_inflate_above),
+                                      _raw_flags(vbz_zstd), ctypes.byref(handle))
     if status != F5_OK:
         raise Fast5NativeError(status_string(status))
     return _unpack_raw_batch(lib, handle)
@@ -330,7 +352,7 @@ def stream_reads(fast5_files, keep=None, threads=0, depth=0):
         lib.f5_stream_close(stream)
 
 
-RAW_ZLIB, RAW_STORED, RAW_VBZ = 0, 1, 2
+RAW_ZLIB, RAW_STORED, RAW_VBZ, RAW_VBZ_ZSTD = 0, 1, 2, 3
 # f5_raw_stream (include/deepbinner_fast5.h) = dbh_inflate_stream (include/deepbinner_hip.h)
 RAW_STREAM = np.dtype([('comp_offset', '<i8'), ('comp_bytes', '<i8'), ('out_offset', '<i8'),
                        ('out_bytes', '<i8'), ('mode', '<i4'), ('read', '<i4')])
@@ -354,20 +376,22 @@ def vbz_decode(chunk, cd, max_samples):
     return out[:n.value].copy()
 
 
-def stream_raw(fast5_files, threads=0, depth=0, host_inflate_above=0):
+def stream_raw(fast5_files, threads=0, depth=0, host_inflate_above=0, vbz_zstd='host'):
     """Multi-read containers as a stream of RAW batches (``f5_stream_open_raw``): the Signal of
     every read as it is stored - zlib streams, mostly - for a decoder elsewhere (the GPU:
     ``hip_backend.classify_pair_deflated``).  Yields, in the order of ``fast5_files``,
     ``(index, read_ids, offsets, status, comp, streams)``: ``offsets`` (samples) say where each
     read's signal lies once decoded, ``comp`` is the byte buffer (uint8, zero-copy: it keeps the
     native batch alive), ``streams`` an array of RAW_STREAM records - or ``(index, None, None,
-    container_status, None, None)`` for a file that could not be opened."""
+    container_status, None, None)`` for a file that could not be opened.  ``vbz_zstd`` as for
+    ``load_batch_raw``."""
     lib = load_library()
     n = len(fast5_files)
     paths = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in fast5_files])
     stream = ctypes.c_void_p()
-    status = lib.f5_stream_open_raw(paths, n, int(threads), int(depth), int(host_inflate_above),
-                                    ctypes.byref(stream))
+    flags = _raw_flags(vbz_zstd)
+    status = lib.f5_stream_open_raw_ex(paths, n, int(threads), int(depth), int(host_inflate_above),
+                                       flags, ctypes.byref(stream))
     if status != F5_OK:
         raise Fast5NativeError(status_string(status))
     try:

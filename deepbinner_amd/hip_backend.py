@@ -116,6 +116,8 @@ def load_library():
         'dbh_host_release': (None, [c_void_p, c_void_p]),
         'dbh_host_is_pinned': (c_int, [c_void_p, c_size_t, P(c_int)]),
         'dbh_inflate_last_error': (ctypes.c_char_p, []),
+        'dbh_zstd_decode_host': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, P(c_size_t),
+                                         P(ctypes.c_int32)]),
         'dbh_inflate_workspace_bytes': (c_int, [c_i64, c_i64, P(c_size_t)]),
         'dbh_inflate_dev': (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p,
                                     c_void_p, c_int, c_void_p]),
@@ -188,7 +190,7 @@ EXPORTED_SYMBOLS = [
     'dbh_host_alloc', 'dbh_host_release',
     'dbh_host_is_pinned',
     'dbh_classify_workspace_bytes', 'dbh_inflate_last_error', 'dbh_inflate_workspace_bytes',
-    'dbh_inflate_dev', 'dbh_inflate', 'dbh_classify_pair_deflated',
+    'dbh_inflate_dev', 'dbh_inflate', 'dbh_zstd_decode_host', 'dbh_classify_pair_deflated',
     'dbh_classify_pair_deflated_verbose',
     'dbh_classify_i16_dev', 'dbh_classify_i16_batched_dev', 'dbh_normalise_windows_dev', 'dbh_merge_calls_dev', 'dbh_combine_calls_dev',
     'dbh_stage_floats', 'dbh_debug_forward', 'dbh_forward_kernel_info',

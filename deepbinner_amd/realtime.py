@@ -76,6 +76,8 @@ def host_inflate_share(n_gpus):
     longest streams); the GPUs inflate the rest.  100 = everything on the host (the CPU-only
     loader path), 0 = everything on the GPUs.  DEEPBINNER_GPU_INFLATE=0 / =1 force either end,
     DEEPBINNER_HOST_INFLATE_SHARE=<per cent> any split.
+    DEEPBINNER_VBZ_ZSTD=gpu leaves the zstd stage of VBZ chunks to the GPU as well (default
+    'host': the loader's threads undo it).
 
     Left alone: all or nothing.  Measured with round 6's kernels (profiles/r06_loader/
     long_reads_cu_sweep.txt and host_share_ordinary.txt; 27 k-sample reads, gzip 1, 16 loader
@@ -385,7 +387,8 @@ class Session:
             # profiles/r06_loader/loader_team_size.txt)
             threads = min(usable_cpus(), RAW_LOADER_THREADS_PER_GPU * max(1, n_gpus))
         stream = fast5_native.stream_raw(fast5s, threads=threads, host_inflate_above=-host_share,
-                                         depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)))
+                                         depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)),
+                                         vbz_zstd=fast5_native.vbz_zstd_route())
         for index, ids, offsets, status, comp, records in stream:
             if ids is None:
                 continue

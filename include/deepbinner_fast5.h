@@ -123,6 +123,13 @@ void f5_stream_close(f5_stream* stream);
 #define F5_RAW_ZLIB 0
 #define F5_RAW_STORED 1
 #define F5_RAW_VBZ 2
+/* F5_RAW_VBZ_ZSTD (only under F5_RAW_FLAG_VBZ_ZSTD_GPU): a VBZ chunk with a zstd stage, AS STORED -
+ * u32 original_size, then the zstd frame - for DBH_INFLATE_VBZ_ZSTD of deepbinner_hip.h.  The host
+ * reads the frame's header alone (its content size is checked against what the samples can
+ * occupy, as for F5_RAW_VBZ); libzstd is not called.  VBZ chunks without a zstd stage stay
+ * F5_RAW_VBZ, chunks with a filter mask or other filters stay what they are. */
+#define F5_RAW_VBZ_ZSTD 3
+#define F5_RAW_FLAG_VBZ_ZSTD_GPU 1u
 typedef struct f5_raw_stream {
     int64_t comp_offset, comp_bytes;
     int64_t out_offset, out_bytes;
@@ -133,6 +140,12 @@ int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads,
 /* the same for a batch of one-read files (f5_load_batch's twin): one batch, read i = file i */
 int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
                       int64_t host_inflate_above, f5_batch** out);
+/* The two calls above plus flags (F5_RAW_FLAG_VBZ_ZSTD_GPU: VBZ chunks with a zstd stage go out
+ * as stored, F5_RAW_VBZ_ZSTD); flags 0 is the calls above. */
+int f5_stream_open_raw_ex(const char* const* paths, int64_t n_paths, int n_threads, int depth,
+                          int64_t host_inflate_above, unsigned flags, f5_stream** out);
+int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_threads,
+                         int64_t host_inflate_above, unsigned flags, f5_batch** out);
 const uint8_t* f5_batch_comp(const f5_batch* batch);
 int64_t f5_batch_comp_bytes(const f5_batch* batch);
 const f5_raw_stream* f5_batch_streams(const f5_batch* batch);

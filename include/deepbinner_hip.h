@@ -243,6 +243,19 @@ int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_cal
 #define DBH_INFLATE_ZLIB 0
 #define DBH_INFLATE_STORED 1
 #define DBH_INFLATE_VBZ 2
+/* DBH_INFLATE_VBZ_ZSTD: a VBZ chunk as the filter stored it - u32 LE original_size, then the zstd
+ * frame (RFC 8878) of the streamvbyte bytes.  A kernel of its own (dbh_zstd.hip, one wave per
+ * frame; what it decodes and what it refuses: dbh_zstd_core.h) writes the frame's content into the
+ * stream's own slots of the workspace (4 * out_bytes bytes), and the DBH_INFLATE_VBZ kernel reads
+ * it from there, with all its self-checks and the same cut / zero-extend rules.  A frame whose
+ * content does not fit the slots is refused: none is whose out_bytes covers its original_size.
+ * Refused by either stage: status != 0 (16..28: the zstd stage's reason), output zeros. */
+#define DBH_INFLATE_VBZ_ZSTD 3
+/* the GPU's zstd decoder run on the host: same core, lanes as a loop (tests, tools).  frame must
+ * be readable for 64 bytes beyond frame_bytes.  Returns 0 unless an argument is null; *status: 0,
+ * or why the frame is refused (16..28, dbh_zstd_core.h), *produced: the content size, 0 if refused. */
+int dbh_zstd_decode_host(const uint8_t* frame, size_t frame_bytes, uint8_t* out,
+                         size_t out_capacity, size_t* produced, int32_t* status);
 typedef struct dbh_inflate_stream {
     int64_t comp_offset, comp_bytes;       /* the stream inside the compressed buffer           */
     int64_t out_offset, out_bytes;         /* its output inside the output buffer (bytes)       */
