@@ -190,7 +190,8 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
         sys.exit('Error: no fast5 files found')
     out_dest = sys.stderr if full_output else sys.stdout
 
-    if not verified_single_read:
+    multi_read = bool(getattr(args, 'multi_read', False))      # --multi_read: containers welcome
+    if not verified_single_read and not multi_read:
         if determine_single_or_multi_fast5s(fast5_files) == 'multi':
             sys.exit('Error: deepbinner classify requires one-read-per-file fast5s - convert with '
                      'multi_to_single_fast5 before running')
@@ -204,10 +205,41 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
 
     classifications, read_id_to_fast5_file = {}, {}
 
+    results = (classify_units if multi_read else _one_read_batches)(
+        fast5_files, start_model, start_input_size, end_model, end_input_size, output_size, args)
+    finished = 0
+    for files, calls, lines, finished in results:
+        read_id_to_fast5_file.update(files)
+        classifications.update(calls)
+        if full_output:
+            for line in lines:
+                print(line)
+        # (--multi_read counts files, where a file may hold any number of reads)
+        print_classification_progress(finished if multi_read else len(classifications),
+                                      len(fast5_files), 'fast5s', out_dest=out_dest)
+    if multi_read and finished < len(fast5_files):      # (files without a readable read, last)
+        print_classification_progress(len(fast5_files), len(fast5_files), 'fast5s',
+                                      out_dest=out_dest)
+
+    if full_output:
+        print('', file=sys.stderr)
+        if summary_table:
+            print_summary_table(classifications)
+    return classifications, read_id_to_fast5_file
+
+
+def _one_read_batches(fast5_files, start_model, start_input_size, end_model, end_input_size,
+                      output_size, args, set_aside=None):
+    """The per-batch loop over one-read files (reference classify.py:141-171), a generator:
+    (its reads' files, calls, table rows, how many files it covered) per batch, in order.
+    ``set_aside`` (--multi_read): a list that takes the multi-read files met on the way, which
+    are an error without it."""
+
     def classify_loaded(loaded, start_replica, end_replica):
-        """One loaded batch on one device -> (its reads' files, calls, table rows)."""
+        """One loaded batch on one device -> (its reads' files, calls, table rows, files)."""
         if isinstance(loaded, RawBatch):
-            return _classify_raw_batch(loaded, start_replica, end_replica, args)
+            return (_classify_raw_batch(loaded, start_replica, end_replica, args) +
+                    (len(loaded.files) - loaded.set_aside,))
         files, read_ids, signals = {}, [], []
         for fast5_file, read_id, signal in loaded:
             if signal is None:
@@ -220,33 +252,83 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
         calls = {}
         lines = classify_read_batch(read_ids, signals, start_replica, start_input_size,
                                     end_replica, end_input_size, output_size, args, calls)
-        return files, calls, lines
+        return files, calls, lines, len(loaded) - getattr(loaded, 'set_aside', 0)
 
     replicas = device_replicas(start_model, end_model)
     host_share = raw_inflate_share(start_model, end_model, args, len(fast5_files), replicas)
+    queues = []
     if host_share is None:
         batches = load_in_batches(fast5_files, args,
-                                  scanned_end_samples(args.scan_size, start_input_size, end_input_size))
+                                  scanned_end_samples(args.scan_size, start_input_size, end_input_size),
+                                  set_aside)
     else:
         # Signals as stored, inflated on the GPU beside the classification of the batch before:
         # several batches in flight per GPU, each on a replica of the models
         from . import realtime
-        replicas, _ = realtime.inflate_queues(replicas, host_share)
-        batches = _raw_batches(fast5_files, args, host_share, len(replicas))
-    for files, calls, lines in dispatch_batches(batches, replicas, classify_loaded):
-        read_id_to_fast5_file.update(files)
-        classifications.update(calls)
-        if full_output:
-            for line in lines:
-                print(line)
-        print_classification_progress(len(classifications), len(fast5_files), 'fast5s',
-                                      out_dest=out_dest)
+        replicas, queues = realtime.inflate_queues(replicas, host_share)
+        batches = _raw_batches(fast5_files, args, host_share, len(replicas), set_aside)
+    try:
+        yield from dispatch_batches(batches, replicas, classify_loaded)
+    finally:
+        for model in queues:                # the forward kernel gets every CU back
+            model.reserve_cus(0)
 
-    if full_output:
-        print('', file=sys.stderr)
-        if summary_table:
-            print_summary_table(classifications)
-    return classifications, read_id_to_fast5_file
+
+def classify_units(fast5_files, start_model, start_input_size, end_model, end_input_size,
+                   output_size, args):
+    """``classify --multi_read``: the reads of ``fast5_files`` - multi-read containers, one-read
+    files, or both - classified where they are; a generator: (its reads' files, calls, table
+    rows, files finished so far) per unit of work.  Five sampled files pick the route
+    (determine_single_or_multi_fast5s): containers go through the units ``realtime`` uses
+    (containers.py: one container = one unit, a stray one-read file is a container of one read),
+    in the order of the file list and reads in container order; a directory of one-read files
+    goes through the one-read batch paths, and a container met there is set aside and classified
+    after them."""
+    from . import containers
+    if not fast5_files:
+        return
+    fast5_files = list(fast5_files)
+    models = (start_model, start_input_size, end_model, end_input_size, output_size)
+    finished = 0
+    if determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
+        later = fast5_files
+    else:
+        later = []
+        singles = fast5_files
+        if reader_kind() == 'python':
+            # (the Python loader's processes cannot hand a file back: look before loading)
+            later = [f for f in fast5_files if _python_holds_several_reads(f)]
+            aside = set(later)
+            singles = [f for f in fast5_files if f not in aside]
+        for files, calls, lines, n_files in _one_read_batches(singles, *models, args,
+                                                              set_aside=later):
+            finished += n_files
+            yield files, calls, lines, finished
+    if not later:
+        return
+    units = containers.Units(args, start_input_size, end_input_size, output_size,
+                             keep=scanned_end_samples(args.scan_size, start_input_size,
+                                                      end_input_size),
+                             want_rows=True, threads=int(getattr(args, 'loader_procs', 0) or 0),
+                             skip_damaged=True)
+    items, work, replicas, queues = containers.route(later, start_model, end_model, units)
+    try:
+        for unit in dispatch_batches(items, replicas, work):
+            files = dict.fromkeys(unit.ids, unit.path)
+            yield (files, dict(zip(unit.ids, unit.names)), unit.lines,
+                   finished + unit.number - (0 if unit.last else 1))
+    finally:
+        for model in queues:                # the forward kernel gets every CU back
+            model.reserve_cus(0)
+
+
+def _python_holds_several_reads(fast5_file):
+    from .load_fast5s import get_root_level_keys
+    try:
+        keys = get_root_level_keys(fast5_file)
+    except Exception:       # a damaged file can trip anything: not a container, the loader skips it
+        return False
+    return 'Raw' not in keys and sum(1 for k in keys if k.startswith('read_')) > 1
 
 
 MODEL_INPUT_SIZE = 1024        # every shipped model (and the persistent forward kernel's size)
@@ -316,11 +398,13 @@ class RawBatch:
     def __init__(self, files, loaded):
         self.files = list(files)
         self.read_ids, self.offsets, self.status, self.comp, self.records = loaded
+        self.set_aside = 0          # multi-read files among them, left for the container units
 
 
-def _raw_batches(fast5_files, args, host_share, n_queues):
+def _raw_batches(fast5_files, args, host_share, n_queues, set_aside=None):
     """RawBatch after RawBatch, loaded ahead of the GPU: two loads at a time on background
-    threads (each on half of the loader's threads), as many waiting as there are queues."""
+    threads (each on half of the loader's threads), as many waiting as there are queues.
+    ``set_aside``: see _native_batches."""
     import collections
     from concurrent.futures import ThreadPoolExecutor
     from . import fast5_native
@@ -346,8 +430,12 @@ def _raw_batches(fast5_files, args, host_share, n_queues):
             chunk = next(upcoming, None)
             if chunk is not None:
                 waiting.append(pool.submit(load, chunk))
-            if (batch.status == fast5_native.F5_ERR_MULTI).any():
-                sys.exit('Error: Deepbinner does not (yet) support multi-read fast5 files')
+            multi = (batch.status == fast5_native.F5_ERR_MULTI)
+            if multi.any():
+                if set_aside is None:
+                    sys.exit('Error: Deepbinner does not (yet) support multi-read fast5 files')
+                set_aside.extend(f for f, m in zip(batch.files, multi.tolist()) if m)
+                batch.set_aside = int(multi.sum())
             warn_about_filters(batch.status)
             yield batch
 
@@ -375,22 +463,45 @@ def _classify_raw_batch(batch, start_replica, end_replica, args):
             read_ids[i] = None
             continue
         if verbose:
-            model = start_replica if start_replica is not None else end_replica
-            row = classify_read_batch(
-                [read_ids[i]], [samples[offsets[0]:offsets[1]]], start_replica,
-                getattr(start_replica, 'input_size', None), end_replica,
-                getattr(end_replica, 'input_size', None), model.n_classes, args, {})[0]
-            redone[i] = row
-            numbers[i] = _CALL_NAMES.index(row.split('\t')[1])
+            redone[i] = redone_verbose_row(read_ids[i], samples[offsets[0]:offsets[1]],
+                                           start_replica, end_replica, args)
+            numbers[i] = call_number(redone[i])
         else:
             numbers[i] = classify_packed_numbers(samples, offsets, start_replica, end_replica,
                                                  args)[0]
-    files, calls, lines = {}, {}, []
-    for i, (read_id, fast5_file, number) in enumerate(zip(read_ids, batch.files, numbers.tolist())):
+    files, calls = {}, {}
+    for read_id, fast5_file, number in zip(read_ids, batch.files, numbers.tolist()):
+        if read_id is not None:
+            files[read_id] = fast5_file
+            calls[read_id] = _CALL_NAMES[number]
+    return files, calls, raw_table_rows(read_ids, numbers, sides, redone, start_replica,
+                                        end_replica, verbose)
+
+
+def redone_verbose_row(read_id, signal, start_replica, end_replica, args):
+    """The verbose row of one read the host had to decode after the GPU's decoder refused its
+    stream: the per-read path of every other route (classify_read_batch)."""
+    model = start_replica if start_replica is not None else end_replica
+    return classify_read_batch(
+        [read_id], [signal], start_replica, getattr(start_replica, 'input_size', None),
+        end_replica, getattr(end_replica, 'input_size', None), model.n_classes, args, {})[0]
+
+
+def call_number(row):
+    """The call number (0 = 'none') a table row carries."""
+    return _CALL_NAMES.index(row.split('\t')[1])
+
+
+def raw_table_rows(read_ids, numbers, sides, redone, start_replica, end_replica, verbose):
+    """The table rows of a batch classified from its stored chunks (classify_pair_deflated):
+    ``numbers`` the final calls, ``sides`` what ``want_sides`` handed back (verbose only),
+    ``redone`` {read index: its finished row} for reads the host decoded; a read whose id is None
+    has no row."""
+    both = start_replica is not None and end_replica is not None
+    lines = []
+    for i, (read_id, number) in enumerate(zip(read_ids, np.asarray(numbers).tolist())):
         if read_id is None:
             continue
-        files[read_id] = fast5_file
-        calls[read_id] = _CALL_NAMES[number]
         if not verbose:
             lines.append(read_id + '\t' + _CALL_NAMES[number])
         elif i in redone:
@@ -406,20 +517,21 @@ def _classify_raw_batch(batch, start_replica, end_replica, args):
                 if both:
                     output.append(_CALL_NAMES[int(sides[side + '_calls'][i])])
             lines.append('\t'.join(output))
-    return files, calls, lines
+    return lines
 
 
-def load_in_batches(fast5_files, args, keep=None):
+def load_in_batches(fast5_files, args, keep=None, set_aside=None):
     """The reference's ``for fast5_batch in chunker(...)`` + per-file load (classify.py:141-150):
     yields, per batch of ``args.batch_size`` files, the list of (fast5_file, read_id, signal).
     With more than one loader process (``--loader_procs``, or automatically for big jobs) the
     files of later batches are loaded while the caller classifies the current one.  ``keep``:
     samples per read end the loaders keep (scanned_end_samples of the models; None = what
-    1024-sample models need)."""
+    1024-sample models need).  ``set_aside``: see _native_batches (the Python loaders leave on a
+    multi-read file whatever it is)."""
     if keep is None:
         keep = scanned_end_samples(args.scan_size)
     if reader_kind() == 'native':
-        yield from _native_batches(fast5_files, args, keep)
+        yield from _native_batches(fast5_files, args, keep, set_aside)
         return
     procs = choose_loader_procs(getattr(args, 'loader_procs', None), len(fast5_files))
     if procs <= 1:
@@ -438,11 +550,13 @@ def load_in_batches(fast5_files, args, keep=None):
             yield batch
 
 
-def _native_batches(fast5_files, args, keep):
+def _native_batches(fast5_files, args, keep, set_aside=None):
     """load_in_batches on the native loader (libdeepbinner_fast5.so): every batch is parsed and
     inflated by the library's own worker threads (``--loader_procs`` of them; 0 = one per hardware
     thread this process may keep busy - misc.usable_cpus - at most 32), and the next batch is loaded on a background thread - the
-    call releases the GIL - while the caller classifies the current one."""
+    call releases the GIL - while the caller classifies the current one.  A multi-read file ends
+    the run, unless the caller gave a list to ``set_aside`` such files in (--multi_read): then
+    the batch goes on without them."""
     from concurrent.futures import ThreadPoolExecutor
     from . import fast5_native
     threads = int(getattr(args, 'loader_procs', 0) or 0) or max(1, min(32, usable_cpus()))
@@ -456,7 +570,8 @@ def _native_batches(fast5_files, args, keep):
         for i, batch in enumerate(batches):
             read_ids, samples, offsets, status = pending.result()
             pending = executor.submit(load, batches[i + 1]) if i + 1 < len(batches) else None
-            if (status == fast5_native.F5_ERR_MULTI).any():
+            multi = (status == fast5_native.F5_ERR_MULTI)
+            if multi.any() and set_aside is None:
                 sys.exit('Error: Deepbinner does not (yet) support multi-read fast5 files')
             warn_about_filters(status)
             loaded = PackedBatch((f, read_ids[k], samples[offsets[k]:offsets[k + 1]]
@@ -464,6 +579,9 @@ def _native_batches(fast5_files, args, keep):
                                  for k, f in enumerate(batch))
             loaded.samples, loaded.offsets = samples, offsets
             loaded.complete = all(r is not None for r in read_ids)
+            if multi.any():
+                set_aside.extend(f for f, m in zip(batch, multi.tolist()) if m)
+                loaded.set_aside = int(multi.sum())
             yield loaded
 
 
@@ -490,6 +608,7 @@ class PackedBatch(list):
     a batch without unreadable files can go to the GPU as it is (``complete``)."""
     samples = offsets = None
     complete = False
+    set_aside = 0           # multi-read files among them, left for the container units
 
 
 class PackedSignals(list):

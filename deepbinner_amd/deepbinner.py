@@ -86,7 +86,11 @@ COMMANDS = {
                  [(('--verbose',), dict(action='store_true',
                                         help='Include the output probabilities for all barcodes '
                                              'in the results (default: just show the final '
-                                             'barcode call)')), _HELP]),
+                                             'barcode call)')),
+                  (('--multi_read',), dict(action='store_true',
+                                           help='Classify the reads of multi-read fast5 files '
+                                                'where they are (one-read files may be mixed '
+                                                'in)')), _HELP]),
     'realtime': ('Sort fast5 files during sequencing',
                  [('Required', [
                      (('--in_dir',), dict(type=str, required=True,

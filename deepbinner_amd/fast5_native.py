@@ -187,12 +187,19 @@ def get_read_id_and_signal(fast5_file):
         return None, None
 
 
-def iter_reads(fast5_file):
-    """(read_id, signal) for every read of a single- or multi-read fast5."""
+def iter_reads(fast5_file, skip_damaged=False):
+    """(read_id, signal) for every read of a single- or multi-read fast5, up to the first one that
+    cannot be read (``skip_damaged``: without those that cannot)."""
     try:
         with File(fast5_file) as f:
             for i in range(f.n_reads):
-                yield f.read_info(i)[0], f.read_signal(i)
+                try:
+                    read = f.read_info(i)[0], f.read_signal(i)
+                except (OSError, KeyError):
+                    if skip_damaged:
+                        continue
+                    raise
+                yield read
     except (OSError, KeyError):
         return
 

@@ -65,16 +65,18 @@ def _python_get_read_id_and_signal(fast5_file):
         return None, None
 
 
-def iter_reads(fast5_file):
-    """Yield (read_id, signal) for every read of a single- or multi-read fast5."""
+def iter_reads(fast5_file, skip_damaged=False):
+    """Yield (read_id, signal) for every read of a single- or multi-read fast5.  At the first read
+    that cannot be read the walk ends - or, with ``skip_damaged``, goes on behind it (what the
+    native loader's container streams do: a damaged read costs itself only)."""
     if reader_kind() == 'native':
         from . import fast5_native
-        yield from fast5_native.iter_reads(fast5_file)
+        yield from fast5_native.iter_reads(fast5_file, skip_damaged)
         return
-    yield from _python_iter_reads(fast5_file)
+    yield from _python_iter_reads(fast5_file, skip_damaged)
 
 
-def _python_iter_reads(fast5_file):
+def _python_iter_reads(fast5_file, skip_damaged=False):
     try:
         with hdf5_lite.File(str(fast5_file), 'r') as hdf5_file:
             keys = list(hdf5_file.keys())
@@ -83,7 +85,13 @@ def _python_iter_reads(fast5_file):
             else:
                 groups = [hdf5_file[k + '/Raw/'] for k in keys if k.startswith('read_')]
             for group in groups:
-                yield group.attrs['read_id'].decode(), group['Signal'][:]
+                try:
+                    read = group.attrs['read_id'].decode(), group['Signal'][:]
+                except Exception:
+                    if skip_damaged:
+                        continue
+                    raise
+                yield read
     except Exception:      # h5py: OSError / KeyError; a damaged file can trip anything else
         return
 
@@ -178,8 +186,10 @@ def find_all_fast5s(directory, verbose=False):
     return fast5s
 
 
-def determine_single_or_multi_fast5s(fast5s):
-    """Inspect up to five randomly chosen files (reference load_fast5s.py:67-90)."""
+def determine_single_or_multi_fast5s(fast5s, mixed_ok=False):
+    """Inspect up to five randomly chosen files (reference load_fast5s.py:67-90).  ``mixed_ok``
+    (``classify --multi_read``, which reads old one-read files and containers alike): old-format
+    files beside multi-read ones are no error."""
     sample = list(fast5s)
     random.shuffle(sample)
     kinds = set()
@@ -193,7 +203,7 @@ def determine_single_or_multi_fast5s(fast5s):
             kinds.add('single-new')
         elif read_count > 1:
             kinds.add('multi')
-    if 'multi' in kinds and 'single-old' in kinds:
+    if 'multi' in kinds and 'single-old' in kinds and not mixed_ok:
         sys.exit('Error: your reads appear to be a mixture of old and new formats. Deepbinner '
                  'can handle one or the other, but not both at once.')
     return 'multi' if 'multi' in kinds else 'single'

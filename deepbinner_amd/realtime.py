@@ -27,8 +27,8 @@ import tempfile
 import threading
 import time
 
-from . import classify
-from .load_fast5s import determine_single_or_multi_fast5s, iter_reads, reader_kind
+from . import classify, containers
+from .load_fast5s import determine_single_or_multi_fast5s, reader_kind
 from .misc import print_summary_table, usable_cpus
 
 POLL_SECONDS = 5
@@ -341,118 +341,11 @@ class Session:
         return None if self._signals_wanted() else classify.scanned_end_samples(
             self.args.scan_size, self.start_size, self.end_size)
 
-    def _packed_containers(self, fast5s):
-        """(container number, path, read ids, samples, offsets) per readable container, in order;
-        unreadable reads are dropped (the reference skips what it cannot read,
-        load_fast5s.py:47-49)."""
-        import numpy as np
-        from . import fast5_native
-        threads = int(getattr(self.args, 'loader_procs', 0) or 0)
-        stream = fast5_native.stream_reads(fast5s, keep=self._keep(), threads=threads,
-                                           depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)))
-        for index, ids, samples, offsets, status in stream:
-            if ids is None:
-                continue
-            classify.warn_about_filters(status)
-            where = list(range(len(ids)))          # which read of the container each one is
-            if any(rid is None for rid in ids):
-                where = [i for i, rid in enumerate(ids) if rid is not None]
-                parts = [samples[offsets[i]:offsets[i + 1]] for i in where]
-                lengths = [len(part) for part in parts]
-                samples = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int16)
-                offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-                ids = [ids[i] for i in where]
-            yield index + 1, fast5s[index], ids, samples, offsets, where
-
-    def _classify_container(self, item, start_replica, end_replica):
-        number, path, ids, samples, offsets, where = item
-        numbers = classify.classify_packed_numbers(samples, offsets, start_replica, end_replica,
-                                                   self.args)
-        names = [classify.call_name(c) for c in numbers.tolist()]
-        signal = (lambda i: samples[offsets[i]:offsets[i + 1]]) if self._signals_wanted() else None
-        return number, path, ids, names, signal, where
-
-    # The same with (part of) the inflating on the GPU: the loader hands over Signal chunks as
-    # stored - zlib streams; 85 % of what loading a read costs a CPU core is inflating them, and a
-    # host has few cores per GPU (DESIGN.md section 9) - and dbh_classify_pair_deflated does the
-    # rest.  The host's threads keep the longest streams of every container (a lane of the GPU
-    # decoder walks ONE stream, however long): `host_inflate_share` of the bytes.
-    def _raw_containers(self, fast5s, host_share, n_gpus=1):
-        from . import fast5_native
-        threads = int(getattr(self.args, 'loader_procs', 0) or 0)
-        if threads <= 0 and host_share == 0:
-            # nothing to inflate: a read costs a loader thread ~5 us, and a GPU takes ~210 k a second -
-            # two threads feed it, sixteen cost the process 19 us of CPU per read instead of 13
-            # (woken sixteen times per container for a fifth of what they can deliver:
-            # profiles/r06_loader/loader_team_size.txt)
-            threads = min(usable_cpus(), RAW_LOADER_THREADS_PER_GPU * max(1, n_gpus))
-        stream = fast5_native.stream_raw(fast5s, threads=threads, host_inflate_above=-host_share,
-                                         depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)),
-                                         vbz_zstd=fast5_native.vbz_zstd_route())
-        for index, ids, offsets, status, comp, records in stream:
-            if ids is None:
-                continue
-            classify.warn_about_filters(status)
-            yield index + 1, fast5s[index], ids, offsets, comp, records
-
-    def _classify_raw_container(self, item, start_replica, end_replica):
-        import numpy as np
-        from . import fast5_native, hip_backend
-        number, path, ids, offsets, comp, records = item
-        cus = inflate_cus_for(records['comp_bytes'].tolist(), records['mode'].tolist())
-        if cus is not None:
-            for model in (start_replica, end_replica):
-                if model is not None:
-                    model.reserve_cus(cus)
-        result = hip_backend.classify_pair_deflated(
-            start_replica, end_replica, comp, records, offsets, int(self.args.scan_size),
-            self.args.score_diff, classify.combine_mode(self.args) if start_replica is not None and
-            end_replica is not None else 'require_either', want_samples=self._signals_wanted())
-        numbers, stream_status = result[0], result[1]
-        samples = result[2] if self._signals_wanted() else None
-        redone = {}
-        for i in sorted(set(records['read'][stream_status != 0].tolist())):
-            # a stream the GPU decoder refused (damaged, or beyond it): zlib on the host has the
-            # last word, as it has in the reference (h5py -> libhdf5 -> zlib)
-            try:
-                _, one, one_offsets, one_status = fast5_native.load_reads(path, first=i, count=1,
-                                                                          threads=1)
-            except OSError:
-                one_status = [1]
-            classify.warn_about_filters(np.asarray(one_status))
-            if one_status[0] != 0:
-                ids[i] = None
-                continue
-            numbers[i] = classify.classify_packed_numbers(one, one_offsets, start_replica,
-                                                          end_replica, self.args)[0]
-            redone[i] = np.array(one)
-        keep = [i for i, rid in enumerate(ids) if rid is not None]
-        names = [classify.call_name(int(numbers[i])) for i in keep]
-
-        def signal(k):
-            i = keep[k]
-            return redone[i] if i in redone else samples[offsets[i]:offsets[i + 1]]
-
-        return (number, path, [ids[i] for i in keep], names,
-                signal if samples is not None else None, keep)
-
-    def _read_chunks(self, fast5s):
-        """The same units for the Python reader and for models without the packed entry point:
-        (container number, path, read ids, signals) per --batch_size reads."""
-        for number, path in enumerate(fast5s, start=1):
-            try:
-                reads = list(iter_reads(path))
-            except OSError:
-                continue
-            for chunk in classify.chunker(reads, self.args.batch_size):
-                yield number, path, [r[0] for r in chunk], [r[1] for r in chunk]
-
-    def _classify_chunk(self, item, start_replica, end_replica):
-        number, path, ids, signals = item
-        found = {}
-        classify.classify_read_batch(ids, signals, start_replica, self.start_size, end_replica,
-                                     self.end_size, self.n_classes, self.args, found)
-        return number, path, ids, [found[rid] for rid in ids], signals.__getitem__, None
+    def _units(self):
+        """What the shared container units (containers.py) take from this session."""
+        return containers.Units(self.args, self.start_size, self.end_size, self.n_classes,
+                                keep=self._keep(), want_signals=self._signals_wanted(),
+                                threads=int(getattr(self.args, 'loader_procs', 0) or 0))
 
     def _tabulate_multi_read_files(self, fast5s, per_pass):
         """Classifies (and bins) the reads of the multi-read containers ``fast5s`` where they are;
@@ -483,20 +376,9 @@ class Session:
             finally:
                 in_flight.release()
 
-        models = [m for m in (self.start_model, self.end_model) if m is not None]
-        packed = reader_kind() == 'native' and all(hasattr(m, 'classify_packed') for m in models)
-        replicas = classify.device_replicas(self.start_model, self.end_model)
-        host_share = host_inflate_share(len({getattr(r[0] or r[1], 'device', 0) for r in replicas}))
-        queues = []
-        if packed and host_share < 100 and all(hasattr(m, 'handle') for m in models):
-            items = self._raw_containers(
-                fast5s, host_share, len({getattr(r[0] or r[1], 'device', 0) for r in replicas}))
-            work = self._classify_raw_container
-            replicas, queues = inflate_queues(replicas, host_share)
-        elif packed:
-            items, work = self._packed_containers(fast5s), self._classify_container
-        else:
-            items, work = self._read_chunks(fast5s), self._classify_chunk
+        # raw chunks inflated on the GPU, packed buffers, or per-batch lists: containers.route
+        items, work, replicas, queues = containers.route(fast5s, self.start_model,
+                                                         self.end_model, self._units())
         metadata = MetadataSource() if not self.table_only else None     # (the Python writer's)
         # The native writer: one call per container, two containers at a time on background
         # threads (the library's own worker threads do the reads of a container in parallel - four
@@ -560,8 +442,9 @@ class Session:
         try:
             with open(str(self.out_dir / 'multi_read_classifications.tsv'), 'at') as table:
                 classify.print_classification_progress(0, 1, 'reads', out_dest=sys.stdout)
-                for number, path, ids, names, signal, where in classify.dispatch_batches(
-                        items, replicas, work):
+                for unit in classify.dispatch_batches(items, replicas, work):
+                    number, path, ids, names = unit.number, unit.path, unit.ids, unit.names
+                    signal, where = unit.signal, unit.where
                     while group_of(number) > group:
                         table.flush()
                         yield close_group(group, calls, written, jobs)

@@ -637,13 +637,17 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
     the rendezvous with DEEPBINNER_COMM=host) so that rank 0 can print the summary and return
     what the single-process path returns (reference classify.py:106-180); the other ranks return
     ``({}, {})``.  A fatal error on any rank (the reference's ``sys.exit('Error: ...')`` cases)
-    is agreed on before any collective, so that all ranks leave together with that message."""
+    is agreed on before any collective, so that all ranks leave together with that message.
+    With ``--multi_read`` the files may be multi-read containers: they are sharded by file all the
+    same, every rank classifies its own with ``classify.classify_units`` (a rank without files
+    still takes part in every collective), and rank 0's progress counts its finished files."""
     from . import classify as c
     from .load_fast5s import determine_single_or_multi_fast5s
     from .misc import print_summary_table
 
     rank, local_rank, world = env_world()
     rdzv = Rendezvous(rank, world)
+    multi_read = bool(getattr(args, 'multi_read', False))
 
     def together(fn):
         """Run fn on this rank; if it fails anywhere - the reference's ``sys.exit('Error: ...')``
@@ -670,7 +674,8 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
             sys.exit('Error: no fast5 files found')
         files = sorted(fast5_files)             # os.walk order may differ between processes
         # the reference samples five files at random; every rank must look at the same five
-        if rank == 0 and determine_single_or_multi_fast5s(files) == 'multi':
+        if (rank == 0 and not multi_read and
+                determine_single_or_multi_fast5s(files) == 'multi'):
             sys.exit('Error: deepbinner classify requires one-read-per-file fast5s - convert '
                      'with multi_to_single_fast5 before running')
         return files
@@ -685,6 +690,17 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
                               output_size)
         sys.stdout.flush()
     classifications, id_to_file, lines = {}, {}, []
+
+    def classify_shard_units():
+        for files_of, calls, rows, finished in c.classify_units(
+                mine, start_model, start_input_size, end_model, end_input_size, output_size,
+                args):
+            id_to_file.update(files_of)
+            classifications.update(calls)
+            lines.extend(rows)
+            if rank == 0:
+                c.print_classification_progress(min(finished * world, len(files)), len(files),
+                                                'fast5s')
 
     def classify_shard():
         keep = c.scanned_end_samples(args.scan_size, start_input_size, end_input_size)
@@ -708,7 +724,7 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
                 c.print_classification_progress(min(len(classifications) * world, len(files)),
                                                 len(files), 'fast5s')
 
-    together(classify_shard)
+    together(classify_shard_units if multi_read else classify_shard)
 
     # the table: every rank writes its own rows when the ranks before it are done
     for turn in range(world):
@@ -738,7 +754,8 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
                 call = int(all_calls[at + k])
                 merged[read_id] = 'none' if call == 0 else str(call)
             at += counts[r]
-        c.print_classification_progress(len(merged), len(files), 'fast5s')
+        c.print_classification_progress(len(files) if multi_read else len(merged), len(files),
+                                        'fast5s')
         print('', file=sys.stderr)
         print_summary_table(merged)
         result = (merged, merged_files)
