@@ -413,10 +413,12 @@ def _raw_batches(fast5_files, args, host_share, n_queues, set_aside=None):
     chunks = list(chunker(fast5_files, size))
 
     def load(chunk):
-        # DEEPBINNER_VBZ_ZSTD=gpu: VBZ chunks keep their zstd stage for the GPU (default: host)
+        # DEEPBINNER_VBZ_ZSTD=gpu: VBZ chunks keep their zstd stage for the GPU (default: host);
+        # DEEPBINNER_SHUFFLE=gpu: so do shuffled chunks their shuffle
         return RawBatch(chunk, fast5_native.load_batch_raw(chunk, max(1, threads // 2),
                                                             -host_share,
-                                                            vbz_zstd=fast5_native.vbz_zstd_route()))
+                                                            vbz_zstd=fast5_native.vbz_zstd_route(),
+                                                            shuffle=fast5_native.shuffle_route()))
 
     with ThreadPoolExecutor(max_workers=2, thread_name_prefix='deepbinner-raw-loader') as pool:
         waiting = collections.deque()

@@ -14,8 +14,8 @@ container with an external tool first (realtime.py:183-190) and refuses it in ``
   at a time through ``classify.classify_read_batch``.
 
 ``route`` picks one (the rule is ``realtime``'s: DEEPBINNER_GPU_INFLATE,
-DEEPBINNER_HOST_INFLATE_SHARE, DEEPBINNER_LOADER_DEPTH, DEEPBINNER_VBZ_ZSTD) and hands back the
-stream of units and the function ``classify.dispatch_batches`` runs on each.
+DEEPBINNER_HOST_INFLATE_SHARE, DEEPBINNER_LOADER_DEPTH, DEEPBINNER_VBZ_ZSTD, DEEPBINNER_SHUFFLE)
+and hands back the stream of units and the function ``classify.dispatch_batches`` runs on each.
 """
 
 import functools
@@ -115,7 +115,8 @@ def raw_containers(fast5s, units, host_share, n_gpus=1):
         threads = min(usable_cpus(), realtime.RAW_LOADER_THREADS_PER_GPU * max(1, n_gpus))
     stream = fast5_native.stream_raw(fast5s, threads=threads, host_inflate_above=-host_share,
                                      depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)),
-                                     vbz_zstd=fast5_native.vbz_zstd_route())
+                                     vbz_zstd=fast5_native.vbz_zstd_route(),
+                                     shuffle=fast5_native.shuffle_route())
     for index, ids, offsets, status, comp, records in stream:
         if ids is None:
             continue

@@ -1418,8 +1418,11 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
     for (int64_t i = 0; i < n_streams; ++i) order[(size_t)i] = (int32_t)i;
     std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
         const dbh_inflate_stream &x = streams_host[a], &y = streams_host[b];
-        const int64_t kx = x.mode == DBH_INFLATE_ZLIB ? x.comp_bytes : -1;
-        const int64_t ky = y.mode == DBH_INFLATE_ZLIB ? y.comp_bytes : -1;
+        // (a shuffled deflate stream is a deflate stream: DBH_INFLATE_ZLIB_SHUFFLE)
+        const bool zx = x.mode == DBH_INFLATE_ZLIB || x.mode == DBH_INFLATE_ZLIB_SHUFFLE;
+        const bool zy = y.mode == DBH_INFLATE_ZLIB || y.mode == DBH_INFLATE_ZLIB_SHUFFLE;
+        const int64_t kx = zx ? x.comp_bytes : -1;
+        const int64_t ky = zy ? y.comp_bytes : -1;
         return kx != ky ? kx > ky : a < b;
     });
     {
@@ -1466,7 +1469,8 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
         if (per_lane <= 0) {
             int64_t sum = 0, count = 0;
             for (int64_t i = 0; i < n_streams; ++i)
-                if (streams_host[i].mode == DBH_INFLATE_ZLIB) {
+                if (streams_host[i].mode == DBH_INFLATE_ZLIB ||
+                    streams_host[i].mode == DBH_INFLATE_ZLIB_SHUFFLE) {
                     sum += streams_host[i].comp_bytes;
                     ++count;
                 }

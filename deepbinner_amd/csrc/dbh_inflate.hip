@@ -38,6 +38,8 @@
 //      could be overtaken by a write that wraps around the ring goes in token order instead:
 //      dbh_inflate_core.h, ring_hazard): 3.04 ms.
 //      The ring is written out in coalesced 256-byte pieces, with the Adler-32 sums on the way.
+// A stream of mode DBH_INFLATE_ZLIB_SHUFFLE (shuffle + deflate) is a zlib stream behind a 4-byte
+// prefix to every kernel here (zlib_view); its bytes are de-interleaved behind them (dbh_vbz.hip).
 // Streams of mode DBH_INFLATE_VBZ (ONT's VBZ filter, zstd stage undone by the loader) and
 // DBH_INFLATE_VBZ_ZSTD (the chunk as stored) are no kernel's here: both kernels pass them by, and
 // dbh_zstd.hip's and dbh_vbz.hip's kernels, launched behind them by dbh_inflate_dev, decode them.
@@ -154,6 +156,35 @@ struct StreamInfo {
     int64_t produced;
 };
 
+// What the inflate kernels make of a record - all four forms of them, through this one helper.
+// A stream of mode DBH_INFLATE_ZLIB_SHUFFLE (u32 LE N, then a zlib stream whose content is N
+// shuffled bytes) is to them the DBH_INFLATE_ZLIB stream behind its prefix, wanted N: its bytes go
+// to the stream's output region, where dbh_vbz.hip's kernel finds and de-interleaves them.  With a
+// prefix that cannot be (odd, beyond out_bytes, outside the buffer) there is nothing to decode: a
+// stored stream of no bytes, i.e. zeros - dbh_vbz.hip's kernel applies the same test and refuses
+// it.  DBH_INFLATE_STORED_SHUFFLE is that kernel's alone (passed_by).  Every other record: itself.
+__device__ __forceinline__ dbh_inflate_stream zlib_view(const dbh_inflate_stream& s,
+                                                        const uint8_t* __restrict__ comp,
+                                                        int64_t comp_total) {
+    if (s.mode != DBH_INFLATE_ZLIB_SHUFFLE) return s;
+    dbh_inflate_stream v = s;
+    v.mode = DBH_INFLATE_STORED;
+    v.comp_bytes = 0;
+    if (s.comp_offset < 0 || s.comp_bytes < 4 || s.comp_offset > comp_total - s.comp_bytes) return v;
+    uint32_t n;
+    __builtin_memcpy(&n, comp + s.comp_offset, 4);
+    if ((n & 1u) || (int64_t)n > s.out_bytes) return v;
+    v.mode = DBH_INFLATE_ZLIB;
+    v.comp_offset = s.comp_offset + 4;
+    v.comp_bytes = s.comp_bytes - 4;
+    v.out_bytes = (int64_t)n;
+    return v;
+}
+// the modes that are other kernels' (dbh_vbz.hip, dbh_zstd.hip): kernel 2 leaves their output alone
+__device__ __forceinline__ bool passed_by(int mode) {
+    return mode == DBH_INFLATE_VBZ || mode == DBH_INFLATE_VBZ_ZSTD || mode == DBH_INFLATE_STORED_SHUFFLE;
+}
+
 // STREAMS PER LANE (round 5; DBI_PER_LANE, default 1).  A token is one dependent chain of ~190
 // vector instructions with five dependent LDS reads in it, and a container's 4,000 streams are 63
 // waves for the GPU's 1,024 SIMDs: a wave decodes alone, nothing fills its latencies.  The obvious
@@ -245,7 +276,7 @@ __global__ __launch_bounds__(kLanes) void inflate_tokens_kernel(
                     more = false;
                     break;
                 }
-                const dbh_inflate_stream st = streams[cur[s]];
+                const dbh_inflate_stream st = zlib_view(streams[cur[s]], comp, comp_total);
                 n_tok[s] = 0;
                 if (st.mode == DBH_INFLATE_ZLIB) {
                     // (the caller's buffer is readable for 64 bytes beyond comp_total)
@@ -550,7 +581,7 @@ __global__ __launch_bounds__(dbi::kWaveLanes) __attribute__((amdgpu_waves_per_eu
     const int lane = threadIdx.x;
     const int i = blockIdx.x;
     if (i >= n_streams) return;
-    const dbh_inflate_stream st = streams[i];
+    const dbh_inflate_stream st = zlib_view(streams[i], comp, comp_total);
     const StreamInfo rec = tokens_wave_stream(lds, comp, comp_total, st, tokens, lane, NoProgress());
     if (lane == 0) info[i] = rec;
 }
@@ -605,7 +636,8 @@ struct AdlerLane {
 };
 
 __global__ __launch_bounds__(64 * kWaves2) void inflate_resolve_kernel(
-    const uint8_t* __restrict__ comp, const dbh_inflate_stream* __restrict__ streams, int n_streams,
+    const uint8_t* __restrict__ comp, int64_t comp_total,
+    const dbh_inflate_stream* __restrict__ streams, int n_streams,
     const uint32_t* __restrict__ tokens, StreamInfo* __restrict__ info, uint8_t* __restrict__ out,
     int32_t* __restrict__ status_out) {
     __shared__ __attribute__((aligned(16))) uint8_t rings[kWaves2 * kRing];
@@ -613,10 +645,10 @@ __global__ __launch_bounds__(64 * kWaves2) void inflate_resolve_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t* ring = rings + wave * kRing;
     for (int i = blockIdx.x * kWaves2 + wave; i < n_streams; i += gridDim.x * kWaves2) {
-        const dbh_inflate_stream s = streams[i];
+        const dbh_inflate_stream s = zlib_view(streams[i], comp, comp_total);
         uint8_t* dst = out + s.out_offset;
         const int64_t cap = s.out_bytes;
-        if (s.mode == DBH_INFLATE_VBZ || s.mode == DBH_INFLATE_VBZ_ZSTD) continue;     // (dbh_vbz.hip, dbh_zstd.hip)
+        if (passed_by(s.mode)) continue;             // (dbh_vbz.hip, dbh_zstd.hip)
         if (s.mode != DBH_INFLATE_ZLIB) {
             // stored as it is (an unfiltered chunk, a contiguous dataset, or bytes the host has
             // inflated itself): copy, zero-extend
@@ -890,7 +922,7 @@ __device__ __forceinline__ void resolve_pre_stream(
     {
         uint8_t* dst = out + s.out_offset;
         const int64_t cap = s.out_bytes;
-        if (s.mode == DBH_INFLATE_VBZ || s.mode == DBH_INFLATE_VBZ_ZSTD) return;       // (dbh_vbz.hip, dbh_zstd.hip)
+        if (passed_by(s.mode)) return;               // (dbh_vbz.hip, dbh_zstd.hip)
         if (s.mode != DBH_INFLATE_ZLIB) {
             const int64_t have = s.comp_bytes < cap ? s.comp_bytes : cap;
             const uint8_t* src = comp + s.comp_offset;
@@ -1037,13 +1069,14 @@ __device__ __forceinline__ void resolve_pre_stream(
 }
 
 __global__ __launch_bounds__(64) void inflate_resolve_pre_kernel(
-    const uint8_t* __restrict__ comp, const dbh_inflate_stream* __restrict__ streams, int n_streams,
+    const uint8_t* __restrict__ comp, int64_t comp_total,
+    const dbh_inflate_stream* __restrict__ streams, int n_streams,
     const uint32_t* __restrict__ tokens, StreamInfo* __restrict__ info, uint8_t* out,
     int32_t* __restrict__ status_out) {
     __shared__ __attribute__((aligned(16))) uint8_t ring[kRing3];
     const int lane = threadIdx.x;
     for (int i = blockIdx.x; i < n_streams; i += gridDim.x) {
-        const dbh_inflate_stream s = streams[i];
+        const dbh_inflate_stream s = zlib_view(streams[i], comp, comp_total);
         resolve_pre_stream(ring, comp, s, tokens, AllTokensThere{info[i]}, out, status_out + i, lane);
     }
 }
@@ -1122,7 +1155,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         words.done = 0;
     }
     __syncthreads();
-    const dbh_inflate_stream st = streams[i];
+    const dbh_inflate_stream st = zlib_view(streams[i], comp, comp_total);
     if (wave == 0) {
         const StreamInfo rec = tokens_wave_stream(decode, comp, comp_total, st, tokens, lane,
                                                   PairProgress{&words, lane});
@@ -1182,12 +1215,14 @@ int hip_failed(hipError_t e, const char* what) {
 
 using namespace dbh_inflate_detail;
 
-// dbh_vbz.hip: the streams of mode DBH_INFLATE_VBZ (the kernels above leave them alone)
+// dbh_vbz.hip: the streams of mode DBH_INFLATE_VBZ (the kernels above leave them alone), and the
+// de-interleave of the shuffled ones (DBH_INFLATE_ZLIB_SHUFFLE, whose records of kernel 1 it reads:
+// `ended` and `produced`; DBH_INFLATE_STORED_SHUFFLE)
 hipError_t dbh_vbz_launch(const uint8_t* comp_dev, int64_t comp_bytes,
                           const dbh_inflate_stream* streams_dev, int n_streams,
                           int64_t total_out_bytes, uint8_t* out_dev, int32_t* status_dev,
-                          const uint8_t* work_dev, const char* produced0, int64_t produced_stride,
-                          hipStream_t stream);
+                          uint8_t* work_dev, const char* produced0, const char* ended0,
+                          int64_t record_stride, hipStream_t stream);
 // dbh_zstd.hip: the zstd stage of the streams of mode DBH_INFLATE_VBZ_ZSTD, into their workspace
 // slots; the content size of each into the `produced` word of its record
 hipError_t dbh_zstd_launch(const uint8_t* comp_dev, int64_t comp_bytes,
@@ -1204,7 +1239,8 @@ int vbz_stages(const uint8_t* comp_dev, int64_t comp_bytes, const dbh_inflate_st
     DBI_HIP(dbh_zstd_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes,
                             (uint8_t*)workspace_dev, status_dev, produced0, (int64_t)sizeof(StreamInfo), stream));
     DBI_HIP(dbh_vbz_launch(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, status_dev,
-                           (const uint8_t*)workspace_dev, produced0, (int64_t)sizeof(StreamInfo), stream));
+                           (uint8_t*)workspace_dev, produced0, reinterpret_cast<const char*>(&info[0].ended),
+                           (int64_t)sizeof(StreamInfo), stream));
     return DBH_OK;
 }
 }  // namespace dbh_inflate_detail
@@ -1264,11 +1300,11 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
     const int blocks = groups < 1024 ? groups : 1024;
     if (resolve_pre())
         hipLaunchKernelGGL(inflate_resolve_pre_kernel, dim3((unsigned)(n < 65536 ? n : 65536)), dim3(64), 0,
-                           (hipStream_t)stream, comp_dev, streams_dev, n, (const uint32_t*)tokens,
+                           (hipStream_t)stream, comp_dev, comp_bytes, streams_dev, n, (const uint32_t*)tokens,
                            info, out_dev, status_dev);
     else
         hipLaunchKernelGGL(inflate_resolve_kernel, dim3((unsigned)blocks), dim3(64 * kWaves2), 0,
-                           (hipStream_t)stream, comp_dev, streams_dev, n, (const uint32_t*)tokens,
+                           (hipStream_t)stream, comp_dev, comp_bytes, streams_dev, n, (const uint32_t*)tokens,
                            info, out_dev, status_dev);
     DBI_HIP(hipGetLastError());
     return vbz_stages(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, workspace_dev, info,

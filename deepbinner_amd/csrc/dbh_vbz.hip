@@ -18,7 +18,11 @@
 // beyond the stream, data that would run past its end or that end before it: status != 0 and
 // the stream's output all zeros; its neighbours are not touched.  Reads stay inside the stream's
 // bytes plus the 3 bytes a 4-byte load of its last value may take beyond them (the compressed
-// buffer is readable for 64 bytes beyond its end).  No LDS, no scalar stores.
+// buffer is readable for 64 bytes beyond its end).  No LDS, vector loads and stores only.
+//
+// The same grid undoes HDF5's shuffle filter for the streams of mode DBH_INFLATE_ZLIB_SHUFFLE and
+// DBH_INFLATE_STORED_SHUFFLE (shuffle_stream below): it visits every stream behind the inflate
+// kernels anyway, and a launch of its own would be empty on every default route.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -160,10 +164,103 @@ __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int
     if (lane == 0) *status_slot = bad ? refused : 0;
 }
 
+// ---- HDF5's shuffle filter for int16, undone (DBH_INFLATE_ZLIB_SHUFFLE, DBH_INFLATE_STORED_SHUFFLE) ----
+// The N shuffled bytes are the N/2 low bytes of the samples, then their N/2 high bytes.  One wave
+// per stream, as everything in this kernel.
+
+// samples [i0, i1) from the two planes: lane by lane up to the first 16-byte boundary of dst, then
+// every lane 8 bytes of each plane, interleaved, as one 16-byte store, then the tail lane by lane
+__device__ __forceinline__ void unshuffle_i16(const uint8_t* lo, const uint8_t* hi, uint8_t* dst,
+                                              int64_t n, int lane) {
+    int64_t head = (int64_t)((16u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) / 2;
+    if (head > n) head = n;
+    const int64_t body = (n - head) / 8;
+    for (int64_t i = lane; i < head; i += 64) {
+        const uint16_t v = (uint16_t)(lo[i] | ((unsigned)hi[i] << 8));
+        *reinterpret_cast<uint16_t*>(dst + 2 * i) = v;
+    }
+    for (int64_t b = lane; b < body; b += 64) {
+        const int64_t i = head + 8 * b;
+        uint64_t l, h;
+        __builtin_memcpy(&l, lo + i, 8);
+        __builtin_memcpy(&h, hi + i, 8);
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t l2 = (uint32_t)(l >> (16 * k)) & 0xFFFFu, h2 = (uint32_t)(h >> (16 * k)) & 0xFFFFu;
+            w[k] = (l2 & 0xFFu) | ((h2 & 0xFFu) << 8) | ((l2 >> 8) << 16) | ((h2 >> 8) << 24);
+        }
+        *reinterpret_cast<uint4*>(dst + 2 * i) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    for (int64_t i = head + 8 * body + lane; i < n; i += 64) {
+        const uint16_t v = (uint16_t)(lo[i] | ((unsigned)hi[i] << 8));
+        *reinterpret_cast<uint16_t*>(dst + 2 * i) = v;
+    }
+}
+
+// `slots`: the stream's token slots in the workspace (4 * out_bytes bytes at 4 * out_offset), dead
+// once the inflate kernels are done with the stream.  DBH_INFLATE_ZLIB_SHUFFLE: they have left the
+// N shuffled bytes in the stream's output region, their verdict in *status_slot, and in `ended` /
+// `produced` whether the deflate data ended, and with how many bytes.
+__device__ __forceinline__ void shuffle_stream(const uint8_t* __restrict__ comp, int64_t comp_total,
+                                               const dbh_inflate_stream& s, int64_t total_out,
+                                               uint8_t* out, int32_t* status_slot, int lane,
+                                               uint8_t* work, int ended, int64_t produced) {
+    // an output region outside the buffer is not written at all
+    if (s.out_offset < 0 || s.out_bytes < 0 || (s.out_offset & 1) ||
+        s.out_offset > total_out - s.out_bytes) {
+        if (lane == 0) *status_slot = DBH_INFLATE_SHUFFLE_REFUSED;
+        return;
+    }
+    uint8_t* const dst = out + s.out_offset;
+    int status = DBH_INFLATE_SHUFFLE_REFUSED;
+    int64_t written = 0;                           // bytes of dst that hold samples
+    if (s.comp_offset >= 0 && s.comp_bytes >= 4 && s.comp_offset <= comp_total - s.comp_bytes) {
+        const uint8_t* const src = comp + s.comp_offset;
+        const int64_t n = (int64_t)load_u32(src);
+        if (s.mode == DBH_INFLATE_STORED_SHUFFLE) {
+            if (!(n & 1) && s.comp_bytes == 4 + n) {
+                written = (n < s.out_bytes ? n : s.out_bytes) & ~(int64_t)1;
+                unshuffle_i16(src + 4, src + 4 + n / 2, dst, written / 2, lane);
+                status = 0;
+            }
+        } else if (!(n & 1) && n <= s.out_bytes) {
+            const int before = *status_slot;       // (every lane reads it before lane 0 writes)
+            if (before != 0) {
+                status = before;                   // the zlib stage's own reason stays
+            } else if (ended && produced == n) {
+                // the region's bytes to the slots, coalesced; then back, de-interleaved
+                uint8_t* const slots = work + 4 * s.out_offset;
+                const int64_t whole = n & ~(int64_t)15;
+                for (int64_t k = 16 * (int64_t)lane; k < whole; k += 1024) {
+                    uint4 v;
+                    __builtin_memcpy(&v, dst + k, 16);
+                    __builtin_memcpy(slots + k, &v, 16);
+                }
+                for (int64_t k = whole + 2 * lane; k < n; k += 128)
+                    *reinterpret_cast<uint16_t*>(slots + k) = *reinterpret_cast<const uint16_t*>(dst + k);
+                // (the lanes of ONE wave: what they stored is what they load behind this - by the
+                // order of accesses that go through one CU's L1, which is what a workgroup-scope
+                // fence stands for in the default mode; a build with -mtgsplit, where the waves of
+                // a workgroup may sit on different CUs, makes the fence do more, never less)
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                unshuffle_i16(slots, slots + n / 2, dst, n / 2, lane);
+                written = n;
+                status = 0;
+            }
+        }
+    }
+    // zero-extension, or all of it for a refused stream
+    for (int64_t k = written + 2 * lane; k + 1 < s.out_bytes; k += 128)
+        *reinterpret_cast<uint16_t*>(dst + k) = 0;
+    if ((s.out_bytes & 1) && lane == 0) dst[s.out_bytes - 1] = 0;      // (half a sample: no data)
+    if (lane == 0) *status_slot = status;
+}
+
 __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
     const uint8_t* __restrict__ comp, int64_t comp_total,
     const dbh_inflate_stream* __restrict__ streams, int n_streams, int64_t total_out,
-    uint8_t* __restrict__ out, int32_t* status_out, const uint8_t* work, const char* produced0,
+    uint8_t* out, int32_t* status_out, uint8_t* work, const char* produced0, const char* ended0,
     int64_t produced_stride) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -177,6 +274,12 @@ __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
                        work + (placed ? 4 * s.out_offset : 0), placed ? have : 0);
             continue;
         }
+        if (s.mode == DBH_INFLATE_ZLIB_SHUFFLE || s.mode == DBH_INFLATE_STORED_SHUFFLE) {
+            shuffle_stream(comp, comp_total, s, total_out, out, status_out + i, lane, work,
+                           *reinterpret_cast<const int32_t*>(ended0 + (int64_t)i * produced_stride),
+                           *reinterpret_cast<const int64_t*>(produced0 + (int64_t)i * produced_stride));
+            continue;
+        }
         if (s.mode != DBH_INFLATE_VBZ) continue;
         vbz_stream(comp, comp_total, s, total_out, out, status_out + i, lane);
     }
@@ -188,11 +291,13 @@ __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
 __attribute__((visibility("hidden"))) hipError_t dbh_vbz_launch(
     const uint8_t* comp_dev, int64_t comp_bytes, const dbh_inflate_stream* streams_dev,
     int n_streams, int64_t total_out_bytes, uint8_t* out_dev, int32_t* status_dev,
-    const uint8_t* work_dev, const char* produced0, int64_t produced_stride, hipStream_t stream) {
+    uint8_t* work_dev, const char* produced0, const char* ended0, int64_t produced_stride,
+    hipStream_t stream) {
     using namespace dbh_vbz_detail;
     const int blocks = (n_streams + kWaves - 1) / kWaves;
     hipLaunchKernelGGL(vbz_decode_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)),
                        dim3(64 * kWaves), 0, stream, comp_dev, comp_bytes, streams_dev, n_streams,
-                       total_out_bytes, out_dev, status_dev, work_dev, produced0, produced_stride);
+                       total_out_bytes, out_dev, status_dev, work_dev, produced0, ended0,
+                       produced_stride);
     return hipGetLastError();
 }

@@ -452,6 +452,11 @@ class Fast5 {
         bool vbz_zstd = false;
         // the chunk goes out as stored, zstd frame and all (F5_RAW_VBZ_ZSTD): the GPU undoes it
         bool vbz_gpu = false;
+        // kZlib / kStored of a shuffled chunk the GPU unshuffles (F5_RAW_ZLIB_SHUFFLE,
+        // F5_RAW_STORED_SHUFFLE): 4, the bytes of the u32 LE count * 2 that goes in front of the
+        // piece's bytes in the batch's byte buffer; every other piece: 0 (a staged stream that
+        // f5_load_batch_raw leaves to the host's share keeps it: inflated, then unshuffled)
+        int prefix = 0;
     };
     enum { kZlib = 0, kStored = 1, kHostDecode = 2, kZeros = 3, kVbz = 4 };
 
@@ -459,8 +464,10 @@ class Fast5 {
     // GPU decoder walks ONE stream: a stream ten times the usual length holds its wave ten times
     // as long, while a CPU core inflates it in a millisecond); <= 0: no limit.
     // vbz_zstd_gpu (F5_RAW_FLAG_VBZ_ZSTD_GPU): VBZ chunks with a zstd stage are handed on as stored.
+    // shuffle_gpu (F5_RAW_FLAG_SHUFFLE_GPU): whole chunks of shuffle (element size 2) + deflate,
+    // or of shuffle alone, with or without fletcher32 behind, go out as stored, a prefix in front.
     void signal_pieces(const SignalInfo& s, int64_t zlib_above, std::vector<RawPiece>* out,
-                       bool vbz_zstd_gpu = false) const {
+                       bool vbz_zstd_gpu = false, bool shuffle_gpu = false) const {
         out->clear();
         if (s.n <= 0) return;
         RawPiece p;
@@ -497,6 +504,9 @@ class Fast5 {
             q.first = k * s.chunk_elems;
             q.count = std::min<int64_t>(s.chunk_elems, s.n - q.first);
         }
+        bool shuffle_i16 = false;                  // the pipeline's shuffle is one of 2-byte elements
+        for (const Filter& f : s.filters)
+            if (f.id == 2) shuffle_i16 = !f.cd.empty() && f.cd[0] == 2;
         auto found = [&](int64_t k, uint64_t addr, uint64_t nbytes, uint32_t mask) {
             if (k < 0 || k >= n_chunks) return;
             RawPiece& q = by_chunk[(size_t)k];
@@ -547,11 +557,28 @@ class Fast5 {
                 } else {
                     q.vbz_bytes = q.vbz_zstd ? 4 + vbz_frame_size(head, (size_t)h, size) : nbytes;
                 }
+            } else if (shuffle_gpu && shuffle_i16 && q.count == s.chunk_elems && applied[0] == 2 &&
+                       ((n_applied == 2 && applied[1] == 1) ||
+                        (n_applied == 3 && applied[1] == 1 && applied[2] == 3 && nbytes >= 4))) {
+                // shuffle + deflate of a chunk that is wanted WHOLE (of a partial one the wanted
+                // high bytes lie behind more low bytes than the read has room for: the host's);
+                // a checksum behind the stream stays unverified, as for plain deflate
+                q.kind = kZlib;
+                q.prefix = 4;
+                q.nbytes = n_applied == 3 ? nbytes - 4 : nbytes;
+            } else if (shuffle_gpu && shuffle_i16 && q.count == s.chunk_elems && applied[0] == 2 &&
+                       (n_applied == 1 || (n_applied == 2 && applied[1] == 3 && nbytes >= 4)) &&
+                       nbytes - (n_applied == 2 ? 4 : 0) == (uint64_t)q.count * 2) {
+                q.kind = kStored;                  // shuffle alone: the two planes as they are
+                q.prefix = 4;
+                q.nbytes = (uint64_t)q.count * 2;
             } else {
                 q.kind = kHostDecode;              // shuffle, or an order not seen in the field
             }
-            if (q.kind == kZlib && zlib_above > 0 && (int64_t)q.nbytes > zlib_above)
+            if (q.kind == kZlib && zlib_above > 0 && (int64_t)q.nbytes > zlib_above) {
                 q.kind = kHostDecode;
+                q.prefix = 0;
+            }
         };
         if (s.addr != kUndef) {
             if (s.index == 0) {
@@ -2436,6 +2463,25 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
     return F5_OK;
 }
 
+// a raw stream's weight in the order of the records: the bytes of its deflate data (a shuffled
+// deflate stream is one), 0 for everything else
+static int64_t deflate_weight(const f5_raw_stream& x) {
+    return x.mode == F5_RAW_ZLIB || x.mode == F5_RAW_ZLIB_SHUFFLE ? x.comp_bytes : 0;
+}
+static void put_u32le(uint8_t* dst, uint32_t v) {
+    for (int k = 0; k < 4; ++k) dst[k] = (uint8_t)(v >> (8 * k));
+}
+// HDF5's shuffle of 2-byte elements undone in place (as decode_chunk does it): low bytes, then high
+static void unshuffle_i16(std::vector<uint8_t>* bytes, std::vector<uint8_t>* scratch) {
+    const size_t n = bytes->size() / 2;
+    scratch->assign(bytes->begin(), bytes->end());
+    for (size_t k = 0; k < n; ++k) {
+        (*scratch)[2 * k] = (*bytes)[k];
+        (*scratch)[2 * k + 1] = (*bytes)[n + k];
+    }
+    bytes->swap(*scratch);
+}
+
 // One-read files with their Signals AS STORED (the one-read twin of f5_stream_open_raw's
 // batches): pass 1, per file on one worker thread, reads and parses the file and stages its
 // Signal pieces' bytes; then the host's share of the inflating is chosen over the whole batch;
@@ -2448,8 +2494,11 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
 
 int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_threads,
                          int64_t host_inflate_above, unsigned flags, f5_batch** out) {
-    if (!paths || !out || n_files < 0 || (flags & ~(unsigned)F5_RAW_FLAG_VBZ_ZSTD_GPU)) return F5_ERR_ARGUMENT;
+    if (!paths || !out || n_files < 0 ||
+        (flags & ~(unsigned)(F5_RAW_FLAG_VBZ_ZSTD_GPU | F5_RAW_FLAG_SHUFFLE_GPU)))
+        return F5_ERR_ARGUMENT;
     const bool vbz_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
+    const bool shuffle_gpu = (flags & F5_RAW_FLAG_SHUFFLE_GPU) != 0;
     *out = nullptr;
     f5_batch* batch = nullptr;
     try {
@@ -2481,7 +2530,7 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
                 }
                 const ReadEntry& r = file.read(0);
                 st.samples = r.signal.n;
-                file.signal_pieces(r.signal, zlib_above, &st.pieces, vbz_gpu);
+                file.signal_pieces(r.signal, zlib_above, &st.pieces, vbz_gpu, shuffle_gpu);
                 for (Fast5::RawPiece& p : st.pieces) {
                     const uint64_t wanted = (uint64_t)p.count * 2;
                     const size_t at = st.bytes.size();
@@ -2550,16 +2599,17 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
                 p.comp_offset = at;
                 p.comp_bytes = p.kind == Fast5::kHostDecode ? p.count * 2
                                : p.kind == Fast5::kVbz      ? (int64_t)p.vbz_bytes
-                                                            : (int64_t)p.nbytes;
+                                                            : p.prefix + (int64_t)p.nbytes;
                 at += p.comp_bytes;
                 f5_raw_stream rec;
                 rec.comp_offset = p.comp_offset;
                 rec.comp_bytes = p.comp_bytes;
                 rec.out_offset = (batch->offsets[(size_t)i] + p.first) * 2;
                 rec.out_bytes = p.count * 2;
-                rec.mode = p.kind == Fast5::kZlib  ? F5_RAW_ZLIB
+                rec.mode = p.kind == Fast5::kZlib  ? (p.prefix ? F5_RAW_ZLIB_SHUFFLE : F5_RAW_ZLIB)
                            : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
-                                                   : F5_RAW_STORED;
+                           : p.kind == Fast5::kStored && p.prefix ? F5_RAW_STORED_SHUFFLE
+                                                                  : F5_RAW_STORED;
                 rec.reserved = (int32_t)i;
                 batch->streams.push_back(rec);
             }
@@ -2588,11 +2638,17 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
                     continue;
                 }
                 if (p.kind != Fast5::kHostDecode) {
-                    std::memcpy(dst, src, (size_t)p.comp_bytes);
+                    if (p.prefix) put_u32le(dst, (uint32_t)(p.count * 2));
+                    std::memcpy(dst + p.prefix, src, (size_t)p.comp_bytes - (size_t)p.prefix);
                     continue;
                 }
                 const int rc = guarded([&] {
                     Fast5::inflate_stream(src, (size_t)p.nbytes, (size_t)p.count * 2 + 8, &tmp, &cache);
+                    if (p.prefix) {                    // a shuffled stream: its halves meet at count
+                        if (tmp.size() != (size_t)p.count * 2)
+                            throw FormatError("shuffled chunk of another size than its samples");
+                        unshuffle_i16(&tmp, &cache.scratch);
+                    }
                 });
                 const size_t have = rc == F5_OK ? std::min(tmp.size(), (size_t)p.count * 2) : 0;
                 if (have) std::memcpy(dst, tmp.data(), have);
@@ -2607,9 +2663,7 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
             }
         std::stable_sort(batch->streams.begin(), batch->streams.end(),
                          [](const f5_raw_stream& x, const f5_raw_stream& y) {
-                             const int64_t wx = x.mode == F5_RAW_ZLIB ? x.comp_bytes : 0;
-                             const int64_t wy = y.mode == F5_RAW_ZLIB ? y.comp_bytes : 0;
-                             return wx > wy;
+                             return deflate_weight(x) > deflate_weight(y);
                          });
     } catch (const std::exception&) {
         delete batch;
@@ -2910,6 +2964,7 @@ struct f5_stream {
     bool raw = false;                // hand out the Signal pieces as stored (f5_stream_open_raw)
     int64_t zlib_above = 0;          // ... except deflate streams longer than this: host-inflated
     bool vbz_zstd_gpu = false;       // F5_RAW_FLAG_VBZ_ZSTD_GPU: VBZ chunks go out as stored
+    bool shuffle_gpu = false;        // F5_RAW_FLAG_SHUFFLE_GPU: shuffled chunks go out as stored
     int host_share = 0;              // ... and the longest ones holding this share (%) of the bytes
     static constexpr int64_t kLongStreamBytes = 64 * 1024;
     std::mutex m;
@@ -3011,7 +3066,8 @@ struct f5_stream {
                 const ReadEntry& r = c->file->read(i);
                 const int64_t n = r.signal.n;
                 c->lengths[(size_t)i] = (!raw && keep > 0 && n > 2 * keep) ? 2 * keep : n;
-                if (raw) c->file->signal_pieces(r.signal, zlib_above, &c->pieces[(size_t)i], vbz_zstd_gpu);
+                if (raw) c->file->signal_pieces(r.signal, zlib_above, &c->pieces[(size_t)i], vbz_zstd_gpu,
+                                                    shuffle_gpu);
                 copy_read_id(r.read_id, &c->batch->read_ids[(size_t)i * F5_READ_ID_MAX]);
             });
     }
@@ -3064,8 +3120,10 @@ struct f5_stream {
                 for (int64_t i = 0; i < c->count; ++i)
                     if (c->batch->status[(size_t)i] == F5_OK)
                         for (Fast5::RawPiece& p : c->pieces[(size_t)i])
-                            if (p.kind == Fast5::kZlib && (int64_t)p.nbytes >= cut)
+                            if (p.kind == Fast5::kZlib && (int64_t)p.nbytes >= cut) {
                                 p.kind = Fast5::kHostDecode;
+                                p.prefix = 0;
+                            }
             }
             // raw: every piece gets its place in the byte buffer (what it occupies there: the
             // stored bytes, or - decoded by the host - its samples) and its record; the records
@@ -3081,8 +3139,8 @@ struct f5_stream {
                 for (Fast5::RawPiece& p : c->pieces[(size_t)i]) {
                     const int64_t wanted = p.count * 2;
                     p.comp_offset = at;
-                    p.comp_bytes = p.kind == Fast5::kZlib     ? (int64_t)p.nbytes
-                                   : p.kind == Fast5::kStored ? std::min<int64_t>((int64_t)p.nbytes, wanted)
+                    p.comp_bytes = p.kind == Fast5::kZlib     ? p.prefix + (int64_t)p.nbytes
+                                   : p.kind == Fast5::kStored ? p.prefix + std::min<int64_t>((int64_t)p.nbytes, wanted)
                                    : p.kind == Fast5::kZeros  ? 0
                                    : p.kind == Fast5::kVbz    ? (int64_t)p.vbz_bytes
                                                               : wanted;
@@ -3092,18 +3150,17 @@ struct f5_stream {
                     rec.comp_bytes = p.comp_bytes;
                     rec.out_offset = (c->batch->offsets[(size_t)i] + p.first) * 2;
                     rec.out_bytes = wanted;
-                    rec.mode = p.kind == Fast5::kZlib  ? F5_RAW_ZLIB
+                    rec.mode = p.kind == Fast5::kZlib  ? (p.prefix ? F5_RAW_ZLIB_SHUFFLE : F5_RAW_ZLIB)
                                : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
-                                                       : F5_RAW_STORED;
+                               : p.kind == Fast5::kStored && p.prefix ? F5_RAW_STORED_SHUFFLE
+                                                                      : F5_RAW_STORED;
                     rec.reserved = (int32_t)i;         // which read of the batch it belongs to
                     c->batch->streams.push_back(rec);
                 }
             }
             std::stable_sort(c->batch->streams.begin(), c->batch->streams.end(),
                              [](const f5_raw_stream& x, const f5_raw_stream& y) {
-                                 const int64_t wx = x.mode == F5_RAW_ZLIB ? x.comp_bytes : 0;
-                                 const int64_t wy = y.mode == F5_RAW_ZLIB ? y.comp_bytes : 0;
-                                 return wx > wy;
+                                 return deflate_weight(x) > deflate_weight(y);
                              });
             c->batch->comp_bytes = at;
             // the fetch pass walks the reads in FILE order (groups are listed by name - random
@@ -3157,8 +3214,12 @@ struct f5_stream {
             if (c->batch->status[(size_t)i] != F5_OK) continue;
             for (const Fast5::RawPiece& p : c->pieces[(size_t)i])
                 if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored ||
-                    (p.kind == Fast5::kVbz && !p.vbz_zstd))
-                    items.push_back({p.file_off, (uint64_t)p.comp_bytes, comp + p.comp_offset, i});
+                    (p.kind == Fast5::kVbz && !p.vbz_zstd)) {
+                    // (a shuffled piece: its size in front, the stored bytes behind it)
+                    if (p.prefix) put_u32le(comp + p.comp_offset, (uint32_t)(p.count * 2));
+                    items.push_back({p.file_off, (uint64_t)(p.comp_bytes - p.prefix),
+                                     comp + p.comp_offset + p.prefix, i});
+                }
         }
         const int rc_all = guarded([&] { c->file->read_many(items, &failed); });
         for (size_t k = 0; k < items.size(); ++k)
@@ -3318,7 +3379,7 @@ int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads,
 
 int f5_stream_open_raw_ex(const char* const* paths, int64_t n_paths, int n_threads, int depth,
                           int64_t host_inflate_above, unsigned flags, f5_stream** out) {
-    if (flags & ~(unsigned)F5_RAW_FLAG_VBZ_ZSTD_GPU) return F5_ERR_ARGUMENT;
+    if (flags & ~(unsigned)(F5_RAW_FLAG_VBZ_ZSTD_GPU | F5_RAW_FLAG_SHUFFLE_GPU)) return F5_ERR_ARGUMENT;
     f5_stream* s = nullptr;
     // A raw container is little work per read (no inflating) behind a serial start (one thread
     // opens and parses it: 5-6 ms of the ~30 ms of CPU a container of 4,000 reads costs): a window
@@ -3344,6 +3405,7 @@ int f5_stream_open_raw_ex(const char* const* paths, int64_t n_paths, int n_threa
             std::lock_guard<std::mutex> g(s->m);
             s->raw = true;
             s->vbz_zstd_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
+            s->shuffle_gpu = (flags & F5_RAW_FLAG_SHUFFLE_GPU) != 0;
             // (>= 0: a length in bytes; < 0: minus the host's share of the bytes in per cent)
             s->zlib_above = host_inflate_above > 0 ? host_inflate_above : 0;
             s->host_share = host_inflate_above < 0

@@ -267,12 +267,16 @@ def _unpack_raw_batch(lib, batch):
 
 
 RAW_FLAG_VBZ_ZSTD_GPU = 1
+RAW_FLAG_SHUFFLE_GPU = 2
 
 
-def _raw_flags(vbz_zstd):
+def _raw_flags(vbz_zstd, shuffle='host'):
     if vbz_zstd not in ('host', 'gpu'):
         raise ValueError("vbz_zstd must be 'host' or 'gpu', not {!r}".format(vbz_zstd))
-    return RAW_FLAG_VBZ_ZSTD_GPU if vbz_zstd == 'gpu' else 0
+    if shuffle not in ('host', 'gpu'):
+        raise ValueError("shuffle must be 'host' or 'gpu', not {!r}".format(shuffle))
+    return ((RAW_FLAG_VBZ_ZSTD_GPU if vbz_zstd == 'gpu' else 0) |
+            (RAW_FLAG_SHUFFLE_GPU if shuffle == 'gpu' else 0))
 
 
 def vbz_zstd_route():
@@ -283,19 +287,32 @@ def vbz_zstd_route():
     return route
 
 
-def load_batch_raw(fast5_files, threads=0, host_inflate_above=0, vbz_zstd='host'):
+def shuffle_route():
+    """DEEPBINNER_SHUFFLE: 'gpu' hands whole chunks of HDF5's shuffle filter (int16), deflated or
+    not, to the GPU as stored (RAW_ZLIB_SHUFFLE, RAW_STORED_SHUFFLE); unset or 'host': the loader's
+    threads inflate and unshuffle them (RAW_STORED)."""
+    route = os.environ.get('DEEPBINNER_SHUFFLE') or 'host'
+    _raw_flags('host', route)
+    return route
+
+
+def load_batch_raw(fast5_files, threads=0, host_inflate_above=0, vbz_zstd='host', shuffle='host'):
     """One-read files with their Signals AS STORED -> (read_ids, offsets, status, comp, records),
     laid out like a batch of ``stream_raw`` (read i = file i), for
     ``hip_backend.classify_pair_deflated``.  ``host_inflate_above`` as there: > 0 bytes, or minus
     the per cent of the batch's compressed bytes (its longest streams) the host's threads inflate
     themselves.  ``vbz_zstd``: 'host' - the loader's threads undo the zstd stage of VBZ chunks
-    (RAW_VBZ) - or 'gpu' - they go out as stored (RAW_VBZ_ZSTD) and libzstd is not called."""
+    (RAW_VBZ) - or 'gpu' - they go out as stored (RAW_VBZ_ZSTD) and libzstd is not called.
+    ``shuffle``: 'host' - the loader's threads decode every chunk that went through HDF5's shuffle
+    filter (RAW_STORED) - or 'gpu' - whole chunks of shuffle (+ deflate) (+ fletcher32) of int16 go
+    out as stored behind a 4-byte size (RAW_ZLIB_SHUFFLE, RAW_STORED_SHUFFLE); a read's partial last
+    chunk stays the host's."""
     lib = load_library()
     n = len(fast5_files)
     paths = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in fast5_files])
     handle = ctypes.c_void_p()
     status = lib.f5_load_batch_raw_ex(paths, n, int(threads), int(host_inflate_above),
-                                      _raw_flags(vbz_zstd), ctypes.byref(handle))
+                                      _raw_flags(vbz_zstd, shuffle), ctypes.byref(handle))
     if status != F5_OK:
         raise Fast5NativeError(status_string(status))
     return _unpack_raw_batch(lib, handle)
@@ -360,6 +377,7 @@ def stream_reads(fast5_files, keep=None, threads=0, depth=0):
 
 
 RAW_ZLIB, RAW_STORED, RAW_VBZ, RAW_VBZ_ZSTD = 0, 1, 2, 3
+RAW_ZLIB_SHUFFLE, RAW_STORED_SHUFFLE = 4, 5
 # f5_raw_stream (include/deepbinner_fast5.h) = dbh_inflate_stream (include/deepbinner_hip.h)
 RAW_STREAM = np.dtype([('comp_offset', '<i8'), ('comp_bytes', '<i8'), ('out_offset', '<i8'),
                        ('out_bytes', '<i8'), ('mode', '<i4'), ('read', '<i4')])
@@ -383,20 +401,21 @@ def vbz_decode(chunk, cd, max_samples):
     return out[:n.value].copy()
 
 
-def stream_raw(fast5_files, threads=0, depth=0, host_inflate_above=0, vbz_zstd='host'):
+def stream_raw(fast5_files, threads=0, depth=0, host_inflate_above=0, vbz_zstd='host',
+               shuffle='host'):
     """Multi-read containers as a stream of RAW batches (``f5_stream_open_raw``): the Signal of
     every read as it is stored - zlib streams, mostly - for a decoder elsewhere (the GPU:
     ``hip_backend.classify_pair_deflated``).  Yields, in the order of ``fast5_files``,
     ``(index, read_ids, offsets, status, comp, streams)``: ``offsets`` (samples) say where each
     read's signal lies once decoded, ``comp`` is the byte buffer (uint8, zero-copy: it keeps the
     native batch alive), ``streams`` an array of RAW_STREAM records - or ``(index, None, None,
-    container_status, None, None)`` for a file that could not be opened.  ``vbz_zstd`` as for
-    ``load_batch_raw``."""
+    container_status, None, None)`` for a file that could not be opened.  ``vbz_zstd`` and
+    ``shuffle`` as for ``load_batch_raw``."""
     lib = load_library()
     n = len(fast5_files)
     paths = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in fast5_files])
     stream = ctypes.c_void_p()
-    flags = _raw_flags(vbz_zstd)
+    flags = _raw_flags(vbz_zstd, shuffle)
     status = lib.f5_stream_open_raw_ex(paths, n, int(threads), int(depth), int(host_inflate_above),
                                        flags, ctypes.byref(stream))
     if status != F5_OK:

@@ -288,6 +288,10 @@ def classify_pair(start_model, end_model, samples, offsets, scan_size, score_dif
 
 
 INFLATE_ZLIB, INFLATE_STORED, INFLATE_VBZ = 0, 1, 2
+# HDF5's shuffle filter (int16) undone on the GPU: u32 LE N, then a zlib stream of the N shuffled
+# bytes / the N shuffled bytes themselves; the status of a stream these modes refuse
+INFLATE_ZLIB_SHUFFLE, INFLATE_STORED_SHUFFLE = 4, 5
+INFLATE_SHUFFLE_REFUSED = 32
 # dbh_inflate_stream (include/deepbinner_hip.h)
 INFLATE_STREAM = np.dtype([('comp_offset', '<i8'), ('comp_bytes', '<i8'), ('out_offset', '<i8'),
                            ('out_bytes', '<i8'), ('mode', '<i4'), ('reserved', '<i4')])

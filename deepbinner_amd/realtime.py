@@ -65,7 +65,7 @@ def inflate_cus_for(comp_bytes, modes):
         return None
     total = count = 0
     for size, mode in zip(comp_bytes, modes):
-        if mode == 0:                   # fast5_native.RAW_ZLIB
+        if mode in (0, 4):              # fast5_native.RAW_ZLIB, RAW_ZLIB_SHUFFLE
             total += int(size)
             count += 1
     return LONG_STREAM_CUS if count and total / count > LONG_STREAM_BYTES else INFLATE_CUS
@@ -78,6 +78,9 @@ def host_inflate_share(n_gpus):
     DEEPBINNER_HOST_INFLATE_SHARE=<per cent> any split.
     DEEPBINNER_VBZ_ZSTD=gpu leaves the zstd stage of VBZ chunks to the GPU as well (default
     'host': the loader's threads undo it).
+    DEEPBINNER_SHUFFLE=gpu leaves HDF5's shuffle filter to the GPU: whole chunks of shuffle
+    (+ deflate) go out as stored (default 'host': the loader's threads decode them; DESIGN.md
+    section 16).
 
     Left alone: all or nothing.  Measured with round 6's kernels (profiles/r06_loader/
     long_reads_cu_sweep.txt and host_share_ordinary.txt; 27 k-sample reads, gzip 1, 16 loader

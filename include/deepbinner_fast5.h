@@ -130,6 +130,23 @@ void f5_stream_close(f5_stream* stream);
  * F5_RAW_VBZ, chunks with a filter mask or other filters stay what they are. */
 #define F5_RAW_VBZ_ZSTD 3
 #define F5_RAW_FLAG_VBZ_ZSTD_GPU 1u
+/* F5_RAW_ZLIB_SHUFFLE, F5_RAW_STORED_SHUFFLE (only under F5_RAW_FLAG_SHUFFLE_GPU): a chunk of HDF5's
+ * shuffle filter with 2-byte elements (cd[0] == 2), AS STORED, for DBH_INFLATE_ZLIB_SHUFFLE /
+ * DBH_INFLATE_STORED_SHUFFLE of deepbinner_hip.h: u32 LE N = 2 * chunk_elems in front (the loader
+ * puts it there), then the stored bytes.  By the filters applied to the chunk, in their order:
+ *   shuffle, deflate               F5_RAW_ZLIB_SHUFFLE    the stored bytes
+ *   shuffle, deflate, fletcher32   F5_RAW_ZLIB_SHUFFLE    the stored bytes less 4 (the checksum
+ *                                  behind the stream stays unverified, as for plain deflate)
+ *   shuffle                        F5_RAW_STORED_SHUFFLE  the stored bytes
+ *   shuffle, fletcher32            F5_RAW_STORED_SHUFFLE  the stored bytes less 4
+ * - for a chunk that is wanted WHOLE.  A partial last chunk, or a chunk longer than the data, stays
+ * the host's (F5_RAW_STORED: libhdf5 stores the whole chunk, and the wanted high bytes lie behind
+ * more low bytes than the read's output has room for): at most one chunk per read.  Other element
+ * sizes and other orders stay what they are.  host_inflate_above treats an F5_RAW_ZLIB_SHUFFLE piece
+ * as the deflate stream it is.  Without the flag every shuffled chunk is decoded by the host. */
+#define F5_RAW_ZLIB_SHUFFLE 4
+#define F5_RAW_STORED_SHUFFLE 5
+#define F5_RAW_FLAG_SHUFFLE_GPU 2u
 typedef struct f5_raw_stream {
     int64_t comp_offset, comp_bytes;
     int64_t out_offset, out_bytes;
@@ -141,7 +158,8 @@ int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads,
 int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
                       int64_t host_inflate_above, f5_batch** out);
 /* The two calls above plus flags (F5_RAW_FLAG_VBZ_ZSTD_GPU: VBZ chunks with a zstd stage go out
- * as stored, F5_RAW_VBZ_ZSTD); flags 0 is the calls above. */
+ * as stored, F5_RAW_VBZ_ZSTD; F5_RAW_FLAG_SHUFFLE_GPU: shuffled chunks go out as stored,
+ * F5_RAW_ZLIB_SHUFFLE / F5_RAW_STORED_SHUFFLE); flags 0 is the calls above. */
 int f5_stream_open_raw_ex(const char* const* paths, int64_t n_paths, int n_threads, int depth,
                           int64_t host_inflate_above, unsigned flags, f5_stream** out);
 int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_threads,

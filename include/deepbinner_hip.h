@@ -251,6 +251,25 @@ int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_cal
  * content does not fit the slots is refused: none is whose out_bytes covers its original_size.
  * Refused by either stage: status != 0 (16..28: the zstd stage's reason), output zeros. */
 #define DBH_INFLATE_VBZ_ZSTD 3
+/* HDF5's shuffle filter (filter 2) for int16: the N bytes of a chunk stored as its N/2 low bytes,
+ * then its N/2 high bytes - byte j of element i at j * (N/2) + i.  Both modes carry a 4-byte prefix
+ * in front of the chunk's bytes, as VBZ does: u32 LE N, the size of the shuffled content.
+ * DBH_INFLATE_ZLIB_SHUFFLE: the prefix, then a zlib stream whose content is the N shuffled bytes
+ * (the pipeline shuffle + deflate).  The inflate kernels decode it as the DBH_INFLATE_ZLIB stream
+ * of comp_bytes - 4 bytes at comp_offset + 4, wanted N, into the stream's own output region; a
+ * wave of the kernel behind them (dbh_vbz.hip) copies the N bytes to the stream's slots of the
+ * workspace and writes them back de-interleaved: N/2 samples, zeros from N to out_bytes.  Accepted
+ * when N is even, 0 <= N <= out_bytes, and the deflate data ENDED with exactly N bytes (the
+ * Adler-32 is then checked as for any stream that ends): a stream that holds more or fewer bytes
+ * cannot be unshuffled - where its halves meet is unknown.
+ * DBH_INFLATE_STORED_SHUFFLE: the prefix, then the N shuffled bytes themselves (comp_bytes == 4 + N,
+ * N even).  Sample i is (c[i], c[N/2 + i]) for 2 i < min(N, out_bytes), zeros behind: any
+ * out_bytes is taken.
+ * Refused: status DBH_INFLATE_SHUFFLE_REFUSED, output zeros - unless the zlib stage has set a
+ * status of its own (1..10), which stays. */
+#define DBH_INFLATE_ZLIB_SHUFFLE 4
+#define DBH_INFLATE_STORED_SHUFFLE 5
+#define DBH_INFLATE_SHUFFLE_REFUSED 32
 /* the GPU's zstd decoder run on the host: same core, lanes as a loop (tests, tools).  frame must
  * be readable for 64 bytes beyond frame_bytes.  Returns 0 unless an argument is null; *status: 0,
  * or why the frame is refused (16..28, dbh_zstd_core.h), *produced: the content size, 0 if refused. */
