@@ -269,8 +269,6 @@ struct dbh_model {
     int cus = 256;               // workgroups of a persistent forward launch (one per CU)
     int cus_total = 256;         // ... before dbh_model_reserve_cus took some away
     bool windows_by_counter = true;        // DEEPBINNER_STATIC_WINDOWS=1: fixed shares (A/B)
-    int inflate_streams_per_lane = 0;      // dbh_classify_pair_deflated -> dbh_inflate_dev; 0 = by
-                                           // the lengths of the streams
     bool launch_per_batch = false;   // DEEPBINNER_LAUNCH_PER_BATCH=1: one launch per batch (A/B)
     // The end of a persistent launch: with fewer than chunk4_rounds x grid windows not yet handed
     // out a workgroup asks for groups of 2 instead of 4, below chunk2_rounds x grid for single
@@ -1460,26 +1458,8 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
         if (e != hipSuccess) return done(hip_fail(e, "hipMemsetAsync"));
     }
     if (n_streams > 0) {
-        // How wide kernel 1 is launched: it lasts as long as its longest stream whatever the
-        // width, so the lanes may as well take as many streams one after the other as fit into
-        // that time - this call is one of several in flight, and what it leaves free the others
-        // use.  (A lane takes a new stream only at a block boundary, ~1.35 blocks to a mean
-        // read: hence the margin.)
-        int per_lane = m->inflate_streams_per_lane;
-        if (per_lane <= 0) {
-            int64_t sum = 0, count = 0;
-            for (int64_t i = 0; i < n_streams; ++i)
-                if (streams_host[i].mode == DBH_INFLATE_ZLIB ||
-                    streams_host[i].mode == DBH_INFLATE_ZLIB_SHUFFLE) {
-                    sum += streams_host[i].comp_bytes;
-                    ++count;
-                }
-            const int64_t longest = count ? streams_host[order[0]].comp_bytes : 0;
-            per_lane = sum > 0 ? (int)(longest * count * 2 / (sum * 3)) : 1;
-            per_lane = per_lane < 1 ? 1 : per_lane > 8 ? 8 : per_lane;
-        }
         st = dbh_inflate_dev((const uint8_t*)d.d_comp, (int64_t)comp_bytes, d_records, n_streams,
-                             out_bytes, (uint8_t*)d.d_samples, d.d_tokens, d_status, per_lane,
+                             out_bytes, (uint8_t*)d.d_samples, d.d_tokens, d_status, 0,
                              (dbh_stream)d.stream);
         if (st != DBH_OK) return done(st);
     }

@@ -11,32 +11,19 @@
 // Two kernels (RFC 1950 / 1951; bit-exact with zlib, same accept / reject decisions; the decoder
 // core is dbh_inflate_core.h + dbh_inflate_wave.h, which the CPU test harness compiles too):
 //   1. Huffman codes -> tokens (literal | match {length, distance}): no output bytes, no window -
-//      nothing here depends on memory the kernel wrote itself.  Two forms, same tokens:
-//      inflate_tokens_wave_kernel (what runs) - ONE WAVEFRONT PER STREAM: the 64 lanes decode 64
-//      consecutive pieces of the same Huffman block at once, each from a guessed first bit, and
-//      re-decode until every piece begins where the one before it ended (prefix codes
-//      re-synchronise: ~2.7 rounds; dbh_inflate_wave.h); 4,000 streams are 4,000 waves, a dozen
-//      per CU, and a launch lasts 2.4 ms instead of 12.9 (84 -> 14 ms both kernels when the
-//      reads' lengths are log-normal: a long read is no longer one lane's work);
-//      inflate_tokens_kernel (DEEPBINNER_INFLATE_KERNEL=lane) - ONE LANE PER STREAM, 64 streams
-//      per wavefront: rounds 3 and 4's kernel, the same work in 30 % less CU time but 63 waves
-//      for as long as the longest stream lasts.  All lanes of a wave step together; streams
-//      deflated with the same settings reach their block boundaries (every 16,383 symbols with
-//      zlib's defaults) on the same step, so the code builds line up; a lane that is done takes
-//      its next stream off a counter there.
+//      nothing here depends on memory the kernel wrote itself.  inflate_tokens_wave_kernel - ONE
+//      WAVEFRONT PER STREAM: the 64 lanes decode 64 consecutive pieces of the same Huffman block
+//      at once, each from a guessed first bit, and re-decode until every piece begins where the
+//      one before it ended (prefix codes re-synchronise: ~2.7 rounds; dbh_inflate_wave.h); 4,000
+//      streams are 4,000 waves, a dozen per CU.  (The one-lane-per-stream kernel of rounds 3 and 4
+//      is retired; what it measured is in HISTORY.md.)
 //   2. tokens -> bytes, ONE WAVE PER STREAM, up to 64 tokens per step: a wave-wide prefix sum of
-//      the token lengths gives every token its output position.  Two forms, same bytes:
-//      inflate_resolve_pre_kernel (what runs; described in front of it) - an 8 KiB ring in LDS
-//      and the stream's own flushed output behind it, twenty streams per CU; the short matches
-//      whose source is complete before their step (four fifths of all) read it at the step
-//      boundary and are stored with the literals, the others go in rounds by the exact rule:
-//      0.84 ms per 4,000 x 54 KB streams;
-//      inflate_resolve_kernel (DEEPBINNER_INFLATE_RESOLVE=rounds; rounds 3-5) - the whole 32 KiB
-//      window as a ring in LDS, five streams per CU; literals are stored at once, every match
-//      copies from the ring as soon as everything it reads has been written (the lanes go in
-//      rounds, the first waiting match deciding who may go; a step in which a far-reaching match
-//      could be overtaken by a write that wraps around the ring goes in token order instead:
-//      dbh_inflate_core.h, ring_hazard): 3.04 ms.
+//      the token lengths gives every token its output position.  inflate_resolve_pre_kernel
+//      (described in front of it) - an 8 KiB ring in LDS and the stream's own flushed output
+//      behind it, twenty streams per CU; the short matches whose source is complete before their
+//      step (four fifths of all) read it at the step boundary and are stored with the literals,
+//      the others go in rounds by the exact rule: 0.84 ms per 4,000 x 54 KB streams.  (The
+//      32 KiB-ring kernel of rounds 3-5 is retired: HISTORY.md.)
 //      The ring is written out in coalesced 256-byte pieces, with the Adler-32 sums on the way.
 // A stream of mode DBH_INFLATE_ZLIB_SHUFFLE (shuffle + deflate) is a zlib stream behind a 4-byte
 // prefix to every kernel here (zlib_view); its bytes are de-interleaved behind them (dbh_vbz.hip).
@@ -65,88 +52,6 @@ namespace dbh_inflate_detail {
 
 using dbi::Lane;
 
-// streams per workgroup of kernel 1 = the active lanes of its one wavefront.  A token costs a wave
-// the same time whether 64 or 16 of its lanes decode; fewer lanes per wave buy LDS per lane - room
-// for the first-level decode tables of dbh_inflate_core.h (-DDBI_LANES=16 -DDBI_LIT_BITS=11: an
-// experiment of round 5, 15 % faster on four times the waves; what ships is 64 lanes, no tables).
-#ifndef DBI_LANES
-#define DBI_LANES 64
-#endif
-constexpr int kLanes = DBI_LANES;
-static_assert(kLanes == 16 || kLanes == 32 || kLanes == 64, "");
-// LDS of kernel 1, every array interleaved by lane ([entry][lane]): consecutive lanes hit
-// consecutive addresses whatever entry each of them wants.
-constexpr int kRingOff = 0;                                              // u32 [34][lanes]
-constexpr int kLitPairOff = kRingOff + dbi::kRingStore * kLanes * 4;     // u32 [16][lanes]
-constexpr int kDistPairOff = kLitPairOff + 16 * kLanes * 4;              // u32 [16][lanes]
-constexpr int kLitSymOff = kDistPairOff + 16 * kLanes * 4;               // u16 [288][lanes]
-constexpr int kCntOff = kLitSymOff + dbi::kLitSyms * kLanes * 2;         // u16 [16][lanes]
-constexpr int kLitTabOff = kCntOff + 16 * kLanes * 2;                    // u16 [2^kLitBits][lanes]
-constexpr int kDistTabOff = kLitTabOff + (dbi::kTables ? (1 << dbi::kLitBits) * kLanes * 2 : 0);
-constexpr int kDistSymOff = kDistTabOff + (dbi::kTables ? (1 << dbi::kDistBits) * kLanes * 2 : 0);  // u8 [32][lanes]
-constexpr int kLensOff = kDistSymOff + dbi::kDistSyms * kLanes;          // u8 [320][lanes]
-constexpr int kLdsBytes1 = kLensOff + dbi::kMaxLens * kLanes;
-static_assert(kLdsBytes1 <= 160 * 1024, "kernel 1's LDS no longer fits a CU");
-
-struct LdsMem {
-    static constexpr int kClTableBits = 0;             // (no table for the code-length code: 64 per wave)
-    __device__ __forceinline__ uint32_t cl_tab(int) const { return 0u; }
-    __device__ __forceinline__ void set_cl_tab(int, uint32_t) {}
-    uint32_t* ring_;
-    uint32_t* lit_pair_;
-    uint32_t* dist_pair_;
-    uint16_t* lit_sym_;
-    uint16_t* cnt_;
-    uint16_t* lit_tab_;
-    uint16_t* dist_tab_;
-    uint8_t* dist_sym_;
-    uint8_t* lens_;
-    // asynchronous reads for the decode front (dbh_inflate_core.h: issue_*): requested here, waited
-    // for by the caller's lds_landed<>()
-    static __device__ __forceinline__ unsigned addr_of(const void* p) {
-        return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-    }
-    __device__ __forceinline__ void ring3_issue(int r, uint32_t& a, uint32_t& b, uint32_t& c) const {
-        uint64_t ab;
-        asm volatile("ds_read2_b32 %0, %2 offset1:%3\n\tds_read_b32 %1, %2 offset:%4"
-                     : "=&v"(ab), "=&v"(c)
-                     : "v"(addr_of(ring_ + r * kLanes)), "n"(kLanes), "n"(kLanes * 8)
-                     : "memory");
-        a = (uint32_t)ab;
-        b = (uint32_t)(ab >> 32);
-    }
-    __device__ __forceinline__ void lit_pair_issue(int l, uint32_t& v) const {
-        asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr_of(lit_pair_ + l * kLanes)) : "memory");
-    }
-    __device__ __forceinline__ void dist_pair_issue(int l, uint32_t& v) const {
-        asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr_of(dist_pair_ + l * kLanes)) : "memory");
-    }
-    __device__ __forceinline__ void lit_sym_issue(int i, uint32_t& v) const {
-        asm volatile("ds_read_u16 %0, %1" : "=v"(v) : "v"(addr_of(lit_sym_ + i * kLanes)) : "memory");
-    }
-    __device__ __forceinline__ void dist_sym_issue(int i, uint32_t& v) const {
-        asm volatile("ds_read_u8 %0, %1" : "=v"(v) : "v"(addr_of(dist_sym_ + i * kLanes)) : "memory");
-    }
-    __device__ __forceinline__ uint32_t lit_tab(int i) const { return lit_tab_[i * kLanes]; }
-    __device__ __forceinline__ void set_lit_tab(int i, uint32_t v) { lit_tab_[i * kLanes] = (uint16_t)v; }
-    __device__ __forceinline__ uint32_t dist_tab(int i) const { return dist_tab_[i * kLanes]; }
-    __device__ __forceinline__ void set_dist_tab(int i, uint32_t v) { dist_tab_[i * kLanes] = (uint16_t)v; }
-    __device__ __forceinline__ uint32_t ring(int r) const { return ring_[r * kLanes]; }
-    __device__ __forceinline__ void set_ring(int r, uint32_t v) { ring_[r * kLanes] = v; }
-    __device__ __forceinline__ int len(int i) const { return lens_[i * kLanes]; }
-    __device__ __forceinline__ void set_len(int i, int v) { lens_[i * kLanes] = (uint8_t)v; }
-    __device__ __forceinline__ int cnt(int l) const { return cnt_[l * kLanes]; }
-    __device__ __forceinline__ void set_cnt(int l, int v) { cnt_[l * kLanes] = (uint16_t)v; }
-    __device__ __forceinline__ uint32_t lit_pair(int l) const { return lit_pair_[l * kLanes]; }
-    __device__ __forceinline__ void set_lit_pair(int l, uint32_t v) { lit_pair_[l * kLanes] = v; }
-    __device__ __forceinline__ uint32_t dist_pair(int l) const { return dist_pair_[l * kLanes]; }
-    __device__ __forceinline__ void set_dist_pair(int l, uint32_t v) { dist_pair_[l * kLanes] = v; }
-    __device__ __forceinline__ uint32_t lit_sym(int i) const { return lit_sym_[i * kLanes]; }
-    __device__ __forceinline__ void set_lit_sym(int i, uint32_t v) { lit_sym_[i * kLanes] = (uint16_t)v; }
-    __device__ __forceinline__ uint32_t dist_sym(int i) const { return dist_sym_[i * kLanes]; }
-    __device__ __forceinline__ void set_dist_sym(int i, uint32_t v) { dist_sym_[i * kLanes] = (uint8_t)v; }
-};
-
 // what kernel 1 leaves for kernel 2 (and for the caller) per stream
 struct StreamInfo {
     int32_t status;
@@ -156,7 +61,7 @@ struct StreamInfo {
     int64_t produced;
 };
 
-// What the inflate kernels make of a record - all four forms of them, through this one helper.
+// What the inflate kernels make of a record - both forms of them, through this one helper.
 // A stream of mode DBH_INFLATE_ZLIB_SHUFFLE (u32 LE N, then a zlib stream whose content is N
 // shuffled bytes) is to them the DBH_INFLATE_ZLIB stream behind its prefix, wanted N: its bytes go
 // to the stream's output region, where dbh_vbz.hip's kernel finds and de-interleaves them.  With a
@@ -185,182 +90,8 @@ __device__ __forceinline__ bool passed_by(int mode) {
     return mode == DBH_INFLATE_VBZ || mode == DBH_INFLATE_VBZ_ZSTD || mode == DBH_INFLATE_STORED_SHUFFLE;
 }
 
-// STREAMS PER LANE (round 5; DBI_PER_LANE, default 1).  A token is one dependent chain of ~190
-// vector instructions with five dependent LDS reads in it, and a container's 4,000 streams are 63
-// waves for the GPU's 1,024 SIMDs: a wave decodes alone, nothing fills its latencies.  The obvious
-// answer - every lane carries TWO independent streams, each with its own decoder state and its
-// own 1.2 KB of LDS, the two "fronts" of a round (look at the next token: dbh_inflate_core.h) side
-// by side - was built three ways and measured (profiles/r05_inflate/README.md; 4,000 streams of
-// 54 KB, both kernels): one slot 15.7 ms; two slots, front after front 28.3 ms; as one software
-// pipeline with hand-counted LDS waits (each request in flight behind the other slot's
-// arithmetic) 27.7 ms; in lockstep, the two chains alternating instruction by instruction
-// 28.5 ms.  Twice the tokens per wave cost twice the time whatever the arrangement: a wave alone
-// on its SIMD is bound by instruction ISSUE (~6.3 cycles per instruction, dependent or not), not
-// by the latencies between its instructions.  What is left is the number of instructions per
-// token, i.e. decode tables instead of the canonical compare chains (a third of all
-// instructions) - 2 to 4 KB per lane, half or a quarter of the lanes per wave.  The kernel keeps
-// the general form (the slots of a lane are a compile-time array) with one slot.
-#ifndef DBI_PER_LANE
-#define DBI_PER_LANE 1
-#endif
-#ifndef DBI_DEFAULT_WAVE
-#define DBI_DEFAULT_WAVE 1
-#endif
-constexpr int kPerLane = DBI_PER_LANE;
-static_assert(kPerLane * kLdsBytes1 <= 160 * 1024 && (kPerLane == 1 || kPerLane == 2),
-              "kernel 1's LDS no longer fits a CU");
-
-__global__ __launch_bounds__(kLanes) void inflate_tokens_kernel(
-    const uint8_t* __restrict__ comp, int64_t comp_total,
-    const dbh_inflate_stream* __restrict__ streams, int n_streams, uint32_t* __restrict__ tokens,
-    StreamInfo* __restrict__ info, int* __restrict__ next_stream) {
-    __shared__ __attribute__((aligned(16))) uint8_t lds_all[kPerLane * kLdsBytes1];
-    const int lane = threadIdx.x;
-    LdsMem mem[kPerLane];
-    Lane L[kPerLane];
-    uint32_t* tok[kPerLane];
-    int n_tok[kPerLane], cur[kPerLane];
-#pragma unroll
-    for (int s = 0; s < kPerLane; ++s) {
-        uint8_t* lds = lds_all + s * kLdsBytes1;
-        mem[s].ring_ = reinterpret_cast<uint32_t*>(lds + kRingOff) + lane;
-        mem[s].lit_pair_ = reinterpret_cast<uint32_t*>(lds + kLitPairOff) + lane;
-        mem[s].dist_pair_ = reinterpret_cast<uint32_t*>(lds + kDistPairOff) + lane;
-        mem[s].lit_sym_ = reinterpret_cast<uint16_t*>(lds + kLitSymOff) + lane;
-        mem[s].cnt_ = reinterpret_cast<uint16_t*>(lds + kCntOff) + lane;
-        mem[s].lit_tab_ = reinterpret_cast<uint16_t*>(lds + kLitTabOff) + lane;
-        mem[s].dist_tab_ = reinterpret_cast<uint16_t*>(lds + kDistTabOff) + lane;
-        mem[s].dist_sym_ = lds + kDistSymOff + lane;
-        mem[s].lens_ = lds + kLensOff + lane;
-        L[s].state = dbi::kDone;
-        L[s].status = dbi::kOk;
-        L[s].ended = 0;
-        L[s].adler = 0;
-        L[s].out_pos = 0;
-        L[s].out_cap = 0;
-        L[s].final_block = 0;
-        L[s].stored_left = 0;
-#pragma unroll
-        for (int l = 0; l < 15; ++l) L[s].lim_lit[l] = L[s].lim_dist[l] = 0;
-        L[s].br.in = comp;
-        L[s].br.limit_bits = 0;
-        L[s].br.bp = L[s].br.wr = 0;
-        L[s].br.pending = 0;
-        L[s].br.fetch_cap = 0;
-        tok[s] = tokens;
-        n_tok[s] = 0;
-        cur[s] = -1;              // the stream this slot of the lane is decoding
-    }
-    bool more = true;             // streams may be left to fetch
-    for (;;) {
-        // A slot that has finished its stream takes the next one off the counter - HERE, where
-        // no lane is inside a block: zlib ends a block after a fixed number of symbols, so
-        // streams that start together reach their block headers together (and the hot loop
-        // below ends when the last lane has left its block); a stream taken up in between
-        // would make every lane of the wave wait for its headers, each time, alone.
-#pragma unroll
-        for (int s = 0; s < kPerLane; ++s) {
-            while (L[s].state == dbi::kDone && more) {
-                if (cur[s] >= 0) {
-                    StreamInfo r;
-                    r.status = L[s].status;
-                    r.ended = L[s].ended;
-                    r.adler = L[s].adler;
-                    r.n_tokens = n_tok[s];
-                    r.produced = L[s].out_pos;
-                    info[cur[s]] = r;
-                }
-                cur[s] = atomicAdd(next_stream, 1);
-                if (cur[s] >= n_streams) {
-                    cur[s] = -1;
-                    more = false;
-                    break;
-                }
-                const dbh_inflate_stream st = zlib_view(streams[cur[s]], comp, comp_total);
-                n_tok[s] = 0;
-                if (st.mode == DBH_INFLATE_ZLIB) {
-                    // (the caller's buffer is readable for 64 bytes beyond comp_total)
-                    dbi::lane_start(L[s], mem[s], comp + st.comp_offset, st.comp_bytes, st.out_bytes,
-                                    comp_total + 64 - st.comp_offset);
-                    tok[s] = tokens + st.out_offset;          // one token slot per byte of output
-                } else {
-                    L[s].status = dbi::kOk;                  // nothing to decode: kernel 2 copies it
-                    L[s].ended = 0;
-                    L[s].adler = 0;
-                    L[s].out_pos = 0;
-                }
-            }
-            // (a slot left with a finished stream when the counter ran out: its record)
-            if (L[s].state == dbi::kDone && !more && cur[s] >= 0) {
-                StreamInfo r;
-                r.status = L[s].status;
-                r.ended = L[s].ended;
-                r.adler = L[s].adler;
-                r.n_tokens = n_tok[s];
-                r.produced = L[s].out_pos;
-                info[cur[s]] = r;
-                cur[s] = -1;
-            }
-        }
-        if (!__any(L[0].state != dbi::kDone || L[kPerLane - 1].state != dbi::kDone)) break;
-        // the rare states: a block header (with its two code builds), a stored block's bytes
-#pragma unroll
-        for (int s = 0; s < kPerLane; ++s) {
-            if (L[s].state == dbi::kNeedBlock) {
-                dbi::lane_block(L[s], mem[s]);
-            } else if (L[s].state == dbi::kStored) {
-                uint32_t token;
-                if (dbi::lane_stored(L[s], mem[s], &token)) tok[s][n_tok[s]++] = token;
-            }
-        }
-        // the hot loop: every slot that is inside a Huffman block decodes four tokens per round
-        // (slots that have left their block wait for the others)
-        while (__any(L[0].state == dbi::kDecode || L[kPerLane - 1].state == dbi::kDecode)) {
-            uint32_t t[kPerLane][4];
-            bool p[kPerLane][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                dbi::Decoded dec[kPerLane];
-                if constexpr (kPerLane == 1 && dbi::kTables) {
-                    // through the first-level tables; a code longer than their index (no entry)
-                    // sends the whole wave the canonical way for this token
-                    const bool fast = dbi::lane_decode_fast(L[0], mem[0], dec[0]);
-#ifndef DBI_ABL_NO_FALLBACK
-                    if (__any(!fast && L[0].state == dbi::kDecode))
-#else
-                    if (false)
-#endif
-                        dec[0] = dbi::lane_decode_front(L[0], mem[0]);
-                } else {
-                    dbi::lane_decode_fronts<kPerLane, LdsMem>(L, mem, dec);
-                }
-#pragma unroll
-                for (int s = 0; s < kPerLane; ++s) {
-                    t[s][k] = 0;
-                    p[s][k] = dbi::lane_decode_commit(L[s], dec[s], &t[s][k]);
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < kPerLane; ++s) {
-                // (a store per token and lane would be 64 partial cache lines per step: four
-                // tokens go out as one 16-byte store - all four real in all but a handful of rounds)
-                if (p[s][0] && p[s][1] && p[s][2] && p[s][3]) {
-                    const uint32_t four[4] = {t[s][0], t[s][1], t[s][2], t[s][3]};
-                    __builtin_memcpy(tok[s] + n_tok[s], four, 16);
-                    n_tok[s] += 4;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (p[s][k]) tok[s][n_tok[s]++] = t[s][k];
-                }
-                L[s].br.checkpoint(mem[s]);
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
-// Kernel 1, second form: ONE WAVE PER STREAM (dbh_inflate_wave.h - the rounds, why they end, what
+// Kernel 1: ONE WAVE PER STREAM (dbh_inflate_wave.h - the rounds, why they end, what
 // they cost).  One wavefront per workgroup, one stream per workgroup, in the caller's order (the
 // longest first, if the caller has sorted them).  LDS: the staged chunk (4.4 KB) and ONE set of
 // canonical code tables (1.3 KB) - a dozen and more waves per CU, which is what hides the LDS
@@ -376,13 +107,9 @@ struct WaveLds {
 // (the code-length code's table - 128 bytes, lane 0's, needed only while a block header is read -
 // lies in the chunk's stage: no chunk is staged then.  128 bytes more would make a CU's LDS hold
 // 15 of these instead of 16.)
-static_assert(sizeof(((WaveLds*)nullptr)->stage) >= 128, "");
+static_assert(sizeof(((WaveLds*)nullptr)->stage) >= (1 << dbi::kClTableBits), "");
 struct WaveMem {
     WaveLds* m;
-#ifndef DBI_WAVE_CL_TABLE
-#define DBI_WAVE_CL_TABLE 7
-#endif
-    static constexpr int kClTableBits = DBI_WAVE_CL_TABLE;      // (7, or 0 = without the table)
     __device__ __forceinline__ uint32_t cl_tab(int i) const {
         return reinterpret_cast<const uint8_t*>(m->stage)[i];
     }
@@ -390,10 +117,6 @@ struct WaveMem {
         reinterpret_cast<uint8_t*>(m->stage)[i] = (uint8_t)v;
     }
     __device__ __forceinline__ uint32_t stage(int i) const { return m->stage[i]; }
-    __device__ __forceinline__ uint32_t lit_tab(int) const { return 0u; }      // (no decode tables)
-    __device__ __forceinline__ void set_lit_tab(int, uint32_t) {}
-    __device__ __forceinline__ uint32_t dist_tab(int) const { return 0u; }
-    __device__ __forceinline__ void set_dist_tab(int, uint32_t) {}
     __device__ __forceinline__ uint32_t wave_lit_tab(int i) const { return m->wave_lit_tab[i]; }
     __device__ __forceinline__ uint32_t wave_dist_tab(int i) const { return m->wave_dist_tab[i]; }
     __device__ __forceinline__ uint32_t ring(int r) const { return m->ring[r]; }
@@ -428,9 +151,8 @@ struct NoProgress {
     __device__ __forceinline__ void tokens(int) const {}
 };
 
-// One stream through kernel 1's one-wavefront-per-stream form: the tokens to `tokens` + the
-// stream's out_offset, its record returned (lane 0's copy is the stream's state).  `lds` is this
-// wave's own, the wave synchronises with nobody (inflate_tokens_wave_kernel: one wave per
+// One stream through kernel 1: the tokens to `tokens` + the stream's out_offset, its record
+// returned (lane 0's copy is the stream's state).  `lds` is this wave's own, the wave synchronises with nobody (inflate_tokens_wave_kernel: one wave per
 // workgroup; inflate_pair_kernel: beside the wave that resolves the same stream's tokens, which
 // `progress.tokens(n)` tells how many are there - behind every chunk and every stored run).
 template <class Progress>
@@ -586,14 +308,7 @@ __global__ __launch_bounds__(dbi::kWaveLanes) __attribute__((amdgpu_waves_per_eu
     if (lane == 0) info[i] = rec;
 }
 
-constexpr int kRing = dbi::kWindowRing;
 static_assert(dbi::kStepTokens == 64, "one token per lane and step");
-constexpr int kWaves2 = 5;                 // streams per workgroup of kernel 2: a 32 KiB ring each
-// timing-only ablations of kernel 2 (wrong bytes): 1 no match copies, 2 no flush of the ring, 4 no
-// literal stores
-#ifndef DBI_K2_ABL
-#define DBI_K2_ABL 0
-#endif
 
 // Wave-wide inclusive prefix sum on the DPP network (no LDS round trips): within rows of 16
 // lanes by shifts, then each row's total handed on to the rows behind it.
@@ -617,182 +332,12 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
     return v;
 }
 
-// Adler-32 without a reduction per piece: s1 = 1 + sum of the bytes, s2 = n + sum over the bytes
-// of (n - position) * byte, n = the stream's length (known from kernel 1) - every lane keeps its
-// own two sums, the wave adds them up once per stream.
-struct AdlerLane {
-    unsigned bytes;
-    unsigned long long weighted;
-    __device__ __forceinline__ void add4(unsigned w, unsigned left) {     // `left` = n - position
-        const unsigned b0 = w & 255u, b1 = (w >> 8) & 255u, b2 = (w >> 16) & 255u, b3 = w >> 24;
-        const unsigned s = b0 + b1 + b2 + b3;
-        bytes += s;
-        weighted += (unsigned long long)left * s - (b1 + 2u * b2 + 3u * b3);
-    }
-    __device__ __forceinline__ void add1(unsigned b, unsigned left) {
-        bytes += b;
-        weighted += (unsigned long long)left * b;
-    }
-};
-
-__global__ __launch_bounds__(64 * kWaves2) void inflate_resolve_kernel(
-    const uint8_t* __restrict__ comp, int64_t comp_total,
-    const dbh_inflate_stream* __restrict__ streams, int n_streams,
-    const uint32_t* __restrict__ tokens, StreamInfo* __restrict__ info, uint8_t* __restrict__ out,
-    int32_t* __restrict__ status_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t rings[kWaves2 * kRing];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    uint8_t* ring = rings + wave * kRing;
-    for (int i = blockIdx.x * kWaves2 + wave; i < n_streams; i += gridDim.x * kWaves2) {
-        const dbh_inflate_stream s = zlib_view(streams[i], comp, comp_total);
-        uint8_t* dst = out + s.out_offset;
-        const int64_t cap = s.out_bytes;
-        if (passed_by(s.mode)) continue;             // (dbh_vbz.hip, dbh_zstd.hip)
-        if (s.mode != DBH_INFLATE_ZLIB) {
-            // stored as it is (an unfiltered chunk, a contiguous dataset, or bytes the host has
-            // inflated itself): copy, zero-extend
-            const int64_t have = s.comp_bytes < cap ? s.comp_bytes : cap;
-            const uint8_t* src = comp + s.comp_offset;
-            const int64_t whole = have & ~(int64_t)7;
-            for (int64_t k = 8 * (int64_t)lane; k < whole; k += 512) {
-                uint64_t v;
-                __builtin_memcpy(&v, src + k, 8);
-                __builtin_memcpy(dst + k, &v, 8);
-            }
-            for (int64_t k = whole + lane; k < cap; k += 64) dst[k] = k < have ? src[k] : (uint8_t)0;
-            if (lane == 0) status_out[i] = dbi::kOk;
-            continue;
-        }
-        StreamInfo r = info[i];
-        int status = r.status;
-        const uint32_t* tok = tokens + s.out_offset;
-        const int n_tok = r.n_tokens;
-        const unsigned n_out = (unsigned)r.produced;
-        int pos = 0, flushed = 0;                    // (a stream's output is far below 2^31 bytes)
-        AdlerLane adler = {0u, 0ull};
-        if (status == dbi::kOk) {
-            uint32_t t_next = lane < n_tok ? tok[lane] : 0u;
-            for (int t0 = 0; t0 < n_tok; t0 += 64) {
-                const bool valid = t0 + lane < n_tok;
-                const uint32_t t = t_next;
-                // (the next step's tokens are on their way while this step's are resolved)
-                t_next = t0 + 64 + lane < n_tok ? tok[t0 + 64 + lane] : 0u;
-                const bool is_match = valid && (t & dbi::kMatchFlag);
-                const int len = !valid ? 0 : is_match ? (int)(t & 0x1FFu) : 1;
-                const int dist = (int)((t >> 9) & 0x7FFFu) + 1;
-                const int incl = wave_scan_i32(len);
-                const int total = __builtin_amdgcn_readlane(incl, 63);
-                const int my = pos + incl - len;
-                if (__any(is_match && dist > my)) {     // reaches before the start of the output
-                    status = dbi::kBadDistance;
-                    break;
-                }
-                const int src = my - dist;
-                if (__any(is_match && dbi::ring_hazard(dist, my, pos + total))) {
-                    // A match of this step reaches back so far that a write near the step's end
-                    // would land on bytes it has yet to read (dbh_inflate_core.h: ring_hazard) -
-                    // rare (distances beyond 16 K with long matches behind them): this step goes
-                    // in strict token order, one lane at a time.
-                    for (int l = 0; l < 64; ++l) {
-                        lds_settle();
-                        if (lane == l && valid) {
-                            if (!is_match) {
-                                ring[my & (kRing - 1)] = (uint8_t)t;
-                            } else {
-                                for (int k = 0; k < len; ++k)
-                                    ring[(my + k) & (kRing - 1)] = ring[(src + k) & (kRing - 1)];
-                            }
-                        }
-                    }
-                    lds_settle();
-                } else {
-                if (!(DBI_K2_ABL & 4) && valid && !is_match) ring[my & (kRing - 1)] = (uint8_t)t;
-                // A match repeats the `dist` bytes before it: byte k is byte k mod dist of them,
-                // so everything it READS lies before its own start, in [src, src + min(len,
-                // dist)) - it may go as soon as that is written, i.e. lies before the earliest
-                // byte still to be written (the first waiting match's start: the positions ascend
-                // with the lanes).  The first waiting match can always go.
-                const int reach = src + (len < dist ? len : dist);
-                bool waiting = is_match && !(DBI_K2_ABL & 1);
-                unsigned long long mask = __ballot(waiting);
-                while (mask != 0ull) {
-                    lds_settle();
-                    const int first = __builtin_amdgcn_readlane(my, __ffsll((long long)mask) - 1);
-                    const bool go = waiting && reach <= first;
-                    int k = 0, o = 0;                    // o = k mod dist
-                    while (__any(go && k < len)) {
-                        if (go && k < len) {
-                            // four bytes at a time: the loads leave together, then the stores
-                            int o1 = o + 1;
-                            o1 = o1 == dist ? 0 : o1;
-                            int o2 = o1 + 1;
-                            o2 = o2 == dist ? 0 : o2;
-                            int o3 = o2 + 1;
-                            o3 = o3 == dist ? 0 : o3;
-                            const uint8_t b0 = ring[(src + o) & (kRing - 1)];
-                            const uint8_t b1 = ring[(src + o1) & (kRing - 1)];
-                            const uint8_t b2 = ring[(src + o2) & (kRing - 1)];
-                            const uint8_t b3 = ring[(src + o3) & (kRing - 1)];
-                            ring[(my + k) & (kRing - 1)] = b0;
-                            if (k + 1 < len) ring[(my + k + 1) & (kRing - 1)] = b1;
-                            if (k + 2 < len) ring[(my + k + 2) & (kRing - 1)] = b2;
-                            if (k + 3 < len) ring[(my + k + 3) & (kRing - 1)] = b3;
-                            o = o3 + 1;
-                            o = o == dist ? 0 : o;
-                            k += 4;
-                        }
-                    }
-                    waiting = waiting && !go;
-                    mask = __ballot(waiting);
-                }
-                }
-                pos += total;
-                // whole 256-byte pieces out of the ring, the Adler-32 sums on the way
-                if (!(DBI_K2_ABL & 2) && pos - flushed >= 256) {
-                    lds_settle();
-                    do {
-                        const uint32_t w = *reinterpret_cast<const uint32_t*>(
-                            ring + ((flushed + 4 * lane) & (kRing - 1)));
-                        uint16_t* d16 = reinterpret_cast<uint16_t*>(dst + flushed + 4 * lane);
-                        d16[0] = (uint16_t)w;             // (a read starts at an even byte, not
-                        d16[1] = (uint16_t)(w >> 16);     //  necessarily at a multiple of four)
-                        adler.add4(w, n_out - (unsigned)(flushed + 4 * lane));
-                        flushed += 256;
-                    } while (pos - flushed >= 256);
-                }
-            }
-        }
-        if (status == dbi::kOk) {
-            lds_settle();
-            const int rest = pos - flushed;           // < 256
-            for (int k = lane; k < rest; k += 64) {
-                const unsigned b = ring[(flushed + k) & (kRing - 1)];
-                dst[flushed + k] = (uint8_t)b;
-                adler.add1(b, n_out - (unsigned)(flushed + k));
-            }
-            if (r.ended) {
-                const unsigned s1 = (1u + wave_sum_u32(adler.bytes)) % 65521u;
-                const unsigned s2 =
-                    (unsigned)(((unsigned long long)n_out + wave_sum_u64(adler.weighted)) % 65521ull);
-                if (((s2 << 16) | s1) != r.adler) status = dbi::kBadChecksum;
-            }
-            // a stream that ends early (MinKNOW's short final chunk): libhdf5 zero-extends it
-            for (int64_t k = pos + lane; k < cap; k += 64) dst[k] = 0;
-        }
-        if (status != dbi::kOk)                       // nothing of a damaged stream is handed on
-            for (int64_t k = lane; k < cap; k += 64) dst[k] = 0;
-        if (lane == 0) status_out[i] = status;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
-// Kernel 2, second form (what runs; DEEPBINNER_INFLATE_RESOLVE=rounds brings the first back).
-// One wave per stream and up to 64 tokens per step as before - another schedule and a smaller
-// ring (dbh_inflate_core.h: "Phase 2's second form").  In the first form every match went through
-// the rounds: a step's ~38 matches of ~3.6 bytes took 3.65 rounds of 4.6 four-byte turns, each a
-// dependent LDS load and store behind a drained queue - ~5 k cycles per step, 60 % of them waiting,
-// with five waves per CU (the 32 KiB rings) and nothing to fill the waits.  Here
+// Kernel 2: one wave per stream and up to 64 tokens per step (dbh_inflate_core.h: "Phase 2's
+// second form").  Its first form (rounds 3-5, retired: HISTORY.md) sent every match through the
+// rounds: a step's ~38 matches of ~3.6 bytes took 3.65 rounds of 4.6 four-byte turns, each a
+// dependent LDS load and store behind a drained queue - ~5 k cycles per step, 60 % of them
+// waiting, with five waves per CU (32 KiB rings) and nothing to fill the waits.  Here
 //   * a short match whose source is complete before its step ("pre", 82 %) reads its eight source
 //     bytes at the boundary in front of the step - one unaligned ds_read_b64 from the ring, or one
 //     unaligned global load from the stream's own output where the source lies further back than
@@ -805,16 +350,16 @@ __global__ __launch_bounds__(64 * kWaves2) void inflate_resolve_kernel(
 //     stream by stream, not when the longest of five has ended).
 // The CPU harness models this schedule byte for byte - which copy of a position (ring slot or
 // flushed output) every read sees - and holds it against the tokens resolved in order.
-constexpr int kRing3 = dbi::kSmallRing;
+constexpr int kRing = dbi::kSmallRing;
 __device__ __forceinline__ uint64_t ring_read8(const uint8_t* ring, int p) {
-    const int slot = p & (kRing3 - 1);
+    const int slot = p & (kRing - 1);
     uint64_t v;
-    if (slot <= kRing3 - 8) {
+    if (slot <= kRing - 8) {
         __builtin_memcpy(&v, ring + slot, 8);          // (byte-aligned: hipcc emits ds_read_b64)
     } else {                                           // over the end of the ring: byte by byte
         v = 0;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v |= (uint64_t)ring[(slot + j) & (kRing3 - 1)] << (8 * j);
+        for (int j = 0; j < 8; ++j) v |= (uint64_t)ring[(slot + j) & (kRing - 1)] << (8 * j);
     }
     return v;
 }
@@ -825,8 +370,8 @@ __device__ __forceinline__ uint64_t output_read8(const uint8_t* dst, int p) {
 }
 // the first `len` (1..8) bytes of v to positions p, p + 1, ...
 __device__ __forceinline__ void ring_store_short(uint8_t* ring, int p, int len, uint64_t v) {
-    const int slot = p & (kRing3 - 1);
-    if (len >= 3 && slot + len <= kRing3) {
+    const int slot = p & (kRing - 1);
+    if (len >= 3 && slot + len <= kRing) {
         if (len >= 4) {                                // two four-byte stores that may overlap
             const uint32_t a = (uint32_t)v, b = (uint32_t)(v >> (8 * (len - 4)));
             __builtin_memcpy(ring + slot, &a, 4);
@@ -839,7 +384,7 @@ __device__ __forceinline__ void ring_store_short(uint8_t* ring, int p, int len, 
     } else {                                           // a cut match of one or two bytes, or over
 #pragma unroll                                         // the end of the ring
         for (int j = 0; j < 8; ++j)
-            if (j < len) ring[(slot + j) & (kRing3 - 1)] = (uint8_t)(v >> (8 * j));
+            if (j < len) ring[(slot + j) & (kRing - 1)] = (uint8_t)(v >> (8 * j));
     }
 }
 
@@ -911,7 +456,7 @@ struct AllTokensThere {
     __device__ __forceinline__ StreamInfo record() const { return r; }
 };
 
-// One stream through kernel 2's second form: its bytes to out + the stream's out_offset, the
+// One stream through kernel 2: its bytes to out + the stream's out_offset, the
 // verdict to *status_slot.  `ring` (kSmallRing bytes) is this wave's own.  `there.wait(need, limit,
 // done)` returns once tokens [0, need) are there or kernel 1 is done with the stream; `limit` = the
 // number of tokens if it is done, INT_MAX otherwise.
@@ -967,9 +512,9 @@ __device__ __forceinline__ void resolve_pre_stream(
                 const int src = c.my - c.dist;
                 const int reach = src + (c.len < c.dist ? c.len : c.dist);
                 const int my_end = c.my + c.len;
-                if (!(DBI_K2_ABL & 4) && c.valid && !c.is_match) ring[c.my & (kRing3 - 1)] = (uint8_t)c.t;
+                if (c.valid && !c.is_match) ring[c.my & (kRing - 1)] = (uint8_t)c.t;
                 if (pre) ring_store_short(ring, c.my, c.len, c.dist < c.len ? dbi::k2_pattern8(pv, c.dist) : pv);
-                bool waiting = c.is_match && !pre && !(DBI_K2_ABL & 1);
+                bool waiting = c.is_match && !pre;
                 unsigned long long mask = __ballot(waiting);
                 while (mask != 0ull) {
                     lds_settle();
@@ -998,14 +543,14 @@ __device__ __forceinline__ void resolve_pre_stream(
                                 int o3 = o2 + 1;
                                 o3 = o3 == c.dist ? 0 : o3;
                                 const bool near = dbi::k2_in_ring(src, end);      // (then all of [src, my) is)
-                                const uint8_t b0 = near ? ring[(src + o) & (kRing3 - 1)] : dst[src + o];
-                                const uint8_t b1 = near ? ring[(src + o1) & (kRing3 - 1)] : dst[src + o1];
-                                const uint8_t b2 = near ? ring[(src + o2) & (kRing3 - 1)] : dst[src + o2];
-                                const uint8_t b3 = near ? ring[(src + o3) & (kRing3 - 1)] : dst[src + o3];
-                                ring[(c.my + k) & (kRing3 - 1)] = b0;
-                                if (k + 1 < c.len) ring[(c.my + k + 1) & (kRing3 - 1)] = b1;
-                                if (k + 2 < c.len) ring[(c.my + k + 2) & (kRing3 - 1)] = b2;
-                                if (k + 3 < c.len) ring[(c.my + k + 3) & (kRing3 - 1)] = b3;
+                                const uint8_t b0 = near ? ring[(src + o) & (kRing - 1)] : dst[src + o];
+                                const uint8_t b1 = near ? ring[(src + o1) & (kRing - 1)] : dst[src + o1];
+                                const uint8_t b2 = near ? ring[(src + o2) & (kRing - 1)] : dst[src + o2];
+                                const uint8_t b3 = near ? ring[(src + o3) & (kRing - 1)] : dst[src + o3];
+                                ring[(c.my + k) & (kRing - 1)] = b0;
+                                if (k + 1 < c.len) ring[(c.my + k + 1) & (kRing - 1)] = b1;
+                                if (k + 2 < c.len) ring[(c.my + k + 2) & (kRing - 1)] = b2;
+                                if (k + 3 < c.len) ring[(c.my + k + 3) & (kRing - 1)] = b3;
                                 o = o3 + 1;
                                 o = o == c.dist ? 0 : o;
                                 k += 4;
@@ -1026,10 +571,10 @@ __device__ __forceinline__ void resolve_pre_stream(
                 if (pre_n && src_n >= 0)
                     pv_n = dbi::k2_in_ring(src_n, pos) ? ring_read8(ring, src_n) : output_read8(dst, src_n);
                 // whole 256-byte pieces out of the ring, the Adler-32 sums on the way
-                if (!(DBI_K2_ABL & 2) && pos - flushed >= 256) {
+                if (pos - flushed >= 256) {
                     do {
                         const uint32_t w = *reinterpret_cast<const uint32_t*>(
-                            ring + ((flushed + 4 * lane) & (kRing3 - 1)));
+                            ring + ((flushed + 4 * lane) & (kRing - 1)));
                         uint16_t* d16 = reinterpret_cast<uint16_t*>(dst + flushed + 4 * lane);
                         d16[0] = (uint16_t)w;             // (a read starts at an even byte, not
                         d16[1] = (uint16_t)(w >> 16);     //  necessarily at a multiple of four)
@@ -1054,7 +599,7 @@ __device__ __forceinline__ void resolve_pre_stream(
             lds_settle();
             const int rest = pos - flushed;           // < 256
             for (int k = lane; k < rest; k += 64) {
-                const unsigned b = ring[(flushed + k) & (kRing3 - 1)];
+                const unsigned b = ring[(flushed + k) & (kRing - 1)];
                 dst[flushed + k] = (uint8_t)b;
                 adler.add1(b, (unsigned)(flushed + k));
             }
@@ -1073,7 +618,7 @@ __global__ __launch_bounds__(64) void inflate_resolve_pre_kernel(
     const dbh_inflate_stream* __restrict__ streams, int n_streams,
     const uint32_t* __restrict__ tokens, StreamInfo* __restrict__ info, uint8_t* out,
     int32_t* __restrict__ status_out) {
-    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing3];
+    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
     const int lane = threadIdx.x;
     for (int i = blockIdx.x; i < n_streams; i += gridDim.x) {
         const dbh_inflate_stream s = zlib_view(streams[i], comp, comp_total);
@@ -1144,7 +689,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const dbh_inflate_stream* __restrict__ streams, int n_streams, uint32_t* tokens,
     StreamInfo* __restrict__ info, uint8_t* out, int32_t* __restrict__ status_out) {
     __shared__ __attribute__((aligned(16))) WaveLds decode;
-    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing3];
+    __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
     __shared__ PairWords words;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1178,27 +723,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 
 thread_local char g_error[256];
 
-// which form of kernel 1 runs: DEEPBINNER_INFLATE_KERNEL=wave (one wavefront per stream) | lane (one
-// lane per stream); read at every call, so that a test can hold the two against each other
-// which form of kernel 2 runs: DEEPBINNER_INFLATE_RESOLVE=pre (short matches with a complete source
-// read at the step boundary, the rest by the exact rule) | rounds (every match through the rounds)
-bool resolve_pre() {
-    const char* v = std::getenv("DEEPBINNER_INFLATE_RESOLVE");
-    if (v && std::strcmp(v, "rounds") == 0) return false;
-    return true;
-}
-
 // both kernels as one launch, a pair of waves per stream (DEEPBINNER_INFLATE_PAIR=0: two launches)
 bool pair_of_waves() {
     const char* v = std::getenv("DEEPBINNER_INFLATE_PAIR");
     return !(v && std::strcmp(v, "0") == 0);
-}
-
-bool wave_per_stream() {
-    const char* v = std::getenv("DEEPBINNER_INFLATE_KERNEL");
-    if (v && std::strcmp(v, "lane") == 0) return false;
-    if (v && std::strcmp(v, "wave") == 0) return true;
-    return DBI_DEFAULT_WAVE != 0;
 }
 
 int hip_failed(hipError_t e, const char* what) {
@@ -1271,41 +799,19 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
     uint32_t* tokens = (uint32_t*)workspace_dev;
     char* behind = (char*)workspace_dev +
                    (((size_t)total_out_bytes * sizeof(uint32_t) + 255) & ~(size_t)255);
-    int* counter = (int*)behind;
-    StreamInfo* info = (StreamInfo*)(behind + 256);
-    const int n = (int)n_streams;
-    DBI_HIP(hipMemsetAsync(counter, 0, sizeof(int), (hipStream_t)stream));
-    // the lanes take streams off a counter: with one stream per lane (the default) a launch is
-    // as wide as it can be and lasts as long as its longest stream; with several, a fraction of
-    // the CUs does the same work in the time the longest stream needs anyway
-    if (pair_of_waves() && wave_per_stream() && resolve_pre()) {
+    StreamInfo* info = (StreamInfo*)(behind + 256);      // (the 256 bytes in front: unused, kept
+    const int n = (int)n_streams;                        //  so that the records do not move)
+    if (pair_of_waves()) {
         hipLaunchKernelGGL(inflate_pair_kernel, dim3((unsigned)n), dim3(128), 0, (hipStream_t)stream,
                            comp_dev, comp_bytes, streams_dev, n, tokens, info, out_dev, status_dev);
-        DBI_HIP(hipGetLastError());
-        return vbz_stages(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, workspace_dev,
-                          info, status_dev, (hipStream_t)stream);
-    }
-    if (wave_per_stream()) {
+    } else {
         hipLaunchKernelGGL(inflate_tokens_wave_kernel, dim3((unsigned)n), dim3(dbi::kWaveLanes), 0,
                            (hipStream_t)stream, comp_dev, comp_bytes, streams_dev, n, tokens, info);
-    } else {
-        const int per_lane = (streams_per_lane > 0 ? streams_per_lane : 1) * kPerLane;
-        const int64_t lanes = (n_streams + per_lane - 1) / per_lane;
-        hipLaunchKernelGGL(inflate_tokens_kernel, dim3((unsigned)((lanes + kLanes - 1) / kLanes)),
-                           dim3(kLanes), 0, (hipStream_t)stream, comp_dev, comp_bytes, streams_dev, n,
-                           tokens, info, counter);
-    }
-    DBI_HIP(hipGetLastError());
-    const int groups = (n + kWaves2 - 1) / kWaves2;
-    const int blocks = groups < 1024 ? groups : 1024;
-    if (resolve_pre())
+        DBI_HIP(hipGetLastError());
         hipLaunchKernelGGL(inflate_resolve_pre_kernel, dim3((unsigned)(n < 65536 ? n : 65536)), dim3(64), 0,
                            (hipStream_t)stream, comp_dev, comp_bytes, streams_dev, n, (const uint32_t*)tokens,
                            info, out_dev, status_dev);
-    else
-        hipLaunchKernelGGL(inflate_resolve_kernel, dim3((unsigned)blocks), dim3(64 * kWaves2), 0,
-                           (hipStream_t)stream, comp_dev, comp_bytes, streams_dev, n, (const uint32_t*)tokens,
-                           info, out_dev, status_dev);
+    }
     DBI_HIP(hipGetLastError());
     return vbz_stages(comp_dev, comp_bytes, streams_dev, n, total_out_bytes, out_dev, workspace_dev, info,
                       status_dev, (hipStream_t)stream);

@@ -1,9 +1,16 @@
 // dbh_inflate_core.h - RFC 1950 / 1951 decoding (zlib streams, the HDF5 "deflate" filter that
-// fast5 Signal chunks are stored with), phase 1: Huffman decoding of ONE stream by ONE lane into a
-// stream of tokens (literal byte | match {length, distance}).  Phase 2 (dbh_inflate.hip) resolves
-// the tokens of a stream into bytes with a whole wavefront and the 32 KiB window in LDS.
-// (Since round 5 what runs by default gives a stream a whole WAVEFRONT in phase 1 too:
-// dbh_inflate_wave.h - the headers, code builds and per-token arithmetic are this header's.)
+// fast5 Signal chunks are stored with).  Three things live here:
+//   * the CANONICAL DECODER of one stream by one lane, into a stream of tokens (literal byte |
+//     match {length, distance}): zlib header, block headers with their code builds, stored bytes,
+//     and the per-token front (lane_decode);
+//   * of that, what LANE 0 of the one-wavefront-per-stream kernel runs as its serial code
+//     (dbh_inflate_wave.h; dbh_inflate.hip: tokens_wave_stream): lane_start, lane_block, lane_ended,
+//     lane_fail, BitReader::seek - and the arithmetic the wave's lanes share with it (first16,
+//     code_length, sorted_index, the entry formats).  The rest - lane_stored, lane_decode and the
+//     BitReader's checkpoints - runs only in the CPU harness, as the REFERENCE the wave form is
+//     held to: it must leave the very tokens and the very lane state of this decoder;
+//   * PHASE 2's rules (tokens -> bytes, dbh_inflate.hip: resolve_pre_stream), shared by the kernel
+//     and the harness's model of its schedule.
 //
 // What the reference does here: h5py -> libhdf5 -> zlib's inflate() on the host, one chunk after
 // the other (deepbinner/load_fast5s.py:33-43 reads `Signal[:]`).  Inflating is ~85 % of what loading
@@ -12,22 +19,21 @@
 // is good at.
 //
 // This header is compiled twice: by hipcc into the kernels, and by g++ into the CPU test harness
-// (oracle/inflate_host_test.cpp via oracle/Makefile), which runs the SAME decoder lane by lane
-// against zlib on the build box.  All per-lane memory is reached through a `Mem` accessor: LDS,
-// interleaved by lane, on the device; plain arrays on the host.
+// (oracle/inflate_host_test.cpp via oracle/Makefile), which runs the SAME decoder
+// against zlib on the build box.  All of a decoder's memory is reached through a `Mem` accessor:
+// the wave's LDS on the device; plain arrays on the host.
 //
 // How a code is decoded - CANONICALLY, without decode tables: the codes of one length are
 // consecutive numbers, and read as 16-bit numbers with the first bit on top (left-justified) the
 // ranges of lengths 1, 2, .. 15 follow each other in ascending order.  So
 //     length  = 1 + the number of range ENDS that are <= the next 16 bits   (15 compares against
-//               per-lane registers: no memory, no branches)
+//               registers: no memory, no branches)
 //     symbol  = sorted[first index of that length + (bits - first code of that length)]
-// and per lane only the symbols sorted by (length, symbol) live in LDS: 288 + 32 entries and two
-// 16-entry {first code, first index} tables - 1.2 KB per lane against the 4.6 KB of zlib-style
-// root and sub-tables, which is what decides how many streams a CU decodes at a time (LDS is the
-// only thing this kernel runs out of).  The sorted entries of the literal/length code carry the
-// decoded meaning (literal byte | end of block | length base and extra bits), so no
-// per-symbol arithmetic is left in the loop.
+// and only the symbols sorted by (length, symbol) live in memory: 288 + 32 entries and two
+// 16-entry {first code, first index} tables - 1.2 KB against the 4.6 KB of zlib-style root and
+// sub-tables.  The sorted entries of the literal/length code carry the decoded meaning (literal
+// byte | end of block | length base and extra bits), so no per-symbol arithmetic is left in the
+// loop.  (The wave form puts first-level tables in front of this: dbh_inflate_wave.h.)
 #pragma once
 #include <stdint.h>
 
@@ -50,28 +56,11 @@ struct U4 {
 constexpr int kMaxLens = 320;            // 288 literal/length + 32 distance code lengths
 constexpr int kLitSyms = 288;
 constexpr int kDistSyms = 32;
-constexpr int kRingRows = 32;            // dwords of input a lane keeps in LDS (+ 2 mirror rows)
+constexpr int kRingRows = 32;            // dwords of input a lane keeps at hand (+ 2 mirror rows)
 constexpr int kRingStore = kRingRows + 2;
 constexpr int kFetchDwords = 8;          // dwords per request
-// First-level decode tables (round 5): index = the next kLitBits / kDistBits bits of the stream
-// (first bit lowest), entry = the code's length and what it means - one LDS read and a handful of
-// instructions where the canonical method walks a 15-step compare chain and two dependent reads.
-// A code longer than the index has no entry (length 0) and goes the canonical way (lockstep: the
-// whole wave does, whenever one of its lanes meets one).
-// Built, bit-exact and measured in round 5 - and NOT what ships (DBI_LIT_BITS 0 = no tables):
-// with 16 lanes per wave and an 11-bit index (5 % of the rounds still go the canonical way) kernel
-// 1 takes 11.1 ms instead of 13.0 for 4,000 streams, on four times the waves; with 32 lanes and 10
-// bits (39 % of the rounds) 12.8 ms (profiles/r05_inflate/README.md).  The CPU harness compiles
-// them in (oracle/inflate_host_test.cpp) and holds every answer against the canonical method.
-#ifndef DBI_LIT_BITS
-#define DBI_LIT_BITS 0
-#endif
-#ifndef DBI_DIST_BITS
-#define DBI_DIST_BITS 8
-#endif
-constexpr bool kTables = DBI_LIT_BITS > 0;
-constexpr int kLitBits = kTables ? DBI_LIT_BITS : 1, kDistBits = kTables ? DBI_DIST_BITS : 1;
-static_assert(kLitBits >= 1 && kLitBits <= 15 && kDistBits >= 1 && kDistBits <= 15, "");
+// the code-length code's table (CodeLengthCode below): Mem::cl_tab has 1 << kClTableBits entries
+constexpr int kClTableBits = 7;
 // token: literal = the byte; match = bit 31 | (distance - 1) << 9 | length
 constexpr uint32_t kMatchFlag = 0x80000000u;
 DBI_HD uint32_t match_token(uint32_t length, uint32_t distance) {
@@ -92,26 +81,16 @@ enum Status : int {
     kTooLong = 10,         // (phase 2, whole-stream mode) more output than announced
 };
 
-// Phase 2 keeps a stream's last 32 KiB of output in a ring of exactly that size (the largest
-// distance deflate knows) and resolves kStepTokens tokens at a time, out of token order: all of a
-// step's literals first, then its matches in rounds.  A byte written at position q takes the
-// slot of byte q - kWindowRing; a step spans up to 64 x 258 bytes, so a write near the step's end
-// can land on what a match near the step's start has yet to read - when that match reaches back
-// far enough: its distance plus the bytes from its start to the step's end exceed the ring.  Such
-// a step (zlib produces them: 32,000 random bytes twice in a row are 258-byte matches at distance
-// 32,000 back to back) is resolved in strict token order instead, where every write follows the
-// reads it could disturb.  Shared by the kernel and by the CPU harness's model of it.
-constexpr int kWindowRing = 32768;
+// Phase 2 (dbh_inflate.hip: resolve_pre_stream) resolves kStepTokens tokens at a time, out of token
+// order, with a ring of the stream's latest output in LDS.
 constexpr int kStepTokens = 64;
-DBI_HD bool ring_hazard(int dist, int my, int step_end) {
-    return dist + (step_end - my) > kWindowRing;
-}
 
-// Phase 2's second form (inflate_resolve_pre_kernel, what runs since the end of round 5).  What
-// the tokens of a read look like (level-1 streams of squiggles, oracle/inflate_host_test with
-// DBI_K2_STATS): distances are spread over the whole window (19 % within 256 bytes, 75 % within
-// 8 K), 99.99 % of the matches are at most kShortMatch bytes long, and only one in ten reads
-// anything its own step writes.  So:
+// Phase 2's second form (inflate_resolve_pre_kernel, what runs since the end of round 5; the
+// first form, the whole 32 KiB window as a ring, is retired: HISTORY.md).  What the tokens of a
+// read look like (level-1 streams of squiggles, oracle/inflate_host_test with DBI_K2_STATS):
+// distances are spread over the whole window (19 % within 256 bytes, 75 % within 8 K), 99.99 % of
+// the matches are at most kShortMatch bytes long, and only one in ten reads anything its own step
+// writes.  So:
 //  * a SHORT match whose source lies wholly before its step - four fifths of all - is "pre"
 //    (k2_pre): its eight source bytes are read at the boundary in front of the step, behind the
 //    last write of the step before, and stored together with the step's literals;
@@ -126,12 +105,9 @@ DBI_HD bool ring_hazard(int dist, int my, int step_end) {
 //    ring always holds a whole step and the unflushed bytes before it: during a step that ends at
 //    `end` position p is in the ring if p >= end - kSmallRing, and in global memory otherwise
 //    (k2_in_ring) - no write of the step can land on a byte that is still to be read from the
-//    ring, and the first form's ring hazard (a step in token order) does not exist.
-#ifndef DBI_SMALL_RING
-#define DBI_SMALL_RING 8192
-#endif
-constexpr int kSmallRing = DBI_SMALL_RING;
-constexpr int kStepSpan = DBI_SMALL_RING / 2;
+//    ring.
+constexpr int kSmallRing = 8192;
+constexpr int kStepSpan = kSmallRing / 2;
 static_assert(kSmallRing >= kStepSpan + 256 + 8 + 8, "a step, the unflushed bytes before it, an eight-byte read");
 DBI_HD bool k2_in_ring(int p, int step_end) { return p >= step_end - kSmallRing; }
 constexpr int kShortMatch = 8;
@@ -179,18 +155,8 @@ DBI_HD uint32_t lit_entry(int s) {
     return kEntryLength | ((uint32_t)len_extra(s - 257) << 8) | (uint32_t)(len_base(s - 257) - 3);
 }
 
-// literal/length entry (16 bits): bits 0-3 code length (0 = no entry), 4-6 extra bits of a length
-// symbol (6 = symbols 286 / 287: never valid, 7 = end of block), 7-14 the literal byte or the
-// length's base - 3, bit 15 = not a literal
-DBI_HD uint32_t lit_tab_entry(int s, int len) {
-    uint32_t e;
-    if (s < 256) e = (uint32_t)s << 7;
-    else if (s == 256) e = 0x8000u | (7u << 4);
-    else if (s > 285) e = 0x8000u | (6u << 4);
-    else e = 0x8000u | ((uint32_t)len_extra(s - 257) << 4) | ((uint32_t)(len_base(s - 257) - 3) << 7);
-    return e | (uint32_t)len;
-}
-// distance entry: bits 0-3 code length (0 = no entry), 4-8 the distance symbol
+// an entry of the wave form's distance table (dbh_inflate_wave.h): bits 0-3 code length (0 = no
+// entry), 4-8 the distance symbol
 DBI_HD uint32_t dist_tab_entry(int s, int len) { return ((uint32_t)s << 4) | (uint32_t)len; }
 
 DBI_HD uint32_t low_bits(uint32_t v, uint32_t n) {      // n <= 16
@@ -204,11 +170,6 @@ DBI_HD uint32_t low_bits(uint32_t v, uint32_t n) {      // n <= 16
 // first bit first, everything else in deflate lowest bit first)
 DBI_HD uint32_t first16(uint32_t w) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#ifdef DBI_NO_SDWA
-    uint32_t r = __builtin_bitreverse32(w) >> 16;
-    asm volatile("" : "+v"(r));      // (a value of its own: not a sub-dword selection in every user)
-    return r;
-#endif
     return __builtin_bitreverse32(w) >> 16;
 #else
     uint32_t r = 0;
@@ -218,11 +179,10 @@ DBI_HD uint32_t first16(uint32_t w) {
 }
 DBI_HD uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
-// The input side of a lane: a ring of 32 dwords in LDS ([row][lane]: whatever row each lane
-// wants, the lanes of a wave hit 64 different banks), filled eight dwords at a time by a request
-// issued at one checkpoint and written to the ring at the next, so that nobody waits for global
-// memory; rows 32 and 33 mirror rows 0 and 1, so that the 64-bit window at any bit position is
-// three consecutive rows.  Nothing is consumed without being checked: a stream that runs beyond
+// The input side of a lane: a ring of 32 dwords in the decoder's memory, filled eight dwords at a
+// time by a request issued at one checkpoint and written to the ring at a later one, so that nobody
+// waits for global memory; rows 32 and 33 mirror rows 0 and 1, so that the 64-bit window at any
+// bit position is three consecutive rows.  Nothing is consumed without being checked: a stream that runs beyond
 // its last byte is told so (overrun), whatever the ring held there.
 struct BitReader {
     const uint8_t* in;
@@ -278,13 +238,10 @@ struct BitReader {
         wr += (uint32_t)kFetchDwords;
         pending = 0;
     }
-    // The checkpoint of the hot loop, every four tokens (<= 6 dwords consumed in between).  A
-    // request goes out EARLY (as soon as the ring has room for it: level <= 24) and is written to
-    // the ring LATE (when the level is down to 16 dwords): at ~1.6 dwords per checkpoint it has
-    // some five checkpoints to make its way from HBM - with the round-4 policy (requested at one
-    // checkpoint, committed at the next) a decoder faster than ~600 cycles per token waited for
-    // memory at every fifth checkpoint, and the first-level tables bought nothing (round 5).
-    // Level after a checkpoint >= 11 (17 with a request pending, minus 6), never above 24: the
+    // The checkpoint of the one-lane decoder's token loop, every four tokens (<= 6 dwords consumed
+    // in between).  A request goes out EARLY (as soon as the ring has room for it: level <= 24) and
+    // is written to the ring LATE (when the level is down to 16 dwords): at ~1.6 dwords per
+    // checkpoint it has some five checkpoints to make its way from memory.  Level after a checkpoint >= 11 (17 with a request pending, minus 6), never above 24: the
     // ring neither runs dry nor is overwritten where it is still to be read.
     template <class Mem>
     DBI_HD void checkpoint(Mem& mem) {
@@ -348,7 +305,7 @@ struct BitReader {
     DBI_HD int64_t limit_bytes() const { return (int64_t)(limit_bits >> 3); }
 };
 
-// One lane's decoder state between iterations of the lockstep loop.
+// One lane's decoder state (in the wave form: lane 0's copy is the stream's).
 struct Lane {
     BitReader br;
     // left-justified ends of the code ranges of lengths 1 .. 15 (65,536 = a complete code's last)
@@ -383,55 +340,41 @@ DBI_HD void fill_table(uint32_t c16, int len, uint32_t entry, const Set& set) {
     }
     for (uint32_t k = rev & ((1u << len) - 1u); k < (1u << BITS); k += 1u << len) set((int)k, entry);
 }
+// The three codes of a block, as build_code sees them: where their {first code, first index}
+// pairs and sorted symbols go, and whether a first-level table is filled beside them.
 template <class Mem>
 struct LitCode {
     Mem* m;
-    static constexpr int kTableBits = kTables ? kLitBits : 0;
+    static constexpr int kTableBits = 0;
     DBI_HD void set_pair(int l, uint32_t v) const { m->set_lit_pair(l, v); }
     DBI_HD uint32_t pair(int l) const { return m->lit_pair(l); }
     DBI_HD void set_sym(int at, int s) const { m->set_lit_sym(at, lit_entry(s)); }
-    DBI_HD void clear_table() const {
-        for (int k = 0; k < (1 << kLitBits); ++k) m->set_lit_tab(k, 0u);
-    }
-    DBI_HD void fill(int s, int len, uint32_t c16) const {
-        Mem* mm = m;
-        fill_table<kLitBits>(c16, len, lit_tab_entry(s, len), [mm](int k, uint32_t v) { mm->set_lit_tab(k, v); });
-    }
 };
 template <class Mem>
 struct DistCode {
     Mem* m;
-    static constexpr int kTableBits = kTables ? kDistBits : 0;
+    static constexpr int kTableBits = 0;
     DBI_HD void set_pair(int l, uint32_t v) const { m->set_dist_pair(l, v); }
     DBI_HD uint32_t pair(int l) const { return m->dist_pair(l); }
     DBI_HD void set_sym(int at, int s) const { m->set_dist_sym(at, (uint32_t)s); }
-    DBI_HD void clear_table() const {
-        for (int k = 0; k < (1 << kDistBits); ++k) m->set_dist_tab(k, 0u);
-    }
-    DBI_HD void fill(int s, int len, uint32_t c16) const {
-        Mem* mm = m;
-        fill_table<kDistBits>(c16, len, dist_tab_entry(s, len), [mm](int k, uint32_t v) { mm->set_dist_tab(k, v); });
-    }
 };
 // The code-length code of a dynamic block: built where the distance code's sorted symbols will
 // be.  Its codes are at most 7 bits long, so a table of 128 bytes {symbol << 3 | code length}
-// answers every one of them - where the decoder's memory has room for it (Mem::kClTableBits = 7:
-// the one-wavefront-per-stream form, whose block headers - ~300 code lengths each, decoded by
-// lane 0 alone, one after the other - are a third of its instructions; 0: one lane per stream,
-// 64 tables per wave).
+// answers every one of them (Mem::cl_tab; the wave form's block headers - ~300 code lengths each,
+// decoded by lane 0 alone, one after the other - are a third of its instructions).
 template <class Mem>
 struct CodeLengthCode {
     Mem* m;
-    static constexpr int kTableBits = Mem::kClTableBits;
+    static constexpr int kTableBits = kClTableBits;
     DBI_HD void set_pair(int l, uint32_t v) const { m->set_dist_pair(l, v); }
     DBI_HD uint32_t pair(int l) const { return m->dist_pair(l); }
     DBI_HD void set_sym(int at, int s) const { m->set_dist_sym(at, (uint32_t)s); }
     DBI_HD void clear_table() const {
-        for (int k = 0; k < 128; ++k) m->set_cl_tab(k, 0u);
+        for (int k = 0; k < (1 << kClTableBits); ++k) m->set_cl_tab(k, 0u);
     }
     DBI_HD void fill(int s, int len, uint32_t c16) const {
         Mem* mm = m;
-        fill_table<7>(c16, len, ((uint32_t)s << 3) | (uint32_t)len, [mm](int k, uint32_t v) { mm->set_cl_tab(k, v); });
+        fill_table<kClTableBits>(c16, len, ((uint32_t)s << 3) | (uint32_t)len, [mm](int k, uint32_t v) { mm->set_cl_tab(k, v); });
     }
 };
 
@@ -471,14 +414,15 @@ DBI_HD int build_code(Mem& mem, Code code, int first, int n, uint32_t (&lim)[15]
     if (max != 0 && left > 0 && (!may_be_incomplete || max != 1)) return kBadCodes;   // incomplete
     // (a complete code writes every index of its first-level table; one that is not - a single
     // code of length 1, or none at all - leaves the rest without an entry)
-    if (Code::kTableBits > 0 && (left > 0 || max == 0)) code.clear_table();
+    if constexpr (Code::kTableBits > 0)
+        if (left > 0 || max == 0) code.clear_table();
     for (int s = 0; s < n; ++s) {
         const int l = mem.len(first + s);
         if (l != 0) {
             const int at = mem.cnt(l);
             code.set_sym(at, s);
             mem.set_cnt(l, at + 1);
-            if (Code::kTableBits > 0) {
+            if constexpr (Code::kTableBits > 0) {
                 // its code, left-justified: the first code of its length + its place among them
                 const uint32_t pair = code.pair(l);
                 const uint32_t c16 = (pair & 0xFFFFu) + (((uint32_t)at - (pair >> 16)) << (16 - l));
@@ -502,30 +446,6 @@ DBI_HD uint32_t code_length(uint32_t c, const uint32_t (&lim)[15]) {
 #else
     for (int l = 0; l < N; ++l) below += (c - lim[l]) >> 31;
     return (uint32_t)(N + 1) - below;
-#endif
-}
-// The same for N slots at once, the slots' chains interleaved instruction by instruction: a
-// vector instruction that needs the result of the one before it issues later than one that does
-// not, and the chain of one slot is 15 dependent instructions long.
-template <int NL, int N>
-DBI_HD void code_lengths(const uint32_t (&c)[N], const uint32_t* const (&lim)[N], uint32_t (&out)[N]) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t below[N];
-#pragma unroll
-    for (int s = 0; s < N; ++s) below[s] = 0;
-#pragma unroll
-    for (int l = 0; l < NL; ++l) {
-#pragma unroll
-        for (int s = 0; s < N; ++s) below[s] = __builtin_amdgcn_alignbit(below[s], c[s] - lim[s][l], 31);
-    }
-#pragma unroll
-    for (int s = 0; s < N; ++s) out[s] = (uint32_t)(NL + 1) - (uint32_t)__builtin_popcount(below[s]);
-#else
-    for (int s = 0; s < N; ++s) {
-        uint32_t below = 0;
-        for (int l = 0; l < NL; ++l) below += (c[s] - lim[s][l]) >> 31;
-        out[s] = (uint32_t)(NL + 1) - below;
-    }
 #endif
 }
 // index of its symbol among the sorted ones, from the {first code, first index} of its length
@@ -622,19 +542,10 @@ DBI_HD void lane_block(Lane& L, Mem& mem) {
             uint32_t used = 0;
             while (have < want && used <= 50u) {
                 const uint32_t v = (uint32_t)(w >> used);
-                uint32_t cl;
-                int s;
-                if (Mem::kClTableBits > 0) {
-                    const uint32_t e = mem.cl_tab((int)(v & 127u));
-                    cl = e & 7u;
-                    s = (int)(e >> 3);
-                    if (cl == 0u) return lane_fail(L, kBadSymbol);
-                } else {
-                    const uint32_t c = first16(v);
-                    cl = code_length<7>(c, lim_cl);
-                    if (cl > 7u) return lane_fail(L, kBadSymbol);
-                    s = (int)mem.dist_sym((int)umin(sorted_index(c, cl, mem.dist_pair((int)cl)), 18u));
-                }
+                const uint32_t e = mem.cl_tab((int)(v & ((1u << kClTableBits) - 1u)));
+                const uint32_t cl = e & 7u;
+                const int s = (int)(e >> 3);
+                if (cl == 0u) return lane_fail(L, kBadSymbol);
                 used += cl;
                 if (s < 16) {
                     mem.set_len(have++, s);
@@ -668,7 +579,7 @@ DBI_HD void lane_block(Lane& L, Mem& mem) {
     int st = build_code(mem, LitCode<Mem>{&mem}, 0, hlit, L.lim_lit, true);
     if (st == kOk) st = build_code(mem, DistCode<Mem>{&mem}, hlit, hdist, L.lim_dist, true);
     if (st != kOk) return lane_fail(L, st);
-    // (the hot loop's checkpoints keep the ring filled only if it is entered well filled)
+    // (the token loop's checkpoints keep the ring filled only if it is entered well filled)
     br.ensure(mem, 16u);
     L.state = kDecode;
 }
@@ -696,195 +607,62 @@ DBI_HD bool lane_stored(Lane& L, Mem& mem, uint32_t* token) {
     return true;
 }
 
-// The hot path: ONE token of a lane that is inside a Huffman block - straight-line code, the
-// same for a literal, a match and an end of block (all lanes of a wave run it together, so a
-// branch would be taken by somebody every time): one 64-bit window (a token is at most 15 + 5 +
-// 15 + 13 bits), both codes decoded from it, the results selected.
-//   In two halves, because a token is ONE dependent chain - window, code length, two dependent
-// LDS reads, selects, the second code the same again - and a wave that decodes alone on its SIMD
-// (a container is 4,000 streams: 63 waves for 1,024 SIMDs) has nothing to fill the latencies with:
-// lane_decode_front only LOOKS (no state changes), so a kernel whose lanes carry two streams each
-// can run the two fronts side by side in one basic block - the compiler interleaves the two chains
-// - and commit them one after the other (dbh_inflate.hip).
+// ONE token of a lane that is inside a Huffman block, in two halves: lane_decode_front only LOOKS
+// (one 64-bit window - a token is at most 15 + 5 + 15 + 13 bits - both codes decoded from it, the
+// results selected: straight-line code, the same for a literal, a match and an end of block),
+// lane_decode_commit changes the lane's state.  On the device this was the one-lane-per-stream
+// kernel's hot loop (retired: HISTORY.md); now only the CPU harness comes here - a plain
+// single-stream function, the reference the wave form's token_decode (dbh_inflate_wave.h: the
+// same arithmetic without a lane's state) is held to.
 struct Decoded {
     uint32_t used, length, token;
     bool bad, fail, is_end, beyond;
 };
-// all ones if bit `bit` of v is set, else zero (selects below are AND / OR with such masks: a
-// ternary may become a branch, and a branch ends the basic block the two chains share)
+// all ones if bit `bit` of v is set, else zero (selects are AND / OR with such masks: no branches)
 DBI_HD uint32_t bit_mask(uint32_t v, int bit) { return (uint32_t)((int32_t)(v << (31 - bit)) >> 31); }
 DBI_HD uint32_t pick(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }
 
-// LDS reads whose latency the front hides behind the OTHER slot's arithmetic: on the device they are
-// issued as they are asked for and waited for where their value is needed, with a count of the
-// requests that may still be in flight behind them (LDS answers in order) - the compiler's own
-// wait would be for everything, right behind the request.  On the host they are plain reads.
-template <class Mem>
-DBI_HD void issue_ring3(const Mem& mem, int row, uint32_t& a, uint32_t& b, uint32_t& c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    mem.ring3_issue(row, a, b, c);
-#else
-    a = mem.ring(row);
-    b = mem.ring(row + 1);
-    c = mem.ring(row + 2);
-#endif
-}
-template <class Mem>
-DBI_HD void issue_lit_pair(const Mem& mem, int l, uint32_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    mem.lit_pair_issue(l, v);
-#else
-    v = mem.lit_pair(l);
-#endif
-}
-template <class Mem>
-DBI_HD void issue_dist_pair(const Mem& mem, int l, uint32_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    mem.dist_pair_issue(l, v);
-#else
-    v = mem.dist_pair(l);
-#endif
-}
-template <class Mem>
-DBI_HD void issue_lit_sym(const Mem& mem, int i, uint32_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    mem.lit_sym_issue(i, v);
-#else
-    v = mem.lit_sym(i);
-#endif
-}
-template <class Mem>
-DBI_HD void issue_dist_sym(const Mem& mem, int i, uint32_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    mem.dist_sym_issue(i, v);
-#else
-    v = mem.dist_sym(i);
-#endif
-}
-// everything but the PENDING youngest LDS requests has landed
-template <int PENDING>
-DBI_HD void lds_landed() {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(PENDING) : "memory");
-#endif
-}
-DBI_HD void pin(uint32_t& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(v));        // (uses of v stay behind the wait in front of this)
-#else
-    (void)v;
-#endif
-}
-
-// The fronts of N slots (N = 1: the CPU harness and lane_decode; N = 2: the kernel), without a
-// branch and in LOCKSTEP over the slots: every statement is made for all slots before the next
-// one, so that the instruction stream alternates between the slots' (independent) chains - a
-// vector instruction that depends on its predecessor issues later than one that does not - and
-// each stage's LDS reads are in flight together.
-template <int N, class Mem>
-DBI_HD void lane_decode_fronts(const Lane (&L)[N], const Mem (&mem)[N], Decoded (&out)[N]) {
-    uint32_t d0[N], d1[N], d2[N], lo[N], hi[N], sh[N];
-    uint32_t c1[N], n1[N], l1[N], pair1[N], e[N], i1[N];
-    uint32_t is_len[N], eb[N], length[N], c2[N], n2[N], l2[N], pair2[N], d[N], i2[N];
-    uint32_t wl[N], wh[N], not_end[N], ext[N];
-    const uint32_t* lim1[N];
-    const uint32_t* lim2[N];
-#if defined(__HIP_DEVICE_COMPILE__)
-#define DBI_SLOTS _Pragma("unroll") for (int s = 0; s < N; ++s)
-#else
-#define DBI_SLOTS for (int s = 0; s < N; ++s)
-#endif
-    DBI_SLOTS {
-        lim1[s] = L[s].lim_lit;
-        lim2[s] = L[s].lim_dist;
-    }
-    DBI_SLOTS issue_ring3(mem[s], (int)((L[s].br.bp >> 5) & (uint32_t)(kRingRows - 1)), d0[s], d1[s], d2[s]);
-    DBI_SLOTS sh[s] = L[s].br.bp & 31u;
-    lds_landed<0>();
-    DBI_SLOTS {
-        pin(d0[s]);
-        pin(d1[s]);
-        pin(d2[s]);
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-    DBI_SLOTS lo[s] = __builtin_amdgcn_alignbit(d1[s], d0[s], sh[s]);
-    DBI_SLOTS hi[s] = __builtin_amdgcn_alignbit(d2[s], d1[s], sh[s]);
-#else
-    DBI_SLOTS lo[s] = (uint32_t)((((uint64_t)d1[s] << 32) | d0[s]) >> sh[s]);
-    DBI_SLOTS hi[s] = (uint32_t)((((uint64_t)d2[s] << 32) | d1[s]) >> sh[s]);
-#endif
-    // literal / length: the code's length, then {first code, first index} of that length ...
-    DBI_SLOTS c1[s] = first16(lo[s]);
-    code_lengths<15, N>(c1, lim1, n1);
-    DBI_SLOTS l1[s] = umin(n1[s], 15u);
-    DBI_SLOTS issue_lit_pair(mem[s], (int)l1[s], pair1[s]);
-    lds_landed<0>();
-    DBI_SLOTS pin(pair1[s]);
-    // ... its entry among the sorted symbols
-    DBI_SLOTS i1[s] = umin(sorted_index(c1[s], l1[s], pair1[s]), (uint32_t)(kLitSyms - 1));
-    DBI_SLOTS issue_lit_sym(mem[s], (int)i1[s], e[s]);
-    // (the window behind the code, while the entry travels)
-    DBI_SLOTS {
-        const uint64_t w = (((uint64_t)hi[s] << 32) | lo[s]) >> l1[s];
-        wl[s] = (uint32_t)w;
-        wh[s] = (uint32_t)(w >> 32);
-    }
-    lds_landed<0>();
-    DBI_SLOTS pin(e[s]);
-    DBI_SLOTS is_len[s] = bit_mask(e[s], 15);                          // kEntryLength
-    DBI_SLOTS eb[s] = (e[s] >> 8) & 7u & is_len[s];
-    DBI_SLOTS not_end[s] = ((e[s] >> 14) & 1u) ^ 1u;                   // kEntryEnd: length 0, a literal: 1
-    DBI_SLOTS ext[s] = low_bits(wl[s], eb[s]);
-    DBI_SLOTS length[s] = pick(is_len[s], 3u + (e[s] & 0xFFu) + ext[s], not_end[s]);
-    DBI_SLOTS {
-        const uint64_t w = (((uint64_t)wh[s] << 32) | wl[s]) >> eb[s];
-        wl[s] = (uint32_t)w;
-        wh[s] = (uint32_t)(w >> 32);
-    }
-    // distance (decoded whatever the symbol was; only looked at behind a length)
-    DBI_SLOTS c2[s] = first16(wl[s]);
-    code_lengths<15, N>(c2, lim2, n2);
-    DBI_SLOTS l2[s] = umin(n2[s], 15u);
-    DBI_SLOTS issue_dist_pair(mem[s], (int)l2[s], pair2[s]);
-    lds_landed<0>();
-    DBI_SLOTS pin(pair2[s]);
-    DBI_SLOTS i2[s] = umin(sorted_index(c2[s], l2[s], pair2[s]), (uint32_t)(kDistSyms - 1));
-    DBI_SLOTS issue_dist_sym(mem[s], (int)i2[s], d[s]);
-    DBI_SLOTS {
-        const uint64_t w = (((uint64_t)wh[s] << 32) | wl[s]) >> l2[s];
-        wl[s] = (uint32_t)w;             // the distance's extra bits
-    }
-    lds_landed<0>();
-    DBI_SLOTS pin(d[s]);
-    DBI_SLOTS {
-        const uint32_t half = d[s] >> 1;
-        const uint32_t db = (half > 1u ? half : 1u) - 1u;
-        const uint32_t small = (uint32_t)((int32_t)(d[s] - 4u) >> 31);          // d < 4
-        const uint32_t dbase = pick(small, d[s] + 1u, 1u + ((2u | (d[s] & 1u)) << db));
-        const uint32_t distance = dbase + low_bits(wl[s], db);
-        const bool bad = n1[s] > 15u || (e[s] & kEntryBad) != 0 ||
-                         (is_len[s] != 0u && (n2[s] > 15u || d[s] > 29u));
-        Decoded& r = out[s];
-        r.used = l1[s] + eb[s] + ((l2[s] + db) & is_len[s]);
-        r.bad = bad;
-        r.fail = bad || L[s].br.bp + r.used > L[s].br.limit_bits;
-        // more data than wanted: a match keeps what is; the lane stops
-        const int room = L[s].out_cap - L[s].out_pos;
-        r.beyond = (int)length[s] > room;
-        const uint32_t fits = umin(length[s], (uint32_t)(room > 0 ? room : 0));
-        r.length = fits;
-        r.is_end = (e[s] & kEntryEnd) != 0;
-        r.token = pick(is_len[s], match_token(fits, distance), e[s] & 0xFFu);
-    }
-#undef DBI_SLOTS
-}
 template <class Mem>
 DBI_HD Decoded lane_decode_front(const Lane& L, const Mem& mem) {
-    // (one slot: references into one-element arrays)
-    Decoded out[1];
-    lane_decode_fronts<1, Mem>(reinterpret_cast<const Lane(&)[1]>(L),
-                               reinterpret_cast<const Mem(&)[1]>(mem), out);
-    return out[0];
+    uint32_t lo, hi;
+    L.br.window64(mem, lo, hi);
+    // literal / length: the code's length, {first code, first index} of that length, its entry
+    // among the sorted symbols
+    const uint32_t c1 = first16(lo);
+    const uint32_t n1 = code_length<15>(c1, L.lim_lit);
+    const uint32_t l1 = umin(n1, 15u);
+    const uint32_t i1 = umin(sorted_index(c1, l1, mem.lit_pair((int)l1)), (uint32_t)(kLitSyms - 1));
+    const uint32_t e = mem.lit_sym((int)i1);
+    uint64_t w = (((uint64_t)hi << 32) | lo) >> l1;
+    const uint32_t is_len = bit_mask(e, 15);                          // kEntryLength
+    const uint32_t eb = (e >> 8) & 7u & is_len;
+    const uint32_t not_end = ((e >> 14) & 1u) ^ 1u;                   // kEntryEnd: length 0, a literal: 1
+    const uint32_t length = pick(is_len, 3u + (e & 0xFFu) + low_bits((uint32_t)w, eb), not_end);
+    w >>= eb;
+    // distance (decoded whatever the symbol was; only looked at behind a length)
+    const uint32_t c2 = first16((uint32_t)w);
+    const uint32_t n2 = code_length<15>(c2, L.lim_dist);
+    const uint32_t l2 = umin(n2, 15u);
+    const uint32_t i2 = umin(sorted_index(c2, l2, mem.dist_pair((int)l2)), (uint32_t)(kDistSyms - 1));
+    const uint32_t d = mem.dist_sym((int)i2);
+    w >>= l2;                                                         // the distance's extra bits
+    const uint32_t half = d >> 1;
+    const uint32_t db = (half > 1u ? half : 1u) - 1u;
+    const uint32_t small = (uint32_t)((int32_t)(d - 4u) >> 31);       // d < 4
+    const uint32_t dbase = pick(small, d + 1u, 1u + ((2u | (d & 1u)) << db));
+    const uint32_t distance = dbase + low_bits((uint32_t)w, db);
+    Decoded r;
+    r.used = l1 + eb + ((l2 + db) & is_len);
+    r.bad = n1 > 15u || (e & kEntryBad) != 0 || (is_len != 0u && (n2 > 15u || d > 29u));
+    r.fail = r.bad || L.br.bp + r.used > L.br.limit_bits;
+    // more data than wanted: a match keeps what fits; the lane stops
+    const int room = L.out_cap - L.out_pos;
+    r.beyond = (int)length > room;
+    const uint32_t fits = umin(length, (uint32_t)(room > 0 ? room : 0));
+    r.length = fits;
+    r.is_end = (e & kEntryEnd) != 0;
+    r.token = pick(is_len, match_token(fits, distance), e & 0xFFu);
+    return r;
 }
 // A lane in any state but kDecode passes through unchanged.  Returns true with *token set when
 // a token was produced.
@@ -905,63 +683,9 @@ DBI_HD bool lane_decode_commit(Lane& L, const Decoded& r, uint32_t* token) {
     *token = r.token;
     return r.length > 0u;
 }
-// The front through the first-level tables.  Returns false where the token's literal/length code
-// - or, behind a length, its distance code - has no entry (it is longer than the table's index):
-// `r` is then not to be used and lane_decode_front decides.
-template <class Mem>
-DBI_HD bool lane_decode_fast(const Lane& L, const Mem& mem, Decoded& r) {
-    const BitReader& br = L.br;
-    uint32_t lo, hi;
-    br.window64(mem, lo, hi);
-    const uint32_t e = mem.lit_tab((int)(lo & ((1u << kLitBits) - 1u)));
-    const uint32_t l1 = e & 15u;
-    const uint32_t not_lit = bit_mask(e, 15);
-    const uint32_t ebf = (e >> 4) & 7u;                        // 6: a bad symbol, 7: end of block
-    const uint32_t is_len = not_lit & (uint32_t)((int32_t)(ebf - 6u) >> 31);       // ebf < 6
-    const uint32_t eb = ebf & is_len;
-    const uint32_t val = (e >> 7) & 0xFFu;
-    uint64_t w = (((uint64_t)hi << 32) | lo) >> l1;
-    // a literal: 1; end of block (or a bad symbol, refused below): 0
-    const uint32_t length = pick(is_len, 3u + val + low_bits((uint32_t)w, eb), (~not_lit) & 1u);
-    w >>= eb;
-    const uint32_t e2 = mem.dist_tab((int)((uint32_t)w & ((1u << kDistBits) - 1u)));
-    const uint32_t l2 = e2 & 15u;
-    const uint32_t d = e2 >> 4;
-    const uint32_t half = d >> 1;
-    const uint32_t db = (half > 1u ? half : 1u) - 1u;
-    const uint32_t small = (uint32_t)((int32_t)(d - 4u) >> 31);          // d < 4
-    const uint32_t dbase = pick(small, d + 1u, 1u + ((2u | (d & 1u)) << db));
-    const uint32_t distance = dbase + low_bits((uint32_t)(w >> l2), db);
-    const bool bad = (not_lit != 0u && ebf == 6u) || (is_len != 0u && d > 29u);
-    r.used = l1 + eb + ((l2 + db) & is_len);
-    r.bad = bad;
-    r.fail = bad || br.bp + r.used > br.limit_bits;
-    const int room = L.out_cap - L.out_pos;
-    r.beyond = (int)length > room;
-    const uint32_t fits = umin(length, (uint32_t)(room > 0 ? room : 0));
-    r.length = fits;
-    r.is_end = not_lit != 0u && ebf == 7u;
-    r.token = pick(is_len, match_token(fits, distance), val);
-    return l1 != 0u && (is_len == 0u || l2 != 0u);
-}
 template <class Mem>
 DBI_HD bool lane_decode(Lane& L, Mem& mem, uint32_t* token) {
-    Decoded r;
-    const bool fast = kTables && lane_decode_fast(L, mem, r);
-#if defined(DBI_CHECK_TABLES)
-    if (L.state == kDecode) dbi_table_answer(fast);
-    // (CPU harness: whenever the tables answer, they must answer what the canonical method does)
-    if (fast && L.state == kDecode) {
-        const Decoded s = lane_decode_front(L, mem);
-        // (a refused token's other fields are never looked at)
-        if (s.bad != r.bad || s.fail != r.fail ||
-            (!s.fail && (s.used != r.used || s.length != r.length || s.token != r.token ||
-                         s.is_end != r.is_end || s.beyond != r.beyond)))
-            dbi_table_mismatch();
-    }
-#endif
-    if (!fast) r = lane_decode_front(L, mem);
-    return lane_decode_commit(L, r, token);
+    return lane_decode_commit(L, lane_decode_front(L, mem), token);
 }
 
 }  // namespace dbi

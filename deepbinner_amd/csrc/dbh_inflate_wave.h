@@ -20,9 +20,9 @@
 //   output    token counts and byte counts are prefix-summed over the lanes, and every lane
 //             decodes its home a last time, writing its tokens where they belong.
 // Three decodes per token instead of one - on 64 lanes instead of one: the one-lane-per-stream
-// kernel (dbh_inflate_core.h) gives a container's 4,000 streams to 63 wavefronts for as long as the
-// LONGEST stream lasts (a 400 k-sample read: ~90 ms); here a stream is a wave's work for 3/64 of
-// that, and 4,000 waves fill the GPU.
+// kernel of rounds 3 and 4 (retired: HISTORY.md) gave a container's 4,000 streams to 63 wavefronts
+// for as long as the LONGEST stream lasts (a 400 k-sample read: ~90 ms); here a stream is a wave's
+// work for 3/64 of that, and 4,000 waves fill the GPU.
 //
 // The block headers and the two code builds are the serial code of the core, run by lane 0 (a
 // fifth of the kernel's instructions, one lane wide: the next thing to spread over the lanes);
@@ -41,10 +41,7 @@ namespace dbi {
 constexpr int kWaveLanes = 64;
 // a lane's home: 17 dwords - an ODD number, so that the lanes' first reads (and, as long as they
 // advance alike, all their reads) fall into different LDS banks
-#ifndef DBI_SUB_DWORDS
-#define DBI_SUB_DWORDS 17
-#endif
-constexpr int kSubDwords = DBI_SUB_DWORDS;
+constexpr int kSubDwords = 17;
 constexpr uint32_t kSubBits = 32u * kSubDwords;
 constexpr int kChunkDwords = kWaveLanes * kSubDwords;
 // a chunk begins at any bit of its first dword, and a lane's last token may begin at the last bit
@@ -59,7 +56,7 @@ struct Tok {
     bool bad, is_end;
 };
 
-// One token from the 64 bits (lo, hi) it begins with: the arithmetic of lane_decode_fronts
+// One token from the 64 bits (lo, hi) it begins with: the arithmetic of lane_decode_front
 // (dbh_inflate_core.h), without a lane's state.
 template <class Mem>
 DBI_HD Tok token_decode(uint32_t lo, uint32_t hi, const uint32_t (&lim_lit)[15],
@@ -102,28 +99,24 @@ DBI_HD Tok token_decode(uint32_t lo, uint32_t hi, const uint32_t (&lim_lit)[15],
 // The canonical decode above is ~60 vector instructions and two dependent LDS reads per code,
 // twice per token; a table indexed by the next kWaveLitBits / kWaveDistBits bits of the stream
 // answers in one read - {code length, meaning} - whenever the code is no longer than the index.
-// With one LANE per stream the tables did not pay (dbh_inflate_core.h: 64 copies of them fill a
-// CU's LDS, and one lane with a longer code sends its whole wave the canonical way); here a wave
+// With one LANE per stream the tables did not pay (HISTORY.md: 64 copies of them fill a CU's
+// LDS, and one lane with a longer code sends its whole wave the canonical way); here a wave
 // has ONE pair of tables, 4.5 KB, and its lanes fill them together behind every block header:
 // lane l decodes indices l, l + 64, .. the canonical way - no serial code at all.  A lane whose
 // code is longer than the index (kWaveLitBits = 11: about one token in 300 of a level-1 squiggle
 // stream) decodes canonically, the others wait for it: the same tokens either way, and the CPU
 // harness holds every table answer against the canonical one.
-#ifndef DBI_WAVE_LIT_BITS
-#define DBI_WAVE_LIT_BITS 11
-#endif
-#ifndef DBI_WAVE_DIST_BITS
-#define DBI_WAVE_DIST_BITS 8
-#endif
-constexpr int kWaveLitBits = DBI_WAVE_LIT_BITS, kWaveDistBits = DBI_WAVE_DIST_BITS;
-constexpr bool kWaveTables = DBI_WAVE_LIT_BITS > 0;
+constexpr int kWaveLitBits = 11, kWaveDistBits = 8;
+constexpr bool kWaveTables = kWaveLitBits > 0;
 static_assert(kWaveLitBits <= 15 && kWaveDistBits >= 1 && kWaveDistBits <= 15, "");
 constexpr int kWaveLitEntries = kWaveTables ? 1 << kWaveLitBits : 1;
 constexpr int kWaveDistEntries = kWaveTables ? 1 << kWaveDistBits : 1;
 
-// the entry of the literal/length table for the index k (the stream's next bits, lowest first):
-// lit_tab_entry's format (dbh_inflate_core.h), 0 = the code that begins so is longer than the index
-// (or does not exist: the canonical decoder refuses it)
+// the entry of the literal/length table for the index k (the stream's next bits, lowest first),
+// 16 bits: bits 0-3 code length, 4-6 extra bits of a length symbol (6 = symbols 286 / 287: never
+// valid, 7 = end of block), 7-14 the literal byte or the length's base - 3, bit 15 = not a literal;
+// 0 = the code that begins so is longer than the index (or does not exist: the canonical decoder
+// refuses it)
 template <class Mem>
 DBI_HD uint32_t wave_lit_entry(uint32_t k, const uint32_t (&lim_lit)[15], const Mem& mem) {
     const uint32_t c1 = first16(k);
@@ -147,8 +140,7 @@ DBI_HD uint32_t wave_dist_entry(uint32_t k, const uint32_t (&lim_dist)[15], cons
     return dist_tab_entry((int)mem.dist_sym((int)i2), (int)n2);
 }
 
-// One token through the tables (the arithmetic of lane_decode_fast, without a lane's state).
-// Returns false where a code has no entry: `t` is then not to be used.
+// One token through the tables.  Returns false where a code has no entry: `t` is then not to be used.
 template <class Mem>
 DBI_HD bool token_decode_tables(uint32_t lo, uint32_t hi, const Mem& mem, Tok& t) {
     const uint32_t e = mem.wave_lit_tab((int)(lo & (uint32_t)(kWaveLitEntries - 1)));
@@ -238,10 +230,7 @@ struct SubResult {
 // lane has more than kSubKeep tokens (a home is 544 bits).  `keep` is the END of the stream's own
 // token region (one slot per byte of output: far more than a stream's tokens, unless it is nearly
 // all literals or short) - keep_room says whether the chunk's tokens stay clear of it.
-#ifndef DBI_SUB_KEEP
-#define DBI_SUB_KEEP 96
-#endif
-constexpr int kSubKeep = DBI_SUB_KEEP;
+constexpr int kSubKeep = 96;
 constexpr int kKeepSlots = kSubKeep * kWaveLanes;
 // may the chunk that begins with n_tok tokens stored use the last kKeepSlots of cap_slots?
 DBI_HD bool keep_room(int n_tok, int64_t cap_slots) {

@@ -301,8 +301,8 @@ def inflate(comp, streams, out_bytes, streams_per_lane=0):
     """zlib streams inflated on the GPU (``dbh_inflate``: host buffers in and out - tests and
     tools; the classify path keeps everything on the device).  ``comp``: uint8 array holding the
     streams, ``streams``: array of INFLATE_STREAM records, ``out_bytes``: size of the output
-    buffer, ``streams_per_lane``: how many streams a lane of kernel 1 takes one after the other
-    (0 = 1; the order is the records') -> (output uint8 array, status int32 per stream,
+    buffer, ``streams_per_lane``: must be >= 0 and is otherwise ignored (it belonged to a retired
+    form of kernel 1) -> (output uint8 array, status int32 per stream,
     milliseconds the two kernels took)."""
     comp = np.ascontiguousarray(comp, dtype=np.uint8)
     streams = np.ascontiguousarray(streams, dtype=INFLATE_STREAM)

@@ -286,17 +286,13 @@ int dbh_inflate_workspace_bytes(int64_t total_out_bytes, int64_t n_streams, size
 /* comp_bytes = size of the compressed buffer (the decoder's read-ahead stops 64 bytes behind it).
  * Kernel 1 (Huffman codes -> tokens) gives every stream a wavefront of its own, in the order of
  * the records (the longest first, if the caller can: the launch then ends evenly).
- * streams_per_lane only matters to the kernel's older form (environment DEEPBINNER_INFLATE_KERNEL=
- * lane: one LANE per stream; 0 = 1): its lanes take streams off a counter - with one stream per
- * lane a launch is as wide as the streams are many and lasts as long as the longest of them; with
- * n, a launch 1/n as wide does the same work, and lasts no longer if the long streams come first
- * in the records and are long enough.
+ * streams_per_lane belonged to a retired form of kernel 1: it must be >= 0 and is otherwise ignored.
  * Kernel 2 (tokens -> bytes) reads the output buffer it writes (a match whose source lies more
  * than 8 KiB back is copied from the stream's own flushed output): out_dev must not be mapped
- * write-combined or read-protected.  DEEPBINNER_INFLATE_RESOLVE=rounds selects its older form
- * (the whole 32 KiB window in LDS).  The two kernels run as ONE launch, a pair of waves per
+ * write-combined or read-protected.  The two kernels run as ONE launch, a pair of waves per
  * stream, kernel 2 resolving a stream's tokens while kernel 1 still decodes it
- * (DEEPBINNER_INFLATE_PAIR=0: two launches). */
+ * (DEEPBINNER_INFLATE_PAIR=0: two launches).  The environment variables DEEPBINNER_INFLATE_KERNEL
+ * and DEEPBINNER_INFLATE_RESOLVE selected retired forms of the kernels and are no longer read. */
 int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
                     const dbh_inflate_stream* streams_dev, int64_t n_streams,
                     int64_t total_out_bytes, uint8_t* out_dev, void* workspace_dev,

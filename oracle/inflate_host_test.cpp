@@ -1,8 +1,9 @@
-// TEST INFRASTRUCTURE (oracle/): the GPU inflate's phase-1 decoder (deepbinner_amd/csrc/
-// dbh_inflate_core.h, the very header the kernels are compiled from) run on the CPU, one lane at a
-// time, with a sequential stand-in for phase 2 - so that tests/test_inflate.py can hold it to
-// zlib (Python's zlib module = the library libhdf5 inflates Signal chunks with) on the build box,
-// without a GPU.  Not part of the product; nothing in deepbinner_amd/ calls it.
+// TEST INFRASTRUCTURE (oracle/): the GPU inflate's phase-1 decoders (deepbinner_amd/csrc/
+// dbh_inflate_core.h and dbh_inflate_wave.h, the very headers the kernels are compiled from) run on
+// the CPU - the one-lane canonical decoder as the reference, the one-wave-per-stream form lane after
+// lane against it - with a sequential stand-in for phase 2 and a model of its kernel's schedule, so
+// that tests/test_inflate.py can hold them to zlib (Python's zlib module = the library libhdf5
+// inflates Signal chunks with) on the build box, without a GPU.  Not part of the product; nothing in deepbinner_amd/ calls it.
 //   cases file: u32 n; per case: u32 comp_bytes, u32 out_cap, bytes
 //   result file: per case: i32 status, i32 ended, i32 adler_ok, u32 n_tokens, u32 out_bytes, bytes
 #include <algorithm>
@@ -11,16 +12,10 @@
 #include <cstring>
 #include <vector>
 
-// the first-level decode tables (an experiment of round 5 the product does not ship: see
-// dbh_inflate_core.h) are compiled in here and every answer of theirs is held against the
-// canonical method's
+// every answer of the wave form's first-level decode tables (dbh_inflate_wave.h) is held against
+// the canonical method's
 #define DBI_CHECK_TABLES 1
-#ifndef DBI_LIT_BITS
-#define DBI_LIT_BITS 10
-#endif
 static void dbi_table_mismatch();
-static long g_answers[2];
-static void dbi_table_answer(bool fast) { ++g_answers[fast ? 1 : 0]; }
 static long g_wave_answers[2];
 static void dbi_wave_table_answer(bool fast) { ++g_wave_answers[fast ? 1 : 0]; }
 #include "../deepbinner_amd/csrc/dbh_inflate_core.h"
@@ -31,24 +26,18 @@ static void dbi_table_mismatch() {
 }
 
 struct HostMem {
-    static constexpr int kClTableBits = 7;            // (the code-length code's table: as the wave form has it)
-    uint8_t cl_tab_[128];
-    uint32_t cl_tab(int i) const { return cl_tab_[check(i, 128)]; }
-    void set_cl_tab(int i, uint32_t v) { cl_tab_[check(i, 128)] = (uint8_t)v; }
+    uint8_t cl_tab_[1 << dbi::kClTableBits];         // (the code-length code's table)
+    uint32_t cl_tab(int i) const { return cl_tab_[check(i, 1 << dbi::kClTableBits)]; }
+    void set_cl_tab(int i, uint32_t v) { cl_tab_[check(i, 1 << dbi::kClTableBits)] = (uint8_t)v; }
     uint32_t ring_[dbi::kRingStore], lit_pair_[16], dist_pair_[16];
     uint16_t lit_sym_[dbi::kLitSyms], cnt_[16];
     uint8_t dist_sym_[dbi::kDistSyms], lens_[dbi::kMaxLens];
-    uint16_t lit_tab_[1 << dbi::kLitBits], dist_tab_[1 << dbi::kDistBits];
     uint32_t stage_[dbi::kStageDwords];      // (the one-wave-per-stream decoder's chunk)
     uint16_t wave_lit_tab_[dbi::kWaveLitEntries], wave_dist_tab_[dbi::kWaveDistEntries];   // (its tables)
     uint32_t wave_lit_tab(int i) const { return wave_lit_tab_[check(i, dbi::kWaveLitEntries)]; }
     uint32_t wave_dist_tab(int i) const { return wave_dist_tab_[check(i, dbi::kWaveDistEntries)]; }
     uint32_t stage(int i) const { return stage_[check(i, dbi::kStageDwords)]; }
     void set_stage(int i, uint32_t v) { stage_[check(i, dbi::kStageDwords)] = v; }
-    uint32_t lit_tab(int i) const { return lit_tab_[check(i, 1 << dbi::kLitBits)]; }
-    void set_lit_tab(int i, uint32_t v) { lit_tab_[check(i, 1 << dbi::kLitBits)] = (uint16_t)v; }
-    uint32_t dist_tab(int i) const { return dist_tab_[check(i, 1 << dbi::kDistBits)]; }
-    void set_dist_tab(int i, uint32_t v) { dist_tab_[check(i, 1 << dbi::kDistBits)] = (uint16_t)v; }
     uint32_t ring(int r) const { return ring_[check(r, dbi::kRingStore)]; }
     void set_ring(int r, uint32_t v) { ring_[check(r, dbi::kRingStore)] = v; }
     int len(int i) const { return lens_[check(i, dbi::kMaxLens)]; }
@@ -78,7 +67,6 @@ struct HostMem {
 // rounds for the lanes whose predecessor ended elsewhere, the output pass.  Must leave the very
 // tokens and the very lane state of the one-lane decoder.
 static long g_wave_chunks, g_wave_rounds, g_wave_walks, g_wave_tokens, g_wave_kept_chunks;
-static long g_k2_steps, g_k2_rounds, g_k2_turns, g_k2_matches, g_k2_match_bytes, g_k2_tokens;
 static long g_k2p_steps, g_k2p_rounds, g_k2p_late, g_k2p_pre, g_k2p_far, g_k2p_short_steps;
 static void run_wave(const std::vector<uint8_t>& comp, uint32_t comp_bytes, uint32_t out_cap,
                      HostMem& mem, dbi::Lane& L, std::vector<uint32_t>& tokens) {
@@ -213,9 +201,6 @@ int main(int argc, char** argv) {
     if (!in || !out) return 2;
     uint32_t n_cases = 0;
     if (std::fread(&n_cases, 4, 1, in) != 1) return 2;
-    if (std::getenv("DBI_TABLE_STATS")) std::atexit([] {
-        std::fprintf(stderr, "tokens answered by the tables: %ld, sent the canonical way: %ld\n", g_answers[1], g_answers[0]);
-    });
     if (std::getenv("DBI_WAVE_STATS")) std::atexit([] {
         std::fprintf(stderr, "one wave per stream: tokens answered by the tables: %ld, sent the canonical way: %ld\n",
                      g_wave_answers[1], g_wave_answers[0]);
@@ -228,10 +213,6 @@ int main(int argc, char** argv) {
                      (double)g_wave_tokens / (64.0 * (double)std::max(1L, g_wave_chunks)));
     });
     if (std::getenv("DBI_K2_STATS")) std::atexit([] {
-        std::fprintf(stderr, "resolve schedule: %ld steps, %.1f tokens, %.1f matches (%.1f bytes each), %.2f rounds, "
-                             "%.2f four-byte turns per step\n", g_k2_steps, (double)g_k2_tokens / g_k2_steps,
-                     (double)g_k2_matches / g_k2_steps, (double)g_k2_match_bytes / std::max(1L, g_k2_matches),
-                     (double)g_k2_rounds / g_k2_steps, (double)g_k2_turns / g_k2_steps);
         std::fprintf(stderr, "second form: %ld steps (%ld cut short by their span), %.1f matches per step read at the "
                              "boundary (%.1f of them from the flushed output), %.2f late ones in %.2f rounds\n",
                      g_k2p_steps, g_k2p_short_steps, (double)g_k2p_pre / std::max(1L, g_k2p_steps),
@@ -264,8 +245,7 @@ int main(int argc, char** argv) {
                 if (dbi::lane_stored(L, mem, &token)) tokens.push_back(token);
                 continue;
             }
-            // (kDecode: the hot path as the kernel runs it - four tokens, then the checkpoint
-            // that keeps the input ring filled)
+            // (kDecode: four tokens, then the checkpoint that keeps the input ring filled)
             for (int k = 0; k < 4; ++k)
                 if (dbi::lane_decode(L, mem, &token)) tokens.push_back(token);
             L.br.checkpoint(mem);
@@ -301,92 +281,6 @@ int main(int argc, char** argv) {
                 } else {
                     bytes.push_back((uint8_t)t);
                 }
-            }
-        }
-        // ... and as the resolve kernel SCHEDULES it (dbh_inflate.hip: inflate_resolve_kernel):
-        // a ring of exactly 32 KiB, 64 tokens per step, all literals of a step first, then the
-        // matches in rounds (whoever reads nothing that is still to be written goes, four bytes
-        // per lockstep turn, the loads of a turn before its stores), steps with a ring hazard in
-        // token order, whole 256-byte pieces flushed after every step.  Must give the same bytes.
-        if (status == dbi::kOk) {
-            std::vector<uint8_t> ring(dbi::kWindowRing, 0), model;
-            auto at = [&](long p) -> uint8_t& { return ring[(size_t)(p & (dbi::kWindowRing - 1))]; };
-            long pos = 0, flushed = 0;
-            const int n_tok = (int)tokens.size();
-            for (int t0 = 0; t0 < n_tok; t0 += dbi::kStepTokens) {
-                const int lanes = std::min(dbi::kStepTokens, n_tok - t0);
-                long my[64];
-                int len[64], dist[64];
-                bool is_match[64];
-                long end = pos;
-                for (int l = 0; l < lanes; ++l) {
-                    const uint32_t t = tokens[t0 + l];
-                    is_match[l] = (t & dbi::kMatchFlag) != 0;
-                    len[l] = is_match[l] ? (int)(t & 0x1FF) : 1;
-                    dist[l] = (int)((t >> 9) & 0x7FFF) + 1;
-                    my[l] = end;
-                    end += len[l];
-                }
-                ++g_k2_steps;
-                g_k2_tokens += lanes;
-                for (int l = 0; l < lanes; ++l)
-                    if (is_match[l]) {
-                        ++g_k2_matches;
-                        g_k2_match_bytes += len[l];
-                    }
-                bool hazard = false;
-                for (int l = 0; l < lanes; ++l)
-                    hazard = hazard || (is_match[l] && dbi::ring_hazard(dist[l], (int)my[l], (int)end));
-                if (hazard) {
-                    for (int l = 0; l < lanes; ++l) {
-                        if (!is_match[l]) at(my[l]) = (uint8_t)tokens[t0 + l];
-                        else for (int k = 0; k < len[l]; ++k) at(my[l] + k) = at(my[l] - dist[l] + k);
-                    }
-                } else {
-                    for (int l = 0; l < lanes; ++l)
-                        if (!is_match[l]) at(my[l]) = (uint8_t)tokens[t0 + l];
-                    bool waiting[64];
-                    for (int l = 0; l < lanes; ++l) waiting[l] = is_match[l];
-                    for (;;) {
-                        int first_lane = -1;
-                        for (int l = 0; l < lanes && first_lane < 0; ++l)
-                            if (waiting[l]) first_lane = l;
-                        if (first_lane < 0) break;
-                        const long first = my[first_lane];
-                        bool go[64];
-                        int longest = 0;
-                        for (int l = 0; l < lanes; ++l) {
-                            const long src = my[l] - dist[l];
-                            go[l] = waiting[l] && src + std::min(len[l], dist[l]) <= first;
-                            if (go[l]) longest = std::max(longest, len[l]);
-                        }
-                        ++g_k2_rounds;
-                        g_k2_turns += (longest + 3) / 4;
-                        for (int k = 0; k < longest; k += 4) {
-                            uint8_t b[64][4];
-                            for (int l = 0; l < lanes; ++l)
-                                if (go[l] && k < len[l])
-                                    for (int j = 0; j < 4; ++j)
-                                        b[l][j] = at(my[l] - dist[l] + (k + j) % dist[l]);
-                            for (int l = 0; l < lanes; ++l)
-                                if (go[l] && k < len[l])
-                                    for (int j = 0; j < 4 && k + j < len[l]; ++j)
-                                        at(my[l] + k + j) = b[l][j];
-                        }
-                        for (int l = 0; l < lanes; ++l) waiting[l] = waiting[l] && !go[l];
-                    }
-                }
-                pos = end;
-                while (pos - flushed >= 256) {
-                    for (int k = 0; k < 256; ++k) model.push_back(at(flushed + k));
-                    flushed += 256;
-                }
-            }
-            for (long k = flushed; k < pos; ++k) model.push_back(at(k));
-            if (model != bytes) {
-                std::fprintf(stderr, "case %u: the resolve kernel's schedule gives other bytes than "
-                                     "the tokens in order\n", c);
-                return 4;
             }
         }
         // ... and as the SECOND form schedules it (inflate_resolve_pre_kernel, what runs; dbh_inflate_

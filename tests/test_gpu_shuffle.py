@@ -1,6 +1,6 @@
 """HDF5's shuffle filter undone on the GPU: streams of mode DBH_INFLATE_ZLIB_SHUFFLE (u32 LE N, a
 zlib stream of the N shuffled bytes) and DBH_INFLATE_STORED_SHUFFLE (u32 LE N, the N shuffled
-bytes) beside zlib, stored and VBZ streams in one launch, under every form of the inflate kernels,
+bytes) beside zlib, stored and VBZ streams in one launch, under both forms of the inflate kernels,
 held against NumPy bit for bit.  Through dbh_inflate_dev the output buffer is filled with a
 sentinel first: every byte outside the streams' regions must still hold it."""
 
@@ -26,18 +26,17 @@ REFUSED = 32
 SENTINEL = 0xA5
 START, END = 'EXP-NBD103_read_starts', 'EXP-NBD103_read_ends'
 FILTER_WARNING = 'Warning: skipping reads whose signal is compressed with a filter'
-# the four forms of the inflate kernels: pair / two launches, wave / lane, resolve pre / rounds
+# both forms of the inflate kernels: one launch of a pair of waves per stream / two launches.
+# 'lane_rounds' exports the two retired switches (it once selected the older kernels they named):
+# nothing reads them any more, so it must be the pair, with the same bytes and statuses
 FORMS = {'pair': {},
          'two_launches': {'DEEPBINNER_INFLATE_PAIR': '0'},
-         'lane': {'DEEPBINNER_INFLATE_KERNEL': 'lane'},
-         'rounds': {'DEEPBINNER_INFLATE_RESOLVE': 'rounds'},
          'lane_rounds': {'DEEPBINNER_INFLATE_KERNEL': 'lane', 'DEEPBINNER_INFLATE_RESOLVE': 'rounds'}}
 SIZES = (2, 4, 6, 30, 32, 34, 1022, 1024, 1026, 2046, 2048, 2050, 6250, 65538, 400000)
 
 
 def set_form(monkeypatch, form):
-    for name in ('DEEPBINNER_INFLATE_PAIR', 'DEEPBINNER_INFLATE_KERNEL', 'DEEPBINNER_INFLATE_RESOLVE'):
-        monkeypatch.delenv(name, raising=False)
+    monkeypatch.delenv('DEEPBINNER_INFLATE_PAIR', raising=False)
     for name, value in FORMS[form].items():
         monkeypatch.setenv(name, value)
 

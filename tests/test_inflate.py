@@ -5,7 +5,8 @@ to zlib - Python's zlib module, i.e. the library libhdf5 inflates fast5 Signal c
 same accept / reject decision for damaged ones.
 
 CPU part: the decoder core compiled for the host (oracle/_build/inflate_host_test, built by
-oracle/Makefile from the very header the kernels use), one lane at a time.
+oracle/Makefile from the very headers the kernels use): the one-lane canonical decoder, and the
+one-wavefront-per-stream form held to it.
 GPU part (`-m gpu`): the kernels through the C ABI (dbh_inflate), whole batches of streams.
 """
 import os
@@ -67,10 +68,10 @@ def valid_cases():
                 bytes(rng.integers(0, 4, 50000, dtype=np.uint8)),              # tiny alphabet
                 b'\x00' * 100000,                                              # RLE, distance 1
                 real[2][:20000] + bytes(33000) + real[2][:20000]]              # distance ~ 32 K
-    # long matches at distances near the window size: a step of the resolve kernel (64 tokens, up
-    # to 16.5 KB) then wraps around its 32 KiB ring onto bytes its own first matches still read
-    # (dbh_inflate_core.h: ring_hazard) - 258-byte matches back to back, and far matches followed
-    # by literals inside one step
+    # long matches at distances near the window size: 64 tokens of them span up to 16.5 KB, more
+    # than the resolve kernel's ring holds (dbh_inflate_core.h: kStepSpan cuts such a step short, and
+    # their sources lie in the flushed output) - 258-byte matches back to back, and far matches
+    # followed by literals inside one step
     far = rng.integers(0, 256, 32000, dtype=np.uint8).tobytes()
     payloads += [far + far, far + far[:774] + b'Q' + far[1000:1600] + b'literal' + far[5000:9000],
                  far[:32768 - 3] + far[:20000] + far[100:400],
@@ -176,8 +177,8 @@ def test_decoder_core_matches_zlib_on_valid_streams(tmp_path):
 
 @needs_harness
 def test_resolve_schedules_on_patchwork_streams(tmp_path):
-    """The harness's models of both forms of kernel 2 (which copy of a byte every read sees) on
-    streams built for them: the tokens resolved as the kernels schedule them give zlib's bytes."""
+    """The harness's model of kernel 2's schedule (which copy of a byte every read sees) on
+    streams built for it: the tokens resolved as the kernel schedules them give zlib's bytes."""
     cases = patchwork_cases()
     results = run_harness([(stream, cap) for stream, cap, _ in cases], tmp_path)
     for k, ((stream, cap, want), (status, ended, adler_ok, n_tokens, got)) in enumerate(zip(cases, results)):
@@ -269,17 +270,13 @@ def pack_streams(hip, cases):
     return np.frombuffer(bytes(comp) if comp else b'\0', dtype=np.uint8), records, out_at, places
 
 
-@pytest.fixture(params=['lane+pre', 'wave+pre', 'wave+rounds', 'wave+pre+pair'])
+@pytest.fixture(params=['wave+pre', 'wave+pre+pair'])
 def kernel1(request, monkeypatch):
-    """Both forms of kernel 1 - one lane per stream, one wavefront per stream - and both forms of
-    kernel 2 - short matches read at the step boundary, every match through the rounds - as two
-    launches, and the default forms as ONE launch of a pair of waves per stream, kernel 2
-    resolving a stream's tokens while kernel 1 still decodes it (dbh_inflate.hip) - whichever of
-    them are the defaults."""
-    parts = request.param.split('+')
-    monkeypatch.setenv('DEEPBINNER_INFLATE_KERNEL', parts[0])
-    monkeypatch.setenv('DEEPBINNER_INFLATE_RESOLVE', parts[1])
-    monkeypatch.setenv('DEEPBINNER_INFLATE_PAIR', '1' if 'pair' in parts else '0')
+    """Both forms in which the two kernels run (dbh_inflate.hip): as two launches - kernel 1, one
+    wavefront per stream, then kernel 2, short matches read at the step boundary - and as ONE
+    launch of a pair of waves per stream, kernel 2 resolving a stream's tokens while kernel 1
+    still decodes it (the default)."""
+    monkeypatch.setenv('DEEPBINNER_INFLATE_PAIR', '1' if 'pair' in request.param else '0')
     return request.param
 
 
@@ -296,8 +293,7 @@ def test_gpu_inflate_matches_zlib(hip, kernel1):
               (raw, 100, hip.INFLATE_STORED), (b'', 10, hip.INFLATE_STORED)]
     want += [raw, raw + bytes(77), raw[:100], bytes(10)]
     comp, records, out_bytes, places = pack_streams(hip, batch)
-    # one stream per lane, and lanes that take several one after the other (each at the first
-    # block boundary behind the end of its stream - while its neighbours are inside theirs)
+    # (streams_per_lane belonged to a retired kernel: any value >= 0 is accepted and changes nothing)
     for per_lane in (0, 3, 8, 1000):
         out, status, ms = hip.inflate(comp, records, out_bytes, per_lane)
         assert (status == 0).all(), (per_lane, np.nonzero(status)[0][:10])
@@ -356,5 +352,31 @@ def test_gpu_inflate_a_container_of_reads(hip, kernel1):
     assert (status == 0).all()
     for (at, cap), j in zip(places, picks):
         assert out[at:at + cap].tobytes() == pool[j]
-    print('gpu inflate (kernel 1: one %s per stream): 4,000 streams, %.1f MB out, %.2f ms in the kernels = %.0f streams/s, '
+    print('gpu inflate (%s): 4,000 streams, %.1f MB out, %.2f ms in the kernels = %.0f streams/s, '
           '%.2f GB/s of output' % (kernel1, out_bytes / 1e6, ms, 4000 / (ms * 1e-3), out_bytes / ms / 1e6))
+
+
+@pytest.mark.gpu
+def test_gpu_inflate_ignores_the_retired_switches(hip, monkeypatch):
+    """DEEPBINNER_INFLATE_KERNEL=lane and DEEPBINNER_INFLATE_RESOLVE=rounds selected kernels that no
+    longer exist.  A deployment that still exports them gets the shipped kernels and the right
+    bytes, not an error: the same bytes and statuses as with both unset."""
+    cases = valid_cases()[:64]
+    batch = [(stream, cap, hip.INFLATE_ZLIB) for stream, cap, _ in cases]
+    want = [w for _, _, w in cases]
+    raw = squiggle(np.random.default_rng(3), 5000)
+    batch += [(raw, len(raw), hip.INFLATE_STORED), (raw, len(raw) + 77, hip.INFLATE_STORED),
+              (raw, 100, hip.INFLATE_STORED), (b'', 10, hip.INFLATE_STORED)]
+    want += [raw, raw + bytes(77), raw[:100], bytes(10)]
+    comp, records, out_bytes, places = pack_streams(hip, batch)
+    monkeypatch.delenv('DEEPBINNER_INFLATE_PAIR', raising=False)
+    monkeypatch.setenv('DEEPBINNER_INFLATE_KERNEL', 'lane')
+    monkeypatch.setenv('DEEPBINNER_INFLATE_RESOLVE', 'rounds')
+    out_set, status_set, _ = hip.inflate(comp, records, out_bytes)
+    monkeypatch.delenv('DEEPBINNER_INFLATE_KERNEL')
+    monkeypatch.delenv('DEEPBINNER_INFLATE_RESOLVE')
+    out_unset, status_unset, _ = hip.inflate(comp, records, out_bytes)
+    assert (status_set == status_unset).all() and (status_unset == 0).all()
+    assert out_set.tobytes() == out_unset.tobytes()
+    for k, ((at, cap), w) in enumerate(zip(places, want)):
+        assert out_unset[at:at + cap].tobytes() == w + bytes(cap - len(w)), (k, len(w), cap)
