@@ -139,6 +139,25 @@ struct SignalInfo {
     std::vector<Filter> filters;
 };
 
+// How the raw loaders (f5_load_batch_raw_ex, f5_stream_open_raw_ex) hand a Signal out, from their
+// arguments (host_inflate_above, flags):
+struct RawOptions {
+    int64_t zlib_above = 0;     // deflate streams longer than this many bytes are the host's; 0: none
+    int host_share = 0;         // ... or the longest ones holding this share (per cent) of the bytes
+    bool vbz_zstd_gpu = false;  // F5_RAW_FLAG_VBZ_ZSTD_GPU: VBZ chunks with a zstd stage go out as stored
+    bool shuffle_gpu = false;   // F5_RAW_FLAG_SHUFFLE_GPU: shuffled chunks go out as stored
+};
+// host_inflate_above > 0: a length in bytes; < 0: minus the host's share in per cent.  false: a flag
+// this reader does not know.
+bool raw_options(int64_t host_inflate_above, unsigned flags, RawOptions* o) {
+    if (flags & ~(unsigned)(F5_RAW_FLAG_VBZ_ZSTD_GPU | F5_RAW_FLAG_SHUFFLE_GPU)) return false;
+    o->zlib_above = host_inflate_above > 0 ? host_inflate_above : 0;
+    o->host_share = host_inflate_above < 0 ? (int)std::min<int64_t>(100, -host_inflate_above) : 0;
+    o->vbz_zstd_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
+    o->shuffle_gpu = (flags & F5_RAW_FLAG_SHUFFLE_GPU) != 0;
+    return true;
+}
+
 // libdeflate, when the system has it (looked up at run time: the image ships libdeflate.so.0 but
 // no header): its whole-buffer inflate is 2-3 times as fast as zlib's streaming one, and inflating
 // is most of what loading a read costs.  Same input (RFC 1950 streams, which is what the HDF5
@@ -302,8 +321,9 @@ struct ChunkCache {
     std::vector<uint8_t> data, scratch;
     std::vector<uint8_t> vbz;           // a VBZ chunk's streamvbyte bytes (zstd stage undone)
     uint64_t addr = ~0ull, bytes = 0;
-    const void* owner = nullptr;        // the file the cached chunk came from (addresses repeat
-                                        // from file to file: a thread may serve several)
+    uint64_t owner = 0;                 // the file the cached chunk came from, by Fast5's serial
+                                        // number (chunk addresses repeat from file to file, and so
+                                        // do the addresses of the Fast5 objects themselves)
     z_stream zs;
     bool zs_ready = false;
     void* fast_inflater = nullptr;      // libdeflate's, when there is one
@@ -460,14 +480,14 @@ class Fast5 {
     };
     enum { kZlib = 0, kStored = 1, kHostDecode = 2, kZeros = 3, kVbz = 4 };
 
-    // zlib_above: deflate streams longer than this many bytes are left to the host (a lane of the
+    // o.zlib_above: deflate streams longer than this many bytes are left to the host (a lane of the
     // GPU decoder walks ONE stream: a stream ten times the usual length holds its wave ten times
     // as long, while a CPU core inflates it in a millisecond); <= 0: no limit.
-    // vbz_zstd_gpu (F5_RAW_FLAG_VBZ_ZSTD_GPU): VBZ chunks with a zstd stage are handed on as stored.
-    // shuffle_gpu (F5_RAW_FLAG_SHUFFLE_GPU): whole chunks of shuffle (element size 2) + deflate,
-    // or of shuffle alone, with or without fletcher32 behind, go out as stored, a prefix in front.
-    void signal_pieces(const SignalInfo& s, int64_t zlib_above, std::vector<RawPiece>* out,
-                       bool vbz_zstd_gpu = false, bool shuffle_gpu = false) const {
+    // o.vbz_zstd_gpu: VBZ chunks with a zstd stage are handed on as stored.
+    // o.shuffle_gpu: whole chunks of shuffle (element size 2) + deflate, or of shuffle alone, with
+    // or without fletcher32 behind, go out as stored, a prefix in front.
+    // (o.host_share is the loaders' business: it is taken over a whole batch.)
+    void signal_pieces(const SignalInfo& s, const RawOptions& o, std::vector<RawPiece>* out) const {
         out->clear();
         if (s.n <= 0) return;
         RawPiece p;
@@ -549,7 +569,7 @@ class Fast5 {
                 const uint64_t h = std::min<uint64_t>(nbytes, sizeof(head));
                 read_bytes(start, h, head);
                 const uint32_t size = vbz_original_size(head, (size_t)h, (size_t)s.chunk_elems * 2);
-                if (q.vbz_zstd && vbz_zstd_gpu) {
+                if (q.vbz_zstd && o.vbz_zstd_gpu) {
                     (void)vbz_frame_size_header(head, (size_t)h, size);     // (sized and checked)
                     q.vbz_zstd = false;                // nothing for the host to undo
                     q.vbz_gpu = true;
@@ -557,7 +577,7 @@ class Fast5 {
                 } else {
                     q.vbz_bytes = q.vbz_zstd ? 4 + vbz_frame_size(head, (size_t)h, size) : nbytes;
                 }
-            } else if (shuffle_gpu && shuffle_i16 && q.count == s.chunk_elems && applied[0] == 2 &&
+            } else if (o.shuffle_gpu && shuffle_i16 && q.count == s.chunk_elems && applied[0] == 2 &&
                        ((n_applied == 2 && applied[1] == 1) ||
                         (n_applied == 3 && applied[1] == 1 && applied[2] == 3 && nbytes >= 4))) {
                 // shuffle + deflate of a chunk that is wanted WHOLE (of a partial one the wanted
@@ -566,7 +586,7 @@ class Fast5 {
                 q.kind = kZlib;
                 q.prefix = 4;
                 q.nbytes = n_applied == 3 ? nbytes - 4 : nbytes;
-            } else if (shuffle_gpu && shuffle_i16 && q.count == s.chunk_elems && applied[0] == 2 &&
+            } else if (o.shuffle_gpu && shuffle_i16 && q.count == s.chunk_elems && applied[0] == 2 &&
                        (n_applied == 1 || (n_applied == 2 && applied[1] == 3 && nbytes >= 4)) &&
                        nbytes - (n_applied == 2 ? 4 : 0) == (uint64_t)q.count * 2) {
                 q.kind = kStored;                  // shuffle alone: the two planes as they are
@@ -575,7 +595,7 @@ class Fast5 {
             } else {
                 q.kind = kHostDecode;              // shuffle, or an order not seen in the field
             }
-            if (q.kind == kZlib && zlib_above > 0 && (int64_t)q.nbytes > zlib_above) {
+            if (q.kind == kZlib && o.zlib_above > 0 && (int64_t)q.nbytes > o.zlib_above) {
                 q.kind = kHostDecode;
                 q.prefix = 0;
             }
@@ -685,12 +705,17 @@ class Fast5 {
     // a piece the host decodes itself -> its samples' bytes at dst (count * 2 of them)
     void decode_piece(const SignalInfo& s, const RawPiece& p, uint8_t* dst, ChunkCache* cache) const {
         decode_chunk(s, p.chunk_addr, p.chunk_bytes, p.mask, cache);
-        cache->owner = nullptr;                    // (not a chunk read_signal may reuse blindly)
+        cache->owner = 0;                          // (not a chunk read_signal may reuse blindly)
         std::memcpy(dst, cache->data.data(), (size_t)p.count * 2);
     }
 
   private:
     static constexpr uint64_t kReadWhole = 8u << 20;   // files up to 8 MiB are read, larger mapped
+    static uint64_t next_serial() {
+        static std::atomic<uint64_t> last{0};
+        return ++last;
+    }
+    const uint64_t serial_ = next_serial();            // never 0, never given twice (ChunkCache)
     int fd_ = -1;
     bool mapped_ = false;
     std::vector<uint8_t> owned_;
@@ -1249,7 +1274,7 @@ class Fast5 {
             s.filters[0].id != 1)
             return false;
         std::vector<RawPiece> pieces;
-        signal_pieces(s, 0, &pieces);
+        signal_pieces(s, RawOptions(), &pieces);
         if (pieces.size() != 1 || pieces[0].kind != kZlib || pieces[0].mask != 0 ||
             pieces[0].count != s.n)
             return false;
@@ -1503,10 +1528,10 @@ class Fast5 {
         if (a >= z) return;
         // the last chunk inflated stays around: a read stored as ONE chunk (common) is asked
         // for twice, once per end, and deflate cannot be entered in the middle
-        if (cache->owner != this || cache->addr != addr || cache->bytes != nbytes) {
+        if (cache->owner != serial_ || cache->addr != addr || cache->bytes != nbytes) {
             cache->addr = ~0ull;
             decode_chunk(s, addr, nbytes, mask, cache);
-            cache->owner = this;
+            cache->owner = serial_;
             cache->addr = addr;
             cache->bytes = nbytes;
         }
@@ -2304,6 +2329,190 @@ struct f5_batch {
     std::vector<f5_raw_stream> streams;
 };
 
+// ---------------------------------------------------------------------------------------------
+// What the loaders share.  Each of them (f5_load_batch, f5_load_batch_raw_ex, f5_load_reads, the
+// packed and the raw f5_stream) deals the work out to its threads in its own way; what is done to
+// a read, a range of reads or a batch is written here, once.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// a batch of n reads, none of them loaded yet
+f5_batch* new_batch(int64_t n) {
+    std::unique_ptr<f5_batch> batch(new f5_batch);
+    batch->offsets.assign((size_t)n + 1, 0);
+    batch->status.assign((size_t)n, F5_ERR_OPEN);
+    batch->read_ids.assign((size_t)n * F5_READ_ID_MAX, 0);
+    return batch.release();
+}
+
+// read i of the batch could not be loaded: no id, and why
+void fail_read(f5_batch* batch, int64_t i, int rc) {
+    std::memset(&batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
+    batch->status[(size_t)i] = rc;
+}
+
+// ---- packed batches ---------------------------------------------------------------------------
+// The head/tail rule: with keep > 0 a read longer than 2 * keep gives its first and its last `keep`
+// samples only (windows are cut from those); how many samples a read of n gives
+int64_t kept_length(int64_t n, int64_t keep) { return keep > 0 && n > 2 * keep ? 2 * keep : n; }
+
+// ... and those samples, kept_length(s.n, keep) of them at dst: one whole read, or the two halves
+void read_ends(Fast5& file, const SignalInfo& s, int64_t keep, int16_t* dst, ChunkCache* cache) {
+    if (kept_length(s.n, keep) < s.n) {
+        file.read_signal(s, 0, keep, dst, cache);
+        file.read_signal(s, s.n - keep, keep, dst + keep, cache);
+    } else {
+        file.read_signal(s, 0, s.n, dst, cache);
+    }
+}
+
+// The passes over reads first .. first + batch size of ONE file (f5_load_reads, f5_stream), each
+// for places [a, b) of the batch.  Resolve: id, status and kept length of every read, each touched
+// by one thread only; also(read, i) is what the caller needs of a resolved read besides.
+template <class Also>
+void resolve_reads(Fast5& file, int64_t first, int64_t keep, f5_batch* batch,
+                   std::vector<int64_t>* lengths, int64_t a, int64_t b, Also&& also) {
+    for (int64_t i = a; i < b; ++i)
+        batch->status[(size_t)i] = guarded([&] {
+            const ReadEntry& r = file.read(first + i);
+            (*lengths)[(size_t)i] = kept_length(r.signal.n, keep);
+            also(r, i);
+            copy_read_id(r.read_id, &batch->read_ids[(size_t)i * F5_READ_ID_MAX]);
+        });
+}
+
+// Between the passes: the offsets, a prefix sum that skips the reads that failed -> all samples
+int64_t place_reads(f5_batch* batch, const std::vector<int64_t>& lengths) {
+    const size_t n = batch->status.size();
+    int64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        batch->offsets[i] = total;
+        total += batch->status[i] == F5_OK ? lengths[i] : 0;
+    }
+    batch->offsets[n] = total;
+    return total;
+}
+
+// Inflate into place: a read whose damage shows only now keeps its range, zero filled
+void inflate_reads(Fast5& file, int64_t first, int64_t keep, f5_batch* batch,
+                   const std::vector<int64_t>& lengths, int64_t a, int64_t b, ChunkCache* cache) {
+    for (int64_t i = a; i < b; ++i) {
+        if (batch->status[(size_t)i] != F5_OK) continue;
+        int16_t* dst = batch->samples.data() + batch->offsets[(size_t)i];
+        const int rc = guarded([&] { read_ends(file, file.read(first + i).signal, keep, dst, cache); });
+        if (rc == F5_OK) continue;
+        std::memset(dst, 0, (size_t)lengths[(size_t)i] * 2);
+        fail_read(batch, i, rc);
+    }
+}
+
+// ---- raw batches ------------------------------------------------------------------------------
+// a raw stream's weight in the order of the records: the bytes of its deflate data (a shuffled
+// deflate stream is one), 0 for everything else
+int64_t deflate_weight(const f5_raw_stream& x) {
+    return x.mode == F5_RAW_ZLIB || x.mode == F5_RAW_ZLIB_SHUFFLE ? x.comp_bytes : 0;
+}
+void put_u32le(uint8_t* dst, uint32_t v) {
+    for (int k = 0; k < 4; ++k) dst[k] = (uint8_t)(v >> (8 * k));
+}
+// HDF5's shuffle of 2-byte elements undone in place (as decode_chunk does it): low bytes, then high
+void unshuffle_i16(std::vector<uint8_t>* bytes, std::vector<uint8_t>* scratch) {
+    const size_t n = bytes->size() / 2;
+    scratch->assign(bytes->begin(), bytes->end());
+    for (size_t k = 0; k < n; ++k) {
+        (*scratch)[2 * k] = (*bytes)[k];
+        (*scratch)[2 * k + 1] = (*bytes)[n + k];
+    }
+    bytes->swap(*scratch);
+}
+
+// What a piece occupies in a raw batch's byte buffer: its stored bytes behind its prefix - of
+// unfiltered data no more than is wanted -, a VBZ chunk with the host's stage undone, nothing for
+// a chunk that was never written, and for a piece the host decodes (kHostDecode) its samples
+int64_t raw_piece_bytes(const Fast5::RawPiece& p) {
+    const int64_t wanted = p.count * 2;
+    return p.kind == Fast5::kZlib     ? p.prefix + (int64_t)p.nbytes
+           : p.kind == Fast5::kStored ? p.prefix + std::min<int64_t>((int64_t)p.nbytes, wanted)
+           : p.kind == Fast5::kZeros  ? 0
+           : p.kind == Fast5::kVbz    ? (int64_t)p.vbz_bytes
+                                      : wanted;
+}
+
+// The pieces of read `read` get their places in the byte buffer, from byte *at on, and their
+// records: where the bytes lie, where the samples go, how the decoder is to take them
+void place_pieces(f5_batch* batch, int64_t read, std::vector<Fast5::RawPiece>* pieces, int64_t* at) {
+    for (Fast5::RawPiece& p : *pieces) {
+        p.comp_offset = *at;
+        p.comp_bytes = raw_piece_bytes(p);
+        *at += p.comp_bytes;
+        f5_raw_stream rec;
+        rec.comp_offset = p.comp_offset;
+        rec.comp_bytes = p.comp_bytes;
+        rec.out_offset = (batch->offsets[(size_t)read] + p.first) * 2;
+        rec.out_bytes = p.count * 2;
+        rec.mode = p.kind == Fast5::kZlib  ? (p.prefix ? F5_RAW_ZLIB_SHUFFLE : F5_RAW_ZLIB)
+                   : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
+                   : p.kind == Fast5::kStored && p.prefix ? F5_RAW_STORED_SHUFFLE
+                                                          : F5_RAW_STORED;
+        rec.reserved = (int32_t)read;          // which read of the batch it belongs to
+        batch->streams.push_back(rec);
+    }
+}
+
+// All pieces placed, `at` bytes of them: the records go out longest deflate stream first, so that
+// the lanes of a wave of the GPU decoder - which step together, one stream each - get streams of
+// one length; the byte buffer is sized (in int16 units), 64 readable zero bytes behind the last
+// stream, since the decoder fetches ahead of itself
+void finish_raw_batch(f5_batch* batch, int64_t at) {
+    std::stable_sort(batch->streams.begin(), batch->streams.end(),
+                     [](const f5_raw_stream& x, const f5_raw_stream& y) {
+                         return deflate_weight(x) > deflate_weight(y);
+                     });
+    batch->comp_bytes = at;
+    batch->comp.resize((size_t)(at + 64 + 1) / 2);
+    std::memset(reinterpret_cast<uint8_t*>(batch->comp.data()) + at, 0, 64);
+}
+
+// The host's zstd stage of a VBZ piece whose streamvbyte stage is the GPU's: the chunk as stored
+// (p.nbytes of it) -> at dst its 4 header bytes and, behind them, the frame's content
+void vbz_host_stage(const uint8_t* chunk, const Fast5::RawPiece& p, uint8_t* dst) {
+    std::memcpy(dst, chunk, 4);
+    vbz_unzstd(chunk, (size_t)p.nbytes, dst + 4, p.vbz_bytes - 4);
+}
+
+// One file of f5_load_batch_raw_ex between its passes
+struct StagedRead {
+    std::vector<Fast5::RawPiece> pieces;       // file_off = offset into `bytes` from here on
+    std::string bytes;
+    int64_t samples = 0;
+};
+
+// The host's share of a batch of ONE-READ files: the deflate streams of the whole batch one by
+// one, longest first, until they hold `share` per cent of its compressed bytes.  Unlike the
+// container's rule (f5_stream::take_host_share) it counts streams, not a length - of several
+// streams of one length some may stay the GPU's - and knows no exception for long streams.  A
+// shuffled stream keeps its prefix: pass 2 inflates the staged bytes and unshuffles them itself.
+void take_host_share(std::vector<StagedRead>* staged, int share) {
+    std::vector<std::pair<uint64_t, Fast5::RawPiece*>> streams;
+    uint64_t total = 0;
+    for (StagedRead& st : *staged)
+        for (Fast5::RawPiece& p : st.pieces)
+            if (p.kind == Fast5::kZlib) {
+                streams.push_back({p.nbytes, &p});
+                total += p.nbytes;
+            }
+    std::sort(streams.begin(), streams.end(),
+              [](const auto& a, const auto& b) { return a.first > b.first; });
+    uint64_t taken = 0;
+    for (const auto& e : streams) {
+        if (taken * 100 >= total * (uint64_t)share) break;
+        e.second->kind = Fast5::kHostDecode;
+        taken += e.first;
+    }
+}
+
+}  // namespace
+
 extern "C" {
 
 const char* f5_version(void) { return "deepbinner_fast5 0.1"; }
@@ -2387,10 +2596,7 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
     *out = nullptr;
     f5_batch* batch = nullptr;
     try {
-        batch = new f5_batch;
-        batch->offsets.assign((size_t)n_files + 1, 0);
-        batch->status.assign((size_t)n_files, F5_ERR_OPEN);
-        batch->read_ids.assign((size_t)n_files * F5_READ_ID_MAX, 0);
+        batch = new_batch(n_files);
         // Pass 1, per file and entirely on one worker thread: read the file into the thread's
         // buffer, parse it, inflate what is asked for into a staging block of its own.  Pass 2,
         // after a prefix sum of the lengths: copy the staging blocks into the packed buffer.
@@ -2413,15 +2619,9 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
                     return;
                 }
                 const ReadEntry& r = file.read(0);
-                const int64_t n = r.signal.n;
-                const int64_t kept = (keep > 0 && n > 2 * keep) ? 2 * keep : n;
+                const int64_t kept = kept_length(r.signal.n, keep);
                 std::unique_ptr<int16_t[]> block(new int16_t[(size_t)std::max<int64_t>(kept, 1)]);
-                if (kept < n) {
-                    file.read_signal(r.signal, 0, keep, block.get(), &cache);
-                    file.read_signal(r.signal, n - keep, keep, block.get() + keep, &cache);
-                } else {
-                    file.read_signal(r.signal, 0, n, block.get(), &cache);
-                }
+                read_ends(file, r.signal, keep, block.get(), &cache);
                 copy_read_id(r.read_id, &batch->read_ids[(size_t)i * F5_READ_ID_MAX]);
                 lengths[(size_t)i] = kept;
                 staged[(size_t)i] = std::move(block);
@@ -2429,9 +2629,10 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
             if (multi) rc = F5_ERR_MULTI;
             if (rc != F5_OK) {      // unreadable, or damaged where only inflating shows it
                 lengths[(size_t)i] = 0;
-                std::memset(&batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
+                fail_read(batch, i, rc);
+            } else {
+                batch->status[(size_t)i] = F5_OK;
             }
-            batch->status[(size_t)i] = rc;
         };
         auto pack_one = [&](int64_t i) {
             if (!staged[(size_t)i]) return;
@@ -2447,13 +2648,7 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
         };
 
         run_parallel(load_one);
-        int64_t total = 0;
-        for (int64_t i = 0; i < n_files; ++i) {
-            batch->offsets[(size_t)i] = total;
-            total += lengths[(size_t)i];
-        }
-        batch->offsets[(size_t)n_files] = total;
-        batch->samples.resize((size_t)total);
+        batch->samples.resize((size_t)place_reads(batch, lengths));
         run_parallel(pack_one);
     } catch (const std::exception&) {
         delete batch;
@@ -2461,25 +2656,6 @@ int f5_load_batch(const char* const* paths, int64_t n_files, int64_t keep, int n
     }
     *out = batch;
     return F5_OK;
-}
-
-// a raw stream's weight in the order of the records: the bytes of its deflate data (a shuffled
-// deflate stream is one), 0 for everything else
-static int64_t deflate_weight(const f5_raw_stream& x) {
-    return x.mode == F5_RAW_ZLIB || x.mode == F5_RAW_ZLIB_SHUFFLE ? x.comp_bytes : 0;
-}
-static void put_u32le(uint8_t* dst, uint32_t v) {
-    for (int k = 0; k < 4; ++k) dst[k] = (uint8_t)(v >> (8 * k));
-}
-// HDF5's shuffle of 2-byte elements undone in place (as decode_chunk does it): low bytes, then high
-static void unshuffle_i16(std::vector<uint8_t>* bytes, std::vector<uint8_t>* scratch) {
-    const size_t n = bytes->size() / 2;
-    scratch->assign(bytes->begin(), bytes->end());
-    for (size_t k = 0; k < n; ++k) {
-        (*scratch)[2 * k] = (*bytes)[k];
-        (*scratch)[2 * k + 1] = (*bytes)[n + k];
-    }
-    bytes->swap(*scratch);
 }
 
 // One-read files with their Signals AS STORED (the one-read twin of f5_stream_open_raw's
@@ -2494,32 +2670,21 @@ int f5_load_batch_raw(const char* const* paths, int64_t n_files, int n_threads,
 
 int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_threads,
                          int64_t host_inflate_above, unsigned flags, f5_batch** out) {
-    if (!paths || !out || n_files < 0 ||
-        (flags & ~(unsigned)(F5_RAW_FLAG_VBZ_ZSTD_GPU | F5_RAW_FLAG_SHUFFLE_GPU)))
+    RawOptions options;
+    if (!paths || !out || n_files < 0 || !raw_options(host_inflate_above, flags, &options))
         return F5_ERR_ARGUMENT;
-    const bool vbz_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
-    const bool shuffle_gpu = (flags & F5_RAW_FLAG_SHUFFLE_GPU) != 0;
     *out = nullptr;
     f5_batch* batch = nullptr;
     try {
-        batch = new f5_batch;
-        batch->offsets.assign((size_t)n_files + 1, 0);
-        batch->status.assign((size_t)n_files, F5_ERR_OPEN);
-        batch->read_ids.assign((size_t)n_files * F5_READ_ID_MAX, 0);
-        struct Staged {
-            std::vector<Fast5::RawPiece> pieces;       // file_off = offset into `bytes` from here on
-            std::string bytes;
-            int64_t samples = 0;
-        };
-        std::vector<Staged> staged((size_t)n_files);
-        const int64_t zlib_above = host_inflate_above > 0 ? host_inflate_above : 0;
+        batch = new_batch(n_files);
+        std::vector<StagedRead> staged((size_t)n_files);
 
         auto stage_one = [&](int64_t i) {
             thread_local std::vector<uint8_t> file_bytes;
             thread_local ChunkCache cache;
             cache.addr = ~0ull;
             bool multi = false;
-            Staged& st = staged[(size_t)i];
+            StagedRead& st = staged[(size_t)i];
             int rc = paths[i] ? F5_OK : F5_ERR_ARGUMENT;
             if (rc == F5_OK) rc = guarded([&] {
                 Fast5 file(paths[i], &file_bytes);
@@ -2530,24 +2695,21 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
                 }
                 const ReadEntry& r = file.read(0);
                 st.samples = r.signal.n;
-                file.signal_pieces(r.signal, zlib_above, &st.pieces, vbz_gpu, shuffle_gpu);
+                file.signal_pieces(r.signal, options, &st.pieces);
                 for (Fast5::RawPiece& p : st.pieces) {
-                    const uint64_t wanted = (uint64_t)p.count * 2;
+                    // what the piece will occupy is what is staged of it - except of a VBZ chunk
+                    // (the stored chunk) and of a piece decoded here and now, stored from here on
                     const size_t at = st.bytes.size();
-                    if (p.kind == Fast5::kZlib || p.kind == Fast5::kStored || p.kind == Fast5::kVbz) {
-                        const uint64_t take = p.kind != Fast5::kStored ? p.nbytes
-                                                                       : std::min(p.nbytes, wanted);
+                    if (p.kind == Fast5::kHostDecode) {
+                        st.bytes.resize(at + (size_t)p.count * 2);
+                        file.decode_piece(r.signal, p, reinterpret_cast<uint8_t*>(&st.bytes[at]), &cache);
+                        p.kind = Fast5::kStored;
+                        p.nbytes = (uint64_t)p.count * 2;
+                    } else if (p.kind != Fast5::kZeros) {
+                        const uint64_t take = p.kind == Fast5::kVbz ? p.nbytes
+                                                                    : (uint64_t)(raw_piece_bytes(p) - p.prefix);
                         st.bytes.resize(at + (size_t)take);
                         file.read_bytes(p.file_off, take, reinterpret_cast<uint8_t*>(&st.bytes[at]));
-                        p.nbytes = take;
-                    } else if (p.kind == Fast5::kHostDecode) {
-                        st.bytes.resize(at + (size_t)wanted);
-                        file.decode_piece(r.signal, p, reinterpret_cast<uint8_t*>(&st.bytes[at]),
-                                          &cache);
-                        p.kind = Fast5::kStored;
-                        p.nbytes = wanted;
-                    } else {
-                        p.nbytes = 0;
                     }
                     p.file_off = at;
                 }
@@ -2555,36 +2717,18 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
             });
             if (multi) rc = F5_ERR_MULTI;
             if (rc != F5_OK) {
-                st = Staged();
-                std::memset(&batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
+                st = StagedRead();
+                fail_read(batch, i, rc);
+            } else {
+                batch->status[(size_t)i] = F5_OK;
             }
-            batch->status[(size_t)i] = rc;
         };
         int threads = thread_count(n_threads);
         threads = (int)std::min<int64_t>(threads, std::max<int64_t>(n_files, 1));
         worker_pool().run(threads, n_files, [&](int64_t i, int) { stage_one(i); });
 
-        // the host's share: the longest streams of the batch holding -host_inflate_above per cent
-        // of its compressed bytes (kHostDecode from here on = "inflate the staged stream")
-        if (host_inflate_above < 0) {
-            std::vector<std::pair<uint64_t, std::pair<int64_t, size_t>>> streams;
-            uint64_t total = 0;
-            for (int64_t i = 0; i < n_files; ++i)
-                for (size_t k = 0; k < staged[(size_t)i].pieces.size(); ++k)
-                    if (staged[(size_t)i].pieces[k].kind == Fast5::kZlib) {
-                        streams.push_back({staged[(size_t)i].pieces[k].nbytes, {i, k}});
-                        total += staged[(size_t)i].pieces[k].nbytes;
-                    }
-            std::sort(streams.begin(), streams.end(),
-                      [](const auto& a, const auto& b) { return a.first > b.first; });
-            const uint64_t share = (uint64_t)std::min<int64_t>(-host_inflate_above, 100);
-            uint64_t taken = 0;
-            for (const auto& e : streams) {
-                if (taken * 100 >= total * share) break;
-                staged[(size_t)e.second.first].pieces[e.second.second].kind = Fast5::kHostDecode;
-                taken += e.first;
-            }
-        }
+        // (kHostDecode from here on = "inflate the staged stream")
+        if (options.host_share > 0) take_host_share(&staged, options.host_share);
         int64_t samples = 0, at = 0;
         size_t n_pieces = 0;
         for (int64_t i = 0; i < n_files; ++i) {
@@ -2594,43 +2738,20 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
         }
         batch->offsets[(size_t)n_files] = samples;
         batch->streams.reserve(n_pieces);
-        for (int64_t i = 0; i < n_files; ++i)
-            for (Fast5::RawPiece& p : staged[(size_t)i].pieces) {
-                p.comp_offset = at;
-                p.comp_bytes = p.kind == Fast5::kHostDecode ? p.count * 2
-                               : p.kind == Fast5::kVbz      ? (int64_t)p.vbz_bytes
-                                                            : p.prefix + (int64_t)p.nbytes;
-                at += p.comp_bytes;
-                f5_raw_stream rec;
-                rec.comp_offset = p.comp_offset;
-                rec.comp_bytes = p.comp_bytes;
-                rec.out_offset = (batch->offsets[(size_t)i] + p.first) * 2;
-                rec.out_bytes = p.count * 2;
-                rec.mode = p.kind == Fast5::kZlib  ? (p.prefix ? F5_RAW_ZLIB_SHUFFLE : F5_RAW_ZLIB)
-                           : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
-                           : p.kind == Fast5::kStored && p.prefix ? F5_RAW_STORED_SHUFFLE
-                                                                  : F5_RAW_STORED;
-                rec.reserved = (int32_t)i;
-                batch->streams.push_back(rec);
-            }
-        batch->comp_bytes = at;
-        batch->comp.resize((size_t)(at + 64 + 1) / 2);
+        for (int64_t i = 0; i < n_files; ++i) place_pieces(batch, i, &staged[(size_t)i].pieces, &at);
+        finish_raw_batch(batch, at);
         uint8_t* comp = reinterpret_cast<uint8_t*>(batch->comp.data());
-        std::memset(comp + at, 0, 64);
         std::vector<int32_t> inflate_failed((size_t)n_files, 0);
         worker_pool().run(threads, n_files, [&](int64_t i, int) {
             thread_local ChunkCache cache;
             thread_local std::vector<uint8_t> tmp;
-            const Staged& st = staged[(size_t)i];
+            const StagedRead& st = staged[(size_t)i];
             for (const Fast5::RawPiece& p : st.pieces) {
                 const uint8_t* src = reinterpret_cast<const uint8_t*>(st.bytes.data()) + p.file_off;
                 uint8_t* dst = comp + p.comp_offset;
                 if (p.kind == Fast5::kVbz && p.vbz_zstd) {
                     // zstd on the host, the streamvbyte stage on the GPU
-                    const int rc = guarded([&] {
-                        std::memcpy(dst, src, 4);
-                        vbz_unzstd(src, (size_t)p.nbytes, dst + 4, p.vbz_bytes - 4);
-                    });
+                    const int rc = guarded([&] { vbz_host_stage(src, p, dst); });
                     if (rc != F5_OK) {
                         std::memset(dst, 0, (size_t)p.comp_bytes);   // (the GPU refuses it too)
                         inflate_failed[(size_t)i] = rc;
@@ -2657,14 +2778,7 @@ int f5_load_batch_raw_ex(const char* const* paths, int64_t n_files, int n_thread
             }
         });
         for (int64_t i = 0; i < n_files; ++i)
-            if (inflate_failed[(size_t)i]) {
-                batch->status[(size_t)i] = inflate_failed[(size_t)i];
-                std::memset(&batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
-            }
-        std::stable_sort(batch->streams.begin(), batch->streams.end(),
-                         [](const f5_raw_stream& x, const f5_raw_stream& y) {
-                             return deflate_weight(x) > deflate_weight(y);
-                         });
+            if (inflate_failed[(size_t)i]) fail_read(batch, i, inflate_failed[(size_t)i]);
     } catch (const std::exception&) {
         delete batch;
         return F5_ERR_OPEN;
@@ -2703,53 +2817,17 @@ int f5_load_reads(const char* path, int64_t first, int64_t count, int64_t keep, 
         std::vector<ChunkCache> caches((size_t)threads);
         const auto t_parsed = now();
 
-        batch = new f5_batch;
-        batch->offsets.assign((size_t)count + 1, 0);
-        batch->status.assign((size_t)count, F5_ERR_OPEN);
-        batch->read_ids.assign((size_t)count * F5_READ_ID_MAX, 0);
+        batch = new_batch(count);
         std::vector<int64_t> lengths((size_t)count, 0);
-
-        auto run_parallel = [&](const std::function<void(Fast5&, int64_t, ChunkCache*)>& fn) {
-            worker_pool().run(threads, count, [&](int64_t i, int slot) {
-                fn(*shared, i, &caches[(size_t)slot]);
-            });
-        };
-        run_parallel([&](Fast5& file, int64_t i, ChunkCache*) {
-            batch->status[(size_t)i] = guarded([&] {
-                const ReadEntry& r = file.read(first + i);
-                const int64_t n = r.signal.n;
-                lengths[(size_t)i] = (keep > 0 && n > 2 * keep) ? 2 * keep : n;
-                copy_read_id(r.read_id, &batch->read_ids[(size_t)i * F5_READ_ID_MAX]);
-            });
+        worker_pool().run(threads, count, [&](int64_t i, int) {
+            resolve_reads(*shared, first, keep, batch, &lengths, i, i + 1, [](const ReadEntry&, int64_t) {});
         });
         const auto t_resolved = now();
-        int64_t total = 0;
-        for (int64_t i = 0; i < count; ++i) {
-            batch->offsets[(size_t)i] = total;
-            total += batch->status[(size_t)i] == F5_OK ? lengths[(size_t)i] : 0;
-        }
-        batch->offsets[(size_t)count] = total;
-        batch->samples.resize((size_t)total);
+        batch->samples.resize((size_t)place_reads(batch, lengths));
         const auto t_allocated = now();
-        run_parallel([&](Fast5& file, int64_t i, ChunkCache* cache) {
-            if (batch->status[(size_t)i] != F5_OK) return;
-            int16_t* dst = batch->samples.data() + batch->offsets[(size_t)i];
-            const int rc = guarded([&] {
-                const ReadEntry& r = file.read(first + i);
-                const int64_t n = r.signal.n;
-                if (keep > 0 && n > 2 * keep) {
-                    file.read_signal(r.signal, 0, keep, dst, cache);
-                    file.read_signal(r.signal, n - keep, keep, dst + keep, cache);
-                } else {
-                    file.read_signal(r.signal, 0, n, dst, cache);
-                }
-            });
-            if (rc != F5_OK) std::memset(dst, 0, (size_t)lengths[(size_t)i] * 2);
-            batch->status[(size_t)i] = rc;
+        worker_pool().run(threads, count, [&](int64_t i, int slot) {
+            inflate_reads(*shared, first, keep, batch, lengths, i, i + 1, &caches[(size_t)slot]);
         });
-        for (int64_t i = 0; i < count; ++i)
-            if (batch->status[(size_t)i] != F5_OK)
-                std::memset(&batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
         if (timing)
             std::fprintf(stderr,
                          "f5_load_reads: %lld reads, %d threads: open+parse %.1f ms, resolve %.1f ms, "
@@ -2958,14 +3036,12 @@ struct f5_stream {
         int64_t a = 0, b = 0;
     };
 
+    // (set by open(), before any worker starts)
     std::vector<std::string> paths;
-    int64_t keep = 0;
+    int64_t keep = 0;                // packed mode; 0 in raw mode
     int depth = 3;
     bool raw = false;                // hand out the Signal pieces as stored (f5_stream_open_raw)
-    int64_t zlib_above = 0;          // ... except deflate streams longer than this: host-inflated
-    bool vbz_zstd_gpu = false;       // F5_RAW_FLAG_VBZ_ZSTD_GPU: VBZ chunks go out as stored
-    bool shuffle_gpu = false;        // F5_RAW_FLAG_SHUFFLE_GPU: shuffled chunks go out as stored
-    int host_share = 0;              // ... and the longest ones holding this share (%) of the bytes
+    RawOptions options;              // ... in this way
     static constexpr int64_t kLongStreamBytes = 64 * 1024;
     std::mutex m;
     std::condition_variable work_cv, done_cv;
@@ -2975,6 +3051,34 @@ struct f5_stream {
     std::vector<std::thread> workers;
 
     static constexpr int64_t kInflateGrain = 8, kResolveGrain = 64, kFetchGrain = 256;
+
+    // The one way to a stream, packed (raw = false: keep counts) or raw (options count): paths,
+    // mode and options are in place before the team of n_threads starts.  depth <= 0: 3.
+    static int open(const char* const* paths, int64_t n_paths, int64_t keep, bool raw,
+                    const RawOptions& options, int n_threads, int depth, f5_stream** out) {
+        for (int64_t i = 0; i < n_paths; ++i)
+            if (!paths[i]) return F5_ERR_ARGUMENT;
+        f5_stream* s = nullptr;
+        try {
+            s = new f5_stream;
+            s->paths.assign(paths, paths + n_paths);
+            s->keep = keep;
+            s->raw = raw;
+            s->options = options;
+            s->depth = depth > 0 ? std::min(depth, 64) : 3;
+            {
+                std::lock_guard<std::mutex> g(s->m);
+                s->admit_locked();
+            }
+            const int threads = thread_count(n_threads);
+            for (int t = 0; t < threads; ++t) s->workers.emplace_back([s] { s->worker(); });
+        } catch (const std::exception&) {
+            delete s;
+            return F5_ERR_OPEN;
+        }
+        *out = s;
+        return F5_OK;
+    }
 
     ~f5_stream() {
         {
@@ -3047,10 +3151,7 @@ struct f5_stream {
         if (c->status == F5_OK) {
             c->count = c->file->n_reads();
             try {
-                c->batch = new f5_batch;
-                c->batch->offsets.assign((size_t)c->count + 1, 0);
-                c->batch->status.assign((size_t)c->count, F5_ERR_OPEN);
-                c->batch->read_ids.assign((size_t)c->count * F5_READ_ID_MAX, 0);
+                c->batch = new_batch(c->count);
                 c->lengths.assign((size_t)c->count, 0);
                 if (raw) c->pieces.resize((size_t)c->count);
             } catch (const std::exception&) {
@@ -3061,15 +3162,49 @@ struct f5_stream {
     }
 
     void resolve(Container* c, int64_t a, int64_t b) {
-        for (int64_t i = a; i < b; ++i)
-            c->batch->status[(size_t)i] = guarded([&] {
-                const ReadEntry& r = c->file->read(i);
-                const int64_t n = r.signal.n;
-                c->lengths[(size_t)i] = (!raw && keep > 0 && n > 2 * keep) ? 2 * keep : n;
-                if (raw) c->file->signal_pieces(r.signal, zlib_above, &c->pieces[(size_t)i], vbz_zstd_gpu,
-                                                    shuffle_gpu);
-                copy_read_id(r.read_id, &c->batch->read_ids[(size_t)i * F5_READ_ID_MAX]);
-            });
+        resolve_reads(*c->file, 0, keep, c->batch, &c->lengths, a, b, [&](const ReadEntry& r, int64_t i) {
+            if (raw) c->file->signal_pieces(r.signal, options, &c->pieces[(size_t)i]);
+        });
+    }
+
+    // The host's share of a CONTAINER's inflating: with options.host_share > 0 the longest deflate
+    // streams holding that share (per cent) of the container's compressed bytes are left to the
+    // host's threads - long streams are what a CPU core is good at (a stream is one lane's work on
+    // the GPU however long it is) and what is left for the GPU is of even length.  Unlike the rule
+    // for a batch of one-read files (take_host_share above) it takes EVERY stream at or above a
+    // cut - the length of the last stream that still counted towards the share, all its equals
+    // with it - and none at all from a container of long streams.  Such a piece loses its prefix:
+    // the fetch pass decodes it from the file (Fast5::decode_piece), shuffle and all.
+    void take_host_share(Container* c) {
+        std::vector<int64_t> sizes;
+        int64_t all = 0;
+        for (int64_t i = 0; i < c->count; ++i)
+            if (c->batch->status[(size_t)i] == F5_OK)
+                for (const Fast5::RawPiece& p : c->pieces[(size_t)i])
+                    if (p.kind == Fast5::kZlib) {
+                        sizes.push_back((int64_t)p.nbytes);
+                        all += (int64_t)p.nbytes;
+                    }
+        std::sort(sizes.begin(), sizes.end(), std::greater<int64_t>());
+        int64_t cut = INT64_MAX, taken = 0;
+        // ... of a container of ORDINARY reads.  Where the streams are long throughout
+        // (mean above kLongStreamBytes: reads of ~50 k samples and more) the host keeps
+        // none: a 200 KB stream is 0.6 ms of a core, and with a wavefront per stream the GPU
+        // decodes such containers alone at 134 k reads/s where a fifth of the bytes on the
+        // host's sixteen threads made it 54 k (profiles/r06_loader).
+        const bool long_streams = !sizes.empty() && all / (int64_t)sizes.size() > kLongStreamBytes;
+        for (int64_t v : sizes) {
+            if (long_streams || taken * 100 >= all * options.host_share) break;
+            taken += v;
+            cut = v;
+        }
+        for (int64_t i = 0; i < c->count; ++i)
+            if (c->batch->status[(size_t)i] == F5_OK)
+                for (Fast5::RawPiece& p : c->pieces[(size_t)i])
+                    if (p.kind == Fast5::kZlib && (int64_t)p.nbytes >= cut) {
+                        p.kind = Fast5::kHostDecode;
+                        p.prefix = 0;
+                    }
     }
 
     void layout(Container* c) {
@@ -3078,91 +3213,22 @@ struct f5_stream {
             Container* c;
             ~MarkEnd() { mark(c, 3); }
         } mark_end{c};
-        int64_t total = 0;
-        for (int64_t i = 0; i < c->count; ++i) {
-            c->batch->offsets[(size_t)i] = total;
-            total += c->batch->status[(size_t)i] == F5_OK ? c->lengths[(size_t)i] : 0;
-        }
-        c->batch->offsets[(size_t)c->count] = total;
+        const int64_t total = place_reads(c->batch, c->lengths);
         try {
             if (!raw) {
                 c->batch->samples.resize((size_t)total);
                 return;
             }
-            // A share of the inflating for the host: with host_share > 0 the longest deflate streams
-            // holding that share (per cent) of the container's compressed bytes are left to the
-            // host's threads - long streams are what a CPU core is good at (a stream is one
-            // lane's work on the GPU however long it is) and what is left for the GPU is of even
-            // length.
-            if (host_share > 0) {
-                std::vector<int64_t> sizes;
-                int64_t all = 0;
-                for (int64_t i = 0; i < c->count; ++i)
-                    if (c->batch->status[(size_t)i] == F5_OK)
-                        for (const Fast5::RawPiece& p : c->pieces[(size_t)i])
-                            if (p.kind == Fast5::kZlib) {
-                                sizes.push_back((int64_t)p.nbytes);
-                                all += (int64_t)p.nbytes;
-                            }
-                std::sort(sizes.begin(), sizes.end(), std::greater<int64_t>());
-                int64_t cut = INT64_MAX, taken = 0;
-                // ... of a container of ORDINARY reads.  Where the streams are long throughout
-                // (mean above kLongStreamBytes: reads of ~50 k samples and more) the host keeps
-                // none: a 200 KB stream is 0.6 ms of a core, and with a wavefront per stream the GPU
-                // decodes such containers alone at 134 k reads/s where a fifth of the bytes on the
-                // host's sixteen threads made it 54 k (profiles/r06_loader).
-                const bool long_streams = !sizes.empty() && all / (int64_t)sizes.size() > kLongStreamBytes;
-                for (int64_t v : sizes) {
-                    if (long_streams || taken * 100 >= all * host_share) break;
-                    taken += v;
-                    cut = v;
-                }
-                for (int64_t i = 0; i < c->count; ++i)
-                    if (c->batch->status[(size_t)i] == F5_OK)
-                        for (Fast5::RawPiece& p : c->pieces[(size_t)i])
-                            if (p.kind == Fast5::kZlib && (int64_t)p.nbytes >= cut) {
-                                p.kind = Fast5::kHostDecode;
-                                p.prefix = 0;
-                            }
-            }
-            // raw: every piece gets its place in the byte buffer (what it occupies there: the
-            // stored bytes, or - decoded by the host - its samples) and its record; the records
-            // go out longest stream first, so that the lanes of a wave of the GPU decoder - which
-            // step together, one stream each - get streams of one length
+            if (options.host_share > 0) take_host_share(c);
+            // raw: every piece gets its place in the byte buffer and its record
             int64_t at = 0;
             size_t n_pieces = 0;
             for (int64_t i = 0; i < c->count; ++i)
                 if (c->batch->status[(size_t)i] == F5_OK) n_pieces += c->pieces[(size_t)i].size();
             c->batch->streams.reserve(n_pieces);
-            for (int64_t i = 0; i < c->count; ++i) {
-                if (c->batch->status[(size_t)i] != F5_OK) continue;
-                for (Fast5::RawPiece& p : c->pieces[(size_t)i]) {
-                    const int64_t wanted = p.count * 2;
-                    p.comp_offset = at;
-                    p.comp_bytes = p.kind == Fast5::kZlib     ? p.prefix + (int64_t)p.nbytes
-                                   : p.kind == Fast5::kStored ? p.prefix + std::min<int64_t>((int64_t)p.nbytes, wanted)
-                                   : p.kind == Fast5::kZeros  ? 0
-                                   : p.kind == Fast5::kVbz    ? (int64_t)p.vbz_bytes
-                                                              : wanted;
-                    at += p.comp_bytes;
-                    f5_raw_stream rec;
-                    rec.comp_offset = p.comp_offset;
-                    rec.comp_bytes = p.comp_bytes;
-                    rec.out_offset = (c->batch->offsets[(size_t)i] + p.first) * 2;
-                    rec.out_bytes = wanted;
-                    rec.mode = p.kind == Fast5::kZlib  ? (p.prefix ? F5_RAW_ZLIB_SHUFFLE : F5_RAW_ZLIB)
-                               : p.kind == Fast5::kVbz ? (p.vbz_gpu ? F5_RAW_VBZ_ZSTD : F5_RAW_VBZ)
-                               : p.kind == Fast5::kStored && p.prefix ? F5_RAW_STORED_SHUFFLE
-                                                                      : F5_RAW_STORED;
-                    rec.reserved = (int32_t)i;         // which read of the batch it belongs to
-                    c->batch->streams.push_back(rec);
-                }
-            }
-            std::stable_sort(c->batch->streams.begin(), c->batch->streams.end(),
-                             [](const f5_raw_stream& x, const f5_raw_stream& y) {
-                                 return deflate_weight(x) > deflate_weight(y);
-                             });
-            c->batch->comp_bytes = at;
+            for (int64_t i = 0; i < c->count; ++i)
+                if (c->batch->status[(size_t)i] == F5_OK) place_pieces(c->batch, i, &c->pieces[(size_t)i], &at);
+            finish_raw_batch(c->batch, at);
             // the fetch pass walks the reads in FILE order (groups are listed by name - random
             // read ids - but written one after the other): neighbours in a task are neighbours in
             // the file, and Fast5::read_many reads them together
@@ -3181,9 +3247,6 @@ struct f5_stream {
                 std::sort(c->fetch_order.begin(), c->fetch_order.end(),
                           [&](int64_t x, int64_t y) { return where[(size_t)x] < where[(size_t)y]; });
             }
-            // (the decoder fetches ahead of itself: 64 readable bytes behind the last stream)
-            c->batch->comp.resize((size_t)(at + 64 + 1) / 2);
-            std::memset(reinterpret_cast<uint8_t*>(c->batch->comp.data()) + at, 0, 64);
         } catch (const std::exception&) {
             c->status = F5_ERR_FORMAT;
         }
@@ -3205,8 +3268,7 @@ struct f5_stream {
                     rec.mode = F5_RAW_STORED;
                     rec.comp_bytes = 0;
                 }
-            std::memset(&c->batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
-            c->batch->status[(size_t)i] = rc;
+            fail_read(c->batch, i, rc);
         };
         items.clear();
         for (int64_t k = a; k < b; ++k) {
@@ -3237,9 +3299,7 @@ struct f5_stream {
                         // zstd on the host, the streamvbyte stage on the GPU
                         vbz_chunk.resize((size_t)p.nbytes);
                         c->file->read_bytes(p.file_off, p.nbytes, vbz_chunk.data());
-                        uint8_t* dst = comp + p.comp_offset;
-                        std::memcpy(dst, vbz_chunk.data(), 4);
-                        vbz_unzstd(vbz_chunk.data(), vbz_chunk.size(), dst + 4, p.vbz_bytes - 4);
+                        vbz_host_stage(vbz_chunk.data(), p, comp + p.comp_offset);
                     }
             });
             if (rc != F5_OK) fail(i, rc);
@@ -3248,33 +3308,12 @@ struct f5_stream {
 
     void inflate(Container* c, int64_t a, int64_t b) {
         thread_local ChunkCache cache;
-        for (int64_t i = a; i < b; ++i) {
-            if (c->batch->status[(size_t)i] != F5_OK) continue;
-            int16_t* dst = c->batch->samples.data() + c->batch->offsets[(size_t)i];
-            const int rc = guarded([&] {
-                const ReadEntry& r = c->file->read(i);
-                const int64_t n = r.signal.n;
-                if (keep > 0 && n > 2 * keep) {
-                    c->file->read_signal(r.signal, 0, keep, dst, &cache);
-                    c->file->read_signal(r.signal, n - keep, keep, dst + keep, &cache);
-                } else {
-                    c->file->read_signal(r.signal, 0, n, dst, &cache);
-                }
-            });
-            if (rc != F5_OK) {
-                std::memset(dst, 0, (size_t)c->lengths[(size_t)i] * 2);
-                std::memset(&c->batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
-            }
-            c->batch->status[(size_t)i] = rc;
-        }
+        inflate_reads(*c->file, 0, keep, c->batch, c->lengths, a, b, &cache);
     }
 
     void finish(Container* c) {      // no read of it is being worked on any more
         mark(c, 4);
-        report(c);
-        for (int64_t i = 0; i < c->count; ++i)
-            if (c->batch->status[(size_t)i] != F5_OK)
-                std::memset(&c->batch->read_ids[(size_t)i * F5_READ_ID_MAX], 0, F5_READ_ID_MAX);
+        report(c);             // (a read that failed lost its id where it failed: fail_read)
         c->file.reset();             // unmap and close now, not when the caller frees the batch
     }
 
@@ -3350,26 +3389,7 @@ int f5_stream_open(const char* const* paths, int64_t n_paths, int64_t keep, int 
                    int depth, f5_stream** out) {
     if (!out || n_paths < 0 || (n_paths > 0 && !paths)) return F5_ERR_ARGUMENT;
     *out = nullptr;
-    for (int64_t i = 0; i < n_paths; ++i)
-        if (!paths[i]) return F5_ERR_ARGUMENT;
-    f5_stream* s = nullptr;
-    try {
-        s = new f5_stream;
-        s->paths.assign(paths, paths + n_paths);
-        s->keep = keep;
-        s->depth = depth > 0 ? std::min(depth, 64) : 3;
-        {
-            std::lock_guard<std::mutex> g(s->m);
-            s->admit_locked();
-        }
-        const int threads = thread_count(n_threads);
-        for (int t = 0; t < threads; ++t) s->workers.emplace_back([s] { s->worker(); });
-    } catch (const std::exception&) {
-        delete s;
-        return F5_ERR_OPEN;
-    }
-    *out = s;
-    return F5_OK;
+    return f5_stream::open(paths, n_paths, keep, false, RawOptions(), n_threads, depth, out);
 }
 
 int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads, int depth,
@@ -3379,49 +3399,15 @@ int f5_stream_open_raw(const char* const* paths, int64_t n_paths, int n_threads,
 
 int f5_stream_open_raw_ex(const char* const* paths, int64_t n_paths, int n_threads, int depth,
                           int64_t host_inflate_above, unsigned flags, f5_stream** out) {
-    if (flags & ~(unsigned)(F5_RAW_FLAG_VBZ_ZSTD_GPU | F5_RAW_FLAG_SHUFFLE_GPU)) return F5_ERR_ARGUMENT;
-    f5_stream* s = nullptr;
+    RawOptions options;
+    if (!raw_options(host_inflate_above, flags, &options)) return F5_ERR_ARGUMENT;
+    if (!out || n_paths < 0 || (n_paths > 0 && !paths)) return F5_ERR_ARGUMENT;
     // A raw container is little work per read (no inflating) behind a serial start (one thread
     // opens and parses it: 5-6 ms of the ~30 ms of CPU a container of 4,000 reads costs): a window
     // of three starves a team of sixteen - 1.2 M reads/s where eight in flight give 1.7 M and
     // sixteen 1.9 M (profiles/r06_loader).  Default: half the team, between 3 and 8.
     if (depth <= 0) depth = std::max(3, std::min(8, thread_count(n_threads) / 2));
-    // (opened without a team first, so that the mode is set before any thread looks at it)
-    const int st = f5_stream_open(paths, 0, 0, 1, depth, &s);
-    if (st != F5_OK) return st;
-    if (!out || n_paths < 0 || (n_paths > 0 && !paths)) {
-        delete s;
-        return F5_ERR_ARGUMENT;
-    }
-    try {
-        for (int64_t i = 0; i < n_paths; ++i) {
-            if (!paths[i]) {
-                delete s;
-                return F5_ERR_ARGUMENT;
-            }
-            s->paths.emplace_back(paths[i]);
-        }
-        {
-            std::lock_guard<std::mutex> g(s->m);
-            s->raw = true;
-            s->vbz_zstd_gpu = (flags & F5_RAW_FLAG_VBZ_ZSTD_GPU) != 0;
-            s->shuffle_gpu = (flags & F5_RAW_FLAG_SHUFFLE_GPU) != 0;
-            // (>= 0: a length in bytes; < 0: minus the host's share of the bytes in per cent)
-            s->zlib_above = host_inflate_above > 0 ? host_inflate_above : 0;
-            s->host_share = host_inflate_above < 0
-                                ? (int)std::min<int64_t>(100, -host_inflate_above) : 0;
-            s->admit_locked();
-        }
-        const int threads = thread_count(n_threads);
-        for (int t = (int)s->workers.size(); t < threads; ++t)
-            s->workers.emplace_back([s] { s->worker(); });
-        s->work_cv.notify_all();
-    } catch (const std::exception&) {
-        delete s;
-        return F5_ERR_OPEN;
-    }
-    *out = s;
-    return F5_OK;
+    return f5_stream::open(paths, n_paths, 0, true, options, n_threads, depth, out);
 }
 
 const uint8_t* f5_batch_comp(const f5_batch* batch) {

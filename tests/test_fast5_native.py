@@ -604,3 +604,52 @@ def test_mutated_files_never_crash_and_agree_with_python_reader(tmp_path):
                 assert a[0] == b[0] and np.array_equal(a[1], b[1]), trial
     assert outcomes['same data'] > 50 and outcomes['both refuse'] > 50, outcomes
 
+
+
+LOADER_HARNESS = os.path.join(REPO, 'oracle', '_build', 'loader_host_test')
+
+
+@pytest.mark.skipif(not os.path.exists(LOADER_HARNESS),
+                    reason='oracle/_build/loader_host_test not built (make -C oracle)')
+def test_every_loader_returns_the_recorded_bytes():
+    """oracle/loader_host_test.cpp - the loader compiled into a program of its own - pushes the 42
+    golden fast5 files through every loader of the ABI (packed and raw, batch and stream, every
+    keep / host_inflate_above / flags of its grid, 1 and 4 threads) and prints a line of digests
+    per call; tests/golden/loader_digests.txt is what it printed before the loaders were put on
+    shared helpers.  Every line has to be there, unchanged.  The program itself fails if a result
+    depends on the thread count or if a raw batch, decoded on the host, is not the packed loader's
+    samples."""
+    root = os.path.join(REPO, 'tests', 'golden', 'fast5')
+    paths = sorted(os.path.join(d, f) for d, _, files in os.walk(root) for f in files
+                   if f.endswith('.fast5'))
+    assert len(paths) == 42
+    done = subprocess.run([LOADER_HARNESS] + paths, capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr[-2000:]
+    got = done.stdout.splitlines()
+    with open(os.path.join(REPO, 'tests', 'golden', 'loader_digests.txt')) as f:
+        want = f.read().splitlines()
+    assert len(got) == len(want) and len(want) > 400
+    for k, (a, b) in enumerate(zip(got, want)):
+        assert a == b, 'line %d' % (k + 1)
+
+
+def test_one_thread_stream_keeps_files_with_a_chunk_at_the_same_address_apart(tmp_path):
+    """Files of one layout hold their one chunk at the same address with the same size; a stream's
+    thread keeps the chunk it decoded last, and the reader object of the next container is
+    allocated where the last one's was freed: the kept chunk must be known by its file, not by
+    that object's address.  (Once a one-thread packed stream returned the samples of the file
+    before.)"""
+    import shuffle_fixtures as sf
+    rng = np.random.default_rng(19)
+    signals = [sf.squiggle(rng, 3000) for _ in range(8)]
+    paths = [sf.write_copy([('read-%03d' % k, s)], str(tmp_path / ('same_place_%d.fast5' % k)), 'shuffle')
+             for k, s in enumerate(signals)]
+    for depth in (1, 3):
+        for keep in (0, 100):
+            got = list(fast5_native.stream_reads(paths, keep=keep, threads=1, depth=depth))
+            assert [g[0] for g in got] == list(range(len(paths)))
+            for (_, ids, samples, offsets, status), want in zip(got, signals):
+                assert list(status) == [0]
+                if keep:
+                    want = np.concatenate([want[:keep], want[-keep:]])
+                assert np.array_equal(samples[offsets[0]:offsets[1]], want), (depth, keep, ids)
