@@ -9,15 +9,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <new>
 #include <string>
-#include <thread>
 #include <utility>
 #include <mutex>
 #include <vector>
 
 #include "../../include/deepbinner_hip.h"
 #include "dbh_general.h"
+#include "dbh_host_layout.h"
+#include "dbh_owned.h"
 #define DBH_FORWARD_NS dbh
 #define DBH_TIMELINE 0
 #include "dbh_forward.hip"
@@ -129,6 +132,11 @@ int hip_fail(hipError_t e, const char* what) {
     do {                                                      \
         hipError_t e_ = (call);                               \
         if (e_ != hipSuccess) return hip_fail(e_, #call);     \
+    } while (0)
+#define DBH_TRY(call)                                         \
+    do {                                                      \
+        const int st_ = (call);                               \
+        if (st_ != DBH_OK) return st_;                        \
     } while (0)
 
 // canonical (Keras) shapes of the 20 convolutions for a given class count
@@ -258,13 +266,64 @@ void pack_weights(const float* w, int n_classes, std::vector<float>& packed) {
     }
 }
 
+using dbh_host::align256;
+using dbh_owned::DeviceBlock;
+using dbh_owned::PinnedBlock;
+
+// Where a forward launch parks its conv17 outputs until the batched tail runs (dbh_forward.hip):
+// a 256-byte header whose first word is the counter the launch's workgroups take their windows
+// off (zero between launches, so zeroed only when the block is new, on the stream that launches
+// next), then kWgScratchFloats floats per workgroup.  One per stream a model launches on: launches
+// on one stream follow each other, launches on two may overlap.
+struct TailScratch {
+    DeviceBlock block;
+    hipError_t reserve(int64_t workgroups, hipStream_t stream) {
+        bool fresh = false;
+        const hipError_t e =
+            block.reserve(256 + (size_t)workgroups * dbh::kWgScratchFloats * sizeof(float), &fresh);
+        return e == hipSuccess && fresh ? hipMemsetAsync(block.get(), 0, 256, stream) : e;
+    }
+    int* counter() const { return block.as<int>(); }
+    float* scratch() const { return block.as<float>(256); }
+};
+
+// live timing of the forward kernel (dbh_forward_timing_*): state here, logic in dbh_probes.h
+struct TimingBrackets {
+    int every = 0;               // 0 = off, n = open an event bracket at every n-th forward launch
+    int span = 1;                // consecutive launches one bracket covers (<= every)
+    hipEvent_t open_stop = nullptr;   // stop event of the bracket being filled
+    int64_t open_windows = 0, launch_counter = 0, timed_launches = 0, timed_windows = 0;
+    std::vector<std::pair<dbh_owned::Event, dbh_owned::Event>> events;
+    size_t events_used = 0;
+    hipError_t begin(hipStream_t stream, int64_t windows);
+    hipError_t end(hipStream_t stream);
+    void reset();
+};
+
+struct HostSlot {
+    dbh_owned::Stream stream;
+    PinnedBlock h_in, h_out;
+    DeviceBlock d_in, d_out, d_work;
+    TailScratch tail;
+};
+
+struct DeflatedQueue {
+    dbh_owned::Stream stream;
+    dbh_owned::Event inflated, classified;      // hand-over to the forward stream
+    PinnedBlock h_small;                        // records, offsets, results
+    PinnedBlock h_comp;                         // staging for pageable input
+    DeviceBlock d_comp, d_small, d_samples, d_tokens, d_out, d_work;
+    TailScratch tail;
+    std::vector<int32_t> order;                 // the records as they were sent
+};
+
 }  // namespace
 
 struct dbh_model {
     int n_classes = 0;
     int input_size = dbh::kWindow;
     int kind = DBH_MODEL_KIND_PERSISTENT;   // DBH_MODEL_KIND_GENERAL: dbh_general.hip runs it
-    dbh_gen::Net gen;                       // ... with these weights
+    dbh_gen::Net gen;                       // ... with these weights (dbh_gen::destroy frees them)
     int device = 0;
     int cus = 256;               // workgroups of a persistent forward launch (one per CU)
     int cus_total = 256;         // ... before dbh_model_reserve_cus took some away
@@ -277,78 +336,33 @@ struct dbh_model {
     // 2 / 1: 5.74 M, 0 / 0 - always four - 5.74 M: a small group pays the whole stage D-E-F chain for
     // one or two windows, so they are kept to the launch's very end)
     int chunk4_rounds = 2, chunk2_rounds = 1;
-    float* d_packed = nullptr;
-    // workspace for the host-pointer entry points, grown on demand
-    void* d_in = nullptr;      size_t in_bytes = 0;
-    void* d_work = nullptr;    size_t work_bytes = 0;
-    void* d_out = nullptr;     size_t out_bytes = 0;
-    // conv17 outputs parked per workgroup until the batched tail runs (dbh_forward.hip); one
-    // buffer per stream a model launches on - launches on one stream follow each other, launches
-    // on two streams may overlap: `tails` for the streams callers of the *_dev entry points
-    // bring, one per staging slot for the host-buffer pipeline
-    struct Tail { hipStream_t stream; void* ptr; size_t bytes; };
-    std::vector<Tail> tails;
-    void* d_tail = nullptr;    size_t tail_bytes = 0;      // the timeline entry points' (null stream)
-    void* d_clock = nullptr;   size_t clock_bytes = 0;     // dbh_forward_clock_enable
+    DeviceBlock packed;
+    DeviceBlock in, work, out;   // workspace of the host-pointer entry points, grown on demand
+    // per stream the callers of the *_dev entry points bring (the null stream among them): the
+    // forward kernel's scratch, and the general path's activations for dbh_predict(_dev)
+    std::map<hipStream_t, TailScratch> tails;
+    std::map<hipStream_t, DeviceBlock> gen_scratch;
+    DeviceBlock clock;                                     // dbh_forward_clock_enable
     bool clock_probe = false;  unsigned clock_grid = 0;
     bool phase_probe = false;      // dbh_forward_phases_enable
+    TimingBrackets timing;
     // staging slots of the host-buffer entry points (classify_host: overlapped H2D / kernels / D2H)
     static constexpr int kSlots = 3;
     static constexpr int64_t kDefaultGroup = 32768;
     int64_t host_group_windows = kDefaultGroup;     // dbh_model_set_host_group
     bool host_zero_copy = true;      // DEEPBINNER_HOST_ZERO_COPY=0: copy host samples to HBM first
-    struct Slot {
-        hipStream_t stream = nullptr;
-        void* h_in = nullptr;   size_t h_in_bytes = 0;     // pinned
-        void* h_out = nullptr;  size_t h_out_bytes = 0;    // pinned
-        void* d_in = nullptr;   size_t d_in_bytes = 0;
-        void* d_out = nullptr;  size_t d_out_bytes = 0;
-        void* d_work = nullptr; size_t d_work_bytes = 0;
-        void* d_tail = nullptr; size_t d_tail_bytes = 0;
-    } slot[kSlots];
+    HostSlot slot[kSlots];
     // buffers of dbh_classify_pair_deflated (the start model's, or the only model's, are used)
-    struct Deflated {
-        hipStream_t stream = nullptr;
-        hipEvent_t inflated = nullptr, classified = nullptr;    // hand-over to the forward stream
-        void* h_small = nullptr;  size_t h_small_bytes = 0;     // pinned: records, offsets, results
-        void* h_comp = nullptr;   size_t h_comp_bytes = 0;      // pinned staging for pageable input
-        void* d_comp = nullptr;   size_t d_comp_bytes = 0;
-        void* d_small = nullptr;  size_t d_small_bytes = 0;
-        void* d_samples = nullptr; size_t d_samples_bytes = 0;
-        void* d_tokens = nullptr; size_t d_tokens_bytes = 0;
-        void* d_out = nullptr;    size_t d_out_bytes = 0;
-        void* d_work = nullptr;   size_t d_work_bytes = 0;
-        void* d_tail = nullptr;   size_t d_tail_bytes = 0;
-        std::vector<int32_t> order;                             // the records as they were sent
-    } deflated;
-    // live timing of the forward kernel (dbh_forward_timing_*)
+    DeflatedQueue deflated;
     int64_t hint_len = 0, hint_cap = 0;   // dbh_model_set_read_length_hint
-    int timing = 0;              // 0 = off, n = open an event bracket at every n-th forward launch
-    int timing_span = 1;         // consecutive launches one bracket covers (<= timing)
-    hipEvent_t open_stop = nullptr;   // stop event of the bracket being filled
-    int64_t open_windows = 0;
-    int64_t timed_launches = 0;
-    int64_t launch_counter = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    size_t events_used = 0;
-    int64_t timed_windows = 0;
-    // activations of the general path's dbh_predict_dev / dbh_predict, per stream (like `tails`)
-    std::vector<Tail> gen_scratch;
+    ~dbh_model() { dbh_gen::destroy(&gen); }
 };
 
 namespace {
 
-int ensure(void** ptr, size_t* have, size_t need) {
-    if (*have >= need) return DBH_OK;
-    if (*ptr) {
-        DBH_HIP(hipFree(*ptr));
-        *ptr = nullptr;
-        *have = 0;
-    }
-    DBH_HIP(hipMalloc(ptr, need));
-    *have = need;
-    return DBH_OK;
-}
+// "every read is len_hint samples long": offsets[0] belongs to read number read0 of the sample
+// buffer, which holds at least hint_cap samples (see dbh_model_set_read_length_hint)
+struct ReadHints { int64_t read0 = 0, len_hint = 0, hint_cap = 0; };
 
 struct FusedInput {          // seam-b2 mode of the forward kernel (all null/zero = seam b1)
     const int16_t* samples = nullptr;
@@ -357,82 +371,33 @@ struct FusedInput {          // seam-b2 mode of the forward kernel (all null/zer
     int side = 0;
     double score_diff = 0.0;
     int32_t* calls = nullptr;
-    // "every read is len_hint samples long": offsets[0] belongs to read number read0 of the
-    // sample buffer, which holds at least hint_cap samples (see dbh_model_set_read_length_hint)
-    int64_t read0 = 0, len_hint = 0, hint_cap = 0;
-    // where this launch parks its conv17 outputs (null = the model's own buffer)
-    void** tail = nullptr;
-    size_t* tail_bytes = nullptr;
+    ReadHints hints;
+    // where this launch parks its conv17 outputs (null = the model's own, by stream)
+    TailScratch* tail = nullptr;
 };
-
-int ensure_host(void** ptr, size_t* have, size_t need) {
-    if (*have >= need) return DBH_OK;
-    if (*ptr) {
-        DBH_HIP(hipHostFree(*ptr));
-        *ptr = nullptr;
-        *have = 0;
-    }
-    DBH_HIP(hipHostMalloc(ptr, need, hipHostMallocDefault));
-    *have = need;
-    return DBH_OK;
-}
 
 int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev,
                    int debug_stage, float* debug_dev, hipStream_t stream,
                    const FusedInput& in = FusedInput()) {
     if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;   // (introspection)
     if (n == 0) return DBH_OK;
+    const bool timed = m->timing.every > 0 && (debug_stage < 0 || debug_stage >= 100);
+    TailScratch* tail = in.tail ? in.tail : &m->tails[stream];
     // grid.x limit is 2^31-1 blocks; chunk anyway to keep launches bounded
     const int64_t kChunk = (int64_t)(1 << 20) * in.steps;   // whole reads per launch
     for (int64_t off = 0; off < n; off += kChunk) {
         const int64_t cnt = (n - off < kChunk) ? (n - off) : kChunk;
-        hipEvent_t ev_stop = nullptr;
-        if (m->timing > 0 && (debug_stage < 0 || debug_stage >= 100)) {
-            const int64_t pos = m->launch_counter++ % m->timing;
-            if (pos == 0) {
-                if (m->events_used == m->events.size()) {
-                    hipEvent_t a, b;
-                    DBH_HIP(hipEventCreate(&a));
-                    DBH_HIP(hipEventCreate(&b));
-                    m->events.emplace_back(a, b);
-                }
-                DBH_HIP(hipEventRecord(m->events[m->events_used].first, stream));
-                m->open_stop = m->events[m->events_used].second;
-                m->open_windows = 0;
-            }
-            if (m->open_stop && pos < m->timing_span) {
-                m->open_windows += cnt;
-                if (pos == m->timing_span - 1) {      // last launch of the bracket
-                    ev_stop = m->open_stop;
-                    m->open_stop = nullptr;
-                }
-            }
-        }
+        if (timed) DBH_HIP(m->timing.begin(stream, cnt));
         // production launches are persistent: at most one workgroup per CU, each walking its
-        // share of the windows; the debug / timeline modes keep one workgroup per window
+        // share of the windows; the debug modes keep one workgroup per window
         // (a workgroup takes its windows in groups of dbh::kGroup: dbh_forward.hip)
-        const bool one_per_group = debug_stage >= 0 && debug_stage != 301;
+        const bool one_per_group = debug_stage >= 0;
         const int64_t groups = (cnt + dbh::kGroup - 1) / dbh::kGroup;
         const unsigned grid = (unsigned)(one_per_group || groups < m->cus ? groups : m->cus);
-        void** tail = in.tail;
-        size_t* tail_bytes = in.tail_bytes;
-        if (!tail) {
-            size_t k = 0;
-            while (k < m->tails.size() && m->tails[k].stream != stream) ++k;
-            if (k == m->tails.size()) m->tails.push_back(dbh_model::Tail{stream, nullptr, 0});
-            tail = &m->tails[k].ptr;
-            tail_bytes = &m->tails[k].bytes;
-        }
-        // (the first 256 bytes: the counter the launch's workgroups take their windows off -
-        // zero between launches, so zeroed here only when the buffer is new)
-        {
-            void* before = *tail;
-            const int st = ensure(tail, tail_bytes, 256 + (size_t)grid * dbh::kWgScratchFloats * sizeof(float));
-            if (st != DBH_OK) return st;
-            if (*tail != before) DBH_HIP(hipMemsetAsync(*tail, 0, 256, stream));
-        }
+        // (a no-op for a tail the deflated path sized before it took the forward stream's lock)
+        DBH_HIP(tail->reserve(grid, stream));
         dbh::ForwardArgs a;
-        a.packed = m->d_packed;
+        a.packed = m->packed.as<float>();
         a.x = x_dev ? x_dev + off * dbh::kWindow : nullptr;
         a.probs = probs_dev ? probs_dev + off * m->n_classes : nullptr;
         a.debug_out = debug_dev ? debug_dev + off * dbh::kStageFloats[debug_stage < 0 || debug_stage > 7 ? 0 : debug_stage]
@@ -440,22 +405,20 @@ int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev
         a.samples = in.samples;
         a.offsets = in.offsets ? (const long long*)(in.offsets + off / in.steps) : nullptr;
         a.calls = in.calls ? (int*)(in.calls + off / in.steps) : nullptr;
-        a.tail_scratch = (float*)((char*)*tail + 256);
-        // production launches hand their windows out by counter; the debug and timeline modes
-        // (which may stop half-way, and index their output by window) keep fixed shares
-        a.win_counter = (debug_stage < 0 && m->windows_by_counter) ? (int*)*tail : nullptr;
+        a.tail_scratch = tail->scratch();
+        // production launches hand their windows out by counter; the debug modes (which may stop
+        // half-way, and index their output by window) keep fixed shares
+        a.win_counter = (debug_stage < 0 && m->windows_by_counter) ? tail->counter() : nullptr;
         a.clock_out = nullptr;
         if (m->clock_probe && debug_stage < 0) {
-            const int st = ensure(&m->d_clock, &m->clock_bytes,
-                                  (size_t)grid * (4 + dbh::kPhaseMarks * dbh::kPhaseGroups) * sizeof(int64_t));
-            if (st != DBH_OK) return st;
-            a.clock_out = (long long*)m->d_clock;
+            DBH_HIP(m->clock.reserve((size_t)grid * (4 + dbh::kPhaseMarks * dbh::kPhaseGroups) * sizeof(int64_t)));
+            a.clock_out = m->clock.as<long long>();
             m->clock_grid = grid;
         }
         a.score_diff = in.score_diff;
-        a.read0 = (long long)(in.read0 + off / in.steps);
-        a.len_hint = (long long)in.len_hint;
-        a.hint_cap = (long long)in.hint_cap;
+        a.read0 = (long long)(in.hints.read0 + off / in.steps);
+        a.len_hint = (long long)in.hints.len_hint;
+        a.hint_cap = (long long)in.hints.hint_cap;
         a.n_windows = (long long)cnt;
         a.n_classes = m->n_classes;
         a.debug_stage = debug_stage;
@@ -464,34 +427,12 @@ int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev
         a.phases = m->phase_probe ? 1 : 0;
         a.chunk4_min_left = m->chunk4_rounds * (int)grid;
         a.chunk2_min_left = m->chunk2_rounds * (int)grid;
-        if (debug_stage == 300)
-            hipLaunchKernelGGL(dbh_timeline::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads),
-                               0, stream, reinterpret_cast<dbh_timeline::ForwardArgs&>(a));
-        else
-            hipLaunchKernelGGL(dbh::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, stream,
-                               a);
+        hipLaunchKernelGGL(dbh::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, stream, a);
         DBH_HIP(hipGetLastError());
-        if (ev_stop) {
-            DBH_HIP(hipEventRecord(ev_stop, stream));
-            ++m->events_used;                          // only closed brackets count
-            m->timed_windows += m->open_windows;
-            m->timed_launches += m->timing_span;
-        }
+        if (timed) DBH_HIP(m->timing.end(stream));
     }
     return DBH_OK;
 }
-
-inline int steps_for(int scan_size) { return scan_size / (dbh::kWindow / 2); }
-
-// scan steps of a model (classify.py:330-331: windows every input_size / 2 samples), 0 when
-// scan_size is not a positive multiple of that (check_input_size, classify.py:396-407)
-inline int model_steps(const dbh_model* m, int scan_size) {
-    const int half = m->input_size / 2;
-    const int steps = scan_size / half;
-    return (steps > 0 && steps * half == scan_size) ? steps : 0;
-}
-
-inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // the general path's share of dbh_classify_workspace_bytes: per-window probabilities, then the
 // activations of one chunk
@@ -505,13 +446,9 @@ size_t general_workspace(const dbh_model* m, int64_t n_reads, int steps) {
 int general_predict(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev,
                     hipStream_t stream) {
     if (n == 0) return DBH_OK;
-    size_t k = 0;
-    while (k < m->gen_scratch.size() && m->gen_scratch[k].stream != stream) ++k;
-    if (k == m->gen_scratch.size()) m->gen_scratch.push_back(dbh_model::Tail{stream, nullptr, 0});
-    dbh_model::Tail& sc = m->gen_scratch[k];
-    const int st = ensure(&sc.ptr, &sc.bytes, dbh_gen::activation_bytes(m->gen, n));
-    if (st != DBH_OK) return st;
-    DBH_HIP(dbh_gen::forward(m->gen, x_dev, nullptr, nullptr, 1, 0, n, probs_dev, sc.ptr, stream));
+    DeviceBlock& act = m->gen_scratch[stream];
+    DBH_HIP(act.reserve(dbh_gen::activation_bytes(m->gen, n)));
+    DBH_HIP(dbh_gen::forward(m->gen, x_dev, nullptr, nullptr, 1, 0, n, probs_dev, act.get(), stream));
     return DBH_OK;
 }
 
@@ -679,11 +616,10 @@ int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int 
         return DBH_ERR_UNSUPPORTED;
     if (n_floats != canon_param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
     int count = 0;
-    int st = dbh_device_count(&count);
-    if (st != DBH_OK) return st;
+    DBH_TRY(dbh_device_count(&count));
     std::vector<float> packed;
     pack_weights(weights, n_classes, packed);
-    dbh_model* m = new (std::nothrow) dbh_model();
+    std::unique_ptr<dbh_model> m(new (std::nothrow) dbh_model());
     if (!m) return DBH_ERR_OUT_OF_MEMORY;
     m->n_classes = n_classes;
     hipError_t e = hipGetDevice(&m->device);
@@ -700,26 +636,20 @@ int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int 
         }
         m->cus_total = m->cus;
     }
-    {
-        const char* knob = std::getenv("DEEPBINNER_LAUNCH_PER_BATCH");
-        m->launch_per_batch = knob && knob[0] == '1';
-        const char* zc = std::getenv("DEEPBINNER_HOST_ZERO_COPY");
-        m->host_zero_copy = !(zc && zc[0] == '0');
-        const char* sw = std::getenv("DEEPBINNER_STATIC_WINDOWS");
-        m->windows_by_counter = !(sw && sw[0] == '1');
-        if (const char* c4 = std::getenv("DEEPBINNER_CHUNK4_ROUNDS")) m->chunk4_rounds = std::atoi(c4);
-        if (const char* c2 = std::getenv("DEEPBINNER_CHUNK2_ROUNDS")) m->chunk2_rounds = std::atoi(c2);
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&m->d_packed, packed.size() * sizeof(float));
+    const char* knob = std::getenv("DEEPBINNER_LAUNCH_PER_BATCH");
+    m->launch_per_batch = knob && knob[0] == '1';
+    const char* zc = std::getenv("DEEPBINNER_HOST_ZERO_COPY");
+    m->host_zero_copy = !(zc && zc[0] == '0');
+    const char* sw = std::getenv("DEEPBINNER_STATIC_WINDOWS");
+    m->windows_by_counter = !(sw && sw[0] == '1');
+    if (const char* c4 = std::getenv("DEEPBINNER_CHUNK4_ROUNDS")) m->chunk4_rounds = std::atoi(c4);
+    if (const char* c2 = std::getenv("DEEPBINNER_CHUNK2_ROUNDS")) m->chunk2_rounds = std::atoi(c2);
+    if (e == hipSuccess) e = m->packed.reserve(packed.size() * sizeof(float));
     if (e == hipSuccess)
-        e = hipMemcpy(m->d_packed, packed.data(), packed.size() * sizeof(float),
+        e = hipMemcpy(m->packed.get(), packed.data(), packed.size() * sizeof(float),
                       hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (m->d_packed) (void)hipFree(m->d_packed);
-        delete m;
-        return hip_fail(e, "dbh_model_create");
-    }
-    *model = m;
+    if (e != hipSuccess) return hip_fail(e, "dbh_model_create");      // (m frees what it holds)
+    *model = m.release();
     return DBH_OK;
 }
 
@@ -732,20 +662,16 @@ int dbh_model_create_ex(const float* weights, int64_t n_floats, int n_classes, i
     if (flags == DBH_MODEL_AUTO && input_size == dbh::kWindow && n_classes <= dbh::kMaxClasses)
         return dbh_model_create(weights, n_floats, n_classes, input_size, model);
     int count = 0;
-    int st = dbh_device_count(&count);
-    if (st != DBH_OK) return st;
-    dbh_model* m = new (std::nothrow) dbh_model();
+    DBH_TRY(dbh_device_count(&count));
+    std::unique_ptr<dbh_model> m(new (std::nothrow) dbh_model());
     if (!m) return DBH_ERR_OUT_OF_MEMORY;
     m->n_classes = n_classes;
     m->input_size = input_size;
     m->kind = DBH_MODEL_KIND_GENERAL;
     hipError_t e = hipGetDevice(&m->device);
     if (e == hipSuccess) e = dbh_gen::create(weights, n_classes, input_size, &m->gen);
-    if (e != hipSuccess) {
-        delete m;
-        return hip_fail(e, "dbh_model_create_ex");
-    }
-    *model = m;
+    if (e != hipSuccess) return hip_fail(e, "dbh_model_create_ex");
+    *model = m.release();
     return DBH_OK;
 }
 
@@ -756,42 +682,7 @@ int dbh_model_kind(const dbh_model* m, int* kind) {
 }
 
 int dbh_model_destroy(dbh_model* m) {
-    if (!m) return DBH_OK;
-    dbh_gen::destroy(&m->gen);
-    for (auto& t : m->gen_scratch)
-        if (t.ptr) (void)hipFree(t.ptr);
-    if (m->d_packed) (void)hipFree(m->d_packed);
-    if (m->d_in) (void)hipFree(m->d_in);
-    if (m->d_work) (void)hipFree(m->d_work);
-    if (m->d_out) (void)hipFree(m->d_out);
-    for (auto& t : m->tails)
-        if (t.ptr) (void)hipFree(t.ptr);
-    if (m->d_tail) (void)hipFree(m->d_tail);
-    if (m->d_clock) (void)hipFree(m->d_clock);
-    for (auto& ev : m->events) {
-        (void)hipEventDestroy(ev.first);
-        (void)hipEventDestroy(ev.second);
-    }
-    {
-        dbh_model::Deflated& d = m->deflated;
-        if (d.stream) (void)hipStreamDestroy(d.stream);
-        if (d.inflated) (void)hipEventDestroy(d.inflated);
-        if (d.classified) (void)hipEventDestroy(d.classified);
-        if (d.h_small) (void)hipHostFree(d.h_small);
-        if (d.h_comp) (void)hipHostFree(d.h_comp);
-        for (void* p : {d.d_comp, d.d_small, d.d_samples, d.d_tokens, d.d_out, d.d_work, d.d_tail})
-            if (p) (void)hipFree(p);
-    }
-    for (auto& sl : m->slot) {
-        if (sl.stream) (void)hipStreamDestroy(sl.stream);
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.d_work) (void)hipFree(sl.d_work);
-        if (sl.d_tail) (void)hipFree(sl.d_tail);
-    }
-    delete m;
+    delete m;      // (every buffer, stream and event is a member that frees itself: dbh_owned.h)
     return DBH_OK;
 }
 
@@ -822,19 +713,16 @@ int dbh_predict(dbh_model* m, const float* x_host, int64_t n, float* probs_host)
     const int64_t L = m->input_size;
     const int64_t kChunk = 65536 * dbh::kWindow / L;
     const int64_t cap = n < kChunk ? n : kChunk;
-    int st = ensure(&m->d_in, &m->in_bytes, (size_t)(cap * L) * sizeof(float));
-    if (st != DBH_OK) return st;
-    st = ensure(&m->d_out, &m->out_bytes, (size_t)cap * m->n_classes * sizeof(float));
-    if (st != DBH_OK) return st;
+    DBH_HIP(m->in.reserve((size_t)(cap * L) * sizeof(float)));
+    DBH_HIP(m->out.reserve((size_t)cap * m->n_classes * sizeof(float)));
     for (int64_t off = 0; off < n; off += kChunk) {
         const int64_t cnt = (n - off < kChunk) ? (n - off) : kChunk;
-        DBH_HIP(hipMemcpyAsync(m->d_in, x_host + off * L, (size_t)(cnt * L) * sizeof(float),
+        DBH_HIP(hipMemcpyAsync(m->in.get(), x_host + off * L, (size_t)(cnt * L) * sizeof(float),
                                hipMemcpyHostToDevice, 0));
-        st = m->kind == DBH_MODEL_KIND_GENERAL
-                 ? general_predict(m, (const float*)m->d_in, cnt, (float*)m->d_out, 0)
-                 : launch_forward(m, (const float*)m->d_in, cnt, (float*)m->d_out, -1, nullptr, 0);
-        if (st != DBH_OK) return st;
-        DBH_HIP(hipMemcpyAsync(probs_host + off * m->n_classes, m->d_out,
+        DBH_TRY(m->kind == DBH_MODEL_KIND_GENERAL
+                    ? general_predict(m, m->in.as<float>(), cnt, m->out.as<float>(), 0)
+                    : launch_forward(m, m->in.as<float>(), cnt, m->out.as<float>(), -1, nullptr, 0));
+        DBH_HIP(hipMemcpyAsync(probs_host + off * m->n_classes, m->out.get(),
                                (size_t)cnt * m->n_classes * sizeof(float), hipMemcpyDeviceToHost, 0));
         DBH_HIP(hipStreamSynchronize(0));
     }
@@ -844,8 +732,8 @@ int dbh_predict(dbh_model* m, const float* x_host, int64_t n, float* probs_host)
 int dbh_normalise_windows_dev(const int16_t* samples_dev, const int64_t* offsets_dev,
                               int64_t n_reads, int side, int scan_size, float* windows_dev,
                               dbh_stream stream) {
-    const int steps = steps_for(scan_size);
-    if (n_reads < 0 || steps <= 0 || steps * (dbh::kWindow / 2) != scan_size ||
+    const int steps = dbh_host::model_steps(dbh::kWindow, scan_size);
+    if (n_reads < 0 || steps <= 0 ||
         (side != DBH_SIDE_START && side != DBH_SIDE_END))
         return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
@@ -911,7 +799,7 @@ int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_cal
 int dbh_classify_workspace_bytes(const dbh_model* m, int64_t n_reads, int scan_size,
                                  size_t* bytes) {
     if (!m || !bytes || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
-    const int steps = model_steps(m, scan_size);
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
     if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
     if (m->kind == DBH_MODEL_KIND_GENERAL) {
         *bytes = general_workspace(m, n_reads, steps);
@@ -930,11 +818,10 @@ namespace {
 int classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offsets_dev,
                      int64_t n_reads, int side, int scan_size, double score_diff,
                      float* probs_dev, int32_t* calls_dev, void* workspace_dev, dbh_stream stream,
-                     int64_t read0, int64_t len_hint, int64_t hint_cap, void** tail = nullptr,
-                     size_t* tail_bytes = nullptr) {
+                     const ReadHints& hints, TailScratch* tail = nullptr) {
     if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
-    const int steps = model_steps(m, scan_size);
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
     if (steps <= 0 || (side != DBH_SIDE_START && side != DBH_SIDE_END) || !samples_dev ||
         !offsets_dev || !probs_dev || !calls_dev)
         return DBH_ERR_INVALID_ARGUMENT;
@@ -955,11 +842,8 @@ int classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* of
     in.steps = steps;
     in.side = side;
     in.score_diff = score_diff;
-    in.read0 = read0;
-    in.len_hint = len_hint;
-    in.hint_cap = hint_cap;
+    in.hints = hints;
     in.tail = tail;
-    in.tail_bytes = tail_bytes;
     if (steps == 1) {
         // one window per read: slice + normalise + CNN + renormalise + call in ONE launch
         in.calls = calls_dev;
@@ -969,74 +853,50 @@ int classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* of
     // leaves per-window probabilities in the workspace; the merge kernel finishes each read
     if (!workspace_dev) return DBH_ERR_INVALID_ARGUMENT;
     float* wprobs = (float*)workspace_dev;
-    int st = launch_forward(m, nullptr, n_reads * steps, wprobs, -1, nullptr, (hipStream_t)stream,
-                            in);
-    if (st != DBH_OK) return st;
+    DBH_TRY(launch_forward(m, nullptr, n_reads * steps, wprobs, -1, nullptr, (hipStream_t)stream, in));
     return dbh_merge_calls_dev(wprobs, n_reads, steps, m->n_classes, score_diff, probs_dev,
                                calls_dev, stream);
 }
-}  // namespace
 
-extern "C" {
-
-int dbh_model_set_read_length_hint(dbh_model* m, int64_t read_length, int64_t capacity_samples) {
-    if (!m || read_length < 0 || capacity_samples < 0) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_OK;       // (nothing to tune)
-    m->hint_len = read_length;
-    m->hint_cap = read_length > 0 ? capacity_samples : 0;
+// A pair of models (start, end; either may be null) on the same reads: they must sit on one
+// device, agree on the class count and take the scan size
+int check_pair(dbh_model* const models[2], int scan_size) {
+    if (models[0] && models[1] && (models[0]->device != models[1]->device ||
+                                   models[0]->n_classes != models[1]->n_classes))
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int j = 0; j < 2; ++j)
+        if (models[j] && dbh_host::model_steps(models[j]->input_size, scan_size) <= 0)
+            return DBH_ERR_INVALID_ARGUMENT;
     return DBH_OK;
 }
 
-int dbh_classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offsets_dev,
-                         int64_t n_reads, int side, int scan_size, double score_diff,
-                         float* probs_dev, int32_t* calls_dev, void* workspace_dev,
-                         dbh_stream stream) {
-    if (!m) return DBH_ERR_INVALID_ARGUMENT;
-    return classify_i16_dev(m, samples_dev, offsets_dev, n_reads, side, scan_size, score_diff,
-                            probs_dev, calls_dev, workspace_dev, stream, 0, m->hint_len,
-                            m->hint_cap);
+// one workspace serves both, their kernels follow each other on one stream (after check_pair, for
+// n_reads >= 0, dbh_classify_workspace_bytes has nothing left to refuse)
+size_t pair_workspace_bytes(dbh_model* const models[2], int64_t n_reads, int scan_size) {
+    size_t bytes = 0, mine = 0;
+    for (int j = 0; j < 2; ++j)
+        if (models[j] && dbh_classify_workspace_bytes(models[j], n_reads, scan_size, &mine) == DBH_OK)
+            bytes = std::max(bytes, mine);
+    return bytes;
 }
 
-int dbh_classify_i16_batched_dev(dbh_model* m, const int16_t* samples_dev,
-                                 const int64_t* offsets_dev, int64_t n_reads, int batch_size,
-                                 int side, int scan_size, double score_diff, float* probs_dev,
-                                 int32_t* calls_dev, dbh_stream stream) {
-    if (!m || n_reads < 0 || batch_size <= 0) return DBH_ERR_INVALID_ARGUMENT;
-    if (n_reads == 0) return DBH_OK;
-    // The reference walks its reads batch by batch because model.predict does (classify.py:130,
-    // 361); a read's result does not depend on its batch.  Here the forward kernel is
-    // persistent - one workgroup per CU walking windows in read order - so the batches flow
-    // through ONE launch without a boundary between them (DEEPBINNER_LAUNCH_PER_BATCH=1 brings
-    // the launch per batch back, for comparison).  Reads with several scan steps go in chunks
-    // whose per-window probabilities fit a bounded workspace, one merge launch per chunk.
-    const int steps = model_steps(m, scan_size);
-    if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
-    // (a general model goes 65,536 windows at a time: its workspace holds them all, C up to 256)
-    const int64_t chunk = m->kind == DBH_MODEL_KIND_GENERAL
-                              ? std::max<int64_t>(1, 65536 / steps)
-                              : m->launch_per_batch ? (int64_t)batch_size
-                                                    : (steps == 1 ? n_reads : ((int64_t)1 << 20) / steps);
-    size_t work = 0;
-    int st = dbh_classify_workspace_bytes(m, chunk < n_reads ? chunk : n_reads, scan_size, &work);
-    if (st != DBH_OK) return st;
-    if (work) {
-        st = ensure(&m->d_work, &m->work_bytes, work);
-        if (st != DBH_OK) return st;
+// Each model of the pair over the same samples - probabilities to probs_dev[j], calls to
+// calls_dev[j] - then, when both are there, combine_calls of the two to final_dev.
+int classify_pair_dev(dbh_model* const models[2], const int sides[2], const int16_t* samples_dev,
+                      const int64_t* offsets_dev, int64_t n_reads, int scan_size, double score_diff,
+                      float* const probs_dev[2], int32_t* const calls_dev[2], int combine_mode,
+                      int32_t* final_dev, void* workspace_dev, hipStream_t stream,
+                      const ReadHints& hints, TailScratch* tail) {
+    for (int j = 0; j < 2; ++j) {
+        if (!models[j]) continue;
+        DBH_TRY(classify_i16_dev(models[j], samples_dev, offsets_dev, n_reads, sides[j], scan_size,
+                                 score_diff, probs_dev[j], calls_dev[j], workspace_dev,
+                                 (dbh_stream)stream, hints, tail));
     }
-    // in-order on the caller's stream, so the workspace can be reused chunk after chunk
-    for (int64_t r0 = 0; r0 < n_reads; r0 += chunk) {
-        const int64_t cnt = (n_reads - r0 < chunk) ? (n_reads - r0) : chunk;
-        st = classify_i16_dev(m, samples_dev, offsets_dev + r0, cnt, side, scan_size, score_diff,
-                              probs_dev + r0 * m->n_classes, calls_dev + r0, m->d_work, stream, r0,
-                              m->hint_len, m->hint_cap);
-        if (st != DBH_OK) return st;
-    }
-    return DBH_OK;
+    if (!(models[0] && models[1])) return DBH_OK;
+    return dbh_combine_calls_dev(calls_dev[0], calls_dev[1], n_reads, combine_mode, final_dev,
+                                 (dbh_stream)stream);
 }
-
-}  // extern "C"
-
-namespace {
 
 // Is [p, p + bytes) host memory the GPU's DMA engine can read in place (hipHostMalloc /
 // hipHostRegister: what dbh_malloc_host and dbh_host_alloc hand out)?
@@ -1051,25 +911,7 @@ bool is_pinned(const void* p, size_t bytes) {
     return a0.type == hipMemoryTypeHost && a1.type == hipMemoryTypeHost;
 }
 
-// Pageable memory -> a pinned staging slot.  One thread moves ~10 GB/s; PCIe takes 50+.  Large
-// copies are cut up between the calling thread and a few helpers.
-void staged_copy(void* dst, const void* src, size_t bytes) {
-    constexpr size_t kPiece = 8u << 20;
-    const int helpers = bytes >= 4 * kPiece ? 3 : (bytes >= 2 * kPiece ? 1 : 0);
-    if (helpers == 0) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    const size_t share = ((bytes / (size_t)(helpers + 1)) + 4095) & ~(size_t)4095;
-    std::vector<std::thread> team;
-    for (int t = 1; t <= helpers; ++t) {
-        const size_t lo = std::min(bytes, share * (size_t)t), hi = std::min(bytes, lo + share);
-        if (hi > lo)
-            team.emplace_back([=] { std::memcpy((char*)dst + lo, (const char*)src + lo, hi - lo); });
-    }
-    std::memcpy(dst, src, std::min(bytes, share));
-    for (std::thread& t : team) t.join();
-}
+using dbh_host::staged_copy;
 
 struct HostJob {
     dbh_model* model[2] = {nullptr, nullptr};      // start model, end model (either may be null)
@@ -1091,19 +933,12 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
     dbh_model* m = job.model[0] ? job.model[0] : job.model[1];      // owns the slots
     if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
-    if (!offsets_host) return DBH_ERR_INVALID_ARGUMENT;
-    int steps = 0;          // the larger of the models' (they may differ in input size)
-    for (dbh_model* mj : job.model) {
-        if (!mj) continue;
-        const int s = model_steps(mj, scan_size);
-        if (s <= 0) return DBH_ERR_INVALID_ARGUMENT;
-        steps = std::max(steps, s);
-    }
     const bool both = job.model[0] && job.model[1];
-    if (both && (job.model[0]->device != job.model[1]->device ||
-                 job.model[0]->n_classes != job.model[1]->n_classes))
+    if (!offsets_host || check_pair(job.model, scan_size) != DBH_OK || (job.final_host && !both))
         return DBH_ERR_INVALID_ARGUMENT;
-    if (job.final_host && !both) return DBH_ERR_INVALID_ARGUMENT;
+    int steps = 0;          // the larger of the models' (they may differ in input size)
+    for (dbh_model* mj : job.model)
+        if (mj) steps = std::max(steps, dbh_host::model_steps(mj->input_size, scan_size));
     // the current device is a per-thread setting: a caller on another thread than the one that
     // created the model gets the model's device
     DBH_HIP(hipSetDevice(m->device));
@@ -1116,38 +951,21 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
         1, (m->kind == DBH_MODEL_KIND_GENERAL ? dbh_model::kDefaultGroup : m->host_group_windows) / steps);
     constexpr int kSlots = dbh_model::kSlots;
     struct Pending { int64_t r0 = 0, cnt = 0; bool live = false; } pending[kSlots];
-    // what comes back per read of a group, in this order
-    const size_t probs_bytes = (size_t)C * sizeof(float);
-    auto out_layout = [&](int64_t cnt, size_t (&off)[5]) -> size_t {
-        size_t at = 0;
-        for (int k = 0; k < 2; ++k) {
-            off[k] = at;
-            if (job.model[k]) at += (size_t)cnt * probs_bytes;
-        }
-        for (int k = 0; k < 2; ++k) {
-            off[2 + k] = at;
-            if (job.model[k]) at += (size_t)cnt * sizeof(int32_t);
-        }
-        off[4] = at;
-        if (both) at += (size_t)cnt * sizeof(int32_t);
-        return at;
-    };
     auto drain = [&](int k) -> int {
-        dbh_model::Slot& sl = m->slot[k];
+        HostSlot& sl = m->slot[k];
         if (!pending[k].live) return DBH_OK;
         DBH_HIP(hipStreamSynchronize(sl.stream));
         const int64_t cnt = pending[k].cnt, r0 = pending[k].r0;
-        size_t off[5];
-        out_layout(cnt, off);
-        const char* h = (const char*)sl.h_out;
+        const dbh_host::GroupOut at(cnt, C, job.model[0], job.model[1]);
+        const char* h = sl.h_out.as<char>();
         for (int j = 0; j < 2; ++j) {
             if (job.model[j] && job.probs_host[j])
-                std::memcpy(job.probs_host[j] + r0 * C, h + off[j], (size_t)cnt * probs_bytes);
+                std::memcpy(job.probs_host[j] + r0 * C, h + at.probs[j], (size_t)cnt * C * sizeof(float));
             if (job.model[j] && job.calls_host[j])
-                std::memcpy(job.calls_host[j] + r0, h + off[2 + j], (size_t)cnt * sizeof(int32_t));
+                std::memcpy(job.calls_host[j] + r0, h + at.calls[j], (size_t)cnt * sizeof(int32_t));
         }
         if (both && job.final_host)
-            std::memcpy(job.final_host + r0, h + off[4], (size_t)cnt * sizeof(int32_t));
+            std::memcpy(job.final_host + r0, h + at.final_calls, (size_t)cnt * sizeof(int32_t));
         pending[k].live = false;
         return DBH_OK;
     };
@@ -1161,84 +979,62 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
     int64_t g = 0;
     for (int64_t r0 = 0; r0 < n_reads; r0 += group, ++g) {
         const int k = (int)(g % kSlots);
-        dbh_model::Slot& sl = m->slot[k];
+        HostSlot& sl = m->slot[k];
         int st = drain(k);
         if (st != DBH_OK) return fail(st);
-        if (!sl.stream) {
-            hipError_t e = hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking);
-            if (e != hipSuccess) return fail(hip_fail(e, "hipStreamCreateWithFlags"));
-        }
+        hipError_t e = hipSuccess;
+        if (!sl.stream) e = hipStreamCreateWithFlags(&sl.stream.h, hipStreamNonBlocking);
+        if (e != hipSuccess) return fail(hip_fail(e, "hipStreamCreateWithFlags"));
         const int64_t cnt = (n_reads - r0 < group) ? (n_reads - r0) : group;
         const int64_t s0 = offsets_host[r0], s1 = offsets_host[r0 + cnt];
         if (s1 < s0) return fail(DBH_ERR_INVALID_ARGUMENT);
         const size_t raw_bytes = (size_t)(s1 - s0) * sizeof(int16_t);
-        const size_t sample_bytes = (raw_bytes + 255) & ~(size_t)255;
+        const size_t sample_bytes = align256(raw_bytes);
         const size_t off_bytes = (size_t)(cnt + 1) * sizeof(int64_t);
-        size_t out_off[5];
-        const size_t out_bytes = out_layout(cnt, out_off);
-        size_t work = 0;
-        for (dbh_model* mj : job.model) {
-            size_t wj = 0;
-            if (mj && st == DBH_OK) st = dbh_classify_workspace_bytes(mj, cnt, scan_size, &wj);
-            work = std::max(work, wj);
-        }
+        const dbh_host::GroupOut out(cnt, C, job.model[0], job.model[1]);
+        const size_t work = pair_workspace_bytes(job.model, cnt, scan_size);
         // host side: the relative offsets always, the samples only when they have to be staged
-        if (st == DBH_OK)
-            st = ensure_host(&sl.h_in, &sl.h_in_bytes, off_bytes + (pinned ? 0 : sample_bytes));
-        if (st == DBH_OK) st = ensure_host(&sl.h_out, &sl.h_out_bytes, out_bytes);
-        if (st == DBH_OK) st = ensure(&sl.d_in, &sl.d_in_bytes, sample_bytes + off_bytes);
-        if (st == DBH_OK) st = ensure(&sl.d_out, &sl.d_out_bytes, out_bytes);
-        if (st == DBH_OK && work) st = ensure(&sl.d_work, &sl.d_work_bytes, work);
-        if (st != DBH_OK) return fail(st);
+        e = sl.h_in.reserve(off_bytes + (pinned ? 0 : sample_bytes));
+        if (e == hipSuccess) e = sl.h_out.reserve(out.total);
+        if (e == hipSuccess) e = sl.d_in.reserve(sample_bytes + off_bytes);
+        if (e == hipSuccess) e = sl.d_out.reserve(out.total);
+        if (e == hipSuccess && work) e = sl.d_work.reserve(work);
+        if (e != hipSuccess) return fail(hip_fail(e, "growing a staging slot"));
 
-        int64_t* rel = (int64_t*)sl.h_in;
+        int64_t* rel = sl.h_in.as<int64_t>();
         for (int64_t i = 0; i <= cnt; ++i) rel[i] = offsets_host[r0 + i] - s0;
-        // all reads of the group equally long?  then the kernel need not wait for the offsets
-        int64_t uniform = rel[1];
-        for (int64_t i = 1; i <= cnt && uniform > 0; ++i)
-            if (rel[i] != i * uniform) uniform = 0;
         const void* src = samples_host + s0;
         if (raw_bytes && !pinned) {
-            staged_copy((char*)sl.h_in + off_bytes, src, raw_bytes);
-            src = (char*)sl.h_in + off_bytes;
+            staged_copy(sl.h_in.as<char>(off_bytes), src, raw_bytes);
+            src = sl.h_in.as<char>(off_bytes);
         }
-        hipError_t e = hipSuccess;
         // The samples reach the kernel either by a copy into HBM first, or not at all: the
         // forward kernel asks for a window's 2 KB ~25,000 cycles before it needs them, which
         // hides a PCIe round trip as well as an HBM one - so it can read pinned host memory in
         // place.  (A copy between two launches cannot overlap them here: the persistent kernel
         // fills every CU's registers and LDS, and the copy of the next group only starts when
         // it has drained - 1.2 ms of idle GPU per 6 ms group, profiles/r03_host_path_trace.txt.)
-        const int16_t* d_samples = (const int16_t*)sl.d_in;
+        const int16_t* d_samples = sl.d_in.as<int16_t>();
+        const int64_t* d_offsets = sl.d_in.as<int64_t>(sample_bytes);
         if (raw_bytes && m->host_zero_copy) {
             void* mapped = nullptr;
             e = hipHostGetDevicePointer(&mapped, const_cast<void*>(src), 0);
             d_samples = (const int16_t*)mapped;
         } else if (raw_bytes) {
-            e = hipMemcpyAsync(sl.d_in, src, raw_bytes, hipMemcpyHostToDevice, sl.stream);
+            e = hipMemcpyAsync(sl.d_in.get(), src, raw_bytes, hipMemcpyHostToDevice, sl.stream);
         }
         if (e == hipSuccess)
-            e = hipMemcpyAsync((char*)sl.d_in + sample_bytes, rel, off_bytes, hipMemcpyHostToDevice,
-                               sl.stream);
+            e = hipMemcpyAsync((void*)d_offsets, rel, off_bytes, hipMemcpyHostToDevice, sl.stream);
         if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync H2D"));
-        int32_t* d_calls[2] = {nullptr, nullptr};
-        for (int j = 0; j < 2; ++j) {
-            if (!job.model[j]) continue;
-            d_calls[j] = (int32_t*)((char*)sl.d_out + out_off[2 + j]);
-            st = classify_i16_dev(job.model[j], d_samples,
-                                  (const int64_t*)((char*)sl.d_in + sample_bytes), cnt, job.side[j],
-                                  scan_size, score_diff, (float*)((char*)sl.d_out + out_off[j]),
-                                  d_calls[j], sl.d_work, (dbh_stream)sl.stream, 0, uniform, s1 - s0,
-                                  &sl.d_tail, &sl.d_tail_bytes);
-            if (st != DBH_OK) return fail(st);
-        }
-        if (both) {
-            st = dbh_combine_calls_dev(d_calls[0], d_calls[1], cnt, job.combine_mode,
-                                       (int32_t*)((char*)sl.d_out + out_off[4]),
-                                       (dbh_stream)sl.stream);
-            if (st != DBH_OK) return fail(st);
-        }
-        e = hipMemcpyAsync(sl.h_out, sl.d_out, out_bytes, hipMemcpyDeviceToHost, sl.stream);
+        float* const d_probs[2] = {sl.d_out.as<float>(out.probs[0]), sl.d_out.as<float>(out.probs[1])};
+        int32_t* const d_calls[2] = {sl.d_out.as<int32_t>(out.calls[0]), sl.d_out.as<int32_t>(out.calls[1])};
+        // (all reads of the group equally long?  then the kernel need not wait for the offsets)
+        st = classify_pair_dev(job.model, job.side, d_samples, d_offsets, cnt, scan_size, score_diff,
+                               d_probs, d_calls, job.combine_mode, sl.d_out.as<int32_t>(out.final_calls),
+                               sl.d_work.get(), sl.stream,
+                               ReadHints{0, dbh_host::uniform_length(rel, cnt), s1 - s0}, &sl.tail);
+        if (st != DBH_OK) return fail(st);
+        e = hipMemcpyAsync(sl.h_out.get(), sl.d_out.get(), out.total, hipMemcpyDeviceToHost, sl.stream);
         if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync D2H"));
         pending[k].r0 = r0;
         pending[k].cnt = cnt;
@@ -1255,6 +1051,56 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
 
 extern "C" {
 
+int dbh_model_set_read_length_hint(dbh_model* m, int64_t read_length, int64_t capacity_samples) {
+    if (!m || read_length < 0 || capacity_samples < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_OK;       // (nothing to tune)
+    m->hint_len = read_length;
+    m->hint_cap = read_length > 0 ? capacity_samples : 0;
+    return DBH_OK;
+}
+
+int dbh_classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offsets_dev,
+                         int64_t n_reads, int side, int scan_size, double score_diff,
+                         float* probs_dev, int32_t* calls_dev, void* workspace_dev,
+                         dbh_stream stream) {
+    if (!m) return DBH_ERR_INVALID_ARGUMENT;
+    return classify_i16_dev(m, samples_dev, offsets_dev, n_reads, side, scan_size, score_diff,
+                            probs_dev, calls_dev, workspace_dev, stream,
+                            ReadHints{0, m->hint_len, m->hint_cap});
+}
+
+int dbh_classify_i16_batched_dev(dbh_model* m, const int16_t* samples_dev,
+                                 const int64_t* offsets_dev, int64_t n_reads, int batch_size,
+                                 int side, int scan_size, double score_diff, float* probs_dev,
+                                 int32_t* calls_dev, dbh_stream stream) {
+    if (!m || n_reads < 0 || batch_size <= 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    // The reference walks its reads batch by batch because model.predict does (classify.py:130,
+    // 361); a read's result does not depend on its batch.  Here the forward kernel is
+    // persistent - one workgroup per CU walking windows in read order - so the batches flow
+    // through ONE launch without a boundary between them (DEEPBINNER_LAUNCH_PER_BATCH=1 brings
+    // the launch per batch back, for comparison).  Reads with several scan steps go in chunks
+    // whose per-window probabilities fit a bounded workspace, one merge launch per chunk.
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
+    if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
+    // (a general model goes 65,536 windows at a time: its workspace holds them all, C up to 256)
+    const int64_t chunk = m->kind == DBH_MODEL_KIND_GENERAL
+                              ? std::max<int64_t>(1, 65536 / steps)
+                              : m->launch_per_batch ? (int64_t)batch_size
+                                                    : (steps == 1 ? n_reads : ((int64_t)1 << 20) / steps);
+    size_t work = 0;
+    DBH_TRY(dbh_classify_workspace_bytes(m, chunk < n_reads ? chunk : n_reads, scan_size, &work));
+    if (work) DBH_HIP(m->work.reserve(work));
+    // in-order on the caller's stream, so the workspace can be reused chunk after chunk
+    for (int64_t r0 = 0; r0 < n_reads; r0 += chunk) {
+        const int64_t cnt = (n_reads - r0 < chunk) ? (n_reads - r0) : chunk;
+        DBH_TRY(classify_i16_dev(m, samples_dev, offsets_dev + r0, cnt, side, scan_size, score_diff,
+                                 probs_dev + r0 * m->n_classes, calls_dev + r0, m->work.get(), stream,
+                                 ReadHints{r0, m->hint_len, m->hint_cap}));
+    }
+    return DBH_OK;
+}
+
 int dbh_classify_i16(dbh_model* m, const int16_t* samples_host, const int64_t* offsets_host,
                      int64_t n_reads, int side, int scan_size, double score_diff,
                      float* probs_host, int32_t* calls_host) {
@@ -1263,11 +1109,7 @@ int dbh_classify_i16(dbh_model* m, const int16_t* samples_host, const int64_t* o
     if (!offsets_host || !probs_host || !calls_host ||
         (side != DBH_SIDE_START && side != DBH_SIDE_END))
         return DBH_ERR_INVALID_ARGUMENT;
-    HostJob job;
-    job.model[0] = m;
-    job.side[0] = side;
-    job.probs_host[0] = probs_host;
-    job.calls_host[0] = calls_host;
+    const HostJob job{{m, nullptr}, {side, DBH_SIDE_END}, {probs_host, nullptr}, {calls_host, nullptr}};
     return classify_host(job, samples_host, offsets_host, n_reads, scan_size, score_diff);
 }
 
@@ -1281,14 +1123,9 @@ int dbh_classify_pair_i16(dbh_model* start_model, dbh_model* end_model,
         return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
     if (!offsets_host || !calls_host) return DBH_ERR_INVALID_ARGUMENT;
-    HostJob job;
-    job.model[0] = start_model;
-    job.model[1] = end_model;
-    job.probs_host[0] = start_probs_host;
-    job.probs_host[1] = end_probs_host;
-    job.calls_host[0] = start_calls_host;
-    job.calls_host[1] = end_calls_host;
-    job.combine_mode = combine_mode;
+    HostJob job{{start_model, end_model}, {DBH_SIDE_START, DBH_SIDE_END},
+                {start_probs_host, end_probs_host}, {start_calls_host, end_calls_host}, nullptr,
+                combine_mode};
     if (start_model && end_model) job.final_host = calls_host;
     else if (start_model && !start_calls_host) job.calls_host[0] = calls_host;
     else if (end_model && !end_calls_host) job.calls_host[1] = calls_host;
@@ -1323,6 +1160,56 @@ bool shared_forward_stream() {
     const char* v = std::getenv("DEEPBINNER_FORWARD_STREAM");
     return !(v && std::strcmp(v, "own") == 0);
 }
+
+// One queue's turn on its device's forward stream.  From acquire() to release() the queue holds the
+// device's lock; what it launches on `stream` runs behind everything the queue's own stream holds
+// so far, and the queue's own stream goes on behind it.  NOTHING ALLOCATES OR FREES WHILE THE LOCK
+// IS HELD (but for the forward stream itself, once per device): hipMalloc / hipFree synchronise the
+// device, and under the lock that would stall every other queue's launch.  With
+// every queue on its own stream (DEEPBINNER_FORWARD_STREAM=own, or a device beyond kMaxDevices)
+// both do nothing and `stream` stays the queue's own.
+struct ForwardTurn {
+    DeflatedQueue& d;
+    const int device;
+    const bool shared = shared_forward_stream() && device >= 0 && device < kMaxDevices;
+    hipStream_t stream = d.stream;       // where the turn's launches go
+    std::unique_lock<std::mutex> lock;
+    int acquire(dbh_model* const models[2]) {
+        if (!shared) return DBH_OK;
+        // before the lock: the hand-over's events, and the forward kernel's scratch at the size the
+        // launches ask for (its counter zeroed on the queue's stream, which the forward stream awaits)
+        hipError_t e = hipSuccess;
+        for (dbh_owned::Event* ev : {&d.inflated, &d.classified})
+            if (e == hipSuccess && !ev->h) e = hipEventCreateWithFlags(&ev->h, hipEventDisableTiming);
+        if (e != hipSuccess) return hip_fail(e, "hipEventCreateWithFlags");
+        int cus = 0;
+        for (int j = 0; j < 2; ++j)
+            if (models[j]) cus = std::max(cus, models[j]->cus);
+        DBH_HIP(d.tail.reserve(cus, d.stream));
+        lock = std::unique_lock<std::mutex>(g_forward_mutex[device]);
+        hipStream_t& fs = g_forward_stream[device];
+        if (!fs) {
+            int least = 0, greatest = 0;
+            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+            e = hipStreamCreateWithPriority(&fs, hipStreamNonBlocking, greatest);
+            if (e != hipSuccess) return hip_fail(e, "hipStreamCreateWithPriority");
+        }
+        stream = fs;
+        e = hipEventRecord(d.inflated, d.stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(stream, d.inflated, 0);
+        return e == hipSuccess ? DBH_OK : hip_fail(e, "handing over to the forward stream");
+    }
+    // (whatever was launched must be waited for, also behind an error)
+    int release() {
+        if (!shared) return DBH_OK;
+        hipError_t e = hipEventRecord(d.classified, stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(d.stream, d.classified, 0);
+        lock.unlock();
+        if (e == hipSuccess) return DBH_OK;
+        (void)hipStreamSynchronize(stream);      // (with the lock released: the other queues launch on)
+        return hip_fail(e, "taking over from the forward stream");
+    }
+};
 }  // namespace
 
 int dbh_classify_pair_deflated(dbh_model* start_model, dbh_model* end_model,
@@ -1348,19 +1235,17 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
                                        double* stage_ms, int32_t* start_calls_host,
                                        int32_t* end_calls_host, float* start_probs_host,
                                        float* end_probs_host) {
+    // ---- validate ----
+    dbh_model* const models[2] = {start_model, end_model};
     dbh_model* m = start_model ? start_model : end_model;
     if (!m || n_reads < 0 || n_streams < 0 || comp_bytes < 0 ||
         combine_mode < DBH_REQUIRE_EITHER || combine_mode > DBH_REQUIRE_BOTH)
         return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
-    if (!offsets_host || !calls_host || (n_streams > 0 && (!streams_host || !comp_host)))
+    if (!offsets_host || !calls_host || (n_streams > 0 && (!streams_host || !comp_host)) ||
+        check_pair(models, scan_size) != DBH_OK)
         return DBH_ERR_INVALID_ARGUMENT;
     const bool both = start_model && end_model;
-    if (both && (start_model->device != end_model->device ||
-                 start_model->n_classes != end_model->n_classes))
-        return DBH_ERR_INVALID_ARGUMENT;
-    for (dbh_model* mj : {start_model, end_model})
-        if (mj && model_steps(mj, scan_size) <= 0) return DBH_ERR_INVALID_ARGUMENT;
     const int64_t total_samples = offsets_host[n_reads] - offsets_host[0];
     if (offsets_host[0] != 0 || total_samples < 0) return DBH_ERR_INVALID_ARGUMENT;
     const int64_t out_bytes = total_samples * 2;
@@ -1371,198 +1256,114 @@ int dbh_classify_pair_deflated_verbose(dbh_model* start_model, dbh_model* end_mo
             r.out_offset + r.out_bytes > out_bytes)
             return DBH_ERR_INVALID_ARGUMENT;
     }
+    // ---- layout ----
     DBH_HIP(hipSetDevice(m->device));
-    dbh_model::Deflated& d = m->deflated;
-    if (!d.stream) DBH_HIP(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    const int C = m->n_classes;
-    // small things travel together: [records | offsets] in, [status | final calls | side calls] out
-    const size_t rec_bytes = ((size_t)n_streams * sizeof(dbh_inflate_stream) + 255) & ~(size_t)255;
-    const size_t off_bytes = ((size_t)(n_reads + 1) * sizeof(int64_t) + 255) & ~(size_t)255;
-    const size_t status_bytes = ((size_t)n_streams * sizeof(int32_t) + 255) & ~(size_t)255;
-    const size_t calls_bytes = ((size_t)n_reads * sizeof(int32_t) + 255) & ~(size_t)255;
-    const size_t in_small = rec_bytes + off_bytes;
-    const size_t out_small = status_bytes + 3 * calls_bytes;
-    const size_t probs_bytes = (size_t)n_reads * C * sizeof(float);
-    size_t token_bytes = 0, work = 0;
-    int st = dbh_inflate_workspace_bytes(out_bytes, n_streams, &token_bytes);
-    for (dbh_model* mj : {start_model, end_model}) {
-        size_t wj = 0;
-        if (mj && st == DBH_OK) st = dbh_classify_workspace_bytes(mj, n_reads, scan_size, &wj);
-        work = std::max(work, wj);
-    }
-    if (st == DBH_OK) st = ensure_host(&d.h_small, &d.h_small_bytes, in_small + out_small);
-    if (st == DBH_OK) st = ensure(&d.d_small, &d.d_small_bytes, in_small + out_small);
-    if (st == DBH_OK) st = ensure(&d.d_comp, &d.d_comp_bytes, (size_t)comp_bytes + 64);
-    if (st == DBH_OK) st = ensure(&d.d_samples, &d.d_samples_bytes, (size_t)out_bytes + 256);
-    if (st == DBH_OK) st = ensure(&d.d_tokens, &d.d_tokens_bytes, token_bytes);
-    if (st == DBH_OK) st = ensure(&d.d_out, &d.d_out_bytes, 2 * probs_bytes + 256);
-    if (st == DBH_OK && work) st = ensure(&d.d_work, &d.d_work_bytes, work);
-    if (st != DBH_OK) return st;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DeflatedQueue& d = m->deflated;
+    if (!d.stream) DBH_HIP(hipStreamCreateWithFlags(&d.stream.h, hipStreamNonBlocking));
+    const dbh_host::DeflatedSmall small(n_streams, n_reads);
+    const size_t probs_bytes = (size_t)n_reads * m->n_classes * sizeof(float);
+    const size_t calls_bytes = (size_t)n_reads * sizeof(int32_t);
+    const size_t work = pair_workspace_bytes(models, n_reads, scan_size);
+    size_t token_bytes = 0;
+    DBH_TRY(dbh_inflate_workspace_bytes(out_bytes, n_streams, &token_bytes));
+    DBH_HIP(d.h_small.reserve(small.total));
+    DBH_HIP(d.d_small.reserve(small.total));
+    DBH_HIP(d.d_comp.reserve((size_t)comp_bytes + 64));
+    DBH_HIP(d.d_samples.reserve((size_t)out_bytes + 256));
+    DBH_HIP(d.d_tokens.reserve(token_bytes));
+    DBH_HIP(d.d_out.reserve(2 * probs_bytes + 256));
+    if (work) DBH_HIP(d.d_work.reserve(work));
+    dbh_owned::Event ev[4];
     if (stage_ms)
-        for (hipEvent_t& e : ev) DBH_HIP(hipEventCreate(&e));
+        for (dbh_owned::Event& e : ev) DBH_HIP(hipEventCreate(&e.h));
     auto done = [&](int status) -> int {
         (void)hipStreamSynchronize(d.stream);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
         return status;
     };
-    char* h = (char*)d.h_small;
-    // the records go over longest stream first (a lane of the decoder takes streams off a counter
-    // in this order: what is long starts early, what is short fills the gaps; streams that need no
-    // decoding last); the status comes back in the same order and is put back below
-    std::vector<int32_t>& order = d.order;
-    order.resize((size_t)n_streams);
-    for (int64_t i = 0; i < n_streams; ++i) order[(size_t)i] = (int32_t)i;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        const dbh_inflate_stream &x = streams_host[a], &y = streams_host[b];
-        // (a shuffled deflate stream is a deflate stream: DBH_INFLATE_ZLIB_SHUFFLE)
-        const bool zx = x.mode == DBH_INFLATE_ZLIB || x.mode == DBH_INFLATE_ZLIB_SHUFFLE;
-        const bool zy = y.mode == DBH_INFLATE_ZLIB || y.mode == DBH_INFLATE_ZLIB_SHUFFLE;
-        const int64_t kx = zx ? x.comp_bytes : -1;
-        const int64_t ky = zy ? y.comp_bytes : -1;
-        return kx != ky ? kx > ky : a < b;
-    });
-    {
-        dbh_inflate_stream* staged = (dbh_inflate_stream*)h;
-        for (int64_t i = 0; i < n_streams; ++i) staged[i] = streams_host[order[(size_t)i]];
-    }
-    std::memcpy(h + rec_bytes, offsets_host, (size_t)(n_reads + 1) * sizeof(int64_t));
-    char* ds = (char*)d.d_small;
-    const dbh_inflate_stream* d_records = (const dbh_inflate_stream*)ds;
-    const int64_t* d_offsets = (const int64_t*)(ds + rec_bytes);
-    int32_t* d_status = (int32_t*)(ds + in_small);
-    int32_t* d_final = (int32_t*)(ds + in_small + status_bytes);
-    int32_t* d_side[2] = {(int32_t*)(ds + in_small + status_bytes + calls_bytes),
-                          (int32_t*)(ds + in_small + status_bytes + 2 * calls_bytes)};
+    // ---- stage and upload ----
+    // the records go over in record_order, the status comes back in it and is put back below
+    char* h = d.h_small.as<char>();
+    dbh_host::record_order(streams_host, n_streams, d.order);
+    for (int64_t i = 0; i < n_streams; ++i)
+        ((dbh_inflate_stream*)(h + small.records))[i] = streams_host[d.order[(size_t)i]];
+    std::memcpy(h + small.offsets, offsets_host, (size_t)(n_reads + 1) * sizeof(int64_t));
     if (ev[0]) (void)hipEventRecord(ev[0], d.stream);
-    hipError_t e = hipMemcpyAsync(ds, h, in_small, hipMemcpyHostToDevice, d.stream);
+    hipError_t e = hipMemcpyAsync(d.d_small.get(), h, small.in_bytes, hipMemcpyHostToDevice, d.stream);
     if (e == hipSuccess && comp_bytes > 0) {
         const void* src = comp_host;
         // the decoder fetches up to 64 bytes beyond the last stream: the loader's buffers carry
         // them; a pageable buffer is staged (and padded) first
         if (!is_pinned(comp_host, (size_t)comp_bytes + 64)) {
-            st = ensure_host(&d.h_comp, &d.h_comp_bytes, (size_t)comp_bytes + 64);
-            if (st != DBH_OK) return done(st);
-            staged_copy(d.h_comp, comp_host, (size_t)comp_bytes);
-            std::memset((char*)d.h_comp + comp_bytes, 0, 64);
-            src = d.h_comp;
+            e = d.h_comp.reserve((size_t)comp_bytes + 64);
+            if (e != hipSuccess) return done(hip_fail(e, "growing the staging buffer"));
+            staged_copy(d.h_comp.get(), comp_host, (size_t)comp_bytes);
+            std::memset(d.h_comp.as<char>((size_t)comp_bytes), 0, 64);
+            src = d.h_comp.get();
         }
-        e = hipMemcpyAsync(d.d_comp, src, (size_t)comp_bytes + 64, hipMemcpyHostToDevice, d.stream);
+        e = hipMemcpyAsync(d.d_comp.get(), src, (size_t)comp_bytes + 64, hipMemcpyHostToDevice, d.stream);
     }
     if (e != hipSuccess) return done(hip_fail(e, "hipMemcpyAsync H2D"));
     if (ev[1]) (void)hipEventRecord(ev[1], d.stream);
+    // ---- decode ----
     // a read without a piece (nothing stored, or nothing readable) must still be zeros
     if (out_bytes > 0) {
-        e = hipMemsetAsync(d.d_samples, 0, (size_t)out_bytes, d.stream);
+        e = hipMemsetAsync(d.d_samples.get(), 0, (size_t)out_bytes, d.stream);
         if (e != hipSuccess) return done(hip_fail(e, "hipMemsetAsync"));
     }
     if (n_streams > 0) {
-        st = dbh_inflate_dev((const uint8_t*)d.d_comp, (int64_t)comp_bytes, d_records, n_streams,
-                             out_bytes, (uint8_t*)d.d_samples, d.d_tokens, d_status, 0,
-                             (dbh_stream)d.stream);
+        const int st = dbh_inflate_dev(d.d_comp.as<uint8_t>(), (int64_t)comp_bytes,
+                                       d.d_small.as<dbh_inflate_stream>(small.records), n_streams,
+                                       out_bytes, d.d_samples.as<uint8_t>(), d.d_tokens.get(),
+                                       d.d_small.as<int32_t>(small.status), 0, (dbh_stream)d.stream);
         if (st != DBH_OK) return done(st);
     }
     if (ev[2]) (void)hipEventRecord(ev[2], d.stream);
-    dbh_model* models[2] = {start_model, end_model};
-    const int32_t* d_calls = both ? d_final : d_side[start_model ? 0 : 1];
+    // ---- classify: both models' launches and combine_calls, as one block on the forward stream ----
     {
-        // both models' launches and combine_calls: on the device's forward stream, as one block
-        const bool shared = shared_forward_stream() && m->device >= 0 && m->device < kMaxDevices;
-        std::unique_lock<std::mutex> block;
-        hipStream_t on = d.stream;
-        if (shared) {
-            e = hipSuccess;
-            if (!d.inflated) e = hipEventCreateWithFlags(&d.inflated, hipEventDisableTiming);
-            if (e == hipSuccess && !d.classified)
-                e = hipEventCreateWithFlags(&d.classified, hipEventDisableTiming);
-            if (e != hipSuccess) return done(hip_fail(e, "hipEventCreateWithFlags"));
-            // The forward kernel's per-workgroup scratch is sized BEFORE the device's lock is taken
-            // (ADVICE round 5): growing it means hipFree / hipMalloc, which synchronise the device,
-            // and under the lock that would stall every other queue's launch.  (Its first 256
-            // bytes - the window counter - are zeroed here when it is new, on this queue's stream,
-            // which the forward stream waits for below.)
-            {
-                void* before = d.d_tail;
-                int cus = 0;
-                for (int j = 0; j < 2; ++j)
-                    if (models[j] && models[j]->cus > cus) cus = models[j]->cus;
-                const int stt = ensure(&d.d_tail, &d.d_tail_bytes,
-                                       256 + (size_t)cus * dbh::kWgScratchFloats * sizeof(float));
-                if (stt != DBH_OK) return done(stt);
-                if (d.d_tail != before) {
-                    e = hipMemsetAsync(d.d_tail, 0, 256, d.stream);
-                    if (e != hipSuccess) return done(hip_fail(e, "hipMemsetAsync"));
-                }
-            }
-            block = std::unique_lock<std::mutex>(g_forward_mutex[m->device]);
-            hipStream_t& fs = g_forward_stream[m->device];
-            if (!fs) {
-                int least = 0, greatest = 0;
-                (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-                e = hipStreamCreateWithPriority(&fs, hipStreamNonBlocking, greatest);
-                if (e != hipSuccess) return done(hip_fail(e, "hipStreamCreateWithPriority"));
-            }
-            on = fs;
-            e = hipEventRecord(d.inflated, d.stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(on, d.inflated, 0);
-            if (e != hipSuccess) return done(hip_fail(e, "handing over to the forward stream"));
-        }
-        for (int j = 0; j < 2; ++j) {
-            if (!models[j]) continue;
-            st = classify_i16_dev(models[j], (const int16_t*)d.d_samples, d_offsets, n_reads,
-                                  j == 0 ? DBH_SIDE_START : DBH_SIDE_END, scan_size, score_diff,
-                                  (float*)((char*)d.d_out + (size_t)j * probs_bytes), d_side[j],
-                                  d.d_work, (dbh_stream)on, 0, 0, 0, &d.d_tail, &d.d_tail_bytes);
-            if (st != DBH_OK) break;
-        }
-        if (st == DBH_OK && both)
-            st = dbh_combine_calls_dev(d_side[0], d_side[1], n_reads, combine_mode, d_final,
-                                       (dbh_stream)on);
-        if (shared) {
-            // (whatever was launched must be waited for, also behind an error)
-            e = hipEventRecord(d.classified, on);
-            if (e == hipSuccess) e = hipStreamWaitEvent(d.stream, d.classified, 0);
-            if (e != hipSuccess) {
-                block.unlock();        // (the wait below must not hold up the other queues' launches)
-                (void)hipStreamSynchronize(on);
-                return done(hip_fail(e, "taking over from the forward stream"));
-            }
-        }
+        const int sides[2] = {DBH_SIDE_START, DBH_SIDE_END};
+        float* const d_probs[2] = {d.d_out.as<float>(), d.d_out.as<float>(probs_bytes)};
+        int32_t* const d_side[2] = {d.d_small.as<int32_t>(small.side_calls[0]),
+                                    d.d_small.as<int32_t>(small.side_calls[1])};
+        ForwardTurn turn{d, m->device};
+        int st = turn.acquire(models);
+        if (st != DBH_OK) return done(st);
+        st = classify_pair_dev(models, sides, d.d_samples.as<int16_t>(),
+                               d.d_small.as<int64_t>(small.offsets), n_reads, scan_size, score_diff,
+                               d_probs, d_side, combine_mode, d.d_small.as<int32_t>(small.final_calls),
+                               d.d_work.get(), turn.stream, ReadHints(), &d.tail);
+        const int back = turn.release();
+        if (back != DBH_OK) return done(back);
         if (st != DBH_OK) return done(st);
     }
     if (ev[3]) (void)hipEventRecord(ev[3], d.stream);
-    e = hipMemcpyAsync(h + in_small, ds + in_small, out_small, hipMemcpyDeviceToHost, d.stream);
+    // ---- download ----
+    e = hipMemcpyAsync(h + small.in_bytes, d.d_small.as<char>(small.in_bytes), small.out_bytes,
+                       hipMemcpyDeviceToHost, d.stream);
     if (e == hipSuccess && samples_host && out_bytes > 0)
-        e = hipMemcpyAsync(samples_host, d.d_samples, (size_t)out_bytes, hipMemcpyDeviceToHost,
+        e = hipMemcpyAsync(samples_host, d.d_samples.get(), (size_t)out_bytes, hipMemcpyDeviceToHost,
                            d.stream);
     // what --verbose prints beside the final call (classify.py:157-171): the sides' probabilities
-    float* side_probs_host[2] = {start_probs_host, end_probs_host};
+    float* const side_probs_host[2] = {start_probs_host, end_probs_host};
     for (int j = 0; j < 2; ++j)
         if (e == hipSuccess && side_probs_host[j] && models[j])
-            e = hipMemcpyAsync(side_probs_host[j], (const char*)d.d_out + (size_t)j * probs_bytes,
+            e = hipMemcpyAsync(side_probs_host[j], d.d_out.as<char>((size_t)j * probs_bytes),
                                probs_bytes, hipMemcpyDeviceToHost, d.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
     if (e != hipSuccess) return done(hip_fail(e, "dbh_classify_pair_deflated"));
-    std::memcpy(calls_host, h + in_small + ((const char*)d_calls - (const char*)d_status),
-                (size_t)n_reads * sizeof(int32_t));
-    // ... and the sides' own calls
-    int32_t* side_calls_host[2] = {start_calls_host, end_calls_host};
+    // ---- scatter: the final calls (one model alone: its own), the sides' own, the status ----
+    std::memcpy(calls_host, h + (both ? small.final_calls : small.side_calls[start_model ? 0 : 1]),
+                calls_bytes);
+    int32_t* const side_calls_host[2] = {start_calls_host, end_calls_host};
     for (int j = 0; j < 2; ++j)
         if (side_calls_host[j] && models[j])
-            std::memcpy(side_calls_host[j],
-                        h + in_small + ((const char*)d_side[j] - (const char*)d_status),
-                        (size_t)n_reads * sizeof(int32_t));
-    if (stream_status_host && n_streams) {
-        const int32_t* sorted_status = (const int32_t*)(h + in_small);
+            std::memcpy(side_calls_host[j], h + small.side_calls[j], calls_bytes);
+    if (stream_status_host)
         for (int64_t i = 0; i < n_streams; ++i)
-            stream_status_host[order[(size_t)i]] = sorted_status[i];
-    }
+            stream_status_host[d.order[(size_t)i]] = ((const int32_t*)(h + small.status))[i];
     if (stage_ms) {
         float ms = 0.f;
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < 3; ++k)
             stage_ms[k] = hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess ? ms : -1.0;
-        }
     }
     return done(DBH_OK);
 }
@@ -1615,16 +1416,13 @@ int dbh_debug_forward(dbh_model* m, const float* x_host, int64_t n, int stage, f
         return DBH_ERR_INVALID_ARGUMENT;
     if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
     const size_t per = (size_t)dbh::kStageFloats[stage];
-    int st = ensure(&m->d_in, &m->in_bytes, (size_t)n * dbh::kWindow * sizeof(float));
-    if (st != DBH_OK) return st;
-    st = ensure(&m->d_work, &m->work_bytes, (size_t)n * per * sizeof(float));
-    if (st != DBH_OK) return st;
-    DBH_HIP(hipMemcpyAsync(m->d_in, x_host, (size_t)n * dbh::kWindow * sizeof(float),
+    DBH_HIP(m->in.reserve((size_t)n * dbh::kWindow * sizeof(float)));
+    DBH_HIP(m->work.reserve((size_t)n * per * sizeof(float)));
+    DBH_HIP(hipMemcpyAsync(m->in.get(), x_host, (size_t)n * dbh::kWindow * sizeof(float),
                            hipMemcpyHostToDevice, 0));
-    DBH_HIP(hipMemsetAsync(m->d_work, 0, (size_t)n * per * sizeof(float), 0));
-    st = launch_forward(m, (const float*)m->d_in, n, nullptr, stage, (float*)m->d_work, 0);
-    if (st != DBH_OK) return st;
-    DBH_HIP(hipMemcpyAsync(out_host, m->d_work, (size_t)n * per * sizeof(float),
+    DBH_HIP(hipMemsetAsync(m->work.get(), 0, (size_t)n * per * sizeof(float), 0));
+    DBH_TRY(launch_forward(m, m->in.as<float>(), n, nullptr, stage, m->work.as<float>(), 0));
+    DBH_HIP(hipMemcpyAsync(out_host, m->work.get(), (size_t)n * per * sizeof(float),
                            hipMemcpyDeviceToHost, 0));
     DBH_HIP(hipStreamSynchronize(0));
     return DBH_OK;
@@ -1655,207 +1453,6 @@ int dbh_forward_truncated_dev(dbh_model* m, const float* x_dev, int64_t n, int l
     return launch_forward(m, x_dev, n, nullptr, 100 + last_stage, nullptr, (hipStream_t)stream);
 }
 
-int dbh_forward_timeline(dbh_model* m, const float* x_host, int64_t n, int64_t* stamps_host) {
-    if (!m || n <= 0 || !x_host || !stamps_host) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    const size_t stamp_bytes = (size_t)n * dbh::kWaves * 64 * sizeof(int64_t);
-    int st = ensure(&m->d_in, &m->in_bytes, (size_t)n * dbh::kWindow * sizeof(float));
-    if (st != DBH_OK) return st;
-    st = ensure(&m->d_work, &m->work_bytes, stamp_bytes);
-    if (st != DBH_OK) return st;
-    st = ensure(&m->d_out, &m->out_bytes, (size_t)n * m->n_classes * sizeof(float));
-    if (st != DBH_OK) return st;
-    DBH_HIP(hipMemcpyAsync(m->d_in, x_host, (size_t)n * dbh::kWindow * sizeof(float),
-                           hipMemcpyHostToDevice, 0));
-    DBH_HIP(hipMemsetAsync(m->d_work, 0, stamp_bytes, 0));
-    {
-        dbh_timeline::ForwardArgs a = {};
-        a.packed = m->d_packed;
-        a.x = (const float*)m->d_in;
-        a.probs = (float*)m->d_out;
-        a.debug_out = (float*)m->d_work;
-        a.n_windows = (long long)n;
-        a.n_classes = m->n_classes;
-        a.debug_stage = 300;
-        a.steps = 1;
-        const unsigned grid = (unsigned)((n + dbh::kGroup - 1) / dbh::kGroup);
-        st = ensure(&m->d_tail, &m->tail_bytes, (size_t)grid * dbh::kWgScratchFloats * sizeof(float));
-        if (st != DBH_OK) return st;
-        a.tail_scratch = (float*)m->d_tail;
-        a.win_counter = nullptr;
-        hipLaunchKernelGGL(dbh_timeline::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, 0, a);
-    }
-    DBH_HIP(hipGetLastError());
-    DBH_HIP(hipMemcpyAsync(stamps_host, m->d_work, stamp_bytes, hipMemcpyDeviceToHost, 0));
-    DBH_HIP(hipStreamSynchronize(0));
-    return DBH_OK;
-}
-
-int dbh_forward_timeline_i16(dbh_model* m, const int16_t* samples_host, int64_t n,
-                             int64_t* stamps_host) {
-    if (!m || n <= 0 || !samples_host || !stamps_host) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    const size_t stamp_bytes = (size_t)n * dbh::kWaves * 64 * sizeof(int64_t);
-    const size_t sample_bytes = (size_t)n * dbh::kWindow * sizeof(int16_t);
-    const size_t offset_bytes = (size_t)(n + 1) * sizeof(int64_t);
-    int st = ensure(&m->d_in, &m->in_bytes, sample_bytes + offset_bytes + 16);
-    if (st != DBH_OK) return st;
-    st = ensure(&m->d_work, &m->work_bytes, stamp_bytes);
-    if (st != DBH_OK) return st;
-    st = ensure(&m->d_out, &m->out_bytes, (size_t)n * (m->n_classes + 1) * sizeof(float));
-    if (st != DBH_OK) return st;
-    std::vector<int64_t> offsets((size_t)n + 1);
-    for (int64_t i = 0; i <= n; ++i) offsets[(size_t)i] = i * dbh::kWindow;
-    char* d_offsets = (char*)m->d_in + ((sample_bytes + 7) & ~(size_t)7);
-    DBH_HIP(hipMemcpyAsync(m->d_in, samples_host, sample_bytes, hipMemcpyHostToDevice, 0));
-    DBH_HIP(hipMemcpyAsync(d_offsets, offsets.data(), offset_bytes, hipMemcpyHostToDevice, 0));
-    DBH_HIP(hipMemsetAsync(m->d_work, 0, stamp_bytes, 0));
-    DBH_HIP(hipStreamSynchronize(0));
-    {
-        dbh_timeline::ForwardArgs a = {};
-        a.packed = m->d_packed;
-        a.probs = (float*)m->d_out;
-        a.debug_out = (float*)m->d_work;
-        a.samples = (const int16_t*)m->d_in;
-        a.offsets = (const long long*)d_offsets;
-        a.calls = (int*)((float*)m->d_out + n * m->n_classes);
-        a.score_diff = 0.5;
-        a.len_hint = (long long)m->hint_len;
-        a.hint_cap = (long long)m->hint_cap;
-        a.n_windows = (long long)n;
-        a.n_classes = m->n_classes;
-        // more windows than CUs: a persistent launch, as in production (stamps per window)
-        a.debug_stage = n > m->cus ? 301 : 300;
-        a.steps = 1;
-        const int64_t groups = (n + dbh::kGroup - 1) / dbh::kGroup;
-        const unsigned grid = (unsigned)(n > m->cus ? (groups < m->cus ? groups : m->cus) : groups);
-        st = ensure(&m->d_tail, &m->tail_bytes, (size_t)grid * dbh::kWgScratchFloats * sizeof(float));
-        if (st != DBH_OK) return st;
-        a.tail_scratch = (float*)m->d_tail;
-        a.win_counter = nullptr;
-        hipLaunchKernelGGL(dbh_timeline::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, 0, a);
-    }
-    DBH_HIP(hipGetLastError());
-    DBH_HIP(hipMemcpyAsync(stamps_host, m->d_work, stamp_bytes, hipMemcpyDeviceToHost, 0));
-    DBH_HIP(hipStreamSynchronize(0));
-    return DBH_OK;
-}
-
-int dbh_forward_timing_enable_span(dbh_model* m, int every_nth, int span) {
-    if (!m || span < 1 || (every_nth > 0 && span > every_nth)) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    m->timing = every_nth > 0 ? every_nth : 0;
-    m->timing_span = span;
-    m->open_stop = nullptr;
-    m->open_windows = 0;
-    m->launch_counter = 0;
-    m->events_used = 0;
-    m->timed_windows = 0;
-    m->timed_launches = 0;
-    return DBH_OK;
-}
-
-int dbh_forward_timing_enable(dbh_model* m, int enable) {
-    if (!m) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    return dbh_forward_timing_enable_span(m, enable, 1);
-}
-
-int dbh_forward_timing_read(dbh_model* m, double* total_ms, int64_t* launches, int64_t* windows) {
-    if (!m || !total_ms || !launches || !windows) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    double sum = 0.0;
-    for (size_t i = 0; i < m->events_used; ++i) {
-        DBH_HIP(hipEventSynchronize(m->events[i].second));
-        float ms = 0.f;
-        DBH_HIP(hipEventElapsedTime(&ms, m->events[i].first, m->events[i].second));
-        sum += ms;
-    }
-    *total_ms = sum;
-    *launches = m->timed_launches;
-    *windows = m->timed_windows;
-    m->events_used = 0;
-    m->timed_windows = 0;
-    m->timed_launches = 0;
-    m->open_stop = nullptr;
-    return DBH_OK;
-}
-
-int dbh_forward_clock_enable(dbh_model* m, int enable) {
-    if (!m) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    m->clock_probe = enable != 0;
-    if (!enable) m->clock_grid = 0;
-    return DBH_OK;
-}
-
-int dbh_forward_clock_read(dbh_model* m, double* shader_ghz) {
-    if (!m || !shader_ghz) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    *shader_ghz = 0.0;
-    if (!m->clock_probe || m->clock_grid == 0 || !m->d_clock) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_HIP(hipSetDevice(m->device));
-    DBH_HIP(hipDeviceSynchronize());
-    const size_t per_wg = 4 + dbh::kPhaseMarks * dbh::kPhaseGroups;
-    std::vector<int64_t> c((size_t)m->clock_grid * per_wg);
-    DBH_HIP(hipMemcpy(c.data(), m->d_clock, c.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-    int wall_khz = 0;      // the rate of s_memrealtime (100 MHz on this hardware)
-    DBH_HIP(hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, m->device));
-    if (wall_khz <= 0) return DBH_ERR_HIP;
-    std::vector<double> ratios;
-    for (unsigned b = 0; b < m->clock_grid; ++b) {
-        const double shader = (double)(c[b * per_wg + 2] - c[b * per_wg]);
-        const double wall = (double)(c[b * per_wg + 3] - c[b * per_wg + 1]);
-        if (shader > 0 && wall > 0) ratios.push_back(shader / wall);
-    }
-    if (ratios.empty()) return DBH_ERR_HIP;
-    std::nth_element(ratios.begin(), ratios.begin() + ratios.size() / 2, ratios.end());
-    *shader_ghz = ratios[ratios.size() / 2] * (double)wall_khz * 1e-6;
-    return DBH_OK;
-}
-
-int dbh_forward_phases_enable(dbh_model* m, int enable) {
-    if (!m) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    m->phase_probe = enable != 0;
-    return DBH_OK;
-}
-
-int dbh_forward_phases_read(dbh_model* m, double* mean_cycles, int64_t* groups) {
-    if (!m || !mean_cycles || !groups) return DBH_ERR_INVALID_ARGUMENT;
-    if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    if (!m->clock_probe || !m->phase_probe || m->clock_grid == 0 || !m->d_clock) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_HIP(hipSetDevice(m->device));
-    DBH_HIP(hipDeviceSynchronize());
-    const size_t per_wg = 4 + dbh::kPhaseMarks * dbh::kPhaseGroups;
-    std::vector<int64_t> c((size_t)m->clock_grid * per_wg);
-    DBH_HIP(hipMemcpy(c.data(), m->d_clock, c.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-    // steady state: not a workgroup's first group (cold), and only groups followed by another one
-    // (the last interval runs to the next group's first stamp)
-    double sum[dbh::kPhaseMarks] = {};
-    int64_t n = 0;
-    for (unsigned b = 0; b < m->clock_grid; ++b) {
-        const int64_t* s = c.data() + b * per_wg + 4;
-        for (int g = 1; g + 1 < dbh::kPhaseGroups; ++g) {
-            const int64_t* a = s + g * dbh::kPhaseMarks;
-            if (a[0] < 0 || a[dbh::kPhaseMarks] < 0 || a[dbh::kPhaseMarks + 1] < 0) break;
-            bool ok = true;
-            double d[dbh::kPhaseMarks];
-            for (int i = 0; i < 5; ++i) {
-                // (the fifth interval runs to the next group's first stamp)
-                const int64_t from = a[i], to = i < 4 ? a[i + 1] : a[dbh::kPhaseMarks];
-                d[i] = (double)(uint32_t)((uint32_t)to - (uint32_t)from);
-                if (d[i] > 4e6) ok = false;                      // (a group that skipped a phase)
-            }
-            for (int i = 5; i < dbh::kPhaseMarks; ++i) d[i] = (double)a[i];      // (sums of intervals)
-            if (!ok) continue;
-            for (int i = 0; i < dbh::kPhaseMarks; ++i) sum[i] += d[i];
-            ++n;
-        }
-    }
-    for (int i = 0; i < dbh::kPhaseMarks; ++i) mean_cycles[i] = n ? sum[i] / (double)n : 0.0;
-    *groups = n;
-    return DBH_OK;
-}
-
 }  // extern "C"
+
+#include "dbh_probes.h"

@@ -47,6 +47,7 @@
 #include "../../include/deepbinner_hip.h"
 #include "dbh_inflate_core.h"
 #include "dbh_inflate_wave.h"
+#include "dbh_owned.h"
 
 namespace dbh_inflate_detail {
 
@@ -830,49 +831,38 @@ int dbh_inflate(const uint8_t* comp_host, size_t comp_bytes, const dbh_inflate_s
             (size_t)(s.out_offset + s.out_bytes) > out_bytes)
             return DBH_ERR_INVALID_ARGUMENT;
     }
-    uint8_t *d_comp = nullptr, *d_out = nullptr;
-    dbh_inflate_stream* d_streams = nullptr;
-    void* d_work = nullptr;
-    int32_t* d_status = nullptr;
+    dbh_owned::DeviceBlock d_comp, d_out, d_streams, d_work, d_status;      // (freed on return)
+    dbh_owned::Event e0, e1;
     size_t work = 0;
     int st = dbh_inflate_workspace_bytes((int64_t)out_bytes, n_streams, &work);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&] {
-        if (d_comp) (void)hipFree(d_comp);
-        if (d_out) (void)hipFree(d_out);
-        if (d_streams) (void)hipFree(d_streams);
-        if (d_work) (void)hipFree(d_work);
-        if (d_status) (void)hipFree(d_status);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    };
-    hipError_t e = hipMalloc((void**)&d_comp, comp_bytes + 64);        // (padded: see the header)
-    if (e == hipSuccess) e = hipMemset(d_comp + comp_bytes, 0, 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes ? out_bytes : 1);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_streams, (size_t)n_streams * sizeof(dbh_inflate_stream));
-    if (e == hipSuccess) e = hipMalloc(&d_work, work);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_status, (size_t)n_streams * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(d_comp, comp_host, comp_bytes, hipMemcpyHostToDevice);
+    hipError_t e = d_comp.reserve(comp_bytes + 64);        // (padded: see the header)
+    if (e == hipSuccess) e = hipMemset(d_comp.as<uint8_t>(comp_bytes), 0, 64);
+    if (e == hipSuccess) e = d_out.reserve(out_bytes ? out_bytes : 1);
+    if (e == hipSuccess) e = d_streams.reserve((size_t)n_streams * sizeof(dbh_inflate_stream));
+    if (e == hipSuccess) e = d_work.reserve(work);
+    if (e == hipSuccess) e = d_status.reserve((size_t)n_streams * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_comp.get(), comp_host, comp_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = hipMemcpy(d_streams, streams_host, (size_t)n_streams * sizeof(dbh_inflate_stream),
+        e = hipMemcpy(d_streams.get(), streams_host, (size_t)n_streams * sizeof(dbh_inflate_stream),
                       hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventCreate(&e0.h);
+    if (e == hipSuccess) e = hipEventCreate(&e1.h);
     if (e == hipSuccess) e = hipEventRecord(e0, nullptr);
     if (e == hipSuccess && st == DBH_OK)
-        st = dbh_inflate_dev(d_comp, (int64_t)comp_bytes, d_streams, n_streams, (int64_t)out_bytes,
-                             d_out, d_work, d_status, streams_per_lane, nullptr);
+        st = dbh_inflate_dev(d_comp.as<uint8_t>(), (int64_t)comp_bytes,
+                             d_streams.as<dbh_inflate_stream>(), n_streams, (int64_t)out_bytes,
+                             d_out.as<uint8_t>(), d_work.get(), d_status.as<int32_t>(),
+                             streams_per_lane, nullptr);
     if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out_host, d_out, out_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_host, d_out.get(), out_bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
-        e = hipMemcpy(status_host, d_status, (size_t)n_streams * sizeof(int32_t),
+        e = hipMemcpy(status_host, d_status.get(), (size_t)n_streams * sizeof(int32_t),
                       hipMemcpyDeviceToHost);
     if (e == hipSuccess && kernel_ms) {
         float ms = 0.f;
         e = hipEventElapsedTime(&ms, e0, e1);
         *kernel_ms = ms;
     }
-    cleanup();
     if (e != hipSuccess) return hip_failed(e, "dbh_inflate");
     return st;
 }

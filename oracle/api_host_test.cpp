@@ -1,0 +1,120 @@
+// TEST INFRASTRUCTURE (oracle/): the host-side arithmetic of libdeepbinner_hip.so's API layer
+// (deepbinner_amd/csrc/dbh_host_layout.h, the very header dbh_api.hip is compiled from) as a program
+// of its own, so that tests/test_api_host.py can hold it to account on the build box, without a
+// GPU - and so that it can run under AddressSanitizer (oracle/Makefile: api_host_test_asan).  Not
+// part of the product; nothing in deepbinner_amd/ calls it.
+//   api_host_test [RECORDS]      RECORDS: a file of dbh_inflate_stream records
+// One line per check, "ok ..." or "FAIL ..."; "model_steps INPUT SCAN = STEPS" and, with RECORDS,
+// "order I J K ..." for the caller to compare.  Exit status 1 if a check failed.
+#include <cstdio>
+#include <cstdlib>
+#include <utility>
+#include <vector>
+
+#include "../deepbinner_amd/csrc/dbh_host_layout.h"
+
+static int g_failed = 0;
+
+static void report(bool ok, const char* what, long a = 0, long b = 0, long c = 0) {
+    std::printf("%s %s %ld %ld %ld\n", ok ? "ok" : "FAIL", what, a, b, c);
+    if (!ok) ++g_failed;
+}
+
+// regions (offset, bytes) in the order they are meant to lie in: each starts where the one before
+// ended (so none overlap and the total is the sum), on a multiple of `align`
+static bool tiles(const std::vector<std::pair<size_t, size_t>>& regions, size_t total, size_t align) {
+    size_t at = 0;
+    for (const auto& r : regions) {
+        if (r.first != at || r.first % align != 0) return false;
+        at += r.second;
+    }
+    return at == total;
+}
+
+static void check_layouts() {
+    using dbh_host::align256;
+    // the small buffer of the deflated path: zero streams, one read, odd counts, a container's worth
+    const long cases[][2] = {{0, 1}, {1, 1}, {3, 1}, {0, 5}, {7, 40}, {64, 64}, {4001, 4000}};
+    for (const auto& c : cases) {
+        const long n_streams = c[0], n_reads = c[1];
+        const dbh_host::DeflatedSmall s(n_streams, n_reads);
+        const size_t calls = align256((size_t)n_reads * 4);
+        const bool ok = tiles({{s.records, align256((size_t)n_streams * sizeof(dbh_inflate_stream))},
+                               {s.offsets, align256((size_t)(n_reads + 1) * 8)},
+                               {s.status, align256((size_t)n_streams * 4)},
+                               {s.final_calls, calls},
+                               {s.side_calls[0], calls},
+                               {s.side_calls[1], calls}},
+                              s.total, 256) &&
+                        s.in_bytes == s.status && s.in_bytes + s.out_bytes == s.total;
+        report(ok, "layout deflated", n_streams, n_reads);
+    }
+    // a group's results on the host path: the start model alone, the end model alone, both
+    for (int has = 1; has <= 3; ++has)
+        for (long n_reads : {1L, 37L})
+            for (int n_classes : {2, 13}) {
+                const bool start = has & 1, end = has & 2;
+                const dbh_host::GroupOut g(n_reads, n_classes, start, end);
+                const size_t probs = (size_t)n_reads * n_classes * 4, calls = (size_t)n_reads * 4;
+                const bool ok = tiles({{g.probs[0], start ? probs : 0},
+                                       {g.probs[1], end ? probs : 0},
+                                       {g.calls[0], start ? calls : 0},
+                                       {g.calls[1], end ? calls : 0},
+                                       {g.final_calls, start && end ? calls : 0}},
+                                      g.total, 4);
+                report(ok, "layout group", has, n_reads, n_classes);
+            }
+}
+
+// destination byte-equal to the source, the guard bytes on both sides untouched; and the pieces
+// the copy is cut into cover the buffer once
+static void check_staged_copy() {
+    const size_t MiB = 1u << 20, kGuard = 64;
+    for (size_t bytes : {(size_t)0, (size_t)1, 16 * MiB - 1, 16 * MiB, 32 * MiB, 32 * MiB + 4097}) {
+        std::vector<unsigned char> src(bytes + 1), dst(bytes + 2 * kGuard, 0xEE);
+        uint32_t x = 0x9E3779B9u ^ (uint32_t)bytes;
+        for (size_t i = 0; i < bytes; ++i) {
+            x = x * 1664525u + 1013904223u;
+            src[i] = (unsigned char)(x >> 24);
+        }
+        dbh_host::staged_copy(dst.data() + kGuard, src.data(), bytes);
+        bool ok = std::memcmp(dst.data() + kGuard, src.data(), bytes) == 0;
+        for (size_t i = 0; i < kGuard; ++i) ok = ok && dst[i] == 0xEE && dst[kGuard + bytes + i] == 0xEE;
+        const dbh_host::CopySplit split = dbh_host::copy_split(bytes);
+        ok = ok && (split.helpers == 0 ? split.share == bytes
+                                       : split.share % 4096 == 0 && split.share * (size_t)(split.helpers + 1) >= bytes &&
+                                             split.share * (size_t)split.helpers < bytes);
+        report(ok, "staged_copy", (long)bytes, split.helpers);
+    }
+}
+
+static void check_uniform_length() {
+    const int64_t same[] = {0, 512, 1024, 1536}, ragged[] = {0, 512, 1024, 1537}, empty[] = {0, 0, 0};
+    report(dbh_host::uniform_length(same, 3) == 512 && dbh_host::uniform_length(same, 1) == 512 &&
+               dbh_host::uniform_length(ragged, 3) == 0 && dbh_host::uniform_length(ragged, 2) == 512 &&
+               dbh_host::uniform_length(empty, 2) == 0,
+           "uniform_length");
+}
+
+int main(int argc, char** argv) {
+    check_layouts();
+    check_staged_copy();
+    check_uniform_length();
+    for (int input : {96, 1024, 2048})
+        for (int scan : {0, 48, 96, 512, 1000, 1024, 1536, 2048, 6144, 6145, 6192})
+            std::printf("model_steps %d %d = %d\n", input, scan, dbh_host::model_steps(input, scan));
+    if (argc > 1) {
+        FILE* in = std::fopen(argv[1], "rb");
+        if (!in) return 2;
+        std::vector<dbh_inflate_stream> records;
+        dbh_inflate_stream r;
+        while (std::fread(&r, sizeof(r), 1, in) == 1) records.push_back(r);
+        std::fclose(in);
+        std::vector<int32_t> order;
+        dbh_host::record_order(records.data(), (int64_t)records.size(), order);
+        std::printf("order");
+        for (int32_t i : order) std::printf(" %d", i);
+        std::printf("\n");
+    }
+    return g_failed ? 1 : 0;
+}

@@ -203,6 +203,62 @@ def test_a_model_on_fewer_cus_and_its_clone_give_the_same_calls(hip, hip_models,
         start.reserve_cus(-1)
 
 
+def deflate_batch(hip, signals, offsets):
+    """The reads as a raw batch for dbh_classify_pair_deflated: one zlib stream per read that has
+    samples (level 1, as build_containers deflates), the 64 bytes of padding behind the last."""
+    streams = [zlib.compress(s.astype('<i2').tobytes(), 1) if len(s) else b'' for s in signals]
+    records = np.zeros(sum(1 for c in streams if c), dtype=hip.INFLATE_STREAM)
+    at = k = 0
+    for i, c in enumerate(streams):
+        if c:
+            records[k] = (at, len(c), 2 * offsets[i], 2 * len(signals[i]), hip.INFLATE_ZLIB, 0)
+            k += 1
+        at += len(c)
+    return np.frombuffer(b''.join(streams) + bytes(64), dtype=np.uint8), records
+
+
+def test_buffers_grow_and_are_reused(hip, hip_models, all_signals):
+    """Fresh clones - nothing of theirs sized yet - through a small batch, a larger one and the
+    small one again, on the host-buffer pipeline (pageable input, one read per group: the three
+    staging slots take turns, grow and are reused) and on the deflated path, with the forward
+    launches going from every CU to one workgroup and back (the per-workgroup scratch grows, and
+    its window counter is zeroed anew): every result is the untouched parent models', bit for bit."""
+    parents = hip_models[START], hip_models[END]
+    start, end = parents[0].clone(), parents[1].clone()
+    few = list(all_signals[:3])
+    many = list(all_signals) + [np.zeros(0, np.int16), np.arange(5, dtype=np.int16),
+                                np.full(300, 7, np.int16)]
+    want = {}
+    try:
+        for m in (start, end):
+            m.set_host_group(12)
+        for step, (signals, reserve) in enumerate(((few, None), (many, 255), (few, 0))):
+            if reserve is not None:
+                start.reserve_cus(reserve)
+                end.reserve_cus(reserve)
+            samples, offsets = pack(signals)
+            if len(signals) not in want:
+                want[len(signals)] = hip.classify_pair(*parents, samples, offsets, 6144, 0.5,
+                                                       'require_either', True, True)
+            calls, sides, probs = want[len(signals)]
+            got = hip.classify_pair(start, end, samples, offsets, 6144, 0.5, 'require_either',
+                                    True, True)
+            assert np.array_equal(got[0], calls), step
+            for j in range(2):
+                assert np.array_equal(got[1][j], sides[j]) and np.array_equal(got[2][j], probs[j]), step
+            comp, records = deflate_batch(hip, signals, offsets)
+            d_calls, status, decoded, d_sides = hip.classify_pair_deflated(
+                start, end, comp, records, offsets, 6144, 0.5, want_samples=True, want_sides=True)
+            assert (status == 0).all() and np.array_equal(decoded, samples), step
+            assert np.array_equal(d_calls, calls), step
+            for j, side in enumerate(('start', 'end')):
+                assert np.array_equal(d_sides[side + '_calls'], sides[j]), step
+                assert np.array_equal(d_sides[side + '_probs'], probs[j]), step
+    finally:
+        start.close()
+        end.close()
+
+
 @pytest.fixture(scope='module')
 def containers(tmp_path_factory, gold):
     directory = str(tmp_path_factory.mktemp('stream'))
