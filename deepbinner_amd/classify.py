@@ -21,7 +21,7 @@ from . import hdf5_lite
 from .load_fast5s import (find_all_fast5s, get_read_id_and_signal,
                           determine_single_or_multi_fast5s, LoaderPool, choose_loader_procs,
                           reader_kind)
-from .misc import print_summary_table, usable_cpus
+from .misc import print_summary_table, usable_cpus      # noqa: F401 (the tools' classify.usable_cpus)
 from .model_format import ModelWeights
 from .trim_signal import normalise
 
@@ -205,21 +205,21 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
 
     classifications, read_id_to_fast5_file = {}, {}
 
-    results = (classify_units if multi_read else _one_read_batches)(
-        fast5_files, start_model, start_input_size, end_model, end_input_size, output_size, args)
-    finished = 0
-    for files, calls, lines, finished in results:
-        read_id_to_fast5_file.update(files)
-        classifications.update(calls)
+    def rows(lines):
         if full_output:
             for line in lines:
                 print(line)
+
+    def progress(finished):
         # (--multi_read counts files, where a file may hold any number of reads)
         print_classification_progress(finished if multi_read else len(classifications),
                                       len(fast5_files), 'fast5s', out_dest=out_dest)
+
+    finished = tabulate_units(
+        classify_units(fast5_files, start_model, start_input_size, end_model, end_input_size,
+                       output_size, args), classifications, read_id_to_fast5_file, rows, progress)
     if multi_read and finished < len(fast5_files):      # (files without a readable read, last)
-        print_classification_progress(len(fast5_files), len(fast5_files), 'fast5s',
-                                      out_dest=out_dest)
+        progress(len(fast5_files))
 
     if full_output:
         print('', file=sys.stderr)
@@ -228,98 +228,55 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
     return classifications, read_id_to_fast5_file
 
 
-def _one_read_batches(fast5_files, start_model, start_input_size, end_model, end_input_size,
-                      output_size, args, set_aside=None):
-    """The per-batch loop over one-read files (reference classify.py:141-171), a generator:
-    (its reads' files, calls, table rows, how many files it covered) per batch, in order.
-    ``set_aside`` (--multi_read): a list that takes the multi-read files met on the way, which
-    are an error without it."""
-
-    def classify_loaded(loaded, start_replica, end_replica):
-        """One loaded batch on one device -> (its reads' files, calls, table rows, files)."""
-        if isinstance(loaded, RawBatch):
-            return (_classify_raw_batch(loaded, start_replica, end_replica, args) +
-                    (len(loaded.files) - loaded.set_aside,))
-        files, read_ids, signals = {}, [], []
-        for fast5_file, read_id, signal in loaded:
-            if signal is None:
-                continue
-            files[read_id] = fast5_file
-            read_ids.append(read_id)
-            signals.append(signal)
-        if getattr(loaded, 'complete', False):      # nothing was skipped: the packed buffer
-            signals = PackedSignals(signals, loaded.samples, loaded.offsets)   # is these reads
-        calls = {}
-        lines = classify_read_batch(read_ids, signals, start_replica, start_input_size,
-                                    end_replica, end_input_size, output_size, args, calls)
-        return files, calls, lines, len(loaded) - getattr(loaded, 'set_aside', 0)
-
-    replicas = device_replicas(start_model, end_model)
-    host_share = raw_inflate_share(start_model, end_model, args, len(fast5_files), replicas)
-    queues = []
-    if host_share is None:
-        batches = load_in_batches(fast5_files, args,
-                                  scanned_end_samples(args.scan_size, start_input_size, end_input_size),
-                                  set_aside)
-    else:
-        # Signals as stored, inflated on the GPU beside the classification of the batch before:
-        # several batches in flight per GPU, each on a replica of the models (DESIGN.md 12)
-        from . import realtime
-        replicas, queues = realtime.inflate_queues(replicas, host_share)
-        batches = _raw_batches(fast5_files, args, host_share, len(replicas), set_aside)
-    try:
-        yield from dispatch_batches(batches, replicas, classify_loaded)
-    finally:
-        for model in queues:                # the forward kernel gets every CU back
-            model.reserve_cus(0)
+def tabulate_units(results, classifications, read_id_to_fast5_file, rows, progress):
+    """The consumer of classify_units: every unit's reads into the two dicts, its table rows to
+    ``rows`` and the files finished so far to ``progress`` -> how many files that was."""
+    finished = 0
+    for unit in results:
+        read_id_to_fast5_file.update(unit.files())
+        classifications.update(zip(unit.ids, unit.names))
+        rows(unit.lines)
+        finished += unit.n_files
+        progress(finished)
+    return finished
 
 
 def classify_units(fast5_files, start_model, start_input_size, end_model, end_input_size,
-                   output_size, args):
-    """``classify --multi_read``: the reads of ``fast5_files`` - multi-read containers, one-read
-    files, or both - classified where they are; a generator: (its reads' files, calls, table
-    rows, files finished so far) per unit of work.  Five sampled files pick the route
-    (determine_single_or_multi_fast5s): containers go through the units ``realtime`` uses
-    (containers.py: one container = one unit, a stray one-read file is a container of one read),
-    in the order of the file list and reads in container order; a directory of one-read files
-    goes through the one-read batch paths, and a container met there is set aside and classified
-    after them."""
+                   output_size, args, host_loader=False):
+    """The reads of ``fast5_files`` classified unit by unit (containers.py), a generator of
+    ``containers.Result``: the per-batch loop over one-read files (reference classify.py:141-171)
+    - ``host_loader``: through load_in_batches whatever raw_inflate_share says - where a
+    multi-read file is an error; with ``--multi_read`` five sampled files pick the route
+    (determine_single_or_multi_fast5s): containers go one container = one unit (a stray one-read
+    file is a container of one read), in the order of the file list and reads in container order;
+    a directory of one-read files goes through the one-read batches, and a container met there is
+    set aside and classified after them."""
     from . import containers
-    if not fast5_files:
-        return
     fast5_files = list(fast5_files)
-    models = (start_model, start_input_size, end_model, end_input_size, output_size)
-    finished = 0
-    if determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
-        later = fast5_files
-    else:
-        later = []
-        singles = fast5_files
-        if reader_kind() == 'python':
-            # (the Python loader's processes cannot hand a file back: look before loading)
-            later = [f for f in fast5_files if _python_holds_several_reads(f)]
-            aside = set(later)
-            singles = [f for f in fast5_files if f not in aside]
-        for files, calls, lines, n_files in _one_read_batches(singles, *models, args,
-                                                              set_aside=later):
-            finished += n_files
-            yield files, calls, lines, finished
-    if not later:
+    if not fast5_files:
         return
     units = containers.Units(args, start_input_size, end_input_size, output_size,
                              keep=scanned_end_samples(args.scan_size, start_input_size,
                                                       end_input_size),
                              want_rows=True, threads=int(getattr(args, 'loader_procs', 0) or 0),
                              skip_damaged=True)
-    items, work, replicas, queues = containers.route(later, start_model, end_model, units)
-    try:
-        for unit in dispatch_batches(items, replicas, work):
-            files = dict.fromkeys(unit.ids, unit.path)
-            yield (files, dict(zip(unit.ids, unit.names)), unit.lines,
-                   finished + unit.number - (0 if unit.last else 1))
-    finally:
-        for model in queues:                # the forward kernel gets every CU back
-            model.reserve_cus(0)
+    multi_read = bool(getattr(args, 'multi_read', False))
+    later = [] if multi_read else None
+    if multi_read and determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
+        later = fast5_files
+    else:
+        singles = fast5_files
+        if multi_read and reader_kind() == 'python':
+            # (the Python loader's processes cannot hand a file back: look before loading)
+            later = [f for f in fast5_files if _python_holds_several_reads(f)]
+            aside = set(later)
+            singles = [f for f in fast5_files if f not in aside]
+        with containers.route(singles, start_model, end_model, units, one_read=True,
+                              set_aside=later, host_loader=host_loader) as results:
+            yield from results
+    if later:
+        with containers.route(later, start_model, end_model, units) as results:
+            yield from results
 
 
 def _python_holds_several_reads(fast5_file):
@@ -392,94 +349,6 @@ def raw_inflate_share(start_model, end_model, args, n_files, replicas):
     return share if share < 100 else None
 
 
-class RawBatch:
-    """A batch of one-read files with their Signals as stored (fast5_native.load_batch_raw)."""
-
-    def __init__(self, files, loaded):
-        self.files = list(files)
-        self.read_ids, self.offsets, self.status, self.comp, self.records = loaded
-        self.set_aside = 0          # multi-read files among them, left for the container units
-
-
-def _raw_batches(fast5_files, args, host_share, n_queues, set_aside=None):
-    """RawBatch after RawBatch, loaded ahead of the GPU: two loads at a time on background
-    threads (each on half of the loader's threads), as many waiting as there are queues.
-    ``set_aside``: see _native_batches."""
-    import collections
-    from concurrent.futures import ThreadPoolExecutor
-    from . import fast5_native
-    threads = int(getattr(args, 'loader_procs', 0) or 0) or max(1, min(32, usable_cpus()))
-    size = max(int(args.batch_size), RAW_BATCH_FILES)
-    chunks = list(chunker(fast5_files, size))
-
-    def load(chunk):
-        # DEEPBINNER_VBZ_ZSTD=gpu: VBZ chunks keep their zstd stage for the GPU (default: host);
-        # DEEPBINNER_SHUFFLE=gpu: so do shuffled chunks their shuffle
-        return RawBatch(chunk, fast5_native.load_batch_raw(chunk, max(1, threads // 2),
-                                                            -host_share,
-                                                            vbz_zstd=fast5_native.vbz_zstd_route(),
-                                                            shuffle=fast5_native.shuffle_route()))
-
-    with ThreadPoolExecutor(max_workers=2, thread_name_prefix='deepbinner-raw-loader') as pool:
-        waiting = collections.deque()
-        upcoming = iter(chunks)
-        for chunk in upcoming:
-            waiting.append(pool.submit(load, chunk))
-            if len(waiting) > n_queues:
-                break
-        while waiting:
-            batch = waiting.popleft().result()
-            chunk = next(upcoming, None)
-            if chunk is not None:
-                waiting.append(pool.submit(load, chunk))
-            multi = (batch.status == fast5_native.F5_ERR_MULTI)
-            if multi.any():
-                if set_aside is None:
-                    sys.exit('Error: Deepbinner does not (yet) support multi-read fast5 files')
-                set_aside.extend(f for f, m in zip(batch.files, multi.tolist()) if m)
-                batch.set_aside = int(multi.sum())
-            warn_about_filters(batch.status)
-            yield batch
-
-
-def _classify_raw_batch(batch, start_replica, end_replica, args):
-    """One RawBatch on one queue -> (its reads' files, calls, table rows): upload, inflate, both
-    models and combine_calls in one call of the C ABI; a stream the GPU's decoder refuses is
-    inflated again by the host's loader, which has the last word."""
-    from . import fast5_native, hip_backend
-    both = start_replica is not None and end_replica is not None
-    verbose = bool(getattr(args, 'verbose', False))
-    result = hip_backend.classify_pair_deflated(
-        start_replica, end_replica, batch.comp, batch.records, batch.offsets, int(args.scan_size),
-        args.score_diff, combine_mode(args) if both else 'require_either', want_sides=verbose)
-    numbers, stream_status = result[0], result[1]
-    sides = result[2] if verbose else None
-    read_ids = list(batch.read_ids)
-    redone = {}           # read index -> its verbose row, for reads the host had to decode
-    for i in sorted(set(batch.records['read'][stream_status != 0].tolist())):
-        ids, samples, offsets, status = fast5_native.load_batch(
-            [batch.files[i]], scanned_end_samples(args.scan_size,
-                                                  models_input_size(start_replica, end_replica)), 1)
-        warn_about_filters(status)       # (damage only the GPU's VBZ self-checks could see)
-        if status[0] != 0:
-            read_ids[i] = None
-            continue
-        if verbose:
-            redone[i] = redone_verbose_row(read_ids[i], samples[offsets[0]:offsets[1]],
-                                           start_replica, end_replica, args)
-            numbers[i] = call_number(redone[i])
-        else:
-            numbers[i] = classify_packed_numbers(samples, offsets, start_replica, end_replica,
-                                                 args)[0]
-    files, calls = {}, {}
-    for read_id, fast5_file, number in zip(read_ids, batch.files, numbers.tolist()):
-        if read_id is not None:
-            files[read_id] = fast5_file
-            calls[read_id] = _CALL_NAMES[number]
-    return files, calls, raw_table_rows(read_ids, numbers, sides, redone, start_replica,
-                                        end_replica, verbose)
-
-
 def redone_verbose_row(read_id, signal, start_replica, end_replica, args):
     """The verbose row of one read the host had to decode after the GPU's decoder refused its
     stream: the per-read path of every other route (classify_read_batch)."""
@@ -489,9 +358,9 @@ def redone_verbose_row(read_id, signal, start_replica, end_replica, args):
         end_replica, getattr(end_replica, 'input_size', None), model.n_classes, args, {})[0]
 
 
-def call_number(row):
-    """The call number (0 = 'none') a table row carries."""
-    return _CALL_NAMES.index(row.split('\t')[1])
+def call_number(name):
+    """The call number (0 = 'none') of a call as the table prints it: call_name's inverse."""
+    return _CALL_NUMBERS[name]
 
 
 def raw_table_rows(read_ids, numbers, sides, redone, start_replica, end_replica, verbose):
@@ -524,21 +393,23 @@ def raw_table_rows(read_ids, numbers, sides, redone, start_replica, end_replica,
 
 def load_in_batches(fast5_files, args, keep=None, set_aside=None):
     """The reference's ``for fast5_batch in chunker(...)`` + per-file load (classify.py:141-150):
-    yields, per batch of ``args.batch_size`` files, the list of (fast5_file, read_id, signal).
-    With more than one loader process (``--loader_procs``, or automatically for big jobs) the
-    files of later batches are loaded while the caller classifies the current one.  ``keep``:
-    samples per read end the loaders keep (scanned_end_samples of the models; None = what
-    1024-sample models need).  ``set_aside``: see _native_batches (the Python loaders leave on a
-    multi-read file whatever it is)."""
+    yields, per batch of ``args.batch_size`` files, its unit (containers.py): the packed buffer of
+    the native loader, or the lists of the Python loaders.  With more than one loader process
+    (``--loader_procs``, or automatically for big jobs) the files of later batches are loaded
+    while the caller classifies the current one.  ``keep``: samples per read end the loaders keep
+    (scanned_end_samples of the models; None = what 1024-sample models need).  ``set_aside``: see
+    containers.containers_among (the Python loaders leave on a multi-read file whatever it is)."""
+    from . import containers
     if keep is None:
         keep = scanned_end_samples(args.scan_size)
     if reader_kind() == 'native':
-        yield from _native_batches(fast5_files, args, keep, set_aside)
+        yield from containers.packed_batches(fast5_files, args, keep, set_aside)
         return
     procs = choose_loader_procs(getattr(args, 'loader_procs', None), len(fast5_files))
     if procs <= 1:
         for fast5_batch in chunker(fast5_files, args.batch_size):
-            yield [(f,) + tuple(get_read_id_and_signal(f)) for f in fast5_batch]
+            yield containers.list_batch([(f,) + tuple(get_read_id_and_signal(f))
+                                         for f in fast5_batch])
         return
     # only the scanned ends of a read matter to call_batch: spare the result pipe the middle
     with LoaderPool(procs) as pool:
@@ -546,45 +417,10 @@ def load_in_batches(fast5_files, args, keep=None, set_aside=None):
         for item in pool.load(list(fast5_files), keep):
             batch.append(item)
             if len(batch) == args.batch_size:
-                yield batch
+                yield containers.list_batch(batch)
                 batch = []
         if batch:
-            yield batch
-
-
-def _native_batches(fast5_files, args, keep, set_aside=None):
-    """load_in_batches on the native loader (libdeepbinner_fast5.so): every batch is parsed and
-    inflated by the library's own worker threads (``--loader_procs`` of them; 0 = one per hardware
-    thread this process may keep busy - misc.usable_cpus - at most 32), and the next batch is loaded on a background thread - the
-    call releases the GIL - while the caller classifies the current one.  A multi-read file ends
-    the run, unless the caller gave a list to ``set_aside`` such files in (--multi_read): then
-    the batch goes on without them."""
-    from concurrent.futures import ThreadPoolExecutor
-    from . import fast5_native
-    threads = int(getattr(args, 'loader_procs', 0) or 0) or max(1, min(32, usable_cpus()))
-    batches = list(chunker(fast5_files, args.batch_size))
-
-    def load(batch):
-        return fast5_native.load_batch(batch, keep, threads)
-
-    with ThreadPoolExecutor(max_workers=1) as executor:
-        pending = executor.submit(load, batches[0]) if batches else None
-        for i, batch in enumerate(batches):
-            read_ids, samples, offsets, status = pending.result()
-            pending = executor.submit(load, batches[i + 1]) if i + 1 < len(batches) else None
-            multi = (status == fast5_native.F5_ERR_MULTI)
-            if multi.any() and set_aside is None:
-                sys.exit('Error: Deepbinner does not (yet) support multi-read fast5 files')
-            warn_about_filters(status)
-            loaded = PackedBatch((f, read_ids[k], samples[offsets[k]:offsets[k + 1]]
-                                  if read_ids[k] is not None else None)
-                                 for k, f in enumerate(batch))
-            loaded.samples, loaded.offsets = samples, offsets
-            loaded.complete = all(r is not None for r in read_ids)
-            if multi.any():
-                set_aside.extend(f for f, m in zip(batch, multi.tolist()) if m)
-                loaded.set_aside = int(multi.sum())
-            yield loaded
+            yield containers.list_batch(batch)
 
 
 _FILTER_WARNING_GIVEN = False
@@ -601,24 +437,6 @@ def warn_about_filters(status):
         _FILTER_WARNING_GIVEN = True
         print('\nWarning: skipping reads whose signal is compressed with a filter this build '
               'cannot decode (VBZ?); convert them with compress_fast5 -c gzip', file=sys.stderr)
-
-
-class PackedBatch(list):
-    """What the native loader returns for a batch - the (fast5_file, read_id, signal) triples the
-    reference's loop builds - together with the packed buffer the signals are slices of:
-    ``samples`` / ``offsets`` in exactly the layout the C ABI takes (dbh_classify_i16), so that
-    a batch without unreadable files can go to the GPU as it is (``complete``)."""
-    samples = offsets = None
-    complete = False
-    set_aside = 0           # multi-read files among them, left for the container units
-
-
-class PackedSignals(list):
-    """The list of signals ``call_batch`` is handed, plus the packed form of the same reads."""
-
-    def __init__(self, signals, samples, offsets):
-        super().__init__(signals)
-        self.packed = (samples, offsets)
 
 
 _HELPER = __import__('threading').local()
@@ -641,6 +459,7 @@ def _independent_models(start_model, end_model):
 
 
 _CALL_NAMES = ['none'] + [str(i) for i in range(1, 256)]
+_CALL_NUMBERS = {name: number for number, name in enumerate(_CALL_NAMES)}
 
 
 def call_name(number):
@@ -648,10 +467,10 @@ def call_name(number):
     return _CALL_NAMES[number]
 
 
-def _array_path(signals, start_model, end_model):
+def _array_path(packed, start_model, end_model):
     """A packed batch and GPU models only: the calls can stay arrays until the table is printed."""
     models = [m for m in (start_model, end_model) if m is not None]
-    return (getattr(signals, 'packed', None) is not None and bool(models)
+    return (packed is not None and bool(models)
             and all(hasattr(m, 'classify_packed') for m in models)
             and (len(models) == 1 or models[0] is not models[1]))
 
@@ -690,10 +509,10 @@ def classify_packed_numbers(samples, offsets, start_model, end_model, args):
     return model.classify_packed(samples, offsets, side, scan_size, args.score_diff)[1]
 
 
-def _classify_packed_batch(read_ids, signals, start_model, end_model, args, classifications):
+def _classify_packed_batch(read_ids, packed, start_model, end_model, args, classifications):
     """classify_read_batch for a packed batch and non-verbose output (no probabilities to print):
     call numbers as arrays, turned into the same strings and table rows at the end."""
-    samples, offsets = signals.packed
+    samples, offsets = packed
     final = classify_packed_numbers(samples, offsets, start_model, end_model, args)
     names = [_CALL_NAMES[c] for c in final.tolist()]
     classifications.update(zip(read_ids, names))
@@ -701,30 +520,34 @@ def _classify_packed_batch(read_ids, signals, start_model, end_model, args, clas
 
 
 def classify_read_batch(read_ids, signals, start_model, start_input_size, end_model,
-                        end_input_size, output_size, args, classifications):
+                        end_input_size, output_size, args, classifications, packed=None):
     """The body of the reference's per-batch loop (classify.py:141-171) for reads already in
-    memory: run the model(s), combine, record calls, and return the TSV lines."""
+    memory: run the model(s), combine, record calls, and return the TSV lines.  ``packed``: the
+    same reads as (samples, offsets) in the layout the C ABI takes (dbh_classify_i16), where the
+    native loader left them so - ``signals`` may then be None."""
     using_read_starts = start_model is not None
     using_read_ends = end_model is not None
-    if not args.verbose and _array_path(signals, start_model, end_model):
-        return _classify_packed_batch(read_ids, signals, start_model, end_model, args,
+    if not args.verbose and _array_path(packed, start_model, end_model):
+        return _classify_packed_batch(read_ids, packed, start_model, end_model, args,
                                       classifications)
+    if signals is None:
+        signals = [packed[0][packed[1][i]:packed[1][i + 1]] for i in range(len(read_ids))]
     start_calls = start_probs = end_calls = end_probs = None
     if using_read_starts and using_read_ends and _independent_models(start_model, end_model):
         # the two models' host <-> device round trips side by side: the end model's call runs on
         # a helper thread (the C ABI releases the GIL and each model has its own streams)
         pending = _helper_thread().submit(call_batch, end_input_size, output_size, read_ids,
-                                          signals, end_model, args, 'end')
+                                          signals, end_model, args, 'end', packed)
         start_calls, start_probs = call_batch(start_input_size, output_size, read_ids, signals,
-                                              start_model, args, 'start')
+                                              start_model, args, 'start', packed)
         end_calls, end_probs = pending.result()
     else:
         if using_read_starts:
             start_calls, start_probs = call_batch(start_input_size, output_size, read_ids,
-                                                  signals, start_model, args, 'start')
+                                                  signals, start_model, args, 'start', packed)
         if using_read_ends:
             end_calls, end_probs = call_batch(end_input_size, output_size, read_ids, signals,
-                                              end_model, args, 'end')
+                                              end_model, args, 'end', packed)
     lines = []
     for i, read_id in enumerate(read_ids):
         if using_read_starts and using_read_ends:
@@ -873,8 +696,9 @@ def combine_call_numbers(start_calls, end_calls, args):
     return np.where(start_calls == end_calls, start_calls, np.where(keep, start_calls, other))
 
 
-def call_batch(input_size, output_size, read_ids, signals, model, args, side):
-    """Reference classify.py:325-384 -> (barcode_calls, probabilities)."""
+def call_batch(input_size, output_size, read_ids, signals, model, args, side, packed=None):
+    """Reference classify.py:325-384 -> (barcode_calls, probabilities).  ``packed`` (not in the
+    reference): see classify_read_batch."""
     assert side in ('start', 'end')
     step_size = input_size // 2
     steps = int(args.scan_size / step_size)
@@ -885,14 +709,13 @@ def call_batch(input_size, output_size, read_ids, signals, model, args, side):
 
     if hasattr(model, 'classify_signals'):
         # Seam b2: the whole of this function runs on the GPU.
-        packed = getattr(signals, 'packed', None)
         if packed is not None and hasattr(model, 'classify_packed'):
             probs, calls = model.classify_packed(packed[0], packed[1], side, int(args.scan_size),
                                                  args.score_diff)
         else:
             probs, calls = model.classify_signals(signals, side, int(args.scan_size),
                                                   args.score_diff)
-        barcode_calls = ['none' if c == 0 else str(int(c)) for c in calls]
+        barcode_calls = [call_name(c) for c in np.asarray(calls).tolist()]
         return barcode_calls, [row for row in probs]
 
     # Seam b1: host windowing around model.predict.

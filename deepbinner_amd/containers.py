@@ -1,25 +1,33 @@
 """
-Multi-read fast5 containers as units of work, shared by ``deepbinner realtime`` (which bins their
-reads) and ``deepbinner classify --multi_read`` (which tabulates them).  The reference unpacks a
-container with an external tool first (realtime.py:183-190) and refuses it in ``classify``
-(classify.py:113-116); here the reads are classified where they are, by one of three routes:
+The units of work of the classify path, shared by ``deepbinner classify`` (which tabulates their
+reads) and ``deepbinner realtime`` (which bins them).  A unit is a multi-read fast5 container - the
+reference unpacks one with an external tool first (realtime.py:183-190) and refuses it in
+``classify`` (classify.py:113-116); here its reads are classified where they are - or a batch of
+one-read files, which is a container whose reads happen to live in separate files: its ``origin``
+(``Container`` / ``OneReadFiles``) says which file read i is and reads it again through the host's
+loader, and nothing else tells the two apart.  A unit goes one of three routes:
 
-* **raw** - ``fast5_native.stream_raw``: the Signal chunks as stored go to the GPU, which inflates
-  them (and undoes streamvbyte / zstd of VBZ chunks) beside the classification of the container
-  before: ``hip_backend.classify_pair_deflated``.  A stream the device decoder refuses is read
-  again by the host's loader, which has the last word.
-* **packed** - ``fast5_native.stream_reads``: the loader's thread team inflates, the packed buffer
-  of a container goes to the C ABI as it is.
-* **lists** - the Python reader, or models without the packed entry point: ``--batch_size`` reads
-  at a time through ``classify.classify_read_batch``.
+* **raw** - ``fast5_native.stream_raw`` / ``load_batch_raw``: the Signal chunks as stored go to the
+  GPU, which inflates them (and undoes streamvbyte / zstd of VBZ chunks, and HDF5's shuffle) beside
+  the classification of the unit before: ``classify_raw`` -> ``hip_backend.classify_pair_deflated``.
+  A stream the device decoder refuses is read again by the host's loader, which has the last word.
+* **packed** - ``fast5_native.stream_reads`` / ``load_batch``: the loader's thread team inflates,
+  the packed buffer of the unit goes to the C ABI as it is (``classify_packed``).
+* **lists** - the Python reader, or containers for models without the packed entry point:
+  ``--batch_size`` reads at a time through ``classify.classify_read_batch`` (``classify_lists``).
 
 ``route`` picks one (the rule is ``realtime``'s: DEEPBINNER_GPU_INFLATE,
-DEEPBINNER_HOST_INFLATE_SHARE, DEEPBINNER_LOADER_DEPTH, DEEPBINNER_VBZ_ZSTD, DEEPBINNER_SHUFFLE)
-and hands back the stream of units and the function ``classify.dispatch_batches`` runs on each.
+DEEPBINNER_HOST_INFLATE_SHARE, DEEPBINNER_LOADER_DEPTH, DEEPBINNER_VBZ_ZSTD, DEEPBINNER_SHUFFLE;
+for one-read files ``classify.raw_inflate_share`` adds its own conditions) and hands back, as a
+context manager, the stream of classified units (``Result``) in the order they went in.
 """
 
+import collections
+import contextlib
 import functools
 import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -29,13 +37,13 @@ from .misc import usable_cpus
 
 
 class Units:
-    """What the container units need from their caller: the run's ``args`` and model geometry,
-    the samples per read end the loaders keep (``keep``; None = whole signals), whether the whole
-    signals are wanted back (``want_signals``: ``realtime``'s Python writer), whether the rows of
+    """What the units need from their caller: the run's ``args`` and model geometry, the samples
+    per read end the loaders keep (``keep``; None = whole signals), whether the whole signals are
+    wanted back (``want_signals``: ``realtime``'s Python writer), whether the rows of
     ``classify``'s table are (``want_rows``), the loader threads asked for (0 = automatic), and
-    what the lists route does at a read it cannot read: ``skip_damaged`` goes on behind it, as
-    the native routes do (``classify --multi_read``); without it the container ends there
-    (``realtime``, as ever)."""
+    what the lists route does at a read of a container it cannot read: ``skip_damaged`` goes on
+    behind it, as the native routes do (``classify --multi_read``); without it the container ends
+    there (``realtime``, as ever)."""
 
     def __init__(self, args, start_size, end_size, n_classes, keep=None, want_signals=False,
                  want_rows=False, threads=0, skip_damaged=False):
@@ -46,89 +54,103 @@ class Units:
         self.skip_damaged = bool(skip_damaged)
 
 
+class Container:
+    """The origin of a unit whose reads are those of one multi-read container; its forward
+    launches leave CUs to the inflate kernels by its streams (realtime.inflate_cus_for)."""
+    files = None            # (every read's file is ``path``)
+    reserves_cus = True
+
+    def __init__(self, path):
+        self.path = path
+
+    def reread(self, i):
+        """Read i again by the host's loader -> (ids, samples, offsets, status)."""
+        from . import fast5_native
+        try:
+            return fast5_native.load_reads(self.path, first=i, count=1, threads=1)
+        except OSError:
+            return None, None, None, np.ones(1, dtype=np.int32)
+
+
+class OneReadFiles:
+    """The origin of a unit whose read i is the read of ``files[i]``; the host's loader reads it
+    again with the ``keep`` samples per end of every other batch."""
+    path = None
+    reserves_cus = False
+
+    def __init__(self, files, keep=None):
+        self.files, self.keep = files, keep
+
+    def reread(self, i):
+        from . import fast5_native
+        return fast5_native.load_batch([self.files[i]], self.keep, 1)
+
+
+class Unit:
+    """One unit on its way to its route's work function: its ``origin``, the read ``ids`` (None
+    for a read nobody could read: raw route only), container ``number`` (from 1, in the order of
+    the file list), how many files of the list are done with it (``n_files``), whether it is its
+    container's ``last``, and what the route carries: ``offsets`` + ``comp`` + ``records`` (raw),
+    ``samples`` + ``offsets`` + ``where`` (packed) or ``signals`` (lists)."""
+
+    def __init__(self, origin, ids, number=0, n_files=1, last=True, **carried):
+        self.origin, self.ids = origin, ids
+        self.number, self.n_files, self.last = number, n_files, last
+        self.__dict__.update(carried)
+
+
 class Result:
-    """One classified unit: container ``number`` (from 1, in the order of the file list) and
-    ``path``, the ``ids`` and call ``names`` of its readable reads, ``signal(k)`` -> read k's
-    whole signal (None unless wanted), ``where`` - which read of the container each one is (None
-    on the lists route), the table ``lines`` (None unless wanted) and ``last``: whether this is
-    the container's last unit."""
-    __slots__ = ('number', 'path', 'ids', 'names', 'signal', 'where', 'lines', 'last')
+    """One classified unit: container ``number`` and ``path`` (None for one-read files), the
+    ``ids`` and call ``names`` of its readable reads, ``signal(k)`` -> read k's whole signal (None
+    unless wanted), ``where`` - which read of the unit each one is (None on the lists route), the
+    table ``lines`` (None unless wanted), ``last``: whether this is the container's last unit, and
+    ``n_files``: how many files of the list are finished with it."""
+    __slots__ = ('number', 'path', 'ids', 'names', 'signal', 'where', 'lines', 'last', 'n_files',
+                 '_files')
 
-    def __init__(self, number, path, ids, names, signal=None, where=None, lines=None, last=True):
-        self.number, self.path, self.ids, self.names = number, path, ids, names
-        self.signal, self.where, self.lines, self.last = signal, where, lines, last
+    def __init__(self, unit, ids, names, signal=None, where=None, lines=None):
+        self.number, self.path, self.last = unit.number, unit.origin.path, unit.last
+        self.n_files, self._files = unit.n_files, unit.origin.files
+        self.ids, self.names, self.signal, self.where, self.lines = ids, names, signal, where, lines
 
-
-def packed_containers(fast5s, units):
-    """(container number, path, read ids, samples, offsets, where) per readable container, in
-    order; unreadable reads are dropped (the reference skips what it cannot read,
-    load_fast5s.py:47-49)."""
-    from . import fast5_native
-    stream = fast5_native.stream_reads(fast5s, keep=units.keep, threads=units.threads,
-                                       depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)))
-    for index, ids, samples, offsets, status in stream:
-        if ids is None:
-            continue
-        classify.warn_about_filters(status)
-        where = list(range(len(ids)))          # which read of the container each one is
-        if any(rid is None for rid in ids):
-            where = [i for i, rid in enumerate(ids) if rid is not None]
-            parts = [samples[offsets[i]:offsets[i + 1]] for i in where]
-            lengths = [len(part) for part in parts]
-            samples = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int16)
-            offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-            ids = [ids[i] for i in where]
-        yield index + 1, fast5s[index], ids, samples, offsets, where
+    def files(self):
+        """{read id: the fast5 file it came from}"""
+        if self._files is None:
+            return dict.fromkeys(self.ids, self.path)
+        if self.where is None:
+            return dict(zip(self.ids, self._files))
+        return {rid: self._files[i] for rid, i in zip(self.ids, self.where)}
 
 
-def classify_container(units, item, start_replica, end_replica):
-    number, path, ids, samples, offsets, where = item
+# ---- the three work functions: (units, unit, start replica, end replica) -> Result ----------------
+def classify_packed(units, unit, start_replica, end_replica):
+    ids, samples, offsets = unit.ids, unit.samples, unit.offsets
     lines = None
     if units.want_rows:
-        signals = classify.PackedSignals([samples[offsets[i]:offsets[i + 1]]
-                                          for i in range(len(ids))], samples, offsets)
-        lines = classify.classify_read_batch(ids, signals, start_replica, units.start_size,
+        lines = classify.classify_read_batch(ids, None, start_replica, units.start_size,
                                              end_replica, units.end_size, units.n_classes,
-                                             units.args, {})
+                                             units.args, {}, packed=(samples, offsets))
         names = [line.split('\t', 2)[1] for line in lines]
     else:
         numbers = classify.classify_packed_numbers(samples, offsets, start_replica, end_replica,
                                                    units.args)
         names = [classify.call_name(c) for c in numbers.tolist()]
     signal = (lambda i: samples[offsets[i]:offsets[i + 1]]) if units.want_signals else None
-    return Result(number, path, ids, names, signal, where, lines)
+    return Result(unit, ids, names, signal, unit.where, lines)
 
 
 # The same with (part of) the inflating on the GPU: the loader hands over Signal chunks as
 # stored - zlib streams; 85 % of what loading a read costs a CPU core is inflating them, and a
 # host has few cores per GPU (DESIGN.md section 9) - and dbh_classify_pair_deflated does the
-# rest.  The host's threads keep the longest streams of every container (a lane of the GPU
-# decoder walks ONE stream, however long): `host_inflate_share` of the bytes.
-def raw_containers(fast5s, units, host_share, n_gpus=1):
-    from . import fast5_native, realtime
-    threads = units.threads
-    if threads <= 0 and host_share == 0:
-        # nothing to inflate: a read costs a loader thread ~5 us, and a GPU takes ~210 k a second -
-        # two threads feed it, sixteen cost the process 19 us of CPU per read instead of 13
-        # (woken sixteen times per container for a fifth of what they can deliver:
-        # profiles/r06_loader/loader_team_size.txt)
-        threads = min(usable_cpus(), realtime.RAW_LOADER_THREADS_PER_GPU * max(1, n_gpus))
-    stream = fast5_native.stream_raw(fast5s, threads=threads, host_inflate_above=-host_share,
-                                     depth=int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0)),
-                                     vbz_zstd=fast5_native.vbz_zstd_route(),
-                                     shuffle=fast5_native.shuffle_route())
-    for index, ids, offsets, status, comp, records in stream:
-        if ids is None:
-            continue
-        classify.warn_about_filters(status)
-        yield index + 1, fast5s[index], ids, offsets, comp, records
-
-
-def classify_raw_container(units, item, start_replica, end_replica):
-    from . import fast5_native, hip_backend, realtime
+# rest.  The host's threads keep the longest streams of every unit (a lane of the GPU decoder
+# walks ONE stream, however long): `host_inflate_share` of the bytes.
+def classify_raw(units, unit, start_replica, end_replica):
+    from . import hip_backend, realtime
     args = units.args
-    number, path, ids, offsets, comp, records = item
-    cus = realtime.inflate_cus_for(records['comp_bytes'].tolist(), records['mode'].tolist())
+    ids, offsets, records = unit.ids, unit.offsets, unit.records
+    cus = None
+    if unit.origin.reserves_cus:
+        cus = realtime.inflate_cus_for(records['comp_bytes'].tolist(), records['mode'].tolist())
     if cus is not None:
         for model in (start_replica, end_replica):
             if model is not None:
@@ -136,7 +158,7 @@ def classify_raw_container(units, item, start_replica, end_replica):
     both = start_replica is not None and end_replica is not None
     verbose = units.want_rows and bool(getattr(args, 'verbose', False))
     result = hip_backend.classify_pair_deflated(
-        start_replica, end_replica, comp, records, offsets, int(args.scan_size),
+        start_replica, end_replica, unit.comp, records, offsets, int(args.scan_size),
         args.score_diff, classify.combine_mode(args) if both else 'require_either',
         want_samples=units.want_signals, want_sides=verbose)
     numbers, stream_status = result[0], result[1]
@@ -146,23 +168,20 @@ def classify_raw_container(units, item, start_replica, end_replica):
     for i in sorted(set(records['read'][stream_status != 0].tolist())):
         # a stream the GPU decoder refused (damaged, or beyond it): zlib on the host has the
         # last word, as it has in the reference (h5py -> libhdf5 -> zlib)
-        try:
-            _, one, one_offsets, one_status = fast5_native.load_reads(path, first=i, count=1,
-                                                                      threads=1)
-        except OSError:
-            one_status = [1]
-        classify.warn_about_filters(np.asarray(one_status))
-        if one_status[0] != 0:
+        _, one, one_offsets, one_status = unit.origin.reread(i)
+        classify.warn_about_filters(np.asarray(one_status))   # (damage only the GPU's VBZ
+        if one_status[0] != 0:                                # self-checks could see)
             ids[i] = None
             continue
         if verbose:
             redone_rows[i] = classify.redone_verbose_row(ids[i], one[one_offsets[0]:one_offsets[1]],
                                                          start_replica, end_replica, args)
-            numbers[i] = classify.call_number(redone_rows[i])
+            numbers[i] = classify.call_number(redone_rows[i].split('\t', 2)[1])
         else:
             numbers[i] = classify.classify_packed_numbers(one, one_offsets, start_replica,
                                                           end_replica, args)[0]
-        redone[i] = np.array(one)
+        if samples is not None:
+            redone[i] = np.array(one)
     keep = [i for i, rid in enumerate(ids) if rid is not None]
     names = [classify.call_name(int(numbers[i])) for i in keep]
     lines = None
@@ -174,15 +193,91 @@ def classify_raw_container(units, item, start_replica, end_replica):
         i = keep[k]
         return redone[i] if i in redone else samples[offsets[i]:offsets[i + 1]]
 
-    return Result(number, path, [ids[i] for i in keep], names,
-                  signal if samples is not None else None, keep, lines)
+    return Result(unit, [ids[i] for i in keep], names, signal if samples is not None else None,
+                  keep, lines)
+
+
+def classify_lists(units, unit, start_replica, end_replica):
+    ids, signals = unit.ids, unit.signals
+    found = {}
+    lines = classify.classify_read_batch(ids, signals, start_replica, units.start_size,
+                                         end_replica, units.end_size, units.n_classes, units.args,
+                                         found)
+    if units.want_rows:         # (a read id seen twice in a unit has two rows and two calls)
+        names = [line.split('\t', 2)[1] for line in lines]
+    else:
+        names = [found[rid] for rid in ids]
+    return Result(unit, ids, names, signals.__getitem__, None, lines if units.want_rows else None)
+
+
+# ---- the units of multi-read containers ---------------------------------------------------------
+def loader_depth():
+    return int(os.environ.get('DEEPBINNER_LOADER_DEPTH', 0))
+
+
+def readable(ids, samples, offsets):
+    """A loaded packed buffer without the reads that could not be read (the reference skips what
+    it cannot read, load_fast5s.py:47-49) -> (ids, samples, offsets, which read each one was)."""
+    where = list(range(len(ids)))
+    if any(rid is None for rid in ids):
+        where = [i for i, rid in enumerate(ids) if rid is not None]
+        parts = [samples[offsets[i]:offsets[i + 1]] for i in where]
+        lengths = [len(part) for part in parts]
+        samples = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int16)
+        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        ids = [ids[i] for i in where]
+    return ids, samples, offsets, where
+
+
+def files_done(units):
+    """Sets every unit's ``n_files`` by its container number: a container nobody could open
+    yields no unit and is done with the next one that does."""
+    done = 0
+    for unit in units:
+        upto = unit.number - (0 if unit.last else 1)
+        unit.n_files, done = upto - done, upto
+        yield unit
+
+
+def packed_containers(fast5s, units):
+    """One packed unit per readable container, in order."""
+    from . import fast5_native
+    stream = fast5_native.stream_reads(fast5s, keep=units.keep, threads=units.threads,
+                                       depth=loader_depth())
+    for index, ids, samples, offsets, status in stream:
+        if ids is None:
+            continue
+        classify.warn_about_filters(status)
+        ids, samples, offsets, where = readable(ids, samples, offsets)
+        yield Unit(Container(fast5s[index]), ids, index + 1, samples=samples, offsets=offsets,
+                   where=where)
+
+
+def raw_containers(fast5s, units, host_share, n_gpus=1):
+    """One raw unit per readable container, in order."""
+    from . import fast5_native, realtime
+    threads = units.threads
+    if threads <= 0 and host_share == 0:
+        # nothing to inflate: a read costs a loader thread ~5 us, and a GPU takes ~210 k a second -
+        # two threads feed it, sixteen cost the process 19 us of CPU per read instead of 13
+        # (woken sixteen times per container for a fifth of what they can deliver:
+        # profiles/r06_loader/loader_team_size.txt)
+        threads = min(usable_cpus(), realtime.RAW_LOADER_THREADS_PER_GPU * max(1, n_gpus))
+    stream = fast5_native.stream_raw(fast5s, threads=threads, host_inflate_above=-host_share,
+                                     depth=loader_depth(), vbz_zstd=fast5_native.vbz_zstd_route(),
+                                     shuffle=fast5_native.shuffle_route())
+    for index, ids, offsets, status, comp, records in stream:
+        if ids is None:
+            continue
+        classify.warn_about_filters(status)
+        yield Unit(Container(fast5s[index]), ids, index + 1, offsets=offsets, comp=comp,
+                   records=records)
 
 
 def read_chunks(fast5s, units):
-    """The same units for the Python reader and for models without the packed entry point:
-    (container number, path, read ids, signals, whether the container ends here) per
-    --batch_size reads.  A read that cannot be read is dropped; the reads behind it are kept
-    with ``units.skip_damaged`` only."""
+    """The same for the Python reader and for models without the packed entry point: a lists
+    unit per --batch_size reads.  A read that cannot be read is dropped; the reads behind it are
+    kept with ``units.skip_damaged`` only."""
     for number, path in enumerate(fast5s, start=1):
         try:
             reads = list(iter_reads(path, skip_damaged=units.skip_damaged))
@@ -190,40 +285,140 @@ def read_chunks(fast5s, units):
             continue
         chunks = list(classify.chunker(reads, units.args.batch_size))
         for k, chunk in enumerate(chunks):
-            yield number, path, [r[0] for r in chunk], [r[1] for r in chunk], k + 1 == len(chunks)
+            yield Unit(Container(path), [r[0] for r in chunk], number, last=k + 1 == len(chunks),
+                       signals=[r[1] for r in chunk])
 
 
-def classify_chunk(units, item, start_replica, end_replica):
-    number, path, ids, signals, last = item
-    found = {}
-    lines = classify.classify_read_batch(ids, signals, start_replica, units.start_size,
-                                         end_replica, units.end_size, units.n_classes, units.args,
-                                         found)
-    if units.want_rows:         # (a read id seen twice in a chunk has two rows and two calls)
-        names = [line.split('\t', 2)[1] for line in lines]
-    else:
-        names = [found[rid] for rid in ids]
-    return Result(number, path, ids, names, signals.__getitem__, None,
-                  lines if units.want_rows else None, last)
+# ---- the units of one-read files ------------------------------------------------------------------
+def loader_threads(args):
+    """The native loader's threads for a batch of one-read files: ``--loader_procs``, or one per
+    hardware thread this process may keep busy (misc.usable_cpus), at most 32."""
+    return int(getattr(args, 'loader_procs', 0) or 0) or max(1, min(32, usable_cpus()))
 
 
-def route(fast5s, start_model, end_model, units):
-    """-> (items, work, replicas, queues): the stream of units of the containers ``fast5s`` by
-    the route this process takes, the function that classifies one of them on a (start, end)
-    replica pair, the pairs ``classify.dispatch_batches`` deals them to, and the models whose
-    ``reserve_cus(0)`` the caller owes when it is done (the raw route's inflate queues)."""
+def containers_among(files, status, set_aside):
+    """The multi-read files a batch of one-read files met -> how many: they end the run, unless
+    the caller gave a list to ``set_aside`` such files in (--multi_read), whose units come after
+    the batches'.  Then the batch goes on without them."""
+    from . import fast5_native
+    multi = (status == fast5_native.F5_ERR_MULTI)
+    if not multi.any():
+        return 0
+    if set_aside is None:
+        sys.exit('Error: Deepbinner does not (yet) support multi-read fast5 files')
+    set_aside.extend(f for f, m in zip(files, multi.tolist()) if m)
+    return int(multi.sum())
+
+
+def loaded_ahead(chunks, load, workers, ahead):
+    """``load(chunk)`` per chunk, in order, on ``workers`` background threads (the native loader
+    releases the GIL): ``ahead`` + 1 chunks are loading or loaded while the caller works on the
+    one before them."""
+    with ThreadPoolExecutor(max_workers=workers, thread_name_prefix='deepbinner-loader') as pool:
+        waiting = collections.deque()
+        upcoming = iter(chunks)
+        for chunk in upcoming:
+            waiting.append((chunk, pool.submit(load, chunk)))
+            if len(waiting) > ahead:
+                break
+        while waiting:
+            chunk, pending = waiting.popleft()
+            loaded = pending.result()
+            following = next(upcoming, None)
+            if following is not None:
+                waiting.append((following, pool.submit(load, following)))
+            yield chunk, loaded
+
+
+def raw_batches(fast5s, units, host_share, n_queues, set_aside=None):
+    """Raw unit after raw unit of max(--batch_size, RAW_BATCH_FILES) one-read files, loaded ahead
+    of the GPU: two loads at a time on background threads (each on half of the loader's threads),
+    as many waiting as there are queues."""
+    from . import fast5_native
+    threads = max(1, loader_threads(units.args) // 2)
+    size = max(int(units.args.batch_size), classify.RAW_BATCH_FILES)
+
+    def load(chunk):
+        # DEEPBINNER_VBZ_ZSTD=gpu: VBZ chunks keep their zstd stage for the GPU (default: host);
+        # DEEPBINNER_SHUFFLE=gpu: so do shuffled chunks their shuffle
+        return fast5_native.load_batch_raw(chunk, threads, -host_share,
+                                           vbz_zstd=fast5_native.vbz_zstd_route(),
+                                           shuffle=fast5_native.shuffle_route())
+
+    for chunk, (ids, offsets, status, comp, records) in loaded_ahead(
+            list(classify.chunker(fast5s, size)), load, 2, n_queues):
+        aside = containers_among(chunk, status, set_aside)
+        classify.warn_about_filters(status)
+        yield Unit(OneReadFiles(list(chunk), units.keep), ids, n_files=len(chunk) - aside,
+                   offsets=offsets, comp=comp, records=records)
+
+
+def packed_batches(fast5s, args, keep, set_aside=None):
+    """Packed unit after packed unit of --batch_size one-read files: every batch is parsed and
+    inflated by the native loader's own worker threads (``loader_threads``), the next one on a
+    background thread while the caller classifies the current one."""
+    from . import fast5_native
+    threads = loader_threads(args)
+
+    def load(chunk):
+        return fast5_native.load_batch(chunk, keep, threads)
+
+    for chunk, (ids, samples, offsets, status) in loaded_ahead(
+            list(classify.chunker(fast5s, args.batch_size)), load, 1, 0):
+        aside = containers_among(chunk, status, set_aside)
+        classify.warn_about_filters(status)
+        ids, samples, offsets, where = readable(ids, samples, offsets)
+        yield Unit(OneReadFiles(chunk, keep), ids, n_files=len(chunk) - aside, samples=samples,
+                   offsets=offsets, where=where)
+
+
+def list_batch(loaded):
+    """The lists unit of the (fast5_file, read_id, signal) triples the reference's loop builds
+    (classify.py:141-150; signal None: a file that could not be read)."""
+    read = [triple for triple in loaded if triple[2] is not None]
+    return Unit(OneReadFiles([f for f, _, _ in read]), [rid for _, rid, _ in read],
+                n_files=len(loaded), signals=[signal for _, _, signal in read])
+
+
+# ---- the route choice -----------------------------------------------------------------------------
+@contextlib.contextmanager
+def route(fast5s, start_model, end_model, units, one_read=False, set_aside=None,
+          host_loader=False):
+    """The files ``fast5s`` - multi-read containers, or with ``one_read`` one-read files - by the
+    route this process takes: the ``Result`` of every unit, in order (``classify.dispatch_batches``
+    deals the units to the (start, end) replica pairs), for as long as the ``with`` lasts; behind
+    it the raw route's inflate queues have given their CUs back (``reserve_cus(0)``).
+    ``set_aside`` (one-read files): see ``containers_among``.  ``host_loader``: one-read files
+    through ``classify.load_in_batches`` whatever ``classify.raw_inflate_share`` says."""
     from . import realtime
     models = [m for m in (start_model, end_model) if m is not None]
     packed = reader_kind() == 'native' and all(hasattr(m, 'classify_packed') for m in models)
     replicas = classify.device_replicas(start_model, end_model)
     n_gpus = len({getattr(r[0] or r[1], 'device', 0) for r in replicas})
-    host_share = realtime.host_inflate_share(n_gpus)
-    queues = []
-    if packed and host_share < 100 and all(hasattr(m, 'handle') for m in models):
-        items, work = raw_containers(fast5s, units, host_share, n_gpus), classify_raw_container
-        replicas, queues = realtime.inflate_queues(replicas, host_share)
-    elif packed:
-        items, work = packed_containers(fast5s, units), classify_container
+    if one_read:
+        host_share = None if host_loader else classify.raw_inflate_share(
+            start_model, end_model, units.args, len(fast5s), replicas)
+        raw = host_share is not None
     else:
-        items, work = read_chunks(fast5s, units), classify_chunk
-    return items, functools.partial(work, units), replicas, queues
+        host_share = realtime.host_inflate_share(n_gpus)
+        raw = packed and host_share < 100 and all(hasattr(m, 'handle') for m in models)
+    queues = []
+    if raw:
+        # several units in flight per GPU, each on a replica of the models (DESIGN.md 12)
+        replicas, queues = realtime.inflate_queues(replicas, host_share)
+        items, work = (raw_batches(fast5s, units, host_share, len(replicas), set_aside) if one_read
+                       else raw_containers(fast5s, units, host_share, n_gpus)), classify_raw
+    elif one_read:
+        items = classify.load_in_batches(fast5s, units.args, units.keep, set_aside)
+        work = classify_packed if reader_kind() == 'native' else classify_lists
+    elif packed:
+        items, work = packed_containers(fast5s, units), classify_packed
+    else:
+        items, work = read_chunks(fast5s, units), classify_lists
+    if not one_read:
+        items = files_done(items)
+    try:
+        yield classify.dispatch_batches(items, replicas, functools.partial(work, units))
+    finally:
+        for model in queues:                # the forward kernel gets every CU back
+            model.reserve_cus(0)

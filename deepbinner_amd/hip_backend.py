@@ -498,8 +498,7 @@ class _TensorSpec:
 
 MODEL_AUTO, MODEL_GENERAL = 0, 1                 # dbh_model_create_ex flags
 KIND_PERSISTENT, KIND_GENERAL = 0, 1             # dbh_model_kind
-MIN_INPUT_SIZE, MAX_INPUT_SIZE = 96, 16384       # the geometry dbh_model_create_ex takes
-MIN_CLASSES, MAX_CLASSES = 2, 256
+# (the geometry dbh_model_create_ex takes: classify.MIN_INPUT_SIZE .. MAX_CLASSES)
 
 
 class HipModel:
@@ -575,8 +574,7 @@ class HipModel:
     def classify_signals(self, signals, side, scan_size, score_diff):
         """signals: list of 1-D integer arrays -> (probs float32 [N, C], calls int32 [N])."""
         n = len(signals)
-        scan_size = int(scan_size)
-        keep = scan_size + self.input_size // 2      # samples any window can touch
+        keep = int(scan_size) + self.input_size // 2      # samples any window can touch
         parts = []
         offsets = np.zeros(n + 1, dtype=np.int64)
         for i, s in enumerate(signals):
@@ -591,17 +589,7 @@ class HipModel:
             parts.append(np.asarray(part, dtype=np.int16))
             offsets[i + 1] = offsets[i] + len(part)
         samples = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int16)
-        samples = np.ascontiguousarray(samples, dtype=np.int16)
-        if samples.size == 0:
-            samples = np.zeros(1, dtype=np.int16)
-        probs = np.empty((n, self.n_classes), dtype=np.float32)
-        calls = np.empty(n, dtype=np.int32)
-        if n:
-            side_code = SIDE_START if side == 'start' else SIDE_END
-            check(self._lib.dbh_classify_i16(self._handle, samples, offsets, n, side_code,
-                                             scan_size, float(score_diff), probs, calls),
-                  'dbh_classify_i16')
-        return probs, calls
+        return self.classify_packed(samples, offsets, side, scan_size, score_diff)
 
     def classify_packed(self, samples, offsets, side, scan_size, score_diff):
         """``classify_signals`` for reads that are already packed the way the C ABI takes them:

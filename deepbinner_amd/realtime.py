@@ -380,8 +380,7 @@ class Session:
                 in_flight.release()
 
         # raw chunks inflated on the GPU, packed buffers, or per-batch lists: containers.route
-        items, work, replicas, queues = containers.route(fast5s, self.start_model,
-                                                         self.end_model, self._units())
+        routed = containers.route(fast5s, self.start_model, self.end_model, self._units())
         metadata = MetadataSource() if not self.table_only else None     # (the Python writer's)
         # The native writer: one call per container, two containers at a time on background
         # threads (the library's own worker threads do the reads of a container in parallel - four
@@ -443,9 +442,10 @@ class Session:
 
         group, calls, done, written, jobs = 0, {}, 0, 0, []
         try:
-            with open(str(self.out_dir / 'multi_read_classifications.tsv'), 'at') as table:
+            with routed as results, \
+                    open(str(self.out_dir / 'multi_read_classifications.tsv'), 'at') as table:
                 classify.print_classification_progress(0, 1, 'reads', out_dest=sys.stdout)
-                for unit in classify.dispatch_batches(items, replicas, work):
+                for unit in results:
                     number, path, ids, names = unit.number, unit.path, unit.ids, unit.names
                     signal, where = unit.signal, unit.where
                     while group_of(number) > group:
@@ -486,8 +486,6 @@ class Session:
             native_jobs.shutdown(wait=True)
             if metadata is not None:
                 metadata.close()
-            for model in queues:                # the forward kernel gets every CU back
-                model.reserve_cus(0)
 
     def _file_name(self, read_id, call):
         """File name (without .fast5) of a binned read.  The id is an attribute of an untrusted

@@ -691,40 +691,21 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
         sys.stdout.flush()
     classifications, id_to_file, lines = {}, {}, []
 
-    def classify_shard_units():
-        for files_of, calls, rows, finished in c.classify_units(
-                mine, start_model, start_input_size, end_model, end_input_size, output_size,
-                args):
-            id_to_file.update(files_of)
-            classifications.update(calls)
-            lines.extend(rows)
+    def classify_shard():
+        # without --multi_read a rank loads through the host's loader (classify.load_in_batches);
+        # rank 0's shard is as large as any: its progress stands for the job
+        def progress(finished):
             if rank == 0:
-                c.print_classification_progress(min(finished * world, len(files)), len(files),
+                done = finished if multi_read else len(classifications)
+                c.print_classification_progress(min(done * world, len(files)), len(files),
                                                 'fast5s')
 
-    def classify_shard():
-        keep = c.scanned_end_samples(args.scan_size, start_input_size, end_input_size)
-        # (the loaders' default keep is that of 1024-sample models)
-        batches = (c.load_in_batches(mine, args) if keep == c.scanned_end_samples(args.scan_size)
-                   else c.load_in_batches(mine, args, keep))
-        for loaded in batches:
-            read_ids, signals = [], []
-            for fast5_file, read_id, signal in loaded:
-                if signal is None:
-                    continue
-                id_to_file[read_id] = fast5_file
-                read_ids.append(read_id)
-                signals.append(signal)
-            if getattr(loaded, 'complete', False):      # the loader's packed buffer is these reads
-                signals = c.PackedSignals(signals, loaded.samples, loaded.offsets)
-            lines.extend(c.classify_read_batch(read_ids, signals, start_model, start_input_size,
-                                               end_model, end_input_size, output_size, args,
-                                               classifications))
-            if rank == 0:    # rank 0's shard is as large as any: its progress stands for the job
-                c.print_classification_progress(min(len(classifications) * world, len(files)),
-                                                len(files), 'fast5s')
+        c.tabulate_units(c.classify_units(mine, start_model, start_input_size, end_model,
+                                          end_input_size, output_size, args,
+                                          host_loader=not multi_read),
+                         classifications, id_to_file, lines.extend, progress)
 
-    together(classify_shard_units if multi_read else classify_shard)
+    together(classify_shard)
 
     # the table: every rank writes its own rows when the ranks before it are done
     for turn in range(world):
@@ -736,8 +717,7 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
 
     # the collective of SURVEY.md section 8e: per-read calls, int32, 0 = 'none'
     order = list(classifications)
-    local = np.array([0 if classifications[r] == 'none' else int(classifications[r])
-                      for r in order], dtype=np.int32)
+    local = np.array([c.call_number(classifications[r]) for r in order], dtype=np.int32)
     counts = [struct.unpack('<q', p)[0] for p in rdzv.all_gather(struct.pack('<q', len(order)))]
     all_calls = gather_calls(local, counts, rdzv)
     id_blobs = rdzv.all_gather('\n'.join('{}\t{}'.format(r, id_to_file[r]) for r in order)
@@ -751,8 +731,7 @@ def classify_fast5_files_sharded(fast5_files, start_model, start_input_size, end
             if r != 0:
                 merged_files.update(l.split('\t', 1) for l in id_blobs[r].decode().split('\n') if l)
             for k, read_id in enumerate(ids):
-                call = int(all_calls[at + k])
-                merged[read_id] = 'none' if call == 0 else str(call)
+                merged[read_id] = c.call_name(int(all_calls[at + k]))
             at += counts[r]
         c.print_classification_progress(len(files) if multi_read else len(merged), len(files),
                                         'fast5s')

@@ -300,7 +300,7 @@ BROKEN_LOADER = r"""
 import deepbinner_amd.sharding as sh
 import deepbinner_amd.load_fast5s as lf
 files = sorted(lf.find_all_fast5s(target))
-def broken(files, args):
+def broken(files, args, *more):
     if int(os.environ['RANK']) == 1:
         raise KeyError('loader blew up')
     return iter(())
