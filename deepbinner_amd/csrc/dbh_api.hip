@@ -21,6 +21,7 @@
 #include "dbh_general.h"
 #include "dbh_host_layout.h"
 #include "dbh_owned.h"
+#include "dbh_train.h"
 #define DBH_FORWARD_NS dbh
 #define DBH_TIMELINE 0
 #include "dbh_forward.hip"
@@ -127,6 +128,13 @@ int hip_fail(hipError_t e, const char* what) {
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? DBH_ERR_OUT_OF_MEMORY : DBH_ERR_HIP;
 }
+
+}  // namespace
+
+// (dbh_train.hip reports through the same text as everything else)
+int dbh_train::report_hip_error(hipError_t e, const char* what) { return hip_fail(e, what); }
+
+namespace {
 
 #define DBH_HIP(call)                                         \
     do {                                                      \

@@ -196,6 +196,12 @@ int dbh_forward_phases_enable(dbh_model* m, int enable) {
     return DBH_OK;
 }
 
+int dbh_forward_phases_count(int* count) {
+    if (!count) return DBH_ERR_INVALID_ARGUMENT;
+    *count = dbh::kPhaseMarks;
+    return DBH_OK;
+}
+
 int dbh_forward_phases_read(dbh_model* m, double* mean_cycles, int64_t* groups) {
     if (!m || !mean_cycles || !groups) return DBH_ERR_INVALID_ARGUMENT;
     if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;

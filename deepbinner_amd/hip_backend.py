@@ -159,6 +159,15 @@ def load_library():
         'dbh_forward_clock_read': (c_int, [c_void_p, P(ctypes.c_double)]),
         'dbh_forward_phases_enable': (c_int, [c_void_p, c_int]),
         'dbh_forward_phases_read': (c_int, [c_void_p, P(ctypes.c_double), P(ctypes.c_int64)]),
+        'dbh_forward_phases_count': (c_int, [P(c_int)]),
+        'dbh_gradients_max_windows': (c_int, [c_int, P(c_i64)]),
+        'dbh_gradients_workspace_bytes': (c_int, [c_int, c_int, c_i64, P(ctypes.c_size_t)]),
+        'dbh_gradients': (c_int, [_f32(), c_i64, c_int, c_int, _f32(),
+                                  ndpointer(np.int32, flags='C_CONTIGUOUS'), c_i64, ctypes.c_float,
+                                  ctypes.c_uint64, P(ctypes.c_double), P(c_i64), _f32(), _f32()]),
+        'dbh_gradients_dev': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_i64,
+                                      ctypes.c_float, ctypes.c_uint64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
         'dbh_comm_available': (c_int, []),
         'dbh_comm_last_error': (ctypes.c_char_p, []),
         'dbh_comm_init_all': (c_int, [c_int, P(c_int), c_int, P(c_void_p)]),
@@ -196,6 +205,8 @@ EXPORTED_SYMBOLS = [
     'dbh_stage_floats', 'dbh_debug_forward', 'dbh_forward_kernel_info',
     'dbh_forward_truncated_dev', 'dbh_forward_executed_mfmas', 'dbh_forward_timeline', 'dbh_forward_timeline_i16', 'dbh_forward_timing_enable', 'dbh_forward_timing_enable_span',
     'dbh_forward_timing_read', 'dbh_forward_clock_enable', 'dbh_forward_clock_read', 'dbh_forward_phases_enable', 'dbh_forward_phases_read',
+    'dbh_forward_phases_count',
+    'dbh_gradients_max_windows', 'dbh_gradients_workspace_bytes', 'dbh_gradients', 'dbh_gradients_dev',
     'dbh_comm_available', 'dbh_comm_last_error', 'dbh_comm_init_all', 'dbh_comm_unique_id',
     'dbh_comm_init_rank', 'dbh_comm_info', 'dbh_comm_all_gather_i32', 'dbh_comm_destroy',
 ]
@@ -700,7 +711,9 @@ class HipModel:
         """Mean shader cycles of the five phases of a group of windows in this model's latest forward
         launch (see dbh_forward_phases_read): stages A-C, the stage D-E chain, stage F, the batched
         tail, what lies between two groups; and the number of groups averaged."""
-        out = (ctypes.c_double * 14)()
+        count = ctypes.c_int(0)
+        check(self._lib.dbh_forward_phases_count(ctypes.byref(count)), 'dbh_forward_phases_count')
+        out = (ctypes.c_double * count.value)()
         n = ctypes.c_int64(0)
         check(self._lib.dbh_forward_phases_read(self._handle, out, ctypes.byref(n)), 'dbh_forward_phases_read')
         return [float(v) for v in out], int(n.value)
@@ -732,6 +745,51 @@ class HipModel:
         shapes = {0: (512, 48), 1: (256, 48), 2: (128, 48), 3: (64, 48), 4: (32, 192),
                   5: (16, 48), 6: (8, 48), 7: (32,)}
         return out.reshape((x.shape[0],) + shapes[idx])
+
+
+BATCH_STATS_FLOATS = 2 * 480       # batch mean then batch variance of batch_normalization_1..7
+
+
+def loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=0):
+    """The first half of a training step (dbh_gradients; reference train_network.py:53-55): the
+    network in training mode on the windows ``x`` [N, input_size] (already normalised; the
+    GaussianNoise layer is the caller's to add), the mean categorical cross-entropy against
+    ``labels`` [N], and its gradient.  Returns ``(loss, n_correct, grads, batch_stats)``: ``grads``
+    a flat fp32 array in the layout of ``weights.flat()`` (``ModelWeights.from_flat`` splits it;
+    the moving-statistics slots are zeros), ``batch_stats`` the 960 batch means and variances."""
+    lib = load_library()
+    flat = weights.flat()
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1, weights.input_size))
+    labels = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.int32))
+    if labels.size != x.shape[0]:
+        raise ValueError('{} labels for {} windows'.format(labels.size, x.shape[0]))
+    grads = np.zeros(flat.size, dtype=np.float32)
+    stats = np.zeros(BATCH_STATS_FLOATS, dtype=np.float32)
+    loss, correct = ctypes.c_double(0), ctypes.c_int64(0)
+    check(lib.dbh_gradients(flat, flat.size, weights.n_classes, weights.input_size, x, labels,
+                            x.shape[0], float(dropout_rate), int(seed) & (2 ** 64 - 1),
+                            ctypes.byref(loss), ctypes.byref(correct), grads, stats),
+          'dbh_gradients')
+    return loss.value, int(correct.value), grads, stats
+
+
+def gradients_workspace_bytes(n_classes, input_size, n_windows):
+    size = ctypes.c_size_t(0)
+    check(load_library().dbh_gradients_workspace_bytes(int(n_classes), int(input_size),
+                                                       int(n_windows), ctypes.byref(size)),
+          'dbh_gradients_workspace_bytes')
+    return size.value
+
+
+def gradients_dev(weights_ptr, n_floats, n_classes, input_size, x_ptr, labels_ptr, n_windows,
+                  dropout_rate, seed, loss_ptr, correct_ptr, grads_ptr, stats_ptr, workspace_ptr,
+                  stream=None):
+    """dbh_gradients_dev on device pointers (``DeviceBuffer.ptr``); queued, not synchronised."""
+    check(load_library().dbh_gradients_dev(weights_ptr, int(n_floats), int(n_classes),
+                                           int(input_size), x_ptr, labels_ptr, int(n_windows),
+                                           float(dropout_rate), int(seed) & (2 ** 64 - 1), loss_ptr,
+                                           correct_ptr, grads_ptr, stats_ptr, workspace_ptr, stream),
+          'dbh_gradients_dev')
 
 
 def forward_executed_mfmas(n_classes):

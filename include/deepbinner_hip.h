@@ -381,6 +381,65 @@ int dbh_merge_calls_dev(const float* window_probs_dev, int64_t n_reads, int step
                         double score_diff, float* probs_dev, int32_t* calls_dev,
                         dbh_stream stream);
 
+/* ---- training: loss and weight gradients of one batch ----------------------------------------- */
+/* The first half of the reference's training step (train_network.py:53-55 compiles build_network,
+ * network_architecture.py:18-95, with categorical cross-entropy; train_network.py:66-68 runs
+ * fit_generator on batches of deepbinner.py:265's default 20 windows): the network in Keras's
+ * TRAINING phase, the loss, and the gradient of the mean loss with respect to every trainable
+ * parameter.  The optimiser (Nadam), the moving averages, the data generator and the `train`
+ * command are not here.  Any geometry dbh_model_create_ex takes; no model handle: the weights
+ * change every step and are read where they lie.
+ *   x        n_windows x input_size fp32, already normalised.  The GaussianNoise(0.02) layer
+ *            (network_architecture.py:26) is the CALLER's to add to x; this call adds none.
+ *   labels   n_windows class numbers in [0, n_classes).
+ *   batch normalisation (network_architecture.py:30,39,50,58,73,79,87): batch statistics per channel
+ *            over all n_windows x length positions of THIS call (biased variance, epsilon 1e-3,
+ *            two passes in fp64), the backward pass through mean and variance.  The blob's moving
+ *            mean and variance are not read.  batch_stats: 960 floats, for layers 1..7 in turn the
+ *            batch mean [C_i] then the batch variance [C_i] (48,48,48,48,192,48,48 channels), from
+ *            which a caller keeps Keras's moving averages.
+ *   dropout  (network_architecture.py:31,40,51,59,74,80,88) inverted, rate dropout_rate in [0, 1),
+ *            behind each batch normalisation.  Element (layer 1..7, window, position, channel) is
+ *            kept by a stateless function of those four and the seed, 32-bit arithmetic:
+ *                mix(h): h ^= h >> 16; h *= 0x7feb352d; h ^= h >> 15; h *= 0x846ca68b; h ^= h >> 16
+ *                h = mix(seed_lo + layer * 0x9e3779b9);  h = mix(h ^ seed_hi);  h = mix(h + window);
+ *                h = mix(h ^ (position * 256 + channel));   kept <=> (h >> 8) >= floor(rate * 2^24)
+ *            and multiplied by (float)(1 / (1 - rate)).  Rate 0 keeps all and multiplies by exactly 1.
+ *            The mask does not depend on how the batch is laid over the GPU.
+ *   loss     of a window: -log softmax(logits)[label] from a stable log-sum-exp; mean_loss is the
+ *            mean over the batch.  Keras clips the probability to [1e-7, 1 - 1e-7] before the
+ *            logarithm; this call does not - the one deliberate difference, visible only where
+ *            p[label] < 1e-7.  n_correct: windows whose argmax (lowest index on ties) is the label.
+ *   grads    n_floats fp32 in the blob's own layout (dbh_model_create): kernel[k][C_in][C_out] and
+ *            bias per convolution, gamma and beta per batch normalisation; the moving-mean and
+ *            moving-variance slots are zeros.  ReLU'(0) = 0; a max-pool tie sends the gradient to
+ *            the first of the pair, the position a 'valid' pool drops gets 0.
+ * No atomics: the same call gives the same bits, and a window's contribution does not depend on
+ * the workgroup that took it.
+ * LIMIT of one call: n_windows * input_size <= 2^20 = 1,048,576 samples (dbh_gradients_max_windows:
+ * 1,024 windows of 1,024 samples, 64 of 16,384); more is DBH_ERR_UNSUPPORTED - the statistics are
+ * per call, so a batch is never split silently.
+ * Errors, all before any device work, nothing written: geometry outside the limits
+ * DBH_ERR_UNSUPPORTED; n_floats not the parameter count DBH_ERR_BAD_WEIGHTS; n_windows < 1, a rate
+ * outside [0, 1), a null pointer, (host entry) a label outside [0, n_classes):
+ * DBH_ERR_INVALID_ARGUMENT. */
+int dbh_gradients_max_windows(int input_size, int64_t* n_windows);
+int dbh_gradients_workspace_bytes(int n_classes, int input_size, int64_t n_windows, size_t* bytes);
+/* host pointers; blocks until the results are in the caller's buffers, like dbh_predict */
+int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                  const float* x_host, const int32_t* labels_host, int64_t n_windows,
+                  float dropout_rate, uint64_t seed, double* mean_loss, int64_t* n_correct,
+                  float* grads_host, float* batch_stats_host);
+/* device pointers (weights_dev 16-byte aligned), the caller's workspace of
+ * dbh_gradients_workspace_bytes() bytes, queued on `stream`, not synchronised: what a training
+ * loop (train_network.py:66-68) calls per step.  The labels are on the device and cannot be
+ * checked here: a label outside [0, n_classes) makes mean_loss NaN. */
+int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes, int input_size,
+                      const float* x_dev, const int32_t* labels_dev, int64_t n_windows,
+                      float dropout_rate, uint64_t seed, double* mean_loss_dev,
+                      int64_t* n_correct_dev, float* grads_dev, float* batch_stats_dev,
+                      void* workspace_dev, dbh_stream stream);
+
 /* ---- introspection ------------------------------------------------------------------------ */
 /* Activations after stage 'A'..'G'  for n_windows windows, row-major
  * [window][position][channel]; out_host must hold n_windows * dbh_stage_floats(stage) floats. */
@@ -447,6 +506,8 @@ int dbh_forward_clock_read(dbh_model* model, double* shader_ghz);
  * top to the start of stage B's chain, the chain, conv1d_7 (of all windows but the group's last);
  * [12], [13]: the group's last conv1d_7, and from its end to the start of the stage D-E chain. */
 int dbh_forward_phases_enable(dbh_model* model, int enable);
+/* how many doubles dbh_forward_phases_read writes (14): size the buffer from this, not from a literal */
+int dbh_forward_phases_count(int* count);
 int dbh_forward_phases_read(dbh_model* model, double* mean_cycles_14, int64_t* groups);
 
 #ifdef __cplusplus

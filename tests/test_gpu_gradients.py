@@ -1,0 +1,236 @@
+"""dbh_gradients on the device against tests/train_reference.py (pinned in
+tests/test_train_reference.py).
+
+The tolerance is not a number fixed in advance: every case runs the reference in fp64 and in fp32;
+per tensor e32 = max|g32 - g64| / max|g64|, and the device may be off by 4 e32, floored at 1e-6
+(fp32's own resolution on a tensor without cancellation).  The same rule holds for the loss and the
+batch statistics.  Measured e32 and the device's worst ratio per case:
+profiles/train_gradients/gradients_gpu.txt.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import train_reference as tr
+import weight_families as wf
+from conftest import GOLD
+from deepbinner_amd.model_format import BN_CHANNELS, param_count
+
+pytestmark = pytest.mark.gpu
+
+# (input size, windows, classes): the smallest shapes at which each kernel can still go wrong
+#   96:   the minimum; lengths 48, 24, 12, 6, 3, 2, 1 - an odd length into conv1d_17, BN7 over 3
+#         elements, every MFMA row tile partial
+#   130:  65 positions after conv1d_1: the pool drops one (gradient 0); SAME padding of a stride-2
+#         layer on an odd length
+#   200:  25 and 3 are odd at two pools; a class count that is no multiple of 16
+#   1024 x 20: the reference's default batch on the shipped starts model and golden windows:
+#         activations of 2^27 through the BN sums
+#   1024 x 3 x 256: the widest head
+CASES = [(96, 3, 2), (130, 5, 13), (200, 2, 33), (1024, 20, 13), (1024, 3, 256)]
+RATES = [0.0, 0.15]
+SEED = 20181018
+
+
+def case_inputs(size, n, classes):
+    if (size, n, classes) == (1024, 20, 13):
+        from general_fixtures import shipped
+        weights = shipped()
+        x = np.load(os.path.join(GOLD, 'windows_start.npy')).reshape(-1, 1024)[:n]
+        x = np.ascontiguousarray(x, dtype=np.float32)
+    else:
+        weights = wf.random_model(size + n, classes, input_size=size)
+        x = np.random.default_rng([size, n, classes]).standard_normal((n, size)).astype(np.float32)
+    if classes == 256:
+        labels = np.full(n, 77, dtype=np.int32)            # every window the same label
+    else:
+        labels = np.random.default_rng(size).integers(classes, size=n).astype(np.int32)
+        labels[0], labels[-1] = 0, classes - 1
+    return weights, x, labels
+
+
+_reference = {}
+
+
+def reference(size, n, classes, rate):
+    """(fp64 result, fp32 result) of a case: computed once, shared, never changed."""
+    key = (size, n, classes, rate)
+    if key not in _reference:
+        weights, x, labels = case_inputs(size, n, classes)
+        _reference[key] = tuple(tr.loss_and_gradients(weights, x, labels, rate=rate, seed=SEED,
+                                                      dtype=d) for d in (np.float64, np.float32))
+    return _reference[key]
+
+
+def stat_slices():
+    out, at = {}, 0
+    for i, c in enumerate(BN_CHANNELS, start=1):
+        out['bn_%d/batch_mean' % i] = slice(at, at + c)
+        out['bn_%d/batch_variance' % i] = slice(at + c, at + 2 * c)
+        at += 2 * c
+    return out
+
+
+def ratios(got, r64, r32, slices):
+    """name -> (e32, device error / bound) with bound = max(4 e32, 1e-6), all relative to
+    max|fp64 tensor|."""
+    out = {}
+    for name, sl in slices.items():
+        want = np.asarray(r64[sl], dtype=np.float64)
+        scale = np.abs(want).max()
+        if scale == 0:
+            out[name] = (0.0, 0.0 if not np.asarray(got[sl]).any() else np.inf)
+            continue
+        e32 = np.abs(np.asarray(r32[sl], dtype=np.float64) - want).max() / scale
+        g = np.asarray(got[sl], dtype=np.float64)
+        err = np.abs(g - want).max() / scale if np.isfinite(g).all() else np.inf
+        out[name] = (float(e32), float(err / max(4 * e32, 1e-6)))
+    return out
+
+
+def check_against_reference(got, r64, r32, classes, tag):
+    loss, n_correct, grads, stats = got
+    slices, moving = tr.tensor_slices(classes)
+    e32 = abs(r32.loss - r64.loss) / abs(r64.loss)
+    loss_ratio = abs(loss - r64.loss) / abs(r64.loss) / max(4 * e32, 1e-6)
+    res = ratios(grads, r64.grads, r32.grads, slices)
+    res_stats = ratios(stats, r64.stats, r32.stats, stat_slices())
+    worst = max(res.items(), key=lambda kv: kv[1][1])
+    worst_s = max(res_stats.items(), key=lambda kv: kv[1][1])
+    print('{}: loss {:.9g} (fp64 {:.9g}, e32 {:.2e}, ratio {:.3f}); gradients worst ratio {:.3f} '
+          '({}, e32 {:.2e}; e32 over tensors {:.2e} .. {:.2e}); statistics worst ratio {:.3f} ({})'
+          .format(tag, loss, r64.loss, e32, loss_ratio, worst[1][1], worst[0], worst[1][0],
+                  min(v[0] for v in res.values()), max(v[0] for v in res.values()),
+                  worst_s[1][1], worst_s[0]))
+    assert n_correct == r64.n_correct
+    assert loss_ratio <= 1.0, (loss, r64.loss, e32)
+    bad = {k: v for k, v in res.items() if not v[1] <= 1.0}
+    assert not bad, bad
+    bad = {k: v for k, v in res_stats.items() if not v[1] <= 1.0}
+    assert not bad, bad
+    for m in moving:
+        assert not grads[m].any()                           # the moving-statistics slots: zeros
+
+
+@pytest.mark.parametrize('rate', RATES)
+@pytest.mark.parametrize('size,n,classes', CASES)
+def test_loss_gradients_and_statistics(hip, size, n, classes, rate):
+    weights, x, labels = case_inputs(size, n, classes)
+    r64, r32 = reference(size, n, classes, rate)
+    got = hip.loss_and_gradients(weights, x, labels, dropout_rate=rate, seed=SEED)
+    assert got[2].size == param_count(classes) and got[3].size == 960
+    check_against_reference(got, r64, r32, classes, 'L{} N{} C{} rate {}'.format(size, n, classes, rate))
+
+
+def run_dev(hip, weights, x, labels, rate, seed):
+    flat = weights.flat()
+    n = x.shape[0]
+    bufs = [hip.DeviceBuffer.from_array(a) for a in (flat, x, labels)]
+    loss, correct = hip.DeviceBuffer(8), hip.DeviceBuffer(8)
+    grads, stats = hip.DeviceBuffer(flat.nbytes), hip.DeviceBuffer(960 * 4)
+    work = hip.DeviceBuffer(hip.gradients_workspace_bytes(weights.n_classes, weights.input_size, n))
+    hip.gradients_dev(bufs[0].ptr, flat.size, weights.n_classes, weights.input_size, bufs[1].ptr,
+                      bufs[2].ptr, n, rate, seed, loss.ptr, correct.ptr, grads.ptr, stats.ptr,
+                      work.ptr)
+    hip.synchronize()
+    out = (float(loss.download((1,), np.float64)[0]), int(correct.download((1,), np.int64)[0]),
+           grads.download((flat.size,), np.float32), stats.download((960,), np.float32))
+    for b in bufs + [loss, correct, grads, stats, work]:
+        b.free()
+    return out
+
+
+def same_bits(a, b):
+    return (np.float64(a[0]).tobytes() == np.float64(b[0]).tobytes() and a[1] == b[1]
+            and a[2].tobytes() == b[2].tobytes() and a[3].tobytes() == b[3].tobytes())
+
+
+def test_same_bits_twice_and_through_the_device_entry(hip):
+    weights, x, labels = case_inputs(130, 5, 13)
+    first = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=SEED)
+    again = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=SEED)
+    assert same_bits(first, again)
+    assert same_bits(first, run_dev(hip, weights, x, labels, 0.15, SEED))
+    other = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=SEED + 1)
+    assert other[2].tobytes() != first[2].tobytes()         # the seed reaches the masks
+
+
+def test_windows_permuted(hip):
+    """Dropout 0 (the masks go by window number): the windows in another order, with their labels,
+    give the same loss and gradients within the bound of the case."""
+    size, n, classes = 130, 5, 13
+    weights, x, labels = case_inputs(size, n, classes)
+    r64, r32 = reference(size, n, classes, 0.0)
+    order = np.array([3, 0, 4, 2, 1])
+    got = hip.loss_and_gradients(weights, x[order], labels[order], dropout_rate=0.0, seed=SEED)
+    check_against_reference(got, r64, r32, classes, 'L130 N5 C13 permuted')
+
+
+def test_closed_form_constant_head(hip):
+    """conv1d_20's kernel zero: every gradient but its bias's is exactly 0; the bias's is
+    mean(softmax - onehot) where the bias is positive, else 0."""
+    n, classes = 4, 13
+    bias = wf.constant_biases(classes)['spread']
+    weights = wf.constant(wf.random_model(3, classes), bias)
+    x = np.random.default_rng(5).standard_normal((n, 1024)).astype(np.float32)
+    labels = np.array([0, 12, 5, 5], dtype=np.int32)
+    loss, n_correct, grads, _ = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=3)
+    slices, _ = tr.tensor_slices(classes)
+    z = np.maximum(bias.astype(np.float64), 0.0)
+    p = np.exp(z - z.max())
+    p /= p.sum()
+    want = np.repeat(p[None, :], n, axis=0)
+    want[np.arange(n), labels] -= 1.0
+    want = want.mean(axis=0) * (bias > 0)
+    for name, sl in slices.items():
+        if name == 'conv1d_20/bias':
+            assert np.abs(grads[sl] - want).max() <= 1e-6 * np.abs(want).max()
+            assert not grads[sl][bias <= 0].any()
+        elif name == 'conv1d_20/kernel':
+            continue        # (d loss / d kernel is h7^T dz: not zero, and not part of this form)
+        else:
+            assert not grads[sl].any(), name
+    want_loss = float(np.mean(np.log(np.exp(z - z.max()).sum()) + z.max() - z[labels]))
+    assert abs(loss - want_loss) <= 1e-6 * want_loss
+    assert n_correct == int((labels == int(np.argmax(z))).sum())
+
+
+def test_closed_form_dead_layers(hip):
+    """Biases of conv1d_2 .. 19 at -1e6: their kernels' and biases' gradients are exactly 0."""
+    classes = 13
+    weights = wf.dead(wf.random_model(0, classes))
+    x = np.random.default_rng(6).standard_normal((3, 1024)).astype(np.float32)
+    labels = np.array([0, 12, 7], dtype=np.int32)
+    loss, _, grads, _ = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=4)
+    assert np.isfinite(loss) and np.isfinite(grads).all()
+    slices, _ = tr.tensor_slices(classes)
+    for i in range(2, 20):
+        for part in ('kernel', 'bias'):
+            assert not grads[slices['conv1d_%d/%s' % (i, part)]].any(), (i, part)
+
+
+def test_refusals_write_nothing(hip):
+    lib = hip.load_library()
+    n, length, classes = 4, 1024, 13
+    count = param_count(classes)
+    w = wf.random_model(1, classes).flat()
+    x = np.zeros((n, length), dtype=np.float32)
+    labels = np.zeros(n, dtype=np.int32)
+    grads = np.full(count, 7.0, dtype=np.float32)
+    stats = np.full(960, 7.0, dtype=np.float32)
+    loss, correct = ctypes.c_double(7.0), ctypes.c_int64(7)
+
+    def call(n_floats=count, classes=classes, length=length, labels=labels, n=n, rate=0.15):
+        return lib.dbh_gradients(w, n_floats, classes, length, x, labels, n, rate, 0,
+                                 ctypes.byref(loss), ctypes.byref(correct), grads, stats)
+
+    assert call(length=94) == 5 and call(length=1001) == 5 and call(classes=257) == 5
+    assert call(n_floats=count + 1) == 4
+    assert call(labels=np.array([0, 13, 1, 2], dtype=np.int32)) == 1
+    assert call(n=0) == 1 and call(rate=1.0) == 1 and call(rate=-0.5) == 1
+    assert call(n=1025) == 5
+    assert (grads == 7.0).all() and (stats == 7.0).all()
+    assert loss.value == 7.0 and correct.value == 7
+    assert call() == 0 and np.isfinite(loss.value) and not (grads == 7.0).all()
