@@ -1,5 +1,5 @@
 // dbh_api.hip — host side of libdeepbinner_hip.so: the C ABI declared in
-// include/deepbinner_hip.h.  Packs the canonical weight blob into the kernel's fragment order,
+// include/deepbinner_hip.h.  Uploads the weights dbh_pack.h packs into the kernel's fragment order,
 // owns the device buffers, launches the kernels of dbh_forward.hip and holds the small seam kernels
 // (stand-alone normalise, merge, combine_calls).
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "dbh_general.h"
 #include "dbh_host_layout.h"
 #include "dbh_owned.h"
+#include "dbh_pack.h"
 #include "dbh_train.h"
 #define DBH_FORWARD_NS dbh
 #define DBH_TIMELINE 0
@@ -146,133 +147,6 @@ namespace {
         const int st_ = (call);                               \
         if (st_ != DBH_OK) return st_;                        \
     } while (0)
-
-// canonical (Keras) shapes of the 20 convolutions for a given class count
-struct CanonConv { int k, cin, cout; };
-void canon_convs(int n_classes, CanonConv out[dbh::kNumConvs]) {
-    for (int i = 0; i < dbh::kNumConvs; ++i) {
-        out[i].k = dbh::kConv[i].taps;
-        out[i].cin = dbh::kConv[i].cin;
-        out[i].cout = (i == dbh::kNumConvs - 1) ? n_classes : dbh::kConv[i].cout_pad;
-    }
-}
-
-int64_t canon_param_count(int n_classes) {
-    CanonConv cc[dbh::kNumConvs];
-    canon_convs(n_classes, cc);
-    int64_t n = 0;
-    for (int i = 0; i < dbh::kNumConvs; ++i) n += (int64_t)cc[i].k * cc[i].cin * cc[i].cout + cc[i].cout;
-    for (int i = 0; i < dbh::kNumBn; ++i) n += 4 * dbh::kBnChannels[i];
-    return n;
-}
-
-// canonical blob -> packed buffer (layout: dbh_layout.h)
-void pack_weights(const float* w, int n_classes, std::vector<float>& packed) {
-    using namespace dbh;
-    packed.assign(kPackedFloats, 0.f);
-    CanonConv cc[kNumConvs];
-    canon_convs(n_classes, cc);
-    // BN2 (scale s, shift t per channel of conv1d_4's pooled output) is folded into conv1d_5, a 1x1
-    // convolution with no padding to get in the way: W5'[c][o] = W5[c][o] s[c], b5'[o] = b5[o] +
-    // sum_c W5[c][o] t[c] - exact algebra, in fp64 here; the forward kernel feeds conv1d_5 the
-    // pooled values as they are (dbh_forward.hip: stage_b_chain)
-    const float* bn_first = w;
-    for (int i = 0; i < kNumConvs; ++i) bn_first += (size_t)cc[i].k * cc[i].cin * cc[i].cout + cc[i].cout;
-    std::vector<double> fold_scale(48, 1.0), fold_shift(48, 0.0);
-    {
-        const float* q = bn_first + 4 * kBnChannels[0];      // BN2 = the second batch normalisation
-        const float *gamma = q, *beta = q + 48, *mean = q + 96, *var = q + 144;
-        for (int c = 0; c < 48; ++c) {
-            fold_scale[c] = (double)gamma[c] / std::sqrt((double)var[c] + 1e-3);
-            fold_shift[c] = (double)beta[c] - (double)mean[c] * fold_scale[c];
-        }
-    }
-    static_assert(kBnChannels[1] == 48 && kConv[4].cin == 48 && kConv[4].taps == 1, "");
-    const float* p = w;
-    for (int i = 0; i < kNumConvs; ++i) {
-        const int k = cc[i].k, cin = cc[i].cin, cout = cc[i].cout;
-        const float* kernel = p;                 // [k][cin][cout]
-        const float* bias = p + (size_t)k * cin * cout;
-        p = bias + cout;
-        float* dst = packed.data() + weight_offset(i);
-        if (i == 0) {
-            // conv1d_1 stays [tap][cout]: one value per lane and channel group, read once per workgroup
-            for (int tap = 0; tap < 3; ++tap)
-                for (int c = 0; c < cout; ++c) dst[tap * 48 + c] = kernel[(tap * cin) * cout + c];
-        } else if (kConv[i].wino) {
-            // Winograd F(2,3) / F(4,3): the transformed matrices V = G g, computed in fp64, each
-            // in fragment order
-            const int sp_n = cin / 8, nt = kConv[i].cout_pad / 16;
-            const int n_xi = kConv[i].wino == 4 ? 6 : 4;
-            static const double G23[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
-            static const double G43[6][3] = {{1. / 4, 0, 0},
-                                             {-1. / 6, -1. / 6, -1. / 6},
-                                             {-1. / 6, 1. / 6, -1. / 6},
-                                             {1. / 24, 1. / 12, 1. / 6},
-                                             {1. / 24, -1. / 12, 1. / 6},
-                                             {0, 0, 1}};
-            for (int xi = 0; xi < n_xi; ++xi) {
-                const double* G = kConv[i].wino == 4 ? G43[xi] : G23[xi];
-                for (int sp = 0; sp < sp_n; ++sp)
-                    for (int t = 0; t < nt; ++t)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 2; ++e) {
-                                // (conv1d_2's k-steps walk the channels in the order conv1d_1's
-                                // transposed MFMAs leave them in registers: dbh_layout.h)
-                                const int ci = frag_cin(i, sp, lane >> 4, e);
-                                const int co = 16 * t + (lane & 15);
-                                double v = 0.0;
-                                if (co < cout)
-                                    for (int tap = 0; tap < 3; ++tap)
-                                        v += G[tap] * (double)kernel[((size_t)tap * cin + ci) * cout + co];
-                                // F(2,3): matrix-major [xi][sp][t][lane][e].  F(4,3): by N tile,
-                                // [t][sp][xi >> 1][lane][xi & 1][e], so that one 16-byte LDS read
-                                // fetches the fragments of two matrices for two k-steps.
-                                const size_t idx =
-                                    kConv[i].wino == 4
-                                        ? (((((size_t)t * sp_n + sp) * 3 + (xi >> 1)) * 64 + lane) * 2 + (xi & 1)) * 2 + e
-                                        : wino2_by_tile(i)
-                                              ? (((((size_t)t * sp_n + sp) * 2 + (xi >> 1)) * 64 + lane) * 2 + (xi & 1)) * 2 + e
-                                              : ((((size_t)xi * sp_n + sp) * nt + t) * 64 + lane) * 2 + e;
-                                dst[idx] = (float)v;
-                            }
-            }
-        } else {
-            const int sp_n = cin / 8, nt = kConv[i].cout_pad / 16;
-            for (int tap = 0; tap < k; ++tap)
-                for (int sp = 0; sp < sp_n; ++sp)
-                    for (int t = 0; t < nt; ++t)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 2; ++e) {
-                                const int ci = frag_cin(i, sp, lane >> 4, e);
-                                const int co = 16 * t + (lane & 15);
-                                float v = co < cout ? kernel[((size_t)tap * cin + ci) * cout + co] : 0.f;
-                                if (i == 4) v = (float)((double)v * fold_scale[ci]);   // BN2's scale
-                                dst[((((size_t)tap * sp_n + sp) * nt + t) * 64 + lane) * 2 + e] = v;
-                            }
-        }
-        float* bdst = packed.data() + bias_offset(i);
-        for (int c = 0; c < cout; ++c) bdst[c] = bias[c] * kActScale;      // (exact: a power of two)
-        if (i == 4)       // ... and BN2's shift, through conv1d_5's weights, in its bias
-            for (int c = 0; c < cout; ++c) {
-                double extra = 0.0;
-                for (int ci = 0; ci < cin; ++ci) extra += (double)kernel[(size_t)ci * cout + c] * fold_shift[ci];
-                bdst[c] = (float)(((double)bias[c] + extra) * (double)kActScale);
-            }
-    }
-    for (int i = 0; i < kNumBn; ++i) {
-        const int c_n = kBnChannels[i];
-        const float *gamma = p, *beta = p + c_n, *mean = p + 2 * c_n, *var = p + 3 * c_n;
-        p += 4 * c_n;
-        float* sc = packed.data() + bn_scale_offset(i);
-        float* sh = packed.data() + bn_shift_offset(i);
-        for (int c = 0; c < c_n; ++c) {
-            const double scale = (double)gamma[c] / std::sqrt((double)var[c] + 1e-3);
-            sc[c] = (float)scale;
-            sh[c] = (float)((double)beta[c] - (double)mean[c] * scale) * kActScale;
-        }
-    }
-}
 
 using dbh_host::align256;
 using dbh_owned::DeviceBlock;
@@ -622,11 +496,11 @@ int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int 
     *model = nullptr;
     if (input_size != dbh::kWindow || n_classes < 2 || n_classes > dbh::kMaxClasses)
         return DBH_ERR_UNSUPPORTED;
-    if (n_floats != canon_param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
+    if (n_floats != dbh_net::param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
     int count = 0;
     DBH_TRY(dbh_device_count(&count));
     std::vector<float> packed;
-    pack_weights(weights, n_classes, packed);
+    dbh_pack::pack_persistent(weights, n_classes, packed);
     std::unique_ptr<dbh_model> m(new (std::nothrow) dbh_model());
     if (!m) return DBH_ERR_OUT_OF_MEMORY;
     m->n_classes = n_classes;
@@ -666,7 +540,7 @@ int dbh_model_create_ex(const float* weights, int64_t n_floats, int n_classes, i
     if (!weights || !model || flags > DBH_MODEL_GENERAL) return DBH_ERR_INVALID_ARGUMENT;
     *model = nullptr;
     if (!dbh_gen::geometry_ok(input_size, n_classes)) return DBH_ERR_UNSUPPORTED;
-    if (n_floats != canon_param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
+    if (n_floats != dbh_net::param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
     if (flags == DBH_MODEL_AUTO && input_size == dbh::kWindow && n_classes <= dbh::kMaxClasses)
         return dbh_model_create(weights, n_floats, n_classes, input_size, model);
     int count = 0;

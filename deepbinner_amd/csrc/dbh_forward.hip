@@ -1161,7 +1161,7 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
         constexpr int g = decltype(g_tag)::value, h = decltype(h_tag)::value;
         f2 y[4];
         w43t_outputs<h>(a, y);
-        // (BN2 is folded into conv5's weights and bias by the packer - dbh_api.hip: pack_weights -
+        // (BN2 is folded into conv5's weights and bias by the packer - dbh_pack.h: pack_persistent -
         // so the pooled values go to conv5 as they are; only the debug dump applies it)
         X[g][h][0] = max_raw2(y[0], y[1]);
         X[g][h][1] = max_raw2(y[2], y[3]);

@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "dbh_pack.h"
+
 namespace dbh_gen {
 
 constexpr int kMinInput = 96;          // the global average needs one position
@@ -21,11 +23,10 @@ inline bool geometry_ok(int input_size, int n_classes) {
            n_classes >= kMinClasses && n_classes <= kMaxClasses;
 }
 
-struct Net {
+struct Net : dbh_pack::GeneralOffsets {      // (where the pieces of d_params lie)
     int L = 0, C = 0;
-    int len[8] = {};               // positions after each stage: len[0] = L .. len[7] (TF rules)
-    float* d_params = nullptr;     // packed weights (device)
-    size_t w_off[20] = {}, b_off[20] = {}, sc_off[7] = {}, sh_off[7] = {};
+    int len[8] = {};               // dbh_net::stage_lengths(L)
+    float* d_params = nullptr;     // packed weights (device): dbh_pack::pack_general
     int64_t chunk = 0;             // windows per pass through the layer chain
     size_t act_floats = 0;         // activation floats per window of a chunk
 };

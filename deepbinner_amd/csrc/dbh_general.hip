@@ -18,7 +18,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 namespace dbh_gen {
 namespace {
@@ -129,8 +128,7 @@ __global__ __launch_bounds__(kThreads) void conv_kernel(ConvArgs a) {
     const long long M = a.n_win * lrows;
     const long long m_base = ((long long)blockIdx.x * 4 + wave) * (16 * kRowTiles);
     if (m_base >= M) return;
-    const int pad_total = (a.lconv - 1) * S + K - a.lin;
-    const int pad_l = pad_total > 0 ? pad_total / 2 : 0;
+    const int pad_l = dbh_net::same_pad_left(K, S, a.lin, a.lconv);
 
     long long row_base[kRowTiles];
     int ipos[kRowTiles];
@@ -337,38 +335,23 @@ __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict
 }
 
 // ---- host ------------------------------------------------------------------------------------
-struct Layer { int k, cin, cout, stride; };
-// the 20 convolutions (network_architecture.py); conv1d_20's C_out is the class count
-constexpr Layer kLayers[20] = {
-    {3, 1, 48, 2},  {3, 48, 48, 1}, {3, 48, 48, 1}, {3, 48, 48, 1}, {1, 48, 16, 1},
-    {3, 16, 48, 1}, {3, 48, 48, 1}, {3, 48, 48, 1}, {3, 48, 48, 1}, {1, 48, 48, 1},
-    {1, 48, 48, 1}, {1, 48, 16, 1}, {3, 16, 48, 1}, {1, 48, 16, 1}, {3, 16, 48, 1},
-    {3, 48, 48, 1}, {3, 192, 48, 2}, {3, 48, 48, 1}, {3, 48, 48, 1}, {1, 48, 0, 1},
-};
-constexpr int kBnChannels[7] = {48, 48, 48, 48, 192, 48, 48};
-
-template <int K, int S, int CIN, int COUT, int IN, bool POOL>
-hipError_t conv(const Net& net, int layer, int bn, const float* x, int lin, int in_stride,
-                int lconv, float* y, int out_stride, int out_off, int64_t n_win,
-                hipStream_t stream) {
-    ConvArgs a;
-    a.x = x;
-    a.w = net.d_params + net.w_off[layer];
-    a.bias = net.d_params + net.b_off[layer];
-    a.sc = bn >= 0 ? net.d_params + net.sc_off[bn] : nullptr;
-    a.sh = bn >= 0 ? net.d_params + net.sh_off[bn] : nullptr;
-    a.y = y;
-    a.n_win = n_win;
-    a.lin = lin;
-    a.in_stride = in_stride;
-    a.lconv = lconv;
-    a.out_stride = out_stride;
-    a.out_off = out_off;
-    const long long rows = (long long)n_win * (POOL ? (lconv & ~1) : lconv);
+// Convolution LAYER (0-based) of dbh_network.h's table, which gives its shapes and lengths.  IN: how
+// its input is transformed as it is loaded (kInBn, kInAvgBn: by the batch normalisation of its
+// input stage); POOL: whether the max-pool follows.
+template <int LAYER, int IN, bool POOL>
+hipError_t conv(const Net& net, const float* x, float* y, int out_stride, int out_off,
+                int64_t n_win, hipStream_t stream) {
+    constexpr dbh_net::Conv kL = dbh_net::kConvs[LAYER];
+    const float* p = net.d_params;
+    constexpr bool bn = IN != kInPlain;      // batch normalisation kL.in, 0-based kL.in - 1
+    const ConvArgs a = {x, p + net.w_off[LAYER], p + net.b_off[LAYER],
+                        bn ? p + net.sc_off[kL.in - 1] : nullptr, bn ? p + net.sh_off[kL.in - 1] : nullptr,
+                        y, n_win, net.len[kL.in], kL.cin, net.len[kL.out], out_stride, out_off};
+    const long long rows = (long long)n_win * (POOL ? (a.lconv & ~1) : a.lconv);
     if (rows == 0) return hipSuccess;
     const long long blocks = (rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    hipLaunchKernelGGL((conv_kernel<K, S, CIN, COUT, IN, POOL>), dim3((unsigned)blocks),
-                       dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL((conv_kernel<kL.k, kL.stride, kL.cin, kL.cout, IN, POOL>),
+                       dim3((unsigned)blocks), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -378,60 +361,8 @@ hipError_t create(const float* canon, int n_classes, int input_size, Net* net) {
     Net n;
     n.L = input_size;
     n.C = n_classes;
-    n.len[0] = input_size;
-    n.len[1] = (input_size + 1) / 2;     // conv1d_1, stride 2, SAME
-    n.len[2] = n.len[1] / 2;             // max-pools: 'valid'
-    n.len[3] = n.len[2] / 2;
-    n.len[4] = n.len[3] / 2;
-    n.len[5] = n.len[4] / 2;
-    n.len[6] = (n.len[5] + 1) / 2;       // conv1d_17, stride 2, SAME
-    n.len[7] = n.len[6] / 2;
-    // packed layout: per conv weights then bias, then BN scale / shift, each 16-byte aligned
-    std::vector<float> packed;
-    auto take = [&](size_t count) {
-        const size_t at = packed.size();
-        packed.resize(at + ((count + 3) & ~(size_t)3), 0.f);
-        return at;
-    };
-    const float* p = canon;
-    for (int i = 0; i < 20; ++i) {
-        const int k = kLayers[i].k, cin = kLayers[i].cin;
-        const int cout = i == 19 ? n_classes : kLayers[i].cout;
-        const float* kernel = p;                   // [k][cin][cout]
-        const float* bias = p + (size_t)k * cin * cout;
-        p = bias + cout;
-        n.w_off[i] = take((size_t)k * cin * cout);
-        float* dst = packed.data() + n.w_off[i];
-        if (i == 0 || i == 19) {
-            std::copy(kernel, kernel + (size_t)k * cin * cout, dst);    // as stored
-        } else {
-            const int G = cin / 16, NT = cout / 16;
-            for (int t = 0; t < k; ++t)
-                for (int g = 0; g < G; ++g)
-                    for (int nt = 0; nt < NT; ++nt)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 4; ++j) {
-                                const int ci = 16 * g + 4 * (lane >> 4) + j;
-                                const int co = 16 * nt + (lane & 15);
-                                dst[((((size_t)t * G + g) * NT + nt) * 64 + lane) * 4 + j] =
-                                    kernel[((size_t)t * cin + ci) * cout + co];
-                            }
-        }
-        n.b_off[i] = take((size_t)cout);
-        std::copy(bias, bias + cout, packed.data() + n.b_off[i]);
-    }
-    for (int i = 0; i < 7; ++i) {
-        const int c_n = kBnChannels[i];
-        const float *gamma = p, *beta = p + c_n, *mean = p + 2 * c_n, *var = p + 3 * c_n;
-        p += 4 * c_n;
-        n.sc_off[i] = take((size_t)c_n);
-        n.sh_off[i] = take((size_t)c_n);
-        for (int c = 0; c < c_n; ++c) {
-            const double scale = (double)gamma[c] / std::sqrt((double)var[c] + 1e-3);
-            packed[n.sc_off[i] + c] = (float)scale;
-            packed[n.sh_off[i] + c] = (float)((double)beta[c] - (double)mean[c] * scale);
-        }
-    }
+    dbh_net::stage_lengths(input_size, n.len);
+    const std::vector<float> packed = dbh_pack::pack_general(canon, n_classes, &n);
     // activations per window: two ping-pong buffers of conv1d_1's size, the inception's 16- and
     // 48-channel intermediates, the 192-channel concat, two buffers for conv1d_17 .. conv1d_19
     n.act_floats = (size_t)2 * n.len[1] * 48 + (size_t)n.len[4] * 64 + (size_t)n.len[5] * 192 +
@@ -477,29 +408,29 @@ hipError_t forward(const Net& net, const float* x, const int16_t* samples, const
                            net.d_params + net.b_off[0], P);
         hipError_t e = hipGetLastError();
         // stage B: BN1 -> conv2 -> conv3 -> conv4 -> pool
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInBn, false>(net, 1, 0, P, len[1], 48, len[1], Q, 48, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInPlain, false>(net, 2, -1, Q, len[1], 48, len[1], P, 48, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInPlain, true>(net, 3, -1, P, len[1], 48, len[1], Q, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<1, kInBn, false>(net, P, Q, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<2, kInPlain, false>(net, Q, P, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<3, kInPlain, true>(net, P, Q, 48, 0, n, stream);
         // stage C: BN2 -> conv5 -> conv6 -> conv7 -> pool
-        if (e == hipSuccess) e = conv<1, 1, 48, 16, kInBn, false>(net, 4, 1, Q, len[2], 48, len[2], P, 16, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 16, 48, kInPlain, false>(net, 5, -1, P, len[2], 16, len[2], Q, 48, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInPlain, true>(net, 6, -1, Q, len[2], 48, len[2], P, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<4, kInBn, false>(net, Q, P, 16, 0, n, stream);
+        if (e == hipSuccess) e = conv<5, kInPlain, false>(net, P, Q, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<6, kInPlain, true>(net, Q, P, 48, 0, n, stream);
         // stage D: BN3 -> conv8 -> conv9 -> pool
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInBn, false>(net, 7, 2, P, len[3], 48, len[3], Q, 48, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInPlain, true>(net, 8, -1, Q, len[3], 48, len[3], P, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<7, kInBn, false>(net, P, Q, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<8, kInPlain, true>(net, Q, P, 48, 0, n, stream);
         // stage E: the inception block on BN4(P), each branch pooled into its slice of Cc
-        if (e == hipSuccess) e = conv<1, 1, 48, 48, kInAvgBn, true>(net, 9, 3, P, len[4], 48, len[4], Cc, 192, 0, n, stream);
-        if (e == hipSuccess) e = conv<1, 1, 48, 48, kInBn, true>(net, 10, 3, P, len[4], 48, len[4], Cc, 192, 48, n, stream);
-        if (e == hipSuccess) e = conv<1, 1, 48, 16, kInBn, false>(net, 11, 3, P, len[4], 48, len[4], T, 16, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 16, 48, kInPlain, true>(net, 12, -1, T, len[4], 16, len[4], Cc, 192, 96, n, stream);
-        if (e == hipSuccess) e = conv<1, 1, 48, 16, kInBn, false>(net, 13, 3, P, len[4], 48, len[4], T, 16, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 16, 48, kInPlain, false>(net, 14, -1, T, len[4], 16, len[4], T48, 48, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInPlain, true>(net, 15, -1, T48, len[4], 48, len[4], Cc, 192, 144, n, stream);
+        if (e == hipSuccess) e = conv<9, kInAvgBn, true>(net, P, Cc, 192, 0, n, stream);
+        if (e == hipSuccess) e = conv<10, kInBn, true>(net, P, Cc, 192, 48, n, stream);
+        if (e == hipSuccess) e = conv<11, kInBn, false>(net, P, T, 16, 0, n, stream);
+        if (e == hipSuccess) e = conv<12, kInPlain, true>(net, T, Cc, 192, 96, n, stream);
+        if (e == hipSuccess) e = conv<13, kInBn, false>(net, P, T, 16, 0, n, stream);
+        if (e == hipSuccess) e = conv<14, kInPlain, false>(net, T, T48, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<15, kInPlain, true>(net, T48, Cc, 192, 144, n, stream);
         // stage F: BN5 -> conv17 (stride 2)
-        if (e == hipSuccess) e = conv<3, 2, 192, 48, kInBn, false>(net, 16, 4, Cc, len[5], 192, len[6], F1, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<16, kInBn, false>(net, Cc, F1, 48, 0, n, stream);
         // stage G: BN6 -> conv18 -> conv19 -> pool
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInBn, false>(net, 17, 5, F1, len[6], 48, len[6], F2, 48, 0, n, stream);
-        if (e == hipSuccess) e = conv<3, 1, 48, 48, kInPlain, true>(net, 18, -1, F2, len[6], 48, len[6], F1, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<17, kInBn, false>(net, F1, F2, 48, 0, n, stream);
+        if (e == hipSuccess) e = conv<18, kInPlain, true>(net, F2, F1, 48, 0, n, stream);
         // head: BN7 -> conv20 -> ReLU -> mean -> softmax
         if (e == hipSuccess) {
             hipLaunchKernelGGL(head_kernel, dim3((unsigned)n), dim3(kThreads), 0, stream, F1,

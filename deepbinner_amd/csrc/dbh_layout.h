@@ -1,20 +1,23 @@
-// dbh_layout.h — compile-time description of the Deepbinner network
-// (reference deepbinner/network_architecture.py:18-95) as the forward kernel sees it:
-// which convolutions run on the MFMA path, where their pre-swizzled "fragment order" weights
-// live in the packed HBM buffer, and how the LDS arena is carved per stage.
-//
-// Shared by the host-side packer (dbh_api.hip) and the device code (dbh_forward.hip).
+// dbh_layout.h — the Deepbinner network as the persistent forward kernel (dbh_forward.hip) sees it:
+// which convolutions run on the MFMA path and how (direct, Winograd F(2,3) or F(4,3)), where their
+// pre-swizzled "fragment order" weights live in the packed HBM buffer, and how the LDS arena is
+// carved per stage.  The network itself - shapes, strides, stage lengths - is dbh_network.h's.
+// Read by the device code (dbh_forward.hip), by the host code that launches it (dbh_api.hip) and by
+// the packer that writes the buffer (dbh_pack.h: pack_persistent).
 #pragma once
+
+#include "dbh_network.h"
 
 namespace dbh {
 
+using dbh_net::kBnChannels, dbh_net::kNumBn, dbh_net::kNumConvs;
+
 constexpr int kWindow = 1024;          // model input size (classify.py:96)
 constexpr int kMaxClasses = 32;        // conv1d_20 is padded to two 16-wide N tiles
-constexpr int kNumConvs = 20;
-constexpr int kNumBn = 7;
 
 // ---------------------------------------------------------------------------------------------
-// Convolution table (index = Keras layer number - 1).  cout_pad is C_out rounded up to 16.
+// Convolution table (index = Keras layer number - 1): taps, cin and stride are dbh_network.h's,
+// cout_pad is C_out rounded up to 16 (conv1d_20: kMaxClasses, zero padded).
 // ---------------------------------------------------------------------------------------------
 // wino = 2: the layer runs as Winograd F(2,3) — two outputs per position pair from FOUR
 //   element-wise-transformed products instead of six (1.5x fewer MFMAs); weights are stored as
@@ -24,35 +27,28 @@ constexpr int kNumBn = 7;
 //   V2 = -(g0-g1+g2)/6, V3 = g0/24+g1/12+g2/6, V4 = g0/24-g1/12+g2/6, V5 = g2.
 // wino = 0: direct convolution.
 struct ConvSpec { int taps, cin, cout_pad, stride; int wino; };
+constexpr ConvSpec spec(int i, int wino) {
+    const dbh_net::Conv& c = dbh_net::kConvs[i];
+    return {c.k, c.cin, (dbh_net::cout(i, kMaxClasses) + 15) / 16 * 16, c.stride, wino};
+}
 constexpr ConvSpec kConv[kNumConvs] = {
-    {3, 1, 48, 2, 0},     // conv1d_1   (K = 3 padded to one MFMA k-step)
-    {3, 48, 48, 1, 4},        // conv1d_2
-    {3, 48, 48, 1, 4},        // conv1d_3
-    {3, 48, 48, 1, 4},        // conv1d_4
-    {1, 48, 16, 1, 0},    // conv1d_5
-    {3, 16, 48, 1, 2},        // conv1d_6
-    {3, 48, 48, 1, 4},        // conv1d_7
-    {3, 48, 48, 1, 4},        // conv1d_8   (round 6: F(4,3), four windows at a time - stage_d_chain)
-    {3, 48, 48, 1, 4},        // conv1d_9
-    {1, 48, 48, 1, 0},    // conv1d_10
-    {1, 48, 48, 1, 0},    // conv1d_11
-    {1, 48, 16, 1, 0},    // conv1d_12
-    {3, 16, 48, 1, 2},        // conv1d_13
-    {1, 48, 16, 1, 0},    // conv1d_14
-    {3, 16, 48, 1, 2},        // conv1d_15
-    {3, 48, 48, 1, 2},    // conv1d_16  (round 6: F(2,3) on the chain's position pairs)
-    {3, 192, 48, 2, 0},   // conv1d_17
-    {3, 48, 48, 1, 0},    // conv1d_18
-    {3, 48, 48, 1, 0},    // conv1d_19
-    {1, 48, 32, 1, 0},    // conv1d_20  (n_classes <= 32, zero padded)
+    spec(0, 0),                                      // conv1d_1 (K = 3 padded to one MFMA k-step)
+    spec(1, 4),  spec(2, 4),  spec(3, 4),  spec(4, 0),    // conv1d_2..5
+    spec(5, 2),  spec(6, 4),                              // conv1d_6, 7
+    spec(7, 4),  spec(8, 4),      // conv1d_8, 9 (round 6: F(4,3), four windows at a time - stage_d_chain)
+    spec(9, 0),  spec(10, 0), spec(11, 0), spec(12, 2), spec(13, 0), spec(14, 2),    // conv1d_10..15
+    spec(15, 2),                  // conv1d_16 (round 6: F(2,3) on the chain's position pairs)
+    spec(16, 0), spec(17, 0), spec(18, 0), spec(19, 0),   // conv1d_17..20
 };
-constexpr int kBnChannels[kNumBn] = {48, 48, 48, 48, 192, 48, 48};
 // F(2,3) layers whose weights are stored by N tile ([t][sp][matrix pair][lane][matrix][e]) for the
 // N-tile-outer loops of dbh_forward.hip (conv1d_6, conv1d_13, conv1d_15, conv1d_16).
 constexpr bool wino2_by_tile(int i) { return i == 5 || i == 12 || i == 14 || i == 15; }
 // positions each convolution produces (after its stride, before any pooling)
-constexpr int kConvLout[kNumConvs] = {512, 512, 512, 512, 256, 256, 256, 128, 128, 64,
-                                      64,  64,  64,  64,  64,  64,  16,  16,  16,  8};
+constexpr int conv_lout(int i) {
+    int len[8] = {};
+    dbh_net::stage_lengths(kWindow, len);
+    return len[dbh_net::kConvs[i].out];
+}
 
 // v_mfma_f32_16x16x4_f32 instructions the forward kernel ISSUES for convolution i of one window
 // (2,048 FLOP each): M tiles of 16 positions (pairs / quads for the Winograd layers) x N tiles of
@@ -63,7 +59,7 @@ constexpr int conv_mfmas(int i, int n_classes) {
     // conv1d_1 is computed inside conv1d_2's first tile, transposed (channels x positions) and with
     // the halo rows of every quad tile recomputed: per wave 6 input rows x 3 channel groups
     if (i == 0) return 8 * 6 * 3;
-    const int units = kConvLout[i] / (kConv[i].wino ? kConv[i].wino : 1);
+    const int units = conv_lout(i) / (kConv[i].wino ? kConv[i].wino : 1);
     const int m_tiles = (units + 15) / 16;
     const int n_tiles = i == kNumConvs - 1 ? (n_classes <= 16 ? 1 : 2) : kConv[i].cout_pad / 16;
     const int mats = kConv[i].wino == 4 ? 6 : kConv[i].wino == 2 ? 4 : kConv[i].taps;
@@ -101,8 +97,7 @@ constexpr float kActUnscale = 1152921504606846976.f;
 
 // ---------------------------------------------------------------------------------------------
 // Packed parameter buffer (floats).  [ weights of conv 1..20 | bias of conv 1..20 (cout_pad
-// each) | BN scale,shift of bn 1..7 ].  BN is pre-folded on the host in fp64:
-//   scale = gamma / sqrt(var + 1e-3),  shift = beta - mean * scale.
+// each) | BN scale,shift of bn 1..7 ].  BN is pre-folded on the host (dbh_network.h: bn_fold).
 // Biases and shifts are stored times kActScale (see above).
 // ---------------------------------------------------------------------------------------------
 constexpr int weight_offset(int i) {
@@ -139,7 +134,7 @@ constexpr int kPackedFloats = bn_scale_offset(kNumBn);
 // (g = channel group of the MFMA, r = result register).  Those registers, ReLU'd, batch-normalised
 // and Winograd-transformed in place, ARE conv1d_2's A fragments if k-step s = 4g + r of conv1d_2
 // contracts over channels {16g + 4q + r : q = 0..3} - a permutation of the input channels that
-// only the packer needs to know about (dbh_api.hip: pack_weights).
+// only the packer needs to know about (dbh_pack.h: pack_persistent).
 // conv1d_3 and conv1d_4 take the same order (round 5): all of stage B runs in that TRANSPOSED
 // orientation (M = 16 output channels, N = 16 quads), so that a layer's accumulators - lane
 // (quad, q), registers = channels 16t + 4q + r - are, after the output transform, ReLU and the next

@@ -25,13 +25,15 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "dbh_network.h"
+
 namespace dbh_train {
 
 // The limit of one call: n_windows * input_size <= kMaxBatchSamples (256 windows of 1,024 samples
 // are a quarter of it, 20 of 16,384 a third).  Batch statistics are per call, so a batch is never
 // split; the workspace grows by about 1.3 KB per sample (dbh_gradients_workspace_bytes).
 constexpr int64_t kMaxBatchSamples = (int64_t)1 << 20;
-constexpr int kBnTotal = 480;              // channels of batch_normalization_1..7
+constexpr int kBnTotal = dbh_net::bn_channel_offset(dbh_net::kNumBn);   // 480 channels, BN 1..7
 constexpr int kStatsFloats = 2 * kBnTotal; // batch mean then batch variance per layer
 
 __host__ __device__ inline uint32_t mix32(uint32_t h) {
@@ -53,7 +55,6 @@ __host__ __device__ inline uint32_t dropout_bits(uint32_t seed_lo, uint32_t seed
     return h >> 8;
 }
 
-int64_t param_count(int n_classes);
 size_t workspace_bytes(int n_classes, int input_size, int64_t n_windows);
 
 // Everything on the device, queued on `stream`, nothing synchronised.  weights: the canonical blob

@@ -23,6 +23,8 @@
 
 #include "../../include/deepbinner_hip.h"
 #include "dbh_general.h"
+#include "dbh_network.h"
+#include "dbh_owned.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,18 +38,10 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int kThreads = 256;
 constexpr int kRowTiles = 2;
 constexpr int kRowsPerBlock = 4 * 16 * kRowTiles;
-constexpr double kBnEps = 1e-3;            // model_format.BN_EPSILON
 constexpr int kMaxPartials = 256;          // partial sums per reduction, at most
 constexpr int kMaxL7 = dbh_gen::kMaxInput / 128;
 
-struct Layer { int k, cin, cout, stride; };
-constexpr Layer kLayers[20] = {
-    {3, 1, 48, 2},  {3, 48, 48, 1}, {3, 48, 48, 1}, {3, 48, 48, 1}, {1, 48, 16, 1},
-    {3, 16, 48, 1}, {3, 48, 48, 1}, {3, 48, 48, 1}, {3, 48, 48, 1}, {1, 48, 48, 1},
-    {1, 48, 48, 1}, {1, 48, 16, 1}, {3, 16, 48, 1}, {1, 48, 16, 1}, {3, 16, 48, 1},
-    {3, 48, 48, 1}, {3, 192, 48, 2}, {3, 48, 48, 1}, {3, 48, 48, 1}, {1, 48, 0, 1},
-};
-constexpr int kBnChannels[7] = {48, 48, 48, 48, 192, 48, 48};
+using namespace dbh_net;      // the network: dbh_network.h
 
 struct Drop {
     uint32_t seed_lo, seed_hi, layer, threshold;
@@ -633,33 +627,8 @@ inline unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) /
 
 struct Geometry {
     int L, C, len[8];
-    size_t w_off[20], b_off[20], bn_off[7];
-    Geometry(int input_size, int n_classes) : L(input_size), C(n_classes) {
-        len[0] = L;
-        len[1] = (L + 1) / 2;
-        for (int i = 2; i <= 5; ++i) len[i] = len[i - 1] / 2;
-        len[6] = (len[5] + 1) / 2;
-        len[7] = len[6] / 2;
-        size_t at = 0;
-        for (int i = 0; i < 20; ++i) {
-            const size_t cout = i == 19 ? (size_t)C : (size_t)kLayers[i].cout;
-            w_off[i] = at;
-            at += (size_t)kLayers[i].k * kLayers[i].cin * cout;
-            b_off[i] = at;
-            at += cout;
-        }
-        for (int i = 0; i < 7; ++i) {
-            bn_off[i] = at;
-            at += (size_t)4 * kBnChannels[i];
-        }
-    }
+    Geometry(int input_size, int n_classes) : L(input_size), C(n_classes) { stage_lengths(L, len); }
 };
-
-// SAME padding on the left of a convolution (TensorFlow: the remainder goes right)
-inline int pad_left(int k, int stride, int lin, int lout) {
-    const int total = (lout - 1) * stride + k - lin;
-    return total > 0 ? total / 2 : 0;
-}
 
 // the workspace, carved in one order by workspace_bytes() and gradients()
 struct Workspace {
@@ -735,21 +704,16 @@ struct Run {
         d.layer = (uint32_t)bn + 1;
         return d;
     }
-    size_t stat_off(int bn) const {
-        size_t at = 0;
-        for (int i = 0; i < bn; ++i) at += kBnChannels[i];
-        return at;
-    }
 
     template <int CA, int CN, bool DGRAD>
     void gemm(int layer, const float* a, int la, int a_stride, int a_off, float* y, int ly,
               int y_stride, int y_off, const float* mask, bool accumulate) {
         if (!ok()) return;
-        const Layer& l = kLayers[layer];
+        const Conv& l = kConvs[layer];
         GemmArgs ga;
         ga.a = a;
-        ga.w = w + g.w_off[layer];
-        ga.bias = w + g.b_off[layer];
+        ga.w = w + blob_kernel(layer, g.C);
+        ga.bias = w + blob_bias(layer, g.C);
         ga.mask = mask;
         ga.y = y;
         ga.n_win = n;
@@ -757,7 +721,7 @@ struct Run {
         ga.ly = ly; ga.y_stride = y_stride; ga.y_off = y_off;
         ga.k = l.k; ga.stride = l.stride; ga.cin = l.cin; ga.cout = l.cout;
         // forward: a is the input (la) and y the output (ly); data gradient: the other way round
-        ga.pad_l = DGRAD ? pad_left(l.k, l.stride, ly, la) : pad_left(l.k, l.stride, la, ly);
+        ga.pad_l = DGRAD ? same_pad_left(l.k, l.stride, ly, la) : same_pad_left(l.k, l.stride, la, ly);
         ga.accumulate = accumulate ? 1 : 0;
         const long long rows = (long long)n * ly;
         hipLaunchKernelGGL((conv_gemm<CA, CN, DGRAD>), dim3((unsigned)((rows + kRowsPerBlock - 1) / kRowsPerBlock)),
@@ -765,7 +729,7 @@ struct Run {
     }
     // forward convolution of `layer`: x [n][lin][cin at x_off of x_stride] -> y
     void conv(int layer, const float* x, int lin, float* y, int lout, int y_stride = 0, int y_off = 0) {
-        const Layer& l = kLayers[layer];
+        const Conv& l = kConvs[layer];
         if (y_stride == 0) y_stride = l.cout;
         if (l.cin == 48 && l.cout == 48) gemm<48, 48, false>(layer, x, lin, 48, 0, y, lout, y_stride, y_off, nullptr, false);
         else if (l.cin == 48 && l.cout == 16) gemm<48, 16, false>(layer, x, lin, 48, 0, y, lout, y_stride, y_off, nullptr, false);
@@ -777,9 +741,9 @@ struct Run {
     // its input, through the ReLU of the layer that produced it where `mask` names that output
     void conv_backward(int layer, const float* x, int lin, const float* dz, int lout, int z_stride,
                        int z_off, float* dx, const float* mask, bool accumulate) {
-        const Layer& l = kLayers[layer];
+        const Conv& l = kConvs[layer];
         const long long rows = (long long)n * lout;
-        bias_grad(dz, rows, l.cout, z_stride, z_off, grads + g.b_off[layer]);
+        bias_grad(dz, rows, l.cout, z_stride, z_off, grads + blob_bias(layer, g.C));
         if (!ok()) return;
         WgradArgs wa;
         wa.x = x; wa.dz = dz; wa.part = (float*)b.part;
@@ -788,7 +752,7 @@ struct Run {
         wa.lx = lin; wa.x_stride = l.cin; wa.x_off = 0;
         wa.lz = lout; wa.z_stride = z_stride; wa.z_off = z_off;
         wa.k = l.k; wa.stride = l.stride; wa.cin = l.cin; wa.cout = l.cout;
-        wa.pad_l = pad_left(l.k, l.stride, lin, lout);
+        wa.pad_l = same_pad_left(l.k, l.stride, lin, lout);
         const long long waves = (rows + wa.rows_per_wave - 1) / wa.rows_per_wave;
         const unsigned wgs = (unsigned)((waves + 3) / 4);
         const dim3 grid(wgs, (unsigned)(l.k * (l.cin / 16)));
@@ -797,7 +761,7 @@ struct Run {
         if (!ok()) return;
         const long long count = (long long)l.k * l.cin * l.cout;
         hipLaunchKernelGGL((reduce_partials<float>), dim3(blocks_for(count)), dim3(kThreads), 0, stream,
-                           (const float*)b.part, (int)(wgs * 4), count, count, grads + g.w_off[layer]);
+                           (const float*)b.part, (int)(wgs * 4), count, count, grads + blob_kernel(layer, g.C));
         if (!dx) return;
         // the data gradient's contraction runs over cout, its output over cin
         if (l.cin == 48 && l.cout == 48) gemm<48, 48, true>(layer, dz, lout, z_stride, z_off, dx, lin, 48, 0, mask, accumulate);
@@ -825,7 +789,7 @@ struct Run {
         if (!ok()) return;
         const int C = kBnChannels[bn];
         const long long rows = (long long)n * len;
-        const size_t so = stat_off(bn);
+        const size_t so = bn_channel_offset(bn);
         ColArgs ca = {};
         ca.a = x; ca.rows = rows; ca.C = C; ca.stride = C; ca.off = 0;
         const unsigned parts = col_launch(ca);
@@ -838,7 +802,7 @@ struct Run {
                            (int)parts, C, (double)rows, (const double*)(b.mean + so), b.istd + so,
                            stats + 2 * so);
         if (!ok()) return;
-        const float* gamma = w + g.bn_off[bn];
+        const float* gamma = w + blob_bn(bn, g.C);
         hipLaunchKernelGGL(bn_apply, dim3(blocks_for(rows * C)), dim3(kThreads), 0, stream, x,
                            rows * C, C, len, gamma, gamma + C, (const double*)(b.mean + so),
                            (const double*)(b.istd + so), drop_of(bn), h);
@@ -848,19 +812,19 @@ struct Run {
         if (!ok()) return;
         const int C = kBnChannels[bn];
         const long long rows = (long long)n * len;
-        const size_t so = stat_off(bn);
+        const size_t so = bn_channel_offset(bn);
         ColArgs ca = {};
         ca.a = dh; ca.rows = rows; ca.C = C; ca.stride = C; ca.off = 0;
         ca.x = x; ca.mean = b.mean + so; ca.istd = b.istd + so; ca.len = len;
         ca.drop = drop_of(bn);
         const unsigned parts = col_launch(ca);
         hipLaunchKernelGGL((col_sums<kColBnBwd>), dim3(parts), dim3(kThreads), 0, stream, ca);
-        float* dgamma = grads + g.bn_off[bn];
+        float* dgamma = grads + blob_bn(bn, g.C);
         hipLaunchKernelGGL(finish_bn_backward, dim3(1), dim3(kThreads), 0, stream,
                            (const double*)b.part, (int)parts, C, dgamma, dgamma + C, b.sums);
         if (!ok()) return;
         hipLaunchKernelGGL(bn_backward_apply, dim3(blocks_for(rows * C)), dim3(kThreads), 0, stream,
-                           dh, x, rows * C, C, len, w + g.bn_off[bn], (const double*)(b.mean + so),
+                           dh, x, rows * C, C, len, w + blob_bn(bn, g.C), (const double*)(b.mean + so),
                            (const double*)(b.istd + so), (const double*)b.sums, 1.0 / (double)rows,
                            drop_of(bn), dx);
     }
@@ -882,11 +846,6 @@ struct Run {
 };
 
 }  // namespace
-
-int64_t param_count(int n_classes) {
-    const Geometry g(dbh_gen::kMinInput, n_classes);
-    return (int64_t)(g.bn_off[6] + (size_t)4 * kBnChannels[6]);
-}
 
 size_t workspace_bytes(int n_classes, int input_size, int64_t n_windows) {
     const Geometry g(input_size, n_classes);
@@ -916,13 +875,13 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     Run r{g, b, weights, grads, stats, n, drop, stream};
 
     // the moving-statistics slots stay zero; everything else is written below
-    r.err = hipMemsetAsync(grads, 0, (size_t)param_count(C) * sizeof(float), stream);
+    r.err = hipMemsetAsync(grads, 0, (size_t)dbh_net::param_count(C) * sizeof(float), stream);
 
     // ---- forward -----------------------------------------------------------------------------
     if (r.ok())
         hipLaunchKernelGGL(conv1_forward, dim3(blocks_for(n * len[1] * 48)), dim3(kThreads), 0,
-                           stream, x, weights + g.w_off[0], (long long)n, g.L, len[1],
-                           pad_left(3, 2, g.L, len[1]), b.a1);
+                           stream, x, weights + blob_kernel(0, g.C), (long long)n, g.L, len[1],
+                           same_pad_left(3, 2, g.L, len[1]), b.a1);
     r.bn_forward(0, b.a1, len[1], b.h1);
     r.conv(1, b.h1, len[1], b.a2, len[1]);
     r.conv(2, b.a2, len[1], b.a3, len[1]);
@@ -958,7 +917,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     r.bn_forward(6, b.p19, len[7], b.h7);
     if (r.ok())
         hipLaunchKernelGGL(head_forward, dim3((unsigned)n), dim3(kThreads), 0, stream,
-                           (const float*)b.h7, len[7], weights + g.w_off[19], weights + g.b_off[19],
+                           (const float*)b.h7, len[7], weights + blob_kernel(19, g.C), weights + blob_bias(19, g.C),
                            C, (const int*)labels, 1.0 / (double)n, b.dz20, b.loss, b.correct);
     if (r.ok())
         hipLaunchKernelGGL(finish_loss, dim3(1), dim3(64), 0, stream, (const double*)b.loss,
@@ -966,7 +925,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
 
     // ---- backward ----------------------------------------------------------------------------
     const long long rows7 = (long long)n * len[7];
-    r.bias_grad(b.dz20, rows7, C, C, 0, grads + g.b_off[19]);
+    r.bias_grad(b.dz20, rows7, C, C, 0, grads + blob_bias(19, g.C));
     if (r.ok()) {
         const long long per = rows_per_part(rows7, 16, 1);
         const unsigned parts = (unsigned)((rows7 + per - 1) / per);
@@ -974,9 +933,9 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
                            (const float*)b.h7, (const float*)b.dz20, rows7, per, C, (double*)b.part);
         hipLaunchKernelGGL((reduce_partials<double>), dim3(blocks_for(48 * C)), dim3(kThreads), 0,
                            stream, (const double*)b.part, (int)parts, (long long)48 * C,
-                           (long long)48 * C, grads + g.w_off[19]);
+                           (long long)48 * C, grads + blob_kernel(19, g.C));
         hipLaunchKernelGGL(head_dgrad, dim3(blocks_for(rows7 * 48)), dim3(kThreads), 0, stream,
-                           (const float*)b.dz20, weights + g.w_off[19], rows7, C, b.gA);
+                           (const float*)b.dz20, weights + blob_kernel(19, g.C), rows7, C, b.gA);
     }
     // stage G
     r.bn_backward(6, b.gA, b.p19, len[7], b.gB);
@@ -1025,7 +984,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
         const long long per = rows_per_part(rows, 64, 1);
         const unsigned parts = (unsigned)((rows + per - 1) / per);
         hipLaunchKernelGGL(conv1_wgrad, dim3(parts), dim3(kThreads), 0, stream, x,
-                           (const float*)b.gB, rows, g.L, len[1], pad_left(3, 2, g.L, len[1]), per,
+                           (const float*)b.gB, rows, g.L, len[1], same_pad_left(3, 2, g.L, len[1]), per,
                            (double*)b.part);
         hipLaunchKernelGGL((reduce_partials<double>), dim3(1), dim3(kThreads), 0, stream,
                            (const double*)b.part, (int)parts, (long long)192, (long long)192, grads);
@@ -1042,18 +1001,11 @@ namespace {
 int check_arguments(int64_t n_floats, int n_classes, int input_size, int64_t n_windows,
                     float dropout_rate) {
     if (!dbh_gen::geometry_ok(input_size, n_classes)) return DBH_ERR_UNSUPPORTED;
-    if (n_floats != dbh_train::param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
+    if (n_floats != dbh_net::param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
     if (n_windows < 1 || !(dropout_rate >= 0.f && dropout_rate < 1.f)) return DBH_ERR_INVALID_ARGUMENT;
     if (n_windows > dbh_train::kMaxBatchSamples / input_size) return DBH_ERR_UNSUPPORTED;
     return DBH_OK;
 }
-
-struct DeviceBlock {
-    void* p = nullptr;
-    ~DeviceBlock() {
-        if (p) (void)hipFree(p);
-    }
-};
 
 #define DBH_TRAIN_HIP(call)                                                       \
     do {                                                                          \
@@ -1074,7 +1026,7 @@ int dbh_gradients_max_windows(int input_size, int64_t* n_windows) {
 int dbh_gradients_workspace_bytes(int n_classes, int input_size, int64_t n_windows, size_t* bytes) {
     if (!bytes) return DBH_ERR_INVALID_ARGUMENT;
     const int st = check_arguments(dbh_gen::geometry_ok(input_size, n_classes)
-                                       ? dbh_train::param_count(n_classes) : 0,
+                                       ? dbh_net::param_count(n_classes) : 0,
                                    n_classes, input_size, n_windows, 0.f);
     if (st != DBH_OK) return st;
     *bytes = dbh_train::workspace_bytes(n_classes, input_size, n_windows);
@@ -1119,9 +1071,9 @@ int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, in
     const size_t at_g = up(w_bytes), at_x = at_g + up(w_bytes), at_l = at_x + up(x_bytes);
     const size_t at_s = at_l + up(l_bytes), at_o = at_s + up(s_bytes), at_w = at_o + 256;
     const size_t total = at_w + dbh_train::workspace_bytes(n_classes, input_size, n_windows);
-    DeviceBlock block;
-    DBH_TRAIN_HIP(hipMalloc(&block.p, total));
-    char* d = (char*)block.p;
+    dbh_owned::DeviceBlock block;
+    DBH_TRAIN_HIP(block.reserve(total));
+    char* d = block.as<char>();
     DBH_TRAIN_HIP(hipMemcpyAsync(d, weights_host, w_bytes, hipMemcpyHostToDevice, 0));
     DBH_TRAIN_HIP(hipMemcpyAsync(d + at_x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
     DBH_TRAIN_HIP(hipMemcpyAsync(d + at_l, labels_host, l_bytes, hipMemcpyHostToDevice, 0));

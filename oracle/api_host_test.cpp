@@ -1,17 +1,25 @@
 // TEST INFRASTRUCTURE (oracle/): the host-side arithmetic of libdeepbinner_hip.so's API layer
-// (deepbinner_amd/csrc/dbh_host_layout.h, the very header dbh_api.hip is compiled from) as a program
+// (deepbinner_amd/csrc/dbh_host_layout.h, dbh_network.h and dbh_pack.h, the very headers the library
+// is compiled from) as a program
 // of its own, so that tests/test_api_host.py can hold it to account on the build box, without a
 // GPU - and so that it can run under AddressSanitizer (oracle/Makefile: api_host_test_asan).  Not
 // part of the product; nothing in deepbinner_amd/ calls it.
 //   api_host_test [RECORDS]      RECORDS: a file of dbh_inflate_stream records
 // One line per check, "ok ..." or "FAIL ..."; "model_steps INPUT SCAN = STEPS" and, with RECORDS,
 // "order I J K ..." for the caller to compare.  Exit status 1 if a check failed.
+//   api_host_test --network [BLOB CLASSES]...      BLOB: a canonical weight blob (fp32) of CLASSES
+// The network table of dbh_network.h ("conv", "bn", "bn_eps", "param_count", "blob",
+// "stage_lengths", "same_pad_left") and, per BLOB, "packed persistent|general NAME CLASSES FLOATS
+// DIGEST": the 64-bit FNV-1a digest of each image dbh_pack.h makes of it - for the caller to compare.
+#include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <utility>
 #include <vector>
 
 #include "../deepbinner_amd/csrc/dbh_host_layout.h"
+#include "../deepbinner_amd/csrc/dbh_pack.h"
 
 static int g_failed = 0;
 
@@ -96,7 +104,84 @@ static void check_uniform_length() {
            "uniform_length");
 }
 
+// the network as dbh_network.h has it, for the caller to hold to model_format.py and the oracle
+static void print_network() {
+    namespace net = dbh_net;
+    for (int i = 0; i < net::kNumConvs; ++i) {
+        const net::Conv& c = net::kConvs[i];
+        std::printf("conv %d %d %d %d %d in %d out %d\n", i + 1, c.k, c.cin, c.cout, c.stride, c.in, c.out);
+    }
+    for (int j = 0; j < net::kNumBn; ++j) std::printf("bn %d %d\n", j + 1, net::kBnChannels[j]);
+    std::printf("bn_eps %.17g\n", net::kBnEps);
+    for (int n_classes : {2, 13, 32, 33, 256})
+        std::printf("param_count %d %lld\n", n_classes, (long long)net::param_count(n_classes));
+    for (int n_classes : {2, 256}) {
+        std::printf("blob %d", n_classes);      // kernel and bias of conv 1..20, then BN 1..7
+        for (int i = 0; i < net::kNumConvs; ++i)
+            std::printf(" %zu %zu", net::blob_kernel(i, n_classes), net::blob_bias(i, n_classes));
+        for (int j = 0; j < net::kNumBn; ++j) std::printf(" %zu", net::blob_bn(j, n_classes));
+        std::printf("\n");
+    }
+    for (int L : {96, 98, 200, 1024, 16382, 16384}) {
+        int len[8];
+        net::stage_lengths(L, len);
+        std::printf("stage_lengths");
+        for (int v : len) std::printf(" %d", v);
+        std::printf("\n");
+    }
+    // every (k, stride) of the table, output length as SAME gives it
+    for (int i = 0; i < net::kNumConvs; ++i)
+        for (int lin : {1, 2, 3, 6, 7}) {
+            const int k = net::kConvs[i].k, stride = net::kConvs[i].stride;
+            const int lout = (lin + stride - 1) / stride;
+            std::printf("same_pad_left %d %d %d %d = %d\n", k, stride, lin, lout,
+                        net::same_pad_left(k, stride, lin, lout));
+        }
+}
+
+// 64-bit FNV-1a, as oracle/loader_host_test.cpp has it
+static uint64_t fnv1a(const void* data, size_t n, uint64_t h = 0xcbf29ce484222325ull) {
+    const uint8_t* p = static_cast<const uint8_t*>(data);
+    for (size_t k = 0; k < n; ++k) h = (h ^ p[k]) * 0x100000001b3ull;
+    return h;
+}
+
+// both packed images of a canonical blob (a file of little-endian fp32), a line each
+static bool print_packed(const char* path, int n_classes) {
+    if (n_classes < 2 || n_classes > 256) return false;
+    std::vector<float> blob((size_t)dbh_net::param_count(n_classes));
+    FILE* in = std::fopen(path, "rb");
+    if (!in) return false;
+    const size_t got = std::fread(blob.data(), sizeof(float), blob.size(), in);
+    const bool whole = got == blob.size() && std::fgetc(in) == EOF;     // the blob and nothing else
+    std::fclose(in);
+    if (!whole) return false;
+    const char* slash = std::strrchr(path, '/');
+    const char* name = slash ? slash + 1 : path;
+    if (n_classes <= dbh::kMaxClasses) {
+        std::vector<float> packed;
+        dbh_pack::pack_persistent(blob.data(), n_classes, packed);
+        std::printf("packed persistent %s %d %zu %016" PRIx64 "\n", name, n_classes, packed.size(),
+                    fnv1a(packed.data(), packed.size() * sizeof(float)));
+    }
+    dbh_pack::GeneralOffsets g;
+    const std::vector<float> packed = dbh_pack::pack_general(blob.data(), n_classes, &g);
+    uint64_t offsets = fnv1a(g.w_off, sizeof(g.w_off));
+    offsets = fnv1a(g.b_off, sizeof(g.b_off), offsets);
+    offsets = fnv1a(g.sc_off, sizeof(g.sc_off), offsets);
+    offsets = fnv1a(g.sh_off, sizeof(g.sh_off), offsets);
+    std::printf("packed general %s %d %zu %016" PRIx64 " offsets %016" PRIx64 "\n", name, n_classes,
+                packed.size(), fnv1a(packed.data(), packed.size() * sizeof(float)), offsets);
+    return true;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "--network") == 0) {
+        print_network();
+        for (int a = 2; a + 1 < argc; a += 2)
+            if (!print_packed(argv[a], std::atoi(argv[a + 1]))) return 2;
+        return 0;
+    }
     check_layouts();
     check_staged_copy();
     check_uniform_length();

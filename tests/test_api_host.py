@@ -1,14 +1,16 @@
-"""The host-side arithmetic of libdeepbinner_hip.so's API layer (deepbinner_amd/csrc/
-dbh_host_layout.h: buffer layouts, the order inflate records travel in, the staged copy, scan
-steps), compiled into a program of its own (oracle/api_host_test.cpp, built by oracle/Makefile from
-the very header dbh_api.hip includes) and run on the build box, without a GPU."""
+"""The host-side arithmetic of libdeepbinner_hip.so (deepbinner_amd/csrc/dbh_host_layout.h: buffer
+layouts, the order inflate records travel in, the staged copy, scan steps; dbh_network.h: the
+network table every native path reads; dbh_pack.h: both weight packers), compiled into a program of
+its own (oracle/api_host_test.cpp, built by oracle/Makefile from the very headers the library
+includes) and run on the build box, without a GPU."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+from conftest import GOLD, REPO
+from deepbinner_amd import model_format
 
 HARNESS = os.path.join(REPO, 'oracle', '_build', 'api_host_test')
 # dbh_inflate_stream (include/deepbinner_hip.h) and its modes
@@ -85,3 +87,102 @@ def test_model_steps_is_check_input_size(lines):
         assert steps == want, line
         seen.add((input_size, steps > 0))
     assert seen == {(size, fits) for size in (96, 1024, 2048) for fits in (True, False)}
+
+
+# ---- dbh_network.h against the specification, dbh_pack.h against the parent's images ------------
+SHIPPED = ['EXP-NBD103_read_ends', 'EXP-NBD103_read_starts', 'SQK-RBK004_read_starts']
+RANDOM_CLASSES = [2, 13, 17, 32, 33, 256]     # weight_families.random_model(0, C)
+STAGE_SIZES = [96, 98, 200, 1024, 16382, 16384]
+
+
+@pytest.fixture(scope='module')
+def network(tmp_path_factory):
+    """The lines of ``api_host_test --network`` over the shipped models' blobs and the random
+    family's, by their first word."""
+    from weight_families import random_model
+    tmp = tmp_path_factory.mktemp('api_host_network')
+    blobs = []
+    for name in SHIPPED:
+        w, _ = model_format.ModelWeights.load(os.path.join(REPO, 'deepbinner_amd', 'models', name + '.dbw'))
+        blobs.append((name, w))
+    blobs += [('random-s0-C{}'.format(c), random_model(0, c)) for c in RANDOM_CLASSES]
+    args = []
+    for name, w in blobs:
+        w.flat().tofile(str(tmp / name))
+        args += [str(tmp / name), str(w.n_classes)]
+    run = subprocess.run([HARNESS, '--network'] + args, capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    out = {}
+    for line in run.stdout.splitlines():
+        out.setdefault(line.split()[0], []).append(line.split()[1:])
+    return out
+
+
+def test_network_table_is_model_format(network):
+    """The 20 rows, the seven BN channel counts and epsilon, the parameter count and the blob's
+    offsets restate model_format.py."""
+    rows = [[int(x) for x in r[:5]] for r in network['conv']]
+    assert rows == [[i + 1, k, cin, cout or 0, stride]
+                    for i, (_, k, cin, cout, stride, _) in enumerate(model_format.CONV_LAYERS)]
+    assert [[int(x) for x in r] for r in network['bn']] == [
+        [j + 1, c] for j, c in enumerate(model_format.BN_CHANNELS)]
+    assert [float(r[0]) for r in network['bn_eps']] == [model_format.BN_EPSILON]
+    assert [[int(x) for x in r] for r in network['param_count']] == [
+        [c, model_format.param_count(c)] for c in (2, 13, 32, 33, 256)]
+    for r, c in zip(network['blob'], (2, 256)):
+        want, at = [c], 0
+        for _, k, cin, cout, _, _ in model_format.conv_shapes(c):
+            want += [at, at + k * cin * cout]
+            at += k * cin * cout + cout
+        for channels in model_format.BN_CHANNELS:
+            want.append(at)
+            at += 4 * channels
+        assert at == model_format.param_count(c)
+        assert [int(x) for x in r] == want
+
+
+def test_stage_lengths_and_stage_indices_are_the_oracles(network):
+    """stage_lengths(L) is the oracle's own stage shapes at the minimum, at sizes odd at the first
+    and the third stage, the shipped size and the two largest; every convolution takes len[in] to
+    len[out] by the padding rule of its row in model_format.py."""
+    from test_log_space_compare import stage_lengths
+    from train_reference import _pads
+    got = {int(r[0]): [int(x) for x in r] for r in network['stage_lengths']}
+    assert sorted(got) == STAGE_SIZES
+    assert got[96][1:] == [48, 24, 12, 6, 3, 2, 1]
+    assert got[98][1:3] == [49, 24]
+    assert got[200][1:] == [100, 50, 25, 12, 6, 3, 1]
+    for size in STAGE_SIZES:
+        assert got[size][1:] == stage_lengths(size), size
+        for r, (_, k, _, _, stride, padding) in zip(network['conv'], model_format.CONV_LAYERS):
+            assert r[5] == 'in' and r[7] == 'out'
+            assert _pads(got[size][int(r[6])], k, stride, padding)[0] == got[size][int(r[8])], (size, r)
+
+
+def test_same_pad_left_is_the_training_references(network):
+    from train_reference import _pads
+    seen = set()
+    for k, stride, lin, lout, _, pad in ([int(x) if x != '=' else x for x in r]
+                                         for r in network['same_pad_left']):
+        assert (lout, pad) == _pads(lin, k, stride, 'same')[:2], (k, stride, lin)
+        seen.add((k, stride, lin))
+    assert seen == {(k, stride, lin) for _, k, _, _, stride, _ in model_format.CONV_LAYERS
+                    for lin in (1, 2, 3, 6, 7)}
+
+
+def test_packed_images_are_the_parents_bit_for_bit(network):
+    """Size and 64-bit FNV-1a digest of the persistent image (C <= 32) and of the general image of
+    the three shipped models and of random_model(0, C), against tests/golden/packed_digests.txt:
+    the lines the two packers printed when they had been moved out of dbh_api.hip and
+    dbh_general.hip word for word, before they were rewritten onto dbh_network.h.  (The parent's
+    pack_weights, cut out of its dbh_api.hip into a g++ program of its own, prints the same three
+    persistent digests for the shipped models: 40e3dec5ca30d7b1, f7e5d613ff8f7391,
+    cc10426847f67325 - profiles/network_table/packed_digests_parent.txt.)"""
+    with open(os.path.join(GOLD, 'packed_digests.txt')) as f:
+        golden = [line.split()[1:] for line in f.read().splitlines()]
+    assert network['packed'] == golden
+    kinds = {(r[0], r[1]) for r in golden}
+    assert {('persistent', n) for n in SHIPPED} | {('general', n) for n in SHIPPED} <= kinds
+    assert {('persistent', 'random-s0-C{}'.format(c)) for c in (2, 17, 32)} <= kinds
+    assert {('general', 'random-s0-C{}'.format(c)) for c in (2, 13, 33, 256)} <= kinds
+    assert all(r[3] == '153248' for r in golden if r[0] == 'persistent')
