@@ -1,7 +1,8 @@
 // dbh_api.hip — host side of libdeepbinner_hip.so: the C ABI declared in
 // include/deepbinner_hip.h.  Uploads the weights dbh_pack.h packs into the kernel's fragment order,
-// owns the device buffers, launches the kernels of dbh_forward.hip and holds the small seam kernels
-// (stand-alone normalise, merge, combine_calls).
+// owns the device buffers and prepares the launches.  Host code only: the forward kernel and the
+// small seam kernels (stand-alone normalise, merge, combine_calls) are built, and launched, in
+// dbh_kernels.hip; this file calls its launch functions (dbh_kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,106 +21,11 @@
 #include "../../include/deepbinner_hip.h"
 #include "dbh_general.h"
 #include "dbh_host_layout.h"
+#include "dbh_kernels.h"
+#include "dbh_layout.h"
 #include "dbh_owned.h"
 #include "dbh_pack.h"
 #include "dbh_train.h"
-#define DBH_FORWARD_NS dbh
-#define DBH_TIMELINE 0
-#include "dbh_forward.hip"
-#undef DBH_FORWARD_NS
-#undef DBH_TIMELINE
-#define DBH_FORWARD_NS dbh_timeline      // the same kernels with the cycle stamps compiled in
-#define DBH_TIMELINE 1
-#include "dbh_forward.hip"
-#undef DBH_FORWARD_NS
-#undef DBH_TIMELINE
-
-// =============================================================================================
-// Seam b2 as kernels of their own (the forward kernel does both itself when it is handed samples):
-// on the arithmetic of dbh_seam.h, like it.
-// =============================================================================================
-namespace dbh {
-
-// One block per (read, step): slice the window (classify.py:337-349), z-normalise it in fp64
-// (trim_signal.py:61-69; the sums are exact integers), zero-pad right ('start') or left ('end')
-// (classify.py:352-357) and emit fp32, which is what Keras casts the float64 input to.
-__global__ __launch_bounds__(256) void dbh_normalise_kernel(
-    const int16_t* __restrict__ samples, const long long* __restrict__ offsets, int steps,
-    int side, float* __restrict__ windows) {
-    __shared__ long long red[2][4];
-    const long long read = blockIdx.x / steps;
-    const int step = blockIdx.x - (int)(read * steps);
-    const long long base = offsets[read];
-    const long long len = offsets[read + 1] - base;
-    long long a, b;
-    window_bounds(len, step, side, kWindow, &a, &b);
-    const int cnt = (int)(b - a);
-    const int tid = threadIdx.x;
-    const int16_t* src = samples + base + a;
-
-    int v[4];
-    long long s1 = 0, s2 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = tid + i * 256;
-        v[i] = (k < cnt) ? (int)src[k] : 0;
-        s1 += v[i];
-        s2 += (long long)v[i] * v[i];
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        s1 += __shfl_xor(s1, off);
-        s2 += __shfl_xor(s2, off);
-    }
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = s1;
-        red[1][tid >> 6] = s2;
-    }
-    __syncthreads();
-    s1 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    s2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-
-    float* out = windows + (long long)blockIdx.x * kWindow;
-    double mean, inv;
-    mean_std(s1, s2, cnt, &mean, &inv);
-    const int pad_left = (side == 0) ? 0 : kWindow - cnt;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = tid + i * 256;          // position in the source slice
-        if (k < cnt) out[pad_left + k] = (float)(((double)v[i] - mean) * inv);
-    }
-    // zero padding: [cnt, 1024) for 'start', [0, 1024-cnt) for 'end'
-    const int pad_begin = (side == 0) ? cnt : 0;
-    const int pad_count = kWindow - cnt;
-    for (int k = tid; k < pad_count; k += 256) out[pad_begin + k] = 0.f;
-}
-
-// 32 lanes per read: merge the per-step softmax vectors (classify.py:368-374: min for class 0,
-// max for the barcodes), rescale the barcodes so the vector sums to one (classify.py:387-393,
-// in fp64 like NumPy-1.x scalar promotion did) and make the call (classify.py:285-295).
-__global__ __launch_bounds__(256) void dbh_merge_kernel(const float* __restrict__ wprobs,
-                                                        long long n_reads, int steps,
-                                                        int n_classes, double score_diff,
-                                                        float* __restrict__ probs,
-                                                        int* __restrict__ calls) {
-    const long long read = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
-    const int c = threadIdx.x & 31;
-    if (read >= n_reads) return;   // whole 32-lane groups exit together
-    const bool valid = c < n_classes;
-    float merged = 0.f;
-    if (valid) {
-        const float* src = wprobs + read * steps * n_classes + c;
-        merged = src[0];
-        for (int s = 1; s < steps; ++s) {
-            const float v = src[(long long)s * n_classes];
-            merged = (c == 0) ? fminf(merged, v) : fmaxf(merged, v);
-        }
-    }
-    renormalise_and_call(merged, c, n_classes, score_diff, probs + read * n_classes,
-                         calls + read);
-}
-
-}  // namespace dbh
 
 namespace {
 
@@ -309,8 +215,7 @@ int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev
         a.phases = m->phase_probe ? 1 : 0;
         a.chunk4_min_left = m->chunk4_rounds * (int)grid;
         a.chunk2_min_left = m->chunk2_rounds * (int)grid;
-        hipLaunchKernelGGL(dbh::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, stream, a);
-        DBH_HIP(hipGetLastError());
+        DBH_HIP(dbh_kernels::launch_forward(a, grid, stream));
         if (timed) DBH_HIP(m->timing.end(stream));
     }
     return DBH_OK;
@@ -623,11 +528,9 @@ int dbh_normalise_windows_dev(const int16_t* samples_dev, const int64_t* offsets
     const int64_t kChunkReads = (1 << 24) / steps;
     for (int64_t r0 = 0; r0 < n_reads; r0 += kChunkReads) {
         const int64_t cnt = (n_reads - r0 < kChunkReads) ? (n_reads - r0) : kChunkReads;
-        hipLaunchKernelGGL(dbh::dbh_normalise_kernel, dim3((unsigned)(cnt * steps)), dim3(256), 0,
-                           (hipStream_t)stream, samples_dev,
-                           (const long long*)(offsets_dev + r0), steps, side,
-                           windows_dev + r0 * steps * dbh::kWindow);
-        DBH_HIP(hipGetLastError());
+        DBH_HIP(dbh_kernels::launch_normalise(samples_dev, (const long long*)(offsets_dev + r0), steps,
+                                              side, windows_dev + r0 * steps * dbh::kWindow,
+                                              (unsigned)(cnt * steps), (hipStream_t)stream));
     }
     return DBH_OK;
 }
@@ -639,31 +542,10 @@ int dbh_merge_calls_dev(const float* window_probs_dev, int64_t n_reads, int step
         return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
     if (!window_probs_dev || !probs_dev || !calls_dev) return DBH_ERR_INVALID_ARGUMENT;
-    const int64_t blocks = (n_reads + 7) / 8;
-    hipLaunchKernelGGL(dbh::dbh_merge_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                       (hipStream_t)stream, window_probs_dev, (long long)n_reads, steps,
-                       n_classes, score_diff, probs_dev, (int*)calls_dev);
-    DBH_HIP(hipGetLastError());
+    DBH_HIP(dbh_kernels::launch_merge(window_probs_dev, (long long)n_reads, steps, n_classes,
+                                      score_diff, probs_dev, (int*)calls_dev, (hipStream_t)stream));
     return DBH_OK;
 }
-
-namespace {
-// classify.py:298-322 on call numbers (0 = 'none'); one read per thread, 12 bytes of traffic each
-__global__ void combine_calls_kernel(const int32_t* __restrict__ start_calls,
-                                     const int32_t* __restrict__ end_calls, long long n, int mode,
-                                     int32_t* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t s = start_calls[i], e = end_calls[i];
-    int32_t call;
-    if (s == e) call = s;
-    else if (mode == DBH_REQUIRE_BOTH) call = DBH_CALL_NONE;
-    else if (e == DBH_CALL_NONE) call = s;
-    else if (mode == DBH_REQUIRE_START) call = DBH_CALL_NONE;
-    else call = (s == DBH_CALL_NONE) ? e : DBH_CALL_NONE;
-    out[i] = call;
-}
-}  // namespace
 
 int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_calls_dev,
                           int64_t n_reads, int mode, int32_t* out_dev, dbh_stream stream) {
@@ -671,10 +553,8 @@ int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_cal
         return DBH_ERR_INVALID_ARGUMENT;
     if (n_reads == 0) return DBH_OK;
     if (!start_calls_dev || !end_calls_dev || !out_dev) return DBH_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(combine_calls_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, start_calls_dev, end_calls_dev, (long long)n_reads,
-                       mode, out_dev);
-    DBH_HIP(hipGetLastError());
+    DBH_HIP(dbh_kernels::launch_combine(start_calls_dev, end_calls_dev, (long long)n_reads, mode,
+                                        out_dev, (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -1312,7 +1192,7 @@ int dbh_debug_forward(dbh_model* m, const float* x_host, int64_t n, int stage, f
 
 int dbh_forward_kernel_info(int* threads_per_block, int* lds_bytes, int* vgprs) {
     hipFuncAttributes attr;
-    DBH_HIP(hipFuncGetAttributes(&attr, (const void*)dbh::dbh_forward_kernel));
+    DBH_HIP(dbh_kernels::forward_attributes(&attr));
     if (threads_per_block) *threads_per_block = dbh::kThreads;
     if (lds_bytes) *lds_bytes = (int)attr.sharedSizeBytes;
     if (vgprs) *vgprs = attr.numRegs;

@@ -44,7 +44,7 @@
 //     conv10 is applied to conv10's OUTPUT (a 1x1 convolution commutes with it);
 //   - conv7 (w43ns_step, w43_nsplit_half: L = 256, a tile per wave PAIR, split by output
 //     channels), between the two chains;
-//   - the kernel's arguments, the window statistics and sample fetch of seam b2;
+//   - the window statistics and sample fetch of seam b2 (the kernel's arguments: dbh_kernels.h);
 //   - dbh_forward_kernel: the persistent loop - stages A-C window by window, stages D-E for the
 //     group, stage F (conv17: every wave an EIGHTH of the contraction for all four windows, weights
 //     from L2 straight to registers; the next group's samples and statistics underneath), and for
@@ -53,10 +53,11 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include "dbh_kernels.h"      // ForwardArgs, kWaves, kThreads: what the launching host code shares
 #include "dbh_layout.h"
 #include "dbh_seam.h"
 
-// This file is compiled twice by dbh_api.hip: as namespace dbh with DBH_TIMELINE 0 (the product)
+// This file is compiled twice by dbh_kernels.hip (the unit that builds and launches the kernels): as namespace dbh with DBH_TIMELINE 0 (the product)
 // and as namespace dbh_timeline with DBH_TIMELINE 1 (cycle stamps for tools/timeline.py).  The
 // stamps are global stores, and on gfx9 a store shares the vmcnt counter with the loads: one
 // conditional store anywhere makes hipcc wait for vmcnt(0) at every later use of a prefetched
@@ -76,9 +77,6 @@ using namespace dbh;
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
-
-constexpr int kWaves = 8;
-constexpr int kThreads = kWaves * 64;
 
 // Tuning values, each the winner of an A/B on the device (HISTORY.md has the other values' cost).
 // How many of the eight waves issue stage B's LDS-DMA requests (the low ones: they run ahead of
@@ -2342,32 +2340,7 @@ __device__ __forceinline__ T* glob(T* p) {
     return (T*)(__attribute__((address_space(1))) T*)p;
 }
 
-// Arguments of the forward kernel (one by-value struct = the kernel-argument segment).
-struct ForwardArgs {
-    const float* packed;         // packed parameters (dbh_layout.h)
-    const float* x;              // seam b1: [n_windows][1024] normalised windows, or null
-    float* probs;                // [n_windows][n_classes]
-    float* debug_out;
-    const int16_t* samples;      // seam b2: int16 signals, or null
-    const long long* offsets;    //          read r = samples[offsets[r] .. offsets[r+1])
-    int* calls;                  //          barcode calls (one scan step per read), or null
-    float* tail_scratch;         // [grid][kTailBatch][16][48]: conv17 outputs parked per workgroup
-    int* win_counter;            // null: workgroup b walks groups b, b + grid, ...; else every
-                                 // workgroup takes its next group of windows off this counter;
-                                 // [1] counts the workgroups that have finished (both 0 between
-                                 // launches: the last workgroup of a launch resets them)
-    long long* clock_out;        // [grid][4 + kPhaseMarks * kPhaseGroups] or null: shader clock and 100
-                                 // MHz clock at a workgroup's start and end (dbh_forward_clock_read),
-                                 // then the phase stamps of its first groups (dbh_forward_phases_read)
-    double score_diff;
-    long long read0, len_hint, hint_cap;     // dbh_model_set_read_length_hint
-    long long n_windows;
-    int n_classes, debug_stage, steps, side;
-    // windows not yet handed out below which a workgroup asks for groups of 2 / of 1 instead of
-    // kGroup (the end of a launch: dbh_forward_kernel)
-    int chunk4_min_left, chunk2_min_left;
-    int phases;                  // clock probe on: also keep the phase stamps (dbh_forward_phases_enable)
-};
+// (the kernel's arguments: struct ForwardArgs of this namespace, dbh_kernels.h)
 
 // Window statistics, step 1: exact integer sums of this lane's two samples, sum(x) and sum(x^2)
 // split in 16-bit halves so that every wave-wide partial stays below 2^31, reduced over the wave

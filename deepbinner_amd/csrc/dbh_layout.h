@@ -2,7 +2,7 @@
 // which convolutions run on the MFMA path and how (direct, Winograd F(2,3) or F(4,3)), where their
 // pre-swizzled "fragment order" weights live in the packed HBM buffer, and how the LDS arena is
 // carved per stage.  The network itself - shapes, strides, stage lengths - is dbh_network.h's.
-// Read by the device code (dbh_forward.hip), by the host code that launches it (dbh_api.hip) and by
+// Read by the device code (dbh_forward.hip), by the host code that prepares its launches (dbh_api.hip) and by
 // the packer that writes the buffer (dbh_pack.h: pack_persistent).
 #pragma once
 

@@ -1,8 +1,9 @@
 // dbh_probes.h — the instruments of the forward kernel: event brackets around production launches
 // (dbh_forward_timing_*), the cycle-stamp build of the kernel (dbh_forward_timeline*), the clock
-// and phase marks a production launch leaves (dbh_forward_clock_*, dbh_forward_phases_*).  Included
-// at the end of dbh_api.hip, whose translation unit compiles the dbh_timeline kernels; of all this
-// the launch path only calls TimingBrackets::begin / end.
+// and phase marks a production launch leaves (dbh_forward_clock_*, dbh_forward_phases_*).  Host code,
+// included at the end of dbh_api.hip for its model object and error macros; the cycle-stamp kernel
+// itself is built and launched in dbh_kernels.hip.  Of all this the launch path only calls
+// TimingBrackets::begin / end.
 #pragma once
 
 namespace {
@@ -49,7 +50,7 @@ void TimingBrackets::reset() {
 // One launch of the cycle-stamp kernel on the null stream: `a` comes with its input and debug
 // stage chosen by the caller; probabilities (and calls, if wanted, behind them) go to the model's
 // `out`, the stamps through `work` to stamps_host.
-int run_timeline(dbh_model* m, dbh_timeline::ForwardArgs a, int64_t n, unsigned grid,
+int run_timeline(dbh_model* m, dbh::ForwardArgs a, int64_t n, unsigned grid,
                  bool with_calls, int64_t* stamps_host) {
     const size_t stamp_bytes = (size_t)n * dbh::kWaves * 64 * sizeof(int64_t);
     TailScratch& tail = m->tails[nullptr];
@@ -66,8 +67,7 @@ int run_timeline(dbh_model* m, dbh_timeline::ForwardArgs a, int64_t n, unsigned 
     a.steps = 1;
     a.tail_scratch = tail.scratch();
     a.win_counter = nullptr;           // (fixed shares: the stamps are indexed by window)
-    hipLaunchKernelGGL(dbh_timeline::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, 0, a);
-    DBH_HIP(hipGetLastError());
+    DBH_HIP(dbh_kernels::launch_forward_timeline(a, grid, 0));
     DBH_HIP(hipMemcpyAsync(stamps_host, m->work.get(), stamp_bytes, hipMemcpyDeviceToHost, 0));
     DBH_HIP(hipStreamSynchronize(0));
     return DBH_OK;
@@ -95,7 +95,7 @@ int dbh_forward_timeline(dbh_model* m, const float* x_host, int64_t n, int64_t* 
     DBH_HIP(m->in.reserve((size_t)n * dbh::kWindow * sizeof(float)));
     DBH_HIP(hipMemcpyAsync(m->in.get(), x_host, (size_t)n * dbh::kWindow * sizeof(float),
                            hipMemcpyHostToDevice, 0));
-    dbh_timeline::ForwardArgs a = {};
+    dbh::ForwardArgs a = {};
     a.x = m->in.as<float>();
     a.debug_stage = 300;
     return run_timeline(m, a, n, (unsigned)((n + dbh::kGroup - 1) / dbh::kGroup), false, stamps_host);
@@ -114,7 +114,7 @@ int dbh_forward_timeline_i16(dbh_model* m, const int16_t* samples_host, int64_t 
     DBH_HIP(hipMemcpyAsync(m->in.get(), samples_host, sample_bytes, hipMemcpyHostToDevice, 0));
     DBH_HIP(hipMemcpyAsync(d_offsets, offsets.data(), offset_bytes, hipMemcpyHostToDevice, 0));
     DBH_HIP(hipStreamSynchronize(0));
-    dbh_timeline::ForwardArgs a = {};
+    dbh::ForwardArgs a = {};
     a.samples = m->in.as<int16_t>();
     a.offsets = (const long long*)d_offsets;
     a.score_diff = 0.5;

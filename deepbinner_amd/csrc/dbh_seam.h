@@ -2,7 +2,7 @@
 // that needs it: in front, which samples of a read make a window (classify.py:337-349) and the
 // constants of its z-normalisation (trim_signal.py:61-69); behind, make_sum_to_one and the barcode
 // call of one read (classify.py:387-393, 285-295).  Used by the persistent forward kernel
-// (dbh_forward.hip), the stand-alone normalise and merge kernels (dbh_api.hip) and the general
+// (dbh_forward.hip), the stand-alone normalise and merge kernels (dbh_kernels.hip) and the general
 // path's front kernel (dbh_general.hip).  Device functions only: a kernel defined here would land in
 // every translation unit that includes this file.
 #ifndef DBH_SEAM_H

@@ -75,6 +75,16 @@ def test_hand_kept_hazards(shipped):
         'python tools/code_object.py --bless, and read the diff')
 
 
+def test_kernels_of_every_source_are_seen(shipped):
+    """kernels() - what --same compares - walks every code object of the library, not the one of the
+    source that happens to come first: the persistent path's, the inflate decoder's, the general
+    path's and training's."""
+    names = list(code_object.kernels(LIB))
+    for part in ('3dbh18dbh_forward_kernel', 'inflate_pair_kernel', '7dbh_gen12_GLOBAL__N_111conv_kernel',
+                 '9dbh_train12_GLOBAL__N_19conv_gemm'):
+        assert any(part in n for n in names), (part, names)
+
+
 def test_guard_notices_a_removed_wait_and_a_spill():
     """The checks above on doctored instruction streams: they must fire."""
     base = ['v_mfma_f32_16x16x4_f32 v[20:23], v117, v125, v[20:23]', 'v_add_u32_e32 v7, 0x1a920, v3', 's_nop 7',

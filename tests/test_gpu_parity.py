@@ -79,6 +79,19 @@ def test_predict_more_windows_than_workgroups(hip_models):
     assert np.array_equal(got, want)
 
 
+def test_timeline_kernel_stamps_every_window(hip_models):
+    """The cycle-stamp build of the forward kernel (dbh_timeline::dbh_forward_kernel, launched from
+    dbh_kernels.hip), on fp32 windows and on int16 reads: 5 windows are one group of four and one of
+    one, two workgroups.  Every wave takes stamp 0 (shader clock) and stamp 62 (100 MHz clock) at the
+    top of every window."""
+    model = hip_models['EXP-NBD103_read_starts']
+    x = np.load(os.path.join(GOLD, 'windows_start.npy')).reshape(-1, 1024)[:5]
+    reads = (np.random.default_rng(11).standard_normal((5, 1024)) * 80 + 500).astype(np.int16)
+    for stamps in (model.timeline(x), model.timeline_i16(reads)):
+        assert stamps.shape == (5, 8, 64) and stamps.dtype == np.int64
+        assert (stamps[:, :, 0] != 0).all() and (stamps[:, :, 62] != 0).all()
+
+
 def test_predict_edge_inputs(hip_models, weights):
     model = hip_models['EXP-NBD103_read_starts']
     assert model.predict(np.zeros((0, 1024, 1))).shape == (0, 13)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""The gfx950 code object inside libdeepbinner_hip.so: kernel metadata (registers, spills, scratch,
-LDS) and a census of the forward kernel's instruction stream.  Used by tests/test_code_object.py
+"""The gfx950 code objects inside libdeepbinner_hip.so, one per source file with kernels: kernel
+metadata (registers, spills, scratch, LDS) of every kernel of the library and a census of the forward
+kernel's instruction stream.  Used by tests/test_code_object.py
 (the CPU-box guard on what ships) and by hand:  python tools/code_object.py [lib.so]
                                                 python tools/code_object.py --same OLD.so NEW.so"""
 import collections
@@ -16,15 +17,37 @@ LLVM = '/opt/rocm/lib/llvm/bin'
 BUNDLE = 'hipv4-amdgcn-amd-amdhsa--gfx950'
 
 
+MAGIC = b'__CLANG_OFFLOAD_BUNDLE__'
+
+
 def extract(lib, workdir):
-    """-> path of the gfx950 ELF code object pulled out of lib's .hip_fatbin section"""
+    """-> paths of the gfx950 ELF code objects pulled out of lib's .hip_fatbin section, in link order:
+    the section is one offload bundle per translation unit with device code, each opened by MAGIC"""
     fat = os.path.join(workdir, 'fatbin')
-    co = os.path.join(workdir, 'gfx950.co')
     subprocess.run([f'{LLVM}/llvm-objcopy', f'--dump-section=.hip_fatbin={fat}', lib, os.path.join(workdir, 'copy.so')],
                    check=True)
-    subprocess.run([f'{LLVM}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={fat}',
-                    f'--targets={BUNDLE}', f'--output={co}'], check=True)
-    return co
+    section = open(fat, 'rb').read()
+    starts = [m.start() for m in re.finditer(re.escape(MAGIC), section)]
+    out = []
+    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(section)])):
+        bundle, co = os.path.join(workdir, f'bundle{i}'), os.path.join(workdir, f'gfx950_{i}.co')
+        with open(bundle, 'wb') as f:
+            f.write(section[a:b])
+        subprocess.run([f'{LLVM}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={bundle}',
+                        f'--targets={BUNDLE}', f'--output={co}'], check=True)
+        if os.path.getsize(co):
+            out.append(co)
+    return out
+
+
+def all_kernel_metadata(lib, workdir):
+    """-> {kernel symbol: (code object path, {field: value})} over every code object of lib"""
+    found = {}
+    for co in extract(lib, workdir):
+        for name, m in kernel_metadata(co).items():
+            assert name not in found, f'{name} is in two code objects'
+            found[name] = (co, m)
+    return found
 
 
 def kernel_metadata(co):
@@ -169,6 +192,7 @@ def lgkm_wait_histogram(insts):
     return {str(k): h[k] for k in sorted(h)}
 
 
+FORWARD = '_ZN3dbh18dbh_forward_kernel'      # dbh::dbh_forward_kernel, whichever code object holds it
 META = ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count',
         'private_segment_fixed_size', 'group_segment_fixed_size')
 
@@ -176,13 +200,13 @@ META = ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spil
 def summary(lib):
     """everything tests/test_code_object.py looks at, as one dict"""
     with tempfile.TemporaryDirectory() as d:
-        co = extract(lib, d)
-        md = kernel_metadata(co)
-        fwd = next(n for n in md if n.startswith('_ZN3dbh18dbh_forward_kernel'))
+        md = all_kernel_metadata(lib, d)
+        fwd = next(n for n in md if n.startswith(FORWARD))
+        co, meta = md[fwd]
         insts = disassemble(co, fwd)
         c = census(insts)
         return {
-            'metadata': {k: md[fwd].get(k) for k in META},
+            'metadata': {k: meta.get(k) for k in META},
             'census': c,
             'lgkm_waits': lgkm_wait_histogram(insts),
             'mfma_read_hazards': [list(b) for b in mfma_read_hazards(insts)][:20],
@@ -190,11 +214,11 @@ def summary(lib):
 
 
 def kernels(lib):
-    """-> {kernel symbol: (instruction count, hash of the instruction stream, metadata fields)}"""
+    """-> {kernel symbol: (instruction count, hash of the instruction stream, metadata fields)},
+    every kernel of the library"""
     out = {}
     with tempfile.TemporaryDirectory() as d:
-        co = extract(lib, d)
-        for name, m in kernel_metadata(co).items():
+        for name, (co, m) in all_kernel_metadata(lib, d).items():
             insts = disassemble(co, name)
             digest = hashlib.sha256('\n'.join(insts).encode()).hexdigest()[:16]
             out[name] = (len(insts), digest, {k: m.get(k) for k in META + ('kernarg_segment_size',)})
@@ -223,8 +247,6 @@ def same(old_lib, new_lib):
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == '--same':
         # python tools/code_object.py --same OLD.so NEW.so: exit status 1 if a kernel of both differs
-        # (only the first translation unit's code object is looked at: build another file of the
-        # library alone, with the Makefile's flags, to compare its kernels)
         lines, differ = same(sys.argv[2], sys.argv[3])
         print('\n'.join(lines))
         print(f'{differ} kernel(s) differ')
@@ -244,16 +266,15 @@ def main():
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(__file__), '..', 'deepbinner_amd',
                                                              'libdeepbinner_hip.so')
     with tempfile.TemporaryDirectory() as d:
-        co = extract(lib, d)
-        md = kernel_metadata(co)
+        md = all_kernel_metadata(lib, d)
         out = {}
-        for name, m in md.items():
+        for name, (_, m) in md.items():
             keep = {k: m.get(k) for k in ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count',
                                           'sgpr_spill_count', 'private_segment_fixed_size',
                                           'group_segment_fixed_size', 'max_flat_workgroup_size')}
             out[name] = keep
-        fwd = next(n for n in md if n.startswith('_ZN3dbh18dbh_forward_kernel'))
-        out['forward_census'] = census(disassemble(co, fwd))
+        fwd = next(n for n in md if n.startswith(FORWARD))
+        out['forward_census'] = census(disassemble(md[fwd][0], fwd))
         print(json.dumps(out, indent=1))
 
 
