@@ -57,8 +57,9 @@
 #include "dbh_layout.h"
 #include "dbh_seam.h"
 
-// This file is compiled twice by dbh_kernels.hip (the unit that builds and launches the kernels): as namespace dbh with DBH_TIMELINE 0 (the product)
-// and as namespace dbh_timeline with DBH_TIMELINE 1 (cycle stamps for tools/timeline.py).  The
+// This file is compiled twice, by the two units that build and launch its kernel: by dbh_kernels.hip
+// as namespace dbh with DBH_TIMELINE 0 (the product) and by dbh_timeline.hip as namespace
+// dbh_timeline with DBH_TIMELINE 1 (cycle stamps for tools/timeline.py).  The
 // stamps are global stores, and on gfx9 a store shares the vmcnt counter with the loads: one
 // conditional store anywhere makes hipcc wait for vmcnt(0) at every later use of a prefetched
 // register, so they must not even be compiled into the production kernel.

@@ -1,6 +1,7 @@
 // dbh_kernels.h — what the host code of libdeepbinner_hip.so (dbh_api.hip, dbh_probes.h) sees of
-// the device unit dbh_kernels.hip: the forward kernel's arguments and launch shape, and one launch
-// function per kernel.  No kernel symbol leaves dbh_kernels.hip.
+// the device units dbh_kernels.hip and dbh_timeline.hip (the forward kernel's cycle-stamp build): the
+// forward kernel's arguments and launch shape, and one launch function per kernel.  No kernel
+// symbol leaves its unit.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,21 +1,14 @@
-// dbh_kernels.hip — the device unit of the persistent path: both builds of the forward kernel and
-// the three small seam kernels, with one host function each that launches it (dbh_kernels.h).  The
-// host code that prepares the launches is dbh_api.hip and dbh_probes.h.
+// dbh_kernels.hip — the device unit of the persistent path: the shipping build of the forward kernel
+// and the three small seam kernels, with one host function each that launches it (dbh_kernels.h).
+// The cycle-stamp build of the forward kernel is a unit of its own, dbh_timeline.hip.  The host code
+// that prepares the launches is dbh_api.hip and dbh_probes.h.
 //
-// THE LIST OF KERNELS IN THIS FILE, AND ITS ORDER, DETERMINES THE SHIPPED INSTRUCTION STREAM.  The
-// functions of dbh_seam.h and dbh_layout.h that these kernels share are not forced inline, and the
-// inliner decides by how many callers a function has in the module - so dbh::dbh_forward_kernel,
-// whose correctness rests on hand-counted waits, comes out differently with other neighbours
-// (instruction count, digest of the stream: tools/code_object.py kernels()):
-//
-//   what is in the unit                          dbh::dbh_forward_kernel   dbh_timeline::dbh_forward_kernel
-//   this file                                    15,423  d617ece62df5dbab  16,088  9153fbbfc8352aa6
-//   dbh_forward.hip alone (DBH_TIMELINE 0)       15,631  34522a5c94022190  -
-//   both builds, nothing else                    as this file              16,312  f651ea5edb0f2d7e
-//                                                                          (104 spilled SGPRs, 12 B scratch)
-//
-// Adding, removing or reordering a kernel here is a change of the forward kernel: compare the
-// libraries with  python tools/code_object.py --same OLD.so NEW.so  (DESIGN.md section 4).
+// A kernel's instruction stream does not depend on which kernels share its unit, or on their
+// order: every __device__ function these kernels call is __forceinline__, and cut at its ELF symbol's
+// size dbh::dbh_forward_kernel is the same 15,360 instructions here, built alone, beside the
+// timeline build or beside any other kernel (dbh_timeline::dbh_forward_kernel: 16,056 wherever it
+// is built; DESIGN.md section 4, profiles/kernel_digest/).  After any rearrangement of the device
+// code, check with  python tools/code_object.py --same OLD.so NEW.so
 #include <hip/hip_runtime.h>
 
 #include "../../include/deepbinner_hip.h"
@@ -23,13 +16,6 @@
 #define DBH_FORWARD_NS dbh
 #define DBH_TIMELINE 0
 #include "dbh_forward.hip"
-#undef DBH_FORWARD_NS
-#undef DBH_TIMELINE
-#define DBH_FORWARD_NS dbh_timeline      // the same kernels with the cycle stamps compiled in
-#define DBH_TIMELINE 1
-#include "dbh_forward.hip"
-#undef DBH_FORWARD_NS
-#undef DBH_TIMELINE
 
 // =============================================================================================
 // Seam b2 as kernels of their own (the forward kernel does both itself when it is handed samples):
@@ -145,12 +131,6 @@ namespace dbh_kernels {
 
 hipError_t launch_forward(const dbh::ForwardArgs& a, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(dbh::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, stream, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_forward_timeline(const dbh::ForwardArgs& a, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(dbh_timeline::dbh_forward_kernel, dim3(grid), dim3(dbh::kThreads), 0, stream,
-                       dbh_timeline::ForwardArgs{a});
     return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // (dbh_forward_timing_*), the cycle-stamp build of the kernel (dbh_forward_timeline*), the clock
 // and phase marks a production launch leaves (dbh_forward_clock_*, dbh_forward_phases_*).  Host code,
 // included at the end of dbh_api.hip for its model object and error macros; the cycle-stamp kernel
-// itself is built and launched in dbh_kernels.hip.  Of all this the launch path only calls
+// itself is built and launched in dbh_timeline.hip.  Of all this the launch path only calls
 // TimingBrackets::begin / end.
 #pragma once
 

@@ -80,9 +80,51 @@ def test_kernels_of_every_source_are_seen(shipped):
     source that happens to come first: the persistent path's, the inflate decoder's, the general
     path's and training's."""
     names = list(code_object.kernels(LIB))
-    for part in ('3dbh18dbh_forward_kernel', 'inflate_pair_kernel', '7dbh_gen12_GLOBAL__N_111conv_kernel',
-                 '9dbh_train12_GLOBAL__N_19conv_gemm'):
+    for part in ('3dbh18dbh_forward_kernel', '12dbh_timeline18dbh_forward_kernel', 'inflate_pair_kernel',
+                 '7dbh_gen12_GLOBAL__N_111conv_kernel', '9dbh_train12_GLOBAL__N_19conv_gemm'):
         assert any(part in n for n in names), (part, names)
+
+
+FIRST = '__global__ void first_kernel(float* out, float v) {\n    out[threadIdx.x] = v;\n}\n'
+SECOND = ('__global__ void second_kernel(float* out) {\n    __shared__ float tile[256];\n'
+          '    tile[threadIdx.x] = out[threadIdx.x];\n    __syncthreads();\n    out[threadIdx.x] = tile[255 - threadIdx.x];\n}\n')
+
+
+def test_digest_ignores_neighbours(tmp_path):
+    """A kernel's count and digest are those of the instructions inside its ELF symbol: the same
+    whether it is alone in its code object - and so the last before the section's padding - or
+    followed by another kernel.  (Read on to the end of .text, the lone kernel counted 269 lines
+    against its 7, and 61 with the second kernel behind it: profiles/kernel_digest/parent_tool.txt.)"""
+    seen = {}
+    for name, text in (('alone', FIRST), ('followed', FIRST + SECOND)):
+        src, lib = tmp_path / f'{name}.hip', tmp_path / f'{name}.so'
+        src.write_text('#include <hip/hip_runtime.h>\n' + text)
+        subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-fPIC', '-shared', str(src), '-o',
+                        str(lib)], check=True)
+        seen[name] = code_object.kernels(str(lib))
+        with tempfile.TemporaryDirectory() as d:
+            (kernel, (co, _)), = [kv for kv in code_object.all_kernel_metadata(str(lib), d).items()
+                                  if 'first_kernel' in kv[0]]
+            assert code_object.disassemble(co, kernel)[-1] == 's_endpgm'
+    assert len(seen['alone']) == 1 and len(seen['followed']) == 2
+    (kernel, alone), = seen['alone'].items()
+    assert alone[:2] == seen['followed'][kernel][:2], (alone, seen['followed'][kernel])
+
+
+def test_every_stream_ends_where_its_kernel_ends(shipped):
+    """No stream runs into the padding behind its kernel.  The forward kernel's last instruction is
+    s_endpgm, and so is that of most kernels; where block placement puts a loop's tail behind the
+    exit (13 kernels of the inflate, zstd, general and training units today) the last instruction
+    is the unconditional s_branch back into the kernel, and the s_endpgm lies before it."""
+    with tempfile.TemporaryDirectory() as d:
+        for name, (co, _) in code_object.all_kernel_metadata(LIB, d).items():
+            insts = code_object.disassemble(co, name)
+            op, _, target = insts[-1].partition(' ')
+            if 'dbh_forward_kernel' in name:
+                assert insts[-1] == 's_endpgm', (name, insts[-3:])
+            assert op in ('s_endpgm', 's_branch'), (name, insts[-3:])
+            if op == 's_branch':          # simm16 in dwords: >= 0x8000 is backwards
+                assert int(target) >= 0x8000 and 's_endpgm' in insts, (name, insts[-3:])
 
 
 def test_guard_notices_a_removed_wait_and_a_spill():

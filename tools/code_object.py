@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The gfx950 code objects inside libdeepbinner_hip.so, one per source file with kernels: kernel
 metadata (registers, spills, scratch, LDS) of every kernel of the library and a census of the forward
-kernel's instruction stream.  Used by tests/test_code_object.py
+kernel's instruction stream.  A kernel's stream is what its ELF symbol covers (disassemble()), so
+its count and digest do not depend on which kernels share its code object or on their order.
+Used by tests/test_code_object.py
 (the CPU-box guard on what ships) and by hand:  python tools/code_object.py [lib.so]
                                                 python tools/code_object.py --same OLD.so NEW.so"""
 import collections
@@ -76,10 +78,29 @@ def kernel_metadata(co):
     return {v['name']: v for v in kernels.values() if 'name' in v}
 
 
+def symbol_range(co, symbol):
+    """-> (address, size) of one function, from the ELF symbol table"""
+    text = subprocess.run([f'{LLVM}/llvm-readelf', '-s', '--wide', co], check=True, capture_output=True,
+                          text=True).stdout
+    for line in text.split('\n'):
+        f = line.split()          # Num: Value Size Type Bind Vis Ndx Name
+        if len(f) == 8 and f[3] == 'FUNC' and f[7] == symbol:
+            return int(f[1], 16), int(f[2], 0)
+    raise KeyError(f'{symbol}: no FUNC symbol in {co}')
+
+
 def disassemble(co, symbol):
-    """-> the instruction lines (mnemonic + operands) of one kernel"""
-    text = subprocess.run([f'{LLVM}/llvm-objdump', '-d', '--no-show-raw-insn', f'--disassemble-symbols={symbol}', co],
-                          check=True, capture_output=True, text=True).stdout
+    """-> the instruction lines (mnemonic + operands) of one kernel: what lies in [address, address +
+    st_size) of its ELF symbol, no more.  (llvm-objdump --disassemble-symbols runs on to the next
+    symbol or the end of .text, so the last kernel of a code object came with the section's
+    trailing s_nop padding, and its count and digest changed with its neighbours.)  The symbol
+    size is the definition: nothing is recognised as padding by its looks.
+    Known limit: branch targets are printed relative, but a PC-relative literal that addresses a
+    table elsewhere in the code object (s_getpc_b64 + an offset) changes when the kernel moves to
+    another unit, although the kernel does not."""
+    start, size = symbol_range(co, symbol)
+    text = subprocess.run([f'{LLVM}/llvm-objdump', '-d', '--no-show-raw-insn', f'--start-address={start:#x}',
+                           f'--stop-address={start + size:#x}', co], check=True, capture_output=True, text=True).stdout
     out = []
     for line in text.split('\n'):
         line = line.split('//')[0].strip()
@@ -215,7 +236,7 @@ def summary(lib):
 
 def kernels(lib):
     """-> {kernel symbol: (instruction count, hash of the instruction stream, metadata fields)},
-    every kernel of the library"""
+    every kernel of the library, each stream cut at its symbol's size (disassemble())"""
     out = {}
     with tempfile.TemporaryDirectory() as d:
         for name, (co, m) in all_kernel_metadata(lib, d).items():
@@ -226,8 +247,9 @@ def kernels(lib):
 
 
 def same(old_lib, new_lib):
-    """the kernels of two builds side by side, for a change that must not alter the compiled code:
-    -> (report lines, number of kernels present on both sides that differ)"""
+    """the kernels of two builds side by side, for a change that must not alter the compiled code -
+    a kernel moved to another source file or given other neighbours included (disassemble() has the
+    one known limit): -> (report lines, number of kernels present on both sides that differ)"""
     old, new = kernels(old_lib), kernels(new_lib)
     lines, differ = [], 0
     for name in sorted(set(old) & set(new)):
