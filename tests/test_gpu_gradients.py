@@ -4,18 +4,29 @@ tests/test_train_reference.py).
 The tolerance is not a number fixed in advance: every case runs the reference in fp64 and in fp32;
 per tensor e32 = max|g32 - g64| / max|g64|, and the device may be off by 4 e32, floored at 1e-6
 (fp32's own resolution on a tensor without cancellation).  The same rule holds for the loss and the
-batch statistics.  Measured e32 and the device's worst ratio per case:
-profiles/train_gradients/gradients_gpu.txt.
+batch statistics.
+
+That rule alone cannot fail where it matters: the fp32 run turns ReLU and pool decisions, so e32 is
+the size of a turned decision (up to 1e-2 of a tensor, and more on larger batches), not of a
+rounding.  So the cases of train_reference.GUARDED, the repeated batches and the tie cases are held
+to a second bound as well, max(4 e_model, 1e-6): e_model is the error of the reference's model mode,
+fp64 arithmetic rounded to fp32 where DESIGN.md section 17 says the device rounds, the largest among
+eight orders of its short sums (train_reference.references says why one order is not enough: with
+one, the device was above the bound on 21 of some 50 small cases, by up to 8.9 bounds, at a median
+device-to-model ratio of 1; with eight, on none, 0.58 of the bound at the most).  Model and device
+round at the same places in different orders - draws of one size, hence the same factor 4.  Those
+cases run on windows on which no decision is close (tests/test_train_reference.py asserts
+it), because a turned decision is covered by no tolerance.  OLD_RULE_ONLY names the tensors that
+stay under the fp32 rule alone.  Measured e_model, e32 and the device's worst ratio under both
+rules, per case: profiles/train_gradients/gradients_gpu.txt.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import train_reference as tr
 import weight_families as wf
-from conftest import GOLD
 from deepbinner_amd.model_format import BN_CHANNELS, param_count
 
 pytestmark = pytest.mark.gpu
@@ -31,24 +42,13 @@ pytestmark = pytest.mark.gpu
 #   1024 x 3 x 256: the widest head
 CASES = [(96, 3, 2), (130, 5, 13), (200, 2, 33), (1024, 20, 13), (1024, 3, 256)]
 RATES = [0.0, 0.15]
-SEED = 20181018
+SEED = tr.SEED
+# tensors held to the fp32 reference's rule alone (at most 5, none of conv1d_2 .. 19's kernels)
+OLD_RULE_ONLY = ()
 
 
 def case_inputs(size, n, classes):
-    if (size, n, classes) == (1024, 20, 13):
-        from general_fixtures import shipped
-        weights = shipped()
-        x = np.load(os.path.join(GOLD, 'windows_start.npy')).reshape(-1, 1024)[:n]
-        x = np.ascontiguousarray(x, dtype=np.float32)
-    else:
-        weights = wf.random_model(size + n, classes, input_size=size)
-        x = np.random.default_rng([size, n, classes]).standard_normal((n, size)).astype(np.float32)
-    if classes == 256:
-        labels = np.full(n, 77, dtype=np.int32)            # every window the same label
-    else:
-        labels = np.random.default_rng(size).integers(classes, size=n).astype(np.int32)
-        labels[0], labels[-1] = 0, classes - 1
-    return weights, x, labels
+    return tr.case_inputs(size, n, classes)
 
 
 _reference = {}
@@ -75,23 +75,54 @@ def stat_slices():
 
 def ratios(got, r64, r32, slices):
     """name -> (e32, device error / bound) with bound = max(4 e32, 1e-6), all relative to
-    max|fp64 tensor|."""
+    max|fp64 tensor|.  ``r32`` may be a list of runs (the model's draws): e is then the largest
+    of their errors."""
     out = {}
+    runs = r32 if isinstance(r32, list) else [r32]
     for name, sl in slices.items():
         want = np.asarray(r64[sl], dtype=np.float64)
         scale = np.abs(want).max()
         if scale == 0:
             out[name] = (0.0, 0.0 if not np.asarray(got[sl]).any() else np.inf)
             continue
-        e32 = np.abs(np.asarray(r32[sl], dtype=np.float64) - want).max() / scale
+        e32 = max(np.abs(np.asarray(r[sl], dtype=np.float64) - want).max() for r in runs) / scale
         g = np.asarray(got[sl], dtype=np.float64)
         err = np.abs(g - want).max() / scale if np.isfinite(g).all() else np.inf
         out[name] = (float(e32), float(err / max(4 * e32, 1e-6)))
     return out
 
 
-def check_against_reference(got, r64, r32, classes, tag):
-    loss, n_correct, grads, stats = got
+def check_against_model(got, r64, rm, classes, tag):
+    """The second rule: ratios() with the model's run in the fp32 run's place."""
+    loss, _, grads, stats = got
+    slices, _ = tr.tensor_slices(classes)
+    em = tr.model_error(r64, rm)
+    loss_ratio = abs(loss - r64.loss) / abs(r64.loss) / max(4 * em, 1e-6)
+    res = ratios(grads, r64.grads, [g for _, g, _ in rm.draws], slices)
+    res_stats = ratios(stats, r64.stats, [s for _, _, s in rm.draws], stat_slices())
+    worst = max(res.items(), key=lambda kv: kv[1][1])
+    worst_s = max(res_stats.items(), key=lambda kv: kv[1][1])
+    print('{} against the model: loss e_model {:.2e}, ratio {:.3f}; gradients worst ratio {:.3f} '
+          '({}, e_model {:.2e}; e_model over tensors {:.2e} .. {:.2e}); statistics worst ratio '
+          '{:.3f} ({})'.format(tag, em, loss_ratio, worst[1][1], worst[0], worst[1][0],
+                               min(v[0] for v in res.values()), max(v[0] for v in res.values()),
+                               worst_s[1][1], worst_s[0]))
+    assert loss_ratio <= 1.0, (loss, r64.loss, em)
+    bad = {k: v for k, v in res.items() if not v[1] <= 1.0 and k not in OLD_RULE_ONLY}
+    assert not bad, bad
+    bad = {k: v for k, v in res_stats.items() if not v[1] <= 1.0}
+    assert not bad, bad
+
+
+def check_against_reference(got, r64, r32, classes, tag, rm=None, n_correct=None):
+    """The fp32 reference's rule, and with ``rm`` the model's as well."""
+    if rm is not None:
+        try:
+            check_against_model(got, r64, rm, classes, tag)
+        finally:
+            check_against_reference(got, r64, r32, classes, tag, n_correct=n_correct)
+        return
+    loss, n_correct_got, grads, stats = got
     slices, moving = tr.tensor_slices(classes)
     e32 = abs(r32.loss - r64.loss) / abs(r64.loss)
     loss_ratio = abs(loss - r64.loss) / abs(r64.loss) / max(4 * e32, 1e-6)
@@ -104,7 +135,7 @@ def check_against_reference(got, r64, r32, classes, tag):
           .format(tag, loss, r64.loss, e32, loss_ratio, worst[1][1], worst[0], worst[1][0],
                   min(v[0] for v in res.values()), max(v[0] for v in res.values()),
                   worst_s[1][1], worst_s[0]))
-    assert n_correct == r64.n_correct
+    assert n_correct_got == (r64.n_correct if n_correct is None else n_correct)
     assert loss_ratio <= 1.0, (loss, r64.loss, e32)
     bad = {k: v for k, v in res.items() if not v[1] <= 1.0}
     assert not bad, bad
@@ -122,6 +153,23 @@ def test_loss_gradients_and_statistics(hip, size, n, classes, rate):
     got = hip.loss_and_gradients(weights, x, labels, dropout_rate=rate, seed=SEED)
     assert got[2].size == param_count(classes) and got[3].size == 960
     check_against_reference(got, r64, r32, classes, 'L{} N{} C{} rate {}'.format(size, n, classes, rate))
+
+
+@pytest.mark.parametrize('case', tr.GUARDED, ids=tr.case_id)
+def test_guarded_cases_under_both_rules(hip, case):
+    size, n, classes, rate, seed, draw = case
+    weights, x, labels = tr.case_inputs(size, n, classes, draw)
+    r64, r32, rm = tr.guarded_references(case)
+    got = hip.loss_and_gradients(weights, x, labels, dropout_rate=rate, seed=seed)
+    check_against_reference(got, r64, r32, classes, tr.case_id(case), rm=rm)
+
+
+def test_high_half_of_the_seed_reaches_the_masks(hip):
+    weights, x, labels = tr.case_inputs(130, 5, 13, 0)
+    low = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.5, seed=tr.SEED)
+    high = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.5, seed=tr.HIGH_SEED)
+    assert tr.HIGH_SEED & 0xFFFFFFFF == tr.SEED and tr.HIGH_SEED >> 32
+    assert high[2].tobytes() != low[2].tobytes() and high[0] != low[0]
 
 
 def run_dev(hip, weights, x, labels, rate, seed):
@@ -155,6 +203,73 @@ def test_same_bits_twice_and_through_the_device_entry(hip):
     assert same_bits(first, run_dev(hip, weights, x, labels, 0.15, SEED))
     other = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=SEED + 1)
     assert other[2].tobytes() != first[2].tobytes()         # the seed reaches the masks
+
+
+# (input size, windows, classes, draw) of a GUARDED case at rate 0, and how often it is repeated.
+# A repeated batch has the batch's own loss, statistics and gradients (pinned for the reference in
+# tests/test_train_reference.py), its activations are the base's, so its decisions are as far from
+# turning: the expected values and both bounds are the base case's own, at row counts where the
+# reductions leave their smallest partition:
+#   (130, 5, 13) x 64: 20,800 rows at conv1d_1, just past 64 rows x 256 parts, odd lengths
+#   (1024, 4, 13) x 130: parts of 1040, 520, ... rows; at length 64 of 130 rounded up to 132 - 253
+#         waves and three with no rows; 4,160 head rows in 245 parts of 17
+#   (1024, 4, 13) x 256: 1,024 windows, the most one call takes
+REPEATED = [((130, 5, 13, 0), 64), ((1024, 4, 13, 1), 130), ((1024, 4, 13, 1), 256)]
+
+
+@pytest.mark.parametrize('base,times', REPEATED, ids=lambda v: str(v).replace(' ', ''))
+def test_training_sized_batches_by_repetition(hip, base, times):
+    size, n, classes, draw = base
+    case = (size, n, classes, 0.0, tr.SEED, draw)
+    assert case in tr.GUARDED
+    weights, x, labels = tr.case_inputs(size, n, classes, draw)
+    r64, r32, rm = tr.guarded_references(case)
+    x, labels = np.tile(x, (times, 1)), np.tile(labels, times)
+    limit = ctypes.c_int64(0)
+    assert hip.load_library().dbh_gradients_max_windows(size, ctypes.byref(limit)) == 0
+    assert n * times <= limit.value and (times != 256 or n * times == limit.value)
+    got = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.0, seed=tr.SEED)
+    if times == 64:
+        assert same_bits(got, run_dev(hip, weights, x, labels, 0.0, tr.SEED))
+    check_against_reference(got, r64, r32, classes, '{} x {}'.format(tr.case_id(case), times),
+                            rm=rm, n_correct=times * r64.n_correct)
+
+
+@pytest.mark.parametrize('layers', tr.TIE_LAYERS, ids=lambda l: 'conv1d_' + '_'.join(map(str, l)))
+def test_positive_pool_ties_go_to_the_first(hip, layers):
+    """Every pool pair behind the named layers is an exact positive tie (train_reference.tie_inputs;
+    that "the second wins" would move the layer's kernel gradient by 100 bounds and more is pinned
+    in tests/test_train_reference.py).  ratios() demands exact zeros where the reference has them:
+    everything upstream.  (Behind a constant layer some tensors are 0 in exact arithmetic and
+    rounding noise of 1e-17 in fp64 - the tied layer's bias, whose gradient is the sum of a BN's
+    backward output - and no relative bound says anything about those; the kernel of the tied
+    layer is not among them.)"""
+    weights, x, labels = tr.tie_inputs(layers)
+    r64, r32, rm = tr.tie_references(layers)
+    slices, _ = tr.tensor_slices(tr.TIE_SHAPE[2])
+    convs, bns = tr.TIE_UPSTREAM[layers[0]]
+    got = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.0, seed=tr.SEED)
+    for name in (['conv1d_%d/%s' % (i, p) for i in convs for p in ('kernel', 'bias')]
+                 + ['bn_%d/%s' % (i, p) for i in bns for p in ('gamma', 'beta')]):
+        assert not r64.grads[slices[name]].any() and not got[2][slices[name]].any(), name
+    for i in layers:
+        assert r64.grads[slices['conv1d_%d/kernel' % i]].any()
+    check_against_reference(got, r64, r32, tr.TIE_SHAPE[2], 'ties behind conv1d_' +
+                            '_'.join(map(str, layers)), rm=rm)
+
+
+def test_equal_logits_go_to_the_lowest_class(hip):
+    """conv1d_20's kernel zero and all its biases equal and positive: every window's logits are
+    equal, class 0 is the prediction, and the loss is log C."""
+    n, classes = 6, 13
+    bias = wf.constant_biases(classes)['equal']
+    assert (bias == bias[0]).all() and bias[0] > 0
+    weights = wf.constant(wf.random_model(3, classes), bias)
+    x = np.random.default_rng(7).standard_normal((n, 1024)).astype(np.float32)
+    labels = np.array([0, 12, 0, 5, 1, 0], dtype=np.int32)
+    loss, n_correct, grads, _ = hip.loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=3)
+    assert n_correct == int((labels == 0).sum()) == 3
+    assert abs(loss - np.log(classes)) <= 1e-6 * np.log(classes)
 
 
 def test_windows_permuted(hip):

@@ -260,3 +260,99 @@ def test_gradient_argument_errors_without_device():
                                  None, None, None, None, None) == BAD_WEIGHTS
     assert lib.dbh_gradients_dev(None, count, classes, length, None, None, n, 0.15, 0, None,
                                  None, None, None, None, None) == INVALID
+
+
+# ---- e. the model of the device's arithmetic and the inputs it is used on ------------------------
+def model_bounds(r64, rm, slices):
+    """name -> max(4 e_model, 1e-6): what tests/test_gpu_gradients.py allows the device."""
+    return {name: max(4 * tr.model_error(r64, rm, sl), 1e-6) for name, sl in slices.items()}
+
+
+@pytest.mark.parametrize('case', tr.GUARDED, ids=tr.case_id)
+def test_model_rounds_and_turns_no_decision(case):
+    """On every direct case of the device tests: no ReLU pre-activation and no pool pair of the fp64
+    run lies within 8 x (what the model's rounding moved it by, floored at 1/16 of its layer's
+    largest move), the model's patterns - in every order of its short sums - are the fp64 run's,
+    its loss is the fp64 loss to 1e-6, and its gradients are not the fp64 bits - it does round."""
+    r64, r32, rm = tr.guarded_references(case)
+    print('{}: {} decisions, {} close; loss off by {:.2e}'.format(
+        tr.case_id(case), rm.n_decisions, rm.close, abs(rm.loss - r64.loss) / abs(r64.loss)))
+    assert rm.close == 0
+    assert rm.same
+    assert rm.n_correct == r64.n_correct
+    assert abs(rm.loss - r64.loss) <= 1e-6 * abs(r64.loss)
+    assert rm.grads.tobytes() != r64.grads.tobytes()
+    assert rm.grads.astype(np.float32).astype(np.float64).tobytes() == rm.grads.tobytes()
+    slices, moving = tr.tensor_slices(case[2])
+    # every order of the short sums is another draw (but for one window at 96, where nothing in
+    # front of the head has a gradient)
+    piped = r64.grads[slices['conv1d_2/kernel']].any()
+    assert piped or case[:2] == (96, 1)
+    assert len({g.tobytes() for _, g, _ in rm.draws}) == (tr.ORDERS if piped else 1)
+    for m in moving:
+        assert not rm.grads[m].any()
+
+
+def test_model_is_tighter_than_the_fp32_reference():
+    """What the yardstick is for: on the default batch shape the fp32 run's error is a few turned
+    decisions, not rounding, and the model's is far below it."""
+    case = (1024, 4, 13, 0.0, tr.SEED, 1)
+    assert case in tr.GUARDED
+    r64, r32, rm = tr.guarded_references(case)
+    slices, _ = tr.tensor_slices(13)
+    e32, em = [], []
+    for sl in slices.values():
+        scale = np.abs(r64.grads[sl]).max()
+        e32.append(np.abs(r32.grads[sl] - r64.grads[sl]).max() / scale)
+        em.append(tr.model_error(r64, rm, sl))
+    print('e_model {:.2e} .. {:.2e}, e32 {:.2e} .. {:.2e}'.format(min(em), max(em), min(e32), max(e32)))
+    assert max(em) < 1e-4                       # (a turned decision moves a tensor by 1e-3 and more)
+    assert np.median(em) < np.median(e32)
+
+
+def test_a_repeated_batch_has_the_batch_s_gradients():
+    """Dropout 0: a batch given R times with its labels has the same mean loss, statistics and
+    gradients; only n_correct grows R-fold.  (What lets the device tests reach training-sized
+    batches with a small case's reference.)  Bound 1e-9 of a tensor's size: fp64 sums in another
+    order lose some 1e-16 x sqrt(rows) x cancellation, and 1e-9 is a thousandth of the floor the
+    device is given."""
+    case = (130, 5, 13, 0.0, tr.SEED, 0)
+    r64, _, _ = tr.guarded_references(case)
+    weights, x, labels = tr.case_inputs(130, 5, 13, 0)
+    rep = tr.loss_and_gradients(weights, np.tile(x, (4, 1)), np.tile(labels, 4), rate=0.0, seed=tr.SEED)
+    assert rep.n_correct == 4 * r64.n_correct
+    assert abs(rep.loss - r64.loss) <= 1e-9 * abs(r64.loss)
+    slices, _ = tr.tensor_slices(13)
+    for name, sl in slices.items():
+        scale = np.abs(r64.grads[sl]).max()
+        assert np.abs(rep.grads[sl] - r64.grads[sl]).max() <= 1e-9 * scale, name
+    assert np.abs(rep.stats - r64.stats).max() <= 1e-9 * np.abs(r64.stats).max()
+
+
+@pytest.mark.parametrize('layers', tr.TIE_LAYERS, ids=lambda l: 'conv1d_' + '_'.join(map(str, l)))
+def test_pool_tie_rule_is_observable(layers):
+    """A zero kernel with bias 0.5 makes every pool pair behind the layer an exact positive tie.
+    Upstream gradients are exactly 0, and the layer's own kernel gradient under "the second wins"
+    is at least 100 bounds away from the contract's: the device test on these weights would
+    notice a ``>`` for the ``>=``."""
+    r64, _, rm = tr.tie_references(layers)
+    assert rm.close == 0 and rm.same
+    weights, x, labels = tr.tie_inputs(layers)
+    assert np.abs(np.diff(x, axis=1)).min() > 0
+    second = tr.loss_and_gradients(weights, x, labels, rate=0.0, seed=tr.SEED, tie_first=False)
+    assert second.loss == r64.loss
+    slices, _ = tr.tensor_slices(tr.TIE_SHAPE[2])
+    bounds = model_bounds(r64, rm, slices)
+    for i in layers:
+        name = 'conv1d_%d/kernel' % i
+        sl = slices[name]
+        scale = np.abs(r64.grads[sl]).max()
+        assert scale > 0
+        moved = np.abs(second.grads[sl] - r64.grads[sl]).max() / scale
+        print('{}: "second wins" moves it by {:.3f} of its size, bound {:.2e}'.format(
+            name, moved, bounds[name]))
+        assert moved >= 100 * bounds[name]
+    convs, bns = tr.TIE_UPSTREAM[layers[0]]
+    for name in (['conv1d_%d/%s' % (i, p) for i in convs for p in ('kernel', 'bias')]
+                 + ['bn_%d/%s' % (i, p) for i in bns for p in ('gamma', 'beta')]):
+        assert not r64.grads[slices[name]].any() and not rm.grads[slices[name]].any(), name
