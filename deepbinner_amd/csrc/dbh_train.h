@@ -4,7 +4,7 @@
 // train_network.py:53-55), for any geometry dbh_gen::geometry_ok accepts.  DESIGN.md section 17.
 //
 // The input windows are taken as given: the reference's GaussianNoise(0.02) layer
-// (network_architecture.py:26) is the caller's to add to x; it is not part of this call.
+// (network_architecture.py:25) is the caller's to add to x (dbh_trainer.hip); it is not part of this call.
 //
 // Dropout (rate, inverted, behind each batch normalisation) keeps an element by a stateless
 // function of (seed, dropout layer 1..7, window, position, channel), 32-bit integers throughout:

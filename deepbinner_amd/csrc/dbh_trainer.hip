@@ -1,0 +1,434 @@
+// dbh_trainer.hip — the training step's second half and the trainer that keeps a model's training
+// state on the device (include/deepbinner_hip.h, "a resident trainer"):
+//   noise_kernel    GaussianNoise (reference network_architecture.py:25): Box-Muller in fp64 from two
+//                   draws of dbh_train.h's hash, layer number 0, one rounding to fp32
+//   update_kernel   one pass over the blob: Keras 2.1.4's Nadam (train_network.py:53-55) on the
+//                   trainable elements, BatchNormalization's moving average on the others, in fp64.
+//                   Which is which comes from dbh_network.h's table (BlobMap below).
+// Every element is a function of its own index: no atomics, no reduction, nothing that depends on
+// the launch geometry.  The library is built with -ffp-contract=off, so each operation below is the
+// IEEE operation it is written as, and NumPy on the host gives the same bits
+// (tests/train_step_reference.py).
+#include "../../include/deepbinner_hip.h"
+#include "dbh_general.h"
+#include "dbh_network.h"
+#include "dbh_owned.h"
+#include "dbh_train.h"
+
+#include <cmath>
+#include <new>
+#include <vector>
+
+namespace {
+
+using namespace dbh_net;
+
+constexpr int kThreads = 256;
+constexpr uint64_t kStepStride = 0x9E3779B97F4A7C15ull;    // step_seed = seed + t0 * kStepStride
+constexpr int64_t kMaxNoiseSamples = dbh_train::kMaxBatchSamples;
+
+inline unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+// ---- noise --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void noise_kernel(const float* __restrict__ x, long long total,
+                                                         int input_size, float noise_std,
+                                                         uint32_t seed_lo, uint32_t seed_hi,
+                                                         float* __restrict__ out) {
+    const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= total) return;
+    const float v = x[idx];
+    if (noise_std == 0.f) {          // bit for bit: no arithmetic (x + 0 would turn -0 into +0)
+        out[idx] = v;
+        return;
+    }
+    const long long window = idx / input_size;
+    const uint32_t position = (uint32_t)(idx - window * input_size);
+    const uint32_t b1 = dbh_train::dropout_bits(seed_lo, seed_hi, 0u, (uint32_t)window, position, 0u);
+    const uint32_t b2 = dbh_train::dropout_bits(seed_lo, seed_hi, 0u, (uint32_t)window, position, 1u);
+    const double u1 = ((double)b1 + 1.0) / 16777216.0;
+    const double u2 = (double)b2 / 16777216.0;
+    const double radius = sqrt(-2.0 * log(u1));
+    const double z = radius * cos(6.283185307179586 * u2);
+    out[idx] = (float)((double)v + (double)noise_std * z);
+}
+
+// ---- update -------------------------------------------------------------------------------------
+// Where the batch normalisations lie in a blob of this class count: bn[j] = blob_bn(j), bn[kNumBn] =
+// the blob's end.  Layer j holds gamma, beta, moving mean, moving variance, a quarter of its floats
+// each; its batch statistics (mean then variance) start at half its distance from bn[0].
+struct BlobMap {
+    int bn[kNumBn + 1];
+};
+
+BlobMap blob_map(int n_classes) {
+    BlobMap map;
+    for (int j = 0; j <= kNumBn; ++j) map.bn[j] = (int)blob_bn(j, n_classes);
+    return map;
+}
+
+__global__ __launch_bounds__(kThreads) void update_kernel(float* __restrict__ params,
+                                                          const float* __restrict__ grads,
+                                                          float* __restrict__ m_blob,
+                                                          float* __restrict__ v_blob,
+                                                          const float* __restrict__ stats,
+                                                          BlobMap map, dbh_nadam_coefficients k) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= map.bn[kNumBn]) return;
+    if (i >= map.bn[0]) {
+        int begin = map.bn[0], end = map.bn[1];
+#pragma unroll
+        for (int j = 1; j < kNumBn; ++j)
+            if (i >= map.bn[j]) {
+                begin = map.bn[j];
+                end = map.bn[j + 1];
+            }
+        const int channels = (end - begin) / 4;
+        const int within = i - begin;
+        if (within >= 2 * channels) {
+            // moving mean (third quarter) or moving variance (fourth): the batch's value lies at the
+            // same distance behind the layer's first statistic
+            const double old = (double)params[i];
+            const double batch = (double)stats[(begin - map.bn[0]) / 2 + (within - 2 * channels)];
+            const double step = (old - batch) * (1.0 - k.bn_momentum);
+            params[i] = (float)(old - step);
+            return;
+        }
+    }
+    const double p = (double)params[i], g = (double)grads[i];
+    const double g_prime = g / (1.0 - k.sched_new);
+    const double m_keep = k.beta_1 * (double)m_blob[i];
+    const double m_add = (1.0 - k.beta_1) * g;
+    const double m = m_keep + m_add;
+    const double m_prime = m / (1.0 - k.sched_next);
+    const double v_keep = k.beta_2 * (double)v_blob[i];
+    const double gg = g * g;
+    const double v_add = (1.0 - k.beta_2) * gg;
+    const double v = v_keep + v_add;
+    const double v_prime = v / (1.0 - k.beta_2_t);
+    const double from_g = (1.0 - k.mu_t) * g_prime;
+    const double from_m = k.mu_t1 * m_prime;
+    const double bar = from_g + from_m;
+    const double denom = sqrt(v_prime) + k.epsilon;
+    const double scaled = k.lr * bar;
+    const double move = scaled / denom;
+    m_blob[i] = (float)m;
+    v_blob[i] = (float)v;
+    params[i] = (float)(p - move);
+}
+
+// ---- host ---------------------------------------------------------------------------------------
+const dbh_trainer_options kDefaults = {
+    (double)0.002f, (double)0.9f, (double)0.999f, 1e-7, 0.004, 0.99, 0.15f, 0.02f, 0,
+};
+
+bool in_unit(double v, bool closed) { return v >= 0.0 && (closed ? v <= 1.0 : v < 1.0); }
+
+int check_options(const dbh_trainer_options& o) {
+    if (!in_unit((double)o.dropout_rate, false) || !(o.noise_std >= 0.f) || !in_unit(o.bn_momentum, true))
+        return DBH_ERR_INVALID_ARGUMENT;
+    return DBH_OK;
+}
+
+int check_noise(int64_t n_windows, int input_size, float noise_std) {
+    if (n_windows < 1 || input_size < 1 || !(noise_std >= 0.f)) return DBH_ERR_INVALID_ARGUMENT;
+    if (input_size > dbh_gen::kMaxInput || n_windows > kMaxNoiseSamples / input_size)
+        return DBH_ERR_UNSUPPORTED;
+    return DBH_OK;
+}
+
+int check_update(int64_t n_floats, int n_classes, const dbh_nadam_coefficients* k) {
+    if (n_classes < dbh_gen::kMinClasses || n_classes > dbh_gen::kMaxClasses) return DBH_ERR_UNSUPPORTED;
+    if (n_floats != param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
+    if (!k || !in_unit(k->bn_momentum, true)) return DBH_ERR_INVALID_ARGUMENT;
+    return DBH_OK;
+}
+
+hipError_t launch_noise(const float* x, int64_t n_windows, int input_size, float noise_std,
+                        uint64_t seed, float* out, hipStream_t stream) {
+    const long long total = (long long)n_windows * input_size;
+    hipLaunchKernelGGL(noise_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, stream, x, total,
+                       input_size, noise_std, (uint32_t)seed, (uint32_t)(seed >> 32), out);
+    return hipGetLastError();
+}
+
+hipError_t launch_update(float* params, const float* grads, float* m, float* v, const float* stats,
+                         int n_classes, const dbh_nadam_coefficients& k, hipStream_t stream) {
+    hipLaunchKernelGGL(update_kernel, dim3(blocks_for(param_count(n_classes))), dim3(kThreads), 0,
+                       stream, params, grads, m, v, stats, blob_map(n_classes), k);
+    return hipGetLastError();
+}
+
+#define DBH_TRAINER_HIP(call)                                                     \
+    do {                                                                          \
+        const hipError_t e_ = (call);                                             \
+        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, #call);      \
+    } while (0)
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+// One block on the device, carved once: the four blobs, the statistics, a batch's windows as given
+// and with their noise, its labels, the loss and the count, dbh_gradients' workspace.
+struct dbh_trainer {
+    dbh_trainer_options options;
+    int n_classes = 0, input_size = 0;
+    int64_t n_floats = 0, max_windows = 0;
+    int64_t iterations = 0;
+    double m_schedule = 1.0;
+    dbh_owned::DeviceBlock block;
+    float *weights = nullptr, *m = nullptr, *v = nullptr, *grads = nullptr, *stats = nullptr;
+    float *x_in = nullptr, *x_noisy = nullptr;
+    int32_t* labels = nullptr;
+    double* loss = nullptr;          // the count follows it: int64 at loss + 1
+    void* workspace = nullptr;
+
+    size_t blob_bytes() const { return (size_t)n_floats * sizeof(float); }
+
+    hipError_t allocate() {
+        const size_t blob = up256(blob_bytes());
+        const size_t x_bytes = up256((size_t)max_windows * input_size * sizeof(float));
+        const size_t at_stats = 4 * blob, at_x = at_stats + up256(dbh_train::kStatsFloats * sizeof(float));
+        const size_t at_labels = at_x + 2 * x_bytes;
+        const size_t at_out = at_labels + up256((size_t)max_windows * sizeof(int32_t));
+        const size_t at_work = at_out + 256;
+        const hipError_t e = block.reserve(
+            at_work + dbh_train::workspace_bytes(n_classes, input_size, max_windows));
+        if (e != hipSuccess) return e;
+        weights = block.as<float>(0);
+        m = block.as<float>(blob);
+        v = block.as<float>(2 * blob);
+        grads = block.as<float>(3 * blob);
+        stats = block.as<float>(at_stats);
+        x_in = block.as<float>(at_x);
+        x_noisy = block.as<float>(at_x + x_bytes);
+        labels = block.as<int32_t>(at_labels);
+        loss = block.as<double>(at_out);
+        workspace = block.as<char>(at_work);
+        return hipSuccess;
+    }
+
+    int check_step(int64_t n_windows) const {
+        if (n_windows < 1) return DBH_ERR_INVALID_ARGUMENT;
+        if (n_windows > max_windows) return DBH_ERR_UNSUPPORTED;
+        return DBH_OK;
+    }
+
+    // noise, gradients, update: queued on `stream`; the host's part of the state moves on at once
+    hipError_t queue_step(const float* x, const int32_t* step_labels, int64_t n_windows,
+                          double* mean_loss, int64_t* n_correct, hipStream_t stream) {
+        const uint64_t step_seed = options.seed + (uint64_t)iterations * kStepStride;
+        dbh_nadam_coefficients k;
+        (void)dbh_nadam_schedule(iterations, m_schedule, &options, &k);
+        hipError_t e = launch_noise(x, n_windows, input_size, options.noise_std, step_seed, x_noisy, stream);
+        if (e == hipSuccess)
+            e = dbh_train::gradients(weights, n_classes, input_size, x_noisy, step_labels, n_windows,
+                                     options.dropout_rate, step_seed, mean_loss, n_correct, grads,
+                                     stats, workspace, stream);
+        if (e == hipSuccess) e = launch_update(weights, grads, m, v, stats, n_classes, k, stream);
+        if (e == hipSuccess) {
+            iterations += 1;
+            m_schedule = k.sched_new;
+        }
+        return e;
+    }
+};
+
+extern "C" {
+
+int dbh_trainer_default_options(dbh_trainer_options* options) {
+    if (!options) return DBH_ERR_INVALID_ARGUMENT;
+    *options = kDefaults;
+    return DBH_OK;
+}
+
+int dbh_nadam_schedule(int64_t t0, double m_schedule, const dbh_trainer_options* hyper,
+                       dbh_nadam_coefficients* k) {
+    if (!k || t0 < 0) return DBH_ERR_INVALID_ARGUMENT;
+    const dbh_trainer_options& o = hyper ? *hyper : kDefaults;
+    const double t = (double)t0 + 1.0;
+    k->lr = o.lr;
+    k->beta_1 = o.beta_1;
+    k->beta_2 = o.beta_2;
+    k->epsilon = o.epsilon;
+    k->mu_t = o.beta_1 * (1.0 - 0.5 * std::pow(0.96, t * o.schedule_decay));
+    k->mu_t1 = o.beta_1 * (1.0 - 0.5 * std::pow(0.96, (t + 1.0) * o.schedule_decay));
+    k->sched_new = m_schedule * k->mu_t;
+    k->sched_next = k->sched_new * k->mu_t1;
+    k->beta_2_t = std::pow(o.beta_2, t);
+    k->bn_momentum = o.bn_momentum;
+    return DBH_OK;
+}
+
+int dbh_train_noise_dev(const float* x_dev, int64_t n_windows, int input_size, float noise_std,
+                        uint64_t seed, float* out_dev, dbh_stream stream) {
+    const int st = check_noise(n_windows, input_size, noise_std);
+    if (st != DBH_OK) return st;
+    if (!x_dev || !out_dev) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_TRAINER_HIP(launch_noise(x_dev, n_windows, input_size, noise_std, seed, out_dev,
+                                 (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_train_noise(const float* x_host, int64_t n_windows, int input_size, float noise_std,
+                    uint64_t seed, float* out_host) {
+    const int st = check_noise(n_windows, input_size, noise_std);
+    if (st != DBH_OK) return st;
+    if (!x_host || !out_host) return DBH_ERR_INVALID_ARGUMENT;
+    const size_t bytes = (size_t)n_windows * input_size * sizeof(float);
+    dbh_owned::DeviceBlock block;
+    DBH_TRAINER_HIP(block.reserve(bytes));
+    float* d = block.as<float>();
+    DBH_TRAINER_HIP(hipMemcpyAsync(d, x_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(launch_noise(d, n_windows, input_size, noise_std, seed, d, 0));
+    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    DBH_TRAINER_HIP(hipMemcpy(out_host, d, bytes, hipMemcpyDeviceToHost));
+    return DBH_OK;
+}
+
+int dbh_nadam_update_dev(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev,
+                         const float* batch_stats_dev, int64_t n_floats, int n_classes,
+                         const dbh_nadam_coefficients* coefficients, dbh_stream stream) {
+    const int st = check_update(n_floats, n_classes, coefficients);
+    if (st != DBH_OK) return st;
+    if (!params_dev || !grads_dev || !m_dev || !v_dev || !batch_stats_dev) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_TRAINER_HIP(launch_update(params_dev, grads_dev, m_dev, v_dev, batch_stats_dev, n_classes,
+                                  *coefficients, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host, float* v_host,
+                     const float* batch_stats_host, int64_t n_floats, int n_classes,
+                     const dbh_nadam_coefficients* coefficients) {
+    const int st = check_update(n_floats, n_classes, coefficients);
+    if (st != DBH_OK) return st;
+    if (!params_host || !grads_host || !m_host || !v_host || !batch_stats_host)
+        return DBH_ERR_INVALID_ARGUMENT;
+    const size_t bytes = (size_t)n_floats * sizeof(float), blob = up256(bytes);
+    const size_t s_bytes = dbh_train::kStatsFloats * sizeof(float);
+    dbh_owned::DeviceBlock block;
+    DBH_TRAINER_HIP(block.reserve(4 * blob + s_bytes));
+    float *p = block.as<float>(0), *g = block.as<float>(blob), *m = block.as<float>(2 * blob);
+    float *v = block.as<float>(3 * blob), *s = block.as<float>(4 * blob);
+    DBH_TRAINER_HIP(hipMemcpyAsync(p, params_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(hipMemcpyAsync(g, grads_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(hipMemcpyAsync(m, m_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(hipMemcpyAsync(v, v_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(hipMemcpyAsync(s, batch_stats_host, s_bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(launch_update(p, g, m, v, s, n_classes, *coefficients, 0));
+    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    DBH_TRAINER_HIP(hipMemcpy(params_host, p, bytes, hipMemcpyDeviceToHost));
+    DBH_TRAINER_HIP(hipMemcpy(m_host, m, bytes, hipMemcpyDeviceToHost));
+    DBH_TRAINER_HIP(hipMemcpy(v_host, v, bytes, hipMemcpyDeviceToHost));
+    return DBH_OK;
+}
+
+int dbh_trainer_create(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                       int64_t max_windows, const dbh_trainer_options* options,
+                       dbh_trainer** trainer) {
+    if (!dbh_gen::geometry_ok(input_size, n_classes)) return DBH_ERR_UNSUPPORTED;
+    if (n_floats != param_count(n_classes)) return DBH_ERR_BAD_WEIGHTS;
+    const dbh_trainer_options& o = options ? *options : kDefaults;
+    if (max_windows < 1 || !weights_host || !trainer || check_options(o) != DBH_OK)
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (max_windows > dbh_train::kMaxBatchSamples / input_size) return DBH_ERR_UNSUPPORTED;
+    dbh_trainer* t = new (std::nothrow) dbh_trainer;
+    if (!t) return DBH_ERR_OUT_OF_MEMORY;
+    t->options = o;
+    t->n_classes = n_classes;
+    t->input_size = input_size;
+    t->n_floats = n_floats;
+    t->max_windows = max_windows;
+    hipError_t e = t->allocate();
+    if (e == hipSuccess) e = hipMemcpy(t->weights, weights_host, t->blob_bytes(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(t->m, 0, t->blob_bytes());
+    if (e == hipSuccess) e = hipMemset(t->v, 0, t->blob_bytes());
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        delete t;
+        return dbh_train::report_hip_error(e, "dbh_trainer_create");
+    }
+    *trainer = t;
+    return DBH_OK;
+}
+
+int dbh_trainer_destroy(dbh_trainer* trainer) {
+    if (trainer) {
+        (void)hipDeviceSynchronize();      // a queued step may still use the block
+        delete trainer;
+    }
+    return DBH_OK;
+}
+
+int dbh_trainer_step_dev(dbh_trainer* trainer, const float* x_dev, const int32_t* labels_dev,
+                         int64_t n_windows, double* mean_loss_dev, int64_t* n_correct_dev,
+                         dbh_stream stream) {
+    if (!trainer || !x_dev || !labels_dev || !mean_loss_dev || !n_correct_dev)
+        return DBH_ERR_INVALID_ARGUMENT;
+    const int st = trainer->check_step(n_windows);
+    if (st != DBH_OK) return st;
+    DBH_TRAINER_HIP(trainer->queue_step(x_dev, labels_dev, n_windows, mean_loss_dev, n_correct_dev,
+                                        (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_trainer_step(dbh_trainer* trainer, const float* x_host, const int32_t* labels_host,
+                     int64_t n_windows, double* mean_loss, int64_t* n_correct) {
+    if (!trainer || !x_host || !labels_host || !mean_loss || !n_correct) return DBH_ERR_INVALID_ARGUMENT;
+    const int st = trainer->check_step(n_windows);
+    if (st != DBH_OK) return st;
+    for (int64_t i = 0; i < n_windows; ++i)
+        if (labels_host[i] < 0 || labels_host[i] >= trainer->n_classes) return DBH_ERR_INVALID_ARGUMENT;
+    dbh_trainer& t = *trainer;
+    DBH_TRAINER_HIP(hipMemcpyAsync(t.x_in, x_host, (size_t)n_windows * t.input_size * sizeof(float),
+                                   hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(hipMemcpyAsync(t.labels, labels_host, (size_t)n_windows * sizeof(int32_t),
+                                   hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(t.queue_step(t.x_in, t.labels, n_windows, t.loss, (int64_t*)(t.loss + 1), 0));
+    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    struct { double loss; int64_t correct; } out;
+    DBH_TRAINER_HIP(hipMemcpy(&out, t.loss, sizeof(out), hipMemcpyDeviceToHost));
+    *mean_loss = out.loss;
+    *n_correct = out.correct;
+    return DBH_OK;
+}
+
+int dbh_trainer_get_weights(dbh_trainer* trainer, float* weights_host, int64_t n_floats) {
+    if (!trainer || !weights_host) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_floats != trainer->n_floats) return DBH_ERR_BAD_WEIGHTS;
+    DBH_TRAINER_HIP(hipDeviceSynchronize());
+    DBH_TRAINER_HIP(hipMemcpy(weights_host, trainer->weights, trainer->blob_bytes(), hipMemcpyDeviceToHost));
+    return DBH_OK;
+}
+
+int dbh_trainer_get_state(dbh_trainer* trainer, float* m_host, float* v_host, int64_t n_floats,
+                          int64_t* iterations, double* m_schedule) {
+    if (!trainer || !m_host || !v_host || !iterations || !m_schedule) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_floats != trainer->n_floats) return DBH_ERR_BAD_WEIGHTS;
+    DBH_TRAINER_HIP(hipDeviceSynchronize());
+    DBH_TRAINER_HIP(hipMemcpy(m_host, trainer->m, trainer->blob_bytes(), hipMemcpyDeviceToHost));
+    DBH_TRAINER_HIP(hipMemcpy(v_host, trainer->v, trainer->blob_bytes(), hipMemcpyDeviceToHost));
+    *iterations = trainer->iterations;
+    *m_schedule = trainer->m_schedule;
+    return DBH_OK;
+}
+
+int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float* v_host,
+                          int64_t n_floats, int64_t iterations, double m_schedule) {
+    if (!trainer || !m_host || !v_host || iterations < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_floats != trainer->n_floats) return DBH_ERR_BAD_WEIGHTS;
+    DBH_TRAINER_HIP(hipDeviceSynchronize());
+    DBH_TRAINER_HIP(hipMemcpy(trainer->m, m_host, trainer->blob_bytes(), hipMemcpyHostToDevice));
+    DBH_TRAINER_HIP(hipMemcpy(trainer->v, v_host, trainer->blob_bytes(), hipMemcpyHostToDevice));
+    trainer->iterations = iterations;
+    trainer->m_schedule = m_schedule;
+    return DBH_OK;
+}
+
+int dbh_trainer_iterations(dbh_trainer* trainer, int64_t* iterations) {
+    if (!trainer || !iterations) return DBH_ERR_INVALID_ARGUMENT;
+    *iterations = trainer->iterations;
+    return DBH_OK;
+}
+
+}  // extern "C"

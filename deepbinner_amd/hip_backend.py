@@ -48,6 +48,21 @@ def _f32(flags='C_CONTIGUOUS'):
     return ndpointer(dtype=np.float32, flags=flags)
 
 
+class TrainerOptions(ctypes.Structure):
+    """dbh_trainer_options"""
+    _fields_ = [(name, ctypes.c_double) for name in
+                ('lr', 'beta_1', 'beta_2', 'epsilon', 'schedule_decay', 'bn_momentum')] + [
+                    ('dropout_rate', ctypes.c_float), ('noise_std', ctypes.c_float),
+                    ('seed', ctypes.c_uint64)]
+
+
+class NadamCoefficients(ctypes.Structure):
+    """dbh_nadam_coefficients"""
+    _fields_ = [(name, ctypes.c_double) for name in
+                ('lr', 'beta_1', 'beta_2', 'epsilon', 'mu_t', 'mu_t1', 'sched_new', 'sched_next',
+                 'beta_2_t', 'bn_momentum')]
+
+
 def load_library():
     """Load (once) and type the shared library.  Raises HipBackendError if it is not built."""
     global _lib
@@ -168,6 +183,29 @@ def load_library():
         'dbh_gradients_dev': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_i64,
                                       ctypes.c_float, ctypes.c_uint64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+        'dbh_trainer_default_options': (c_int, [P(TrainerOptions)]),
+        'dbh_nadam_schedule': (c_int, [c_i64, ctypes.c_double, P(TrainerOptions),
+                                       P(NadamCoefficients)]),
+        'dbh_train_noise': (c_int, [_f32(), c_i64, c_int, ctypes.c_float, ctypes.c_uint64, _f32()]),
+        'dbh_train_noise_dev': (c_int, [c_void_p, c_i64, c_int, ctypes.c_float, ctypes.c_uint64,
+                                        c_void_p, c_void_p]),
+        'dbh_nadam_update': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int,
+                                     P(NadamCoefficients)]),
+        'dbh_nadam_update_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                         c_int, P(NadamCoefficients), c_void_p]),
+        'dbh_trainer_create': (c_int, [c_void_p, c_i64, c_int, c_int, c_i64, P(TrainerOptions),
+                                       P(c_void_p)]),
+        'dbh_trainer_destroy': (c_int, [c_void_p]),
+        'dbh_trainer_step': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, P(ctypes.c_double),
+                                     P(c_i64)]),
+        'dbh_trainer_step_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                         c_void_p]),
+        'dbh_trainer_get_weights': (c_int, [c_void_p, _f32(), c_i64]),
+        'dbh_trainer_get_state': (c_int, [c_void_p, _f32(), _f32(), c_i64, P(c_i64),
+                                          P(ctypes.c_double)]),
+        'dbh_trainer_set_state': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64,
+                                          ctypes.c_double]),
+        'dbh_trainer_iterations': (c_int, [c_void_p, P(c_i64)]),
         'dbh_comm_available': (c_int, []),
         'dbh_comm_last_error': (ctypes.c_char_p, []),
         'dbh_comm_init_all': (c_int, [c_int, P(c_int), c_int, P(c_void_p)]),
@@ -207,6 +245,10 @@ EXPORTED_SYMBOLS = [
     'dbh_forward_timing_read', 'dbh_forward_clock_enable', 'dbh_forward_clock_read', 'dbh_forward_phases_enable', 'dbh_forward_phases_read',
     'dbh_forward_phases_count',
     'dbh_gradients_max_windows', 'dbh_gradients_workspace_bytes', 'dbh_gradients', 'dbh_gradients_dev',
+    'dbh_trainer_default_options', 'dbh_nadam_schedule', 'dbh_train_noise', 'dbh_train_noise_dev',
+    'dbh_nadam_update', 'dbh_nadam_update_dev', 'dbh_trainer_create', 'dbh_trainer_destroy',
+    'dbh_trainer_step', 'dbh_trainer_step_dev', 'dbh_trainer_get_weights', 'dbh_trainer_get_state',
+    'dbh_trainer_set_state', 'dbh_trainer_iterations',
     'dbh_comm_available', 'dbh_comm_last_error', 'dbh_comm_init_all', 'dbh_comm_unique_id',
     'dbh_comm_init_rank', 'dbh_comm_info', 'dbh_comm_all_gather_i32', 'dbh_comm_destroy',
 ]
@@ -790,6 +832,197 @@ def gradients_dev(weights_ptr, n_floats, n_classes, input_size, x_ptr, labels_pt
                                            float(dropout_rate), int(seed) & (2 ** 64 - 1), loss_ptr,
                                            correct_ptr, grads_ptr, stats_ptr, workspace_ptr, stream),
           'dbh_gradients_dev')
+
+
+# ---- the resident trainer (include/deepbinner_hip.h, "a resident trainer") --
+# Nadam as Keras 2.1.4 configures it for optimizer='nadam' (reference train_network.py:53-55; the
+# shipped model files' training_config records lr, beta_1 and beta_2 as fp32 values), Keras's
+# BatchNormalization momentum, and the network's own Dropout(0.15) and GaussianNoise(0.02)
+# (network_architecture.py:25,31).  These are what Trainer passes unless told otherwise.
+TRAINER_DEFAULTS = {
+    'lr': float(np.float32(0.002)), 'beta_1': float(np.float32(0.9)),
+    'beta_2': float(np.float32(0.999)), 'epsilon': 1e-7, 'schedule_decay': 0.004,
+    'bn_momentum': 0.99, 'dropout_rate': 0.15, 'noise_std': 0.02, 'seed': 0,
+}
+STEP_SEED_STRIDE = 0x9E3779B97F4A7C15
+
+
+def trainer_options(**options):
+    """A TrainerOptions struct: TRAINER_DEFAULTS with ``options`` over them."""
+    unknown = sorted(set(options) - set(TRAINER_DEFAULTS))
+    if unknown:
+        raise TypeError('unknown trainer option(s): {}'.format(', '.join(unknown)))
+    merged = dict(TRAINER_DEFAULTS, **options)
+    merged['seed'] = int(merged['seed']) & (2 ** 64 - 1)
+    return TrainerOptions(**merged)
+
+
+def library_trainer_defaults():
+    """The defaults the library itself uses for a null options pointer, as a dict."""
+    o = TrainerOptions()
+    check(load_library().dbh_trainer_default_options(ctypes.byref(o)), 'dbh_trainer_default_options')
+    return {name: getattr(o, name) for name, _ in TrainerOptions._fields_}
+
+
+def step_seed(seed, t0):
+    """The seed of the step behind ``t0`` steps: noise and dropout of that step hash it."""
+    return (int(seed) + int(t0) * STEP_SEED_STRIDE) & (2 ** 64 - 1)
+
+
+def nadam_schedule(t0, m_schedule=1.0, **options):
+    """dbh_nadam_schedule (host only): the coefficients of step ``t0`` as a dict; its 'sched_new' is
+    the m_schedule of the step after."""
+    k = NadamCoefficients()
+    o = trainer_options(**options)
+    check(load_library().dbh_nadam_schedule(int(t0), float(m_schedule), ctypes.byref(o),
+                                            ctypes.byref(k)), 'dbh_nadam_schedule')
+    return {name: getattr(k, name) for name, _ in NadamCoefficients._fields_}
+
+
+def train_noise(x, noise_std, seed):
+    """dbh_train_noise: ``x`` [N, input_size] plus the step's Gaussian noise, a new fp32 array."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError('expected windows of shape (N, input_size)')
+    out = np.empty_like(x)
+    check(load_library().dbh_train_noise(x, x.shape[0], x.shape[1], float(noise_std),
+                                         int(seed) & (2 ** 64 - 1), out), 'dbh_train_noise')
+    return out
+
+
+def nadam_update(params, grads, m, v, batch_stats, n_classes, coefficients):
+    """dbh_nadam_update on copies: returns the new ``(params, m, v)``; ``coefficients`` as
+    nadam_schedule() gives them."""
+    params, m, v = (np.array(a, dtype=np.float32, order='C').ravel() for a in (params, m, v))
+    grads = np.ascontiguousarray(grads, dtype=np.float32).ravel()
+    batch_stats = np.ascontiguousarray(batch_stats, dtype=np.float32).ravel()
+    if not (grads.size == m.size == v.size == params.size) or batch_stats.size != BATCH_STATS_FLOATS:
+        raise ValueError('params, grads, m and v must have one size, batch_stats {} floats'
+                         .format(BATCH_STATS_FLOATS))
+    k = NadamCoefficients(**coefficients)
+    check(load_library().dbh_nadam_update(params.ctypes.data, grads.ctypes.data, m.ctypes.data,
+                                          v.ctypes.data, batch_stats.ctypes.data, params.size,
+                                          int(n_classes), ctypes.byref(k)), 'dbh_nadam_update')
+    return params, m, v
+
+
+class Trainer:
+    """A model in training, resident on one MI355X: weights, Nadam's m and v, gradients and batch
+    statistics stay on the device between steps.  ``options``: TRAINER_DEFAULTS' names."""
+
+    def __init__(self, weights, max_windows, device=None, **options):
+        if not isinstance(weights, ModelWeights):
+            raise TypeError('weights must be a ModelWeights')
+        self._lib = load_library()
+        self._handle = None
+        self.options = dict(TRAINER_DEFAULTS, **options)
+        struct = trainer_options(**options)
+        if device is not None:
+            set_device(device)
+        self.n_classes, self.input_size = weights.n_classes, weights.input_size
+        self.max_windows = int(max_windows)
+        flat = weights.flat()
+        self.n_floats = flat.size
+        handle = ctypes.c_void_p()
+        check(self._lib.dbh_trainer_create(flat.ctypes.data, flat.size, self.n_classes,
+                                           self.input_size, self.max_windows, ctypes.byref(struct),
+                                           ctypes.byref(handle)), 'dbh_trainer_create')
+        self._handle = handle
+
+    def close(self):
+        if self._handle:
+            self._lib.dbh_trainer_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, x, labels):
+        """One training step on the windows ``x`` [N, input_size] (normalised, without noise) and
+        ``labels`` [N]: returns (mean loss, windows called right) of the batch before the update."""
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1, self.input_size))
+        labels = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.int32))
+        if labels.size != x.shape[0]:
+            raise ValueError('{} labels for {} windows'.format(labels.size, x.shape[0]))
+        loss, correct = ctypes.c_double(0), ctypes.c_int64(0)
+        check(self._lib.dbh_trainer_step(self._handle, x.ctypes.data, labels.ctypes.data, x.shape[0],
+                                         ctypes.byref(loss), ctypes.byref(correct)),
+              'dbh_trainer_step')
+        return loss.value, int(correct.value)
+
+    def step_dev(self, x_ptr, labels_ptr, n_windows, loss_ptr, correct_ptr, stream=None):
+        """dbh_trainer_step_dev on device pointers; queued, not synchronised."""
+        check(self._lib.dbh_trainer_step_dev(self._handle, x_ptr, labels_ptr, int(n_windows),
+                                             loss_ptr, correct_ptr, stream), 'dbh_trainer_step_dev')
+
+    def weights(self):
+        flat = np.empty(self.n_floats, dtype=np.float32)
+        check(self._lib.dbh_trainer_get_weights(self._handle, flat, flat.size),
+              'dbh_trainer_get_weights')
+        return ModelWeights.from_flat(flat, self.n_classes, self.input_size)
+
+    def state(self):
+        """Nadam's state: {'m', 'v' (flat fp32, the blob's layout), 'iterations', 'm_schedule'}."""
+        m = np.empty(self.n_floats, dtype=np.float32)
+        v = np.empty(self.n_floats, dtype=np.float32)
+        iterations, schedule = ctypes.c_int64(0), ctypes.c_double(0)
+        check(self._lib.dbh_trainer_get_state(self._handle, m, v, m.size, ctypes.byref(iterations),
+                                              ctypes.byref(schedule)), 'dbh_trainer_get_state')
+        return {'m': m, 'v': v, 'iterations': int(iterations.value), 'm_schedule': schedule.value}
+
+    def load_state(self, state):
+        m = np.ascontiguousarray(state['m'], dtype=np.float32).ravel()
+        v = np.ascontiguousarray(state['v'], dtype=np.float32).ravel()
+        if m.size != self.n_floats or v.size != self.n_floats:
+            raise ValueError('m and v must have {} floats'.format(self.n_floats))
+        check(self._lib.dbh_trainer_set_state(self._handle, m.ctypes.data, v.ctypes.data, m.size,
+                                              int(state['iterations']), float(state['m_schedule'])),
+              'dbh_trainer_set_state')
+
+    @property
+    def iterations(self):
+        n = ctypes.c_int64(0)
+        check(self._lib.dbh_trainer_iterations(self._handle, ctypes.byref(n)),
+              'dbh_trainer_iterations')
+        return int(n.value)
+
+    # -- checkpoints: the weights as a model file `classify` loads as it is, the rest beside it ----
+    @staticmethod
+    def state_path(path):
+        return str(path) + '.state.npz'
+
+    def save_checkpoint(self, path):
+        self.weights().save(path)
+        options = {'option_' + name: np.asarray(value, dtype=np.float64)
+                   for name, value in self.options.items() if name != 'seed'}
+        options['option_seed'] = np.asarray(int(self.options['seed']) & (2 ** 64 - 1), dtype=np.uint64)
+        state = self.state()
+        with open(self.state_path(path), 'wb') as f:
+            np.savez(f, m=state['m'], v=state['v'],
+                     iterations=np.asarray(state['iterations'], dtype=np.int64),
+                     m_schedule=np.asarray(state['m_schedule'], dtype=np.float64), **options)
+
+    @classmethod
+    def from_checkpoint(cls, path, max_windows, device=None, **options):
+        """The trainer save_checkpoint wrote, with its options unless ``options`` names others."""
+        weights, _ = ModelWeights.load(path)
+        with np.load(cls.state_path(path)) as z:
+            saved = {name[len('option_'):]: (int(z[name]) if name == 'option_seed' else float(z[name]))
+                     for name in z.files if name.startswith('option_')}
+            state = {'m': z['m'], 'v': z['v'], 'iterations': int(z['iterations']),
+                     'm_schedule': float(z['m_schedule'])}
+        trainer = cls(weights, max_windows, device=device, **dict(saved, **options))
+        trainer.load_state(state)
+        return trainer
 
 
 def forward_executed_mfmas(n_classes):

@@ -119,6 +119,24 @@ class ModelWeights:
             pos += 4 * c
         return cls(n_classes, convs, bns, input_size)
 
+    @classmethod
+    def fresh(cls, n_classes, input_size=INPUT_SIZE, seed=0):
+        """An untrained model as ``build_network`` makes it (reference train_network.py:46-48) under
+        Keras's defaults: kernels glorot_uniform - uniform within +-sqrt(6 / (k C_in + k C_out)) -
+        biases 0, batch normalisation gamma 1, beta 0, moving mean 0, moving variance 1.  NumPy's
+        generator on the host: the same ``seed`` gives the same model, not Keras's draws."""
+        rng = np.random.default_rng(seed)
+        convs = []
+        for _, k, cin, cout, _, _ in conv_shapes(n_classes):
+            limit = np.float32(np.sqrt(6.0 / (k * cin + k * cout)))
+            if float(limit) > np.sqrt(6.0 / (k * cin + k * cout)):
+                limit = np.nextafter(limit, np.float32(0))
+            kernel = rng.uniform(-float(limit), float(limit), size=(k, cin, cout)).astype('<f4')
+            convs.append((np.clip(kernel, -limit, limit), np.zeros(cout, dtype='<f4')))
+        bns = [(np.ones(c, dtype='<f4'), np.zeros(c, dtype='<f4'), np.zeros(c, dtype='<f4'),
+                np.ones(c, dtype='<f4')) for c in BN_CHANNELS]
+        return cls(n_classes, convs, bns, input_size)
+
     # -- .dbw container ----------------------------------------------------------------------
     def save(self, path):
         flat = self.flat()

@@ -386,11 +386,11 @@ int dbh_merge_calls_dev(const float* window_probs_dev, int64_t n_reads, int step
  * network_architecture.py:18-95, with categorical cross-entropy; train_network.py:66-68 runs
  * fit_generator on batches of deepbinner.py:265's default 20 windows): the network in Keras's
  * TRAINING phase, the loss, and the gradient of the mean loss with respect to every trainable
- * parameter.  The optimiser (Nadam), the moving averages, the data generator and the `train`
- * command are not here.  Any geometry dbh_model_create_ex takes; no model handle: the weights
+ * parameter.  The noise, the optimiser (Nadam) and the moving averages are the next section's; the
+ * data generator and the `train` command are not built.  Any geometry dbh_model_create_ex takes; no model handle: the weights
  * change every step and are read where they lie.
  *   x        n_windows x input_size fp32, already normalised.  The GaussianNoise(0.02) layer
- *            (network_architecture.py:26) is the CALLER's to add to x; this call adds none.
+ *            (network_architecture.py:25) is the CALLER's to add to x (dbh_train_noise); this call adds none.
  *   labels   n_windows class numbers in [0, n_classes).
  *   batch normalisation (network_architecture.py:30,39,50,58,73,79,87): batch statistics per channel
  *            over all n_windows x length positions of THIS call (biased variance, epsilon 1e-3,
@@ -439,6 +439,119 @@ int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes,
                       float dropout_rate, uint64_t seed, double* mean_loss_dev,
                       int64_t* n_correct_dev, float* grads_dev, float* batch_stats_dev,
                       void* workspace_dev, dbh_stream stream);
+
+/* ---- training: a resident trainer (noise, Nadam, moving statistics) ---------------------------- */
+/* The second half of the reference's training step, and a trainer that keeps a model's training
+ * state on the device: train_network.py:53-55 compiles the network with optimizer='nadam' under
+ * Keras 2.1.4 (the version the shipped model files record), network_architecture.py:25 puts
+ * GaussianNoise(0.02) in front of conv1d_1.  DESIGN.md section 18.  Not here: the data generator
+ * with its modify_signal augmentation, validation and checkpoint policy, a `train` command.
+ *
+ * Defaults (dbh_trainer_default_options): Nadam's configuration as the shipped model files'
+ * training_config attribute records it - lr (float)0.002, beta_1 (float)0.9, beta_2 (float)0.999 as
+ * the doubles of those fp32 values, epsilon 1e-7, schedule_decay 0.004 - bn_momentum 0.99 (Keras's
+ * BatchNormalization default), dropout_rate 0.15, noise_std 0.02, seed 0.
+ *
+ * One step of a trainer, t0 = the steps already taken (iterations):
+ *   step_seed = seed + t0 * 0x9E3779B97F4A7C15 (mod 2^64)
+ *   noise     dbh_train_noise(x, noise_std, step_seed): stateless, dbh_gradients' hash with the
+ *             free layer number 0.  For sample (window, position), with lo/hi the halves of the seed:
+ *                 b1 = bits(lo, hi, layer 0, window, position, channel 0)       24 bits each
+ *                 b2 = bits(lo, hi, layer 0, window, position, channel 1)
+ *                 u1 = (b1 + 1) / 2^24;  u2 = b2 / 2^24;  z = sqrt(-2 ln u1) * cos((2 pi) u2)
+ *                 x' = (float)((double)x + (double)noise_std * z)
+ *             in fp64, rounded once: |z| <= sqrt(2 ln 2^24) = 5.77.  noise_std == 0 returns x bit
+ *             for bit, no arithmetic done.
+ *   gradient  dbh_gradients on x' with dropout_rate and step_seed as its seed.  mean_loss and
+ *             n_correct are those of the batch BEFORE the update, as Keras reports them.
+ *   update    dbh_nadam_update with the coefficients dbh_nadam_schedule(t0, m_schedule) gives:
+ *             one pass over the blob, each element from its own index alone, no atomics.
+ *             Keras 2.1.4 Nadam.get_updates; on the host, in double:
+ *                 t = t0 + 1
+ *                 mu_t  = beta_1 * (1 - 0.5 * 0.96^(t * schedule_decay))
+ *                 mu_t1 = beta_1 * (1 - 0.5 * 0.96^((t + 1) * schedule_decay))
+ *                 sched_new = m_schedule * mu_t;  sched_next = sched_new * mu_t1;  beta_2_t = beta_2^t
+ *             (m_schedule starts at 1 and becomes sched_new), and per trainable element, in fp64 from
+ *             the fp32 p, g, m, v, every operation a separate IEEE operation in this order:
+ *                 g' = g / (1 - sched_new)
+ *                 m  = beta_1 * m + (1 - beta_1) * g;      m' = m / (1 - sched_next)
+ *                 v  = beta_2 * v + (1 - beta_2) * (g * g);  v' = v / (1 - beta_2_t)
+ *                 p  = p - (lr * ((1 - mu_t) * g' + mu_t1 * m')) / (sqrt(v') + epsilon)
+ *             m, v and p are rounded to fp32 once each, where they are stored.  Keras does this in
+ *             fp32; fp64 is a deliberate difference (like the unclipped loss): a host can replay it
+ *             bit for bit.  Per moving-mean and moving-variance element, Keras 2.1.4's
+ *             BatchNormalization:
+ *                 new = (float)(old - (old - batch) * (1 - bn_momentum))        in fp64
+ *             with batch the fp32 value of dbh_gradients' batch_stats: the BIASED batch variance,
+ *             which is what 2.1.4 averages.  Later versions of Keras scale the batch variance by
+ *             n / (n - 1 - eps) first; this library does not.  Those elements' m and v are not
+ *             touched (they stay zero), and the trainable elements do not read batch_stats.
+ * The same state, options and batches give the same bits, also across dbh_trainer_get_state /
+ * dbh_trainer_set_state. */
+typedef struct dbh_trainer dbh_trainer;
+typedef struct dbh_trainer_options {
+    double lr, beta_1, beta_2, epsilon, schedule_decay, bn_momentum;
+    float dropout_rate, noise_std;
+    uint64_t seed;
+} dbh_trainer_options;
+typedef struct dbh_nadam_coefficients {
+    double lr, beta_1, beta_2, epsilon, mu_t, mu_t1, sched_new, sched_next, beta_2_t, bn_momentum;
+} dbh_nadam_coefficients;
+int dbh_trainer_default_options(dbh_trainer_options* options);
+/* Host only, no device: the coefficients of step t0 (>= 0) from the m_schedule before it; hyper
+ * null = the defaults.  After the step m_schedule is coefficients->sched_new. */
+int dbh_nadam_schedule(int64_t t0, double m_schedule, const dbh_trainer_options* hyper,
+                       dbh_nadam_coefficients* coefficients);
+/* out = x + noise (see above); n_windows * input_size <= 2^20 samples, input_size <= 16,384 (more:
+ * DBH_ERR_UNSUPPORTED); noise_std < 0 or not a number, a null pointer, a count < 1:
+ * DBH_ERR_INVALID_ARGUMENT.  Host pointers, blocks; _dev: device pointers (out_dev may be x_dev),
+ * queued on `stream`, not synchronised. */
+int dbh_train_noise(const float* x_host, int64_t n_windows, int input_size, float noise_std,
+                    uint64_t seed, float* out_host);
+int dbh_train_noise_dev(const float* x_dev, int64_t n_windows, int input_size, float noise_std,
+                        uint64_t seed, float* out_dev, dbh_stream stream);
+/* One update in place: params, m, v (n_floats each, the blob's layout) from grads (n_floats) and
+ * batch_stats (960 floats, dbh_gradients' layout).  n_classes outside [2, 256]:
+ * DBH_ERR_UNSUPPORTED; n_floats not the parameter count: DBH_ERR_BAD_WEIGHTS; a null pointer or
+ * bn_momentum outside [0, 1]: DBH_ERR_INVALID_ARGUMENT.  Host pointers: blocks, and the caller's
+ * arrays are written only once the whole call has succeeded.  _dev: queued, not synchronised. */
+int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host, float* v_host,
+                     const float* batch_stats_host, int64_t n_floats, int n_classes,
+                     const dbh_nadam_coefficients* coefficients);
+int dbh_nadam_update_dev(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev,
+                         const float* batch_stats_dev, int64_t n_floats, int n_classes,
+                         const dbh_nadam_coefficients* coefficients, dbh_stream stream);
+/* A trainer owns, on the current device: the weights blob, m and v (zeros), the gradient blob, the
+ * batch statistics, dbh_gradients' workspace for max_windows windows, and staging for the windows
+ * and labels of a batch.  options null = the defaults.  Errors, all before any device work, nothing
+ * written: geometry outside the limits, max_windows (or a step's n_windows) over
+ * dbh_gradients_max_windows, n_windows > max_windows: DBH_ERR_UNSUPPORTED; n_floats not the
+ * parameter count: DBH_ERR_BAD_WEIGHTS; a count < 1, dropout_rate outside [0, 1), noise_std < 0,
+ * bn_momentum outside [0, 1], a null pointer, (host entry) a label outside [0, n_classes):
+ * DBH_ERR_INVALID_ARGUMENT. */
+int dbh_trainer_create(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                       int64_t max_windows, const dbh_trainer_options* options,
+                       dbh_trainer** trainer);
+int dbh_trainer_destroy(dbh_trainer* trainer);        /* null is fine */
+/* One step on host arrays; blocks until the step is done and mean_loss, n_correct are written. */
+int dbh_trainer_step(dbh_trainer* trainer, const float* x_host, const int32_t* labels_host,
+                     int64_t n_windows, double* mean_loss, int64_t* n_correct);
+/* The same on device arrays, queued on `stream` and never synchronised: a loop of steps keeps the
+ * device busy.  The trainer's buffers serve one step at a time: queue a trainer's steps on one
+ * stream (or order the streams).  A label outside [0, n_classes) makes mean_loss NaN (and the
+ * weights with it).  x_dev is not changed. */
+int dbh_trainer_step_dev(dbh_trainer* trainer, const float* x_dev, const int32_t* labels_dev,
+                         int64_t n_windows, double* mean_loss_dev, int64_t* n_correct_dev,
+                         dbh_stream stream);
+/* These wait for the device, then copy.  A state is m, v, the step count and m_schedule; a new
+ * trainer created from dbh_trainer_get_weights' blob with the same options and given that state
+ * continues bit for bit. */
+int dbh_trainer_get_weights(dbh_trainer* trainer, float* weights_host, int64_t n_floats);
+int dbh_trainer_get_state(dbh_trainer* trainer, float* m_host, float* v_host, int64_t n_floats,
+                          int64_t* iterations, double* m_schedule);
+int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float* v_host,
+                          int64_t n_floats, int64_t iterations, double m_schedule);
+int dbh_trainer_iterations(dbh_trainer* trainer, int64_t* iterations);
 
 /* ---- introspection ------------------------------------------------------------------------ */
 /* Activations after stage 'A'..'G'  for n_windows windows, row-major
