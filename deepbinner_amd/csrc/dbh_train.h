@@ -64,6 +64,14 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
                      double* mean_loss, int64_t* n_correct, float* grads, float* stats,
                      void* workspace, hipStream_t stream);
 
+// The same forward pass in Keras's test phase: the blob's moving statistics in place of the batch's,
+// no dropout, nothing written to the weights.  Queued, not synchronised.  The losses are ADDED, in
+// window order, to *loss_sum, the hits to *n_correct (zero them in front of a set's first chunk);
+// window_loss (n_windows doubles) may be null.  The workspace is workspace_bytes()'.
+hipError_t evaluate(const float* weights, int n_classes, int input_size, const float* x,
+                    const int32_t* labels, int64_t n_windows, double* loss_sum, int64_t* n_correct,
+                    double* window_loss, void* workspace, hipStream_t stream);
+
 // dbh_api.hip: keeps the text for dbh_last_error() and maps the error to a dbh_status
 int report_hip_error(hipError_t e, const char* what);
 

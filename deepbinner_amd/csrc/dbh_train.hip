@@ -595,6 +595,34 @@ __global__ void finish_loss(const double* __restrict__ loss, const int* __restri
     *n_correct = k;
 }
 
+// ---- inference phase (evaluate) ---------------------------------------------------------------------
+// mean and 1 / std of a batch normalisation from the blob's moving statistics, as finish_var forms
+// 1 / std from a batch variance
+__global__ void moving_stats(const float* __restrict__ moving_mean,
+                             const float* __restrict__ moving_var, int C,
+                             double* __restrict__ mean, double* __restrict__ istd) {
+    const int c = threadIdx.x;
+    if (c >= C) return;
+    mean[c] = (double)moving_mean[c];
+    istd[c] = 1.0 / sqrt((double)moving_var[c] + kBnEps);
+}
+
+// running totals over the chunks of a set: the losses added in window order by one thread
+__global__ void add_losses(const double* __restrict__ loss, const int* __restrict__ correct,
+                           long long n_win, double* __restrict__ loss_sum,
+                           long long* __restrict__ n_correct, double* __restrict__ window_loss) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = *loss_sum;
+    long long k = *n_correct;
+    for (long long i = 0; i < n_win; ++i) {
+        s += loss[i];
+        k += correct[i];
+        if (window_loss) window_loss[i] = loss[i];
+    }
+    *loss_sum = s;
+    *n_correct = k;
+}
+
 // conv1d_20's kernel gradient: grid (48 * C / 256, partials), fp64 partials [partial][48][C]
 __global__ __launch_bounds__(kThreads) void head_wgrad(const float* __restrict__ h,
                                                        const float* __restrict__ dz, long long rows,
@@ -693,6 +721,7 @@ struct Run {
     int64_t n;
     Drop drop;
     hipStream_t stream;
+    bool inference = false;    // Keras's test phase: the blob's moving statistics, no dropout
     hipError_t err = hipSuccess;
 
     bool ok() {
@@ -790,19 +819,24 @@ struct Run {
         const int C = kBnChannels[bn];
         const long long rows = (long long)n * len;
         const size_t so = bn_channel_offset(bn);
-        ColArgs ca = {};
-        ca.a = x; ca.rows = rows; ca.C = C; ca.stride = C; ca.off = 0;
-        const unsigned parts = col_launch(ca);
-        hipLaunchKernelGGL((col_sums<kColSum>), dim3(parts), dim3(kThreads), 0, stream, ca);
-        hipLaunchKernelGGL(finish_mean, dim3(1), dim3(kThreads), 0, stream, (const double*)b.part,
-                           (int)parts, C, (double)rows, b.mean + so);
-        ca.mean = b.mean + so;
-        hipLaunchKernelGGL((col_sums<kColVar>), dim3(parts), dim3(kThreads), 0, stream, ca);
-        hipLaunchKernelGGL(finish_var, dim3(1), dim3(kThreads), 0, stream, (const double*)b.part,
-                           (int)parts, C, (double)rows, (const double*)(b.mean + so), b.istd + so,
-                           stats + 2 * so);
-        if (!ok()) return;
         const float* gamma = w + blob_bn(bn, g.C);
+        if (inference) {
+            hipLaunchKernelGGL(moving_stats, dim3(1), dim3(kThreads), 0, stream, gamma + 2 * C,
+                               gamma + 3 * C, C, b.mean + so, b.istd + so);
+        } else {
+            ColArgs ca = {};
+            ca.a = x; ca.rows = rows; ca.C = C; ca.stride = C; ca.off = 0;
+            const unsigned parts = col_launch(ca);
+            hipLaunchKernelGGL((col_sums<kColSum>), dim3(parts), dim3(kThreads), 0, stream, ca);
+            hipLaunchKernelGGL(finish_mean, dim3(1), dim3(kThreads), 0, stream, (const double*)b.part,
+                               (int)parts, C, (double)rows, b.mean + so);
+            ca.mean = b.mean + so;
+            hipLaunchKernelGGL((col_sums<kColVar>), dim3(parts), dim3(kThreads), 0, stream, ca);
+            hipLaunchKernelGGL(finish_var, dim3(1), dim3(kThreads), 0, stream, (const double*)b.part,
+                               (int)parts, C, (double)rows, (const double*)(b.mean + so), b.istd + so,
+                               stats + 2 * so);
+        }
+        if (!ok()) return;
         hipLaunchKernelGGL(bn_apply, dim3(blocks_for(rows * C)), dim3(kThreads), 0, stream, x,
                            rows * C, C, len, gamma, gamma + C, (const double*)(b.mean + so),
                            (const double*)(b.istd + so), drop_of(bn), h);
@@ -845,6 +879,57 @@ struct Run {
     }
 };
 
+// The forward pass, from the windows to each window's loss and hit (b.loss, b.correct): the half that
+// gradients() and evaluate() share.  r.inference chooses the phase.
+void forward(Run& r, const float* x, const int32_t* labels) {
+    const Geometry& g = r.g;
+    const Buffers& b = r.b;
+    const int* len = g.len;
+    const int64_t n = r.n;
+    const int C = g.C;
+    if (r.ok())
+        hipLaunchKernelGGL(conv1_forward, dim3(blocks_for(n * len[1] * 48)), dim3(kThreads), 0,
+                           r.stream, x, r.w + blob_kernel(0, g.C), (long long)n, g.L, len[1],
+                           same_pad_left(3, 2, g.L, len[1]), b.a1);
+    r.bn_forward(0, b.a1, len[1], b.h1);
+    r.conv(1, b.h1, len[1], b.a2, len[1]);
+    r.conv(2, b.a2, len[1], b.a3, len[1]);
+    r.conv(3, b.a3, len[1], b.a4, len[1]);
+    r.pool(b.a4, len[1], len[2], 48, b.p4);
+    r.bn_forward(1, b.p4, len[2], b.h2);
+    r.conv(4, b.h2, len[2], b.a5, len[2]);
+    r.conv(5, b.a5, len[2], b.a6, len[2]);
+    r.conv(6, b.a6, len[2], b.a7, len[2]);
+    r.pool(b.a7, len[2], len[3], 48, b.p7);
+    r.bn_forward(2, b.p7, len[3], b.h3);
+    r.conv(7, b.h3, len[3], b.a8, len[3]);
+    r.conv(8, b.a8, len[3], b.a9, len[3]);
+    r.pool(b.a9, len[3], len[4], 48, b.p9);
+    r.bn_forward(3, b.p9, len[4], b.h4);
+    if (r.ok())
+        hipLaunchKernelGGL(avg_forward, dim3(blocks_for(n * len[4] * 48)), dim3(kThreads), 0, r.stream,
+                           (const float*)b.h4, (long long)n, len[4], 48, b.avg);
+    r.conv(9, b.avg, len[4], b.cc, len[4], 192, 0);
+    r.conv(10, b.h4, len[4], b.cc, len[4], 192, 48);
+    r.conv(11, b.h4, len[4], b.a12, len[4]);
+    r.conv(12, b.a12, len[4], b.cc, len[4], 192, 96);
+    r.conv(13, b.h4, len[4], b.a14, len[4]);
+    r.conv(14, b.a14, len[4], b.a15, len[4]);
+    r.conv(15, b.a15, len[4], b.cc, len[4], 192, 144);
+    r.pool(b.cc, len[4], len[5], 192, b.pcc);
+    r.bn_forward(4, b.pcc, len[5], b.h5);
+    r.conv(16, b.h5, len[5], b.a17, len[6]);
+    r.bn_forward(5, b.a17, len[6], b.h6);
+    r.conv(17, b.h6, len[6], b.a18, len[6]);
+    r.conv(18, b.a18, len[6], b.a19, len[6]);
+    r.pool(b.a19, len[6], len[7], 48, b.p19);
+    r.bn_forward(6, b.p19, len[7], b.h7);
+    if (r.ok())
+        hipLaunchKernelGGL(head_forward, dim3((unsigned)n), dim3(kThreads), 0, r.stream,
+                           (const float*)b.h7, len[7], r.w + blob_kernel(19, g.C), r.w + blob_bias(19, g.C),
+                           C, (const int*)labels, 1.0 / (double)n, b.dz20, b.loss, b.correct);
+}
+
 }  // namespace
 
 size_t workspace_bytes(int n_classes, int input_size, int64_t n_windows) {
@@ -877,48 +962,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     // the moving-statistics slots stay zero; everything else is written below
     r.err = hipMemsetAsync(grads, 0, (size_t)dbh_net::param_count(C) * sizeof(float), stream);
 
-    // ---- forward -----------------------------------------------------------------------------
-    if (r.ok())
-        hipLaunchKernelGGL(conv1_forward, dim3(blocks_for(n * len[1] * 48)), dim3(kThreads), 0,
-                           stream, x, weights + blob_kernel(0, g.C), (long long)n, g.L, len[1],
-                           same_pad_left(3, 2, g.L, len[1]), b.a1);
-    r.bn_forward(0, b.a1, len[1], b.h1);
-    r.conv(1, b.h1, len[1], b.a2, len[1]);
-    r.conv(2, b.a2, len[1], b.a3, len[1]);
-    r.conv(3, b.a3, len[1], b.a4, len[1]);
-    r.pool(b.a4, len[1], len[2], 48, b.p4);
-    r.bn_forward(1, b.p4, len[2], b.h2);
-    r.conv(4, b.h2, len[2], b.a5, len[2]);
-    r.conv(5, b.a5, len[2], b.a6, len[2]);
-    r.conv(6, b.a6, len[2], b.a7, len[2]);
-    r.pool(b.a7, len[2], len[3], 48, b.p7);
-    r.bn_forward(2, b.p7, len[3], b.h3);
-    r.conv(7, b.h3, len[3], b.a8, len[3]);
-    r.conv(8, b.a8, len[3], b.a9, len[3]);
-    r.pool(b.a9, len[3], len[4], 48, b.p9);
-    r.bn_forward(3, b.p9, len[4], b.h4);
-    if (r.ok())
-        hipLaunchKernelGGL(avg_forward, dim3(blocks_for(n * len[4] * 48)), dim3(kThreads), 0, stream,
-                           (const float*)b.h4, (long long)n, len[4], 48, b.avg);
-    r.conv(9, b.avg, len[4], b.cc, len[4], 192, 0);
-    r.conv(10, b.h4, len[4], b.cc, len[4], 192, 48);
-    r.conv(11, b.h4, len[4], b.a12, len[4]);
-    r.conv(12, b.a12, len[4], b.cc, len[4], 192, 96);
-    r.conv(13, b.h4, len[4], b.a14, len[4]);
-    r.conv(14, b.a14, len[4], b.a15, len[4]);
-    r.conv(15, b.a15, len[4], b.cc, len[4], 192, 144);
-    r.pool(b.cc, len[4], len[5], 192, b.pcc);
-    r.bn_forward(4, b.pcc, len[5], b.h5);
-    r.conv(16, b.h5, len[5], b.a17, len[6]);
-    r.bn_forward(5, b.a17, len[6], b.h6);
-    r.conv(17, b.h6, len[6], b.a18, len[6]);
-    r.conv(18, b.a18, len[6], b.a19, len[6]);
-    r.pool(b.a19, len[6], len[7], 48, b.p19);
-    r.bn_forward(6, b.p19, len[7], b.h7);
-    if (r.ok())
-        hipLaunchKernelGGL(head_forward, dim3((unsigned)n), dim3(kThreads), 0, stream,
-                           (const float*)b.h7, len[7], weights + blob_kernel(19, g.C), weights + blob_bias(19, g.C),
-                           C, (const int*)labels, 1.0 / (double)n, b.dz20, b.loss, b.correct);
+    forward(r, x, labels);
     if (r.ok())
         hipLaunchKernelGGL(finish_loss, dim3(1), dim3(64), 0, stream, (const double*)b.loss,
                            (const int*)b.correct, (long long)n, mean_loss, (long long*)n_correct);
@@ -993,6 +1037,23 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     return r.err;
 }
 
+hipError_t evaluate(const float* weights, int n_classes, int input_size, const float* x,
+                    const int32_t* labels, int64_t n_windows, double* loss_sum, int64_t* n_correct,
+                    double* window_loss, void* workspace, hipStream_t stream) {
+    const Geometry g(input_size, n_classes);
+    Workspace ws(workspace);
+    const Buffers b(ws, g, n_windows);
+    const Drop keep_all = {0u, 0u, 0u, 0u, 1.f};
+    Run r{g, b, weights, nullptr, nullptr, n_windows, keep_all, stream, true};
+    forward(r, x, labels);
+    if (r.ok())
+        hipLaunchKernelGGL(add_losses, dim3(1), dim3(64), 0, stream, (const double*)b.loss,
+                           (const int*)b.correct, (long long)n_windows, loss_sum,
+                           (long long*)n_correct, window_loss);
+    r.ok();
+    return r.err;
+}
+
 }  // namespace dbh_train
 
 // ---- C ABI (include/deepbinner_hip.h, "training") ------------------------------------------------
@@ -1047,6 +1108,60 @@ int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes,
                                        n_windows, dropout_rate, seed, mean_loss_dev, n_correct_dev,
                                        grads_dev, batch_stats_dev, workspace_dev,
                                        (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_evaluate_dev(const float* weights_dev, int64_t n_floats, int n_classes, int input_size,
+                     const float* x_dev, const int32_t* labels_dev, int64_t n_windows,
+                     double* loss_sum_dev, int64_t* n_correct_dev, double* window_loss_dev,
+                     void* workspace_dev, dbh_stream stream) {
+    const int st = check_arguments(n_floats, n_classes, input_size, n_windows, 0.f);
+    if (st != DBH_OK) return st;
+    if (!weights_dev || !x_dev || !labels_dev || !loss_sum_dev || !n_correct_dev || !workspace_dev ||
+        ((uintptr_t)weights_dev & 15))
+        return DBH_ERR_INVALID_ARGUMENT;
+    DBH_TRAIN_HIP(dbh_train::evaluate(weights_dev, n_classes, input_size, x_dev, labels_dev,
+                                      n_windows, loss_sum_dev, n_correct_dev, window_loss_dev,
+                                      workspace_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_evaluate(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                 const float* x_host, const int32_t* labels_host, int64_t n_windows,
+                 double* loss_sum, int64_t* n_correct, double* window_loss_host) {
+    const int st = check_arguments(n_floats, n_classes, input_size, n_windows, 0.f);
+    if (st != DBH_OK) return st;
+    if (!weights_host || !x_host || !labels_host || !loss_sum || !n_correct)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_windows; ++i)
+        if (labels_host[i] < 0 || labels_host[i] >= n_classes) return DBH_ERR_INVALID_ARGUMENT;
+
+    const size_t w_bytes = (size_t)n_floats * sizeof(float);
+    const size_t x_bytes = (size_t)n_windows * input_size * sizeof(float);
+    const size_t l_bytes = (size_t)n_windows * sizeof(int32_t);
+    const size_t wl_bytes = (size_t)n_windows * sizeof(double);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // one block: weights, windows, labels, the totals, the windows' losses, the workspace
+    const size_t at_x = up(w_bytes), at_l = at_x + up(x_bytes), at_o = at_l + up(l_bytes);
+    const size_t at_wl = at_o + 256, at_w = at_wl + up(wl_bytes);
+    dbh_owned::DeviceBlock block;
+    DBH_TRAIN_HIP(block.reserve(at_w + dbh_train::workspace_bytes(n_classes, input_size, n_windows)));
+    char* d = block.as<char>();
+    DBH_TRAIN_HIP(hipMemcpyAsync(d, weights_host, w_bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAIN_HIP(hipMemcpyAsync(d + at_x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAIN_HIP(hipMemcpyAsync(d + at_l, labels_host, l_bytes, hipMemcpyHostToDevice, 0));
+    DBH_TRAIN_HIP(hipMemsetAsync(d + at_o, 0, 16, 0));
+    DBH_TRAIN_HIP(dbh_train::evaluate((const float*)d, n_classes, input_size,
+                                      (const float*)(d + at_x), (const int32_t*)(d + at_l),
+                                      n_windows, (double*)(d + at_o), (int64_t*)(d + at_o + 8),
+                                      (double*)(d + at_wl), d + at_w, 0));
+    DBH_TRAIN_HIP(hipStreamSynchronize(0));
+    struct { double loss; int64_t correct; } out;
+    DBH_TRAIN_HIP(hipMemcpy(&out, d + at_o, sizeof(out), hipMemcpyDeviceToHost));
+    if (window_loss_host)
+        DBH_TRAIN_HIP(hipMemcpy(window_loss_host, d + at_wl, wl_bytes, hipMemcpyDeviceToHost));
+    *loss_sum = out.loss;
+    *n_correct = out.correct;
     return DBH_OK;
 }
 

@@ -10,6 +10,7 @@
 // IEEE operation it is written as, and NumPy on the host gives the same bits
 // (tests/train_step_reference.py).
 #include "../../include/deepbinner_hip.h"
+#include "dbh_feed.h"
 #include "dbh_general.h"
 #include "dbh_network.h"
 #include "dbh_owned.h"
@@ -169,7 +170,8 @@ size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 }  // namespace
 
 // One block on the device, carved once: the four blobs, the statistics, a batch's windows as given
-// and with their noise, its labels, the loss and the count, dbh_gradients' workspace.
+// and with their noise, its labels, the loss and the count (and an evaluation's totals behind
+// them), dbh_gradients' workspace, a batch's sample indices.
 struct dbh_trainer {
     dbh_trainer_options options;
     int n_classes = 0, input_size = 0;
@@ -180,8 +182,10 @@ struct dbh_trainer {
     float *weights = nullptr, *m = nullptr, *v = nullptr, *grads = nullptr, *stats = nullptr;
     float *x_in = nullptr, *x_noisy = nullptr;
     int32_t* labels = nullptr;
-    double* loss = nullptr;          // the count follows it: int64 at loss + 1
+    double* loss = nullptr;          // the count follows it: int64 at loss + 1; an evaluation's
+                                     // loss sum and count at loss + 2 and loss + 3
     void* workspace = nullptr;
+    int64_t* indices = nullptr;
 
     size_t blob_bytes() const { return (size_t)n_floats * sizeof(float); }
 
@@ -192,8 +196,8 @@ struct dbh_trainer {
         const size_t at_labels = at_x + 2 * x_bytes;
         const size_t at_out = at_labels + up256((size_t)max_windows * sizeof(int32_t));
         const size_t at_work = at_out + 256;
-        const hipError_t e = block.reserve(
-            at_work + dbh_train::workspace_bytes(n_classes, input_size, max_windows));
+        const size_t at_indices = at_work + up256(dbh_train::workspace_bytes(n_classes, input_size, max_windows));
+        const hipError_t e = block.reserve(at_indices + (size_t)max_windows * sizeof(int64_t));
         if (e != hipSuccess) return e;
         weights = block.as<float>(0);
         m = block.as<float>(blob);
@@ -205,6 +209,7 @@ struct dbh_trainer {
         labels = block.as<int32_t>(at_labels);
         loss = block.as<double>(at_out);
         workspace = block.as<char>(at_work);
+        indices = block.as<int64_t>(at_indices);
         return hipSuccess;
     }
 
@@ -231,6 +236,24 @@ struct dbh_trainer {
             m_schedule = k.sched_new;
         }
         return e;
+    }
+
+    // what a data-set entry checks before any device work
+    int check_dataset(const dbh_feed::View* ds, int64_t n_windows, double augmentation,
+                      uint32_t* threshold) const {
+        if (!ds || !dbh_feed::augment_threshold(augmentation, threshold)) return DBH_ERR_INVALID_ARGUMENT;
+        if (ds->input_size != input_size || ds->n_classes != n_classes) return DBH_ERR_UNSUPPORTED;
+        return check_step(n_windows);
+    }
+
+    // augment (into x_in and labels), then the step: one step seed for all of it
+    hipError_t queue_dataset_step(const dbh_feed::View& ds, const int64_t* indices_dev,
+                                  int64_t n_windows, uint32_t threshold, double* mean_loss,
+                                  int64_t* n_correct, hipStream_t stream) {
+        const uint64_t step_seed = options.seed + (uint64_t)iterations * kStepStride;
+        const hipError_t e = dbh_feed::assemble(ds, indices_dev, 0, n_windows, threshold, step_seed,
+                                                x_in, labels, stream);
+        return e == hipSuccess ? queue_step(x_in, labels, n_windows, mean_loss, n_correct, stream) : e;
     }
 };
 
@@ -428,6 +451,76 @@ int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float
 int dbh_trainer_iterations(dbh_trainer* trainer, int64_t* iterations) {
     if (!trainer || !iterations) return DBH_ERR_INVALID_ARGUMENT;
     *iterations = trainer->iterations;
+    return DBH_OK;
+}
+
+int dbh_trainer_step_dataset_dev(dbh_trainer* trainer, const dbh_dataset* ds,
+                                 const int64_t* indices_dev, int64_t n_windows, double augmentation,
+                                 double* mean_loss_dev, int64_t* n_correct_dev, dbh_stream stream) {
+    if (!trainer || !indices_dev || !mean_loss_dev || !n_correct_dev) return DBH_ERR_INVALID_ARGUMENT;
+    uint32_t threshold = 0;
+    const int st = trainer->check_dataset(dbh_dataset_view(ds), n_windows, augmentation, &threshold);
+    if (st != DBH_OK) return st;
+    DBH_TRAINER_HIP(trainer->queue_dataset_step(*dbh_dataset_view(ds), indices_dev, n_windows,
+                                                threshold, mean_loss_dev, n_correct_dev,
+                                                (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_trainer_step_dataset(dbh_trainer* trainer, const dbh_dataset* ds, const int64_t* indices_host,
+                             int64_t n_windows, double augmentation, double* mean_loss,
+                             int64_t* n_correct) {
+    if (!trainer || !indices_host || !mean_loss || !n_correct) return DBH_ERR_INVALID_ARGUMENT;
+    uint32_t threshold = 0;
+    const dbh_feed::View* view = dbh_dataset_view(ds);
+    const int st = trainer->check_dataset(view, n_windows, augmentation, &threshold);
+    if (st != DBH_OK) return st;
+    for (int64_t i = 0; i < n_windows; ++i)
+        if (indices_host[i] < 0 || indices_host[i] >= view->n) return DBH_ERR_INVALID_ARGUMENT;
+    dbh_trainer& t = *trainer;
+    DBH_TRAINER_HIP(hipMemcpyAsync(t.indices, indices_host, (size_t)n_windows * sizeof(int64_t),
+                                   hipMemcpyHostToDevice, 0));
+    DBH_TRAINER_HIP(t.queue_dataset_step(*view, t.indices, n_windows, threshold, t.loss,
+                                         (int64_t*)(t.loss + 1), 0));
+    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    struct { double loss; int64_t correct; } out;
+    DBH_TRAINER_HIP(hipMemcpy(&out, t.loss, sizeof(out), hipMemcpyDeviceToHost));
+    *mean_loss = out.loss;
+    *n_correct = out.correct;
+    return DBH_OK;
+}
+
+int dbh_trainer_evaluate_dataset(dbh_trainer* trainer, const dbh_dataset* ds, int64_t first,
+                                 int64_t count, double* loss_sum, int64_t* n_correct,
+                                 double* window_loss_host) {
+    const dbh_feed::View* view = dbh_dataset_view(ds);
+    if (!trainer || !view || !loss_sum || !n_correct || count < 1 || first < 0 ||
+        first > view->n || count > view->n - first)
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (view->input_size != trainer->input_size || view->n_classes != trainer->n_classes)
+        return DBH_ERR_UNSUPPORTED;
+    dbh_trainer& t = *trainer;
+    dbh_owned::DeviceBlock per_window;
+    if (window_loss_host) DBH_TRAINER_HIP(per_window.reserve((size_t)count * sizeof(double)));
+    double* totals = t.loss + 2;
+    DBH_TRAINER_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(double), 0));
+    // file order, unaugmented (threshold 0), chunk by chunk through the step's own buffers
+    for (int64_t done = 0; done < count; done += t.max_windows) {
+        const int64_t n = count - done < t.max_windows ? count - done : t.max_windows;
+        DBH_TRAINER_HIP(dbh_feed::assemble(*view, nullptr, first + done, n, 0u, 0, t.x_in, t.labels, 0));
+        DBH_TRAINER_HIP(dbh_train::evaluate(t.weights, t.n_classes, t.input_size, t.x_in, t.labels, n,
+                                            totals, (int64_t*)(totals + 1),
+                                            window_loss_host ? per_window.as<double>() + done : nullptr,
+                                            t.workspace, 0));
+    }
+    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    struct { double loss; int64_t correct; } out;
+    DBH_TRAINER_HIP(hipMemcpy(&out, totals, sizeof(out), hipMemcpyDeviceToHost));
+    if (window_loss_host)
+        DBH_TRAINER_HIP(hipMemcpy(window_loss_host, per_window.get(), (size_t)count * sizeof(double),
+                                  hipMemcpyDeviceToHost));
+    *loss_sum = out.loss;
+    *n_correct = out.correct;
     return DBH_OK;
 }
 

@@ -3,9 +3,10 @@ Command line of the classify path: the ``classify`` and ``realtime`` sub-command
 defaults, validation and error messages of the reference's ``deepbinner/deepbinner.py``
 (:90-156 options, :283-345 checks and preset resolution), so that existing command lines keep
 working, plus ``bin`` (:159-176), the consumer of the table ``classify`` writes.  The options are
-declared as data (``OPTIONS``) and turned into argparse calls by one loop.  The reference's
-training-side sub-commands (prep, balance, train, refine) are outside the GPU hot path and answer
-with a one-line refusal.
+declared as data (``OPTIONS``) and turned into argparse calls by one loop.  ``fit`` is the
+reference's ``train`` (:246-269: the same options and defaults, plus ``--seed``) on the resident
+trainer - under another name, because ``train`` and the reference's other training-side
+sub-commands (prep, balance, refine) answer with a one-line refusal.
 """
 
 import argparse
@@ -113,6 +114,29 @@ COMMANDS = {
             [(('--threads',), dict(type=int, default=0,
                                    help='Threads that compress the output (0 = automatic)')),
              _HELP]),
+    'fit': ('Train the neural network (the reference\'s train command)',
+            [('Required', [
+                (('--train',), dict(type=str, required=True,
+                                    help='Balanced training data produced by the balance command')),
+                (('--val',), dict(type=str, required=True,
+                                  help='Validation data used to assess the training')),
+                (('--model_out',), dict(type=str, required=True,
+                                        help='Filename for the trained model'))]),
+             None],
+            [(('--model_in',), dict(type=str,
+                                    help='An existing model to use as a starting point for '
+                                         'training')),
+             (('--epochs',), dict(type=int, default=100, help='Number of training epochs')),
+             (('--aug',), dict(type=float, default=2.0,
+                               help='Data augmentation factor (1 = no augmentation)')),
+             (('--batch_size',), dict(type=int, default=20, help='Training batch size')),
+             (('--batches_per_epoch',), dict(type=int, default=5000,
+                                             help='The number of samples per epoch will be this '
+                                                  'times the batch size')),
+             (('--seed',), dict(type=int, default=0,
+                                help='Seed of the epoch order, augmentation, noise and dropout '
+                                     '(the same seed gives the same model, bit for bit)')),
+             _HELP]),
 }
 USES_MODELS = ('classify', 'realtime')
 
@@ -159,6 +183,8 @@ def main(argv=None):
         from .realtime import realtime as run
     elif args.subparser_name == 'bin':
         from .bin import bin_reads as run
+    elif args.subparser_name == 'fit':
+        from .fit import fit as run
     else:
         return
     run(args)

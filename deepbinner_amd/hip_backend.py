@@ -206,6 +206,24 @@ def load_library():
         'dbh_trainer_set_state': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64,
                                           ctypes.c_double]),
         'dbh_trainer_iterations': (c_int, [c_void_p, P(c_i64)]),
+        'dbh_epoch_order': (c_int, [ctypes.c_uint64, c_i64, c_i64, c_void_p]),
+        'dbh_dataset_create': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_int, P(c_void_p)]),
+        'dbh_dataset_destroy': (c_int, [c_void_p]),
+        'dbh_dataset_count': (c_int, [c_void_p, P(c_i64)]),
+        'dbh_dataset_batch': (c_int, [c_void_p, c_void_p, c_i64, ctypes.c_double, ctypes.c_uint64,
+                                      c_void_p, c_void_p]),
+        'dbh_dataset_batch_dev': (c_int, [c_void_p, c_void_p, c_i64, ctypes.c_double,
+                                          ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
+        'dbh_evaluate': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_i64,
+                                 P(ctypes.c_double), P(c_i64), c_void_p]),
+        'dbh_evaluate_dev': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_i64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        'dbh_trainer_step_dataset': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, ctypes.c_double,
+                                             P(ctypes.c_double), P(c_i64)]),
+        'dbh_trainer_step_dataset_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_i64,
+                                                 ctypes.c_double, c_void_p, c_void_p, c_void_p]),
+        'dbh_trainer_evaluate_dataset': (c_int, [c_void_p, c_void_p, c_i64, c_i64,
+                                                 P(ctypes.c_double), P(c_i64), c_void_p]),
         'dbh_comm_available': (c_int, []),
         'dbh_comm_last_error': (ctypes.c_char_p, []),
         'dbh_comm_init_all': (c_int, [c_int, P(c_int), c_int, P(c_void_p)]),
@@ -249,6 +267,9 @@ EXPORTED_SYMBOLS = [
     'dbh_nadam_update', 'dbh_nadam_update_dev', 'dbh_trainer_create', 'dbh_trainer_destroy',
     'dbh_trainer_step', 'dbh_trainer_step_dev', 'dbh_trainer_get_weights', 'dbh_trainer_get_state',
     'dbh_trainer_set_state', 'dbh_trainer_iterations',
+    'dbh_epoch_order', 'dbh_dataset_create', 'dbh_dataset_destroy', 'dbh_dataset_count',
+    'dbh_dataset_batch', 'dbh_dataset_batch_dev', 'dbh_evaluate', 'dbh_evaluate_dev',
+    'dbh_trainer_step_dataset', 'dbh_trainer_step_dataset_dev', 'dbh_trainer_evaluate_dataset',
     'dbh_comm_available', 'dbh_comm_last_error', 'dbh_comm_init_all', 'dbh_comm_unique_id',
     'dbh_comm_init_rank', 'dbh_comm_info', 'dbh_comm_all_gather_i32', 'dbh_comm_destroy',
 ]
@@ -906,6 +927,159 @@ def nadam_update(params, grads, m, v, batch_stats, n_classes, coefficients):
     return params, m, v
 
 
+# ---- device-fed batches and validation (include/deepbinner_hip.h, "device-fed batches"; DESIGN.md
+# section 19) ------------------------------------------------------------------------------------
+def epoch_order(seed, epoch_pass, n):
+    """dbh_epoch_order (host only): the int64 sample order of pass ``epoch_pass`` over ``n``
+    samples."""
+    order = np.empty(max(int(n), 0), dtype=np.int64)
+    check(load_library().dbh_epoch_order(int(seed) & (2 ** 64 - 1), int(epoch_pass), int(n),
+                                         order.ctypes.data), 'dbh_epoch_order')
+    return order
+
+
+class TrainingDataError(ValueError):
+    pass
+
+
+_DATA_MESSAGES = {'label': 'a non-integer barcode class was encountered in {}',
+                  'line': 'training signal not formatted correctly',
+                  'sizes': 'inconsistent signal sizes in training data'}
+
+
+def read_training_data(path, input_size=None, messages=None):
+    """A training-data text file (``label<TAB>v1,v2,...`` per line) as (int16 samples [n, L],
+    int32 labels [n]), in one pass.  ``input_size`` None: the first line's.  A line that does not
+    fit raises TrainingDataError; values outside int16 name the line, as in ``classify``."""
+    messages = messages or _DATA_MESSAGES
+    labels, rows = [], []
+    with open(path, 'rt') as text:
+        for number, line in enumerate(text, 1):
+            fields = line.strip().split('\t')
+            if len(fields) != 2:
+                raise TrainingDataError(messages['line'])
+            label, values = fields
+            if not label.lstrip('+-').isdigit():
+                raise TrainingDataError(messages['label'].format(path))
+            try:
+                row = np.array(values.split(','), dtype=np.int64)
+            except (ValueError, OverflowError):
+                raise TrainingDataError(messages['line'])
+            if row.size and (row.min() < -32768 or row.max() > 32767):
+                raise TrainingDataError('line {} of {} holds signal values outside the int16 range'
+                                        .format(number, path))
+            input_size = row.size if input_size is None else input_size
+            if row.size != input_size:
+                raise TrainingDataError(messages['sizes'])
+            labels.append(int(label))
+            rows.append(row.astype(np.int16))
+    if not rows:
+        raise TrainingDataError(messages['line'])
+    return np.stack(rows), np.array(labels, dtype=np.int32)
+
+
+class Dataset:
+    """A training-data set resident on the device: the int16 windows as the file holds them, their
+    labels, and each window's mean and standard deviation (dbh_dataset)."""
+
+    def __init__(self, samples, labels, n_classes, device=None):
+        self._lib = load_library()
+        self._handle = None
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        labels = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.int32))
+        if samples.ndim != 2 or labels.size != samples.shape[0]:
+            raise ValueError('expected samples of shape (n, input_size) and n labels')
+        if device is not None:
+            set_device(device)
+        self.input_size, self.n_classes = int(samples.shape[1]), int(n_classes)
+        handle = ctypes.c_void_p()
+        check(self._lib.dbh_dataset_create(samples.ctypes.data, labels.ctypes.data,
+                                           samples.shape[0], self.input_size, self.n_classes,
+                                           ctypes.byref(handle)), 'dbh_dataset_create')
+        self._handle = handle
+
+    @classmethod
+    def from_arrays(cls, samples, labels, n_classes, device=None):
+        return cls(samples, labels, n_classes, device=device)
+
+    @classmethod
+    def from_file(cls, path, n_classes, input_size=None, device=None):
+        samples, labels = read_training_data(path, input_size)
+        return cls(samples, labels, n_classes, device=device)
+
+    @property
+    def handle(self):
+        return self._handle
+
+    def __len__(self):
+        n = ctypes.c_int64(0)
+        check(self._lib.dbh_dataset_count(self._handle, ctypes.byref(n)), 'dbh_dataset_count')
+        return int(n.value)
+
+    def batch(self, indices, augmentation=1.0, seed=0):
+        """dbh_dataset_batch: (x fp32 [N, input_size], labels int32 [N]) for the samples
+        ``indices``, normalised, and augmented as ``seed`` decides per batch slot."""
+        indices = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+        x = np.empty((indices.size, self.input_size), dtype=np.float32)
+        labels = np.empty(indices.size, dtype=np.int32)
+        check(self._lib.dbh_dataset_batch(self._handle, indices.ctypes.data, indices.size,
+                                          float(augmentation), int(seed) & (2 ** 64 - 1),
+                                          x.ctypes.data, labels.ctypes.data), 'dbh_dataset_batch')
+        return x, labels
+
+    def batch_dev(self, indices_ptr, n_windows, augmentation, seed, x_ptr, labels_ptr, stream=None):
+        """dbh_dataset_batch_dev on device pointers; queued, not synchronised."""
+        check(self._lib.dbh_dataset_batch_dev(self._handle, indices_ptr, int(n_windows),
+                                              float(augmentation), int(seed) & (2 ** 64 - 1), x_ptr,
+                                              labels_ptr, stream), 'dbh_dataset_batch_dev')
+
+    def close(self):
+        if self._handle:
+            self._lib.dbh_dataset_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def evaluate(weights, x, labels):
+    """dbh_evaluate: the network in Keras's test phase (moving statistics, no dropout, no noise) on
+    the windows ``x`` [N, input_size]: (loss sum, windows called right, fp64 loss per window)."""
+    lib = load_library()
+    flat = weights.flat()
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1, weights.input_size))
+    labels = np.ascontiguousarray(np.asarray(labels).reshape(-1).astype(np.int32))
+    if labels.size != x.shape[0]:
+        raise ValueError('{} labels for {} windows'.format(labels.size, x.shape[0]))
+    per_window = np.empty(x.shape[0], dtype=np.float64)
+    loss, correct = ctypes.c_double(0), ctypes.c_int64(0)
+    check(lib.dbh_evaluate(flat.ctypes.data, flat.size, weights.n_classes, weights.input_size,
+                           x.ctypes.data, labels.ctypes.data, x.shape[0], ctypes.byref(loss),
+                           ctypes.byref(correct), per_window.ctypes.data), 'dbh_evaluate')
+    return loss.value, int(correct.value), per_window
+
+
+def write_npz(path, arrays):
+    """An uncompressed ``.npz`` that ``np.load`` reads, with the zip members' time stamps fixed:
+    the same arrays give the same bytes (``np.savez`` stamps the time of writing)."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_STORED, allowZip64=True) as z:
+        for name, array in arrays.items():
+            info = zipfile.ZipInfo(name + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.external_attr = 0o600 << 16
+            with z.open(info, 'w', force_zip64=True) as member:
+                np.lib.format.write_array(member, np.asanyarray(array), allow_pickle=False)
+
+
 class Trainer:
     """A model in training, resident on one MI355X: weights, Nadam's m and v, gradients and batch
     statistics stay on the device between steps.  ``options``: TRAINER_DEFAULTS' names."""
@@ -964,6 +1138,58 @@ class Trainer:
         check(self._lib.dbh_trainer_step_dev(self._handle, x_ptr, labels_ptr, int(n_windows),
                                              loss_ptr, correct_ptr, stream), 'dbh_trainer_step_dev')
 
+    def step_dataset(self, dataset, indices, augmentation=1.0):
+        """One step on the samples ``indices`` of a ``Dataset``, assembled on the device with this
+        step's seed (dbh_trainer_step_dataset): (mean loss, windows called right)."""
+        indices = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+        loss, correct = ctypes.c_double(0), ctypes.c_int64(0)
+        check(self._lib.dbh_trainer_step_dataset(self._handle, dataset.handle, indices.ctypes.data,
+                                                 indices.size, float(augmentation),
+                                                 ctypes.byref(loss), ctypes.byref(correct)),
+              'dbh_trainer_step_dataset')
+        return loss.value, int(correct.value)
+
+    def step_dataset_dev(self, dataset, indices_ptr, n_windows, augmentation, loss_ptr, correct_ptr,
+                         stream=None):
+        """dbh_trainer_step_dataset_dev: int64 indices on the device; queued, not synchronised."""
+        check(self._lib.dbh_trainer_step_dataset_dev(self._handle, dataset.handle, indices_ptr,
+                                                     int(n_windows), float(augmentation), loss_ptr,
+                                                     correct_ptr, stream),
+              'dbh_trainer_step_dataset_dev')
+
+    def run_epoch(self, dataset, indices, batch_size, augmentation):
+        """``len(indices) // batch_size`` steps queued without a host synchronisation in between:
+        the indices are uploaded once, every step writes its own loss and count slot, one
+        synchronisation at the end.  -> (mean loss per step fp64, windows right per step int64)."""
+        batch_size = int(batch_size)
+        steps = len(indices) // batch_size
+        indices = np.ascontiguousarray(np.asarray(indices)[:steps * batch_size], dtype=np.int64)
+        on_device = DeviceBuffer.from_array(indices)
+        losses, counts = DeviceBuffer(steps * 8), DeviceBuffer(steps * 8)
+        try:
+            for t in range(steps):
+                self.step_dataset_dev(dataset, on_device.ptr + 8 * batch_size * t, batch_size,
+                                      augmentation, losses.ptr + 8 * t, counts.ptr + 8 * t)
+            synchronize()
+            return losses.download(steps, np.float64), counts.download(steps, np.int64)
+        finally:
+            for buffer in (on_device, losses, counts):
+                buffer.free()
+
+    def evaluate(self, dataset, first=0, count=None, window_losses=False):
+        """The resident weights in Keras's test phase on the samples [first, first + count) of a
+        ``Dataset`` (dbh_trainer_evaluate_dataset): (loss sum, windows called right), and with
+        ``window_losses`` the fp64 loss of each window as a third value."""
+        count = len(dataset) - first if count is None else int(count)
+        per_window = np.empty(count, dtype=np.float64) if window_losses else None
+        loss, correct = ctypes.c_double(0), ctypes.c_int64(0)
+        check(self._lib.dbh_trainer_evaluate_dataset(
+            self._handle, dataset.handle, int(first), count, ctypes.byref(loss),
+            ctypes.byref(correct), per_window.ctypes.data if window_losses else None),
+            'dbh_trainer_evaluate_dataset')
+        result = (loss.value, int(correct.value))
+        return result + (per_window,) if window_losses else result
+
     def weights(self):
         flat = np.empty(self.n_floats, dtype=np.float32)
         check(self._lib.dbh_trainer_get_weights(self._handle, flat, flat.size),
@@ -1006,10 +1232,9 @@ class Trainer:
                    for name, value in self.options.items() if name != 'seed'}
         options['option_seed'] = np.asarray(int(self.options['seed']) & (2 ** 64 - 1), dtype=np.uint64)
         state = self.state()
-        with open(self.state_path(path), 'wb') as f:
-            np.savez(f, m=state['m'], v=state['v'],
-                     iterations=np.asarray(state['iterations'], dtype=np.int64),
-                     m_schedule=np.asarray(state['m_schedule'], dtype=np.float64), **options)
+        write_npz(self.state_path(path), dict(
+            m=state['m'], v=state['v'], iterations=np.asarray(state['iterations'], dtype=np.int64),
+            m_schedule=np.asarray(state['m_schedule'], dtype=np.float64), **options))
 
     @classmethod
     def from_checkpoint(cls, path, max_windows, device=None, **options):

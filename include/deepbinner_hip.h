@@ -387,7 +387,7 @@ int dbh_merge_calls_dev(const float* window_probs_dev, int64_t n_reads, int step
  * fit_generator on batches of deepbinner.py:265's default 20 windows): the network in Keras's
  * TRAINING phase, the loss, and the gradient of the mean loss with respect to every trainable
  * parameter.  The noise, the optimiser (Nadam) and the moving averages are the next section's; the
- * data generator and the `train` command are not built.  Any geometry dbh_model_create_ex takes; no model handle: the weights
+ * data generator, validation and the `fit` command's pieces the one after.  Any geometry dbh_model_create_ex takes; no model handle: the weights
  * change every step and are read where they lie.
  *   x        n_windows x input_size fp32, already normalised.  The GaussianNoise(0.02) layer
  *            (network_architecture.py:25) is the CALLER's to add to x (dbh_train_noise); this call adds none.
@@ -444,8 +444,9 @@ int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes,
 /* The second half of the reference's training step, and a trainer that keeps a model's training
  * state on the device: train_network.py:53-55 compiles the network with optimizer='nadam' under
  * Keras 2.1.4 (the version the shipped model files record), network_architecture.py:25 puts
- * GaussianNoise(0.02) in front of conv1d_1.  DESIGN.md section 18.  Not here: the data generator
- * with its modify_signal augmentation, validation and checkpoint policy, a `train` command.
+ * GaussianNoise(0.02) in front of conv1d_1.  DESIGN.md section 18.  The data generator with its modify_signal
+ * augmentation and validation are the next section's; the checkpoint policy and the command are
+ * Python's (deepbinner_amd/fit.py).
  *
  * Defaults (dbh_trainer_default_options): Nadam's configuration as the shipped model files'
  * training_config attribute records it - lr (float)0.002, beta_1 (float)0.9, beta_2 (float)0.999 as
@@ -552,6 +553,94 @@ int dbh_trainer_get_state(dbh_trainer* trainer, float* m_host, float* v_host, in
 int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float* v_host,
                           int64_t n_floats, int64_t iterations, double m_schedule);
 int dbh_trainer_iterations(dbh_trainer* trainer, int64_t* iterations);
+
+/* ---- training: device-fed batches, validation -------------------------------------------------- */
+/* The reference's data generator (train_network.py:127-193) and Keras's validation pass, without a
+ * host loop per sample: a training-data file's windows stay on the device as the int16 samples the
+ * file holds, and one kernel per batch gathers, normalises and augments.  DESIGN.md section 19;
+ * tests/feed_reference.py restates all of it in NumPy.  bits() below is dbh_gradients' hash before
+ * its comparison (24 bits), with the layer numbers 8, 9 and 10 that nothing else uses.
+ *
+ * Normalise (trim_signal.py:61-69 at train_network.py:144).  For a window of L int16 samples x:
+ *     S = sum x, Q = sum x^2 in int64;  D = L * Q - S^2 (exact, < 2^59 for L <= 16,384)
+ *     mean = (double)S / L;  std = sqrt((double)D) / L
+ *     value = (float)(((double)x - mean) / std),  or (float)((double)x - mean) where D == 0
+ * in fp64, each value rounded once; the sums are integers, so no order of summation exists.
+ *
+ * Augment (modify_signal and augmentation_chance, train_network.py:135,160-193), with s the seed
+ * and w the batch SLOT (not the sample) as the hash's window:
+ *     slot w is augmented  <=>  bits(s, 8, w, position 0, channel 0) < floor((1 - 1/aug) * 2^24)
+ *     (the threshold formed on the host in double; aug = 1: 0, every window copied bit for bit)
+ *     key(i) = bits(s, 9, w, i, 0);  rank(i) = the place of (key(i), i) in ascending order (equal
+ *     keys rank by index);  half = L / 4 rounded half to even, as Python's round()
+ *     position i is written twice where rank < half, dropped where half <= rank < 2 half, once
+ *     otherwise; outputs keep the input's order: exactly L of them.
+ * That is the reference's law - a uniform subset of 2 half positions, split uniformly - not its
+ * random stream.  Every value is a function of its source sample alone, so normalising and
+ * augmenting commute.
+ *
+ * Epoch order (random.shuffle at train_network.py:145,155): dbh_epoch_order, host only, no device:
+ * order = the sample indices 0 .. n-1 in a stable ascending sort by
+ * bits(seed, 10, sample index, pass mod 2^14, 0).  The sample stream is pass 0's order, then pass
+ * 1's, and so on; step t takes stream positions [t B, (t+1) B), so a batch may span two passes.
+ * n up to 2^31 (more: DBH_ERR_UNSUPPORTED); n < 1, pass < 0, null: DBH_ERR_INVALID_ARGUMENT.
+ *
+ * A data set owns one device block: the samples [n][input_size], the labels, mean and std per
+ * window (computed once, at creation).  Errors of every entry below come before any device work and
+ * nothing is written: a geometry dbh_trainer_create would refuse, n > 2^31 - 1, n_windows *
+ * input_size > 2^20: DBH_ERR_UNSUPPORTED; a label outside [0, n_classes), a count < 1, a null
+ * pointer, augmentation < 1 or not a number, (host entries) an index outside [0, n):
+ * DBH_ERR_INVALID_ARGUMENT.  In the _dev entries an index outside [0, n) gives a window of NaN with
+ * the label -1 (so a NaN loss), never a read outside the block. */
+typedef struct dbh_dataset dbh_dataset;
+int dbh_epoch_order(uint64_t seed, int64_t pass, int64_t n, int64_t* order);
+int dbh_dataset_create(const int16_t* samples_host, const int32_t* labels_host, int64_t n,
+                       int input_size, int n_classes, dbh_dataset** ds);
+int dbh_dataset_destroy(dbh_dataset* ds);             /* null is fine */
+int dbh_dataset_count(const dbh_dataset* ds, int64_t* n);
+/* Slot w of x [n_windows][input_size] and labels [n_windows] from sample indices[w].  Stateless.
+ * Host pointers: blocks (for tests and host loops).  _dev: device pointers, queued on `stream`,
+ * not synchronised. */
+int dbh_dataset_batch(const dbh_dataset* ds, const int64_t* indices_host, int64_t n_windows,
+                      double augmentation, uint64_t seed, float* x_host, int32_t* labels_host);
+int dbh_dataset_batch_dev(const dbh_dataset* ds, const int64_t* indices_dev, int64_t n_windows,
+                          double augmentation, uint64_t seed, float* x_dev, int32_t* labels_dev,
+                          dbh_stream stream);
+/* dbh_gradients' forward pass in Keras's TEST phase (what fit_generator's validation and
+ * model.evaluate run): each batch normalisation uses the blob's moving mean and variance,
+ * 1 / sqrt(var + 1e-3) in fp64, no dropout, no noise; nothing is written to the weights.  The loss of
+ * a window as in dbh_gradients (unclipped); loss_sum adds them in window order in fp64, n_correct
+ * counts the windows whose argmax (lowest index on ties) is the label.  dbh_gradients' limits,
+ * workspace (dbh_gradients_workspace_bytes) and errors.  window_loss (n_windows doubles) may be
+ * null.  _dev: queued, not synchronised, and the totals are ADDED to *loss_sum_dev and
+ * *n_correct_dev - zero them, then queue a set chunk by chunk and synchronise once. */
+int dbh_evaluate(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                 const float* x_host, const int32_t* labels_host, int64_t n_windows,
+                 double* loss_sum, int64_t* n_correct, double* window_loss_host);
+int dbh_evaluate_dev(const float* weights_dev, int64_t n_floats, int n_classes, int input_size,
+                     const float* x_dev, const int32_t* labels_dev, int64_t n_windows,
+                     double* loss_sum_dev, int64_t* n_correct_dev, double* window_loss_dev,
+                     void* workspace_dev, dbh_stream stream);
+/* A trainer's step on a data set's samples: assemble(indices, augmentation, step_seed) into the
+ * trainer's own batch buffers, then the step of dbh_trainer_step_dev - the order is augment, noise,
+ * gradients, update, all with the one step_seed.  The data set's input_size and n_classes must be
+ * the trainer's (else DBH_ERR_UNSUPPORTED); otherwise the errors of dbh_trainer_step and of
+ * dbh_dataset_batch.  The host entry blocks; the _dev entry (indices on the device) is queued on
+ * `stream` and never synchronised. */
+int dbh_trainer_step_dataset(dbh_trainer* trainer, const dbh_dataset* ds, const int64_t* indices_host,
+                             int64_t n_windows, double augmentation, double* mean_loss,
+                             int64_t* n_correct);
+int dbh_trainer_step_dataset_dev(dbh_trainer* trainer, const dbh_dataset* ds,
+                                 const int64_t* indices_dev, int64_t n_windows, double augmentation,
+                                 double* mean_loss_dev, int64_t* n_correct_dev, dbh_stream stream);
+/* dbh_evaluate on the trainer's resident weights over the samples [first, first + count) in file
+ * order, unaugmented, in chunks of max_windows through the step's own buffers (a window's result
+ * does not depend on its chunk); one synchronisation at the end.  The weights, m, v and the step
+ * count are not touched.  window_loss_host (count doubles) may be null.  first or count outside
+ * the set: DBH_ERR_INVALID_ARGUMENT. */
+int dbh_trainer_evaluate_dataset(dbh_trainer* trainer, const dbh_dataset* ds, int64_t first,
+                                 int64_t count, double* loss_sum, int64_t* n_correct,
+                                 double* window_loss_host);
 
 /* ---- introspection ------------------------------------------------------------------------ */
 /* Activations after stage 'A'..'G'  for n_windows windows, row-major
