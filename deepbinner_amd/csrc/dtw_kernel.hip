@@ -17,6 +17,10 @@
 // Arithmetic as in dtw.cpp, in fp64 and without contraction (-ffp-contract=off): cost = best of
 // (diagonal, left, up) + (ref[i] - query[j])^2, the diagonal winning ties, an exact left/up tie
 // going LEFT (the reference draws rand() there, dtw.cpp:40-45).
+//
+// Beside dtw_kernel: the kernels of prep's signal stage (dtw_rescaled_batch, dtw_locate_batch) -
+// normalise, the line fit between two passes of dtw_kernel, the verdict on slope and fit, the
+// first hit of a group - which keep the rescaled DTW and prep's scans on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -227,6 +231,111 @@ __global__ __launch_bounds__(kLanes) void dtw_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
+// prep's signal stage (include/deepbinner_dtw.h, "Rescaled DTW" and "Locate"): what runs between
+// and around two passes of dtw_kernel so that nothing has to cross to the host in between.
+
+// One block per read: int16 region -> fp64, ((double)x - mean) / std, or (double)x - mean where
+// std is 0.  mean and std are the whole trimmed read's, formed by the host from exact integer sums.
+__global__ __launch_bounds__(256) void normalise_kernel(
+    const int16_t* __restrict__ samples, const int64_t* __restrict__ region_offsets,
+    const double* __restrict__ mean_std, double* __restrict__ out) {
+    const int64_t first = region_offsets[blockIdx.x], last = region_offsets[blockIdx.x + 1];
+    const double mean = mean_std[2 * (size_t)blockIdx.x], sd = mean_std[2 * (size_t)blockIdx.x + 1];
+    for (int64_t k = first + threadIdx.x; k < last; k += 256) {
+        const double centred = (double)samples[k] - mean;
+        out[k] = (sd > 0.0) ? centred / sd : centred;
+    }
+}
+
+// One wave per pair, between the passes: the line y = m x + b through (query[j], ref[i]) over the
+// alignment pass 1 left on the device, and the pair's own rescaled query.  Summation order (the
+// header fixes it): lane l adds path entries l, l + 64, ... in stored order (from the alignment's
+// END backwards) into its four partial sums, starting from +0.0; the totals start from +0.0 and
+// take the 64 partials in lane order.  x * x and x * y are rounded before they are added.
+__global__ __launch_bounds__(kLanes) void fit_kernel(
+    const PairJob* __restrict__ first_pass, const PairJob* __restrict__ second_pass,
+    const double* __restrict__ refs, const double* __restrict__ queries,
+    const int32_t* __restrict__ alignment, const int32_t* __restrict__ path_lengths,
+    double* __restrict__ rescaled, double* __restrict__ slopes, int32_t* __restrict__ bad_fit) {
+    const PairJob job = first_pass[blockIdx.x];
+    const int lane = threadIdx.x;
+    const double* ref = refs + job.ref_off;
+    const double* query = queries + job.query_off;
+    double* out = rescaled + second_pass[blockIdx.x].query_off;
+    const int2* pairs = reinterpret_cast<const int2*>(alignment + job.align_off);
+    const int n = path_lengths[job.pair];
+    double sx = 0.0, sy = 0.0, sxx = 0.0, sxy = 0.0;
+    for (int k = lane; k < n; k += kLanes) {
+        const int2 ij = pairs[k];
+        const double y = ref[ij.x], x = query[ij.y];
+        sx += x;
+        sy += y;
+        sxx += x * x;
+        sxy += x * y;
+    }
+    double Sx = 0.0, Sy = 0.0, Sxx = 0.0, Sxy = 0.0;
+    for (int l = 0; l < kLanes; ++l) {
+        Sx += lane_value(sx, l);
+        Sy += lane_value(sy, l);
+        Sxx += lane_value(sxx, l);
+        Sxy += lane_value(sxy, l);
+    }
+    const double count = (double)n;
+    const double denominator = count * Sxx - Sx * Sx;
+    // a constant query (or sums that left the finite range): no line, the query stays as it is
+    // and the verdict makes the distance +inf
+    const bool bad = !(denominator != 0.0 && fabs(denominator) <= DBL_MAX);
+    double m = 1.0, b = 0.0;
+    if (!bad) {
+        m = (count * Sxy - Sx * Sy) / denominator;
+        b = (Sy - m * Sx) / count;
+    }
+    for (int j = lane; j < job.query_len; j += kLanes) {
+        const double scaled = m * query[j];
+        out[j] = bad ? query[j] : scaled + b;
+    }
+    if (lane == 0) {
+        slopes[job.pair] = bad ? __builtin_nan("") : m;
+        bad_fit[job.pair] = bad ? 1 : 0;
+    }
+}
+
+// One thread per pair, after pass 2: a slope outside 0.75 .. 1.333 (reference
+// dtw_semi_global.py:91-93) or a fit that could not be made turns the distance into +inf; a
+// skipped job (empty window) gets +inf, positions -1 and a NaN slope.
+__global__ __launch_bounds__(256) void verdict_kernel(
+    int64_t n, const int32_t* __restrict__ ref_lengths, const int32_t* __restrict__ bad_fit,
+    double* __restrict__ slopes, double* __restrict__ distances, int32_t* __restrict__ positions) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    if (ref_lengths[k] == 0) {
+        distances[k] = HUGE_VAL;
+        positions[2 * k] = positions[2 * k + 1] = -1;
+        slopes[k] = __builtin_nan("");
+        return;
+    }
+    const double m = slopes[k];
+    if (bad_fit[k] || m < 0.75 || m > 1.333) distances[k] = HUGE_VAL;
+}
+
+// One thread per group: its first job, in job order, with a finite distance <= threshold.
+__global__ __launch_bounds__(256) void select_kernel(
+    int64_t n_groups, const int64_t* __restrict__ group_offsets,
+    const double* __restrict__ distances, double threshold, int32_t* __restrict__ hits) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n_groups) return;
+    int32_t hit = -1;
+    for (int64_t k = group_offsets[g]; k < group_offsets[g + 1]; ++k) {
+        const double d = distances[k];
+        if (d <= threshold && d < HUGE_VAL) {
+            hit = (int32_t)k;
+            break;
+        }
+    }
+    hits[g] = hit;
+}
+
+// ------------------------------------------------------------------------------------------------
 thread_local std::string g_error;
 
 struct DeviceBuffer {
@@ -249,6 +358,9 @@ struct Context {
     hipStream_t stream = nullptr;
     hipEvent_t begin = nullptr, end = nullptr;
     DeviceBuffer refs, queries, jobs, path, edges, distances, positions, lengths, alignment;
+    // the resident entries (dtw_rescaled_batch, dtw_locate_batch) only
+    DeviceBuffer second_jobs, first_alignment, rescaled, slopes, bad_fit, ref_lengths, samples,
+        region_offsets, mean_std, group_offsets, hits;
     double last_ms = 0.0;
     int64_t last_cells = 0;
 };
@@ -279,7 +391,10 @@ int prepare(Context& ctx) {
         }
         // first use, or the caller switched devices: buffers of the other device are dropped
         for (DeviceBuffer* b : {&ctx.refs, &ctx.queries, &ctx.jobs, &ctx.path, &ctx.edges,
-                                &ctx.distances, &ctx.positions, &ctx.lengths, &ctx.alignment})
+                                &ctx.distances, &ctx.positions, &ctx.lengths, &ctx.alignment,
+                                &ctx.second_jobs, &ctx.first_alignment, &ctx.rescaled, &ctx.slopes,
+                                &ctx.bad_fit, &ctx.ref_lengths, &ctx.samples, &ctx.region_offsets,
+                                &ctx.mean_std, &ctx.group_offsets, &ctx.hits})
             *b = DeviceBuffer{};
         ctx.device = device;
         DTW_HIP(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
@@ -420,6 +535,344 @@ int run_batch(Context& ctx, const double* refs, const int64_t* ref_offsets, cons
     return DTW_OK;
 }
 
+// ---- the resident entries ----------------------------------------------------------------------
+// A pair of the rescaled DTW: where its reference and its query lie in ctx.refs / ctx.queries, and
+// where its pass-2 alignment goes.  ref_len == 0: a skipped job (dtw_locate_batch's empty window).
+struct ResidentPair {
+    int64_t ref_off, query_off, align_off;
+    int32_t ref_len, query_len;
+};
+
+// One part: pairs of one lane width whose direction words fit the budget.  A pair's pass 1, fit
+// and pass 2 are all in its part; the direction words, the edge columns and the pass-1 alignments
+// are the part's and are used again by the next part, in stream order.
+struct Part {
+    int c;
+    size_t first, count;   // its jobs in the two job arrays
+};
+
+template <int C>
+void launch_pass(Context& ctx, const Part& part, const PairJob* jobs, const double* queries,
+                 int32_t* alignment) {
+    hipLaunchKernelGGL(dtw_kernel<C>, dim3((unsigned)part.count), dim3(kLanes), 0, ctx.stream,
+                       jobs + part.first, (const double*)ctx.refs.ptr, queries,
+                       (Word*)ctx.path.ptr, (double*)ctx.edges.ptr, (double*)ctx.distances.ptr,
+                       (int32_t*)ctx.positions.ptr, (int32_t*)ctx.lengths.ptr, alignment);
+}
+
+void launch_pass(Context& ctx, const Part& part, const PairJob* jobs, const double* queries,
+                 int32_t* alignment) {
+    switch (part.c) {
+        case 4: launch_pass<4>(ctx, part, jobs, queries, alignment); break;
+        case 8: launch_pass<8>(ctx, part, jobs, queries, alignment); break;
+        default: launch_pass<16>(ctx, part, jobs, queries, alignment); break;
+    }
+}
+
+// What plan_rescaled works out and queue_rescaled launches.  The job arrays are copied to the
+// device asynchronously, so the plan is the caller's and lives until the caller has synchronised.
+struct ResidentPlan {
+    std::vector<Part> parts;
+    std::vector<PairJob> first_jobs, second_jobs;   // pass 1 and pass 2, part after part
+    std::vector<int32_t> ref_lengths;
+    size_t n_pairs = 0;
+    bool want_alignment = false;
+};
+
+// Cuts the pairs into parts, sizes every buffer the launches need (once: nothing is allocated
+// between the launches) and queues the upload of the job arrays.
+int plan_rescaled(Context& ctx, const std::vector<ResidentPair>& pairs, bool want_alignment,
+                  size_t alignment_ints, ResidentPlan& plan) {
+    const size_t n = pairs.size();
+    const size_t budget = path_budget_bytes();
+    std::vector<Part>& parts = plan.parts;
+    std::vector<PairJob>& first_jobs = plan.first_jobs;
+    std::vector<PairJob>& second_jobs = plan.second_jobs;
+    std::vector<int32_t>& ref_lengths = plan.ref_lengths;
+    plan.n_pairs = n;
+    plan.want_alignment = want_alignment;
+    parts.clear();
+    ref_lengths.assign(n, 0);
+    size_t rescaled_doubles = 0, max_words = 0, max_edges = 0, max_first_alignment = 0;
+    std::vector<int64_t> rescaled_off(n);
+    for (size_t p = 0; p < n; ++p) {
+        ref_lengths[p] = pairs[p].ref_len;
+        rescaled_off[p] = (int64_t)rescaled_doubles;
+        if (pairs[p].ref_len > 0) rescaled_doubles += (size_t)pairs[p].query_len;
+    }
+    first_jobs.clear();
+    ctx.last_ms = 0.0;
+    ctx.last_cells = 0;
+    for (int c : {4, 8, 16}) {
+        const int panel = kLanes * c;
+        auto close_part = [&](size_t first) {
+            if (first == first_jobs.size()) return;
+            // the longest first, as run_group has them
+            std::sort(first_jobs.begin() + first, first_jobs.end(),
+                      [](const PairJob& a, const PairJob& b) {
+                          return (int64_t)a.ref_len * a.query_len > (int64_t)b.ref_len * b.query_len;
+                      });
+            size_t words = 0, edge_doubles = 0, align_ints = 0;
+            for (size_t k = first; k < first_jobs.size(); ++k) {
+                PairJob& job = first_jobs[k];
+                const int panels = (job.query_len + panel - 1) / panel;
+                job.path_off = (int64_t)words;
+                words += (size_t)panels * ((size_t)job.ref_len + kLanes - 1) * kLanes;
+                job.edge_off = (int64_t)edge_doubles;
+                if (panels > 1) edge_doubles += (size_t)2 * job.ref_len;
+                job.align_off = (int64_t)align_ints;
+                align_ints += (size_t)2 * ((size_t)job.ref_len + job.query_len);
+            }
+            max_words = std::max(max_words, words);
+            max_edges = std::max(max_edges, edge_doubles);
+            max_first_alignment = std::max(max_first_alignment, align_ints);
+            parts.push_back(Part{c, first, first_jobs.size() - first});
+        };
+        size_t first = first_jobs.size(), bytes = 0;
+        for (size_t p = 0; p < n; ++p) {
+            const ResidentPair& pair = pairs[p];
+            if (pair.ref_len == 0 || cells_per_lane(pair.query_len) != c) continue;
+            const size_t panels = ((size_t)pair.query_len + panel - 1) / panel;
+            const size_t need = panels * ((size_t)pair.ref_len + kLanes - 1) * kLanes * sizeof(Word);
+            if (first != first_jobs.size() && bytes + need > budget) {
+                close_part(first);
+                first = first_jobs.size();
+                bytes = 0;
+            }
+            PairJob job{};
+            job.ref_off = pair.ref_off;
+            job.query_off = pair.query_off;
+            job.ref_len = pair.ref_len;
+            job.query_len = pair.query_len;
+            job.pair = (int32_t)p;
+            first_jobs.push_back(job);
+            bytes += need;
+            ctx.last_cells += (int64_t)2 * pair.ref_len * pair.query_len;
+        }
+        close_part(first);
+    }
+    // pass 2 of a pair: the same job on its own rescaled query, its alignment where the caller
+    // wants it
+    second_jobs = first_jobs;
+    for (PairJob& job : second_jobs) {
+        job.query_off = rescaled_off[job.pair];
+        job.align_off = pairs[job.pair].align_off;
+    }
+    const size_t n_jobs = first_jobs.size();
+    DTW_HIP(ctx.path.reserve(std::max<size_t>(max_words * sizeof(Word), 8)));
+    DTW_HIP(ctx.edges.reserve(std::max<size_t>(max_edges * sizeof(double), 8)));
+    DTW_HIP(ctx.first_alignment.reserve(std::max<size_t>(max_first_alignment * sizeof(int32_t), 8)));
+    DTW_HIP(ctx.rescaled.reserve(std::max<size_t>(rescaled_doubles * sizeof(double), 8)));
+    DTW_HIP(ctx.jobs.reserve(std::max<size_t>(n_jobs * sizeof(PairJob), 8)));
+    DTW_HIP(ctx.second_jobs.reserve(std::max<size_t>(n_jobs * sizeof(PairJob), 8)));
+    DTW_HIP(ctx.distances.reserve(n * sizeof(double)));
+    DTW_HIP(ctx.positions.reserve(n * 2 * sizeof(int32_t)));
+    DTW_HIP(ctx.lengths.reserve(n * sizeof(int32_t)));
+    DTW_HIP(ctx.slopes.reserve(n * sizeof(double)));
+    DTW_HIP(ctx.bad_fit.reserve(n * sizeof(int32_t)));
+    DTW_HIP(ctx.ref_lengths.reserve(n * sizeof(int32_t)));
+    if (want_alignment)
+        DTW_HIP(ctx.alignment.reserve(std::max<size_t>(alignment_ints * sizeof(int32_t), 8)));
+    if (n_jobs) {
+        DTW_HIP(hipMemcpyAsync(ctx.jobs.ptr, first_jobs.data(), n_jobs * sizeof(PairJob),
+                               hipMemcpyHostToDevice, ctx.stream));
+        DTW_HIP(hipMemcpyAsync(ctx.second_jobs.ptr, second_jobs.data(), n_jobs * sizeof(PairJob),
+                               hipMemcpyHostToDevice, ctx.stream));
+    }
+    DTW_HIP(hipMemcpyAsync(ctx.ref_lengths.ptr, ref_lengths.data(), n * sizeof(int32_t),
+                           hipMemcpyHostToDevice, ctx.stream));
+    return DTW_OK;
+}
+
+// Queues, on ctx.stream and without a synchronise: pass 1, fit, pass 2 for every part, then the
+// verdict.  ctx.refs and ctx.queries are filled by work queued before.  Leaves, per pair, on the
+// device: distances, positions, lengths (of pass 2), slopes; the rescaled queries back to back in
+// pair order in ctx.rescaled; the pass-2 alignments in ctx.alignment when wanted.
+int queue_rescaled(Context& ctx, const ResidentPlan& plan) {
+    const size_t n = plan.n_pairs;
+    const bool want_alignment = plan.want_alignment;
+    for (const Part& part : plan.parts) {
+        launch_pass(ctx, part, (const PairJob*)ctx.jobs.ptr, (const double*)ctx.queries.ptr,
+                    (int32_t*)ctx.first_alignment.ptr);
+        hipLaunchKernelGGL(fit_kernel, dim3((unsigned)part.count), dim3(kLanes), 0, ctx.stream,
+                           (const PairJob*)ctx.jobs.ptr + part.first,
+                           (const PairJob*)ctx.second_jobs.ptr + part.first,
+                           (const double*)ctx.refs.ptr, (const double*)ctx.queries.ptr,
+                           (const int32_t*)ctx.first_alignment.ptr,
+                           (const int32_t*)ctx.lengths.ptr, (double*)ctx.rescaled.ptr,
+                           (double*)ctx.slopes.ptr, (int32_t*)ctx.bad_fit.ptr);
+        launch_pass(ctx, part, (const PairJob*)ctx.second_jobs.ptr,
+                    (const double*)ctx.rescaled.ptr,
+                    want_alignment ? (int32_t*)ctx.alignment.ptr : nullptr);
+        DTW_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(verdict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx.stream,
+                       (int64_t)n, (const int32_t*)ctx.ref_lengths.ptr,
+                       (const int32_t*)ctx.bad_fit.ptr, (double*)ctx.slopes.ptr,
+                       (double*)ctx.distances.ptr, (int32_t*)ctx.positions.ptr);
+    DTW_HIP(hipGetLastError());
+    return DTW_OK;
+}
+
+int finish_timing(Context& ctx) {
+    float ms = 0.f;
+    DTW_HIP(hipEventElapsedTime(&ms, ctx.begin, ctx.end));
+    ctx.last_ms = ms;
+    return DTW_OK;
+}
+
+int run_rescaled(Context& ctx, const double* refs, const int64_t* ref_offsets,
+                 const double* queries, const int64_t* query_offsets, int64_t n_pairs,
+                 double* distances, int32_t* positions, double* slopes, double* rescaled,
+                 int32_t* path_lengths, int32_t* alignment) {
+    const int64_t n_ref = ref_offsets[n_pairs] - ref_offsets[0];
+    const int64_t n_query = query_offsets[n_pairs] - query_offsets[0];
+    const size_t align_first = (size_t)2 * (size_t)(ref_offsets[0] + query_offsets[0]);
+    const size_t align_ints =
+        (size_t)2 * (size_t)(ref_offsets[n_pairs] + query_offsets[n_pairs]) - align_first;
+    DTW_HIP(ctx.refs.reserve((size_t)n_ref * sizeof(double)));
+    DTW_HIP(ctx.queries.reserve((size_t)n_query * sizeof(double)));
+    DTW_HIP(hipMemcpyAsync(ctx.refs.ptr, refs + ref_offsets[0], (size_t)n_ref * sizeof(double),
+                           hipMemcpyHostToDevice, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(ctx.queries.ptr, queries + query_offsets[0],
+                           (size_t)n_query * sizeof(double), hipMemcpyHostToDevice, ctx.stream));
+    std::vector<ResidentPair> pairs((size_t)n_pairs);
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        ResidentPair& pair = pairs[(size_t)p];
+        pair.ref_off = ref_offsets[p] - ref_offsets[0];
+        pair.query_off = query_offsets[p] - query_offsets[0];
+        pair.align_off = 2 * (ref_offsets[p] + query_offsets[p]) - (int64_t)align_first;
+        pair.ref_len = (int32_t)(ref_offsets[p + 1] - ref_offsets[p]);
+        pair.query_len = (int32_t)(query_offsets[p + 1] - query_offsets[p]);
+    }
+    ResidentPlan plan;
+    int st = plan_rescaled(ctx, pairs, alignment != nullptr, align_ints, plan);
+    if (st != DTW_OK) return st;
+    DTW_HIP(hipEventRecord(ctx.begin, ctx.stream));
+    st = queue_rescaled(ctx, plan);
+    if (st != DTW_OK) return st;
+    DTW_HIP(hipEventRecord(ctx.end, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(distances, ctx.distances.ptr, (size_t)n_pairs * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(positions, ctx.positions.ptr, (size_t)n_pairs * 2 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(slopes, ctx.slopes.ptr, (size_t)n_pairs * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx.stream));
+    // every pair has a reference here, so the rescaled queries lie as the queries do
+    if (rescaled)
+        DTW_HIP(hipMemcpyAsync(rescaled + query_offsets[0], ctx.rescaled.ptr,
+                               (size_t)n_query * sizeof(double), hipMemcpyDeviceToHost,
+                               ctx.stream));
+    if (path_lengths)
+        DTW_HIP(hipMemcpyAsync(path_lengths, ctx.lengths.ptr, (size_t)n_pairs * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, ctx.stream));
+    if (alignment)
+        DTW_HIP(hipMemcpyAsync(alignment + align_first, ctx.alignment.ptr,
+                               align_ints * sizeof(int32_t), hipMemcpyDeviceToHost, ctx.stream));
+    DTW_HIP(hipStreamSynchronize(ctx.stream));
+    return finish_timing(ctx);
+}
+
+struct LocateArguments {
+    const int16_t* samples;
+    const int64_t* region_offsets;
+    const double* mean_std;
+    int64_t n_reads;
+    const double* queries;
+    const int64_t* query_offsets;
+    int64_t n_queries;
+    const int64_t* jobs;
+    int64_t n_jobs;
+    const int64_t* group_offsets;
+    int64_t n_groups;
+    double threshold;
+};
+
+int run_locate(Context& ctx, const LocateArguments& a, double* distances, int32_t* positions,
+               double* slopes, int32_t* hits) {
+    const int64_t n_samples = a.region_offsets[a.n_reads] - a.region_offsets[0];
+    const int64_t n_query = a.query_offsets[a.n_queries] - a.query_offsets[0];
+    std::vector<int64_t> regions((size_t)a.n_reads + 1);
+    for (int64_t r = 0; r <= a.n_reads; ++r)
+        regions[(size_t)r] = a.region_offsets[r] - a.region_offsets[0];
+    DTW_HIP(ctx.samples.reserve(std::max<size_t>((size_t)n_samples * sizeof(int16_t), 8)));
+    DTW_HIP(ctx.refs.reserve(std::max<size_t>((size_t)n_samples * sizeof(double), 8)));
+    DTW_HIP(ctx.queries.reserve((size_t)n_query * sizeof(double)));
+    DTW_HIP(ctx.region_offsets.reserve(regions.size() * sizeof(int64_t)));
+    DTW_HIP(ctx.mean_std.reserve((size_t)a.n_reads * 2 * sizeof(double)));
+    DTW_HIP(ctx.group_offsets.reserve(((size_t)a.n_groups + 1) * sizeof(int64_t)));
+    DTW_HIP(ctx.hits.reserve(std::max<size_t>((size_t)a.n_groups * sizeof(int32_t), 8)));
+    if (n_samples)
+        DTW_HIP(hipMemcpyAsync(ctx.samples.ptr, a.samples + a.region_offsets[0],
+                               (size_t)n_samples * sizeof(int16_t), hipMemcpyHostToDevice,
+                               ctx.stream));
+    DTW_HIP(hipMemcpyAsync(ctx.queries.ptr, a.queries + a.query_offsets[0],
+                           (size_t)n_query * sizeof(double), hipMemcpyHostToDevice, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(ctx.region_offsets.ptr, regions.data(),
+                           regions.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(ctx.mean_std.ptr, a.mean_std, (size_t)a.n_reads * 2 * sizeof(double),
+                           hipMemcpyHostToDevice, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(ctx.group_offsets.ptr, a.group_offsets,
+                           ((size_t)a.n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                           ctx.stream));
+    // the windows overlap: every job points into the one normalised buffer, none is copied
+    std::vector<ResidentPair> pairs((size_t)a.n_jobs);
+    for (int64_t k = 0; k < a.n_jobs; ++k) {
+        const int64_t read = a.jobs[4 * k], from = a.jobs[4 * k + 1], to = a.jobs[4 * k + 2];
+        const int64_t query = a.jobs[4 * k + 3];
+        ResidentPair& pair = pairs[(size_t)k];
+        pair.ref_off = regions[(size_t)read] + from;
+        pair.query_off = a.query_offsets[query] - a.query_offsets[0];
+        pair.align_off = 0;
+        pair.ref_len = (int32_t)(to - from);
+        pair.query_len = (int32_t)(a.query_offsets[query + 1] - a.query_offsets[query]);
+    }
+    ResidentPlan plan;
+    int st = plan_rescaled(ctx, pairs, false, 0, plan);
+    if (st != DTW_OK) return st;
+    DTW_HIP(hipEventRecord(ctx.begin, ctx.stream));
+    hipLaunchKernelGGL(normalise_kernel, dim3((unsigned)a.n_reads), dim3(256), 0, ctx.stream,
+                       (const int16_t*)ctx.samples.ptr, (const int64_t*)ctx.region_offsets.ptr,
+                       (const double*)ctx.mean_std.ptr, (double*)ctx.refs.ptr);
+    DTW_HIP(hipGetLastError());
+    st = queue_rescaled(ctx, plan);
+    if (st != DTW_OK) return st;
+    if (a.n_groups)
+        hipLaunchKernelGGL(select_kernel, dim3((unsigned)((a.n_groups + 255) / 256)), dim3(256),
+                           0, ctx.stream, a.n_groups, (const int64_t*)ctx.group_offsets.ptr,
+                           (const double*)ctx.distances.ptr, a.threshold,
+                           (int32_t*)ctx.hits.ptr);
+    DTW_HIP(hipGetLastError());
+    DTW_HIP(hipEventRecord(ctx.end, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(distances, ctx.distances.ptr, (size_t)a.n_jobs * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(positions, ctx.positions.ptr, (size_t)a.n_jobs * 2 * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, ctx.stream));
+    DTW_HIP(hipMemcpyAsync(slopes, ctx.slopes.ptr, (size_t)a.n_jobs * sizeof(double),
+                           hipMemcpyDeviceToHost, ctx.stream));
+    if (a.n_groups)
+        DTW_HIP(hipMemcpyAsync(hits, ctx.hits.ptr, (size_t)a.n_groups * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, ctx.stream));
+    DTW_HIP(hipStreamSynchronize(ctx.stream));
+    return finish_timing(ctx);
+}
+
+int bad_argument(const char* text) {
+    g_error = text;
+    return DTW_ERR_ARGUMENT;
+}
+
+// offsets[0 .. n]: not negative, ascending (equal neighbours allowed when `may_be_empty`), every
+// stretch at most 2^30 long
+bool offsets_fine(const int64_t* offsets, int64_t n, bool may_be_empty) {
+    if (offsets[0] < 0) return false;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t length = offsets[k + 1] - offsets[k];
+        if (length < (may_be_empty ? 0 : 1) || length > (1 << 30)) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -478,6 +931,81 @@ double semi_global_dtw(const double* ref, const double* query, int ref_len, int 
     if (st != DTW_OK) return std::nan("");
     path_length[0] = n;
     return distance;
+}
+
+int dtw_rescaled_batch(const double* refs, const int64_t* ref_offsets, const double* queries,
+                       const int64_t* query_offsets, int64_t n_pairs, double* distances,
+                       int32_t* positions, double* slopes, double* rescaled,
+                       int32_t* path_lengths, int32_t* alignment) {
+    if (n_pairs < 0 || (n_pairs > 0 && (!refs || !ref_offsets || !queries || !query_offsets ||
+                                        !distances || !positions || !slopes)))
+        return bad_argument("null pointer or negative pair count");
+    if (alignment && !path_lengths)
+        return bad_argument("an alignment is of no use without its path lengths");
+    if (n_pairs == 0) return DTW_OK;
+    if (n_pairs > INT32_MAX) return bad_argument("more than 2^31 - 1 pairs");
+    if (!offsets_fine(ref_offsets, n_pairs, false) || !offsets_fine(query_offsets, n_pairs, false))
+        return bad_argument("offsets ascending from 0 or more, please, and every pair with "
+                            "1 .. 2^30 samples of reference and of query");
+    std::lock_guard<std::mutex> guard(g_ctx.lock);
+    const int st = prepare(g_ctx);
+    if (st != DTW_OK) return st;
+    return run_rescaled(g_ctx, refs, ref_offsets, queries, query_offsets, n_pairs, distances,
+                        positions, slopes, rescaled, path_lengths, alignment);
+}
+
+int dtw_locate_batch(const int16_t* samples, const int64_t* region_offsets,
+                     const double* mean_std, int64_t n_reads, const double* queries,
+                     const int64_t* query_offsets, int64_t n_queries, const int64_t* jobs,
+                     int64_t n_jobs, const int64_t* group_offsets, int64_t n_groups,
+                     double threshold, double* distances, int32_t* positions, double* slopes,
+                     int32_t* hits) {
+    if (n_reads < 0 || n_queries < 0 || n_jobs < 0 || n_groups < 0)
+        return bad_argument("negative count");
+    if (!group_offsets || (n_groups > 0 && !hits)) return bad_argument("null pointer");
+    if (group_offsets[0] != 0 || group_offsets[n_groups] != n_jobs)
+        return bad_argument("the groups cover the jobs: group_offsets runs from 0 to n_jobs");
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (group_offsets[g + 1] < group_offsets[g])
+            return bad_argument("group offsets not ascending");
+    if (n_jobs == 0) {
+        for (int64_t g = 0; g < n_groups; ++g) hits[g] = -1;
+        return DTW_OK;
+    }
+    if (!samples || !region_offsets || !mean_std || !queries || !query_offsets || !jobs ||
+        !distances || !positions || !slopes)
+        return bad_argument("null pointer");
+    if (n_jobs > INT32_MAX || n_reads > INT32_MAX)
+        return bad_argument("more than 2^31 - 1 jobs or reads");
+    if (n_reads < 1 || n_queries < 1) return bad_argument("jobs without reads or without queries");
+    if (!offsets_fine(region_offsets, n_reads, true))
+        return bad_argument("region offsets ascending from 0 or more, please, and no region "
+                            "longer than 2^30 samples");
+    if (!offsets_fine(query_offsets, n_queries, false))
+        return bad_argument("query offsets ascending from 0 or more, please, and every query "
+                            "with 1 .. 2^30 samples");
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const double mean = mean_std[2 * r], sd = mean_std[2 * r + 1];
+        if (!(std::fabs(mean) <= DBL_MAX) || !(sd >= 0.0 && sd <= DBL_MAX))
+            return bad_argument("a read's mean is not finite, or its std is not finite or "
+                                "negative");
+    }
+    if (!(threshold == threshold)) return bad_argument("the threshold is not a number");
+    for (int64_t k = 0; k < n_jobs; ++k) {
+        const int64_t read = jobs[4 * k], from = jobs[4 * k + 1], to = jobs[4 * k + 2];
+        const int64_t query = jobs[4 * k + 3];
+        if (read < 0 || read >= n_reads) return bad_argument("a job's read is out of range");
+        if (query < 0 || query >= n_queries) return bad_argument("a job's query is out of range");
+        if (from < 0 || to < from || to > region_offsets[read + 1] - region_offsets[read])
+            return bad_argument("a job's window is not inside its read's region");
+    }
+    std::lock_guard<std::mutex> guard(g_ctx.lock);
+    const int st = prepare(g_ctx);
+    if (st != DTW_OK) return st;
+    const LocateArguments arguments{samples, region_offsets, mean_std, n_reads, queries,
+                                    query_offsets, n_queries, jobs, n_jobs, group_offsets,
+                                    n_groups, threshold};
+    return run_locate(g_ctx, arguments, distances, positions, slopes, hits);
 }
 
 int dtw_last_kernel_time(double* milliseconds, int64_t* cells) {

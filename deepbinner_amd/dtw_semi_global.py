@@ -11,6 +11,11 @@ and, new, the batched forms that give the device something to do - ``semi_global
 ``semi_global_dtw_with_rescaling_batch`` take lists of signals and run every pair of a pass in one
 launch.  Results per pair are exactly those of the one-pair functions.
 
+``semi_global_dtw_with_rescaling_batch(..., resident=True)`` and ``rescaled_batch`` keep both passes
+and the fit between them on the device (``dtw_rescaled_batch``), by the contract written in
+``include/deepbinner_dtw.h``: normal equations with a fixed summation order in place of ``lstsq``.
+``locate_batch`` is the binding of ``dtw_locate_batch``, which ``prep_signal`` builds on.
+
 There is no CPU fallback: without the library or without a gfx950 device the calls raise.
 """
 
@@ -21,7 +26,8 @@ import numpy as np
 from numpy.ctypeslib import ndpointer
 
 EXPORTED_SYMBOLS = ('dtw_version', 'dtw_status_string', 'dtw_last_error', 'semi_global_dtw',
-                    'dtw_semi_global_batch', 'dtw_last_kernel_time')
+                    'dtw_semi_global_batch', 'dtw_rescaled_batch', 'dtw_locate_batch',
+                    'dtw_last_kernel_time')
 LIB_NAME = 'libdeepbinner_dtw.so'
 _lib = None
 
@@ -58,6 +64,14 @@ def load_library():
     lib.dtw_semi_global_batch.restype = ctypes.c_int
     lib.dtw_semi_global_batch.argtypes = [f64, i64, f64, i64, ctypes.c_int64, f64, i32, i32,
                                           ctypes.c_void_p]
+    lib.dtw_rescaled_batch.restype = ctypes.c_int
+    lib.dtw_rescaled_batch.argtypes = [f64, i64, f64, i64, ctypes.c_int64, f64, i32, f64,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.dtw_locate_batch.restype = ctypes.c_int
+    lib.dtw_locate_batch.argtypes = [ndpointer(ctypes.c_int16, flags='C_CONTIGUOUS'), i64, f64,
+                                     ctypes.c_int64, f64, i64, ctypes.c_int64, i64,
+                                     ctypes.c_int64, i64, ctypes.c_int64, ctypes.c_double, f64,
+                                     i32, f64, i32]
     lib.dtw_last_kernel_time.restype = ctypes.c_int
     lib.dtw_last_kernel_time.argtypes = [ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_int64)]
@@ -152,9 +166,84 @@ def _refit(ref, query, pairs):
     return slope * query + intercept, slope
 
 
-def semi_global_dtw_with_rescaling_batch(refs, queries):
+def rescaled_batch(refs, queries, alignments=True):
+    """The rescaled DTW of every pair (refs[k], queries[k]) with both passes and the fit between
+    them on the device (``dtw_rescaled_batch``).  Returns a list of
+    ``(distance, ref_start, ref_end, slope, pairs, rescaled_query)``: ``pairs`` as
+    ``semi_global_dtw_batch`` gives them, of pass 2, or ``None`` when ``alignments`` is false."""
+    if len(refs) != len(queries):
+        raise ValueError('as many queries as references, please')
+    lib = load_library()
+    n = len(refs)
+    if n == 0:
+        return []
+    flat_refs, ref_offsets = _pack(refs)
+    flat_queries, query_offsets = _pack(queries)
+    distances = np.empty(n, dtype=np.float64)
+    positions = np.empty(2 * n, dtype=np.int32)
+    slopes = np.empty(n, dtype=np.float64)
+    rescaled = np.empty(len(flat_queries), dtype=np.float64)
+    lengths = np.empty(n, dtype=np.int32)
+    alignment = np.empty(2 * int(ref_offsets[-1] + query_offsets[-1]), dtype=np.int32) \
+        if alignments else None
+    status = lib.dtw_rescaled_batch(
+        flat_refs, ref_offsets, flat_queries, query_offsets, n, distances, positions, slopes,
+        rescaled.ctypes.data, lengths.ctypes.data, alignment.ctypes.data if alignments else None)
+    if status != 0:
+        _failed(lib, 'dtw_rescaled_batch', status)
+    results = []
+    for k in range(n):
+        pairs = None
+        if alignments:
+            at = 2 * int(ref_offsets[k] + query_offsets[k])
+            pairs = alignment[at:at + 2 * int(lengths[k])].reshape(-1, 2)[::-1]
+        results.append((float(distances[k]), int(positions[2 * k]), int(positions[2 * k + 1]),
+                        float(slopes[k]), pairs,
+                        rescaled[int(query_offsets[k]):int(query_offsets[k + 1])]))
+    return results
+
+
+def locate_batch(samples, region_offsets, mean_std, queries, query_offsets, jobs, group_offsets,
+                 threshold):
+    """``dtw_locate_batch`` as the header has it: int16 regions of reads, (mean, std) per read,
+    a table of query signals, jobs (read, from, to, query) in groups.  Returns
+    ``(distances, positions[n_jobs, 2], slopes, hits)`` as arrays."""
+    lib = load_library()
+    samples = np.ascontiguousarray(samples, dtype=np.int16)
+    region_offsets = np.ascontiguousarray(region_offsets, dtype=np.int64)
+    mean_std = np.ascontiguousarray(mean_std, dtype=np.float64).reshape(-1)
+    queries = np.ascontiguousarray(queries, dtype=np.float64)
+    query_offsets = np.ascontiguousarray(query_offsets, dtype=np.int64)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int64).reshape(-1)
+    group_offsets = np.ascontiguousarray(group_offsets, dtype=np.int64)
+    n_reads, n_queries = len(region_offsets) - 1, len(query_offsets) - 1
+    n_jobs, n_groups = len(jobs) // 4, len(group_offsets) - 1
+    if n_reads < 0 or n_queries < 0 or n_groups < 0 or len(jobs) % 4 or \
+            len(mean_std) != 2 * max(n_reads, 0):
+        raise ValueError('offset arrays have one entry more than there are reads, queries and '
+                         'groups; four numbers per job and two per read, please')
+    distances = np.empty(n_jobs, dtype=np.float64)
+    positions = np.empty(2 * n_jobs, dtype=np.int32)
+    slopes = np.empty(n_jobs, dtype=np.float64)
+    hits = np.empty(n_groups, dtype=np.int32)
+    status = lib.dtw_locate_batch(samples, region_offsets, mean_std, n_reads, queries,
+                                  query_offsets, n_queries, jobs, n_jobs, group_offsets, n_groups,
+                                  float(threshold), distances, positions, slopes, hits)
+    if status != 0:
+        _failed(lib, 'dtw_locate_batch', status)
+    return distances, positions.reshape(-1, 2), slopes, hits
+
+
+def semi_global_dtw_with_rescaling_batch(refs, queries, resident=False):
     """``semi_global_dtw_with_rescaling`` for many pairs: each of the two passes is one launch.
-    Returns a list of ``(distance, ref_start, ref_end, [(ref value, query value), ...])``."""
+    Returns a list of ``(distance, ref_start, ref_end, [(ref value, query value), ...])``.
+    ``resident=True``: both passes and the fit stay on the device (``rescaled_batch``); the fit is
+    then the header's normal equations, not ``lstsq``, and a constant query gives inf."""
+    if resident:
+        refs = [np.ascontiguousarray(r, dtype=np.float64) for r in refs]
+        return [(distance, start, end, list(zip(refs[k][pairs[:, 0]], rescaled[pairs[:, 1]])))
+                for k, (distance, start, end, _, pairs, rescaled)
+                in enumerate(rescaled_batch(refs, queries))]
     refs = [np.ascontiguousarray(r, dtype=np.float64) for r in refs]
     queries = [np.array(q, dtype=np.float64) for q in queries]
     slopes = [1.0] * len(refs)
@@ -175,8 +264,8 @@ def semi_global_dtw_with_rescaling_batch(refs, queries):
     return out
 
 
-def semi_global_dtw_with_rescaling(ref, query):
+def semi_global_dtw_with_rescaling(ref, query, resident=False):
     """Reference :62-95 (after https://arxiv.org/abs/1705.01620): align, fit the query to the
     reference over the aligned pairs, align again; a total slope outside 0.75 .. 1.333 means the
     fit went wrong and the distance becomes inf."""
-    return semi_global_dtw_with_rescaling_batch([ref], [query])[0]
+    return semi_global_dtw_with_rescaling_batch([ref], [query], resident=resident)[0]
