@@ -580,18 +580,31 @@ def classify_training_data(input_file, start_model, start_input_size, end_model,
     assert (start_model is None) != (end_model is None)
     model, input_size = ((start_model, start_input_size) if end_model is None
                          else (end_model, end_input_size))
-    with open(input_file, 'rt') as text:
-        records = [line.rstrip().split('\t') for line in text]
-    total = len(records)
+    # DEEPBINNER_TEXT_PARSE=gpu: the text is parsed on the device where every line is a strict one
+    # (hip_backend.strict_training_text) - a label's text is then str(label)
+    from . import hip_backend
+    strict = (hip_backend.strict_training_text(input_file)
+              if hip_backend.text_parse_route() == 'gpu' else None)
+    if strict is None:
+        with open(input_file, 'rt') as text:
+            records = [line.rstrip().split('\t') for line in text]
+        total = len(records)
+    else:
+        total = len(strict[1])
     print_classification_progress(0, total, 'training data')
     print_output_header(args.verbose, start_model is not None, end_model is not None, output_size)
 
     classifications = {}
     for first in range(0, max(total, 1), args.batch_size):
-        batch = records[first:first + args.batch_size]
-        read_ids = ['line_{}_barcode_{}'.format(first + k + 1, label)
-                    for k, (label, _) in enumerate(batch)]
-        signals = [np.array([int(v) for v in values.split(',')]) for _, values in batch]
+        if strict is not None:
+            read_ids = ['line_{}_barcode_{}'.format(first + k + 1, label) for k, label in
+                        enumerate(strict[1][first:first + args.batch_size].tolist())]
+            signals = list(strict[0][first:first + args.batch_size])
+        else:
+            batch = records[first:first + args.batch_size]
+            read_ids = ['line_{}_barcode_{}'.format(first + k + 1, label)
+                        for k, (label, _) in enumerate(batch)]
+            signals = [np.array([int(v) for v in values.split(',')]) for _, values in batch]
         for k, signal in enumerate(signals):
             # the device path carries raw signals as int16, which is what a sequencer produces;
             # the reference would normalise any integers (float64) - say which line it is

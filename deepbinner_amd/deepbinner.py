@@ -136,6 +136,10 @@ COMMANDS = {
              (('--seed',), dict(type=int, default=0,
                                 help='Seed of the epoch order, augmentation, noise and dropout '
                                      '(the same seed gives the same model, bit for bit)')),
+             (('--parse',), dict(type=str, choices=['host', 'gpu'], default=None,
+                                 help='Where the training-data text is parsed: host, or gpu for '
+                                      'whole blocks on the device with the same result (default: '
+                                      'DEEPBINNER_TEXT_PARSE, else host)')),
              _HELP]),
 }
 USES_MODELS = ('classify', 'realtime')

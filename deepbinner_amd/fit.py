@@ -37,10 +37,11 @@ def fit(args, trainer_factory=None, dataset_factory=None, epoch_order=None):
     check_options(args)
 
     print()
-    train_samples, train_labels = load_data(args.train)
+    parse = getattr(args, 'parse', None)
+    train_samples, train_labels = load_data(args.train, parse=parse)
     class_count = int(train_labels.max()) + 1
     signal_size = train_samples.shape[1]
-    val_samples, val_labels = load_data(args.val, signal_size)
+    val_samples, val_labels = load_data(args.val, signal_size, parse=parse)
     report(MESSAGES['classes'], class_count, class_count - 1)
     report(MESSAGES['size'], signal_size)
     for which, count in (('training', len(train_labels)), ('validation', len(val_labels))):
@@ -149,13 +150,15 @@ def load_starting_model(model_file):
     return weights
 
 
-def load_data(filename, signal_size=None):
+def load_data(filename, signal_size=None, parse=None):
     """(int16 samples [n, L], int32 labels [n]) of a training-data file, read in one pass
     (hip_backend.read_training_data); whatever is wrong with a line is an ``Error:`` with the
     reference's text where it has one.  The reference takes the signal size from the first hundred
-    lines and asserts it for the rest; here every line is held to it, under the same message."""
+    lines and asserts it for the rest; here every line is held to it, under the same message.
+    ``parse``: 'host', 'gpu' (the text parsed on the device) or None for DEEPBINNER_TEXT_PARSE;
+    either route gives the same arrays and the same errors."""
     from .hip_backend import TrainingDataError, read_training_data
     try:
-        return read_training_data(filename, signal_size, MESSAGES)
+        return read_training_data(filename, signal_size, MESSAGES, parse=parse)
     except TrainingDataError as e:
         sys.exit('Error: {}'.format(e))

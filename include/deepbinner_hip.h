@@ -642,6 +642,58 @@ int dbh_trainer_evaluate_dataset(dbh_trainer* trainer, const dbh_dataset* ds, in
                                  int64_t count, double* loss_sum, int64_t* n_correct,
                                  double* window_loss_host);
 
+/* ---- training-data text: a file's lines parsed on the GPU ---------------------------------------- */
+/* The text that fit and classify read (train_network.py:127-133, classify.py:183-239), one sample
+ * per line, to the int16 rows dbh_dataset_create takes.  DESIGN.md section 22;
+ * csrc/dbh_text_core.h is the parser, compiled into the kernel and into the host model;
+ * tests/text_parse_reference.py restates the grammar with regular expressions.
+ *
+ * The device parses a STRICT form only; what Python's parser takes beyond it (' 5', '1_0', '+1' or
+ * '01' as labels, a lone CR as a line end, digits outside ASCII) is left to the host, which has
+ * the last word on every line that is not DBH_TEXT_OK.  A strict line, as bytes:
+ *     line  := label TAB value ( ',' value )* [CR] LF
+ *     label := '0' | ['-'] [1-9] [0-9]{0,8}        (str(int(label)) == label; fits int32)
+ *     value := ['+' | '-'] [0-9]{1,7}
+ * A line's kind is the first of these that applies:
+ *     DBH_TEXT_FORM   anything outside the grammar: an empty line, a second TAB or none, an empty
+ *                     value, a NUL, a byte >= 0x80, a CR that no LF follows, eight digits, ...
+ *     DBH_TEXT_COUNT  strict, but the number of values is not input_size
+ *     DBH_TEXT_RANGE  strict with input_size values, one of them outside -32768..32767
+ *     DBH_TEXT_OK     otherwise
+ * A BLOCK is a run of whole lines: n_bytes >= 1 and its last byte is a LF (the caller cuts a file
+ * at a LF and appends one to a last line that has none).  Line k is what lies between the k-th LF
+ * and the next.  Outputs: samples [n_lines][input_size] int16, labels [n_lines] int32, kinds
+ * [n_lines] (one byte each), *n_lines, and *first_bad_line = the smallest k whose kind is not
+ * DBH_TEXT_OK, or -1.  The row and the label of a line that is not DBH_TEXT_OK are unspecified.
+ * The caller's arrays hold max_lines lines; a block with more gives DBH_ERR_INVALID_ARGUMENT with
+ * *n_lines set to the block's count and nothing else written - never a write past the end.
+ * Stateless and replayable: a line's result depends on its bytes and input_size alone, not on the
+ * block it is in, its place or alignment there, or how the blocks were cut.
+ *
+ * Errors, before any device work: a null pointer, input_size < 1, n_bytes < 0, max_lines < 0, an
+ * empty block or one whose last byte is not a LF: DBH_ERR_INVALID_ARGUMENT; input_size > 2^20 or
+ * n_bytes > 2^30: DBH_ERR_UNSUPPORTED.
+ *
+ * dbh_text_parse: `block` is host memory; uploads it, runs four launches on one stream (the LFs
+ * per tile, their prefix, the line starts, one wave per line), synchronises once and downloads the
+ * n_lines results.  Every device buffer is sized from n_bytes, input_size and max_lines before the
+ * first launch.  dbh_text_parse_host: the same parser on the CPU - the walk in the same 1,024-byte
+ * steps and 16-byte pieces - and no device; the two agree bit for bit on kinds, n_lines,
+ * first_bad_line and on the rows and labels of DBH_TEXT_OK lines.  dbh_text_stage_ms: what the
+ * calling thread's last successful dbh_text_parse spent, in ms - upload and kernels by device
+ * events, download by the host's clock. */
+#define DBH_TEXT_OK 0
+#define DBH_TEXT_FORM 1
+#define DBH_TEXT_COUNT 2
+#define DBH_TEXT_RANGE 3
+int dbh_text_parse(const uint8_t* block_host, int64_t n_bytes, int input_size, int64_t max_lines,
+                   int16_t* samples_host, int32_t* labels_host, uint8_t* kinds_host,
+                   int64_t* n_lines, int64_t* first_bad_line);
+int dbh_text_parse_host(const uint8_t* block_host, int64_t n_bytes, int input_size, int64_t max_lines,
+                        int16_t* samples_host, int32_t* labels_host, uint8_t* kinds_host,
+                        int64_t* n_lines, int64_t* first_bad_line);
+int dbh_text_stage_ms(double* upload, double* kernels, double* download);
+
 /* ---- introspection ------------------------------------------------------------------------ */
 /* Activations after stage 'A'..'G'  for n_windows windows, row-major
  * [window][position][channel]; out_host must hold n_windows * dbh_stage_floats(stage) floats. */
