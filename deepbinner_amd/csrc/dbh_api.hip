@@ -117,6 +117,7 @@ struct dbh_model {
     int cus_total = 256;         // ... before dbh_model_reserve_cus took some away
     bool windows_by_counter = true;        // DEEPBINNER_STATIC_WINDOWS=1: fixed shares (A/B)
     bool launch_per_batch = false;   // DEEPBINNER_LAUNCH_PER_BATCH=1: one launch per batch (A/B)
+    bool forward_lean = true;        // DEEPBINNER_FORWARD_BUILD=full: production launches on the full kernel (A/B)
     // The end of a persistent launch: with fewer than chunk4_rounds x grid windows not yet handed
     // out a workgroup asks for groups of 2 instead of 4, below chunk2_rounds x grid for single
     // windows (DEEPBINNER_CHUNK4_ROUNDS / DEEPBINNER_CHUNK2_ROUNDS: A/B)
@@ -215,7 +216,13 @@ int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev
         a.phases = m->phase_probe ? 1 : 0;
         a.chunk4_min_left = m->chunk4_rounds * (int)grid;
         a.chunk2_min_left = m->chunk2_rounds * (int)grid;
-        DBH_HIP(dbh_kernels::launch_forward(a, grid, stream));
+        // production launches run the lean build of the kernel (dbh_lean.hip); the debug stages,
+        // the 100 + k timing stops and the timeline stay on the full one.  (The lean build keeps
+        // the phase stamps - compiling them out as well measured +0.3 %, inside the runs' spread -
+        // so phase_cycles_per_group is still measured on the kernel that ships.)
+        const bool lean = m->forward_lean && debug_stage < 0;
+        DBH_HIP(lean ? dbh_kernels::launch_forward_lean(a, grid, stream)
+                     : dbh_kernels::launch_forward(a, grid, stream));
         if (timed) DBH_HIP(m->timing.end(stream));
     }
     return DBH_OK;
@@ -429,6 +436,8 @@ int dbh_model_create(const float* weights, int64_t n_floats, int n_classes, int 
     m->host_zero_copy = !(zc && zc[0] == '0');
     const char* sw = std::getenv("DEEPBINNER_STATIC_WINDOWS");
     m->windows_by_counter = !(sw && sw[0] == '1');
+    const char* fb = std::getenv("DEEPBINNER_FORWARD_BUILD");
+    m->forward_lean = !(fb && std::strcmp(fb, "full") == 0);
     if (const char* c4 = std::getenv("DEEPBINNER_CHUNK4_ROUNDS")) m->chunk4_rounds = std::atoi(c4);
     if (const char* c2 = std::getenv("DEEPBINNER_CHUNK2_ROUNDS")) m->chunk2_rounds = std::atoi(c2);
     if (e == hipSuccess) e = m->packed.reserve(packed.size() * sizeof(float));

@@ -57,20 +57,32 @@
 #include "dbh_layout.h"
 #include "dbh_seam.h"
 
-// This file is compiled twice, by the two units that build and launch its kernel: by dbh_kernels.hip
-// as namespace dbh with DBH_TIMELINE 0 (the product) and by dbh_timeline.hip as namespace
-// dbh_timeline with DBH_TIMELINE 1 (cycle stamps for tools/timeline.py).  The
+// This file is compiled three times, by the units that build and launch its kernel: by
+// dbh_kernels.hip as namespace dbh with DBH_TIMELINE 0 (the full kernel: every debug mode), by
+// dbh_timeline.hip as namespace dbh_timeline with DBH_TIMELINE 1 (cycle stamps for
+// tools/timeline.py), and by dbh_lean.hip as namespace dbh_lean with DBH_FORWARD_DEBUG 0 (what
+// production launches run).  The
 // stamps are global stores, and on gfx9 a store shares the vmcnt counter with the loads: one
 // conditional store anywhere makes hipcc wait for vmcnt(0) at every later use of a prefetched
 // register, so they must not even be compiled into the production kernel.
-// These two are the file's only build-time variants: what an experiment decided is plain code here
-// (HISTORY.md lists the switches that were retired), and a new one is a patched copy built beside
-// the product (the Makefile's EXTRA, tools/ab_variants.sh).
+// DBH_FORWARD_DEBUG 0 makes debug_stage the constant -1: the debug stages 0-7 with their dumps, the
+// 100 + k timing stops and tail_every_group fold away, and with them the scalars they kept alive
+// across the persistent loop (92 SGPRs spilled to vector lanes in the full kernel) and the waits
+// hipcc puts where their branches merge.  Nothing else differs: the same arithmetic, the same
+// requests in the same order.  With 1, the default, the kernel is instruction for instruction
+// the one from before the switch existed (tools/code_object.py --same).
+// These are the file's only build-time variants, each set by the including unit and never by a
+// -D: what an experiment decided is plain code here (HISTORY.md lists the switches that were
+// retired), and a new one is a patched copy built beside the product (the Makefile's EXTRA,
+// tools/ab_variants.sh).
 #ifndef DBH_FORWARD_NS
 #define DBH_FORWARD_NS dbh
 #endif
 #ifndef DBH_TIMELINE
 #define DBH_TIMELINE 0
+#endif
+#ifndef DBH_FORWARD_DEBUG
+#define DBH_FORWARD_DEBUG 1
 #endif
 
 namespace DBH_FORWARD_NS {
@@ -2425,7 +2437,11 @@ __global__ __launch_bounds__(kThreads, 2) void dbh_forward_kernel(ForwardArgs by
         return p;
     };
     const float* __restrict__ packed_entry = glob(args()->packed);
+#if DBH_FORWARD_DEBUG
     const int debug_stage = args()->debug_stage;
+#else
+    const int debug_stage = -1;     // (the lean build: the launching host code sends it nothing else)
+#endif
     // (window indices fit 32 bits: the host launches at most 2^20 reads at a time)
     const int n_windows = (int)args()->n_windows;
     // (the two pointers every window's first instructions branch on: read once - a scalar load at

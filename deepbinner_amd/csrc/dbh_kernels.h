@@ -1,5 +1,6 @@
 // dbh_kernels.h — what the host code of libdeepbinner_hip.so (dbh_api.hip, dbh_probes.h) sees of
-// the device units dbh_kernels.hip and dbh_timeline.hip (the forward kernel's cycle-stamp build): the
+// the device units dbh_kernels.hip, dbh_timeline.hip (the forward kernel's cycle-stamp build) and
+// dbh_lean.hip (its build without the debug stages, which production launches run): the
 // forward kernel's arguments and launch shape, and one launch function per kernel.  No kernel
 // symbol leaves its unit.
 #pragma once
@@ -46,14 +47,21 @@ namespace dbh_timeline {
 // is part of its kernel's mangled name; the cycle-stamp build's is the same fields.
 struct ForwardArgs : dbh::ForwardArgs {};
 }  // namespace dbh_timeline
+namespace dbh_lean {
+// (the lean build's: it never reads debug_stage, which its launches leave at -1)
+struct ForwardArgs : dbh::ForwardArgs {};
+}  // namespace dbh_lean
 
 // The launches: each queues one kernel on `stream` and returns hipGetLastError().
 namespace dbh_kernels {
 
-// dbh::dbh_forward_kernel / dbh_timeline::dbh_forward_kernel: grid workgroups of dbh::kThreads
+// dbh::dbh_forward_kernel / dbh_timeline::dbh_forward_kernel / dbh_lean::dbh_forward_kernel: grid
+// workgroups of dbh::kThreads.  launch_forward_lean is for production launches only (debug_stage
+// < 0): the lean kernel has no debug stages, timing stops or tail behind every group.
 hipError_t launch_forward(const dbh::ForwardArgs& a, unsigned grid, hipStream_t stream);
 hipError_t launch_forward_timeline(const dbh::ForwardArgs& a, unsigned grid, hipStream_t stream);
-// (dbh_forward_kernel_info: the production build's registers and LDS)
+hipError_t launch_forward_lean(const dbh::ForwardArgs& a, unsigned grid, hipStream_t stream);
+// (dbh_forward_kernel_info: the full build's registers and LDS; the lean build's are the same)
 hipError_t forward_attributes(hipFuncAttributes* attr);
 
 // dbh::dbh_normalise_kernel: one block per window, windows <= 2^31 - 1

@@ -3,9 +3,10 @@
 metadata (registers, spills, scratch, LDS) of every kernel of the library and a census of the forward
 kernel's instruction stream.  A kernel's stream is what its ELF symbol covers (disassemble()), so
 its count and digest do not depend on which kernels share its code object or on their order.
-Used by tests/test_code_object.py
-(the CPU-box guard on what ships) and by hand:  python tools/code_object.py [lib.so]
-                                                python tools/code_object.py --same OLD.so NEW.so"""
+Used by tests/test_code_object.py and tests/test_code_object_lean.py
+(the CPU-box guards on what ships) and by hand: python tools/code_object.py [lib.so]
+                                                python tools/code_object.py --same OLD.so NEW.so
+                                                python tools/code_object.py --bless [lean]"""
 import collections
 import hashlib
 import json
@@ -214,15 +215,19 @@ def lgkm_wait_histogram(insts):
 
 
 FORWARD = '_ZN3dbh18dbh_forward_kernel'      # dbh::dbh_forward_kernel, whichever code object holds it
+LEAN = '_ZN8dbh_lean18dbh_forward_kernel'    # dbh_lean::dbh_forward_kernel (csrc/dbh_lean.hip)
+# what --bless writes for which kernel prefix
+GOLDEN = {FORWARD: 'code_object.json', LEAN: 'code_object_lean.json'}
 META = ('vgpr_count', 'agpr_count', 'sgpr_count', 'vgpr_spill_count', 'sgpr_spill_count',
         'private_segment_fixed_size', 'group_segment_fixed_size')
 
 
-def summary(lib):
-    """everything tests/test_code_object.py looks at, as one dict"""
+def summary(lib, prefix=FORWARD):
+    """everything tests/test_code_object.py looks at, as one dict, for the kernel whose symbol starts
+    with `prefix` (the full forward kernel unless told otherwise: LEAN is the lean build's)"""
     with tempfile.TemporaryDirectory() as d:
         md = all_kernel_metadata(lib, d)
-        fwd = next(n for n in md if n.startswith(FORWARD))
+        fwd = next(n for n in md if n.startswith(prefix))
         co, meta = md[fwd]
         insts = disassemble(co, fwd)
         c = census(insts)
@@ -275,13 +280,17 @@ def main():
         sys.exit(1 if differ else 0)
     if len(sys.argv) > 1 and sys.argv[1] == '--bless':
         # record what the built library carries (tests/golden/code_object.json): run after every
-        # deliberate change of the forward kernel, and read the diff
+        # deliberate change of the forward kernel, and read the diff.  --bless PREFIX (or `lean`)
+        # does the same for another build of it: `--bless lean` writes code_object_lean.json
         lib = os.path.join(os.path.dirname(__file__), '..', 'deepbinner_amd', 'libdeepbinner_hip.so')
-        s = summary(lib)
+        prefix = FORWARD if len(sys.argv) < 3 else LEAN if sys.argv[2] == 'lean' else sys.argv[2]
+        if prefix not in GOLDEN:
+            sys.exit(f'--bless: no golden file for kernel prefix {prefix!r} (known: {sorted(GOLDEN)})')
+        s = summary(lib, prefix)
         keep = {'mfma_static': s['census']['mfma'], 'lds_dma': s['census'].get('lds_dma', 0),
                 's_barrier': s['census'].get('s_barrier', 0), 'lgkm_waits': s['lgkm_waits'],
                 'vgpr_count': int(s['metadata']['vgpr_count']), 'sgpr_spill_count': int(s['metadata']['sgpr_spill_count'])}
-        path = os.path.join(os.path.dirname(__file__), '..', 'tests', 'golden', 'code_object.json')
+        path = os.path.join(os.path.dirname(__file__), '..', 'tests', 'golden', GOLDEN[prefix])
         json.dump(keep, open(path, 'w'), indent=1, sort_keys=True)
         print(json.dumps(keep, indent=1, sort_keys=True))
         return
