@@ -9,7 +9,9 @@
 
 namespace dbh_feed {
 
-// the layer numbers of dbh_train.h's hash that the feed uses (dropout has 1..7, the noise 0)
+// the layer numbers of dbh_train.h's hash that the feed uses (dropout has 1..7, the noise 0; the
+// random signals of dbh_random_core.h take 11..14: kLayerSignal, kLayerSegment, kLayerDraw,
+// kLayerGradient)
 constexpr uint32_t kLayerChance = 8, kLayerKey = 9, kLayerOrder = 10;
 
 struct View {

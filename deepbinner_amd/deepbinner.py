@@ -3,10 +3,11 @@ Command line of the classify path: the ``classify`` and ``realtime`` sub-command
 defaults, validation and error messages of the reference's ``deepbinner/deepbinner.py``
 (:90-156 options, :283-345 checks and preset resolution), so that existing command lines keep
 working, plus ``bin`` (:159-176), the consumer of the table ``classify`` writes.  The options are
-declared as data (``OPTIONS``) and turned into argparse calls by one loop.  ``fit`` is the
-reference's ``train`` (:246-269: the same options and defaults, plus ``--seed``) on the resident
-trainer - under another name, because ``train`` and the reference's other training-side
-sub-commands (prep, balance, refine) answer with a one-line refusal.
+declared as data (``OPTIONS``) and turned into argparse calls by one loop.  The training side:
+``balance`` (:228-243, plus ``--seed``) and ``refine`` (:272-280, plus the fused ``--model`` form)
+are the reference's commands, and ``fit`` is its ``train`` (:246-269: the same options and
+defaults, plus ``--seed``) on the resident trainer - under another name, because ``train`` and
+``prep`` answer with a one-line refusal.
 """
 
 import argparse
@@ -15,7 +16,7 @@ import sys
 
 from .version import __version__
 
-NOT_PROVIDED = ('prep', 'balance', 'train', 'refine')
+NOT_PROVIDED = ('prep', 'train')
 PRESETS = {'native': ('EXP-NBD103_read_starts', 'EXP-NBD103_read_ends'),
            'rapid': ('SQK-RBK004_read_starts', None)}
 TWO_MODEL_FLAGS = ('require_either', 'require_start', 'require_both')
@@ -141,6 +142,45 @@ COMMANDS = {
                                       'whole blocks on the device with the same result (default: '
                                       'DEEPBINNER_TEXT_PARSE, else host)')),
              _HELP]),
+    'balance': ('Select balanced training set',
+                [('Positional', [
+                    (('training_data',), dict(type=str, nargs='+',
+                                              help='Files of raw training data produced by the '
+                                                   'prep command'))]),
+                 None],
+                [(('--barcodes',), dict(type=str,
+                                        help='A comma-delimited list of which barcodes to include '
+                                             '(default: include all barcodes)')),
+                 (('--random_signal',), dict(type=float, default=1.0,
+                                             help='This many random signals will be added to the '
+                                                  'output as no-barcode training samples '
+                                                  '(expressed as a multiple of the balanced '
+                                                  'per-barcode count, default: 1.0)')),
+                 (('--seed',), dict(type=int, default=0,
+                                    help='Seed of the selection and of the random signals (the '
+                                         'same seed gives the same output, byte for byte)')),
+                 _HELP]),
+    'refine': ('Refine the training set',
+               [('Positional', [
+                   (('training_data',), dict(type=str,
+                                             help='Balanced training data produced by the balance '
+                                                  'command')),
+                   (('classification_data',), dict(type=str, nargs='?', default=None,
+                                                   help='Training data barcode calls produced by '
+                                                        'the classify command (or give --model)'))]),
+                None],
+               [(('--model',), dict(type=str, default=None,
+                                    help='Classify the training data with this model here, '
+                                         'instead of reading a classification file')),
+                (('--scan_size',), dict(type=float, default=6144,
+                                        help="With --model: this much of a sample's signal will "
+                                             "be examined for barcode signals")),
+                (('--score_diff',), dict(type=float, default=0.5,
+                                         help='With --model: the difference between the best and '
+                                              'second-best barcode scores that a call needs')),
+                (('--batch_size',), dict(type=int, default=256,
+                                         help='With --model: samples handed to the GPU per call')),
+                _HELP]),
 }
 USES_MODELS = ('classify', 'realtime')
 
@@ -177,7 +217,7 @@ def main(argv=None):
         sys.exit(1)
     if argv[0] in NOT_PROVIDED:
         sys.exit('Error: the {} command is not part of this build - it covers the classify, '
-                 'realtime and bin commands only'.format(argv[0]))
+                 'realtime, bin, balance, fit and refine commands only'.format(argv[0]))
     args = parser.parse_args(argv)
     if args.subparser_name in USES_MODELS:
         check_classify_and_realtime_arguments(args)
@@ -189,6 +229,10 @@ def main(argv=None):
         from .bin import bin_reads as run
     elif args.subparser_name == 'fit':
         from .fit import fit as run
+    elif args.subparser_name == 'balance':
+        from .balance import balance as run
+    elif args.subparser_name == 'refine':
+        from .refine import refine as run
     else:
         return
     run(args)

@@ -694,6 +694,94 @@ int dbh_text_parse_host(const uint8_t* block_host, int64_t n_bytes, int input_si
                         int64_t* n_lines, int64_t* first_bad_line);
 int dbh_text_stage_ms(double* upload, double* kernels, double* download);
 
+/* ---- random signals: the synthetic no-barcode samples of `balance` ------------------------------ */
+/* The reference's balance command appends random signals as no-barcode samples (balance.py:155-193):
+ * one of four kinds, drawn one random.gauss and one str() per value.  Here value i of signal s is a
+ * function of (seed, s, i, input_size) alone - the reference's law, not its Mersenne-Twister
+ * stream.  DESIGN.md section 23; csrc/dbh_random_core.h is the generator, compiled into the kernel
+ * and into the host model; tests/random_signal_reference.py restates it in NumPy.
+ *
+ * bits(layer, s, p, c) is dbh_gradients' hash (see "training" above) with the halves of `seed`,
+ * the free layer numbers 11..14, s as its window, p as its position and c as its channel: 24 bits.
+ * u(b) = b / 2^24.  All arithmetic is fp64, one IEEE operation per operation written here, left to
+ * right; a value is truncated toward zero (a C cast, Python's int()).
+ *
+ * Per signal, b_c = bits(11, s, 0, c):
+ *     kind    = b_0 % 4          0 flat, 1 gaussian, 2 multi_gaussian, 3 perlin
+ *     level   = b_1 % 1001
+ *     mean    = 300 + 300 * u(b_2)          stdev  = 10 + 490 * u(b_3)
+ *     octaves = 1 + b_4 % 4                 step   = 0.001 + 0.039 * u(b_5)
+ *     start   = u(b_6)                      factor = 10 + 290 * u(b_7)
+ * (the ranges of balance.py:164-190).
+ *   flat            every value is level.
+ *   gaussian        z(i) = sqrt(-2 * log(u1)) * cos(6.283185307179586 * u2) with
+ *                   u1 = (bits(13, s, i, 0) + 1) / 2^24 and u2 = bits(13, s, i, 1) / 2^24 - the
+ *                   trainer's Box-Muller - and value = trunc(mean + stdev * z(i)).
+ *   multi_gaussian  segment k = 0, 1, ... holds 100 + bits(12, s, k, 0) % 401 values, laid end to
+ *                   end from value 0, with its own mean = 300 + 300 * u(bits(12, s, k, 1)) and
+ *                   stdev = 10 + 490 * u(bits(12, s, k, 2)); value i = trunc(mean_k + stdev_k * z(i))
+ *                   of the segment k it lies in.
+ *   perlin          gradient noise of noise.pnoise1's construction with hashed gradients (not its
+ *                   permutation table).  x = start + i * step; sum = weights = 0; for k = 0 ..
+ *                   octaves - 1 in turn, with amp = 0.5^k:
+ *                       xk = x * 2^k;  j = floor(xk);  t = xk - j
+ *                       g(j) = 2 * u(bits(14, s, j, k)) - 1
+ *                       f = t * t * t * (t * (t * 6 - 15) + 10)
+ *                       a = g(j) * t;  b = g(j + 1) * (t - 1);  n = a + f * (b - a)
+ *                       sum = sum + amp * 2 * n;  weights = weights + amp
+ *                   value = trunc(mean + factor * (sum / weights)).
+ * Every value lies far inside int16.  log and cos are the math library's: a host and the device
+ * may differ in their last place, which moves a truncated value (by one) only where the value
+ * before truncation lies on an integer; everything else is bit for bit.
+ *
+ * out: int16 [n_signals][input_size], signal first_signal + k in row k - a range may be cut into
+ * calls anywhere.  Errors, before any device work: a null pointer, n_signals < 1, input_size < 1,
+ * first_signal < 0 or first_signal + n_signals > 2^32: DBH_ERR_INVALID_ARGUMENT; input_size > 2^20
+ * or n_signals * input_size > 2^30: DBH_ERR_UNSUPPORTED.
+ * dbh_random_signals: out is host memory; one launch, one synchronisation, one download.  _dev:
+ * device memory, queued on `stream`, never synchronised.  _host: the same generator on the CPU,
+ * no device. */
+int dbh_random_signals(uint64_t seed, int64_t first_signal, int64_t n_signals, int input_size,
+                       int16_t* out_host);
+int dbh_random_signals_dev(uint64_t seed, int64_t first_signal, int64_t n_signals, int input_size,
+                           int16_t* out_dev, dbh_stream stream);
+int dbh_random_signals_host(uint64_t seed, int64_t first_signal, int64_t n_signals, int input_size,
+                            int16_t* out_host);
+
+/* ---- training-data text, written: int16 rows to the lines dbh_text_parse reads -------------------- */
+/* labels [n_lines] int32 and samples [n_lines][input_size] int16 become the bytes
+ *     label TAB v1 ',' v2 ',' ... vL LF          per line, numbers as Python's str() writes them
+ * - the strict grammar above, so dbh_text_parse gives the arrays back.  csrc/dbh_format_core.h is
+ * the formatter, compiled into the kernels and into the host model; DESIGN.md section 23.
+ * A value takes 1 to 6 bytes and the byte behind it; a label is '0' or up to nine digits with an
+ * optional '-' (a label outside +-(10^9 - 1): DBH_ERR_INVALID_ARGUMENT).  dbh_text_format_bound:
+ * n_lines * (12 + 7 * input_size), which no text exceeds.
+ *
+ * `out` holds `capacity` bytes; *n_bytes becomes the text's length.  A capacity below it gives
+ * DBH_ERR_INVALID_ARGUMENT with *n_bytes set to the need and nothing written - never a write past
+ * the end.  Errors, before any device work: a null pointer, n_lines < 1, input_size < 1,
+ * capacity < 0: DBH_ERR_INVALID_ARGUMENT; input_size > 2^20 or n_lines * input_size > 2^30:
+ * DBH_ERR_UNSUPPORTED.
+ *
+ * dbh_text_format: host memory; uploads, five launches on one stream (the bytes of each line, one
+ * wave per line; their prefix over tiles of 1,024 lines, in three; the bytes themselves, one wave
+ * per line), one synchronisation, and
+ * the text's bytes downloaded.  Every device buffer is sized from n_lines, input_size and the
+ * capacity before the first launch.  _dev: device memory throughout, queued on `stream`, never
+ * synchronised; workspace_dev holds dbh_text_format_workspace_bytes(n_lines) bytes, 8-byte
+ * aligned; *n_bytes_dev becomes the length, or -1 for a refused label, and nothing is written to
+ * out_dev where it is -1 or above the capacity.  _host: the same formatter on the CPU, no device;
+ * the three agree byte for byte. */
+int dbh_text_format_bound(int64_t n_lines, int input_size, int64_t* bytes);
+int dbh_text_format_workspace_bytes(int64_t n_lines, size_t* bytes);
+int dbh_text_format(const int32_t* labels_host, const int16_t* samples_host, int64_t n_lines,
+                    int input_size, uint8_t* out_host, int64_t capacity, int64_t* n_bytes);
+int dbh_text_format_dev(const int32_t* labels_dev, const int16_t* samples_dev, int64_t n_lines,
+                        int input_size, uint8_t* out_dev, int64_t capacity, int64_t* n_bytes_dev,
+                        void* workspace_dev, dbh_stream stream);
+int dbh_text_format_host(const int32_t* labels_host, const int16_t* samples_host, int64_t n_lines,
+                         int input_size, uint8_t* out_host, int64_t capacity, int64_t* n_bytes);
+
 /* ---- introspection ------------------------------------------------------------------------ */
 /* Activations after stage 'A'..'G'  for n_windows windows, row-major
  * [window][position][channel]; out_host must hold n_windows * dbh_stage_floats(stage) floats. */
