@@ -11,6 +11,11 @@ batch forms that give the device something to do:
   ``locate_adapters(signals, adapter, side)``               all reads of a batch in one call
   ``locate_barcodes(signals, adapter_positions, barcodes, side)``
 
+and two host pieces beside them:
+
+  ``trim_positions(signals)``                               section 21's integer trim rule
+  ``read_squiggles(path)``, ``write_squiggles(path, table)``
+
 The expected squiggles of adapters and barcodes are not part of this package: the caller passes
 them.  The sequence stage of ``prep`` (mappy, edlib) does not exist here and ``prep`` as a command
 stays refused.
@@ -296,3 +301,118 @@ def align_barcode_to_read_dtw(barcode_search_signal, barcode_search_signal_start
         print('  verdict: skipping due to high barcode DTW distance', file=sys.stderr)
         return None, None
     return start, end
+
+
+# ------------------------------------------------------------------------------------------------
+# Host pieces: the trim rule in integers for a list of reads, and the
+# expected squiggles as a text file.
+TRIM_SKIP, TRIM_STEP, TRIM_AHEAD, TRIM_NEEDED = 10, 25, 5, 4      # trim_signal.py:24-58
+TRIM_BOUND = 250000            # 25 Q - S^2 above this: a population std above 20.0 (section 21)
+
+
+TRIM_FIRST_LOOK = 16           # windows looked at first: most reads begin within 410 samples
+
+
+def _trim_look(signals, windows):
+    """The trim rule over the first ``windows`` windows of every read at once.  Returns an int64
+    array: the position, -1 (CannotTrim), or -2 where the rule needs windows further on."""
+    n = len(signals)
+    n_full = np.array([0 if len(s) < TRIM_SKIP + TRIM_STEP else (len(s) - TRIM_SKIP) // TRIM_STEP
+                       for s in signals], dtype=np.int64)
+    seen = np.minimum(n_full, windows)
+    block = np.zeros((n, windows * TRIM_STEP), dtype=np.int64)     # padding: windows that are not high
+    for r, signal in enumerate(signals):
+        take = int(seen[r]) * TRIM_STEP
+        block[r, :take] = signal[TRIM_SKIP:TRIM_SKIP + take]
+    x = block.reshape(n, windows, TRIM_STEP)
+    s, q = x.sum(axis=2), (x * x).sum(axis=2)
+    high = TRIM_STEP * q - s * s > TRIM_BOUND
+    running = np.concatenate((np.zeros((n, 1), dtype=np.int64), np.cumsum(high, axis=1)), axis=1)
+    ahead = np.zeros((n, windows), dtype=np.int64)                 # high among k .. k+4
+    whole = windows - TRIM_AHEAD + 1
+    ahead[:, :whole] = running[:, TRIM_AHEAD:] - running[:, :whole]
+    last = np.arange(windows)[None, :] + TRIM_AHEAD - 1            # k + 4
+    known = last < seen[:, None]               # all five windows are among those looked at
+    beyond = last >= n_full[:, None]           # (b): the look-ahead leaves the read
+    stop = high & known & (ahead >= TRIM_NEEDED)                   # (c)
+    event = stop | (high & ~known)             # (c), (b), or a high window that needs more
+    first = np.argmax(event, axis=1)
+    rows = np.arange(n)
+    out = np.where(stop[rows, first], TRIM_SKIP + TRIM_STEP * first,
+                   np.where(beyond[rows, first], -1, -2))
+    # no event: (a) at the end of the read, or quiet so far
+    return np.where(event.any(axis=1), out, np.where(seen == n_full, -1, -2)).astype(np.int64)
+
+
+def trim_positions(signals):
+    """The trim position of every raw int16 read of a list, by the integer rule of DESIGN.md
+    section 21, as an int64 array: what ``find_signal_start_pos`` returns, and -1 where it raises
+    ``CannotTrim``.  The first 16 windows of all reads are decided in one set of NumPy operations;
+    the reads whose rule needs windows further on are looked at again, eight times as far each
+    time - in place of one ``np.std`` per window and read."""
+    signals = [_as_int16(s) for s in signals]
+    positions = np.full(len(signals), -1, dtype=np.int64)
+    todo, windows = np.arange(len(signals)), TRIM_FIRST_LOOK
+    while len(todo):
+        found = _trim_look([signals[r] for r in todo], windows)
+        positions[todo] = found
+        todo = todo[found == -2]
+        windows *= 8
+    return positions
+
+
+def _barcode_number(name):
+    if not name.isdigit() or len(name) > 4:
+        raise ValueError('a squiggle is named adapter or by its barcode number, not {!r}'
+                         .format(name))
+    return int(name)
+
+
+def read_squiggles(path):
+    """Expected squiggles from a text file, one per line: ``name<TAB>v1,v2,...``.  The name
+    ``adapter`` is required; every other name is a barcode number (``01``, ``1``, ...).  Returns
+    ``{'adapter': float64 array, 1: float64 array, ...}``.  ValueError, naming the line, for a
+    duplicate name, a missing ``adapter``, and an empty, non-numeric or non-finite value."""
+    table = {}
+    with open(path, 'rt') as lines:
+        for number, line in enumerate(lines, 1):
+            line = line.rstrip('\r\n')
+            if not line.strip():
+                continue
+            where = 'line {} of {}'.format(number, path)
+            parts = line.split('\t')
+            if len(parts) != 2:
+                raise ValueError('{}: expected name<TAB>v1,v2,...'.format(where))
+            name = parts[0].strip()
+            try:
+                key = name if name == 'adapter' else _barcode_number(name)
+            except ValueError as e:
+                raise ValueError('{}: {}'.format(where, e))
+            if key in table:
+                raise ValueError('{}: a second squiggle named {}'.format(where, name))
+            try:
+                values = np.array([float(v) for v in parts[1].split(',')], dtype=np.float64)
+            except ValueError:
+                raise ValueError('{}: an empty or non-numeric value'.format(where))
+            if not np.isfinite(values).all():
+                raise ValueError('{}: a value that is not finite'.format(where))
+            table[key] = values
+    if 'adapter' not in table:
+        raise ValueError('{}: no squiggle named adapter'.format(path))
+    return table
+
+
+def write_squiggles(path, table):
+    """The counterpart of ``read_squiggles``: ``adapter`` first, then the barcodes in ascending
+    number, every value by ``repr`` so that it reads back to the same double."""
+    if 'adapter' not in table:
+        raise ValueError('no squiggle named adapter')
+    names = ['adapter'] + sorted(k for k in table if k != 'adapter')
+    with open(path, 'wt') as out:
+        for key in names:
+            values = np.asarray(table[key], dtype=np.float64).ravel()
+            if not len(values) or not np.isfinite(values).all():
+                raise ValueError('squiggle {} is empty or holds a value that is not finite'
+                                 .format(key))
+            name = key if key == 'adapter' else '{:02d}'.format(int(key))
+            out.write('{}\t{}\n'.format(name, ','.join(repr(float(v)) for v in values)))
