@@ -103,6 +103,13 @@ int main() {
         ok = ok && check_text(l, s, size);
         ok = ok && check_text({l[5]}, std::vector<int16_t>(s.begin(), s.begin() + size), size);
     }
+    // long rows: 100,003 values (no multiple of the wave's 64) and 2^20, the longest the entries take
+    for (int size : {100003, 1 << 20}) {
+        std::vector<int32_t> l = {labels[5], labels[4]};
+        std::vector<int16_t> s((size_t)2 * size);
+        for (size_t p = 0; p < s.size(); ++p) s[p] = extremes[(p * 7 + p / size) % n_extremes];
+        ok = ok && check_text(l, s, size);
+    }
     // a label outside +-(10^9 - 1) is refused
     {
         int32_t bad[2] = {0, 1000000000};
@@ -114,10 +121,13 @@ int main() {
         ok = ok && dbh_text_format_host(bad, v, 2, 1, out, 64, &n_bytes) == 1;
     }
     // every kind of signal, at L = 1, around one segment (96, 102), and over many segments
-    for (int size : {1, 96, 102, 1024, 16384}) {
+    // (131,072 values: more than the 256 segments of 500 that the kernel draws at a time; 2^20: the
+    // longest row - of these, 8 signals from 0 on and the 4 last ones)
+    for (int size : {1, 96, 102, 1024, 16384, 131072, 1 << 20}) {
         int kinds[4] = {0, 0, 0, 0};
-        ok = ok && check_signals(5 + (uint64_t)size, 0, size > 1024 ? 24 : 64, size, kinds);
-        ok = ok && check_signals(0xfeedfacecafef00dull, ((int64_t)1 << 32) - 8, 8, size, kinds);
+        const int64_t n = size > 16384 ? 8 : (size > 1024 ? 24 : 64), at_end = size > 16384 ? 4 : 8;
+        ok = ok && check_signals(5 + (uint64_t)size, 0, n, size, kinds);
+        ok = ok && check_signals(0xfeedfacecafef00dull, ((int64_t)1 << 32) - at_end, at_end, size, kinds);
         for (int k = 0; k < 4; ++k) ok = ok && kinds[k] > 0;
         if (!ok) std::fprintf(stderr, "format_model_check: signals of %d values failed\n", size);
     }

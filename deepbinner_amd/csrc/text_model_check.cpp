@@ -130,6 +130,11 @@ int main() {
                     ok = check_block({line.substr(0, cut), line}, shift, input_size);
         }
     }
+    {   // one line of 2^20 values, the most a line may hold: thousands of steps, at two alignments
+        std::string longest = "-999999999\t0";
+        for (int i = 1; i < (1 << 20); ++i) longest += "," + std::to_string((int)((i * 7919LL) % 65536) - 32768);
+        for (int shift : {0, 15}) ok = ok && check_block({longest}, shift, 1 << 20);
+    }
     std::printf("text_model_check: %ld blocks, %ld lines: %s\n", g_blocks, g_lines, ok ? "clean" : "FAILED");
     return ok ? 0 : 1;
 }

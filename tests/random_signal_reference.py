@@ -5,6 +5,8 @@ kinds go through ``log`` and ``cos`` of another library, which can move a trunca
 only where the value before truncation lies on an integer - ``signals`` returns each value's
 distance from the nearest integer so that a test can demand that its cases stay clear of that.
 """
+import functools
+
 import numpy as np
 
 import train_reference as tr
@@ -102,6 +104,58 @@ def signals(seed, first, n, size):
         nearest = min(nearest, near)
     return np.stack(rows), np.array(kinds), nearest
 
+
+# Rows past one chunk of 256 multi_gaussian segments (256 * 500 = 128,000 values), and the longest
+# row the entries take: 8 signals each, seed 3 + size, first signal 0.  Both hold all four kinds,
+# every multi_gaussian one has more than 256 segments, and the guard holds (test_random_signals.py).
+LONG_SIZES = [131072, 2 ** 20]
+LONG_SIGNALS = 8
+# More signals than the grid has workgroups (65,536), of 102 values - the smallest row with two
+# segments.  The guard over all 6.7 million values holds at seed 8, the first seed tried.
+MANY_SEED, MANY_SIGNALS, MANY_SIZE = 8, 65536 + 64, 102
+
+
+@functools.lru_cache(maxsize=None)
+def long_case(size):
+    """signals() of a LONG_SIZES case, computed once; the rows are read-only"""
+    rows, kinds, nearest = signals(3 + size, 0, LONG_SIGNALS, size)
+    rows.setflags(write=False)
+    return rows, kinds, nearest
+
+
+@functools.lru_cache(maxsize=None)
+def many_case_nearest():
+    return nearest_of_many(MANY_SEED, 0, MANY_SIGNALS, MANY_SIZE)
+
+
+def nearest_of_many(seed, first, n, size):
+    """signals()' third result for n short signals, without a loop over the signals: the draws are
+    hashed for every (signal, position) at once, and only the multi_gaussian signals walk their
+    segments, all of them together, segment number by segment number"""
+    s = np.arange(first, first + n, dtype=np.uint64)
+    kind = bits(seed, LAYER_SIGNAL, s, 0, 0) % np.uint64(4)
+    drawn = np.flatnonzero((kind == GAUSSIAN) | (kind == MULTI_GAUSSIAN))
+    if not drawn.size:
+        return np.inf
+    multi = kind[drawn] == MULTI_GAUSSIAN
+    column, i = s[drawn][:, None], np.arange(size, dtype=np.uint64)[None, :]
+    u1 = (bits(seed, LAYER_DRAW, column, i, 0).astype(np.float64) + 1.0) / 16777216.0
+    u2 = bits(seed, LAYER_DRAW, column, i, 1).astype(np.float64) / 16777216.0
+    z = np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)
+    mean = np.broadcast_to((300.0 + 300.0 * unit(bits(seed, LAYER_SIGNAL, column, 0, 2))), z.shape).copy()
+    stdev = np.broadcast_to((10.0 + 490.0 * unit(bits(seed, LAYER_SIGNAL, column, 0, 3))), z.shape).copy()
+    walkers = s[drawn][multi]
+    seg_mean, seg_stdev = np.empty((walkers.size, size)), np.empty((walkers.size, size))
+    at, k, places = np.zeros(walkers.size, dtype=np.int64), 0, np.arange(size)[None, :]
+    while (at < size).any():
+        length = 100 + (bits(seed, LAYER_SEGMENT, walkers, k, 0) % np.uint64(401)).astype(np.int64)
+        inside = (places >= at[:, None]) & (places < (at + length)[:, None])
+        seg_mean = np.where(inside, (300.0 + 300.0 * unit(bits(seed, LAYER_SEGMENT, walkers, k, 1)))[:, None], seg_mean)
+        seg_stdev = np.where(inside, (10.0 + 490.0 * unit(bits(seed, LAYER_SEGMENT, walkers, k, 2)))[:, None], seg_stdev)
+        at, k = at + length, k + 1
+    mean[multi], stdev[multi] = seg_mean, seg_stdev
+    raw = mean + stdev * z
+    return float(np.abs(raw - np.rint(raw)).min())
 
 
 def nearest_at_size_one(seed, first, n):

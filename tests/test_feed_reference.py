@@ -15,6 +15,11 @@ from deepbinner_amd.model_format import param_count
 INVALID, BAD_WEIGHTS, UNSUPPORTED = 1, 4, 5
 # a key tie that straddles a rank boundary: (input size, seed, slot)
 TIES = [(16384, 7, 29), (1024, 24, 36)]
+# The same for the sizes at which an assembling thread holds 2, 3, 5 and 16 positions and the last
+# busy thread fewer (tests/test_gpu_feed.py): for each size the first hit of a search over seeds
+# 0..1999 and slots 0..63, seeds in order, every size found (seeds 24, 10, 1 and 8).
+PARTIAL_SIZES = [1026, 2050, 5000, 16382]
+PARTIAL_TIES = [(1026, 24, 36), (2050, 10, 14), (5000, 1, 13), (16382, 8, 29)]
 
 
 # ---- normalise -----------------------------------------------------------------------------------
@@ -39,9 +44,10 @@ def test_normalise_has_the_reference_formulas_fp32_bits(length):
 # ---- augment -------------------------------------------------------------------------------------
 def test_half_is_pythons_round():
     assert [fr.half_of(n) for n in (96, 98, 102, 130, 1024, 16384)] == [24, 24, 26, 32, 256, 4096]
+    assert [fr.half_of(n) for n in PARTIAL_SIZES] == [256, 512, 1250, 4096]
 
 
-@pytest.mark.parametrize('length', [96, 98, 102, 130, 1024])
+@pytest.mark.parametrize('length', [96, 98, 102, 130, 1024] + PARTIAL_SIZES)
 def test_augment_doubles_half_drops_half_and_keeps_the_order(length):
     half = fr.half_of(length)
     for slot in range(4):
@@ -78,7 +84,7 @@ def test_doubling_is_uniform_over_positions():
     assert abs(chosen - n / 2) <= 5 * np.sqrt(n / 4)
 
 
-@pytest.mark.parametrize('length,seed,slot', TIES)
+@pytest.mark.parametrize('length,seed,slot', TIES + PARTIAL_TIES)
 def test_equal_keys_rank_by_index(length, seed, slot):
     keys = fr.keys_of(seed, slot, length)
     half = fr.half_of(length)

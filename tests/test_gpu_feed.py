@@ -55,6 +55,14 @@ def signal_windows(length, n, classes):
 BATCH_CASES = [(96, 8, 1.0, 1), (96, 64, 2.0, tr.SEED), (98, 9, 1e9, 2), (102, 11, 2.0, tr.HIGH_SEED),
                (130, 16, 1e9, 3), (1024, 33, 2.0, 4), (16384, 8, 2.0, 5),
                (1024, 40, 1e9, 24), (16384, 30, 1e9, 7)]
+# Sizes between 1024 and 16384, where a thread holds `per` = 2 .. 16 positions and the last busy
+# thread fewer: 1026 (per 2, 513 threads busy), 2050 (per 3, thread 683 holds one), 5000 (per 5,
+# 1,000 busy), 16382 (per 16, the last thread holds 14).  Then each size again with a key tie
+# across a rank boundary in an augmented slot (tests/test_feed_reference.py, PARTIAL_TIES).
+BATCH_CASES += [(1026, 10, 1e9, 11), (2050, 10, 2.0, 12), (5000, 10, 1e9, 13), (16382, 10, 1e9, 14),
+                (1026, 40, 1e9, 24), (2050, 16, 1e9, 10), (5000, 14, 1e9, 1), (16382, 30, 1e9, 8)]
+# (input size, seed, slot) of the key ties
+TIES = [(16384, 7, 29), (1024, 24, 36), (1026, 24, 36), (2050, 10, 14), (5000, 1, 13), (16382, 8, 29)]
 
 
 @pytest.mark.parametrize('length,slots,aug,seed', BATCH_CASES, ids=str)
@@ -65,7 +73,7 @@ def test_batch_equals_the_numpy_restatement_bit_for_bit(hip, length, slots, aug,
     indices = rng.integers(n, size=slots)
     indices[:6] = [0, n - 1, n - 4, n - 3, n - 2, n - 1]      # both ends, a repeat, the special windows
     indices[-1] = 0
-    for tie_length, tie_seed, tie_slot in ((16384, 7, 29), (1024, 24, 36)):
+    for tie_length, tie_seed, tie_slot in TIES:
         if (length, seed) == (tie_length, tie_seed):
             assert slots > tie_slot and fr.slot_is_augmented(seed, tie_slot, fr.augment_threshold(aug))
     want_x, want_labels = fr.batch(samples, labels, indices, aug, seed)
@@ -92,6 +100,39 @@ def test_batch_equals_the_numpy_restatement_bit_for_bit(hip, length, slots, aug,
         changed = (bits(x) != bits(plain)).any(axis=1)
         constant = indices == n - 4
         assert (changed == (np.array(augmented) & ~constant)).all()
+
+
+def test_windows_past_the_stats_grid(hip):
+    """65,536 + 40 windows of 96: window_stats runs 65,536 workgroups, so the last 40 windows are
+    their workgroups' second, and their mean, deviation and label lie past index 65,535.  The last
+    40 are signal_windows' draws and special windows."""
+    classes, grid = 5, 65536
+    rng = np.random.default_rng(96)
+    tail, tail_labels = signal_windows(96, 40, classes)
+    level = rng.integers(300, 700, size=(grid, 1))
+    front = (level + rng.integers(-200, 201, size=(grid, 96))).astype(np.int16)
+    samples = np.concatenate([front, tail])
+    labels = np.concatenate([rng.integers(classes, size=grid).astype(np.int32), tail_labels])
+    n = grid + 40
+    indices = np.array([0, grid - 1, grid, n - 1, n - 4, n - 3, n - 2, grid + 1, grid + 17, 1, n - 1])
+    aug, seed = 2.0, 6
+    picked = samples[indices]
+    want_x, want_labels = fr.batch(picked, labels[indices], np.arange(indices.size), aug, seed)
+    augmented = [fr.slot_is_augmented(seed, w, fr.augment_threshold(aug)) for w in range(indices.size)]
+    assert any(augmented) and not all(augmented)
+    with hip.Dataset.from_arrays(samples, labels, classes) as data:
+        assert len(data) == n
+        x, got_labels = data.batch(indices, aug, seed)
+        same_bits(x, want_x, 'batch')
+        assert (got_labels == want_labels).all()
+        x, got_labels = data.batch(indices, 1.0)
+        same_bits(x, fr.normalise(picked), 'aug = 1')
+        assert (got_labels == labels[indices]).all()
+        # every window's statistics, through batches of all of them in turn
+        plain = fr.normalise(samples)
+        for first in range(0, n, 8192):
+            some = np.arange(first, min(first + 8192, n))
+            same_bits(data.batch(some, 1.0)[0], plain[some], 'windows from {}'.format(first))
 
 
 def test_batch_refuses_before_it_works(hip):

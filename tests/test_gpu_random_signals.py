@@ -51,6 +51,52 @@ def test_one_signal_of_every_kind(hip, size):
         assert np.array_equal(hip.random_signals(seed, s, 1, size), model)
 
 
+def long_model(hip, size):
+    """the CPU model's 8 signals of a long row, once per size, after the guard; with their kinds"""
+    key = (3 + size, 0, rr.LONG_SIGNALS, size)
+    if key not in _guarded:
+        want, kinds, nearest = rr.long_case(size)
+        assert nearest > rr.GUARD
+        assert set(kinds.tolist()) == {rr.FLAT, rr.GAUSSIAN, rr.MULTI_GAUSSIAN, rr.PERLIN}
+        for s in np.flatnonzero(kinds == rr.MULTI_GAUSSIAN):
+            assert rr.segments(3 + size, int(s), size)[2] > 256      # a second chunk of segments
+        model = hip.random_signals(3 + size, 0, rr.LONG_SIGNALS, size, host=True)
+        assert np.array_equal(model, want)
+        model.setflags(write=False)
+        _guarded[key] = (model, kinds)
+    return _guarded[key]
+
+
+def first_difference(got, model, size):
+    """where a row of the device first leaves the model: signal, value, and the chunk of 256
+    segments in which a multi_gaussian value there lies at the earliest (a segment holds 500 at most)"""
+    differ = np.flatnonzero(np.ravel(got) != np.ravel(model))
+    if not differ.size:
+        return None
+    s, i = divmod(int(differ[0]), size)
+    return 'signal {} value {} (chunk {} or later): {} against {}; {} values differ'.format(
+        s, i, i // (256 * 500), np.ravel(got)[differ[0]], np.ravel(model)[differ[0]], differ.size)
+
+
+@pytest.mark.parametrize('size', rr.LONG_SIZES)
+def test_rows_past_one_chunk_of_segments(hip, size):
+    """131,072 values: above 256 * 500, so every multi_gaussian signal takes a second chunk of 256
+    segments - the start carried over, the tables in LDS written again, the bisection in a chunk
+    that does not begin at 0; 2^20, the longest row: 14 chunks or so"""
+    model, _ = long_model(hip, size)
+    got = hip.random_signals(3 + size, 0, rr.LONG_SIGNALS, size)
+    assert got.dtype == np.int16 and first_difference(got, model, size) is None
+
+
+def test_one_long_signal_of_every_kind(hip):
+    size = rr.LONG_SIZES[0]
+    model, kinds = long_model(hip, size)
+    for kind in range(4):
+        s = int(np.flatnonzero(kinds == kind)[0])
+        got = hip.random_signals(3 + size, s, 1, size)
+        assert first_difference(got, model[s:s + 1], size) is None, kind
+
+
 def test_a_range_may_be_cut_anywhere_and_replayed(hip):
     model, _ = guarded_model(hip, 3 + 1024, 0, 64, 1024)
     parts = [hip.random_signals(3 + 1024, 0, 10, 1024), hip.random_signals(3 + 1024, 10, 54, 1024)]
@@ -78,3 +124,17 @@ def test_more_signals_than_the_grid_has_workgroups(hip):
     model = hip.random_signals(8, 0, 70000, 1, host=True)
     assert np.array_equal(model[:300], rr.signals(8, 0, 300, 1)[0])
     assert np.array_equal(hip.random_signals(8, 0, 70000, 1), model)
+
+
+def test_a_workgroups_second_signal_has_rows_of_its_own(hip):
+    """65,536 + 64 signals of 102 values: the last 64 are their workgroups' second signals, of
+    every kind, the multi_gaussian ones with two segments - behind a first signal of any kind"""
+    seed, n, size = rr.MANY_SEED, rr.MANY_SIGNALS, rr.MANY_SIZE
+    assert rr.many_case_nearest() > rr.GUARD                  # over all 6.7 million values
+    model = hip.random_signals(seed, 0, n, size, host=True)
+    for first, count in ((0, 300), (n - 64, 64)):
+        want, kinds, _ = rr.signals(seed, first, count, size)
+        assert np.array_equal(model[first:first + count], want)
+        assert set(kinds.tolist()) == {rr.FLAT, rr.GAUSSIAN, rr.MULTI_GAUSSIAN, rr.PERLIN}
+    got = hip.random_signals(seed, 0, n, size)
+    assert first_difference(got, model, size) is None

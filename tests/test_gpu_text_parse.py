@@ -71,6 +71,35 @@ def test_block_sizes_and_replay(hip, case):
         assert first[3] == -1 and not first[2].any()
 
 
+@pytest.mark.parametrize('refused', tr.MANY_VARIANTS, ids=str)
+def test_more_lines_than_the_grid_has_waves(hip, refused):
+    """70,000 lines of 7 values over 32,768 waves: lines 32,768.. are a wave's second, lines
+    65,536.. its third.  The first refused line is the minimum over all trips: line 0 of the first,
+    line 40,000 of the second where line 0 is strict, line 69,999 of the third where it alone is
+    refused."""
+    data = tr.many_lines(refused)
+    samples, labels, kinds, first_bad = both(hip, data, tr.MANY_SIZE)
+    assert len(kinds) == tr.MANY_LINES and first_bad == refused[0]
+    assert np.flatnonzero(kinds).tolist() == list(refused)
+    assert [int(kinds[k]) for k in refused] == [tr.REFUSED[k][0] for k in refused]
+
+
+@pytest.mark.parametrize('shift', tr.LONG_SHIFTS)
+@pytest.mark.parametrize('input_size', tr.LONG_SIZES)
+def test_lines_past_16384_values(hip, input_size, shift):
+    """lines of 100,003 and of 2^20 values, hundreds and thousands of steps each: OK, a value out
+    of range three from the end, a value short.  (At shift > 0 the line in front is refused too:
+    tests/test_text_parse.py, test_model_equals_the_restatement_on_long_lines.)"""
+    lines, values = tr.long_lines(input_size)
+    data, skipped = tr.block(lines, shift)
+    samples, labels, kinds, first_bad = both(hip, data, input_size)
+    assert kinds[skipped:].tolist() == [tr.OK, tr.RANGE, tr.COUNT]
+    assert first_bad == (0 if skipped else 1) and np.flatnonzero(kinds[skipped:])[0] == 1
+    differ = np.flatnonzero(samples[skipped] != np.array(values))
+    assert differ.size == 0, 'the OK line differs from the restatement first at value {}'.format(differ[0])
+    assert labels[skipped] == int(lines[0].split(b'\t')[0])
+
+
 def test_more_lines_than_the_arrays_hold(hip):
     data = b'\n' * 5000 + b'1\t5\n'
     with pytest.raises(hip.HipBackendError):

@@ -24,6 +24,32 @@ def test_host_model_equals_the_restatement(seed, first, n, size):
     assert np.array_equal(got, want)
 
 
+@pytest.mark.parametrize('size', rr.LONG_SIZES)
+def test_host_model_equals_the_restatement_past_one_chunk_of_segments(size):
+    """8 signals of more than 256 * 500 values: the kernel draws a multi_gaussian's segments 256 at
+    a time, and the device is held to this model at these sizes (tests/test_gpu_random_signals.py)"""
+    seed = 3 + size
+    want, kinds, nearest = rr.long_case(size)
+    assert nearest > rr.GUARD
+    assert set(kinds.tolist()) == {rr.FLAT, rr.GAUSSIAN, rr.MULTI_GAUSSIAN, rr.PERLIN}
+    for s in np.flatnonzero(kinds == rr.MULTI_GAUSSIAN):
+        assert rr.segments(seed, int(s), size)[2] > 256
+    got = hip_backend.random_signals(seed, 0, rr.LONG_SIGNALS, size, host=True)
+    assert got.dtype == np.int16 and np.array_equal(got, want)
+
+
+def test_the_guard_of_many_short_signals():
+    """tests/test_gpu_random_signals.py guards 65,600 signals of 102 values with this"""
+    for seed, first, n, size in [(5, 0, 40, 102), (5, 2 ** 32 - 64, 64, 300), (9, 7, 30, 96), (4, 5, 50, 1)]:
+        assert rr.nearest_of_many(seed, first, n, size) == rr.signals(seed, first, n, size)[2]
+    seed, n, size = rr.MANY_SEED, rr.MANY_SIGNALS, rr.MANY_SIZE
+    assert rr.many_case_nearest() > rr.GUARD
+    # the model on both ends of the range; the device is held to the model on all of it
+    for first, count in ((0, 300), (n - 64, 64)):
+        want = rr.signals(seed, first, count, size)[0]
+        assert np.array_equal(hip_backend.random_signals(seed, first, count, size, host=True), want)
+
+
 def test_the_guard_of_many_one_value_signals():
     """tests/test_gpu_random_signals.py guards 70,000 signals of one value with this"""
     assert rr.nearest_at_size_one(4, 5, 300) == rr.signals(4, 5, 300, 1)[2]

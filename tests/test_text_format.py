@@ -36,6 +36,29 @@ def test_many_short_lines_and_a_split():
     assert whole == b''.join(parts)
 
 
+@pytest.mark.parametrize('size', fr.LONG_SIZES)
+def test_host_model_writes_long_rows_as_python_does(size):
+    """the device is held to this model at these sizes (tests/test_gpu_text_format.py)"""
+    labels, samples, want = fr.long_rows(size)
+    got = hip_backend.format_training_text(labels, samples, host=True)
+    assert got == want
+    assert len(got) <= fr.bound(2, size) == hip_backend.text_format_bound(2, size)
+    back, back_labels, kinds, first_bad = hip_backend.parse_training_text_host(got, size)
+    assert first_bad == -1 and not kinds.any()
+    assert np.array_equal(back, samples) and np.array_equal(back_labels, labels)
+
+
+def test_more_lines_than_the_tile_scan_has_threads_and_a_split():
+    """1,100,000 lines are 1,075 tiles of 1,024: the device's scan over tiles gives a thread two"""
+    labels, samples, want = fr.many_lines()
+    assert (len(labels) + 1023) // 1024 == 1075 and fr.SPLIT % 1024
+    whole = hip_backend.format_training_text(labels, samples, host=True)
+    assert whole == want
+    parts = [hip_backend.format_training_text(labels[a:b], samples[a:b], host=True)
+             for a, b in ((0, fr.SPLIT), (fr.SPLIT, fr.MANY_LINES))]
+    assert whole == b''.join(parts)
+
+
 def test_write_training_data_is_read_back(tmp_path):
     labels, samples = fr.rows(65)
     path = tmp_path / 'written.txt'

@@ -44,6 +44,49 @@ def test_the_corpus_meets_every_seam():
     assert all(kinds.get(k, 0) >= 5 for k in (tr.OK, tr.FORM, tr.COUNT, tr.RANGE))
 
 
+@pytest.mark.parametrize('refused', tr.MANY_VARIANTS, ids=str)
+def test_model_equals_the_restatement_on_more_lines_than_the_grid_has_waves(refused):
+    """70,000 lines: the device is held to this model on them (tests/test_gpu_text_parse.py)"""
+    data = tr.many_lines(refused)
+    got = model(data, tr.MANY_SIZE)
+    tr.same_as_restatement(got, data, tr.MANY_SIZE)
+    assert len(got[2]) == tr.MANY_LINES and got[3] == refused[0]
+    assert np.flatnonzero(got[2]).tolist() == list(refused)
+    assert [int(got[2][k]) for k in refused] == [tr.REFUSED[k][0] for k in refused]
+
+
+@pytest.mark.parametrize('shift', tr.LONG_SHIFTS)
+@pytest.mark.parametrize('input_size', tr.LONG_SIZES)
+def test_model_equals_the_restatement_on_long_lines(input_size, shift):
+    """lines of 100,003 and of 2^20 values - hundreds and thousands of 1,024-byte steps - OK, with
+    a value out of range near the end, and a value short.  At shift > 0 the line that block() puts
+    in front is itself refused (it is never strict), so first_bad is 0 there and the RANGE line is
+    the first refused one behind it."""
+    lines, values = tr.long_lines(input_size)
+    data, skipped = tr.block(lines, shift)
+    assert len(lines[0]) > 4 * input_size > 115 * 1024
+    got = model(data, input_size)
+    tr.same_as_restatement(got, data, input_size)
+    assert got[2][skipped:].tolist() == [tr.OK, tr.RANGE, tr.COUNT]
+    assert got[3] == (0 if skipped else 1) and np.flatnonzero(got[2][skipped:])[0] == 1
+    assert got[0][skipped].tolist() == values
+
+
+def test_the_long_lines_meet_every_seam():
+    """in each long OK line, at each alignment it is run at, a value begins at every place of a
+    1,024-byte step - so at each of the places around the step seam, split every way, and at
+    every place of a 16-byte piece - and the value out of range lies in the line's last step"""
+    for input_size in tr.LONG_SIZES:
+        lines, _ = tr.long_lines(input_size)
+        text = np.frombuffer(lines[0], dtype=np.uint8)
+        separators = np.flatnonzero((text == ord(',')) | (text == ord('\t')))
+        for shift in tr.LONG_SHIFTS:
+            starts = shift + separators + 1          # from the 16-byte boundary the walk begins at
+            assert np.unique(starts % 1024).size == 1024
+            steps = (shift + len(lines[1]) + 1023) // 1024
+            assert steps > 115 and (shift + lines[1].rindex(b'40000')) // 1024 == steps - 1
+
+
 def test_kinds_come_in_order():
     data = b'x\t99999\n1\t99999\n1\t99999,1\n1\t1,2\n'
     samples, labels, kinds, first_bad = model(data, 2)

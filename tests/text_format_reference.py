@@ -1,6 +1,8 @@
 """A helper, not a test: training-data text as Python itself writes it - the contract of
 ``include/deepbinner_hip.h``, "training-data text, written"  - and the rows
 that the formatter's tests, with and without a device, share."""
+import functools
+
 import numpy as np
 
 MAX_LABEL = 10 ** 9 - 1
@@ -37,3 +39,32 @@ def many_short_lines(n, seed=3):
     rng = np.random.RandomState(seed)
     labels = rng.choice(LABELS, size=n).astype(np.int32)
     return labels, rng.randint(-32768, 32768, size=(n, 1)).astype(np.int16)
+
+
+# Rows of more than 16,384 values, kept out of SIZES (which the tests multiply by other
+# parameters): 100,003 is no multiple of 64, so a wave's last step of 64 values is a partial one,
+# and 2^20 is the longest row the entries take (16,384 steps; several million bytes carried).
+LONG_SIZES = [100003, 2 ** 20]
+# More lines than the scan over tiles of 1,024 lines has threads: 1,075 tiles, two to a thread,
+# the last busy thread with one.  SPLIT is no multiple of 1,024.
+MANY_LINES, SPLIT = 1100000, 500003
+
+
+@functools.lru_cache(maxsize=None)
+def long_rows(input_size):
+    """(labels, samples [2, input_size], Python's text of them), once per size: the row of every
+    width in turn and a full-range draw, under the widest label and -1"""
+    _, samples = rows(input_size)
+    labels, samples = np.array([999999999, -1], dtype=np.int32), samples[[5, 3]].copy()
+    samples.setflags(write=False)
+    labels.setflags(write=False)
+    return labels, samples, text(labels, samples)
+
+
+@functools.lru_cache(maxsize=None)
+def many_lines():
+    """(labels, samples, Python's text) of many_short_lines(MANY_LINES), once"""
+    labels, samples = many_short_lines(MANY_LINES)
+    samples.setflags(write=False)
+    labels.setflags(write=False)
+    return labels, samples, text(labels, samples)

@@ -3,6 +3,7 @@ DESIGN.md section 22) restated with regular expressions, and the corpus that the
 (dbh_text_parse_host) and the device entry (dbh_text_parse) are both held to.  Nothing here looks
 at how the parser walks a line; the corpus is built so that its 1,024-byte steps and 16-byte
 pieces fall everywhere."""
+import functools
 import random
 import re
 
@@ -127,6 +128,50 @@ def random_strict_line(rng, n_values, crlf=False):
         sign = b'-' if v < 0 else rng.choice([b'', b'', b'', b'+'])
         values.append(sign + text)
     return label + b'\t' + b','.join(values) + (b'\r' if crlf else b'')
+
+
+# ---- beyond the corpus: more lines than the grid has waves, and lines past 16,384 values ------------
+# 70,000 lines of 7 values: the parse kernel's 8,192 workgroups hold 32,768 waves, a line each, so
+# lines 32,768.. are a wave's second and lines 65,536.. its third.  A variant names the lines it
+# has refused: one each of FORM, COUNT and RANGE.
+MANY_LINES, MANY_SIZE = 70000, 7
+REFUSED = {0: (FORM, b'1\t5,,6,1,2,3,4'), 40000: (COUNT, b'1\t5,6,1,2,3,4'),
+           69999: (RANGE, b'1\t5,6,1,40000,2,3,4')}
+MANY_VARIANTS = [(0, 40000, 69999), (40000, 69999), (69999,)]
+LONG_SIZES = [100003, 2 ** 20]
+LONG_SHIFTS = (0, 1, 15)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_strict_lines():
+    # 2,003 lines of random_strict_line, every one used 34 or 35 times: 2,003 is prime, so line k
+    # and line k + 32,768 (one wave's first and second) are never the same text
+    rng = random.Random(70)
+    pool = [random_strict_line(rng, MANY_SIZE, crlf=rng.random() < 0.1) for _ in range(2003)]
+    return [pool[(5 * k) % 2003] for k in range(MANY_LINES)]
+
+
+def many_lines(refused):
+    """the block of MANY_LINES lines with REFUSED's lines at the indices `refused`"""
+    lines = list(_many_strict_lines())
+    for k in refused:
+        lines[k] = REFUSED[k][1]
+    return b''.join(line + b'\n' for line in lines)
+
+
+@functools.lru_cache(maxsize=None)
+def long_lines(input_size):
+    """(lines, the OK line's values): an OK line of `input_size` values, the same with a value out
+    of range three from its end, and the same a value short - kinds OK, RANGE, COUNT.  The OK
+    line's values are those of one random_strict_line of 10,007 values, over and over: its text is
+    no multiple of 16 bytes long, so every round falls elsewhere in the pieces and steps."""
+    rng = random.Random(input_size)
+    label, values = random_strict_line(rng, 10007).split(b'\t')
+    values = values.split(b',')
+    values = (values * (input_size // len(values) + 1))[:input_size]
+    out_of_range = values[:-3] + [b'40000'] + values[-2:]
+    lines = [label + b'\t' + b','.join(v) for v in (values, out_of_range, values[:-1])]
+    return lines, [int(v) for v in values]
 
 
 def block(lines, shift=0):
