@@ -25,29 +25,22 @@
 #include "dbh_layout.h"
 #include "dbh_owned.h"
 #include "dbh_pack.h"
-#include "dbh_train.h"
+#include "dbh_status.h"
 
 namespace {
-
 thread_local std::string g_last_error;
+}  // namespace
 
-int hip_fail(hipError_t e, const char* what) {
+// (every unit that reports through dbh_last_error() comes here: dbh_status.h)
+int dbh_hip::hip_fail(hipError_t e, const char* what) {
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? DBH_ERR_OUT_OF_MEMORY : DBH_ERR_HIP;
 }
 
-}  // namespace
-
-// (dbh_train.hip reports through the same text as everything else)
-int dbh_train::report_hip_error(hipError_t e, const char* what) { return hip_fail(e, what); }
-
 namespace {
 
-#define DBH_HIP(call)                                         \
-    do {                                                      \
-        hipError_t e_ = (call);                               \
-        if (e_ != hipSuccess) return hip_fail(e_, #call);     \
-    } while (0)
+using dbh_hip::hip_fail;
+
 #define DBH_TRY(call)                                         \
     do {                                                      \
         const int st_ = (call);                               \

@@ -20,8 +20,11 @@
 
 #include "../../include/deepbinner_hip.h"
 #include "dbh_general.h"
+#include "dbh_host_layout.h"
 #include "dbh_owned.h"
+#include "dbh_status.h"
 #include "dbh_train.h"
+#include "dbh_wave.h"
 
 #include <cmath>
 #include <new>
@@ -57,10 +60,8 @@ __global__ __launch_bounds__(kStatThreads) void window_stats(const int16_t* __re
             s += v;
             q += v * v;
         }
-        for (int o = kStatThreads / 2; o >= 1; o >>= 1) {
-            s += __shfl_xor(s, o);
-            q += __shfl_xor(q, o);
-        }
+        s = dbh_wave::wave_sum(s);
+        q = dbh_wave::wave_sum(q);
         if (threadIdx.x == 0) {
             const long long d = (long long)L * q - s * s;    // L^2 * variance, exact: below 2^59
             mean[w] = (double)s / (double)L;
@@ -77,7 +78,7 @@ __device__ inline float normalised(int16_t x, double mean, double sd) {
 // the sum of a word over the workgroup: shuffles within a wave, one LDS word per wave, one barrier
 // (the word buffers alternate with the round, so that a round's words outlive its readers)
 __device__ inline uint32_t block_sum(uint32_t v, uint32_t (*words)[kWaves], int round, int tid) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    v = dbh_wave::wave_sum(v);
     uint32_t* buf = words[round & 1];
     if ((tid & 63) == 0) buf[tid >> 6] = v;
     __syncthreads();
@@ -191,15 +192,8 @@ __global__ __launch_bounds__(kThreads) void assemble_kernel(View ds, const long 
         if (j >= per) break;
         if (key[j] != kNoKey) mine += copies_of(key[j], (uint32_t)(base + j), k1, i1, k2, i2);
     }
-    int scan = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(scan, o);
-        if ((tid & 63) >= o) scan += up;
-    }
-    if ((tid & 63) == 63) totals[tid >> 6] = scan;
-    __syncthreads();
-    int at = scan - mine;
-    for (int w = 0; w < (tid >> 6); ++w) at += totals[w];
+    int total;
+    int at = dbh_wave::block_prefix<kWaves>(mine, totals, &total);
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
         if (j >= per) break;
@@ -218,14 +212,6 @@ int check_batch(const dbh_dataset* ds, int64_t n_windows, double augmentation, u
     if (n_windows > dbh_train::kMaxBatchSamples / ds->view.input_size) return DBH_ERR_UNSUPPORTED;
     return DBH_OK;
 }
-
-#define DBH_FEED_HIP(call)                                                        \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, #call);      \
-    } while (0)
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -291,30 +277,31 @@ int dbh_dataset_create(const int16_t* samples_host, const int32_t* labels_host, 
     dbh_dataset* d = new (std::nothrow) dbh_dataset;
     if (!d) return DBH_ERR_OUT_OF_MEMORY;
     const size_t s_bytes = (size_t)n * input_size * sizeof(int16_t), l_bytes = (size_t)n * sizeof(int32_t);
-    const size_t at_l = up256(s_bytes), at_m = at_l + up256(l_bytes);
-    const size_t at_s = at_m + up256((size_t)n * sizeof(double));
-    hipError_t e = d->block.reserve(at_s + up256((size_t)n * sizeof(double)));
-    if (e == hipSuccess) e = hipMemcpy(d->block.as<char>(), samples_host, s_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d->block.as<char>(at_l), labels_host, l_bytes, hipMemcpyHostToDevice);
+    int16_t* samples;
+    int32_t* labels;
+    double *mean, *sd;
+    hipError_t e = d->block.carve([&](dbh_host::Carve& c) {
+        d->view.samples = samples = c.take<int16_t>((size_t)n * input_size);
+        d->view.labels = labels = c.take<int32_t>((size_t)n);
+        d->view.mean = mean = c.take<double>((size_t)n);
+        d->view.std = sd = c.take<double>((size_t)n);
+    });
+    if (e == hipSuccess) e = hipMemcpy(samples, samples_host, s_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(labels, labels_host, l_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
-        hipLaunchKernelGGL(window_stats, dim3(grid), dim3(kStatThreads), 0, 0,
-                           d->block.as<int16_t>(), (long long)n, input_size,
-                           d->block.as<double>(at_m), d->block.as<double>(at_s));
+        hipLaunchKernelGGL(window_stats, dim3(grid), dim3(kStatThreads), 0, 0, samples, (long long)n,
+                           input_size, mean, sd);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         delete d;
-        return dbh_train::report_hip_error(e, "dbh_dataset_create");
+        return dbh_hip::hip_fail(e, "dbh_dataset_create");
     }
     d->view.n = n;
     d->view.input_size = input_size;
     d->view.n_classes = n_classes;
-    d->view.samples = d->block.as<int16_t>();
-    d->view.labels = d->block.as<int32_t>(at_l);
-    d->view.mean = d->block.as<double>(at_m);
-    d->view.std = d->block.as<double>(at_s);
     *ds = d;
     return DBH_OK;
 }
@@ -340,8 +327,8 @@ int dbh_dataset_batch_dev(const dbh_dataset* ds, const int64_t* indices_dev, int
     const int st = check_batch(ds, n_windows, augmentation, &threshold);
     if (st != DBH_OK) return st;
     if (!indices_dev || !x_dev || !labels_dev) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_FEED_HIP(assemble(ds->view, indices_dev, 0, n_windows, threshold, seed, x_dev, labels_dev,
-                          (hipStream_t)stream));
+    DBH_HIP(assemble(ds->view, indices_dev, 0, n_windows, threshold, seed, x_dev, labels_dev,
+                     (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -355,15 +342,21 @@ int dbh_dataset_batch(const dbh_dataset* ds, const int64_t* indices_host, int64_
         if (indices_host[i] < 0 || indices_host[i] >= ds->view.n) return DBH_ERR_INVALID_ARGUMENT;
     const size_t i_bytes = (size_t)n_windows * sizeof(int64_t), l_bytes = (size_t)n_windows * sizeof(int32_t);
     const size_t x_bytes = (size_t)n_windows * ds->view.input_size * sizeof(float);
-    const size_t at_l = up256(i_bytes), at_x = at_l + up256(l_bytes);
+    int64_t* indices;
+    int32_t* labels;
+    float* x;
+    auto lay_out = [&](dbh_host::Carve& c) {
+        indices = c.take<int64_t>((size_t)n_windows);
+        labels = c.take<int32_t>((size_t)n_windows);
+        x = c.take<float>((size_t)n_windows * ds->view.input_size);
+    };
     dbh_owned::DeviceBlock block;
-    DBH_FEED_HIP(block.reserve(at_x + x_bytes));
-    DBH_FEED_HIP(hipMemcpyAsync(block.as<char>(), indices_host, i_bytes, hipMemcpyHostToDevice, 0));
-    DBH_FEED_HIP(assemble(ds->view, block.as<int64_t>(), 0, n_windows, threshold, seed,
-                          block.as<float>(at_x), block.as<int32_t>(at_l), 0));
-    DBH_FEED_HIP(hipStreamSynchronize(0));
-    DBH_FEED_HIP(hipMemcpy(x_host, block.as<char>(at_x), x_bytes, hipMemcpyDeviceToHost));
-    DBH_FEED_HIP(hipMemcpy(labels_host, block.as<char>(at_l), l_bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(block.carve(lay_out));
+    DBH_HIP(hipMemcpyAsync(indices, indices_host, i_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(assemble(ds->view, indices, 0, n_windows, threshold, seed, x, labels, 0));
+    DBH_HIP(hipStreamSynchronize(0));
+    DBH_HIP(hipMemcpy(x_host, x, x_bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(labels_host, labels, l_bytes, hipMemcpyDeviceToHost));
     return DBH_OK;
 }
 

@@ -57,24 +57,16 @@ __attribute__((visibility("default"))) int dbh_text_format_host(
 
 #if defined(__HIPCC__)
 #include "../../include/deepbinner_hip.h"
+#include "dbh_host_layout.h"
 #include "dbh_owned.h"
-#include "dbh_train.h"
+#include "dbh_status.h"
+#include "dbh_wave.h"
 
 namespace dbh_format_detail {
 
 constexpr int kLineThreads = 256, kLineWaves = kLineThreads / 64;
 constexpr int kLineBlocks = 8192;
 constexpr int kScanThreads = 1024;
-
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ int wave_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int below = __shfl_up(v, d);
-        if (lane >= d) v += below;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(kLineThreads) void line_bytes(const int32_t* __restrict__ labels,
                                                            const int16_t* __restrict__ samples,
@@ -86,26 +78,12 @@ __global__ __launch_bounds__(kLineThreads) void line_bytes(const int32_t* __rest
         const int16_t* row = samples + line * input_size;
         int32_t sum = 0;
         for (int32_t i = lane; i < input_size; i += 64) sum += dbf::value_width(row[i]) + 1;
-        const int32_t all = wave_scan(sum, lane);
+        const int32_t all = dbh_wave::wave_scan_inclusive(sum);
         if (lane == 63) {
             const int32_t label = labels[line];
             counts[line] = dbf::label_ok(label) ? all + dbf::label_width(label) + 1 : dbf::kBadLabel;
         }
     }
-}
-
-// inclusive prefix sum over the workgroup's kScanThreads threads, all of which call it, once
-__device__ __forceinline__ int64_t block_scan(int64_t v, int64_t* part) {
-    const int t = threadIdx.x;
-    part[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const int64_t below = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += below;
-        __syncthreads();
-    }
-    return part[t];
 }
 
 // a tile of kScanThreads lines per workgroup, a line per thread: the tile's bytes, -1 where a
@@ -117,7 +95,8 @@ __global__ __launch_bounds__(kScanThreads) void tile_bytes(const int32_t* __rest
     const int64_t line = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
     const int32_t c = line < n_lines ? counts[line] : 0;
     if (threadIdx.x == 0) any_bad = 0;
-    const int64_t incl = block_scan(c < 0 ? 0 : c, part);       // (barriers: any_bad is 0 behind it)
+    // (barriers in the scan: any_bad is 0 behind it)
+    const int64_t incl = dbh_wave::block_scan_inclusive<int64_t, kScanThreads>(c < 0 ? 0 : c, part);
     if (c < 0) any_bad = 1;                                     // every writer stores the same value
     __syncthreads();
     if (threadIdx.x == kScanThreads - 1) tiles[blockIdx.x] = any_bad ? -1 : incl;
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_tiles(int64_t* __restrict__
         bad = bad || c < 0;
         sum += c < 0 ? 0 : c;
     }
-    const int64_t incl = block_scan(sum, part);
+    const int64_t incl = dbh_wave::block_scan_inclusive<int64_t, kScanThreads>(sum, part);
     if (bad) any_bad = 1;
     int64_t running = incl - sum;
     for (int64_t i = first; i < last; ++i) {
@@ -164,7 +143,7 @@ __global__ __launch_bounds__(kScanThreads) void line_starts(const int32_t* __res
     const int64_t line = (int64_t)blockIdx.x * kScanThreads + threadIdx.x;
     const int32_t c = line < n_lines ? counts[line] : 0;
     const int64_t v = c < 0 ? 0 : c;
-    const int64_t incl = block_scan(v, part);
+    const int64_t incl = dbh_wave::block_scan_inclusive<int64_t, kScanThreads>(v, part);
     if (line < n_lines) starts[line] = tiles[blockIdx.x] + incl - v;
 }
 
@@ -192,7 +171,7 @@ __global__ __launch_bounds__(kLineThreads) void write_lines(const int32_t* __res
             const int32_t i = i0 + lane;
             const int32_t v = i < input_size ? row[i] : 0;
             const int32_t w = i < input_size ? dbf::value_width(v) + 1 : 0;
-            const int32_t incl = wave_scan(w, lane);
+            const int32_t incl = dbh_wave::wave_scan_inclusive(w);
             if (i < input_size) {
                 uint8_t* p = at + carried + incl - w;
                 dbf::put_number(p, v, w - 1, dbf::kValueDigits);
@@ -203,20 +182,18 @@ __global__ __launch_bounds__(kLineThreads) void write_lines(const int32_t* __res
     }
 }
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-inline int64_t tiles_of(int64_t n_lines) { return (n_lines + kScanThreads - 1) / kScanThreads; }
-// the line lengths (int32), the line starts (int64, one more than lines), the tiles (int64)
-inline size_t workspace_bytes(int64_t n_lines) {
-    return up256((size_t)n_lines * sizeof(int32_t)) + up256((size_t)(n_lines + 1) * sizeof(int64_t)) +
-           up256((size_t)tiles_of(n_lines) * sizeof(int64_t));
-}
-
+// The workspace: the line lengths, the line starts (one more than lines), the tiles.  Over a null
+// workspace it is sized (*bytes) and nothing is launched; over the caller's the same lines carve it.
 hipError_t launch(const int32_t* labels, const int16_t* samples, int64_t n_lines, int input_size,
-                  uint8_t* out, int64_t capacity, int64_t* n_bytes, void* workspace, hipStream_t stream) {
-    int32_t* counts = (int32_t*)workspace;
-    int64_t* starts = (int64_t*)((char*)workspace + up256((size_t)n_lines * sizeof(int32_t)));
-    int64_t* tiles = (int64_t*)((char*)starts + up256((size_t)(n_lines + 1) * sizeof(int64_t)));
-    const unsigned n_tiles = (unsigned)tiles_of(n_lines);
+                  uint8_t* out, int64_t capacity, int64_t* n_bytes, void* workspace, hipStream_t stream,
+                  size_t* bytes = nullptr) {
+    const unsigned n_tiles = dbh_host::blocks_for(n_lines, kScanThreads);
+    dbh_host::Carve c(workspace);
+    int32_t* counts = c.take<int32_t>((size_t)n_lines);
+    int64_t* starts = c.take<int64_t>((size_t)n_lines + 1);
+    int64_t* tiles = c.take<int64_t>(n_tiles);
+    if (bytes) *bytes = c.used;
+    if (!workspace) return hipSuccess;
     const int64_t want = (n_lines + kLineWaves - 1) / kLineWaves;
     const unsigned grid = (unsigned)(want < kLineBlocks ? want : kLineBlocks);
     hipLaunchKernelGGL(line_bytes, dim3(grid), dim3(kLineThreads), 0, stream, labels, samples, n_lines,
@@ -238,15 +215,17 @@ hipError_t launch(const int32_t* labels, const int16_t* samples, int64_t n_lines
     return hipGetLastError();
 }
 
+inline size_t workspace_bytes(int64_t n_lines) {
+    size_t bytes = 0;
+    (void)launch(nullptr, nullptr, n_lines, 0, nullptr, 0, nullptr, nullptr, 0, &bytes);
+    return bytes;
+}
+
 }  // namespace dbh_format_detail
 
 using namespace dbh_format_detail;
 
-#define DBH_FORMAT_HIP(call)                                                        \
-    do {                                                                            \
-        const hipError_t e_ = (call);                                               \
-        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, "dbh_text_format"); \
-    } while (0)
+#define DBH_FORMAT_HIP(call) DBH_HIP_AS("dbh_text_format", call)
 
 extern "C" {
 
@@ -281,25 +260,32 @@ int dbh_text_format(const int32_t* labels, const int16_t* samples, int64_t n_lin
     const size_t text_bytes = (size_t)(capacity < bound ? capacity : bound);
     const size_t label_bytes = (size_t)n_lines * sizeof(int32_t);
     const size_t sample_bytes = (size_t)n_lines * (size_t)input_size * sizeof(int16_t);
-    const size_t at_samples = up256(label_bytes);
-    const size_t at_total = at_samples + up256(sample_bytes);
-    const size_t at_work = at_total + 256;
-    const size_t at_text = at_work + workspace_bytes(n_lines);
+    int32_t* labels_dev;
+    int16_t* samples_dev;
+    int64_t* total_dev;
+    char* work;
+    uint8_t* text;
+    auto lay_out = [&](dbh_host::Carve& c) {
+        labels_dev = c.take<int32_t>((size_t)n_lines);
+        samples_dev = c.take<int16_t>((size_t)n_lines * (size_t)input_size);
+        total_dev = c.take<int64_t>(1);
+        work = c.take<char>(workspace_bytes(n_lines));
+        text = c.take<uint8_t>(text_bytes + 256);          // (slack behind the text)
+    };
     dbh_owned::DeviceBlock dev;
-    DBH_FORMAT_HIP(dev.reserve(at_text + text_bytes + 256));
+    DBH_FORMAT_HIP(dev.carve(lay_out));
     hipStream_t stream = 0;
-    DBH_FORMAT_HIP(hipMemcpyAsync(dev.as<char>(), labels, label_bytes, hipMemcpyHostToDevice, stream));
-    DBH_FORMAT_HIP(hipMemcpyAsync(dev.as<char>(at_samples), samples, sample_bytes, hipMemcpyHostToDevice, stream));
-    DBH_FORMAT_HIP(launch(dev.as<int32_t>(), dev.as<int16_t>(at_samples), n_lines, input_size,
-                          dev.as<uint8_t>(at_text), (int64_t)text_bytes, dev.as<int64_t>(at_total),
-                          dev.as<char>(at_work), stream));
+    DBH_FORMAT_HIP(hipMemcpyAsync(labels_dev, labels, label_bytes, hipMemcpyHostToDevice, stream));
+    DBH_FORMAT_HIP(hipMemcpyAsync(samples_dev, samples, sample_bytes, hipMemcpyHostToDevice, stream));
+    DBH_FORMAT_HIP(launch(labels_dev, samples_dev, n_lines, input_size, text, (int64_t)text_bytes,
+                          total_dev, work, stream));
     int64_t total = 0;
-    DBH_FORMAT_HIP(hipMemcpyAsync(&total, dev.as<char>(at_total), sizeof(total), hipMemcpyDeviceToHost, stream));
+    DBH_FORMAT_HIP(hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, stream));
     DBH_FORMAT_HIP(hipStreamSynchronize(stream));          // the one synchronisation
     if (total < 0) return DBH_ERR_INVALID_ARGUMENT;
     *n_bytes = total;
     if (total > capacity) return DBH_ERR_INVALID_ARGUMENT; // nothing written
-    DBH_FORMAT_HIP(hipMemcpy(out, dev.as<char>(at_text), (size_t)total, hipMemcpyDeviceToHost));
+    DBH_FORMAT_HIP(hipMemcpy(out, text, (size_t)total, hipMemcpyDeviceToHost));
     return DBH_OK;
 }
 

@@ -1,6 +1,6 @@
-// dbh_host_layout.h — the host-side arithmetic of dbh_api.hip that touches no HIP call: scan
-// steps, where things lie in the staging buffers, the order the inflate records travel in, the
-// staged copy.  No HIP include, so that oracle/api_host_test.cpp compiles it with a plain g++.
+// dbh_host_layout.h — the host-side arithmetic of libdeepbinner_hip.so that touches no HIP call:
+// regions of a buffer (align256, Carve), grid sizes, and dbh_api.hip's scan steps, staging layouts,
+// inflate record order and staged copy.  No HIP include: oracle/api_host_test.cpp compiles it with g++.
 #pragma once
 
 #include <algorithm>
@@ -24,6 +24,24 @@ inline int model_steps(int input_size, int scan_size) {
 }
 
 inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// workgroups of `threads` that cover n elements
+inline unsigned blocks_for(long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+// One buffer cut into regions by ONE sequence of take() calls that runs twice: over a null base it
+// sizes (every pointer null, `used` the bytes to allocate), over the buffer it carves, so the two
+// cannot disagree.  Every region is a multiple of 256 bytes.  A new layout is laid out with this.
+struct Carve {
+    char* base;
+    size_t used = 0;
+    explicit Carve(void* p) : base((char*)p) {}
+    template <typename T>
+    T* take(size_t count) {
+        T* p = base ? (T*)(base + used) : nullptr;
+        used += align256(count * sizeof(T));
+        return p;
+    }
+};
 
 // What comes back per group of the host-buffer pipeline (classify_host), packed: each present
 // model's probabilities, each present model's calls, the combined calls when both are there.

@@ -45,13 +45,18 @@
 #include <vector>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_host_layout.h"
 #include "dbh_inflate_core.h"
 #include "dbh_inflate_wave.h"
 #include "dbh_owned.h"
+#include "dbh_wave.h"
 
 namespace dbh_inflate_detail {
 
 using dbi::Lane;
+using dbh_wave::from_lane_before;
+using dbh_wave::wave_scan_inclusive;
+using dbh_wave::wave_sum;
 
 // what kernel 1 leaves for kernel 2 (and for the caller) per stream
 struct StreamInfo {
@@ -140,9 +145,6 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 __device__ __forceinline__ uint32_t uni(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
-__device__ __forceinline__ int wave_scan_i32(int v);
-// a value of the lane before (lane 0: its own)
-__device__ __forceinline__ uint32_t from_lane_before(uint32_t v) { return (uint32_t)__shfl_up((int)v, 1); }
 
 // a compiler barrier that also drains the wave's LDS queue: what other lanes wrote is there (a
 // wave's LDS operations execute in order; this is all the synchronisation ONE wave needs)
@@ -250,7 +252,7 @@ __device__ __forceinline__ StreamInfo tokens_wave_stream(
         // where every lane's tokens and bytes go; the lane in which the wanted number of bytes is
         // exceeded ends the chunk, if that comes first
         const int cnt_m = lane <= last ? r.count : 0, bytes_m = lane <= last ? r.bytes : 0;
-        const int incl_c = wave_scan_i32(cnt_m), incl_b = wave_scan_i32(bytes_m);
+        const int incl_c = wave_scan_inclusive(cnt_m), incl_b = wave_scan_inclusive(bytes_m);
         const unsigned long long m_over = __ballot(lane <= last && out_pos + incl_b > out_cap);
         if (m_over) {
             const int over = __ffsll((long long)m_over) - 1;
@@ -310,28 +312,6 @@ __global__ __launch_bounds__(dbi::kWaveLanes) __attribute__((amdgpu_waves_per_eu
 }
 
 static_assert(dbi::kStepTokens == 64, "one token per lane and step");
-
-// Wave-wide inclusive prefix sum on the DPP network (no LDS round trips): within rows of 16
-// lanes by shifts, then each row's total handed on to the rows behind it.
-__device__ __forceinline__ int wave_scan_i32(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);      // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);      // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);      // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);      // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);      // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);      // row_bcast:31 -> rows 2, 3
-    return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Kernel 2: one wave per stream and up to 64 tokens per step (dbh_inflate_core.h: "Phase 2's
@@ -405,7 +385,7 @@ __device__ __forceinline__ StepTokens place_step(uint32_t raw, int first, int n_
     s.is_match = s.valid && (raw & dbi::kMatchFlag);
     s.len = !s.valid ? 0 : s.is_match ? (int)(raw & 0x1FFu) : 1;
     s.dist = (int)((raw >> 9) & 0x7FFFu) + 1;
-    const int incl = wave_scan_i32(s.len);
+    const int incl = wave_scan_inclusive(s.len);
     s.total = __builtin_amdgcn_readlane(incl, 63);
     s.count = n_tok - first < 64 ? n_tok - first : 64;
     if (s.total > dbi::kStepSpan) {                    // (rare: long matches)
@@ -439,7 +419,7 @@ struct AdlerSums {
     }
     // (wave-uniform) the stream's Adler-32, n = its length
     __device__ __forceinline__ unsigned finish(unsigned n) const {
-        const unsigned long long S = wave_sum_u32(bytes) % 65521u, P = wave_sum_u64(weighted) % 65521ull;
+        const unsigned long long S = wave_sum(bytes) % 65521u, P = wave_sum(weighted) % 65521ull;
         const unsigned long long nm = n % 65521u;
         const unsigned s1 = (unsigned)((1ull + S) % 65521ull);
         const unsigned s2 = (unsigned)((nm + nm * S + 65521ull - P) % 65521ull);
@@ -798,8 +778,7 @@ int dbh_inflate_dev(const uint8_t* comp_dev, int64_t comp_bytes,
     if (!comp_dev || !streams_dev || !out_dev || !workspace_dev || !status_dev)
         return DBH_ERR_INVALID_ARGUMENT;
     uint32_t* tokens = (uint32_t*)workspace_dev;
-    char* behind = (char*)workspace_dev +
-                   (((size_t)total_out_bytes * sizeof(uint32_t) + 255) & ~(size_t)255);
+    char* behind = (char*)workspace_dev + dbh_host::align256((size_t)total_out_bytes * sizeof(uint32_t));
     StreamInfo* info = (StreamInfo*)(behind + 256);      // (the 256 bytes in front: unused, kept
     const int n = (int)n_streams;                        //  so that the records do not move)
     if (pair_of_waves()) {

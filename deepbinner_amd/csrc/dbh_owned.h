@@ -1,13 +1,15 @@
 // dbh_owned.h — move-only owners of what the HIP runtime hands out: a device block, a pinned host
 // block, a stream, an event.  Whoever holds one as a member frees it by being destroyed; nothing in
 // libdeepbinner_hip.so keeps a list of things to free.  Failures come back as the hipError_t of the
-// call that failed, for the caller's own status mapping (DBH_HIP / hip_fail in dbh_api.hip).
+// call that failed, for the caller's own status mapping (DBH_HIP / hip_fail: dbh_status.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <utility>
+
+#include "dbh_host_layout.h"
 
 namespace dbh_owned {
 namespace {      // (internal linkage: each translation unit of the library has its own copy)
@@ -48,6 +50,16 @@ struct Block {
         if (e == hipSuccess) e = Alloc(&ptr, need);
         if (e == hipSuccess) bytes = need;
         else ptr = nullptr;
+        return e;
+    }
+    // lay_out(Carve&): run over a null base for the size to reserve, then over the block
+    template <class LayOut>
+    hipError_t carve(LayOut&& lay_out) {
+        dbh_host::Carve sizing(nullptr);
+        lay_out(sizing);
+        const hipError_t e = reserve(sizing.used);
+        dbh_host::Carve regions(ptr);
+        lay_out(regions);
         return e;
     }
     void* get() const { return ptr; }

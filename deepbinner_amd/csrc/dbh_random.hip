@@ -8,7 +8,7 @@
 //                 stride over the values.  flat, gaussian and perlin values need nothing else.  A
 //                 multi_gaussian's segments are laid end to end, so a value's segment depends on
 //                 the lengths in front of it: the workgroup draws 256 segments at a time, scans
-//                 their lengths (shuffles within a wave, four totals through LDS), keeps their
+//                 their lengths (dbh_wave.h: within a wave, four totals through LDS), keeps their
 //                 starts, means and deviations in LDS, and each value finds its segment there by
 //                 bisection.  256 segments cover 25,600 values at least, so the chunk loop runs
 //                 input_size / 25,600 + 1 times at most.
@@ -39,7 +39,8 @@ __attribute__((visibility("default"))) int dbh_random_signals_host(
 #if defined(__HIPCC__)
 #include "../../include/deepbinner_hip.h"
 #include "dbh_owned.h"
-#include "dbh_train.h"
+#include "dbh_status.h"
+#include "dbh_wave.h"
 
 namespace dbh_random_detail {
 
@@ -47,23 +48,13 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kChunkSegments = kThreads;                 // one segment per thread and chunk
 constexpr int kMaxBlocks = 1 << 16;
 
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ int wave_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int below = __shfl_up(v, d);
-        if (lane >= d) v += below;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kThreads) void random_signals(uint32_t lo, uint32_t hi, uint32_t first_signal,
                                                            int64_t n_signals, int32_t input_size,
                                                            int16_t* __restrict__ out) {
     __shared__ int32_t seg_start[kChunkSegments];
     __shared__ double seg_mean[kChunkSegments], seg_stdev[kChunkSegments];
     __shared__ int32_t wave_total[kWaves];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     for (int64_t k = blockIdx.x; k < n_signals; k += gridDim.x) {
         const uint32_t s = first_signal + (uint32_t)k;
         int16_t* row = out + k * input_size;
@@ -83,16 +74,8 @@ __global__ __launch_bounds__(kThreads) void random_signals(uint32_t lo, uint32_t
             for (int32_t chunk = 0; chunk < chunks && at < input_size; ++chunk) {
                 const uint32_t segment = (uint32_t)(chunk * kChunkSegments + t);
                 const int32_t length = dbr::segment_length(lo, hi, s, segment);
-                const int32_t incl = wave_scan(length, lane);
-                if (lane == 63) wave_total[wave] = incl;
-                __syncthreads();
-                int32_t before = 0, total = 0;
-#pragma unroll
-                for (int w = 0; w < kWaves; ++w) {
-                    before += w < wave ? wave_total[w] : 0;
-                    total += wave_total[w];
-                }
-                seg_start[t] = at + before + incl - length;
+                int32_t total;
+                seg_start[t] = at + dbh_wave::block_prefix<kWaves>(length, wave_total, &total);
                 seg_mean[t] = dbr::segment_mean(lo, hi, s, segment);
                 seg_stdev[t] = dbr::segment_stdev(lo, hi, s, segment);
                 __syncthreads();
@@ -122,11 +105,7 @@ hipError_t launch(uint64_t seed, int64_t first_signal, int64_t n_signals, int in
 
 }  // namespace dbh_random_detail
 
-#define DBH_RANDOM_HIP(call)                                                           \
-    do {                                                                               \
-        const hipError_t e_ = (call);                                                  \
-        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, "dbh_random_signals"); \
-    } while (0)
+#define DBH_RANDOM_HIP(call) DBH_HIP_AS("dbh_random_signals", call)
 
 extern "C" {
 

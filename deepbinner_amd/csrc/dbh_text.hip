@@ -70,12 +70,14 @@ __attribute__((visibility("default"))) int dbh_text_parse_host(
 #include <chrono>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_host_layout.h"
 #include "dbh_owned.h"
-#include "dbh_train.h"
+#include "dbh_status.h"
+#include "dbh_wave.h"
 
 namespace dbh_text_detail {
 
-constexpr int kTile = 4096, kTileThreads = kTile / dbt::kPiece;      // 256 threads, 4 waves
+constexpr int kTile = 4096, kTileThreads = kTile / dbt::kPiece, kTileWaves = kTileThreads / 64;   // 256 threads
 constexpr int kScanThreads = 1024;
 constexpr int kParseThreads = 256, kParseWaves = kParseThreads / 64;
 constexpr int kParseBlocks = 8192;
@@ -94,39 +96,13 @@ __device__ __forceinline__ uint32_t lf_mask(const uint8_t* __restrict__ block, i
     return mask;
 }
 
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ int wave_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int below = __shfl_up(v, d);
-        if (lane >= d) v += below;
-    }
-    return v;
-}
-
-// this thread's LFs in front of it within the tile (exclusive), and the tile's total
-__device__ __forceinline__ int tile_scan(int count, int* total) {
-    __shared__ int wave_total[kTileThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int incl = wave_scan(count, lane);
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < kTileThreads / 64; ++k) {
-        before += k < wave ? wave_total[k] : 0;
-        all += wave_total[k];
-    }
-    *total = all;
-    return before + incl - count;
-}
-
 __global__ __launch_bounds__(kTileThreads) void count_lf(const uint8_t* __restrict__ block,
                                                           int64_t n_bytes, int32_t* __restrict__ tile_count) {
     const int64_t at = (int64_t)blockIdx.x * kTile + threadIdx.x * dbt::kPiece;
     const int count = at < n_bytes ? __popc(lf_mask(block, at, n_bytes)) : 0;
+    __shared__ int wave_total[kTileWaves];
     int total;
-    (void)tile_scan(count, &total);
+    (void)dbh_wave::block_prefix<kTileWaves>(count, wave_total, &total);
     if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
@@ -139,21 +115,14 @@ __global__ __launch_bounds__(kScanThreads) void scan_tiles(int32_t* __restrict__
     const int first = t * per, last = min(first + per, n_tiles);
     int sum = 0;
     for (int i = first; i < last; ++i) sum += tile_count[i];
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kScanThreads; d <<= 1) {
-        const int below = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += below;
-        __syncthreads();
-    }
-    int running = part[t] - sum;
+    const int incl = dbh_wave::block_scan_inclusive<int, kScanThreads>(sum, part);
+    int running = incl - sum;
     for (int i = first; i < last; ++i) {
         const int c = tile_count[i];
         tile_count[i] = running;
         running += c;
     }
-    if (t == kScanThreads - 1) *n_lines = part[t];
+    if (t == kScanThreads - 1) *n_lines = incl;
 }
 
 // starts [max_lines + 1]: starts[k] = the first byte of line k, starts[n_lines] = n_bytes
@@ -163,8 +132,9 @@ __global__ __launch_bounds__(kTileThreads) void line_starts(const uint8_t* __res
                                                              int64_t max_lines, int64_t* __restrict__ starts) {
     const int64_t at = (int64_t)blockIdx.x * kTile + threadIdx.x * dbt::kPiece;
     const uint32_t mask = at < n_bytes ? lf_mask(block, at, n_bytes) : 0u;
+    __shared__ int wave_total[kTileWaves];
     int total;
-    const int before = tile_scan(__popc(mask), &total);
+    const int before = dbh_wave::block_prefix<kTileWaves>(__popc(mask), wave_total, &total);
     int64_t line = (int64_t)tile_before[blockIdx.x] + before;      // the line this piece begins in
     if (blockIdx.x == 0 && threadIdx.x == 0) starts[0] = 0;
 #pragma unroll
@@ -209,7 +179,7 @@ __global__ __launch_bounds__(kParseThreads) void parse_lines(
                 }
                 const uint32_t w[8] = {cur.x, cur.y, cur.z, cur.w, next.x, next.y, next.z, next.w};
                 const int commas = dbt::piece_commas(w, rel0, l.tab, l.end);
-                const int incl = wave_scan(commas, lane);
+                const int incl = dbh_wave::wave_scan_inclusive_shfl(commas);
                 flags |= dbt::piece_values(w, rel0, l.tab, l.end, carried + incl - commas, input_size, row);
                 carried += __shfl(incl, 63);
             }
@@ -225,19 +195,13 @@ __global__ __launch_bounds__(kParseThreads) void parse_lines(
     }
 }
 
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 thread_local double g_stage_ms[3] = {0.0, 0.0, 0.0};
 
 }  // namespace dbh_text_detail
 
 using namespace dbh_text_detail;
 
-#define DBH_TEXT_HIP(call)                                                         \
-    do {                                                                           \
-        const hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, "dbh_text_parse"); \
-    } while (0)
+#define DBH_TEXT_HIP(call) DBH_HIP_AS("dbh_text_parse", call)
 
 extern "C" {
 
@@ -252,20 +216,24 @@ int dbh_text_parse(const uint8_t* block, int64_t n_bytes, int input_size, int64_
     const int n_tiles = (int)((n_bytes + kTile - 1) / kTile);
     const size_t text_bytes = ((size_t)n_bytes + 15) & ~(size_t)15;
     const size_t row_bytes = (size_t)input_size * sizeof(int16_t);
-    const size_t at_tiles = up256(text_bytes);
-    const size_t at_starts = at_tiles + up256((size_t)n_tiles * sizeof(int32_t));
-    const size_t at_counts = at_starts + up256((size_t)(max_lines + 1) * sizeof(int64_t));
-    const size_t at_labels = at_counts + 256;              // n_lines, first_bad
-    const size_t at_kinds = at_labels + up256((size_t)max_lines * sizeof(int32_t));
-    const size_t at_samples = at_kinds + up256((size_t)max_lines);
+    uint8_t *text, *kinds_dev;
+    int32_t *tiles, *counts, *labels_dev;
+    int64_t* starts;
+    int16_t* samples_dev;
+    auto lay_out = [&](dbh_host::Carve& c) {
+        text = c.take<uint8_t>(text_bytes);
+        tiles = c.take<int32_t>((size_t)n_tiles);
+        starts = c.take<int64_t>((size_t)max_lines + 1);
+        counts = c.take<int32_t>(2);                       // n_lines, first_bad
+        labels_dev = c.take<int32_t>((size_t)max_lines);
+        kinds_dev = c.take<uint8_t>((size_t)max_lines);
+        samples_dev = c.take<int16_t>((size_t)max_lines * (size_t)input_size);
+        (void)c.take<char>(256);                           // (slack behind the rows)
+    };
     dbh_owned::DeviceBlock dev;
     dbh_owned::Event ev[3];
-    DBH_TEXT_HIP(dev.reserve(at_samples + (size_t)max_lines * row_bytes + 256));
+    DBH_TEXT_HIP(dev.carve(lay_out));
     for (auto& e : ev) DBH_TEXT_HIP(hipEventCreate(&e.h));
-    uint8_t* text = dev.as<uint8_t>();
-    int32_t* tiles = dev.as<int32_t>(at_tiles);
-    int64_t* starts = dev.as<int64_t>(at_starts);
-    int32_t* counts = dev.as<int32_t>(at_counts);
 
     hipStream_t stream = 0;
     DBH_TEXT_HIP(hipEventRecord(ev[0], stream));
@@ -283,8 +251,7 @@ int dbh_text_parse(const uint8_t* block, int64_t n_bytes, int input_size, int64_
         const int64_t want = (max_lines + kParseWaves - 1) / kParseWaves;
         const unsigned grid = (unsigned)(want < kParseBlocks ? want : kParseBlocks);
         hipLaunchKernelGGL(parse_lines, dim3(grid), dim3(kParseThreads), 0, stream, text, starts, counts,
-                           max_lines, (int32_t)input_size, dev.as<int16_t>(at_samples),
-                           dev.as<int32_t>(at_labels), dev.as<uint8_t>(at_kinds), counts + 1);
+                           max_lines, (int32_t)input_size, samples_dev, labels_dev, kinds_dev, counts + 1);
         DBH_TEXT_HIP(hipGetLastError());
     }
     DBH_TEXT_HIP(hipEventRecord(ev[2], stream));
@@ -296,9 +263,9 @@ int dbh_text_parse(const uint8_t* block, int64_t n_bytes, int input_size, int64_
     if (found[0] > max_lines) return DBH_ERR_INVALID_ARGUMENT;        // nothing else is written
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n = (size_t)found[0];
-    DBH_TEXT_HIP(hipMemcpy(samples, dev.as<char>(at_samples), n * row_bytes, hipMemcpyDeviceToHost));
-    DBH_TEXT_HIP(hipMemcpy(labels, dev.as<char>(at_labels), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    DBH_TEXT_HIP(hipMemcpy(kinds, dev.as<char>(at_kinds), n, hipMemcpyDeviceToHost));
+    DBH_TEXT_HIP(hipMemcpy(samples, samples_dev, n * row_bytes, hipMemcpyDeviceToHost));
+    DBH_TEXT_HIP(hipMemcpy(labels, labels_dev, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DBH_TEXT_HIP(hipMemcpy(kinds, kinds_dev, n, hipMemcpyDeviceToHost));
     *first_bad_line = found[1] == kNoBadLine ? -1 : found[1];
     float upload = 0.f, kernels = 0.f;
     DBH_TEXT_HIP(hipEventElapsedTime(&upload, ev[0], ev[1]));

@@ -72,7 +72,4 @@ hipError_t evaluate(const float* weights, int n_classes, int input_size, const f
                     const int32_t* labels, int64_t n_windows, double* loss_sum, int64_t* n_correct,
                     double* window_loss, void* workspace, hipStream_t stream);
 
-// dbh_api.hip: keeps the text for dbh_last_error() and maps the error to a dbh_status
-int report_hip_error(hipError_t e, const char* what);
-
 }  // namespace dbh_train

@@ -23,8 +23,10 @@
 
 #include "../../include/deepbinner_hip.h"
 #include "dbh_general.h"
+#include "dbh_host_layout.h"
 #include "dbh_network.h"
 #include "dbh_owned.h"
+#include "dbh_status.h"
 
 #include <algorithm>
 #include <cmath>
@@ -42,6 +44,8 @@ constexpr int kMaxPartials = 256;          // partial sums per reduction, at mos
 constexpr int kMaxL7 = dbh_gen::kMaxInput / 128;
 
 using namespace dbh_net;      // the network: dbh_network.h
+using dbh_host::blocks_for;
+using dbh_host::Carve;
 
 struct Drop {
     uint32_t seed_lo, seed_hi, layer, threshold;
@@ -651,26 +655,12 @@ __global__ __launch_bounds__(kThreads) void head_dgrad(const float* __restrict__
 }
 
 // ---- host -------------------------------------------------------------------------------------------
-inline unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 struct Geometry {
     int L, C, len[8];
     Geometry(int input_size, int n_classes) : L(input_size), C(n_classes) { stage_lengths(L, len); }
 };
 
-// the workspace, carved in one order by workspace_bytes() and gradients()
-struct Workspace {
-    char* base;
-    size_t used = 0;
-    explicit Workspace(void* p) : base((char*)p) {}
-    template <typename T>
-    T* take(size_t count) {
-        T* p = base ? (T*)(base + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
+// the workspace, carved in one order by workspace_bytes(), gradients() and evaluate()
 struct Buffers {
     float *a1, *h1, *a2, *a3, *a4, *p4, *h2, *a5, *a6, *a7, *p7, *h3, *a8, *a9, *p9, *h4;
     float *avg, *a12, *a14, *a15, *cc, *pcc, *h5, *a17, *h6, *a18, *a19, *p19, *h7, *dz20;
@@ -680,7 +670,7 @@ struct Buffers {
     int* correct;
     void* part;
     size_t part_bytes;
-    Buffers(Workspace& ws, const Geometry& g, int64_t n) {
+    Buffers(Carve& ws, const Geometry& g, int64_t n) {
         const int* len = g.len;
         auto f = [&](int l, int c) { return ws.take<float>((size_t)n * l * c); };
         a1 = f(len[1], 48); h1 = f(len[1], 48); a2 = f(len[1], 48); a3 = f(len[1], 48);
@@ -789,7 +779,7 @@ struct Run {
         else hipLaunchKernelGGL((wgrad<1>), grid, dim3(kThreads), 0, stream, wa);
         if (!ok()) return;
         const long long count = (long long)l.k * l.cin * l.cout;
-        hipLaunchKernelGGL((reduce_partials<float>), dim3(blocks_for(count)), dim3(kThreads), 0, stream,
+        hipLaunchKernelGGL((reduce_partials<float>), dim3(blocks_for(count, kThreads)), dim3(kThreads), 0, stream,
                            (const float*)b.part, (int)(wgs * 4), count, count, grads + blob_kernel(layer, g.C));
         if (!dx) return;
         // the data gradient's contraction runs over cout, its output over cin
@@ -810,7 +800,7 @@ struct Run {
         const unsigned parts = col_launch(ca);
         hipLaunchKernelGGL((col_sums<kColSum>), dim3(parts), dim3(kThreads), 0, stream, ca);
         if (!ok()) return;
-        hipLaunchKernelGGL((reduce_partials<double>), dim3(blocks_for(C)), dim3(kThreads), 0, stream,
+        hipLaunchKernelGGL((reduce_partials<double>), dim3(blocks_for(C, kThreads)), dim3(kThreads), 0, stream,
                            (const double*)b.part, (int)parts, (long long)2 * C, (long long)C, out);
     }
     // batch normalisation `bn` and its dropout: x [n][len][C] -> h
@@ -837,7 +827,7 @@ struct Run {
                                stats + 2 * so);
         }
         if (!ok()) return;
-        hipLaunchKernelGGL(bn_apply, dim3(blocks_for(rows * C)), dim3(kThreads), 0, stream, x,
+        hipLaunchKernelGGL(bn_apply, dim3(blocks_for(rows * C, kThreads)), dim3(kThreads), 0, stream, x,
                            rows * C, C, len, gamma, gamma + C, (const double*)(b.mean + so),
                            (const double*)(b.istd + so), drop_of(bn), h);
     }
@@ -857,19 +847,19 @@ struct Run {
         hipLaunchKernelGGL(finish_bn_backward, dim3(1), dim3(kThreads), 0, stream,
                            (const double*)b.part, (int)parts, C, dgamma, dgamma + C, b.sums);
         if (!ok()) return;
-        hipLaunchKernelGGL(bn_backward_apply, dim3(blocks_for(rows * C)), dim3(kThreads), 0, stream,
+        hipLaunchKernelGGL(bn_backward_apply, dim3(blocks_for(rows * C, kThreads)), dim3(kThreads), 0, stream,
                            dh, x, rows * C, C, len, w + blob_bn(bn, g.C), (const double*)(b.mean + so),
                            (const double*)(b.istd + so), (const double*)b.sums, 1.0 / (double)rows,
                            drop_of(bn), dx);
     }
     void pool(const float* a, int li, int lo, int C, float* p) {
         if (!ok() || lo == 0) return;
-        hipLaunchKernelGGL(pool_forward, dim3(blocks_for((long long)n * lo * C)), dim3(kThreads), 0,
+        hipLaunchKernelGGL(pool_forward, dim3(blocks_for((long long)n * lo * C, kThreads)), dim3(kThreads), 0,
                            stream, a, (long long)n, li, lo, C, p);
     }
     void unpool(bool pooled, const float* gr, const float* a, int li, int lo, int C, float* dz) {
         if (!ok()) return;
-        const dim3 grid(blocks_for((long long)n * li * C));
+        const dim3 grid(blocks_for((long long)n * li * C, kThreads));
         if (pooled)
             hipLaunchKernelGGL((relu_pool_backward<true>), grid, dim3(kThreads), 0, stream, gr, a,
                                (long long)n, li, lo, C, dz);
@@ -888,7 +878,7 @@ void forward(Run& r, const float* x, const int32_t* labels) {
     const int64_t n = r.n;
     const int C = g.C;
     if (r.ok())
-        hipLaunchKernelGGL(conv1_forward, dim3(blocks_for(n * len[1] * 48)), dim3(kThreads), 0,
+        hipLaunchKernelGGL(conv1_forward, dim3(blocks_for(n * len[1] * 48, kThreads)), dim3(kThreads), 0,
                            r.stream, x, r.w + blob_kernel(0, g.C), (long long)n, g.L, len[1],
                            same_pad_left(3, 2, g.L, len[1]), b.a1);
     r.bn_forward(0, b.a1, len[1], b.h1);
@@ -907,7 +897,7 @@ void forward(Run& r, const float* x, const int32_t* labels) {
     r.pool(b.a9, len[3], len[4], 48, b.p9);
     r.bn_forward(3, b.p9, len[4], b.h4);
     if (r.ok())
-        hipLaunchKernelGGL(avg_forward, dim3(blocks_for(n * len[4] * 48)), dim3(kThreads), 0, r.stream,
+        hipLaunchKernelGGL(avg_forward, dim3(blocks_for(n * len[4] * 48, kThreads)), dim3(kThreads), 0, r.stream,
                            (const float*)b.h4, (long long)n, len[4], 48, b.avg);
     r.conv(9, b.avg, len[4], b.cc, len[4], 192, 0);
     r.conv(10, b.h4, len[4], b.cc, len[4], 192, 48);
@@ -934,7 +924,7 @@ void forward(Run& r, const float* x, const int32_t* labels) {
 
 size_t workspace_bytes(int n_classes, int input_size, int64_t n_windows) {
     const Geometry g(input_size, n_classes);
-    Workspace ws(nullptr);
+    Carve ws(nullptr);
     const Buffers b(ws, g, n_windows);
     (void)b;
     return ws.used;
@@ -945,7 +935,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
                      double* mean_loss, int64_t* n_correct, float* grads, float* stats,
                      void* workspace, hipStream_t stream) {
     const Geometry g(input_size, n_classes);
-    Workspace ws(workspace);
+    Carve ws(workspace);
     const Buffers b(ws, g, n_windows);
     const int* len = g.len;
     const int64_t n = n_windows;
@@ -973,12 +963,12 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     if (r.ok()) {
         const long long per = rows_per_part(rows7, 16, 1);
         const unsigned parts = (unsigned)((rows7 + per - 1) / per);
-        hipLaunchKernelGGL(head_wgrad, dim3(blocks_for(48 * C), parts), dim3(kThreads), 0, stream,
+        hipLaunchKernelGGL(head_wgrad, dim3(blocks_for(48 * C, kThreads), parts), dim3(kThreads), 0, stream,
                            (const float*)b.h7, (const float*)b.dz20, rows7, per, C, (double*)b.part);
-        hipLaunchKernelGGL((reduce_partials<double>), dim3(blocks_for(48 * C)), dim3(kThreads), 0,
+        hipLaunchKernelGGL((reduce_partials<double>), dim3(blocks_for(48 * C, kThreads)), dim3(kThreads), 0,
                            stream, (const double*)b.part, (int)parts, (long long)48 * C,
                            (long long)48 * C, grads + blob_kernel(19, g.C));
-        hipLaunchKernelGGL(head_dgrad, dim3(blocks_for(rows7 * 48)), dim3(kThreads), 0, stream,
+        hipLaunchKernelGGL(head_dgrad, dim3(blocks_for(rows7 * 48, kThreads)), dim3(kThreads), 0, stream,
                            (const float*)b.dz20, weights + blob_kernel(19, g.C), rows7, C, b.gA);
     }
     // stage G
@@ -1001,7 +991,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     r.conv_backward(10, b.h4, len[4], b.gE, len[4], 192, 48, b.gD, nullptr, true);
     r.conv_backward(9, b.avg, len[4], b.gE, len[4], 192, 0, b.gavg, nullptr, false);
     if (r.ok())
-        hipLaunchKernelGGL(avg_backward_add, dim3(blocks_for(n * len[4] * 48)), dim3(kThreads), 0,
+        hipLaunchKernelGGL(avg_backward_add, dim3(blocks_for(n * len[4] * 48, kThreads)), dim3(kThreads), 0,
                            stream, (const float*)b.gavg, (long long)n, len[4], 48, b.gD);
     // stage D
     r.bn_backward(3, b.gD, b.p9, len[4], b.gA);
@@ -1041,7 +1031,7 @@ hipError_t evaluate(const float* weights, int n_classes, int input_size, const f
                     const int32_t* labels, int64_t n_windows, double* loss_sum, int64_t* n_correct,
                     double* window_loss, void* workspace, hipStream_t stream) {
     const Geometry g(input_size, n_classes);
-    Workspace ws(workspace);
+    Carve ws(workspace);
     const Buffers b(ws, g, n_windows);
     const Drop keep_all = {0u, 0u, 0u, 0u, 1.f};
     Run r{g, b, weights, nullptr, nullptr, n_windows, keep_all, stream, true};
@@ -1067,12 +1057,6 @@ int check_arguments(int64_t n_floats, int n_classes, int input_size, int64_t n_w
     if (n_windows > dbh_train::kMaxBatchSamples / input_size) return DBH_ERR_UNSUPPORTED;
     return DBH_OK;
 }
-
-#define DBH_TRAIN_HIP(call)                                                       \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, #call);      \
-    } while (0)
 
 }  // namespace
 
@@ -1104,10 +1088,10 @@ int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes,
     if (!weights_dev || !x_dev || !labels_dev || !mean_loss_dev || !n_correct_dev || !grads_dev ||
         !batch_stats_dev || !workspace_dev || ((uintptr_t)weights_dev & 15))
         return DBH_ERR_INVALID_ARGUMENT;
-    DBH_TRAIN_HIP(dbh_train::gradients(weights_dev, n_classes, input_size, x_dev, labels_dev,
-                                       n_windows, dropout_rate, seed, mean_loss_dev, n_correct_dev,
-                                       grads_dev, batch_stats_dev, workspace_dev,
-                                       (hipStream_t)stream));
+    DBH_HIP(dbh_train::gradients(weights_dev, n_classes, input_size, x_dev, labels_dev,
+                                 n_windows, dropout_rate, seed, mean_loss_dev, n_correct_dev,
+                                 grads_dev, batch_stats_dev, workspace_dev,
+                                 (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -1120,9 +1104,9 @@ int dbh_evaluate_dev(const float* weights_dev, int64_t n_floats, int n_classes, 
     if (!weights_dev || !x_dev || !labels_dev || !loss_sum_dev || !n_correct_dev || !workspace_dev ||
         ((uintptr_t)weights_dev & 15))
         return DBH_ERR_INVALID_ARGUMENT;
-    DBH_TRAIN_HIP(dbh_train::evaluate(weights_dev, n_classes, input_size, x_dev, labels_dev,
-                                      n_windows, loss_sum_dev, n_correct_dev, window_loss_dev,
-                                      workspace_dev, (hipStream_t)stream));
+    DBH_HIP(dbh_train::evaluate(weights_dev, n_classes, input_size, x_dev, labels_dev,
+                                n_windows, loss_sum_dev, n_correct_dev, window_loss_dev,
+                                workspace_dev, (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -1140,26 +1124,32 @@ int dbh_evaluate(const float* weights_host, int64_t n_floats, int n_classes, int
     const size_t x_bytes = (size_t)n_windows * input_size * sizeof(float);
     const size_t l_bytes = (size_t)n_windows * sizeof(int32_t);
     const size_t wl_bytes = (size_t)n_windows * sizeof(double);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // one block: weights, windows, labels, the totals, the windows' losses, the workspace
-    const size_t at_x = up(w_bytes), at_l = at_x + up(x_bytes), at_o = at_l + up(l_bytes);
-    const size_t at_wl = at_o + 256, at_w = at_wl + up(wl_bytes);
+    float *w, *x;
+    int32_t* labels;
+    double *totals, *window_loss;      // (the totals: the loss, the count as int64 behind it)
+    char* work;
+    auto lay_out = [&](dbh_host::Carve& c) {
+        w = c.take<float>((size_t)n_floats);
+        x = c.take<float>((size_t)n_windows * input_size);
+        labels = c.take<int32_t>((size_t)n_windows);
+        totals = c.take<double>(2);
+        window_loss = c.take<double>((size_t)n_windows);
+        work = c.take<char>(dbh_train::workspace_bytes(n_classes, input_size, n_windows));
+    };
     dbh_owned::DeviceBlock block;
-    DBH_TRAIN_HIP(block.reserve(at_w + dbh_train::workspace_bytes(n_classes, input_size, n_windows)));
-    char* d = block.as<char>();
-    DBH_TRAIN_HIP(hipMemcpyAsync(d, weights_host, w_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAIN_HIP(hipMemcpyAsync(d + at_x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAIN_HIP(hipMemcpyAsync(d + at_l, labels_host, l_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAIN_HIP(hipMemsetAsync(d + at_o, 0, 16, 0));
-    DBH_TRAIN_HIP(dbh_train::evaluate((const float*)d, n_classes, input_size,
-                                      (const float*)(d + at_x), (const int32_t*)(d + at_l),
-                                      n_windows, (double*)(d + at_o), (int64_t*)(d + at_o + 8),
-                                      (double*)(d + at_wl), d + at_w, 0));
-    DBH_TRAIN_HIP(hipStreamSynchronize(0));
+    DBH_HIP(block.carve(lay_out));
+    DBH_HIP(hipMemcpyAsync(w, weights_host, w_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(labels, labels_host, l_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemsetAsync(totals, 0, 16, 0));
+    DBH_HIP(dbh_train::evaluate(w, n_classes, input_size, x, labels, n_windows, totals,
+                                (int64_t*)(totals + 1), window_loss, work, 0));
+    DBH_HIP(hipStreamSynchronize(0));
     struct { double loss; int64_t correct; } out;
-    DBH_TRAIN_HIP(hipMemcpy(&out, d + at_o, sizeof(out), hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(&out, totals, sizeof(out), hipMemcpyDeviceToHost));
     if (window_loss_host)
-        DBH_TRAIN_HIP(hipMemcpy(window_loss_host, d + at_wl, wl_bytes, hipMemcpyDeviceToHost));
+        DBH_HIP(hipMemcpy(window_loss_host, window_loss, wl_bytes, hipMemcpyDeviceToHost));
     *loss_sum = out.loss;
     *n_correct = out.correct;
     return DBH_OK;
@@ -1181,28 +1171,33 @@ int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, in
     const size_t x_bytes = (size_t)n_windows * input_size * sizeof(float);
     const size_t l_bytes = (size_t)n_windows * sizeof(int32_t);
     const size_t s_bytes = dbh_train::kStatsFloats * sizeof(float);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // one block: weights, gradients, windows, labels, statistics, loss and count, the workspace
-    const size_t at_g = up(w_bytes), at_x = at_g + up(w_bytes), at_l = at_x + up(x_bytes);
-    const size_t at_s = at_l + up(l_bytes), at_o = at_s + up(s_bytes), at_w = at_o + 256;
-    const size_t total = at_w + dbh_train::workspace_bytes(n_classes, input_size, n_windows);
+    float *w, *grads, *x, *stats;
+    int32_t* labels;
+    double* loss;                      // (the count as int64 behind it)
+    char* work;
+    auto lay_out = [&](dbh_host::Carve& c) {
+        w = c.take<float>((size_t)n_floats);
+        grads = c.take<float>((size_t)n_floats);
+        x = c.take<float>((size_t)n_windows * input_size);
+        labels = c.take<int32_t>((size_t)n_windows);
+        stats = c.take<float>(dbh_train::kStatsFloats);
+        loss = c.take<double>(2);
+        work = c.take<char>(dbh_train::workspace_bytes(n_classes, input_size, n_windows));
+    };
     dbh_owned::DeviceBlock block;
-    DBH_TRAIN_HIP(block.reserve(total));
-    char* d = block.as<char>();
-    DBH_TRAIN_HIP(hipMemcpyAsync(d, weights_host, w_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAIN_HIP(hipMemcpyAsync(d + at_x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAIN_HIP(hipMemcpyAsync(d + at_l, labels_host, l_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAIN_HIP(dbh_train::gradients((const float*)d, n_classes, input_size,
-                                       (const float*)(d + at_x), (const int32_t*)(d + at_l),
-                                       n_windows, dropout_rate, seed, (double*)(d + at_o),
-                                       (int64_t*)(d + at_o + 8), (float*)(d + at_g),
-                                       (float*)(d + at_s), d + at_w, 0));
-    DBH_TRAIN_HIP(hipStreamSynchronize(0));
+    DBH_HIP(block.carve(lay_out));
+    DBH_HIP(hipMemcpyAsync(w, weights_host, w_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(labels, labels_host, l_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(dbh_train::gradients(w, n_classes, input_size, x, labels, n_windows, dropout_rate, seed,
+                                 loss, (int64_t*)(loss + 1), grads, stats, work, 0));
+    DBH_HIP(hipStreamSynchronize(0));
     // results reach the caller's buffers only once the whole call has succeeded
     struct { double loss; int64_t correct; } out;
-    DBH_TRAIN_HIP(hipMemcpy(&out, d + at_o, sizeof(out), hipMemcpyDeviceToHost));
-    DBH_TRAIN_HIP(hipMemcpy(grads_host, d + at_g, w_bytes, hipMemcpyDeviceToHost));
-    DBH_TRAIN_HIP(hipMemcpy(batch_stats_host, d + at_s, s_bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(&out, loss, sizeof(out), hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(grads_host, grads, w_bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(batch_stats_host, stats, s_bytes, hipMemcpyDeviceToHost));
     *mean_loss = out.loss;
     *n_correct = out.correct;
     return DBH_OK;

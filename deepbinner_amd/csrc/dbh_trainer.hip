@@ -12,8 +12,10 @@
 #include "../../include/deepbinner_hip.h"
 #include "dbh_feed.h"
 #include "dbh_general.h"
+#include "dbh_host_layout.h"
 #include "dbh_network.h"
 #include "dbh_owned.h"
+#include "dbh_status.h"
 #include "dbh_train.h"
 
 #include <cmath>
@@ -23,12 +25,11 @@
 namespace {
 
 using namespace dbh_net;
+using dbh_host::blocks_for;
 
 constexpr int kThreads = 256;
 constexpr uint64_t kStepStride = 0x9E3779B97F4A7C15ull;    // step_seed = seed + t0 * kStepStride
 constexpr int64_t kMaxNoiseSamples = dbh_train::kMaxBatchSamples;
-
-inline unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 // ---- noise --------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void noise_kernel(const float* __restrict__ x, long long total,
@@ -147,25 +148,17 @@ int check_update(int64_t n_floats, int n_classes, const dbh_nadam_coefficients* 
 hipError_t launch_noise(const float* x, int64_t n_windows, int input_size, float noise_std,
                         uint64_t seed, float* out, hipStream_t stream) {
     const long long total = (long long)n_windows * input_size;
-    hipLaunchKernelGGL(noise_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, stream, x, total,
+    hipLaunchKernelGGL(noise_kernel, dim3(blocks_for(total, kThreads)), dim3(kThreads), 0, stream, x, total,
                        input_size, noise_std, (uint32_t)seed, (uint32_t)(seed >> 32), out);
     return hipGetLastError();
 }
 
 hipError_t launch_update(float* params, const float* grads, float* m, float* v, const float* stats,
                          int n_classes, const dbh_nadam_coefficients& k, hipStream_t stream) {
-    hipLaunchKernelGGL(update_kernel, dim3(blocks_for(param_count(n_classes))), dim3(kThreads), 0,
+    hipLaunchKernelGGL(update_kernel, dim3(blocks_for(param_count(n_classes), kThreads)), dim3(kThreads), 0,
                        stream, params, grads, m, v, stats, blob_map(n_classes), k);
     return hipGetLastError();
 }
-
-#define DBH_TRAINER_HIP(call)                                                     \
-    do {                                                                          \
-        const hipError_t e_ = (call);                                             \
-        if (e_ != hipSuccess) return dbh_train::report_hip_error(e_, #call);      \
-    } while (0)
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -190,27 +183,19 @@ struct dbh_trainer {
     size_t blob_bytes() const { return (size_t)n_floats * sizeof(float); }
 
     hipError_t allocate() {
-        const size_t blob = up256(blob_bytes());
-        const size_t x_bytes = up256((size_t)max_windows * input_size * sizeof(float));
-        const size_t at_stats = 4 * blob, at_x = at_stats + up256(dbh_train::kStatsFloats * sizeof(float));
-        const size_t at_labels = at_x + 2 * x_bytes;
-        const size_t at_out = at_labels + up256((size_t)max_windows * sizeof(int32_t));
-        const size_t at_work = at_out + 256;
-        const size_t at_indices = at_work + up256(dbh_train::workspace_bytes(n_classes, input_size, max_windows));
-        const hipError_t e = block.reserve(at_indices + (size_t)max_windows * sizeof(int64_t));
-        if (e != hipSuccess) return e;
-        weights = block.as<float>(0);
-        m = block.as<float>(blob);
-        v = block.as<float>(2 * blob);
-        grads = block.as<float>(3 * blob);
-        stats = block.as<float>(at_stats);
-        x_in = block.as<float>(at_x);
-        x_noisy = block.as<float>(at_x + x_bytes);
-        labels = block.as<int32_t>(at_labels);
-        loss = block.as<double>(at_out);
-        workspace = block.as<char>(at_work);
-        indices = block.as<int64_t>(at_indices);
-        return hipSuccess;
+        return block.carve([this](dbh_host::Carve& c) {
+            weights = c.take<float>((size_t)n_floats);
+            m = c.take<float>((size_t)n_floats);
+            v = c.take<float>((size_t)n_floats);
+            grads = c.take<float>((size_t)n_floats);
+            stats = c.take<float>(dbh_train::kStatsFloats);
+            x_in = c.take<float>((size_t)max_windows * input_size);
+            x_noisy = c.take<float>((size_t)max_windows * input_size);
+            labels = c.take<int32_t>((size_t)max_windows);
+            loss = c.take<double>(4);
+            workspace = c.take<char>(dbh_train::workspace_bytes(n_classes, input_size, max_windows));
+            indices = c.take<int64_t>((size_t)max_windows);
+        });
     }
 
     int check_step(int64_t n_windows) const {
@@ -288,8 +273,8 @@ int dbh_train_noise_dev(const float* x_dev, int64_t n_windows, int input_size, f
     const int st = check_noise(n_windows, input_size, noise_std);
     if (st != DBH_OK) return st;
     if (!x_dev || !out_dev) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_TRAINER_HIP(launch_noise(x_dev, n_windows, input_size, noise_std, seed, out_dev,
-                                 (hipStream_t)stream));
+    DBH_HIP(launch_noise(x_dev, n_windows, input_size, noise_std, seed, out_dev,
+                         (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -300,12 +285,12 @@ int dbh_train_noise(const float* x_host, int64_t n_windows, int input_size, floa
     if (!x_host || !out_host) return DBH_ERR_INVALID_ARGUMENT;
     const size_t bytes = (size_t)n_windows * input_size * sizeof(float);
     dbh_owned::DeviceBlock block;
-    DBH_TRAINER_HIP(block.reserve(bytes));
+    DBH_HIP(block.reserve(bytes));
     float* d = block.as<float>();
-    DBH_TRAINER_HIP(hipMemcpyAsync(d, x_host, bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(launch_noise(d, n_windows, input_size, noise_std, seed, d, 0));
-    DBH_TRAINER_HIP(hipStreamSynchronize(0));
-    DBH_TRAINER_HIP(hipMemcpy(out_host, d, bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpyAsync(d, x_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(launch_noise(d, n_windows, input_size, noise_std, seed, d, 0));
+    DBH_HIP(hipStreamSynchronize(0));
+    DBH_HIP(hipMemcpy(out_host, d, bytes, hipMemcpyDeviceToHost));
     return DBH_OK;
 }
 
@@ -315,8 +300,8 @@ int dbh_nadam_update_dev(float* params_dev, const float* grads_dev, float* m_dev
     const int st = check_update(n_floats, n_classes, coefficients);
     if (st != DBH_OK) return st;
     if (!params_dev || !grads_dev || !m_dev || !v_dev || !batch_stats_dev) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_TRAINER_HIP(launch_update(params_dev, grads_dev, m_dev, v_dev, batch_stats_dev, n_classes,
-                                  *coefficients, (hipStream_t)stream));
+    DBH_HIP(launch_update(params_dev, grads_dev, m_dev, v_dev, batch_stats_dev, n_classes,
+                          *coefficients, (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -327,22 +312,28 @@ int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host,
     if (st != DBH_OK) return st;
     if (!params_host || !grads_host || !m_host || !v_host || !batch_stats_host)
         return DBH_ERR_INVALID_ARGUMENT;
-    const size_t bytes = (size_t)n_floats * sizeof(float), blob = up256(bytes);
+    const size_t bytes = (size_t)n_floats * sizeof(float);
     const size_t s_bytes = dbh_train::kStatsFloats * sizeof(float);
+    float *p, *g, *m, *v, *s;
+    auto lay_out = [&](dbh_host::Carve& c) {
+        p = c.take<float>((size_t)n_floats);
+        g = c.take<float>((size_t)n_floats);
+        m = c.take<float>((size_t)n_floats);
+        v = c.take<float>((size_t)n_floats);
+        s = c.take<float>(dbh_train::kStatsFloats);
+    };
     dbh_owned::DeviceBlock block;
-    DBH_TRAINER_HIP(block.reserve(4 * blob + s_bytes));
-    float *p = block.as<float>(0), *g = block.as<float>(blob), *m = block.as<float>(2 * blob);
-    float *v = block.as<float>(3 * blob), *s = block.as<float>(4 * blob);
-    DBH_TRAINER_HIP(hipMemcpyAsync(p, params_host, bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(hipMemcpyAsync(g, grads_host, bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(hipMemcpyAsync(m, m_host, bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(hipMemcpyAsync(v, v_host, bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(hipMemcpyAsync(s, batch_stats_host, s_bytes, hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(launch_update(p, g, m, v, s, n_classes, *coefficients, 0));
-    DBH_TRAINER_HIP(hipStreamSynchronize(0));
-    DBH_TRAINER_HIP(hipMemcpy(params_host, p, bytes, hipMemcpyDeviceToHost));
-    DBH_TRAINER_HIP(hipMemcpy(m_host, m, bytes, hipMemcpyDeviceToHost));
-    DBH_TRAINER_HIP(hipMemcpy(v_host, v, bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(block.carve(lay_out));
+    DBH_HIP(hipMemcpyAsync(p, params_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(g, grads_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(m, m_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(v, v_host, bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(s, batch_stats_host, s_bytes, hipMemcpyHostToDevice, 0));
+    DBH_HIP(launch_update(p, g, m, v, s, n_classes, *coefficients, 0));
+    DBH_HIP(hipStreamSynchronize(0));
+    DBH_HIP(hipMemcpy(params_host, p, bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(m_host, m, bytes, hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(v_host, v, bytes, hipMemcpyDeviceToHost));
     return DBH_OK;
 }
 
@@ -369,7 +360,7 @@ int dbh_trainer_create(const float* weights_host, int64_t n_floats, int n_classe
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         delete t;
-        return dbh_train::report_hip_error(e, "dbh_trainer_create");
+        return dbh_hip::hip_fail(e, "dbh_trainer_create");
     }
     *trainer = t;
     return DBH_OK;
@@ -390,8 +381,8 @@ int dbh_trainer_step_dev(dbh_trainer* trainer, const float* x_dev, const int32_t
         return DBH_ERR_INVALID_ARGUMENT;
     const int st = trainer->check_step(n_windows);
     if (st != DBH_OK) return st;
-    DBH_TRAINER_HIP(trainer->queue_step(x_dev, labels_dev, n_windows, mean_loss_dev, n_correct_dev,
-                                        (hipStream_t)stream));
+    DBH_HIP(trainer->queue_step(x_dev, labels_dev, n_windows, mean_loss_dev, n_correct_dev,
+                                (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -403,14 +394,14 @@ int dbh_trainer_step(dbh_trainer* trainer, const float* x_host, const int32_t* l
     for (int64_t i = 0; i < n_windows; ++i)
         if (labels_host[i] < 0 || labels_host[i] >= trainer->n_classes) return DBH_ERR_INVALID_ARGUMENT;
     dbh_trainer& t = *trainer;
-    DBH_TRAINER_HIP(hipMemcpyAsync(t.x_in, x_host, (size_t)n_windows * t.input_size * sizeof(float),
-                                   hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(hipMemcpyAsync(t.labels, labels_host, (size_t)n_windows * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(t.queue_step(t.x_in, t.labels, n_windows, t.loss, (int64_t*)(t.loss + 1), 0));
-    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    DBH_HIP(hipMemcpyAsync(t.x_in, x_host, (size_t)n_windows * t.input_size * sizeof(float),
+                           hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(t.labels, labels_host, (size_t)n_windows * sizeof(int32_t),
+                           hipMemcpyHostToDevice, 0));
+    DBH_HIP(t.queue_step(t.x_in, t.labels, n_windows, t.loss, (int64_t*)(t.loss + 1), 0));
+    DBH_HIP(hipStreamSynchronize(0));
     struct { double loss; int64_t correct; } out;
-    DBH_TRAINER_HIP(hipMemcpy(&out, t.loss, sizeof(out), hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(&out, t.loss, sizeof(out), hipMemcpyDeviceToHost));
     *mean_loss = out.loss;
     *n_correct = out.correct;
     return DBH_OK;
@@ -419,8 +410,8 @@ int dbh_trainer_step(dbh_trainer* trainer, const float* x_host, const int32_t* l
 int dbh_trainer_get_weights(dbh_trainer* trainer, float* weights_host, int64_t n_floats) {
     if (!trainer || !weights_host) return DBH_ERR_INVALID_ARGUMENT;
     if (n_floats != trainer->n_floats) return DBH_ERR_BAD_WEIGHTS;
-    DBH_TRAINER_HIP(hipDeviceSynchronize());
-    DBH_TRAINER_HIP(hipMemcpy(weights_host, trainer->weights, trainer->blob_bytes(), hipMemcpyDeviceToHost));
+    DBH_HIP(hipDeviceSynchronize());
+    DBH_HIP(hipMemcpy(weights_host, trainer->weights, trainer->blob_bytes(), hipMemcpyDeviceToHost));
     return DBH_OK;
 }
 
@@ -428,9 +419,9 @@ int dbh_trainer_get_state(dbh_trainer* trainer, float* m_host, float* v_host, in
                           int64_t* iterations, double* m_schedule) {
     if (!trainer || !m_host || !v_host || !iterations || !m_schedule) return DBH_ERR_INVALID_ARGUMENT;
     if (n_floats != trainer->n_floats) return DBH_ERR_BAD_WEIGHTS;
-    DBH_TRAINER_HIP(hipDeviceSynchronize());
-    DBH_TRAINER_HIP(hipMemcpy(m_host, trainer->m, trainer->blob_bytes(), hipMemcpyDeviceToHost));
-    DBH_TRAINER_HIP(hipMemcpy(v_host, trainer->v, trainer->blob_bytes(), hipMemcpyDeviceToHost));
+    DBH_HIP(hipDeviceSynchronize());
+    DBH_HIP(hipMemcpy(m_host, trainer->m, trainer->blob_bytes(), hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(v_host, trainer->v, trainer->blob_bytes(), hipMemcpyDeviceToHost));
     *iterations = trainer->iterations;
     *m_schedule = trainer->m_schedule;
     return DBH_OK;
@@ -440,9 +431,9 @@ int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float
                           int64_t n_floats, int64_t iterations, double m_schedule) {
     if (!trainer || !m_host || !v_host || iterations < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_floats != trainer->n_floats) return DBH_ERR_BAD_WEIGHTS;
-    DBH_TRAINER_HIP(hipDeviceSynchronize());
-    DBH_TRAINER_HIP(hipMemcpy(trainer->m, m_host, trainer->blob_bytes(), hipMemcpyHostToDevice));
-    DBH_TRAINER_HIP(hipMemcpy(trainer->v, v_host, trainer->blob_bytes(), hipMemcpyHostToDevice));
+    DBH_HIP(hipDeviceSynchronize());
+    DBH_HIP(hipMemcpy(trainer->m, m_host, trainer->blob_bytes(), hipMemcpyHostToDevice));
+    DBH_HIP(hipMemcpy(trainer->v, v_host, trainer->blob_bytes(), hipMemcpyHostToDevice));
     trainer->iterations = iterations;
     trainer->m_schedule = m_schedule;
     return DBH_OK;
@@ -461,9 +452,9 @@ int dbh_trainer_step_dataset_dev(dbh_trainer* trainer, const dbh_dataset* ds,
     uint32_t threshold = 0;
     const int st = trainer->check_dataset(dbh_dataset_view(ds), n_windows, augmentation, &threshold);
     if (st != DBH_OK) return st;
-    DBH_TRAINER_HIP(trainer->queue_dataset_step(*dbh_dataset_view(ds), indices_dev, n_windows,
-                                                threshold, mean_loss_dev, n_correct_dev,
-                                                (hipStream_t)stream));
+    DBH_HIP(trainer->queue_dataset_step(*dbh_dataset_view(ds), indices_dev, n_windows,
+                                        threshold, mean_loss_dev, n_correct_dev,
+                                        (hipStream_t)stream));
     return DBH_OK;
 }
 
@@ -478,13 +469,13 @@ int dbh_trainer_step_dataset(dbh_trainer* trainer, const dbh_dataset* ds, const 
     for (int64_t i = 0; i < n_windows; ++i)
         if (indices_host[i] < 0 || indices_host[i] >= view->n) return DBH_ERR_INVALID_ARGUMENT;
     dbh_trainer& t = *trainer;
-    DBH_TRAINER_HIP(hipMemcpyAsync(t.indices, indices_host, (size_t)n_windows * sizeof(int64_t),
-                                   hipMemcpyHostToDevice, 0));
-    DBH_TRAINER_HIP(t.queue_dataset_step(*view, t.indices, n_windows, threshold, t.loss,
-                                         (int64_t*)(t.loss + 1), 0));
-    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    DBH_HIP(hipMemcpyAsync(t.indices, indices_host, (size_t)n_windows * sizeof(int64_t),
+                           hipMemcpyHostToDevice, 0));
+    DBH_HIP(t.queue_dataset_step(*view, t.indices, n_windows, threshold, t.loss,
+                                 (int64_t*)(t.loss + 1), 0));
+    DBH_HIP(hipStreamSynchronize(0));
     struct { double loss; int64_t correct; } out;
-    DBH_TRAINER_HIP(hipMemcpy(&out, t.loss, sizeof(out), hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(&out, t.loss, sizeof(out), hipMemcpyDeviceToHost));
     *mean_loss = out.loss;
     *n_correct = out.correct;
     return DBH_OK;
@@ -501,24 +492,24 @@ int dbh_trainer_evaluate_dataset(dbh_trainer* trainer, const dbh_dataset* ds, in
         return DBH_ERR_UNSUPPORTED;
     dbh_trainer& t = *trainer;
     dbh_owned::DeviceBlock per_window;
-    if (window_loss_host) DBH_TRAINER_HIP(per_window.reserve((size_t)count * sizeof(double)));
+    if (window_loss_host) DBH_HIP(per_window.reserve((size_t)count * sizeof(double)));
     double* totals = t.loss + 2;
-    DBH_TRAINER_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(double), 0));
+    DBH_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(double), 0));
     // file order, unaugmented (threshold 0), chunk by chunk through the step's own buffers
     for (int64_t done = 0; done < count; done += t.max_windows) {
         const int64_t n = count - done < t.max_windows ? count - done : t.max_windows;
-        DBH_TRAINER_HIP(dbh_feed::assemble(*view, nullptr, first + done, n, 0u, 0, t.x_in, t.labels, 0));
-        DBH_TRAINER_HIP(dbh_train::evaluate(t.weights, t.n_classes, t.input_size, t.x_in, t.labels, n,
-                                            totals, (int64_t*)(totals + 1),
-                                            window_loss_host ? per_window.as<double>() + done : nullptr,
-                                            t.workspace, 0));
+        DBH_HIP(dbh_feed::assemble(*view, nullptr, first + done, n, 0u, 0, t.x_in, t.labels, 0));
+        DBH_HIP(dbh_train::evaluate(t.weights, t.n_classes, t.input_size, t.x_in, t.labels, n,
+                                    totals, (int64_t*)(totals + 1),
+                                    window_loss_host ? per_window.as<double>() + done : nullptr,
+                                    t.workspace, 0));
     }
-    DBH_TRAINER_HIP(hipStreamSynchronize(0));
+    DBH_HIP(hipStreamSynchronize(0));
     struct { double loss; int64_t correct; } out;
-    DBH_TRAINER_HIP(hipMemcpy(&out, totals, sizeof(out), hipMemcpyDeviceToHost));
+    DBH_HIP(hipMemcpy(&out, totals, sizeof(out), hipMemcpyDeviceToHost));
     if (window_loss_host)
-        DBH_TRAINER_HIP(hipMemcpy(window_loss_host, per_window.get(), (size_t)count * sizeof(double),
-                                  hipMemcpyDeviceToHost));
+        DBH_HIP(hipMemcpy(window_loss_host, per_window.get(), (size_t)count * sizeof(double),
+                          hipMemcpyDeviceToHost));
     *loss_sum = out.loss;
     *n_correct = out.correct;
     return DBH_OK;

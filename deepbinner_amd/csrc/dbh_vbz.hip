@@ -28,6 +28,7 @@
 #include <cstdint>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_wave.h"
 
 namespace dbh_vbz_detail {
 
@@ -36,17 +37,7 @@ constexpr int kPerLane = 16;               // values per lane and step (4 contro
 constexpr int kStep = 64 * kPerLane;
 constexpr int kRefused = 1;                // status of a stream that fails a self-check
 
-// wave-wide inclusive prefix sum, modulo 2^32, on the DPP network (as dbh_inflate.hip's
-// wave_scan_i32): within rows of 16 lanes by shifts, then each row's total to the rows behind it
-__device__ __forceinline__ unsigned scan_u32(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
-}
+using dbh_wave::wave_scan_inclusive;       // (of unsigned here: modulo 2^32)
 
 __device__ __forceinline__ uint32_t load_u32(const uint8_t* p) {
     uint32_t v;
@@ -107,7 +98,7 @@ __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int
             }
             const uint32_t span = (uint32_t)valid + (uint32_t)__builtin_popcount(w & 0x55555555u) +
                                   2u * (uint32_t)__builtin_popcount(w & 0xAAAAAAAAu);
-            const uint32_t incl = scan_u32(span);
+            const uint32_t incl = wave_scan_inclusive(span);
             const uint32_t step_bytes = __builtin_amdgcn_readlane(incl, 63);
             const int64_t my = doff + (int64_t)(incl - span);
             const bool overrun = my + (int64_t)span > data_len;
@@ -133,7 +124,7 @@ __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int
                 sum += k < valid ? (u >> 1) ^ (0u - (u & 1u)) : 0u;
                 run[k] = sum;
             }
-            const uint32_t incl2 = scan_u32(sum);
+            const uint32_t incl2 = wave_scan_inclusive(sum);
             const uint32_t prefix = carry + incl2 - sum;
             carry += __builtin_amdgcn_readlane(incl2, 63);
             doff += step_bytes;

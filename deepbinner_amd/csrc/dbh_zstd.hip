@@ -35,19 +35,9 @@ __attribute__((visibility("default"))) int dbh_zstd_decode_host(
 
 #if defined(__HIPCC__)
 #include "../../include/deepbinner_hip.h"
+#include "dbh_wave.h"
 
 namespace dbh_zstd_detail {
-
-// wave-wide inclusive prefix sum on the DPP network (as dbh_vbz.hip's scan_u32)
-__device__ __forceinline__ unsigned scan_u32(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
-}
 
 struct WaveExec {
     int lane;
@@ -115,7 +105,7 @@ struct WaveExec {
         const int32_t stop = piece_start(bits, k + 1, per);
         Piece r = huf_piece(tab, log, src, start, stop, nullptr);
         for (;;) {
-            const int32_t prev_end = __shfl_up(r.end, 1);
+            const int32_t prev_end = dbh_wave::from_lane_before(r.end);
             const int32_t want = k == 0 ? start : prev_end;
             const bool moved = want != start;
             if (__ballot(moved) == 0ull) break;
@@ -124,7 +114,7 @@ struct WaveExec {
                 r = huf_piece(tab, log, src, start, stop, nullptr);
             }
         }
-        const uint32_t incl = scan_u32((uint32_t)r.count);
+        const uint32_t incl = dbh_wave::wave_scan_inclusive((uint32_t)r.count);
         const uint32_t base = (uint32_t)__shfl((int)(incl - (uint32_t)r.count), j * per);
         const uint32_t sum = (uint32_t)__shfl((int)incl, j * per + per - 1) - base;
         if (__ballot(r.bad || sum != stream_symbols(c, j)) != 0ull) return kBadBitstream;

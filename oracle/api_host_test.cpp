@@ -74,6 +74,54 @@ static void check_layouts() {
             }
 }
 
+// Carve: one sequence of take() calls, over a null base (the sizing pass) and over a buffer (the
+// carving pass).  Both end at the same `used`; the sizing pass hands out null pointers only; every
+// carved pointer lies a multiple of 256 bytes behind the base, where the one before it ended; no
+// elements take no bytes; and the buffer, allocated with exactly `used` bytes, takes a write to
+// every region's first and last byte (the sanitizer build is what holds that to account).
+static void check_carve() {
+    const size_t counts[] = {0, 1, 63, 64, 65, 1000, 4097};     // elements per take, three types each
+    auto run = [&](void* base, std::vector<char*>& got, std::vector<size_t>& bytes) {
+        dbh_host::Carve c(base);
+        for (size_t n : counts) {
+            got.push_back((char*)c.take<char>(n));
+            bytes.push_back(n);
+            got.push_back((char*)c.take<int32_t>(n));
+            bytes.push_back(n * 4);
+            got.push_back((char*)c.take<double>(n));
+            bytes.push_back(n * 8);
+        }
+        return c.used;
+    };
+    std::vector<char*> sized, carved;
+    std::vector<size_t> bytes, bytes_again;
+    const size_t need = run(nullptr, sized, bytes);
+    std::vector<char> buffer(need);
+    const size_t used = run(buffer.data(), carved, bytes_again);
+    report(need == used && need % 256 == 0, "carve used", (long)need, (long)used);
+    bool all_null = true, aligned = true, in_order = true;
+    size_t at = 0;
+    for (size_t k = 0; k < carved.size(); ++k) {
+        all_null = all_null && sized[k] == nullptr;
+        const size_t offset = (size_t)(carved[k] - buffer.data());
+        aligned = aligned && offset % 256 == 0;
+        in_order = in_order && offset == at;
+        at += dbh_host::align256(bytes[k]);
+        if (bytes[k]) carved[k][0] = carved[k][bytes[k] - 1] = (char)k;
+    }
+    report(all_null, "carve null_base");
+    report(aligned, "carve aligned");
+    report(in_order && at == used, "carve in_order", (long)at);
+    dbh_host::Carve none(buffer.data());
+    report(none.take<char>(0) == buffer.data() && none.used == 0 && none.take<double>(0) == (double*)buffer.data() &&
+               none.used == 0,
+           "carve take_nothing");
+    report(dbh_host::blocks_for(0, 256) == 0 && dbh_host::blocks_for(1, 256) == 1 &&
+               dbh_host::blocks_for(256, 256) == 1 && dbh_host::blocks_for(257, 256) == 2 &&
+               dbh_host::blocks_for((1LL << 40) + 1, 1024) == (1u << 30) + 1,
+           "blocks_for");
+}
+
 // destination byte-equal to the source, the guard bytes on both sides untouched; and the pieces
 // the copy is cut into cover the buffer once
 static void check_staged_copy() {
@@ -183,6 +231,7 @@ int main(int argc, char** argv) {
         return 0;
     }
     check_layouts();
+    check_carve();
     check_staged_copy();
     check_uniform_length();
     for (int input : {96, 1024, 2048})

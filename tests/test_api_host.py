@@ -57,6 +57,21 @@ def test_layouts_and_staged_copy(lines):
     assert any(c[1] == 'uniform_length' for c in checks)
 
 
+def test_carve_sizes_and_carves_alike(lines):
+    """dbh_host::Carve, which lays out every buffer of the training-data units: the sizing pass
+    (null base) and the carving pass of one sequence of take() calls end at the same `used`, the
+    sizing pass yields null pointers, every carved pointer is a multiple of 256 bytes from the base
+    and starts where the region before it ended, and no elements take no bytes."""
+    checks = {c[2]: c for c in (line.split() for line in lines) if c[1] == 'carve'}
+    assert set(checks) == {'used', 'null_base', 'aligned', 'in_order', 'take_nothing'}
+    assert all(c[0] == 'ok' for c in checks.values()), checks
+    need, used = int(checks['used'][3]), int(checks['used'][4])
+    # 7 counts x (char, int32, double), each region rounded up to 256 bytes
+    assert need == used == sum((n * size + 255) // 256 * 256
+                               for n in (0, 1, 63, 64, 65, 1000, 4097) for size in (1, 4, 8))
+    assert any(line.split()[:2] == ['ok', 'blocks_for'] for line in lines)
+
+
 def test_record_order_is_longest_deflate_stream_first(lines):
     records = seeded_records()
     got = [int(x) for x in next(line for line in lines if line.startswith('order')).split()[1:]]

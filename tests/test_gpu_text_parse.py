@@ -71,6 +71,22 @@ def test_block_sizes_and_replay(hip, case):
         assert first[3] == -1 and not first[2].any()
 
 
+def test_an_lf_in_every_piece_of_two_tiles(hip):
+    """Lines of 4 to 8 bytes, just over two tiles of 4,096 of them: every 16-byte piece holds one to
+    four LFs, so every lane adds to the tile's prefix - on both sides of every row of 16 lanes and
+    of every wave of a workgroup - and a line that started a byte off would parse as another."""
+    values = [(-1) ** k * (k * 37 % 10 ** (1 + k % 4)) for k in range(1500)]
+    data = b''.join(b'%d\t%d\n' % (k % 10, v) for k, v in enumerate(values))
+    while len(data) > 8192 + 40:
+        values.pop()
+        data = data[:data.rindex(b'\n', 0, -1) + 1]
+    assert 8192 < len(data) and max(len(line) for line in data.split(b'\n')) <= 7
+    assert all(b'\n' in data[at:at + 16] for at in range(0, len(data) - 16, 16))
+    samples, labels, kinds, first_bad = both(hip, data, 1)
+    assert first_bad == -1 and not kinds.any()
+    assert samples[:, 0].tolist() == values and labels.tolist() == [k % 10 for k in range(len(values))]
+
+
 @pytest.mark.parametrize('refused', tr.MANY_VARIANTS, ids=str)
 def test_more_lines_than_the_grid_has_waves(hip, refused):
     """70,000 lines of 7 values over 32,768 waves: lines 32,768.. are a wave's second, lines
