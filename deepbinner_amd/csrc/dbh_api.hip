@@ -2,7 +2,8 @@
 // include/deepbinner_hip.h.  Uploads the weights dbh_pack.h packs into the kernel's fragment order,
 // owns the device buffers and prepares the launches.  Host code only: the forward kernel and the
 // small seam kernels (stand-alone normalise, merge, combine_calls) are built, and launched, in
-// dbh_kernels.hip; this file calls its launch functions (dbh_kernels.h).
+// dbh_kernels.hip; this file calls its launch functions (dbh_kernels.h).  The sweep's fold and tally
+// kernels likewise: dbh_sweep.hip behind dbh_sweep.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +27,7 @@
 #include "dbh_owned.h"
 #include "dbh_pack.h"
 #include "dbh_status.h"
+#include "dbh_sweep.h"
 
 namespace {
 thread_local std::string g_last_error;
@@ -901,6 +903,301 @@ int dbh_classify_pair_i16(dbh_model* start_model, dbh_model* end_model,
             std::memcpy(calls_host, side_calls, (size_t)n_reads * sizeof(int32_t));
     }
     return st;
+}
+
+// ---- sweep: every scan size and every threshold from one window pass (dbh_sweep.hip) -------------
+int dbh_sweep_windows_dev(const dbh_model* m, const float* window_probs_dev, int64_t n_reads,
+                          int steps, int32_t* best_dev, double* margin_dev, dbh_stream stream) {
+    if (!m || n_reads < 0 || steps < 1) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!window_probs_dev || !best_dev || !margin_dev) return DBH_ERR_INVALID_ARGUMENT;
+    // the form whose sums run in the order of the model's own merge
+    DBH_HIP(m->kind == DBH_MODEL_KIND_GENERAL
+                ? dbh_sweep::fold256(window_probs_dev, n_reads, steps, m->n_classes, best_dev,
+                                     margin_dev, (hipStream_t)stream)
+                : dbh_sweep::fold32(window_probs_dev, n_reads, steps, m->n_classes, best_dev,
+                                    margin_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_sweep_workspace_bytes(const dbh_model* m, int64_t n_reads, int max_scan_size,
+                              size_t* bytes) {
+    if (!m || !bytes || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
+    const int steps = dbh_host::model_steps(m->input_size, max_scan_size);
+    if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
+    // every window's probabilities, one scan step included: the fold reads them all
+    *bytes = m->kind == DBH_MODEL_KIND_GENERAL
+                 ? general_workspace(m, n_reads, steps)
+                 : (size_t)n_reads * steps * m->n_classes * sizeof(float) + 256;
+    return DBH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the model's own window pass at max_scan_size, then the fold where classify_i16_dev has the merge
+int sweep_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offsets_dev,
+                  int64_t n_reads, int side, int max_scan_size, int32_t* best_dev,
+                  double* margin_dev, void* workspace_dev, dbh_stream stream,
+                  const ReadHints& hints, TailScratch* tail = nullptr) {
+    if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
+    const int steps = dbh_host::model_steps(m->input_size, max_scan_size);
+    if (steps <= 0 || (side != DBH_SIDE_START && side != DBH_SIDE_END))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!samples_dev || !offsets_dev || !best_dev || !margin_dev || !workspace_dev)
+        return DBH_ERR_INVALID_ARGUMENT;
+    float* wprobs = (float*)workspace_dev;
+    if (m->kind == DBH_MODEL_KIND_GENERAL) {
+        void* act = (char*)workspace_dev + align256((size_t)(n_reads * steps) * m->n_classes * sizeof(float));
+        DBH_HIP(dbh_gen::forward(m->gen, nullptr, samples_dev, offsets_dev, steps, side,
+                                 n_reads * steps, wprobs, act, (hipStream_t)stream));
+    } else {
+        // no calls pointer: the forward kernel leaves per-window probabilities, at one scan step
+        // too (where classify takes the fused one-launch finish)
+        FusedInput in;
+        in.samples = samples_dev;
+        in.offsets = offsets_dev;
+        in.steps = steps;
+        in.side = side;
+        in.hints = hints;
+        in.tail = tail;
+        DBH_TRY(launch_forward(m, nullptr, n_reads * steps, wprobs, -1, nullptr, (hipStream_t)stream, in));
+    }
+    return dbh_sweep_windows_dev(m, wprobs, n_reads, steps, best_dev, margin_dev, stream);
+}
+
+// A pair for a sweep: one device, one class count and - one fold serves both sides' prefixes -
+// one input size, which max_scan_size must fit.  -> steps, or 0
+int sweep_pair_steps(dbh_model* const models[2], int max_scan_size) {
+    const dbh_model* m = models[0] ? models[0] : models[1];
+    if (!m) return 0;
+    if (models[0] && models[1] && (models[0]->device != models[1]->device ||
+                                   models[0]->n_classes != models[1]->n_classes ||
+                                   models[0]->input_size != models[1]->input_size))
+        return 0;
+    return dbh_host::model_steps(m->input_size, max_scan_size);
+}
+
+// what comes back per group of sweep_host: each present model's best, then its margin
+struct SweepOut {
+    int32_t* best[2] = {nullptr, nullptr};
+    double* margin[2] = {nullptr, nullptr};
+    size_t total = 0;
+    SweepOut(void* base, int64_t n_reads, int steps, dbh_model* const models[2]) {
+        dbh_host::Carve carve(base);
+        for (int j = 0; j < 2; ++j) {
+            if (!models[j]) continue;
+            best[j] = carve.take<int32_t>((size_t)n_reads * steps);
+            margin[j] = carve.take<double>((size_t)n_reads * steps);
+        }
+        total = carve.used;
+    }
+};
+
+// classify_host's pipeline - the same groups, the same three slots and streams, pinned buffers read
+// in place - with the fold in the merge's place and (best, margin) of every prefix coming back
+int sweep_host(dbh_model* const models[2], const int16_t* samples_host, const int64_t* offsets_host,
+               int64_t n_reads, int max_scan_size, int32_t* const best_host[2],
+               double* const margin_host[2]) {
+    dbh_model* m = models[0] ? models[0] : models[1];      // owns the slots
+    const int steps = sweep_pair_steps(models, max_scan_size);
+    if (!m || n_reads < 0 || steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
+    for (int j = 0; j < 2; ++j)
+        if (models[j] && n_reads > 0 && (!best_host[j] || !margin_host[j])) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!offsets_host) return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t total_samples = offsets_host[n_reads] - offsets_host[0];
+    if (total_samples < 0 || (total_samples > 0 && !samples_host)) return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (offsets_host[i + 1] < offsets_host[i]) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(m->device));
+    const bool pinned = total_samples > 0 &&
+                        is_pinned(samples_host + offsets_host[0], (size_t)total_samples * 2);
+    const int64_t group = std::max<int64_t>(
+        1, (m->kind == DBH_MODEL_KIND_GENERAL ? dbh_model::kDefaultGroup : m->host_group_windows) / steps);
+    constexpr int kSlots = dbh_model::kSlots;
+    struct Pending { int64_t r0 = 0, cnt = 0; bool live = false; } pending[kSlots];
+    auto drain = [&](int k) -> int {
+        HostSlot& sl = m->slot[k];
+        if (!pending[k].live) return DBH_OK;
+        DBH_HIP(hipStreamSynchronize(sl.stream));
+        const int64_t cnt = pending[k].cnt, r0 = pending[k].r0;
+        const SweepOut h(sl.h_out.get(), cnt, steps, models);
+        for (int j = 0; j < 2; ++j) {
+            if (!models[j]) continue;
+            std::memcpy(best_host[j] + r0 * steps, h.best[j], (size_t)cnt * steps * sizeof(int32_t));
+            std::memcpy(margin_host[j] + r0 * steps, h.margin[j], (size_t)cnt * steps * sizeof(double));
+        }
+        pending[k].live = false;
+        return DBH_OK;
+    };
+    auto fail = [&](int status) -> int {
+        for (auto& sl : m->slot)
+            if (sl.stream) (void)hipStreamSynchronize(sl.stream);
+        return status;
+    };
+    int64_t g = 0;
+    for (int64_t r0 = 0; r0 < n_reads; r0 += group, ++g) {
+        const int k = (int)(g % kSlots);
+        HostSlot& sl = m->slot[k];
+        int st = drain(k);
+        if (st != DBH_OK) return fail(st);
+        hipError_t e = hipSuccess;
+        if (!sl.stream) e = hipStreamCreateWithFlags(&sl.stream.h, hipStreamNonBlocking);
+        if (e != hipSuccess) return fail(hip_fail(e, "hipStreamCreateWithFlags"));
+        const int64_t cnt = (n_reads - r0 < group) ? (n_reads - r0) : group;
+        const int64_t s0 = offsets_host[r0], s1 = offsets_host[r0 + cnt];
+        const size_t raw_bytes = (size_t)(s1 - s0) * sizeof(int16_t);
+        const size_t sample_bytes = align256(raw_bytes);
+        const size_t off_bytes = (size_t)(cnt + 1) * sizeof(int64_t);
+        const size_t out_bytes = SweepOut(nullptr, cnt, steps, models).total;
+        size_t work = 0, mine = 0;
+        for (int j = 0; j < 2; ++j)
+            if (models[j] && dbh_sweep_workspace_bytes(models[j], cnt, max_scan_size, &mine) == DBH_OK)
+                work = std::max(work, mine);
+        e = sl.h_in.reserve(off_bytes + (pinned ? 0 : sample_bytes));
+        if (e == hipSuccess) e = sl.h_out.reserve(out_bytes);
+        if (e == hipSuccess) e = sl.d_in.reserve(sample_bytes + off_bytes);
+        if (e == hipSuccess) e = sl.d_out.reserve(out_bytes);
+        if (e == hipSuccess) e = sl.d_work.reserve(work);
+        if (e != hipSuccess) return fail(hip_fail(e, "growing a staging slot"));
+
+        int64_t* rel = sl.h_in.as<int64_t>();
+        for (int64_t i = 0; i <= cnt; ++i) rel[i] = offsets_host[r0 + i] - s0;
+        const void* src = samples_host + s0;
+        if (raw_bytes && !pinned) {
+            staged_copy(sl.h_in.as<char>(off_bytes), src, raw_bytes);
+            src = sl.h_in.as<char>(off_bytes);
+        }
+        // (zero copy or a copy into HBM first: as classify_host)
+        const int16_t* d_samples = sl.d_in.as<int16_t>();
+        const int64_t* d_offsets = sl.d_in.as<int64_t>(sample_bytes);
+        if (raw_bytes && m->host_zero_copy) {
+            void* mapped = nullptr;
+            e = hipHostGetDevicePointer(&mapped, const_cast<void*>(src), 0);
+            d_samples = (const int16_t*)mapped;
+        } else if (raw_bytes) {
+            e = hipMemcpyAsync(sl.d_in.get(), src, raw_bytes, hipMemcpyHostToDevice, sl.stream);
+        }
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((void*)d_offsets, rel, off_bytes, hipMemcpyHostToDevice, sl.stream);
+        if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync H2D"));
+        const SweepOut d(sl.d_out.get(), cnt, steps, models);
+        const ReadHints hints{0, dbh_host::uniform_length(rel, cnt), s1 - s0};
+        for (int j = 0; j < 2; ++j) {
+            if (!models[j]) continue;
+            st = sweep_i16_dev(models[j], d_samples, d_offsets, cnt, j == 0 ? DBH_SIDE_START : DBH_SIDE_END,
+                               max_scan_size, d.best[j], d.margin[j], sl.d_work.get(),
+                               (dbh_stream)sl.stream.h, hints, &sl.tail);
+            if (st != DBH_OK) return fail(st);
+        }
+        e = hipMemcpyAsync(sl.h_out.get(), sl.d_out.get(), out_bytes, hipMemcpyDeviceToHost, sl.stream);
+        if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync D2H"));
+        pending[k].r0 = r0;
+        pending[k].cnt = cnt;
+        pending[k].live = true;
+    }
+    for (int i = 0; i < kSlots; ++i) {       // oldest first
+        const int st = drain((int)((g + i) % kSlots));
+        if (st != DBH_OK) return fail(st);
+    }
+    return DBH_OK;
+}
+
+// the arguments of both tally entries (device or host pointers alike)
+bool tally_arguments_ok(const void* start_best, const void* start_margin, const void* end_best,
+                        const void* end_margin, int64_t n_reads, int steps, int n_classes,
+                        const void* thresholds, int n_thresholds, const void* counts) {
+    const bool start = start_best && start_margin, end = end_best && end_margin;
+    if ((start_best != nullptr) != (start_margin != nullptr) ||
+        (end_best != nullptr) != (end_margin != nullptr))
+        return false;
+    return (start || end) && n_reads >= 0 && steps >= 1 && n_classes >= 2 &&
+           n_classes <= dbh_sweep::kMaxClasses && n_thresholds >= 1 && thresholds && counts;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dbh_sweep_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offsets_dev,
+                      int64_t n_reads, int side, int max_scan_size, int32_t* best_dev,
+                      double* margin_dev, void* workspace_dev, dbh_stream stream) {
+    if (!m) return DBH_ERR_INVALID_ARGUMENT;
+    return sweep_i16_dev(m, samples_dev, offsets_dev, n_reads, side, max_scan_size, best_dev,
+                         margin_dev, workspace_dev, stream, ReadHints{0, m->hint_len, m->hint_cap});
+}
+
+int dbh_sweep_pair_i16(dbh_model* start_model, dbh_model* end_model, const int16_t* samples_host,
+                       const int64_t* offsets_host, int64_t n_reads, int max_scan_size,
+                       int32_t* start_best_host, double* start_margin_host,
+                       int32_t* end_best_host, double* end_margin_host) {
+    dbh_model* const models[2] = {start_model, end_model};
+    int32_t* const best[2] = {start_best_host, end_best_host};
+    double* const margin[2] = {start_margin_host, end_margin_host};
+    return sweep_host(models, samples_host, offsets_host, n_reads, max_scan_size, best, margin);
+}
+
+int dbh_sweep_tally_dev(const int32_t* start_best_dev, const double* start_margin_dev,
+                        const int32_t* end_best_dev, const double* end_margin_dev,
+                        const int32_t* labels_dev, int64_t n_reads, int steps, int n_classes,
+                        const double* thresholds_dev, int n_thresholds, int64_t* counts_dev,
+                        dbh_stream stream) {
+    if (!tally_arguments_ok(start_best_dev, start_margin_dev, end_best_dev, end_margin_dev, n_reads,
+                            steps, n_classes, thresholds_dev, n_thresholds, counts_dev))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    DBH_HIP(dbh_sweep::tally(start_best_dev, start_margin_dev, end_best_dev, end_margin_dev,
+                             labels_dev, n_reads, steps, n_classes, thresholds_dev, n_thresholds,
+                             (unsigned long long*)counts_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_sweep_tally(const int32_t* start_best_host, const double* start_margin_host,
+                    const int32_t* end_best_host, const double* end_margin_host,
+                    const int32_t* labels_host, int64_t n_reads, int steps, int n_classes,
+                    const double* thresholds_host, int n_thresholds, int64_t* counts_host) {
+    if (!tally_arguments_ok(start_best_host, start_margin_host, end_best_host, end_margin_host,
+                            n_reads, steps, n_classes, thresholds_host, n_thresholds, counts_host))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    const bool start = start_best_host != nullptr, end = end_best_host != nullptr;
+    const size_t per_side = (size_t)n_reads * steps;
+    const size_t cells = (size_t)steps * n_thresholds * (start && end ? 3 : 1) * (n_classes + 3);
+    // one block on the calling thread's device, freed on return
+    DeviceBlock block;
+    int32_t *d_best[2] = {nullptr, nullptr}, *d_labels = nullptr;
+    double *d_margin[2] = {nullptr, nullptr}, *d_thresholds = nullptr;
+    int64_t* d_counts = nullptr;
+    DBH_HIP(block.carve([&](dbh_host::Carve& c) {
+        d_best[0] = c.take<int32_t>(start ? per_side : 0);
+        d_margin[0] = c.take<double>(start ? per_side : 0);
+        d_best[1] = c.take<int32_t>(end ? per_side : 0);
+        d_margin[1] = c.take<double>(end ? per_side : 0);
+        d_labels = c.take<int32_t>(labels_host ? (size_t)n_reads : 0);
+        d_thresholds = c.take<double>((size_t)n_thresholds);
+        d_counts = c.take<int64_t>(cells);
+    }));
+    const int32_t* const h_best[2] = {start_best_host, end_best_host};
+    const double* const h_margin[2] = {start_margin_host, end_margin_host};
+    for (int j = 0; j < 2; ++j) {
+        if (!h_best[j]) continue;
+        DBH_HIP(hipMemcpy(d_best[j], h_best[j], per_side * sizeof(int32_t), hipMemcpyHostToDevice));
+        DBH_HIP(hipMemcpy(d_margin[j], h_margin[j], per_side * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (labels_host)
+        DBH_HIP(hipMemcpy(d_labels, labels_host, (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice));
+    DBH_HIP(hipMemcpy(d_thresholds, thresholds_host, (size_t)n_thresholds * sizeof(double), hipMemcpyHostToDevice));
+    DBH_HIP(hipMemset(d_counts, 0, cells * sizeof(int64_t)));
+    DBH_HIP(dbh_sweep::tally(start ? d_best[0] : nullptr, start ? d_margin[0] : nullptr,
+                             end ? d_best[1] : nullptr, end ? d_margin[1] : nullptr,
+                             labels_host ? d_labels : nullptr, n_reads, steps, n_classes,
+                             d_thresholds, n_thresholds, (unsigned long long*)d_counts, 0));
+    std::vector<int64_t> got(cells);
+    DBH_HIP(hipMemcpy(got.data(), d_counts, cells * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < cells; ++i) counts_host[i] += got[i];
+    return DBH_OK;
 }
 
 namespace {

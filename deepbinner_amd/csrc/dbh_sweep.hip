@@ -1,0 +1,275 @@
+// dbh_sweep.hip — the device unit of the sweep (dbh_sweep.h; include/deepbinner_hip.h, "sweep"):
+// the calls of every scan size and every threshold out of ONE window pass at the largest scan size.
+//
+// Window s of a read is the same samples whatever the scan size (dbh_seam.h: window_bounds), and the
+// merge over windows is a running min (class 0) / max (barcodes), so the merged vector after k
+// windows is what a run at scan_size = k * L/2 merges.  The fold kernels walk the windows once and
+// finish every prefix as the merge kernels finish the last: make_sum_to_one in fp64
+// (classify.py:387-393), best class with ties to the lower index and the runner-up
+// (classify.py:285-295).  What they keep per prefix is (best, best - second), from which the call at
+// ANY threshold t is  best != 0 && margin >= t ? best : 0.
+//
+// Two forms, because the two merges sum the barcodes in different orders and a sweep has to agree
+// with them to the bit:
+//   fold32_kernel    32 lanes per read, the reductions of dbh_seam.h (reduce32: DPP inside the rows,
+//                    v_permlane16_swap across them) in renormalise_and_call's order
+//   fold256_kernel   one workgroup per read, the halving trees in LDS of dbh_general.hip's
+//                    merge_kernel (kept in that file, shaped to it: the three trees below restate
+//                    them, same pairing, same order)
+// One guard the merges do not have: a read whose barcodes are all zero (rest == 0) keeps them zero
+// instead of 0 * (x / 0); class 0 is then the best class here as it is there, so no call changes, and
+// the margin is a number.
+//
+// tally_kernel counts the outcomes: integers only, so the result depends on neither the launch shape
+// nor on how the reads were split into calls.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/deepbinner_hip.h"
+#include "dbh_seam.h"
+#include "dbh_sweep.h"
+
+namespace dbh_sweep {
+namespace {
+
+constexpr int kThreads = 256;
+
+// ---- 32 lanes per read (persistent models, C <= 32) ---------------------------------------------
+// dbh_merge_kernel's shape: eight reads per workgroup, lane c = class c, whole 32-lane groups exit
+// together; every reduction runs in control flow that is uniform over the group.
+__global__ __launch_bounds__(kThreads) void fold32_kernel(const float* __restrict__ wprobs,
+                                                          long long n_reads, int steps,
+                                                          int n_classes, int* __restrict__ best,
+                                                          double* __restrict__ margin) {
+    using namespace dbh;
+    const long long read = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int c = threadIdx.x & 31;
+    if (read >= n_reads) return;
+    const bool valid = c < n_classes;
+    const float* src = wprobs + read * steps * n_classes + c;      // (read only where valid)
+    float merged = 0.f;
+    for (int s = 0; s < steps; ++s) {
+        if (valid) {
+            const float v = src[(long long)s * n_classes];
+            merged = s == 0 ? v : (c == 0 ? fminf(merged, v) : fmaxf(merged, v));
+        }
+        double p = (double)merged;
+        const double rest =
+            reduce32(RedF64{(valid && c > 0) ? p : 0.0},
+                     [](const RedF64& a, const RedF64& b) { return RedF64{a.v + b.v}; }).v;
+        const double p0 = __shfl(p, 0, 32);                        // lane 0 of this read's 32
+        const double factor = rest > 0.0 ? (1.0 - p0) / rest : 0.0;
+        if (c > 0) p = p * factor;
+        const RedBest top = reduce32(RedBest{valid ? p : -1.0, c}, [](const RedBest& a, const RedBest& b) {
+            return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
+        });
+        const double second =
+            reduce32(RedF64{(valid && c != top.i) ? p : -1.0},
+                     [](const RedF64& a, const RedF64& b) { return RedF64{fmax(a.v, b.v)}; }).v;
+        if (c == 0) {
+            best[read * steps + s] = top.i;
+            margin[read * steps + s] = top.v - second;
+        }
+    }
+}
+
+// ---- one workgroup per read (general models, C <= 256) ------------------------------------------
+// The three halving trees of dbh_general.hip's merge_kernel; all kThreads threads call each, and the
+// closing barrier lets the next call write rv / ri again.
+__device__ __forceinline__ double tree_sum(double* rv, int c, double v) {
+    rv[c] = v;
+    __syncthreads();
+    for (int half = kThreads / 2; half >= 1; half >>= 1) {
+        if (c < half) rv[c] += rv[c + half];
+        __syncthreads();
+    }
+    const double all = rv[0];
+    __syncthreads();
+    return all;
+}
+__device__ __forceinline__ double tree_best(double* rv, int* ri, int c, double v, int* index) {
+    rv[c] = v;
+    ri[c] = c;
+    __syncthreads();
+    for (int half = kThreads / 2; half >= 1; half >>= 1) {
+        if (c < half) {
+            const double o = rv[c + half];
+            const int oi = ri[c + half];
+            if (o > rv[c] || (o == rv[c] && oi < ri[c])) {
+                rv[c] = o;
+                ri[c] = oi;
+            }
+        }
+        __syncthreads();
+    }
+    const double top = rv[0];
+    *index = ri[0];
+    __syncthreads();
+    return top;
+}
+__device__ __forceinline__ double tree_max(double* rv, int c, double v) {
+    rv[c] = v;
+    __syncthreads();
+    for (int half = kThreads / 2; half >= 1; half >>= 1) {
+        if (c < half) rv[c] = fmax(rv[c], rv[c + half]);
+        __syncthreads();
+    }
+    const double top = rv[0];
+    __syncthreads();
+    return top;
+}
+
+__global__ __launch_bounds__(kThreads) void fold256_kernel(const float* __restrict__ wprobs,
+                                                           int steps, int C,
+                                                           int* __restrict__ best,
+                                                           double* __restrict__ margin) {
+    __shared__ double rv[kThreads];
+    __shared__ int ri[kThreads];
+    __shared__ double first;
+    const long long read = blockIdx.x;
+    const int c = threadIdx.x;
+    const bool valid = c < C;
+    const float* src = wprobs + read * steps * C + c;              // (read only where valid)
+    float merged = 0.f;
+    for (int s = 0; s < steps; ++s) {
+        if (valid) {
+            const float v = src[(long long)s * C];
+            merged = s == 0 ? v : (c == 0 ? fminf(merged, v) : fmaxf(merged, v));
+        }
+        double p = (double)merged;
+        const double rest = tree_sum(rv, c, (valid && c > 0) ? p : 0.0);
+        if (c == 0) first = p;
+        __syncthreads();
+        const double p0 = first;
+        if (c > 0) p = p * (rest > 0.0 ? (1.0 - p0) / rest : 0.0);
+        int top_i;
+        const double top_v = tree_best(rv, ri, c, valid ? p : -1.0, &top_i);
+        const double second = tree_max(rv, c, (valid && c != top_i) ? p : -1.0);
+        if (c == 0) {
+            best[read * steps + s] = top_i;
+            margin[read * steps + s] = top_v - second;
+        }
+        // (`first` is written again only behind the next step's tree_sum, which has barriers)
+    }
+}
+
+// ---- the tally ----------------------------------------------------------------------------------
+// Workgroup b = (chunk of 256 reads b / steps, prefix k = b % steps), one read per thread, which
+// keeps its (best, margin) of both sides and its label in registers.  For every (threshold, mode) in
+// turn the workgroup counts its reads in LDS and adds what is not zero to the caller's counts: a few
+// global atomics per workgroup and cell, not one per read.  A `best` outside [0, C) is counted in
+// no class.
+__global__ __launch_bounds__(kThreads) void tally_kernel(
+    const int* __restrict__ start_best, const double* __restrict__ start_margin,
+    const int* __restrict__ end_best, const double* __restrict__ end_margin,
+    const int* __restrict__ labels, long long n_reads, int steps, int C,
+    const double* __restrict__ thresholds, int n_thresholds, unsigned long long* __restrict__ counts) {
+    __shared__ unsigned hist[kMaxClasses + 3];
+    const unsigned chunk = blockIdx.x / (unsigned)steps;
+    const int k = (int)(blockIdx.x - chunk * (unsigned)steps);
+    const int tid = threadIdx.x;
+    const long long read = (long long)chunk * kThreads + tid;
+    const bool live = read < n_reads;
+    const bool both = start_best != nullptr && end_best != nullptr;
+    const int modes = both ? 3 : 1;
+    const int width = C + 3;
+    int sb = 0, eb = 0, label = -1;
+    double sm = 0.0, em = 0.0;
+    if (live) {
+        const long long at = read * steps + k;
+        if (start_best) {
+            sb = start_best[at];
+            sm = start_margin[at];
+        }
+        if (end_best) {
+            eb = end_best[at];
+            em = end_margin[at];
+        }
+        if (labels) label = labels[read];
+    }
+    for (int t = 0; t < n_thresholds; ++t) {
+        const double threshold = thresholds[t];
+        const int s = (sb != 0 && sm >= threshold) ? sb : 0;
+        const int e = (eb != 0 && em >= threshold) ? eb : 0;
+        for (int mode = 0; mode < modes; ++mode) {
+            for (int i = tid; i < width; i += kThreads) hist[i] = 0;
+            __syncthreads();
+            if (live) {
+                int call;                       // combine_calls_kernel's rule (classify.py:298-322)
+                if (!both) call = start_best ? s : e;
+                else if (s == e) call = s;
+                else if (mode == DBH_REQUIRE_BOTH) call = DBH_CALL_NONE;
+                else if (e == DBH_CALL_NONE) call = s;
+                else if (mode == DBH_REQUIRE_START) call = DBH_CALL_NONE;
+                else call = (s == DBH_CALL_NONE) ? e : DBH_CALL_NONE;
+                if ((unsigned)call < (unsigned)C) atomicAdd(&hist[call], 1u);
+                if (label >= 0) atomicAdd(&hist[call == label ? C : (call != 0 ? C + 1 : C + 2)], 1u);
+            }
+            __syncthreads();
+            unsigned long long* cell =
+                counts + (((long long)k * n_thresholds + t) * modes + mode) * width;
+            for (int i = tid; i < width; i += kThreads)
+                if (hist[i]) atomicAdd(&cell[i], (unsigned long long)hist[i]);
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace
+
+// =============================================================================================
+// The launches (dbh_sweep.h)
+// =============================================================================================
+hipError_t fold32(const float* wprobs, int64_t n_reads, int steps, int n_classes, int32_t* best,
+                  double* margin, hipStream_t stream) {
+    constexpr int64_t kReads = (int64_t)1 << 28;           // per launch: 2^25 workgroups
+    for (int64_t r0 = 0; r0 < n_reads; r0 += kReads) {
+        const int64_t n = std::min<int64_t>(kReads, n_reads - r0);
+        hipLaunchKernelGGL(fold32_kernel, dim3((unsigned)((n + 7) / 8)), dim3(kThreads), 0, stream,
+                           wprobs + r0 * steps * n_classes, (long long)n, steps, n_classes,
+                           (int*)(best + r0 * steps), margin + r0 * steps);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t fold256(const float* wprobs, int64_t n_reads, int steps, int n_classes, int32_t* best,
+                   double* margin, hipStream_t stream) {
+    constexpr int64_t kReads = (int64_t)1 << 30;           // one workgroup per read
+    for (int64_t r0 = 0; r0 < n_reads; r0 += kReads) {
+        const int64_t n = std::min<int64_t>(kReads, n_reads - r0);
+        hipLaunchKernelGGL(fold256_kernel, dim3((unsigned)n), dim3(kThreads), 0, stream,
+                           wprobs + r0 * steps * n_classes, steps, n_classes,
+                           (int*)(best + r0 * steps), margin + r0 * steps);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t tally(const int32_t* start_best, const double* start_margin, const int32_t* end_best,
+                 const double* end_margin, const int32_t* labels, int64_t n_reads, int steps,
+                 int n_classes, const double* thresholds, int n_thresholds,
+                 unsigned long long* counts, hipStream_t stream) {
+    // at most 2^30 workgroups per launch: chunks of 256 reads x steps prefixes
+    const int64_t chunks_per_launch = std::max<int64_t>(1, ((int64_t)1 << 30) / steps);
+    const int64_t reads_per_launch = chunks_per_launch * kThreads;
+    for (int64_t r0 = 0; r0 < n_reads; r0 += reads_per_launch) {
+        const int64_t n = std::min<int64_t>(reads_per_launch, n_reads - r0);
+        const int64_t chunks = (n + kThreads - 1) / kThreads;
+        hipLaunchKernelGGL(tally_kernel, dim3((unsigned)(chunks * steps)), dim3(kThreads), 0, stream,
+                           start_best ? (const int*)(start_best + r0 * steps) : nullptr,
+                           start_margin ? start_margin + r0 * steps : nullptr,
+                           end_best ? (const int*)(end_best + r0 * steps) : nullptr,
+                           end_margin ? end_margin + r0 * steps : nullptr,
+                           labels ? (const int*)(labels + r0) : nullptr, (long long)n, steps,
+                           n_classes, thresholds, n_thresholds, counts);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace dbh_sweep

@@ -7,7 +7,8 @@ declared as data (``OPTIONS``) and turned into argparse calls by one loop.  The 
 ``balance`` (:228-243, plus ``--seed``) and ``refine`` (:272-280, plus the fused ``--model`` form)
 are the reference's commands, and ``fit`` is its ``train`` (:246-269: the same options and
 defaults, plus ``--seed``) on the resident trainer - under another name, because ``train`` and
-``prep`` answer with a one-line refusal.
+``prep`` answer with a one-line refusal.  ``sweep`` is not the reference's: the calls of every scan
+size and score difference counted in one pass (sweep.py).
 """
 
 import argparse
@@ -181,6 +182,39 @@ COMMANDS = {
                 (('--batch_size',), dict(type=int, default=256,
                                          help='With --model: samples handed to the GPU per call')),
                 _HELP]),
+    'sweep': ('Count the calls of every scan size and score difference in one pass',
+              [('Positional', [
+                  (('input',), dict(type=str,
+                                    help='One of the following: a single fast5 file, a directory '
+                                         'of fast5 files (will be searched recursively) or a '
+                                         'tab-delimited file of training data (whose labels are '
+                                         'then the labels)'))]),
+               OPTIONS[0], OPTIONS[1],
+               ('Sweep', [
+                   (('--max_scan_size',), dict(type=float, default=12288,
+                                               help='The largest scan size: every multiple of half '
+                                                    'the model input size up to it is counted')),
+                   (('--score_diffs',), dict(type=str, default='0.1,0.2,0.3,0.4,0.5,0.6,0.7,0.8,0.9',
+                                             help='Comma-delimited score differences to count, '
+                                                  'each in (0, 1]')),
+                   (('--labels',), dict(type=str, default=None,
+                                        help='Known barcodes of the reads: a sequencing summary '
+                                             '(read_id, barcode_arrangement) or a table made '
+                                             'with the deepbinner classify command; adds the '
+                                             'right, wrong and missed columns'))]),
+               ('Performance', [
+                   (('--batch_size',), dict(type=int, default=256,
+                                            help='Number of reads handed to the GPU per call')),
+                   (('--loader_procs',), dict(type=int, default=0,
+                                              help='Threads (native reader) or processes (Python '
+                                                   'reader) that load fast5 files ahead of the GPU '
+                                                   '(0 = automatic)')),
+                   (('--devices',), dict(type=int, default=0,
+                                         help='A sweep runs on one GPU: more than 1 is refused'))]),
+               None],
+              [(('--multi_read',), dict(action='store_true',
+                                        help='Take the reads of multi-read fast5 files where '
+                                             'they are (one-read files may be mixed in)')), _HELP]),
 }
 USES_MODELS = ('classify', 'realtime')
 
@@ -217,7 +251,7 @@ def main(argv=None):
         sys.exit(1)
     if argv[0] in NOT_PROVIDED:
         sys.exit('Error: the {} command is not part of this build - it covers the classify, '
-                 'realtime, bin, balance, fit and refine commands only'.format(argv[0]))
+                 'realtime, bin, balance, fit, refine and sweep commands only'.format(argv[0]))
     args = parser.parse_args(argv)
     if args.subparser_name in USES_MODELS:
         check_classify_and_realtime_arguments(args)
@@ -233,6 +267,10 @@ def main(argv=None):
         from .balance import balance as run
     elif args.subparser_name == 'refine':
         from .refine import refine as run
+    elif args.subparser_name == 'sweep':
+        if resolve_presets(args) == 0:
+            sys.exit('Error: you must provide at least one model')
+        from .sweep import sweep as run
     else:
         return
     run(args)
@@ -241,18 +279,7 @@ def main(argv=None):
 def check_classify_and_realtime_arguments(args):
     """Preset resolution and option checks with the reference's messages (deepbinner.py:283-317);
     with two models and no mode given the mode is require_either (:315-316)."""
-    chosen = [name for name in PRESETS if getattr(args, name)]
-    if len(chosen) > 1:
-        sys.exit('Error: you can only use one model preset (--native or --rapid)')
-    if chosen:
-        if args.start_model is not None or args.end_model is not None:
-            sys.exit('Error: you cannot explicitly specify a model and '
-                     'also use a model preset (--{})'.format(chosen[0]))
-        start, end = PRESETS[chosen[0]]
-        args.start_model = find_model(start)
-        args.end_model = find_model(end) if end else None
-
-    n_models = sum(m is not None for m in (args.start_model, args.end_model))
+    n_models = resolve_presets(args)
     if n_models == 0:
         sys.exit('Error: you must provide at least one model')
     if not 0.0 < args.score_diff <= 1.0:
@@ -267,6 +294,22 @@ def check_classify_and_realtime_arguments(args):
     if not given:
         args.require_either = True
     assert two_model_args_used(args) == 1
+
+
+def resolve_presets(args):
+    """--native / --rapid -> args.start_model, args.end_model (deepbinner.py:283-300, same
+    messages) -> how many models the run has."""
+    chosen = [name for name in PRESETS if getattr(args, name)]
+    if len(chosen) > 1:
+        sys.exit('Error: you can only use one model preset (--native or --rapid)')
+    if chosen:
+        if args.start_model is not None or args.end_model is not None:
+            sys.exit('Error: you cannot explicitly specify a model and '
+                     'also use a model preset (--{})'.format(chosen[0]))
+        start, end = PRESETS[chosen[0]]
+        args.start_model = find_model(start)
+        args.end_model = find_model(end) if end else None
+    return sum(m is not None for m in (args.start_model, args.end_model))
 
 
 def two_model_args_used(args):

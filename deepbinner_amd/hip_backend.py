@@ -158,6 +158,17 @@ def load_library():
         'dbh_merge_calls_dev': (c_int, [c_void_p, c_i64, c_int, c_int, ctypes.c_double, c_void_p,
                                         c_void_p, c_void_p]),
         'dbh_combine_calls_dev': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
+        'dbh_sweep_windows_dev': (c_int, [c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p,
+                                          c_void_p]),
+        'dbh_sweep_workspace_bytes': (c_int, [c_void_p, c_i64, c_int, P(c_size_t)]),
+        'dbh_sweep_i16_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+        'dbh_sweep_pair_i16': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+        'dbh_sweep_tally_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                        c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+        'dbh_sweep_tally': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int,
+                                    c_int, c_void_p, c_int, c_void_p]),
         'dbh_stage_floats': (c_int, [c_int, P(c_i64)]),
         'dbh_debug_forward': (c_int, [c_void_p, _f32(), c_i64, c_int, _f32()]),
         'dbh_forward_kernel_info': (c_int, [P(c_int), P(c_int), P(c_int)]),
@@ -273,6 +284,8 @@ EXPORTED_SYMBOLS = [
     'dbh_inflate_dev', 'dbh_inflate', 'dbh_zstd_decode_host', 'dbh_classify_pair_deflated',
     'dbh_classify_pair_deflated_verbose',
     'dbh_classify_i16_dev', 'dbh_classify_i16_batched_dev', 'dbh_normalise_windows_dev', 'dbh_merge_calls_dev', 'dbh_combine_calls_dev',
+    'dbh_sweep_windows_dev', 'dbh_sweep_workspace_bytes', 'dbh_sweep_i16_dev', 'dbh_sweep_pair_i16',
+    'dbh_sweep_tally_dev', 'dbh_sweep_tally',
     'dbh_stage_floats', 'dbh_debug_forward', 'dbh_forward_kernel_info',
     'dbh_forward_truncated_dev', 'dbh_forward_executed_mfmas', 'dbh_forward_timeline', 'dbh_forward_timeline_i16', 'dbh_forward_timing_enable', 'dbh_forward_timing_enable_span',
     'dbh_forward_timing_read', 'dbh_forward_clock_enable', 'dbh_forward_clock_read', 'dbh_forward_phases_enable', 'dbh_forward_phases_read',
@@ -378,6 +391,127 @@ def classify_pair(start_model, end_model, samples, offsets, scan_size, score_dif
     if want_sides or want_probs:
         return calls, tuple(side_calls), tuple(side_probs)
     return calls
+
+
+def _packed(samples, offsets):
+    samples = np.ascontiguousarray(samples, dtype=np.int16)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    if n < 0 or (n and (offsets[0] != 0 or offsets[-1] != len(samples))):
+        raise ValueError('offsets do not describe the sample buffer')
+    return samples, offsets, n
+
+
+def sweep_steps(input_size, max_scan_size):
+    """Scan sizes a sweep covers: input_size / 2 times 1 .. this many."""
+    half = int(input_size) // 2
+    steps = int(max_scan_size) // half if half else 0
+    if steps < 1 or steps * half != int(max_scan_size):
+        raise ValueError('max_scan_size must be a positive multiple of half the model input size')
+    return steps
+
+
+def sweep_pair(start_model, end_model, samples, offsets, max_scan_size):
+    """One batch of packed reads (as ``classify_pair`` takes them) through the window pass of the
+    start and the end model at ``max_scan_size`` and the fold over scan sizes, in ONE call of the
+    C ABI (``dbh_sweep_pair_i16``) -> ((best_s, margin_s), (best_e, margin_e)): int32 and float64
+    [N, K], column k - 1 for scan size k * input_size / 2.  The call at threshold t is
+    ``np.where((best != 0) & (margin >= t), best, 0)``.  The pair of a model that is None is
+    (None, None)."""
+    lib = load_library()
+    models = (start_model, end_model)
+    first = next((m for m in models if m is not None), None)
+    if first is None:
+        raise ValueError('no model')
+    if any(m is not None and m.input_size != first.input_size for m in models):
+        raise ValueError('the two models of a sweep must have one input size')
+    steps = sweep_steps(first.input_size, max_scan_size)
+    samples, offsets, n = _packed(samples, offsets)
+    best = [np.zeros((n, steps), dtype=np.int32) if m is not None else None for m in models]
+    margin = [np.zeros((n, steps), dtype=np.float64) if m is not None else None for m in models]
+    ptr = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
+    if n > 0:
+        check(lib.dbh_sweep_pair_i16(
+            start_model.handle if start_model is not None else None,
+            end_model.handle if end_model is not None else None,
+            samples.ctypes.data if samples.size else None, offsets.ctypes.data, n,
+            int(max_scan_size), ptr(best[0]), ptr(margin[0]), ptr(best[1]), ptr(margin[1])),
+            'dbh_sweep_pair_i16')
+    return (best[0], margin[0]), (best[1], margin[1])
+
+
+SWEEP_MODES = ('either', 'start', 'both')      # DBH_REQUIRE_EITHER, _START, _BOTH
+
+
+def sweep_counts(steps, n_thresholds, both, n_classes):
+    """The zeroed counts of ``sweep_tally``: int64 [K, T, modes, C + 3] - per final class, then
+    right, wrong, missed - with three modes (SWEEP_MODES) for two sides and one for one."""
+    return np.zeros((int(steps), int(n_thresholds), 3 if both else 1, int(n_classes) + 3),
+                    dtype=np.int64)
+
+
+def sweep_tally(start, end, thresholds, n_classes, labels=None, counts=None):
+    """The outcomes of one batch, counted on the device (``dbh_sweep_tally``): ``start`` / ``end``
+    are the (best, margin) pairs of ``sweep_pair`` (None or (None, None): that side is not there),
+    ``labels`` int32 per read (0 = known to carry no barcode, negative = unknown) or None.  ADDS
+    into ``counts`` (``sweep_counts``; made when None) and returns it."""
+    sides = [side if side is not None and side[0] is not None else None for side in (start, end)]
+    if sides[0] is None and sides[1] is None:
+        raise ValueError('no side')
+    shape = next(side[0].shape for side in sides if side is not None)
+    n, steps = shape
+    held = []
+    for side in sides:
+        if side is None:
+            held.append((None, None))
+            continue
+        best = np.ascontiguousarray(side[0], dtype=np.int32)
+        margin = np.ascontiguousarray(side[1], dtype=np.float64)
+        if best.shape != shape or margin.shape != shape:
+            raise ValueError('best and margin of both sides must be [N, K] alike')
+        held.append((best, margin))
+    thresholds = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if labels.shape != (n,):
+            raise ValueError('one label per read')
+    if counts is None:
+        counts = sweep_counts(steps, len(thresholds), sides[0] is not None and sides[1] is not None,
+                              n_classes)
+    want = sweep_counts(steps, len(thresholds), sides[0] is not None and sides[1] is not None,
+                        n_classes).shape
+    if counts.shape != want or counts.dtype != np.int64 or not counts.flags['C_CONTIGUOUS']:
+        raise ValueError('counts must be a C-contiguous int64 array of shape {}'.format(want))
+    ptr = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
+    check(load_library().dbh_sweep_tally(
+        ptr(held[0][0]), ptr(held[0][1]), ptr(held[1][0]), ptr(held[1][1]), ptr(labels), n, steps,
+        int(n_classes), thresholds.ctypes.data if thresholds.size else None, len(thresholds),
+        counts.ctypes.data), 'dbh_sweep_tally')
+    return counts
+
+
+def sweep_windows(model, window_probs):
+    """The fold alone (``dbh_sweep_windows_dev``; parity tests): per-window probabilities float32
+    [N, K, C] of ``model``'s class count -> (best int32 [N, K], margin float64 [N, K]), by the form
+    of the fold that belongs to the model's kind."""
+    window_probs = np.ascontiguousarray(window_probs, dtype=np.float32)
+    n, steps, n_classes = window_probs.shape
+    if n_classes != model.n_classes:
+        raise ValueError('window_probs must have the model\'s {} classes'.format(model.n_classes))
+    best = np.zeros((n, steps), dtype=np.int32)
+    margin = np.zeros((n, steps), dtype=np.float64)
+    if n == 0:
+        return best, margin
+    d_probs = DeviceBuffer.from_array(window_probs)
+    d_best, d_margin = DeviceBuffer(best.nbytes), DeviceBuffer(margin.nbytes)
+    try:
+        check(load_library().dbh_sweep_windows_dev(model.handle, d_probs.ptr, n, steps, d_best.ptr,
+                                                   d_margin.ptr, None), 'dbh_sweep_windows_dev')
+        synchronize()
+        return (d_best.download(best.shape, np.int32), d_margin.download(margin.shape, np.float64))
+    finally:
+        for buf in (d_probs, d_best, d_margin):
+            buf.free()
 
 
 INFLATE_ZLIB, INFLATE_STORED, INFLATE_VBZ = 0, 1, 2
@@ -704,6 +838,13 @@ class HipModel:
                                              int(scan_size), float(score_diff), probs, calls),
                   'dbh_classify_i16')
         return probs, calls
+
+    def sweep_packed(self, samples, offsets, side, max_scan_size):
+        """``classify_packed``'s reads through the window pass at ``max_scan_size`` and the fold
+        over scan sizes -> (best int32 [N, K], margin float64 [N, K]): see ``sweep_pair``."""
+        pair = sweep_pair(self if side == 'start' else None, None if side == 'start' else self,
+                          samples, offsets, max_scan_size)
+        return pair[0] if side == 'start' else pair[1]
 
     # -- device-resident entry points (inputs/outputs are raw device pointers) -----------------
     def workspace_bytes(self, n_reads, scan_size):

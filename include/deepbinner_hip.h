@@ -220,6 +220,73 @@ int dbh_classify_i16_batched_dev(dbh_model* model, const int16_t* samples_dev,
 int dbh_combine_calls_dev(const int32_t* start_calls_dev, const int32_t* end_calls_dev,
                           int64_t n_reads, int mode, int32_t* out_dev, dbh_stream stream);
 
+/* ---- sweep: the calls of every scan size and every threshold from one window pass ------------ */
+/* call_batch (classify.py:325-393) looks at steps = scan_size / (input_size / 2) windows per read
+ * end.  Window s is the same samples whatever the scan size (classify.py:337-349), and the merge
+ * over windows is a running minimum for class 0 and a running maximum for the barcodes
+ * (classify.py:368-374): the merged vector after k windows IS what a run at scan_size =
+ * k * input_size / 2 merges.  One window pass at max_scan_size therefore holds the call of every
+ * smaller scan size, and - kept as the best class and its lead over the runner-up - of every
+ * --score_diff.
+ *
+ * The fold.  For read r and k = 1 .. steps: merge windows 0 .. k-1, make_sum_to_one in fp64
+ * (classify.py:387-393; a read whose barcodes are all zero keeps them zero instead of dividing by
+ * their sum), then the top two (classify.py:285-295, ties to the lower class):
+ *     best[r][k-1]    int32, the best class; 0 = class 0 leads, no barcode at any threshold
+ *     margin[r][k-1]  fp64, best value - second value
+ * The call at threshold t is   best != 0 && margin >= t ? best : 0   - to the bit what
+ * dbh_classify_i16(_dev) at scan_size = k * input_size / 2 and score_diff = t calls, because the
+ * model chooses the form of the fold whose sums run in the order of its own merge (persistent
+ * models: 32 lanes per read; general models: one workgroup per read, up to 256 classes).
+ *
+ * dbh_sweep_windows_dev is the fold alone, over window_probs_dev [n_reads][steps][n_classes] fp32
+ * (read-major, as the forward paths leave them), exposed for parity tests as dbh_merge_calls_dev
+ * is.  dbh_sweep_i16_dev runs the model's window pass at max_scan_size and then the fold;
+ * workspace_dev holds dbh_sweep_workspace_bytes() bytes and is needed at every scan size (one step
+ * included: the fold reads per-window probabilities).  best_dev / margin_dev: n_reads x steps.
+ * dbh_sweep_pair_i16 takes host buffers through the groups and slots of dbh_classify_pair_i16;
+ * either model may be NULL (its two arrays are then not touched), a pair must live on one device
+ * and agree on n_classes AND on the input size.  Every argument is checked before any device work
+ * - a null pointer, n_reads < 0, steps < 1 or a max_scan_size that is no positive multiple of half
+ * the input size, a mismatched pair, offsets that run backwards: DBH_ERR_INVALID_ARGUMENT, nothing
+ * written.  n_reads == 0 is DBH_OK.  The _dev entries do not block the host. */
+int dbh_sweep_windows_dev(const dbh_model* model, const float* window_probs_dev, int64_t n_reads,
+                          int steps, int32_t* best_dev, double* margin_dev, dbh_stream stream);
+int dbh_sweep_workspace_bytes(const dbh_model* model, int64_t n_reads, int max_scan_size,
+                              size_t* bytes);
+int dbh_sweep_i16_dev(dbh_model* model, const int16_t* samples_dev, const int64_t* offsets_dev,
+                      int64_t n_reads, int side, int max_scan_size, int32_t* best_dev,
+                      double* margin_dev, void* workspace_dev, dbh_stream stream);
+int dbh_sweep_pair_i16(dbh_model* start_model, dbh_model* end_model, const int16_t* samples_host,
+                       const int64_t* offsets_host, int64_t n_reads, int max_scan_size,
+                       int32_t* start_best_host, double* start_margin_host,
+                       int32_t* end_best_host, double* end_margin_host);
+/* The tally.  From the folds of the start side, the end side or both (a side that is not given is
+ * two NULLs), n_thresholds thresholds (fp64) and optional labels (int32 per read: the class the
+ * read is known to carry, 0 = known to carry none, negative = unknown; NULL = none known) it ADDS
+ * into counts, which the caller zeroed before the first call:
+ *     counts[steps][n_thresholds][modes][n_classes + 3]   int64, C order
+ *         [0 .. n_classes)   reads whose final call is that class (0 = none)
+ *         [n_classes]        right:  labelled reads with call == label (none on label 0 included)
+ *         [n_classes + 1]    wrong:  labelled reads with call != label and call != 0
+ *         [n_classes + 2]    missed: labelled reads with call == 0 and label != 0
+ * modes = 3 with both sides - the final call by combine_calls (classify.py:298-322) under
+ * DBH_REQUIRE_EITHER, _START, _BOTH, in that order - and 1 with one side, whose call is final.
+ * Only integers are added, so the result depends neither on the launch shape nor on how the reads
+ * were split into calls.  A best outside [0, n_classes) counts in no class.  2 <= n_classes <= 256.
+ * dbh_sweep_tally (host buffers) works on the calling thread's current device and blocks;
+ * dbh_sweep_tally_dev queues on `stream`.  A null thresholds or counts, a side given by half,
+ * no side, a count < 1 (n_reads < 0): DBH_ERR_INVALID_ARGUMENT, nothing written. */
+int dbh_sweep_tally_dev(const int32_t* start_best_dev, const double* start_margin_dev,
+                        const int32_t* end_best_dev, const double* end_margin_dev,
+                        const int32_t* labels_dev, int64_t n_reads, int steps, int n_classes,
+                        const double* thresholds_dev, int n_thresholds, int64_t* counts_dev,
+                        dbh_stream stream);
+int dbh_sweep_tally(const int32_t* start_best_host, const double* start_margin_host,
+                    const int32_t* end_best_host, const double* end_margin_host,
+                    const int32_t* labels_host, int64_t n_reads, int steps, int n_classes,
+                    const double* thresholds_host, int n_thresholds, int64_t* counts_host);
+
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's
  * inflate() over every chunk on the host.  Here the loader may hand over the chunks AS STORED
