@@ -8,7 +8,8 @@ declared as data (``OPTIONS``) and turned into argparse calls by one loop.  The 
 are the reference's commands, and ``fit`` is its ``train`` (:246-269: the same options and
 defaults, plus ``--seed``) on the resident trainer - under another name, because ``train`` and
 ``prep`` answer with a one-line refusal.  ``sweep`` is not the reference's: the calls of every scan
-size and score difference counted in one pass (sweep.py).
+size and score difference counted in one pass (sweep.py).  Nor is ``scan``: every window of a read
+through the network, and the places inside it where a barcode class leads (scan.py).
 """
 
 import argparse
@@ -215,8 +216,19 @@ COMMANDS = {
               [(('--multi_read',), dict(action='store_true',
                                         help='Take the reads of multi-read fast5 files where '
                                              'they are (one-read files may be mixed in)')), _HELP]),
+    'scan': ('Flag reads with barcode signal inside the read (chimeras)',
+             [('Positional', [
+                 (('input',), dict(type=str,
+                                   help='One of the following: a single fast5 file or a directory '
+                                        'of fast5 files (will be searched recursively)'))])],
+             [(('--min_windows',), dict(type=int, default=1,
+                                        help='An event is this many consecutive windows of one '
+                                             'barcode class at least')),
+              (('--multi_read',), dict(action='store_true',
+                                       help='Take the reads of multi-read fast5 files where '
+                                            'they are (one-read files may be mixed in)')), _HELP]),
 }
-USES_MODELS = ('classify', 'realtime')
+USES_MODELS = ('classify', 'realtime', 'scan')
 
 
 def _add_groups(parser, groups):
@@ -251,7 +263,7 @@ def main(argv=None):
         sys.exit(1)
     if argv[0] in NOT_PROVIDED:
         sys.exit('Error: the {} command is not part of this build - it covers the classify, '
-                 'realtime, bin, balance, fit, refine and sweep commands only'.format(argv[0]))
+                 'realtime, bin, balance, fit, refine, sweep and scan commands only'.format(argv[0]))
     args = parser.parse_args(argv)
     if args.subparser_name in USES_MODELS:
         check_classify_and_realtime_arguments(args)
@@ -271,6 +283,8 @@ def main(argv=None):
         if resolve_presets(args) == 0:
             sys.exit('Error: you must provide at least one model')
         from .sweep import sweep as run
+    elif args.subparser_name == 'scan':
+        from .scan import scan as run
     else:
         return
     run(args)

@@ -169,6 +169,14 @@ def load_library():
                                         c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
         'dbh_sweep_tally': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int,
                                     c_int, c_void_p, c_int, c_void_p]),
+        'dbh_scan_window_count': (c_int, [c_int, c_i64, P(c_i64)]),
+        'dbh_scan_window_offsets_dev': (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p]),
+        'dbh_scan_windows_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_i64,
+                                         c_i64, c_void_p, c_void_p]),
+        'dbh_scan_events_dev': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, ctypes.c_double, c_int,
+                                        c_int, c_void_p, c_i64, c_void_p, c_void_p, c_void_p]),
+        'dbh_scan_i16': (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, ctypes.c_double, c_int,
+                                 c_int, c_void_p, c_void_p, c_void_p, c_i64, P(c_i64), P(c_i64)]),
         'dbh_stage_floats': (c_int, [c_int, P(c_i64)]),
         'dbh_debug_forward': (c_int, [c_void_p, _f32(), c_i64, c_int, _f32()]),
         'dbh_forward_kernel_info': (c_int, [P(c_int), P(c_int), P(c_int)]),
@@ -286,6 +294,8 @@ EXPORTED_SYMBOLS = [
     'dbh_classify_i16_dev', 'dbh_classify_i16_batched_dev', 'dbh_normalise_windows_dev', 'dbh_merge_calls_dev', 'dbh_combine_calls_dev',
     'dbh_sweep_windows_dev', 'dbh_sweep_workspace_bytes', 'dbh_sweep_i16_dev', 'dbh_sweep_pair_i16',
     'dbh_sweep_tally_dev', 'dbh_sweep_tally',
+    'dbh_scan_window_count', 'dbh_scan_window_offsets_dev', 'dbh_scan_windows_dev',
+    'dbh_scan_events_dev', 'dbh_scan_i16',
     'dbh_stage_floats', 'dbh_debug_forward', 'dbh_forward_kernel_info',
     'dbh_forward_truncated_dev', 'dbh_forward_executed_mfmas', 'dbh_forward_timeline', 'dbh_forward_timeline_i16', 'dbh_forward_timing_enable', 'dbh_forward_timing_enable_span',
     'dbh_forward_timing_read', 'dbh_forward_clock_enable', 'dbh_forward_clock_read', 'dbh_forward_phases_enable', 'dbh_forward_phases_read',
@@ -511,6 +521,111 @@ def sweep_windows(model, window_probs):
         return (d_best.download(best.shape, np.int32), d_margin.download(margin.shape, np.float64))
     finally:
         for buf in (d_probs, d_best, d_margin):
+            buf.free()
+
+
+# dbh_scan_event: a run of windows of one read that fire one class (include/deepbinner_hip.h, "scan")
+SCAN_EVENT = np.dtype([('read', np.int64), ('cls', np.int32), ('first', np.int32),
+                       ('last', np.int32), ('reserved', np.int32), ('peak', np.float64)])
+assert SCAN_EVENT.itemsize == 32
+
+
+def scan_window_count(input_size, n_samples):
+    """W(n): the windows a scan cuts from a read of ``n_samples`` samples (an integer, or an array
+    of them -> int64 array): 1 up to ``input_size`` samples, then one more per half input size
+    begun (``dbh_scan_window_count``)."""
+    input_size = int(input_size)
+    if input_size % 2 or not 96 <= input_size <= 16384:
+        raise ValueError('input_size must be even and from 96 to 16,384')
+    if np.ndim(n_samples):
+        n = np.asarray(n_samples, dtype=np.int64)
+        if (n < 0).any():
+            raise ValueError('a read cannot have a negative length')
+        half = input_size // 2
+        return np.where(n <= input_size, 1, (n - input_size + half - 1) // half + 1).astype(np.int64)
+    count = ctypes.c_int64(0)
+    check(load_library().dbh_scan_window_count(input_size, int(n_samples), ctypes.byref(count)),
+          'dbh_scan_window_count')
+    return count.value
+
+
+def scan_packed(model, samples, offsets, side, threshold, min_windows=1, skip_windows=0):
+    """``model.scan_packed`` as a function of the backend (what ``scan.scan`` calls)."""
+    return model.scan_packed(samples, offsets, side, threshold, min_windows, skip_windows)
+
+
+def scan_window_offsets(offsets, input_size):
+    """``dbh_scan_window_offsets_dev`` alone (parity tests): sample offsets int64 [N + 1] ->
+    window offsets int64 [N + 1]."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    d_offsets, d_out = DeviceBuffer.from_array(offsets), DeviceBuffer(8 * (n + 1))
+    try:
+        check(load_library().dbh_scan_window_offsets_dev(d_offsets.ptr, n, int(input_size),
+                                                         d_out.ptr, None),
+              'dbh_scan_window_offsets_dev')
+        synchronize()
+        return d_out.download((n + 1,), np.int64)
+    finally:
+        d_offsets.free()
+        d_out.free()
+
+
+def scan_windows(samples, offsets, input_size, side, first_window=0, n_windows=None):
+    """The scan's front alone (``dbh_scan_windows_dev``; parity tests): global windows
+    [first_window, first_window + n_windows) of the packed reads, cut, normalised and padded ->
+    float32 [n_windows, input_size].  ``n_windows`` None: up to the batch's last."""
+    samples, offsets, n = _packed(samples, offsets)
+    lib = load_library()
+    window_offsets = np.concatenate(
+        [[0], np.cumsum(scan_window_count(input_size, np.diff(offsets)))]).astype(np.int64)
+    if n_windows is None:
+        n_windows = int(window_offsets[-1]) - int(first_window)
+    x = np.zeros((int(n_windows), int(input_size)), dtype=np.float32)
+    if n == 0 or n_windows == 0:
+        return x
+    held = [DeviceBuffer.from_array(samples), DeviceBuffer.from_array(offsets),
+            DeviceBuffer(window_offsets.nbytes), DeviceBuffer(x.nbytes)]
+    try:
+        check(lib.dbh_scan_window_offsets_dev(held[1].ptr, n, int(input_size), held[2].ptr, None),
+              'dbh_scan_window_offsets_dev')
+        check(lib.dbh_scan_windows_dev(held[0].ptr, held[1].ptr, held[2].ptr, n, int(input_size),
+                                       0 if side == 'start' else 1, int(first_window),
+                                       int(n_windows), held[3].ptr, None), 'dbh_scan_windows_dev')
+        synchronize()
+        return held[3].download(x.shape, np.float32)
+    finally:
+        for buf in held:
+            buf.free()
+
+
+def scan_events(best, margin, window_offsets, threshold, min_windows=1, skip_windows=0,
+                max_events=None):
+    """The event pass alone (``dbh_scan_events_dev``): a track in global window order (``best``
+    int32, ``margin`` float64) and the reads' window offsets -> (events SCAN_EVENT array - the
+    first ``max_events`` of them; None: room for all - , the true total, interior events per read
+    int32 [N])."""
+    best = np.ascontiguousarray(best, dtype=np.int32)
+    margin = np.ascontiguousarray(margin, dtype=np.float64)
+    window_offsets = np.ascontiguousarray(window_offsets, dtype=np.int64)
+    n = len(window_offsets) - 1
+    if best.shape != margin.shape or best.ndim != 1 or (n >= 0 and len(best) != window_offsets[-1]):
+        raise ValueError('best and margin must hold one entry per window')
+    capacity = len(best) if max_events is None else int(max_events)
+    held = [DeviceBuffer.from_array(best), DeviceBuffer.from_array(margin),
+            DeviceBuffer.from_array(window_offsets), DeviceBuffer(max(capacity, 1) * 32),
+            DeviceBuffer(max(n, 1) * 4), DeviceBuffer(8)]
+    try:
+        check(load_library().dbh_scan_events_dev(
+            held[0].ptr, held[1].ptr, held[2].ptr, n, float(threshold), int(min_windows),
+            int(skip_windows), held[3].ptr, capacity, held[4].ptr, held[5].ptr, None),
+            'dbh_scan_events_dev')
+        synchronize()
+        total = int(held[5].download((1,), np.int64)[0])
+        events = held[3].download((min(total, capacity),), SCAN_EVENT)
+        return events, total, held[4].download((max(n, 0),), np.int32)
+    finally:
+        for buf in held:
             buf.free()
 
 
@@ -845,6 +960,33 @@ class HipModel:
         pair = sweep_pair(self if side == 'start' else None, None if side == 'start' else self,
                           samples, offsets, max_scan_size)
         return pair[0] if side == 'start' else pair[1]
+
+    def scan_packed(self, samples, offsets, side, threshold, min_windows=1, skip_windows=0,
+                    track=False):
+        """EVERY window of the packed reads through the network (``dbh_scan_i16``) -> the events
+        of the track as a SCAN_EVENT array ordered by (read, first): runs of at least
+        ``min_windows`` consecutive windows of one read whose best class is one barcode leading
+        by ``threshold``; an event is interior when ``first >= skip_windows``.  ``track=True``:
+        (events, best int32, margin float64, window_offsets int64 [N + 1]) - the whole ragged
+        track in global window order."""
+        samples, offsets, n = _packed(samples, offsets)
+        window_offsets = np.concatenate(
+            [[0], np.cumsum(scan_window_count(self.input_size, np.diff(offsets)))]).astype(np.int64)
+        total = int(window_offsets[-1])
+        events = np.zeros(total, dtype=SCAN_EVENT)          # (no more events than windows)
+        best = np.zeros(total, dtype=np.int32) if track else None
+        margin = np.zeros(total, dtype=np.float64) if track else None
+        found, interior = ctypes.c_int64(0), ctypes.c_int64(0)
+        if n > 0:
+            check(self._lib.dbh_scan_i16(
+                self._handle, samples.ctypes.data if samples.size else None, offsets.ctypes.data,
+                n, 0 if side == 'start' else 1, float(threshold), int(min_windows),
+                int(skip_windows), best.ctypes.data if track else None,
+                margin.ctypes.data if track else None, events.ctypes.data, total,
+                ctypes.byref(found), ctypes.byref(interior)), 'dbh_scan_i16')
+        events = events[:found.value]
+        assert int((events['first'] >= skip_windows).sum()) == interior.value
+        return (events, best, margin, window_offsets) if track else events
 
     # -- device-resident entry points (inputs/outputs are raw device pointers) -----------------
     def workspace_bytes(self, n_reads, scan_size):

@@ -79,37 +79,38 @@ def pack(signals, keep):
     return (np.concatenate(parts) if parts else np.zeros(0, dtype=np.int16)), offsets
 
 
-def fast5_batches(fast5_files, args, classify, keep, sizes, n_classes, labels):
-    """(samples, offsets, labels or None, files finished) per unit of ``classify``'s loaders:
-    batches of one-read files, then - with ``--multi_read`` - the containers among them."""
+def fast5_units(fast5_files, args, classify, keep, sizes, n_classes, command='sweep'):
+    """The units of ``classify``'s loaders (containers.py): batches of one-read files, then - with
+    ``--multi_read`` - the containers among them."""
     from . import containers
     from .load_fast5s import determine_single_or_multi_fast5s, reader_kind
     if not fast5_files:
         sys.exit('Error: no fast5 files found')
     multi_read = bool(getattr(args, 'multi_read', False))
     if not multi_read and determine_single_or_multi_fast5s(fast5_files) == 'multi':
-        sys.exit('Error: deepbinner sweep requires one-read-per-file fast5s - convert with '
-                 'multi_to_single_fast5 before running, or give --multi_read')
+        sys.exit('Error: deepbinner {} requires one-read-per-file fast5s - convert with '
+                 'multi_to_single_fast5 before running, or give --multi_read'.format(command))
     units = containers.Units(args, sizes[0], sizes[1], n_classes, keep=keep,
                              threads=int(getattr(args, 'loader_procs', 0) or 0), skip_damaged=True)
-
-    def loaded():
-        later = [] if multi_read else None
-        if multi_read and determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
-            later = fast5_files
+    later = [] if multi_read else None
+    if multi_read and determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
+        later = fast5_files
+    else:
+        singles = fast5_files
+        if multi_read and reader_kind() == 'python':
+            later = [f for f in fast5_files if classify._python_holds_several_reads(f)]
+            singles = [f for f in fast5_files if f not in set(later)]
+        yield from classify.load_in_batches(singles, args, keep, later)
+    if later:
+        if reader_kind() == 'native':
+            yield from containers.files_done(containers.packed_containers(later, units))
         else:
-            singles = fast5_files
-            if multi_read and reader_kind() == 'python':
-                later = [f for f in fast5_files if classify._python_holds_several_reads(f)]
-                singles = [f for f in fast5_files if f not in set(later)]
-            yield from classify.load_in_batches(singles, args, keep, later)
-        if later:
-            if reader_kind() == 'native':
-                yield from containers.files_done(containers.packed_containers(later, units))
-            else:
-                yield from containers.files_done(containers.read_chunks(later, units))
+            yield from containers.files_done(containers.read_chunks(later, units))
 
-    for unit in loaded():
+
+def fast5_batches(fast5_files, args, classify, keep, sizes, n_classes, labels):
+    """(samples, offsets, labels or None, files finished) per unit of ``fast5_units``."""
+    for unit in fast5_units(fast5_files, args, classify, keep, sizes, n_classes):
         if hasattr(unit, 'samples'):
             samples, offsets = unit.samples, unit.offsets
         else:

@@ -287,6 +287,79 @@ int dbh_sweep_tally(const int32_t* start_best_host, const double* start_margin_h
                     const int32_t* labels_host, int64_t n_reads, int steps, int n_classes,
                     const double* thresholds_host, int n_thresholds, int64_t* counts_host);
 
+/* ---- scan: barcode signal in EVERY window of a read, and the events it makes ------------------ */
+/* call_batch looks at the first (or last) scan_size samples of a read (classify.py:337-357).  A
+ * chimeric read - two molecules in one signal - carries its second adapter and barcode somewhere in
+ * the middle, where no window of classify ever lies.  The scan carries the same windows on to the
+ * read's other end and says where a barcode class leads.  What it finds with the shipped models are
+ * SYNTHETIC junctions (reads packed end to end); nothing here has been validated on real chimeric
+ * reads.
+ *
+ * L = the model's input size, h = L / 2, a read has n samples.
+ *   Window count.  W(n) = 1 for n <= L, else ceil((n - L) / h) + 1: the last window reaches the
+ *       read's end and holds more than h samples.  dbh_scan_window_count (host only).
+ *   Window k, side start: samples [k h, min(k h + L, n)), normalised over the samples present,
+ *       zero-padded behind.  Side end: samples [max(n - k h - L, 0), n - k h), padded in front.
+ *       For k < scan_size / h these are exactly call_batch's windows (classify.py:337-357).
+ *   Normalising is the data set's rule ("device-fed batches", above): S and Q in int64, exact
+ *       D = m Q - S^2 over the m samples present, mean = (double)S / m, std = sqrt((double)D) / m,
+ *       each value (float)(((double)x - mean) / std), or (float)((double)x - mean) where D == 0; an
+ *       empty window (n == 0) is all zeros.
+ *   Track.  Per window (best, margin): the sweep's fold at steps = 1 applied to that window alone
+ *       - make_sum_to_one, then the top two, ties to the lower class (classify.py:285-295) - which
+ *       is dbh_sweep_windows_dev(model, probs, n_windows, 1, ...) with the windows as its reads.
+ *   Fire.  Window k fires class b at threshold t when best == b != 0 && margin >= t.
+ *   Event.  A maximal run of consecutive windows of ONE read that fire the same class, at least
+ *       min_windows long: (read, class, first, last, peak = the highest margin of the run).
+ *       Adjacent runs of different classes are separate events.  An event is INTERIOR when
+ *       first >= skip_windows (the scan command passes scan_size / h: the windows classify itself
+ *       looks at).  Events come back ordered by (read, first).
+ *   Capacity.  The first max_events events are written; n_events reports the true total.
+ * Events are integers and comparisons only: the result depends neither on the launch shape nor on
+ * how the reads were split into chunks.
+ *
+ * The windows of a batch are numbered through: window_offsets [n_reads + 1] int64 is the exclusive
+ * prefix of W over the reads (dbh_scan_window_offsets_dev), global window g of the batch is window
+ * g - window_offsets[r] of the read r it falls into.  dbh_scan_windows_dev is the front alone, for
+ * parity tests: x_dev [n_windows][input_size] fp32 for global windows [first_window, first_window
+ * + n_windows), any even input_size from 96 to 16,384; a window outside the batch is all zeros.
+ * dbh_scan_events_dev takes the track in global window order (best int32, margin fp64);
+ * per_read_interior_dev (n_reads int32, may be NULL) gets each read's count of interior events,
+ * counted whatever the capacity.  It owns a temporary block for the per-read counts, so unlike the
+ * other _dev entries it returns when the events are written.
+ * dbh_scan_i16: host buffers, blocks.  The windows go through the paths that take normalised
+ * windows (what dbh_predict_dev launches) in chunks of at most 256 MiB of fp32 input - and, on a
+ * persistent model, of at most dbh_model_set_host_group windows.  best_host / margin_host are
+ * optional: the whole ragged track in global window order (the sum of W over the reads each); NULL
+ * = not wanted.  events_host holds max_events entries (NULL with max_events == 0); *n_interior
+ * counts the interior events, whatever the capacity.
+ * Every entry checks its arguments before any device work and writes nothing on error: a null
+ * model or pointer, n_reads < 0, a side that is neither DBH_SIDE_START nor DBH_SIDE_END,
+ * min_windows < 1, skip_windows < 0, max_events < 0, first_window or n_windows < 0, offsets that
+ * run backwards (host entry), an input_size that is odd or outside 96 .. 16,384:
+ * DBH_ERR_INVALID_ARGUMENT.  n_reads == 0 is DBH_OK (the host entry then reports no events). */
+typedef struct dbh_scan_event {
+    int64_t read;
+    int32_t cls, first, last, reserved;
+    double peak;
+} dbh_scan_event;
+int dbh_scan_window_count(int input_size, int64_t n_samples, int64_t* count);
+int dbh_scan_window_offsets_dev(const int64_t* offsets_dev, int64_t n_reads, int input_size,
+                                int64_t* window_offsets_dev, dbh_stream stream);
+int dbh_scan_windows_dev(const int16_t* samples_dev, const int64_t* offsets_dev,
+                         const int64_t* window_offsets_dev, int64_t n_reads, int input_size,
+                         int side, int64_t first_window, int64_t n_windows, float* x_dev,
+                         dbh_stream stream);
+int dbh_scan_events_dev(const int32_t* best_dev, const double* margin_dev,
+                        const int64_t* window_offsets_dev, int64_t n_reads, double threshold,
+                        int min_windows, int skip_windows, dbh_scan_event* events_dev,
+                        int64_t max_events, int32_t* per_read_interior_dev, int64_t* n_events_dev,
+                        dbh_stream stream);
+int dbh_scan_i16(dbh_model* model, const int16_t* samples_host, const int64_t* offsets_host,
+                 int64_t n_reads, int side, double threshold, int min_windows, int skip_windows,
+                 int32_t* best_host, double* margin_host, dbh_scan_event* events_host,
+                 int64_t max_events, int64_t* n_events, int64_t* n_interior);
+
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's
  * inflate() over every chunk on the host.  Here the loader may hand over the chunks AS STORED
