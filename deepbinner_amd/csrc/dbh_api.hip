@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <new>
@@ -132,7 +133,7 @@ struct dbh_model {
     bool clock_probe = false;  unsigned clock_grid = 0;
     bool phase_probe = false;      // dbh_forward_phases_enable
     TimingBrackets timing;
-    // staging slots of the host-buffer entry points (classify_host: overlapped H2D / kernels / D2H)
+    // staging slots of the host-buffer entry points (host_groups: overlapped H2D / kernels / D2H)
     static constexpr int kSlots = 3;
     static constexpr int64_t kDefaultGroup = 32768;
     int64_t host_group_windows = kDefaultGroup;     // dbh_model_set_host_group
@@ -225,12 +226,35 @@ int launch_forward(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev
     return DBH_OK;
 }
 
-// the general path's share of dbh_classify_workspace_bytes: per-window probabilities, then the
-// activations of one chunk
+// the general path's workspace (its share of dbh_classify_workspace_bytes and of
+// dbh_sweep_workspace_bytes): per-window probabilities, then, at general_act_offset, the
+// activations of one chunk.  Sizing and window_probs_dev place them by the one function.
+size_t general_act_offset(const dbh_model* m, int64_t windows) {
+    return align256((size_t)windows * m->n_classes * sizeof(float));
+}
 size_t general_workspace(const dbh_model* m, int64_t n_reads, int steps) {
     const int64_t windows = n_reads * steps;
-    return align256((size_t)windows * m->n_classes * sizeof(float)) +
-           dbh_gen::activation_bytes(m->gen, windows);
+    return general_act_offset(m, windows) + dbh_gen::activation_bytes(m->gen, windows);
+}
+
+// The window pass of either model kind: the probabilities of every window of n_reads reads,
+// [n_reads * steps, C], to the front of the workspace.  A general model runs layer by layer with its
+// activations behind them; a persistent model's forward kernel slices and normalises its own windows
+// and, given no calls pointer, leaves per-window probabilities at one scan step too.  (score_diff
+// only travels with the launch: nothing is called here.)
+int window_probs_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offsets_dev,
+                     int64_t n_reads, int steps, int side, double score_diff, const ReadHints& hints,
+                     TailScratch* tail, void* workspace_dev, hipStream_t stream) {
+    if (!workspace_dev) return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t windows = n_reads * steps;
+    float* wprobs = (float*)workspace_dev;
+    if (m->kind == DBH_MODEL_KIND_GENERAL) {
+        DBH_HIP(dbh_gen::forward(m->gen, nullptr, samples_dev, offsets_dev, steps, side, windows, wprobs,
+                                 (char*)workspace_dev + general_act_offset(m, windows), stream));
+        return DBH_OK;
+    }
+    const FusedInput in{samples_dev, offsets_dev, steps, side, score_diff, nullptr, hints, tail};
+    return launch_forward(m, nullptr, windows, wprobs, -1, nullptr, stream, in);
 }
 
 // dbh_predict(_dev) on a general model: activations in a per-stream buffer of the model
@@ -593,35 +617,21 @@ int classify_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* of
     if (steps <= 0 || (side != DBH_SIDE_START && side != DBH_SIDE_END) || !samples_dev ||
         !offsets_dev || !probs_dev || !calls_dev)
         return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind == DBH_MODEL_KIND_PERSISTENT && steps == 1) {
+        // one window per read: slice + normalise + CNN + renormalise + call in ONE launch
+        const FusedInput in{samples_dev, offsets_dev, steps, side, score_diff, calls_dev, hints, tail};
+        return launch_forward(m, nullptr, n_reads, probs_dev, -1, nullptr, (hipStream_t)stream, in);
+    }
+    // a general model (any steps, C <= 256), or several scan steps per read: every window's
+    // probabilities to the workspace, then the model's merge kernel finishes each read
+    DBH_TRY(window_probs_dev(m, samples_dev, offsets_dev, n_reads, steps, side, score_diff, hints, tail,
+                             workspace_dev, (hipStream_t)stream));
+    const float* wprobs = (const float*)workspace_dev;
     if (m->kind == DBH_MODEL_KIND_GENERAL) {
-        // every window's probabilities to the workspace, then the merge (any steps, C <= 256)
-        if (!workspace_dev) return DBH_ERR_INVALID_ARGUMENT;
-        float* wprobs = (float*)workspace_dev;
-        void* act = (char*)workspace_dev + align256((size_t)(n_reads * steps) * m->n_classes * sizeof(float));
-        DBH_HIP(dbh_gen::forward(m->gen, nullptr, samples_dev, offsets_dev, steps, side,
-                                 n_reads * steps, wprobs, act, (hipStream_t)stream));
         DBH_HIP(dbh_gen::merge(wprobs, n_reads, steps, m->n_classes, score_diff, probs_dev,
                                calls_dev, (hipStream_t)stream));
         return DBH_OK;
     }
-    FusedInput in;
-    in.samples = samples_dev;
-    in.offsets = offsets_dev;
-    in.steps = steps;
-    in.side = side;
-    in.score_diff = score_diff;
-    in.hints = hints;
-    in.tail = tail;
-    if (steps == 1) {
-        // one window per read: slice + normalise + CNN + renormalise + call in ONE launch
-        in.calls = calls_dev;
-        return launch_forward(m, nullptr, n_reads, probs_dev, -1, nullptr, (hipStream_t)stream, in);
-    }
-    // several scan steps per read: the CNN kernel slices and normalises its own windows and
-    // leaves per-window probabilities in the workspace; the merge kernel finishes each read
-    if (!workspace_dev) return DBH_ERR_INVALID_ARGUMENT;
-    float* wprobs = (float*)workspace_dev;
-    DBH_TRY(launch_forward(m, nullptr, n_reads * steps, wprobs, -1, nullptr, (hipStream_t)stream, in));
     return dbh_merge_calls_dev(wprobs, n_reads, steps, m->n_classes, score_diff, probs_dev,
                                calls_dev, stream);
 }
@@ -681,59 +691,43 @@ bool is_pinned(const void* p, size_t bytes) {
 
 using dbh_host::staged_copy;
 
-struct HostJob {
-    dbh_model* model[2] = {nullptr, nullptr};      // start model, end model (either may be null)
-    int side[2] = {DBH_SIDE_START, DBH_SIDE_END};
-    float* probs_host[2] = {nullptr, nullptr};     // per model: n_reads x C, or null
-    int32_t* calls_host[2] = {nullptr, nullptr};   // per model: n_reads, or null
-    int32_t* final_host = nullptr;                 // combine_calls of the two, or null
-    int combine_mode = DBH_REQUIRE_EITHER;
+// One call of the host-buffer pipeline (host_groups): what its tenants differ in.
+struct GroupJob {
+    int steps = 1;                                    // windows per read: sets the group size
+    std::function<size_t(int64_t cnt)> out_bytes;     // a group's results (sl.d_out, sl.h_out)
+    std::function<size_t(int64_t cnt)> work_bytes;    // ... and its workspace (sl.d_work)
+    // the device work of a group of cnt reads, on sl.stream, results to sl.d_out -> status
+    std::function<int(HostSlot& sl, const int16_t* d_samples, const int64_t* d_offsets, int64_t cnt,
+                      const ReadHints& hints)> launch;
+    // reads r0 .. r0 + cnt - 1 are back: h_out is what their group left at sl.d_out
+    std::function<void(int64_t r0, int64_t cnt, const char* h_out)> collect;
 };
 
-// The host-buffer pipeline behind dbh_classify_i16 and dbh_classify_pair_i16.  Reads travel in
-// groups of at most ~32k windows per model through kSlots staging slots, each with its own
-// stream: while the GPU works on group g, group g+1 is uploaded (straight from the caller's
-// buffer when that is pinned, through a pinned staging copy otherwise) and the results of group
-// g-1 come back.  Both models read the SAME uploaded samples; their kernels, the merge kernels and
-// the combine kernel of a group follow each other on the group's stream.
-int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t* offsets_host,
-                  int64_t n_reads, int scan_size, double score_diff) {
-    dbh_model* m = job.model[0] ? job.model[0] : job.model[1];      // owns the slots
-    if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
-    if (n_reads == 0) return DBH_OK;
-    const bool both = job.model[0] && job.model[1];
-    if (!offsets_host || check_pair(job.model, scan_size) != DBH_OK || (job.final_host && !both))
-        return DBH_ERR_INVALID_ARGUMENT;
-    int steps = 0;          // the larger of the models' (they may differ in input size)
-    for (dbh_model* mj : job.model)
-        if (mj) steps = std::max(steps, dbh_host::model_steps(mj->input_size, scan_size));
+// The host-buffer pipeline behind dbh_classify_i16, dbh_classify_pair_i16 and dbh_sweep_pair_i16.
+// Reads travel in groups of at most ~32k windows per model through the kSlots staging slots of m,
+// each with its own stream: while the GPU works on group g, group g+1 is uploaded (straight from
+// the caller's buffer when that is pinned, through a pinned staging copy otherwise) and the results
+// of group g-1 come back.  What a group launches reads the SAME uploaded samples, kernel after
+// kernel on the group's stream.  The slots keep what they have grown to from call to call, whichever
+// tenant's layout they held last.  For n_reads > 0 and offsets_host not null.
+int host_groups(dbh_model* m, const GroupJob& job, const int16_t* samples_host,
+                const int64_t* offsets_host, int64_t n_reads) {
     // the current device is a per-thread setting: a caller on another thread than the one that
     // created the model gets the model's device
     DBH_HIP(hipSetDevice(m->device));
-    const int C = m->n_classes;
     const int64_t total_samples = offsets_host[n_reads] - offsets_host[0];
     if (total_samples < 0 || (total_samples > 0 && !samples_host)) return DBH_ERR_INVALID_ARGUMENT;
     const bool pinned = total_samples > 0 &&
                         is_pinned(samples_host + offsets_host[0], (size_t)total_samples * 2);
     const int64_t group = std::max<int64_t>(
-        1, (m->kind == DBH_MODEL_KIND_GENERAL ? dbh_model::kDefaultGroup : m->host_group_windows) / steps);
+        1, (m->kind == DBH_MODEL_KIND_GENERAL ? dbh_model::kDefaultGroup : m->host_group_windows) / job.steps);
     constexpr int kSlots = dbh_model::kSlots;
     struct Pending { int64_t r0 = 0, cnt = 0; bool live = false; } pending[kSlots];
     auto drain = [&](int k) -> int {
         HostSlot& sl = m->slot[k];
         if (!pending[k].live) return DBH_OK;
         DBH_HIP(hipStreamSynchronize(sl.stream));
-        const int64_t cnt = pending[k].cnt, r0 = pending[k].r0;
-        const dbh_host::GroupOut at(cnt, C, job.model[0], job.model[1]);
-        const char* h = sl.h_out.as<char>();
-        for (int j = 0; j < 2; ++j) {
-            if (job.model[j] && job.probs_host[j])
-                std::memcpy(job.probs_host[j] + r0 * C, h + at.probs[j], (size_t)cnt * C * sizeof(float));
-            if (job.model[j] && job.calls_host[j])
-                std::memcpy(job.calls_host[j] + r0, h + at.calls[j], (size_t)cnt * sizeof(int32_t));
-        }
-        if (both && job.final_host)
-            std::memcpy(job.final_host + r0, h + at.final_calls, (size_t)cnt * sizeof(int32_t));
+        job.collect(pending[k].r0, pending[k].cnt, sl.h_out.as<char>());
         pending[k].live = false;
         return DBH_OK;
     };
@@ -759,13 +753,12 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
         const size_t raw_bytes = (size_t)(s1 - s0) * sizeof(int16_t);
         const size_t sample_bytes = align256(raw_bytes);
         const size_t off_bytes = (size_t)(cnt + 1) * sizeof(int64_t);
-        const dbh_host::GroupOut out(cnt, C, job.model[0], job.model[1]);
-        const size_t work = pair_workspace_bytes(job.model, cnt, scan_size);
+        const size_t out_bytes = job.out_bytes(cnt), work = job.work_bytes(cnt);
         // host side: the relative offsets always, the samples only when they have to be staged
         e = sl.h_in.reserve(off_bytes + (pinned ? 0 : sample_bytes));
-        if (e == hipSuccess) e = sl.h_out.reserve(out.total);
+        if (e == hipSuccess) e = sl.h_out.reserve(out_bytes);
         if (e == hipSuccess) e = sl.d_in.reserve(sample_bytes + off_bytes);
-        if (e == hipSuccess) e = sl.d_out.reserve(out.total);
+        if (e == hipSuccess) e = sl.d_out.reserve(out_bytes);
         if (e == hipSuccess && work) e = sl.d_work.reserve(work);
         if (e != hipSuccess) return fail(hip_fail(e, "growing a staging slot"));
 
@@ -794,15 +787,11 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
         if (e == hipSuccess)
             e = hipMemcpyAsync((void*)d_offsets, rel, off_bytes, hipMemcpyHostToDevice, sl.stream);
         if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync H2D"));
-        float* const d_probs[2] = {sl.d_out.as<float>(out.probs[0]), sl.d_out.as<float>(out.probs[1])};
-        int32_t* const d_calls[2] = {sl.d_out.as<int32_t>(out.calls[0]), sl.d_out.as<int32_t>(out.calls[1])};
         // (all reads of the group equally long?  then the kernel need not wait for the offsets)
-        st = classify_pair_dev(job.model, job.side, d_samples, d_offsets, cnt, scan_size, score_diff,
-                               d_probs, d_calls, job.combine_mode, sl.d_out.as<int32_t>(out.final_calls),
-                               sl.d_work.get(), sl.stream,
-                               ReadHints{0, dbh_host::uniform_length(rel, cnt), s1 - s0}, &sl.tail);
+        st = job.launch(sl, d_samples, d_offsets, cnt,
+                        ReadHints{0, dbh_host::uniform_length(rel, cnt), s1 - s0});
         if (st != DBH_OK) return fail(st);
-        e = hipMemcpyAsync(sl.h_out.get(), sl.d_out.get(), out.total, hipMemcpyDeviceToHost, sl.stream);
+        e = hipMemcpyAsync(sl.h_out.get(), sl.d_out.get(), out_bytes, hipMemcpyDeviceToHost, sl.stream);
         if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync D2H"));
         pending[k].r0 = r0;
         pending[k].cnt = cnt;
@@ -813,6 +802,55 @@ int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t
         if (st != DBH_OK) return fail(st);
     }
     return DBH_OK;
+}
+
+struct HostJob {
+    dbh_model* model[2] = {nullptr, nullptr};      // start model, end model (either may be null)
+    int side[2] = {DBH_SIDE_START, DBH_SIDE_END};
+    float* probs_host[2] = {nullptr, nullptr};     // per model: n_reads x C, or null
+    int32_t* calls_host[2] = {nullptr, nullptr};   // per model: n_reads, or null
+    int32_t* final_host = nullptr;                 // combine_calls of the two, or null
+    int combine_mode = DBH_REQUIRE_EITHER;
+};
+
+// dbh_classify_i16 and dbh_classify_pair_i16 through host_groups: per group both models' kernels,
+// the merge kernels and the combine kernel, a GroupOut coming back
+int classify_host(const HostJob& job, const int16_t* samples_host, const int64_t* offsets_host,
+                  int64_t n_reads, int scan_size, double score_diff) {
+    dbh_model* m = job.model[0] ? job.model[0] : job.model[1];      // owns the slots
+    if (!m || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    const bool both = job.model[0] && job.model[1];
+    if (!offsets_host || check_pair(job.model, scan_size) != DBH_OK || (job.final_host && !both))
+        return DBH_ERR_INVALID_ARGUMENT;
+    const int C = m->n_classes;
+    auto layout = [&](int64_t cnt) { return dbh_host::GroupOut(cnt, C, job.model[0], job.model[1]); };
+    GroupJob groups;
+    for (dbh_model* mj : job.model)      // the larger of the models' (they may differ in input size)
+        if (mj) groups.steps = std::max(groups.steps, dbh_host::model_steps(mj->input_size, scan_size));
+    groups.out_bytes = [&](int64_t cnt) { return layout(cnt).total; };
+    groups.work_bytes = [&](int64_t cnt) { return pair_workspace_bytes(job.model, cnt, scan_size); };
+    groups.launch = [&](HostSlot& sl, const int16_t* d_samples, const int64_t* d_offsets, int64_t cnt,
+                        const ReadHints& hints) {
+        const dbh_host::GroupOut out = layout(cnt);
+        float* const d_probs[2] = {sl.d_out.as<float>(out.probs[0]), sl.d_out.as<float>(out.probs[1])};
+        int32_t* const d_calls[2] = {sl.d_out.as<int32_t>(out.calls[0]), sl.d_out.as<int32_t>(out.calls[1])};
+        return classify_pair_dev(job.model, job.side, d_samples, d_offsets, cnt, scan_size, score_diff,
+                                 d_probs, d_calls, job.combine_mode, sl.d_out.as<int32_t>(out.final_calls),
+                                 sl.d_work.get(), sl.stream, hints, &sl.tail);
+    };
+    groups.collect = [&](int64_t r0, int64_t cnt, const char* h) {
+        const dbh_host::GroupOut at = layout(cnt);
+        for (int j = 0; j < 2; ++j) {
+            if (job.model[j] && job.probs_host[j])
+                std::memcpy(job.probs_host[j] + r0 * C, h + at.probs[j], (size_t)cnt * C * sizeof(float));
+            if (job.model[j] && job.calls_host[j])
+                std::memcpy(job.calls_host[j] + r0, h + at.calls[j], (size_t)cnt * sizeof(int32_t));
+        }
+        if (both && job.final_host)
+            std::memcpy(job.final_host + r0, h + at.final_calls, (size_t)cnt * sizeof(int32_t));
+    };
+    return host_groups(m, groups, samples_host, offsets_host, n_reads);
 }
 
 }  // namespace
@@ -949,24 +987,11 @@ int sweep_i16_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* offse
     if (n_reads == 0) return DBH_OK;
     if (!samples_dev || !offsets_dev || !best_dev || !margin_dev || !workspace_dev)
         return DBH_ERR_INVALID_ARGUMENT;
-    float* wprobs = (float*)workspace_dev;
-    if (m->kind == DBH_MODEL_KIND_GENERAL) {
-        void* act = (char*)workspace_dev + align256((size_t)(n_reads * steps) * m->n_classes * sizeof(float));
-        DBH_HIP(dbh_gen::forward(m->gen, nullptr, samples_dev, offsets_dev, steps, side,
-                                 n_reads * steps, wprobs, act, (hipStream_t)stream));
-    } else {
-        // no calls pointer: the forward kernel leaves per-window probabilities, at one scan step
-        // too (where classify takes the fused one-launch finish)
-        FusedInput in;
-        in.samples = samples_dev;
-        in.offsets = offsets_dev;
-        in.steps = steps;
-        in.side = side;
-        in.hints = hints;
-        in.tail = tail;
-        DBH_TRY(launch_forward(m, nullptr, n_reads * steps, wprobs, -1, nullptr, (hipStream_t)stream, in));
-    }
-    return dbh_sweep_windows_dev(m, wprobs, n_reads, steps, best_dev, margin_dev, stream);
+    // (at one scan step too, where classify takes the fused one-launch finish)
+    DBH_TRY(window_probs_dev(m, samples_dev, offsets_dev, n_reads, steps, side, 0.0, hints, tail,
+                             workspace_dev, (hipStream_t)stream));
+    return dbh_sweep_windows_dev(m, (const float*)workspace_dev, n_reads, steps, best_dev, margin_dev,
+                                 stream);
 }
 
 // A pair for a sweep: one device, one class count and - one fold serves both sides' prefixes -
@@ -981,24 +1006,8 @@ int sweep_pair_steps(dbh_model* const models[2], int max_scan_size) {
     return dbh_host::model_steps(m->input_size, max_scan_size);
 }
 
-// what comes back per group of sweep_host: each present model's best, then its margin
-struct SweepOut {
-    int32_t* best[2] = {nullptr, nullptr};
-    double* margin[2] = {nullptr, nullptr};
-    size_t total = 0;
-    SweepOut(void* base, int64_t n_reads, int steps, dbh_model* const models[2]) {
-        dbh_host::Carve carve(base);
-        for (int j = 0; j < 2; ++j) {
-            if (!models[j]) continue;
-            best[j] = carve.take<int32_t>((size_t)n_reads * steps);
-            margin[j] = carve.take<double>((size_t)n_reads * steps);
-        }
-        total = carve.used;
-    }
-};
-
-// classify_host's pipeline - the same groups, the same three slots and streams, pinned buffers read
-// in place - with the fold in the merge's place and (best, margin) of every prefix coming back
+// dbh_sweep_pair_i16 through host_groups: per group each model's window pass and fold, a SweepOut -
+// (best, margin) of every prefix - coming back
 int sweep_host(dbh_model* const models[2], const int16_t* samples_host, const int64_t* offsets_host,
                int64_t n_reads, int max_scan_size, int32_t* const best_host[2],
                double* const margin_host[2]) {
@@ -1013,98 +1022,39 @@ int sweep_host(dbh_model* const models[2], const int16_t* samples_host, const in
     if (total_samples < 0 || (total_samples > 0 && !samples_host)) return DBH_ERR_INVALID_ARGUMENT;
     for (int64_t i = 0; i < n_reads; ++i)
         if (offsets_host[i + 1] < offsets_host[i]) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_HIP(hipSetDevice(m->device));
-    const bool pinned = total_samples > 0 &&
-                        is_pinned(samples_host + offsets_host[0], (size_t)total_samples * 2);
-    const int64_t group = std::max<int64_t>(
-        1, (m->kind == DBH_MODEL_KIND_GENERAL ? dbh_model::kDefaultGroup : m->host_group_windows) / steps);
-    constexpr int kSlots = dbh_model::kSlots;
-    struct Pending { int64_t r0 = 0, cnt = 0; bool live = false; } pending[kSlots];
-    auto drain = [&](int k) -> int {
-        HostSlot& sl = m->slot[k];
-        if (!pending[k].live) return DBH_OK;
-        DBH_HIP(hipStreamSynchronize(sl.stream));
-        const int64_t cnt = pending[k].cnt, r0 = pending[k].r0;
-        const SweepOut h(sl.h_out.get(), cnt, steps, models);
+    auto layout = [&](const void* base, int64_t cnt) {
+        return dbh_host::SweepOut(const_cast<void*>(base), cnt, steps, models[0], models[1]);
+    };
+    GroupJob groups;
+    groups.steps = steps;
+    groups.out_bytes = [&](int64_t cnt) { return layout(nullptr, cnt).total; };
+    groups.work_bytes = [&](int64_t cnt) {
+        size_t work = 0, mine = 0;
+        for (int j = 0; j < 2; ++j)
+            if (models[j] && dbh_sweep_workspace_bytes(models[j], cnt, max_scan_size, &mine) == DBH_OK)
+                work = std::max(work, mine);
+        return work;
+    };
+    groups.launch = [&](HostSlot& sl, const int16_t* d_samples, const int64_t* d_offsets, int64_t cnt,
+                        const ReadHints& hints) {
+        const dbh_host::SweepOut d = layout(sl.d_out.get(), cnt);
+        for (int j = 0; j < 2; ++j) {
+            if (!models[j]) continue;
+            DBH_TRY(sweep_i16_dev(models[j], d_samples, d_offsets, cnt, j == 0 ? DBH_SIDE_START : DBH_SIDE_END,
+                                  max_scan_size, d.best[j], d.margin[j], sl.d_work.get(),
+                                  (dbh_stream)sl.stream.h, hints, &sl.tail));
+        }
+        return (int)DBH_OK;
+    };
+    groups.collect = [&](int64_t r0, int64_t cnt, const char* h_out) {
+        const dbh_host::SweepOut h = layout(h_out, cnt);
         for (int j = 0; j < 2; ++j) {
             if (!models[j]) continue;
             std::memcpy(best_host[j] + r0 * steps, h.best[j], (size_t)cnt * steps * sizeof(int32_t));
             std::memcpy(margin_host[j] + r0 * steps, h.margin[j], (size_t)cnt * steps * sizeof(double));
         }
-        pending[k].live = false;
-        return DBH_OK;
     };
-    auto fail = [&](int status) -> int {
-        for (auto& sl : m->slot)
-            if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-        return status;
-    };
-    int64_t g = 0;
-    for (int64_t r0 = 0; r0 < n_reads; r0 += group, ++g) {
-        const int k = (int)(g % kSlots);
-        HostSlot& sl = m->slot[k];
-        int st = drain(k);
-        if (st != DBH_OK) return fail(st);
-        hipError_t e = hipSuccess;
-        if (!sl.stream) e = hipStreamCreateWithFlags(&sl.stream.h, hipStreamNonBlocking);
-        if (e != hipSuccess) return fail(hip_fail(e, "hipStreamCreateWithFlags"));
-        const int64_t cnt = (n_reads - r0 < group) ? (n_reads - r0) : group;
-        const int64_t s0 = offsets_host[r0], s1 = offsets_host[r0 + cnt];
-        const size_t raw_bytes = (size_t)(s1 - s0) * sizeof(int16_t);
-        const size_t sample_bytes = align256(raw_bytes);
-        const size_t off_bytes = (size_t)(cnt + 1) * sizeof(int64_t);
-        const size_t out_bytes = SweepOut(nullptr, cnt, steps, models).total;
-        size_t work = 0, mine = 0;
-        for (int j = 0; j < 2; ++j)
-            if (models[j] && dbh_sweep_workspace_bytes(models[j], cnt, max_scan_size, &mine) == DBH_OK)
-                work = std::max(work, mine);
-        e = sl.h_in.reserve(off_bytes + (pinned ? 0 : sample_bytes));
-        if (e == hipSuccess) e = sl.h_out.reserve(out_bytes);
-        if (e == hipSuccess) e = sl.d_in.reserve(sample_bytes + off_bytes);
-        if (e == hipSuccess) e = sl.d_out.reserve(out_bytes);
-        if (e == hipSuccess) e = sl.d_work.reserve(work);
-        if (e != hipSuccess) return fail(hip_fail(e, "growing a staging slot"));
-
-        int64_t* rel = sl.h_in.as<int64_t>();
-        for (int64_t i = 0; i <= cnt; ++i) rel[i] = offsets_host[r0 + i] - s0;
-        const void* src = samples_host + s0;
-        if (raw_bytes && !pinned) {
-            staged_copy(sl.h_in.as<char>(off_bytes), src, raw_bytes);
-            src = sl.h_in.as<char>(off_bytes);
-        }
-        // (zero copy or a copy into HBM first: as classify_host)
-        const int16_t* d_samples = sl.d_in.as<int16_t>();
-        const int64_t* d_offsets = sl.d_in.as<int64_t>(sample_bytes);
-        if (raw_bytes && m->host_zero_copy) {
-            void* mapped = nullptr;
-            e = hipHostGetDevicePointer(&mapped, const_cast<void*>(src), 0);
-            d_samples = (const int16_t*)mapped;
-        } else if (raw_bytes) {
-            e = hipMemcpyAsync(sl.d_in.get(), src, raw_bytes, hipMemcpyHostToDevice, sl.stream);
-        }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((void*)d_offsets, rel, off_bytes, hipMemcpyHostToDevice, sl.stream);
-        if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync H2D"));
-        const SweepOut d(sl.d_out.get(), cnt, steps, models);
-        const ReadHints hints{0, dbh_host::uniform_length(rel, cnt), s1 - s0};
-        for (int j = 0; j < 2; ++j) {
-            if (!models[j]) continue;
-            st = sweep_i16_dev(models[j], d_samples, d_offsets, cnt, j == 0 ? DBH_SIDE_START : DBH_SIDE_END,
-                               max_scan_size, d.best[j], d.margin[j], sl.d_work.get(),
-                               (dbh_stream)sl.stream.h, hints, &sl.tail);
-            if (st != DBH_OK) return fail(st);
-        }
-        e = hipMemcpyAsync(sl.h_out.get(), sl.d_out.get(), out_bytes, hipMemcpyDeviceToHost, sl.stream);
-        if (e != hipSuccess) return fail(hip_fail(e, "hipMemcpyAsync D2H"));
-        pending[k].r0 = r0;
-        pending[k].cnt = cnt;
-        pending[k].live = true;
-    }
-    for (int i = 0; i < kSlots; ++i) {       // oldest first
-        const int st = drain((int)((g + i) % kSlots));
-        if (st != DBH_OK) return fail(st);
-    }
-    return DBH_OK;
+    return host_groups(m, groups, samples_host, offsets_host, n_reads);
 }
 
 // the arguments of both tally entries (device or host pointers alike)

@@ -15,6 +15,7 @@
 // the batch or the stream it travels in.
 #include "dbh_general.h"
 #include "dbh_seam.h"
+#include "dbh_trees.h"
 
 #include <algorithm>
 #include <cmath>
@@ -293,45 +294,18 @@ __global__ __launch_bounds__(kThreads) void merge_kernel(const float* __restrict
         }
     }
     double p = (double)merged;
-    rv[c] = (valid && c > 0) ? p : 0.0;
-    __syncthreads();
-    for (int half = kThreads / 2; half >= 1; half >>= 1) {
-        if (c < half) rv[c] += rv[c + half];
-        __syncthreads();
-    }
-    const double rest = rv[0];
-    __syncthreads();
+    const double rest = dbh::tree_sum<kThreads>(rv, c, (valid && c > 0) ? p : 0.0);
     if (c == 0) rv[0] = p;
     __syncthreads();
     const double p0 = rv[0];
     __syncthreads();
     if (c > 0) p = p * ((1.0 - p0) / rest);
     if (valid) probs[read * C + c] = (float)p;
-    // best: highest probability, lowest class among equals
-    rv[c] = valid ? p : -1.0;
-    ri[c] = c;
-    __syncthreads();
-    for (int half = kThreads / 2; half >= 1; half >>= 1) {
-        if (c < half) {
-            const double o = rv[c + half];
-            const int oi = ri[c + half];
-            if (o > rv[c] || (o == rv[c] && oi < ri[c])) {
-                rv[c] = o;
-                ri[c] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    const double best_v = rv[0];
-    const int best = ri[0];
-    __syncthreads();
-    rv[c] = (valid && c != best) ? p : -1.0;
-    __syncthreads();
-    for (int half = kThreads / 2; half >= 1; half >>= 1) {
-        if (c < half) rv[c] = fmax(rv[c], rv[c + half]);
-        __syncthreads();
-    }
-    if (c == 0) calls[read] = (best != 0 && (best_v - rv[0]) >= score_diff) ? best : 0;
+    // best: highest probability, lowest class among equals; then the runner-up (dbh_trees.h)
+    int best;
+    const double best_v = dbh::tree_best<kThreads>(rv, ri, c, valid ? p : -1.0, &best);
+    const double second = dbh::tree_max<kThreads>(rv, c, (valid && c != best) ? p : -1.0);
+    if (c == 0) calls[read] = (best != 0 && (best_v - second) >= score_diff) ? best : 0;
 }
 
 // ---- host ------------------------------------------------------------------------------------

@@ -43,8 +43,8 @@ struct Carve {
     }
 };
 
-// What comes back per group of the host-buffer pipeline (classify_host), packed: each present
-// model's probabilities, each present model's calls, the combined calls when both are there.
+// What comes back per group of the host-buffer pipeline (host_groups) to classify_host, packed: each
+// present model's probabilities, each present model's calls, the combined calls when both are there.
 struct GroupOut {
     size_t probs[2], calls[2], final_calls, total;
     GroupOut(int64_t n_reads, int n_classes, bool has_start, bool has_end) {
@@ -55,6 +55,24 @@ struct GroupOut {
         calls[1] = calls[0] + (has_start ? n * sizeof(int32_t) : 0);
         final_calls = calls[1] + (has_end ? n * sizeof(int32_t) : 0);
         total = final_calls + (has_start && has_end ? n * sizeof(int32_t) : 0);
+    }
+};
+
+// ... and to sweep_host: each present model's best, then its margin, n_reads x steps of each, carved
+// from `base` (null: sizes only)
+struct SweepOut {
+    int32_t* best[2] = {nullptr, nullptr};
+    double* margin[2] = {nullptr, nullptr};
+    size_t total = 0;
+    SweepOut(void* base, int64_t n_reads, int steps, bool has_start, bool has_end) {
+        Carve carve(base);
+        const bool has[2] = {has_start, has_end};
+        for (int j = 0; j < 2; ++j) {
+            if (!has[j]) continue;
+            best[j] = carve.take<int32_t>((size_t)n_reads * steps);
+            margin[j] = carve.take<double>((size_t)n_reads * steps);
+        }
+        total = carve.used;
     }
 };
 

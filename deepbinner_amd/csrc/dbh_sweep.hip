@@ -13,9 +13,8 @@
 // with them to the bit:
 //   fold32_kernel    32 lanes per read, the reductions of dbh_seam.h (reduce32: DPP inside the rows,
 //                    v_permlane16_swap across them) in renormalise_and_call's order
-//   fold256_kernel   one workgroup per read, the halving trees in LDS of dbh_general.hip's
-//                    merge_kernel (kept in that file, shaped to it: the three trees below restate
-//                    them, same pairing, same order)
+//   fold256_kernel   one workgroup per read, the halving trees in LDS that dbh_general.hip's
+//                    merge_kernel runs: both call dbh_trees.h's, one text
 // One guard the merges do not have: a read whose barcodes are all zero (rest == 0) keeps them zero
 // instead of 0 * (x / 0); class 0 is then the best class here as it is there, so no call changes, and
 // the margin is a number.
@@ -29,6 +28,7 @@
 #include "../../include/deepbinner_hip.h"
 #include "dbh_seam.h"
 #include "dbh_sweep.h"
+#include "dbh_trees.h"
 
 namespace dbh_sweep {
 namespace {
@@ -75,51 +75,7 @@ __global__ __launch_bounds__(kThreads) void fold32_kernel(const float* __restric
 }
 
 // ---- one workgroup per read (general models, C <= 256) ------------------------------------------
-// The three halving trees of dbh_general.hip's merge_kernel; all kThreads threads call each, and the
-// closing barrier lets the next call write rv / ri again.
-__device__ __forceinline__ double tree_sum(double* rv, int c, double v) {
-    rv[c] = v;
-    __syncthreads();
-    for (int half = kThreads / 2; half >= 1; half >>= 1) {
-        if (c < half) rv[c] += rv[c + half];
-        __syncthreads();
-    }
-    const double all = rv[0];
-    __syncthreads();
-    return all;
-}
-__device__ __forceinline__ double tree_best(double* rv, int* ri, int c, double v, int* index) {
-    rv[c] = v;
-    ri[c] = c;
-    __syncthreads();
-    for (int half = kThreads / 2; half >= 1; half >>= 1) {
-        if (c < half) {
-            const double o = rv[c + half];
-            const int oi = ri[c + half];
-            if (o > rv[c] || (o == rv[c] && oi < ri[c])) {
-                rv[c] = o;
-                ri[c] = oi;
-            }
-        }
-        __syncthreads();
-    }
-    const double top = rv[0];
-    *index = ri[0];
-    __syncthreads();
-    return top;
-}
-__device__ __forceinline__ double tree_max(double* rv, int c, double v) {
-    rv[c] = v;
-    __syncthreads();
-    for (int half = kThreads / 2; half >= 1; half >>= 1) {
-        if (c < half) rv[c] = fmax(rv[c], rv[c + half]);
-        __syncthreads();
-    }
-    const double top = rv[0];
-    __syncthreads();
-    return top;
-}
-
+// dbh_trees.h's three halving trees, the very ones merge_kernel finishes a read with.
 __global__ __launch_bounds__(kThreads) void fold256_kernel(const float* __restrict__ wprobs,
                                                            int steps, int C,
                                                            int* __restrict__ best,
@@ -138,14 +94,14 @@ __global__ __launch_bounds__(kThreads) void fold256_kernel(const float* __restri
             merged = s == 0 ? v : (c == 0 ? fminf(merged, v) : fmaxf(merged, v));
         }
         double p = (double)merged;
-        const double rest = tree_sum(rv, c, (valid && c > 0) ? p : 0.0);
+        const double rest = dbh::tree_sum<kThreads>(rv, c, (valid && c > 0) ? p : 0.0);
         if (c == 0) first = p;
         __syncthreads();
         const double p0 = first;
         if (c > 0) p = p * (rest > 0.0 ? (1.0 - p0) / rest : 0.0);
         int top_i;
-        const double top_v = tree_best(rv, ri, c, valid ? p : -1.0, &top_i);
-        const double second = tree_max(rv, c, (valid && c != top_i) ? p : -1.0);
+        const double top_v = dbh::tree_best<kThreads>(rv, ri, c, valid ? p : -1.0, &top_i);
+        const double second = dbh::tree_max<kThreads>(rv, c, (valid && c != top_i) ? p : -1.0);
         if (c == 0) {
             best[read * steps + s] = top_i;
             margin[read * steps + s] = top_v - second;

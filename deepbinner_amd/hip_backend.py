@@ -379,28 +379,30 @@ def classify_pair(start_model, end_model, samples, offsets, scan_size, score_dif
     models = (start_model, end_model)
     if start_model is None and end_model is None:
         raise ValueError('no model')
-    samples = np.ascontiguousarray(samples, dtype=np.int16)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n = len(offsets) - 1
-    if n < 0 or (n and (offsets[0] != 0 or offsets[-1] != len(samples))):
-        raise ValueError('offsets do not describe the sample buffer')
+    samples, offsets, n = _packed(samples, offsets)
     calls = np.empty(max(n, 0), dtype=np.int32)
     n_classes = next(m.n_classes for m in models if m is not None)
     side_calls = [np.empty(n, dtype=np.int32) if (want_sides and m is not None) else None
                   for m in models]
     side_probs = [np.empty((n, n_classes), dtype=np.float32) if (want_probs and m is not None)
                   else None for m in models]
-    ptr = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
     if n > 0:
         check(lib.dbh_classify_pair_i16(
-            start_model.handle if start_model is not None else None,
-            end_model.handle if end_model is not None else None,
+            _handle(start_model), _handle(end_model),
             samples.ctypes.data if samples.size else None, offsets.ctypes.data, n, int(scan_size),
-            float(score_diff), COMBINE_MODES[mode], calls.ctypes.data, ptr(side_calls[0]),
-            ptr(side_calls[1]), ptr(side_probs[0]), ptr(side_probs[1])), 'dbh_classify_pair_i16')
+            float(score_diff), COMBINE_MODES[mode], calls.ctypes.data, _ptr(side_calls[0]),
+            _ptr(side_calls[1]), _ptr(side_probs[0]), _ptr(side_probs[1])), 'dbh_classify_pair_i16')
     if want_sides or want_probs:
         return calls, tuple(side_calls), tuple(side_probs)
     return calls
+
+
+def _ptr(array):
+    return array.ctypes.data if array is not None else None
+
+
+def _handle(model):
+    return model.handle if model is not None else None
 
 
 def _packed(samples, offsets):
@@ -439,13 +441,11 @@ def sweep_pair(start_model, end_model, samples, offsets, max_scan_size):
     samples, offsets, n = _packed(samples, offsets)
     best = [np.zeros((n, steps), dtype=np.int32) if m is not None else None for m in models]
     margin = [np.zeros((n, steps), dtype=np.float64) if m is not None else None for m in models]
-    ptr = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
     if n > 0:
         check(lib.dbh_sweep_pair_i16(
-            start_model.handle if start_model is not None else None,
-            end_model.handle if end_model is not None else None,
+            _handle(start_model), _handle(end_model),
             samples.ctypes.data if samples.size else None, offsets.ctypes.data, n,
-            int(max_scan_size), ptr(best[0]), ptr(margin[0]), ptr(best[1]), ptr(margin[1])),
+            int(max_scan_size), _ptr(best[0]), _ptr(margin[0]), _ptr(best[1]), _ptr(margin[1])),
             'dbh_sweep_pair_i16')
     return (best[0], margin[0]), (best[1], margin[1])
 
@@ -492,9 +492,8 @@ def sweep_tally(start, end, thresholds, n_classes, labels=None, counts=None):
                         n_classes).shape
     if counts.shape != want or counts.dtype != np.int64 or not counts.flags['C_CONTIGUOUS']:
         raise ValueError('counts must be a C-contiguous int64 array of shape {}'.format(want))
-    ptr = lambda a: a.ctypes.data if a is not None else None      # noqa: E731
     check(load_library().dbh_sweep_tally(
-        ptr(held[0][0]), ptr(held[0][1]), ptr(held[1][0]), ptr(held[1][1]), ptr(labels), n, steps,
+        _ptr(held[0][0]), _ptr(held[0][1]), _ptr(held[1][0]), _ptr(held[1][1]), _ptr(labels), n, steps,
         int(n_classes), thresholds.ctypes.data if thresholds.size else None, len(thresholds),
         counts.ctypes.data), 'dbh_sweep_tally')
     return counts
@@ -686,17 +685,14 @@ def classify_pair_deflated(start_model, end_model, comp, streams, offsets, scan_
                 sides[side + '_calls'] = np.zeros(max(n, 0), dtype=np.int32)
                 sides[side + '_probs'] = np.zeros((max(n, 0), model.n_classes), dtype=np.float32)
 
-    def ptr(a):
-        return a.ctypes.data if a is not None else None
     if n > 0:
         check(lib.dbh_classify_pair_deflated_verbose(
-            start_model.handle if start_model is not None else None,
-            end_model.handle if end_model is not None else None,
+            _handle(start_model), _handle(end_model),
             comp.ctypes.data, max(comp.nbytes - 64, 0), streams.ctypes.data, len(streams),
             offsets.ctypes.data, n, int(scan_size), float(score_diff), COMBINE_MODES[mode],
             calls.ctypes.data, status.ctypes.data, samples.ctypes.data if want_samples else None,
-            stages if want_stages else None, ptr(sides['start_calls']), ptr(sides['end_calls']),
-            ptr(sides['start_probs']), ptr(sides['end_probs'])), 'dbh_classify_pair_deflated_verbose')
+            stages if want_stages else None, _ptr(sides['start_calls']), _ptr(sides['end_calls']),
+            _ptr(sides['start_probs']), _ptr(sides['end_probs'])), 'dbh_classify_pair_deflated_verbose')
     out = [calls, status]
     if want_samples:
         out.append(samples)

@@ -72,6 +72,38 @@ static void check_layouts() {
                                       g.total, 4);
                 report(ok, "layout group", has, n_reads, n_classes);
             }
+    // a group's results of the sweep, a Carve: the sizing pass (null base: null pointers) ends at the
+    // same `used` as the carving pass; a present side's best then its margin, start before end, tile
+    // the buffer on multiples of 256 bytes; an absent side has null pointers and takes no bytes; and
+    // the buffer, allocated with exactly `total` bytes, takes a write to every region's two ends
+    for (int has = 1; has <= 3; ++has)
+        for (long n_reads : {0L, 1L, 300L})
+            for (int steps : {1, 24}) {
+                const bool present[2] = {(has & 1) != 0, (has & 2) != 0};
+                const dbh_host::SweepOut sized(nullptr, n_reads, steps, present[0], present[1]);
+                std::vector<char> buffer(sized.total ? sized.total : 1);      // (data() is never null)
+                const dbh_host::SweepOut s(buffer.data(), n_reads, steps, present[0], present[1]);
+                const size_t cells = (size_t)n_reads * steps;
+                bool ok = sized.total == s.total && s.total % 256 == 0;
+                std::vector<std::pair<size_t, size_t>> regions;
+                for (int j = 0; j < 2; ++j) {
+                    ok = ok && !sized.best[j] && !sized.margin[j];
+                    if (!present[j]) {
+                        ok = ok && !s.best[j] && !s.margin[j];
+                        continue;
+                    }
+                    ok = ok && s.best[j] && s.margin[j];
+                    regions.push_back({(size_t)((char*)s.best[j] - buffer.data()), align256(cells * 4)});
+                    regions.push_back({(size_t)((char*)s.margin[j] - buffer.data()), align256(cells * 8)});
+                    if (cells) {
+                        s.best[j][0] = s.best[j][cells - 1] = j;
+                        s.margin[j][0] = s.margin[j][cells - 1] = 0.5;
+                    }
+                }
+                ok = ok && tiles(regions, s.total, 256) &&
+                     s.total == (size_t)(present[0] + present[1]) * (align256(cells * 4) + align256(cells * 8));
+                report(ok, "layout sweep", has, n_reads, steps);
+            }
 }
 
 // Carve: one sequence of take() calls, over a null base (the sizing pass) and over a buffer (the

@@ -57,6 +57,17 @@ def test_layouts_and_staged_copy(lines):
     assert any(c[1] == 'uniform_length' for c in checks)
 
 
+def test_sweep_layout_sizes_and_carves_alike(lines):
+    """dbh_host::SweepOut, what a group of the sweep brings back: for the start model alone, the end
+    model alone and both, at 0, 1 and 300 reads and 1 and 24 scan steps, the sizing pass (null base)
+    ends at the same total as the carving pass, a present side's best and margin lie in order,
+    256-aligned and without overlap, and an absent side has null pointers and takes no bytes."""
+    checks = [line.split() for line in lines if line.split()[1:3] == ['layout', 'sweep']]
+    assert all(c[0] == 'ok' for c in checks), [c for c in checks if c[0] != 'ok']
+    assert sorted(tuple(int(x) for x in c[3:6]) for c in checks) == sorted(
+        (has, n_reads, steps) for has in (1, 2, 3) for n_reads in (0, 1, 300) for steps in (1, 24))
+
+
 def test_carve_sizes_and_carves_alike(lines):
     """dbh_host::Carve, which lays out every buffer of the training-data units: the sizing pass
     (null base) and the carving pass of one sequence of take() calls end at the same `used`, the

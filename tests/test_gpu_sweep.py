@@ -2,6 +2,7 @@
 probabilities; the whole entry against ``classify_pair`` at every scan size, device against device
 and exact, down to the equality edge of ``>=``; the tally kernel against the restated tally; the
 command beside ``classify``'s table."""
+import contextlib
 import ctypes
 import os
 
@@ -182,6 +183,112 @@ def test_general_model_end_to_end(hip, all_signals):
     try:
         assert model.kind == hip.KIND_GENERAL
         check_end_to_end(hip, None, model, 96, 12, all_signals)
+    finally:
+        model.close()
+
+
+# ---- the host-buffer pipeline the sweep shares with classify --------------------------------------
+def same_sweep(got, want):
+    return all((got[j][part] is None and want[j][part] is None) or
+               np.array_equal(got[j][part], want[j][part]) for j in (0, 1) for part in (0, 1))
+
+
+@contextlib.contextmanager
+def pinned_copy(hip, samples):
+    """``samples`` in a dbh_malloc_host buffer, which the DMA engine reads in place."""
+    lib = hip.load_library()
+    ptr = ctypes.c_void_p()
+    hip.check(lib.dbh_malloc_host(ctypes.byref(ptr), samples.nbytes))
+    try:
+        pinned = np.ctypeslib.as_array(ctypes.cast(ptr.value, ctypes.POINTER(ctypes.c_int16)),
+                                       shape=samples.shape)
+        pinned[:] = samples
+        assert hip.is_pinned(pinned) and not hip.is_pinned(samples)
+        yield pinned
+    finally:
+        hip.check(lib.dbh_free_host(ptr))
+
+
+@pytest.fixture(scope='module')
+def ragged_sweep(hip, hip_models, native_sweep):
+    """The fixture's 300 reads with a zero-length read and a 5-sample read appended, and their sweep
+    in one group; the 300 come out as they did without the two."""
+    samples, offsets, swept = native_sweep
+    samples = np.concatenate([samples, np.arange(5, dtype=np.int16)])
+    offsets = np.concatenate([offsets, offsets[-1:], offsets[-1:] + 5])
+    whole = hip.sweep_pair(hip_models[STARTS], hip_models[ENDS], samples, offsets, K * 512)
+    assert same_sweep([[a[:300] for a in side] for side in whole], swept)
+    return samples, offsets, whole
+
+
+def test_pinned_input_is_the_pageable_run(hip, hip_models, native_sweep):
+    samples, offsets, swept = native_sweep
+    with pinned_copy(hip, samples) as pinned:
+        got = hip.sweep_pair(hip_models[STARTS], hip_models[ENDS], pinned, offsets, K * 512)
+    assert same_sweep(got, swept)
+
+
+@pytest.mark.parametrize('memory', ['pinned', 'pageable'])
+@pytest.mark.parametrize('reads_per_group', [1, 7])
+def test_group_shapes(hip, hip_models, ragged_sweep, reads_per_group, memory):
+    """One read per group, and seven: 302 reads then make 44 groups, the last one short, and every
+    slot comes round many times."""
+    samples, offsets, whole = ragged_sweep
+    start, end = hip_models[STARTS], hip_models[ENDS]
+    with pinned_copy(hip, samples) if memory == 'pinned' else contextlib.nullcontext(samples) as held:
+        start.set_host_group(reads_per_group * K)
+        try:
+            got = hip.sweep_pair(start, end, held, offsets, K * 512)
+        finally:
+            start.set_host_group(0)
+    assert same_sweep(got, whole)
+
+
+def test_one_slot_ring_two_tenants(hip, hip_models, ragged_sweep):
+    """classify, sweep, classify, the start model's sweep alone, seven reads per group on the same two
+    models: the slots' buffers hold layouts of different sizes in turn, and every call gives what it
+    gives on its own in one group."""
+    samples, offsets, whole = ragged_sweep
+    start, end = hip_models[STARTS], hip_models[ENDS]
+
+    def classify():
+        return hip.classify_pair(start, end, samples, offsets, K * 512, 0.5, want_sides=True,
+                                 want_probs=True)
+
+    def same_classify(got, want):
+        return np.array_equal(got[0], want[0]) and all(
+            np.array_equal(got[i][j], want[i][j]) for i in (1, 2) for j in (0, 1))
+
+    classified = classify()
+    start_alone = hip.sweep_pair(start, None, samples, offsets, K * 512)
+    assert same_sweep(start_alone, (whole[0], (None, None)))
+    start.set_host_group(7 * K)
+    end.set_host_group(7 * K)
+    try:
+        assert same_classify(classify(), classified)
+        assert same_sweep(hip.sweep_pair(start, end, samples, offsets, K * 512), whole)
+        assert same_classify(classify(), classified)
+        assert same_sweep(hip.sweep_pair(start, None, samples, offsets, K * 512), start_alone)
+    finally:
+        start.set_host_group(0)
+        end.set_host_group(0)
+
+
+def test_general_model_through_groups(hip, all_signals):
+    """A general model takes its group from the default 32,768 windows whatever set_host_group says:
+    3,000 reads at K = 12 scan steps (2,730 reads per group) go in two groups, the second one short,
+    and come out as their two halves do in a call - and so a group - of their own."""
+    model = hip.HipModel(general_fixtures.geometry(96, 33, name=ENDS), device=0)
+    try:
+        samples, offsets = random_reads(96, K, 13, all_signals, n=3000)
+        assert 32768 // K < 3000 and 1500 <= 32768 // K
+        whole = hip.sweep_pair(None, model, samples, offsets, K * 48)
+        cut = offsets[1500]
+        first = hip.sweep_pair(None, model, samples[:cut], offsets[:1501], K * 48)
+        second = hip.sweep_pair(None, model, samples[cut:], offsets[1500:] - cut, K * 48)
+        assert whole[0] == (None, None) and whole[1][0].shape == whole[1][1].shape == (3000, K)
+        for part in (0, 1):
+            assert np.array_equal(whole[1][part], np.concatenate([first[1][part], second[1][part]]))
     finally:
         model.close()
 
