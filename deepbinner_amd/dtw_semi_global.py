@@ -25,11 +25,34 @@ import os
 import numpy as np
 from numpy.ctypeslib import ndpointer
 
-EXPORTED_SYMBOLS = ('dtw_version', 'dtw_status_string', 'dtw_last_error', 'semi_global_dtw',
-                    'dtw_semi_global_batch', 'dtw_rescaled_batch', 'dtw_locate_batch',
-                    'dtw_last_kernel_time')
+from . import _cabi
+
 LIB_NAME = 'libdeepbinner_dtw.so'
 _lib = None
+
+
+def _signatures():
+    c_int, c_i64, c_double, c_void_p = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
+    i16, i32, i64, f64 = (ndpointer(t, flags='C_CONTIGUOUS') for t in
+                          (ctypes.c_int16, ctypes.c_int32, ctypes.c_int64, ctypes.c_double))
+    return {
+        'dtw_version': (ctypes.c_char_p, []),
+        'dtw_status_string': (ctypes.c_char_p, [c_int]),
+        'dtw_last_error': (ctypes.c_char_p, []),
+        # exactly the reference's binding (dtw_semi_global.py:33-41)
+        'semi_global_dtw': (c_double, [f64, f64, c_int, c_int, i32, i32, i32]),
+        'dtw_semi_global_batch': (c_int, [f64, i64, f64, i64, c_i64, f64, i32, i32, c_void_p]),
+        'dtw_rescaled_batch': (c_int, [f64, i64, f64, i64, c_i64, f64, i32, f64, c_void_p,
+                                       c_void_p, c_void_p]),
+        'dtw_locate_batch': (c_int, [i16, i64, f64, c_i64, f64, i64, c_i64, i64, c_i64, i64, c_i64,
+                                     c_double, f64, i32, f64, i32]),
+        'dtw_last_kernel_time': (c_int, [ctypes.POINTER(c_double), ctypes.POINTER(c_i64)]),
+    }
+
+
+# The ABI, once: {name: (restype, argtypes)}.  tests/test_dtw.py holds its names to the header.
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = list(SIGNATURES)
 
 
 def library_path():
@@ -49,34 +72,8 @@ def load_library():
     if not os.path.isfile(path):
         raise RuntimeError('{} is not built (run `make -C deepbinner_amd/csrc`): the DTW has no '
                            'CPU fallback'.format(path))
-    lib = ctypes.CDLL(path)
-    f64 = ndpointer(ctypes.c_double, flags='C_CONTIGUOUS')
-    i64 = ndpointer(ctypes.c_int64, flags='C_CONTIGUOUS')
-    i32 = ndpointer(ctypes.c_int32, flags='C_CONTIGUOUS')
-    for name in ('dtw_version', 'dtw_last_error'):
-        getattr(lib, name).restype = ctypes.c_char_p
-        getattr(lib, name).argtypes = []
-    lib.dtw_status_string.restype = ctypes.c_char_p
-    lib.dtw_status_string.argtypes = [ctypes.c_int]
-    # exactly the reference's binding (dtw_semi_global.py:33-41)
-    lib.semi_global_dtw.restype = ctypes.c_double
-    lib.semi_global_dtw.argtypes = [f64, f64, ctypes.c_int, ctypes.c_int, i32, i32, i32]
-    lib.dtw_semi_global_batch.restype = ctypes.c_int
-    lib.dtw_semi_global_batch.argtypes = [f64, i64, f64, i64, ctypes.c_int64, f64, i32, i32,
-                                          ctypes.c_void_p]
-    lib.dtw_rescaled_batch.restype = ctypes.c_int
-    lib.dtw_rescaled_batch.argtypes = [f64, i64, f64, i64, ctypes.c_int64, f64, i32, f64,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.dtw_locate_batch.restype = ctypes.c_int
-    lib.dtw_locate_batch.argtypes = [ndpointer(ctypes.c_int16, flags='C_CONTIGUOUS'), i64, f64,
-                                     ctypes.c_int64, f64, i64, ctypes.c_int64, i64,
-                                     ctypes.c_int64, i64, ctypes.c_int64, ctypes.c_double, f64,
-                                     i32, f64, i32]
-    lib.dtw_last_kernel_time.restype = ctypes.c_int
-    lib.dtw_last_kernel_time.argtypes = [ctypes.POINTER(ctypes.c_double),
-                                         ctypes.POINTER(ctypes.c_int64)]
-    _lib = lib
-    return lib
+    _lib = _cabi.bind(path, SIGNATURES)
+    return _lib
 
 
 def _failed(lib, what, status=None):

@@ -14,6 +14,8 @@ import weakref
 
 import numpy as np
 
+from . import _cabi
+
 _LIB_NAME = 'libdeepbinner_fast5.so'
 _lib = None
 
@@ -21,16 +23,6 @@ _lib = None
  F5_ERR_FILTER, F5_ERR_EXISTS) = range(8)
 F5_READ_ID_MAX = 64
 LAYOUT_NONE, LAYOUT_SINGLE_OLD, LAYOUT_SINGLE_NEW, LAYOUT_MULTI = range(4)
-
-EXPORTED_SYMBOLS = [
-    'f5_version', 'f5_status_string', 'f5_usable_cpus', 'f5_open', 'f5_close', 'f5_layout', 'f5_read_info',
-    'f5_read_signal', 'f5_load_batch', 'f5_load_reads', 'f5_batch_size', 'f5_batch_samples', 'f5_batch_offsets', 'f5_batch_status',
-    'f5_batch_read_ids', 'f5_batch_free', 'f5_stream_open', 'f5_stream_next', 'f5_stream_close',
-    'f5_set_sample_allocator', 'f5_release_idle_buffers', 'f5_stream_open_raw', 'f5_batch_comp',
-    'f5_batch_comp_bytes', 'f5_batch_streams', 'f5_batch_n_streams', 'f5_write_single_reads',
-    'f5_single_read_image', 'f5_load_batch_raw', 'f5_vbz_decode', 'f5_stream_open_raw_ex',
-    'f5_load_batch_raw_ex',
-]
 
 
 class Fast5NativeError(OSError):
@@ -47,18 +39,10 @@ def available():
     return os.path.isfile(library_path())
 
 
-def load_library():
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
-    if not os.path.isfile(path):
-        raise Fast5NativeError('{} not found - build it with `make -C deepbinner_amd/csrc` '
-                               '(python -c "import __graft_entry__ as g; g.build()")'.format(path))
-    lib = ctypes.cdll.LoadLibrary(path)
+def _signatures():
     c_int, c_i64, c_void_p, c_char_p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_char_p
     P = ctypes.POINTER
-    sigs = {
+    return {
         'f5_version': (c_char_p, []),
         'f5_status_string': (c_char_p, [c_int]),
         'f5_usable_cpus': (c_int, []),
@@ -96,12 +80,23 @@ def load_library():
         'f5_vbz_decode': (c_int, [c_void_p, c_i64, P(ctypes.c_uint32), c_int, c_i64, c_void_p,
                                   P(c_i64)]),
     }
-    for name, (restype, argtypes) in sigs.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = lib
-    return lib
+
+
+# The ABI, once: {name: (restype, argtypes)}; tests/test_fast5_native.py holds it to the header.
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = list(SIGNATURES)
+
+
+def load_library():
+    global _lib
+    if _lib is not None:
+        return _lib
+    path = library_path()
+    if not os.path.isfile(path):
+        raise Fast5NativeError('{} not found - build it with `make -C deepbinner_amd/csrc` '
+                               '(python -c "import __graft_entry__ as g; g.build()")'.format(path))
+    _lib = _cabi.bind(path, SIGNATURES)
+    return _lib
 
 
 def usable_cpus():
@@ -113,8 +108,16 @@ def status_string(status):
     return load_library().f5_status_string(int(status)).decode()
 
 
-class File:
+def _check(status, what=None):
+    if status != F5_OK:
+        text = status_string(status)
+        raise Fast5NativeError(text if what is None else '{}: {}'.format(what, text))
+
+
+class File(_cabi.Owner, _cabi.Scoped, _cabi.Finalised):
     """One open fast5 file: ``layout``, ``n_reads``, ``read_info(i)``, ``read_signal(i, ...)``."""
+
+    _release = 'f5_close'
 
     def __init__(self, path):
         self._lib = load_library()
@@ -127,23 +130,6 @@ class File:
         self._lib.f5_layout(self._handle, ctypes.byref(layout), ctypes.byref(n))
         self.layout, self.n_reads = layout.value, n.value
 
-    def close(self):
-        if self._handle:
-            self._lib.f5_close(self._handle)
-            self._handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def read_info(self, index):
         """-> (read_id str, n_samples); KeyError when the read lacks read_id / Signal."""
         rid = (ctypes.c_char * F5_READ_ID_MAX)()
@@ -151,8 +137,7 @@ class File:
         status = self._lib.f5_read_info(self._handle, int(index), rid, ctypes.byref(n))
         if status == F5_ERR_NO_READ:
             raise KeyError('read {} (read_id / Signal)'.format(index))
-        if status != F5_OK:
-            raise Fast5NativeError(status_string(status))
+        _check(status)
         try:
             return rid.value.decode(), n.value
         except UnicodeDecodeError:
@@ -165,8 +150,7 @@ class File:
         status = self._lib.f5_read_signal(self._handle, int(index), int(first), int(count), out)
         if status == F5_ERR_NO_READ:
             raise KeyError('sample range {}+{} of read {}'.format(first, count, index))
-        if status != F5_OK:
-            raise Fast5NativeError(status_string(status))
+        _check(status)
         return out
 
 
@@ -313,8 +297,7 @@ def load_batch_raw(fast5_files, threads=0, host_inflate_above=0, vbz_zstd='host'
     handle = ctypes.c_void_p()
     status = lib.f5_load_batch_raw_ex(paths, n, int(threads), int(host_inflate_above),
                                       _raw_flags(vbz_zstd, shuffle), ctypes.byref(handle))
-    if status != F5_OK:
-        raise Fast5NativeError(status_string(status))
+    _check(status)
     return _unpack_raw_batch(lib, handle)
 
 
@@ -329,8 +312,7 @@ def load_batch(fast5_files, keep=None, threads=0):
     paths = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(p)) for p in fast5_files])
     handle = ctypes.c_void_p()
     status = lib.f5_load_batch(paths, n, int(keep or 0), int(threads), ctypes.byref(handle))
-    if status != F5_OK:
-        raise Fast5NativeError(status_string(status))
+    _check(status)
     return _unpack_batch(lib, handle, n)
 
 
@@ -342,8 +324,7 @@ def load_reads(fast5_file, first=0, count=None, keep=None, threads=0):
     status = lib.f5_load_reads(os.fsencode(str(fast5_file)), int(first),
                                -1 if count is None else int(count), int(keep or 0),
                                int(threads), ctypes.byref(handle))
-    if status != F5_OK:
-        raise Fast5NativeError('{}: {}'.format(fast5_file, status_string(status)))
+    _check(status, fast5_file)
     return _unpack_batch(lib, handle, int(lib.f5_batch_size(handle)))
 
 
@@ -360,8 +341,7 @@ def stream_reads(fast5_files, keep=None, threads=0, depth=0):
     stream = ctypes.c_void_p()
     status = lib.f5_stream_open(paths, n, int(keep or 0), int(threads), int(depth),
                                 ctypes.byref(stream))
-    if status != F5_OK:
-        raise Fast5NativeError(status_string(status))
+    _check(status)
     try:
         index, container_status = ctypes.c_int64(0), ctypes.c_int(0)
         handle = ctypes.c_void_p()
@@ -396,8 +376,7 @@ def vbz_decode(chunk, cd, max_samples):
                                len(cd), int(max_samples), out.ctypes.data, ctypes.byref(n))
     if status == F5_ERR_FILTER:
         return None
-    if status != F5_OK:
-        raise Fast5NativeError(status_string(status))
+    _check(status)
     return out[:n.value].copy()
 
 
@@ -418,8 +397,7 @@ def stream_raw(fast5_files, threads=0, depth=0, host_inflate_above=0, vbz_zstd='
     flags = _raw_flags(vbz_zstd, shuffle)
     status = lib.f5_stream_open_raw_ex(paths, n, int(threads), int(depth), int(host_inflate_above),
                                        flags, ctypes.byref(stream))
-    if status != F5_OK:
-        raise Fast5NativeError(status_string(status))
+    _check(status)
     try:
         index, container_status = ctypes.c_int64(0), ctypes.c_int(0)
         handle = ctypes.c_void_p()
@@ -449,8 +427,7 @@ def write_single_reads(container, read_indices, out_paths, threads=0):
     written = ctypes.c_int64(0)
     rc = lib.f5_write_single_reads(os.fsencode(container), n, indices, paths, int(threads), status,
                                    ctypes.byref(written))
-    if rc != F5_OK:
-        raise Fast5NativeError('{}: {}'.format(container, status_string(rc)))
+    _check(rc, container)
     return np.frombuffer(status, dtype=np.int32, count=n).copy(), written.value
 
 
@@ -460,13 +437,11 @@ def single_read_image(container, read_index):
     size = ctypes.c_int64(0)
     rc = lib.f5_single_read_image(os.fsencode(container), int(read_index), None, 0,
                                   ctypes.byref(size))
-    if rc != F5_OK:
-        raise Fast5NativeError('{}: {}'.format(container, status_string(rc)))
+    _check(rc, container)
     buf = ctypes.create_string_buffer(size.value)
     rc = lib.f5_single_read_image(os.fsencode(container), int(read_index), buf, size.value,
                                   ctypes.byref(size))
-    if rc != F5_OK:
-        raise Fast5NativeError('{}: {}'.format(container, status_string(rc)))
+    _check(rc, container)
     return buf.raw[:size.value]
 
 
@@ -476,8 +451,7 @@ def set_sample_allocator(alloc_address=None, release_address=None, user=None):
     use_pinned_loader_buffers()`` passes the pinned-host-memory pair of libdeepbinner_hip.so - or
     nothing for malloc."""
     status = load_library().f5_set_sample_allocator(alloc_address, release_address, user)
-    if status != F5_OK:
-        raise Fast5NativeError(status_string(status))
+    _check(status)
 
 
 def release_idle_buffers():

@@ -236,7 +236,7 @@ def test_parse_follows_the_environment(tmp_path, monkeypatch):
         calls.append(len(data))
         return model(data, input_size)
 
-    monkeypatch.setattr(hip_backend, 'parse_training_text', parser)
+    monkeypatch.setattr(hip_backend._training_file, 'parse_training_text', parser)
     monkeypatch.delenv('DEEPBINNER_TEXT_PARSE', raising=False)
     hip_backend.read_training_data(str(path))
     monkeypatch.setenv('DEEPBINNER_TEXT_PARSE', 'host')
@@ -261,7 +261,7 @@ def test_fit_has_the_switch_and_passes_it_on(tmp_path, monkeypatch):
     with pytest.raises(SystemExit):
         cli.build_parser().parse_args(argv + ['--parse', 'cpu'])
     seen = []
-    monkeypatch.setattr(hip_backend, 'parse_training_text',
+    monkeypatch.setattr(hip_backend._training_file, 'parse_training_text',
                         lambda data, n: seen.append(n) or model(data, n))
     path = str(write(tmp_path / 'two.txt', [b'1\t1,2', b'2\t3,4']))
     assert fit.load_data(path, parse='gpu')[1].tolist() == [1, 2] and seen == [2]
@@ -309,7 +309,7 @@ def test_classify_prints_the_same_on_both_routes(oracle_backend, gold, tmp_path,
     args = argparse.Namespace(verbose=True, batch_size=2, scan_size=6144, score_diff=0.5,
                               require_either=False, require_start=False, require_both=False)
     parsed = []
-    monkeypatch.setattr(hip_backend, 'parse_training_text',
+    monkeypatch.setattr(hip_backend._training_file, 'parse_training_text',
                         lambda data, n: parsed.append(n) or model(data, n))
     printed = {}
     for route in ('host', 'gpu'):
