@@ -17,6 +17,12 @@
 // or the window, a frame that produces other than its content size.  A bitstream read that
 // reaches beyond the stream's first bit is refused where it happens (libzstd 1.4.8 reads on and
 // refuses, or in a few cases accepts, at the end).
+// Refused here and taken by libzstd 1.4.8's one-shot call, all by design (tests/test_zstd_written.py
+// holds a written frame for each): the checksum flag; a dictionary id field, also one that holds 0;
+// no content size; a skippable frame in front of the frame; a second frame behind it; a tree of
+// depth 12; reserved bits set in the sequences' modes byte; an offset beyond the window but inside
+// the output; sequence bits left over behind the last sequence; a last sequence whose fields reach
+// beyond the stream's first bit.
 //
 // THE SCHEDULE.  Serial work (headers, tree and table descriptions) is one lane's; the tables it
 // builds live in a Ctx (LDS on the device).  The Huffman table is filled by all lanes.  The

@@ -6,7 +6,6 @@ decoder's CPU model (which tests/test_zstd_model.py holds against libzstd), and 
 the streams' regions is seen to be untouched."""
 
 import contextlib
-import ctypes
 import io
 import os
 import struct
@@ -19,61 +18,13 @@ import pytest
 import vbz_fixtures as vf
 import zstd_cases as zc
 from conftest import MODEL_DIR
+from zstd_gpu import VBZ_ZSTD, run, samples_of
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(vf.zstd_lib() is None, reason='no libzstd.so.1 on this host')]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, '..', 'deepbinner_amd', 'libdeepbinner_hip.so')
-VBZ_ZSTD = 3
-SENTINEL = 0xA5
-
-
-def run(hip, items):
-    """items: [(bytes, out_bytes, mode)] as one dbh_inflate_dev call -> (per stream output bytes,
-    status, per stream workspace slots).  The outputs lie at even offsets of every residue modulo
-    16 with gaps between them; the output buffer is filled with a sentinel first and every byte
-    outside the streams' regions must still hold it."""
-    lib = hip.load_library()
-    streams, comp_at, out_at = [], 0, 0
-    for k, (data, out_bytes, mode) in enumerate(items):
-        out_at += 2 * (k % 8) + 2
-        streams.append((comp_at, len(data), out_at, out_bytes, mode, 0))
-        comp_at += len(data)
-        out_at += out_bytes
-    total_out = out_at + 64
-    comp = np.zeros(comp_at + 64, dtype=np.uint8)
-    comp[:comp_at] = np.frombuffer(b''.join(d for d, _, _ in items), dtype=np.uint8)
-    records = np.array(streams, dtype=hip.INFLATE_STREAM)
-    work_bytes = ctypes.c_size_t(0)
-    hip.check(lib.dbh_inflate_workspace_bytes(total_out, len(records), ctypes.byref(work_bytes)))
-    d_comp = hip.DeviceBuffer.from_array(comp)
-    d_rec = hip.DeviceBuffer.from_array(records)
-    d_out = hip.DeviceBuffer.from_array(np.full(total_out, SENTINEL, dtype=np.uint8))
-    d_work = hip.DeviceBuffer(work_bytes.value)
-    d_status = hip.DeviceBuffer.from_array(np.full(len(records), -7, dtype=np.int32))
-    try:
-        hip.check(lib.dbh_inflate_dev(d_comp.ptr, comp_at, d_rec.ptr, len(records), total_out, d_out.ptr,
-                                      d_work.ptr, d_status.ptr, 0, None), 'dbh_inflate_dev')
-        hip.synchronize()
-        raw = d_out.download(total_out, np.uint8)
-        status = d_status.download(len(records), np.int32)
-        work = d_work.download(4 * total_out, np.uint8)
-    finally:
-        for b in (d_comp, d_rec, d_out, d_work, d_status):
-            b.free()
-    outside = np.ones(total_out, dtype=bool)
-    for r in records:
-        outside[r['out_offset']:r['out_offset'] + r['out_bytes']] = False
-    assert (raw[outside] == SENTINEL).all(), 'a byte outside the streams\' regions was changed'
-    outs = [raw[r['out_offset']:r['out_offset'] + r['out_bytes']] for r in records]
-    slots = [work[4 * r['out_offset']:4 * (r['out_offset'] + r['out_bytes'])] for r in records]
-    return outs, status, slots
-
-
-def samples_of(content, n):
-    from deepbinner_amd import fast5_native
-    return fast5_native.vbz_decode(struct.pack('<I', 2 * n) + content, (0, 2, 1, 0), n)
 
 
 def signal_frames():
