@@ -2,7 +2,7 @@
 // version 0) ON THE GPU: streams of mode DBH_INFLATE_VBZ of dbh_inflate_dev (C ABI: the
 // "compressed input" section of include/deepbinner_hip.h), launched in the same call as the
 // inflate kernels, behind them on the same queue.  The loader's threads have undone the zstd stage
-// (fast5_reader.cpp: f5_stream_open_raw, f5_load_batch_raw); a stream holds
+// (f5_stream_open_raw, f5_load_batch_raw: vbz_host_stage in fast5_batch.h); a stream holds
 //   u32 LE original_size | ceil(n/4) control bytes | data bytes        (n = original_size / 2)
 // control byte j holds the 2-bit codes of values 4j..4j+3, low bits first; value k takes
 // code + 1 little-endian bytes; u -> (u >> 1) ^ -(u & 1) -> running sum, truncated to int16.
@@ -14,7 +14,7 @@
 //     loads go out together) and sums their deltas;
 //   - a second wave prefix sum of the lane sums, on top of the carry of the steps before, gives
 //     every sample.
-// Self-checks as the host's (fast5_reader.cpp, vbz_unpack): an odd original_size, control bytes
+// Self-checks as the host's (fast5_codecs.h, vbz_unpack): an odd original_size, control bytes
 // beyond the stream, data that would run past its end or that end before it: status != 0 and
 // the stream's output all zeros; its neighbours are not touched.  Reads stay inside the stream's
 // bytes plus the 3 bytes a 4-byte load of its last value may take beyond them (the compressed

@@ -45,7 +45,7 @@ class Hdf5FormatError(OSError):
 
 
 # ---- VBZ (ONT's HDF5 filter 32020), version 0 - the layout and self-checks of DESIGN.md, "VBZ",
-# the same accept / reject decisions as the native loader's (fast5_reader.cpp, vbz_decode) ------
+# the same accept / reject decisions as the native loader's (csrc/fast5_codecs.h, vbz_decode) ------
 _ZSTD = []
 
 

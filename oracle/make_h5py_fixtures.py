@@ -1,7 +1,7 @@
 #!/opt/conda/bin/python3.9
 """
 ORACLE tooling - fast5-shaped HDF5 files written by the real HDF5 library, to pin this
-repository's two HDF5 readers (deepbinner_amd/hdf5_lite.py and csrc/fast5_reader.cpp) against it.
+repository's two HDF5 readers (deepbinner_amd/hdf5_lite.py and csrc/fast5_hdf5.h, fast5_signal.h) against it.
 
 Run with the image's conda interpreter, the only one that has h5py (3.3.0 on libhdf5 1.10.6):
     /opt/conda/bin/python3.9 oracle/make_h5py_fixtures.py [out_dir [seed [committed|full]]]

@@ -1,4 +1,4 @@
-"""The native one-read fast5 writer (f5_write_single_reads in deepbinner_amd/csrc/fast5_reader.cpp):
+"""The native one-read fast5 writer (f5_write_single_reads; deepbinner_amd/csrc/fast5_write.h):
 what `deepbinner realtime` files the reads of multi-read containers with.  Its oracle is the
 Python writer (deepbinner_amd/hdf5_write.py), which tests/test_hdf5_write.py pins to the real HDF5
 library and to the reference's own loader: same bytes for the same read, on the real MinKNOW

@@ -2,7 +2,7 @@
 A reference for the streamvbyte + zigzag + delta stage of VBZ ("VBZ") and the streams
 the GPU decoder (deepbinner_amd/csrc/dbh_vbz.hip) is held to it on.  No GPU, no ctypes.
 
-``decode`` / ``expected`` restate fast5_reader.cpp's ``vbz_unpack`` with the header rules the
+``decode`` / ``expected`` restate fast5_codecs.h's ``vbz_unpack`` with the header rules the
 kernel states and the cut / zero-extension contract of include/deepbinner_hip.h;
 ``decode_plain`` is the same thing one value at a time, in plain Python integers, and the CPU
 tests hold the two (and both host decoders) to each other.

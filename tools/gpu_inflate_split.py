@@ -83,7 +83,7 @@ def main():
     # dispatcher), and the rest of the process - the loader's team and the HIP runtime's own threads
     # (tools/loader_cost.py has the loader's share alone)
     # ... and by thread name, sampled from /proc while the passes run (a thread's last sample stands
-    # for it once it is gone): f5-stream = the loader's team (fast5_reader.cpp names it)
+    # for it once it is gone): f5-stream = the loader's team (fast5_stream.h names it)
     by_name, seen, stop_sampling = {}, {}, threading.Event()
     ticks = os.sysconf('SC_CLK_TCK')
 
