@@ -26,6 +26,7 @@
 #include "dbh_host_layout.h"
 #include "dbh_kernels.h"
 #include "dbh_layout.h"
+#include "dbh_locate.h"
 #include "dbh_owned.h"
 #include "dbh_pack.h"
 #include "dbh_scan.h"
@@ -250,20 +251,22 @@ int window_probs_dev(dbh_model* m, const int16_t* samples_dev, const int64_t* of
     float* wprobs = (float*)workspace_dev;
     if (m->kind == DBH_MODEL_KIND_GENERAL) {
         DBH_HIP(dbh_gen::forward(m->gen, nullptr, samples_dev, offsets_dev, steps, side, windows, wprobs,
-                                 (char*)workspace_dev + general_act_offset(m, windows), stream));
+                                 nullptr, (char*)workspace_dev + general_act_offset(m, windows), stream));
         return DBH_OK;
     }
     const FusedInput in{samples_dev, offsets_dev, steps, side, score_diff, nullptr, hints, tail};
     return launch_forward(m, nullptr, windows, wprobs, -1, nullptr, stream, in);
 }
 
-// dbh_predict(_dev) on a general model: activations in a per-stream buffer of the model
+// dbh_predict(_dev) and dbh_evidence_dev on a general model: activations in a per-stream buffer of
+// the model (evidence_dev null: the probabilities alone)
 int general_predict(dbh_model* m, const float* x_dev, int64_t n, float* probs_dev,
-                    hipStream_t stream) {
+                    hipStream_t stream, float* evidence_dev = nullptr) {
     if (n == 0) return DBH_OK;
     DeviceBlock& act = m->gen_scratch[stream];
     DBH_HIP(act.reserve(dbh_gen::activation_bytes(m->gen, n)));
-    DBH_HIP(dbh_gen::forward(m->gen, x_dev, nullptr, nullptr, 1, 0, n, probs_dev, act.get(), stream));
+    DBH_HIP(dbh_gen::forward(m->gen, x_dev, nullptr, nullptr, 1, 0, n, probs_dev, evidence_dev,
+                             act.get(), stream));
     return DBH_OK;
 }
 
@@ -1304,6 +1307,165 @@ int dbh_scan_i16(dbh_model* m, const int16_t* samples_host, const int64_t* offse
     for (int32_t v : interior) inside += v;
     *n_events = found;
     *n_interior = inside;
+    return DBH_OK;
+}
+
+// ---- locate: where in the signal a call comes from (dbh_locate.hip) ------------------------------
+}  // extern "C"
+
+namespace {
+// the arguments dbh_locate_dev and dbh_locate_host share: a geometry the general path takes, the
+// cells that geometry has, steps whose flat cell index fits an int
+bool locate_shape_ok(int64_t n_reads, int steps, int cells, int n_classes, int input_size, int side) {
+    if (n_reads < 0 || steps < 1 || !dbh_gen::geometry_ok(input_size, n_classes) ||
+        (side != DBH_SIDE_START && side != DBH_SIDE_END))
+        return false;
+    int len[8];
+    dbh_net::stage_lengths(input_size, len);
+    return cells == len[7] && (int64_t)steps * cells <= (int64_t)1 << 24;
+}
+
+// reads per group of dbh_locate_i16: the windows of a group fit one chunk of the layer chain, so
+// that evidence plus activations stay inside the general path's budget.  DEEPBINNER_LOCATE_GROUP=n:
+// at most n reads (tests: groups of a few reads out of a few dozen)
+int64_t locate_group_reads(const dbh_model* m, int steps) {
+    int64_t reads = std::max<int64_t>(1, m->gen.chunk / steps);
+    if (const char* cap = std::getenv("DEEPBINNER_LOCATE_GROUP")) {
+        const long long c = std::atoll(cap);
+        if (c > 0 && c < reads) reads = c;
+    }
+    return reads;
+}
+
+// the device workspace of one group of `reads` reads, laid out once for sizing and for use
+struct LocateGroup {
+    float *wprobs = nullptr, *evidence = nullptr;
+    char* act = nullptr;
+    void lay_out(dbh_host::Carve& c, const dbh_model* m, int64_t reads, int steps) {
+        const size_t windows = (size_t)reads * steps;
+        wprobs = c.take<float>(windows * m->n_classes);
+        evidence = c.take<float>(windows * m->gen.len[7] * m->n_classes);
+        act = c.take<char>(dbh_gen::activation_bytes(m->gen, (int64_t)windows));
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int dbh_evidence_floats(const dbh_model* m, int64_t* per_window) {
+    if (!m || !per_window) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_GENERAL) return DBH_ERR_UNSUPPORTED;
+    *per_window = (int64_t)m->gen.len[7] * m->n_classes;
+    return DBH_OK;
+}
+
+int dbh_evidence_dev(dbh_model* m, const float* x_dev, int64_t n_windows, float* probs_dev,
+                     float* evidence_dev, dbh_stream stream) {
+    if (!m || n_windows < 0 || (n_windows > 0 && (!x_dev || !probs_dev || !evidence_dev)))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_GENERAL) return DBH_ERR_UNSUPPORTED;
+    return general_predict(m, x_dev, n_windows, probs_dev, (hipStream_t)stream, evidence_dev);
+}
+
+int dbh_locate_dev(const float* evidence_dev, const int32_t* calls_dev, const int64_t* offsets_dev,
+                   int64_t n_reads, int steps, int cells, int n_classes, int input_size, int side,
+                   dbh_location* locations_dev, dbh_stream stream) {
+    if (!locate_shape_ok(n_reads, steps, cells, n_classes, input_size, side))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!evidence_dev || !calls_dev || !offsets_dev || !locations_dev) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(dbh_locate::locate(evidence_dev, calls_dev, offsets_dev, n_reads, steps, cells, n_classes,
+                               input_size, side, locations_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_locate_host(const float* evidence_host, const int32_t* calls_host,
+                    const int64_t* offsets_host, int64_t n_reads, int steps, int cells,
+                    int n_classes, int input_size, int side, dbh_location* locations_host) {
+    if (!locate_shape_ok(n_reads, steps, cells, n_classes, input_size, side))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!evidence_host || !calls_host || !offsets_host || !locations_host)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (offsets_host[i + 1] < offsets_host[i]) return DBH_ERR_INVALID_ARGUMENT;
+    dbh_locate::locate_host(evidence_host, calls_host, offsets_host, n_reads, steps, cells, n_classes,
+                            input_size, side, locations_host);
+    return DBH_OK;
+}
+
+int dbh_locate_workspace_bytes(const dbh_model* m, int64_t n_reads, int scan_size, size_t* bytes) {
+    if (!m || !bytes || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_GENERAL) return DBH_ERR_UNSUPPORTED;
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
+    if (steps <= 0) return DBH_ERR_INVALID_ARGUMENT;
+    dbh_host::Carve sizing(nullptr);
+    LocateGroup().lay_out(sizing, m, std::min(n_reads, locate_group_reads(m, steps)), steps);
+    *bytes = sizing.used;
+    return DBH_OK;
+}
+
+int dbh_locate_i16(dbh_model* m, const int16_t* samples_host, const int64_t* offsets_host,
+                   int64_t n_reads, int side, int scan_size, double score_diff, float* probs_host,
+                   int32_t* calls_host, dbh_location* locations_host) {
+    if (!m || n_reads < 0 || (side != DBH_SIDE_START && side != DBH_SIDE_END))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_GENERAL) return DBH_ERR_UNSUPPORTED;
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
+    if (steps <= 0 || !(score_diff == score_diff)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!offsets_host || !probs_host || !calls_host || !locations_host)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (offsets_host[i + 1] < offsets_host[i]) return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t total_samples = offsets_host[n_reads] - offsets_host[0];
+    if (total_samples > 0 && !samples_host) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(m->device));      // (see dbh_classify_i16)
+    const int C = m->n_classes, cells = m->gen.len[7];
+    const int64_t group = std::min(n_reads, locate_group_reads(m, steps));
+    // one block for the call, freed on return: the reads, the results of every read, then one
+    // group's workspace.  The groups follow each other on one stream, which is what lets them share
+    // that workspace; nothing is waited for until the results are copied back.
+    DeviceBlock block;
+    int16_t* d_samples = nullptr;
+    int64_t* d_offsets = nullptr;
+    float* d_probs = nullptr;
+    int32_t* d_calls = nullptr;
+    dbh_location* d_locations = nullptr;
+    LocateGroup g;
+    DBH_HIP(block.carve([&](dbh_host::Carve& c) {
+        d_samples = c.take<int16_t>((size_t)std::max<int64_t>(total_samples, 1));
+        d_offsets = c.take<int64_t>((size_t)n_reads + 1);
+        d_probs = c.take<float>((size_t)n_reads * C);
+        d_calls = c.take<int32_t>((size_t)n_reads);
+        d_locations = c.take<dbh_location>((size_t)n_reads);
+        g.lay_out(c, m, group, steps);
+    }));
+    std::vector<int64_t> rel((size_t)n_reads + 1);
+    for (int64_t i = 0; i <= n_reads; ++i) rel[(size_t)i] = offsets_host[i] - offsets_host[0];
+    if (total_samples > 0)
+        DBH_HIP(hipMemcpyAsync(d_samples, samples_host + offsets_host[0],
+                               (size_t)total_samples * sizeof(int16_t), hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(d_offsets, rel.data(), rel.size() * sizeof(int64_t),
+                           hipMemcpyHostToDevice, 0));
+    for (int64_t r0 = 0; r0 < n_reads; r0 += group) {
+        const int64_t cnt = std::min(group, n_reads - r0);
+        // slice + forward with evidence, merge and call, then the rule: a read's results come from
+        // its own windows alone, so the grouping does not show in them
+        DBH_HIP(dbh_gen::forward(m->gen, nullptr, d_samples, d_offsets + r0, steps, side, cnt * steps,
+                                 g.wprobs, g.evidence, g.act, 0));
+        DBH_HIP(dbh_gen::merge(g.wprobs, cnt, steps, C, score_diff, d_probs + r0 * C, d_calls + r0,
+                               0));
+        DBH_HIP(dbh_locate::locate(g.evidence, d_calls + r0, d_offsets + r0, cnt, steps, cells, C,
+                                   m->input_size, side, d_locations + r0, 0));
+    }
+    DBH_HIP(hipMemcpyAsync(probs_host, d_probs, (size_t)n_reads * C * sizeof(float),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipMemcpyAsync(calls_host, d_calls, (size_t)n_reads * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipMemcpyAsync(locations_host, d_locations, (size_t)n_reads * sizeof(dbh_location),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipStreamSynchronize(0));
     return DBH_OK;
 }
 

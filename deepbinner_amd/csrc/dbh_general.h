@@ -42,8 +42,10 @@ size_t activation_bytes(const Net& net, int64_t n_windows);
 // Softmax probabilities [n_windows][C] of windows given either as fp32 [n_windows][L] (x != null:
 // dbh_predict) or sliced from int16 reads (x == null: window w = read w / steps, scan step
 // w % steps, normalised and zero-padded as classify.py:330-357 does).  act: activation_bytes().
+// evidence (null: not wanted): [n_windows][len[7]][C], the post-ReLU conv1d_20 output per position
+// whose mean over the positions is the logit; the probabilities are the same bits with and without.
 hipError_t forward(const Net& net, const float* x, const int16_t* samples, const int64_t* offsets,
-                   int steps, int side, int64_t n_windows, float* probs, void* act,
+                   int steps, int side, int64_t n_windows, float* probs, float* evidence, void* act,
                    hipStream_t stream);
 
 // merge + make_sum_to_one + top-2 call for C <= 256 (the contract of dbh_merge_calls_dev)

@@ -225,12 +225,17 @@ __global__ __launch_bounds__(kThreads) void conv_kernel(ConvArgs a) {
 }
 
 // ---- head: BN7 -> conv1d_20 (1x1, 48 -> C) + ReLU -> global average -> softmax ----------------
+// EVIDENCE: the post-ReLU value of every position and class, whose mean is the logit, is stored as
+// well - ev [window][l7][C], coalesced over the class threads (include/deepbinner_hip.h, "locate").
+// The sum and the softmax are the same lines either way: the probabilities do not change by a bit.
+template <bool EVIDENCE>
 __global__ __launch_bounds__(kThreads) void head_kernel(const float* __restrict__ x, int l7,
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ bias,
                                                         const float* __restrict__ sc,
                                                         const float* __restrict__ sh, int C,
-                                                        long long w0, float* __restrict__ probs) {
+                                                        long long w0, float* __restrict__ probs,
+                                                        float* __restrict__ ev) {
     __shared__ float xs[kMaxL7 * 48];
     __shared__ float red[kThreads];
     const int tid = threadIdx.x;
@@ -249,6 +254,7 @@ __global__ __launch_bounds__(kThreads) void head_kernel(const float* __restrict_
             for (int ci = 0; ci < 48; ++ci) s = fmaf(xs[p * 48 + ci], w[ci * C + tid], s);
             s += bias[tid];
             sum += s > 0.f ? s : 0.f;
+            if (EVIDENCE) ev[((w0 + blockIdx.x) * l7 + p) * C + tid] = s > 0.f ? s : 0.f;
         }
         logit = sum / (float)l7;
     }
@@ -364,7 +370,7 @@ size_t activation_bytes(const Net& net, int64_t n_windows) {
 }
 
 hipError_t forward(const Net& net, const float* x, const int16_t* samples, const int64_t* offsets,
-                   int steps, int side, int64_t n_windows, float* probs, void* act,
+                   int steps, int side, int64_t n_windows, float* probs, float* evidence, void* act,
                    hipStream_t stream) {
     const int* len = net.len;
     for (int64_t w0 = 0; w0 < n_windows; w0 += net.chunk) {
@@ -407,10 +413,10 @@ hipError_t forward(const Net& net, const float* x, const int16_t* samples, const
         if (e == hipSuccess) e = conv<18, kInPlain, true>(net, F2, F1, 48, 0, n, stream);
         // head: BN7 -> conv20 -> ReLU -> mean -> softmax
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(head_kernel, dim3((unsigned)n), dim3(kThreads), 0, stream, F1,
-                               len[7], net.d_params + net.w_off[19], net.d_params + net.b_off[19],
-                               net.d_params + net.sc_off[6], net.d_params + net.sh_off[6], net.C,
-                               (long long)w0, probs);
+            hipLaunchKernelGGL(evidence ? head_kernel<true> : head_kernel<false>, dim3((unsigned)n),
+                               dim3(kThreads), 0, stream, F1, len[7], net.d_params + net.w_off[19],
+                               net.d_params + net.b_off[19], net.d_params + net.sc_off[6],
+                               net.d_params + net.sh_off[6], net.C, (long long)w0, probs, evidence);
             e = hipGetLastError();
         }
         if (e != hipSuccess) return e;

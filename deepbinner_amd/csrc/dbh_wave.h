@@ -48,6 +48,22 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
+// the highest value over the wave's 64 lanes and the lowest index that holds it, in every lane: the
+// butterfly over (value, index) pairs.  The order is total - higher value, then lower index - so the
+// result does not depend on which lane held what; a NaN wins no comparison (hand none in as a pick).
+// All 64 lanes call it.
+__device__ __forceinline__ void wave_best(float* value, int* index) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(*value, o);
+        const int oi = __shfl_xor(*index, o);
+        if (ov > *value || (ov == *value && oi < *index)) {
+            *value = ov;
+            *index = oi;
+        }
+    }
+}
+
 // This thread's exclusive prefix of `count` within its workgroup of kWaves waves, all of whose
 // threads call it, and the workgroup's sum in *total.  wave_total: kWaves words of LDS, the
 // caller's; one barrier here, between their writes and their reads - a caller that comes again (a

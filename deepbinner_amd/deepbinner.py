@@ -9,7 +9,9 @@ are the reference's commands, and ``fit`` is its ``train`` (:246-269: the same o
 defaults, plus ``--seed``) on the resident trainer - under another name, because ``train`` and
 ``prep`` answer with a one-line refusal.  ``sweep`` is not the reference's: the calls of every scan
 size and score difference counted in one pass (sweep.py).  Nor is ``scan``: every window of a read
-through the network, and the places inside it where a barcode class leads (scan.py).
+through the network, and the places inside it where a barcode class leads (scan.py).  Nor is
+``locate``: where in the signal each side's call comes from, read out of the network's last layers
+(locate.py).
 """
 
 import argparse
@@ -227,8 +229,16 @@ COMMANDS = {
               (('--multi_read',), dict(action='store_true',
                                        help='Take the reads of multi-read fast5 files where '
                                             'they are (one-read files may be mixed in)')), _HELP]),
+    'locate': ('Report where in the signal each barcode call comes from',
+               [('Positional', [
+                   (('input',), dict(type=str,
+                                     help='One of the following: a single fast5 file or a directory '
+                                          'of fast5 files (will be searched recursively)'))])],
+               [(('--multi_read',), dict(action='store_true',
+                                         help='Take the reads of multi-read fast5 files where '
+                                              'they are (one-read files may be mixed in)')), _HELP]),
 }
-USES_MODELS = ('classify', 'realtime', 'scan')
+USES_MODELS = ('classify', 'realtime', 'scan', 'locate')
 
 
 def _add_groups(parser, groups):
@@ -263,7 +273,8 @@ def main(argv=None):
         sys.exit(1)
     if argv[0] in NOT_PROVIDED:
         sys.exit('Error: the {} command is not part of this build - it covers the classify, '
-                 'realtime, bin, balance, fit, refine, sweep and scan commands only'.format(argv[0]))
+                 'realtime, bin, balance, fit, refine, sweep, scan and locate commands only'
+                 .format(argv[0]))
     args = parser.parse_args(argv)
     if args.subparser_name in USES_MODELS:
         check_classify_and_realtime_arguments(args)
@@ -285,6 +296,8 @@ def main(argv=None):
         from .sweep import sweep as run
     elif args.subparser_name == 'scan':
         from .scan import scan as run
+    elif args.subparser_name == 'locate':
+        from .locate import locate as run
     else:
         return
     run(args)

@@ -16,7 +16,7 @@ There is deliberately NO CPU fallback: if the library or a GPU is missing the er
 
 This file is the public surface and only that: it imports and re-exports.  The code lies in the
 private submodules beside it, one per subsystem, each building on those before it: ``_abi``,
-``_device``, ``_sweep``, ``_scan``, ``_model``, ``_text``, ``_training_file``, ``_training``
+``_device``, ``_sweep``, ``_scan``, ``_locate``, ``_model``, ``_text``, ``_training_file``, ``_training``
 ("The binding as a package").  Code outside this package goes through this file.
 """
 
@@ -29,10 +29,13 @@ from ._sweep import (SWEEP_MODES, sweep_counts, sweep_pair, sweep_steps, sweep_t
                      sweep_windows)
 from ._scan import (SCAN_EVENT, scan_events, scan_packed, scan_window_count, scan_window_offsets,
                     scan_windows)
+from ._locate import (CELL_SAMPLES, LOCATION, evidence_floats, locate_packed, locate_rule,
+                      locate_rule_dev, locate_workspace_bytes)
 from ._model import (INFLATE_SHUFFLE_REFUSED, INFLATE_STORED, INFLATE_STORED_SHUFFLE,
                      INFLATE_STREAM, INFLATE_VBZ, INFLATE_ZLIB, INFLATE_ZLIB_SHUFFLE, HipModel,
                      ModelWeights, _TensorSpec, classify_pair, classify_pair_deflated,
-                     combine_calls_dev, forward_executed_mfmas, forward_kernel_info, inflate)
+                     combine_calls_dev, forward_executed_mfmas, forward_kernel_info, general_model,
+                     inflate)
 from ._text import (TEXT_COUNT, TEXT_FORM, TEXT_OK, TEXT_RANGE, DeviceSignals, ResidentText,
                     format_training_text, parse_training_text, parse_training_text_host,
                     random_signals, text_format_bound, text_stage_ms, write_training_data)

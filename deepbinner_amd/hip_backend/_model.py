@@ -7,9 +7,10 @@ import numpy as np
 
 from .._cabi import Finalised, Owner
 from ..model_format import ModelWeights
-from ._abi import (COMBINE_MODES, MODEL_AUTO, MODEL_GENERAL, HipBackendError, _handle, _packed,
-                   _ptr, _side, check, load_library)
+from ._abi import (COMBINE_MODES, KIND_GENERAL, MODEL_AUTO, MODEL_GENERAL, HipBackendError,
+                   _handle, _packed, _ptr, _side, check, load_library)
 from ._device import device_count, get_device, set_device
+from ._locate import evidence, locate_packed, locate_signals
 from ._scan import SCAN_EVENT, host_window_offsets
 from ._sweep import sweep_pair
 
@@ -266,6 +267,19 @@ class HipModel(Owner, Finalised):
         assert int((events['first'] >= skip_windows).sum()) == interior.value
         return (events, best, margin, window_offsets) if track else events
 
+    # -- locate (general-kind models: _locate.py) ------------------------------------------------
+    def evidence(self, windows):
+        """windows [N, L] -> (probs [N, C], the bits of ``predict``; evidence [N, cells, C])."""
+        return evidence(self, windows)
+
+    def locate_signals(self, signals, side, scan_size, score_diff):
+        """Whole reads -> (probs [N, C], calls [N], locations LOCATION [N])."""
+        return locate_signals(self, signals, side, scan_size, score_diff)
+
+    def locate_packed(self, samples, offsets, side, scan_size, score_diff):
+        """``locate_signals`` for whole reads already packed."""
+        return locate_packed(self, samples, offsets, side, scan_size, score_diff)
+
     # -- device-resident entry points (inputs/outputs are raw device pointers) -----------------
     def workspace_bytes(self, n_reads, scan_size):
         n = ctypes.c_size_t(0)
@@ -387,6 +401,17 @@ class HipModel(Owner, Finalised):
         shapes = {0: (512, 48), 1: (256, 48), 2: (128, 48), 3: (64, 48), 4: (32, 192),
                   5: (16, 48), 6: (8, 48), 7: (32,)}
         return out.reshape((x.shape[0],) + shapes[idx])
+
+
+def general_model(model):
+    """The model ``locate`` needs from the one ``classify.build_model`` made: general-kind, whatever
+    the geometry.  A persistent-kind model is closed and its weights loaded again on the general
+    path; a general-kind one comes back as it is."""
+    if model is None or model.kind == KIND_GENERAL:
+        return model
+    general = HipModel(model.weights, device=model.device, general=True)
+    model.close()
+    return general
 
 
 def forward_executed_mfmas(n_classes):

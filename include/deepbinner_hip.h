@@ -360,6 +360,84 @@ int dbh_scan_i16(dbh_model* model, const int16_t* samples_host, const int64_t* o
                  int32_t* best_host, double* margin_host, dbh_scan_event* events_host,
                  int64_t max_events, int64_t* n_events, int64_t* n_interior);
 
+/* ---- locate: where in the signal each barcode call comes from ---------------------------------- */
+/* The network ends in conv1d_20 (1x1) -> ReLU -> global average -> softmax
+ * (network_architecture.py:91-93), so a class's logit IS the mean, over the positions of stage 7, of
+ * that class's post-ReLU conv1d_20 output.  Each position is one cell of 2^7 = 128 samples.  That
+ * per-cell value is the class's EVIDENCE: a decomposition of the logit, not a heuristic.  It says
+ * where the NETWORK sees the barcode; nothing here has been checked against where the barcode is.
+ *
+ * L = the model's input size, h = L / 2, C its classes, cells = len7 = the positions of stage 7
+ * ((L/2)/2/2/2/2, halved rounding up, halved again: 8 at L = 1024), a read has n samples.
+ *   Windows.  call_batch's own, per side (classify.py:330-357): steps = scan_size / h.  Window s of
+ *       side start begins at read sample o = s h; window s of side end at o = n - s h - L, which may
+ *       be negative: the zero pad in front counts as window positions.
+ *   Evidence.  e[p][c] = max(0, bias[c] + sum_ci BN7(G)[p][ci] * w20[ci][c]) for p in [0, cells), in
+ *       the arithmetic and order of the general path's head; fp32 [window][cells][C], the windows
+ *       [read][step].  The mean of e[.][c] over p is class c's logit.
+ *   Cell.  Cell p of a window covers window positions [128 p, min(128 (p + 1), L)); in read samples
+ *       that range shifted by o and clipped to [0, n).  Positions behind 128 cells belong to no cell
+ *       (L = 160 has one cell: positions 128 .. 159 have none).
+ *   Rule, per read and side, for the side's call c after merge and score_diff (what
+ *       dbh_classify_i16 calls):
+ *       c == 0 (or no class of the model): no location - cls 0, every other integer -1, the floats 0.
+ *       The deciding window is the one with the largest max_p e[s][p][c], the lowest s among equals.
+ *           (Not the window of the highest probability: the probabilities of two overlapping windows
+ *           saturate, and rounding would decide.)
+ *       The peak cell is the lowest p that holds the maximum.
+ *       The span is the longest run of consecutive cells around the peak with e >= 0.5f * peak, an
+ *           fp32 comparison (the halving is exact).
+ *       share = the sum of e over the span / the sum over all cells of that window and class, both
+ *           sums fp64 in cell order, the quotient rounded to float once; 0 where the sum is 0.
+ *       All-zero evidence: window 0, peak cell 0, a span of every cell, share 0.
+ *       A NaN never wins a '>' (and equals nothing): a NaN cell is never the peak and ends a span.
+ *   Result.  dbh_location: samples are [first_sample, end_sample); where clipping empties the range,
+ *       end_sample = first_sample.  reserved is 0.
+ *
+ * A model for locate is general-kind (DBH_MODEL_GENERAL), whatever its geometry: the general path
+ * has stage G in memory.  dbh_evidence_floats, dbh_evidence_dev, dbh_locate_workspace_bytes and
+ * dbh_locate_i16 on a persistent-kind model return DBH_ERR_UNSUPPORTED.
+ * dbh_evidence_floats: cells * C, the evidence floats of one window.
+ * dbh_evidence_dev is dbh_predict_dev's twin: x_dev [n_windows][L] -> probs_dev [n_windows][C] and
+ * evidence_dev [n_windows][cells][C].  The probabilities are bit-identical to dbh_predict_dev's, and
+ * windows cross the chunks of the layer chain exactly as they do there.
+ * dbh_locate_dev applies the rule: evidence_dev [n_reads][steps][cells][C], calls_dev int32
+ * [n_reads], offsets_dev int64 [n_reads + 1] (the reads' sample offsets; only their differences are
+ * read) -> locations_dev [n_reads].  No allocation, no synchronisation.  dbh_locate_host takes the
+ * same arguments as host pointers and is the CPU model of the kernel: the same lines, bit for bit.
+ * dbh_locate_i16: host buffers, blocks - the whole route: slice, forward with evidence, merge and
+ * call (as dbh_classify_i16 on the same model), then the rule.  probs_host [n_reads][C], calls_host
+ * and locations_host [n_reads].  Reads go through in groups whose windows fit one chunk of the layer
+ * chain; a read's results come from its own windows alone and do not depend on the grouping.
+ * dbh_locate_workspace_bytes: the device bytes of one such group - per-window probabilities,
+ * evidence, activations - which the groups of a call share (the samples, the offsets and the
+ * results of every read come on top).
+ * Every entry checks its arguments before any device work and writes nothing on error: a null model
+ * or pointer, n_reads < 0, steps < 1, cells that are not the cells of input_size, a geometry outside
+ * dbh_model_create_ex's, a side that is neither DBH_SIDE_START nor DBH_SIDE_END, a scan_size that is
+ * no positive multiple of h, offsets that run backwards (host entries): DBH_ERR_INVALID_ARGUMENT.
+ * n_reads == 0 is DBH_OK. */
+typedef struct dbh_location {
+    int32_t cls, window, peak_cell, first_cell, last_cell;
+    float peak, share;
+    int32_t reserved;
+    int64_t first_sample, end_sample;
+} dbh_location;
+int dbh_evidence_floats(const dbh_model* model, int64_t* per_window);
+int dbh_evidence_dev(dbh_model* model, const float* x_dev, int64_t n_windows, float* probs_dev,
+                     float* evidence_dev, dbh_stream stream);
+int dbh_locate_dev(const float* evidence_dev, const int32_t* calls_dev, const int64_t* offsets_dev,
+                   int64_t n_reads, int steps, int cells, int n_classes, int input_size, int side,
+                   dbh_location* locations_dev, dbh_stream stream);
+int dbh_locate_host(const float* evidence_host, const int32_t* calls_host,
+                    const int64_t* offsets_host, int64_t n_reads, int steps, int cells,
+                    int n_classes, int input_size, int side, dbh_location* locations_host);
+int dbh_locate_workspace_bytes(const dbh_model* model, int64_t n_reads, int scan_size,
+                               size_t* bytes);
+int dbh_locate_i16(dbh_model* model, const int16_t* samples_host, const int64_t* offsets_host,
+                   int64_t n_reads, int side, int scan_size, double score_diff, float* probs_host,
+                   int32_t* calls_host, dbh_location* locations_host);
+
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's
  * inflate() over every chunk on the host.  Here the loader may hand over the chunks AS STORED
