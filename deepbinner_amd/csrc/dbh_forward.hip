@@ -1397,6 +1397,10 @@ __device__ __forceinline__ void stage_b_chain(float* lds, const float* __restric
                 w5[4] = ds_read_f2<4 * 512>(w5_addr);
                 w5[5] = ds_read_f2<5 * 512>(w5_addr);
             }
+            // (word 1, for the check in front of conv6: until this peek was here that check looked
+            // at the peek of word 0 above, which is complete a tile earlier - it never waited, and
+            // a wave could read conv6's weights before the other waves' pieces had landed)
+            if constexpr (SP == 5) pk_a = chain_peek(lds, 1);
         },
         [&](auto tag) {
             constexpr int SP = decltype(tag)::value;

@@ -5,8 +5,8 @@
 //
 // A kernel's instruction stream does not depend on which kernels share its unit, or on their
 // order: every __device__ function these kernels call is __forceinline__, and cut at its ELF symbol's
-// size dbh::dbh_forward_kernel is the same 15,360 instructions here, built alone, beside the
-// timeline build or beside any other kernel (dbh_timeline::dbh_forward_kernel: 16,056 wherever it
+// size dbh::dbh_forward_kernel is the same 15,365 instructions here, built alone, beside the
+// timeline build or beside any other kernel (dbh_timeline::dbh_forward_kernel: 16,061 wherever it
 // is built; DESIGN.md section 4, profiles/kernel_digest/).  After any rearrangement of the device
 // code, check with  python tools/code_object.py --same OLD.so NEW.so
 #include <hip/hip_runtime.h>

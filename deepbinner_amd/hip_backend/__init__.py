@@ -23,8 +23,9 @@ private submodules beside it, one per subsystem, each building on those before i
 from ._abi import (COMBINE_MODES, ERR_COMM, EXPORTED_SYMBOLS, KIND_GENERAL, KIND_PERSISTENT,
                    MODEL_AUTO, MODEL_GENERAL, SIDE_END, SIDE_START, SIGNATURES, HipBackendError,
                    NadamCoefficients, TrainerOptions, check, library_path, load_library, ndpointer)
-from ._device import (DeviceBuffer, Event, Stream, device_arrays, device_count, device_name,
-                      get_device, is_pinned, set_device, synchronize, use_pinned_loader_buffers)
+from ._device import (LDS_ARENA_WORDS, DeviceBuffer, Event, Stream, device_arrays, device_count,
+                      device_name, fill_lds, get_device, is_pinned, set_device, survey_lds,
+                      synchronize, use_pinned_loader_buffers)
 from ._sweep import (SWEEP_MODES, sweep_counts, sweep_pair, sweep_steps, sweep_tally,
                      sweep_windows)
 from ._scan import (SCAN_EVENT, scan_events, scan_packed, scan_window_count, scan_window_offsets,

@@ -160,6 +160,9 @@ def _signatures():
         'dbh_forward_phases_enable': (c_int, [ptr, c_int]),
         'dbh_forward_phases_read': (c_int, [ptr, P(c_double), P(c_i64)]),
         'dbh_forward_phases_count': (c_int, [P(c_int)]),
+        'dbh_lds_fill': (c_int, [c_int, ctypes.c_uint32, c_int, c_int, P(c_int), P(c_int)]),
+        'dbh_lds_survey': (c_int, [c_int, ctypes.c_uint32, c_int, c_int, i64, i64, P(c_int),
+                                   P(c_int)]),
         'dbh_gradients_max_windows': (c_int, [c_int, P(c_i64)]),
         'dbh_gradients_workspace_bytes': (c_int, [c_int, c_int, c_i64, P(c_size_t)]),
         'dbh_gradients': (c_int, [f32, c_i64, c_int, c_int, f32, i32, c_i64, c_float, c_u64,

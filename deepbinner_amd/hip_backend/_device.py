@@ -36,6 +36,33 @@ def synchronize():
     check(load_library().dbh_device_synchronize(), 'dbh_device_synchronize')
 
 
+LDS_CU_SLOTS = 1024                 # DBH_LDS_CU_SLOTS
+LDS_ARENA_WORDS = 160 * 1024 // 4
+
+
+def fill_lds(pattern, device=0, grid_multiple=0, hold_us=-1):
+    """Store the 32-bit ``pattern`` in every word of every CU's LDS (test support: what a kernel
+    launched next finds in the words it has not written yet).  Null stream, synchronised.  Returns
+    (distinct CUs a workgroup ran on, CUs of the device): the fill counts when the two are equal."""
+    seen, total = ctypes.c_int(0), ctypes.c_int(0)
+    check(load_library().dbh_lds_fill(device, pattern & 0xFFFFFFFF, grid_multiple, hold_us,
+                                      ctypes.byref(seen), ctypes.byref(total)), 'dbh_lds_fill')
+    return seen.value, total.value
+
+
+def survey_lds(pattern, device=0, grid_multiple=0, hold_us=-1):
+    """Count, storing nothing to LDS, the words of every CU's LDS that equal ``pattern``.  Returns
+    (matching, looked_at, CUs of the device): int64 arrays with one row per CU a workgroup ran on."""
+    matching, looked_at = (np.zeros(LDS_CU_SLOTS, np.int64) for _ in range(2))
+    seen, total = ctypes.c_int(0), ctypes.c_int(0)
+    check(load_library().dbh_lds_survey(device, pattern & 0xFFFFFFFF, grid_multiple, hold_us,
+                                        matching, looked_at, ctypes.byref(seen),
+                                        ctypes.byref(total)), 'dbh_lds_survey')
+    ran = looked_at > 0
+    assert int(ran.sum()) == seen.value
+    return matching[ran], looked_at[ran], total.value
+
+
 _PINNED_LOADER = False
 
 

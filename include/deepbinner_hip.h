@@ -1070,6 +1070,29 @@ int dbh_forward_phases_enable(dbh_model* model, int enable);
 int dbh_forward_phases_count(int* count);
 int dbh_forward_phases_read(dbh_model* model, double* mean_cycles_14, int64_t* groups);
 
+/* ---- LDS state (test support) --------------------------------------------------------------- */
+/* LDS is not cleared between workgroups: a kernel that reads a word of its __shared__ arena before
+ * it has written it computes with what the workgroup before it left on that CU.  These two put
+ * that state in a test's hands (csrc/dbh_lds_state.hip).
+ *
+ * dbh_lds_fill: one launch on `device`'s null stream of grid_multiple x (number of CUs) workgroups
+ * of 512 threads with all 160 KiB of LDS each (one workgroup per CU at a time); every word of the
+ * arena is stored as `pattern`, then the workgroup keeps its CU for hold_us microseconds (a counted
+ * wait on the constant-rate clock), so that the grid's later workgroups go to the CUs that had none.
+ * The device is synchronised before the call returns.  *cus_seen: distinct CUs a workgroup ran on
+ * (by XCC, shader engine and CU id); *cus_total (may be null): the device's CU count.  A fill has
+ * reached every CU when the two are equal.
+ * dbh_lds_survey: the same shape, but nothing is stored to LDS: the workgroups count the words of
+ * the arena that equal `pattern`.  matching[s], looked_at[s] (DBH_LDS_CU_SLOTS int64 each): words
+ * that matched and words read on the CU with id s, both 0 where no workgroup ran.
+ * grid_multiple 0 and hold_us < 0 ask for the defaults (4 and 50); grid_multiple > 64,
+ * hold_us > 10,000 or a null cus_seen / matching / looked_at: DBH_ERR_INVALID_ARGUMENT. */
+#define DBH_LDS_CU_SLOTS 1024
+int dbh_lds_fill(int device, uint32_t pattern, int grid_multiple, int hold_us, int* cus_seen,
+                 int* cus_total);
+int dbh_lds_survey(int device, uint32_t pattern, int grid_multiple, int hold_us, int64_t* matching,
+                   int64_t* looked_at, int* cus_seen, int* cus_total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ SUBMODULES = [importlib.import_module(hip_backend.__name__ + '.' + info.name)
 def test_facade_exports_the_names_of_the_one_file_module():
     with open(os.path.join(REPO, 'tests', 'golden', 'hip_backend_names.txt')) as f:
         names = f.read().split()
-    assert len(names) == 88
+    assert len(names) == 90          # (the 88 of the one-file module, fill_lds and survey_lds)
     missing = [name for name in names if not hasattr(hip_backend, name)]
     assert not missing, missing
     from deepbinner_amd.hip_backend import _TensorSpec       # what tests/conftest.py imports
