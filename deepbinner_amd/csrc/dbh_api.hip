@@ -27,6 +27,7 @@
 #include "dbh_kernels.h"
 #include "dbh_layout.h"
 #include "dbh_locate.h"
+#include "dbh_occlude.h"
 #include "dbh_owned.h"
 #include "dbh_pack.h"
 #include "dbh_scan.h"
@@ -1464,6 +1465,198 @@ int dbh_locate_i16(dbh_model* m, const int16_t* samples_host, const int64_t* off
     DBH_HIP(hipMemcpyAsync(calls_host, d_calls, (size_t)n_reads * sizeof(int32_t),
                            hipMemcpyDeviceToHost, 0));
     DBH_HIP(hipMemcpyAsync(locations_host, d_locations, (size_t)n_reads * sizeof(dbh_location),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipStreamSynchronize(0));
+    return DBH_OK;
+}
+
+// ---- occlude: blank the located span and call the read again (dbh_occlude.hip) -------------------
+}  // extern "C"
+
+namespace {
+// the arguments the plan and window entries share
+bool occlude_shape_ok(int64_t n_reads, int steps, int input_size, int side) {
+    return n_reads >= 0 && steps >= 1 && scan_input_size_ok(input_size) &&
+           (int64_t)steps * input_size <= (int64_t)1 << 30 &&
+           (side == DBH_SIDE_START || side == DBH_SIDE_END);
+}
+
+bool offsets_run_forwards(const int64_t* offsets, int64_t n_reads) {
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] < offsets[i]) return false;
+    return true;
+}
+
+// what a group of dbh_locate_occluded_i16 holds beside locate's: its windows as sliced, the three
+// variants' windows, their merged probabilities and calls, the plans.  The four passes go through
+// LocateGroup's workspace one after another.
+struct OccludeGroup {
+    float *x = nullptr, *variants[3] = {nullptr, nullptr, nullptr}, *vprobs = nullptr;
+    int32_t* vcalls = nullptr;
+    dbh_occlude_plan* plans = nullptr;
+    void lay_out(dbh_host::Carve& c, const dbh_model* m, int64_t reads, int steps) {
+        const size_t floats = (size_t)reads * steps * m->input_size;
+        x = c.take<float>(floats);
+        for (float*& v : variants) v = c.take<float>(floats);
+        vprobs = c.take<float>((size_t)3 * reads * m->n_classes);
+        vcalls = c.take<int32_t>((size_t)3 * reads);
+        plans = c.take<dbh_occlude_plan>((size_t)reads);
+    }
+};
+}  // namespace
+
+extern "C" {
+
+int dbh_occlude_plan_dev(const dbh_location* locations_dev, const int64_t* offsets_dev,
+                         int64_t n_reads, int steps, int input_size, int side,
+                         dbh_occlude_plan* plans_dev, dbh_occlusion* occlusions_dev,
+                         dbh_stream stream) {
+    if (!occlude_shape_ok(n_reads, steps, input_size, side)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!locations_dev || !offsets_dev || !plans_dev || !occlusions_dev)
+        return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(dbh_occlude::plan(locations_dev, offsets_dev, n_reads, steps, input_size, side,
+                              plans_dev, occlusions_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_occlude_plan_host(const dbh_location* locations_host, const int64_t* offsets_host,
+                          int64_t n_reads, int steps, int input_size, int side,
+                          dbh_occlude_plan* plans_host, dbh_occlusion* occlusions_host) {
+    if (!occlude_shape_ok(n_reads, steps, input_size, side)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!locations_host || !offsets_host || !plans_host || !occlusions_host ||
+        !offsets_run_forwards(offsets_host, n_reads))
+        return DBH_ERR_INVALID_ARGUMENT;
+    dbh_occlude::plan_host(locations_host, offsets_host, n_reads, steps, input_size, side,
+                           plans_host, occlusions_host);
+    return DBH_OK;
+}
+
+int dbh_occlude_windows_dev(const float* x_dev, const int64_t* offsets_dev,
+                            const dbh_occlude_plan* plans_dev, int64_t n_reads, int steps,
+                            int input_size, int side, float* variants_dev, dbh_stream stream) {
+    if (!occlude_shape_ok(n_reads, steps, input_size, side)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!x_dev || !offsets_dev || !plans_dev || !variants_dev) return DBH_ERR_INVALID_ARGUMENT;
+    const size_t floats = (size_t)n_reads * steps * input_size;
+    float* const out[3] = {variants_dev, variants_dev + floats, variants_dev + 2 * floats};
+    DBH_HIP(dbh_occlude::windows(x_dev, offsets_dev, plans_dev, n_reads, steps, input_size, side,
+                                 out, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_occlude_windows_host(const float* x_host, const int64_t* offsets_host,
+                             const dbh_occlude_plan* plans_host, int64_t n_reads, int steps,
+                             int input_size, int side, float* variants_host) {
+    if (!occlude_shape_ok(n_reads, steps, input_size, side)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!x_host || !offsets_host || !plans_host || !variants_host ||
+        !offsets_run_forwards(offsets_host, n_reads))
+        return DBH_ERR_INVALID_ARGUMENT;
+    const size_t floats = (size_t)n_reads * steps * input_size;
+    float* const out[3] = {variants_host, variants_host + floats, variants_host + 2 * floats};
+    dbh_occlude::windows_host(x_host, offsets_host, plans_host, n_reads, steps, input_size, side,
+                              out);
+    return DBH_OK;
+}
+
+int dbh_locate_occluded_workspace_bytes(const dbh_model* m, int64_t n_reads, int scan_size,
+                                        size_t* bytes) {
+    if (!m || !bytes || n_reads < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_GENERAL) return DBH_ERR_UNSUPPORTED;
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
+    if (steps <= 0 || !occlude_shape_ok(n_reads, steps, m->input_size, DBH_SIDE_START))
+        return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t group = std::min(n_reads, locate_group_reads(m, steps));
+    dbh_host::Carve sizing(nullptr);
+    LocateGroup().lay_out(sizing, m, group, steps);
+    OccludeGroup().lay_out(sizing, m, group, steps);
+    *bytes = sizing.used;
+    return DBH_OK;
+}
+
+int dbh_locate_occluded_i16(dbh_model* m, const int16_t* samples_host, const int64_t* offsets_host,
+                            int64_t n_reads, int side, int scan_size, double score_diff,
+                            float* probs_host, int32_t* calls_host, dbh_location* locations_host,
+                            dbh_occlusion* occlusions_host) {
+    if (!m || n_reads < 0 || (side != DBH_SIDE_START && side != DBH_SIDE_END))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (m->kind != DBH_MODEL_KIND_GENERAL) return DBH_ERR_UNSUPPORTED;
+    const int steps = dbh_host::model_steps(m->input_size, scan_size);
+    if (steps <= 0 || !(score_diff == score_diff) ||
+        !occlude_shape_ok(n_reads, steps, m->input_size, side))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    if (!offsets_host || !probs_host || !calls_host || !locations_host || !occlusions_host ||
+        !offsets_run_forwards(offsets_host, n_reads))
+        return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t total_samples = offsets_host[n_reads] - offsets_host[0];
+    if (total_samples > 0 && !samples_host) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(m->device));      // (see dbh_classify_i16)
+    const int C = m->n_classes, cells = m->gen.len[7], L = m->input_size;
+    const int64_t group = std::min(n_reads, locate_group_reads(m, steps));
+    // dbh_locate_i16's block and stream order, with the occlusions beside the other results and the
+    // group's windows beside its workspace
+    DeviceBlock block;
+    int16_t* d_samples = nullptr;
+    int64_t* d_offsets = nullptr;
+    float* d_probs = nullptr;
+    int32_t* d_calls = nullptr;
+    dbh_location* d_locations = nullptr;
+    dbh_occlusion* d_occlusions = nullptr;
+    LocateGroup g;
+    OccludeGroup o;
+    DBH_HIP(block.carve([&](dbh_host::Carve& c) {
+        d_samples = c.take<int16_t>((size_t)std::max<int64_t>(total_samples, 1));
+        d_offsets = c.take<int64_t>((size_t)n_reads + 1);
+        d_probs = c.take<float>((size_t)n_reads * C);
+        d_calls = c.take<int32_t>((size_t)n_reads);
+        d_locations = c.take<dbh_location>((size_t)n_reads);
+        d_occlusions = c.take<dbh_occlusion>((size_t)n_reads);
+        g.lay_out(c, m, group, steps);
+        o.lay_out(c, m, group, steps);
+    }));
+    std::vector<int64_t> rel((size_t)n_reads + 1);
+    for (int64_t i = 0; i <= n_reads; ++i) rel[(size_t)i] = offsets_host[i] - offsets_host[0];
+    if (total_samples > 0)
+        DBH_HIP(hipMemcpyAsync(d_samples, samples_host + offsets_host[0],
+                               (size_t)total_samples * sizeof(int16_t), hipMemcpyHostToDevice, 0));
+    DBH_HIP(hipMemcpyAsync(d_offsets, rel.data(), rel.size() * sizeof(int64_t),
+                           hipMemcpyHostToDevice, 0));
+    for (int64_t r0 = 0; r0 < n_reads; r0 += group) {
+        const int64_t cnt = std::min(group, n_reads - r0);
+        // the group's windows, sliced and normalised once; the unblanked pass on them (the front
+        // takes a window given as fp32 as the value it would have sliced), merge, call and locate
+        DBH_HIP(dbh_occlude::slice(d_samples, d_offsets + r0, cnt, steps, L, side, o.x, 0));
+        DBH_HIP(dbh_gen::forward(m->gen, o.x, nullptr, nullptr, steps, side, cnt * steps, g.wprobs,
+                                 g.evidence, g.act, 0));
+        DBH_HIP(dbh_gen::merge(g.wprobs, cnt, steps, C, score_diff, d_probs + r0 * C, d_calls + r0,
+                               0));
+        DBH_HIP(dbh_locate::locate(g.evidence, d_calls + r0, d_offsets + r0, cnt, steps, cells, C,
+                                   L, side, d_locations + r0, 0));
+        // the plan, the three variants' windows, and one pass each through the same workspace
+        DBH_HIP(dbh_occlude::plan(d_locations + r0, d_offsets + r0, cnt, steps, L, side, o.plans,
+                                  d_occlusions + r0, 0));
+        DBH_HIP(dbh_occlude::windows(o.x, d_offsets + r0, o.plans, cnt, steps, L, side, o.variants,
+                                     0));
+        for (int v = 0; v < 3; ++v) {
+            DBH_HIP(dbh_gen::forward(m->gen, o.variants[v], nullptr, nullptr, steps, side,
+                                     cnt * steps, g.wprobs, nullptr, g.act, 0));
+            DBH_HIP(dbh_gen::merge(g.wprobs, cnt, steps, C, score_diff,
+                                   o.vprobs + (size_t)v * group * C, o.vcalls + (size_t)v * group,
+                                   0));
+        }
+        DBH_HIP(dbh_occlude::gather(o.plans, d_probs + r0 * C, o.vprobs, o.vcalls, cnt, group, C,
+                                    d_occlusions + r0, 0));
+    }
+    DBH_HIP(hipMemcpyAsync(probs_host, d_probs, (size_t)n_reads * C * sizeof(float),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipMemcpyAsync(calls_host, d_calls, (size_t)n_reads * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipMemcpyAsync(locations_host, d_locations, (size_t)n_reads * sizeof(dbh_location),
+                           hipMemcpyDeviceToHost, 0));
+    DBH_HIP(hipMemcpyAsync(occlusions_host, d_occlusions, (size_t)n_reads * sizeof(dbh_occlusion),
                            hipMemcpyDeviceToHost, 0));
     DBH_HIP(hipStreamSynchronize(0));
     return DBH_OK;

@@ -236,7 +236,12 @@ COMMANDS = {
                                           'of fast5 files (will be searched recursively)'))])],
                [(('--multi_read',), dict(action='store_true',
                                          help='Take the reads of multi-read fast5 files where '
-                                              'they are (one-read files may be mixed in)')), _HELP]),
+                                              'they are (one-read files may be mixed in)')),
+                (('--occlude',), dict(action='store_true',
+                                      help='Call each located side again with the located samples '
+                                           'blanked, with everything else blanked and with a '
+                                           'control stretch blanked (six more columns per side)')),
+                _HELP]),
 }
 USES_MODELS = ('classify', 'realtime', 'scan', 'locate')
 

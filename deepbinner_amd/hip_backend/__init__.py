@@ -30,8 +30,10 @@ from ._sweep import (SWEEP_MODES, sweep_counts, sweep_pair, sweep_steps, sweep_t
                      sweep_windows)
 from ._scan import (SCAN_EVENT, scan_events, scan_packed, scan_window_count, scan_window_offsets,
                     scan_windows)
-from ._locate import (CELL_SAMPLES, LOCATION, evidence_floats, locate_packed, locate_rule,
-                      locate_rule_dev, locate_workspace_bytes)
+from ._locate import (CELL_SAMPLES, LOCATION, OCCLUDE_PLAN, OCCLUSION, evidence_floats,
+                      locate_occluded_packed, locate_occluded_workspace_bytes, locate_packed,
+                      locate_rule, locate_rule_dev, locate_workspace_bytes, occlude_plan,
+                      occlude_windows)
 from ._model import (INFLATE_SHUFFLE_REFUSED, INFLATE_STORED, INFLATE_STORED_SHUFFLE,
                      INFLATE_STREAM, INFLATE_VBZ, INFLATE_ZLIB, INFLATE_ZLIB_SHUFFLE, HipModel,
                      ModelWeights, _TensorSpec, classify_pair, classify_pair_deflated,

@@ -144,6 +144,13 @@ def _signatures():
         'dbh_locate_host': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_int, c_int, c_int, ptr]),
         'dbh_locate_workspace_bytes': (c_int, [ptr, c_i64, c_int, P(c_size_t)]),
         'dbh_locate_i16': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_double, ptr, ptr, ptr]),
+        'dbh_occlude_plan_dev': (c_int, [ptr, ptr, c_i64, c_int, c_int, c_int, ptr, ptr, ptr]),
+        'dbh_occlude_plan_host': (c_int, [ptr, ptr, c_i64, c_int, c_int, c_int, ptr, ptr]),
+        'dbh_occlude_windows_dev': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_int, ptr, ptr]),
+        'dbh_occlude_windows_host': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_int, ptr]),
+        'dbh_locate_occluded_workspace_bytes': (c_int, [ptr, c_i64, c_int, P(c_size_t)]),
+        'dbh_locate_occluded_i16': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_double, ptr, ptr,
+                                            ptr, ptr]),
         'dbh_stage_floats': (c_int, [c_int, P(c_i64)]),
         'dbh_debug_forward': (c_int, [ptr, f32, c_i64, c_int, f32]),
         'dbh_forward_kernel_info': (c_int, [P(c_int), P(c_int), P(c_int)]),

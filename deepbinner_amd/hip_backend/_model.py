@@ -10,7 +10,8 @@ from ..model_format import ModelWeights
 from ._abi import (COMBINE_MODES, KIND_GENERAL, MODEL_AUTO, MODEL_GENERAL, HipBackendError,
                    _handle, _packed, _ptr, _side, check, load_library)
 from ._device import device_count, get_device, set_device
-from ._locate import evidence, locate_packed, locate_signals
+from ._locate import (evidence, locate_occluded_packed, locate_occluded_signals, locate_packed,
+                      locate_signals)
 from ._scan import SCAN_EVENT, host_window_offsets
 from ._sweep import sweep_pair
 
@@ -279,6 +280,14 @@ class HipModel(Owner, Finalised):
     def locate_packed(self, samples, offsets, side, scan_size, score_diff):
         """``locate_signals`` for whole reads already packed."""
         return locate_packed(self, samples, offsets, side, scan_size, score_diff)
+
+    def locate_occluded_signals(self, signals, side, scan_size, score_diff):
+        """Whole reads -> (probs, calls, locations as ``locate_signals``, occlusions OCCLUSION [N])."""
+        return locate_occluded_signals(self, signals, side, scan_size, score_diff)
+
+    def locate_occluded_packed(self, samples, offsets, side, scan_size, score_diff):
+        """``locate_occluded_signals`` for whole reads already packed."""
+        return locate_occluded_packed(self, samples, offsets, side, scan_size, score_diff)
 
     # -- device-resident entry points (inputs/outputs are raw device pointers) -----------------
     def workspace_bytes(self, n_reads, scan_size):

@@ -365,7 +365,8 @@ int dbh_scan_i16(dbh_model* model, const int16_t* samples_host, const int64_t* o
  * (network_architecture.py:91-93), so a class's logit IS the mean, over the positions of stage 7, of
  * that class's post-ReLU conv1d_20 output.  Each position is one cell of 2^7 = 128 samples.  That
  * per-cell value is the class's EVIDENCE: a decomposition of the logit, not a heuristic.  It says
- * where the NETWORK sees the barcode; nothing here has been checked against where the barcode is.
+ * where the NETWORK sees the barcode; nothing here has been checked against where the barcode is
+ * (whether the call DEPENDS on the located samples is what the occlude section below tests).
  *
  * L = the model's input size, h = L / 2, C its classes, cells = len7 = the positions of stage 7
  * ((L/2)/2/2/2/2, halved rounding up, halved again: 8 at L = 1024), a read has n samples.
@@ -437,6 +438,101 @@ int dbh_locate_workspace_bytes(const dbh_model* model, int64_t n_reads, int scan
 int dbh_locate_i16(dbh_model* model, const int16_t* samples_host, const int64_t* offsets_host,
                    int64_t n_reads, int side, int scan_size, double score_diff, float* probs_host,
                    int32_t* calls_host, dbh_location* locations_host);
+
+/* ---- occlude: blank the located span and call the read again ----------------------------------- */
+/* A location says where the network looks; it does not say that the call DEPENDS on those samples.
+ * The faithfulness test of an attribution: take the located samples away and see whether the call
+ * goes, take away everything else and see whether it stays, take away an equally long stretch
+ * elsewhere and see that nothing happens.  "Away" is 0.0f: what the zero pad of a short window is
+ * after normalisation (classify.py:330-357), the window's mean - a value the network was trained
+ * on.  This tests the attribution against the MODEL, still not against where the barcode is.
+ *
+ * L, h, n as in the locate section.  Per read and side, after dbh_locate_i16's own pass, for a side
+ * whose location has cls = c > 0 and span [first_sample, end_sample) of m > 0 read samples:
+ *   Scanned region R.  The read samples the side's `steps` windows cover:
+ *       side start: [0, min(n, (steps - 1) h + L));  side end: [max(0, n - (steps - 1) h - L), n).
+ *       (A span given from outside is first held to R; dbh_locate_dev's lies inside it.)
+ *   Variant.  The side's same `steps` windows, sliced and normalised exactly as for the unblanked
+ *       pass, with the statistics of the unblanked samples; then every window position whose read
+ *       sample (o + position, o the window's origin of the locate section) lies in the blank set B
+ *       is stored as 0.0f.  Pad positions are 0 already.  Nothing is renormalised.
+ *       DBH_OCCLUDE_OUT:  B = the span.
+ *       DBH_OCCLUDE_ONLY: B = R minus the span.
+ *       DBH_OCCLUDE_CTRL: B = a control stretch of m samples: the last m samples of R if the span's
+ *           midpoint lies below R's (first_sample + end_sample < R.lo + R.hi, the doubled integers),
+ *           otherwise the first m.  If the control stretch overlaps the span there is no control.
+ *   Result per variant.  The variant's windows go through the same forward, merge and call as the
+ *       unblanked pass: call_v, and p_v = class c's merged, normalised probability - c the
+ *       UNBLANKED call, not the variant's.
+ *   No result.  A side without a location, m == 0 after clipping (all three variants), or a missing
+ *       control (DBH_OCCLUDE_CTRL alone): call = -1, p = NaN, control samples -1, -1.
+ *   Record.  dbh_occlusion, 64 bytes: cls (0: no location) and p, class c's probability in the
+ *       unblanked pass (NaN where cls == 0); variant[v] = (call_v, p_v); [ctrl_first, ctrl_end) the
+ *       control stretch; reserved is 0.
+ *   Plan.  dbh_occlude_plan, 64 bytes, what the window kernel reads: per variant an interval
+ *       [first[v], end[v]) of read samples, bit v of `invert` set where the variant blanks the read's
+ *       samples OUTSIDE its interval (DBH_OCCLUDE_ONLY: the read samples of a window all lie in R),
+ *       bit v of `valid` set where the variant has a result.  A variant without a result has an
+ *       empty interval and no invert bit: its windows are copies.
+ *
+ * dbh_occlude_plan_dev / _host: locations [n_reads], offsets int64 [n_reads + 1] (only their
+ * differences are read) -> plans [n_reads] and occlusions [n_reads] with cls, the control samples
+ * and every "no result" field written (p and the variants of a result are NaN / -1 until the route
+ * fills them).  dbh_occlude_windows_dev / _host: x [n_reads][steps][L] normalised windows, offsets,
+ * plans -> variants [3][n_reads][steps][L].  Copies and zeros: the _host entries are the CPU models
+ * of the kernels, the same lines, bit for bit.  The _dev entries queue and return; no allocation,
+ * no synchronisation; pointers need the alignment of their element type only, and x and the
+ * variants must not overlap.
+ * dbh_locate_occluded_i16: dbh_locate_i16 with the three variant passes added per group: the
+ * group's windows are sliced and normalised once, and the four passes follow each other through
+ * the group's one workspace.  probs_host, calls_host and locations_host are dbh_locate_i16's to the
+ * bit; occlusions_host [n_reads].  No result depends on the grouping.
+ * dbh_locate_occluded_workspace_bytes: dbh_locate_workspace_bytes plus the group's four sets of
+ * windows, three sets of merged probabilities and calls, and its plans.
+ * The entries that take a model are general-kind only (DBH_ERR_UNSUPPORTED otherwise), as locate's.
+ * Every entry checks its arguments before any device work and writes nothing on error: a null model
+ * or pointer, n_reads < 0, steps < 1, steps * L above 2^30, an input_size that is odd or outside
+ * 96 .. 16,384, a side that is neither DBH_SIDE_START nor DBH_SIDE_END, a scan_size that is no
+ * positive multiple of h, offsets that run backwards (host entries): DBH_ERR_INVALID_ARGUMENT.
+ * n_reads == 0 is DBH_OK. */
+#define DBH_OCCLUDE_OUT 0
+#define DBH_OCCLUDE_ONLY 1
+#define DBH_OCCLUDE_CTRL 2
+typedef struct dbh_occlude_plan {
+    int64_t first[3], end[3];
+    int32_t invert, valid;
+    int64_t reserved;
+} dbh_occlude_plan;
+typedef struct dbh_occlusion_result {
+    int32_t call;
+    float p;
+} dbh_occlusion_result;
+typedef struct dbh_occlusion {
+    int32_t cls;
+    float p;
+    dbh_occlusion_result variant[3];
+    int64_t ctrl_first, ctrl_end;
+    int64_t reserved[2];
+} dbh_occlusion;
+int dbh_occlude_plan_dev(const dbh_location* locations_dev, const int64_t* offsets_dev,
+                         int64_t n_reads, int steps, int input_size, int side,
+                         dbh_occlude_plan* plans_dev, dbh_occlusion* occlusions_dev,
+                         dbh_stream stream);
+int dbh_occlude_plan_host(const dbh_location* locations_host, const int64_t* offsets_host,
+                          int64_t n_reads, int steps, int input_size, int side,
+                          dbh_occlude_plan* plans_host, dbh_occlusion* occlusions_host);
+int dbh_occlude_windows_dev(const float* x_dev, const int64_t* offsets_dev,
+                            const dbh_occlude_plan* plans_dev, int64_t n_reads, int steps,
+                            int input_size, int side, float* variants_dev, dbh_stream stream);
+int dbh_occlude_windows_host(const float* x_host, const int64_t* offsets_host,
+                             const dbh_occlude_plan* plans_host, int64_t n_reads, int steps,
+                             int input_size, int side, float* variants_host);
+int dbh_locate_occluded_workspace_bytes(const dbh_model* model, int64_t n_reads, int scan_size,
+                                        size_t* bytes);
+int dbh_locate_occluded_i16(dbh_model* model, const int16_t* samples_host,
+                            const int64_t* offsets_host, int64_t n_reads, int side, int scan_size,
+                            double score_diff, float* probs_host, int32_t* calls_host,
+                            dbh_location* locations_host, dbh_occlusion* occlusions_host);
 
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's
