@@ -4,7 +4,7 @@
 // small seam kernels (stand-alone normalise, merge, combine_calls) are built, and launched, in
 // dbh_kernels.hip; this file calls its launch functions (dbh_kernels.h).  The sweep's fold and tally
 // kernels likewise: dbh_sweep.hip behind dbh_sweep.h; the scan's front and event kernels:
-// dbh_scan.hip behind dbh_scan.h.
+// dbh_scan.hip behind dbh_scan.h; the live sessions' kernels: dbh_live.hip behind dbh_live.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +26,7 @@
 #include "dbh_host_layout.h"
 #include "dbh_kernels.h"
 #include "dbh_layout.h"
+#include "dbh_live.h"
 #include "dbh_locate.h"
 #include "dbh_occlude.h"
 #include "dbh_owned.h"
@@ -1659,6 +1660,239 @@ int dbh_locate_occluded_i16(dbh_model* m, const int16_t* samples_host, const int
     DBH_HIP(hipMemcpyAsync(occlusions_host, d_occlusions, (size_t)n_reads * sizeof(dbh_occlusion),
                            hipMemcpyDeviceToHost, 0));
     DBH_HIP(hipStreamSynchronize(0));
+    return DBH_OK;
+}
+
+// ---- live: each read's barcode called while its signal arrives (dbh_live.hip) --------------------
+}  // extern "C"
+
+// A session: the channels' state on the device, and on the host a mirror of every channel's record
+// and gate.  The mirror runs dbh_live_core.h's append over the arguments of a push - the lines the
+// append kernel runs over the device's copy - so the host knows how many windows the push makes
+// ready without reading the device back, and a push needs no synchronise between its kernels.  What
+// only the device can know (a decision, and with it the stop under STOP_ON_DECISION) comes back in
+// the results at the push's one synchronise and is put into the mirror there.  Destroy a session
+// before its model.
+struct dbh_live_session {
+    dbh_model* model = nullptr;
+    int n_channels = 0;
+    dbh_live::Shape shape{};
+    int64_t round_windows = 0;
+    dbh_owned::Stream stream;
+    DeviceBlock state_block, push_block, in_block;
+    PinnedBlock h_in, h_out;
+    dbh_live::State st{};
+    dbh_live::Chunk* d_chunks = nullptr;
+    int32_t *d_first = nullptr, *d_count = nullptr;
+    int64_t* d_win_offsets = nullptr;
+    float *d_x = nullptr, *d_probs = nullptr;
+    dbh_live_result* d_results = nullptr;
+    std::vector<dbh_live_result> rec;          // the mirror
+    std::vector<dbh_live::Gate> gate;
+    std::vector<int64_t> seen;                 // the push that last named the channel
+    int64_t pushes = 0;
+};
+
+namespace {
+bool live_fold_general(const dbh_model* m) { return m->kind == DBH_MODEL_KIND_GENERAL; }
+}  // namespace
+
+extern "C" {
+
+int dbh_live_create(dbh_model* m, int n_channels, int scan_size, double score_diff,
+                    int min_windows, uint32_t flags, int64_t max_round_windows,
+                    dbh_live_session** session) {
+    if (!m || !session || n_channels < 1 || n_channels > DBH_LIVE_MAX_CHANNELS ||
+        max_round_windows < 0)
+        return DBH_ERR_INVALID_ARGUMENT;
+    const dbh_live::Shape shape =
+        dbh_live::shape_of(m->input_size, scan_size, score_diff, min_windows, flags);
+    if (!dbh_live::shape_ok(shape, scan_size)) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(m->device));
+    std::unique_ptr<dbh_live_session> s(new (std::nothrow) dbh_live_session);
+    if (!s) return DBH_ERR_OUT_OF_MEMORY;
+    s->model = m;
+    s->n_channels = n_channels;
+    s->shape = shape;
+    const int L = shape.L, C = m->n_classes, steps = shape.steps;
+    const int64_t all = (int64_t)n_channels * steps;
+    // a forward round: what the caller said, else 64 MiB of fp32 input; never more than all windows
+    const int64_t by_default = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)L * 4));
+    s->round_windows = std::min(all, max_round_windows > 0 ? max_round_windows : by_default);
+    DBH_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
+    const size_t n = (size_t)n_channels;
+    s->st.stride = (shape.cap + 7) & ~(long long)7;
+    s->st.n_classes = C;
+    DBH_HIP(s->state_block.carve([&](dbh_host::Carve& c) {
+        s->st.samples = c.take<int16_t>(n * (size_t)s->st.stride);
+        s->st.rec = c.take<dbh_live_result>(n);
+        s->st.gate = c.take<dbh_live::Gate>(n);
+        s->st.merged = c.take<float>(n * C);
+        s->st.best = c.take<int32_t>(n * steps);
+        s->st.margin = c.take<double>(n * steps);
+    }));
+    DBH_HIP(s->push_block.carve([&](dbh_host::Carve& c) {
+        s->d_first = c.take<int32_t>(n);
+        s->d_count = c.take<int32_t>(n);
+        s->d_win_offsets = c.take<int64_t>(n + 1);
+        s->d_results = c.take<dbh_live_result>(n);
+        s->d_x = c.take<float>((size_t)s->round_windows * L);
+        s->d_probs = c.take<float>((size_t)s->round_windows * C);
+    }));
+    DBH_HIP(s->h_out.reserve(n * sizeof(dbh_live_result)));
+    s->rec.assign(n, dbh_live::fresh_record());
+    s->gate.assign(n, dbh_live::Gate{0, 0});
+    s->seen.assign(n, -1);
+    DBH_HIP(hipMemcpyAsync(s->st.rec, s->rec.data(), n * sizeof(dbh_live_result),
+                           hipMemcpyHostToDevice, s->stream));
+    DBH_HIP(hipMemsetAsync(s->st.gate, 0, n * sizeof(dbh_live::Gate), s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    *session = s.release();
+    return DBH_OK;
+}
+
+int dbh_live_destroy(dbh_live_session* s) {
+    delete s;      // (stream, device state and pinned memory are members that free themselves)
+    return DBH_OK;
+}
+
+int dbh_live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
+                  const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+                  int64_t n_chunks) {
+    if (!s || n_chunks < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_chunks == 0) return DBH_OK;
+    if (!channels || !offsets || !samples || !flags || !results || n_chunks > s->n_channels)
+        return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t push = s->pushes + 1;        // (`seen` is scratch: a refused push leaves no state)
+    for (int64_t i = 0; i < n_chunks; ++i) {
+        const int32_t ch = channels[i];
+        if (ch < 0 || ch >= s->n_channels || s->seen[(size_t)ch] == push ||
+            offsets[i + 1] < offsets[i] || (flags[i] & ~(uint32_t)(DBH_LIVE_BEGIN | DBH_LIVE_END))) {
+            for (int64_t j = 0; j < i; ++j) s->seen[(size_t)channels[j]] = -1;
+            return DBH_ERR_INVALID_ARGUMENT;
+        }
+        s->seen[(size_t)ch] = push;
+    }
+    s->pushes = push;
+    const dbh_live::Shape& shape = s->shape;
+    DBH_HIP(hipSetDevice(s->model->device));
+    // the plan: the mirror's copy of every chunk's channel through append, the kept samples placed
+    // so that source and row are aligned alike (16-byte copies in the append kernel)
+    const size_t n = (size_t)n_chunks;
+    std::vector<dbh_live_result> rec(n);
+    std::vector<dbh_live::Gate> gate(n);
+    std::vector<dbh_live::Append> plan(n);
+    std::vector<dbh_live::Chunk> chunks(n);
+    int64_t staged = 0, total_windows = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t ch = (size_t)channels[i];
+        rec[i] = s->rec[ch];
+        gate[i] = s->gate[ch];
+        const int64_t length = offsets[i + 1] - offsets[i];
+        plan[i] = dbh_live::append(&rec[i], &gate[i], flags[i], length, shape);
+        const int64_t at = staged + ((plan[i].at - staged) & 7);       // at % 8 == plan.at % 8
+        chunks[i] = dbh_live::Chunk{at, length, channels[i], flags[i]};
+        staged = at + plan[i].keep;
+        total_windows += plan[i].count;
+    }
+    const size_t table_bytes = align256(n * sizeof(dbh_live::Chunk));
+    const size_t in_bytes = table_bytes + align256((size_t)staged * sizeof(int16_t) + 16);
+    DBH_HIP(s->h_in.reserve(in_bytes));
+    DBH_HIP(s->in_block.reserve(in_bytes));
+    std::memcpy(s->h_in.get(), chunks.data(), n * sizeof(dbh_live::Chunk));
+    int16_t* h_samples = s->h_in.as<int16_t>(table_bytes);
+    for (size_t i = 0; i < n; ++i)
+        if (plan[i].keep > 0)
+            std::memcpy(h_samples + chunks[i].src, samples + offsets[i],
+                        (size_t)plan[i].keep * sizeof(int16_t));
+    hipStream_t stream = s->stream;
+    DBH_HIP(hipMemcpyAsync(s->in_block.get(), s->h_in.get(), in_bytes, hipMemcpyHostToDevice,
+                           stream));
+    const dbh_live::Chunk* d_chunks = s->in_block.as<dbh_live::Chunk>();
+    const int16_t* d_in = s->in_block.as<int16_t>(table_bytes);
+    DBH_HIP(dbh_live::append(s->st, shape, d_chunks, d_in, (int)n_chunks, s->d_first, s->d_count,
+                             stream));
+    DBH_HIP(dbh_live::window_list(s->d_count, (int)n_chunks, s->d_win_offsets, stream));
+    for (int64_t w0 = 0; w0 < total_windows; w0 += s->round_windows) {
+        const int64_t cnt = std::min(s->round_windows, total_windows - w0);
+        DBH_HIP(dbh_live::front(s->st, shape, d_chunks, s->d_first, s->d_win_offsets, (int)n_chunks,
+                                w0, cnt, s->d_x, stream));
+        DBH_TRY(dbh_predict_dev(s->model, s->d_x, cnt, s->d_probs, (dbh_stream)stream));
+        DBH_HIP(dbh_live::fold(live_fold_general(s->model), s->st, shape, d_chunks,
+                               s->d_win_offsets, n_chunks, w0, cnt, s->d_probs, stream));
+    }
+    DBH_HIP(dbh_live::results(s->st, d_chunks, s->d_first, (int)n_chunks, s->d_results, stream));
+    DBH_HIP(hipMemcpyAsync(s->h_out.get(), s->d_results, n * sizeof(dbh_live_result),
+                           hipMemcpyDeviceToHost, stream));
+    DBH_HIP(hipStreamSynchronize(stream));
+    std::memcpy(results, s->h_out.get(), n * sizeof(dbh_live_result));
+    for (size_t i = 0; i < n; ++i) {
+        if (plan[i].idle) continue;
+        s->rec[(size_t)channels[i]] = results[i];       // (the decision is the device's to make)
+        s->gate[(size_t)channels[i]] = gate[i];
+    }
+    return DBH_OK;
+}
+
+int dbh_live_track(dbh_live_session* s, int channel, int32_t* best, double* margin,
+                   int32_t* windows) {
+    if (!s || !best || !margin || !windows || channel < 0 || channel >= s->n_channels)
+        return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(s->model->device));
+    const int steps = s->shape.steps;
+    DBH_HIP(hipMemcpyAsync(best, s->st.best + (size_t)channel * steps, (size_t)steps * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, s->stream));
+    DBH_HIP(hipMemcpyAsync(margin, s->st.margin + (size_t)channel * steps,
+                           (size_t)steps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    *windows = s->rec[(size_t)channel].windows;
+    return DBH_OK;
+}
+
+int dbh_live_fold_dev(const dbh_model* m, const float* window_probs_dev,
+                      const int64_t* window_offsets_dev, int64_t n_channels, int64_t n_windows,
+                      int steps, double score_diff, int min_windows, uint32_t flags,
+                      float* merged_dev, dbh_live_result* state_dev, int32_t* best_dev,
+                      double* margin_dev, dbh_stream stream) {
+    if (!m || n_channels < 0 || n_windows < 0 || steps < 1) return DBH_ERR_INVALID_ARGUMENT;
+    const int half = m->input_size / 2;
+    if ((int64_t)steps * half > INT32_MAX) return DBH_ERR_INVALID_ARGUMENT;
+    const dbh_live::Shape shape =
+        dbh_live::shape_of(m->input_size, steps * half, score_diff, min_windows, flags);
+    if (!dbh_live::shape_ok(shape, steps * half)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_channels == 0) return DBH_OK;
+    if (!window_offsets_dev || !merged_dev || !state_dev || !best_dev || !margin_dev ||
+        (n_windows > 0 && !window_probs_dev))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (n_windows == 0) return DBH_OK;
+    dbh_live::State st{};
+    st.rec = state_dev;
+    st.merged = merged_dev;
+    st.best = best_dev;
+    st.margin = margin_dev;
+    st.n_classes = m->n_classes;
+    DBH_HIP(dbh_live::fold(live_fold_general(m), st, shape, nullptr, window_offsets_dev, n_channels,
+                           0, n_windows, window_probs_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_live_plan_host(int input_size, int scan_size, double score_diff, int min_windows,
+                       uint32_t flags, const int64_t* lengths, const uint32_t* chunk_flags,
+                       int64_t n_chunks, const int32_t* track_best, const double* track_margin,
+                       dbh_live_result* results_host, int32_t* new_windows_host) {
+    if (n_chunks < 0) return DBH_ERR_INVALID_ARGUMENT;
+    const dbh_live::Shape shape =
+        dbh_live::shape_of(input_size, scan_size, score_diff, min_windows, flags);
+    if (!dbh_live::shape_ok(shape, scan_size)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_chunks == 0) return DBH_OK;
+    if (!lengths || !chunk_flags || !track_best || !track_margin || !results_host)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_chunks; ++i)
+        if (lengths[i] < 0 || (chunk_flags[i] & ~(uint32_t)(DBH_LIVE_BEGIN | DBH_LIVE_END)))
+            return DBH_ERR_INVALID_ARGUMENT;
+    dbh_live::plan_channel(shape, (const long long*)lengths, (const unsigned*)chunk_flags,
+                           (long long)n_chunks, (const int*)track_best, track_margin, results_host,
+                           (int*)new_windows_host);
     return DBH_OK;
 }
 

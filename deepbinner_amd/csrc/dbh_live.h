@@ -1,0 +1,61 @@
+// dbh_live.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_live.hip: the
+// kernels of a live session's push, one launch function each.  No kernel symbol leaves the unit.
+// The contract is include/deepbinner_hip.h's ("live"); the rules are dbh_live_core.h's.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "dbh_live_core.h"
+
+namespace dbh_live {
+
+constexpr int kMaxClasses = 256;      // the general path's limit (dbh_general.h)
+
+// one chunk of a push as the kernels read it: `length` samples for `channel`, of which the ones
+// that are kept lie from in[src] on
+struct Chunk {
+    long long src, length;
+    int channel;
+    unsigned flags;
+};
+
+// the channels' state on the device: sample rows of `stride` int16 (a multiple of 8, so that every
+// row begins on a 16-byte boundary), the records and gates, merged [C], the track [steps]
+struct State {
+    int16_t* samples;
+    long long stride;
+    dbh_live_result* rec;
+    Gate* gate;
+    float* merged;
+    int32_t* best;
+    double* margin;
+    int n_classes;
+};
+
+// per chunk: reset on BEGIN, the kept samples into the channel's row, the counters; first[i] /
+// count[i] get the windows this push made ready (first -1: an idle chunk)
+hipError_t append(const State& st, const Shape& shape, const Chunk* chunks, const int16_t* in,
+                  int n_chunks, int32_t* first, int32_t* count, hipStream_t stream);
+
+// win_offsets[n_chunks + 1]: the exclusive prefix of count, the total behind it
+hipError_t window_list(const int32_t* count, int n_chunks, int64_t* win_offsets,
+                       hipStream_t stream);
+
+// x[n][L]: listed windows [w0, w0 + n), cut from the channels' rows, normalised and padded
+hipError_t front(const State& st, const Shape& shape, const Chunk* chunks, const int32_t* first,
+                 const int64_t* win_offsets, int n_chunks, int64_t w0, int64_t n, float* x,
+                 hipStream_t stream);
+
+// Folds listed windows [w0, w0 + n), whose probabilities are probs[n][C], into their channels in
+// order: merged, record and track.  chunks null: chunk i is channel i.  general: one workgroup per
+// chunk with dbh_trees.h's sums (C <= 256), else 32 lanes per chunk (C <= 32).
+hipError_t fold(bool general, const State& st, const Shape& shape, const Chunk* chunks,
+                const int64_t* win_offsets, int64_t n_chunks, int64_t w0, int64_t n,
+                const float* probs, hipStream_t stream);
+
+// results[i]: the record of chunk i's channel, IDLE where first[i] < 0
+hipError_t results(const State& st, const Chunk* chunks, const int32_t* first, int n_chunks,
+                   dbh_live_result* results, hipStream_t stream);
+
+}  // namespace dbh_live

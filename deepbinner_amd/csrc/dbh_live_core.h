@@ -1,0 +1,163 @@
+// dbh_live_core.h - the rules of a live session (include/deepbinner_hip.h, "live"; DESIGN.md section
+// 32) that are integers and comparisons: which windows of a channel are ready, what of a chunk is
+// stored, and what a folded window does to the channel's record.  The GPU's threads (dbh_live.hip),
+// the session's host mirror (dbh_api.hip: it knows every push's window count without reading the
+// device back) and the CPU model (dbh_live_plan_host; live_model_check.cpp) compile these lines.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/deepbinner_hip.h"
+
+#if defined(__HIPCC__)
+#define DBLIVE_FN __host__ __device__ __forceinline__
+#else
+#define DBLIVE_FN inline
+#endif
+
+namespace dbh_live {
+
+// the shape of a session: L = input size, h = L / 2, cap = scan_size + h
+struct Shape {
+    int L, h, steps;
+    long long cap;
+    double score_diff;
+    int min_windows;
+    unsigned flags;                      // DBH_LIVE_STOP_ON_DECISION
+};
+
+DBLIVE_FN Shape shape_of(int input_size, int scan_size, double score_diff, int min_windows,
+                         unsigned flags) {
+    Shape s;
+    s.L = input_size;
+    s.h = input_size / 2;
+    s.steps = s.h > 0 ? scan_size / s.h : 0;
+    s.cap = (long long)scan_size + s.h;
+    s.score_diff = score_diff;
+    s.min_windows = min_windows;
+    s.flags = flags;
+    return s;
+}
+
+// what creation takes: even L, scan_size a positive multiple of h, 1 <= min_windows <= steps, the
+// one flag bit, a threshold that is a number
+DBLIVE_FN bool shape_ok(const Shape& s, int scan_size) {
+    return s.L >= 2 && s.L % 2 == 0 && scan_size > 0 && s.steps >= 1 &&
+           (long long)s.steps * s.h == scan_size && s.min_windows >= 1 && s.min_windows <= s.steps &&
+           (s.flags & ~(unsigned)DBH_LIVE_STOP_ON_DECISION) == 0 && s.score_diff == s.score_diff;
+}
+
+// a channel apart from its record: is a read open, has it ended
+struct Gate {
+    int open, ended;
+};
+
+DBLIVE_FN dbh_live_result fresh_record() {
+    dbh_live_result r;
+    r.status = DBH_LIVE_IDLE;
+    r.call = 0;
+    r.final_call = -1;
+    r.windows = 0;
+    r.decided_windows = 0;
+    r.best = 0;
+    r.margin = 0.0;
+    r.samples = 0;
+    r.decided_samples = 0;
+    return r;
+}
+
+// windows 0 .. ready - 1 of a read of n samples can run: k h + L <= n, or every one behind END
+DBLIVE_FN int ready_windows(long long n, int ended, const Shape& s) {
+    if (ended) return s.steps;
+    if (n < s.L) return 0;
+    const long long w = (n - s.L) / s.h + 1;
+    return w < s.steps ? (int)w : s.steps;
+}
+
+// stores and runs nothing more
+DBLIVE_FN bool stopped(const dbh_live_result& r, const Shape& s) {
+    return r.status == DBH_LIVE_FINAL ||
+           (r.status == DBH_LIVE_DECIDED && (s.flags & DBH_LIVE_STOP_ON_DECISION) != 0);
+}
+
+// What one chunk does: the first `keep` of its samples go to [at, at + keep) of the channel's
+// buffer, and windows [first, first + count) have to run.  idle: nothing changed.
+struct Append {
+    long long at, keep;
+    int first, count, idle;
+};
+
+// reset on BEGIN, append, set ended on END - in this order
+DBLIVE_FN Append append(dbh_live_result* r, Gate* g, unsigned chunk_flags, long long length,
+                        const Shape& s) {
+    Append a;
+    a.at = a.keep = 0;
+    a.first = a.count = a.idle = 0;
+    if (chunk_flags & DBH_LIVE_BEGIN) {
+        *r = fresh_record();
+        r->status = DBH_LIVE_PENDING;
+        g->open = 1;
+        g->ended = 0;
+    } else if (!g->open) {
+        a.idle = 1;
+        return a;
+    }
+    const bool stop = stopped(*r, s);
+    a.at = r->samples < s.cap ? r->samples : s.cap;            // the clip at cap
+    a.keep = stop ? 0 : (length < s.cap - a.at ? length : s.cap - a.at);
+    r->samples += length;
+    if (chunk_flags & DBH_LIVE_END) {
+        g->ended = 1;
+        g->open = 0;
+    }
+    a.first = r->windows;
+    a.count = stop ? 0 : ready_windows(r->samples, g->ended, s) - r->windows;
+    return a;
+}
+
+// may window r->windows be folded?  (under STOP_ON_DECISION the fold ends behind the deciding one)
+DBLIVE_FN bool may_fold(const dbh_live_result& r, const Shape& s) {
+    return r.windows < s.steps && !stopped(r, s);
+}
+
+// window k = r->windows was folded and the prefix ends in (best, margin)
+DBLIVE_FN void folded(dbh_live_result* r, int best, double margin, const Shape& s) {
+    const int k = r->windows;
+    r->windows = k + 1;
+    r->best = best;
+    r->margin = margin;
+    const bool leads = best != 0 && margin >= s.score_diff;
+    if (r->decided_windows == 0 && k + 1 >= s.min_windows && leads) {
+        r->call = best;
+        r->decided_windows = k + 1;
+        r->decided_samples = r->samples;
+        r->status = DBH_LIVE_DECIDED;
+    }
+    if (r->windows == s.steps) {
+        r->status = DBH_LIVE_FINAL;
+        r->final_call = leads ? best : 0;
+    }
+}
+
+// One channel through n_chunks pushes on the host: window k folds to (track_best[k],
+// track_margin[k]).  results[i]: the record behind push i; new_windows[i] (may be null): the
+// windows that push folded.
+DBLIVE_FN void plan_channel(const Shape& s, const long long* lengths, const unsigned* chunk_flags,
+                            long long n_chunks, const int* track_best, const double* track_margin,
+                            dbh_live_result* results, int* new_windows) {
+    dbh_live_result r = fresh_record();
+    Gate g;
+    g.open = g.ended = 0;
+    for (long long i = 0; i < n_chunks; ++i) {
+        const Append a = append(&r, &g, chunk_flags[i], lengths[i], s);
+        int done = 0;
+        for (int j = 0; j < a.count && may_fold(r, s); ++j, ++done)
+            folded(&r, track_best[r.windows], track_margin[r.windows], s);
+        results[i] = r;
+        if (a.idle) results[i].status = DBH_LIVE_IDLE;
+        if (new_windows) new_windows[i] = done;
+    }
+}
+
+}  // namespace dbh_live

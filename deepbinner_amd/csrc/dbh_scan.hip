@@ -25,6 +25,7 @@
 
 #include <algorithm>
 
+#include "dbh_front.h"
 #include "dbh_scan.h"
 #include "dbh_wave.h"
 
@@ -35,14 +36,9 @@ constexpr int kThreads = 256;                 // four waves: four windows, or fo
 constexpr int kPrefixThreads = 1024;
 constexpr int kSearchDepth = 64;              // halvings of a range of at most 2^63 reads
 
-// One trip of a prefix over values handed out 1,024 at a time: this thread's exclusive prefix,
-// the carry moved on by the trip's total.  All threads call it; `part` is free again on return.
+// one trip of a prefix over values handed out 1,024 at a time (dbh_wave.h)
 __device__ __forceinline__ long long prefix_trip(long long v, long long* part, long long* carry) {
-    const long long incl = dbh_wave::block_scan_inclusive<long long, kPrefixThreads>(v, part);
-    const long long before = *carry + incl - v;
-    *carry += part[kPrefixThreads - 1];
-    __syncthreads();
-    return before;
+    return dbh_wave::prefix_trip<kPrefixThreads>(v, part, carry);
 }
 
 __global__ __launch_bounds__(kPrefixThreads) void window_offsets_kernel(
@@ -75,12 +71,7 @@ __global__ __launch_bounds__(kPrefixThreads) void event_offsets_kernel(
     }
 }
 
-// ---- the ragged front ---------------------------------------------------------------------------
-__device__ __forceinline__ float normalised(int16_t x, double mean, double sd) {
-    const double d = (double)x - mean;
-    return sd == 0.0 ? (float)d : (float)(d / sd);
-}
-
+// ---- the ragged front (the rule itself: dbh_front.h, shared with dbh_live.hip) ------------------
 __global__ __launch_bounds__(kThreads) void windows_kernel(
     const int16_t* __restrict__ samples, const long long* __restrict__ offsets,
     const long long* __restrict__ window_offsets, long long n_reads, int L, int side,
@@ -110,26 +101,8 @@ __global__ __launch_bounds__(kThreads) void windows_kernel(
         m = b - a;
         a += offsets[lo];
     }
-    const int16_t* src = samples + a;
-    long long s = 0, q = 0;
-    for (int i = lane; i < m; i += 64) {
-        const long long v = src[i];
-        s += v;
-        q += v * v;
-    }
-    s = dbh_wave::wave_sum(s);
-    q = dbh_wave::wave_sum(q);
-    double mean = 0.0, sd = 0.0;
-    if (m > 0) {
-        const long long d = m * q - s * s;                     // m^2 * variance, exact: below 2^59
-        mean = (double)s / (double)m;
-        sd = sqrt((double)d) / (double)m;
-    }
     const int pad = side == DBH_SIDE_START ? 0 : L - (int)m;   // zeros in front
-    for (int i = lane; i < L; i += 64) {
-        const int j = i - pad;
-        out[i] = (j >= 0 && j < m) ? normalised(src[j], mean, sd) : 0.f;
-    }
+    dbh_front::window(samples + a, m, L, pad, lane, out);
 }
 
 // ---- events -------------------------------------------------------------------------------------

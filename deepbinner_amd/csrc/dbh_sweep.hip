@@ -15,6 +15,8 @@
 //                    v_permlane16_swap across them) in renormalise_and_call's order
 //   fold256_kernel   one workgroup per read, the halving trees in LDS that dbh_general.hip's
 //                    merge_kernel runs: both call dbh_trees.h's, one text
+// The step itself - one window merged in, the prefix finished - is dbh_fold.h's, which the live
+// sessions' resumable fold (dbh_live.hip) calls as well.
 // One guard the merges do not have: a read whose barcodes are all zero (rest == 0) keeps them zero
 // instead of 0 * (x / 0); class 0 is then the best class here as it is there, so no call changes, and
 // the margin is a number.
@@ -26,9 +28,8 @@
 #include <algorithm>
 
 #include "../../include/deepbinner_hip.h"
-#include "dbh_seam.h"
+#include "dbh_fold.h"
 #include "dbh_sweep.h"
-#include "dbh_trees.h"
 
 namespace dbh_sweep {
 namespace {
@@ -50,26 +51,13 @@ __global__ __launch_bounds__(kThreads) void fold32_kernel(const float* __restric
     const float* src = wprobs + read * steps * n_classes + c;      // (read only where valid)
     float merged = 0.f;
     for (int s = 0; s < steps; ++s) {
-        if (valid) {
-            const float v = src[(long long)s * n_classes];
-            merged = s == 0 ? v : (c == 0 ? fminf(merged, v) : fmaxf(merged, v));
-        }
-        double p = (double)merged;
-        const double rest =
-            reduce32(RedF64{(valid && c > 0) ? p : 0.0},
-                     [](const RedF64& a, const RedF64& b) { return RedF64{a.v + b.v}; }).v;
-        const double p0 = __shfl(p, 0, 32);                        // lane 0 of this read's 32
-        const double factor = rest > 0.0 ? (1.0 - p0) / rest : 0.0;
-        if (c > 0) p = p * factor;
-        const RedBest top = reduce32(RedBest{valid ? p : -1.0, c}, [](const RedBest& a, const RedBest& b) {
-            return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-        });
-        const double second =
-            reduce32(RedF64{(valid && c != top.i) ? p : -1.0},
-                     [](const RedF64& a, const RedF64& b) { return RedF64{fmax(a.v, b.v)}; }).v;
+        if (valid) merged = fold_merge(merged, src[(long long)s * n_classes], s == 0, c);
+        int top;
+        double lead;
+        fold32_step(merged, valid, c, &top, &lead);                // (dbh_fold.h)
         if (c == 0) {
-            best[read * steps + s] = top.i;
-            margin[read * steps + s] = top.v - second;
+            best[read * steps + s] = top;
+            margin[read * steps + s] = lead;
         }
     }
 }
@@ -89,24 +77,14 @@ __global__ __launch_bounds__(kThreads) void fold256_kernel(const float* __restri
     const float* src = wprobs + read * steps * C + c;              // (read only where valid)
     float merged = 0.f;
     for (int s = 0; s < steps; ++s) {
-        if (valid) {
-            const float v = src[(long long)s * C];
-            merged = s == 0 ? v : (c == 0 ? fminf(merged, v) : fmaxf(merged, v));
-        }
-        double p = (double)merged;
-        const double rest = dbh::tree_sum<kThreads>(rv, c, (valid && c > 0) ? p : 0.0);
-        if (c == 0) first = p;
-        __syncthreads();
-        const double p0 = first;
-        if (c > 0) p = p * (rest > 0.0 ? (1.0 - p0) / rest : 0.0);
-        int top_i;
-        const double top_v = dbh::tree_best<kThreads>(rv, ri, c, valid ? p : -1.0, &top_i);
-        const double second = dbh::tree_max<kThreads>(rv, c, (valid && c != top_i) ? p : -1.0);
+        if (valid) merged = dbh::fold_merge(merged, src[(long long)s * C], s == 0, c);
+        int top;
+        double lead;
+        dbh::fold256_step<kThreads>(merged, valid, c, rv, ri, &first, &top, &lead);   // (dbh_fold.h)
         if (c == 0) {
-            best[read * steps + s] = top_i;
-            margin[read * steps + s] = top_v - second;
+            best[read * steps + s] = top;
+            margin[read * steps + s] = lead;
         }
-        // (`first` is written again only behind the next step's tree_sum, which has barriers)
     }
 }
 

@@ -100,4 +100,16 @@ __device__ __forceinline__ T block_scan_inclusive(T v, T* part) {
     return part[t];
 }
 
+// One trip of a prefix over values handed out kThreads at a time (the scan's window and event
+// offsets, the live sessions' window list): this thread's exclusive prefix, the carry moved on by
+// the trip's total.  All threads call it; `part` is free again on return.
+template <int kThreads>
+__device__ __forceinline__ long long prefix_trip(long long v, long long* part, long long* carry) {
+    const long long incl = block_scan_inclusive<long long, kThreads>(v, part);
+    const long long before = *carry + incl - v;
+    *carry += part[kThreads - 1];
+    __syncthreads();
+    return before;
+}
+
 }  // namespace dbh_wave

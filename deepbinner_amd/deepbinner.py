@@ -242,8 +242,28 @@ COMMANDS = {
                                            'blanked, with everything else blanked and with a '
                                            'control stretch blanked (six more columns per side)')),
                 _HELP]),
+    'replay': ('Play reads back as a sequencer delivers them and call each while it arrives',
+               [('Positional', [
+                   (('input',), dict(type=str,
+                                     help='One of the following: a single fast5 file or a directory '
+                                          'of fast5 files (will be searched recursively)'))])],
+               [(('--channels',), dict(type=int, default=512,
+                                       help='Reads in flight at a time, one per sequencer channel')),
+                (('--chunk_samples',), dict(type=int, default=1600,
+                                            help='Samples of every open read per round (1600: 0.4 s '
+                                                 'at 4 kHz)')),
+                (('--min_windows',), dict(type=int, default=1,
+                                          help='A read is decided no earlier than at this many '
+                                               'windows')),
+                (('--stop_on_decision',), dict(action='store_true',
+                                               help='Run no further window of a read once it is '
+                                                    'decided')),
+                (('--multi_read',), dict(action='store_true',
+                                         help='Take the reads of multi-read fast5 files where '
+                                              'they are (one-read files may be mixed in)')),
+                _HELP]),
 }
-USES_MODELS = ('classify', 'realtime', 'scan', 'locate')
+USES_MODELS = ('classify', 'realtime', 'scan', 'locate', 'replay')
 
 
 def _add_groups(parser, groups):
@@ -278,7 +298,7 @@ def main(argv=None):
         sys.exit(1)
     if argv[0] in NOT_PROVIDED:
         sys.exit('Error: the {} command is not part of this build - it covers the classify, '
-                 'realtime, bin, balance, fit, refine, sweep, scan and locate commands only'
+                 'realtime, bin, balance, fit, refine, replay, sweep, scan and locate commands only'
                  .format(argv[0]))
     args = parser.parse_args(argv)
     if args.subparser_name in USES_MODELS:
@@ -303,6 +323,8 @@ def main(argv=None):
         from .scan import scan as run
     elif args.subparser_name == 'locate':
         from .locate import locate as run
+    elif args.subparser_name == 'replay':
+        from .replay import replay as run
     else:
         return
     run(args)

@@ -16,7 +16,7 @@ There is deliberately NO CPU fallback: if the library or a GPU is missing the er
 
 This file is the public surface and only that: it imports and re-exports.  The code lies in the
 private submodules beside it, one per subsystem, each building on those before it: ``_abi``,
-``_device``, ``_sweep``, ``_scan``, ``_locate``, ``_model``, ``_text``, ``_training_file``, ``_training``
+``_device``, ``_sweep``, ``_scan``, ``_locate``, ``_live``, ``_model``, ``_text``, ``_training_file``, ``_training``
 ("The binding as a package").  Code outside this package goes through this file.
 """
 
@@ -34,6 +34,9 @@ from ._locate import (CELL_SAMPLES, LOCATION, OCCLUDE_PLAN, OCCLUSION, evidence_
                       locate_occluded_packed, locate_occluded_workspace_bytes, locate_packed,
                       locate_rule, locate_rule_dev, locate_workspace_bytes, occlude_plan,
                       occlude_windows)
+from ._live import (LIVE_BEGIN, LIVE_DECIDED, LIVE_END, LIVE_FINAL, LIVE_IDLE, LIVE_PENDING,
+                    LIVE_RESULT, LIVE_STOP_ON_DECISION, LiveSession, live_chunk_flags, live_fold,
+                    live_plan_host)
 from ._model import (INFLATE_SHUFFLE_REFUSED, INFLATE_STORED, INFLATE_STORED_SHUFFLE,
                      INFLATE_STREAM, INFLATE_VBZ, INFLATE_ZLIB, INFLATE_ZLIB_SHUFFLE, HipModel,
                      ModelWeights, _TensorSpec, classify_pair, classify_pair_deflated,

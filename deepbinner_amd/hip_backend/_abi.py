@@ -151,6 +151,15 @@ def _signatures():
         'dbh_locate_occluded_workspace_bytes': (c_int, [ptr, c_i64, c_int, P(c_size_t)]),
         'dbh_locate_occluded_i16': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_double, ptr, ptr,
                                             ptr, ptr]),
+        'dbh_live_create': (c_int, [ptr, c_int, c_int, c_double, c_int, ctypes.c_uint32, c_i64,
+                                    P(ptr)]),
+        'dbh_live_destroy': (c_int, [ptr]),
+        'dbh_live_push': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_i64]),
+        'dbh_live_track': (c_int, [ptr, c_int, ptr, ptr, P(ctypes.c_int32)]),
+        'dbh_live_fold_dev': (c_int, [ptr, ptr, ptr, c_i64, c_i64, c_int, c_double, c_int,
+                                      ctypes.c_uint32, ptr, ptr, ptr, ptr, ptr]),
+        'dbh_live_plan_host': (c_int, [c_int, c_int, c_double, c_int, ctypes.c_uint32, ptr, ptr,
+                                       c_i64, ptr, ptr, ptr, ptr]),
         'dbh_stage_floats': (c_int, [c_int, P(c_i64)]),
         'dbh_debug_forward': (c_int, [ptr, f32, c_i64, c_int, f32]),
         'dbh_forward_kernel_info': (c_int, [P(c_int), P(c_int), P(c_int)]),

@@ -1,0 +1,153 @@
+"""Live sessions: each channel's barcode called while its signal arrives (include/deepbinner_hip.h,
+"live").  ``LiveSession`` holds the channels' state on the device between pushes; ``live_fold`` and
+``live_plan_host`` are the parity-only entries of its parts."""
+
+import ctypes
+
+import numpy as np
+
+from .._cabi import Finalised, Owner, Scoped
+from ._abi import check, load_library
+from ._device import device_arrays, synchronize
+
+# dbh_live_result (include/deepbinner_hip.h, "live"): a channel's record behind a push
+LIVE_RESULT = np.dtype([('status', np.int32), ('call', np.int32), ('final_call', np.int32),
+                        ('windows', np.int32), ('decided_windows', np.int32), ('best', np.int32),
+                        ('margin', np.float64), ('samples', np.int64),
+                        ('decided_samples', np.int64)])
+assert LIVE_RESULT.itemsize == 48
+
+LIVE_IDLE, LIVE_PENDING, LIVE_DECIDED, LIVE_FINAL = 0, 1, 2, 3       # status
+LIVE_BEGIN, LIVE_END = 1, 2                                          # chunk flags
+LIVE_STOP_ON_DECISION = 1                                            # session flag
+
+
+def live_chunk_flags(n, begin=None, end=None):
+    """``begin`` / ``end`` (None, one truth value or one per chunk) as the ABI's chunk flags."""
+    flags = np.zeros(n, dtype=np.uint32)
+    for bit, which in ((LIVE_BEGIN, begin), (LIVE_END, end)):
+        if which is not None:
+            flags |= np.where(np.broadcast_to(np.asarray(which, dtype=bool), (n,)), bit,
+                              0).astype(np.uint32)
+    return flags
+
+
+class LiveSession(Owner, Scoped, Finalised):
+    """``n_channels`` sequencer channels of one start-side ``model``: ``push`` appends a chunk of
+    signal to each channel named, runs the windows that became complete and folds them; a channel
+    is DECIDED at the first window from ``min_windows`` on whose best class is a barcode that leads
+    by ``score_diff``, and FINAL when all ``scan_size`` windows are folded.  Close it before its
+    model."""
+
+    _held, _release = 'handle', 'dbh_live_destroy'
+
+    def __init__(self, model, n_channels, scan_size=6144, score_diff=0.5, min_windows=1,
+                 stop_on_decision=False, max_round_windows=0):
+        self._lib = load_library()
+        self.model, self.n_channels, self.scan_size = model, int(n_channels), int(scan_size)
+        half = model.input_size // 2
+        self.steps = self.scan_size // half if half else 0
+        handle = ctypes.c_void_p()
+        check(self._lib.dbh_live_create(model.handle, self.n_channels, self.scan_size,
+                                        float(score_diff), int(min_windows),
+                                        LIVE_STOP_ON_DECISION if stop_on_decision else 0,
+                                        int(max_round_windows), ctypes.byref(handle)),
+              'dbh_live_create')
+        self.handle = handle.value
+
+    def push_packed(self, channels, offsets, samples, flags):
+        """``dbh_live_push`` as it is: int32 channels [n], int64 offsets [n + 1] into int16
+        ``samples``, uint32 flags [n] -> LIVE_RESULT [n]."""
+        channels = np.ascontiguousarray(channels, dtype=np.int32)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        samples = np.ascontiguousarray(samples, dtype=np.int16)
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        n = len(channels)
+        if len(offsets) != n + 1 or len(flags) != n or (n and offsets[-1] > len(samples)):
+            raise ValueError('one offset more than channels, one flag per channel')
+        if samples.size == 0:
+            samples = np.zeros(1, dtype=np.int16)           # (a pointer, whatever the chunks hold)
+        results = np.zeros(n, dtype=LIVE_RESULT)
+        check(self._lib.dbh_live_push(self.handle, channels.ctypes.data, offsets.ctypes.data,
+                                      samples.ctypes.data, flags.ctypes.data, results.ctypes.data,
+                                      n), 'dbh_live_push')
+        return results
+
+    def push(self, channels, chunks, begin=None, end=None):
+        """One chunk of int16 signal per channel named (each channel at most once) -> LIVE_RESULT
+        [n].  ``begin``: a new read starts with this chunk; ``end``: the read ends with it (one
+        truth value, or one per chunk).  Chunks may be empty."""
+        chunks = [np.ascontiguousarray(chunk, dtype=np.int16).reshape(-1) for chunk in chunks]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.int64)
+        np.cumsum([len(chunk) for chunk in chunks], out=offsets[1:])
+        samples = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
+        return self.push_packed(channels, offsets, samples,
+                                live_chunk_flags(len(chunks), begin, end))
+
+    def track(self, channel):
+        """(best int32 [windows], margin float64 [windows]) of the channel's read so far: entry k
+        is what a run at scan size (k + 1) * input_size / 2 would say."""
+        best = np.zeros(max(self.steps, 1), dtype=np.int32)
+        margin = np.zeros(max(self.steps, 1), dtype=np.float64)
+        windows = ctypes.c_int32(0)
+        check(self._lib.dbh_live_track(self.handle, int(channel), best.ctypes.data,
+                                       margin.ctypes.data, ctypes.byref(windows)), 'dbh_live_track')
+        return best[:windows.value].copy(), margin[:windows.value].copy()
+
+
+def live_fold(model, window_probs, counts, steps, merged=None, state=None, score_diff=0.5,
+              min_windows=1, stop_on_decision=False):
+    """The resumable fold alone (``dbh_live_fold_dev``; parity tests): ``window_probs`` float32
+    [sum of counts, C] holds, channel after channel, the ``counts[i]`` windows that come next for
+    channel i; ``merged`` float32 [N, C] and ``state`` LIVE_RESULT [N] are what an earlier call gave
+    back (None: nothing folded yet).  -> (merged, state, best int32 [N, steps], margin float64
+    [N, steps]); of best and margin only the entries of the windows folded here are written."""
+    counts = np.asarray(counts, dtype=np.int64)
+    n, n_classes = len(counts), model.n_classes
+    window_probs = np.ascontiguousarray(window_probs, dtype=np.float32).reshape(-1, n_classes)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    if offsets[-1] != len(window_probs):
+        raise ValueError('window_probs must hold the sum of counts windows')
+    merged = np.zeros((n, n_classes), np.float32) if merged is None else \
+        np.ascontiguousarray(merged, dtype=np.float32)
+    if state is None:
+        state = np.zeros(n, dtype=LIVE_RESULT)
+        state['final_call'] = -1
+        state['status'] = LIVE_PENDING
+    state = np.ascontiguousarray(state, dtype=LIVE_RESULT)
+    best = np.zeros((n, int(steps)), dtype=np.int32)
+    margin = np.zeros((n, int(steps)), dtype=np.float64)
+    probs = window_probs if len(window_probs) else np.zeros((1, n_classes), np.float32)
+    with device_arrays(probs, offsets, merged, state, best, margin) as \
+            (d_probs, d_offsets, d_merged, d_state, d_best, d_margin):
+        check(load_library().dbh_live_fold_dev(
+            model.handle, d_probs.ptr, d_offsets.ptr, n, len(window_probs), int(steps),
+            float(score_diff), int(min_windows), LIVE_STOP_ON_DECISION if stop_on_decision else 0,
+            d_merged.ptr, d_state.ptr, d_best.ptr, d_margin.ptr, None), 'dbh_live_fold_dev')
+        synchronize()
+        return (d_merged.download(merged.shape, np.float32), d_state.download((n,), LIVE_RESULT),
+                d_best.download(best.shape, np.int32), d_margin.download(margin.shape, np.float64))
+
+
+def live_plan_host(input_size, scan_size, lengths, flags, track_best, track_margin, score_diff=0.5,
+                   min_windows=1, stop_on_decision=False):
+    """One channel's planning and decision rules on the host (``dbh_live_plan_host``, the lines the
+    kernels compile): pushes of ``lengths[i]`` samples with chunk ``flags[i]``, window k folding to
+    (track_best[k], track_margin[k]) -> (LIVE_RESULT [n], the record behind each push; int32 [n],
+    the windows each push made ready)."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    half = int(input_size) // 2
+    steps = max(int(scan_size) // half if half else 0, 1)
+    track_best = np.ascontiguousarray(track_best, dtype=np.int32)
+    track_margin = np.ascontiguousarray(track_margin, dtype=np.float64)
+    if len(flags) != len(lengths) or len(track_best) < steps or len(track_margin) < steps:
+        raise ValueError('one flag per length, a track of scan_size / (input_size / 2) windows')
+    results = np.zeros(len(lengths), dtype=LIVE_RESULT)
+    new_windows = np.zeros(len(lengths), dtype=np.int32)
+    check(load_library().dbh_live_plan_host(
+        int(input_size), int(scan_size), float(score_diff), int(min_windows),
+        LIVE_STOP_ON_DECISION if stop_on_decision else 0, lengths.ctypes.data, flags.ctypes.data,
+        len(lengths), track_best.ctypes.data, track_margin.ctypes.data, results.ctypes.data,
+        new_windows.ctypes.data), 'dbh_live_plan_host')
+    return results, new_windows

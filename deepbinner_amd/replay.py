@@ -1,0 +1,157 @@
+"""
+The ``replay`` command: play recorded reads back as a sequencer would deliver them and call each
+read's barcode WHILE its signal arrives.  Not a command of the reference, whose every entry takes
+whole reads: ``classify`` starts when the read has left the pore and its file is written.  Barcode-
+aware adaptive sampling - eject a read, balance a barcode - has to decide from the first second of
+signal, while the molecule is still in the pore.
+
+``--channels`` reads are in flight at a time, one per channel of a live session
+(``hip_backend.LiveSession``: include/deepbinner_hip.h, "live").  Each round pushes the next
+``--chunk_samples`` samples (1600: 0.4 s at 4 kHz) of every open read; a read's last chunk carries
+END, and the channel then begins the next read in file order.  The session runs every window that
+became complete through the start model and folds it; a read is DECIDED at the first window, from
+``--min_windows`` on, whose best class is a barcode leading by ``--score_diff``, and FINAL when all
+``--scan_size`` samples' windows are in - what ``classify`` with the start model alone calls.
+
+One row per read, in file order: ``read_ID``, ``live_call``, ``decided_windows``,
+``decided_samples`` (how much of the read had arrived at the push that decided; ``-`` where nothing
+decided), ``final_call`` (``-`` under ``--stop_on_decision`` when the read never became FINAL),
+``samples`` and ``agree`` (``yes`` / ``no``; ``-`` where either call is missing).  A summary goes to
+stderr.  An early call can differ from the final one by construction - a later window may raise
+another barcode - and ``agree`` is there to choose ``--min_windows`` and ``--score_diff`` by.  All of
+this is what the network says on prefixes of recorded reads; nothing has been checked on a
+sequencer.
+
+Only the start model is used: the end of a read is not known while it arrives.  ``-e`` alone is
+refused, a preset's end model is ignored.  ``replay(args, backend=None)`` takes its device entries as
+a parameter, so that the loop and the table also run against a host stand-in
+(tests/live_reference.py).  ``--devices``: a replay runs on one GPU; a value above 1 is refused.
+"""
+import sys
+
+import numpy as np
+
+KEEP_ALL = 1 << 40              # samples per read end the loaders keep: every read whole
+NO_TRAINING_DATA = ('Error: a training-data file cannot be replayed - its samples are one window '
+                    'long, not reads that arrive')
+NO_START_MODEL = ('Error: replay needs a start model (-s, --native or --rapid) - the end of a read '
+                  'is not known while it arrives')
+HEADER = ['read_ID', 'live_call', 'decided_windows', 'decided_samples', 'final_call', 'samples',
+          'agree']
+
+
+def reads_in_file_order(units, sweep):
+    """(read id, int16 signal) of every read of every unit, as the loaders give them."""
+    for unit in units:
+        if hasattr(unit, 'samples'):
+            samples, offsets = unit.samples, unit.offsets
+        else:
+            samples, offsets = sweep.pack(unit.signals, KEEP_ALL)
+        for r, read_id in enumerate(unit.ids):
+            yield read_id, np.asarray(samples[offsets[r]:offsets[r + 1]], dtype=np.int16)
+
+
+def result_row(read_id, result, backend, call_name):
+    """A read's last record as the table's row, and (decided, agrees or None) for the summary."""
+    decided = int(result['decided_windows']) > 0
+    final = int(result['status']) == backend.LIVE_FINAL
+    agree = (int(result['call']) == int(result['final_call'])) if decided and final else None
+    row = [read_id,
+           call_name(int(result['call'])) if decided else 'none',
+           str(int(result['decided_windows'])) if decided else '-',
+           str(int(result['decided_samples'])) if decided else '-',
+           call_name(int(result['final_call'])) if final else '-',
+           str(int(result['samples'])),
+           '-' if agree is None else ('yes' if agree else 'no')]
+    return row, decided, agree
+
+
+def replay(args, backend=None):
+    from . import classify, sweep
+    if backend is None:
+        from . import hip_backend as backend
+    if int(getattr(args, 'devices', 0) or 0) > 1:
+        sys.exit('Error: a replay runs on one GPU (--devices {} is not supported)'
+                 .format(args.devices))
+    if args.start_model is None:
+        sys.exit(NO_START_MODEL)
+    if args.channels < 1 or args.channels > 16384:
+        sys.exit('Error: --channels must be from 1 to 16384')
+    if args.chunk_samples < 1:
+        sys.exit('Error: --chunk_samples must be at least 1')
+    if args.min_windows < 1:
+        sys.exit('Error: --min_windows must be at least 1')
+    kind = classify.determine_input_type(args.input)
+    if kind == 'training_data':
+        sys.exit(NO_TRAINING_DATA)
+    classify.set_tensorflow_threads(args)
+    model, size, _, _, n_classes, _ = classify.load_and_check_models(args.start_model, None,
+                                                                     args.scan_size)
+    scan_size = int(args.scan_size)
+    if args.min_windows > scan_size // (size // 2):
+        sys.exit('Error: --min_windows cannot be more than the {} windows of --scan_size'
+                 .format(scan_size // (size // 2)))
+    fast5s = (classify.find_all_fast5s(args.input, verbose=True) if kind == 'directory'
+              else [args.input])
+    units = sweep.fast5_units(fast5s, args, classify, KEEP_ALL, (size, None), n_classes,
+                              command='replay')
+    reads = enumerate(reads_in_file_order(units, sweep))
+    print('', file=sys.stderr)
+    print('\t'.join(HEADER))
+
+    session = backend.LiveSession(model, args.channels, scan_size=scan_size,
+                                  score_diff=args.score_diff, min_windows=args.min_windows,
+                                  stop_on_decision=bool(args.stop_on_decision))
+    slots = [None] * args.channels              # per channel: [read number, id, signal, position]
+    rows, printed = {}, 0                       # finished rows that wait for their turn
+    decided_samples, n_reads, n_agree, n_compared, n_late, n_never = [], 0, 0, 0, 0, 0
+    exhausted = False
+    try:
+        while True:
+            for ch in range(args.channels):
+                if slots[ch] is None and not exhausted:
+                    nxt = next(reads, None)
+                    if nxt is None:
+                        exhausted = True
+                    else:
+                        slots[ch] = [nxt[0], nxt[1][0], nxt[1][1], 0]
+            active = [ch for ch in range(args.channels) if slots[ch] is not None]
+            if not active:
+                break
+            chunks, begin, end = [], [], []
+            for ch in active:
+                _, _, signal, at = slots[ch]
+                chunks.append(signal[at:at + args.chunk_samples])
+                begin.append(at == 0)
+                end.append(at + args.chunk_samples >= len(signal))
+                slots[ch][3] = at + args.chunk_samples
+            results = session.push(active, chunks, begin=begin, end=end)
+            for ch, result, last in zip(active, results, end):
+                if not last:
+                    continue
+                number, read_id = slots[ch][0], slots[ch][1]
+                row, decided, agree = result_row(read_id, result, backend, classify.call_name)
+                rows[number] = row
+                slots[ch] = None
+                n_reads += 1
+                if decided:
+                    decided_samples.append(int(result['decided_samples']))
+                    n_late += int(result['decided_windows']) > args.min_windows
+                else:
+                    n_never += 1
+                if agree is not None:
+                    n_compared += 1
+                    n_agree += bool(agree)
+            while printed in rows:
+                print('\t'.join(rows.pop(printed)))
+                printed += 1
+    finally:
+        session.close()
+    print('{} reads, {} decided'.format(n_reads, len(decided_samples)), file=sys.stderr)
+    if decided_samples:
+        print('  decided_samples: median {}, maximum {}'.format(
+            int(np.median(decided_samples)), max(decided_samples)), file=sys.stderr)
+    print('  live call agrees with the final call: {} of {}'.format(n_agree, n_compared),
+          file=sys.stderr)
+    print('  decided later than window {}: {}, never: {}'.format(args.min_windows, n_late, n_never),
+          file=sys.stderr)

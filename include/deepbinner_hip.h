@@ -534,6 +534,100 @@ int dbh_locate_occluded_i16(dbh_model* model, const int16_t* samples_host,
                             double score_diff, float* probs_host, int32_t* calls_host,
                             dbh_location* locations_host, dbh_occlusion* occlusions_host);
 
+/* ---- live: each read's barcode called while its signal arrives --------------------------------- */
+/* Every entry above takes whole reads.  A live session keeps, per sequencer channel, the signal
+ * received so far and the fold over the windows that are already complete, so a caller can act on a
+ * barcode while the molecule is still in the pore.  Window s of the start side is the same samples
+ * whatever comes after it (classify.py:337-349) and the merge is a running min / max
+ * (classify.py:368-374), so the merged vector after k windows is what a run at scan_size = k h
+ * merges ("sweep", above): the session is that fold, stopped after the windows a push made ready
+ * and taken up again at the next.  Checked against the network's answers on prefixes of recorded
+ * reads, not on a sequencer; an early call can differ from the final one by construction.
+ *
+ * L = the model's input size, h = L / 2, steps = scan_size / h, cap = scan_size + h (the last
+ * window ends at (steps - 1) h + L = cap).
+ *   Session.  One model (persistent or general kind), side start only, 1 <= n_channels <= 16,384,
+ *       scan_size a positive multiple of h, 1 <= min_windows <= steps, flags 0 or
+ *       DBH_LIVE_STOP_ON_DECISION.  max_round_windows: how many windows one forward round holds,
+ *       0 = 64 MiB of fp32 input.  The session owns a stream, its device state and pinned memory.
+ *   State per channel, on the device: cap int16 samples; n, every sample received, kept or not;
+ *       open, ended, windows_done; the merged fp32 vector; the track best[steps] int32 and
+ *       margin[steps] fp64; the decision.
+ *   Push.  n_chunks chunks, chunk i for channels[i] (each channel at most once per push) with the
+ *       samples [offsets[i], offsets[i + 1]) and flags[i] of DBH_LIVE_BEGIN | DBH_LIVE_END.  Per
+ *       chunk, in this order: BEGIN resets the channel and opens a read; the samples are appended
+ *       (n grows by the chunk's length, samples are stored only up to cap); END sets ended and
+ *       closes the read.  A chunk for a channel with no read open and no BEGIN changes nothing and
+ *       reports DBH_LIVE_IDLE.  A channel that is FINAL, or DECIDED under STOP_ON_DECISION, counts
+ *       n on but stores and runs nothing more.
+ *   Ready.  Window k < steps is ready when k h + L <= n, or when the read has ended (then every
+ *       k < steps is: call_batch's short and empty windows).  Its samples are
+ *       [min(k h, n), min(k h + L, n)), normalised over the samples present by the scan's front
+ *       rule ("scan", above: int64 S and Q, exact D, one fp64 expression per value) and
+ *       zero-padded behind.  The windows a push made ready, windows_done .. ready - 1 per channel,
+ *       go through what dbh_predict_dev launches, in rounds of at most max_round_windows, and are
+ *       folded in order of k: the sweep's fold step, in the form of the model's kind.  (best,
+ *       margin) after each window goes into the track.
+ *   Decision.  The first k with k + 1 >= min_windows && best != 0 && margin >= score_diff decides:
+ *       call = that best, decided_windows = k + 1, decided_samples = n; the call never changes.
+ *       Under STOP_ON_DECISION the fold stops behind that window.  windows_done == steps makes the
+ *       channel FINAL with final_call = best != 0 && margin >= score_diff ? best : 0.
+ *   Result.  dbh_live_result, 48 bytes, one per chunk: the channel's record behind the push (for an
+ *       IDLE chunk the record as it stands, with status DBH_LIVE_IDLE).
+ * dbh_live_push takes host buffers and blocks once, at its end.  dbh_live_track copies a channel's
+ * track to the host (best / margin hold steps entries; *windows of them are valid).
+ * dbh_live_fold_dev is the resumable fold alone, for parity tests: window_probs_dev
+ * [window_offsets[n_channels]][n_classes] fp32 holds, for channel i, the windows
+ * [window_offsets_dev[i], window_offsets_dev[i + 1]) (int64, on the device) that come next;
+ * merged_dev [n_channels][n_classes] and state_dev [n_channels] (windows = done, samples as the
+ * caller has them) go in and out, best_dev / margin_dev [n_channels][steps] get the new entries.
+ * dbh_live_plan_host runs ONE channel's rules on the host (dbh_live_core.h, what the kernels
+ * compile): n_chunks pushes of lengths[i] samples with chunk_flags[i], window k folding to
+ * (track_best[k], track_margin[k]) -> results_host[i], the record behind push i, and
+ * new_windows_host[i] (may be NULL), the windows that push made ready.
+ * Every entry checks its arguments before any device work and changes no state on error: a null
+ * pointer, n_chunks < 0, a channel outside the session or twice in one push, offsets that run
+ * backwards, unknown flag bits, the limits of creation: DBH_ERR_INVALID_ARGUMENT.  n_chunks == 0 is
+ * DBH_OK. */
+typedef struct dbh_live_session dbh_live_session;
+#define DBH_LIVE_STOP_ON_DECISION 1      /* session flag */
+#define DBH_LIVE_BEGIN 1                 /* chunk flags */
+#define DBH_LIVE_END 2
+#define DBH_LIVE_IDLE 0                  /* status */
+#define DBH_LIVE_PENDING 1
+#define DBH_LIVE_DECIDED 2
+#define DBH_LIVE_FINAL 3
+#define DBH_LIVE_MAX_CHANNELS 16384
+typedef struct dbh_live_result {
+    int32_t status;             /* DBH_LIVE_IDLE .. DBH_LIVE_FINAL */
+    int32_t call;               /* 0 until decided */
+    int32_t final_call;         /* -1 until FINAL */
+    int32_t windows;            /* windows folded: windows_done */
+    int32_t decided_windows;    /* 0 until decided */
+    int32_t best;               /* of the last window folded */
+    double margin;              /* of the last window folded */
+    int64_t samples;            /* n */
+    int64_t decided_samples;    /* n at the push that decided */
+} dbh_live_result;
+int dbh_live_create(dbh_model* model, int n_channels, int scan_size, double score_diff,
+                    int min_windows, uint32_t flags, int64_t max_round_windows,
+                    dbh_live_session** session);
+int dbh_live_destroy(dbh_live_session* session);
+int dbh_live_push(dbh_live_session* session, const int32_t* channels, const int64_t* offsets,
+                  const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+                  int64_t n_chunks);
+int dbh_live_track(dbh_live_session* session, int channel, int32_t* best, double* margin,
+                   int32_t* windows);
+int dbh_live_fold_dev(const dbh_model* model, const float* window_probs_dev,
+                      const int64_t* window_offsets_dev, int64_t n_channels, int64_t n_windows,
+                      int steps, double score_diff, int min_windows, uint32_t flags,
+                      float* merged_dev, dbh_live_result* state_dev, int32_t* best_dev,
+                      double* margin_dev, dbh_stream stream);
+int dbh_live_plan_host(int input_size, int scan_size, double score_diff, int min_windows,
+                       uint32_t flags, const int64_t* lengths, const uint32_t* chunk_flags,
+                       int64_t n_chunks, const int32_t* track_best, const double* track_margin,
+                       dbh_live_result* results_host, int32_t* new_windows_host);
+
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's
  * inflate() over every chunk on the host.  Here the loader may hand over the chunks AS STORED

@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""What a live session's push costs, in one process on one GPU: the shipped
+start model (persistent kind), `--channels` channels (512, then 3,000) each playing reads cut from
+the seven golden reads plus noise, 1,600 samples (0.4 s at 4 kHz) per channel and round; a read of
+6,000 to 20,000 samples ends with END and the channel begins the next one.
+
+  push          LiveSession.push_packed: staging, append, window list, front, forward rounds, fold,
+                results, one synchronise - the wall time of the call
+  reclassify    the only alternative without a session: HipModel.classify_packed over every open
+                channel's accumulated prefix, at the largest scan size (a multiple of half the input
+                size, at most 6,144) not above the prefix; one call per scan size.  Channels whose
+                prefix already covered scan size + half a window a round earlier are left out (their
+                call cannot change any more), and the packing of the prefixes is not timed.
+
+Both are timed in the same loop, alternating, on the same reads: `--pushes` (200) rounds after a
+warm-up of `--warmup` (40) rounds, which is longer than the longest read and so covers every shape;
+`--repeats` (3) times over.  Per repeat the median and the 99th percentile of a push's wall time,
+the windows per push, the kernel launches per push as counted from the code (append, list and
+results once; front, forward and fold per forward round; two copies beside them), and the same for
+the alternative.  A record, not a bound.
+
+    python tools/live_rate.py [--channels 512,3000] [--pushes 200] [--out profiles/live/rate.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+CHUNK, SCAN, SIZE = 1600, 6144, 1024
+CAP = SCAN + SIZE // 2
+
+
+def percentiles(seconds):
+    s = np.sort(np.asarray(seconds))
+    return {'median_ms': 1e3 * float(s[len(s) // 2]),
+            'p99_ms': 1e3 * float(s[min(len(s) - 1, int(np.ceil(0.99 * len(s))) - 1)]),
+            'max_ms': 1e3 * float(s[-1])}
+
+
+class Player:
+    """The channels' reads: each one a golden read's start, carried on by its own samples again,
+    plus a little noise; lengths 6,000 .. 20,000."""
+
+    def __init__(self, golden, n_channels, seed):
+        self.rng = np.random.default_rng(seed)
+        self.bases = [np.resize(g, 20000 + CHUNK).astype(np.int16) for g in golden]
+        self.noise = self.rng.integers(-3, 4, 1 << 22).astype(np.int16)
+        self.n = n_channels
+        self.base = np.zeros(n_channels, np.int64)
+        self.length = np.zeros(n_channels, np.int64)
+        self.at = np.zeros(n_channels, np.int64)
+        for ch in range(n_channels):
+            self.begin(ch)
+            self.at[ch] = -int(self.rng.integers(0, 8)) * CHUNK      # the channels out of step
+        self.prefix = np.zeros((n_channels, CAP), np.int16)
+
+    def begin(self, ch):
+        self.base[ch] = self.rng.integers(0, len(self.bases))
+        self.length[ch] = self.rng.integers(6000, 20001)
+        self.at[ch] = 0
+
+    def round(self):
+        """-> (channels, offsets, samples, flags) of the next push; keeps every prefix up to date"""
+        channels, parts, flags = [], [], []
+        for ch in range(self.n):
+            at = int(self.at[ch])
+            if at < 0:                                  # this channel has not begun yet
+                self.at[ch] = at + CHUNK
+                continue
+            end = min(at + CHUNK, int(self.length[ch]))
+            shift = int(self.rng.integers(0, len(self.noise) - CHUNK))
+            part = self.bases[self.base[ch]][at:end] + self.noise[shift:shift + end - at]
+            if at < CAP:
+                self.prefix[ch, at:min(end, CAP)] = part[:max(0, min(end, CAP) - at)]
+            channels.append(ch)
+            parts.append(part)
+            flags.append((1 if at == 0 else 0) | (2 if end == self.length[ch] else 0))
+            self.at[ch] = end
+        offsets = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([len(p) for p in parts], out=offsets[1:])
+        return (np.array(channels, np.int32), offsets, np.concatenate(parts),
+                np.array(flags, np.uint32))
+
+    def finish(self, channels, flags):
+        for ch, f in zip(channels, flags):
+            if f & 2:
+                self.begin(int(ch))
+
+    def prefixes(self, channels):
+        """The alternative's work this round: {scan size: (samples, offsets)} over the channels
+        whose prefix holds half a window at least and had not covered CAP a round earlier."""
+        groups = {}
+        for ch in channels:
+            n = int(self.at[ch])
+            if n < SIZE // 2 or n - CHUNK >= CAP:
+                continue
+            scan = min(SCAN, n // (SIZE // 2) * (SIZE // 2))
+            groups.setdefault(scan, []).append(self.prefix[ch, :min(n, CAP)])
+        packed = {}
+        for scan, parts in groups.items():
+            offsets = np.zeros(len(parts) + 1, np.int64)
+            np.cumsum([len(p) for p in parts], out=offsets[1:])
+            packed[scan] = (np.concatenate(parts), offsets)
+        return packed
+
+
+def measure(hb, model, golden, n_channels, opts, seed):
+    player = Player(golden, n_channels, seed)
+    push_s, alt_s, windows, rounds, alt_windows, alt_calls = [], [], [], [], [], []
+    with hb.LiveSession(model, n_channels, scan_size=SCAN) as session:
+        round_windows = min(n_channels * 12, (64 << 20) // (SIZE * 4))
+        before = np.zeros(n_channels, np.int64)
+        for r in range(opts.warmup + opts.pushes):
+            channels, offsets, samples, flags = player.round()
+            t0 = time.perf_counter()
+            results = session.push_packed(channels, offsets, samples, flags)
+            t1 = time.perf_counter()
+            packed = player.prefixes(channels)
+            t2 = time.perf_counter()
+            for scan, (s, o) in packed.items():
+                model.classify_packed(s, o, 'start', scan, 0.5)
+            t3 = time.perf_counter()
+            new = int((results['windows'] - np.where(flags & 1, 0, before[channels])).sum())
+            before[channels] = results['windows']
+            player.finish(channels, flags)
+            if r >= opts.warmup:
+                push_s.append(t1 - t0)
+                alt_s.append(t3 - t2)
+                windows.append(new)
+                rounds.append(-(-new // round_windows))
+                alt_windows.append(sum((len(o) - 1) * (scan // (SIZE // 2))
+                                       for scan, (_, o) in packed.items()))
+                alt_calls.append(len(packed))
+    return {
+        'pushes': len(push_s), 'push': percentiles(push_s), 'reclassify': percentiles(alt_s),
+        'windows_per_push': {'mean': float(np.mean(windows)), 'max': int(np.max(windows))},
+        'kernel_launches_per_push': {'mean': float(np.mean([3 + 3 * k for k in rounds])),
+                                     'max': int(max(3 + 3 * k for k in rounds)), 'copies': 2},
+        'reclassify_windows_per_round': {'mean': float(np.mean(alt_windows)),
+                                         'max': int(np.max(alt_windows))},
+        'reclassify_calls_per_round': float(np.mean(alt_calls)),
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
+    ap.add_argument('--channels', type=str, default='512,3000')
+    ap.add_argument('--pushes', type=int, default=200)
+    ap.add_argument('--warmup', type=int, default=40)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--out', type=str, default=None)
+    opts = ap.parse_args()
+    from deepbinner_amd import hip_backend as hb
+    from deepbinner_amd.model_format import ModelWeights
+    assert hb.device_count() >= 1, 'no HIP device visible'
+    weights = ModelWeights.load(os.path.join(REPO, 'deepbinner_amd', 'models',
+                                             'EXP-NBD103_read_starts.dbw'))[0]
+    model = hb.HipModel(weights, device=0)
+    reads = np.load(os.path.join(REPO, 'tests', 'golden', 'reads.npz'))
+    golden = [reads['samples'][reads['offsets'][i]:reads['offsets'][i + 1]] for i in range(7)]
+    record = {'device': hb.device_name(0), 'model': 'EXP-NBD103_read_starts, persistent kind',
+              'chunk_samples': CHUNK, 'chunk_period_ms': 400.0, 'scan_size': SCAN,
+              'warmup_pushes': opts.warmup, 'channels': {}}
+    for n_channels in [int(v) for v in opts.channels.split(',')]:
+        repeats = [measure(hb, model, golden, n_channels, opts, seed=100 * n_channels + k)
+                   for k in range(opts.repeats)]
+        medians = sorted(rep['push']['median_ms'] for rep in repeats)
+        alt = sorted(rep['reclassify']['median_ms'] for rep in repeats)
+        record['channels'][str(n_channels)] = {
+            'repeats': repeats,
+            'push_median_ms': {'median': medians[len(medians) // 2], 'min': medians[0],
+                               'max': medians[-1]},
+            'reclassify_median_ms': {'median': alt[len(alt) // 2], 'min': alt[0], 'max': alt[-1]},
+            'reclassify_over_push': alt[len(alt) // 2] / medians[len(medians) // 2],
+            'push_share_of_chunk_period': medians[len(medians) // 2] / 400.0,
+        }
+    text = json.dumps(record, indent=1)
+    print(text, flush=True)
+    if opts.out:
+        os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
+        with open(opts.out, 'w') as f:
+            f.write(text + '\n')
+
+
+if __name__ == '__main__':
+    main()
