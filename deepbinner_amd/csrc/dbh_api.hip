@@ -1687,14 +1687,108 @@ struct dbh_live_session {
     int64_t* d_win_offsets = nullptr;
     float *d_x = nullptr, *d_probs = nullptr;
     dbh_live_result* d_results = nullptr;
+    dbh_live_end_result* d_end_results = nullptr;
     std::vector<dbh_live_result> rec;          // the mirror
     std::vector<dbh_live::Gate> gate;
     std::vector<int64_t> seen;                 // the push that last named the channel
     int64_t pushes = 0;
+    // a pair session (dbh_live_create_pair; pair.ring null: start only): the end model, the rings
+    // and the end fold's state, its forward rounds, and per channel whether the end track stands
+    dbh_model* end_model = nullptr;
+    dbh_live::Pair pair{};
+    int64_t end_round_windows = 0;
+    std::vector<char> end_done;
 };
 
 namespace {
 bool live_fold_general(const dbh_model* m) { return m->kind == DBH_MODEL_KIND_GENERAL; }
+
+// a forward round: what the caller said, else 64 MiB of fp32 input; never more than all windows
+int64_t live_round_windows(int64_t all, int L, int64_t max_round_windows) {
+    const int64_t by_default = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)L * 4));
+    return std::min(all, max_round_windows > 0 ? max_round_windows : by_default);
+}
+
+// dbh_live_create (end null) and dbh_live_create_pair
+int live_create(dbh_model* m, dbh_model* end, int n_channels, int scan_size, double score_diff,
+                int min_windows, uint32_t flags, int combine_mode, int64_t max_round_windows,
+                dbh_live_session** session) {
+    const dbh_live::Shape shape =
+        dbh_live::shape_of(m->input_size, scan_size, score_diff, min_windows, flags);
+    if (!dbh_live::shape_ok(shape, scan_size)) return DBH_ERR_INVALID_ARGUMENT;
+    dbh_live::Shape end_shape{};
+    if (end) {
+        end_shape = dbh_live::shape_of(end->input_size, scan_size, score_diff, 1, 0);
+        if (!dbh_live::shape_ok(end_shape, scan_size)) return DBH_ERR_INVALID_ARGUMENT;
+    }
+    DBH_HIP(hipSetDevice(m->device));
+    std::unique_ptr<dbh_live_session> s(new (std::nothrow) dbh_live_session);
+    if (!s) return DBH_ERR_OUT_OF_MEMORY;
+    s->model = m;
+    s->end_model = end;
+    s->n_channels = n_channels;
+    s->shape = shape;
+    const int L = shape.L, C = m->n_classes, steps = shape.steps;
+    s->round_windows = live_round_windows((int64_t)n_channels * steps, L, max_round_windows);
+    const int Le = end_shape.L, steps_e = end_shape.steps;
+    if (end)
+        s->end_round_windows =
+            live_round_windows((int64_t)n_channels * steps_e, Le, max_round_windows);
+    DBH_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
+    const size_t n = (size_t)n_channels;
+    s->st.stride = (shape.cap + 7) & ~(long long)7;
+    s->st.n_classes = C;
+    dbh_live::Pair& pair = s->pair;
+    pair.shape = end_shape;
+    pair.stride = (end_shape.cap + 7) & ~(long long)7;
+    pair.combine_mode = combine_mode;
+    pair.end.n_classes = C;
+    DBH_HIP(s->state_block.carve([&](dbh_host::Carve& c) {
+        s->st.samples = c.take<int16_t>(n * (size_t)s->st.stride);
+        s->st.rec = c.take<dbh_live_result>(n);
+        s->st.gate = c.take<dbh_live::Gate>(n);
+        s->st.merged = c.take<float>(n * C);
+        s->st.best = c.take<int32_t>(n * steps);
+        s->st.margin = c.take<double>(n * steps);
+        if (end) {
+            pair.ring = c.take<int16_t>(n * (size_t)pair.stride);
+            pair.end.rec = c.take<dbh_live_result>(n);
+            pair.end.merged = c.take<float>(n * C);
+            pair.end.best = c.take<int32_t>(n * steps_e);
+            pair.end.margin = c.take<double>(n * steps_e);
+        }
+    }));
+    // one x and one probs serve both sides' rounds, which run one after the other
+    const size_t x_floats = std::max((size_t)s->round_windows * L, (size_t)s->end_round_windows * Le);
+    const size_t p_floats = (size_t)std::max(s->round_windows, s->end_round_windows) * C;
+    DBH_HIP(s->push_block.carve([&](dbh_host::Carve& c) {
+        s->d_first = c.take<int32_t>(n);
+        s->d_count = c.take<int32_t>(n);
+        s->d_win_offsets = c.take<int64_t>(n + 1);
+        s->d_results = c.take<dbh_live_result>(n);
+        if (end) s->d_end_results = c.take<dbh_live_end_result>(n);
+        s->d_x = c.take<float>(x_floats);
+        s->d_probs = c.take<float>(p_floats);
+    }));
+    DBH_HIP(s->h_out.reserve(n * (sizeof(dbh_live_result) + sizeof(dbh_live_end_result))));
+    s->rec.assign(n, dbh_live::fresh_record());
+    s->gate.assign(n, dbh_live::Gate{0, 0});
+    s->seen.assign(n, -1);
+    s->end_done.assign(n, 0);
+    DBH_HIP(hipMemcpyAsync(s->st.rec, s->rec.data(), n * sizeof(dbh_live_result),
+                           hipMemcpyHostToDevice, s->stream));
+    DBH_HIP(hipMemsetAsync(s->st.gate, 0, n * sizeof(dbh_live::Gate), s->stream));
+    if (end)
+        DBH_HIP(hipMemcpyAsync(pair.end.rec, s->rec.data(), n * sizeof(dbh_live_result),
+                               hipMemcpyHostToDevice, s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    *session = s.release();
+    return DBH_OK;
+}
+
+int live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
+              const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+              dbh_live_end_result* end_results, int64_t n_chunks);
 }  // namespace
 
 extern "C" {
@@ -1705,50 +1799,22 @@ int dbh_live_create(dbh_model* m, int n_channels, int scan_size, double score_di
     if (!m || !session || n_channels < 1 || n_channels > DBH_LIVE_MAX_CHANNELS ||
         max_round_windows < 0)
         return DBH_ERR_INVALID_ARGUMENT;
-    const dbh_live::Shape shape =
-        dbh_live::shape_of(m->input_size, scan_size, score_diff, min_windows, flags);
-    if (!dbh_live::shape_ok(shape, scan_size)) return DBH_ERR_INVALID_ARGUMENT;
-    DBH_HIP(hipSetDevice(m->device));
-    std::unique_ptr<dbh_live_session> s(new (std::nothrow) dbh_live_session);
-    if (!s) return DBH_ERR_OUT_OF_MEMORY;
-    s->model = m;
-    s->n_channels = n_channels;
-    s->shape = shape;
-    const int L = shape.L, C = m->n_classes, steps = shape.steps;
-    const int64_t all = (int64_t)n_channels * steps;
-    // a forward round: what the caller said, else 64 MiB of fp32 input; never more than all windows
-    const int64_t by_default = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)L * 4));
-    s->round_windows = std::min(all, max_round_windows > 0 ? max_round_windows : by_default);
-    DBH_HIP(hipStreamCreateWithFlags(&s->stream.h, hipStreamNonBlocking));
-    const size_t n = (size_t)n_channels;
-    s->st.stride = (shape.cap + 7) & ~(long long)7;
-    s->st.n_classes = C;
-    DBH_HIP(s->state_block.carve([&](dbh_host::Carve& c) {
-        s->st.samples = c.take<int16_t>(n * (size_t)s->st.stride);
-        s->st.rec = c.take<dbh_live_result>(n);
-        s->st.gate = c.take<dbh_live::Gate>(n);
-        s->st.merged = c.take<float>(n * C);
-        s->st.best = c.take<int32_t>(n * steps);
-        s->st.margin = c.take<double>(n * steps);
-    }));
-    DBH_HIP(s->push_block.carve([&](dbh_host::Carve& c) {
-        s->d_first = c.take<int32_t>(n);
-        s->d_count = c.take<int32_t>(n);
-        s->d_win_offsets = c.take<int64_t>(n + 1);
-        s->d_results = c.take<dbh_live_result>(n);
-        s->d_x = c.take<float>((size_t)s->round_windows * L);
-        s->d_probs = c.take<float>((size_t)s->round_windows * C);
-    }));
-    DBH_HIP(s->h_out.reserve(n * sizeof(dbh_live_result)));
-    s->rec.assign(n, dbh_live::fresh_record());
-    s->gate.assign(n, dbh_live::Gate{0, 0});
-    s->seen.assign(n, -1);
-    DBH_HIP(hipMemcpyAsync(s->st.rec, s->rec.data(), n * sizeof(dbh_live_result),
-                           hipMemcpyHostToDevice, s->stream));
-    DBH_HIP(hipMemsetAsync(s->st.gate, 0, n * sizeof(dbh_live::Gate), s->stream));
-    DBH_HIP(hipStreamSynchronize(s->stream));
-    *session = s.release();
-    return DBH_OK;
+    return live_create(m, nullptr, n_channels, scan_size, score_diff, min_windows, flags,
+                       DBH_REQUIRE_EITHER, max_round_windows, session);
+}
+
+int dbh_live_create_pair(dbh_model* start_model, dbh_model* end_model, int n_channels,
+                         int scan_size, double score_diff, int min_windows, uint32_t flags,
+                         int combine_mode, int64_t max_round_windows,
+                         dbh_live_session** session) {
+    if (!start_model || !end_model || !session || n_channels < 1 ||
+        n_channels > DBH_LIVE_MAX_CHANNELS || max_round_windows < 0 ||
+        combine_mode < DBH_REQUIRE_EITHER || combine_mode > DBH_REQUIRE_BOTH)
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (start_model->device != end_model->device || start_model->n_classes != end_model->n_classes)
+        return DBH_ERR_INVALID_ARGUMENT;
+    return live_create(start_model, end_model, n_channels, scan_size, score_diff, min_windows,
+                       flags, combine_mode, max_round_windows, session);
 }
 
 int dbh_live_destroy(dbh_live_session* s) {
@@ -1759,6 +1825,22 @@ int dbh_live_destroy(dbh_live_session* s) {
 int dbh_live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
                   const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
                   int64_t n_chunks) {
+    return live_push(s, channels, offsets, samples, flags, results, nullptr, n_chunks);
+}
+
+int dbh_live_push_pair(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
+                       const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+                       dbh_live_end_result* end_results, int64_t n_chunks) {
+    if (s && end_results && !s->pair.ring) return DBH_ERR_INVALID_ARGUMENT;
+    return live_push(s, channels, offsets, samples, flags, results, end_results, n_chunks);
+}
+
+}  // extern "C"
+
+namespace {
+int live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
+              const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+              dbh_live_end_result* end_results, int64_t n_chunks) {
     if (!s || n_chunks < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_chunks == 0) return DBH_OK;
     if (!channels || !offsets || !samples || !flags || !results || n_chunks > s->n_channels)
@@ -1775,15 +1857,22 @@ int dbh_live_push(dbh_live_session* s, const int32_t* channels, const int64_t* o
     }
     s->pushes = push;
     const dbh_live::Shape& shape = s->shape;
+    const dbh_live::Pair& pair = s->pair;
+    const bool is_pair = pair.ring != nullptr;
     DBH_HIP(hipSetDevice(s->model->device));
     // the plan: the mirror's copy of every chunk's channel through append, the kept samples placed
-    // so that source and row are aligned alike (16-byte copies in the append kernel)
+    // so that source and row are aligned alike (16-byte copies in the append kernel).  A pair
+    // session's chunk is staged whole where the start side's samples and the ring's tail touch
+    // (a chunk no longer than cap_e); else the tail is a piece of its own, aligned like its place
+    // in the ring.
     const size_t n = (size_t)n_chunks;
     std::vector<dbh_live_result> rec(n);
     std::vector<dbh_live::Gate> gate(n);
     std::vector<dbh_live::Append> plan(n);
     std::vector<dbh_live::Chunk> chunks(n);
-    int64_t staged = 0, total_windows = 0;
+    std::vector<dbh_live::Tail> tails(is_pair ? n : 0);
+    std::vector<int64_t> end_offsets(is_pair ? n + 1 : 0);
+    int64_t staged = 0, total_windows = 0, end_windows = 0;
     for (size_t i = 0; i < n; ++i) {
         const size_t ch = (size_t)channels[i];
         rec[i] = s->rec[ch];
@@ -1791,27 +1880,54 @@ int dbh_live_push(dbh_live_session* s, const int32_t* channels, const int64_t* o
         const int64_t length = offsets[i + 1] - offsets[i];
         plan[i] = dbh_live::append(&rec[i], &gate[i], flags[i], length, shape);
         const int64_t at = staged + ((plan[i].at - staged) & 7);       // at % 8 == plan.at % 8
-        chunks[i] = dbh_live::Chunk{at, length, channels[i], flags[i]};
+        chunks[i] = dbh_live::Chunk{at, length, at, channels[i], flags[i]};
         staged = at + plan[i].keep;
         total_windows += plan[i].count;
+        if (!is_pair) continue;
+        end_offsets[i] = end_windows;
+        dbh_live::Tail& tail = tails[i];
+        tail = dbh_live::Tail{0, 0, 0, 0};
+        if (plan[i].idle) continue;
+        tail = dbh_live::tail_store(rec[i].samples - length, length, pair.shape);
+        if (plan[i].keep > 0 && tail.from <= plan[i].keep) {           // one piece: the whole chunk
+            chunks[i].tail = at + tail.from;
+            staged = at + length;
+        } else {                                                       // tail % 8 == tail.at % 8
+            chunks[i].tail = staged + ((tail.at - staged) & 7);
+            staged = chunks[i].tail + tail.keep;
+        }
+        if (flags[i] & DBH_LIVE_END) end_windows += pair.shape.steps;
     }
+    if (is_pair) end_offsets[n] = end_windows;
     const size_t table_bytes = align256(n * sizeof(dbh_live::Chunk));
-    const size_t in_bytes = table_bytes + align256((size_t)staged * sizeof(int16_t) + 16);
+    const size_t ends_bytes = is_pair ? align256((n + 1) * sizeof(int64_t)) : 0;
+    const size_t in_bytes =
+        table_bytes + ends_bytes + align256((size_t)staged * sizeof(int16_t) + 16);
     DBH_HIP(s->h_in.reserve(in_bytes));
     DBH_HIP(s->in_block.reserve(in_bytes));
     std::memcpy(s->h_in.get(), chunks.data(), n * sizeof(dbh_live::Chunk));
-    int16_t* h_samples = s->h_in.as<int16_t>(table_bytes);
-    for (size_t i = 0; i < n; ++i)
-        if (plan[i].keep > 0)
+    if (is_pair)
+        std::memcpy(s->h_in.as<char>(table_bytes), end_offsets.data(), (n + 1) * sizeof(int64_t));
+    int16_t* h_samples = s->h_in.as<int16_t>(table_bytes + ends_bytes);
+    for (size_t i = 0; i < n; ++i) {
+        const bool whole = is_pair && tails[i].keep > 0 && plan[i].keep > 0 &&
+                           tails[i].from <= plan[i].keep;
+        const int64_t head = whole ? offsets[i + 1] - offsets[i] : plan[i].keep;
+        if (head > 0)
             std::memcpy(h_samples + chunks[i].src, samples + offsets[i],
-                        (size_t)plan[i].keep * sizeof(int16_t));
+                        (size_t)head * sizeof(int16_t));
+        if (is_pair && !whole && tails[i].keep > 0)
+            std::memcpy(h_samples + chunks[i].tail, samples + offsets[i] + tails[i].from,
+                        (size_t)tails[i].keep * sizeof(int16_t));
+    }
     hipStream_t stream = s->stream;
     DBH_HIP(hipMemcpyAsync(s->in_block.get(), s->h_in.get(), in_bytes, hipMemcpyHostToDevice,
                            stream));
     const dbh_live::Chunk* d_chunks = s->in_block.as<dbh_live::Chunk>();
-    const int16_t* d_in = s->in_block.as<int16_t>(table_bytes);
-    DBH_HIP(dbh_live::append(s->st, shape, d_chunks, d_in, (int)n_chunks, s->d_first, s->d_count,
-                             stream));
+    const int64_t* d_end_offsets = s->in_block.as<int64_t>(table_bytes);
+    const int16_t* d_in = s->in_block.as<int16_t>(table_bytes + ends_bytes);
+    DBH_HIP(dbh_live::append(s->st, shape, pair, d_chunks, d_in, (int)n_chunks, s->d_first,
+                             s->d_count, stream));
     DBH_HIP(dbh_live::window_list(s->d_count, (int)n_chunks, s->d_win_offsets, stream));
     for (int64_t w0 = 0; w0 < total_windows; w0 += s->round_windows) {
         const int64_t cnt = std::min(s->round_windows, total_windows - w0);
@@ -1821,18 +1937,39 @@ int dbh_live_push(dbh_live_session* s, const int32_t* channels, const int64_t* o
         DBH_HIP(dbh_live::fold(live_fold_general(s->model), s->st, shape, d_chunks,
                                s->d_win_offsets, n_chunks, w0, cnt, s->d_probs, stream));
     }
-    DBH_HIP(dbh_live::results(s->st, d_chunks, s->d_first, (int)n_chunks, s->d_results, stream));
+    // the end side of the reads that ended with this push: behind the start side's folds, so that
+    // the end record combines with the start record as it stands at END
+    for (int64_t w0 = 0; w0 < end_windows; w0 += s->end_round_windows) {
+        const int64_t cnt = std::min(s->end_round_windows, end_windows - w0);
+        DBH_HIP(dbh_live::end_front(s->st, pair, d_chunks, d_end_offsets, (int)n_chunks, w0, cnt,
+                                    s->d_x, stream));
+        DBH_TRY(dbh_predict_dev(s->end_model, s->d_x, cnt, s->d_probs, (dbh_stream)stream));
+        DBH_HIP(dbh_live::fold(live_fold_general(s->end_model), pair.end, pair.shape, d_chunks,
+                               d_end_offsets, n_chunks, w0, cnt, s->d_probs, stream));
+    }
+    dbh_live_end_result* d_ends = end_results ? s->d_end_results : nullptr;
+    DBH_HIP(dbh_live::results(s->st, pair, d_chunks, s->d_first, (int)n_chunks, s->d_results, d_ends,
+                              stream));
     DBH_HIP(hipMemcpyAsync(s->h_out.get(), s->d_results, n * sizeof(dbh_live_result),
                            hipMemcpyDeviceToHost, stream));
+    dbh_live_end_result* h_ends = s->h_out.as<dbh_live_end_result>(n * sizeof(dbh_live_result));
+    if (d_ends)
+        DBH_HIP(hipMemcpyAsync(h_ends, d_ends, n * sizeof(dbh_live_end_result),
+                               hipMemcpyDeviceToHost, stream));
     DBH_HIP(hipStreamSynchronize(stream));
     std::memcpy(results, s->h_out.get(), n * sizeof(dbh_live_result));
+    if (d_ends) std::memcpy(end_results, h_ends, n * sizeof(dbh_live_end_result));
     for (size_t i = 0; i < n; ++i) {
         if (plan[i].idle) continue;
         s->rec[(size_t)channels[i]] = results[i];       // (the decision is the device's to make)
         s->gate[(size_t)channels[i]] = gate[i];
+        s->end_done[(size_t)channels[i]] = is_pair && (flags[i] & DBH_LIVE_END) != 0;
     }
     return DBH_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int dbh_live_track(dbh_live_session* s, int channel, int32_t* best, double* margin,
                    int32_t* windows) {
@@ -1846,6 +1983,22 @@ int dbh_live_track(dbh_live_session* s, int channel, int32_t* best, double* marg
                            (size_t)steps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DBH_HIP(hipStreamSynchronize(s->stream));
     *windows = s->rec[(size_t)channel].windows;
+    return DBH_OK;
+}
+
+int dbh_live_end_track(dbh_live_session* s, int channel, int32_t* best, double* margin,
+                       int32_t* windows) {
+    if (!s || !s->pair.ring || !best || !margin || !windows || channel < 0 ||
+        channel >= s->n_channels)
+        return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(s->model->device));
+    const int steps = s->pair.shape.steps;
+    DBH_HIP(hipMemcpyAsync(best, s->pair.end.best + (size_t)channel * steps,
+                           (size_t)steps * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    DBH_HIP(hipMemcpyAsync(margin, s->pair.end.margin + (size_t)channel * steps,
+                           (size_t)steps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    *windows = s->end_done[(size_t)channel] ? steps : 0;
     return DBH_OK;
 }
 
@@ -1893,6 +2046,24 @@ int dbh_live_plan_host(int input_size, int scan_size, double score_diff, int min
     dbh_live::plan_channel(shape, (const long long*)lengths, (const unsigned*)chunk_flags,
                            (long long)n_chunks, (const int*)track_best, track_margin, results_host,
                            (int*)new_windows_host);
+    return DBH_OK;
+}
+
+int dbh_live_tail_plan_host(int end_input_size, int scan_size, const int64_t* lengths,
+                            const uint32_t* chunk_flags, int64_t n_chunks, int64_t* store_host,
+                            int64_t* samples_host, int32_t* ends_host, int64_t* windows_host) {
+    if (n_chunks < 0) return DBH_ERR_INVALID_ARGUMENT;
+    const dbh_live::Shape shape = dbh_live::shape_of(end_input_size, scan_size, 0.5, 1, 0);
+    if (!dbh_live::shape_ok(shape, scan_size)) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_chunks == 0) return DBH_OK;
+    if (!lengths || !chunk_flags || !store_host || !samples_host || !ends_host || !windows_host)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_chunks; ++i)
+        if (lengths[i] < 0 || (chunk_flags[i] & ~(uint32_t)(DBH_LIVE_BEGIN | DBH_LIVE_END)))
+            return DBH_ERR_INVALID_ARGUMENT;
+    dbh_live::plan_tail(shape, (const long long*)lengths, (const unsigned*)chunk_flags,
+                        (long long)n_chunks, (long long*)store_host, (long long*)samples_host,
+                        (int*)ends_host, (long long*)windows_host);
     return DBH_OK;
 }
 

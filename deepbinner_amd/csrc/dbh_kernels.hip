@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_combine.h"
 #include "dbh_kernels.h"
 #define DBH_FORWARD_NS dbh
 #define DBH_TIMELINE 0
@@ -106,20 +107,14 @@ __global__ __launch_bounds__(256) void dbh_merge_kernel(const float* __restrict_
 
 extern "C" {      // (the kernel's symbol is unmangled)
 namespace {
-// classify.py:298-322 on call numbers (0 = 'none'); one read per thread, 12 bytes of traffic each
+// classify.py:298-322 on call numbers (0 = 'none'), the rule of dbh_combine.h; one read per thread,
+// 12 bytes of traffic each
 __global__ void combine_calls_kernel(const int32_t* __restrict__ start_calls,
                                      const int32_t* __restrict__ end_calls, long long n, int mode,
                                      int32_t* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int32_t s = start_calls[i], e = end_calls[i];
-    int32_t call;
-    if (s == e) call = s;
-    else if (mode == DBH_REQUIRE_BOTH) call = DBH_CALL_NONE;
-    else if (e == DBH_CALL_NONE) call = s;
-    else if (mode == DBH_REQUIRE_START) call = DBH_CALL_NONE;
-    else call = (s == DBH_CALL_NONE) ? e : DBH_CALL_NONE;
-    out[i] = call;
+    out[i] = dbh::combine_calls(start_calls[i], end_calls[i], mode);     // (dbh_combine.h)
 }
 }  // namespace
 }  // extern "C"

@@ -13,9 +13,10 @@ namespace dbh_live {
 constexpr int kMaxClasses = 256;      // the general path's limit (dbh_general.h)
 
 // one chunk of a push as the kernels read it: `length` samples for `channel`, of which the ones
-// that are kept lie from in[src] on
+// that the start side keeps lie from in[src] on and the ones the tail ring keeps (a pair session's
+// last min(length, cap_e)) from in[tail] on
 struct Chunk {
-    long long src, length;
+    long long src, length, tail;
     int channel;
     unsigned flags;
 };
@@ -33,10 +34,24 @@ struct State {
     int n_classes;
 };
 
+// The end side of a pair session: the tail rings, rows of `stride` int16 (a multiple of 8), the END
+// model's shape, and as `end` what the fold keeps of the end windows - its record (fresh at END,
+// FINAL behind the steps_e windows), merged [C], the end track [steps_e]; end.samples is not used.
+// ring null: a start-only session.
+struct Pair {
+    int16_t* ring;
+    long long stride;
+    Shape shape;
+    State end;
+    int combine_mode;
+};
+
 // per chunk: reset on BEGIN, the kept samples into the channel's row, the counters; first[i] /
-// count[i] get the windows this push made ready (first -1: an idle chunk)
-hipError_t append(const State& st, const Shape& shape, const Chunk* chunks, const int16_t* in,
-                  int n_chunks, int32_t* first, int32_t* count, hipStream_t stream);
+// count[i] get the windows this push made ready (first -1: an idle chunk).  A pair session's chunks
+// also store their tails into the ring and make the end fold's record fresh at END.
+hipError_t append(const State& st, const Shape& shape, const Pair& pair, const Chunk* chunks,
+                  const int16_t* in, int n_chunks, int32_t* first, int32_t* count,
+                  hipStream_t stream);
 
 // win_offsets[n_chunks + 1]: the exclusive prefix of count, the total behind it
 hipError_t window_list(const int32_t* count, int n_chunks, int64_t* win_offsets,
@@ -54,8 +69,16 @@ hipError_t fold(bool general, const State& st, const Shape& shape, const Chunk* 
                 const int64_t* win_offsets, int64_t n_chunks, int64_t w0, int64_t n,
                 const float* probs, hipStream_t stream);
 
-// results[i]: the record of chunk i's channel, IDLE where first[i] < 0
-hipError_t results(const State& st, const Chunk* chunks, const int32_t* first, int n_chunks,
-                   dbh_live_result* results, hipStream_t stream);
+// x[n][L_e]: end windows [w0, w0 + n) of the list end_offsets[n_chunks + 1] (steps_e windows for
+// every chunk that ended a read), read out of the channels' rings, normalised and padded in front
+hipError_t end_front(const State& st, const Pair& pair, const Chunk* chunks,
+                     const int64_t* end_offsets, int n_chunks, int64_t w0, int64_t n, float* x,
+                     hipStream_t stream);
+
+// results[i]: the record of chunk i's channel, IDLE where first[i] < 0; end_results (may be null;
+// pair sessions): the end record beside it
+hipError_t results(const State& st, const Pair& pair, const Chunk* chunks, const int32_t* first,
+                   int n_chunks, dbh_live_result* results, dbh_live_end_result* end_results,
+                   hipStream_t stream);
 
 }  // namespace dbh_live

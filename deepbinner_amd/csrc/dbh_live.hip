@@ -6,7 +6,9 @@
 //                    dbh_live_core.h's append (reset on BEGIN, the clip at cap, the counters, the
 //                    windows this push made ready), the kept samples into the channel's row - 16
 //                    bytes per thread where source and row are aligned alike (the host stages them
-//                    so), single int16 values at the edges and otherwise
+//                    so), single int16 values at the edges and otherwise.  Its pair form also
+//                    stores the chunk's tail into the channel's ring, two spans at the wrap, by
+//                    the same copy, and makes the end fold's record fresh at END
 //   list_kernel      the exclusive prefix of the new-window counts: one workgroup walks the chunks
 //                    1,024 at a time, dbh_wave.h's block scan per trip and a carry
 //   front_kernel     one wave per listed window: find its chunk by binary search, cut
@@ -16,7 +18,12 @@
 //   fold256_kernel   one workgroup per chunk (general models): load merged and the record, fold
 //                    this round's windows of the channel in order by dbh_fold.h's step - the
 //                    sweep's - write the track, decide by dbh_live_core.h's folded(), store
-//   results_kernel   the record of every chunk's channel, IDLE for an idle chunk
+//   end_front_kernel one wave per end window of every chunk that carried END (pair sessions):
+//                    its m samples out of the ring through the wrap, the same front rule, padded
+//                    in front; the forward pass and the fold kernels above take it from there,
+//                    on the end model and the end side's record, merged vector and track
+//   results_kernel   the record of every chunk's channel, IDLE for an idle chunk; its pair form
+//                    the end record beside it (dbh_live_core.h's end_record: combine_calls)
 //
 // The forward pass between front and fold is what dbh_predict_dev launches, in rounds; a round may
 // end in the middle of a channel's windows, the fold takes up where the record says.  Every loop is
@@ -40,7 +47,24 @@ constexpr int kPrefixThreads = 1024;
 constexpr int kSearchDepth = 32;              // halvings of a range of at most 2^31 chunks
 
 // ---- append -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void append_kernel(State st, Shape shape,
+// n samples src -> dst, all threads of the workgroup: 16 bytes per thread where src and dst agree
+// modulo 16 bytes, single int16 values in front of dst's first 16-byte boundary, behind the last
+// whole piece and where they do not agree
+__device__ __forceinline__ void copy_span(int16_t* __restrict__ dst,
+                                          const int16_t* __restrict__ src, long long n, int t) {
+    long long head = (8 - (((unsigned long long)dst >> 1) & 7)) & 7;
+    if (head > n) head = n;
+    long long body = 0;                                        // 16-byte pieces behind the head
+    if ((((unsigned long long)(src + head)) & 15) == 0) body = (n - head) / 8;
+    for (long long j = t; j < head; j += kThreads) dst[j] = src[j];
+    const int4* src16 = (const int4*)(src + head);
+    int4* dst16 = (int4*)(dst + head);
+    for (long long j = t; j < body; j += kThreads) dst16[j] = src16[j];
+    for (long long j = head + body * 8 + t; j < n; j += kThreads) dst[j] = src[j];
+}
+
+template <bool kPair>
+__global__ __launch_bounds__(kThreads) void append_kernel(State st, Shape shape, Pair pair,
                                                           const Chunk* __restrict__ chunks,
                                                           const int16_t* __restrict__ in,
                                                           int* __restrict__ first,
@@ -57,21 +81,23 @@ __global__ __launch_bounds__(kThreads) void append_kernel(State st, Shape shape,
         if (!a.idle) {
             st.rec[chunk.channel] = r;
             st.gate[chunk.channel] = g;
+            if (kPair && (chunk.flags & DBH_LIVE_END)) {       // the end fold starts from fresh
+                dbh_live_result f = fresh_record();
+                f.status = DBH_LIVE_PENDING;
+                pair.end.rec[chunk.channel] = f;
+            }
         }
     }
-    if (a.keep <= 0) return;
-    // the row begins on a 16-byte boundary: dst is aligned where (at + head) % 8 == 0
-    int16_t* dst = st.samples + (long long)chunk.channel * st.stride + a.at;
-    const int16_t* src = in + chunk.src;
-    long long head = (8 - (a.at & 7)) & 7;
-    if (head > a.keep) head = a.keep;
-    long long body = 0;                                        // 16-byte pieces behind the head
-    if ((((unsigned long long)(src + head)) & 15) == 0) body = (a.keep - head) / 8;
-    for (long long j = t; j < head; j += kThreads) dst[j] = src[j];
-    const int4* src16 = (const int4*)(src + head);
-    int4* dst16 = (int4*)(dst + head);
-    for (long long j = t; j < body; j += kThreads) dst16[j] = src16[j];
-    for (long long j = head + body * 8 + t; j < a.keep; j += kThreads) dst[j] = src[j];
+    // the row begins on a 16-byte boundary: the host stages src so that it agrees with at modulo 8
+    if (a.keep > 0)
+        copy_span(st.samples + (long long)chunk.channel * st.stride + a.at, in + chunk.src, a.keep, t);
+    if (kPair && !a.idle) {                                    // whatever the start side's record says
+        const Tail tail = tail_store(r.samples - chunk.length, chunk.length, pair.shape);
+        int16_t* ring = pair.ring + (long long)chunk.channel * pair.stride;
+        const int16_t* src = in + chunk.tail;
+        copy_span(ring + tail.at, src, tail.head, t);
+        copy_span(ring, src + tail.head, tail.keep - tail.head, t);      // behind the wrap
+    }
 }
 
 // ---- the window list ----------------------------------------------------------------------------
@@ -119,6 +145,49 @@ __global__ __launch_bounds__(kThreads) void front_kernel(State st, Shape shape,
         }
     }
     dbh_front::window(src, m, shape.L, 0, lane, x + slot * shape.L);
+}
+
+// ---- the end windows (pair sessions) ------------------------------------------------------------
+// where in the ring's row sample j of a window lies that begins at index `at`: through the wrap,
+// once at the most (m <= cap)
+struct RingAt {
+    long long at, cap;
+    __device__ __forceinline__ long long operator()(int j) const {
+        const long long p = at + j;
+        return p < cap ? p : p - cap;
+    }
+};
+
+__global__ __launch_bounds__(kThreads) void end_front_kernel(State st, Pair pair,
+                                                             const Chunk* __restrict__ chunks,
+                                                             const long long* __restrict__ end_offsets,
+                                                             int n_chunks, long long w0, long long n,
+                                                             float* __restrict__ x) {
+    const long long slot = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (slot >= n) return;                                     // (whole waves)
+    const long long g = w0 + slot;
+    const int16_t* row = pair.ring;
+    RingAt from{0, pair.shape.cap};
+    long long m = 0;                                           // a window outside the list: zeros
+    int pad = pair.shape.L;
+    if (g >= end_offsets[0] && g < end_offsets[n_chunks]) {
+        int lo = 0, hi = n_chunks;                             // end_offsets[lo] <= g < [hi]
+        for (int d = 0; d < kSearchDepth && hi - lo > 1; ++d) {
+            const int mid = lo + (hi - lo) / 2;
+            if (end_offsets[mid] <= g) lo = mid; else hi = mid;
+        }
+        const long long s = g - end_offsets[lo];
+        const int channel = chunks[lo].channel;
+        if (s < pair.shape.steps) {                            // (so a >= n - cap: inside the ring)
+            const EndWindow w = end_window(st.rec[channel].samples, (int)s, pair.shape);
+            row = pair.ring + (long long)channel * pair.stride;
+            from.at = w.at;
+            m = w.m;
+            pad = w.pad;
+        }
+    }
+    dbh_front::window(row, m, pair.shape.L, pad, lane, x + slot * pair.shape.L, from);
 }
 
 // ---- the resumable fold -------------------------------------------------------------------------
@@ -200,14 +269,23 @@ __global__ __launch_bounds__(kThreads) void fold256_kernel(FoldArgs a) {
 }
 
 // ---- results ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void results_kernel(State st,
+template <bool kPair>
+__global__ __launch_bounds__(kThreads) void results_kernel(State st, Pair pair,
                                                            const Chunk* __restrict__ chunks,
                                                            const int* __restrict__ first,
                                                            int n_chunks,
-                                                           dbh_live_result* __restrict__ results) {
+                                                           dbh_live_result* __restrict__ results,
+                                                           dbh_live_end_result* __restrict__ end_results) {
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n_chunks) return;
-    dbh_live_result r = st.rec[chunks[i].channel];
+    const int channel = chunks[i].channel;
+    dbh_live_result r = st.rec[channel];
+    if (kPair && end_results) {
+        dbh_live_end_result e =
+            end_record(r, st.gate[channel], pair.end.rec[channel], pair.combine_mode);
+        if (first[i] < 0) e.status = DBH_LIVE_IDLE;
+        end_results[i] = e;
+    }
     if (first[i] < 0) r.status = DBH_LIVE_IDLE;
     results[i] = r;
 }
@@ -217,10 +295,15 @@ __global__ __launch_bounds__(kThreads) void results_kernel(State st,
 // =============================================================================================
 // The launches (dbh_live.h)
 // =============================================================================================
-hipError_t append(const State& st, const Shape& shape, const Chunk* chunks, const int16_t* in,
-                  int n_chunks, int32_t* first, int32_t* count, hipStream_t stream) {
-    hipLaunchKernelGGL(append_kernel, dim3((unsigned)n_chunks), dim3(kThreads), 0, stream, st, shape,
-                       chunks, in, (int*)first, (int*)count);
+hipError_t append(const State& st, const Shape& shape, const Pair& pair, const Chunk* chunks,
+                  const int16_t* in, int n_chunks, int32_t* first, int32_t* count,
+                  hipStream_t stream) {
+    if (pair.ring)
+        hipLaunchKernelGGL(append_kernel<true>, dim3((unsigned)n_chunks), dim3(kThreads), 0, stream,
+                           st, shape, pair, chunks, in, (int*)first, (int*)count);
+    else
+        hipLaunchKernelGGL(append_kernel<false>, dim3((unsigned)n_chunks), dim3(kThreads), 0, stream,
+                           st, shape, pair, chunks, in, (int*)first, (int*)count);
     return hipGetLastError();
 }
 
@@ -253,10 +336,25 @@ hipError_t fold(bool general, const State& st, const Shape& shape, const Chunk* 
     return hipGetLastError();
 }
 
-hipError_t results(const State& st, const Chunk* chunks, const int32_t* first, int n_chunks,
-                   dbh_live_result* results, hipStream_t stream) {
-    hipLaunchKernelGGL(results_kernel, dim3((unsigned)((n_chunks + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, stream, st, chunks, (const int*)first, n_chunks, results);
+hipError_t end_front(const State& st, const Pair& pair, const Chunk* chunks,
+                     const int64_t* end_offsets, int n_chunks, int64_t w0, int64_t n, float* x,
+                     hipStream_t stream) {
+    hipLaunchKernelGGL(end_front_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, stream,
+                       st, pair, chunks, (const long long*)end_offsets, n_chunks, (long long)w0,
+                       (long long)n, x);
+    return hipGetLastError();
+}
+
+hipError_t results(const State& st, const Pair& pair, const Chunk* chunks, const int32_t* first,
+                   int n_chunks, dbh_live_result* results, dbh_live_end_result* end_results,
+                   hipStream_t stream) {
+    const dim3 grid((unsigned)((n_chunks + kThreads - 1) / kThreads));
+    if (pair.ring)
+        hipLaunchKernelGGL(results_kernel<true>, grid, dim3(kThreads), 0, stream, st, pair, chunks,
+                           (const int*)first, n_chunks, results, end_results);
+    else
+        hipLaunchKernelGGL(results_kernel<false>, grid, dim3(kThreads), 0, stream, st, pair, chunks,
+                           (const int*)first, n_chunks, results, end_results);
     return hipGetLastError();
 }
 

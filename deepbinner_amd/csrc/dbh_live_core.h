@@ -1,6 +1,7 @@
 // dbh_live_core.h - the rules of a live session (include/deepbinner_hip.h, "live"; DESIGN.md section
 // 32) that are integers and comparisons: which windows of a channel are ready, what of a chunk is
-// stored, and what a folded window does to the channel's record.  The GPU's threads (dbh_live.hip),
+// stored, what a folded window does to the channel's record, and - for a pair session - the tail
+// ring, the end windows and the end record.  The GPU's threads (dbh_live.hip),
 // the session's host mirror (dbh_api.hip: it knows every push's window count without reading the
 // device back) and the CPU model (dbh_live_plan_host; live_model_check.cpp) compile these lines.
 #pragma once
@@ -9,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_combine.h"
 
 #if defined(__HIPCC__)
 #define DBLIVE_FN __host__ __device__ __forceinline__
@@ -157,6 +159,115 @@ DBLIVE_FN void plan_channel(const Shape& s, const long long* lengths, const unsi
         results[i] = r;
         if (a.idle) results[i].status = DBH_LIVE_IDLE;
         if (new_windows) new_windows[i] = done;
+    }
+}
+
+// =============================================================================================
+// The end side of a pair session.  `e` is the END model's shape: L_e, h_e,
+// steps_e, cap_e = scan_size + h_e; its score_diff is the session's, min_windows 1, flags 0.
+// =============================================================================================
+
+// The tail ring: sample p of a read (counted from BEGIN) lives at ring[p % cap_e].  A chunk of
+// `length` samples arriving at n stores its last `keep` = min(length, cap_e): the chunk's samples
+// [from, length) go to ring positions at, at + 1, .. through the wrap - `head` of them up to the
+// row's end, the others from ring[0] on.  Every chunk of an open read stores, whatever the start
+// side's record says; BEGIN resets nothing here.
+struct Tail {
+    long long from, keep, at, head;
+};
+
+DBLIVE_FN Tail tail_store(long long n, long long length, const Shape& e) {
+    Tail t;
+    t.keep = length < e.cap ? length : e.cap;
+    t.from = length - t.keep;
+    t.at = (n + t.from) % e.cap;
+    t.head = t.keep < e.cap - t.at ? t.keep : e.cap - t.at;
+    return t;
+}
+
+// End window s of a read of n samples, known at END (call_batch with side == 'end',
+// classify.py:343-357): samples [a, a + m), the values at out[pad .. L_e), zeros in front; sample
+// a + j is ring[(at + j) % cap_e].  Window steps_e - 1 reaches back to n - cap_e at the most.
+struct EndWindow {
+    long long a, m, at;
+    int pad;
+};
+
+DBLIVE_FN EndWindow end_window(long long n, int s, const Shape& e) {
+    EndWindow w;
+    const long long lo = n - ((long long)s * e.h + e.L), hi = n - (long long)s * e.h;
+    w.a = lo > 0 ? lo : 0;
+    w.m = (hi > 0 ? hi : 0) - w.a;
+    w.at = w.a % e.cap;
+    w.pad = e.L - (int)w.m;
+    return w;
+}
+
+// what the start side gives combine_calls: the final call, or - stopped on a decision - the early one
+DBLIVE_FN int start_side_call(const dbh_live_result& r) {
+    return r.status == DBH_LIVE_FINAL ? r.final_call : r.call;
+}
+
+DBLIVE_FN dbh_live_end_result fresh_end_record() {
+    dbh_live_end_result r;
+    r.status = DBH_LIVE_IDLE;
+    r.end_call = r.start_call = r.read_call = -1;
+    r.end_best = 0;
+    r.end_windows = 0;
+    r.end_margin = 0.0;
+    r.samples = 0;
+    return r;
+}
+
+// The end record of a channel from its start record `r`, its gate and the end fold's record `f`
+// (a dbh_live_result folded from fresh over the steps_e end windows: FINAL behind them).
+DBLIVE_FN dbh_live_end_result end_record(const dbh_live_result& r, const Gate& g,
+                                         const dbh_live_result& f, int combine_mode) {
+    dbh_live_end_result o = fresh_end_record();
+    if (r.status == DBH_LIVE_IDLE) return o;                   // no read yet
+    o.status = DBH_LIVE_PENDING;
+    o.samples = r.samples;
+    if (!g.ended || f.status != DBH_LIVE_FINAL) return o;
+    o.status = DBH_LIVE_FINAL;
+    o.end_call = f.final_call;
+    o.start_call = start_side_call(r);
+    o.read_call = dbh::combine_calls(o.start_call, o.end_call, combine_mode);
+    o.end_best = f.best;
+    o.end_windows = f.windows;
+    o.end_margin = f.margin;
+    return o;
+}
+
+// One channel's ring and end windows through n_chunks pushes on the host.  Per chunk i:
+// store[i] = (from, keep, at, head) of tail_store (zeros for an idle chunk), n_after[i] = n behind
+// it; a chunk that carries END on an open read has ends[i] = 1 and windows[4 (i steps_e + s) ..] =
+// (a, m, pad, at) of end window s (the other chunks' entries are not written).
+DBLIVE_FN void plan_tail(const Shape& e, const long long* lengths,
+                         const unsigned* chunk_flags, long long n_chunks, long long* store,
+                         long long* n_after, int* ends, long long* windows) {
+    dbh_live_result r = fresh_record();
+    Gate g;
+    g.open = g.ended = 0;
+    for (long long i = 0; i < n_chunks; ++i) {
+        const Append a = append(&r, &g, chunk_flags[i], lengths[i], e);    // (gate and n only)
+        Tail t;
+        t.from = t.keep = t.at = t.head = 0;
+        if (!a.idle) t = tail_store(r.samples - lengths[i], lengths[i], e);
+        store[4 * i] = t.from;
+        store[4 * i + 1] = t.keep;
+        store[4 * i + 2] = t.at;
+        store[4 * i + 3] = t.head;
+        n_after[i] = r.samples;
+        ends[i] = !a.idle && (chunk_flags[i] & DBH_LIVE_END) != 0;
+        if (!ends[i]) continue;
+        for (int s = 0; s < e.steps; ++s) {
+            const EndWindow w = end_window(r.samples, s, e);
+            long long* out = windows + 4 * (i * e.steps + s);
+            out[0] = w.a;
+            out[1] = w.m;
+            out[2] = w.pad;
+            out[3] = w.at;
+        }
     }
 }
 

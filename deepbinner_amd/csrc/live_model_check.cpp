@@ -4,7 +4,12 @@
 // every chunking, the append clip at cap - 1, cap and cap + 1, the decision rules on planted tracks.
 // A channel's row is a heap block of exactly cap samples, a chunk one of exactly its length, a track
 // one of exactly steps entries, so that an access one element outside is caught.  Every case also
-// states what the rule has to give.  No device, no Python.
+// states what the rule has to give.  The pair sessions' rules too: the tail ring (tail_store) and
+// the end windows (end_window) at every read length 0 .. 3 cap_e + 7 of L = 96 under a set of
+// chunkings - a ring of exactly cap_e samples and beside it who wrote each of them, so that every
+// position an end window reads at END is one this read wrote and holds the right sample -, the
+// host plan entry's form of the same (plan_tail), the end record and the combine rule.  No device,
+// no Python.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -131,9 +136,205 @@ void decide(const char* what, double score_diff, int min_windows, unsigned flags
     std::free(new_windows);
 }
 
+// ---- the pair sessions' rules ----------------------------------------------------------------------
+int16_t sample_of(long long read, long long p) { return (int16_t)(p * 7 + 1 + read * 131); }
+
+// One channel, ring and who-wrote-it of exactly cap_e entries.  A read of `length` samples is
+// delivered in chunks of the sizes `sizes[0 .. n_sizes)` in turn (0: an empty chunk), END with the
+// last chunk or alone behind it.  stopped: the start side's record says DECIDED under
+// STOP_ON_DECISION from the first chunk on - the ring must go on all the same.
+struct RingChannel {
+    dbh_live::Shape start, e;
+    int16_t* ring;
+    long long* who;                      // the position p of the sample at ring[i], and
+    long long* whose;                    // the read that wrote it
+    dbh_live_result r;
+    dbh_live::Gate g;
+    long long read;
+};
+
+void ring_push(RingChannel& c, long long len, unsigned flags, long long sent, bool stopped) {
+    int16_t* chunk = exactly<int16_t>((size_t)len);
+    if (flags & DBH_LIVE_BEGIN) ++c.read;
+    for (long long j = 0; j < len; ++j) chunk[j] = sample_of(c.read, sent + j);
+    const dbh_live::Append a = dbh_live::append(&c.r, &c.g, flags, len, c.start);
+    if (stopped && !a.idle) {
+        c.r.status = DBH_LIVE_DECIDED;
+        c.r.call = 3;
+        c.r.decided_windows = 1;
+    }
+    if (!a.idle) {
+        const dbh_live::Tail t = dbh_live::tail_store(c.r.samples - len, len, c.e);
+        if (t.keep < 0 || t.keep > len || t.keep > c.e.cap || t.from != len - t.keep || t.at < 0 ||
+            t.at >= c.e.cap || t.head < 0 || t.head > t.keep || t.at + t.head > c.e.cap ||
+            t.keep - t.head > t.at)
+            fail("tail", t.at, t.keep, t.head);
+        for (long long j = 0; j < t.keep; ++j) {                   // two spans at the wrap
+            const long long i = j < t.head ? t.at + j : j - t.head;
+            c.ring[i] = chunk[t.from + j];
+            c.who[i] = c.r.samples - len + t.from + j;
+            c.whose[i] = c.read;
+        }
+    } else if (len > 0 && (flags & DBH_LIVE_BEGIN)) {
+        fail("idle with BEGIN", len, flags, 0);
+    }
+    std::free(chunk);
+    if (a.idle || !(flags & DBH_LIVE_END)) return;
+    const long long n = c.r.samples;
+    for (int s = 0; s < c.e.steps; ++s) {
+        const dbh_live::EndWindow w = dbh_live::end_window(n, s, c.e);
+        const long long lo = n - ((long long)s * c.e.h + c.e.L), hi = n - (long long)s * c.e.h;
+        if (w.a != (lo > 0 ? lo : 0) || w.a + w.m != (hi > 0 ? hi : 0) || w.m < 0 || w.m > c.e.L ||
+            w.pad != c.e.L - w.m || w.at != w.a % c.e.cap || w.a < n - c.e.cap)
+            fail("end window", n, s, w.a);
+        for (long long j = 0; j < w.m; ++j) {
+            const long long i = w.at + j < c.e.cap ? w.at + j : w.at + j - c.e.cap;
+            if (c.whose[i] != c.read || c.who[i] != w.a + j || c.ring[i] != sample_of(c.read, w.a + j)) {
+                fail("ring read", n, s, j);
+                break;
+            }
+        }
+    }
+}
+
+void deliver_tail(RingChannel& c, long long length, const long long* sizes, int n_sizes,
+                  bool end_alone, bool stopped) {
+    long long sent = 0;
+    bool first = true, ended = false;
+    for (int k = 0; !ended; ++k) {
+        const long long size = sizes[k % n_sizes];
+        const long long len = length - sent < size ? length - sent : size;
+        const bool last = sent + len >= length && (size > 0 || length == 0 || k > 64);
+        unsigned flags = first ? DBH_LIVE_BEGIN : 0;
+        if (last && !(end_alone && len > 0)) flags |= DBH_LIVE_END;
+        ring_push(c, len, flags, sent, stopped);
+        sent += len;
+        ended = (flags & DBH_LIVE_END) != 0;
+        first = false;
+    }
+    if (c.r.samples != length || c.g.open || !c.g.ended) fail("tail n", c.r.samples, length, 0);
+}
+
+void tail_rules() {
+    const int L = 96, steps = 12, h = L / 2;
+    const unsigned stop = DBH_LIVE_STOP_ON_DECISION;
+    RingChannel c;
+    c.start = dbh_live::shape_of(L, steps * h, 0.5, 1, stop);
+    c.e = dbh_live::shape_of(L, steps * h, 0.5, 1, 0);
+    const long long cap = c.e.cap;
+    c.ring = exactly<int16_t>((size_t)cap);
+    c.who = exactly<long long>((size_t)cap);
+    c.whose = exactly<long long>((size_t)cap);
+    for (long long i = 0; i < cap; ++i) {
+        c.ring[i] = 0;
+        c.who[i] = c.whose[i] = -1;
+    }
+    c.r = dbh_live::fresh_record();
+    c.g = dbh_live::Gate{0, 0};
+    c.read = 0;
+    // one channel all the way: every read follows another one's leftovers in the ring
+    const long long whole[] = {4 * cap}, one[] = {1}, below[] = {h - 1}, half[] = {h}, above[] = {h + 1};
+    const long long at_cap[] = {cap, h}, over_cap[] = {cap + 1, 7}, long_one[] = {2 * cap + 3, 5};
+    const long long empties[] = {0, h + 5, 0, 0, 1600}, sequencer[] = {1600};
+    const struct { const long long* sizes; int n; } chunkings[] = {
+        {whole, 1}, {one, 1}, {below, 1}, {half, 1}, {above, 1}, {at_cap, 2}, {over_cap, 2},
+        {long_one, 2}, {empties, 5}, {sequencer, 1}};
+    for (long long length = 0; length <= 3 * cap + 7; ++length)
+        for (const auto& ch : chunkings) {
+            if (ch.sizes == one && length % 5 != 0 && length > L + 2) continue;   // (keeps it quick)
+            deliver_tail(c, length, ch.sizes, ch.n, false, false);
+            deliver_tail(c, length, ch.sizes, ch.n, true, length % 2 == 0);
+        }
+    {   // BEGIN inside a read, BEGIN|END on an empty chunk, a chunk with no read open
+        ring_push(c, 2 * cap + 9, DBH_LIVE_BEGIN, 0, false);
+        ring_push(c, 5, DBH_LIVE_BEGIN, 0, false);
+        ring_push(c, 3, DBH_LIVE_END, 5, false);
+        if (c.r.samples != 8) fail("BEGIN inside a read", c.r.samples, 8, 0);
+        ring_push(c, 0, DBH_LIVE_BEGIN | DBH_LIVE_END, 0, false);
+        if (c.r.samples != 0 || c.g.open) fail("BEGIN|END", c.r.samples, c.g.open, 0);
+        const long long before = c.who[0];
+        ring_push(c, 100, DBH_LIVE_END, 0, false);
+        if (c.who[0] != before || c.r.samples != 0) fail("idle stores", c.who[0], before, 0);
+    }
+    {   // plan_tail, the host entry's form, against the same rules chunk by chunk
+        const long long lengths[] = {2 * cap + 5, 0, 7, 100, 30, 0};
+        const unsigned flags[] = {DBH_LIVE_BEGIN, DBH_LIVE_END, 0, DBH_LIVE_BEGIN, 0, DBH_LIVE_END};
+        const int n = 6;
+        long long* store = exactly<long long>(4 * n);
+        long long* n_after = exactly<long long>(n);
+        int* ends = exactly<int>(n);
+        long long* windows = exactly<long long>((size_t)4 * n * steps);
+        dbh_live::plan_tail(c.e, lengths, flags, n, store, n_after, ends, windows);
+        const long long want_n[] = {2 * cap + 5, 2 * cap + 5, 2 * cap + 5, 100, 130, 130};
+        const int want_ends[] = {0, 1, 0, 0, 0, 1};
+        for (int i = 0; i < n; ++i)
+            if (n_after[i] != want_n[i] || ends[i] != want_ends[i]) fail("plan_tail", i, n_after[i], ends[i]);
+        if (store[0] != cap + 5 || store[1] != cap || store[2] != 5 || store[3] != cap - 5)
+            fail("plan_tail store", store[0], store[1], store[2]);
+        if (store[8] || store[9] || store[10] || store[11]) fail("plan_tail idle", 2, store[9], 0);
+        const dbh_live::EndWindow w = dbh_live::end_window(130, 1, c.e);
+        const long long* got = windows + 4 * (5 * steps + 1);
+        if (got[0] != w.a || got[1] != w.m || got[2] != w.pad || got[3] != w.at || w.a != 0 || w.m != 82)
+            fail("plan_tail window", got[0], got[1], got[2]);
+        std::free(store);
+        std::free(n_after);
+        std::free(ends);
+        std::free(windows);
+    }
+    std::free(c.ring);
+    std::free(c.who);
+    std::free(c.whose);
+}
+
+void end_records() {
+    // the combine rule: the reference's truth table (tests/test_combine_calls.py:27-51)
+    const struct { int mode, s, e, want; } table[] = {
+        {DBH_REQUIRE_EITHER, 1, 2, 0}, {DBH_REQUIRE_EITHER, 4, 4, 4}, {DBH_REQUIRE_EITHER, 5, 0, 5},
+        {DBH_REQUIRE_EITHER, 0, 7, 7}, {DBH_REQUIRE_EITHER, 0, 0, 0}, {DBH_REQUIRE_START, 1, 2, 0},
+        {DBH_REQUIRE_START, 4, 4, 4},  {DBH_REQUIRE_START, 5, 0, 5},  {DBH_REQUIRE_START, 0, 7, 0},
+        {DBH_REQUIRE_START, 0, 0, 0},  {DBH_REQUIRE_BOTH, 1, 2, 0},   {DBH_REQUIRE_BOTH, 4, 4, 4},
+        {DBH_REQUIRE_BOTH, 5, 0, 0},   {DBH_REQUIRE_BOTH, 0, 7, 0},   {DBH_REQUIRE_BOTH, 0, 0, 0}};
+    for (const auto& row : table)
+        if (dbh::combine_calls(row.s, row.e, row.mode) != row.want) fail("combine", row.mode, row.s, row.e);
+    dbh_live_result r = dbh_live::fresh_record(), f = dbh_live::fresh_record();
+    dbh_live::Gate g{0, 0};
+    dbh_live_end_result o = dbh_live::end_record(r, g, f, DBH_REQUIRE_EITHER);
+    if (o.status != DBH_LIVE_IDLE || o.end_call != -1 || o.start_call != -1 || o.read_call != -1 ||
+        o.end_windows != 0 || o.samples != 0)
+        fail("end record, no read", o.status, o.end_call, o.samples);
+    r.status = DBH_LIVE_DECIDED;                                   // open, decided early, not ended
+    r.call = 3;
+    r.samples = 5000;
+    g.open = 1;
+    f.status = DBH_LIVE_FINAL;                                     // (the read before this one)
+    f.final_call = 9;
+    o = dbh_live::end_record(r, g, f, DBH_REQUIRE_EITHER);
+    if (o.status != DBH_LIVE_PENDING || o.end_call != -1 || o.read_call != -1 || o.samples != 5000)
+        fail("end record, pending", o.status, o.end_call, o.samples);
+    g.open = 0;                                                    // ended behind a stop: the early call
+    g.ended = 1;
+    f.final_call = 0;
+    f.best = 4;
+    f.windows = 12;
+    f.margin = 0.25;
+    o = dbh_live::end_record(r, g, f, DBH_REQUIRE_EITHER);
+    if (o.status != DBH_LIVE_FINAL || o.start_call != 3 || o.end_call != 0 || o.read_call != 3 ||
+        o.end_best != 4 || o.end_windows != 12 || o.end_margin != 0.25)
+        fail("end record, stopped", o.start_call, o.end_call, o.read_call);
+    r.status = DBH_LIVE_FINAL;                                     // FINAL: the final call goes in
+    r.final_call = 0;
+    f.final_call = 7;
+    o = dbh_live::end_record(r, g, f, DBH_REQUIRE_EITHER);
+    if (o.start_call != 0 || o.end_call != 7 || o.read_call != 7) fail("end record, final", o.start_call, o.end_call, o.read_call);
+    o = dbh_live::end_record(r, g, f, DBH_REQUIRE_START);
+    if (o.read_call != 0) fail("end record, require start", o.start_call, o.end_call, o.read_call);
+}
+
 }  // namespace
 
 int main() {
+    tail_rules();
+    end_records();
     const int shapes[2][2] = {{96, 12}, {1024, 4}};                // (L, steps) of the tests' models
     for (const auto& shape : shapes) {
         const int L = shape[0], steps = shape[1], h = L / 2;

@@ -261,6 +261,10 @@ COMMANDS = {
                 (('--multi_read',), dict(action='store_true',
                                          help='Take the reads of multi-read fast5 files where '
                                               'they are (one-read files may be mixed in)')),
+                (('--both_ends',), dict(action='store_true',
+                                        help='Also call each read\'s end barcode when the read '
+                                             'ends, and combine the two calls as classify does '
+                                             '(needs both models)')),
                 _HELP]),
 }
 USES_MODELS = ('classify', 'realtime', 'scan', 'locate', 'replay')

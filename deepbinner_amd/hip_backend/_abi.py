@@ -160,6 +160,11 @@ def _signatures():
                                       ctypes.c_uint32, ptr, ptr, ptr, ptr, ptr]),
         'dbh_live_plan_host': (c_int, [c_int, c_int, c_double, c_int, ctypes.c_uint32, ptr, ptr,
                                        c_i64, ptr, ptr, ptr, ptr]),
+        'dbh_live_create_pair': (c_int, [ptr, ptr, c_int, c_int, c_double, c_int, ctypes.c_uint32,
+                                         c_int, c_i64, P(ptr)]),
+        'dbh_live_push_pair': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, c_i64]),
+        'dbh_live_end_track': (c_int, [ptr, c_int, ptr, ptr, P(ctypes.c_int32)]),
+        'dbh_live_tail_plan_host': (c_int, [c_int, c_int, ptr, ptr, c_i64, ptr, ptr, ptr, ptr]),
         'dbh_stage_floats': (c_int, [c_int, P(c_i64)]),
         'dbh_debug_forward': (c_int, [ptr, f32, c_i64, c_int, f32]),
         'dbh_forward_kernel_info': (c_int, [P(c_int), P(c_int), P(c_int)]),

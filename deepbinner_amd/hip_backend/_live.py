@@ -1,13 +1,14 @@
 """Live sessions: each channel's barcode called while its signal arrives (include/deepbinner_hip.h,
-"live").  ``LiveSession`` holds the channels' state on the device between pushes; ``live_fold`` and
-``live_plan_host`` are the parity-only entries of its parts."""
+"live").  ``LiveSession`` holds the channels' state on the device between pushes - with an ``end_model`` also
+the tail of every open read, and gives the read's full call when it ends; ``live_fold``,
+``live_plan_host`` and ``live_tail_plan_host`` are the parity-only entries of its parts."""
 
 import ctypes
 
 import numpy as np
 
 from .._cabi import Finalised, Owner, Scoped
-from ._abi import check, load_library
+from ._abi import COMBINE_MODES, check, load_library
 from ._device import device_arrays, synchronize
 
 # dbh_live_result (include/deepbinner_hip.h, "live"): a channel's record behind a push
@@ -16,6 +17,12 @@ LIVE_RESULT = np.dtype([('status', np.int32), ('call', np.int32), ('final_call',
                         ('margin', np.float64), ('samples', np.int64),
                         ('decided_samples', np.int64)])
 assert LIVE_RESULT.itemsize == 48
+# dbh_live_end_result: a channel's end side and combined call, known behind END (pair sessions)
+LIVE_END_RESULT = np.dtype([('status', np.int32), ('end_call', np.int32), ('start_call', np.int32),
+                            ('read_call', np.int32), ('end_best', np.int32),
+                            ('end_windows', np.int32), ('end_margin', np.float64),
+                            ('samples', np.int64)])
+assert LIVE_END_RESULT.itemsize == 40
 
 LIVE_IDLE, LIVE_PENDING, LIVE_DECIDED, LIVE_FINAL = 0, 1, 2, 3       # status
 LIVE_BEGIN, LIVE_END = 1, 2                                          # chunk flags
@@ -36,28 +43,40 @@ class LiveSession(Owner, Scoped, Finalised):
     """``n_channels`` sequencer channels of one start-side ``model``: ``push`` appends a chunk of
     signal to each channel named, runs the windows that became complete and folds them; a channel
     is DECIDED at the first window from ``min_windows`` on whose best class is a barcode that leads
-    by ``score_diff``, and FINAL when all ``scan_size`` windows are folded.  Close it before its
-    model."""
+    by ``score_diff``, and FINAL when all ``scan_size`` windows are folded.  With an ``end_model`` (a
+    pair session) the push that ends a read also runs the end model over the read's last
+    ``scan_size`` samples and combines the two sides under ``combine`` ('either', 'start' or 'both':
+    ``--require_*``): ``push_pair`` returns that beside the start records.  Close it before its
+    models."""
 
     _held, _release = 'handle', 'dbh_live_destroy'
 
     def __init__(self, model, n_channels, scan_size=6144, score_diff=0.5, min_windows=1,
-                 stop_on_decision=False, max_round_windows=0):
+                 stop_on_decision=False, max_round_windows=0, end_model=None, combine='either'):
         self._lib = load_library()
         self.model, self.n_channels, self.scan_size = model, int(n_channels), int(scan_size)
+        self.end_model = end_model
         half = model.input_size // 2
         self.steps = self.scan_size // half if half else 0
+        flags = LIVE_STOP_ON_DECISION if stop_on_decision else 0
         handle = ctypes.c_void_p()
-        check(self._lib.dbh_live_create(model.handle, self.n_channels, self.scan_size,
-                                        float(score_diff), int(min_windows),
-                                        LIVE_STOP_ON_DECISION if stop_on_decision else 0,
-                                        int(max_round_windows), ctypes.byref(handle)),
-              'dbh_live_create')
+        if end_model is None:
+            check(self._lib.dbh_live_create(model.handle, self.n_channels, self.scan_size,
+                                            float(score_diff), int(min_windows), flags,
+                                            int(max_round_windows), ctypes.byref(handle)),
+                  'dbh_live_create')
+        else:
+            end_half = end_model.input_size // 2
+            self.end_steps = self.scan_size // end_half if end_half else 0
+            mode = COMBINE_MODES[combine if combine.startswith('require_') else 'require_' + combine]
+            check(self._lib.dbh_live_create_pair(model.handle, end_model.handle, self.n_channels,
+                                                 self.scan_size, float(score_diff),
+                                                 int(min_windows), flags, mode,
+                                                 int(max_round_windows), ctypes.byref(handle)),
+                  'dbh_live_create_pair')
         self.handle = handle.value
 
-    def push_packed(self, channels, offsets, samples, flags):
-        """``dbh_live_push`` as it is: int32 channels [n], int64 offsets [n + 1] into int16
-        ``samples``, uint32 flags [n] -> LIVE_RESULT [n]."""
+    def _packed(self, channels, offsets, samples, flags, want_end):
         channels = np.ascontiguousarray(channels, dtype=np.int32)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         samples = np.ascontiguousarray(samples, dtype=np.int16)
@@ -68,21 +87,49 @@ class LiveSession(Owner, Scoped, Finalised):
         if samples.size == 0:
             samples = np.zeros(1, dtype=np.int16)           # (a pointer, whatever the chunks hold)
         results = np.zeros(n, dtype=LIVE_RESULT)
-        check(self._lib.dbh_live_push(self.handle, channels.ctypes.data, offsets.ctypes.data,
-                                      samples.ctypes.data, flags.ctypes.data, results.ctypes.data,
-                                      n), 'dbh_live_push')
-        return results
+        if not want_end:
+            check(self._lib.dbh_live_push(self.handle, channels.ctypes.data, offsets.ctypes.data,
+                                          samples.ctypes.data, flags.ctypes.data,
+                                          results.ctypes.data, n), 'dbh_live_push')
+            return results
+        ends = np.zeros(n, dtype=LIVE_END_RESULT)
+        ends['end_call'] = ends['start_call'] = ends['read_call'] = -1
+        check(self._lib.dbh_live_push_pair(self.handle, channels.ctypes.data, offsets.ctypes.data,
+                                           samples.ctypes.data, flags.ctypes.data,
+                                           results.ctypes.data, ends.ctypes.data, n),
+              'dbh_live_push_pair')
+        return results, ends
+
+    def push_packed(self, channels, offsets, samples, flags):
+        """``dbh_live_push`` as it is: int32 channels [n], int64 offsets [n + 1] into int16
+        ``samples``, uint32 flags [n] -> LIVE_RESULT [n]."""
+        return self._packed(channels, offsets, samples, flags, False)
+
+    def push_pair_packed(self, channels, offsets, samples, flags):
+        """``dbh_live_push_pair`` as it is -> (LIVE_RESULT [n], LIVE_END_RESULT [n])."""
+        return self._packed(channels, offsets, samples, flags, True)
+
+    @staticmethod
+    def _pack(chunks):
+        chunks = [np.ascontiguousarray(chunk, dtype=np.int16).reshape(-1) for chunk in chunks]
+        offsets = np.zeros(len(chunks) + 1, dtype=np.int64)
+        np.cumsum([len(chunk) for chunk in chunks], out=offsets[1:])
+        return offsets, np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
 
     def push(self, channels, chunks, begin=None, end=None):
         """One chunk of int16 signal per channel named (each channel at most once) -> LIVE_RESULT
         [n].  ``begin``: a new read starts with this chunk; ``end``: the read ends with it (one
         truth value, or one per chunk).  Chunks may be empty."""
-        chunks = [np.ascontiguousarray(chunk, dtype=np.int16).reshape(-1) for chunk in chunks]
-        offsets = np.zeros(len(chunks) + 1, dtype=np.int64)
-        np.cumsum([len(chunk) for chunk in chunks], out=offsets[1:])
-        samples = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int16)
+        offsets, samples = self._pack(chunks)
         return self.push_packed(channels, offsets, samples,
                                 live_chunk_flags(len(chunks), begin, end))
+
+    def push_pair(self, channels, chunks, begin=None, end=None):
+        """``push`` on a pair session -> (LIVE_RESULT [n], LIVE_END_RESULT [n]): behind END the end
+        model's call, the start call that went into ``combine_calls`` and the read's call."""
+        offsets, samples = self._pack(chunks)
+        return self.push_pair_packed(channels, offsets, samples,
+                                     live_chunk_flags(len(chunks), begin, end))
 
     def track(self, channel):
         """(best int32 [windows], margin float64 [windows]) of the channel's read so far: entry k
@@ -92,6 +139,17 @@ class LiveSession(Owner, Scoped, Finalised):
         windows = ctypes.c_int32(0)
         check(self._lib.dbh_live_track(self.handle, int(channel), best.ctypes.data,
                                        margin.ctypes.data, ctypes.byref(windows)), 'dbh_live_track')
+        return best[:windows.value].copy(), margin[:windows.value].copy()
+
+    def end_track(self, channel):
+        """(best int32 [windows], margin float64 [windows]) of the end side of the channel's read:
+        ``end_steps`` entries behind END, window s = 0 the read's last samples; none before."""
+        best = np.zeros(max(self.end_steps, 1), dtype=np.int32)
+        margin = np.zeros(max(self.end_steps, 1), dtype=np.float64)
+        windows = ctypes.c_int32(0)
+        check(self._lib.dbh_live_end_track(self.handle, int(channel), best.ctypes.data,
+                                           margin.ctypes.data, ctypes.byref(windows)),
+              'dbh_live_end_track')
         return best[:windows.value].copy(), margin[:windows.value].copy()
 
 
@@ -151,3 +209,26 @@ def live_plan_host(input_size, scan_size, lengths, flags, track_best, track_marg
         len(lengths), track_best.ctypes.data, track_margin.ctypes.data, results.ctypes.data,
         new_windows.ctypes.data), 'dbh_live_plan_host')
     return results, new_windows
+
+
+def live_tail_plan_host(end_input_size, scan_size, lengths, flags):
+    """One channel's tail ring and end windows on the host (``dbh_live_tail_plan_host``, the lines
+    the kernels compile): pushes of ``lengths[i]`` samples with chunk ``flags[i]`` -> (store int64
+    [n, 4]: from, keep, ring index, samples before the wrap; samples int64 [n]: n behind each push;
+    ends int32 [n]; windows int64 [n, steps_e, 4]: a, m, pad, ring index of a - filled where ends)."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    if len(flags) != len(lengths):
+        raise ValueError('one flag per length')
+    half = int(end_input_size) // 2
+    steps = max(int(scan_size) // half if half else 0, 1)
+    n = len(lengths)
+    store = np.zeros((n, 4), dtype=np.int64)
+    samples = np.zeros(n, dtype=np.int64)
+    ends = np.zeros(n, dtype=np.int32)
+    windows = np.zeros((n, steps, 4), dtype=np.int64)
+    check(load_library().dbh_live_tail_plan_host(
+        int(end_input_size), int(scan_size), lengths.ctypes.data, flags.ctypes.data, n,
+        store.ctypes.data, samples.ctypes.data, ends.ctypes.data, windows.ctypes.data),
+        'dbh_live_tail_plan_host')
+    return store, samples, ends, windows

@@ -22,9 +22,17 @@ another barcode - and ``agree`` is there to choose ``--min_windows`` and ``--sco
 this is what the network says on prefixes of recorded reads; nothing has been checked on a
 sequencer.
 
-Only the start model is used: the end of a read is not known while it arrives.  ``-e`` alone is
-refused, a preset's end model is ignored.  ``replay(args, backend=None)`` takes its device entries as
-a parameter, so that the loop and the table also run against a host stand-in
+Without ``--both_ends`` only the start model is used: the end of a read is not known while it
+arrives.  ``-e`` alone is refused, a preset's end model is ignored.  With ``--both_ends`` the session
+is a pair session (both models: ``-s`` and ``-e``, or a preset): the push that carries a read's END
+also runs the end model over the read's last ``--scan_size`` samples and combines the two sides as
+``classify`` does, under ``--require_either`` / ``--require_start`` / ``--require_both``.  Two columns
+follow ``agree``: ``end_call``, and ``read_call`` = ``combine_calls`` of the start side and
+``end_call``.  The start side is ``final_call`` where the read became FINAL; under
+``--stop_on_decision`` a read stops at its decision, and ``read_call`` is then combined from the
+early start call (``live_call``), not from a final one.  The summary gains one line: how many
+reads were called from the start only, the end only, both sides in agreement, and how many had both
+sides disagree.  ``replay(args, backend=None)`` takes its device entries as a parameter, so that the loop and the table also run against a host stand-in
 (tests/live_reference.py).  ``--devices``: a replay runs on one GPU; a value above 1 is refused.
 """
 import sys
@@ -36,8 +44,11 @@ NO_TRAINING_DATA = ('Error: a training-data file cannot be replayed - its sample
                     'long, not reads that arrive')
 NO_START_MODEL = ('Error: replay needs a start model (-s, --native or --rapid) - the end of a read '
                   'is not known while it arrives')
+NO_PAIR = ('Error: replay --both_ends needs a start model and an end model (-s and -e, --native or '
+           '--rapid)')
 HEADER = ['read_ID', 'live_call', 'decided_windows', 'decided_samples', 'final_call', 'samples',
           'agree']
+PAIR_HEADER = HEADER + ['end_call', 'read_call']
 
 
 def reads_in_file_order(units, sweep):
@@ -73,6 +84,9 @@ def replay(args, backend=None):
     if int(getattr(args, 'devices', 0) or 0) > 1:
         sys.exit('Error: a replay runs on one GPU (--devices {} is not supported)'
                  .format(args.devices))
+    both_ends = bool(getattr(args, 'both_ends', False))
+    if both_ends and (args.start_model is None or getattr(args, 'end_model', None) is None):
+        sys.exit(NO_PAIR)
     if args.start_model is None:
         sys.exit(NO_START_MODEL)
     if args.channels < 1 or args.channels > 16384:
@@ -85,23 +99,25 @@ def replay(args, backend=None):
     if kind == 'training_data':
         sys.exit(NO_TRAINING_DATA)
     classify.set_tensorflow_threads(args)
-    model, size, _, _, n_classes, _ = classify.load_and_check_models(args.start_model, None,
-                                                                     args.scan_size)
+    model, size, end_model, end_size, n_classes, _ = classify.load_and_check_models(
+        args.start_model, args.end_model if both_ends else None, args.scan_size)
     scan_size = int(args.scan_size)
     if args.min_windows > scan_size // (size // 2):
         sys.exit('Error: --min_windows cannot be more than the {} windows of --scan_size'
                  .format(scan_size // (size // 2)))
     fast5s = (classify.find_all_fast5s(args.input, verbose=True) if kind == 'directory'
               else [args.input])
-    units = sweep.fast5_units(fast5s, args, classify, KEEP_ALL, (size, None), n_classes,
+    units = sweep.fast5_units(fast5s, args, classify, KEEP_ALL, (size, end_size), n_classes,
                               command='replay')
     reads = enumerate(reads_in_file_order(units, sweep))
     print('', file=sys.stderr)
-    print('\t'.join(HEADER))
+    print('\t'.join(PAIR_HEADER if both_ends else HEADER))
 
+    pair = dict(end_model=end_model, combine=classify.combine_mode(args)) if both_ends else {}
     session = backend.LiveSession(model, args.channels, scan_size=scan_size,
                                   score_diff=args.score_diff, min_windows=args.min_windows,
-                                  stop_on_decision=bool(args.stop_on_decision))
+                                  stop_on_decision=bool(args.stop_on_decision), **pair)
+    sides = {'start only': 0, 'end only': 0, 'both agree': 0, 'both disagree': 0}
     slots = [None] * args.channels              # per channel: [read number, id, signal, position]
     rows, printed = {}, 0                       # finished rows that wait for their turn
     decided_samples, n_reads, n_agree, n_compared, n_late, n_never = [], 0, 0, 0, 0, 0
@@ -125,12 +141,24 @@ def replay(args, backend=None):
                 begin.append(at == 0)
                 end.append(at + args.chunk_samples >= len(signal))
                 slots[ch][3] = at + args.chunk_samples
-            results = session.push(active, chunks, begin=begin, end=end)
-            for ch, result, last in zip(active, results, end):
+            if both_ends:
+                results, end_results = session.push_pair(active, chunks, begin=begin, end=end)
+            else:
+                results = session.push(active, chunks, begin=begin, end=end)
+            for i, (ch, result, last) in enumerate(zip(active, results, end)):
                 if not last:
                     continue
                 number, read_id = slots[ch][0], slots[ch][1]
                 row, decided, agree = result_row(read_id, result, backend, classify.call_name)
+                if both_ends:
+                    ended = end_results[i]
+                    start_call, end_call = int(ended['start_call']), int(ended['end_call'])
+                    row += [classify.call_name(end_call),
+                            classify.call_name(int(ended['read_call']))]
+                    if start_call and end_call:
+                        sides['both agree' if start_call == end_call else 'both disagree'] += 1
+                    elif start_call or end_call:
+                        sides['start only' if start_call else 'end only'] += 1
                 rows[number] = row
                 slots[ch] = None
                 n_reads += 1
@@ -155,3 +183,6 @@ def replay(args, backend=None):
           file=sys.stderr)
     print('  decided later than window {}: {}, never: {}'.format(args.min_windows, n_late, n_never),
           file=sys.stderr)
+    if both_ends:
+        print('  barcode on: ' + ', '.join('{} {}'.format(name, count)
+                                           for name, count in sides.items()), file=sys.stderr)

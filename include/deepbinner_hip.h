@@ -585,6 +585,47 @@ int dbh_locate_occluded_i16(dbh_model* model, const int16_t* samples_host,
  * compile): n_chunks pushes of lengths[i] samples with chunk_flags[i], window k folding to
  * (track_best[k], track_margin[k]) -> results_host[i], the record behind push i, and
  * new_windows_host[i] (may be NULL), the windows that push made ready.
+ *
+ * Pair sessions: the read's full call when it ends.  At the push that carries DBH_LIVE_END the end
+ * of the read is known, and the session gives what classify gives: the end model over the last
+ * scan_size samples (call_batch with side == 'end', classify.py:343-357) and combine_calls
+ * (classify.py:298-322) of the two sides.  _e marks the end model's L, h, steps and cap.
+ *   Session.  dbh_live_create_pair: a start and an end model under the pair conditions of
+ *       dbh_classify_pair_i16 - both non-NULL here, one device, equal n_classes - of either kind
+ *       each; scan_size a positive multiple of h and of h_e; combine_mode one of DBH_REQUIRE_*.
+ *       The other arguments and the whole start side are dbh_live_create's.
+ *   Tail ring.  cap_e more int16 samples per channel: sample p of a read, counted from BEGIN,
+ *       lives at ring[p % cap_e].  A chunk of `length` samples arriving at n stores its last
+ *       min(length, cap_e).  Every chunk of an open read stores, also once the start side is FINAL
+ *       or stopped on a decision; BEGIN resets nothing in the ring - a read's windows read
+ *       positions [max(n - cap_e, 0), n) only, all written by this read.
+ *   End windows.  At END, n final, window s = 0 .. steps_e - 1 in this order: samples [a, b) with
+ *       a = max(n - (s h_e + L_e), 0), b = max(n - s h_e, 0), m = b - a, read out of the ring
+ *       through the wrap, normalised over the m samples present by the scan's front rule, the
+ *       values at out[L_e - m .. L_e), zeros in front.  They go through what dbh_predict_dev
+ *       launches for the end model, in rounds of at most max_round_windows, and through the same
+ *       fold from a fresh record into the end track best[steps_e], margin[steps_e].
+ *   End record.  dbh_live_end_result, 40 bytes, one per chunk: IDLE with -1 calls before any read;
+ *       PENDING with -1 calls from BEGIN on; behind END status FINAL, end_call = the end track's
+ *       last best if it is a barcode leading by score_diff, else 0; start_call = the start
+ *       record's final_call if it is FINAL, else its call (the early call of a read stopped on a
+ *       decision); read_call = combine_calls(start_call, end_call) under combine_mode.  An IDLE
+ *       chunk reports the channel's record as it stands with status DBH_LIVE_IDLE.
+ * dbh_live_push_pair is dbh_live_push with the end records beside the start records; end_results
+ * may be NULL, and dbh_live_push on a pair session is that: the end side still runs, and its record
+ * is read with the channel's next push or through dbh_live_end_track (best / margin hold steps_e
+ * entries; *windows is steps_e behind END, 0 from BEGIN until then).  A push in which no chunk
+ * carries END launches the kernels of a start-only push, no more; still one synchronise per push.
+ * On a session made by dbh_live_create, dbh_live_push_pair with end_results and dbh_live_end_track
+ * are DBH_ERR_INVALID_ARGUMENT.
+ * dbh_live_tail_plan_host runs ONE channel's ring and end-window rules on the host
+ * (dbh_live_core.h), as dbh_live_plan_host does the start side's: for n_chunks pushes of lengths[i]
+ * samples with chunk_flags[i] -> store_host[i][4] = (from, keep, at, head): the chunk's samples
+ * [from, from + keep) go to ring[at ..], head of them before the wrap (zeros for an IDLE chunk);
+ * samples_host[i] = n behind the chunk; ends_host[i] = 1 where the chunk ended an open read, and
+ * there windows_host[i][s][4] = (a, m, pad, ring index of a) of end window s (other chunks' entries
+ * are left alone).
+ *
  * Every entry checks its arguments before any device work and changes no state on error: a null
  * pointer, n_chunks < 0, a channel outside the session or twice in one push, offsets that run
  * backwards, unknown flag bits, the limits of creation: DBH_ERR_INVALID_ARGUMENT.  n_chunks == 0 is
@@ -627,6 +668,27 @@ int dbh_live_plan_host(int input_size, int scan_size, double score_diff, int min
                        uint32_t flags, const int64_t* lengths, const uint32_t* chunk_flags,
                        int64_t n_chunks, const int32_t* track_best, const double* track_margin,
                        dbh_live_result* results_host, int32_t* new_windows_host);
+typedef struct dbh_live_end_result {
+    int32_t status;             /* DBH_LIVE_IDLE; DBH_LIVE_PENDING until END; DBH_LIVE_FINAL behind it */
+    int32_t end_call;           /* -1 until END */
+    int32_t start_call;         /* -1 until END: what went into combine_calls */
+    int32_t read_call;          /* -1 until END */
+    int32_t end_best;           /* of the last end window folded */
+    int32_t end_windows;        /* 0, or steps_e behind END */
+    double end_margin;          /* of the last end window folded */
+    int64_t samples;            /* n */
+} dbh_live_end_result;
+int dbh_live_create_pair(dbh_model* start_model, dbh_model* end_model, int n_channels,
+                         int scan_size, double score_diff, int min_windows, uint32_t flags,
+                         int combine_mode, int64_t max_round_windows, dbh_live_session** session);
+int dbh_live_push_pair(dbh_live_session* session, const int32_t* channels, const int64_t* offsets,
+                       const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+                       dbh_live_end_result* end_results, int64_t n_chunks);
+int dbh_live_end_track(dbh_live_session* session, int channel, int32_t* best, double* margin,
+                       int32_t* windows);
+int dbh_live_tail_plan_host(int end_input_size, int scan_size, const int64_t* lengths,
+                            const uint32_t* chunk_flags, int64_t n_chunks, int64_t* store_host,
+                            int64_t* samples_host, int32_t* ends_host, int64_t* windows_host);
 
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's

@@ -20,6 +20,23 @@ results once; front, forward and fold per forward round; two copies beside them)
 the alternative.  A record, not a bound.
 
     python tools/live_rate.py [--channels 512,3000] [--pushes 200] [--out profiles/live/rate.json]
+
+`--pair` times instead, in the same loop on the same pushes, alternating:
+
+  start_only    the start-only session's push, as above
+  pair          a pair session's push (LiveSession with the shipped end model, push_pair_packed):
+                the ring store in every push, and in a push that ends reads their end windows, the
+                end model's forward rounds, the fold and combine_calls.  Reads end at their natural
+                rate: every read of 6,000 to 20,000 samples once
+  alternative   what there is without a pair session: the start-only push plus one classify_pair
+                call (end model only) per push on the tails - the last scan size + half a window
+                samples, kept by the caller - of the reads that ended in it; the keeping and packing
+                of the tails is not timed
+
+and, apart, pushes in which no read ends, for the cost of the ring store alone.  Median, 99th
+percentile, launches per push; over `--repeats` the median and the range of the medians.
+
+    python tools/live_rate.py --pair --out profiles/live/pair_rate.json
 """
 import argparse
 import json
@@ -47,7 +64,7 @@ class Player:
     """The channels' reads: each one a golden read's start, carried on by its own samples again,
     plus a little noise; lengths 6,000 .. 20,000."""
 
-    def __init__(self, golden, n_channels, seed):
+    def __init__(self, golden, n_channels, seed, keep_whole=False):
         self.rng = np.random.default_rng(seed)
         self.bases = [np.resize(g, 20000 + CHUNK).astype(np.int16) for g in golden]
         self.noise = self.rng.integers(-3, 4, 1 << 22).astype(np.int16)
@@ -59,6 +76,8 @@ class Player:
             self.begin(ch)
             self.at[ch] = -int(self.rng.integers(0, 8)) * CHUNK      # the channels out of step
         self.prefix = np.zeros((n_channels, CAP), np.int16)
+        # --pair: every read whole, for the alternative's tails
+        self.whole = np.zeros((n_channels, 20000 + CHUNK), np.int16) if keep_whole else None
 
     def begin(self, ch):
         self.base[ch] = self.rng.integers(0, len(self.bases))
@@ -78,6 +97,8 @@ class Player:
             part = self.bases[self.base[ch]][at:end] + self.noise[shift:shift + end - at]
             if at < CAP:
                 self.prefix[ch, at:min(end, CAP)] = part[:max(0, min(end, CAP) - at)]
+            if self.whole is not None:
+                self.whole[ch, at:end] = part
             channels.append(ch)
             parts.append(part)
             flags.append((1 if at == 0 else 0) | (2 if end == self.length[ch] else 0))
@@ -91,6 +112,14 @@ class Player:
         for ch, f in zip(channels, flags):
             if f & 2:
                 self.begin(int(ch))
+
+    def tails(self, channels, flags):
+        """(samples, offsets) of the last CAP samples of the reads that ended with this push"""
+        parts = [self.whole[ch, max(0, int(self.at[ch]) - CAP):int(self.at[ch])]
+                 for ch, f in zip(channels, flags) if f & 2]
+        offsets = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([len(p) for p in parts], out=offsets[1:])
+        return (np.concatenate(parts) if parts else np.zeros(0, np.int16)), offsets
 
     def prefixes(self, channels):
         """The alternative's work this round: {scan size: (samples, offsets)} over the channels
@@ -148,6 +177,105 @@ def measure(hb, model, golden, n_channels, opts, seed):
     }
 
 
+def measure_pair(hb, model, end_model, golden, n_channels, opts, seed):
+    player = Player(golden, n_channels, seed, keep_whole=True)
+    start_s, pair_s, alt_s = [], [], []
+    ended, launches_start, launches_pair = [], [], []
+    round_windows = min(n_channels * 12, (64 << 20) // (SIZE * 4))
+    with hb.LiveSession(model, n_channels, scan_size=SCAN) as alone, \
+            hb.LiveSession(model, n_channels, scan_size=SCAN, end_model=end_model) as both:
+        before = np.zeros(n_channels, np.int64)
+        for r in range(opts.warmup + opts.pushes):
+            channels, offsets, samples, flags = player.round()
+            t0 = time.perf_counter()
+            results = alone.push_packed(channels, offsets, samples, flags)
+            t1 = time.perf_counter()
+            got, ends = both.push_pair_packed(channels, offsets, samples, flags)
+            t2 = time.perf_counter()
+            tails, tail_offsets = player.tails(channels, flags)
+            n_ended = len(tail_offsets) - 1
+            t3 = time.perf_counter()
+            if n_ended:
+                end_calls = hb.classify_pair(None, end_model, tails, tail_offsets, SCAN, 0.5)
+            t4 = time.perf_counter()
+            assert got.tobytes() == results.tobytes()
+            if n_ended:
+                assert np.array_equal(ends['end_call'][(flags & 2) != 0], end_calls)
+            new = int((results['windows'] - np.where(flags & 1, 0, before[channels])).sum())
+            before[channels] = results['windows']
+            player.finish(channels, flags)
+            if r >= opts.warmup:
+                start_s.append(t1 - t0)
+                pair_s.append(t2 - t1)
+                alt_s.append((t1 - t0) + (t4 - t3))
+                ended.append(n_ended)
+                k = -(-new // round_windows)
+                launches_start.append(3 + 3 * k)
+                launches_pair.append(3 + 3 * k + 3 * -(-(n_ended * 12) // round_windows))
+        # pushes in which no read ends: every channel begins a 20,000-sample read at once, twelve
+        # chunks of it, three times over (BEGIN inside a read starts anew).  The first five chunks
+        # of a read complete start windows; behind cap the start side stores nothing, and a pair
+        # push is the ring store alone
+        channels = np.arange(n_channels, dtype=np.int32)
+        offsets = np.arange(n_channels + 1, dtype=np.int64) * CHUNK
+        early_start, early_pair, late_start, late_pair = [], [], [], []
+        for r in range(36):
+            samples = np.concatenate([player.bases[(ch + r) % len(player.bases)][
+                (r % 12) * CHUNK:(r % 12 + 1) * CHUNK] for ch in range(n_channels)])
+            flags = np.full(n_channels, 1 if r % 12 == 0 else 0, np.uint32)
+            t0 = time.perf_counter()
+            results = alone.push_packed(channels, offsets, samples, flags)
+            t1 = time.perf_counter()
+            got, _ = both.push_pair_packed(channels, offsets, samples, flags)
+            t2 = time.perf_counter()
+            assert got.tobytes() == results.tobytes()
+            if r >= 12:                                 # (the first read: warm-up of these shapes)
+                (early_start if r % 12 < 5 else late_start).append(t1 - t0)
+                (early_pair if r % 12 < 5 else late_pair).append(t2 - t1)
+    quiet = {'start_only_with_windows': percentiles(early_start),
+             'pair_with_windows': percentiles(early_pair),
+             'start_only_behind_cap': percentiles(late_start),
+             'pair_behind_cap': percentiles(late_pair), 'kernel_launches_per_push': 'the same: '
+             '6 with new windows, 3 behind cap', 'pushes': len(early_start) + len(late_start)}
+    out = {
+        'pushes': len(start_s), 'start_only': percentiles(start_s), 'pair': percentiles(pair_s),
+        'no_read_ends': quiet,
+        'alternative': percentiles(alt_s),
+        'reads_ended_per_push': {'mean': float(np.mean(ended)), 'max': int(np.max(ended))},
+        'kernel_launches_per_push': {
+            'start_only': {'mean': float(np.mean(launches_start)), 'max': int(max(launches_start)),
+                           'copies': 2},
+            'pair': {'mean': float(np.mean(launches_pair)), 'max': int(max(launches_pair)),
+                     'copies': 3}},
+    }
+    return out
+
+
+def spread(values):
+    values = sorted(values)
+    return {'median': values[len(values) // 2], 'min': values[0], 'max': values[-1]}
+
+
+def main_pair(hb, model, golden, opts, record):
+    from deepbinner_amd.model_format import ModelWeights
+    end_model = hb.HipModel(ModelWeights.load(os.path.join(
+        REPO, 'deepbinner_amd', 'models', 'EXP-NBD103_read_ends.dbw'))[0], device=0)
+    record['end_model'] = 'EXP-NBD103_read_ends, persistent kind'
+    for n_channels in [int(v) for v in opts.channels.split(',')]:
+        repeats = [measure_pair(hb, model, end_model, golden, n_channels, opts,
+                                seed=100 * n_channels + k) for k in range(opts.repeats)]
+        entry = {'repeats': repeats}
+        for key in ('start_only', 'pair', 'alternative'):
+            entry[key + '_median_ms'] = spread([rep[key]['median_ms'] for rep in repeats])
+            entry[key + '_p99_ms'] = spread([rep[key]['p99_ms'] for rep in repeats])
+        for key in ('start_only_with_windows', 'pair_with_windows', 'start_only_behind_cap',
+                    'pair_behind_cap'):
+            entry['no_read_ends_' + key + '_median_ms'] = spread(
+                [rep['no_read_ends'][key]['median_ms'] for rep in repeats])
+        entry['pair_share_of_chunk_period'] = entry['pair_median_ms']['median'] / 400.0
+        record['channels'][str(n_channels)] = entry
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument('--channels', type=str, default='512,3000')
@@ -155,6 +283,8 @@ def main():
     ap.add_argument('--warmup', type=int, default=40)
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--out', type=str, default=None)
+    ap.add_argument('--pair', action='store_true',
+                    help='time a pair session beside the start-only one and the alternative')
     opts = ap.parse_args()
     from deepbinner_amd import hip_backend as hb
     from deepbinner_amd.model_format import ModelWeights
@@ -167,7 +297,9 @@ def main():
     record = {'device': hb.device_name(0), 'model': 'EXP-NBD103_read_starts, persistent kind',
               'chunk_samples': CHUNK, 'chunk_period_ms': 400.0, 'scan_size': SCAN,
               'warmup_pushes': opts.warmup, 'channels': {}}
-    for n_channels in [int(v) for v in opts.channels.split(',')]:
+    if opts.pair:
+        main_pair(hb, model, golden, opts, record)
+    for n_channels in [] if opts.pair else [int(v) for v in opts.channels.split(',')]:
         repeats = [measure(hb, model, golden, n_channels, opts, seed=100 * n_channels + k)
                    for k in range(opts.repeats)]
         medians = sorted(rep['push']['median_ms'] for rep in repeats)
