@@ -1698,6 +1698,10 @@ struct dbh_live_session {
     dbh_live::Pair pair{};
     int64_t end_round_windows = 0;
     std::vector<char> end_done;
+    // a yield policy (dbh_live_set_policy; pol.weight null: none): on the device the weights, the
+    // two yields, every channel's action and a push's action records
+    DeviceBlock policy_block;
+    dbh_live::PolicyArgs pol{};
 };
 
 namespace {
@@ -1788,7 +1792,7 @@ int live_create(dbh_model* m, dbh_model* end, int n_channels, int scan_size, dou
 
 int live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
               const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
-              dbh_live_end_result* end_results, int64_t n_chunks);
+              dbh_live_end_result* end_results, dbh_live_action* actions, int64_t n_chunks);
 }  // namespace
 
 extern "C" {
@@ -1825,14 +1829,82 @@ int dbh_live_destroy(dbh_live_session* s) {
 int dbh_live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
                   const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
                   int64_t n_chunks) {
-    return live_push(s, channels, offsets, samples, flags, results, nullptr, n_chunks);
+    return live_push(s, channels, offsets, samples, flags, results, nullptr, nullptr, n_chunks);
 }
 
 int dbh_live_push_pair(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
                        const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
                        dbh_live_end_result* end_results, int64_t n_chunks) {
     if (s && end_results && !s->pair.ring) return DBH_ERR_INVALID_ARGUMENT;
-    return live_push(s, channels, offsets, samples, flags, results, end_results, n_chunks);
+    return live_push(s, channels, offsets, samples, flags, results, end_results, nullptr, n_chunks);
+}
+
+int dbh_live_set_policy(dbh_live_session* s, const int32_t* weights, int n_classes,
+                        int64_t slack_samples, int undecided_action) {
+    if (!s || s->pol.weight || s->pushes != 0 || !weights || n_classes != s->model->n_classes ||
+        !dbh_live::policy_ok(weights, n_classes, slack_samples, undecided_action))
+        return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(s->model->device));
+    const size_t n = (size_t)s->n_channels, C = (size_t)n_classes;
+    dbh_live::PolicyArgs pol{};
+    int32_t* d_weight = nullptr;
+    DBH_HIP(s->policy_block.carve([&](dbh_host::Carve& c) {
+        d_weight = c.take<int32_t>(C);
+        pol.yield_samples = c.take<long long>(C);
+        pol.yield_reads = c.take<long long>(C);
+        pol.channel_action = c.take<int32_t>(n);
+        pol.actions = c.take<dbh_live_action>(n);
+    }));
+    DBH_HIP(s->h_out.reserve(n * (sizeof(dbh_live_result) + sizeof(dbh_live_end_result) +
+                                  sizeof(dbh_live_action))));
+    DBH_HIP(hipMemsetAsync(s->policy_block.get(), 0, s->policy_block.bytes, s->stream));
+    DBH_HIP(hipMemcpyAsync(d_weight, weights, C * sizeof(int32_t), hipMemcpyHostToDevice,
+                           s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    pol.weight = d_weight;
+    pol.n_classes = n_classes;
+    pol.slack = slack_samples;
+    pol.undecided = undecided_action;
+    s->pol = pol;
+    return DBH_OK;
+}
+
+int dbh_live_push_policy(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
+                         const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+                         dbh_live_end_result* end_results, dbh_live_action* actions,
+                         int64_t n_chunks) {
+    if (!s || !s->pol.weight || (end_results && !s->pair.ring) || (n_chunks > 0 && !actions))
+        return DBH_ERR_INVALID_ARGUMENT;
+    return live_push(s, channels, offsets, samples, flags, results, end_results, actions, n_chunks);
+}
+
+int dbh_live_yield(dbh_live_session* s, int64_t* samples_host, int64_t* reads_host) {
+    if (!s || !s->pol.weight) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(s->model->device));
+    const size_t bytes = (size_t)s->pol.n_classes * sizeof(int64_t);
+    if (samples_host)
+        DBH_HIP(hipMemcpyAsync(samples_host, s->pol.yield_samples, bytes, hipMemcpyDeviceToHost,
+                               s->stream));
+    if (reads_host)
+        DBH_HIP(hipMemcpyAsync(reads_host, s->pol.yield_reads, bytes, hipMemcpyDeviceToHost,
+                               s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    return DBH_OK;
+}
+
+int dbh_live_set_yield(dbh_live_session* s, const int64_t* samples_host,
+                       const int64_t* reads_host) {
+    if (!s || !s->pol.weight || !samples_host || !reads_host) return DBH_ERR_INVALID_ARGUMENT;
+    for (int c = 0; c < s->pol.n_classes; ++c)
+        if (samples_host[c] < 0 || reads_host[c] < 0) return DBH_ERR_INVALID_ARGUMENT;
+    DBH_HIP(hipSetDevice(s->model->device));
+    const size_t bytes = (size_t)s->pol.n_classes * sizeof(int64_t);
+    DBH_HIP(hipMemcpyAsync(s->pol.yield_samples, samples_host, bytes, hipMemcpyHostToDevice,
+                           s->stream));
+    DBH_HIP(hipMemcpyAsync(s->pol.yield_reads, reads_host, bytes, hipMemcpyHostToDevice,
+                           s->stream));
+    DBH_HIP(hipStreamSynchronize(s->stream));
+    return DBH_OK;
 }
 
 }  // extern "C"
@@ -1840,7 +1912,7 @@ int dbh_live_push_pair(dbh_live_session* s, const int32_t* channels, const int64
 namespace {
 int live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offsets,
               const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
-              dbh_live_end_result* end_results, int64_t n_chunks) {
+              dbh_live_end_result* end_results, dbh_live_action* actions, int64_t n_chunks) {
     if (!s || n_chunks < 0) return DBH_ERR_INVALID_ARGUMENT;
     if (n_chunks == 0) return DBH_OK;
     if (!channels || !offsets || !samples || !flags || !results || n_chunks > s->n_channels)
@@ -1956,9 +2028,23 @@ int live_push(dbh_live_session* s, const int32_t* channels, const int64_t* offse
     if (d_ends)
         DBH_HIP(hipMemcpyAsync(h_ends, d_ends, n * sizeof(dbh_live_end_result),
                                hipMemcpyDeviceToHost, stream));
+    // a yield policy: the push's ENDs into the yields, then every chunk's action (two launches)
+    dbh_live_action* h_actions = s->h_out.as<dbh_live_action>(
+        n * (sizeof(dbh_live_result) + sizeof(dbh_live_end_result)));
+    if (s->pol.weight) {
+        dbh_live::PolicyArgs pol = s->pol;
+        pol.records = s->d_results;
+        pol.chunks = d_chunks;
+        pol.n_chunks = n_chunks;
+        DBH_HIP(dbh_live::policy(pol, stream));
+        if (actions)
+            DBH_HIP(hipMemcpyAsync(h_actions, pol.actions, n * sizeof(dbh_live_action),
+                                   hipMemcpyDeviceToHost, stream));
+    }
     DBH_HIP(hipStreamSynchronize(stream));
     std::memcpy(results, s->h_out.get(), n * sizeof(dbh_live_result));
     if (d_ends) std::memcpy(end_results, h_ends, n * sizeof(dbh_live_end_result));
+    if (actions) std::memcpy(actions, h_actions, n * sizeof(dbh_live_action));
     for (size_t i = 0; i < n; ++i) {
         if (plan[i].idle) continue;
         s->rec[(size_t)channels[i]] = results[i];       // (the decision is the device's to make)
@@ -2064,6 +2150,84 @@ int dbh_live_tail_plan_host(int end_input_size, int scan_size, const int64_t* le
     dbh_live::plan_tail(shape, (const long long*)lengths, (const unsigned*)chunk_flags,
                         (long long)n_chunks, (long long*)store_host, (long long*)samples_host,
                         (int*)ends_host, (long long*)windows_host);
+    return DBH_OK;
+}
+
+int dbh_live_policy_dev(const dbh_live_result* records_dev, const uint32_t* chunk_flags_dev,
+                        const int32_t* channels_dev, int64_t n_chunks, const int32_t* weights_dev,
+                        int n_classes, int64_t slack_samples, int undecided_action,
+                        int64_t* yield_samples_dev, int64_t* yield_reads_dev,
+                        int32_t* channel_action_dev, dbh_live_action* actions_dev,
+                        dbh_stream stream) {
+    if (n_chunks < 0 || n_chunks > DBH_LIVE_MAX_CHANNELS || n_classes < 1 ||
+        n_classes > dbh_live::kMaxClasses || slack_samples < 0 ||
+        (undecided_action != DBH_LIVE_ACTION_KEEP && undecided_action != DBH_LIVE_ACTION_EJECT))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (!weights_dev || !yield_samples_dev || !yield_reads_dev) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_chunks == 0) return DBH_OK;
+    if (!records_dev || !chunk_flags_dev || !channels_dev || !channel_action_dev || !actions_dev)
+        return DBH_ERR_INVALID_ARGUMENT;
+    dbh_live::PolicyArgs pol{};
+    pol.records = records_dev;
+    pol.chunk_flags = chunk_flags_dev;
+    pol.channels = channels_dev;
+    pol.n_chunks = n_chunks;
+    pol.weight = weights_dev;
+    pol.n_classes = n_classes;
+    pol.slack = slack_samples;
+    pol.undecided = undecided_action;
+    pol.yield_samples = (long long*)yield_samples_dev;
+    pol.yield_reads = (long long*)yield_reads_dev;
+    pol.channel_action = channel_action_dev;
+    pol.actions = actions_dev;
+    DBH_HIP(dbh_live::policy(pol, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_live_policy_plan_host(const int32_t* weights, int n_classes, int64_t slack_samples,
+                              int undecided_action, const int64_t* push_offsets, int64_t n_pushes,
+                              const int32_t* channels_host, const uint32_t* chunk_flags_host,
+                              const dbh_live_result* records_host, int n_channels,
+                              int32_t* channel_action_host, int64_t* yield_samples_host,
+                              int64_t* yield_reads_host, dbh_live_action* actions_host,
+                              int64_t* yield_trace_host) {
+    if (n_pushes < 0 || n_channels < 1 || n_channels > DBH_LIVE_MAX_CHANNELS ||
+        n_classes > dbh_live::kMaxClasses ||
+        !dbh_live::policy_ok(weights, n_classes, slack_samples, undecided_action))
+        return DBH_ERR_INVALID_ARGUMENT;
+    if (!channel_action_host || !yield_samples_host || !yield_reads_host)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int c = 0; c < n_classes; ++c)
+        if (yield_samples_host[c] < 0 || yield_reads_host[c] < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_pushes == 0) return DBH_OK;
+    if (!push_offsets || push_offsets[0] != 0) return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t p = 0; p < n_pushes; ++p)
+        if (push_offsets[p + 1] < push_offsets[p] ||
+            push_offsets[p + 1] - push_offsets[p] > n_channels)
+            return DBH_ERR_INVALID_ARGUMENT;
+    const int64_t total = push_offsets[n_pushes];
+    if (total > 0 && (!channels_host || !chunk_flags_host || !records_host || !actions_host))
+        return DBH_ERR_INVALID_ARGUMENT;
+    std::vector<int64_t> seen((size_t)n_channels, -1);          // the push that last named the channel
+    for (int64_t p = 0; p < n_pushes; ++p)
+        for (int64_t i = push_offsets[p]; i < push_offsets[p + 1]; ++i) {
+            const int32_t ch = channels_host[i];
+            if (ch < 0 || ch >= n_channels || seen[(size_t)ch] == p ||
+                (chunk_flags_host[i] & ~(uint32_t)(DBH_LIVE_BEGIN | DBH_LIVE_END)))
+                return DBH_ERR_INVALID_ARGUMENT;
+            seen[(size_t)ch] = p;
+        }
+    for (int64_t p = 0; p < n_pushes; ++p) {
+        const int64_t at = push_offsets[p];
+        dbh_live::plan_policy_push(weights, n_classes, slack_samples, undecided_action,
+                                   channels_host + at, chunk_flags_host + at, records_host + at,
+                                   push_offsets[p + 1] - at, channel_action_host,
+                                   yield_samples_host, yield_reads_host, actions_host + at);
+        if (!yield_trace_host) continue;
+        int64_t* trace = yield_trace_host + (size_t)p * 2 * n_classes;
+        std::memcpy(trace, yield_samples_host, (size_t)n_classes * sizeof(int64_t));
+        std::memcpy(trace + n_classes, yield_reads_host, (size_t)n_classes * sizeof(int64_t));
+    }
     return DBH_OK;
 }
 

@@ -81,4 +81,27 @@ hipError_t results(const State& st, const Pair& pair, const Chunk* chunks, const
                    int n_chunks, dbh_live_result* results, dbh_live_end_result* end_results,
                    hipStream_t stream);
 
+// The yield policy of a push (dbh_live_core.h, "Yield policies"): the records behind the push with
+// either the push's chunk table or, chunks null, the caller's flags and channels; the session's
+// yields [n_classes] and the channels' actions, in and out; one action record per chunk.
+struct PolicyArgs {
+    const dbh_live_result* records;
+    const Chunk* chunks;
+    const uint32_t* chunk_flags;
+    const int32_t* channels;
+    long long n_chunks;
+    const int32_t* weight;
+    int n_classes;
+    long long slack;
+    int undecided;
+    long long* yield_samples;
+    long long* yield_reads;
+    int32_t* channel_action;
+    dbh_live_action* actions;
+};
+
+// two launches: the yields of the chunks that ended a read (a workgroup per class), then the floor
+// and every chunk's action (a thread per chunk).  n_classes <= kMaxClasses, n_chunks >= 1.
+hipError_t policy(const PolicyArgs& args, hipStream_t stream);
+
 }  // namespace dbh_live

@@ -24,6 +24,12 @@
 //                    on the end model and the end side's record, merged vector and track
 //   results_kernel   the record of every chunk's channel, IDLE for an idle chunk; its pair form
 //                    the end record beside it (dbh_live_core.h's end_record: combine_calls)
+//   yield_kernel     sessions with a yield policy: one workgroup per class sums, over the push's
+//                    chunks, the samples and reads of the records that ended with that call (int64,
+//                    dbh_wave.h's sum) and adds them to the session's yields
+//   action_kernel    the lowest level over the balanced classes by a reduction, then a thread per
+//                    chunk: the action record by dbh_live_core.h's action_of and the channel's
+//                    action, which BEGIN (the chunk's flags) makes NONE again
 //
 // The forward pass between front and fold is what dbh_predict_dev launches, in rounds; a round may
 // end in the middle of a channel's windows, the fold takes up where the record says.  Every loop is
@@ -290,6 +296,73 @@ __global__ __launch_bounds__(kThreads) void results_kernel(State st, Pair pair,
     results[i] = r;
 }
 
+// ---- the yield policy ---------------------------------------------------------------------------
+// The sum over the workgroup's kThreads threads, in thread 0 (int64: a yield passes 2^32 within
+// seconds of sequencing).  part: kThreads / 64 words of LDS; all threads call it, once.
+__device__ __forceinline__ long long block_sum(long long v, long long* part) {
+    v = dbh_wave::wave_sum(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    long long sum = 0;
+    for (int w = 0; w < kThreads / 64; ++w) sum += part[w];
+    return sum;
+}
+
+// (a session's push has its chunk table, dbh_live_policy_dev the caller's two arrays)
+__device__ __forceinline__ unsigned flags_of(const PolicyArgs& a, long long i) {
+    return a.chunks ? a.chunks[i].flags : a.chunk_flags[i];
+}
+
+// One workgroup per class: its threads walk the push's chunks, each summing the records that ended
+// with this class as their call; one sum over the workgroup, and thread 0 adds it to the session's
+// yields.  Integer sums: the same bits in any order.
+__global__ __launch_bounds__(kThreads) void yield_kernel(PolicyArgs a) {
+    __shared__ long long part_samples[kThreads / 64], part_reads[kThreads / 64];
+    const int c = blockIdx.x;
+    long long samples = 0, reads = 0;
+    for (long long i = threadIdx.x; i < a.n_chunks; i += kThreads) {
+        const dbh_live_result r = a.records[i];
+        if (yield_class(r, flags_of(a, i), a.n_classes) == c) {
+            samples += r.samples;
+            reads += 1;
+        }
+    }
+    samples = block_sum(samples, part_samples);
+    reads = block_sum(reads, part_reads);
+    if (threadIdx.x == 0) {
+        a.yield_samples[c] += samples;
+        a.yield_reads[c] += reads;
+    }
+}
+
+// Every workgroup finds the floor for itself - thread c the level of class c (n_classes <=
+// kThreads), the lowest over the workgroup - then one thread per chunk: the action record by
+// dbh_live_core.h's action_of, and the channel's action where the chunk is not idle.
+__global__ __launch_bounds__(kThreads) void action_kernel(PolicyArgs a) {
+    __shared__ long long part[kThreads / 64];
+    const int t = threadIdx.x;
+    long long lowest = kNoLevel;
+    if (t < a.n_classes && balanced(a.weight[t])) lowest = level_of(a.yield_samples[t], a.weight[t]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const long long other = __shfl_xor(lowest, o);
+        lowest = other < lowest ? other : lowest;
+    }
+    if ((t & 63) == 0) part[t >> 6] = lowest;
+    __syncthreads();
+    for (int w = 0; w < kThreads / 64; ++w) lowest = part[w] < lowest ? part[w] : lowest;
+    const long long floor = floor_from(lowest);
+    const long long i = (long long)blockIdx.x * kThreads + t;
+    if (i >= a.n_chunks) return;
+    const dbh_live_result r = a.records[i];
+    const int channel = a.chunks ? a.chunks[i].channel : a.channels[i];
+    const dbh_live_action act =
+        action_of(r, flags_of(a, i), a.channel_action[channel], a.weight, a.n_classes,
+                  (const int64_t*)a.yield_samples, floor, a.slack, a.undecided);
+    a.actions[i] = act;
+    if (r.status != DBH_LIVE_IDLE) a.channel_action[channel] = act.action;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -355,6 +428,16 @@ hipError_t results(const State& st, const Pair& pair, const Chunk* chunks, const
     else
         hipLaunchKernelGGL(results_kernel<false>, grid, dim3(kThreads), 0, stream, st, pair, chunks,
                            (const int*)first, n_chunks, results, end_results);
+    return hipGetLastError();
+}
+
+hipError_t policy(const PolicyArgs& args, hipStream_t stream) {
+    static_assert(kMaxClasses <= kThreads, "action_kernel: thread c holds class c's level");
+    hipLaunchKernelGGL(yield_kernel, dim3((unsigned)args.n_classes), dim3(kThreads), 0, stream, args);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(action_kernel, dim3((unsigned)((args.n_chunks + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, stream, args);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // dbh_live_core.h - the rules of a live session (include/deepbinner_hip.h, "live"; DESIGN.md section
 // 32) that are integers and comparisons: which windows of a channel are ready, what of a chunk is
 // stored, what a folded window does to the channel's record, and - for a pair session - the tail
-// ring, the end windows and the end record.  The GPU's threads (dbh_live.hip),
+// ring, the end windows and the end record; for a session with a yield policy, what a barcode has
+// yielded, its level and the keep / eject action.  The GPU's threads (dbh_live.hip),
 // the session's host mirror (dbh_api.hip: it knows every push's window count without reading the
 // device back) and the CPU model (dbh_live_plan_host; live_model_check.cpp) compile these lines.
 #pragma once
@@ -268,6 +269,119 @@ DBLIVE_FN void plan_tail(const Shape& e, const long long* lengths,
             out[2] = w.pad;
             out[3] = w.at;
         }
+    }
+}
+
+// =============================================================================================
+// Yield policies: keep or eject a read by what its barcode has yielded so
+// far.  Integers only - int64 wherever a yield or a level passes.
+// =============================================================================================
+
+// weight -1: always kept, outside the balance; 0: always ejected; 1 .. 1 << 20: balanced by share
+DBLIVE_FN bool balanced(int weight) { return weight >= 1; }
+
+// what dbh_live_set_policy takes: a weight per class of -1 .. 1 << 20, class 0 kept, slack >= 0,
+// KEEP or EJECT for a read that ends undecided
+DBLIVE_FN bool policy_ok(const int32_t* weight, int n_classes, long long slack, int undecided) {
+    if (!weight || n_classes < 1 || slack < 0) return false;
+    if (undecided != DBH_LIVE_ACTION_KEEP && undecided != DBH_LIVE_ACTION_EJECT) return false;
+    if (weight[0] != -1) return false;
+    for (int c = 0; c < n_classes; ++c)
+        if (weight[c] < -1 || weight[c] > DBH_LIVE_MAX_WEIGHT) return false;
+    return true;
+}
+
+// the class whose yield a chunk's record adds to: its call where the chunk carried END on an open
+// read (an idle chunk's record reports IDLE), else -1
+DBLIVE_FN int yield_class(const dbh_live_result& r, unsigned chunk_flags, int n_classes) {
+    if (r.status == DBH_LIVE_IDLE || !(chunk_flags & DBH_LIVE_END)) return -1;
+    return r.call >= 0 && r.call < n_classes ? r.call : -1;
+}
+
+// a balanced class's level: its yield by its share, rounded down (0 where the class is not balanced)
+DBLIVE_FN long long level_of(long long yield_samples, int weight) {
+    return balanced(weight) ? yield_samples / weight : 0;
+}
+
+// (no balanced class: floor_of's start value, turned into 0 by floor_from)
+constexpr long long kNoLevel = INT64_MAX;
+DBLIVE_FN long long floor_from(long long lowest) { return lowest == kNoLevel ? 0 : lowest; }
+
+// the lowest level of the balanced classes, 0 if there is none (the kernel: a reduction instead)
+DBLIVE_FN long long floor_of(const int32_t* weight, const int64_t* yield_samples, int n_classes) {
+    long long lowest = kNoLevel;
+    for (int c = 0; c < n_classes; ++c)
+        if (balanced(weight[c])) {
+            const long long level = level_of(yield_samples[c], weight[c]);
+            if (level < lowest) lowest = level;
+        }
+    return floor_from(lowest);
+}
+
+DBLIVE_FN dbh_live_action standing_action(int action) {
+    dbh_live_action a;
+    a.action = action;
+    a.reason = DBH_LIVE_REASON_NONE;
+    a.klass = a.reserved = 0;
+    a.level = a.floor = 0;
+    return a;
+}
+
+// The action record of one chunk behind the push's yields.  `standing`: the channel's action in
+// front of this push; BEGIN makes it NONE.  An action that stands, an idle chunk and a read that is
+// neither decided nor FINAL report what stands and nothing else.
+DBLIVE_FN dbh_live_action action_of(const dbh_live_result& r, unsigned chunk_flags, int standing,
+                                    const int32_t* weight, int n_classes,
+                                    const int64_t* yield_samples, long long floor, long long slack,
+                                    int undecided) {
+    if (chunk_flags & DBH_LIVE_BEGIN) standing = DBH_LIVE_ACTION_NONE;
+    dbh_live_action a = standing_action(standing);
+    if (r.status == DBH_LIVE_IDLE || standing != DBH_LIVE_ACTION_NONE) return a;
+    if (r.decided_windows > 0) {
+        const int c = r.call;
+        if (c < 0 || c >= n_classes) return a;                 // (not a call of this model)
+        a.klass = c;
+        a.floor = floor;
+        a.level = level_of(yield_samples[c], weight[c]);
+        if (weight[c] == -1) {
+            a.action = DBH_LIVE_ACTION_KEEP;
+            a.reason = DBH_LIVE_REASON_WEIGHT_KEEP;
+        } else if (weight[c] == 0) {
+            a.action = DBH_LIVE_ACTION_EJECT;
+            a.reason = DBH_LIVE_REASON_WEIGHT_EJECT;
+        } else if (a.level - floor > slack) {                  // (level >= floor >= 0: no overflow)
+            a.action = DBH_LIVE_ACTION_EJECT;
+            a.reason = DBH_LIVE_REASON_OVER_LEVEL;
+        } else {
+            a.action = DBH_LIVE_ACTION_KEEP;
+            a.reason = DBH_LIVE_REASON_BALANCED;
+        }
+    } else if (r.status == DBH_LIVE_FINAL) {
+        a.floor = floor;
+        a.action = undecided;
+        a.reason = DBH_LIVE_REASON_UNDECIDED;
+    }
+    return a;
+}
+
+// One push on the host: the yields of its ENDs, then the floor, then every chunk's action - the
+// order the two kernels run in.  channel_action [channels named], the two yields: in and out.
+DBLIVE_FN void plan_policy_push(const int32_t* weight, int n_classes, long long slack, int undecided,
+                                const int32_t* channels, const uint32_t* chunk_flags,
+                                const dbh_live_result* records, long long n_chunks,
+                                int32_t* channel_action, int64_t* yield_samples,
+                                int64_t* yield_reads, dbh_live_action* actions) {
+    for (long long i = 0; i < n_chunks; ++i) {
+        const int c = yield_class(records[i], chunk_flags[i], n_classes);
+        if (c < 0) continue;
+        yield_samples[c] += records[i].samples;
+        yield_reads[c] += 1;
+    }
+    const long long floor = floor_of(weight, yield_samples, n_classes);
+    for (long long i = 0; i < n_chunks; ++i) {
+        actions[i] = action_of(records[i], chunk_flags[i], channel_action[channels[i]], weight,
+                               n_classes, yield_samples, floor, slack, undecided);
+        if (records[i].status != DBH_LIVE_IDLE) channel_action[channels[i]] = actions[i].action;
     }
 }
 

@@ -8,8 +8,10 @@
 // the end windows (end_window) at every read length 0 .. 3 cap_e + 7 of L = 96 under a set of
 // chunkings - a ring of exactly cap_e samples and beside it who wrote each of them, so that every
 // position an end window reads at END is one this read wrote and holds the right sample -, the
-// host plan entry's form of the same (plan_tail), the end record and the combine rule.  No device,
-// no Python.
+// host plan entry's form of the same (plan_tail), the end record and the combine rule.  The yield
+// policy too (policy_ok, yield_class, level_of, floor_of, action_of, plan_policy_push): random push
+// sequences on 1 to 300 channels and 2 to 256 classes with yields up to 2^50, in heap blocks of
+// exactly the sizes given, against a plain loop written here.  No device, no Python.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -330,6 +332,110 @@ void end_records() {
     if (o.read_call != 0) fail("end record, require start", o.start_call, o.end_call, o.read_call);
 }
 
+// ---- the yield policy ---------------------------------------------------------------------------
+unsigned long long rng_state = 34;
+unsigned long long draw(unsigned long long below) {                 // (a 64-bit LCG's high bits)
+    rng_state = rng_state * 6364136223846793005ULL + 1442695040888963407ULL;
+    return below ? (rng_state >> 20) % below : 0;
+}
+
+// One random session: n_pushes pushes of up to n_channels chunks through plan_policy_push, and the
+// same said again as a plain loop - yields first, then the lowest level, then chunk by chunk.
+void policy_session(int n_channels, int n_classes, int n_pushes) {
+    int32_t* weight = exactly<int32_t>((size_t)n_classes);
+    const int kinds[] = {-1, 0, 1, 2, 7, 1 << 20};
+    for (int c = 0; c < n_classes; ++c) weight[c] = c ? kinds[draw(6)] : -1;
+    const long long slack = draw(3) == 0 ? 0 : (draw(2) ? 5 : 1LL << 40);
+    const int undecided = draw(2) ? DBH_LIVE_ACTION_KEEP : DBH_LIVE_ACTION_EJECT;
+    if (!dbh_live::policy_ok(weight, n_classes, slack, undecided)) fail("policy_ok", n_classes, slack, 0);
+    int64_t* ys = exactly<int64_t>((size_t)n_classes);
+    int64_t* yr = exactly<int64_t>((size_t)n_classes);
+    int64_t* want_ys = exactly<int64_t>((size_t)n_classes);
+    int64_t* want_yr = exactly<int64_t>((size_t)n_classes);
+    for (int c = 0; c < n_classes; ++c) {
+        ys[c] = want_ys[c] = draw(4) ? (int64_t)draw((1ULL << 50) + 1) : (int64_t)(1LL << 50);
+        yr[c] = want_yr[c] = (int64_t)draw(1000);
+    }
+    int32_t* standing = exactly<int32_t>((size_t)n_channels);
+    int32_t* want_standing = exactly<int32_t>((size_t)n_channels);
+    for (int ch = 0; ch < n_channels; ++ch) standing[ch] = want_standing[ch] = DBH_LIVE_ACTION_NONE;
+    std::vector<int> order((size_t)n_channels);
+    for (int ch = 0; ch < n_channels; ++ch) order[(size_t)ch] = ch;
+    for (int p = 0; p < n_pushes; ++p) {
+        const size_t n = (size_t)draw((unsigned long long)n_channels + 1);
+        for (size_t i = 0; i < n; ++i)                              // n distinct channels
+            std::swap(order[i], order[i + (size_t)draw((unsigned long long)n_channels - i)]);
+        int32_t* channels = exactly<int32_t>(n);
+        uint32_t* flags = exactly<uint32_t>(n);
+        dbh_live_result* records = exactly<dbh_live_result>(n);
+        dbh_live_action* actions = exactly<dbh_live_action>(n);
+        for (size_t i = 0; i < n; ++i) {
+            channels[i] = order[i];
+            flags[i] = (uint32_t)draw(4);
+            dbh_live_result r = dbh_live::fresh_record();
+            r.status = (int32_t)draw(4);
+            r.samples = (int64_t)draw(1ULL << 34);
+            if (r.status != DBH_LIVE_PENDING && draw(4)) {
+                r.call = (int32_t)draw((unsigned long long)n_classes);
+                r.decided_windows = r.call ? 1 : 0;
+            }
+            records[i] = r;
+        }
+        dbh_live::plan_policy_push(weight, n_classes, slack, undecided, channels, flags, records,
+                                   (long long)n, standing, ys, yr, actions);
+        // ... and plainly
+        for (size_t i = 0; i < n; ++i)
+            if ((flags[i] & DBH_LIVE_END) && records[i].status != DBH_LIVE_IDLE) {
+                want_ys[records[i].call] += records[i].samples;
+                want_yr[records[i].call] += 1;
+            }
+        bool any = false;
+        long long floor = 0;
+        for (int c = 0; c < n_classes; ++c)
+            if (weight[c] >= 1 && (!any || want_ys[c] / weight[c] < floor)) {
+                floor = want_ys[c] / weight[c];
+                any = true;
+            }
+        for (size_t i = 0; i < n; ++i) {
+            const dbh_live_result& r = records[i];
+            int was = (flags[i] & DBH_LIVE_BEGIN) ? DBH_LIVE_ACTION_NONE : want_standing[channels[i]];
+            dbh_live_action w{was, 0, 0, 0, 0, 0};
+            if (r.status != DBH_LIVE_IDLE && was == DBH_LIVE_ACTION_NONE) {
+                if (r.decided_windows > 0) {
+                    const int wt = weight[r.call];
+                    const long long level = wt >= 1 ? want_ys[r.call] / wt : 0;
+                    w.klass = r.call;
+                    w.level = level;
+                    w.floor = floor;
+                    if (wt == -1) { w.action = DBH_LIVE_ACTION_KEEP; w.reason = DBH_LIVE_REASON_WEIGHT_KEEP; }
+                    else if (wt == 0) { w.action = DBH_LIVE_ACTION_EJECT; w.reason = DBH_LIVE_REASON_WEIGHT_EJECT; }
+                    else if (level > floor + slack) { w.action = DBH_LIVE_ACTION_EJECT; w.reason = DBH_LIVE_REASON_OVER_LEVEL; }
+                    else { w.action = DBH_LIVE_ACTION_KEEP; w.reason = DBH_LIVE_REASON_BALANCED; }
+                } else if (r.status == DBH_LIVE_FINAL) {
+                    w.action = undecided;
+                    w.reason = DBH_LIVE_REASON_UNDECIDED;
+                    w.floor = floor;
+                }
+            }
+            if (r.status != DBH_LIVE_IDLE) want_standing[channels[i]] = w.action;
+            if (std::memcmp(&w, &actions[i], sizeof w) != 0)
+                fail("action", p, (long long)i, actions[i].action * 10 + w.action);
+        }
+        if (std::memcmp(ys, want_ys, (size_t)n_classes * sizeof(int64_t)) != 0 ||
+            std::memcmp(yr, want_yr, (size_t)n_classes * sizeof(int64_t)) != 0)
+            fail("yields", p, n_classes, n_channels);
+        if (std::memcmp(standing, want_standing, (size_t)n_channels * sizeof(int32_t)) != 0)
+            fail("standing actions", p, n_classes, n_channels);
+        std::free(channels);
+        std::free(flags);
+        std::free(records);
+        std::free(actions);
+    }
+    for (void* q : {(void*)weight, (void*)ys, (void*)yr, (void*)want_ys, (void*)want_yr,
+                    (void*)standing, (void*)want_standing})
+        std::free(q);
+}
+
 }  // namespace
 
 int main() {
@@ -378,6 +484,34 @@ int main() {
             if (dbh_live::shape_ok(dbh_live::shape_of(c.L, c.scan, 0.5, c.min_windows, c.flags),
                                    c.scan) != c.ok)
                 fail("shape_ok", c.L, c.scan, c.min_windows);
+    }
+    {   // the yield policy: the sizes at the edges, then random ones
+        const int edges[][2] = {{1, 2}, {300, 256}, {1, 256}, {300, 2}, {64, 13}};
+        for (const auto& e : edges) policy_session(e[0], e[1], 12);
+        for (int trial = 0; trial < 60; ++trial)
+            policy_session(1 + (int)draw(300), 2 + (int)draw(255), 1 + (int)draw(20));
+        // what set_policy refuses
+        const int32_t good[3] = {-1, 1, 0}, kept0[3] = {0, 1, 0}, low[3] = {-1, -2, 0},
+                      high[3] = {-1, (1 << 20) + 1, 0};
+        if (!dbh_live::policy_ok(good, 3, 0, DBH_LIVE_ACTION_KEEP)) fail("policy_ok good", 0, 0, 0);
+        if (dbh_live::policy_ok(kept0, 3, 0, DBH_LIVE_ACTION_KEEP) ||
+            dbh_live::policy_ok(low, 3, 0, DBH_LIVE_ACTION_KEEP) ||
+            dbh_live::policy_ok(high, 3, 0, DBH_LIVE_ACTION_KEEP) ||
+            dbh_live::policy_ok(good, 3, -1, DBH_LIVE_ACTION_KEEP) ||
+            dbh_live::policy_ok(good, 3, 0, DBH_LIVE_ACTION_NONE) ||
+            dbh_live::policy_ok(good, 0, 0, DBH_LIVE_ACTION_KEEP) ||
+            dbh_live::policy_ok(nullptr, 3, 0, DBH_LIVE_ACTION_KEEP))
+            fail("policy_ok refuses", 0, 0, 0);
+        // a yield_class outside the model's classes adds nothing; level_of of an unbalanced class is 0
+        dbh_live_result r = dbh_live::fresh_record();
+        r.status = DBH_LIVE_FINAL;
+        r.call = 3;
+        if (dbh_live::yield_class(r, DBH_LIVE_END, 3) != -1 || dbh_live::yield_class(r, DBH_LIVE_END, 4) != 3 ||
+            dbh_live::yield_class(r, DBH_LIVE_BEGIN, 4) != -1)
+            fail("yield_class", 0, 0, 0);
+        if (dbh_live::level_of(1LL << 50, -1) != 0 || dbh_live::level_of(1LL << 50, 0) != 0 ||
+            dbh_live::level_of((1LL << 50) + 7, 1 << 20) != (1LL << 30))
+            fail("level_of", 0, 0, 0);
     }
     if (failures) {
         std::printf("%d failures\n", failures);

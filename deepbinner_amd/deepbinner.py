@@ -265,6 +265,22 @@ COMMANDS = {
                                         help='Also call each read\'s end barcode when the read '
                                              'ends, and combine the two calls as classify does '
                                              '(needs both models)')),
+                (('--balance',), dict(type=str, default=None, metavar='LIST',
+                                      help='Barcodes to balance: eject a read whose barcode is ahead '
+                                           'of the one that has yielded least (1,2,5; 1:2,2:1 sets '
+                                           'integer shares)')),
+                (('--deplete',), dict(type=str, default=None, metavar='LIST',
+                                      help='Barcodes whose reads are always ejected')),
+                (('--keep',), dict(type=str, default=None, metavar='LIST',
+                                   help='Keep these barcodes and eject every other one')),
+                (('--slack_samples',), dict(type=int, default=0,
+                                            help='How many samples a balanced barcode may be ahead '
+                                                 'before its reads are ejected')),
+                (('--eject_undecided',), dict(action='store_true',
+                                              help='Eject a read that ends without a decision')),
+                (('--eject_samples',), dict(type=int, default=None,
+                                            help='Simulated ejection delay: samples an ejected read '
+                                                 'still delivers (default: one --chunk_samples)')),
                 _HELP]),
 }
 USES_MODELS = ('classify', 'realtime', 'scan', 'locate', 'replay')

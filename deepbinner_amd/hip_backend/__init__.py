@@ -34,9 +34,11 @@ from ._locate import (CELL_SAMPLES, LOCATION, OCCLUDE_PLAN, OCCLUSION, evidence_
                       locate_occluded_packed, locate_occluded_workspace_bytes, locate_packed,
                       locate_rule, locate_rule_dev, locate_workspace_bytes, occlude_plan,
                       occlude_windows)
-from ._live import (LIVE_BEGIN, LIVE_DECIDED, LIVE_END, LIVE_END_RESULT, LIVE_FINAL, LIVE_IDLE,
-                    LIVE_PENDING, LIVE_RESULT, LIVE_STOP_ON_DECISION, LiveSession, live_chunk_flags,
-                    live_fold, live_plan_host, live_tail_plan_host)
+from ._live import (LIVE_ACTION, LIVE_ACTIONS, LIVE_BEGIN, LIVE_DECIDED, LIVE_EJECT, LIVE_END,
+                    LIVE_END_RESULT, LIVE_FINAL, LIVE_IDLE, LIVE_KEEP, LIVE_NO_ACTION, LIVE_PENDING,
+                    LIVE_REASONS, LIVE_RESULT, LIVE_STOP_ON_DECISION, LiveSession,
+                    live_chunk_flags, live_fold, live_plan_host, live_policy_dev,
+                    live_policy_plan_host, live_tail_plan_host)
 from ._model import (INFLATE_SHUFFLE_REFUSED, INFLATE_STORED, INFLATE_STORED_SHUFFLE,
                      INFLATE_STREAM, INFLATE_VBZ, INFLATE_ZLIB, INFLATE_ZLIB_SHUFFLE, HipModel,
                      ModelWeights, _TensorSpec, classify_pair, classify_pair_deflated,

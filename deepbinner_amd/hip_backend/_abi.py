@@ -165,6 +165,14 @@ def _signatures():
         'dbh_live_push_pair': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, c_i64]),
         'dbh_live_end_track': (c_int, [ptr, c_int, ptr, ptr, P(ctypes.c_int32)]),
         'dbh_live_tail_plan_host': (c_int, [c_int, c_int, ptr, ptr, c_i64, ptr, ptr, ptr, ptr]),
+        'dbh_live_set_policy': (c_int, [ptr, ptr, c_int, c_i64, c_int]),
+        'dbh_live_push_policy': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, c_i64]),
+        'dbh_live_yield': (c_int, [ptr, ptr, ptr]),
+        'dbh_live_set_yield': (c_int, [ptr, ptr, ptr]),
+        'dbh_live_policy_dev': (c_int, [ptr, ptr, ptr, c_i64, ptr, c_int, c_i64, c_int, ptr, ptr,
+                                        ptr, ptr, ptr]),
+        'dbh_live_policy_plan_host': (c_int, [ptr, c_int, c_i64, c_int, ptr, c_i64, ptr, ptr, ptr,
+                                              c_int, ptr, ptr, ptr, ptr, ptr]),
         'dbh_stage_floats': (c_int, [c_int, P(c_i64)]),
         'dbh_debug_forward': (c_int, [ptr, f32, c_i64, c_int, f32]),
         'dbh_forward_kernel_info': (c_int, [P(c_int), P(c_int), P(c_int)]),

@@ -1,7 +1,9 @@
 """Live sessions: each channel's barcode called while its signal arrives (include/deepbinner_hip.h,
 "live").  ``LiveSession`` holds the channels' state on the device between pushes - with an ``end_model`` also
-the tail of every open read, and gives the read's full call when it ends; ``live_fold``,
-``live_plan_host`` and ``live_tail_plan_host`` are the parity-only entries of its parts."""
+the tail of every open read, and gives the read's full call when it ends; with a ``policy`` also
+what each barcode has yielded, and gives a keep / eject action with the push that decides.
+``live_fold``, ``live_plan_host``, ``live_tail_plan_host``, ``live_policy_dev`` and
+``live_policy_plan_host`` are the parity-only entries of its parts."""
 
 import ctypes
 
@@ -23,6 +25,13 @@ LIVE_END_RESULT = np.dtype([('status', np.int32), ('end_call', np.int32), ('star
                             ('end_windows', np.int32), ('end_margin', np.float64),
                             ('samples', np.int64)])
 assert LIVE_END_RESULT.itemsize == 40
+# dbh_live_action: what a yield policy says about a chunk's read ("Yield policies")
+LIVE_ACTION = np.dtype([('action', np.int32), ('reason', np.int32), ('klass', np.int32),
+                        ('reserved', np.int32), ('level', np.int64), ('floor', np.int64)])
+assert LIVE_ACTION.itemsize == 32
+LIVE_NO_ACTION, LIVE_KEEP, LIVE_EJECT = 0, 1, 2                      # action
+LIVE_ACTIONS = {'keep': LIVE_KEEP, 'eject': LIVE_EJECT}
+LIVE_REASONS = ('none', 'weight_keep', 'balanced', 'weight_eject', 'over_level', 'undecided')
 
 LIVE_IDLE, LIVE_PENDING, LIVE_DECIDED, LIVE_FINAL = 0, 1, 2, 3       # status
 LIVE_BEGIN, LIVE_END = 1, 2                                          # chunk flags
@@ -46,13 +55,17 @@ class LiveSession(Owner, Scoped, Finalised):
     by ``score_diff``, and FINAL when all ``scan_size`` windows are folded.  With an ``end_model`` (a
     pair session) the push that ends a read also runs the end model over the read's last
     ``scan_size`` samples and combines the two sides under ``combine`` ('either', 'start' or 'both':
-    ``--require_*``): ``push_pair`` returns that beside the start records.  Close it before its
-    models."""
+    ``--require_*``): ``push_pair`` returns that beside the start records.  ``policy``:
+    ``dict(weights=..., slack_samples=0, undecided='keep')`` - int32 weights per class (-1 always
+    keep, 0 always eject, 1 .. 1 << 20 a share of the balance); ``push_policy`` then returns a
+    LIVE_ACTION per chunk beside the records, and ``yields`` what each barcode has yielded.  Close it
+    before its models."""
 
     _held, _release = 'handle', 'dbh_live_destroy'
 
     def __init__(self, model, n_channels, scan_size=6144, score_diff=0.5, min_windows=1,
-                 stop_on_decision=False, max_round_windows=0, end_model=None, combine='either'):
+                 stop_on_decision=False, max_round_windows=0, end_model=None, combine='either',
+                 policy=None):
         self._lib = load_library()
         self.model, self.n_channels, self.scan_size = model, int(n_channels), int(scan_size)
         self.end_model = end_model
@@ -75,8 +88,24 @@ class LiveSession(Owner, Scoped, Finalised):
                                                  int(max_round_windows), ctypes.byref(handle)),
                   'dbh_live_create_pair')
         self.handle = handle.value
+        self.policy = None
+        if policy is not None:
+            try:
+                self._set_policy(**policy)
+            except BaseException:
+                self.close()
+                raise
 
-    def _packed(self, channels, offsets, samples, flags, want_end):
+    def _set_policy(self, weights, slack_samples=0, undecided='keep'):
+        weights = np.ascontiguousarray(weights, dtype=np.int32)
+        if undecided not in LIVE_ACTIONS:
+            raise ValueError("undecided must be 'keep' or 'eject'")
+        check(self._lib.dbh_live_set_policy(self.handle, weights.ctypes.data, len(weights),
+                                            int(slack_samples), LIVE_ACTIONS[undecided]),
+              'dbh_live_set_policy')
+        self.policy = dict(weights=weights, slack_samples=int(slack_samples), undecided=undecided)
+
+    def _packed(self, channels, offsets, samples, flags, want_end, want_actions=False):
         channels = np.ascontiguousarray(channels, dtype=np.int32)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         samples = np.ascontiguousarray(samples, dtype=np.int16)
@@ -87,6 +116,17 @@ class LiveSession(Owner, Scoped, Finalised):
         if samples.size == 0:
             samples = np.zeros(1, dtype=np.int16)           # (a pointer, whatever the chunks hold)
         results = np.zeros(n, dtype=LIVE_RESULT)
+        if want_actions:
+            ends = None
+            if want_end:
+                ends = np.zeros(n, dtype=LIVE_END_RESULT)
+                ends['end_call'] = ends['start_call'] = ends['read_call'] = -1
+            actions = np.zeros(max(n, 1), dtype=LIVE_ACTION)[:n]
+            check(self._lib.dbh_live_push_policy(
+                self.handle, channels.ctypes.data, offsets.ctypes.data, samples.ctypes.data,
+                flags.ctypes.data, results.ctypes.data, None if ends is None else ends.ctypes.data,
+                actions.ctypes.data, n), 'dbh_live_push_policy')
+            return results, ends, actions
         if not want_end:
             check(self._lib.dbh_live_push(self.handle, channels.ctypes.data, offsets.ctypes.data,
                                           samples.ctypes.data, flags.ctypes.data,
@@ -109,6 +149,11 @@ class LiveSession(Owner, Scoped, Finalised):
         """``dbh_live_push_pair`` as it is -> (LIVE_RESULT [n], LIVE_END_RESULT [n])."""
         return self._packed(channels, offsets, samples, flags, True)
 
+    def push_policy_packed(self, channels, offsets, samples, flags):
+        """``dbh_live_push_policy`` as it is -> (LIVE_RESULT [n], LIVE_END_RESULT [n] or None on a
+        start-only session, LIVE_ACTION [n])."""
+        return self._packed(channels, offsets, samples, flags, self.end_model is not None, True)
+
     @staticmethod
     def _pack(chunks):
         chunks = [np.ascontiguousarray(chunk, dtype=np.int16).reshape(-1) for chunk in chunks]
@@ -130,6 +175,31 @@ class LiveSession(Owner, Scoped, Finalised):
         offsets, samples = self._pack(chunks)
         return self.push_pair_packed(channels, offsets, samples,
                                      live_chunk_flags(len(chunks), begin, end))
+
+    def push_policy(self, channels, chunks, begin=None, end=None):
+        """``push`` on a session with a policy -> (LIVE_RESULT [n], LIVE_END_RESULT [n] or None,
+        LIVE_ACTION [n]): the action the policy takes on each chunk's read - with the push that
+        decides it, standing from then on."""
+        offsets, samples = self._pack(chunks)
+        return self.push_policy_packed(channels, offsets, samples,
+                                       live_chunk_flags(len(chunks), begin, end))
+
+    def yields(self):
+        """(samples int64 [C], reads int64 [C]): what the reads that ended with each call held."""
+        n_classes = self.model.n_classes
+        samples, reads = np.zeros(n_classes, np.int64), np.zeros(n_classes, np.int64)
+        check(self._lib.dbh_live_yield(self.handle, samples.ctypes.data, reads.ctypes.data),
+              'dbh_live_yield')
+        return samples, reads
+
+    def set_yields(self, samples, reads):
+        """Seeds the yields: a run taken up again, or yield from before the session."""
+        samples = np.ascontiguousarray(samples, dtype=np.int64)
+        reads = np.ascontiguousarray(reads, dtype=np.int64)
+        if len(samples) != self.model.n_classes or len(reads) != self.model.n_classes:
+            raise ValueError('one yield per class')
+        check(self._lib.dbh_live_set_yield(self.handle, samples.ctypes.data, reads.ctypes.data),
+              'dbh_live_set_yield')
 
     def track(self, channel):
         """(best int32 [windows], margin float64 [windows]) of the channel's read so far: entry k
@@ -232,3 +302,85 @@ def live_tail_plan_host(end_input_size, scan_size, lengths, flags):
         store.ctypes.data, samples.ctypes.data, ends.ctypes.data, windows.ctypes.data),
         'dbh_live_tail_plan_host')
     return store, samples, ends, windows
+
+
+def _policy_arguments(weights, undecided, yield_samples, yield_reads):
+    weights = np.ascontiguousarray(weights, dtype=np.int32)
+    n_classes = len(weights)
+    if undecided not in LIVE_ACTIONS:
+        raise ValueError("undecided must be 'keep' or 'eject'")
+    zeros = np.zeros(n_classes, np.int64)
+    yield_samples = np.array(zeros if yield_samples is None else yield_samples, dtype=np.int64)
+    yield_reads = np.array(zeros if yield_reads is None else yield_reads, dtype=np.int64)
+    if len(yield_samples) != n_classes or len(yield_reads) != n_classes:
+        raise ValueError('one yield per class')
+    return weights, n_classes, yield_samples, yield_reads
+
+
+def live_policy_dev(records, flags, channels, weights, slack_samples=0, undecided='keep',
+                    yield_samples=None, yield_reads=None, channel_action=None):
+    """The two policy kernels alone (``dbh_live_policy_dev``; parity tests): LIVE_RESULT ``records``
+    [n] as a push reports them, chunk ``flags`` [n], ``channels`` [n] (each at most once), the
+    policy, the yields so far (None: zeros) and every channel's action so far (None: NONE for
+    max(channels) + 1 channels).  -> (LIVE_ACTION [n], yield_samples, yield_reads, channel_action)"""
+    records = np.ascontiguousarray(records, dtype=LIVE_RESULT)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32)
+    channels = np.ascontiguousarray(channels, dtype=np.int32)
+    n = len(records)
+    weights, n_classes, yield_samples, yield_reads = _policy_arguments(weights, undecided,
+                                                                       yield_samples, yield_reads)
+    if channel_action is None:
+        channel_action = np.zeros(int(channels.max()) + 1 if n else 1, np.int32)
+    channel_action = np.array(channel_action, dtype=np.int32)
+    if len(flags) != n or len(channels) != n:
+        raise ValueError('one flag and one channel per record')
+    if n and (channels.min() < 0 or channels.max() >= len(channel_action) or
+              len(np.unique(channels)) != n):
+        raise ValueError('each channel once, inside channel_action')
+    actions = np.zeros(max(n, 1), dtype=LIVE_ACTION)
+    pad = lambda a: a if len(a) else np.zeros(1, a.dtype)          # noqa: E731
+    with device_arrays(pad(records), pad(flags), pad(channels), weights, yield_samples, yield_reads,
+                       channel_action, actions) as (d_records, d_flags, d_channels, d_weights,
+                                                    d_samples, d_reads, d_action, d_actions):
+        check(load_library().dbh_live_policy_dev(
+            d_records.ptr, d_flags.ptr, d_channels.ptr, n, d_weights.ptr, n_classes,
+            int(slack_samples), LIVE_ACTIONS[undecided], d_samples.ptr, d_reads.ptr, d_action.ptr,
+            d_actions.ptr, None), 'dbh_live_policy_dev')
+        synchronize()
+        return (d_actions.download(actions.shape, LIVE_ACTION)[:n],
+                d_samples.download((n_classes,), np.int64), d_reads.download((n_classes,), np.int64),
+                d_action.download(channel_action.shape, np.int32))
+
+
+def live_policy_plan_host(pushes, weights, n_channels, slack_samples=0, undecided='keep',
+                          yield_samples=None, yield_reads=None, channel_action=None):
+    """The policy's rules on the host (``dbh_live_policy_plan_host``, the lines the kernels compile)
+    over ``pushes``, each (channels [n], chunk flags [n], LIVE_RESULT records [n]).  -> (a list of
+    LIVE_ACTION [n] per push, yield trace int64 [pushes, 2, C]: samples and reads behind each push,
+    channel_action int32 [n_channels] behind the last)"""
+    weights, n_classes, yield_samples, yield_reads = _policy_arguments(weights, undecided,
+                                                                       yield_samples, yield_reads)
+    channel_action = np.array(np.zeros(n_channels, np.int32) if channel_action is None
+                              else channel_action, dtype=np.int32)
+    if len(channel_action) != n_channels:
+        raise ValueError('one action per channel')
+    sizes = [len(p[0]) for p in pushes]
+    for channels, flags, records in pushes:
+        if len(flags) != len(channels) or len(records) != len(channels):
+            raise ValueError('one flag and one record per channel of a push')
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    total = int(offsets[-1])
+    join = lambda k, dtype: np.ascontiguousarray(                    # noqa: E731
+        np.concatenate([np.asarray(p[k], dtype=dtype) for p in pushes] +
+                       [np.zeros(1, dtype)]), dtype=dtype)
+    channels, flags, records = join(0, np.int32), join(1, np.uint32), join(2, LIVE_RESULT)
+    actions = np.zeros(total + 1, dtype=LIVE_ACTION)
+    trace = np.zeros((max(len(pushes), 1), 2, n_classes), dtype=np.int64)
+    check(load_library().dbh_live_policy_plan_host(
+        weights.ctypes.data, n_classes, int(slack_samples), LIVE_ACTIONS[undecided],
+        offsets.ctypes.data, len(pushes), channels.ctypes.data, flags.ctypes.data,
+        records.ctypes.data, int(n_channels), channel_action.ctypes.data,
+        yield_samples.ctypes.data, yield_reads.ctypes.data, actions.ctypes.data,
+        trace.ctypes.data), 'dbh_live_policy_plan_host')
+    return ([actions[a:b].copy() for a, b in zip(offsets[:-1], offsets[1:])], trace[:len(pushes)],
+            channel_action)

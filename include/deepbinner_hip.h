@@ -628,8 +628,9 @@ int dbh_locate_occluded_i16(dbh_model* model, const int16_t* samples_host,
  *
  * Every entry checks its arguments before any device work and changes no state on error: a null
  * pointer, n_chunks < 0, a channel outside the session or twice in one push, offsets that run
- * backwards, unknown flag bits, the limits of creation: DBH_ERR_INVALID_ARGUMENT.  n_chunks == 0 is
- * DBH_OK. */
+ * backwards, unknown flag bits, the limits of creation, a policy outside its limits, set twice or
+ * behind a push, a negative yield (the policy entries are declared further down):
+ * DBH_ERR_INVALID_ARGUMENT.  n_chunks == 0 is DBH_OK. */
 typedef struct dbh_live_session dbh_live_session;
 #define DBH_LIVE_STOP_ON_DECISION 1      /* session flag */
 #define DBH_LIVE_BEGIN 1                 /* chunk flags */
@@ -689,6 +690,97 @@ int dbh_live_end_track(dbh_live_session* session, int channel, int32_t* best, do
 int dbh_live_tail_plan_host(int end_input_size, int scan_size, const int64_t* lengths,
                             const uint32_t* chunk_flags, int64_t n_chunks, int64_t* store_host,
                             int64_t* samples_host, int32_t* ends_host, int64_t* windows_host);
+/* Yield policies: what to do with the read.  A session with a policy keeps, on the device, how many
+ * samples and reads each barcode has yielded so far, and gives with every push an action per chunk:
+ * keep the read or eject it.  Integers only (dbh_live_core.h: policy_ok, yield_class, level_of,
+ * action_of - the lines the two kernels, the session's host code, dbh_live_policy_plan_host and
+ * live_model_check.cpp compile).  A simulation's building block: checked on recorded reads, not on
+ * a sequencer.
+ *   Policy.  Fixed by dbh_live_set_policy, allowed once, before the first push, on a start-only or
+ *       a pair session: int32 weights[n_classes] (n_classes the model's), int64 slack_samples >= 0,
+ *       undecided_action DBH_LIVE_ACTION_KEEP or _EJECT.  weight -1: the barcode is always kept and
+ *       does not enter the balance; 0: always ejected; 1 .. 1 << 20: balanced with that share.
+ *       weights[0] must be -1 (class 0 is never a decided call).
+ *   State.  Session: yield_samples[n_classes], yield_reads[n_classes], int64, zero at creation.
+ *       Channel: action, int32, NONE from BEGIN on, set once, standing until the next BEGIN.
+ *   Per push, behind the last fold, in this order:
+ *       1. Yield.  Every chunk that carried END on an open read adds its record's samples to
+ *          yield_samples[record.call] and 1 to yield_reads[record.call] (call is 0 until decided).
+ *          All ENDs of a push are added before any action of the push is taken.
+ *       2. Level.  level[c] = yield_samples[c] / weights[c] (int64, floor) where weights[c] >= 1;
+ *          floor = the lowest of these levels, 0 if no class is balanced.
+ *       3. Action, for every chunk that is not IDLE and whose channel's action is NONE: a decided
+ *          record (decided_windows > 0) with call c gets KEEP (WEIGHT_KEEP) for weight -1, EJECT
+ *          (WEIGHT_EJECT) for weight 0, EJECT (OVER_LEVEL) if level[c] - floor > slack_samples,
+ *          else KEEP (BALANCED); a record that is FINAL and undecided gets undecided_action
+ *          (UNDECIDED); any other stays NONE.
+ *       The action changes nothing else: records, end records and tracks are byte for byte those
+ *       of the same pushes through a session without a policy.  The caller acts on EJECT; the read
+ *       ends when it ends, and yield counts what arrived.
+ *   Action record.  dbh_live_action, 32 bytes, one per chunk.  Where the push took the action:
+ *       action, reason, klass = the call acted on (0 for UNDECIDED), level = level[klass] (0 where
+ *       klass is not balanced) and floor, both as the decision saw them.  Else - an IDLE chunk, a
+ *       channel whose action already stands, a read not yet decided - action = the channel's
+ *       action as it stands and every other field 0.
+ * dbh_live_push_policy is dbh_live_push_pair with `actions` beside the records; end_results is NULL
+ * on a start-only session (and may be on a pair session).  dbh_live_push and dbh_live_push_pair on
+ * a policy session still run the policy: the action is then read with the channel's next push.  A
+ * policy push adds two kernel launches and one download to the push and still synchronises once.
+ * On a session without a policy dbh_live_push_policy is DBH_ERR_INVALID_ARGUMENT, and such a
+ * session launches what it launched before.
+ * dbh_live_yield copies the two yield arrays to the host (either may be NULL); dbh_live_set_yield
+ * seeds them (both non-NULL, no negative value): resuming a run, or yield from before the session.
+ * dbh_live_policy_dev is the two kernels alone on the caller's device arrays, for parity tests:
+ * records_dev [n_chunks] as a push's results hold them (status IDLE = an idle chunk), uint32
+ * chunk_flags_dev and int32 channels_dev [n_chunks] (each channel at most once, every one an index
+ * into channel_action_dev), int32 weights_dev [n_classes]; yield_samples_dev / yield_reads_dev
+ * [n_classes] and channel_action_dev go in and out, actions_dev [n_chunks] comes out.  A chunk
+ * whose flags carry BEGIN starts from action NONE.  0 <= n_chunks <= 16,384, 1 <= n_classes <= 256.
+ * dbh_live_policy_plan_host runs the same rules on the host over n_pushes pushes:
+ * push p holds chunks [push_offsets[p], push_offsets[p + 1]) of channels_host / chunk_flags_host /
+ * records_host; channel_action_host [n_channels] and the two yield arrays go in and out (seed them
+ * with zeros for a fresh session), actions_host gets one record per chunk; yield_trace_host (may be
+ * NULL) gets [n_pushes][2][n_classes]: yield_samples, then yield_reads, behind each push. */
+#define DBH_LIVE_ACTION_NONE 0
+#define DBH_LIVE_ACTION_KEEP 1
+#define DBH_LIVE_ACTION_EJECT 2
+#define DBH_LIVE_REASON_NONE 0
+#define DBH_LIVE_REASON_WEIGHT_KEEP 1
+#define DBH_LIVE_REASON_BALANCED 2
+#define DBH_LIVE_REASON_WEIGHT_EJECT 3
+#define DBH_LIVE_REASON_OVER_LEVEL 4
+#define DBH_LIVE_REASON_UNDECIDED 5
+#define DBH_LIVE_MAX_WEIGHT (1 << 20)
+typedef struct dbh_live_action {   /* 32 bytes */
+    int32_t action;                /* DBH_LIVE_ACTION_NONE 0, _KEEP 1, _EJECT 2 */
+    int32_t reason;                /* DBH_LIVE_REASON_* */
+    int32_t klass;                 /* the call acted on, 0 for UNDECIDED / NONE */
+    int32_t reserved;              /* 0 */
+    int64_t level;                 /* level[klass] at the decision, 0 where not balanced */
+    int64_t floor;                 /* at the decision */
+} dbh_live_action;
+int dbh_live_set_policy(dbh_live_session* session, const int32_t* weights, int n_classes,
+                        int64_t slack_samples, int undecided_action);
+int dbh_live_push_policy(dbh_live_session* session, const int32_t* channels, const int64_t* offsets,
+                         const int16_t* samples, const uint32_t* flags, dbh_live_result* results,
+                         dbh_live_end_result* end_results, dbh_live_action* actions,
+                         int64_t n_chunks);
+int dbh_live_yield(dbh_live_session* session, int64_t* samples_host, int64_t* reads_host);
+int dbh_live_set_yield(dbh_live_session* session, const int64_t* samples_host,
+                       const int64_t* reads_host);
+int dbh_live_policy_dev(const dbh_live_result* records_dev, const uint32_t* chunk_flags_dev,
+                        const int32_t* channels_dev, int64_t n_chunks, const int32_t* weights_dev,
+                        int n_classes, int64_t slack_samples, int undecided_action,
+                        int64_t* yield_samples_dev, int64_t* yield_reads_dev,
+                        int32_t* channel_action_dev, dbh_live_action* actions_dev,
+                        dbh_stream stream);
+int dbh_live_policy_plan_host(const int32_t* weights, int n_classes, int64_t slack_samples,
+                              int undecided_action, const int64_t* push_offsets, int64_t n_pushes,
+                              const int32_t* channels_host, const uint32_t* chunk_flags_host,
+                              const dbh_live_result* records_host, int n_channels,
+                              int32_t* channel_action_host, int64_t* yield_samples_host,
+                              int64_t* yield_reads_host, dbh_live_action* actions_host,
+                              int64_t* yield_trace_host);
 
 /* ---- compressed input: the Signal chunks of fast5 files, inflated on the GPU ---------------- */
 /* The reference reads `Signal[:]` through h5py (load_fast5s.py:33-43): libhdf5 runs zlib's

@@ -37,6 +37,19 @@ and, apart, pushes in which no read ends, for the cost of the ring store alone. 
 percentile, launches per push; over `--repeats` the median and the range of the medians.
 
     python tools/live_rate.py --pair --out profiles/live/pair_rate.json
+
+`--policy` times instead, in the same loop on identical chunks, alternating:
+
+  start_only    the start-only session's push, as above
+  policy        the push of a session with a yield policy (barcodes 1, 2, 3 and 12 balanced, the
+                others kept; push_policy_packed): the two policy kernels behind the results kernel
+                and the download of the action records
+
+Median and 99th percentile per repeat, over `--repeats` the median and the range of the medians, the
+kernel launches per push as counted from the code (the policy push: two more), the copies (one
+more) and the synchronises (one each).  The start records of the two pushes are compared as bytes.
+
+    python tools/live_rate.py --policy --out profiles/live/policy_rate.json
 """
 import argparse
 import json
@@ -251,6 +264,65 @@ def measure_pair(hb, model, end_model, golden, n_channels, opts, seed):
     return out
 
 
+def measure_policy(hb, model, golden, n_channels, opts, seed):
+    player = Player(golden, n_channels, seed)
+    weights = np.full(13, -1, np.int32)
+    weights[[1, 2, 3, 12]] = 1
+    start_s, policy_s, launches, ejected, decided = [], [], [], 0, 0
+    round_windows = min(n_channels * 12, (64 << 20) // (SIZE * 4))
+    with hb.LiveSession(model, n_channels, scan_size=SCAN) as alone, \
+            hb.LiveSession(model, n_channels, scan_size=SCAN, policy=dict(weights=weights)) as ruled:
+        before = np.zeros(n_channels, np.int64)
+        for r in range(opts.warmup + opts.pushes):
+            channels, offsets, samples, flags = player.round()
+            order = (alone, ruled) if r % 2 == 0 else (ruled, alone)       # who goes first alternates
+            taken = {}
+            for session in order:
+                t0 = time.perf_counter()
+                if session is alone:
+                    results = session.push_packed(channels, offsets, samples, flags)
+                else:
+                    got, _, actions = session.push_policy_packed(channels, offsets, samples, flags)
+                taken[session is alone] = time.perf_counter() - t0
+            assert got.tobytes() == results.tobytes()
+            new = int((results['windows'] - np.where(flags & 1, 0, before[channels])).sum())
+            before[channels] = results['windows']
+            player.finish(channels, flags)
+            if r >= opts.warmup:
+                start_s.append(taken[True])
+                policy_s.append(taken[False])
+                launches.append(3 + 3 * -(-new // round_windows))
+                took = actions[actions['reason'] != 0]
+                decided += len(took)
+                ejected += int((took['action'] == hb.LIVE_EJECT).sum())
+        yield_samples, yield_reads = ruled.yields()
+    return {
+        'pushes': len(start_s), 'start_only': percentiles(start_s), 'policy': percentiles(policy_s),
+        'kernel_launches_per_push': {
+            'start_only': {'mean': float(np.mean(launches)), 'max': int(max(launches)), 'copies': 2,
+                           'synchronises': 1},
+            'policy': {'mean': float(np.mean(launches)) + 2, 'max': int(max(launches)) + 2,
+                       'copies': 3, 'synchronises': 1}},
+        'actions_taken': decided, 'of_them_eject': ejected,
+        'yield_reads': int(yield_reads.sum()), 'yield_samples': int(yield_samples.sum()),
+    }
+
+
+def main_policy(hb, model, golden, opts, record):
+    record['policy'] = 'barcodes 1, 2, 3, 12 balanced with share 1, slack 0, the others kept'
+    for n_channels in [int(v) for v in opts.channels.split(',')]:
+        repeats = [measure_policy(hb, model, golden, n_channels, opts, seed=100 * n_channels + k)
+                   for k in range(opts.repeats)]
+        entry = {'repeats': repeats}
+        for key in ('start_only', 'policy'):
+            entry[key + '_median_ms'] = spread([rep[key]['median_ms'] for rep in repeats])
+            entry[key + '_p99_ms'] = spread([rep[key]['p99_ms'] for rep in repeats])
+        entry['policy_minus_start_only_median_ms'] = spread(
+            [rep['policy']['median_ms'] - rep['start_only']['median_ms'] for rep in repeats])
+        entry['policy_share_of_chunk_period'] = entry['policy_median_ms']['median'] / 400.0
+        record['channels'][str(n_channels)] = entry
+
+
 def spread(values):
     values = sorted(values)
     return {'median': values[len(values) // 2], 'min': values[0], 'max': values[-1]}
@@ -285,6 +357,8 @@ def main():
     ap.add_argument('--out', type=str, default=None)
     ap.add_argument('--pair', action='store_true',
                     help='time a pair session beside the start-only one and the alternative')
+    ap.add_argument('--policy', action='store_true',
+                    help='time the push of a session with a yield policy beside the start-only one')
     opts = ap.parse_args()
     from deepbinner_amd import hip_backend as hb
     from deepbinner_amd.model_format import ModelWeights
@@ -299,7 +373,9 @@ def main():
               'warmup_pushes': opts.warmup, 'channels': {}}
     if opts.pair:
         main_pair(hb, model, golden, opts, record)
-    for n_channels in [] if opts.pair else [int(v) for v in opts.channels.split(',')]:
+    if opts.policy:
+        main_policy(hb, model, golden, opts, record)
+    for n_channels in [] if opts.pair or opts.policy else [int(v) for v in opts.channels.split(',')]:
         repeats = [measure(hb, model, golden, n_channels, opts, seed=100 * n_channels + k)
                    for k in range(opts.repeats)]
         medians = sorted(rep['push']['median_ms'] for rep in repeats)
