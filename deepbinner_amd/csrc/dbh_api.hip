@@ -33,6 +33,7 @@
 #include "dbh_pack.h"
 #include "dbh_scan.h"
 #include "dbh_status.h"
+#include "dbh_early_core.h"
 #include "dbh_sweep.h"
 
 namespace {
@@ -1154,6 +1155,144 @@ int dbh_sweep_tally(const int32_t* start_best_host, const double* start_margin_h
     std::vector<int64_t> got(cells);
     DBH_HIP(hipMemcpy(got.data(), d_counts, cells * sizeof(int64_t), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < cells; ++i) counts_host[i] += got[i];
+    return DBH_OK;
+}
+
+// ---- the early tally: the live decision of every min_windows and threshold (dbh_early_core.h) ----
+}  // extern "C"
+
+namespace {
+// the arguments of the three early entries (device or host pointers alike) -> P, or 0 if refused
+int early_pushes_ok(const void* start_best, const void* start_margin, const void* end_best,
+                    const void* end_margin, const void* lengths, int64_t n_reads, int steps,
+                    int n_classes, int input_size, int64_t chunk_samples, const void* thresholds,
+                    int n_thresholds, const void* calls, const void* early, const void* windows,
+                    const void* pushes) {
+    if (!start_best || !start_margin || (end_best != nullptr) != (end_margin != nullptr) ||
+        !thresholds || !calls || !early || !windows || (lengths != nullptr) != (pushes != nullptr))
+        return 0;
+    if (!dbh_early::shape_ok(n_reads, steps, n_classes, input_size, chunk_samples, n_thresholds))
+        return 0;
+    return (int)dbh_early::pushes_bound(input_size, (long long)steps * (input_size / 2),
+                                        chunk_samples);
+}
+}  // namespace
+
+extern "C" {
+
+int dbh_sweep_early_pushes(int input_size, int scan_size, int64_t chunk_samples, int* pushes) {
+    if (!pushes || input_size < 2 || input_size % 2 != 0 || chunk_samples < 1 ||
+        dbh_host::model_steps(input_size, scan_size) <= 0)
+        return DBH_ERR_INVALID_ARGUMENT;
+    const long long p = dbh_early::pushes_bound(input_size, scan_size, chunk_samples);
+    if (p > dbh_early::kMaxPushes) return DBH_ERR_INVALID_ARGUMENT;
+    *pushes = (int)p;
+    return DBH_OK;
+}
+
+int dbh_sweep_early_tally_dev(const int32_t* start_best_dev, const double* start_margin_dev,
+                              const int32_t* end_best_dev, const double* end_margin_dev,
+                              const int32_t* labels_dev, const int64_t* lengths_dev,
+                              int64_t n_reads, int steps, int n_classes, int input_size,
+                              int64_t chunk_samples, const double* thresholds_dev,
+                              int n_thresholds, int64_t* calls_dev, int64_t* early_dev,
+                              int64_t* windows_dev, int64_t* pushes_dev, dbh_stream stream) {
+    const int P = early_pushes_ok(start_best_dev, start_margin_dev, end_best_dev, end_margin_dev,
+                                  lengths_dev, n_reads, steps, n_classes, input_size, chunk_samples,
+                                  thresholds_dev, n_thresholds, calls_dev, early_dev, windows_dev,
+                                  pushes_dev);
+    if (P < 1) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    DBH_HIP(dbh_sweep::early_tally(
+        start_best_dev, start_margin_dev, end_best_dev, end_margin_dev, labels_dev, lengths_dev,
+        n_reads, steps, n_classes, input_size, chunk_samples, thresholds_dev, n_thresholds, P,
+        (unsigned long long*)calls_dev, (unsigned long long*)early_dev,
+        (unsigned long long*)windows_dev, (unsigned long long*)pushes_dev, (hipStream_t)stream));
+    return DBH_OK;
+}
+
+int dbh_sweep_early_host(const int32_t* start_best_host, const double* start_margin_host,
+                         const int32_t* end_best_host, const double* end_margin_host,
+                         const int32_t* labels_host, const int64_t* lengths_host, int64_t n_reads,
+                         int steps, int n_classes, int input_size, int64_t chunk_samples,
+                         const double* thresholds_host, int n_thresholds, int64_t* calls_host,
+                         int64_t* early_host, int64_t* windows_host, int64_t* pushes_host) {
+    if (early_pushes_ok(start_best_host, start_margin_host, end_best_host, end_margin_host,
+                        lengths_host, n_reads, steps, n_classes, input_size, chunk_samples,
+                        thresholds_host, n_thresholds, calls_host, early_host, windows_host,
+                        pushes_host) < 1)
+        return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; lengths_host && i < n_reads; ++i)
+        if (lengths_host[i] < 0) return DBH_ERR_INVALID_ARGUMENT;
+    dbh_early::tally_host(start_best_host, start_margin_host, end_best_host, end_margin_host,
+                          labels_host, lengths_host, n_reads, steps, n_classes, input_size,
+                          chunk_samples, thresholds_host, n_thresholds, calls_host, early_host,
+                          windows_host, pushes_host);
+    return DBH_OK;
+}
+
+int dbh_sweep_early_tally(const int32_t* start_best_host, const double* start_margin_host,
+                          const int32_t* end_best_host, const double* end_margin_host,
+                          const int32_t* labels_host, const int64_t* lengths_host, int64_t n_reads,
+                          int steps, int n_classes, int input_size, int64_t chunk_samples,
+                          const double* thresholds_host, int n_thresholds, int64_t* calls_host,
+                          int64_t* early_host, int64_t* windows_host, int64_t* pushes_host) {
+    const int P = early_pushes_ok(start_best_host, start_margin_host, end_best_host,
+                                  end_margin_host, lengths_host, n_reads, steps, n_classes,
+                                  input_size, chunk_samples, thresholds_host, n_thresholds,
+                                  calls_host, early_host, windows_host, pushes_host);
+    if (P < 1) return DBH_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; lengths_host && i < n_reads; ++i)
+        if (lengths_host[i] < 0) return DBH_ERR_INVALID_ARGUMENT;
+    if (n_reads == 0) return DBH_OK;
+    const bool end = end_best_host != nullptr;
+    const size_t per_side = (size_t)n_reads * steps, cells = (size_t)steps * n_thresholds;
+    // the four arrays in one run of int64: calls, early, windows, pushes
+    const size_t n_out[4] = {cells * (end ? 3 : 1) * (n_classes + 3), cells * dbh_early::kColumns,
+                             cells * steps, lengths_host ? cells * P : 0};
+    const size_t n_all = n_out[0] + n_out[1] + n_out[2] + n_out[3];
+    // one block on the calling thread's device, freed on return
+    DeviceBlock block;
+    int32_t *d_best[2] = {nullptr, nullptr}, *d_labels = nullptr;
+    double *d_margin[2] = {nullptr, nullptr}, *d_thresholds = nullptr;
+    int64_t *d_lengths = nullptr, *d_out = nullptr;
+    DBH_HIP(block.carve([&](dbh_host::Carve& c) {
+        d_best[0] = c.take<int32_t>(per_side);
+        d_margin[0] = c.take<double>(per_side);
+        d_best[1] = c.take<int32_t>(end ? per_side : 0);
+        d_margin[1] = c.take<double>(end ? per_side : 0);
+        d_labels = c.take<int32_t>(labels_host ? (size_t)n_reads : 0);
+        d_lengths = c.take<int64_t>(lengths_host ? (size_t)n_reads : 0);
+        d_thresholds = c.take<double>((size_t)n_thresholds);
+        d_out = c.take<int64_t>(n_all);
+    }));
+    const int32_t* const h_best[2] = {start_best_host, end_best_host};
+    const double* const h_margin[2] = {start_margin_host, end_margin_host};
+    for (int j = 0; j < 2; ++j) {
+        if (!h_best[j]) continue;
+        DBH_HIP(hipMemcpy(d_best[j], h_best[j], per_side * sizeof(int32_t), hipMemcpyHostToDevice));
+        DBH_HIP(hipMemcpy(d_margin[j], h_margin[j], per_side * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (labels_host)
+        DBH_HIP(hipMemcpy(d_labels, labels_host, (size_t)n_reads * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (lengths_host)
+        DBH_HIP(hipMemcpy(d_lengths, lengths_host, (size_t)n_reads * sizeof(int64_t), hipMemcpyHostToDevice));
+    DBH_HIP(hipMemcpy(d_thresholds, thresholds_host, (size_t)n_thresholds * sizeof(double), hipMemcpyHostToDevice));
+    DBH_HIP(hipMemset(d_out, 0, n_all * sizeof(int64_t)));
+    int64_t* const d_early = d_out + n_out[0];
+    int64_t* const d_windows = d_early + n_out[1];
+    DBH_HIP(dbh_sweep::early_tally(
+        d_best[0], d_margin[0], end ? d_best[1] : nullptr, end ? d_margin[1] : nullptr,
+        labels_host ? d_labels : nullptr, lengths_host ? d_lengths : nullptr, n_reads, steps,
+        n_classes, input_size, chunk_samples, d_thresholds, n_thresholds, P,
+        (unsigned long long*)d_out, (unsigned long long*)d_early, (unsigned long long*)d_windows,
+        lengths_host ? (unsigned long long*)(d_windows + n_out[2]) : nullptr, 0));
+    std::vector<int64_t> got(n_all);
+    DBH_HIP(hipMemcpy(got.data(), d_out, n_all * sizeof(int64_t), hipMemcpyDeviceToHost));
+    int64_t* const out[4] = {calls_host, early_host, windows_host, pushes_host};
+    size_t at = 0;
+    for (int a = 0; a < 4; ++a)
+        for (size_t i = 0; i < n_out[a]; ++i) out[a][i] += got[at++];
     return DBH_OK;
 }
 

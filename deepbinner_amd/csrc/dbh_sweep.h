@@ -1,6 +1,7 @@
 // dbh_sweep.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_sweep.hip: the
-// fold over scan sizes in its two forms and the tally of outcomes, one launch function each.  No
-// kernel symbol leaves the unit.  The contract is include/deepbinner_hip.h's ("sweep").
+// fold over scan sizes in its two forms, the tally of outcomes and the early tally, one launch
+// function each.  No kernel symbol leaves the unit.  The contract is include/deepbinner_hip.h's
+// ("sweep").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,5 +27,18 @@ hipError_t tally(const int32_t* start_best, const double* start_margin, const in
                  const double* end_margin, const int32_t* labels, int64_t n_reads, int steps,
                  int n_classes, const double* thresholds, int n_thresholds,
                  unsigned long long* counts, hipStream_t stream);
+
+// The early tally (dbh_early_core.h): adds what a live session would have decided at every
+// min_windows 1 .. steps and every threshold into calls[steps][T][modes][n_classes + 3],
+// early[steps][T][8], windows[steps][T][steps] and - with lengths - pushes[steps][T][n_pushes],
+// n_pushes = pushes_bound(): one workgroup per 256 reads.  The end side, labels and lengths (with
+// pushes) may be null; a negative length counts as 0.
+hipError_t early_tally(const int32_t* start_best, const double* start_margin,
+                       const int32_t* end_best, const double* end_margin, const int32_t* labels,
+                       const int64_t* lengths, int64_t n_reads, int steps, int n_classes,
+                       int input_size, int64_t chunk_samples, const double* thresholds,
+                       int n_thresholds, int n_pushes, unsigned long long* calls,
+                       unsigned long long* early, unsigned long long* windows,
+                       unsigned long long* pushes, hipStream_t stream);
 
 }  // namespace dbh_sweep

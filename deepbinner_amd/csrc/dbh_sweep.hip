@@ -22,12 +22,14 @@
 // the margin is a number.
 //
 // tally_kernel counts the outcomes: integers only, so the result depends on neither the launch shape
-// nor on how the reads were split into calls.
+// nor on how the reads were split into calls.  early_kernel counts, from the same start track, what a
+// live session would have decided early at every min_windows and threshold (dbh_early_core.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_early_core.h"
 #include "dbh_fold.h"
 #include "dbh_sweep.h"
 
@@ -150,6 +152,116 @@ __global__ __launch_bounds__(kThreads) void tally_kernel(
     }
 }
 
+// ---- the early tally ----------------------------------------------------------------------------
+// One workgroup per chunk of 256 reads, one read per thread, which keeps its label, length and end
+// call in registers and walks its row of the start track.  Per threshold ONE pass over k from
+// steps - 1 down to 0 keeps the first crossing at or behind k (dbh_early_core.h: step), which is the
+// decision of min_windows = k + 1: the workgroup counts that cell in LDS - the calls, the eight
+// columns (64-bit from the first add), the first kTile bins of the window and push histograms - and
+// adds what is not zero to the caller's arrays; bins from kTile on follow tile by tile.  Every loop
+// runs to a count the host passed, in control flow that is uniform over the workgroup.
+constexpr int kTile = kThreads;         // histogram bins held in LDS at a time: one per thread
+
+struct EarlySink {
+    unsigned *calls_, *windows_, *pushes_;
+    unsigned long long* early_;
+    int width, pushes_end;
+    __device__ void calls(int mode, int column) { atomicAdd(&calls_[mode * width + column], 1u); }
+    __device__ void early(int column, long long value) {
+        atomicAdd(&early_[column], (unsigned long long)value);
+    }
+    __device__ void window(int d) {
+        if (d < kTile) atomicAdd(&windows_[d], 1u);
+    }
+    __device__ void push(long long r) {
+        if (r < pushes_end) atomicAdd(&pushes_[r], 1u);
+    }
+};
+
+// bins [base, base + kTile) of a histogram of `bins` bins: bin `mine` of every thread with `counts`
+__device__ __forceinline__ void early_tile(unsigned* hist, bool counts, long long mine, int base,
+                                           int bins, unsigned long long* out) {
+    const int tid = threadIdx.x;
+    hist[tid] = 0;
+    __syncthreads();
+    if (counts && mine >= base && mine < (long long)base + kTile) atomicAdd(&hist[mine - base], 1u);
+    __syncthreads();
+    if (base + tid < bins && hist[tid]) atomicAdd(&out[base + tid], (unsigned long long)hist[tid]);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kThreads) void early_kernel(
+    const int* __restrict__ start_best, const double* __restrict__ start_margin,
+    const int* __restrict__ end_best, const double* __restrict__ end_margin,
+    const int* __restrict__ labels, const long long* __restrict__ lengths, long long n_reads,
+    int steps, int C, int input_size, long long chunk_samples,
+    const double* __restrict__ thresholds, int n_thresholds, int P,
+    unsigned long long* __restrict__ calls, unsigned long long* __restrict__ early,
+    unsigned long long* __restrict__ windows, unsigned long long* __restrict__ pushes) {
+    __shared__ unsigned h_calls[3 * (kMaxClasses + 3)];
+    __shared__ unsigned h_windows[kTile], h_pushes[kTile];
+    __shared__ unsigned long long h_early[dbh_early::kColumns];
+    const int tid = threadIdx.x;
+    const long long read = (long long)blockIdx.x * kThreads + tid;
+    const bool live = read < n_reads;
+    const bool both = end_best != nullptr, has_len = lengths != nullptr;
+    const int modes = both ? 3 : 1, width = C + 3, n_calls = modes * width;
+    const long long row = read * steps;
+    int label = -1, eb = 0;
+    double em = 0.0;
+    long long len = 0;
+    if (live) {
+        if (labels) label = labels[read];
+        if (both) {
+            eb = end_best[row + steps - 1];
+            em = end_margin[row + steps - 1];
+        }
+        if (has_len) len = lengths[read] > 0 ? lengths[read] : 0;      // (a negative length: 0)
+    }
+    EarlySink sink = {h_calls, h_windows, h_pushes, h_early, width, P < kTile ? P : kTile};
+    for (int t = 0; t < n_thresholds; ++t) {
+        const double threshold = thresholds[t];
+        const int end_call = dbh_early::lead(eb, em, threshold) ? eb : 0;
+        dbh_early::Crossing x = dbh_early::no_crossing();
+        int final_call = 0;
+        for (int k = steps - 1; k >= 0; --k) {
+            if (live) dbh_early::step(&x, k, start_best[row + k], start_margin[row + k], threshold);
+            if (k == steps - 1) final_call = x.call;
+            for (int i = tid; i < n_calls; i += kThreads) h_calls[i] = 0;
+            h_windows[tid] = 0;
+            h_pushes[tid] = 0;
+            if (tid < dbh_early::kColumns) h_early[tid] = 0;
+            __syncthreads();
+            if (live)
+                dbh_early::count_read(sink, x, k, final_call, both, end_call, label, C, has_len, len,
+                                      input_size, chunk_samples);
+            __syncthreads();
+            const long long cell = (long long)k * n_thresholds + t;
+            unsigned long long* cell_windows = windows + cell * steps;
+            unsigned long long* cell_pushes = has_len ? pushes + cell * P : nullptr;
+            for (int i = tid; i < n_calls; i += kThreads)
+                if (h_calls[i]) atomicAdd(&calls[cell * n_calls + i], (unsigned long long)h_calls[i]);
+            if (tid < steps && h_windows[tid])
+                atomicAdd(&cell_windows[tid], (unsigned long long)h_windows[tid]);
+            if (has_len && tid < P && h_pushes[tid])
+                atomicAdd(&cell_pushes[tid], (unsigned long long)h_pushes[tid]);
+            if (tid < dbh_early::kColumns && h_early[tid])
+                atomicAdd(&early[cell * dbh_early::kColumns + tid], h_early[tid]);
+            __syncthreads();
+            // the bins behind the first tile: windows from k's tile on (d >= k), every push tile
+            const bool decided = live && x.d >= 0;
+            for (int base = k / kTile * kTile < kTile ? kTile : k / kTile * kTile; base < steps;
+                 base += kTile)
+                early_tile(h_windows, decided, x.d, base, steps, cell_windows);
+            if (has_len && P > kTile) {
+                const long long r = decided ? dbh_early::push_of(x.d, input_size, len, chunk_samples) : 0;
+                for (int base = kTile; base < P; base += kTile)
+                    early_tile(h_pushes, decided, r - 1, base, P, cell_pushes);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -200,6 +312,32 @@ hipError_t tally(const int32_t* start_best, const double* start_margin, const in
                            end_margin ? end_margin + r0 * steps : nullptr,
                            labels ? (const int*)(labels + r0) : nullptr, (long long)n, steps,
                            n_classes, thresholds, n_thresholds, counts);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t early_tally(const int32_t* start_best, const double* start_margin,
+                       const int32_t* end_best, const double* end_margin, const int32_t* labels,
+                       const int64_t* lengths, int64_t n_reads, int steps, int n_classes,
+                       int input_size, int64_t chunk_samples, const double* thresholds,
+                       int n_thresholds, int n_pushes, unsigned long long* calls,
+                       unsigned long long* early, unsigned long long* windows,
+                       unsigned long long* pushes, hipStream_t stream) {
+    // at most 2^22 workgroups per launch: chunks of 256 reads
+    constexpr int64_t reads_per_launch = ((int64_t)1 << 22) * kThreads;
+    for (int64_t r0 = 0; r0 < n_reads; r0 += reads_per_launch) {
+        const int64_t n = std::min<int64_t>(reads_per_launch, n_reads - r0);
+        const int64_t chunks = (n + kThreads - 1) / kThreads;
+        hipLaunchKernelGGL(early_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, stream,
+                           (const int*)(start_best + r0 * steps), start_margin + r0 * steps,
+                           end_best ? (const int*)(end_best + r0 * steps) : nullptr,
+                           end_margin ? end_margin + r0 * steps : nullptr,
+                           labels ? (const int*)(labels + r0) : nullptr,
+                           lengths ? (const long long*)(lengths + r0) : nullptr, (long long)n, steps,
+                           n_classes, input_size, (long long)chunk_samples, thresholds, n_thresholds,
+                           n_pushes, calls, early, windows, pushes);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -204,7 +204,14 @@ COMMANDS = {
                                         help='Known barcodes of the reads: a sequencing summary '
                                              '(read_id, barcode_arrangement) or a table made '
                                              'with the deepbinner classify command; adds the '
-                                             'right, wrong and missed columns'))]),
+                                             'right, wrong and missed columns')),
+                   (('--live',), dict(action='store_true',
+                                      help='Count instead what replay --stop_on_decision would '
+                                           'decide early at every --min_windows and score '
+                                           'difference')),
+                   (('--chunk_samples',), dict(type=int, default=None,
+                                               help='With --live: samples of a read per push '
+                                                    '(default: 1600, 0.4 s at 4 kHz)'))]),
                ('Performance', [
                    (('--batch_size',), dict(type=int, default=256,
                                             help='Number of reads handed to the GPU per call')),

@@ -26,8 +26,9 @@ from ._abi import (COMBINE_MODES, ERR_COMM, EXPORTED_SYMBOLS, KIND_GENERAL, KIND
 from ._device import (LDS_ARENA_WORDS, DeviceBuffer, Event, Stream, device_arrays, device_count,
                       device_name, fill_lds, get_device, is_pinned, set_device, survey_lds,
                       synchronize, use_pinned_loader_buffers)
-from ._sweep import (SWEEP_MODES, sweep_counts, sweep_pair, sweep_steps, sweep_tally,
-                     sweep_windows)
+from ._sweep import (EARLY_COLUMNS, SWEEP_MODES, sweep_counts, sweep_early_counts,
+                     sweep_early_host, sweep_early_pushes, sweep_early_tally, sweep_pair,
+                     sweep_steps, sweep_tally, sweep_windows)
 from ._scan import (SCAN_EVENT, scan_events, scan_packed, scan_window_count, scan_window_offsets,
                     scan_windows)
 from ._locate import (CELL_SAMPLES, LOCATION, OCCLUDE_PLAN, OCCLUSION, evidence_floats,

@@ -129,6 +129,13 @@ def _signatures():
         'dbh_sweep_tally_dev': (c_int, [ptr, ptr, ptr, ptr, ptr, c_i64, c_int, c_int, ptr, c_int,
                                         ptr, ptr]),
         'dbh_sweep_tally': (c_int, [ptr, ptr, ptr, ptr, ptr, c_i64, c_int, c_int, ptr, c_int, ptr]),
+        'dbh_sweep_early_pushes': (c_int, [c_int, c_int, c_i64, P(c_int)]),
+        'dbh_sweep_early_tally_dev': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_i64, c_int, c_int, c_int,
+                                              c_i64, ptr, c_int, ptr, ptr, ptr, ptr, ptr]),
+        'dbh_sweep_early_tally': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_i64, c_int, c_int, c_int,
+                                          c_i64, ptr, c_int, ptr, ptr, ptr, ptr]),
+        'dbh_sweep_early_host': (c_int, [ptr, ptr, ptr, ptr, ptr, ptr, c_i64, c_int, c_int, c_int,
+                                         c_i64, ptr, c_int, ptr, ptr, ptr, ptr]),
         'dbh_scan_window_count': (c_int, [c_int, c_i64, P(c_i64)]),
         'dbh_scan_window_offsets_dev': (c_int, [ptr, c_i64, c_int, ptr, ptr]),
         'dbh_scan_windows_dev': (c_int, [ptr, ptr, ptr, c_i64, c_int, c_int, c_i64, c_i64, ptr,

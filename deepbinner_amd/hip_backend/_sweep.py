@@ -1,5 +1,7 @@
 """The sweep: calls at every scan size from one window pass, and their tally ("sweep")."""
 
+import ctypes
+
 import numpy as np
 
 from ._abi import _handle, _packed, _ptr, check, load_library
@@ -87,6 +89,79 @@ def sweep_tally(start, end, thresholds, n_classes, labels=None, counts=None):
         int(n_classes), thresholds.ctypes.data if thresholds.size else None, len(thresholds),
         counts.ctypes.data), 'dbh_sweep_tally')
     return counts
+
+
+EARLY_COLUMNS = ('decided', 'agree', 'changed', 'lost', 'late', 'windows', 'samples', 'length')
+
+
+def sweep_early_pushes(input_size, scan_size, chunk_samples):
+    """P = ceil((scan_size + input_size / 2) / chunk_samples): the push by which a replay in chunks
+    of ``chunk_samples`` has folded every window (``dbh_sweep_early_pushes``; above 4096: refused)."""
+    pushes = ctypes.c_int(0)
+    check(load_library().dbh_sweep_early_pushes(int(input_size), int(scan_size), int(chunk_samples),
+                                                ctypes.byref(pushes)), 'dbh_sweep_early_pushes')
+    return pushes.value
+
+
+def sweep_early_counts(steps, n_thresholds, both, n_classes, pushes=None):
+    """The zeroed arrays of ``sweep_early_tally``, all int64 with first axis min_windows - 1:
+    calls [K, T, modes, C + 3] (``sweep_counts``), early [K, T, 8] (EARLY_COLUMNS), windows
+    [K, T, K] and pushes [K, T, ``pushes``] (None without ``pushes``: no read lengths)."""
+    k, t = int(steps), int(n_thresholds)
+    return (sweep_counts(k, t, both, n_classes), np.zeros((k, t, 8), dtype=np.int64),
+            np.zeros((k, t, k), dtype=np.int64),
+            None if pushes is None else np.zeros((k, t, int(pushes)), dtype=np.int64))
+
+
+def _early(entry, start, end, thresholds, n_classes, labels, lengths, input_size, chunk_samples,
+           counts):
+    best = np.ascontiguousarray(start[0], dtype=np.int32)
+    (n, steps), held = best.shape, [best, np.ascontiguousarray(start[1], dtype=np.float64)]
+    both = end is not None and end[0] is not None
+    if both:
+        held += [np.ascontiguousarray(end[0], dtype=np.int32),
+                 np.ascontiguousarray(end[1], dtype=np.float64)]
+    if any(a.shape != (n, steps) for a in held):
+        raise ValueError('best and margin of both sides must be [N, K] alike')
+    thresholds = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    if labels is not None:
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+    if lengths is not None:
+        lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    if any(a is not None and a.shape != (n,) for a in (labels, lengths)):
+        raise ValueError('one label and one length per read')
+    pushes = None if lengths is None else sweep_early_pushes(input_size, steps * (int(input_size) // 2),
+                                                             chunk_samples)
+    fresh = sweep_early_counts(steps, len(thresholds), both, n_classes, pushes)
+    counts = fresh if counts is None else tuple(counts)
+    for got, want in zip(counts, fresh):
+        if (got is None) != (want is None) or (want is not None and (
+                got.shape != want.shape or got.dtype != np.int64 or not got.flags['C_CONTIGUOUS'])):
+            raise ValueError('counts must be the arrays of sweep_early_counts')
+    check(getattr(load_library(), entry)(
+        _ptr(held[0]), _ptr(held[1]), _ptr(held[2]) if both else None,
+        _ptr(held[3]) if both else None, _ptr(labels), _ptr(lengths), n, steps, int(n_classes),
+        int(input_size), int(chunk_samples), thresholds.ctypes.data if thresholds.size else None,
+        len(thresholds), *[_ptr(a) for a in counts]), entry)
+    return counts
+
+
+def sweep_early_tally(start, end, thresholds, n_classes, labels=None, lengths=None, input_size=1024,
+                      chunk_samples=1600, counts=None):
+    """What a live session would have decided early at every ``min_windows`` 1 .. K and every
+    threshold, counted on the device from the tracks of ``sweep_pair`` (``dbh_sweep_early_tally``):
+    ``start`` is required, ``end`` (or None) makes the calls those of a pair session; ``lengths``
+    int64 per read, taken before any clip (None: no pushes, samples or length).  ADDS into ``counts``
+    (``sweep_early_counts``; made when None) and returns (calls, early, windows, pushes)."""
+    return _early('dbh_sweep_early_tally', start, end, thresholds, n_classes, labels, lengths,
+                  input_size, chunk_samples, counts)
+
+
+def sweep_early_host(start, end, thresholds, n_classes, labels=None, lengths=None, input_size=1024,
+                     chunk_samples=1600, counts=None):
+    """``sweep_early_tally`` by the same rule on the host, no device (``dbh_sweep_early_host``)."""
+    return _early('dbh_sweep_early_host', start, end, thresholds, n_classes, labels, lengths,
+                  input_size, chunk_samples, counts)
 
 
 def sweep_windows(model, window_probs):

@@ -16,10 +16,26 @@ and counts the outcomes of every (scan size, threshold, two-model rule) there
 and the table also run against a host stand-in (tests/sweep_reference.py).
 
 ``--devices``: a sweep runs on one GPU; a value above 1 is refused.
+
+``--live`` asks the other question the same pass answers: what ``replay --stop_on_decision`` would
+decide EARLY, while the read arrives in chunks of ``--chunk_samples``, at every ``--min_windows``
+from 1 to the windows of ``--max_scan_size`` and every threshold.  A live session's track is the
+sweep's fold, and its decision is integers and comparisons over that track and the read's length
+(include/deepbinner_hip.h, "early tally"), so the device counts every setting from the one window
+pass (``hip_backend.sweep_early_tally``) where ``replay`` takes one run per setting.  One row per
+(min_windows, score_diff, mode): how many reads were decided, never decided, agree with the call of
+the whole scan, changed, lost it, were decided later than ``min_windows``; the sums of the deciding
+window numbers, of the samples received at the decision and of those reads' lengths; ``push_median``,
+the smallest push by which half of the decided reads were decided (0: none were); then the calls as
+the sweep's table counts them - with two models the read call of a pair session stopped on its
+decision.  The start model is required (``-e`` alone is refused as ``replay`` refuses it) and a
+training-data file is refused.  Recorded reads, as ever: nothing here is checked on a sequencer.
 """
 import sys
 
 import numpy as np
+
+MAX_PUSHES = 4096               # dbh_sweep_early_pushes refuses more
 
 THRESHOLD_RANGE = ('Error: every --score_diffs value must be in the range (0, 1] (greater than 0 '
                    'and less than or equal to 1)')
@@ -137,6 +153,48 @@ def training_batches(path, args, keep):
         yield samples, offsets, np.array([int(label) for label, _ in batch], dtype=np.int32), len(batch)
 
 
+def live_batches(fast5_files, args, classify, keep, sizes, n_classes, labels):
+    """``fast5_batches`` for ``--live``: the loaders keep every read whole, so that its length is
+    known, and the pack clips it here; a fifth value, the lengths (int64), follows."""
+    from .replay import KEEP_ALL
+    for unit in fast5_units(fast5_files, args, classify, KEEP_ALL, sizes, n_classes):
+        if hasattr(unit, 'samples'):
+            signals = [unit.samples[unit.offsets[i]:unit.offsets[i + 1]]
+                       for i in range(len(unit.offsets) - 1)]
+        else:
+            signals = unit.signals
+        lengths = np.array([len(signal) for signal in signals], dtype=np.int64)
+        samples, offsets = pack(signals, keep)
+        known = None
+        if labels is not None:
+            known = np.array([-1 if labels.get(rid) is None else labels[rid] for rid in unit.ids],
+                             dtype=np.int32).reshape(-1)
+        yield samples, offsets, known, unit.n_files, lengths
+
+
+def check_live(args, backend, input_size, max_scan_size, kind):
+    """``--live`` and ``--chunk_samples`` -> chunk_samples (None: not live) and P, or a one-line error."""
+    from .replay import NO_START_MODEL
+    chunk = getattr(args, 'chunk_samples', None)
+    if not getattr(args, 'live', False):
+        if chunk is not None:
+            sys.exit('Error: --chunk_samples needs --live')
+        return None, None
+    chunk = 1600 if chunk is None else int(chunk)
+    if chunk < 1:
+        sys.exit('Error: --chunk_samples must be at least 1')
+    if args.start_model is None:
+        sys.exit(NO_START_MODEL)
+    if kind == 'training_data':
+        sys.exit('Error: a training-data file cannot be swept with --live - its samples are one '
+                 'window long, not reads that arrive')
+    cap = max_scan_size + input_size // 2
+    if -(-cap // chunk) > MAX_PUSHES:
+        sys.exit('Error: --chunk_samples {} takes more than {} pushes to deliver the {} samples a '
+                 'read is called from'.format(chunk, MAX_PUSHES, cap))
+    return chunk, backend.sweep_early_pushes(input_size, max_scan_size, chunk)
+
+
 def sweep(args, backend=None):
     from . import classify
     if backend is None:
@@ -154,6 +212,7 @@ def sweep(args, backend=None):
     keep = classify.scanned_end_samples(max_scan_size, input_size)
 
     kind = classify.determine_input_type(args.input)
+    chunk_samples, pushes = check_live(args, backend, input_size, max_scan_size, kind)
     labels = None
     if kind == 'training_data':
         if start_model is not None and end_model is not None:
@@ -173,25 +232,66 @@ def sweep(args, backend=None):
         total = len(fast5s)
         sizes = (input_size if start_model is not None else None,
                  input_size if end_model is not None else None)
-        batches, what = fast5_batches(fast5s, args, classify, keep, sizes, n_classes, labels), 'fast5s'
+        batches = (live_batches if chunk_samples else fast5_batches)(
+            fast5s, args, classify, keep, sizes, n_classes, labels)
+        what = 'fast5s'
     labelled = kind == 'training_data' or labels is not None
     both = start_model is not None and end_model is not None
 
     print('', file=sys.stderr)
-    counts = backend.sweep_counts(steps, len(thresholds), both, n_classes)
+    if chunk_samples:
+        counts = backend.sweep_early_counts(steps, len(thresholds), both, n_classes, pushes)
+    else:
+        counts = backend.sweep_counts(steps, len(thresholds), both, n_classes)
     done = reads = 0
     classify.print_classification_progress(0, max(total, 1), what)
-    for samples, offsets, known, n_files in batches:
+    for samples, offsets, known, n_files, *lengths in batches:
         n = len(offsets) - 1
         if n > 0:
             start, end = backend.sweep_pair(start_model, end_model, samples, offsets, max_scan_size)
-            backend.sweep_tally(start, end, thresholds, n_classes, known if labelled else None, counts)
+            known = known if labelled else None
+            if chunk_samples:
+                backend.sweep_early_tally(start, end, thresholds, n_classes, known, lengths[0],
+                                          input_size, chunk_samples, counts)
+            else:
+                backend.sweep_tally(start, end, thresholds, n_classes, known, counts)
             reads += n
         done += n_files
         classify.print_classification_progress(min(done, total), max(total, 1), what)
     print('', file=sys.stderr)
-    print_table(counts, [half * k for k in range(1, steps + 1)], thresholds,
-                backend.SWEEP_MODES if both else ('-',), reads, n_classes, labelled)
+    modes = backend.SWEEP_MODES if both else ('-',)
+    if chunk_samples:
+        print_live_table(counts, thresholds, modes, reads, n_classes, labelled)
+    else:
+        print_table(counts, [half * k for k in range(1, steps + 1)], thresholds, modes, reads,
+                    n_classes, labelled)
+
+
+def print_live_table(counts, thresholds, modes, reads, n_classes, labelled):
+    """``--live``: one row per (min_windows, threshold, mode), nested and ordered as ``print_table``'s;
+    the columns of the start side's early decision repeat in each mode's rows."""
+    calls, early, _, pushes = counts
+    columns = ['min_windows', 'score_diff', 'mode', 'reads', 'decided', 'never', 'agree', 'changed',
+               'lost', 'late', 'windows_sum', 'push_median', 'samples_sum', 'length_sum',
+               'classified', 'none']
+    if labelled:
+        columns += ['right', 'wrong', 'missed']
+    print('\t'.join(columns + [str(c) for c in range(1, n_classes)]))
+    for m in range(calls.shape[0]):
+        for t, threshold in enumerate(thresholds):
+            decided, agree, changed, lost, late, windows, samples, length = (
+                int(v) for v in early[m, t])
+            by_push, median = np.cumsum(pushes[m, t]), 0
+            if decided:                 # the smallest push by which half of the decided reads were
+                median = int(np.argmax(2 * by_push >= decided)) + 1
+            for j, mode in enumerate(modes):
+                cell = [int(v) for v in calls[m, t, j]]
+                row = [m + 1, repr(float(threshold)), mode, reads, decided, reads - decided, agree,
+                       changed, lost, late, windows, median, samples, length,
+                       sum(cell[1:n_classes]), cell[0]]
+                if labelled:
+                    row += cell[n_classes:n_classes + 3]
+                print('\t'.join(str(v) for v in row + cell[1:n_classes]))
 
 
 def print_table(counts, scan_sizes, thresholds, modes, reads, n_classes, labelled):

@@ -286,6 +286,62 @@ int dbh_sweep_tally(const int32_t* start_best_host, const double* start_margin_h
                     const int32_t* end_best_host, const double* end_margin_host,
                     const int32_t* labels_host, int64_t n_reads, int steps, int n_classes,
                     const double* thresholds_host, int n_thresholds, int64_t* counts_host);
+/* The early tally: what a live session ("live", below) would have decided EARLY, for every
+ * min_windows m = 1 .. steps and every threshold t, read out of the same start track.  A channel's
+ * track is the sweep's fold under every chunking, and what decides is integers and comparisons over
+ * it and the read's length, so one sweep holds every setting's outcome.  Per read, with L =
+ * input_size, h = L / 2, cap = (steps + 1) h, c = chunk_samples, len = its length:
+ *     lead(k)         = best[k] != 0 && margin[k] >= t          (a NaN margin leads nowhere)
+ *     d               = the smallest k >= m - 1 with lead(k); none: the read is never decided
+ *     call            = best[d], decided_windows = d + 1        (never decided: call 0)
+ *     final_call      = lead(steps - 1) ? best[steps - 1] : 0
+ *     pushes          R = max(1, ceil(len / c)): push r (from 1) brings the read to min(r c, len)
+ *                     samples, the last one carries END - as the replay command delivers a read
+ *     push            r = min(ceil((d h + L) / c), R), decided_samples = min(r c, len)
+ * dbh_sweep_early_pushes gives P = ceil(cap / c), the latest push of any decision; P > 4096 is
+ * refused.  The three tally entries ADD int64 into arrays the caller zeroed, all in C order with
+ * first axis m - 1:
+ *     calls[steps][T][modes][n_classes + 3]   dbh_sweep_tally's cell and its right / wrong / missed,
+ *         of the early call; with an end side (both arrays; modes = 3) of combine_calls(early call,
+ *         end call at t from end track entry steps - 1) under EITHER, START, BOTH - what a pair
+ *         session stopped on its decision reports as read_call.  One side: modes = 1.
+ *     early[steps][T][8]     0 decided: reads with a decision         1 agree: call == final_call
+ *         2 changed: final_call is neither 0 nor call                 3 lost: final_call == 0
+ *         4 late: decided_windows > m       5 windows: sum of decided_windows
+ *         6 samples: sum of decided_samples 7 length: sum of len      (all over decided reads;
+ *         6 and 7 stay 0 without lengths)
+ *     windows[steps][T][steps]   decided reads by decided_windows - 1
+ *     pushes[steps][T][P]        decided reads by r - 1; given exactly when lengths is
+ * The start side is required; the end side, labels and lengths may be NULL.  A best outside
+ * [0, n_classes) leads like any barcode and counts in no class.  A null required pointer, an end
+ * side given by half, n_reads < 0, steps < 1, n_classes outside 2 .. 256, an odd or non-positive
+ * input_size, chunk_samples < 1, P > 4096, n_thresholds < 1, lengths without pushes or the reverse:
+ * DBH_ERR_INVALID_ARGUMENT, nothing written; so is a negative length on the two entries that take
+ * host buffers, while dbh_sweep_early_tally_dev - which does not read its inputs on the host - takes
+ * a negative length as 0.  n_reads == 0 is DBH_OK.  Only integers are added: the result depends
+ * neither on the launch shape nor on how the reads were split into calls.  dbh_sweep_early_tally
+ * works on the calling thread's current device and blocks; dbh_sweep_early_host runs the same rule
+ * (csrc/dbh_early_core.h) on the host, with no device. */
+int dbh_sweep_early_pushes(int input_size, int scan_size, int64_t chunk_samples, int* pushes);
+int dbh_sweep_early_tally_dev(const int32_t* start_best_dev, const double* start_margin_dev,
+                              const int32_t* end_best_dev, const double* end_margin_dev,
+                              const int32_t* labels_dev, const int64_t* lengths_dev,
+                              int64_t n_reads, int steps, int n_classes, int input_size,
+                              int64_t chunk_samples, const double* thresholds_dev,
+                              int n_thresholds, int64_t* calls_dev, int64_t* early_dev,
+                              int64_t* windows_dev, int64_t* pushes_dev, dbh_stream stream);
+int dbh_sweep_early_tally(const int32_t* start_best_host, const double* start_margin_host,
+                          const int32_t* end_best_host, const double* end_margin_host,
+                          const int32_t* labels_host, const int64_t* lengths_host, int64_t n_reads,
+                          int steps, int n_classes, int input_size, int64_t chunk_samples,
+                          const double* thresholds_host, int n_thresholds, int64_t* calls_host,
+                          int64_t* early_host, int64_t* windows_host, int64_t* pushes_host);
+int dbh_sweep_early_host(const int32_t* start_best_host, const double* start_margin_host,
+                         const int32_t* end_best_host, const double* end_margin_host,
+                         const int32_t* labels_host, const int64_t* lengths_host, int64_t n_reads,
+                         int steps, int n_classes, int input_size, int64_t chunk_samples,
+                         const double* thresholds_host, int n_thresholds, int64_t* calls_host,
+                         int64_t* early_host, int64_t* windows_host, int64_t* pushes_host);
 
 /* ---- scan: barcode signal in EVERY window of a read, and the events it makes ------------------ */
 /* call_batch looks at the first (or last) scan_size samples of a read (classify.py:337-357).  A

@@ -16,6 +16,28 @@ After a warm-up of each - in which the sweep's calls at score difference 0.5 are
 the wall time around calls that end synchronised.  A record, not a bound.
 
     python tools/sweep_rate.py [--reads 10000] [--rounds 3]
+
+`--live` times instead what choosing `replay`'s --min_windows and --score_diff
+costs: 10,000 reads of 6,000 to 20,000 samples - two in three with the start of a golden read in
+front, so that barcodes lead - through the shipped start model at scan size 6144 (12 windows), in
+chunks of 1,600 samples:
+
+  sweep_live    what `sweep --live` does per batch: the reads clipped as its pack clips them,
+                hip_backend.sweep_pair, then sweep_early_tally for min_windows 1 .. 12 and nine
+                thresholds (108 settings); the two timed apart, and early_kernel's own time from an
+                event pair around dbh_sweep_early_tally_dev on buffers already on the device
+  sweep_tally   hip_backend.sweep_tally on the same tracks, for scale
+  replay        the only route without it: the loop of `replay --stop_on_decision` (512 channels, one
+                chunk per open read per round, a LiveSession) once per setting, for the SUBSET of
+                settings in the output, at least twelve; `replay_108_scaled` is their median time
+                per setting times 108 - scaled, not run
+
+`--rounds` times over, alternating; medians and ranges.  A last pass with the forward kernel's
+launch tally on counts the windows the sweep ran: one window pass per read is reads x 12.  For every
+replayed setting the counts made from the session's records are compared with the tally's cell.
+A record, not a bound.
+
+    python tools/sweep_rate.py --live        (writes profiles/sweep/live_rate.json, or --out)
 """
 import argparse
 import ctypes
@@ -49,11 +71,167 @@ def spread(values):
     return {'median': values[len(values) // 2], 'min': values[0], 'max': values[-1]}
 
 
+LIVE_SCAN_SIZE, LIVE_CHUNK, LIVE_CHANNELS = 6144, 1600, 512
+# the replayed subset: the corners and the middle of the 12 x 9 grid
+LIVE_SUBSET = [(1, 0.1), (1, 0.5), (1, 0.9), (2, 0.3), (2, 0.5), (3, 0.5), (4, 0.7), (6, 0.1), (6, 0.5),
+               (6, 0.9), (9, 0.5), (12, 0.1), (12, 0.5), (12, 0.9)]
+
+
+def live_reads(n, seed):
+    golden = np.load(os.path.join(REPO, 'tests', 'golden', 'reads.npz'))
+    real = [golden['samples'][golden['offsets'][i]:golden['offsets'][i + 1]] for i in range(7)]
+    rng = np.random.default_rng(seed)
+    lengths = rng.integers(6000, 20001, n)
+    noise = squiggles(64, 20000, seed)
+    reads = []
+    for i, length in enumerate(lengths.tolist()):
+        read = noise[i % 64, :length].copy()
+        if i % 3:
+            front = min(length, len(real[i % 7]), 8000)
+            read[:front] = real[i % 7][:front]
+        reads.append(read)
+    return reads
+
+
+def replay_once(hb, model, reads, m, t):
+    """The loop of the replay command under --stop_on_decision -> the reads' last records."""
+    last = [None] * len(reads)
+    slots, nxt = [None] * LIVE_CHANNELS, 0
+    with hb.LiveSession(model, LIVE_CHANNELS, scan_size=LIVE_SCAN_SIZE, score_diff=t, min_windows=m,
+                        stop_on_decision=True) as session:
+        while True:
+            for ch in range(LIVE_CHANNELS):
+                if slots[ch] is None and nxt < len(reads):
+                    slots[ch], nxt = [nxt, 0], nxt + 1
+            active = [ch for ch in range(LIVE_CHANNELS) if slots[ch] is not None]
+            if not active:
+                return last
+            chunks, begin, end = [], [], []
+            for ch in active:
+                i, at = slots[ch]
+                chunks.append(reads[i][at:at + LIVE_CHUNK])
+                begin.append(at == 0)
+                end.append(at + LIVE_CHUNK >= len(reads[i]))
+                slots[ch][1] = at + LIVE_CHUNK
+            results = session.push(active, chunks, begin=begin, end=end)
+            for ch, result, done in zip(active, results, end):
+                if done:
+                    last[slots[ch][0]] = result.copy()
+                    slots[ch] = None
+
+
+def live(opts):
+    from deepbinner_amd import classify, sweep
+    from deepbinner_amd import hip_backend as hb
+    from deepbinner_amd.model_format import ModelWeights
+    assert hb.device_count() >= 1, 'no HIP device visible'
+    model = hb.HipModel(ModelWeights.load(os.path.join(
+        REPO, 'deepbinner_amd', 'models', 'EXP-NBD103_read_starts.dbw'))[0], device=0)
+    steps = LIVE_SCAN_SIZE // HALF
+    reads = live_reads(opts.reads, 1)
+    lengths = np.array([len(r) for r in reads], dtype=np.int64)
+    keep = classify.scanned_end_samples(LIVE_SCAN_SIZE, 2 * HALF)
+
+    def sweep_pass():
+        t0 = time.perf_counter()
+        samples, offsets = sweep.pack(reads, keep)
+        t1 = time.perf_counter()
+        start, _ = hb.sweep_pair(model, None, samples, offsets, LIVE_SCAN_SIZE)
+        t2 = time.perf_counter()
+        counts = hb.sweep_early_tally(start, None, THRESHOLDS, 13, None, lengths, 2 * HALF, LIVE_CHUNK)
+        t3 = time.perf_counter()
+        hb.sweep_tally(start, None, THRESHOLDS, 13)
+        t4 = time.perf_counter()
+        return start, counts, {'pack': t1 - t0, 'sweep_pair': t2 - t1, 'early_tally': t3 - t2,
+                               'sweep_live': t3 - t0, 'sweep_tally': t4 - t3}
+
+    def kernel_ms(start):
+        """early_kernel alone: an event pair around the device entry, buffers resident."""
+        lib = hb.load_library()
+        pushes = hb.sweep_early_pushes(2 * HALF, LIVE_SCAN_SIZE, LIVE_CHUNK)
+        fresh = hb.sweep_early_counts(steps, len(THRESHOLDS), False, 13, pushes)
+        bufs = [hb.DeviceBuffer.from_array(a) for a in
+                (start[0], start[1], lengths, np.array(THRESHOLDS)) + tuple(fresh)]
+        first, second = hb.Event(), hb.Event()
+        try:
+            hb.synchronize()
+            first.record()
+            hb.check(lib.dbh_sweep_early_tally_dev(
+                bufs[0].ptr, bufs[1].ptr, None, None, None, bufs[2].ptr, len(lengths), steps, 13,
+                2 * HALF, LIVE_CHUNK, bufs[3].ptr, len(THRESHOLDS), *[b.ptr for b in bufs[4:]], None),
+                'dbh_sweep_early_tally_dev')
+            second.record()
+            second.synchronize()
+            return first.elapsed_ms(second)
+        finally:
+            for b in bufs:
+                b.free()
+
+    start, counts, _ = sweep_pass()                            # warm-up
+    replay_once(hb, model, reads[:2 * LIVE_CHANNELS], 1, 0.5)
+    parts = {name: [] for name in ('pack', 'sweep_pair', 'early_tally', 'sweep_live', 'sweep_tally')}
+    kernel, replay_seconds = [], {setting: [] for setting in LIVE_SUBSET}
+    for _ in range(opts.rounds):
+        start, counts, seconds = sweep_pass()
+        for name, value in seconds.items():
+            parts[name].append(value)
+        kernel.append(kernel_ms(start))
+        for m, t in LIVE_SUBSET:
+            t0 = time.perf_counter()
+            last = replay_once(hb, model, reads, m, t)
+            replay_seconds[m, t].append(time.perf_counter() - t0)
+            decided = [r for r in last if int(r['decided_windows']) > 0]
+            cell = counts[1][m - 1, THRESHOLDS.index(t)]
+            assert [len(decided), sum(int(r['decided_windows']) for r in decided),
+                    sum(int(r['decided_samples']) for r in decided)] == \
+                [int(cell[0]), int(cell[5]), int(cell[6])], (m, t)
+    model.timing_enable(1)                                     # the windows the sweep's pass runs
+    model.timing_read()
+    sweep_pass()
+    _, launches, windows = model.timing_read()
+    model.timing_enable(0)
+    per_setting = [spread(s)['median'] for s in replay_seconds.values()]
+    per_setting_median = sorted(per_setting)[len(per_setting) // 2]
+    sweep_live = spread(parts['sweep_live'])
+    out = {
+        'device': hb.device_name(0), 'reads': len(reads), 'samples': int(lengths.sum()),
+        'scan_size': LIVE_SCAN_SIZE, 'chunk_samples': LIVE_CHUNK, 'min_windows': steps,
+        'thresholds': len(THRESHOLDS), 'settings': steps * len(THRESHOLDS), 'rounds': opts.rounds,
+        'seconds': {name: spread(s) for name, s in parts.items()},
+        'early_kernel_ms': spread(kernel),
+        'forward_launches_of_one_pass': launches, 'windows_of_one_pass': windows,
+        'one_window_pass_per_read': windows == len(reads) * steps,
+        'replay_channels': LIVE_CHANNELS,
+        'replay_seconds_per_setting': {'{},{}'.format(m, t): spread(s)
+                                       for (m, t), s in replay_seconds.items()},
+        'replay_settings_run': len(LIVE_SUBSET),
+        'replay_subset_seconds': spread([sum(s[i] for s in replay_seconds.values())
+                                         for i in range(opts.rounds)]),
+        'replay_108_scaled': {'seconds': per_setting_median * steps * len(THRESHOLDS),
+                              'how': 'median seconds per replayed setting x 108; scaled, not run'},
+        'replay_108_scaled_over_sweep_live': per_setting_median * steps * len(THRESHOLDS) / sweep_live['median'],
+        'early_tally_over_sweep_tally': spread(parts['early_tally'])['median'] / spread(parts['sweep_tally'])['median'],
+        'decided_at_1_0.5': int(counts[1][0, THRESHOLDS.index(0.5), 0]),
+        'same_counts_as_replay': True}
+    text = json.dumps(out, indent=1)
+    print(text, flush=True)
+    if opts.out:
+        os.makedirs(os.path.dirname(os.path.abspath(opts.out)), exist_ok=True)
+        with open(opts.out, 'w') as f:
+            f.write(text + '\n')
+    model.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument('--reads', type=int, default=10000)
     ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--live', action='store_true')
+    ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'sweep', 'live_rate.json'),
+                    help='with --live: where the record is written')
     opts = ap.parse_args()
+    if opts.live:
+        return live(opts)
     from deepbinner_amd import hip_backend as hb
     from deepbinner_amd.model_format import ModelWeights
     assert hb.device_count() >= 1, 'no HIP device visible'
