@@ -22,6 +22,7 @@ from .load_fast5s import (find_all_fast5s, get_read_id_and_signal,
                           determine_single_or_multi_fast5s, LoaderPool, choose_loader_procs,
                           reader_kind)
 from .misc import print_summary_table, usable_cpus      # noqa: F401 (the tools' classify.usable_cpus)
+from .pod5_lite import is_pod5
 from .model_format import ModelWeights
 from .trim_signal import normalise
 
@@ -110,6 +111,9 @@ def classify(args):
     """``deepbinner classify`` (reference classify.py:32-55): load the model(s), work out what
     ``args.input`` is and hand it to the matching driver."""
     set_tensorflow_threads(args)
+    _POD5_OPENED.clear()
+    if is_pod5(args.input) and os.path.isfile(str(args.input)):
+        check_pod5_files([args.input])      # (a refused file ends the run before a model is loaded)
     *models, model_count = load_and_check_models(args.start_model, args.end_model, args.scan_size)
 
     kind = determine_input_type(args.input)
@@ -120,13 +124,16 @@ def classify(args):
         classify_training_data(args.input, *models, args)
         return
     print('', file=sys.stderr)
-    assert kind in ('directory', 'single_fast5')
+    assert kind in ('directory', 'single_fast5', 'single_pod5')
     from . import sharding
     rank, _, world = sharding.env_world()
-    if kind == 'single_fast5' and world > 1 and rank != 0:
+    if kind != 'directory' and world > 1 and rank != 0:
         return          # one file is one rank's work: rank 0 classifies and prints it
-    fast5s = find_all_fast5s(args.input, verbose=True) if kind == 'directory' else [args.input]
+    fast5s = (find_all_fast5s(args.input, verbose=True, pod5=True) if kind == 'directory'
+              else [args.input])
     if kind == 'directory' and world > 1:
+        if any(is_pod5(f) for f in fast5s):
+            sys.exit('Error: POD5 files are not sharded over one process per GPU - use --devices')
         # one process per GPU (torch.distributed.run): shard the reads, gather the calls
         sharding.classify_fast5_files_sharded(fast5s, *models, args)
     else:
@@ -191,8 +198,11 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
     out_dest = sys.stderr if full_output else sys.stdout
 
     multi_read = bool(getattr(args, 'multi_read', False))      # --multi_read: containers welcome
-    if not verified_single_read and not multi_read:
-        if determine_single_or_multi_fast5s(fast5_files) == 'multi':
+    pod5s = [f for f in fast5_files if is_pod5(f)]             # (a POD5 file needs no --multi_read)
+    check_pod5_files(pod5s)
+    one_read_files = [f for f in fast5_files if not is_pod5(f)]
+    if not verified_single_read and not multi_read and one_read_files:
+        if determine_single_or_multi_fast5s(one_read_files) == 'multi':
             sys.exit('Error: deepbinner classify requires one-read-per-file fast5s - convert with '
                      'multi_to_single_fast5 before running')
 
@@ -211,14 +221,14 @@ def classify_fast5_files(fast5_files, start_model, start_input_size, end_model, 
                 print(line)
 
     def progress(finished):
-        # (--multi_read counts files, where a file may hold any number of reads)
-        print_classification_progress(finished if multi_read else len(classifications),
+        # (--multi_read and POD5 count files, where a file may hold any number of reads)
+        print_classification_progress(finished if multi_read or pod5s else len(classifications),
                                       len(fast5_files), 'fast5s', out_dest=out_dest)
 
     finished = tabulate_units(
         classify_units(fast5_files, start_model, start_input_size, end_model, end_input_size,
                        output_size, args), classifications, read_id_to_fast5_file, rows, progress)
-    if multi_read and finished < len(fast5_files):      # (files without a readable read, last)
+    if (multi_read or pod5s) and finished < len(fast5_files):   # (files without a readable read, last)
         progress(len(fast5_files))
 
     if full_output:
@@ -252,8 +262,9 @@ def classify_units(fast5_files, start_model, start_input_size, end_model, end_in
     a directory of one-read files goes through the one-read batches, and a container met there is
     set aside and classified after them."""
     from . import containers
-    fast5_files = list(fast5_files)
-    if not fast5_files:
+    pod5s = [f for f in fast5_files if is_pod5(f)]
+    fast5_files = [f for f in fast5_files if not is_pod5(f)]
+    if not fast5_files and not pod5s:
         return
     units = containers.Units(args, start_input_size, end_input_size, output_size,
                              keep=scanned_end_samples(args.scan_size, start_input_size,
@@ -262,7 +273,9 @@ def classify_units(fast5_files, start_model, start_input_size, end_model, end_in
                              skip_damaged=True)
     multi_read = bool(getattr(args, 'multi_read', False))
     later = [] if multi_read else None
-    if multi_read and determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
+    if not fast5_files:
+        pass
+    elif multi_read and determine_single_or_multi_fast5s(fast5_files, mixed_ok=True) == 'multi':
         later = fast5_files
     else:
         singles = fast5_files
@@ -277,6 +290,65 @@ def classify_units(fast5_files, start_model, start_input_size, end_model, end_in
     if later:
         with containers.route(later, start_model, end_model, units) as results:
             yield from results
+    if pod5s:           # POD5 files behind the fast5 files, each a container of its own
+        with containers.route(pod5s, start_model, end_model, units, pod5=True) as results:
+            yield from results
+
+
+_POD5_OPENED = {}       # path -> pod5_lite.Pod5, from check_pod5_files until its units take it
+
+
+def check_pod5_files(pod5s):
+    """A POD5 file the reader refuses ends the run before anything is classified, in one line that
+    names the file.  The files stay open for their units (opened_pod5): a
+    file is parsed once."""
+    if not pod5s:
+        return
+    from . import pod5_lite
+    for path in pod5s:
+        if str(path) in _POD5_OPENED:
+            continue
+        try:
+            _POD5_OPENED[str(path)] = pod5_lite.open(path)
+        except pod5_lite.Pod5Error as refused:
+            _POD5_OPENED.clear()
+            sys.exit('Error: {}'.format(refused))
+    if any(pod5.compressed for pod5 in _POD5_OPENED.values()):
+        try:
+            pod5_lite._zstd()       # (the host's last word needs it: say so now, in one line)
+        except pod5_lite.Pod5Error as missing:
+            _POD5_OPENED.clear()
+            sys.exit('Error: {}'.format(missing))
+
+
+def opened_pod5(path):
+    """The open file check_pod5_files left for ``path`` (handed over once), or a fresh one."""
+    from . import pod5_lite
+    pod5 = _POD5_OPENED.pop(str(path), None)
+    return pod5 if pod5 is not None else pod5_lite.open(path)
+
+
+def refuse_pod5(path, command):
+    """``sweep``, ``scan``, ``locate`` and ``replay`` take packed units of whole batches from the
+    fast5 loaders (sweep.fast5_units), ``realtime`` bins the fast5 files of a watched directory by
+    writing fast5 files: a ``.pod5`` path - or, for ``realtime``, a directory that holds POD5 files,
+    which it would otherwise wait beside for ever - is refused in one line."""
+    if is_pod5(path):
+        sys.exit('Error: deepbinner {} does not read POD5 files ({}) - deepbinner classify '
+                 'does'.format(command, path))
+    if command == 'realtime' and os.path.isdir(str(path)):
+        for _, _, names in os.walk(str(path)):
+            held = [name for name in names if is_pod5(name)]
+            if held:
+                sys.exit('Error: deepbinner realtime does not read POD5 files ({} holds {}) - '
+                         'deepbinner classify does'.format(path, held[0]))
+
+
+def warn_about_pod5_read(path, read_id):
+    """A read of a POD5 file whose rows are not what the reads table says, or do not decode, is
+    skipped, as a damaged read of a fast5 container is - with a line on stderr."""
+    print('\nWarning: skipping read {} of {}: its signal rows cannot be decoded'
+          .format(read_id, path), file=sys.stderr)
 
 
 def _python_holds_several_reads(fast5_file):
@@ -623,7 +695,8 @@ def classify_training_data(input_file, start_model, start_input_size, end_model,
 
 
 def determine_input_type(input_file_or_dir):
-    """'directory' | 'single_fast5' | 'training_data' (reference classify.py:242-263): a file that
+    """'directory' | 'single_fast5' | 'single_pod5' (a file named ``*.pod5``; not in the
+    reference) | 'training_data' (reference classify.py:242-263): a file that
     is not HDF5 counts as training data when its first line is ``<int>TAB<int>,<int>,...`` with
     more than ten values."""
     path = pathlib.Path(input_file_or_dir)
@@ -631,6 +704,8 @@ def determine_input_type(input_file_or_dir):
         return 'directory'
     if not path.is_file():
         sys.exit('Error: {} is neither a file nor a directory'.format(input_file_or_dir))
+    if is_pod5(path):
+        return 'single_pod5'
     try:
         hdf5_lite.File(str(path), 'r').close()
     except OSError:

@@ -2,7 +2,8 @@
 The units of work of the classify path, shared by ``deepbinner classify`` (which tabulates their
 reads) and ``deepbinner realtime`` (which bins them).  A unit is a multi-read fast5 container - the
 reference unpacks one with an external tool first (realtime.py:183-190) and refuses it in
-``classify`` (classify.py:113-116); here its reads are classified where they are - or a batch of
+``classify`` (classify.py:113-116); here its reads are classified where they are - or a POD5 file
+(``Pod5Container``: the same, its signal rows read by ``pod5_lite``) - or a batch of
 one-read files, which is a container whose reads happen to live in separate files: its ``origin``
 (``Container`` / ``OneReadFiles``) says which file read i is and reads it again through the host's
 loader, and nothing else tells the two apart.  A unit goes one of three routes:
@@ -70,6 +71,33 @@ class Container:
             return fast5_native.load_reads(self.path, first=i, count=1, threads=1)
         except OSError:
             return None, None, None, np.ones(1, dtype=np.int32)
+
+
+class Pod5Container:
+    """The origin of a unit whose reads are reads ``first`` onwards of one POD5 file (``pod5``: the
+    open ``pod5_lite.Pod5``, shared by the file's units); dealt and given CUs like ``Container``."""
+    files = None
+    reserves_cus = True
+
+    def __init__(self, path, pod5=None, first=0):
+        self.path, self.pod5, self.first = path, pod5, int(first)
+
+    def reread(self, i):
+        """Read i of the unit decoded on the host (``pod5_lite.signal``), which has the last word
+        -> (ids, samples, offsets, status)."""
+        from . import fast5_native, pod5_lite
+        if self.pod5 is None:
+            self.pod5 = classify.opened_pod5(self.path)
+        k = self.first + i
+        try:
+            signal = pod5_lite.signal(self.pod5, k)
+        except OSError:                         # (no libzstd on this host)
+            signal = None
+        if signal is None:
+            classify.warn_about_pod5_read(self.path, self.pod5.read_ids[k])
+            return None, None, None, np.full(1, fast5_native.F5_ERR_FORMAT, dtype=np.int32)
+        return ([self.pod5.read_ids[k]], signal, np.array([0, len(signal)], dtype=np.int64),
+                np.zeros(1, dtype=np.int32))
 
 
 class OneReadFiles:
@@ -289,6 +317,85 @@ def read_chunks(fast5s, units):
                        signals=[r[1] for r in chunk])
 
 
+# ---- the units of POD5 files --------------------------------------------------------------------
+def pod5_host_only():
+    """Whether POD5 files are decoded on the host (the lists route): only where the GPU inflate is
+    switched off in so many words - DEEPBINNER_GPU_INFLATE=0, or DEEPBINNER_HOST_INFLATE_SHARE=100.
+    A host with cores to spare (``realtime.host_inflate_share``'s rule for fast5, where the C++
+    loader's thread team is then as fast as the GPU) changes nothing here: the alternative to the
+    kernels is NumPy on one thread."""
+    if os.environ.get('DEEPBINNER_GPU_INFLATE') == '0':
+        return True
+    if os.environ.get('DEEPBINNER_GPU_INFLATE') == '1':
+        return False
+    explicit = os.environ.get('DEEPBINNER_HOST_INFLATE_SHARE')
+    return bool(explicit) and int(explicit) >= 100
+
+
+def pod5_raw_units(pod5s, units):
+    """Raw units of at most ``pod5_lite.READS_PER_UNIT`` reads per POD5 file, in order: one record
+    per signal row, the rows' zstd frames undone here or left to the GPU (DEEPBINNER_VBZ_ZSTD);
+    the next unit is put together on a background thread while the caller classifies this one."""
+    from . import pod5_lite
+    zstd = pod5_lite.zstd_route()
+    opened = {}
+
+    def chunks():
+        for number, path in enumerate(pod5s, start=1):
+            try:
+                pod5 = opened[path] = classify.opened_pod5(path)
+            except OSError:
+                continue
+            firsts = list(range(0, len(pod5), pod5_lite.READS_PER_UNIT))
+            for first in firsts:
+                yield number, path, first, first == firsts[-1]
+
+    def load(chunk):
+        _, path, first, _ = chunk
+        return pod5_lite.raw_unit(opened[path], first, pod5_lite.READS_PER_UNIT, zstd=zstd,
+                                  threads=units.threads)
+
+    for (number, path, first, last), (ids, offsets, comp, records) in loaded_ahead(
+            chunks(), load, 1, 1):
+        pod5 = opened[path]
+        for k, rid in enumerate(ids):
+            if rid is None:
+                classify.warn_about_pod5_read(path, pod5.read_ids[first + k])
+        if all(rid is None for rid in ids):     # (nothing for the device: no unit, as for a
+            continue                            #  container nobody could open)
+        yield Unit(Pod5Container(path, pod5, first), ids, number, last=last, offsets=offsets,
+                   comp=comp, records=records)
+
+
+def pod5_chunks(pod5s, units):
+    """The same files read on the host (``pod5_lite.signal``): a lists unit per --batch_size
+    reads, handed on as soon as its reads are decoded (one unit's signals are held at a time); a
+    read that is refused is dropped."""
+    from . import pod5_lite
+    size = max(1, int(units.args.batch_size))
+    for number, path in enumerate(pod5s, start=1):
+        try:
+            pod5 = classify.opened_pod5(path)
+        except OSError:
+            continue
+        ids, signals = [], []
+        for i, read_id in enumerate(pod5.read_ids):
+            try:
+                signal = pod5_lite.signal(pod5, i)
+            except OSError:                     # (no libzstd: said once by classify)
+                signal = None
+            if signal is None:
+                classify.warn_about_pod5_read(path, read_id)
+                continue
+            ids.append(read_id)
+            signals.append(signal)
+            if len(ids) == size and i + 1 < len(pod5):
+                yield Unit(Pod5Container(path, pod5), ids, number, last=False, signals=signals)
+                ids, signals = [], []
+        if ids:
+            yield Unit(Pod5Container(path, pod5), ids, number, last=True, signals=signals)
+
+
 # ---- the units of one-read files ------------------------------------------------------------------
 def loader_threads(args):
     """The native loader's threads for a batch of one-read files: ``--loader_procs``, or one per
@@ -383,13 +490,16 @@ def list_batch(loaded):
 # ---- the route choice -----------------------------------------------------------------------------
 @contextlib.contextmanager
 def route(fast5s, start_model, end_model, units, one_read=False, set_aside=None,
-          host_loader=False):
+          host_loader=False, pod5=False):
     """The files ``fast5s`` - multi-read containers, or with ``one_read`` one-read files - by the
     route this process takes: the ``Result`` of every unit, in order (``classify.dispatch_batches``
     deals the units to the (start, end) replica pairs), for as long as the ``with`` lasts; behind
     it the raw route's inflate queues have given their CUs back (``reserve_cus(0)``).
     ``set_aside`` (one-read files): see ``containers_among``.  ``host_loader``: one-read files
-    through ``classify.load_in_batches`` whatever ``classify.raw_inflate_share`` says."""
+    through ``classify.load_in_batches`` whatever ``classify.raw_inflate_share`` says.  ``pod5``:
+    the files are POD5 files - the raw route (``pod5_raw_units``) on every host, whichever fast5
+    reader this process has, unless the GPU inflate is switched off (``pod5_host_only``) or the
+    models are stand-ins without a device handle: then the lists route."""
     from . import realtime
     models = [m for m in (start_model, end_model) if m is not None]
     packed = reader_kind() == 'native' and all(hasattr(m, 'classify_packed') for m in models)
@@ -399,6 +509,9 @@ def route(fast5s, start_model, end_model, units, one_read=False, set_aside=None,
         host_share = None if host_loader else classify.raw_inflate_share(
             start_model, end_model, units.args, len(fast5s), replicas)
         raw = host_share is not None
+    elif pod5:
+        host_share = 100 if pod5_host_only() else 0     # (no share in between: every row is the GPU's)
+        raw = host_share < 100 and all(hasattr(m, 'handle') for m in models)
     else:
         host_share = realtime.host_inflate_share(n_gpus)
         raw = packed and host_share < 100 and all(hasattr(m, 'handle') for m in models)
@@ -407,7 +520,10 @@ def route(fast5s, start_model, end_model, units, one_read=False, set_aside=None,
         # several units in flight per GPU, each on a replica of the models
         replicas, queues = realtime.inflate_queues(replicas, host_share)
         items, work = (raw_batches(fast5s, units, host_share, len(replicas), set_aside) if one_read
+                       else pod5_raw_units(fast5s, units) if pod5
                        else raw_containers(fast5s, units, host_share, n_gpus)), classify_raw
+    elif pod5:
+        items, work = pod5_chunks(fast5s, units), classify_lists
     elif one_read:
         items = classify.load_in_batches(fast5s, units.args, units.keep, set_aside)
         work = classify_packed if reader_kind() == 'native' else classify_lists

@@ -29,7 +29,8 @@
 // prefix to every kernel here (zlib_view); its bytes are de-interleaved behind them (dbh_vbz.hip).
 // Streams of mode DBH_INFLATE_VBZ (ONT's VBZ filter, zstd stage undone by the loader) and
 // DBH_INFLATE_VBZ_ZSTD (the chunk as stored) are no kernel's here: both kernels pass them by, and
-// dbh_zstd.hip's and dbh_vbz.hip's kernels, launched behind them by dbh_inflate_dev, decode them.
+// dbh_zstd.hip's and dbh_vbz.hip's kernels, launched behind them by dbh_inflate_dev, decode them;
+// so are DBH_INFLATE_SVB16 and DBH_INFLATE_SVB16_ZSTD, the rows of a POD5 signal table.
 // What dbh_inflate_dev launches is both of them AT ONCE, a pair of waves per stream
 // (inflate_pair_kernel: wave 0 is kernel 1, wave 1 is kernel 2 resolving the tokens as they come;
 // described in front of it) - a stream then lasts as long as the slower of its halves, not their
@@ -93,7 +94,8 @@ __device__ __forceinline__ dbh_inflate_stream zlib_view(const dbh_inflate_stream
 }
 // the modes that are other kernels' (dbh_vbz.hip, dbh_zstd.hip): kernel 2 leaves their output alone
 __device__ __forceinline__ bool passed_by(int mode) {
-    return mode == DBH_INFLATE_VBZ || mode == DBH_INFLATE_VBZ_ZSTD || mode == DBH_INFLATE_STORED_SHUFFLE;
+    return mode == DBH_INFLATE_VBZ || mode == DBH_INFLATE_VBZ_ZSTD || mode == DBH_INFLATE_STORED_SHUFFLE ||
+           mode == DBH_INFLATE_SVB16 || mode == DBH_INFLATE_SVB16_ZSTD;
 }
 
 // ---------------------------------------------------------------------------------------------

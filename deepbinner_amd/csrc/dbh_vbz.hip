@@ -20,6 +20,11 @@
 // bytes plus the 3 bytes a 4-byte load of its last value may take beyond them (the compressed
 // buffer is readable for 64 bytes beyond its end).  No LDS, vector loads and stores only.
 //
+// Streams of mode DBH_INFLATE_SVB16 and DBH_INFLATE_SVB16_ZSTD - the rows of a POD5 signal table,
+// whose code has 1-bit keys and 1- or 2-byte values (dbh_svb16_core.h) - are decoded by the same
+// grid in the same shape (svb16_stream below); dbh_svb16_decode_host at the end of this file runs
+// the same rules with loops for lanes.
+//
 // The same grid undoes HDF5's shuffle filter for the streams of mode DBH_INFLATE_ZLIB_SHUFFLE and
 // DBH_INFLATE_STORED_SHUFFLE (shuffle_stream below): it visits every stream behind the inflate
 // kernels anyway, and a launch of its own would be empty on every default route.
@@ -28,6 +33,7 @@
 #include <cstdint>
 
 #include "../../include/deepbinner_hip.h"
+#include "dbh_svb16_core.h"
 #include "dbh_wave.h"
 
 namespace dbh_vbz_detail {
@@ -155,6 +161,108 @@ __device__ __forceinline__ void vbz_stream(const uint8_t* __restrict__ comp, int
     if (lane == 0) *status_slot = bad ? refused : 0;
 }
 
+// ---- POD5's 16-bit streamvbyte code (DBH_INFLATE_SVB16, DBH_INFLATE_SVB16_ZSTD) ----
+// The same shape as vbz_stream with the rules of dbh_svb16_core.h: 1-bit keys, two key bytes per
+// lane and step, a lane's data 16 + popcount(keys) bytes, fetched as four 8-byte groups whose
+// addresses the key bits give before the first load; sums modulo 2^32, cut to 16 bits at the store.
+// Reads stay inside the stream's bytes plus the dbh_svb16::kReadBeyond (7) a group's fetch may
+// take beyond its last value.  `unpacked`: as for vbz_stream (mode DBH_INFLATE_SVB16_ZSTD).
+__device__ __forceinline__ uint64_t load_u64(const uint8_t* p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+}
+
+__device__ __forceinline__ void svb16_stream(const uint8_t* __restrict__ comp, int64_t comp_total,
+                                             const dbh_inflate_stream& s, int64_t total_out,
+                                             uint8_t* __restrict__ out, int32_t* status_slot,
+                                             int lane, const uint8_t* unpacked = nullptr,
+                                             int64_t unpacked_bytes = 0) {
+    namespace sv = dbh_svb16;
+    static_assert(sv::kPerLane == kPerLane && sv::kLanes == 64, "one lane, sixteen values");
+    // an output region outside the buffer is not written at all
+    if (s.out_offset < 0 || s.out_bytes < 0 || (s.out_offset & 1) ||
+        s.out_offset > total_out - s.out_bytes) {
+        if (lane == 0) *status_slot = sv::kRefused;
+        return;
+    }
+    int16_t* const dst = reinterpret_cast<int16_t*>(out + s.out_offset);
+    const int64_t out_n = s.out_bytes / 2;
+    bool bad = s.comp_offset < 0 || s.comp_bytes < 4 || s.comp_offset > comp_total - s.comp_bytes;
+    int64_t written = 0;
+    int refused = sv::kRefused;
+    if (unpacked && !bad) {
+        const int before = *status_slot;                   // (every lane reads it before lane 0 writes)
+        if (before != 0) {
+            bad = true;
+            refused = before;
+        }
+    }
+    const int64_t payload = unpacked ? unpacked_bytes : s.comp_bytes - 4;
+    if (!bad) {
+        const uint8_t* const src = comp + s.comp_offset;
+        const uint32_t size = load_u32(src);
+        const int64_t n = size / 2;
+        int64_t key_bytes = 0, data_len = 0;
+        bad = !sv::prefix_ok(size) || !sv::shape(n, payload, &key_bytes, &data_len);
+        const uint8_t* const kbase = unpacked ? unpacked : src + 4;
+        const uint8_t* const dbase = kbase + key_bytes;
+        const int64_t keep = n < out_n ? n : out_n;
+        const bool aligned16 = (s.out_offset & 15) == 0;
+        int64_t doff = 0;                          // data bytes of the steps before (uniform)
+        uint32_t carry = 0;                        // the running sample behind them (uniform)
+        for (int64_t v0 = 0; !bad && v0 < n; v0 += sv::kStep) {
+            const int64_t base = v0 + (int64_t)lane * kPerLane;
+            const int valid = sv::lane_valid(n, base);
+            uint32_t kb = 0;
+            if (sv::lane_key_bytes(valid) > 0) kb = kbase[base / 8];
+            if (sv::lane_key_bytes(valid) > 1) kb |= (uint32_t)kbase[base / 8 + 1] << 8;
+            const uint32_t keys = sv::lane_keys(kb, valid);
+            const uint32_t span = sv::lane_span(keys, valid);
+            const uint32_t incl = wave_scan_inclusive(span);
+            const uint32_t step_bytes = __builtin_amdgcn_readlane(incl, 63);
+            const int64_t my = doff + (int64_t)(incl - span);
+            const bool overrun = my + (int64_t)span > data_len;
+            // the four groups: addresses first, then the loads, then the values
+            const uint8_t* const mine = dbase + my;
+            uint64_t grp[sv::kGroups];
+#pragma unroll
+            for (int g = 0; g < sv::kGroups; ++g)
+                grp[g] = sv::group_used(valid, g) && !overrun ? load_u64(mine + sv::group_start(keys, g)) : 0ull;
+            uint32_t run[kPerLane];
+            const uint32_t sum = sv::lane_decode(keys, valid, grp, run);
+            const uint32_t incl2 = wave_scan_inclusive(sum);
+            const uint32_t prefix = carry + incl2 - sum;
+            carry += __builtin_amdgcn_readlane(incl2, 63);
+            doff += step_bytes;
+            if (__builtin_amdgcn_ballot_w64(overrun) != 0) {
+                bad = true;
+                break;
+            }
+            // int16 stores: a lane's 16 samples are 32 consecutive bytes
+            if (aligned16 && base + kPerLane <= keep) {
+                uint32_t packed[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    packed[k] = ((prefix + run[2 * k]) & 0xFFFFu) | ((prefix + run[2 * k + 1]) << 16);
+                uint4* q = reinterpret_cast<uint4*>(dst + base);
+                q[0] = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+                q[1] = make_uint4(packed[4], packed[5], packed[6], packed[7]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kPerLane; ++k)
+                    if (base + k < keep) dst[base + k] = (int16_t)(uint16_t)(prefix + run[k]);
+            }
+        }
+        if (!bad && doff != data_len) bad = true;  // data that end before the stream does
+        written = bad ? 0 : keep;
+    }
+    // zero-extension (a row shorter than asked for), or all of it for a refused stream
+    for (int64_t k = written + lane; k < out_n; k += 64) dst[k] = 0;
+    if ((s.out_bytes & 1) && lane == 0) out[s.out_offset + s.out_bytes - 1] = 0;   // (half a sample: no data)
+    if (lane == 0) *status_slot = bad ? refused : 0;
+}
+
 // ---- HDF5's shuffle filter for int16, undone (DBH_INFLATE_ZLIB_SHUFFLE, DBH_INFLATE_STORED_SHUFFLE) ----
 // The N shuffled bytes are the N/2 low bytes of the samples, then their N/2 high bytes.  One wave
 // per stream, as everything in this kernel.
@@ -257,12 +365,20 @@ __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int i = blockIdx.x * kWaves + wave; i < n_streams; i += gridDim.x * kWaves) {
         const dbh_inflate_stream s = streams[i];
-        if (s.mode == DBH_INFLATE_VBZ_ZSTD) {
+        if (s.mode == DBH_INFLATE_VBZ_ZSTD || s.mode == DBH_INFLATE_SVB16_ZSTD) {
             // (a stream with no room in the workspace was refused by the zstd kernel: nothing is read)
             const int64_t have = *reinterpret_cast<const int64_t*>(produced0 + (int64_t)i * produced_stride);
             const bool placed = s.out_offset >= 0 && s.out_bytes >= 0 && s.out_offset <= total_out - s.out_bytes;
-            vbz_stream(comp, comp_total, s, total_out, out, status_out + i, lane,
-                       work + (placed ? 4 * s.out_offset : 0), placed ? have : 0);
+            if (s.mode == DBH_INFLATE_VBZ_ZSTD)
+                vbz_stream(comp, comp_total, s, total_out, out, status_out + i, lane,
+                           work + (placed ? 4 * s.out_offset : 0), placed ? have : 0);
+            else
+                svb16_stream(comp, comp_total, s, total_out, out, status_out + i, lane,
+                             work + (placed ? 4 * s.out_offset : 0), placed ? have : 0);
+            continue;
+        }
+        if (s.mode == DBH_INFLATE_SVB16) {
+            svb16_stream(comp, comp_total, s, total_out, out, status_out + i, lane);
             continue;
         }
         if (s.mode == DBH_INFLATE_ZLIB_SHUFFLE || s.mode == DBH_INFLATE_STORED_SHUFFLE) {
@@ -277,6 +393,16 @@ __global__ __launch_bounds__(64 * kWaves) void vbz_decode_kernel(
 }
 
 }  // namespace dbh_vbz_detail
+
+extern "C" {
+/* the GPU's svb16 decoder run on the host: same core, lanes as a loop (tests, tools) */
+__attribute__((visibility("default"))) int dbh_svb16_decode_host(
+    const uint8_t* stream, size_t stream_bytes, int64_t n, int16_t* out, int32_t* status) {
+    if ((!stream && stream_bytes) || n < 0 || (!out && n) || !status) return 1;   // DBH_ERR_INVALID_ARGUMENT
+    *status = dbh_svb16::decode_host(stream, (int64_t)stream_bytes, n, out);
+    return 0;
+}
+}
 
 // (dbh_inflate.hip's dbh_inflate_dev launches it; not part of the C ABI)
 __attribute__((visibility("hidden"))) hipError_t dbh_vbz_launch(

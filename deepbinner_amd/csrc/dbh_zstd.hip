@@ -1,6 +1,7 @@
 // dbh_zstd.hip - the zstd stage of ONT's VBZ filter ON THE GPU: streams of mode
 // DBH_INFLATE_VBZ_ZSTD of dbh_inflate_dev (C ABI: the "compressed input" section of
-// include/deepbinner_hip.h) - u32 LE original_size, then the zstd frame as the filter stored it.
+// include/deepbinner_hip.h) - u32 LE original_size, then the zstd frame as the filter stored it -
+// and of mode DBH_INFLATE_SVB16_ZSTD, the same for a row of a POD5 signal table.
 // The decoder is dbh_zstd_core.h (what is decoded, what is refused, the schedule); this file is
 // the wave that runs it and the host entry that runs the same code with loops for lanes.
 //
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(64) void zstd_decode_kernel(
     const int i = blockIdx.x;
     if (i >= n_streams) return;
     const dbh_inflate_stream s = streams[i];
-    if (s.mode != DBH_INFLATE_VBZ_ZSTD) return;
+    if (s.mode != DBH_INFLATE_VBZ_ZSTD && s.mode != DBH_INFLATE_SVB16_ZSTD) return;
     const int lane = threadIdx.x;
     int32_t st = 1;                                        // (refused, as dbh_vbz.hip's kRefused)
     size_t produced = 0;

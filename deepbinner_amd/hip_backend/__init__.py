@@ -41,7 +41,8 @@ from ._live import (LIVE_ACTION, LIVE_ACTIONS, LIVE_BEGIN, LIVE_DECIDED, LIVE_EJ
                     live_chunk_flags, live_fold, live_plan_host, live_policy_dev,
                     live_policy_plan_host, live_tail_plan_host)
 from ._model import (INFLATE_SHUFFLE_REFUSED, INFLATE_STORED, INFLATE_STORED_SHUFFLE,
-                     INFLATE_STREAM, INFLATE_VBZ, INFLATE_ZLIB, INFLATE_ZLIB_SHUFFLE, HipModel,
+                     INFLATE_STREAM, INFLATE_SVB16, INFLATE_SVB16_ZSTD, INFLATE_VBZ, INFLATE_ZLIB,
+                     INFLATE_ZLIB_SHUFFLE, HipModel,
                      ModelWeights, _TensorSpec, classify_pair, classify_pair_deflated,
                      combine_calls_dev, forward_executed_mfmas, forward_kernel_info, general_model,
                      inflate)

@@ -106,6 +106,7 @@ def _signatures():
         'dbh_inflate_last_error': (c_char_p, []),
         'dbh_zstd_decode_host': (c_int, [ptr, c_size_t, ptr, c_size_t, P(c_size_t),
                                          P(ctypes.c_int32)]),
+        'dbh_svb16_decode_host': (c_int, [ptr, c_size_t, c_i64, ptr, P(ctypes.c_int32)]),
         'dbh_inflate_workspace_bytes': (c_int, [c_i64, c_i64, P(c_size_t)]),
         'dbh_inflate_dev': (c_int, [ptr, c_i64, ptr, c_i64, c_i64, ptr, ptr, ptr, c_int, ptr]),
         'dbh_inflate': (c_int, [ptr, c_size_t, ptr, c_i64, ptr, c_size_t, ptr, c_int, P(c_double)]),

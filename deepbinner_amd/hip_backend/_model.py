@@ -59,6 +59,8 @@ INFLATE_ZLIB, INFLATE_STORED, INFLATE_VBZ = 0, 1, 2
 # bytes / the N shuffled bytes themselves; the status of a stream these modes refuse
 INFLATE_ZLIB_SHUFFLE, INFLATE_STORED_SHUFFLE = 4, 5
 INFLATE_SHUFFLE_REFUSED = 32
+# a row of a POD5 signal table: u32 LE 2n, then its svb16 stream / the zstd frame of it as stored
+INFLATE_SVB16, INFLATE_SVB16_ZSTD = 6, 7
 # dbh_inflate_stream (include/deepbinner_hip.h)
 INFLATE_STREAM = np.dtype([('comp_offset', '<i8'), ('comp_bytes', '<i8'), ('out_offset', '<i8'),
                            ('out_bytes', '<i8'), ('mode', '<i4'), ('reserved', '<i4')])

@@ -173,14 +173,24 @@ def choose_loader_procs(requested, n_files):
     return max(1, min(8, usable_cpus() // 2))
 
 
-def find_all_fast5s(directory, verbose=False):
+def find_all_fast5s(directory, verbose=False, pod5=False):
+    """The fast5 files under ``directory``, in the order of the walk.  ``pod5`` (``classify``):
+    the POD5 files as well; a tree that holds any lists both kinds sorted by name, one without
+    lists what it always did."""
     if verbose:
         print('Looking for fast5 files in {}... '.format(directory), file=sys.stderr, end='',
               flush=True)
+    ends = ('.fast5', '.pod5') if pod5 else ('.fast5',)
     fast5s = [os.path.join(root, name)
               for root, _, names in os.walk(str(directory))
-              for name in names if name.endswith('.fast5')]
-    if verbose:
+              for name in names if name.endswith(ends)]
+    n_pod5 = sum(1 for name in fast5s if name.endswith('.pod5'))
+    if n_pod5:
+        fast5s.sort(key=lambda path: path.split(os.sep))
+    if verbose and n_pod5:
+        print('{} fast5 and {} pod5 files found'.format(len(fast5s) - n_pod5, n_pod5),
+              file=sys.stderr)
+    elif verbose:
         print('{} {} found'.format(len(fast5s), 'fast5' if len(fast5s) == 1 else 'fast5s'),
               file=sys.stderr)
     return fast5s

@@ -76,6 +76,7 @@ def locate(args, backend=None):
         sys.exit('Error: --batch_size must be at least 1')
     if args.start_model is None and args.end_model is None:
         sys.exit('Error: you must provide at least one model')
+    classify.refuse_pod5(args.input, 'locate')
     kind = classify.determine_input_type(args.input)
     if kind == 'training_data':
         sys.exit(NO_POSITIONS)

@@ -579,6 +579,7 @@ class MetadataSource:
 
 def realtime(args):
     """Entry point of the ``realtime`` sub-command (reference realtime.py:28-70)."""
+    classify.refuse_pod5(args.in_dir, 'realtime')
     print()
     session = Session(args)
     idle_announced = False

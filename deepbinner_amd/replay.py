@@ -172,6 +172,7 @@ def replay(args, backend=None):
         sys.exit('Error: --chunk_samples must be at least 1')
     if args.min_windows < 1:
         sys.exit('Error: --min_windows must be at least 1')
+    classify.refuse_pod5(args.input, 'replay')
     kind = classify.determine_input_type(args.input)
     if kind == 'training_data':
         sys.exit(NO_TRAINING_DATA)

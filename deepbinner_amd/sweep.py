@@ -199,6 +199,7 @@ def sweep(args, backend=None):
     from . import classify
     if backend is None:
         from . import hip_backend as backend
+    classify.refuse_pod5(args.input, 'sweep')
     thresholds = parse_score_diffs(args.score_diffs)
     if int(getattr(args, 'devices', 0) or 0) > 1:
         sys.exit('Error: a sweep runs on one GPU (--devices {} is not supported)'.format(args.devices))

@@ -893,6 +893,31 @@ int dbh_live_policy_plan_host(const int32_t* weights, int n_classes, int64_t sla
  * or why the frame is refused (16..28, dbh_zstd_core.h), *produced: the content size, 0 if refused. */
 int dbh_zstd_decode_host(const uint8_t* frame, size_t frame_bytes, uint8_t* out,
                          size_t out_capacity, size_t* produced, int32_t* status);
+/* A row of a POD5 signal table (a `minknow.vbz` value): "svb16", the 16-bit
+ * streamvbyte code - ceil(n/8) key bytes, bit i & 7 of key byte i >> 3 (low bit first) saying
+ * whether value i takes one byte (0) or two, little-endian (1), then the data bytes;
+ * v -> (v >> 1) ^ (0 - (v & 1)) in 16 bits, sample i the sum of values 0..i modulo 2^16 as int16.
+ * DBH_INFLATE_SVB16: u32 LE original_size (= 2 n) in front, as DBH_INFLATE_VBZ has, then the
+ * svb16 stream (the zstd frame undone by the host) - n int16 at out_offset, cut or zero-extended
+ * to out_bytes as the other modes are (an odd out_bytes: whole samples, then one zero byte),
+ * decoded by a sibling of the VBZ wave in the same kernel
+ * (dbh_vbz.hip: svb16_stream; the rules: csrc/dbh_svb16_core.h).  Refused (status 1, output all
+ * zeros, neighbours untouched): comp_bytes < 4, an odd original_size, key bytes beyond the
+ * stream, data that would run past its end or that end before it; an output region outside the
+ * buffer is not written at all.  The unused bits of the last key byte are not looked at.  Reads
+ * stay inside the stream plus 7 bytes.
+ * DBH_INFLATE_SVB16_ZSTD: the same prefix, then the zstd frame as the file stores it.  The zstd
+ * kernel writes the frame's content into the stream's workspace slots (4 * out_bytes bytes, which
+ * cover ceil(n/8) + 2 n whenever out_bytes >= 2 n), the svb16 stage reads it from there; a zstd
+ * refusal keeps its own status (16..28), as in DBH_INFLATE_VBZ_ZSTD. */
+#define DBH_INFLATE_SVB16 6
+#define DBH_INFLATE_SVB16_ZSTD 7
+/* the GPU's svb16 decoder run on the host: same core, lanes as a loop (tests, tools).  stream:
+ * exactly stream_bytes readable bytes holding the svb16 stream of n values (no prefix); out: n
+ * samples.  Returns 0 unless an argument is null or n < 0; *status: 0, or 1 if the stream is
+ * refused (out is then all zeros). */
+int dbh_svb16_decode_host(const uint8_t* stream, size_t stream_bytes, int64_t n, int16_t* out,
+                          int32_t* status);
 typedef struct dbh_inflate_stream {
     int64_t comp_offset, comp_bytes;       /* the stream inside the compressed buffer           */
     int64_t out_offset, out_bytes;         /* its output inside the output buffer (bytes)       */
