@@ -1,6 +1,8 @@
 // dbh_host_layout.h — the host-side arithmetic of libdeepbinner_hip.so that touches no HIP call:
-// regions of a buffer (align256, Carve), grid sizes, and dbh_api.hip's scan steps, staging layouts,
-// inflate record order and staged copy.  No HIP include: oracle/api_host_test.cpp compiles it with g++.
+// regions of a buffer (align256, Carve), grid sizes, and the host units' (dbh_api*.hip) scan steps,
+// staging layouts, inflate record order, staged copy and the pure checks of their arguments (do the
+// offsets run forwards, a live chunk's flags).  No HIP include: oracle/api_host_test.cpp compiles it
+// with g++.
 #pragma once
 
 #include <algorithm>
@@ -116,6 +118,21 @@ inline int64_t uniform_length(const int64_t* rel, int64_t n) {
     for (int64_t i = 1; i <= n && uniform > 0; ++i)
         if (rel[i] != i * uniform) uniform = 0;
     return uniform;
+}
+
+// offsets[0 .. n_reads] of n_reads reads, wherever offsets[0] lies: does no read end before it
+// starts?  *total: the samples from the first read's start to the last read's end (no read: 0, and
+// the table is not looked at).
+inline bool offsets_run_forwards(const int64_t* offsets, int64_t n_reads, int64_t* total = nullptr) {
+    if (total) *total = n_reads > 0 ? offsets[n_reads] - offsets[0] : 0;
+    for (int64_t i = 0; i < n_reads; ++i)
+        if (offsets[i + 1] < offsets[i]) return false;
+    return true;
+}
+
+// the flags of a live session's chunk: DBH_LIVE_BEGIN, DBH_LIVE_END, both or neither
+inline bool live_chunk_flags_ok(uint32_t flags) {
+    return (flags & ~(uint32_t)(DBH_LIVE_BEGIN | DBH_LIVE_END)) == 0;
 }
 
 // Pageable memory -> a pinned staging slot.  One thread moves ~10 GB/s; PCIe takes 50+.  Large

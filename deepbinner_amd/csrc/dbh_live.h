@@ -1,4 +1,4 @@
-// dbh_live.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_live.hip: the
+// dbh_live.h — what the library's host code (dbh_api_live.hip) sees of dbh_live.hip: the
 // kernels of a live session's push, one launch function each.  No kernel symbol leaves the unit.
 // The contract is include/deepbinner_hip.h's ("live"); the rules are dbh_live_core.h's.
 #pragma once

@@ -3,7 +3,7 @@
 // stored, what a folded window does to the channel's record, and - for a pair session - the tail
 // ring, the end windows and the end record; for a session with a yield policy, what a barcode has
 // yielded, its level and the keep / eject action.  The GPU's threads (dbh_live.hip),
-// the session's host mirror (dbh_api.hip: it knows every push's window count without reading the
+// the session's host mirror (dbh_api_live.hip: it knows every push's window count without reading the
 // device back) and the CPU model (dbh_live_plan_host; live_model_check.cpp) compile these lines.
 #pragma once
 

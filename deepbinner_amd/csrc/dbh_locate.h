@@ -1,4 +1,4 @@
-// dbh_locate.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_locate.hip: the
+// dbh_locate.h — what the library's host code (dbh_api_locate.hip) sees of dbh_locate.hip: the
 // rule of `locate` over a batch of reads on the device, and the same rule on the host (the CPU model).
 // No kernel symbol leaves the unit.  The contract is include/deepbinner_hip.h's ("locate").
 #pragma once

@@ -1,4 +1,4 @@
-// dbh_occlude.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_occlude.hip:
+// dbh_occlude.h — what the library's host code (dbh_api_locate.hip) sees of dbh_occlude.hip:
 // the rule of `locate --occlude` over a batch of reads on the device, and the same rule on the host
 // (the CPU models).  No kernel symbol leaves the unit.  The contract is include/deepbinner_hip.h's
 // ("occlude").

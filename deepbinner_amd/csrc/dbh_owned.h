@@ -11,8 +11,9 @@
 
 #include "dbh_host_layout.h"
 
-namespace dbh_owned {
-namespace {      // (internal linkage: each translation unit of the library has its own copy)
+// (one definition for every unit - dbh_model.h's objects hold these as members in several units -
+// and none of it a symbol of the library)
+namespace dbh_owned __attribute__((visibility("hidden"))) {
 
 inline hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
 inline hipError_t pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
@@ -68,5 +69,4 @@ struct Block {
 using DeviceBlock = Block<device_alloc, hipFree>;
 using PinnedBlock = Block<pinned_alloc, hipHostFree>;
 
-}  // namespace
 }  // namespace dbh_owned

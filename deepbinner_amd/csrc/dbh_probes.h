@@ -1,16 +1,17 @@
 // dbh_probes.h — the instruments of the forward kernel: event brackets around production launches
 // (dbh_forward_timing_*), the cycle-stamp build of the kernel (dbh_forward_timeline*), the clock
 // and phase marks a production launch leaves (dbh_forward_clock_*, dbh_forward_phases_*).  Host code,
-// included at the end of dbh_api.hip for its model object and error macros; the cycle-stamp kernel
-// itself is built and launched in dbh_timeline.hip.  Of all this the launch path only calls
-// TimingBrackets::begin / end.
+// a part of the core unit (dbh_api.hip includes it once) over the model object of dbh_model.h; the
+// cycle-stamp kernel itself is built and launched in dbh_timeline.hip.  Of all this the launch path
+// only calls TimingBrackets::begin / end.
 #pragma once
 
-namespace {
+#include "dbh_kernels.h"
+#include "dbh_model.h"
 
 // Launch number pos of every `every`: pos 0 opens a bracket (start event recorded in front of the
 // launch), launches 0 .. span-1 belong to it, the last of them closes it in end().
-hipError_t TimingBrackets::begin(hipStream_t stream, int64_t windows) {
+hipError_t dbh_api::TimingBrackets::begin(hipStream_t stream, int64_t windows) {
     const int64_t pos = launch_counter++ % every;
     if (pos == 0) {
         if (events_used == events.size()) {
@@ -31,7 +32,7 @@ hipError_t TimingBrackets::begin(hipStream_t stream, int64_t windows) {
     return hipSuccess;
 }
 
-hipError_t TimingBrackets::end(hipStream_t stream) {
+hipError_t dbh_api::TimingBrackets::end(hipStream_t stream) {
     if (!open_stop || (launch_counter - 1) % every != span - 1) return hipSuccess;
     const hipError_t e = hipEventRecord(std::exchange(open_stop, nullptr), stream);
     if (e != hipSuccess) return e;
@@ -41,11 +42,13 @@ hipError_t TimingBrackets::end(hipStream_t stream) {
     return hipSuccess;
 }
 
-void TimingBrackets::reset() {
+void dbh_api::TimingBrackets::reset() {
     open_stop = nullptr;
     events_used = 0;
     timed_windows = timed_launches = 0;
 }
+
+namespace {
 
 // One launch of the cycle-stamp kernel on the null stream: `a` comes with its input and debug
 // stage chosen by the caller; probabilities (and calls, if wanted, behind them) go to the model's
@@ -53,7 +56,7 @@ void TimingBrackets::reset() {
 int run_timeline(dbh_model* m, dbh::ForwardArgs a, int64_t n, unsigned grid,
                  bool with_calls, int64_t* stamps_host) {
     const size_t stamp_bytes = (size_t)n * dbh::kWaves * 64 * sizeof(int64_t);
-    TailScratch& tail = m->tails[nullptr];
+    dbh_api::TailScratch& tail = m->tails[nullptr];
     DBH_HIP(m->work.reserve(stamp_bytes));
     DBH_HIP(m->out.reserve((size_t)n * (m->n_classes + (with_calls ? 1 : 0)) * sizeof(float)));
     DBH_HIP(tail.reserve(grid, nullptr));
@@ -145,7 +148,7 @@ int dbh_forward_timing_enable(dbh_model* m, int enable) {
 int dbh_forward_timing_read(dbh_model* m, double* total_ms, int64_t* launches, int64_t* windows) {
     if (!m || !total_ms || !launches || !windows) return DBH_ERR_INVALID_ARGUMENT;
     if (m->kind != DBH_MODEL_KIND_PERSISTENT) return DBH_ERR_UNSUPPORTED;
-    TimingBrackets& t = m->timing;
+    dbh_api::TimingBrackets& t = m->timing;
     double sum = 0.0;
     for (size_t i = 0; i < t.events_used; ++i) {
         DBH_HIP(hipEventSynchronize(t.events[i].second));

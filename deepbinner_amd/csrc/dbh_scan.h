@@ -1,4 +1,4 @@
-// dbh_scan.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_scan.hip: the
+// dbh_scan.h — what the library's host code (dbh_api_scan.hip) sees of dbh_scan.hip: the
 // window offsets of a batch of ragged reads, the front that cuts EVERY window of every read, and the
 // pass from a per-window track to events, one launch function each.  No kernel symbol leaves the
 // unit.  The contract is include/deepbinner_hip.h's ("scan").

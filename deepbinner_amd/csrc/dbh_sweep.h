@@ -1,4 +1,4 @@
-// dbh_sweep.h — what the host code of libdeepbinner_hip.so (dbh_api.hip) sees of dbh_sweep.hip: the
+// dbh_sweep.h — what the library's host code (dbh_api_sweep.hip) sees of dbh_sweep.hip: the
 // fold over scan sizes in its two forms, the tally of outcomes and the early tally, one launch
 // function each.  No kernel symbol leaves the unit.  The contract is include/deepbinner_hip.h's
 // ("sweep").

@@ -5,8 +5,10 @@
 // GPU - and so that it can run under AddressSanitizer (oracle/Makefile: api_host_test_asan).  Not
 // part of the product; nothing in deepbinner_amd/ calls it.
 //   api_host_test [RECORDS]      RECORDS: a file of dbh_inflate_stream records
-// One line per check, "ok ..." or "FAIL ..."; "model_steps INPUT SCAN = STEPS" and, with RECORDS,
-// "order I J K ..." for the caller to compare.  Exit status 1 if a check failed.
+// One line per check, "ok ..." or "FAIL ..."; "model_steps INPUT SCAN = STEPS", "offsets_forwards
+// CASE = ok TOTAL | bad" and "chunk_flags FLAGS = ok | bad" (what the pure checks of the host units'
+// arguments answer) and, with RECORDS, "order I J K ..." for the caller to compare.  Exit status 1 if
+// a check failed.
 //   api_host_test --network [BLOB CLASSES]...      BLOB: a canonical weight blob (fp32) of CLASSES
 // The network table of dbh_network.h ("conv", "bn", "bn_eps", "param_count", "blob",
 // "stage_lengths", "same_pad_left") and, per BLOB, "packed persistent|general NAME CLASSES FLOATS
@@ -184,6 +186,35 @@ static void check_uniform_length() {
            "uniform_length");
 }
 
+// what the host units' pure argument checks answer, a line each for the caller to compare: do the
+// offsets run forwards (and the samples they span), is a live chunk's flag word BEGIN, END, both or
+// neither
+static void print_argument_checks() {
+    struct Table { const char* name; std::vector<int64_t> offsets; };
+    const Table tables[] = {
+        {"empty", {}},                                   // no read: the table is not looked at
+        {"one_read_no_samples", {5, 5}},
+        {"forwards", {0, 3, 3, 10}},
+        {"backward_first", {4, 3, 8, 10}},
+        {"backward_middle", {0, 6, 5, 10}},
+        {"backward_last", {0, 3, 8, 7}},
+        {"first_not_zero", {100, 103, 110}},
+    };
+    for (const Table& t : tables) {
+        const int64_t n_reads = t.offsets.empty() ? 0 : (int64_t)t.offsets.size() - 1;
+        int64_t total = -1;
+        const bool ok = dbh_host::offsets_run_forwards(t.offsets.empty() ? nullptr : t.offsets.data(),
+                                                       n_reads, &total);
+        if (ok) std::printf("offsets_forwards %s = ok %lld\n", t.name, (long long)total);
+        else std::printf("offsets_forwards %s = bad\n", t.name);
+    }
+    // each flag bit beside one bit outside the mask, and the words a session takes
+    for (uint32_t flags : {0u, (uint32_t)DBH_LIVE_BEGIN, (uint32_t)DBH_LIVE_END,
+                           (uint32_t)(DBH_LIVE_BEGIN | DBH_LIVE_END), 4u, DBH_LIVE_BEGIN | 4u,
+                           DBH_LIVE_END | 4u, DBH_LIVE_BEGIN | DBH_LIVE_END | 0x80000000u})
+        std::printf("chunk_flags %u = %s\n", flags, dbh_host::live_chunk_flags_ok(flags) ? "ok" : "bad");
+}
+
 // the network as dbh_network.h has it, for the caller to hold to model_format.py and the oracle
 static void print_network() {
     namespace net = dbh_net;
@@ -266,6 +297,7 @@ int main(int argc, char** argv) {
     check_carve();
     check_staged_copy();
     check_uniform_length();
+    print_argument_checks();
     for (int input : {96, 1024, 2048})
         for (int scan : {0, 48, 96, 512, 1000, 1024, 1536, 2048, 6144, 6145, 6192})
             std::printf("model_steps %d %d = %d\n", input, scan, dbh_host::model_steps(input, scan));

@@ -1,5 +1,6 @@
 """The host-side arithmetic of libdeepbinner_hip.so (deepbinner_amd/csrc/dbh_host_layout.h: buffer
-layouts, the order inflate records travel in, the staged copy, scan steps; dbh_network.h: the
+layouts, the order inflate records travel in, the staged copy, scan steps, the offsets check and
+the live chunk-flag mask; dbh_network.h: the
 network table every native path reads; dbh_pack.h: both weight packers), compiled into a program of
 its own (oracle/api_host_test.cpp, built by oracle/Makefile from the very headers the library
 includes) and run on the build box, without a GPU."""
@@ -48,7 +49,8 @@ def test_layouts_and_staged_copy(lines):
     """The program's own checks: regions of both layouts tile their buffer in order, aligned as they
     are documented, for one model, two models, zero streams and one read; staged_copy over sizes
     on both sides of its thresholds copies every byte and no other."""
-    checks = [line.split() for line in lines if not line.startswith(('model_steps', 'order'))]
+    checks = [line.split() for line in lines
+              if not line.startswith(('model_steps', 'order', 'offsets_forwards', 'chunk_flags'))]
     assert all(c[0] == 'ok' for c in checks), [c for c in checks if c[0] != 'ok']
     assert sum(c[1:3] == ['layout', 'deflated'] for c in checks) >= 6
     assert sum(c[1:3] == ['layout', 'group'] for c in checks) == 12
@@ -113,6 +115,33 @@ def test_model_steps_is_check_input_size(lines):
         assert steps == want, line
         seen.add((input_size, steps > 0))
     assert seen == {(size, fits) for size in (96, 1024, 2048) for fits in (True, False)}
+
+
+def test_offsets_check_and_chunk_flag_mask(lines):
+    """The pure checks every host route's arguments go through, line for line.  offsets_run_forwards:
+    no read (the table is not looked at), one read of no samples, a backward step in the first, a
+    middle and the last position, and a table that starts at 100 - which runs forwards, its total
+    counted from there.  live_chunk_flags_ok: BEGIN, END, both and neither are a chunk's flags; bit 2
+    alone, beside either flag, and bit 31 beside both are not."""
+    assert [line for line in lines if line.startswith('offsets_forwards')] == [
+        'offsets_forwards empty = ok 0',
+        'offsets_forwards one_read_no_samples = ok 0',
+        'offsets_forwards forwards = ok 10',
+        'offsets_forwards backward_first = bad',
+        'offsets_forwards backward_middle = bad',
+        'offsets_forwards backward_last = bad',
+        'offsets_forwards first_not_zero = ok 10',
+    ]
+    assert [line for line in lines if line.startswith('chunk_flags')] == [
+        'chunk_flags 0 = ok',
+        'chunk_flags 1 = ok',
+        'chunk_flags 2 = ok',
+        'chunk_flags 3 = ok',
+        'chunk_flags 4 = bad',
+        'chunk_flags 5 = bad',
+        'chunk_flags 6 = bad',
+        'chunk_flags {} = bad'.format(3 | 1 << 31),
+    ]
 
 
 # ---- dbh_network.h against the specification, dbh_pack.h against the parent's images ------------

@@ -212,7 +212,7 @@ def test_the_rules_are_one_text():
     for name in ('yield_class', 'level_of', 'action_of', 'yield_kernel', 'action_kernel'):
         assert name in kernels, name
     assert 'asm' not in kernels and 'atomic' not in kernels
-    api = open(os.path.join(CSRC, 'dbh_api.hip')).read()
+    api = open(os.path.join(CSRC, 'dbh_api_live.hip')).read()
     assert 'plan_policy_push' in api and 'policy_ok' in api
 
 

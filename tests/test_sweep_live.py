@@ -229,7 +229,7 @@ def test_the_model_check_program_is_there():
     assert 'int main()' in source and 'dbh_early_core.h' in source
     kernels = open(os.path.join(csrc, 'dbh_sweep.hip')).read()
     assert 'dbh_early_core.h' in kernels and 'asm' not in kernels
-    assert 'dbh_early_core.h' in open(os.path.join(csrc, 'dbh_api.hip')).read()
+    assert 'dbh_early_core.h' in open(os.path.join(csrc, 'dbh_api_sweep.hip')).read()
 
 
 # ---- the command against a host stand-in ----------------------------------------------------------
