@@ -57,12 +57,29 @@ __host__ __device__ inline uint32_t dropout_bits(uint32_t seed_lo, uint32_t seed
 
 size_t workspace_bytes(int n_classes, int input_size, int64_t n_windows);
 
+// Frozen blocks: block j = 1..7 ends at batch normalisation j, so it holds
+// the convolutions that read stage j - 1 (dbh_network.h: in == j - 1) and that normalisation.  With
+// the first f blocks frozen, the first frozen_convs(f) = 0, 1, 4, 7, 9, 16, 17, 19 convolutions and
+// batch_normalization_1 .. f take no gradient and no update; the head (conv1d_20) is never frozen.
+constexpr int kMaxFrozenBlocks = dbh_net::kNumBn;
+constexpr int frozen_convs(int frozen_blocks) {
+    int n = 0;
+    for (int i = 0; i < dbh_net::kNumConvs; ++i) n += dbh_net::kConvs[i].in < frozen_blocks ? 1 : 0;
+    return n;
+}
+static_assert(frozen_convs(0) == 0 && frozen_convs(4) == 9 && frozen_convs(kMaxFrozenBlocks) == 19,
+              "blocks follow the stages of dbh_network.h");
+inline bool frozen_ok(int frozen_blocks) { return frozen_blocks >= 0 && frozen_blocks <= kMaxFrozenBlocks; }
+
 // Everything on the device, queued on `stream`, nothing synchronised.  weights: the canonical blob
 // (16-byte aligned); grads: the same layout, moving-statistics slots zero; stats: kStatsFloats.
+// frozen_blocks (0 .. kMaxFrozenBlocks, the caller's to check): the forward pass is the same; the
+// backward pass ends at the first trainable convolution's weight gradient, without that layer's
+// data gradient, and the frozen tensors' slots of grads are zero like the moving-statistics slots.
 hipError_t gradients(const float* weights, int n_classes, int input_size, const float* x,
                      const int32_t* labels, int64_t n_windows, float dropout_rate, uint64_t seed,
                      double* mean_loss, int64_t* n_correct, float* grads, float* stats,
-                     void* workspace, hipStream_t stream);
+                     void* workspace, hipStream_t stream, int frozen_blocks);
 
 // The same forward pass in Keras's test phase: the blob's moving statistics in place of the batch's,
 // no dropout, nothing written to the weights.  Queued, not synchronised.  The losses are ADDED, in

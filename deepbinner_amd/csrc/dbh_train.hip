@@ -933,7 +933,7 @@ size_t workspace_bytes(int n_classes, int input_size, int64_t n_windows) {
 hipError_t gradients(const float* weights, int n_classes, int input_size, const float* x,
                      const int32_t* labels, int64_t n_windows, float dropout_rate, uint64_t seed,
                      double* mean_loss, int64_t* n_correct, float* grads, float* stats,
-                     void* workspace, hipStream_t stream) {
+                     void* workspace, hipStream_t stream, int frozen_blocks) {
     const Geometry g(input_size, n_classes);
     Carve ws(workspace);
     const Buffers b(ws, g, n_windows);
@@ -949,7 +949,7 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
     drop.scale = (float)(1.0 / (1.0 - (double)dropout_rate));
     Run r{g, b, weights, grads, stats, n, drop, stream};
 
-    // the moving-statistics slots stay zero; everything else is written below
+    // the moving-statistics slots and the frozen tensors' stay zero; everything else is written below
     r.err = hipMemsetAsync(grads, 0, (size_t)dbh_net::param_count(C) * sizeof(float), stream);
 
     forward(r, x, labels);
@@ -958,6 +958,9 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
                            (const int*)b.correct, (long long)n, mean_loss, (long long*)n_correct);
 
     // ---- backward ----------------------------------------------------------------------------
+    // With f blocks frozen the pass ends at the first trainable convolutions: their weight and bias
+    // gradients, no data gradient into the frozen part.  What runs is launched as at f = 0.
+    const int f = frozen_blocks;
     const long long rows7 = (long long)n * len[7];
     r.bias_grad(b.dz20, rows7, C, C, 0, grads + blob_bias(19, g.C));
     if (r.ok()) {
@@ -968,60 +971,69 @@ hipError_t gradients(const float* weights, int n_classes, int input_size, const 
         hipLaunchKernelGGL((reduce_partials<double>), dim3(blocks_for(48 * C, kThreads)), dim3(kThreads), 0,
                            stream, (const double*)b.part, (int)parts, (long long)48 * C,
                            (long long)48 * C, grads + blob_kernel(19, g.C));
-        hipLaunchKernelGGL(head_dgrad, dim3(blocks_for(rows7 * 48, kThreads)), dim3(kThreads), 0, stream,
-                           (const float*)b.dz20, weights + blob_kernel(19, g.C), rows7, C, b.gA);
+        if (f < 7)
+            hipLaunchKernelGGL(head_dgrad, dim3(blocks_for(rows7 * 48, kThreads)), dim3(kThreads), 0, stream,
+                               (const float*)b.dz20, weights + blob_kernel(19, g.C), rows7, C, b.gA);
     }
-    // stage G
-    r.bn_backward(6, b.gA, b.p19, len[7], b.gB);
-    r.unpool(true, b.gB, b.a19, len[6], len[7], 48, b.gA);
-    r.conv_backward(18, b.a18, len[6], b.gA, len[6], 48, 0, b.gB, b.a18, false);
-    r.conv_backward(17, b.h6, len[6], b.gB, len[6], 48, 0, b.gA, nullptr, false);
-    // stage F
-    r.bn_backward(5, b.gA, b.a17, len[6], b.gB);
-    r.unpool(false, b.gB, b.a17, len[6], len[6], 48, b.gA);
-    r.conv_backward(16, b.h5, len[5], b.gA, len[6], 48, 0, b.gB, nullptr, false);
-    // stage E: the four branches' data gradients add in gD
-    r.bn_backward(4, b.gB, b.pcc, len[5], b.gA);
-    r.unpool(true, b.gA, b.cc, len[4], len[5], 192, b.gE);
-    r.conv_backward(15, b.a15, len[4], b.gE, len[4], 192, 144, b.g48, b.a15, false);
-    r.conv_backward(14, b.a14, len[4], b.g48, len[4], 48, 0, b.g16, b.a14, false);
-    r.conv_backward(13, b.h4, len[4], b.g16, len[4], 16, 0, b.gD, nullptr, false);
-    r.conv_backward(12, b.a12, len[4], b.gE, len[4], 192, 96, b.g16, b.a12, false);
-    r.conv_backward(11, b.h4, len[4], b.g16, len[4], 16, 0, b.gD, nullptr, true);
-    r.conv_backward(10, b.h4, len[4], b.gE, len[4], 192, 48, b.gD, nullptr, true);
-    r.conv_backward(9, b.avg, len[4], b.gE, len[4], 192, 0, b.gavg, nullptr, false);
-    if (r.ok())
-        hipLaunchKernelGGL(avg_backward_add, dim3(blocks_for(n * len[4] * 48, kThreads)), dim3(kThreads), 0,
-                           stream, (const float*)b.gavg, (long long)n, len[4], 48, b.gD);
-    // stage D
-    r.bn_backward(3, b.gD, b.p9, len[4], b.gA);
-    r.unpool(true, b.gA, b.a9, len[3], len[4], 48, b.gB);
-    r.conv_backward(8, b.a8, len[3], b.gB, len[3], 48, 0, b.gA, b.a8, false);
-    r.conv_backward(7, b.h3, len[3], b.gA, len[3], 48, 0, b.gB, nullptr, false);
-    // stage C
-    r.bn_backward(2, b.gB, b.p7, len[3], b.gA);
-    r.unpool(true, b.gA, b.a7, len[2], len[3], 48, b.gB);
-    r.conv_backward(6, b.a6, len[2], b.gB, len[2], 48, 0, b.gA, b.a6, false);
-    r.conv_backward(5, b.a5, len[2], b.gA, len[2], 48, 0, b.gB, b.a5, false);
-    r.conv_backward(4, b.h2, len[2], b.gB, len[2], 16, 0, b.gA, nullptr, false);
-    // stage B
-    r.bn_backward(1, b.gA, b.p4, len[2], b.gB);
-    r.unpool(true, b.gB, b.a4, len[1], len[2], 48, b.gA);
-    r.conv_backward(3, b.a3, len[1], b.gA, len[1], 48, 0, b.gB, b.a3, false);
-    r.conv_backward(2, b.a2, len[1], b.gB, len[1], 48, 0, b.gA, b.a2, false);
-    r.conv_backward(1, b.h1, len[1], b.gA, len[1], 48, 0, b.gB, nullptr, false);
-    // stage A: conv1d_1 has one input channel and needs no data gradient
-    r.bn_backward(0, b.gB, b.a1, len[1], b.gA);
-    r.unpool(false, b.gA, b.a1, len[1], len[1], 48, b.gB);
-    if (r.ok()) {
-        const long long rows = (long long)n * len[1];
-        const long long per = rows_per_part(rows, 64, 1);
-        const unsigned parts = (unsigned)((rows + per - 1) / per);
-        hipLaunchKernelGGL(conv1_wgrad, dim3(parts), dim3(kThreads), 0, stream, x,
-                           (const float*)b.gB, rows, g.L, len[1], same_pad_left(3, 2, g.L, len[1]), per,
-                           (double*)b.part);
-        hipLaunchKernelGGL((reduce_partials<double>), dim3(1), dim3(kThreads), 0, stream,
-                           (const double*)b.part, (int)parts, (long long)192, (long long)192, grads);
+    if (f < 7) {    // stage G
+        r.bn_backward(6, b.gA, b.p19, len[7], b.gB);
+        r.unpool(true, b.gB, b.a19, len[6], len[7], 48, b.gA);
+        r.conv_backward(18, b.a18, len[6], b.gA, len[6], 48, 0, b.gB, b.a18, false);
+        r.conv_backward(17, b.h6, len[6], b.gB, len[6], 48, 0, f < 6 ? b.gA : nullptr, nullptr, false);
+    }
+    if (f < 6) {    // stage F
+        r.bn_backward(5, b.gA, b.a17, len[6], b.gB);
+        r.unpool(false, b.gB, b.a17, len[6], len[6], 48, b.gA);
+        r.conv_backward(16, b.h5, len[5], b.gA, len[6], 48, 0, f < 5 ? b.gB : nullptr, nullptr, false);
+    }
+    if (f < 5) {    // stage E: the four branches' data gradients add in gD
+        float* const gD = f < 4 ? b.gD : nullptr;
+        r.bn_backward(4, b.gB, b.pcc, len[5], b.gA);
+        r.unpool(true, b.gA, b.cc, len[4], len[5], 192, b.gE);
+        r.conv_backward(15, b.a15, len[4], b.gE, len[4], 192, 144, b.g48, b.a15, false);
+        r.conv_backward(14, b.a14, len[4], b.g48, len[4], 48, 0, b.g16, b.a14, false);
+        r.conv_backward(13, b.h4, len[4], b.g16, len[4], 16, 0, gD, nullptr, false);
+        r.conv_backward(12, b.a12, len[4], b.gE, len[4], 192, 96, b.g16, b.a12, false);
+        r.conv_backward(11, b.h4, len[4], b.g16, len[4], 16, 0, gD, nullptr, true);
+        r.conv_backward(10, b.h4, len[4], b.gE, len[4], 192, 48, gD, nullptr, true);
+        r.conv_backward(9, b.avg, len[4], b.gE, len[4], 192, 0, gD ? b.gavg : nullptr, nullptr, false);
+        if (gD && r.ok())
+            hipLaunchKernelGGL(avg_backward_add, dim3(blocks_for(n * len[4] * 48, kThreads)), dim3(kThreads), 0,
+                               stream, (const float*)b.gavg, (long long)n, len[4], 48, b.gD);
+    }
+    if (f < 4) {    // stage D
+        r.bn_backward(3, b.gD, b.p9, len[4], b.gA);
+        r.unpool(true, b.gA, b.a9, len[3], len[4], 48, b.gB);
+        r.conv_backward(8, b.a8, len[3], b.gB, len[3], 48, 0, b.gA, b.a8, false);
+        r.conv_backward(7, b.h3, len[3], b.gA, len[3], 48, 0, f < 3 ? b.gB : nullptr, nullptr, false);
+    }
+    if (f < 3) {    // stage C
+        r.bn_backward(2, b.gB, b.p7, len[3], b.gA);
+        r.unpool(true, b.gA, b.a7, len[2], len[3], 48, b.gB);
+        r.conv_backward(6, b.a6, len[2], b.gB, len[2], 48, 0, b.gA, b.a6, false);
+        r.conv_backward(5, b.a5, len[2], b.gA, len[2], 48, 0, b.gB, b.a5, false);
+        r.conv_backward(4, b.h2, len[2], b.gB, len[2], 16, 0, f < 2 ? b.gA : nullptr, nullptr, false);
+    }
+    if (f < 2) {    // stage B
+        r.bn_backward(1, b.gA, b.p4, len[2], b.gB);
+        r.unpool(true, b.gB, b.a4, len[1], len[2], 48, b.gA);
+        r.conv_backward(3, b.a3, len[1], b.gA, len[1], 48, 0, b.gB, b.a3, false);
+        r.conv_backward(2, b.a2, len[1], b.gB, len[1], 48, 0, b.gA, b.a2, false);
+        r.conv_backward(1, b.h1, len[1], b.gA, len[1], 48, 0, f < 1 ? b.gB : nullptr, nullptr, false);
+    }
+    if (f < 1) {    // stage A: conv1d_1 has one input channel and needs no data gradient
+        r.bn_backward(0, b.gB, b.a1, len[1], b.gA);
+        r.unpool(false, b.gA, b.a1, len[1], len[1], 48, b.gB);
+        if (r.ok()) {
+            const long long rows = (long long)n * len[1];
+            const long long per = rows_per_part(rows, 64, 1);
+            const unsigned parts = (unsigned)((rows + per - 1) / per);
+            hipLaunchKernelGGL(conv1_wgrad, dim3(parts), dim3(kThreads), 0, stream, x,
+                               (const float*)b.gB, rows, g.L, len[1], same_pad_left(3, 2, g.L, len[1]), per,
+                               (double*)b.part);
+            hipLaunchKernelGGL((reduce_partials<double>), dim3(1), dim3(kThreads), 0, stream,
+                               (const double*)b.part, (int)parts, (long long)192, (long long)192, grads);
+        }
     }
     r.ok();
     return r.err;
@@ -1078,21 +1090,33 @@ int dbh_gradients_workspace_bytes(int n_classes, int input_size, int64_t n_windo
     return DBH_OK;
 }
 
-int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes, int input_size,
-                      const float* x_dev, const int32_t* labels_dev, int64_t n_windows,
-                      float dropout_rate, uint64_t seed, double* mean_loss_dev,
-                      int64_t* n_correct_dev, float* grads_dev, float* batch_stats_dev,
-                      void* workspace_dev, dbh_stream stream) {
+int dbh_gradients_frozen_dev(const float* weights_dev, int64_t n_floats, int n_classes,
+                             int input_size, const float* x_dev, const int32_t* labels_dev,
+                             int64_t n_windows, float dropout_rate, uint64_t seed,
+                             double* mean_loss_dev, int64_t* n_correct_dev, float* grads_dev,
+                             float* batch_stats_dev, void* workspace_dev, dbh_stream stream,
+                             int frozen_blocks) {
     const int st = check_arguments(n_floats, n_classes, input_size, n_windows, dropout_rate);
     if (st != DBH_OK) return st;
+    if (!dbh_train::frozen_ok(frozen_blocks)) return DBH_ERR_INVALID_ARGUMENT;
     if (!weights_dev || !x_dev || !labels_dev || !mean_loss_dev || !n_correct_dev || !grads_dev ||
         !batch_stats_dev || !workspace_dev || ((uintptr_t)weights_dev & 15))
         return DBH_ERR_INVALID_ARGUMENT;
     DBH_HIP(dbh_train::gradients(weights_dev, n_classes, input_size, x_dev, labels_dev,
                                  n_windows, dropout_rate, seed, mean_loss_dev, n_correct_dev,
                                  grads_dev, batch_stats_dev, workspace_dev,
-                                 (hipStream_t)stream));
+                                 (hipStream_t)stream, frozen_blocks));
     return DBH_OK;
+}
+
+int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes, int input_size,
+                      const float* x_dev, const int32_t* labels_dev, int64_t n_windows,
+                      float dropout_rate, uint64_t seed, double* mean_loss_dev,
+                      int64_t* n_correct_dev, float* grads_dev, float* batch_stats_dev,
+                      void* workspace_dev, dbh_stream stream) {
+    return dbh_gradients_frozen_dev(weights_dev, n_floats, n_classes, input_size, x_dev, labels_dev,
+                                    n_windows, dropout_rate, seed, mean_loss_dev, n_correct_dev,
+                                    grads_dev, batch_stats_dev, workspace_dev, stream, 0);
 }
 
 int dbh_evaluate_dev(const float* weights_dev, int64_t n_floats, int n_classes, int input_size,
@@ -1155,12 +1179,13 @@ int dbh_evaluate(const float* weights_host, int64_t n_floats, int n_classes, int
     return DBH_OK;
 }
 
-int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
-                  const float* x_host, const int32_t* labels_host, int64_t n_windows,
-                  float dropout_rate, uint64_t seed, double* mean_loss, int64_t* n_correct,
-                  float* grads_host, float* batch_stats_host) {
+int dbh_gradients_frozen(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                         const float* x_host, const int32_t* labels_host, int64_t n_windows,
+                         float dropout_rate, uint64_t seed, double* mean_loss, int64_t* n_correct,
+                         float* grads_host, float* batch_stats_host, int frozen_blocks) {
     const int st = check_arguments(n_floats, n_classes, input_size, n_windows, dropout_rate);
     if (st != DBH_OK) return st;
+    if (!dbh_train::frozen_ok(frozen_blocks)) return DBH_ERR_INVALID_ARGUMENT;
     if (!weights_host || !x_host || !labels_host || !mean_loss || !n_correct || !grads_host ||
         !batch_stats_host)
         return DBH_ERR_INVALID_ARGUMENT;
@@ -1191,7 +1216,7 @@ int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, in
     DBH_HIP(hipMemcpyAsync(x, x_host, x_bytes, hipMemcpyHostToDevice, 0));
     DBH_HIP(hipMemcpyAsync(labels, labels_host, l_bytes, hipMemcpyHostToDevice, 0));
     DBH_HIP(dbh_train::gradients(w, n_classes, input_size, x, labels, n_windows, dropout_rate, seed,
-                                 loss, (int64_t*)(loss + 1), grads, stats, work, 0));
+                                 loss, (int64_t*)(loss + 1), grads, stats, work, 0, frozen_blocks));
     DBH_HIP(hipStreamSynchronize(0));
     // results reach the caller's buffers only once the whole call has succeeded
     struct { double loss; int64_t correct; } out;
@@ -1201,6 +1226,15 @@ int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, in
     *mean_loss = out.loss;
     *n_correct = out.correct;
     return DBH_OK;
+}
+
+int dbh_gradients(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                  const float* x_host, const int32_t* labels_host, int64_t n_windows,
+                  float dropout_rate, uint64_t seed, double* mean_loss, int64_t* n_correct,
+                  float* grads_host, float* batch_stats_host) {
+    return dbh_gradients_frozen(weights_host, n_floats, n_classes, input_size, x_host, labels_host,
+                                n_windows, dropout_rate, seed, mean_loss, n_correct, grads_host,
+                                batch_stats_host, 0);
 }
 
 }  // extern "C"

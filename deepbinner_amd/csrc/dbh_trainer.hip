@@ -4,7 +4,8 @@
 //                   draws of dbh_train.h's hash, layer number 0, one rounding to fp32
 //   update_kernel   one pass over the blob: Keras 2.1.4's Nadam (train_network.py:53-55) on the
 //                   trainable elements, BatchNormalization's moving average on the others, in fp64.
-//                   Which is which comes from dbh_network.h's table (BlobMap below).
+//                   Which is which comes from dbh_network.h's table (BlobMap below).  The elements
+//                   of frozen blocks it neither reads nor writes.
 // Every element is a function of its own index: no atomics, no reduction, nothing that depends on
 // the launch geometry.  The library is built with -ffp-contract=off, so each operation below is the
 // IEEE operation it is written as, and NumPy on the host gives the same bits
@@ -58,13 +59,18 @@ __global__ __launch_bounds__(kThreads) void noise_kernel(const float* __restrict
 // Where the batch normalisations lie in a blob of this class count: bn[j] = blob_bn(j), bn[kNumBn] =
 // the blob's end.  Layer j holds gamma, beta, moving mean, moving variance, a quarter of its floats
 // each; its batch statistics (mean then variance) start at half its distance from bn[0].
+// Frozen blocks (dbh_train.h): the convolutions' elements below frozen_floats and the whole of the
+// first frozen_bn batch normalisations are left as they are - not read, not written.
 struct BlobMap {
     int bn[kNumBn + 1];
+    int frozen_floats, frozen_bn;
 };
 
-BlobMap blob_map(int n_classes) {
+BlobMap blob_map(int n_classes, int frozen_blocks) {
     BlobMap map;
     for (int j = 0; j <= kNumBn; ++j) map.bn[j] = (int)blob_bn(j, n_classes);
+    map.frozen_floats = (int)blob_kernel(dbh_train::frozen_convs(frozen_blocks), n_classes);
+    map.frozen_bn = frozen_blocks;
     return map;
 }
 
@@ -75,15 +81,17 @@ __global__ __launch_bounds__(kThreads) void update_kernel(float* __restrict__ pa
                                                           const float* __restrict__ stats,
                                                           BlobMap map, dbh_nadam_coefficients k) {
     const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= map.bn[kNumBn]) return;
+    if (i >= map.bn[kNumBn] || i < map.frozen_floats) return;
     if (i >= map.bn[0]) {
-        int begin = map.bn[0], end = map.bn[1];
+        int begin = map.bn[0], end = map.bn[1], layer = 0;
 #pragma unroll
         for (int j = 1; j < kNumBn; ++j)
             if (i >= map.bn[j]) {
                 begin = map.bn[j];
                 end = map.bn[j + 1];
+                layer = j;
             }
+        if (layer < map.frozen_bn) return;
         const int channels = (end - begin) / 4;
         const int within = i - begin;
         if (within >= 2 * channels) {
@@ -154,9 +162,10 @@ hipError_t launch_noise(const float* x, int64_t n_windows, int input_size, float
 }
 
 hipError_t launch_update(float* params, const float* grads, float* m, float* v, const float* stats,
-                         int n_classes, const dbh_nadam_coefficients& k, hipStream_t stream) {
+                         int n_classes, const dbh_nadam_coefficients& k, int frozen_blocks,
+                         hipStream_t stream) {
     hipLaunchKernelGGL(update_kernel, dim3(blocks_for(param_count(n_classes), kThreads)), dim3(kThreads), 0,
-                       stream, params, grads, m, v, stats, blob_map(n_classes), k);
+                       stream, params, grads, m, v, stats, blob_map(n_classes, frozen_blocks), k);
     return hipGetLastError();
 }
 
@@ -171,6 +180,7 @@ struct dbh_trainer {
     int64_t n_floats = 0, max_windows = 0;
     int64_t iterations = 0;
     double m_schedule = 1.0;
+    int frozen_blocks = 0;           // an option of the run (dbh_trainer_set_frozen), not of the state
     dbh_owned::DeviceBlock block;
     float *weights = nullptr, *m = nullptr, *v = nullptr, *grads = nullptr, *stats = nullptr;
     float *x_in = nullptr, *x_noisy = nullptr;
@@ -214,8 +224,9 @@ struct dbh_trainer {
         if (e == hipSuccess)
             e = dbh_train::gradients(weights, n_classes, input_size, x_noisy, step_labels, n_windows,
                                      options.dropout_rate, step_seed, mean_loss, n_correct, grads,
-                                     stats, workspace, stream);
-        if (e == hipSuccess) e = launch_update(weights, grads, m, v, stats, n_classes, k, stream);
+                                     stats, workspace, stream, frozen_blocks);
+        if (e == hipSuccess)
+            e = launch_update(weights, grads, m, v, stats, n_classes, k, frozen_blocks, stream);
         if (e == hipSuccess) {
             iterations += 1;
             m_schedule = k.sched_new;
@@ -294,23 +305,35 @@ int dbh_train_noise(const float* x_host, int64_t n_windows, int input_size, floa
     return DBH_OK;
 }
 
-int dbh_nadam_update_dev(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev,
-                         const float* batch_stats_dev, int64_t n_floats, int n_classes,
-                         const dbh_nadam_coefficients* coefficients, dbh_stream stream) {
+int dbh_nadam_update_frozen_dev(float* params_dev, const float* grads_dev, float* m_dev,
+                                float* v_dev, const float* batch_stats_dev, int64_t n_floats,
+                                int n_classes, const dbh_nadam_coefficients* coefficients,
+                                dbh_stream stream, int frozen_blocks) {
     const int st = check_update(n_floats, n_classes, coefficients);
     if (st != DBH_OK) return st;
-    if (!params_dev || !grads_dev || !m_dev || !v_dev || !batch_stats_dev) return DBH_ERR_INVALID_ARGUMENT;
+    if (!params_dev || !grads_dev || !m_dev || !v_dev || !batch_stats_dev ||
+        !dbh_train::frozen_ok(frozen_blocks))
+        return DBH_ERR_INVALID_ARGUMENT;
     DBH_HIP(launch_update(params_dev, grads_dev, m_dev, v_dev, batch_stats_dev, n_classes,
-                          *coefficients, (hipStream_t)stream));
+                          *coefficients, frozen_blocks, (hipStream_t)stream));
     return DBH_OK;
 }
 
-int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host, float* v_host,
-                     const float* batch_stats_host, int64_t n_floats, int n_classes,
-                     const dbh_nadam_coefficients* coefficients) {
+int dbh_nadam_update_dev(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev,
+                         const float* batch_stats_dev, int64_t n_floats, int n_classes,
+                         const dbh_nadam_coefficients* coefficients, dbh_stream stream) {
+    return dbh_nadam_update_frozen_dev(params_dev, grads_dev, m_dev, v_dev, batch_stats_dev, n_floats,
+                                       n_classes, coefficients, stream, 0);
+}
+
+int dbh_nadam_update_frozen(float* params_host, const float* grads_host, float* m_host,
+                            float* v_host, const float* batch_stats_host, int64_t n_floats,
+                            int n_classes, const dbh_nadam_coefficients* coefficients,
+                            int frozen_blocks) {
     const int st = check_update(n_floats, n_classes, coefficients);
     if (st != DBH_OK) return st;
-    if (!params_host || !grads_host || !m_host || !v_host || !batch_stats_host)
+    if (!params_host || !grads_host || !m_host || !v_host || !batch_stats_host ||
+        !dbh_train::frozen_ok(frozen_blocks))
         return DBH_ERR_INVALID_ARGUMENT;
     const size_t bytes = (size_t)n_floats * sizeof(float);
     const size_t s_bytes = dbh_train::kStatsFloats * sizeof(float);
@@ -329,12 +352,19 @@ int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host,
     DBH_HIP(hipMemcpyAsync(m, m_host, bytes, hipMemcpyHostToDevice, 0));
     DBH_HIP(hipMemcpyAsync(v, v_host, bytes, hipMemcpyHostToDevice, 0));
     DBH_HIP(hipMemcpyAsync(s, batch_stats_host, s_bytes, hipMemcpyHostToDevice, 0));
-    DBH_HIP(launch_update(p, g, m, v, s, n_classes, *coefficients, 0));
+    DBH_HIP(launch_update(p, g, m, v, s, n_classes, *coefficients, frozen_blocks, 0));
     DBH_HIP(hipStreamSynchronize(0));
     DBH_HIP(hipMemcpy(params_host, p, bytes, hipMemcpyDeviceToHost));
     DBH_HIP(hipMemcpy(m_host, m, bytes, hipMemcpyDeviceToHost));
     DBH_HIP(hipMemcpy(v_host, v, bytes, hipMemcpyDeviceToHost));
     return DBH_OK;
+}
+
+int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host, float* v_host,
+                     const float* batch_stats_host, int64_t n_floats, int n_classes,
+                     const dbh_nadam_coefficients* coefficients) {
+    return dbh_nadam_update_frozen(params_host, grads_host, m_host, v_host, batch_stats_host, n_floats,
+                                   n_classes, coefficients, 0);
 }
 
 int dbh_trainer_create(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
@@ -442,6 +472,19 @@ int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float
 int dbh_trainer_iterations(dbh_trainer* trainer, int64_t* iterations) {
     if (!trainer || !iterations) return DBH_ERR_INVALID_ARGUMENT;
     *iterations = trainer->iterations;
+    return DBH_OK;
+}
+
+// (a step's launches carry the count they were queued with: no wait is needed here)
+int dbh_trainer_set_frozen(dbh_trainer* trainer, int frozen_blocks) {
+    if (!trainer || !dbh_train::frozen_ok(frozen_blocks)) return DBH_ERR_INVALID_ARGUMENT;
+    trainer->frozen_blocks = frozen_blocks;
+    return DBH_OK;
+}
+
+int dbh_trainer_get_frozen(dbh_trainer* trainer, int* frozen_blocks) {
+    if (!trainer || !frozen_blocks) return DBH_ERR_INVALID_ARGUMENT;
+    *frozen_blocks = trainer->frozen_blocks;
     return DBH_OK;
 }
 

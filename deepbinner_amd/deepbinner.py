@@ -131,6 +131,16 @@ COMMANDS = {
             [(('--model_in',), dict(type=str,
                                     help='An existing model to use as a starting point for '
                                          'training')),
+             (('--freeze',), dict(type=int, default=None, metavar='N',
+                                  help='With --model_in: keep the first N blocks (1-7) of the '
+                                       'starting model as they are and train only what is behind '
+                                       'them (a block ends at a batch normalisation; the last '
+                                       'convolution is never frozen)')),
+             (('--fresh_head',), dict(action='store_true',
+                                      help='With --model_in: draw a new last convolution for the '
+                                           'number of classes in the training data (with --seed), '
+                                           'so that a model of another barcode set can be the '
+                                           'starting point')),
              (('--epochs',), dict(type=int, default=100, help='Number of training epochs')),
              (('--aug',), dict(type=float, default=2.0,
                                help='Data augmentation factor (1 = no augmentation)')),

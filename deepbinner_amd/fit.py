@@ -13,6 +13,11 @@ doubled and a quarter dropped with chance 1 - 1/aug), not its draws.  And every 
 validation windows in file order, where the reference validates a rolling ``val_count //
 batch_size`` batches of a shuffled generator.
 
+Fine-tuning, with ``--model_in``: ``--freeze N`` leaves the first N blocks of
+the starting model as they are (``Trainer(frozen_blocks=N)``), ``--fresh_head`` re-draws conv1d_20
+for the data's class count with ``--seed`` (``ModelWeights.with_fresh_head``), which is how a model
+is reused on another barcode set.
+
 ``fit`` takes its device classes as parameters, so that the loop and the checkpoint policy also run
 against host stand-ins (tests/feed_reference.py).
 """
@@ -21,7 +26,7 @@ import sys
 
 import numpy as np
 
-from .model_format import ModelWeights
+from .model_format import ModelWeights, param_count, trainable_count
 
 
 # an evaluation runs in chunks of the trainer's max_windows; a step takes batch_size of them
@@ -52,14 +57,21 @@ def fit(args, trainer_factory=None, dataset_factory=None, epoch_order=None):
         if labels.min() < 0 or labels.max() >= class_count:
             sys.exit('Error: {} holds a barcode class outside 0-{}'.format(name, class_count - 1))
 
+    freeze = getattr(args, 'freeze', None) or 0
     if args.model_in:
         weights = load_starting_model(args.model_in)
         if weights.input_size != signal_size:
             sys.exit(MESSAGES['model size'].format(weights.input_size, signal_size))
+        if getattr(args, 'fresh_head', False):
+            weights = weights.with_fresh_head(class_count, seed=args.seed)
         if weights.n_classes != class_count:
             sys.exit(MESSAGES['model classes'].format(weights.n_classes, class_count))
+        if freeze:
+            print(MESSAGES['frozen'].format(freeze, trainable_count(class_count, freeze),
+                                            param_count(class_count)))
     else:
         weights = ModelWeights.fresh(class_count, signal_size, seed=args.seed)
+    frozen = {'frozen_blocks': freeze} if freeze else {}
 
     batch = args.batch_size
     steps = min(len(train_labels) // batch, args.batches_per_epoch)
@@ -67,7 +79,7 @@ def fit(args, trainer_factory=None, dataset_factory=None, epoch_order=None):
     best = None
     with dataset_factory(train_samples, train_labels, class_count) as train_set, \
             dataset_factory(val_samples, val_labels, class_count) as val_set, \
-            trainer_factory(weights, max_windows, seed=args.seed) as trainer:
+            trainer_factory(weights, max_windows, seed=args.seed, **frozen) as trainer:
         n_train, n_val = len(train_set), len(val_set)
         for epoch in range(args.epochs):
             indices = stream_indices(epoch_order, args.seed, n_train, epoch * steps * batch,
@@ -116,6 +128,10 @@ MESSAGES = {
                   'data\'s size ({})',
     'model classes': 'Error: the provided model\'s output classes ({}) are not equal to the '
                      'training data\'s classes ({})',
+    # this build's own
+    'frozen': 'Frozen blocks: {} of 7 - training {:,} of {:,} parameters',
+    'needs model': 'Error: --{} needs --model_in (a starting model to fine-tune)',
+    'freeze range': 'Error: --freeze must be a number of blocks from 1 to 7',
 }
 
 
@@ -134,6 +150,12 @@ def check_options(args):
     for name in ('epochs', 'batch_size', 'batches_per_epoch'):
         if getattr(args, name) < 1:
             sys.exit('Error: --{} must be a positive integer'.format(name))
+    freeze = getattr(args, 'freeze', None)
+    if freeze is not None and not 1 <= freeze <= 7:
+        sys.exit(MESSAGES['freeze range'])
+    for name in ('freeze', 'fresh_head'):
+        if getattr(args, name, None) and not args.model_in:
+            sys.exit(MESSAGES['needs model'].format(name))
 
 
 def load_starting_model(model_file):

@@ -51,7 +51,8 @@ from ._text import (TEXT_COUNT, TEXT_FORM, TEXT_OK, TEXT_RANGE, DeviceSignals, R
                     random_signals, text_format_bound, text_stage_ms, write_training_data)
 from ._training_file import (TEXT_BLOCK_BYTES, TrainingDataError, read_training_data,
                              strict_training_text, text_parse_route, training_text_blocks)
-from ._training import (BATCH_STATS_FLOATS, STEP_SEED_STRIDE, TRAINER_DEFAULTS, Dataset, Trainer,
+from ._training import (BATCH_STATS_FLOATS, MAX_FROZEN_BLOCKS, STEP_SEED_STRIDE, TRAINER_DEFAULTS,
+                        Dataset, Trainer,
                         epoch_order, evaluate, gradients_dev, gradients_workspace_bytes,
                         library_trainer_defaults, loss_and_gradients, nadam_schedule,
                         nadam_update, step_seed, train_noise, trainer_options, write_npz)

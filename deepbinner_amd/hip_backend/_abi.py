@@ -206,6 +206,10 @@ def _signatures():
                                   P(c_double), P(c_i64), f32, f32]),
         'dbh_gradients_dev': (c_int, [ptr, c_i64, c_int, c_int, ptr, ptr, c_i64, c_float, c_u64,
                                       ptr, ptr, ptr, ptr, ptr, ptr]),
+        'dbh_gradients_frozen': (c_int, [f32, c_i64, c_int, c_int, f32, i32, c_i64, c_float, c_u64,
+                                         P(c_double), P(c_i64), f32, f32, c_int]),
+        'dbh_gradients_frozen_dev': (c_int, [ptr, c_i64, c_int, c_int, ptr, ptr, c_i64, c_float,
+                                             c_u64, ptr, ptr, ptr, ptr, ptr, ptr, c_int]),
         'dbh_trainer_default_options': (c_int, [P(TrainerOptions)]),
         'dbh_nadam_schedule': (c_int, [c_i64, c_double, P(TrainerOptions), P(NadamCoefficients)]),
         'dbh_train_noise': (c_int, [f32, c_i64, c_int, c_float, c_u64, f32]),
@@ -213,6 +217,10 @@ def _signatures():
         'dbh_nadam_update': (c_int, [ptr, ptr, ptr, ptr, ptr, c_i64, c_int, P(NadamCoefficients)]),
         'dbh_nadam_update_dev': (c_int, [ptr, ptr, ptr, ptr, ptr, c_i64, c_int,
                                          P(NadamCoefficients), ptr]),
+        'dbh_nadam_update_frozen': (c_int, [ptr, ptr, ptr, ptr, ptr, c_i64, c_int,
+                                            P(NadamCoefficients), c_int]),
+        'dbh_nadam_update_frozen_dev': (c_int, [ptr, ptr, ptr, ptr, ptr, c_i64, c_int,
+                                                P(NadamCoefficients), ptr, c_int]),
         'dbh_trainer_create': (c_int, [ptr, c_i64, c_int, c_int, c_i64, P(TrainerOptions), P(ptr)]),
         'dbh_trainer_destroy': (c_int, [ptr]),
         'dbh_trainer_step': (c_int, [ptr, ptr, ptr, c_i64, P(c_double), P(c_i64)]),
@@ -221,6 +229,8 @@ def _signatures():
         'dbh_trainer_get_state': (c_int, [ptr, f32, f32, c_i64, P(c_i64), P(c_double)]),
         'dbh_trainer_set_state': (c_int, [ptr, ptr, ptr, c_i64, c_i64, c_double]),
         'dbh_trainer_iterations': (c_int, [ptr, P(c_i64)]),
+        'dbh_trainer_set_frozen': (c_int, [ptr, c_int]),
+        'dbh_trainer_get_frozen': (c_int, [ptr, P(c_int)]),
         'dbh_epoch_order': (c_int, [c_u64, c_i64, c_i64, ptr]),
         'dbh_dataset_create': (c_int, [ptr, ptr, c_i64, c_int, c_int, P(ptr)]),
         'dbh_dataset_destroy': (c_int, [ptr]),

@@ -22,23 +22,28 @@ def _windows_and_labels(x, labels, input_size):
     return x, labels
 
 
-def loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=0):
+MAX_FROZEN_BLOCKS = 7              # block j ends at batch_normalization_j; conv1d_20 is never frozen
+
+
+def loss_and_gradients(weights, x, labels, dropout_rate=0.15, seed=0, frozen_blocks=0):
     """The first half of a training step (dbh_gradients; reference train_network.py:53-55): the
     network in training mode on the windows ``x`` [N, input_size] (already normalised; the
     GaussianNoise layer is the caller's to add), the mean categorical cross-entropy against
     ``labels`` [N], and its gradient.  Returns ``(loss, n_correct, grads, batch_stats)``: ``grads``
     a flat fp32 array in the layout of ``weights.flat()`` (``ModelWeights.from_flat`` splits it;
-    the moving-statistics slots are zeros), ``batch_stats`` the 960 batch means and variances."""
+    the moving-statistics slots are zeros), ``batch_stats`` the 960 batch means and variances.
+    ``frozen_blocks`` 1..7 (dbh_gradients_frozen): the same forward pass, the gradients of the
+    tensors behind the frozen blocks with the bits they have at 0, zeros in the frozen slots."""
     lib = load_library()
     flat = weights.flat()
     x, labels = _windows_and_labels(x, labels, weights.input_size)
     grads = np.zeros(flat.size, dtype=np.float32)
     stats = np.zeros(BATCH_STATS_FLOATS, dtype=np.float32)
     loss, correct = ctypes.c_double(0), ctypes.c_int64(0)
-    check(lib.dbh_gradients(flat, flat.size, weights.n_classes, weights.input_size, x, labels,
-                            x.shape[0], float(dropout_rate), _seed64(seed),
-                            ctypes.byref(loss), ctypes.byref(correct), grads, stats),
-          'dbh_gradients')
+    check(lib.dbh_gradients_frozen(flat, flat.size, weights.n_classes, weights.input_size, x, labels,
+                                   x.shape[0], float(dropout_rate), _seed64(seed),
+                                   ctypes.byref(loss), ctypes.byref(correct), grads, stats,
+                                   int(frozen_blocks)), 'dbh_gradients_frozen')
     return loss.value, int(correct.value), grads, stats
 
 
@@ -52,13 +57,13 @@ def gradients_workspace_bytes(n_classes, input_size, n_windows):
 
 def gradients_dev(weights_ptr, n_floats, n_classes, input_size, x_ptr, labels_ptr, n_windows,
                   dropout_rate, seed, loss_ptr, correct_ptr, grads_ptr, stats_ptr, workspace_ptr,
-                  stream=None):
-    """dbh_gradients_dev on device pointers (``DeviceBuffer.ptr``); queued, not synchronised."""
-    check(load_library().dbh_gradients_dev(weights_ptr, int(n_floats), int(n_classes),
-                                           int(input_size), x_ptr, labels_ptr, int(n_windows),
-                                           float(dropout_rate), _seed64(seed), loss_ptr,
-                                           correct_ptr, grads_ptr, stats_ptr, workspace_ptr, stream),
-          'dbh_gradients_dev')
+                  stream=None, frozen_blocks=0):
+    """dbh_gradients_frozen_dev on device pointers (``DeviceBuffer.ptr``); queued, not
+    synchronised."""
+    check(load_library().dbh_gradients_frozen_dev(
+        weights_ptr, int(n_floats), int(n_classes), int(input_size), x_ptr, labels_ptr,
+        int(n_windows), float(dropout_rate), _seed64(seed), loss_ptr, correct_ptr, grads_ptr,
+        stats_ptr, workspace_ptr, stream, int(frozen_blocks)), 'dbh_gradients_frozen_dev')
 
 
 # ---- the resident trainer (include/deepbinner_hip.h, "a resident trainer"; DESIGN.md section 18) --
@@ -117,9 +122,10 @@ def train_noise(x, noise_std, seed):
     return out
 
 
-def nadam_update(params, grads, m, v, batch_stats, n_classes, coefficients):
-    """dbh_nadam_update on copies: returns the new ``(params, m, v)``; ``coefficients`` as
-    nadam_schedule() gives them."""
+def nadam_update(params, grads, m, v, batch_stats, n_classes, coefficients, frozen_blocks=0):
+    """dbh_nadam_update_frozen on copies: returns the new ``(params, m, v)``; ``coefficients`` as
+    nadam_schedule() gives them.  The elements of the first ``frozen_blocks`` blocks - weights,
+    moments, moving statistics - come back as they went in."""
     params, m, v = (np.array(a, dtype=np.float32, order='C').ravel() for a in (params, m, v))
     grads = np.ascontiguousarray(grads, dtype=np.float32).ravel()
     batch_stats = np.ascontiguousarray(batch_stats, dtype=np.float32).ravel()
@@ -127,9 +133,9 @@ def nadam_update(params, grads, m, v, batch_stats, n_classes, coefficients):
         raise ValueError('params, grads, m and v must have one size, batch_stats {} floats'
                          .format(BATCH_STATS_FLOATS))
     k = NadamCoefficients(**coefficients)
-    check(load_library().dbh_nadam_update(params.ctypes.data, grads.ctypes.data, m.ctypes.data,
-                                          v.ctypes.data, batch_stats.ctypes.data, params.size,
-                                          int(n_classes), ctypes.byref(k)), 'dbh_nadam_update')
+    check(load_library().dbh_nadam_update_frozen(
+        params.ctypes.data, grads.ctypes.data, m.ctypes.data, v.ctypes.data, batch_stats.ctypes.data,
+        params.size, int(n_classes), ctypes.byref(k), int(frozen_blocks)), 'dbh_nadam_update_frozen')
     return params, m, v
 
 
@@ -230,13 +236,17 @@ def write_npz(path, arrays):
 
 class Trainer(Owner, Scoped, Finalised):
     """A model in training, resident on one MI355X: weights, Nadam's m and v, gradients and batch
-    statistics stay on the device between steps.  ``options``: TRAINER_DEFAULTS' names."""
+    statistics stay on the device between steps.  ``options``: TRAINER_DEFAULTS' names.
+    ``frozen_blocks`` 1..7: every step leaves the first blocks' weights, moments and moving
+    statistics as they are; an option of the run, kept in no state file."""
 
     _release = 'dbh_trainer_destroy'
 
-    def __init__(self, weights, max_windows, device=None, **options):
+    def __init__(self, weights, max_windows, frozen_blocks=0, device=None, **options):
         if not isinstance(weights, ModelWeights):
             raise TypeError('weights must be a ModelWeights')
+        if not 0 <= int(frozen_blocks) <= MAX_FROZEN_BLOCKS:     # before anything is allocated
+            raise ValueError('frozen_blocks must be 0 to {}'.format(MAX_FROZEN_BLOCKS))
         self._lib = load_library()
         self._handle = None
         self.options = dict(TRAINER_DEFAULTS, **options)
@@ -252,6 +262,19 @@ class Trainer(Owner, Scoped, Finalised):
                                            self.input_size, self.max_windows, ctypes.byref(struct),
                                            ctypes.byref(handle)), 'dbh_trainer_create')
         self._handle = handle
+        if frozen_blocks:
+            self.frozen_blocks = frozen_blocks
+
+    @property
+    def frozen_blocks(self):
+        f = ctypes.c_int(0)
+        check(self._lib.dbh_trainer_get_frozen(self._handle, ctypes.byref(f)), 'dbh_trainer_get_frozen')
+        return int(f.value)
+
+    @frozen_blocks.setter
+    def frozen_blocks(self, value):
+        """Allowed between steps: the steps queued from here on use it."""
+        check(self._lib.dbh_trainer_set_frozen(self._handle, int(value)), 'dbh_trainer_set_frozen')
 
     def step(self, x, labels):
         """One training step on the windows ``x`` [N, input_size] (normalised, without noise) and
@@ -361,14 +384,16 @@ class Trainer(Owner, Scoped, Finalised):
             m_schedule=np.asarray(state['m_schedule'], dtype=np.float64), **options))
 
     @classmethod
-    def from_checkpoint(cls, path, max_windows, device=None, **options):
-        """The trainer save_checkpoint wrote, with its options unless ``options`` names others."""
+    def from_checkpoint(cls, path, max_windows, frozen_blocks=0, device=None, **options):
+        """The trainer save_checkpoint wrote, with its options unless ``options`` names others
+        (``frozen_blocks`` is not in the file: it is the caller's to give again)."""
         weights, _ = ModelWeights.load(path)
         with np.load(cls.state_path(path)) as z:
             saved = {name[len('option_'):]: (int(z[name]) if name == 'option_seed' else float(z[name]))
                      for name in z.files if name.startswith('option_')}
             state = {'m': z['m'], 'v': z['v'], 'iterations': int(z['iterations']),
                      'm_schedule': float(z['m_schedule'])}
-        trainer = cls(weights, max_windows, device=device, **dict(saved, **options))
+        trainer = cls(weights, max_windows, frozen_blocks=frozen_blocks, device=device,
+                      **dict(saved, **options))
         trainer.load_state(state)
         return trainer

@@ -70,6 +70,20 @@ def param_count(n_classes):
     return n + 4 * sum(BN_CHANNELS)
 
 
+# Blocks, for fine-tuning behind a frozen front: block j = 1..7 ends at
+# batch_normalization_j.  FROZEN_CONVS[f]: with the first f blocks frozen, conv1d_1 .. that number
+# are frozen (with batch_normalization_1 .. f); conv1d_20 never is.
+FROZEN_CONVS = (0, 1, 4, 7, 9, 16, 17, 19)
+
+
+def trainable_count(n_classes, frozen_blocks=0):
+    """Kernel, bias, gamma and beta elements that a step with ``frozen_blocks`` updates (the moving
+    statistics are in param_count() but in no count of trainable ones, as in Keras's summary)."""
+    convs = conv_shapes(n_classes)[FROZEN_CONVS[frozen_blocks]:]
+    return (sum(k * cin * cout + cout for _, k, cin, cout, _, _ in convs)
+            + 2 * sum(BN_CHANNELS[frozen_blocks:]))
+
+
 class ModelWeights:
     """Weights of one trained model in canonical order."""
 
@@ -136,6 +150,15 @@ class ModelWeights:
         bns = [(np.ones(c, dtype='<f4'), np.zeros(c, dtype='<f4'), np.zeros(c, dtype='<f4'),
                 np.ones(c, dtype='<f4')) for c in BN_CHANNELS]
         return cls(n_classes, convs, bns, input_size)
+
+    def with_fresh_head(self, n_classes, seed=0):
+        """A copy for ``n_classes`` classes: conv1d_20's kernel and bias are those of
+        ``fresh(n_classes, input_size, seed=seed)``, every other tensor is this model's, bit for
+        bit - the start of fine-tuning on another barcode set."""
+        head = ModelWeights.fresh(n_classes, self.input_size, seed=seed).convs[-1]
+        convs = [(kernel.copy(), bias.copy()) for kernel, bias in self.convs[:-1]] + [head]
+        return ModelWeights(n_classes, convs, [tuple(a.copy() for a in bn) for bn in self.bns],
+                            self.input_size)
 
     # -- .dbw container ----------------------------------------------------------------------
     def save(self, path):

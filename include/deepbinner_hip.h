@@ -1082,6 +1082,41 @@ int dbh_gradients_dev(const float* weights_dev, int64_t n_floats, int n_classes,
                       float dropout_rate, uint64_t seed, double* mean_loss_dev,
                       int64_t* n_correct_dev, float* grads_dev, float* batch_stats_dev,
                       void* workspace_dev, dbh_stream stream);
+/* FROZEN BLOCKS: fine-tuning behind a frozen front.  Block j = 1..7 is what
+ * ends at batch_normalization_j; frozen_blocks = f in 0..7 freezes blocks 1..f, and f = 0 is the
+ * two calls above, bit for bit.  The head, conv1d_20, is never frozen.
+ *   f   frozen in addition      first trainable        the backward pass ends with
+ *   1   conv1d_1, bn_1          conv1d_2               conv1d_2's weight and bias gradient (no data
+ *                                                      gradient into its input, likewise below)
+ *   2   conv1d_2..4, bn_2       conv1d_5               conv1d_5's
+ *   3   conv1d_5..7, bn_3       conv1d_8               conv1d_8's
+ *   4   conv1d_8, 9, bn_4       conv1d_10, 11, 12, 14  those four's; none of their data gradients,
+ *                                                      nothing back through the average pool
+ *   5   conv1d_10..16, bn_5     conv1d_17              conv1d_17's
+ *   6   conv1d_17, bn_6         conv1d_18              conv1d_18's
+ *   7   conv1d_18, 19, bn_7     conv1d_20              conv1d_20's; no data gradient out of the head
+ * The phase is Keras 2.1.4's for a layer with trainable = False: the layer leaves
+ * trainable_weights and its updates are empty, but in the learning phase its BatchNormalization
+ * still normalises by the BATCH's statistics and the Dropout behind it still drops.  So the forward
+ * pass is the one above, bit for bit: the same mean_loss, n_correct and all 960 batch_stats.  What
+ * changes is which gradients are formed.  Every launch that is kept is the launch of f = 0 (same
+ * geometry, same part sizes, same order), so a trainable tensor's gradient has the bits it has at
+ * f = 0; the slots of every frozen tensor (kernel, bias, gamma, beta) are written +0.0 like the
+ * moving-statistics slots, whatever grads held.  Known consequence: the frozen blocks were trained
+ * against their own moving statistics and are fine-tuned against the batch's.  This is this
+ * library's contract, stated from Keras 2.1.4's rules; it is not held to a Keras run.
+ * frozen_blocks outside 0..7: DBH_ERR_INVALID_ARGUMENT before any device work; otherwise the
+ * errors of the calls above. */
+int dbh_gradients_frozen(const float* weights_host, int64_t n_floats, int n_classes, int input_size,
+                         const float* x_host, const int32_t* labels_host, int64_t n_windows,
+                         float dropout_rate, uint64_t seed, double* mean_loss, int64_t* n_correct,
+                         float* grads_host, float* batch_stats_host, int frozen_blocks);
+int dbh_gradients_frozen_dev(const float* weights_dev, int64_t n_floats, int n_classes,
+                             int input_size, const float* x_dev, const int32_t* labels_dev,
+                             int64_t n_windows, float dropout_rate, uint64_t seed,
+                             double* mean_loss_dev, int64_t* n_correct_dev, float* grads_dev,
+                             float* batch_stats_dev, void* workspace_dev, dbh_stream stream,
+                             int frozen_blocks);
 
 /* ---- training: a resident trainer (noise, Nadam, moving statistics) ---------------------------- */
 /* The second half of the reference's training step, and a trainer that keeps a model's training
@@ -1165,6 +1200,20 @@ int dbh_nadam_update(float* params_host, const float* grads_host, float* m_host,
 int dbh_nadam_update_dev(float* params_dev, const float* grads_dev, float* m_dev, float* v_dev,
                          const float* batch_stats_dev, int64_t n_floats, int n_classes,
                          const dbh_nadam_coefficients* coefficients, dbh_stream stream);
+/* The same update with blocks 1..frozen_blocks frozen (see dbh_gradients_frozen): an element of a
+ * frozen tensor - kernel, bias, gamma, beta - and of a frozen batch normalisation's moving mean and
+ * variance is neither read nor written, p, m and v alike, so a state whose moments there are not
+ * zero leaves those weights alone too.  Every other element is dbh_nadam_update's, bit for bit;
+ * still one pass over the blob, each element decided from its own index.  frozen_blocks outside
+ * 0..7: DBH_ERR_INVALID_ARGUMENT; 0 is the call above. */
+int dbh_nadam_update_frozen(float* params_host, const float* grads_host, float* m_host,
+                            float* v_host, const float* batch_stats_host, int64_t n_floats,
+                            int n_classes, const dbh_nadam_coefficients* coefficients,
+                            int frozen_blocks);
+int dbh_nadam_update_frozen_dev(float* params_dev, const float* grads_dev, float* m_dev,
+                                float* v_dev, const float* batch_stats_dev, int64_t n_floats,
+                                int n_classes, const dbh_nadam_coefficients* coefficients,
+                                dbh_stream stream, int frozen_blocks);
 /* A trainer owns, on the current device: the weights blob, m and v (zeros), the gradient blob, the
  * batch statistics, dbh_gradients' workspace for max_windows windows, and staging for the windows
  * and labels of a batch.  options null = the defaults.  Errors, all before any device work, nothing
@@ -1196,6 +1245,15 @@ int dbh_trainer_get_state(dbh_trainer* trainer, float* m_host, float* v_host, in
 int dbh_trainer_set_state(dbh_trainer* trainer, const float* m_host, const float* v_host,
                           int64_t n_floats, int64_t iterations, double m_schedule);
 int dbh_trainer_iterations(dbh_trainer* trainer, int64_t* iterations);
+/* Frozen blocks of a trainer (0 when created): every step entry queued after the call - step,
+ * step_dev, and the data-set entries of the next section, an epoch queued whole included - uses
+ * dbh_gradients_frozen and dbh_nadam_update_frozen with this count; steps already queued keep the
+ * count they were queued with.  Allowed between steps.  dbh_trainer_evaluate_dataset (test phase)
+ * does not change.  It is an option of the run, not part of a state: dbh_trainer_get_state and
+ * dbh_trainer_set_state neither carry nor change it.  Outside 0..7 or a null pointer:
+ * DBH_ERR_INVALID_ARGUMENT, nothing changed. */
+int dbh_trainer_set_frozen(dbh_trainer* trainer, int frozen_blocks);
+int dbh_trainer_get_frozen(dbh_trainer* trainer, int* frozen_blocks);
 
 /* ---- training: device-fed batches, validation -------------------------------------------------- */
 /* The reference's data generator (train_network.py:127-193) and Keras's validation pass, without a
